@@ -109,10 +109,18 @@ def main():
                          "projected patches, chi = 128, farmed over the ranks (eight at a time per GPU), ONE all_gather_into_tensor of the "
                          "padded patch cores; strong scaling.  pi-shard: configs[2] through a native HOST callback, every candidate matrix "
                          "evaluated by column blocks over the ranks and all-gathered, rrLU replicated (SURVEY.md 8e row 2)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="headline mode: after the timed steps, write what the last timed sweep computed (rank 0's TCI2: site tensors, "
+                         "index sets, errors) as DIR/<name>.npy in float64, for an output-for-output comparison of two builds; the inputs "
+                         "are fixed (built-in function, seeded options), so the same arguments give the same inputs in every run")
     args = ap.parse_args()
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
+    if args.dump_outputs and args.mode != "headline":
+        raise SystemExit("--dump-outputs is implemented for --mode headline only")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # not started by a launcher: start the N ranks ourselves (fresh child processes, nothing has touched the GPU yet)
         # and leave with the launcher's exit code
@@ -208,7 +216,8 @@ def main():
     tci.profile_reset()
     barrier()
     t0 = time.perf_counter()
-    if world == 1 and not os.environ.get("T4A_BENCH_PER_SWEEP"):
+    one_call = world == 1 and not os.environ.get("T4A_BENCH_PER_SWEEP")
+    if one_call:
         # K full sweeps = 2K iterations of optimize_with_finder in one call: fill_site_tensors of iteration t runs on
         # its own stream and overlaps with the bond updates of iteration t+1 (they only need the index sets)
         tci.optimize(opts(2 * args.steps), final_sweep1site=False)
@@ -219,6 +228,13 @@ def main():
     dt = time.perf_counter() - t0
     prof = tci.profile()
     variants_timed = tci.profile_variants()
+    # every optimize call starts a fresh history: the last call of the timed region must have run all of its iterations
+    # (ncheck_history = 10^6 keeps the convergence check from ending it early)
+    iters = len(tci.history()[0])
+    if iters != (2 * args.steps if one_call else 2):
+        raise SystemExit(f"the timed region stopped after {iters} iterations of its last optimize call")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(tci, args.dump_outputs)
     # calibration outside the timed region: the same sweeps with HIP events around every rrLU launch (the timed region uses the
     # kernels' own start / end stamps: event records between the launches of a chain would be two more packets per bond)
     ev_ms = {}
@@ -383,6 +399,41 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(tci, out_dir):
+    """--dump-outputs: what a caller of the timed path holds after its last sweep, as float64 .npy files — the tensor train
+    (site_tensor_PP, (left link, 2, right link)), the nested index sets (i_set_PP for PP >= 1, j_set_PP for PP <= d - 2, one
+    multi-index per row), the link dimensions, the per-bond errors, the max sample value and the (rank, error) history of the
+    sweep's two iterations.  All of it fits the limit at d = 30, chi = 256 (about 17 MB), so nothing is sampled."""
+    import numpy as np
+    ranks, errors = tci.history()
+    arrays = {
+        "link_dims": tci.link_dims(),
+        "bond_errors": tci.bond_errors(),
+        "max_sample_value": [tci.max_sample_value()],
+        "history_ranks": ranks[-2:],
+        "history_errors": errors[-2:],
+    }
+    for p in range(N_SITES):
+        arrays[f"site_tensor_{p:02d}"] = tci.site_tensor(p)
+        if p > 0:               # I_0 and J_(d-1) hold only the empty multi-index: nothing to write
+            arrays[f"i_set_{p:02d}"] = tci.i_set(p)
+        if p < N_SITES - 1:
+            arrays[f"j_set_{p:02d}"] = tci.j_set(p)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    empty = [k for k, a in arrays.items() if a.size == 0]
+    if empty:
+        raise SystemExit(f"--dump-outputs: empty outputs {empty}")
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES} byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 XCD_EXCHANGE_FLOOR_US_R4 = 1.12  # what `tools/xcd_bench floor` measured on the round-4 boxes (key gather + column + two barriers)

@@ -1219,6 +1219,9 @@ void Tci2::fill_site_tensors_impl(bool async)
             if (fill_timed_) T4A_HIP(hipEventRecord(ev_fill_.a, st));
             for (auto& f : ops) f();
             ops.clear();
+            // the callback evaluations below write max|P| on the MAIN stream: the zeroing must have landed before them, or a late
+            // memset (queued behind other handles' fills, e.g. in fill_site_tensors_group) erases max|P| and the guard zeroes the core
+            T4A_HIP(hipStreamSynchronize(st));
         }
     }
 

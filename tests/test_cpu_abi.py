@@ -181,3 +181,16 @@ def test_bench_gpus_flag_is_checked_against_the_launcher():
         subprocess.call = real
     cmd = seen["cmd"]
     assert "--nproc-per-node=8" in cmd and "127.0.0.1" in cmd and cmd[cmd.index("-m") + 1] == "torch.distributed.run"
+
+
+def test_bench_refuses_zero_steps_and_dumps_outside_the_headline_mode():
+    """bench.py checks --steps and --dump-outputs before it touches a GPU: no timed region without a step, and no dump from a mode
+    that does not write one."""
+    import subprocess
+    import sys
+    for argv, msg in ((["--steps", "0"], "--steps must be >= 1"),
+                      (["--mode", "pi-shard", "--dump-outputs", os.path.join(ROOT, "no_such_dump")], "--dump-outputs")):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"] + argv, capture_output=True, text=True,
+                             timeout=120)
+        assert out.returncode != 0 and msg in (out.stderr + out.stdout)
+    assert not os.path.exists(os.path.join(ROOT, "no_such_dump"))

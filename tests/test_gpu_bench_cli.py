@@ -82,3 +82,27 @@ def test_bench_pi_shard_mode_single_gpu():
     # (callback_ms is an ESTIMATE: points x the per-point cost calibrated on a probe batch; it is most of the step, and noise of the probe
     # may push it a few per cent past the measured wall time)
     assert 0.5 * line["ms_per_step"] < line["callback_ms_per_step"][0] < 1.25 * line["ms_per_step"]
+
+
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs DIR: the tensor train, index sets and errors of the last timed sweep as float64 .npy files (64 MB at most), and
+    --steps is the number of timed sweeps."""
+    import numpy as np
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "0",
+                          "--no-cpu-baseline", "--no-aux", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    line = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line["steps"] == 2
+    arrays = {f[:-4]: np.load(os.path.join(str(tmp_path), f)) for f in os.listdir(str(tmp_path)) if f.endswith(".npy")}
+    assert all(a.dtype == np.float64 and a.size > 0 for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    n = line["config"]["n_sites"]
+    assert len(arrays) == 5 + n + 2 * (n - 1) and "i_set_00" not in arrays and f"j_set_{n - 1:02d}" not in arrays
+    links = [1] + [int(x) for x in arrays["link_dims"]] + [1]
+    assert len(links) == n + 1 and max(links) == 256
+    for p in range(n):
+        assert arrays[f"site_tensor_{p:02d}"].shape == (links[p], 2, links[p + 1])
+        assert p == 0 or arrays[f"i_set_{p:02d}"].shape == (links[p], p)
+        assert p == n - 1 or arrays[f"j_set_{p:02d}"].shape == (links[p + 1], n - 1 - p)
+        assert np.isfinite(arrays[f"site_tensor_{p:02d}"]).all()
+    assert arrays["history_ranks"].tolist() == [256.0, 256.0] and np.isfinite(arrays["history_errors"]).all()
