@@ -1259,11 +1259,12 @@ void Engine::svd_plain(const double* d_a, int M, int N, double* d_u, double* d_s
     // 64 x 64 against 3.7: profiles/r04_linalg_probe.txt).  T4A_SVD_SMALL_N moves the boundary, T4A_SVD_NO_BLOCK=1 restores the
     // round-3 behaviour (one launch up to 128 columns, launch-per-round beyond).
     static const int small_n = diag_env("T4A_SVD_SMALL_N") ? std::atoi(diag_env("T4A_SVD_SMALL_N")) : 16;
+    const bool small = !groups && jacobi_fits_small(m, n) && (no_block || n <= small_n);
     if (groups) {
         if (!jacobi_groups_launch(W, m, V, n, max_sweeps, flags + 2, stream_))
             throw Error(T4A_GPU_INTERNAL_ERROR, "svd: jacobi_fits_groups and jacobi_groups_launch disagree");
-    } else if (jacobi_fits_small(m, n) && (no_block || n <= small_n)) {
-        jacobi_small_launch(W, m, V, n, max_sweeps, stream_);
+    } else if (small) {
+        jacobi_small_launch(W, m, V, n, max_sweeps, flags + 3, stream_);
     } else {
         // sweeps in batches of two: the kernels of a sweep behind a converged one return at once (flags[3], jacobi_sweep_end_kernel), the
         // host reads the flags once per batch (a copy and a stream synchronisation per sweep were ~0.5 ms of a 512 x 256 decomposition)
@@ -1284,6 +1285,8 @@ void Engine::svd_plain(const double* d_a, int M, int N, double* d_u, double* d_s
                 break;
             }
         }
+        static const bool dbg = std::getenv("T4A_SVD_DEBUG") != nullptr;
+        if (dbg && !h[3]) std::fprintf(stderr, "[t4a svd] %d x %d: did not converge within %d sweeps\n", m, n, max_sweeps);
     }
     // the taller factor (m x n) and the square one (n x n): write straight to the outputs where no transpose is needed
     double* Ubig = flip ? d_su_.get() : d_u;   // m x n
@@ -1296,9 +1299,10 @@ void Engine::svd_plain(const double* d_a, int M, int N, double* d_u, double* d_s
     if (h[2]) throw Error(T4A_GPU_INVALID_ARGUMENT, "SVD computation failed: non-finite input");
     // (the one-launch kernel iterated on 2^-e A and left W that way: U = W / sigma does not see the factor, the singular values do)
     if (groups && h5[4] != 0) scale_pow2_launch(d_s, d_s, (size_t)n, h5[4], stream_);
-    if (groups) {
+    if (groups || small) { // (the one-launch kernels leave the sweep count in flags[3], 0 when max_sweeps ran out)
         static const bool dbg = std::getenv("T4A_SVD_DEBUG") != nullptr;
-        if (dbg) std::fprintf(stderr, "[t4a svd] %d x %d: one launch, converged within %d sweeps\n", m, n, h[3]);
+        if (dbg && h[3]) std::fprintf(stderr, "[t4a svd] %d x %d: one launch, converged within %d sweeps\n", m, n, h[3]);
+        if (dbg && !h[3]) std::fprintf(stderr, "[t4a svd] %d x %d: one launch, did not converge within %d sweeps\n", m, n, max_sweeps);
     }
     if (h[1] > 0) svd_complete_launch(Ubig, m, n, flags + 8, d_ssig_.get() + n, stream_);
     if (flip)

@@ -590,8 +590,8 @@ __host__ __device__ inline int pow2_scale_exponent(double amax) { return (amax >
 // dst = src * 2^(sign * e) with e = pow2_scale_exponent of the magnitude nonfinite_absmax_launch left in *d_absmax_bits (device side)
 void scale_pow2_dev_launch(double* dst, const double* src, size_t count, const unsigned long long* d_absmax_bits, int sign, hipStream_t stream);
 bool jacobi_fits_small(int m, int n);
-// all sweeps inside one workgroup (m >= n, n <= 128)
-void jacobi_small_launch(double* W, int m, double* V, int n, int max_sweeps, hipStream_t stream);
+// all sweeps inside one workgroup (m >= n, n <= 128); *d_sweeps receives the number of sweeps (left alone when max_sweeps ran out)
+void jacobi_small_launch(double* W, int m, double* V, int n, int max_sweeps, int* d_sweeps, hipStream_t stream);
 // all sweeps inside one workgroup, a group of 8 or 16 lanes per column pair, W and V in the LDS (m >= n, n <= 96; see jg_plan);
 // V is an output only, d_nonfinite[0] is set for an Inf / NaN input, d_nonfinite[1] receives the sweep count, d_nonfinite[2] the exponent e
 // when the kernel iterated on (and returns) 2^-e W

@@ -83,15 +83,26 @@ struct Rot {
 // A pair rotates when the cosine of the angle between its columns exceeds tol = sqrt(m) * eps — the stopping rule of LAPACK's one-sided
 // Jacobi (dgesvj: "TOL = SQRT(M) * EPS").  Round 5: with tol = eps the last two sweeps of every decomposition found 1 - 200 of the 32 640
 // pairs of a 256-column matrix to rotate (angles of a few eps); singular values and vectors agree to the same 1e-14 either way.
+// The scale of the pair test, sqrt(alpha beta).  Where the product of the two squared norms leaves the normal range (columns of norm
+// below ~1e-77 inside a matrix that is not rescaled: alpha * beta underflowed to 0 and EVERY pair with a nonzero gamma passed the test,
+// so the iteration never converged) the product of the two square roots; in the normal range the same expression as before, bit for bit.
+__device__ inline double pair_scale(double alpha, double beta)
+{
+    const double ab = alpha * beta;
+    if (ab >= 2.2250738585072014e-308 && ab <= 1.79769313486231570e308) return sqrt(ab);
+    return sqrt(alpha) * sqrt(beta);
+}
 __device__ inline Rot jacobi_rotation(double alpha, double beta, double gamma, double tol)
 {
     Rot r;
     r.c = 1.0;
     r.s = 0.0;
     r.apply = 0;
-    if (gamma == 0.0 || !(fabs(gamma) > tol * sqrt(alpha * beta))) return r;
+    if (gamma == 0.0 || !(fabs(gamma) > tol * pair_scale(alpha, beta))) return r;
     const double zeta = (beta - alpha) / (2.0 * gamma);
     const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+    // |zeta| > 1e154: zeta * zeta overflows and t = 0 — the identity, which must not count as a rotation (the sweep would never converge)
+    if (t == 0.0) return r;
     // c = (1 + t^2)^(-1/2), |t| <= 1: the hardware estimate and two Newton steps (y <- y (3 - x y^2) / 2) instead of a square root and a
     // division in the longest dependent chain of a local round
     const double x = 1.0 + t * t;
@@ -146,7 +157,7 @@ __global__ void __launch_bounds__(256) jacobi_round_kernel(double* W, int m, dou
 // Whole Jacobi iteration inside one workgroup (small problems): one wave per pair, all sweeps in-kernel,
 // W and V staged through LDS when they fit.
 __global__ void __launch_bounds__(1024) jacobi_small_kernel(double* Wg, int m, double* Vg, int n, int np,
-                                                            int max_sweeps, int use_lds)
+                                                            int max_sweeps, int use_lds, int* sweeps)
 {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     __shared__ int s_rot;
@@ -201,7 +212,10 @@ __global__ void __launch_bounds__(1024) jacobi_small_kernel(double* Wg, int m, d
         }
         const int any = s_rot;
         __syncthreads();
-        if (!any) break;
+        if (!any) {
+            if (tid == 0) *sweeps = sweep + 1; // (stays 0 when max_sweeps ran out: T4A_SVD_DEBUG)
+            break;
+        }
     }
     if (use_lds) {
         for (int e = tid; e < m * n; e += T) Wg[e] = W[e];
@@ -224,7 +238,7 @@ template <int G> __device__ inline double group_sum(double v)
 // steps (the rotation arithmetic is the longest dependent chain of a round of jacobi_groups_kernel).  The ANGLE (zeta, t) is computed to
 // ~2^-46: an error there leaves a residual inner product of that relative size, which the next sweep removes; the COSINE keeps both
 // Newton steps (c^2 + s^2 = 1 to rounding: every rotation stays orthogonal).  Out-of-range intermediates (|zeta| > 1e154, subnormal
-// gamma) surface as a NaN and mean "no rotation", as the threshold test does for an overflowing alpha * beta.
+// gamma) surface as a NaN and hand the pair to the exact jacobi_rotation.
 __device__ inline Rot jacobi_rotation_fast(double alpha, double beta, double gamma, double tol)
 {
     Rot r;
@@ -233,7 +247,8 @@ __device__ inline Rot jacobi_rotation_fast(double alpha, double beta, double gam
     r.apply = 0;
     if (gamma == 0.0) return r;
     const double ab = alpha * beta;
-    const double sq = ab == 0.0 ? 0.0 : ab * __builtin_amdgcn_rsq(ab); // sqrt(alpha beta) to 2^-23: a threshold
+    // sqrt(alpha beta) to 2^-23: a threshold (outside the normal range of alpha * beta the exact scale: pair_scale)
+    const double sq = (ab >= 2.2250738585072014e-308 && ab <= 1.79769313486231570e308) ? ab * __builtin_amdgcn_rsq(ab) : pair_scale(alpha, beta);
     if (!(fabs(gamma) > tol * sq)) return r;
     const double den = 2.0 * gamma;
     double rd = __builtin_amdgcn_rcp(den);
@@ -251,7 +266,9 @@ __device__ inline Rot jacobi_rotation_fast(double alpha, double beta, double gam
     c = c * (1.5 - 0.5 * x2 * c * c);
     c = c * (1.5 - 0.5 * x2 * c * c);
     const double sn = c * t;
-    if (!(c == c) || !(sn == sn)) return r;
+    // a pair that passed the test but whose estimates left the range (a subnormal gamma: rcp(2 gamma) overflows; |zeta| > 1e154): the
+    // exact rotation, with IEEE division and square roots (skipping it left live columns of norm ~1e-150 un-orthogonalised, silently)
+    if (!(c == c) || !(sn == sn)) return jacobi_rotation(alpha, beta, gamma, tol);
     r.c = c;
     r.s = sn;
     r.apply = 1;
@@ -1197,7 +1214,7 @@ void scale_pow2_dev_launch(double* dst, const double* src, size_t count, const u
 
 bool jacobi_fits_small(int m, int n) { return n <= 128 && m <= 2048; }
 
-void jacobi_small_launch(double* W, int m, double* V, int n, int max_sweeps, hipStream_t stream)
+void jacobi_small_launch(double* W, int m, double* V, int n, int max_sweeps, int* d_sweeps, hipStream_t stream)
 {
     static std::atomic<bool> attr_set{false}; // (launches come from several host threads; setting the attribute twice is harmless)
     if (!attr_set) {
@@ -1211,7 +1228,7 @@ void jacobi_small_launch(double* W, int m, double* V, int n, int max_sweeps, hip
     int T = 64 * (np / 2 > 0 ? np / 2 : 1);
     if (T > 1024) T = 1024;
     hipLaunchKernelGGL(jacobi_small_kernel, dim3(1), dim3(T), use_lds ? bytes : 0, stream, W, m, V, n, np, max_sweeps,
-                       use_lds);
+                       use_lds, d_sweeps);
 }
 
 // One workgroup, sixteen lanes per column pair (jacobi_groups_kernel): W (m x n, m >= n) and V together in the LDS.
