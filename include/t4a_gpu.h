@@ -58,9 +58,7 @@ t4a_gpu_status t4a_gpu_device_count(int32_t* out_count);
 t4a_gpu_status t4a_gpu_set_device(int32_t device);
 /* Library version string. */
 const char* t4a_gpu_version(void);
-/* 1: the library was built with -DT4A_DIAG_SWITCHES (experiment switches of tools/ are read from the environment), 0: a production
- * build — every T4A_* experiment variable is a no-op there (a known one found in the environment is reported on stderr once).  The A/B
- * launchers under tools/ call this and refuse to label a run as a variant on a production build. */
+/* Always 0: the library has no experiment switches.  Kept so that existing binders keep linking. */
 int32_t t4a_gpu_diag_switches_enabled(void);
 
 /* The random stream of the reference's seeded searches: `rand 0.9` `StdRng::seed_from_u64(seed)` followed by

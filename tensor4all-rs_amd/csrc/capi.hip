@@ -326,22 +326,7 @@ t4a_gpu_status t4a_gpu_set_device(int32_t device)
 }
 
 const char* t4a_gpu_version(void) { return "t4a-mi355x 0.1.0 (gfx950)"; }
-int32_t t4a_gpu_diag_switches_enabled(void)
-{
-    if (!t4a::kDiagSwitches) {
-        // a known experiment switch in the environment of a production build measures the default path: say so once
-        static const char* const known[] = {"T4A_NO_FUSED_PI", "T4A_NO_SMALL_FILL", "T4A_EXPORT_SYNC", "T4A_FILL_GRAPH_SHARED", "T4A_SVD_NO_PRECOND",
-                                            "T4A_FILL_DEFER", "T4A_OLD_PRESIZE", "T4A_FILL_GRAPH_NO_COPY"};
-        static bool warned = false;
-        if (!warned)
-            for (const char* k : known)
-                if (std::getenv(k)) {
-                    std::fprintf(stderr, "[t4a] %s is set, but this library was built without -DT4A_DIAG_SWITCHES: the switch has NO effect\n", k);
-                    warned = true;
-                }
-    }
-    return t4a::kDiagSwitches ? 1 : 0;
-}
+int32_t t4a_gpu_diag_switches_enabled(void) { return 0; }
 
 // ------------------------------------------------------------------------------------------------ dense
 t4a_gpu_status t4a_gpu_rrlu_f64(double* a_inout, size_t m, size_t n, size_t max_bond_dim, double rel_tol,

@@ -13,7 +13,6 @@
 #include <vector>
 
 #include "../../include/t4a_gpu.h"
-#include "diag.hpp"
 
 namespace t4a {
 

@@ -376,8 +376,7 @@ LuciResult Engine::luci(const double* d_a, int M, int N, const RrLUOptions& opts
         a.pivot_vals = d_pivvals;
         a.keys = d_xkeys_.get();
         a.salt = xcd_salt_;
-        static const double xspec = diag_env("T4A_XCD_SPECFRAC") ? std::atof(diag_env("T4A_XCD_SPECFRAC")) : 0.8;
-        a.spec_frac = xspec;
+        a.spec_frac = 0.8;
         a.stamps = want_stamps ? d_stamps_.get() : nullptr;
         std::memset(h_out_.get(), 0, 32);
         a.h_block = reinterpret_cast<unsigned long long*>(h_out_.get());
@@ -452,19 +451,13 @@ LuciResult Engine::luci(const double* d_a, int M, int N, const RrLUOptions& opts
         a.keys_next = keys_next;
         a.keys_next_u64 = keys_ready ? keys_half : 0;
         a.salt = rrlu_salt_;
-        static const int col_delay = diag_env("T4A_RRLU_COLDELAY") ? std::atoi(diag_env("T4A_RRLU_COLDELAY")) : 0;
-        a.col_delay = col_delay;
-        // measured optimum of the poller's initial sleep (tools/probe_delay.py): 12 units below ~100 workgroups, 14 above
-        static const int poll_delay_env = diag_env("T4A_RRLU_POLLDELAY") ? std::atoi(diag_env("T4A_RRLU_POLLDELAY")) : -1;
-        a.poll_delay = poll_delay_env >= 0 ? poll_delay_env : (rplan.W > 100 ? 14 : 12);
-        static const int ncopy_env = diag_env("T4A_RRLU_NCOPY") ? std::atoi(diag_env("T4A_RRLU_NCOPY")) : 1;
-        a.ncopy = ncopy_env < 1 ? 1 : (ncopy_env > RRLU_MAX_COPIES ? RRLU_MAX_COPIES : ncopy_env);
-        static const int spec_env = diag_env("T4A_RRLU_SPEC") ? std::atoi(diag_env("T4A_RRLU_SPEC")) : 2;
-        a.spec = spec_env < 0 ? 0 : (spec_env > 2 ? 2 : spec_env);
-        static const double spec_frac_env = diag_env("T4A_RRLU_SPECFRAC") ? std::atof(diag_env("T4A_RRLU_SPECFRAC")) : 0.8;
-        a.spec_frac = spec_frac_env;
-        static const int key16_env = diag_env("T4A_RRLU_KEY16") ? std::atoi(diag_env("T4A_RRLU_KEY16")) : 1;
-        a.key16 = key16_env; // bit 0: 16-byte key loads, bit 1: 16-byte key store
+        a.col_delay = 0;
+        // measured optimum of the poller's initial sleep: 12 units below ~100 workgroups, 14 above
+        a.poll_delay = rplan.W > 100 ? 14 : 12;
+        a.ncopy = 1;
+        a.spec = 2;
+        a.spec_frac = 0.8;
+        a.key16 = 1; // bit 0: 16-byte key loads, bit 1: 16-byte key store
         a.spin_limit = 1u << 20;
         a.stamps = want_stamps ? d_stamps_.get() : nullptr;
         // results land in the pinned mirror straight from the kernel: no device-to-host copy afterwards
@@ -487,8 +480,7 @@ LuciResult Engine::luci(const double* d_a, int M, int N, const RrLUOptions& opts
         a.dev_token = 0u;
         a.rowmap = nullptr;
         a.ts_u64 = 0;
-        static const bool no_token_spin = diag_env("T4A_NO_TOKEN_SPIN") != nullptr;
-        if (rplan.W == 1 && !prof.enabled && !no_token_spin) {
+        if (rplan.W == 1 && !prof.enabled) {
             if (++done_token_ == 0u) ++done_token_;
             a.done_token = done_token_;
             spin_token = done_token_;
@@ -767,7 +759,6 @@ bool Engine::chain_plan(int kM, int kN, ChainRrluPlan* out) const
     ChainRrluPlan pl;
     pl.kM = kM;
     pl.kN = kN;
-    static const bool no_single = diag_env("T4A_CHAIN_NO_SINGLE") != nullptr;
     // tiny matrices keep the fused single-workgroup plan (the candidate matrix is built in the registers: no extra launch);
     // everything else that fits one workgroup takes the LDS-exchange kernel, with 63 more workgroups for the speculative
     // candidate matrix of the next bond
@@ -778,7 +769,7 @@ bool Engine::chain_plan(int kM, int kN, ChainRrluPlan* out) const
         *out = pl;
         return true;
     }
-    if (!no_single && (long long)kM * kN <= 64 * 64 && rrlu_reg_make_plan(kM, kN, num_cus_, &pl.reg) && pl.reg.W == 1) {
+    if ((long long)kM * kN <= 64 * 64 && rrlu_reg_make_plan(kM, kN, num_cus_, &pl.reg) && pl.reg.W == 1) {
         pl.kind = 1;
         pl.fused = pl.reg.RPT * pl.reg.CPT <= RRLU_FUSED_MAX_VALUES;
         pl.code = pl.reg.RPT * 1000 + pl.reg.CPT * 10 + 2 + ((pl.reg.TR % 64) == 0 ? 1 : 0); // (+4 for the row-major tie order: chain_rrlu)
@@ -883,8 +874,7 @@ unsigned Engine::chain_group_args(const ChainRrluPlan& pl, bool left, const doub
     a.pivot_vals = d_pivvals;
     a.keys = d_xkeys_.get();
     a.salt = xcd_salt_;
-    static const double xspec = diag_env("T4A_XCD_SPECFRAC") ? std::atof(diag_env("T4A_XCD_SPECFRAC")) : 0.8;
-    a.spec_frac = xspec;
+    a.spec_frac = 0.8;
     a.stamps = nullptr;
     a.h_block = reinterpret_cast<unsigned long long*>(blk.host);
     a.block_u64 = (int)(blk.bytes / 8);
@@ -972,8 +962,7 @@ void Engine::build_factors_from(const double* lu, const int* d_rowperm_ptr_, con
     d_left_.reserve((size_t)M * (rk > 0 ? rk : 1));
     d_right_.reserve((size_t)N * (rk > 0 ? rk : 1));
     if (rk == 0) return;
-    static const bool no_small = diag_env("T4A_NO_SMALL_FACTORS") != nullptr;
-    if (!no_small && luci_factors_small_launch(lu, M, N, rk, d_rowperm_ptr_, d_colperm_ptr_, left_orth, d_left_.get(), d_right_.get(), stream_)) {
+    if (luci_factors_small_launch(lu, M, N, rk, d_rowperm_ptr_, d_colperm_ptr_, left_orth, d_left_.get(), d_right_.get(), stream_)) {
         T4A_HIP(hipGetLastError());
         return;
     }
@@ -1123,13 +1112,12 @@ void Engine::lu_permuted_factors(const LuciResult& r, bool left_orth)
 // unfoldings of a tensor train under compression look like (Drmac / Veselic; measured with the cyclic ordering used here on 256 x 128:
 // sigma_i = 2^-i 29 sweeps -> 12, a rank-40 matrix with 10 decades 28 -> 13, Gaussian 11 -> 11) — and every sweep works on n x n
 // instead of m x n.  (Round 4 had tried the iteration on R itself: no gain — it is the TRANSPOSE that helps.)  Costs one Householder QR
-// and one GEMM.  T4A_SVD_NO_PRECOND=1 (diagnostic builds) restores the plain iteration.
+// and one GEMM.
 void Engine::svd(const double* d_a, int M, int N, double* d_u, double* d_s, double* d_vt)
 {
     if (M <= 0 || N <= 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "svd: empty matrix");
     const int kmin = M < N ? M : N, kmax = M < N ? N : M;
-    static const bool no_groups = diag_env("T4A_SVD_NO_GROUPS") != nullptr;
-    if (!no_groups && jacobi_fits_groups(kmax, kmin)) { // one launch: the kernel checks and scales its input itself (svd_plain)
+    if (jacobi_fits_groups(kmax, kmin)) { // one launch: the kernel checks and scales its input itself (svd_plain)
         svd_plain(d_a, M, N, d_u, d_s, d_vt);
         return;
     }
@@ -1167,9 +1155,8 @@ void Engine::svd(const double* d_a, int M, int N, double* d_u, double* d_s, doub
 
 void Engine::svd_in_range(const double* d_a, int M, int N, double* d_u, double* d_s, double* d_vt)
 {
-    static const bool no_precond = diag_env("T4A_SVD_NO_PRECOND") != nullptr;
     const int kmin = M < N ? M : N;
-    if (no_precond || kmin < 64) {
+    if (kmin < 64) {
         svd_plain(d_a, M, N, d_u, d_s, d_vt);
         return;
     }
@@ -1237,9 +1224,8 @@ void Engine::svd_plain(const double* d_a, int M, int N, double* d_u, double* d_s
     // W and V of up to 96 columns fit one workgroup's LDS together: the whole iteration in ONE launch, sixteen lanes per column pair
     // (jacobi_groups_kernel; a 64 x 64 call 0.65 ms, of which the kernel 0.54, against 1.39 ms through QR + blocked tournament, 1.17 ms
     // for the blocked tournament alone and 2.23 ms for jacobi_small_kernel — profiles/r06_svd_small.txt; the kernel checks the input for
-    // Inf / NaN itself and starts V from the identity).  T4A_SVD_NO_GROUPS=1 restores the round-5 routes.
-    static const bool no_groups = diag_env("T4A_SVD_NO_GROUPS") != nullptr;
-    const bool groups = !no_groups && jacobi_fits_groups(m, n);
+    // Inf / NaN itself and starts V from the identity).
+    const bool groups = jacobi_fits_groups(m, n);
     if (!groups) nonfinite_flag_launch(d_a, (size_t)M * N, flags + 2, stream_);
     double* W = d_sw_.get();
     if (flip)
@@ -1253,13 +1239,10 @@ void Engine::svd_plain(const double* d_a, int M, int N, double* d_u, double* d_s
     }
     const int max_sweeps = 60;
     int h[4] = {0, 0, 0, 0};
-    static const bool no_block = diag_env("T4A_SVD_NO_BLOCK") != nullptr;
     // tiny matrices (n <= 16: the cores of a small train, 2 x 2 rotations in the tests): the whole iteration in ONE launch of one
     // workgroup, no host round trip per sweep; everything else the blocked tournament (12.8 ms at 512 x 256 against 16.6, 2.3 ms at
-    // 64 x 64 against 3.7: profiles/r04_linalg_probe.txt).  T4A_SVD_SMALL_N moves the boundary, T4A_SVD_NO_BLOCK=1 restores the
-    // round-3 behaviour (one launch up to 128 columns, launch-per-round beyond).
-    static const int small_n = diag_env("T4A_SVD_SMALL_N") ? std::atoi(diag_env("T4A_SVD_SMALL_N")) : 16;
-    const bool small = !groups && jacobi_fits_small(m, n) && (no_block || n <= small_n);
+    // 64 x 64 against 3.7: profiles/r04_linalg_probe.txt).
+    const bool small = !groups && jacobi_fits_small(m, n) && n <= 16;
     if (groups) {
         if (!jacobi_groups_launch(W, m, V, n, max_sweeps, flags + 2, stream_))
             throw Error(T4A_GPU_INTERNAL_ERROR, "svd: jacobi_fits_groups and jacobi_groups_launch disagree");
@@ -1273,7 +1256,7 @@ void Engine::svd_plain(const double* d_a, int M, int N, double* d_u, double* d_s
             for (int k = 0; k < batch; ++k) {
                 // blocked iteration (a tournament over column blocks, the pairs of a block pair inside one workgroup's LDS);
                 // columns too long for the LDS keep the launch-per-round form
-                if (no_block || !jacobi_block_sweep_launch(W, m, V, n, flags, stream_)) jacobi_sweep_launch(W, m, V, n, flags, stream_);
+                if (!jacobi_block_sweep_launch(W, m, V, n, flags, stream_)) jacobi_sweep_launch(W, m, V, n, flags, stream_);
                 jacobi_sweep_end_launch(flags, stream_);
             }
             T4A_HIP(hipMemcpyAsync(h, flags, sizeof(int) * 4, hipMemcpyDeviceToHost, stream_));

@@ -9,7 +9,6 @@
 #include <cstdint>
 
 #include "../../include/t4a_testfunctions.h"
-#include "diag.hpp"
 
 namespace t4a {
 
@@ -363,13 +362,11 @@ struct ChainWalkArgs {
     size_t factors_stride;
     unsigned token_base;                // bond number k of the half-sweep completes with token token_base + k
     int timed;                          // device time stamps of every factorisation at off_ts
-    int lean_prep;                      // 1: the preparation of a bond by one wave out of the LDS (walk_prep_wave0); 0: chain_prep_body (T4A_WALK_OLD_PREP=1)
+    int lean_prep;                      // 1: the preparation of a bond by one wave out of the LDS (walk_prep_wave0); 0: chain_prep_body
     unsigned long long* phase_ticks;    // diagnostic (T4A_WALK_DEBUG): [8] 100 MHz ticks summed over the bonds: preparation, candidate matrix, rrLU, total; [4] gather [5] dependent list (inside the preparation)
 };
 void chain_walk_launch(const ChainCommon& c, const FnDevice& fn, const ChainWalkArgs& w, int columns, hipStream_t stream);
 void chain_indep_launch(const ChainCommon& c, int n_bonds, hipStream_t stream);
-// behind a chain whose preparations ran with defer_host_writes: tables -> pinned mirrors, dims -> hdims, in one launch
-void chain_mirror_launch(const ChainCommon& c, int n_bonds, hipStream_t stream);
 // forward 1-site sweep with update_tensors: the LAST site's tensor Pi1 = f(kron(I_{n-1}, d_{n-1}), J_{n-1}) (tensorci2.rs:902-912, fill_tensor
 // :813-850), evaluated from the device tables right behind the chain — core[l + L (s + S r)], L = |I_{n-1}| as the chain left it
 void chain_last_core_launch(const ChainCommon& c, const FnDevice& fn, double* core, int max_entries, hipStream_t stream);

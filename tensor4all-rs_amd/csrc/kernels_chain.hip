@@ -444,7 +444,6 @@ __device__ __forceinline__ void chain_mirror_body(const ChainCommon& c, int nb)
         for (int e = gtid; e < nb * 4; e += gsz)
             if ((e & 3) != 3) c.hdims[e] = __hip_atomic_load(c.dims + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-__global__ void __launch_bounds__(1024) chain_mirror_kernel(ChainCommon c, int nb) { chain_mirror_body(c, nb); }
 
 // the last site's tensor of a forward 1-site sweep, straight from the tables (see kernels.hpp): value = f(acc(I_{n-1}[l]) + w[s] + acc(J_{n-1}[r])),
 // the accumulator sums of pi_eval_kernel over the rows kron(I_{n-1}, d_{n-1}) (parent outer, digit inner) and the columns J_{n-1}
@@ -891,11 +890,6 @@ void chain_last_core_launch(const ChainCommon& c, const FnDevice& fn, double* co
 {
     const int blocks = max_entries > 256 * 64 ? 64 : (max_entries + 255) / 256;
     hipLaunchKernelGGL(chain_last_core_kernel, dim3(blocks > 0 ? blocks : 1), dim3(256), 0, stream, c, fn, core, max_entries);
-}
-
-void chain_mirror_launch(const ChainCommon& c, int n_bonds, hipStream_t stream)
-{
-    hipLaunchKernelGGL(chain_mirror_kernel, dim3(8), dim3(1024), 0, stream, c, n_bonds);
 }
 
 } // namespace t4a

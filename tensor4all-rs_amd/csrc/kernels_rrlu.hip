@@ -515,18 +515,10 @@ __global__ void __launch_bounds__(1024) rrlu_kernel(RrluArgs p)
 RrluPlan rrlu_make_plan(int M, int N, int num_cus)
 {
     RrluPlan plan;
-    const char* ew = diag_env("T4A_RRLU_W");
-    const char* et = diag_env("T4A_RRLU_T");
     int T = 256;
-    if (et) T = std::atoi(et);
-    if (T < 64) T = 64;
-    if (T > 1024) T = 1024;
-    T = (T / 64) * 64;
     const size_t elems = (size_t)M * (size_t)N;
     int W;
-    if (ew) {
-        W = std::atoi(ew);
-    } else if (elems <= 96 * 96) {
+    if (elems <= 96 * 96) {
         W = 1;
     } else {
         // aim at ~6 columns (<= ~36 KiB) per workgroup; the exchange cost grows slowly with W while the
@@ -549,7 +541,7 @@ RrluPlan rrlu_make_plan(int M, int N, int num_cus)
         if (W > N) W = N;
     }
     if (plan.W > 1 && plan.lds_bytes < 84 * 1024) plan.lds_bytes = 84 * 1024; // one workgroup per CU
-    if (plan.W == 1 && !et) {
+    if (plan.W == 1) {
         // single workgroup: use more threads for bigger slabs
         T = elems >= 4096 ? 1024 : (elems >= 1024 ? 512 : 256);
     }

@@ -34,8 +34,7 @@
 // Barriers per pivot step: 3.
 // Thresholded speculative publication of the pivot column is compiled in (measured on MI355X: 42.1 -> 40.8 ms of rrLU per
 // sweep at d = 30, chi = 256; selecting the mode through RrluRegArgs::spec at run time costs the default path 2 ms of
-// code-generation noise, so it is a build-time choice).  Remove the define to get the run-time switch back.
-#define T4A_RRLU_SPEC2 1
+// code-generation noise, so it is a build-time choice: RrluRegArgs::spec is not read).
 #include "kernels.hpp"
 
 #include <mutex>
@@ -49,10 +48,6 @@ namespace {
 
 constexpr unsigned NOPOS = 0xFFFFFFFFu;
 
-__device__ __forceinline__ void st_u64_sc1(unsigned long long* p, unsigned long long v)
-{
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 __device__ __forceinline__ unsigned long long ld_u64_sc1(const unsigned long long* p)
 {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -67,20 +62,15 @@ __device__ __forceinline__ void st_b128_sc1(void* p, u32x4 v)
     asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
 }
 // one pivot-column row = two tagged 8-byte granules {value lo | tag, value hi | tag}, stored as ONE 16-byte write-through
-// store (a single fabric write; measured against two 8-byte stores with T4A_RRLU_COL_ST8 builds)
+// store (a single fabric write; measured against two 8-byte stores)
 __device__ __forceinline__ void st_col_row(unsigned long long* dst, unsigned long long tagbits, unsigned long long vb)
 {
-#ifdef T4A_RRLU_COL_ST8
-    st_u64_sc1(dst, tagbits | (vb & 0xFFFFFFFFull));
-    st_u64_sc1(dst + 1, tagbits | (vb >> 32));
-#else
     u32x4 v;
     v.x = (unsigned)vb;
     v.y = (unsigned)(tagbits >> 32);
     v.z = (unsigned)(vb >> 32);
     v.w = (unsigned)(tagbits >> 32);
     st_b128_sc1(dst, v);
-#endif
 }
 template <int N> struct Load16;
 template <> struct Load16<1> {
@@ -217,12 +207,6 @@ __host__ __device__ inline size_t reg_smem_layout(int M, int N, int cols_per_wg,
     return off;
 }
 
-// thresholded speculative column publication compiled in (T4A_RRLU_SPEC2) or selected at run time (RrluRegArgs::spec)
-#ifdef T4A_RRLU_SPEC2
-#define T4A_SPEC(p) 2
-#else
-#define T4A_SPEC(p) ((p).spec)
-#endif
 #define T4A_RSTAMP(slot)                                                  \
     do {                                                                  \
         if (stamp_on) {                                                   \
@@ -371,29 +355,6 @@ rrlu_reg_kernel(RrluRegArgs p)
             int cps[CPT];
 #pragma unroll
             for (int q = 0; q < CPT; ++q) cps[q] = UNI ? __builtin_amdgcn_readfirstlane(cpos[q]) : cpos[q];
-#ifdef T4A_RRLU_FLAT_PASS // measured: the pass itself gets 15 % shorter, the step does not (the exchange dominates)
-            {
-                // branch-free form: every element is updated speculatively and selected by its activity masks
-#pragma unroll
-                for (int r = 0; r < RPT; ++r) {
-                    const bool ract = rpos[r] > k;
-#pragma unroll
-                    for (int q = 0; q < CPT; ++q) {
-                        const bool act = ract && (cps[q] > k);
-                        double t = a[q][r];
-                        if (k >= 0) {
-                            const double prod = l[r] * u[q]; // update_trailing_submatrix (matrixlu.rs:593-612)
-                            const double upd = t - prod;
-                            const bool piv = ract && (cps[q] == k); // scale_column_tail: owners store l_i
-                            t = act ? upd : (piv ? l[r] : t);
-                            a[q][r] = t;
-                        }
-                        const double sc = vmax(m, t * t); // maxNum drops NaN scores (matrixlu.rs:506)
-                        m = act ? sc : m;
-                    }
-                }
-            }
-#else
             {
 #pragma unroll
                 for (int r = 0; r < RPT; ++r) {
@@ -413,7 +374,6 @@ rrlu_reg_kernel(RrluRegArgs p)
                     }
                 }
             }
-#endif
         }
         npiv = k + 1;
         if (k + 1 >= max_steps) break; // the reference stops before another arg-max (matrixlu.rs:747)
@@ -554,17 +514,12 @@ rrlu_reg_kernel(RrluRegArgs p)
                 unsigned long long* kd = p.keys + ((size_t)par * p.W + w) * 2;
                 const unsigned long long k0 = (tag16 << 48) | (vb >> 16);
                 const unsigned long long k1 = (tag16 << 48) | ((vb & 0xFFFFull) << 32) | (unsigned long long)bpos;
-#ifdef T4A_RRLU_KEY_ST8 // the two 8-byte stores of the first versions (A/B builds only)
-                st_u64_sc1(kd + 0, k0);
-                st_u64_sc1(kd + 1, k1);
-#else
                 u32x4 kv; // one 16-byte write-through store: a single fabric write instead of two
                 kv.x = (unsigned)k0;
                 kv.y = (unsigned)(k0 >> 32);
                 kv.z = (unsigned)k1;
                 kv.w = (unsigned)(k1 >> 32);
                 st_b128_sc1(kd, kv);
-#endif
             }
             // everybody else (and the pusher afterwards) prepares the candidate column while the keys travel
 #pragma unroll
@@ -579,7 +534,7 @@ rrlu_reg_kernel(RrluRegArgs p)
             // column is already in flight while the keys are gathered (one hand-off per pivot step instead of two)
             // thresholded mode (spec == 2): only workgroups whose candidate is within a factor of the previous pivot publish
             // early (a handful per step instead of all W), the others catch up after the gather if they win
-            early_pub = T4A_SPEC(p) == 1 || (T4A_SPEC(p) == 2 && bsc >= spec_frac * prev_sq);
+            early_pub = bsc >= spec_frac * prev_sq;
             if (early_pub && qstar >= 0) {
 #pragma unroll
                 for (int r = 0; r < RPT; ++r)
@@ -605,34 +560,19 @@ rrlu_reg_kernel(RrluRegArgs p)
                 unsigned long long g[KPL][2];
                 for (;;) {
                     bool ok = true;
-#ifdef T4A_RRLU_KEY_LD8 // two 8-byte loads per key (A/B builds only); a run-time switch here costs the loop 1 %
-                    const bool key_ld16 = false;
-#else
-                    const bool key_ld16 = true;
-#endif
-                    if (key_ld16) { // one 16-byte load per key instead of two 8-byte ones
-                        const void* ptrs[KPL];
-                        u32x4 got[KPL];
+                    // one 16-byte load per key instead of two 8-byte ones
+                    const void* ptrs[KPL];
+                    u32x4 got[KPL];
 #pragma unroll
-                        for (int j = 0; j < KPL; ++j) {
-                            const int qw = lane + 64 * j;
-                            ptrs[j] = kb + 2 * (size_t)(qw < p.W ? qw : 0);
-                        }
-                        Load16<KPL>::run(ptrs, got);
+                    for (int j = 0; j < KPL; ++j) {
+                        const int qw = lane + 64 * j;
+                        ptrs[j] = kb + 2 * (size_t)(qw < p.W ? qw : 0);
+                    }
+                    Load16<KPL>::run(ptrs, got);
 #pragma unroll
-                        for (int j = 0; j < KPL; ++j) {
-                            g[j][0] = ((unsigned long long)got[j].y << 32) | got[j].x;
-                            g[j][1] = ((unsigned long long)got[j].w << 32) | got[j].z;
-                        }
-                    } else {
-#pragma unroll
-                        for (int j = 0; j < KPL; ++j) {
-                            const int qw = lane + 64 * j;
-                            if (qw < p.W) {
-                                g[j][0] = ld_u64_sc1(kb + 2 * (size_t)qw);
-                                g[j][1] = ld_u64_sc1(kb + 2 * (size_t)qw + 1);
-                            }
-                        }
+                    for (int j = 0; j < KPL; ++j) {
+                        g[j][0] = ((unsigned long long)got[j].y << 32) | got[j].x;
+                        g[j][1] = ((unsigned long long)got[j].w << 32) | got[j].z;
                     }
 #pragma unroll
                     for (int j = 0; j < KPL; ++j) {
@@ -695,8 +635,8 @@ rrlu_reg_kernel(RrluRegArgs p)
             wkey = (unsigned)s.win_i[1];
             ww = s.win_i[0];
             // hop 2: only the winner's owning column group publishes the pivot column: one 16-byte store of two
-            // tagged granules per row, replicated into `ncopy` copies so that at most W/ncopy readers share a line
-            if (T4A_SPEC(p) == 2 && !early_pub && ww == w && qstar >= 0) { // the winner did not speculate: publish into its slot now
+            // tagged granules per row
+            if (!early_pub && ww == w && qstar >= 0) { // the winner did not speculate: publish into its slot now
 #pragma unroll
                 for (int r = 0; r < RPT; ++r)
                     if (irow[r] >= 0) {
@@ -705,31 +645,16 @@ rrlu_reg_kernel(RrluRegArgs p)
                         st_col_row(dst, tagbits, vb);
                     }
             }
-            if (!T4A_SPEC(p) && ww == w && qstar >= 0) {
-#pragma unroll
-                for (int r = 0; r < RPT; ++r)
-                    if (irow[r] >= 0) {
-                        const unsigned long long vb = (unsigned long long)__double_as_longlong(colv[r]);
-                        for (int c = 0; c < p.ncopy; ++c) {
-                            unsigned long long* dst = p.cols + (((size_t)par * p.ncopy + c) * (size_t)M + irow[r]) * 2;
-                            st_u64_sc1(dst, tagbits | (vb & 0xFFFFFFFFull));
-                            st_u64_sc1(dst + 1, tagbits | (vb >> 32));
-                        }
-                    }
-            }
         }
         const bool need_fetch = !SINGLE && !(ww == w && qstar >= 0);
-        const unsigned long long* colsrc =
-            SINGLE ? nullptr
-                   : (T4A_SPEC(p) ? p.cols + ((size_t)((k + 1) & 1) * p.W + ww) * (size_t)M * 2
-                             : p.cols + ((size_t)((k + 1) & 1) * p.ncopy + (w % p.ncopy)) * (size_t)M * 2);
+        const unsigned long long* colsrc = SINGLE ? nullptr : p.cols + ((size_t)((k + 1) & 1) * p.W + ww) * (size_t)M * 2;
         unsigned long long cg0[RPT], cg1[RPT];
 #pragma unroll
         for (int r = 0; r < RPT; ++r) {
             cg0[r] = 0ull;
             cg1[r] = 0ull;
         }
-        if (need_fetch && T4A_SPEC(p) == 2) { // the winner most likely published with its key: the column is already there
+        if (need_fetch) { // the winner most likely published with its key: the column is already there
 #pragma unroll
             for (int r = 0; r < RPT; ++r)
                 if (irow[r] >= 0) {
@@ -779,17 +704,6 @@ rrlu_reg_kernel(RrluRegArgs p)
             }
         }
         if (w == 0 && tid == 0) p.pivot_vals[kn] = wval;
-
-        // issue the pivot-column loads (issuing them before the bookkeeping measured worse: more first-sweep misses; in the
-        // thresholded speculative mode they were already issued straight after the gather)
-        if (need_fetch && T4A_SPEC(p) != 2) {
-#pragma unroll
-            for (int r = 0; r < RPT; ++r)
-                if (irow[r] >= 0) {
-                    cg0[r] = ld_u64_sc1(colsrc + 2 * (size_t)irow[r]);
-                    cg1[r] = ld_u64_sc1(colsrc + 2 * (size_t)irow[r] + 1);
-                }
-        }
 
         // ---- pivot column -> l (scaled) ----
         if (SINGLE) {
@@ -980,22 +894,15 @@ int norm_cpt(int c) { return c <= 1 ? 1 : (c <= 6 ? c : 8); }
 bool rrlu_reg_make_plan(int M, int N, int num_cus, RrluRegPlan* out)
 {
     RrluRegPlan plan;
-    const char* ew = diag_env("T4A_RRLU_W");
-    const char* et = diag_env("T4A_RRLU_T");
-    const char* ec = diag_env("T4A_RRLU_CPT");
     // (the key-table poller reads 4 keys per lane and the engine reserves 256 slots: never plan more workgroups than that)
     const int maxw = std::min(num_cus > 16 ? num_cus - 8 : num_cus, 256);
     const long long elems = (long long)M * N;
-    static const long long single_max = diag_env("T4A_RRLU_SINGLE_MAX") ? std::atoll(diag_env("T4A_RRLU_SINGLE_MAX")) : 64 * 64;
-    bool single = elems <= single_max;
-    if (ew) single = std::atoi(ew) == 1;
     bool found = false;
-    if (single) {
+    if (elems <= 64 * 64) {
         // one workgroup: TR x TC thread grid with <= 4 x 8 elements per thread; minimise the per-thread work,
         // then the thread count
         int best_cost = 1 << 30;
         for (int T = 64; T <= 512; T *= 2) {
-            if (et && T != std::atoi(et)) continue;
             for (int TR = 16; TR <= T; TR *= 2) {
                 const int TC = T / TR;
                 const int RPT = (M + TR - 1) / TR;
@@ -1022,37 +929,14 @@ bool rrlu_reg_make_plan(int M, int N, int num_cus, RrluRegPlan* out)
         int TR = round_up((M + RPT - 1) / RPT, 64);
         int TC = 1;
         if (TR < 256) TC = 256 / TR;
-        if (et) {
-            int T = round_up(std::atoi(et), 64);
-            if (T > 1024) T = 1024;
-            if (T >= round_up(M, 64)) {
-                RPT = 1;
-                TR = round_up(M, 64);
-                TC = T / TR;
-            } else {
-                RPT = (M + T - 1) / T;
-                TR = round_up((M + RPT - 1) / RPT, 64);
-                TC = 1;
-            }
-        }
-        if (const char* etr = diag_env("T4A_RRLU_TR")) { // experiment: explicit thread grid TR x TC
-            TR = round_up(std::atoi(etr), 64);
-            RPT = (M + TR - 1) / TR;
-            TC = diag_env("T4A_RRLU_TC") ? std::atoi(diag_env("T4A_RRLU_TC")) : 1;
-            if (TC < 1) TC = 1;
-        }
         if (RPT > 4 || TR > 1024) return false; // beyond the register budget: LDS kernel
         // more, thinner workgroups win once the key table is shared (measured: 3 columns per thread and 230 workgroups
         // beat 4 / 172 by 3.5 % at 685 x 688); fall back to 4 and 8 when that would need more workgroups than CUs
-        int CPT = ec ? norm_cpt(std::atoi(ec)) : 3;
+        int CPT = 3;
         int W = (N + TC * CPT - 1) / (TC * CPT);
-        if (!ec && W > maxw) {
+        if (W > maxw) {
             CPT = 4;
             W = (N + TC * CPT - 1) / (TC * CPT);
-        }
-        if (ew && std::atoi(ew) > 1) {
-            W = std::atoi(ew);
-            CPT = norm_cpt((N + W * TC - 1) / (W * TC));
         }
         while (W > maxw && CPT < 8) {
             CPT = CPT < 6 ? CPT + 1 : 8; // 3 -> 4 -> 5 -> 6 -> 8 columns per thread

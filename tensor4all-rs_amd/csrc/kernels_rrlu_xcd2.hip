@@ -53,41 +53,10 @@ static_assert(Xcd2Lds<16, 3>::bytes == (int)xcd2_lds_total(16, 3), "plan.lds_byt
 #ifndef T4A_XCD_STAMP_WAVE
 #define T4A_XCD_STAMP_WAVE 0
 #endif
-// T4A_X2_POLLEARLY = 1 (experiment): the polling wave issues its sweep of the early keys in the middle of its own position search
-// (behind the ballots, in front of the slot sweep) instead of behind its full-key store
-// T4A_X2_CSTRIDE (experiment): byte distance between consecutive 256-byte chunks (16 rows) of a column slot in the mailbox; 256 =
-// contiguous.  A larger stride spreads a column over more L2 channels if the channel interleave is coarser than 256 bytes (the
-// host sizes the mailbox with T4A_XCD_CSTRIDE set to the same value).
-#ifndef T4A_X2_CSTRIDE
-#define T4A_X2_CSTRIDE 256
-#endif
-// T4A_X2_DUPLOAD = 1 (measurement only): every dividing wave fetches its rows of the winner's column TWICE — if the step gets slower by
-// about the time the hand-off takes, the hand-off is bound by the L2 serving 29 workgroups the same lines, not by latency
-// T4A_X2_NOBARB = 1 (experiment): barrier (B) is replaced by a step tag inside the record: the polling wave's
-// lane 0 stores the record with the tag, every other wave spins on the record in the LDS.  (Safe: a record of step kn exists only after
-// every agent's early key of step kn, i.e. after every wave of this workgroup has finished reading the previous step's l.)
-#ifndef T4A_X2_NOBARB
-#define T4A_X2_NOBARB 0
-#endif
-#ifndef T4A_X2_DUPLOAD
-#define T4A_X2_DUPLOAD 0
-#endif
-#ifndef T4A_X2_POLLEARLY
-#define T4A_X2_POLLEARLY 0
-#endif
-// T4A_X2_KHEARLY = 1: the polling wave requests the FULL keys together with every sweep of the early keys instead of behind the
-// successful one — when the winner's position search has finished by then (its full key carries the right tag) the pick does not wait
-// for a second L2 round trip; a stale one is fetched again as before
-#ifndef T4A_X2_KHEARLY
-#define T4A_X2_KHEARLY 0
-#endif
-// T4A_X2_FSTAGGER = 1 (agents on several XCDs): the remote finalists are requested THREE times, staggered — when the early keys are
-// complete (as before), when the local winner is known, and behind the publication of the own finalist — and examined oldest first.
-// A read across the fabric takes ~2 400 cycles and samples the memory side somewhere in the middle: a single read issued before the
-// remote XCDs have picked comes back stale and the next one costs another full trip.
-#ifndef T4A_X2_FSTAGGER
-#define T4A_X2_FSTAGGER 1
-#endif
+// Agents on several XCDs: the remote finalists are requested THREE times, staggered — when the early keys are complete, when the
+// local winner is known, and behind the publication of the own finalist — and examined oldest first.  A read across the fabric takes
+// ~2 400 cycles and samples the memory side somewhere in the middle: a single read issued before the remote XCDs have picked comes
+// back stale and the next one costs another full trip.
 
 // full-key meta word (second generation): bits 0..10 row index of the candidate (up to 1536 rows since round 5), 11..12 column slot
 // of the publishing agent, bit 13 the agent has a candidate.  Positions are NOT carried: whoever needs one reads the LDS tables (the
@@ -264,7 +233,7 @@ __device__ __forceinline__ void rrlu_xcd2_body(const RrluXcdArgs& p, const RrluX
     // resource for every store and load of the exchange)
     const unsigned k2_base = 2u * (unsigned)NW * 16u;
     const unsigned cols_base = 4u * (unsigned)NW * 16u;
-    const unsigned fin_base = cols_base + 2u * (unsigned)NW * (unsigned)(MP / 16) * (unsigned)T4A_X2_CSTRIDE; // [2][KX] finalist granules (agents on several XCDs)
+    const unsigned fin_base = cols_base + 2u * (unsigned)NW * (unsigned)(MP / 16) * 256u; // [2][KX] finalist granules (agents on several XCDs)
     const unsigned k3_base = fin_base + 256u;  // [2][NW] write-through copies of the full keys (agents on several XCDs: the exact walk)
     const __amdgpu_buffer_rsrc_t mail =
         __builtin_amdgcn_make_buffer_rsrc((void*)p.keys, 0, (int)(k3_base + (KX > 1 ? 2u * (unsigned)NW * 16u : 0u)), 0x00020000);
@@ -330,7 +299,6 @@ __device__ __forceinline__ void rrlu_xcd2_body(const RrluXcdArgs& p, const RrluX
             if (lane == 0) __builtin_amdgcn_raw_buffer_store_b128(kv, mail, kslot, 0, 0); // (read inside this XCD only: a plain store, also when the agents span several XCDs)
         }
         u32x4 kg[4], kh[4];
-        bool kg_issued = false;
         bool has_cand = false;         // this agent has a candidate
         double cval = 0.0;             // its value
         int cirow = 0, qstar = 0;      // its row index and my column slot
@@ -346,14 +314,6 @@ __device__ __forceinline__ void rrlu_xcd2_body(const RrluXcdArgs& p, const RrluX
                     bq[q] = __ballot(mq[q] == wmax); // (columns outside the trailing block keep mq = -1)
                     nhit += __builtin_popcountll(bq[q]);
                 }
-#if T4A_X2_POLLEARLY
-                if (poller) {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        kg[j] = __builtin_amdgcn_raw_buffer_load_b128(mail, (par * NW + pbase + min(lane + 64 * j, NWL - 1)) * 16, 0, BUF_SC1);
-                    kg_issued = true;
-                }
-#endif
                 if (nhit == 1) { // one lane of one column holds the maximum: the normal case
 #pragma unroll
                     for (int q = 0; q < CPT; ++q)
@@ -440,21 +400,16 @@ __device__ __forceinline__ void rrlu_xcd2_body(const RrluXcdArgs& p, const RrluX
         // the polling wave sweeps the early keys now — they left their agents a whole position search ago, so this first sweep
         // normally finds them all.  Every lane fetches four keys; lanes beyond NW re-read the last key (a valid duplicate), so
         // neither the arrival check nor the maximum needs a mask or a count of live groups.
-        if (poller && !kg_issued) {
+        if (poller) {
 #pragma unroll
             for (int j = 0; j < 4; ++j)
                 kg[j] = __builtin_amdgcn_raw_buffer_load_b128(mail, (par * NW + pbase + min(lane + 64 * j, NWL - 1)) * 16, 0, BUF_SC1);
-#if T4A_X2_KHEARLY
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                kh[j] = __builtin_amdgcn_raw_buffer_load_b128(mail, (int)k2_base + (par * NW + pbase + min(lane + 64 * j, NWL - 1)) * 16, 0, BUF_SC1);
-#endif
         }
         // thresholded speculative publication of the candidate column: pivots shrink slowly, so the next winner is almost
         // always an agent whose candidate is close to the previous pivot; its column is then already in the L2 when the
         // keys have been gathered
         const bool early_pub = !poller && has_cand && (sq >= spec_frac * prev_sq); // (a polling wave never stores a column early: those stores would sit in front of its key loads)
-        constexpr int CS = T4A_X2_CSTRIDE, SLOTB = (MP / 16) * CS; // chunk stride / bytes of a column slot
+        constexpr int CS = 256, SLOTB = (MP / 16) * CS; // chunk stride / bytes of a column slot
         const int myslot = (int)cols_base + (par * NW + g) * SLOTB + (lane >> 4) * CS + (lane & 15) * 16; // byte offset of my row `lane` in the mailbox
         if (early_pub) {
             if (qstar == 0) xcd_publish_column<0, RPT, ST_AUX>(a[0], mail, myslot, tag, 4 * CS);
@@ -482,11 +437,6 @@ __device__ __forceinline__ void rrlu_xcd2_body(const RrluXcdArgs& p, const RrluX
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
                     kg[j] = __builtin_amdgcn_raw_buffer_load_b128(mail, (par * NW + pbase + min(lane + 64 * j, NWL - 1)) * 16, 0, BUF_SC1);
-#if T4A_X2_KHEARLY
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    kh[j] = __builtin_amdgcn_raw_buffer_load_b128(mail, (int)k2_base + (par * NW + pbase + min(lane + 64 * j, NWL - 1)) * 16, 0, BUF_SC1);
-#endif
             }
             if (stamp_on) lds_stamps[5] += spins;
             // agents on several XCDs: the first read of the REMOTE finalists goes out now — a read across the fabric takes ~2 400 cycles,
@@ -499,11 +449,9 @@ __device__ __forceinline__ void rrlu_xcd2_body(const RrluXcdArgs& p, const RrluX
                 fr = __builtin_amdgcn_raw_buffer_load_b128(mail, fslot + xr * 16, 0, BUF_SC1);
             }
             // the full keys: fetched now, in flight while the early ones are examined (a late one is fetched again below)
-#if !T4A_X2_KHEARLY
 #pragma unroll
             for (int j = 0; j < 4; ++j)
                 kh[j] = __builtin_amdgcn_raw_buffer_load_b128(mail, (int)k2_base + (par * NW + pbase + min(lane + 64 * j, NWL - 1)) * 16, 0, BUF_SC1);
-#endif
             XSTAMP(8);
             int wa_ = 0;
             unsigned wkx = 0u, wky = 0u, wkz = 0u; // the winner's full key
@@ -642,9 +590,7 @@ __device__ __forceinline__ void rrlu_xcd2_body(const RrluXcdArgs& p, const RrluX
                     // reads per round through the fabric; profiles/r05_xcd2m_phase_stamps.txt.)
                     // finalist granule: {value lo, value hi, meta | agent << 14 | give-up << 26 | undecided << 31, tag ^ fold}
                     bool need_exact = (wkz >> 31) != 0u; // (this XCD could not decide on its early keys alone)
-#if T4A_X2_FSTAGGER
                     u32x4 fr1 = __builtin_amdgcn_raw_buffer_load_b128(mail, fslot + xr * 16, 0, BUF_SC1);
-#endif
                     if (rank == xi * p.W && lane == 0) {
                         u32x4 fv;
                         fv.x = wkx;
@@ -661,13 +607,11 @@ __device__ __forceinline__ void rrlu_xcd2_body(const RrluXcdArgs& p, const RrluX
                     double best = __builtin_fabs(mk_f64(wkx, wky));
                     {
                         unsigned sp2 = 0;
-#if T4A_X2_FSTAGGER
                         u32x4 fr2 = __builtin_amdgcn_raw_buffer_load_b128(mail, fslot + xr * 16, 0, BUF_SC1);
                         if (!__all((fr.x ^ fr.y ^ fr.z ^ fr.w) == tag)) {
                             fr = fr1;
                             if (!__all((fr.x ^ fr.y ^ fr.z ^ fr.w) == tag)) fr = fr2;
                         }
-#endif
                         for (;;) {
                             if (__all((fr.x ^ fr.y ^ fr.z ^ fr.w) == tag)) break;
                             xcd_poll_again();
@@ -760,7 +704,7 @@ __device__ __forceinline__ void rrlu_xcd2_body(const RrluXcdArgs& p, const RrluX
                     if (lds_ptrs[1]) reinterpret_cast<volatile int*>(lds_ptrs[1])[5] = giveup;
                 }
                 int4 rec;
-                rec.x = wa_ | (giveup << 30) | (T4A_X2_NOBARB ? ((((kn & 0x7F) + 1)) << 16) : 0);
+                rec.x = wa_ | (giveup << 30);
                 rec.y = (int)wkx;
                 rec.z = (int)wky;
                 rec.w = (int)wkz;
@@ -768,26 +712,14 @@ __device__ __forceinline__ void rrlu_xcd2_body(const RrluXcdArgs& p, const RrluX
             }
             XSTAMP(9);
         }
-#if !T4A_X2_NOBARB
         __syncthreads(); // (B)
-#endif
         XSTAMP(3);
         int4 rec; // the record in ONE LDS round trip
         {
             int zero = 0;
-#if T4A_X2_NOBARB
-            for (;;) {
-                asm volatile("ds_read_b128 %0, %1 offset:%2\n\ts_waitcnt lgkmcnt(0)" : "=&v"(rec) : "v"(zero), "n"(L::o_wi + 16) : "memory");
-                if (((__builtin_amdgcn_readfirstlane(rec.x) >> 16) & 0xFF) == ((kn & 0x7F) + 1)) break;
-#if T4A_X2_NOBARB > 1
-                __builtin_amdgcn_s_sleep(T4A_X2_NOBARB - 1); // (spinning waves take issue slots from the polling wave on their SIMD)
-#endif
-            }
-#else
             asm volatile("ds_read_b128 %0, %1 offset:%2\n\ts_waitcnt lgkmcnt(0)" : "=&v"(rec) : "v"(zero), "n"(L::o_wi + 16) : "memory");
-#endif
         }
-        const unsigned recw = (unsigned)__builtin_amdgcn_readfirstlane(rec.x) & (T4A_X2_NOBARB ? 0xC000FFFFu : 0xFFFFFFFFu);
+        const unsigned recw = (unsigned)__builtin_amdgcn_readfirstlane(rec.x);
         if (recw >> 30) {
             timed_out = true;
             break;
@@ -807,12 +739,6 @@ __device__ __forceinline__ void rrlu_xcd2_body(const RrluXcdArgs& p, const RrluX
 #pragma unroll
         for (int j = 0; j < XR; ++j)
             if (sr0 >= 0 && sr0 + X2_DIVW * j < RPT) cc[j] = __builtin_amdgcn_raw_buffer_load_b128(mail, slot_off + j * X2_DIVW * 4 * CS, 0, BUF_SC1);
-#if T4A_X2_DUPLOAD
-        u32x4 cd[XR];
-#pragma unroll
-        for (int j = 0; j < XR; ++j)
-            if (sr0 >= 0 && sr0 + X2_DIVW * j < RPT) cd[j] = __builtin_amdgcn_raw_buffer_load_b128(mail, slot_off + j * X2_DIVW * 4 * CS, 0, BUF_SC1);
-#endif
         // who sits at position kn now (the polling wave moves them behind its stop test)
         int rk_ = 0, ck_ = 0;
         int prp_ = 0, pcp_ = 0; // ... and where the pivot's row and column sit
@@ -893,11 +819,6 @@ __device__ __forceinline__ void rrlu_xcd2_body(const RrluXcdArgs& p, const RrluX
 #pragma unroll
                 for (int j = 0; j < XR; ++j)
                     if (sr0 + X2_DIVW * j < RPT) ok &= ((cc[j].x ^ cc[j].y ^ cc[j].z ^ cc[j].w) == tag);
-#if T4A_X2_DUPLOAD
-#pragma unroll
-                for (int j = 0; j < XR; ++j)
-                    if (sr0 + X2_DIVW * j < RPT) asm volatile("" ::"v"(cd[j].x), "v"(cd[j].w)); // (the second copy must have arrived too)
-#endif
                 if (__all(ok)) break;
                 xcd_poll_again();
                 if (++spins > XSPIN) {

@@ -284,8 +284,7 @@ hipStream_t stream_get(int kind)
     hipStream_t s = nullptr;
     int least = 0, greatest = 0;
     T4A_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
-    static const bool flat = diag_env("T4A_FLAT_PRIORITY") != nullptr;
-    if (kind == 0 || flat || least == greatest)
+    if (kind == 0 || least == greatest)
         T4A_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
     else
         T4A_HIP(hipStreamCreateWithPriority(&s, hipStreamNonBlocking, kind == 1 ? greatest : least));

@@ -64,27 +64,22 @@ bool rrlu_xcd_make_plan(int M, int N, RrluXcdPlan* out, bool any_size, int max_w
     if (max_w < 1 || max_w > 32) max_w = 32;
     if (M < 1 || N < 1) return false;
     if (M > 1024 || N > 1024) return allow_big && max_w == 32 && xcd_make_big_plan(M, N, out);
-    static const int min_elems = diag_env("T4A_XCD_MIN") ? std::atoi(diag_env("T4A_XCD_MIN")) : 64 * 64;
-    if (!any_size && (long long)M * N <= (long long)min_elems) return false; // tiny matrices: the single-workgroup plan of the chip-wide kernel
+    if (!any_size && (long long)M * N <= 64 * 64) return false; // tiny matrices: the single-workgroup plan of the chip-wide kernel
     const int rpt = xcd_norm_rpt((M + 63) / 64);
     if (rpt < 0) return false;
     // columns per agent: as few as the 32 compute units of an XCD allow.  A step costs an agent ~500 cycles per owned column
     // (update, its share of the search, pivot-row extraction) and the gather is the same four key loads per lane for any
     // number of agents up to 256 (measured per step: 2.0 - 2.2 us with one column per agent, 2.45 us with two, 2.65 us with
-    // three; T4A_XCD_COST=old restores the round-2 model that traded columns against 64-agent key groups)
-    static const bool old_cost = diag_env("T4A_XCD_COST") != nullptr;
-    static const int w_env = diag_env("T4A_XCD_W") ? std::atoi(diag_env("T4A_XCD_W")) : 0;
-    static const int cpt_env = diag_env("T4A_XCD_CPT") ? std::atoi(diag_env("T4A_XCD_CPT")) : 0;
+    // three)
     int best_cpt = -1, best_w = 0;
     long best_cost = 0;
     for (int c = 1; c <= XCD_MAX_CPT; ++c) {
         const int cpt = xcd_norm_cpt(c);
         if (cpt != c) continue;
-        if (cpt_env > 0 && cpt != cpt_env) continue;
         const int w = (N + XWAVES * cpt - 1) / (XWAVES * cpt);
         if (w > max_w) continue;
         if (rpt * cpt > XCD_MAX_VALUES) continue;
-        const long cost = old_cost ? 24L * rpt * cpt + 250L * ((w * XWAVES + 63) / 64) : (long)cpt;
+        const long cost = cpt;
         if (best_cpt < 0 || cost < best_cost) {
             best_cpt = cpt;
             best_w = w;
@@ -92,12 +87,6 @@ bool rrlu_xcd_make_plan(int M, int N, RrluXcdPlan* out, bool any_size, int max_w
         }
     }
     if (best_cpt < 0) return false;
-    if (w_env > 0) {
-        best_w = w_env > max_w ? max_w : w_env;
-        int c = (N + XWAVES * best_w - 1) / (XWAVES * best_w);
-        best_cpt = xcd_norm_cpt(c);
-        if (best_cpt < 0 || rpt * best_cpt > XCD_MAX_VALUES) return false;
-    }
     RrluXcdPlan plan;
     plan.W = best_w;
     plan.RPT = rpt;
@@ -107,8 +96,6 @@ bool rrlu_xcd_make_plan(int M, int N, RrluXcdPlan* out, bool any_size, int max_w
     // each — and a padded request keeps other kernels' workgroups that only have to RETURN on this XCD, see lu_update_kernel,
     // from being placed at all)
     plan.lds_bytes = xcd_lds_total(rpt);
-    static const bool pad_lds = diag_env("T4A_XCD_PAD_LDS") != nullptr;
-    if (pad_lds && plan.lds_bytes < 84 * 1024) plan.lds_bytes = 84 * 1024;
     *out = plan;
     return true;
 }
@@ -116,9 +103,8 @@ bool rrlu_xcd_make_plan(int M, int N, RrluXcdPlan* out, bool any_size, int max_w
 size_t rrlu_xcd_keys_bytes(const RrluXcdPlan& plan) { return (size_t)4 * plan.K * plan.W * XWAVES * 16; } // early keys + full keys, two step parities each
 size_t rrlu_xcd_cols_bytes(const RrluXcdPlan& plan, int)
 {
-    // slots are padded to 64 * RPT rows; T4A_XCD_CSTRIDE (experiment, with a library built with -DT4A_X2_CSTRIDE): sparse slots
-    static const size_t cstride = diag_env("T4A_XCD_CSTRIDE") ? (size_t)std::atol(diag_env("T4A_XCD_CSTRIDE")) : 256;
-    return (size_t)2 * plan.K * plan.W * XWAVES * (size_t)(4 * plan.RPT) * (cstride < 256 ? 256 : cstride) + (plan.K > 1 ? 256 + (size_t)2 * plan.K * plan.W * XWAVES * 16 : 0); // (+ the finalist granules of the XCDs and the write-through copies of the full keys)
+    // slots are padded to 64 * RPT rows
+    return (size_t)2 * plan.K * plan.W * XWAVES * (size_t)(4 * plan.RPT) * 256 + (plan.K > 1 ? 256 + (size_t)2 * plan.K * plan.W * XWAVES * 16 : 0); // (+ the finalist granules of the XCDs and the write-through copies of the full keys)
 }
 
 

@@ -418,13 +418,8 @@ void Tci2::stage_accumulators(const IndexSet& a, size_t a0, const IndexSet& b, s
         return;
     }
     d_rowacc_.reserve(need);
-    static const bool dma_copy = diag_env("T4A_ACC_DMA") != nullptr;
-    if (dma_copy) {
-        T4A_HIP(hipMemcpyAsync(d_rowacc_.get(), ha, need * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    } else {
-        stage_copy_launch(ha, d_rowacc_.get(), need, st);
-        T4A_HIP(hipGetLastError());
-    }
+    stage_copy_launch(ha, d_rowacc_.get(), need, st);
+    T4A_HIP(hipGetLastError());
     *d_ra = d_rowacc_.get();
     *d_rb = d_rowacc_.get() + ra.size();
 }
@@ -583,15 +578,13 @@ LuciResult Tci2::luci_on_sets(const IndexSet& is, const IndexSet& js, const RrLU
 {
     const size_t M = is.count, N = js.count;
     hipStream_t st = eng.stream();
-    static const bool no_fuse = diag_env("T4A_NO_FUSED_PI") != nullptr;
-    if (fn_kind_ == FnKind::Builtin && !no_fuse && M > 0 && N > 0) {
+    if (fn_kind_ == FnKind::Builtin && M > 0 && N > 0) {
         // built-in functor: only the accumulators travel; the rrLU kernel evaluates Pi into its registers
         FusedPi fp;
         fp.fn = fn_dev_;
         // small bonds (the single-workgroup plan with the fused candidate-matrix build takes them): the kernel reads the few
         // hundred bytes of accumulators straight from the pinned arena — no staging kernel in front of a 10 us factorisation
-        static const bool no_in_place = diag_env("T4A_ACC_STAGE_ALWAYS") != nullptr;
-        fp.host_resident = !no_in_place && (M * N <= (size_t)64 * 64);
+        fp.host_resident = M * N <= (size_t)64 * 64;
         stage_accumulators(is, 0, js, is.width, acc_rows, acc_cols, &fp.d_rowacc, &fp.d_colacc, fp.host_resident);
         eng.prof.v[11] += (double)M * (double)N;
         LuciResult lu = eng.luci(nullptr, (int)M, (int)N, o, need_factors, false, &fp);
@@ -756,17 +749,15 @@ void Tci2::update_pivots(size_t b, bool left_orthogonal, const TCI2Options& opti
     const IndexSet& j_comb = have_cols ? ready.set : j_own;
     const bool acc_ready = ready.valid && fn_kind_ == FnKind::Builtin;
     if (i_comb.count == 0 || j_comb.count == 0) return;
-    if (prefetch_.wanted || prefetch_.fill_site >= 0 || prefetch_.flush_fill) {
+    if (prefetch_.wanted || prefetch_.fill_site >= 0) {
         // host work that does not depend on this bond: the independent side of the NEXT bond and the fill
         // accumulators of a site that is already final; runs while this bond's kernels are in flight
         const Prefetch pf = prefetch_;
         prefetch_.wanted = false;
         prefetch_.fill_site = -1;
-        prefetch_.flush_fill = false;
         eng.overlap_hook = [this, pf]() {
             if (pf.wanted) build_side(pf.bond, pf.cols, *pf.extra, prep_);
             if (pf.fill_site >= 0) prepare_fill_site((size_t)pf.fill_site);
-            if (pf.flush_fill) flush_deferred_fill(); // the previous half-sweep's fill: its stream operations go out now
         };
     }
     const auto hp_t1 = std::chrono::steady_clock::now();
@@ -994,10 +985,6 @@ void Tci2::issue_fill_ops(std::vector<std::function<void()>>& ops, const std::ve
     hipStream_t st = fill_stream_;
     static const bool use_graph = std::getenv("T4A_NO_FILL_GRAPH") == nullptr;
     if (fill_timed_) T4A_HIP(hipEventRecord(ev_fill_.a, st));
-    for (auto& f : fill_pre_ops_) f(); // (diagnosis switch T4A_FILL_GRAPH_NO_COPY: the upload in front of the graph)
-    fill_pre_ops_.clear();
-    static const bool dev_sync_first = diag_env("T4A_FILL_GRAPH_DEVSYNC") != nullptr; // (diagnosis)
-    if (dev_sync_first) T4A_HIP(hipDeviceSynchronize());
     bool done = false;
     // (no graph replay on a handle whose cores are exported / imported through the LEGACY DEFAULT STREAM.  Round 4 saw GPU memory
     // faults in 25 - 75 % of `bench.py --mode site-shard` runs with replay on; round 5 bisected them (tools/r5_gpu_shardfault*.sh,
@@ -1014,8 +1001,7 @@ void Tci2::issue_fill_ops(std::vector<std::function<void()>>& ops, const std::ve
     // does not explain the faults, and no multi-GPU soak of the patch-farm path exists).  The default is therefore the round-4 guard —
     // no replay on ANY handle whose site tensors are exported / imported asynchronously; the relaxed guard (replay unless the legacy
     // stream or a blocking stream took part) is an opt-in: t4a_gpu_tci2_set_chain bit 4.  The gain it buys is ~0.4 % of a sweep.
-    static const bool graph_shared = diag_env("T4A_FILL_GRAPH_SHARED") != nullptr; // (diagnosis: replay even then)
-    const bool shared_ok = !cores_shared_async_ || (fill_graph_relaxed && !cores_shared_legacy_stream_) || graph_shared;
+    const bool shared_ok = !cores_shared_async_ || (fill_graph_relaxed && !cores_shared_legacy_stream_);
     if (use_graph && !fill_graph_broken_ && shared_ok) {
         if (fill_graph_exec_ && sig == fill_graph_sig_) {
             T4A_HIP(hipGraphLaunch(fill_graph_exec_, st));
@@ -1061,18 +1047,8 @@ void Tci2::issue_fill_ops(std::vector<std::function<void()>>& ops, const std::ve
     if (fill_timed_) T4A_HIP(hipEventRecord(ev_fill_.b, st));
 }
 
-void Tci2::flush_deferred_fill()
-{
-    if (fill_deferred_.empty()) return;
-    std::vector<std::function<void()>> ops;
-    ops.swap(fill_deferred_);
-    issue_fill_ops(ops, fill_deferred_sig_);
-    fill_inflight_ = true;
-}
-
 void Tci2::fill_wait()
 {
-    flush_deferred_fill();
     if (import_inflight_) { // cores of the other ranks' sites (site-sharded fill) still on their way into this handle
         import_inflight_ = false;
         T4A_HIP(hipStreamSynchronize(import_stream_));
@@ -1121,12 +1097,6 @@ void Tci2::fill_site_tensors_impl(bool async)
     const bool builtin = fn_kind_ == FnKind::Builtin;
     static const bool sync_fill = std::getenv("T4A_SYNC_FILL") != nullptr; // measurement switch: no overlap at all
     if (!builtin || sync_fill) async = false;
-    // deferred mode (optimize only): everything up to the upload buffer is prepared now, the ~25 stream operations are
-    // issued later from an overlap hook, when the host would otherwise wait for a long bond-update kernel
-    static const bool defer_env = diag_env("T4A_FILL_DEFER") != nullptr; // measured: no net gain (the fill then
-    // overlaps the long mid-chain kernels and slows them down by as much as the host time it hides)
-    const bool defer = async && builtin && fill_defer_requested_ && defer_env;
-    fill_defer_requested_ = false;
     std::vector<std::function<void()>> ops; // the stream operations of this fill, in order (no event records)
     std::vector<uint64_t> sig;              // everything those operations depend on: equal signature <=> same graph
     auto dev = [&](std::function<void()> f) { ops.push_back(std::move(f)); };
@@ -1311,8 +1281,7 @@ void Tci2::fill_site_tensors_impl(bool async)
     const PiJob* d_pis = nullptr;
     // small problems (BASELINE configs[1], the first iterations of every run): evaluation, solve and packing of all sites in ONE
     // launch (fill_small_kernel) instead of five dependent ones — bitwise the same cores
-    static const bool no_small_fill = diag_env("T4A_NO_SMALL_FILL") != nullptr;
-    bool small_fill = builtin && !no_small_fill;
+    bool small_fill = builtin;
 #ifdef T4A_TEST_HOOKS
     // libt4a_gpu_testhooks.so only: the general five-launch path for small problems too, so that a test can compare the two bit by bit
     // (tests/test_gpu_tci2.py::test_small_problem_fill_in_one_launch_is_bitwise_the_general_path)
@@ -1411,18 +1380,12 @@ void Tci2::fill_site_tensors_impl(bool async)
                 std::memcpy(&bits, &fn.params[q], sizeof(bits));
                 sg(bits);
             }
-            static const bool copies_outside = diag_env("T4A_FILL_GRAPH_NO_COPY") != nullptr; // (diagnosis: the upload is issued directly, in front of the graph)
-            if (copies_outside) {
-                fill_pre_ops_.push_back([=]() { T4A_HIP(hipMemcpyAsync(db, hb, total_bytes, hipMemcpyHostToDevice, st)); });
-                dev([=]() { pi_eval_batched_launch(fn, dj, npi, max_M, max_N, st); });
-            } else {
-                sg((uint64_t)small_fill);
-                const bool small = small_fill;
-                dev([=]() {
-                    T4A_HIP(hipMemcpyAsync(db, hb, total_bytes, hipMemcpyHostToDevice, st));
-                    if (!small) pi_eval_batched_launch(fn, dj, npi, max_M, max_N, st);
-                });
-            }
+            sg((uint64_t)small_fill);
+            const bool small = small_fill;
+            dev([=]() {
+                T4A_HIP(hipMemcpyAsync(db, hb, total_bytes, hipMemcpyHostToDevice, st));
+                if (!small) pi_eval_batched_launch(fn, dj, npi, max_M, max_N, st);
+            });
         }
         d_lups = reinterpret_cast<const LuProblem*>(db + off_lu);
         d_trs = reinterpret_cast<const TrsmProblem*>(db + off_tr);
@@ -1509,15 +1472,11 @@ void Tci2::fill_site_tensors_impl(bool async)
         for (auto& f : ops) f();
         if (fill_timed_) T4A_HIP(hipEventRecord(ev_fill_.b, st));
         fill_inflight_ = true;
-    } else if (defer) {
-        fill_deferred_ = std::move(ops);
-        fill_deferred_sig_ = std::move(sig);
-        fill_inflight_ = false;
     } else {
         issue_fill_ops(ops, sig);
         fill_inflight_ = true;
     }
-    if (host_prof_fill && !defer) {
+    if (host_prof_fill) {
         static double acc_ms = 0;
         static long calls = 0;
         acc_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - hpf_t0).count();
@@ -1571,19 +1530,12 @@ void Tci2::export_site_shard_async(double* d_dst, size_t stride, hipStream_t con
     cores_shared_async_ = true;
     if (stream_orders_with_legacy(consumer)) cores_shared_legacy_stream_ = true; // (see issue_fill_ops)
     hipStream_t st = fill_inflight_ ? fill_stream_ : eng.stream();
-    static const bool export_sync = diag_env("T4A_EXPORT_SYNC") != nullptr; // (diagnosis: the fill has completed before the copies are enqueued)
-    if (export_sync) T4A_HIP(hipStreamSynchronize(st));
     size_t k = 0;
     for (size_t s = shard_rank; s < n_; s += shard_world, ++k) {
         const DevCore& c = cores[s];
         if (c.size() > stride) throw Error(T4A_GPU_BUFFER_TOO_SMALL, "export_site_shard: stride smaller than a site tensor");
         if (c.size())
             T4A_HIP(hipMemcpyAsync(d_dst + k * stride, c.buf.get(), c.size() * sizeof(double), hipMemcpyDeviceToDevice, st));
-    }
-    static const bool export_hostsync = diag_env("T4A_EXPORT_HOSTSYNC") != nullptr; // (diagnosis: no event, the host waits for the copies)
-    if (export_hostsync) {
-        T4A_HIP(hipStreamSynchronize(st));
-        return;
     }
     if (!export_event_) T4A_HIP(hipEventCreateWithFlags(&export_event_, hipEventDisableTiming));
     T4A_HIP(hipEventRecord(export_event_, st));
@@ -1604,14 +1556,9 @@ void Tci2::import_site_shard_async(const double* d_src, size_t stride, size_t pe
     // at most one import in flight: the one of the previous half-sweep is long done (a whole chain of bond updates ago),
     // and with it every read of the receive buffer that the caller is about to reuse
     T4A_HIP(hipStreamSynchronize(import_stream_));
-    static const bool import_hostsync = diag_env("T4A_IMPORT_HOSTSYNC") != nullptr; // (diagnosis: the host waits for the producer, no event)
-    if (import_hostsync) {
-        T4A_HIP(hipStreamSynchronize(producer));
-    } else {
-        if (!import_event_) T4A_HIP(hipEventCreateWithFlags(&import_event_, hipEventDisableTiming));
-        T4A_HIP(hipEventRecord(import_event_, producer));
-        T4A_HIP(hipStreamWaitEvent(import_stream_, import_event_, 0));
-    }
+    if (!import_event_) T4A_HIP(hipEventCreateWithFlags(&import_event_, hipEventDisableTiming));
+    T4A_HIP(hipEventRecord(import_event_, producer));
+    T4A_HIP(hipStreamWaitEvent(import_stream_, import_event_, 0));
     for (size_t s = 0; s < n_; ++s) {
         const size_t r = s % shard_world;
         if (r == shard_rank) continue;
@@ -1838,8 +1785,7 @@ void Tci2::opt_begin(OptRun& r)
         std::vector<size_t> lb(n_ + 1, 1), rb(n_ + 1, 1);
         for (size_t b = 0; b < n_; ++b) lb[b + 1] = std::min(chi, lb[b] * local_dims[b]);
         for (size_t b = n_; b-- > 0;) rb[b] = std::min(chi, rb[b + 1] * local_dims[b]);
-        static const bool old_presize = diag_env("T4A_OLD_PRESIZE") != nullptr; // (debug: every bond at chi)
-        auto bond = [&](size_t b) { return old_presize ? chi : std::min(lb[b], rb[b]); }; // bond b sits left of site b
+        auto bond = [&](size_t b) { return std::min(lb[b], rb[b]); }; // bond b sits left of site b
         size_t totA = 0, totB = 0, tot_cores = 0;
         for (size_t b = 0; b < n_; ++b) {
             if (shard_world > 1 && (b % shard_world) != shard_rank) continue;
@@ -1929,20 +1875,10 @@ bool Tci2::opt_iter_start(OptRun& r, bool defer_launch)
             invalidate_fill_cache();
         }
         const bool fill_ahead = fn_kind_ == FnKind::Builtin && options.pivot_search == 0;
-        // a fill deferred by the previous iteration is issued from the hook of the 9th bond of this half-sweep (the
-        // first kernels that are long enough to hide the host work); shorter chains: from the last bond
-        const size_t nb_ = n_ - 1;
-        static const int defer_k = diag_env("T4A_FILL_DEFER") ? std::atoi(diag_env("T4A_FILL_DEFER")) : 8;
-        const size_t want_k = defer_k > 0 ? (size_t)defer_k : 8;
-        const size_t flush_k = nb_ > want_k + 1 ? want_k : nb_ - 1;
-        const size_t flush_at_fwd = flush_k, flush_at_bwd = nb_ - 1 - flush_k;
-        flush_deferred_fill();
         // built-in functor, full pivot search: the whole half-sweep is enqueued at once (tci2_chain.hip) ...
         r.is_forward = is_forward;
         r.ext_idx = ext_idx;
         r.fill_ahead = fill_ahead;
-        r.flush_at_fwd = flush_at_fwd;
-        r.flush_at_bwd = flush_at_bwd;
         {
             OptSeg seg_(2);
             r.chained = chain_enqueue(is_forward, options, ext_idx, true, !defer_launch);
@@ -1981,7 +1917,6 @@ void Tci2::opt_iter_finish(OptRun& r)
     const double norm = r.norm, abs_tol = r.abs_tol;
     const bool is_forward = r.is_forward, chained = r.chained, fill_ahead = r.fill_ahead;
     const long ext_idx = r.ext_idx;
-    const size_t flush_at_fwd = r.flush_at_fwd, flush_at_bwd = r.flush_at_bwd;
     do { // (one pass; `break` = the convergence exit of the reference's loop)
         {
             OptSeg seg_(3);
@@ -2010,7 +1945,6 @@ void Tci2::opt_iter_finish(OptRun& r)
                     prefetch_.extra = prefetch_.wanted ? &extra_j[b + 1] : nullptr;
                     // site b-1 only reads I_{b-1}, J_{b-1}, I_b: final since bond b-1 (forward bonds write I_{b+1}, J_b)
                     prefetch_.fill_site = (fill_ahead && b >= 1) ? (long)(b - 1) : -1;
-                    prefetch_.flush_fill = (b == flush_at_fwd);
                     update_pivots(b, true, options, extra_i[b + 1], extra_j[b]);
                 }
             } else {
@@ -2022,7 +1956,6 @@ void Tci2::opt_iter_finish(OptRun& r)
                     prefetch_.extra = prefetch_.wanted ? &extra_i[b] : nullptr;
                     // site b+2 reads I_{b+2}, J_{b+2}, I_{b+3}: final since bond b+1 (backward bonds write I_{b+1}, J_b)
                     prefetch_.fill_site = (fill_ahead && b + 2 < n_) ? (long)(b + 2) : -1;
-                    prefetch_.flush_fill = (b == flush_at_bwd);
                     update_pivots(b, false, options, extra_i[b + 1], extra_j[b]);
                 }
             }
@@ -2031,7 +1964,6 @@ void Tci2::opt_iter_finish(OptRun& r)
         prefetch_.fill_site = -1;
         prep_.valid = false;
         // the cores are not needed by the next half-sweep unless the global pivot search evaluates the TT
-        flush_deferred_fill(); // (normally already gone; guarantees the order of consecutive fills)
         const bool fill_async = options.nsearch == 0 && !options.strictly_nested;
         if (chained && chain_.digits_stale && fill_async) {
             // this fill's accumulators (out of the mirror), descriptors and launches go out after the NEXT iteration's chain
@@ -2039,7 +1971,6 @@ void Tci2::opt_iter_finish(OptRun& r)
             r.pending_fill = true;
         } else {
             fill_cache_trusted_ = fill_ahead && !chained;
-            fill_defer_requested_ = fill_ahead && !chained && iter + 1 < options.max_iter;
             fill_no_main_sync_ = chained && chain_.digits_stale;
             fill_site_tensors_impl(fill_async);
         }
@@ -2085,7 +2016,6 @@ void Tci2::opt_end(OptRun& r)
     opt_end_issue_fill(r);
     // the cores of the last iteration are complete (deferred solve errors surface here); in pipelined mode the wait
     // is left to the first reader (site_tensor*, evaluate, export_site_tensors_async, the next fill)
-    flush_deferred_fill();
     if (!keep_site_tensors || final_sweep1site) fill_wait();
     if (final_sweep1site) { // :1781-1794
         const double norm = (options.normalize_error && max_sample_value > 0.0) ? max_sample_value : 1.0;

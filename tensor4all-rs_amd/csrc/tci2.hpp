@@ -96,7 +96,6 @@ public:
         double norm = 1.0, abs_tol = 0.0;
         bool is_forward = true, chained = false, fill_ahead = false;
         long ext_idx = -1;
-        size_t flush_at_fwd = 0, flush_at_bwd = 0;
         // small-problem engine (tci2_small.hip): offered every run unless the caller drives several handles in lock-step
         bool allow_small = true;
         bool small_complete = false; // the engine finished the whole call (iterations and, when asked for, the final 1-site sweep)
@@ -241,7 +240,6 @@ private:
         bool cols = false;
         const IndexSet* extra = nullptr;
         long fill_site = -1;        // a site whose I/J sets are already final: its fill accumulators can be built now
-        bool flush_fill = false;    // issue the stream operations of the previous half-sweep's (deferred) fill
     } prefetch_;
     // accumulators of fill_site_tensors (J_b, kron_i(b), I_{b+1}) built ahead of time, site by site, while the bond
     // updates of the same half-sweep are running; only valid inside optimize() between the bond loop and its fill
@@ -251,13 +249,9 @@ private:
     };
     std::vector<FillAcc> fill_cache_;
     bool fill_cache_trusted_ = false;
-    bool fill_defer_requested_ = false;
-    std::vector<std::function<void()>> fill_deferred_; // stream operations of a prepared, not yet issued fill
-    void flush_deferred_fill();
     void issue_fill_ops(std::vector<std::function<void()>>& ops, const std::vector<uint64_t>& sig);
-    std::vector<uint64_t> fill_deferred_sig_, fill_last_sig_, fill_graph_sig_;
+    std::vector<uint64_t> fill_last_sig_, fill_graph_sig_;
     hipGraphExec_t fill_graph_exec_ = nullptr;
-    std::vector<std::function<void()>> fill_pre_ops_; // (diagnosis switch T4A_FILL_GRAPH_NO_COPY)
     bool fill_graph_broken_ = false;
     void prepare_fill_site(size_t b);
     void invalidate_fill_cache();                    // set by the sweep loop: which side of which bond is independent of the current one

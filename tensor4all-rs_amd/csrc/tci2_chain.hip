@@ -498,13 +498,11 @@ void Tci2::chain_launch()
     const std::vector<size_t>& ind_ub = chain_.ind_ub;
     std::vector<unsigned>& tokens = chain_.tokens;
     hipStream_t st = eng.stream();
-    // result blocks reach the host in ONE copy behind the chain (T4A_CHAIN_HOST_MIRROR=1: every rrLU kernel mirrors its own block
-    // into pinned memory as it ends — stores over PCIe that the kernel's end has to wait for, once per bond)
-    static const bool per_launch_mirror = diag_env("T4A_CHAIN_HOST_MIRROR") != nullptr;
+    // result blocks reach the host in ONE copy behind the chain
     auto block_of = [&](size_t b) {
         ChainBlock k = proto;
         k.dev = chain_.blocks.get() + b * proto.bytes;
-        k.host = per_launch_mirror ? chain_.hblocks.get() + b * proto.bytes : nullptr;
+        k.host = nullptr;
         return k;
     };
     {
@@ -518,13 +516,12 @@ void Tci2::chain_launch()
     try {
         chain_indep_launch(c, (int)nb, st);
         unsigned* tile_counters = reinterpret_cast<unsigned*>(chain_.dims.get() + nb * 4);
-        static const bool no_spec = diag_env("T4A_CHAIN_NO_SPEC") != nullptr;
-        const bool solo = g_chains_inflight.fetch_add(1) == 0 && !no_spec;
+        const bool solo = g_chains_inflight.fetch_add(1) == 0;
         counted = true;
         // every matrix of the half-sweep fits the one-wave kernel: ONE persistent workgroup walks the bonds (kernels_chain.hip)
         static const bool no_walk = std::getenv("T4A_NO_WALK") != nullptr;
         size_t walk_cols = 0;
-        bool walk = !no_walk && !timed_events && !per_launch_mirror && nb <= 128; // (128: WALK_MAX_BONDS, kernels_chain.hip)
+        bool walk = !no_walk && !timed_events && nb <= 128; // (128: WALK_MAX_BONDS, kernels_chain.hip)
         for (size_t b = 0; walk && b < nb; ++b) {
             walk = dep_ub[b] <= 64 && ind_ub[b] <= 32; // (wider: the launched chain's one-workgroup kernel beats one wave)
             walk_cols = std::max(walk_cols, ind_ub[b]);
@@ -549,8 +546,7 @@ void Tci2::chain_launch()
             w.token_base = chain_.walk_token;
             chain_.walk_token += (unsigned)nb;
             w.timed = chain_.timed ? 1 : 0;
-            static const bool old_prep = diag_env("T4A_WALK_OLD_PREP") != nullptr;
-            w.lean_prep = old_prep ? 0 : 1;
+            w.lean_prep = 1;
             static const bool walk_dbg = std::getenv("T4A_WALK_DEBUG") != nullptr;
             if (walk_dbg) {
                 chain_.walk_dbg.reserve(8);
@@ -562,10 +558,6 @@ void Tci2::chain_launch()
             chain_walk_launch(c, fn_dev_, w, (int)walk_cols, st);
             ++chain_stats_ext[0];
         }
-        // T4A_CHAIN_DEFER_MIRROR=1: the launched chain's preparations leave the pinned mirrors alone and one bulk copy follows the
-        // chain (measured: 21.44 against 21.39 ms per cfg3 sweep — the stores over PCIe are not what a preparation's 8.6 us consist
-        // of, and the extra launch costs what they cost; the persistent half-sweep always copies in bulk)
-        static const bool defer_mirror = diag_env("T4A_CHAIN_DEFER_MIRROR") != nullptr;
         static const bool want_prep_dbg = std::getenv("T4A_PREP_DEBUG") != nullptr; // phase times of the preparation kernels of this chain
         unsigned long long* prep_dbg = nullptr;
         if (want_prep_dbg && !walk) {
@@ -586,7 +578,7 @@ void Tci2::chain_launch()
             pa.b = (int)b;
             pa.do_build = 1;
             pa.dbg = prep_dbg;
-            pa.defer_host_writes = defer_mirror ? 1 : 0;
+            pa.defer_host_writes = 0;
             pa.with_rowmap = spec_here ? 1 : 0;
             pa.prev_b = -1;
             if (k > 0) {
@@ -643,18 +635,16 @@ void Tci2::chain_launch()
             ChainPrepArgs pa;
             std::memset(&pa, 0, sizeof(pa));
             pa.do_build = 0;
-            pa.defer_host_writes = defer_mirror ? 1 : 0;
+            pa.defer_host_writes = 0;
             pa.prev_b = (int)pb;
             pa.prev_iresult = reinterpret_cast<const int*>(pblk.dev + 16);
             pa.prev_rowperm = reinterpret_cast<const int*>(pblk.dev + pblk.off_rp);
             pa.prev_colperm = reinterpret_cast<const int*>(pblk.dev + pblk.off_cp);
             pa.prev_token = tokens[pb];
             chain_prep_launch(c, pa, st);
-            if (defer_mirror) chain_mirror_launch(c, (int)nb, st);
         }
         chain_.cores_batched = false;
-        static const bool no_batched_cores = diag_env("T4A_NO_BATCHED_CORES") != nullptr;
-        if (chain_.one_site && chain_.factors_stride && forward && !no_batched_cores && nb <= (size_t)LUCI_LEFT_CORES_MAX_JOBS) {
+        if (chain_.one_site && chain_.factors_stride && forward && nb <= (size_t)LUCI_LEFT_CORES_MAX_JOBS) {
             // the site tensors of every bond of rank <= 16 in one launch behind the chain (kernels_dense.hip): shapes, ranks and
             // permutations are read where the chain left them; the buffers are sized for the upper bounds
             LeftCoreJobs jobs;
@@ -679,8 +669,7 @@ void Tci2::chain_launch()
             chain_.cores_batched = true;
         }
         chain_.last_core_launched = false;
-        static const bool no_last_core = diag_env("T4A_NO_CHAIN_LAST_CORE") != nullptr;
-        if (chain_.one_site && chain_.factors_stride && forward && !no_last_core) {
+        if (chain_.one_site && chain_.factors_stride && forward) {
             // ... and the last site's tensor (tensorci2.rs:902-912): I_{n-1} is final behind the last bond; evaluated from the tables, no
             // host round trip (accumulators built on the host, staged, evaluated, packed, synchronised: ~50 us of a small solve)
             const size_t last = n_ - 1;
@@ -692,8 +681,7 @@ void Tci2::chain_launch()
                 chain_.last_core_launched = true;
             }
         }
-        if (!per_launch_mirror)
-            T4A_HIP(hipMemcpyAsync(chain_.hblocks.get(), chain_.blocks.get(), nb * proto.bytes, hipMemcpyDeviceToHost, st));
+        T4A_HIP(hipMemcpyAsync(chain_.hblocks.get(), chain_.blocks.get(), nb * proto.bytes, hipMemcpyDeviceToHost, st));
         T4A_HIP(hipGetLastError());
     } catch (...) {
         (void)hipStreamSynchronize(st);
@@ -716,10 +704,9 @@ void Tci2::chain_launch()
 // kernels, same order.
 void Tci2::chain_group_launch(const std::vector<Tci2*>& hs)
 {
-    static const bool no_group = diag_env("T4A_CHAIN_NO_GROUP") != nullptr;
     const size_t nh = hs.size();
     if (nh == 0) return;
-    bool ok = nh >= 2 && nh <= (size_t)CHAIN_GROUP_MAX && !no_group;
+    bool ok = nh >= 2 && nh <= (size_t)CHAIN_GROUP_MAX;
     Tci2* lead = hs[0];
     for (Tci2* h : hs) {
         if (!h->chain_.prepared) throw Error(T4A_GPU_INTERNAL_ERROR, "bond chain: a handle of the group has nothing prepared");
@@ -778,11 +765,10 @@ void Tci2::chain_group_launch(const std::vector<Tci2*>& hs)
         const ChainGroupSlot* d_slots = lead->chain_.gslots.get();
         lead->eng.chain_group_lock();
         locked = true;
-        static const bool per_launch_mirror = diag_env("T4A_CHAIN_HOST_MIRROR") != nullptr;
         auto block_of = [&](Tci2* h, size_t b) {
             ChainBlock k = h->chain_.proto;
             k.dev = h->chain_.blocks.get() + b * k.bytes;
-            k.host = per_launch_mirror ? h->chain_.hblocks.get() + b * k.bytes : nullptr;
+            k.host = nullptr;
             return k;
         };
         auto prev_of = [&](Tci2* h, size_t pb, ChainPrepArgs& pa) {
@@ -824,9 +810,8 @@ void Tci2::chain_group_launch(const std::vector<Tci2*>& hs)
             for (size_t i = 0; i < nh; ++i) prev_of(hs[i], order[nb - 1], pg.a[i]);
             chain_prep_group_launch(d_slots, pg, (int)nh, st);
         }
-        if (!per_launch_mirror)
-            for (Tci2* h : hs)
-                T4A_HIP(hipMemcpyAsync(h->chain_.hblocks.get(), h->chain_.blocks.get(), nb * h->chain_.proto.bytes, hipMemcpyDeviceToHost, st));
+        for (Tci2* h : hs)
+            T4A_HIP(hipMemcpyAsync(h->chain_.hblocks.get(), h->chain_.blocks.get(), nb * h->chain_.proto.bytes, hipMemcpyDeviceToHost, st));
         T4A_HIP(hipGetLastError());
     } catch (...) {
         (void)hipStreamSynchronize(st);
@@ -1119,7 +1104,6 @@ void Tci2::chain_finish(const TCI2Options& options)
     prep_.valid = false;
     prefetch_.wanted = false;
     prefetch_.fill_site = -1;
-    prefetch_.flush_fill = false;
     invalidate_fill_cache();
     std::vector<IndexSet> no_i(n_), no_j(n_);
     for (size_t p = 0; p < n_; ++p) {

@@ -79,8 +79,7 @@ def version():
 
 
 def diag_switches_enabled():
-    """True when the loaded library was built with -DT4A_DIAG_SWITCHES (the experiment switches of tools/ are read from the environment);
-    on a production build they are no-ops and an A/B arm labelled with one measures the default path."""
+    """Always False: the library has no experiment switches (kept for callers of the earlier API)."""
     _lib.t4a_gpu_diag_switches_enabled.restype = ctypes.c_int32
     return bool(_lib.t4a_gpu_diag_switches_enabled())
 

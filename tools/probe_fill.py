@@ -1,5 +1,5 @@
 """fill_site_tensors alone (no bond chain beside it) on a saturated handle: wall time per call (the call returns after the device has
-finished) for BASELINE configs[2] (d = 30, chi = 256) and configs[3] (d = 40, chi = 512).  T4A_NO_FUSED_SOLVE=1: the two-step path."""
+finished) for BASELINE configs[2] (d = 30, chi = 256) and configs[3] (d = 40, chi = 512)."""
 import sys
 import time
 sys.path.insert(0, "tensor4all-rs_amd/python")

@@ -1,6 +1,6 @@
 """One-wave and one-workgroup rrLU kernels against what would run without them (T4A_NO_W1=1, T4A_NO_WG=1): time per pivot step as
 the SLOPE between a factorisation capped at r and one capped at r / 2 steps (the fixed cost of a call drops out), digests of all.
-Usage: python tools/probe_wg.py [M N r]...   (T4A_WG_MAXV=96 lifts the plan limit of the one-workgroup kernel)"""
+Usage: python tools/probe_wg.py [M N r]..."""
 import hashlib
 import os
 import subprocess
