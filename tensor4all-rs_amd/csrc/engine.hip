@@ -57,21 +57,137 @@ void xcd_disable()
                              "timed out); the chip-wide kernels take over\n");
 }
 
-// The single-XCD kernel is kernels_rrlu_xcd2.hip (the first generation was retired in round 6).  A launch that meets non-finite values
-// gives up with code 2; the caller then runs the chip-wide kernels for that matrix (they implement the NaN-incumbent rule).
-int xcd_version() { return 2; }
-void rrlu_xcd_launch_v(int version, const RrluXcdPlan& plan, const RrluXcdArgs& args, hipStream_t stream)
+// ---- rrLU routes ----
+namespace {
+// the rrLU switches, read once: T4A_RRLU_IMPL=lds|global|reg forces that chip-wide kernel; matrices of at most T4A_WG_MIN entries
+// (default 64) skip the one-wave / one-workgroup kernels
+struct RrluEnv {
+    bool force_lds, force_global, force_reg;
+    long wg_min;
+};
+const RrluEnv& rrlu_env()
 {
-    if (plan.wg == 2) rrlu_w1_launch(plan, args, stream);
-    else if (plan.wg) rrlu_wg_launch(plan, args, stream);
-    else if (plan.big()) rrlu_xcd2m_launch(plan, args, stream); // (second generation only: rrlu_xcd_make_plan hands such plans out with allow_big)
-    else rrlu_xcd2_launch(plan, args, stream);
+    static const char* impl = std::getenv("T4A_RRLU_IMPL");
+    static const RrluEnv env = {impl && !std::strcmp(impl, "lds"), impl && !std::strcmp(impl, "global"), impl && !std::strcmp(impl, "reg"),
+                                std::getenv("T4A_WG_MIN") ? std::atol(std::getenv("T4A_WG_MIN")) : 64};
+    return env;
 }
-void rrlu_xcd_group_launch_v(int version, const RrluXcdPlan& plan, const RrluXcdGroupArgs& args, bool tie_row_major, hipStream_t stream)
+void acquire_for(XcdArbiter::Lock& lock, RrluLock scope, int xcc)
 {
-    if (plan.wg == 2) rrlu_w1_group_launch(plan, args, tie_row_major, stream);
-    else if (plan.wg) rrlu_wg_group_launch(plan, args, tie_row_major, stream);
-    else rrlu_xcd2_group_launch(plan, args, tie_row_major, stream);
+    if (scope != RrluLock::None) lock.acquire(scope == RrluLock::Chip ? -1 : xcc);
+}
+// the RrluRegArgs of a host launch, except what the caller sets: Aout, the salt and key tables, poll_delay, stamps, the done / dev
+// tokens, the fused accumulators, dims and rowmap (zero here)
+void reg_args(RrluRegArgs& a, const RrluRoute& rt, bool left, const double* A, int max_steps, double rel_tol, double abs_tol, const RrluBlock& blk)
+{
+    std::memset(&a, 0, sizeof(a));
+    a.A = A;
+    a.M = rt.kM;
+    a.N = rt.kN;
+    a.max_steps = max_steps;
+    a.rel_tol = rel_tol;
+    a.abs_tol = abs_tol;
+    a.tie_row_major = left ? 0 : 1;
+    a.out_transposed = left ? 0 : 1;
+    a.W = rt.reg.W;
+    a.TR = rt.reg.TR;
+    a.TC = rt.reg.TC;
+    a.row_perm = left ? blk.row_perm() : blk.col_perm();
+    a.col_perm = left ? blk.col_perm() : blk.row_perm();
+    a.iresult = blk.iresult();
+    a.dresult = blk.dresult();
+    a.pivot_vals = blk.pivot_vals();
+    a.ncopy = 1;
+    a.spec = 2;
+    a.spec_frac = 0.8;
+    a.key16 = 1; // bit 0: 16-byte key loads, bit 1: 16-byte key store
+    a.spin_limit = 1u << 20;
+    a.h_block = reinterpret_cast<unsigned long long*>(blk.host);
+    a.block_u64 = (int)(blk.bytes / 8);
+    a.ts_u64 = (int)(blk.off_ts / 8);
+}
+} // namespace
+
+RrluRoute RrluRoute::of_xcd(const RrluXcdPlan& plan, int kM, int kN)
+{
+    RrluRoute rt;
+    rt.kind = plan.wg == 2 ? RrluKind::OneWave : plan.wg ? RrluKind::OneWorkgroup : plan.big() ? RrluKind::MultiXcd : RrluKind::SingleXcd;
+    rt.xcd = plan;
+    rt.kM = kM;
+    rt.kN = kN;
+    return rt;
+}
+RrluRoute RrluRoute::of_reg(const RrluRegPlan& plan, int kM, int kN)
+{
+    RrluRoute rt;
+    rt.kind = RrluKind::Reg;
+    rt.reg = plan;
+    rt.kM = kM;
+    rt.kN = kN;
+    rt.fused = plan.RPT * plan.CPT <= RRLU_FUSED_MAX_VALUES;
+    return rt;
+}
+int RrluRoute::code(bool tie_row_major, bool saturated) const
+{
+    const int tie = tie_row_major ? 4 : 0, sat = saturated ? 10000000 : 0;
+    switch (kind) {
+    case RrluKind::OneWave: return sat + 300000 + xcd.RPT * 1000 + xcd.CPT * 10 + tie;
+    case RrluKind::OneWorkgroup: return sat + 200000 + xcd.RPT * 1000 + xcd.CPT * 10 + tie;
+    case RrluKind::SingleXcd: return sat + 100000 + xcd.RPT * 100 + xcd.CPT * 10 + tie;
+    case RrluKind::MultiXcd: return sat + 400000 + xcd.K * 10000 + xcd.RPT * 100 + xcd.CPT * 10 + tie;
+    case RrluKind::Reg: return sat + reg.RPT * 1000 + reg.CPT * 10 + tie + (reg.W == 1 ? 2 : 0) + ((reg.TR % 64) == 0 ? 1 : 0);
+    case RrluKind::Lds: return sat + (lds.W == 1 ? -1 : -2);
+    case RrluKind::Global: return sat - 3;
+    default: return 0;
+    }
+}
+RrluLock RrluRoute::lock() const
+{
+    switch (kind) {
+    case RrluKind::OneWave:
+    case RrluKind::OneWorkgroup:
+    case RrluKind::SingleXcd:
+    case RrluKind::MultiXcd:
+        // a launch has 8 W workgroups of which 7 W pass through the other XCDs and need a free compute unit there for a moment:
+        // two handles that each fill (nearly) all 32 compute units of their XCD would block each other's dispatch
+        return xcd.W > kXcdSharedMaxW || xcd.K > 1 ? RrluLock::Chip : RrluLock::Xcd;
+    case RrluKind::Reg: return reg.W > 1 ? RrluLock::Chip : RrluLock::None;
+    case RrluKind::Lds: return lds.W > 1 ? RrluLock::Chip : RrluLock::None;
+    default: return RrluLock::None;
+    }
+}
+size_t RrluRoute::xcd_mailbox_words() const { return (rrlu_xcd_keys_bytes(xcd) + rrlu_xcd_cols_bytes(xcd, kM)) / sizeof(unsigned long long); }
+// A launch of the single-XCD family that meets non-finite values gives up with code 2; luci then runs the chip-wide kernels for
+// that matrix (they implement the NaN-incumbent rule).
+void RrluRoute::launch(const RrluXcdArgs& args, hipStream_t stream) const
+{
+    switch (kind) {
+    case RrluKind::OneWave: rrlu_w1_launch(xcd, args, stream); break;
+    case RrluKind::OneWorkgroup: rrlu_wg_launch(xcd, args, stream); break;
+    case RrluKind::SingleXcd: rrlu_xcd2_launch(xcd, args, stream); break;
+    case RrluKind::MultiXcd: rrlu_xcd2m_launch(xcd, args, stream); break;
+    default: throw Error(T4A_GPU_INTERNAL_ERROR, "rrLU: the route has no single-XCD launch");
+    }
+}
+void RrluRoute::launch_group(const RrluXcdGroupArgs& args, bool tie_row_major, hipStream_t stream) const
+{
+    switch (kind) {
+    case RrluKind::OneWave: rrlu_w1_group_launch(xcd, args, tie_row_major, stream); break;
+    case RrluKind::OneWorkgroup: rrlu_wg_group_launch(xcd, args, tie_row_major, stream); break;
+    case RrluKind::SingleXcd: rrlu_xcd2_group_launch(xcd, args, tie_row_major, stream); break;
+    default: throw Error(T4A_GPU_INTERNAL_ERROR, "rrLU: the route has no group launch");
+    }
+}
+
+RrluBlock RrluBlock::layout(size_t max_steps, size_t M, size_t N, bool with_timestamps)
+{
+    RrluBlock b;
+    b.off_rp = b.off_piv + sizeof(double) * std::max<size_t>(max_steps, 1);
+    b.off_cp = b.off_rp + sizeof(int) * M;
+    const size_t end = (b.off_cp + sizeof(int) * N + 7) / 8 * 8;
+    b.off_ts = with_timestamps ? end : 0;
+    b.bytes = with_timestamps ? end + 16 : end;
+    return b;
 }
 
 // Placement census (once per process, first Engine): the single-XCD kernel assumes that workgroup b of a grid lands on XCD
@@ -226,6 +342,69 @@ Engine::~Engine()
     if (stream_) pool::stream_put(stream_, 1); // (synchronises it)
 }
 
+namespace {
+int chain_max_steps(const RrluRoute& rt, size_t max_bond_dim)
+{
+    const int mn = rt.kM < rt.kN ? rt.kM : rt.kN;
+    return max_bond_dim < (size_t)mn ? (int)max_bond_dim : mn;
+}
+// T4A_RRLU_STAMPS: the per-phase cycle stamps of one launch (hs: the 24 stamp words, steps: the pivot steps it took)
+void print_stamps(const RrluRoute& rt, int M, int N, int steps, const unsigned long long* hs)
+{
+    const double st = steps > 0 ? (double)steps : 1.0;
+    switch (rt.kind) {
+    case RrluKind::OneWave:
+        std::fprintf(stderr, "[rrlu stamps w1] M=%d N=%d columns=%d steps=%d cycles/step: search=%.0f stop+divide+clear=%.0f tables=%.0f update=%.0f | launch (cycles): "
+                             "load+init=%llu steps=%llu write-out=%llu | shader clock %.0f MHz\n",
+                     M, N, rt.xcd.CPT, steps, hs[0] / st, hs[1] / st, hs[2] / st, hs[3] / st, hs[16], hs[17], hs[18], hs[21] ? 100.0 * (double)hs[20] / (double)hs[21] : 0.0);
+        break;
+    case RrluKind::OneWorkgroup:
+    case RrluKind::SingleXcd:
+    case RrluKind::MultiXcd:
+        std::fprintf(stderr, "[rrlu stamps xcd] M=%d N=%d W=%d steps=%d cycles/step: pass=%.0f search=%.0f publish=%.0f | prefetch=%.0f keys=%.0f pick=%.0f slow+stop=%.0f recwr=%.0f barB=%.0f | record=%.0f "
+                             "tables+u=%.0f colwait=%.0f divide=%.0f barC=%.0f lread=%.0f | pollspins=%llu | launch (cycles): election=%llu load+init=%llu steps=%llu write-out=%llu\n",
+                     M, N, rt.xcd.W, steps, hs[0] / st, hs[1] / st, hs[2] / st, hs[6] / st, hs[8] / st, hs[14] / st, hs[15] / st, hs[9] / st, hs[3] / st, hs[10] / st, hs[11] / st, hs[12] / st,
+                     hs[4] / st, hs[13] / st, hs[7] / st, hs[5], hs[16], hs[17], hs[18], hs[19]);
+        break;
+    default: {
+        const bool reg = rt.kind == RrluKind::Reg;
+        const int W = reg ? rt.reg.W : rt.kind == RrluKind::Lds ? rt.lds.W : rrlu_global_blocks(M, N);
+        const int T = reg ? rt.reg.T : rt.kind == RrluKind::Lds ? rt.lds.T : 256;
+        std::fprintf(stderr, "[rrlu stamps %s] M=%d N=%d W=%d T=%d steps=%d | s0=%llu s1=%llu s2=%llu s3=%llu s4=%llu pollspins=%llu colspins=%llu s7=%llu "
+                             "(cycles, wg0/thread0; lds: publish,poll,colfetch,pass,reduce; reg: pass,reduce,publish,poll,fetch)\n",
+                     reg ? "reg" : "lds", M, N, W, T, steps, hs[0], hs[1], hs[2], hs[3], hs[4], hs[5], hs[6], hs[7]);
+    }
+    }
+}
+} // namespace
+
+// luci's policy: T4A_RRLU_IMPL forces a chip-wide kernel; otherwise the one-wave / one-workgroup kernels above T4A_WG_MIN entries,
+// then the single-XCD family (disabled for good once a launch timed out), then the chip-wide register, LDS and HBM-resident
+// kernels.  A retry after non-finite values skips the single-XCD family: its kernels hand such matrices back, the chip-wide ones
+// implement the NaN-incumbent rule.
+RrluRoute Engine::luci_route(int M, int N, bool left) const
+{
+    const RrluEnv& env = rrlu_env();
+    // the register- and LDS-resident kernels pack positions into 16 bits; larger matrices go to the HBM-resident kernel
+    const bool huge = M > 65535 || N > 65535;
+    const int kM = left ? M : N, kN = left ? N : M;
+    if (!huge && !env.force_lds && !env.force_global && !env.force_reg && !nonfinite_retry_) {
+        RrluXcdPlan xplan;
+        if ((long)kM * kN > env.wg_min && (rrlu_w1_make_plan(kM, kN, &xplan, 0) || rrlu_wg_make_plan(kM, kN, &xplan, 0)))
+            return RrluRoute::of_xcd(xplan, kM, kN);
+        if (!xcd_disabled() && (rrlu_xcd_make_plan(kM, kN, &xplan, false, xcd_plan_max_w()) || rrlu_xcd_make_plan(kM, kN, &xplan, false, 32, true)))
+            return RrluRoute::of_xcd(xplan, kM, kN);
+    }
+    RrluRegPlan rplan;
+    if (!huge && !env.force_lds && !env.force_global && rrlu_reg_make_plan(kM, kN, num_cus_, &rplan)) return RrluRoute::of_reg(rplan, kM, kN);
+    RrluRoute rt; // the LDS- and HBM-resident kernels take the matrix as it is
+    rt.kM = M;
+    rt.kN = N;
+    if (!huge && !env.force_global) rt.lds = rrlu_make_plan(M, N, num_cus_);
+    rt.kind = huge || env.force_global || rt.lds.lds_bytes > 160 * 1024 ? RrluKind::Global : RrluKind::Lds;
+    return rt;
+}
+
 LuciResult Engine::luci(const double* d_a, int M, int N, const RrLUOptions& opts, bool need_factors, bool want_lu_copy,
                         const FusedPi* fused)
 {
@@ -244,8 +423,6 @@ LuciResult Engine::luci(const double* d_a, int M, int N, const RrLUOptions& opts
         r.has_factors = need_factors;
         return r;
     }
-    // the register- and LDS-resident kernels pack positions into 16 bits; larger matrices go to the HBM-resident kernel
-    const bool huge = M > 65535 || N > 65535;
     if ((size_t)M * (size_t)N > ((size_t)1 << 33))
         throw Error(T4A_GPU_NOT_IMPLEMENTED, "rrLU: matrices with more than 2^33 entries are not supported");
 
@@ -254,21 +431,14 @@ LuciResult Engine::luci(const double* d_a, int M, int N, const RrLUOptions& opts
     if (ms > (size_t)N) ms = N;
     const int max_steps = (int)ms;
 
-    // one packed result block: [dresult 2 f64][iresult 4 i32][pivot_vals max_steps f64][row_perm M i32][col_perm N i32]
-    // -> one memset of the 32-byte header, one device-to-host copy per bond
-    const size_t off_piv = 32;
-    const size_t off_rp = off_piv + sizeof(double) * (size_t)(max_steps > 0 ? max_steps : 1);
-    const size_t off_cp = off_rp + sizeof(int) * (size_t)M;
-    const size_t out_bytes = (off_cp + sizeof(int) * (size_t)N + 7) / 8 * 8;
-    d_out_.reserve(out_bytes);
-    h_out_.reserve(out_bytes);
-    double* d_dres = reinterpret_cast<double*>(d_out_.get());
-    int* d_ires = reinterpret_cast<int*>(d_out_.get() + 16);
-    double* d_pivvals = reinterpret_cast<double*>(d_out_.get() + off_piv);
-    int* d_rowperm = reinterpret_cast<int*>(d_out_.get() + off_rp);
-    int* d_colperm = reinterpret_cast<int*>(d_out_.get() + off_cp);
-    d_rowperm_ptr_ = d_rowperm;
-    d_colperm_ptr_ = d_colperm;
+    // one packed result block -> one memset of the 32-byte header, one device-to-host copy per bond
+    RrluBlock blk = RrluBlock::layout(max_steps, M, N, false);
+    d_out_.reserve(blk.bytes);
+    h_out_.reserve(blk.bytes);
+    blk.dev = d_out_.get();
+    blk.host = h_out_.get();
+    d_rowperm_ptr_ = blk.row_perm();
+    d_colperm_ptr_ = blk.col_perm();
     const bool keep_lu = need_factors || want_lu_copy;
     if (keep_lu) d_lu_.reserve((size_t)M * N);
     // the register kernel resets the header at its end; everything else (first use, regrown buffer, LDS kernel, a launch
@@ -277,125 +447,63 @@ LuciResult Engine::luci(const double* d_a, int M, int N, const RrLUOptions& opts
     header_clean_ = false;
     if (!header_clean) T4A_HIP(hipMemsetAsync(d_out_.get(), 0, 32, stream_));
     static const bool want_stamps = std::getenv("T4A_RRLU_STAMPS") != nullptr;
-    static const bool force_lds = std::getenv("T4A_RRLU_IMPL") != nullptr && std::string(std::getenv("T4A_RRLU_IMPL")) == "lds";
-    static const bool force_global = std::getenv("T4A_RRLU_IMPL") != nullptr && std::string(std::getenv("T4A_RRLU_IMPL")) == "global";
     if (want_stamps) {
         d_stamps_.reserve(24);
         T4A_HIP(hipMemsetAsync(d_stamps_.get(), 0, 24 * sizeof(unsigned long long), stream_));
     }
 
-    // Fast path: register-resident kernel (left-orthogonal only).  A right-orthogonal factorisation is the
-    // left-orthogonal one of A^T with row-major tie order; rows/columns swap roles on the way out.
+    // The register kernels factorise left-orthogonally: a right-orthogonal factorisation is the left-orthogonal one of A^T with
+    // row-major tie order; rows/columns swap roles on the way out.
     const bool left = opts.left_orthogonal;
-    const int kM = left ? M : N, kN = left ? N : M;
-    RrluRegPlan rplan;
-    RrluXcdPlan xplan;
-    static const bool force_reg = std::getenv("T4A_RRLU_IMPL") != nullptr && std::string(std::getenv("T4A_RRLU_IMPL")) == "reg";
-    // first choice: all workgroups on one XCD (exchange through that XCD's L2); disabled for good once a launch timed out
-    // (a retry after non-finite values: none of the register kernels of this family — they hand such matrices back — but the chip-wide
-    // register / LDS / global kernels below, which implement the NaN-incumbent rule)
-    const int xcd_v = xcd_version();
-    // matrices that fit one workgroup: the LDS-exchange kernel (not on a retry after non-finite values: it does not handle them)
-    static const long wg_min = std::getenv("T4A_WG_MIN") ? std::atol(std::getenv("T4A_WG_MIN")) : 64;
-    const bool use_wg = !huge && !force_lds && !force_global && !force_reg && !xcd_retry_v1_ && (long)kM * kN > wg_min &&
-                        (rrlu_w1_make_plan(kM, kN, &xplan, 0) || rrlu_wg_make_plan(kM, kN, &xplan, 0));
-    const bool use_xcd = use_wg || (!huge && !force_lds && !force_global && !force_reg && !xcd_disabled() &&
-                         !xcd_retry_v1_ &&
-                         (rrlu_xcd_make_plan(kM, kN, &xplan, false, xcd_plan_max_w()) || rrlu_xcd_make_plan(kM, kN, &xplan, false, 32, true)));
-    const bool use_reg = !use_xcd && !huge && !force_lds && !force_global && rrlu_reg_make_plan(kM, kN, num_cus_, &rplan);
-    bool fuse = false;
+    const RrluRoute rt = luci_route(M, N, left);
+    const bool on_xcd = rt.on_xcd();
+    const bool fuse = fused && rt.fused;
     bool xcd_src_transposed = false;
-    if (fused) {
-        fuse = use_reg && rplan.RPT * rplan.CPT <= RRLU_FUSED_MAX_VALUES;
-        if (!fuse) { // this plan cannot build the matrix in registers: materialise it like the Π kernel would
-            const uint64_t* ra = fused->d_rowacc;
-            const uint64_t* ca = fused->d_colacc;
-            if (fused->host_resident) { // (the Π kernel re-reads accumulators many times: never over PCIe)
-                const size_t nr = (size_t)M * fused->fn.n_acc, nc = (size_t)N * fused->fn.n_acc;
-                d_accstage_.reserve(nr + nc);
-                stage_copy_launch(ra, d_accstage_.get(), nr, stream_);
-                stage_copy_launch(ca, d_accstage_.get() + nr, nc, stream_);
-                ra = d_accstage_.get();
-                ca = d_accstage_.get() + nr;
-            }
-            double* buf = pi((size_t)M * N);
-            if (use_xcd && !left) { // the kernel works on the transpose: evaluate it in that layout straight away
-                pi_eval_launch(fused->fn, ca, N, ra, M, buf, N, false, nullptr, stream_);
-                xcd_src_transposed = true;
-            } else {
-                pi_eval_launch(fused->fn, ra, M, ca, N, buf, M, false, nullptr, stream_);
-            }
-            d_a = buf;
+    if (fused && !fuse) { // this plan cannot build the matrix in registers: materialise it like the Π kernel would
+        const uint64_t* ra = fused->d_rowacc;
+        const uint64_t* ca = fused->d_colacc;
+        if (fused->host_resident) { // (the Π kernel re-reads accumulators many times: never over PCIe)
+            const size_t nr = (size_t)M * fused->fn.n_acc, nc = (size_t)N * fused->fn.n_acc;
+            d_accstage_.reserve(nr + nc);
+            stage_copy_launch(ra, d_accstage_.get(), nr, stream_);
+            stage_copy_launch(ca, d_accstage_.get() + nr, nc, stream_);
+            ra = d_accstage_.get();
+            ca = d_accstage_.get() + nr;
         }
+        double* buf = pi((size_t)M * N);
+        if (on_xcd && !left) { // the kernel works on the transpose: evaluate it in that layout straight away
+            pi_eval_launch(fused->fn, ca, N, ra, M, buf, N, false, nullptr, stream_);
+            xcd_src_transposed = true;
+        } else {
+            pi_eval_launch(fused->fn, ra, M, ca, N, buf, M, false, nullptr, stream_);
+        }
+        d_a = buf;
     }
-    int plan_W = 1, plan_T = 0, plan_code = 0;
-    bool mirrored = false;
+    const bool mirrored = on_xcd || rt.kind == RrluKind::Reg; // the kernel writes the pinned mirror of its result block itself
     unsigned spin_token = 0u; // non-zero: a single-workgroup launch that announces its completion in the pinned block
     if (prof.enabled) T4A_HIP(hipEventRecord(ev_rrlu_.a, stream_));
     XcdArbiter::Lock xcd_lock; // multi-workgroup persistent kernels need their compute units to themselves
-    if (use_xcd) {
+    if (on_xcd) {
         const double* src = d_a;
         if (!left && !xcd_src_transposed) {
             d_at_.reserve((size_t)M * N);
             transpose_launch(d_a, M, N, M, d_at_.get(), N, stream_);
             src = d_at_.get();
         }
-        const size_t need_keys = rrlu_xcd_keys_bytes(xplan) / sizeof(unsigned long long);
-        const size_t need_cols = rrlu_xcd_cols_bytes(xplan, kM) / sizeof(unsigned long long);
+        const size_t need = rt.xcd_mailbox_words();
+        if (need > d_xkeys_.cap || xcd_salt_ >= 65535u || !d_xticket_.get()) xcd_mailbox_clear(need, stream_);
         ++xcd_salt_;
-        if (need_keys + need_cols > d_xkeys_.cap || xcd_salt_ > 65535u || !d_xticket_.get()) {
-            // granules carry launch-salted tags: clear the mailbox (keys, then column slots) whenever it moves or the 16-bit
-            // salt wraps.  (Plans differ in where the column slots start; a stale granule of another plan still carries
-            // another launch's salt.)
-            d_xkeys_.reserve(need_keys + need_cols);
-            d_xticket_.reserve(16);
-            T4A_HIP(hipMemsetAsync(d_xkeys_.get(), 0, d_xkeys_.cap * sizeof(unsigned long long), stream_));
-            T4A_HIP(hipMemsetAsync(d_xticket_.get(), 0, 16 * sizeof(unsigned), stream_));
-            xcd_ticket_base_ = xcd_ticket_base_multi_ = 0;
-            xcd_salt_ = 1;
-        }
+        if (keep_lu) d_xurows_.reserve((size_t)(max_steps > 0 ? max_steps : 1) * rt.kN);
         RrluXcdArgs a;
-        a.A = src;
+        xcd_args(a, rt, left, src, max_steps, opts.rel_tol, opts.abs_tol, blk, xcc_);
         a.Aout = keep_lu ? d_lu_.get() : nullptr;
-        if (keep_lu) d_xurows_.reserve((size_t)(max_steps > 0 ? max_steps : 1) * kN);
         a.urows = keep_lu ? d_xurows_.get() : nullptr;
-        a.M = kM;
-        a.N = kN;
-        a.max_steps = max_steps;
-        a.rel_tol = opts.rel_tol;
-        a.abs_tol = opts.abs_tol;
-        a.tie_row_major = left ? 0 : 1;
-        a.out_transposed = left ? 0 : 1;
-        a.W = xplan.W;
-        a.xcc = xcc_;
-        xcd_take_tickets(xplan, a); // exactly grid / 8 workgroups of a launch land on one XCD (the one-workgroup kernel takes no tickets)
-        a.row_perm = left ? d_rowperm : d_colperm;
-        a.col_perm = left ? d_colperm : d_rowperm;
-        a.iresult = d_ires;
-        a.dresult = d_dres;
-        a.pivot_vals = d_pivvals;
-        a.keys = d_xkeys_.get();
-        a.salt = xcd_salt_;
-        a.spec_frac = 0.8;
         a.stamps = want_stamps ? d_stamps_.get() : nullptr;
         std::memset(h_out_.get(), 0, 32);
-        a.h_block = reinterpret_cast<unsigned long long*>(h_out_.get());
-        a.block_u64 = (int)(out_bytes / 8);
-        a.dims = nullptr;
-        a.dims_swap = 0;
-        a.rowmap = nullptr;
-        std::memset(&a.spec, 0, sizeof(a.spec));
-        a.ts_u64 = 0;
-        mirrored = true;
-        // a launch has 8 W workgroups of which 7 W pass through the other XCDs and need a free compute unit there for a moment:
-        // two handles that each fill (nearly) all 32 compute units of their XCD would block each other's dispatch
-        xcd_lock.acquire((xplan.W > kXcdSharedMaxW || xplan.K > 1) ? -1 : xcc_);
-        rrlu_xcd_launch_v(xcd_v, xplan, a, stream_);
-        plan_W = xplan.W;
-        plan_T = 512;
-        plan_code = (xplan.wg == 2 ? 300000 + xplan.RPT * 1000 : xplan.wg ? 200000 + xplan.RPT * 1000 : xplan.big() ? 400000 + xplan.K * 10000 + xplan.RPT * 100 : 100000 + xplan.RPT * 100) +
-                    xplan.CPT * 10 + (a.tie_row_major ? 4 : 0); // (the one-workgroup / one-wave kernels under their own codes)
-    } else if (use_reg) {
+        acquire_for(xcd_lock, rt.lock(), xcc_);
+        rt.launch(a, stream_);
+    } else if (rt.kind == RrluKind::Reg) {
+        const RrluRegPlan& rplan = rt.reg;
         const double* src = d_a;
         if (!left && !fuse) {
             d_at_.reserve((size_t)M * N);
@@ -411,7 +519,7 @@ LuciResult Engine::luci(const double* d_a, int M, int N, const RrLUOptions& opts
             // 16-bit salt wraps, so that no stale granule can ever match a live tag (no per-launch memset).
             // The key table exists twice: a launch polls one copy and clears the other one for its successor.
             const size_t need_keys = 2 * (rrlu_reg_keys_bytes(rplan) / sizeof(unsigned long long));
-            const size_t need_cols = rrlu_reg_cols_bytes(rplan, kM) / sizeof(unsigned long long);
+            const size_t need_cols = rrlu_reg_cols_bytes(rplan, rt.kM) / sizeof(unsigned long long);
             ++rrlu_salt_;
             if (need_keys > d_rkeys_.cap || need_cols > d_rcols_.cap || rrlu_salt_ > 65535u || !keys_clean_) {
                 d_rkeys_.reserve(2 * (size_t)(2 * 256 * 2)); // room for any W up to 256 in both copies
@@ -429,82 +537,44 @@ LuciResult Engine::luci(const double* d_a, int M, int N, const RrLUOptions& opts
             keys_ready = true;
         }
         RrluRegArgs a;
-        a.A = src;
+        reg_args(a, rt, left, src, max_steps, opts.rel_tol, opts.abs_tol, blk);
         a.Aout = keep_lu ? d_lu_.get() : nullptr;
-        a.M = kM;
-        a.N = kN;
-        a.max_steps = max_steps;
-        a.rel_tol = opts.rel_tol;
-        a.abs_tol = opts.abs_tol;
-        a.tie_row_major = left ? 0 : 1;
-        a.out_transposed = left ? 0 : 1;
-        a.W = rplan.W;
-        a.TR = rplan.TR;
-        a.TC = rplan.TC;
-        a.row_perm = left ? d_rowperm : d_colperm;
-        a.col_perm = left ? d_colperm : d_rowperm;
-        a.iresult = d_ires;
-        a.dresult = d_dres;
-        a.pivot_vals = d_pivvals;
         a.keys = keys_this;
         a.cols = d_rcols_.get();
         a.keys_next = keys_next;
         a.keys_next_u64 = keys_ready ? keys_half : 0;
         a.salt = rrlu_salt_;
-        a.col_delay = 0;
         // measured optimum of the poller's initial sleep: 12 units below ~100 workgroups, 14 above
         a.poll_delay = rplan.W > 100 ? 14 : 12;
-        a.ncopy = 1;
-        a.spec = 2;
-        a.spec_frac = 0.8;
-        a.key16 = 1; // bit 0: 16-byte key loads, bit 1: 16-byte key store
-        a.spin_limit = 1u << 20;
         a.stamps = want_stamps ? d_stamps_.get() : nullptr;
         // results land in the pinned mirror straight from the kernel: no device-to-host copy afterwards
         std::memset(h_out_.get(), 0, 32);
-        a.fused = fuse ? 1 : 0;
         if (fuse) { // the kernel's rows are the matrix rows (left) or the matrix columns (right-orthogonal = transposed)
+            a.fused = 1;
             a.rowacc = left ? fused->d_rowacc : fused->d_colacc;
             a.colacc = left ? fused->d_colacc : fused->d_rowacc;
             a.fn = fused->fn;
-        } else {
-            a.rowacc = nullptr;
-            a.colacc = nullptr;
-            std::memset(&a.fn, 0, sizeof(a.fn));
         }
-        a.h_block = reinterpret_cast<unsigned long long*>(h_out_.get());
-        a.block_u64 = (int)(out_bytes / 8);
-        a.done_token = 0u;
-        a.dims = nullptr;
-        a.dims_swap = 0;
-        a.dev_token = 0u;
-        a.rowmap = nullptr;
-        a.ts_u64 = 0;
         if (rplan.W == 1 && !prof.enabled) {
             if (++done_token_ == 0u) ++done_token_;
             a.done_token = done_token_;
             spin_token = done_token_;
         }
-        a.trace = nullptr;
 #ifdef T4A_RRLU_TRACE
         static const char* trace_file = std::getenv("T4A_RRLU_TRACE_FILE");
         const size_t trace_words = (size_t)rplan.W * (1 + 4 * (size_t)(max_steps + 1));
-        const bool tracing = trace_file && rplan.W > 1 && kM > 600 && trace_dumps_ >= 20 && trace_dumps_ < 24;
-        if (trace_file && rplan.W > 1 && kM > 600) ++trace_dumps_;
+        const bool tracing = trace_file && rplan.W > 1 && rt.kM > 600 && trace_dumps_ >= 20 && trace_dumps_ < 24;
+        if (trace_file && rplan.W > 1 && rt.kM > 600) ++trace_dumps_;
         if (tracing) {
             d_trace_.reserve(trace_words);
             T4A_HIP(hipMemsetAsync(d_trace_.get(), 0, trace_words * 8, stream_));
             a.trace = d_trace_.get();
         }
 #endif
-        mirrored = true;
         keys_clean_ = false; // becomes true again once the launch is known to have finished cleanly
-        if (rplan.W > 1) xcd_lock.acquire(-1); // chip-wide persistent launch: every XCD
+        acquire_for(xcd_lock, rt.lock(), xcc_);
         rrlu_reg_launch(rplan, a, stream_, true);
-        plan_W = rplan.W;
-        plan_T = rplan.T;
-        plan_code = rplan.RPT * 1000 + rplan.CPT * 10 + (a.tie_row_major ? 4 : 0) + (rplan.W == 1 ? 2 : 0) + ((rplan.TR % 64) == 0 ? 1 : 0);
-    } else if (huge || force_global || rrlu_make_plan(M, N, num_cus_).lds_bytes > 160 * 1024) {
+    } else if (rt.kind == RrluKind::Global) {
         // neither the register file nor the LDS of the chip holds this matrix: HBM-resident kernel pair per pivot step
         const int gb = rrlu_global_blocks(M, N);
         d_gints_.reserve(rrlu_global_int_words(M, N, gb));
@@ -518,17 +588,14 @@ LuciResult Engine::luci(const double* d_a, int M, int N, const RrLUOptions& opts
         a.rel_tol = opts.rel_tol;
         a.abs_tol = opts.abs_tol;
         a.left_orth = opts.left_orthogonal ? 1 : 0;
-        a.row_perm = d_rowperm;
-        a.col_perm = d_colperm;
-        a.iresult = d_ires;
-        a.dresult = d_dres;
-        a.pivot_vals = d_pivvals;
+        a.row_perm = blk.row_perm();
+        a.col_perm = blk.col_perm();
+        a.iresult = blk.iresult();
+        a.dresult = blk.dresult();
+        a.pivot_vals = blk.pivot_vals();
         rrlu_global_launch(a, d_gints_.get(), d_gdbls_.get(), stream_);
-        plan_W = gb;
-        plan_T = 256;
-        plan_code = -3; // HBM-resident kernel
     } else {
-        const RrluPlan plan = rrlu_make_plan(M, N, num_cus_);
+        const RrluPlan& plan = rt.lds;
         if (plan.W > 1) {
             d_keys_.reserve(rrlu_keys_bytes(plan) / sizeof(unsigned long long));
             d_cols_.reserve(rrlu_cols_bytes(plan, M) / sizeof(unsigned long long));
@@ -545,25 +612,22 @@ LuciResult Engine::luci(const double* d_a, int M, int N, const RrLUOptions& opts
         a.W = plan.W;
         a.cpw = plan.cpw;
         a.Mld = plan.Mld;
-        a.row_perm = d_rowperm;
-        a.col_perm = d_colperm;
-        a.iresult = d_ires;
-        a.dresult = d_dres;
-        a.pivot_vals = d_pivvals;
+        a.row_perm = blk.row_perm();
+        a.col_perm = blk.col_perm();
+        a.iresult = blk.iresult();
+        a.dresult = blk.dresult();
+        a.pivot_vals = blk.pivot_vals();
         a.keys = d_keys_.get();
         a.cols = d_cols_.get();
         a.spin_limit = 1u << 20;
         a.stamps = want_stamps ? d_stamps_.get() : nullptr;
-        if (plan.W > 1) xcd_lock.acquire(-1);
+        acquire_for(xcd_lock, rt.lock(), xcc_);
         rrlu_launch(plan, a, stream_);
-        plan_W = plan.W;
-        plan_T = plan.T;
-        plan_code = plan.W == 1 ? -1 : -2; // LDS kernel (single / multi workgroup)
     }
     T4A_HIP(hipGetLastError());
     if (prof.enabled) T4A_HIP(hipEventRecord(ev_rrlu_.b, stream_));
 
-    if (!mirrored) T4A_HIP(hipMemcpyAsync(h_out_.get(), d_out_.get(), out_bytes, hipMemcpyDeviceToHost, stream_));
+    if (!mirrored) T4A_HIP(hipMemcpyAsync(h_out_.get(), d_out_.get(), blk.bytes, hipMemcpyDeviceToHost, stream_));
     if (overlap_hook) { // the device is busy for the next ~millisecond: do the caller's independent host work now
         std::function<void()> hook;
         hook.swap(overlap_hook);
@@ -587,27 +651,26 @@ LuciResult Engine::luci(const double* d_a, int M, int N, const RrLUOptions& opts
     }
     if (!completed) T4A_HIP(hipStreamSynchronize(stream_));
     xcd_lock.release();
-    if (use_xcd && (xcd_v == 2 || use_wg) && reinterpret_cast<const int*>(h_out_.get() + 16)[1] == 2) {
+    if (on_xcd && reinterpret_cast<const int*>(h_out_.get() + 16)[1] == 2) {
         // the kernel met a NaN / an infinity (input or overflow): the chip-wide kernels implement the NaN-incumbent rule of
-        // matrixlu.rs:480-519 (the first-generation single-XCD kernel, kept for this case until round 5, is gone); every workgroup of the
-        // launch was elected normally, the tickets stay valid
+        // matrixlu.rs:480-519; every workgroup of the launch was elected normally, the tickets stay valid
         T4A_HIP(hipMemsetAsync(d_out_.get(), 0, 32, stream_));
         header_clean_ = false;
         {
             static const bool dbg = std::getenv("T4A_CHAIN_DEBUG") != nullptr;
-            if (dbg) std::fprintf(stderr, "[t4a luci] %d x %d: the %s kernel met non-finite values, re-running with the chip-wide kernels\n", M, N, use_wg ? "one-workgroup" : "single-XCD");
+            if (dbg) std::fprintf(stderr, "[t4a luci] %d x %d: the %s kernel met non-finite values, re-running with the chip-wide kernels\n", M, N, rt.xcd.wg ? "one-workgroup" : "single-XCD");
         }
-        xcd_retry_v1_ = true;
+        nonfinite_retry_ = true;
         try {
             LuciResult r1 = luci(d_a_in, M, N, opts, need_factors, want_lu_copy, fused);
-            xcd_retry_v1_ = false;
+            nonfinite_retry_ = false;
             return r1;
         } catch (...) {
-            xcd_retry_v1_ = false;
+            nonfinite_retry_ = false;
             throw;
         }
     }
-    if (use_xcd && (reinterpret_cast<const int*>(h_out_.get() + 16)[1] != 0 || reinterpret_cast<const int*>(h_out_.get() + 16)[3] != (int)xcd_salt_)) {
+    if (on_xcd && (reinterpret_cast<const int*>(h_out_.get() + 16)[1] != 0 || reinterpret_cast<const int*>(h_out_.get() + 16)[3] != (int)xcd_salt_)) {
         // the placement assumption of the single-XCD kernel did not hold (or another process holds the compute units):
         // never try it again in this process and run this factorisation with the chip-wide kernels
         xcd_disable();
@@ -619,30 +682,22 @@ LuciResult Engine::luci(const double* d_a, int M, int N, const RrLUOptions& opts
     }
 
 #ifdef T4A_RRLU_TRACE
-    if (mirrored && d_trace_.get() && std::getenv("T4A_RRLU_TRACE_FILE") && trace_dumps_ > 20 && trace_dumps_ <= 24 && plan_W > 1) {
-        const size_t words = (size_t)plan_W * (1 + 4 * (size_t)(max_steps + 1));
+    if (rt.kind == RrluKind::Reg && d_trace_.get() && std::getenv("T4A_RRLU_TRACE_FILE") && trace_dumps_ > 20 && trace_dumps_ <= 24 && rt.reg.W > 1) {
+        const size_t words = (size_t)rt.reg.W * (1 + 4 * (size_t)(max_steps + 1));
         std::vector<unsigned long long> ht(words);
         T4A_HIP(hipMemcpy(ht.data(), d_trace_.get(), words * 8, hipMemcpyDeviceToHost));
         if (FILE* f = std::fopen(std::getenv("T4A_RRLU_TRACE_FILE"), "ab")) {
-            const long long hdr[4] = {M, N, plan_W, max_steps};
+            const long long hdr[4] = {M, N, rt.reg.W, max_steps};
             std::fwrite(hdr, sizeof(hdr), 1, f);
             std::fwrite(ht.data(), 8, words, f);
             std::fclose(f);
         }
     }
 #endif
-    // host views of the packed block (hp: [4 + M + N] ints, hr: [2 + max_steps] doubles, as before)
-    std::vector<int>& hpv = h_ints_;
-    hpv.resize(4 + (size_t)M + N);
-    std::memcpy(hpv.data(), h_out_.get() + 16, 4 * sizeof(int));
-    std::memcpy(hpv.data() + 4, h_out_.get() + off_rp, sizeof(int) * (size_t)M);
-    std::memcpy(hpv.data() + 4 + M, h_out_.get() + off_cp, sizeof(int) * (size_t)N);
-    std::vector<double>& hrv = h_dbls_;
-    hrv.resize(2 + (size_t)(max_steps > 0 ? max_steps : 1));
-    std::memcpy(hrv.data(), h_out_.get(), 2 * sizeof(double));
-    std::memcpy(hrv.data() + 2, h_out_.get() + off_piv, sizeof(double) * (size_t)(max_steps > 0 ? max_steps : 1));
-    const int* hp = hpv.data();
-    const double* hr = hrv.data();
+    // the host mirror of the packed block: hp = iresult, hr = dresult, pivot values
+    const int* hp = reinterpret_cast<const int*>(h_out_.get() + 16);
+    const double* hr = reinterpret_cast<const double*>(h_out_.get());
+    const double* hpiv = reinterpret_cast<const double*>(h_out_.get() + blk.off_piv);
     float rrlu_ms_this = 0.f;
     if (prof.enabled) {
         T4A_HIP(hipEventElapsedTime(&rrlu_ms_this, ev_rrlu_.a, ev_rrlu_.b));
@@ -652,22 +707,7 @@ LuciResult Engine::luci(const double* d_a, int M, int N, const RrLUOptions& opts
     if (want_stamps) {
         unsigned long long hs[24];
         T4A_HIP(hipMemcpy(hs, d_stamps_.get(), sizeof(hs), hipMemcpyDeviceToHost));
-        if (use_xcd && xplan.wg == 2) {
-            const double st = hp[0] > 0 ? (double)hp[0] : 1.0;
-            std::fprintf(stderr, "[rrlu stamps w1] M=%d N=%d columns=%d steps=%d cycles/step: search=%.0f stop+divide+clear=%.0f tables=%.0f update=%.0f | launch (cycles): "
-                                 "load+init=%llu steps=%llu write-out=%llu | shader clock %.0f MHz\n",
-                         M, N, xplan.CPT, hp[0], hs[0] / st, hs[1] / st, hs[2] / st, hs[3] / st, hs[16], hs[17], hs[18], hs[21] ? 100.0 * (double)hs[20] / (double)hs[21] : 0.0);
-        } else if (use_xcd) {
-            const double st = hp[0] > 0 ? (double)hp[0] : 1.0;
-            std::fprintf(stderr, "[rrlu stamps xcd] M=%d N=%d W=%d steps=%d cycles/step: pass=%.0f search=%.0f publish=%.0f | prefetch=%.0f keys=%.0f pick=%.0f slow+stop=%.0f recwr=%.0f barB=%.0f | record=%.0f "
-                                 "tables+u=%.0f colwait=%.0f divide=%.0f barC=%.0f lread=%.0f | pollspins=%llu | launch (cycles): election=%llu load+init=%llu steps=%llu write-out=%llu\n",
-                         M, N, plan_W, hp[0], hs[0] / st, hs[1] / st, hs[2] / st, hs[6] / st, hs[8] / st, hs[14] / st, hs[15] / st, hs[9] / st, hs[3] / st, hs[10] / st, hs[11] / st, hs[12] / st,
-                         hs[4] / st, hs[13] / st, hs[7] / st, hs[5], hs[16], hs[17], hs[18], hs[19]);
-        } else {
-            std::fprintf(stderr, "[rrlu stamps %s] M=%d N=%d W=%d T=%d steps=%d | s0=%llu s1=%llu s2=%llu s3=%llu s4=%llu pollspins=%llu colspins=%llu s7=%llu "
-                                 "(cycles, wg0/thread0; lds: publish,poll,colfetch,pass,reduce; reg: pass,reduce,publish,poll,fetch)\n",
-                         use_reg ? "reg" : "lds", M, N, plan_W, plan_T, hp[0], hs[0], hs[1], hs[2], hs[3], hs[4], hs[5], hs[6], hs[7]);
-        }
+        print_stamps(rt, M, N, hp[0], hs);
     }
     if (hp[1] != 0)
         throw Error(T4A_GPU_KERNEL_TIMEOUT, "rrLU kernel: inter-workgroup hand-off timed out (bounded spin gave up)");
@@ -683,37 +723,13 @@ LuciResult Engine::luci(const double* d_a, int M, int N, const RrLUOptions& opts
     } else {
         r.last_error = hr[0];
     }
-    {
-        unsigned long long bits;
-        std::memcpy(&bits, &hr[1], sizeof(bits));
-        double am;
-        std::memcpy(&am, &bits, sizeof(am));
-        r.abs_max = am;
-    }
-    for (int i = 0; i < M; ++i) r.row_perm[i] = hp[4 + i];
-    for (int j = 0; j < N; ++j) r.col_perm[j] = hp[4 + M + j];
+    std::memcpy(&r.abs_max, &hr[1], sizeof(double)); // (the bits of max sqrt(v*v) as the kernel wrote them)
+    std::memcpy(r.row_perm.data(), h_out_.get() + blk.off_rp, sizeof(int) * (size_t)M);
+    std::memcpy(r.col_perm.data(), h_out_.get() + blk.off_cp, sizeof(int) * (size_t)N);
     r.pivot_errors.resize(r.rank + 1);
-    for (int k = 0; k < r.rank; ++k) r.pivot_errors[k] = std::sqrt(hr[2 + k] * hr[2 + k]);
+    for (int k = 0; k < r.rank; ++k) r.pivot_errors[k] = std::sqrt(hpiv[k] * hpiv[k]);
     r.pivot_errors[r.rank] = r.last_error;
-    // work model
-    {
-        double bytes = 8.0 * M * N, flops = 0.0;
-        for (int k = 0; k < r.rank; ++k) {
-            const double mr = (double)(M - k - 1), nr_ = (double)(N - k - 1);
-            bytes += 16.0 * mr * nr_;
-            flops += 2.0 * mr * nr_ + mr;
-        }
-        prof.v[8] += r.rank;
-        prof.v[9] += bytes;
-        prof.v[10] += flops;
-        if (prof.enabled) { // per kernel-instantiation statistics (the dominant one feeds bench.py's roofline)
-            auto& vs = variant_stats_[plan_code];
-            vs[0] += rrlu_ms_this;
-            vs[1] += 1.0;
-            vs[2] += bytes;
-            vs[3] += r.rank;
-        }
-    }
+    rrlu_account(rt, !left, M, N, r.rank, prof.enabled, rrlu_ms_this, false);
     if (hp[2] != 0) throw Error(T4A_GPU_NAN_ENCOUNTERED, "NaN encountered in L or U of the rrLU factorisation");
 
     if (need_factors) {
@@ -753,200 +769,163 @@ void Engine::xcd_take_tickets(const RrluXcdPlan& plan, RrluXcdArgs& a)
     }
 }
 
-bool Engine::chain_plan(int kM, int kN, ChainRrluPlan* out) const
+// The mailbox of the single-XCD family (keys, then column slots) holds at least `words` and is clear, tickets included, behind the
+// work on `stream`.  Granules carry launch-salted tags: it is cleared whenever it moves or the 16-bit salt wraps.  (Plans differ in
+// where the column slots start; a stale granule of another plan still carries another launch's salt.)
+void Engine::xcd_mailbox_clear(size_t words, hipStream_t stream)
 {
-    if (kM < 1 || kN < 1 || kM > 65535 || kN > 65535) return false;
-    ChainRrluPlan pl;
-    pl.kM = kM;
-    pl.kN = kN;
-    // tiny matrices keep the fused single-workgroup plan (the candidate matrix is built in the registers: no extra launch);
-    // everything else that fits one workgroup takes the LDS-exchange kernel, with 63 more workgroups for the speculative
-    // candidate matrix of the next bond
-    static const long wg_min = std::getenv("T4A_WG_MIN") ? std::atol(std::getenv("T4A_WG_MIN")) : 64;
-    if ((long long)kM * kN > wg_min && (rrlu_w1_make_plan(kM, kN, &pl.xcd, 63) || rrlu_wg_make_plan(kM, kN, &pl.xcd, 63))) {
-        pl.kind = 2;
-        pl.code = (pl.xcd.wg == 2 ? 300000 : 200000) + pl.xcd.RPT * 1000 + pl.xcd.CPT * 10;
-        *out = pl;
-        return true;
-    }
-    if ((long long)kM * kN <= 64 * 64 && rrlu_reg_make_plan(kM, kN, num_cus_, &pl.reg) && pl.reg.W == 1) {
-        pl.kind = 1;
-        pl.fused = pl.reg.RPT * pl.reg.CPT <= RRLU_FUSED_MAX_VALUES;
-        pl.code = pl.reg.RPT * 1000 + pl.reg.CPT * 10 + 2 + ((pl.reg.TR % 64) == 0 ? 1 : 0); // (+4 for the row-major tie order: chain_rrlu)
-        *out = pl;
-        return true;
-    }
-    // (shapes that only fit with more than kXcdSharedMaxW workgroups keep their plan: the launch then reserves the whole chip)
-    if (xcd_disabled() || !(rrlu_xcd_make_plan(kM, kN, &pl.xcd, true, xcd_plan_max_w()) || rrlu_xcd_make_plan(kM, kN, &pl.xcd, true, 32, true)))
-        return false;
-    pl.kind = 2;
-    pl.code = (pl.xcd.big() ? 400000 + pl.xcd.K * 10000 : 100000) + pl.xcd.RPT * 100 + pl.xcd.CPT * 10;
-    *out = pl;
-    return true;
+    d_xkeys_.reserve(words);
+    d_xticket_.reserve(16);
+    T4A_HIP(hipMemsetAsync(d_xkeys_.get(), 0, d_xkeys_.cap * sizeof(unsigned long long), stream));
+    T4A_HIP(hipMemsetAsync(d_xticket_.get(), 0, 16 * sizeof(unsigned), stream));
+    xcd_ticket_base_ = xcd_ticket_base_multi_ = 0;
+    xcd_salt_ = 0;
 }
 
-void Engine::chain_begin(const std::vector<ChainRrluPlan>& plans, size_t reserve_mailbox_words)
+// The RrluXcdArgs of a host launch on XCD `xcc`, with the launch's tickets and the salt the caller advanced to, except what the
+// caller sets: Aout / urows, dims, rowmap, spec and stamps (zero here).
+void Engine::xcd_args(RrluXcdArgs& a, const RrluRoute& rt, bool left, const double* A, int max_steps, double rel_tol, double abs_tol,
+                      const RrluBlock& blk, int xcc)
 {
-    size_t need = 0;
-    int max_w = 0;
-    for (const ChainRrluPlan& pl : plans)
-        if (pl.kind == 2) {
-            const size_t n = (rrlu_xcd_keys_bytes(pl.xcd) + rrlu_xcd_cols_bytes(pl.xcd, pl.kM)) / sizeof(unsigned long long);
-            need = std::max(need, n);
-            max_w = std::max(max_w, pl.xcd.K > 1 ? 33 : pl.xcd.W); // (a plan over several XCDs reserves the whole chip)
-        }
-    if (need > 0) {
-        if (need > d_xkeys_.cap || !d_xticket_.get()) {
-            d_xkeys_.reserve(std::max(need, reserve_mailbox_words));
-            d_xticket_.reserve(16);
-            T4A_HIP(hipMemsetAsync(d_xkeys_.get(), 0, d_xkeys_.cap * sizeof(unsigned long long), stream_));
-            T4A_HIP(hipMemsetAsync(d_xticket_.get(), 0, 16 * sizeof(unsigned), stream_));
-            xcd_ticket_base_ = xcd_ticket_base_multi_ = 0;
-            xcd_salt_ = 0;
-        }
-        chain_lock_.acquire(max_w > kXcdSharedMaxW ? -1 : xcc_);
-    }
-}
-
-void Engine::chain_end() { chain_lock_.release(); }
-
-bool Engine::chain_group_plan(int kM, int kN, ChainRrluPlan* out)
-{
-    if (kM < 1 || kN < 1 || kM > 1024 || kN > 1024 || xcd_disabled()) return false;
-    ChainRrluPlan pl;
-    pl.kM = kM;
-    pl.kN = kN;
-    if (!rrlu_w1_make_plan(kM, kN, &pl.xcd, 0) && !rrlu_wg_make_plan(kM, kN, &pl.xcd, 0) && !rrlu_xcd_make_plan(kM, kN, &pl.xcd, true, 32)) return false;
-    pl.kind = 2;
-    pl.code = pl.xcd.wg == 2 ? 300000 + pl.xcd.RPT * 1000 + pl.xcd.CPT * 10 : pl.xcd.wg ? 200000 + pl.xcd.RPT * 1000 + pl.xcd.CPT * 10 : 100000 + pl.xcd.RPT * 100 + pl.xcd.CPT * 10;
-    *out = pl;
-    return true;
-}
-
-void Engine::chain_group_reserve(const std::vector<ChainRrluPlan>& plans, size_t reserve_mailbox_words, hipStream_t order_stream)
-{
-    size_t need = 0;
-    for (const ChainRrluPlan& pl : plans)
-        if (pl.kind == 2) need = std::max(need, (rrlu_xcd_keys_bytes(pl.xcd) + rrlu_xcd_cols_bytes(pl.xcd, pl.kM)) / sizeof(unsigned long long));
-    if (need > 0 && (need > d_xkeys_.cap || !d_xticket_.get())) {
-        d_xkeys_.reserve(std::max(need, reserve_mailbox_words));
-        d_xticket_.reserve(16);
-        T4A_HIP(hipMemsetAsync(d_xkeys_.get(), 0, d_xkeys_.cap * sizeof(unsigned long long), order_stream));
-        T4A_HIP(hipMemsetAsync(d_xticket_.get(), 0, 16 * sizeof(unsigned), order_stream));
-        xcd_ticket_base_ = xcd_ticket_base_multi_ = 0;
-        xcd_salt_ = 0;
-    }
-}
-
-unsigned Engine::chain_group_args(const ChainRrluPlan& pl, bool left, const double* d_a, const int* d_dims, size_t max_bond_dim, double rel_tol,
-                                  double abs_tol, const ChainBlock& blk, int slot, RrluXcdArgs* out, hipStream_t order_stream)
-{
-    double* d_dres = reinterpret_cast<double*>(blk.dev);
-    int* d_ires = reinterpret_cast<int*>(blk.dev + 16);
-    double* d_pivvals = reinterpret_cast<double*>(blk.dev + blk.off_piv);
-    int* d_rowperm = reinterpret_cast<int*>(blk.dev + blk.off_rp);
-    int* d_colperm = reinterpret_cast<int*>(blk.dev + blk.off_cp);
-    const int mn = pl.kM < pl.kN ? pl.kM : pl.kN;
-    const int max_steps = max_bond_dim < (size_t)mn ? (int)max_bond_dim : mn;
-    if (++xcd_salt_ > 65535u) { // the 16-bit launch salt wraps: stale granules could match again, clear the mailbox
-        T4A_HIP(hipMemsetAsync(d_xkeys_.get(), 0, d_xkeys_.cap * sizeof(unsigned long long), order_stream));
-        xcd_salt_ = 1;
-    }
-    RrluXcdArgs a;
     std::memset(&a, 0, sizeof(a));
-    a.A = d_a;
-    a.Aout = nullptr;
-    a.urows = nullptr;
-    a.M = pl.kM;
-    a.N = pl.kN;
+    a.A = A;
+    a.M = rt.kM;
+    a.N = rt.kN;
     a.max_steps = max_steps;
     a.rel_tol = rel_tol;
     a.abs_tol = abs_tol;
     a.tie_row_major = left ? 0 : 1;
     a.out_transposed = left ? 0 : 1;
-    a.W = pl.xcd.W;
-    a.xcc = slot;
-    xcd_take_tickets(pl.xcd, a); // (the one-workgroup kernel takes no tickets)
-    a.row_perm = left ? d_rowperm : d_colperm;
-    a.col_perm = left ? d_colperm : d_rowperm;
-    a.iresult = d_ires;
-    a.dresult = d_dres;
-    a.pivot_vals = d_pivvals;
+    a.W = rt.xcd.W;
+    a.xcc = xcc;
+    xcd_take_tickets(rt.xcd, a); // exactly grid / 8 workgroups of a launch land on one XCD (the one-workgroup kernel takes no tickets)
+    a.row_perm = left ? blk.row_perm() : blk.col_perm();
+    a.col_perm = left ? blk.col_perm() : blk.row_perm();
+    a.iresult = blk.iresult();
+    a.dresult = blk.dresult();
+    a.pivot_vals = blk.pivot_vals();
     a.keys = d_xkeys_.get();
     a.salt = xcd_salt_;
     a.spec_frac = 0.8;
-    a.stamps = nullptr;
     a.h_block = reinterpret_cast<unsigned long long*>(blk.host);
     a.block_u64 = (int)(blk.bytes / 8);
-    a.dims = d_dims;
-    a.dims_swap = left ? 0 : 1;
-    a.rowmap = nullptr;
     a.ts_u64 = (int)(blk.off_ts / 8);
-    *out = a;
+}
+
+void Engine::rrlu_account(const RrluRoute& rt, bool tie_row_major, int M, int N, int rank, bool record, float ms, bool saturated)
+{
+    double bytes = 8.0 * M * N, flops = 0.0;
+    for (int k = 0; k < rank; ++k) {
+        const double mr = (double)(M - k - 1), nr = (double)(N - k - 1);
+        bytes += 16.0 * mr * nr;
+        flops += 2.0 * mr * nr + mr;
+    }
+    prof.v[8] += rank;
+    prof.v[9] += bytes;
+    prof.v[10] += flops;
+    if (!record) return;
+    // per kernel-instantiation statistics (the dominant one feeds bench.py's roofline)
+    auto add = [&](int code) {
+        auto& vs = variant_stats_[code];
+        vs[0] += ms;
+        vs[1] += 1.0;
+        vs[2] += bytes;
+        vs[3] += rank;
+    };
+    add(rt.code(tie_row_major));
+    if (saturated) add(rt.code(tie_row_major, true));
+}
+
+// The bond chain's policy: above T4A_WG_MIN entries the one-wave / one-workgroup kernels, with 63 more workgroups for the
+// speculative candidate matrix of the next bond; tiny matrices keep the fused single-workgroup register plan (the candidate matrix
+// is built in the registers: no extra launch); everything else takes any shape of the single-XCD family (shapes that only fit
+// with more than kXcdSharedMaxW workgroups keep their plan: the launch then reserves the whole chip).
+RrluRoute Engine::chain_route(int kM, int kN) const
+{
+    if (kM < 1 || kN < 1 || kM > 65535 || kN > 65535) return RrluRoute();
+    RrluXcdPlan xplan;
+    if ((long long)kM * kN > rrlu_env().wg_min && (rrlu_w1_make_plan(kM, kN, &xplan, 63) || rrlu_wg_make_plan(kM, kN, &xplan, 63)))
+        return RrluRoute::of_xcd(xplan, kM, kN);
+    RrluRegPlan rplan;
+    if ((long long)kM * kN <= 64 * 64 && rrlu_reg_make_plan(kM, kN, num_cus_, &rplan) && rplan.W == 1) return RrluRoute::of_reg(rplan, kM, kN);
+    if (!xcd_disabled() && (rrlu_xcd_make_plan(kM, kN, &xplan, true, xcd_plan_max_w()) || rrlu_xcd_make_plan(kM, kN, &xplan, true, 32, true)))
+        return RrluRoute::of_xcd(xplan, kM, kN);
+    return RrluRoute();
+}
+
+void Engine::chain_begin(const std::vector<RrluRoute>& routes, size_t reserve_mailbox_words)
+{
+    chain_group_reserve(routes, reserve_mailbox_words, stream_);
+    RrluLock scope = RrluLock::None;
+    for (const RrluRoute& rt : routes)
+        if (rt.on_xcd()) scope = std::max(scope, rt.lock());
+    acquire_for(chain_lock_, scope, xcc_);
+}
+
+void Engine::chain_end() { chain_lock_.release(); }
+
+// The group chain's policy: the single-XCD family without the speculative workgroups, without T4A_WG_MIN and without the plans
+// beyond one XCD.
+RrluRoute Engine::chain_group_route(int kM, int kN)
+{
+    if (kM < 1 || kN < 1 || kM > 1024 || kN > 1024 || xcd_disabled()) return RrluRoute();
+    RrluXcdPlan xplan;
+    if (rrlu_w1_make_plan(kM, kN, &xplan, 0) || rrlu_wg_make_plan(kM, kN, &xplan, 0) || rrlu_xcd_make_plan(kM, kN, &xplan, true, 32))
+        return RrluRoute::of_xcd(xplan, kM, kN);
+    return RrluRoute();
+}
+
+void Engine::chain_group_reserve(const std::vector<RrluRoute>& routes, size_t reserve_mailbox_words, hipStream_t order_stream)
+{
+    size_t need = 0;
+    for (const RrluRoute& rt : routes)
+        if (rt.on_xcd()) need = std::max(need, rt.xcd_mailbox_words());
+    if (need > 0 && (need > d_xkeys_.cap || !d_xticket_.get())) xcd_mailbox_clear(std::max(need, reserve_mailbox_words), order_stream);
+}
+
+unsigned Engine::chain_group_args(const RrluRoute& rt, bool left, const double* d_a, const int* d_dims, size_t max_bond_dim, double rel_tol,
+                                  double abs_tol, const RrluBlock& blk, int slot, RrluXcdArgs* out, hipStream_t order_stream)
+{
+    if (++xcd_salt_ > 65535u) { // the 16-bit launch salt wraps: stale granules could match again, clear the mailbox
+        T4A_HIP(hipMemsetAsync(d_xkeys_.get(), 0, d_xkeys_.cap * sizeof(unsigned long long), order_stream));
+        xcd_salt_ = 1;
+    }
+    xcd_args(*out, rt, left, d_a, chain_max_steps(rt, max_bond_dim), rel_tol, abs_tol, blk, slot);
+    out->dims = d_dims;
+    out->dims_swap = left ? 0 : 1;
     return xcd_salt_;
 }
 
-unsigned Engine::chain_rrlu(const ChainRrluPlan& pl, bool left, const double* d_a, const int* d_rowmap, const FusedPi* fused, const int* d_dims,
-                            size_t max_bond_dim, double rel_tol, double abs_tol, const ChainBlock& blk, const XcdSpecArgs* spec, double* d_aout, double* d_urows)
+unsigned Engine::chain_rrlu(const RrluRoute& rt, bool left, const double* d_a, const int* d_rowmap, const FusedPi* fused, const int* d_dims,
+                            size_t max_bond_dim, double rel_tol, double abs_tol, const RrluBlock& blk, const XcdSpecArgs* spec, double* d_aout, double* d_urows)
 {
-    double* d_dres = reinterpret_cast<double*>(blk.dev);
-    int* d_ires = reinterpret_cast<int*>(blk.dev + 16);
-    double* d_pivvals = reinterpret_cast<double*>(blk.dev + blk.off_piv);
-    int* d_rowperm = reinterpret_cast<int*>(blk.dev + blk.off_rp);
-    int* d_colperm = reinterpret_cast<int*>(blk.dev + blk.off_cp);
-    const int mn = pl.kM < pl.kN ? pl.kM : pl.kN;
-    const int max_steps = max_bond_dim < (size_t)mn ? (int)max_bond_dim : mn;
     unsigned token = 0u;
-    if (pl.kind == 2) {
+    if (rt.on_xcd()) {
         RrluXcdArgs a;
-        token = chain_group_args(pl, left, d_a, d_dims, max_bond_dim, rel_tol, abs_tol, blk, xcc_, &a, stream_);
+        token = chain_group_args(rt, left, d_a, d_dims, max_bond_dim, rel_tol, abs_tol, blk, xcc_, &a, stream_);
         a.rowmap = d_rowmap;
         a.Aout = d_aout;
         a.urows = d_aout ? d_urows : nullptr;
         if (spec) a.spec = *spec;
-        rrlu_xcd_launch_v(xcd_version(), pl.xcd, a, stream_);
+        rt.launch(a, stream_);
     } else {
         if (++done_token_ == 0u) ++done_token_;
         RrluRegArgs a;
-        std::memset(&a, 0, sizeof(a));
-        a.A = d_a;
+        reg_args(a, rt, left, d_a, chain_max_steps(rt, max_bond_dim), rel_tol, abs_tol, blk);
         a.Aout = d_aout;
-        a.M = pl.kM;
-        a.N = pl.kN;
-        a.max_steps = max_steps;
-        a.rel_tol = rel_tol;
-        a.abs_tol = abs_tol;
-        a.tie_row_major = left ? 0 : 1;
-        a.out_transposed = left ? 0 : 1;
-        a.W = 1;
-        a.TR = pl.reg.TR;
-        a.TC = pl.reg.TC;
-        a.row_perm = left ? d_rowperm : d_colperm;
-        a.col_perm = left ? d_colperm : d_rowperm;
-        a.iresult = d_ires;
-        a.dresult = d_dres;
-        a.pivot_vals = d_pivvals;
         a.salt = 1;
-        a.ncopy = 1;
-        a.spec = 2;
-        a.spec_frac = 0.8;
-        a.key16 = 1;
-        a.spin_limit = 1u << 20;
-        a.fused = (pl.fused && fused) ? 1 : 0;
+        a.fused = (rt.fused && fused) ? 1 : 0;
         if (a.fused) { // (the chain hands over the accumulators of the KERNEL's rows and columns)
             a.rowacc = fused->d_rowacc;
             a.colacc = fused->d_colacc;
             a.fn = fused->fn;
         }
-        a.h_block = reinterpret_cast<unsigned long long*>(blk.host);
-        a.block_u64 = (int)(blk.bytes / 8);
         a.dims = d_dims;
         a.dims_swap = left ? 0 : 1;
         a.rowmap = a.fused ? nullptr : d_rowmap;
-        a.ts_u64 = (int)(blk.off_ts / 8);
         a.dev_token = done_token_;
         a.done_token = done_token_; // (also to int word 7 of the host mirror, like the single-XCD kernel's salt)
-        rrlu_reg_launch(pl.reg, a, stream_, true);
+        rrlu_reg_launch(rt.reg, a, stream_, true);
         token = done_token_;
     }
     T4A_HIP(hipGetLastError());

@@ -49,9 +49,6 @@ struct Profile {
 // process-wide arbiter of the persistent multi-workgroup rrLU kernels (engine.hip)
 bool xcd_disabled();
 void xcd_disable();
-int xcd_version(); // generation of the single-XCD rrLU kernel (2: kernels_rrlu_xcd2.hip; the first generation was retired in round 6)
-void rrlu_xcd_launch_v(int version, const RrluXcdPlan& plan, const RrluXcdArgs& args, hipStream_t stream);
-void rrlu_xcd_group_launch_v(int version, const RrluXcdPlan& plan, const RrluXcdGroupArgs& args, bool tie_row_major, hipStream_t stream);
 int xcd_assign();
 int xcd_plan_max_w();
 struct XcdArbiter {
@@ -69,19 +66,52 @@ struct XcdArbiter {
     };
 };
 
-// rrLU launch of one bond of a device-side bond chain (tci2_chain.hip): planned for upper bounds, dimensions read on the device
-struct ChainRrluPlan {
-    int kind = 0;        // 1: single-workgroup register kernel   2: single-XCD kernel
-    bool fused = false;  // kind 1: the candidate matrix is built in the registers from the accumulators (no matrix in memory)
-    RrluRegPlan reg;
-    RrluXcdPlan xcd;
-    int kM = 0, kN = 0;  // upper bounds of the matrix the KERNEL sees (transposed for a right-orthogonal factorisation)
-    int code = 0;        // profile code of the kernel instantiation (Engine::variant_stats_)
+// The rrLU kernel one factorisation runs on, with its launch plan.  Engine::luci_route, Engine::chain_route and
+// Engine::chain_group_route pick it (one policy each); everything that follows from the choice is decided here.
+enum class RrluKind {
+    None,         // no route (the chain planners: this bond cannot be chained)
+    OneWave,      // kernels_rrlu_w1.hip (xcd.wg == 2)
+    OneWorkgroup, // kernels_rrlu_wg.hip (xcd.wg == 1)
+    SingleXcd,    // kernels_rrlu_xcd2.hip
+    MultiXcd,     // kernels_rrlu_xcd2m.hip (xcd.big(): agents on K > 1 XCDs or more than 16 row slots per lane)
+    Reg,          // chip-wide register kernel (kernels_rrlu_reg.hip)
+    Lds,          // LDS-resident kernel (kernels_rrlu.hip)
+    Global,       // HBM-resident kernel (kernels_rrlu_global.hip)
 };
-struct ChainBlock {      // packed result block of one bond: [dresult 2 f64][iresult 4 i32][pivot values][row perm][col perm]
+enum class RrluLock { None, Xcd, Chip }; // what a launch reserves through XcdArbiter: nothing, the engine's XCD, the whole chip
+struct RrluRoute {
+    RrluKind kind = RrluKind::None;
+    RrluXcdPlan xcd;     // OneWave .. MultiXcd
+    RrluRegPlan reg;     // Reg
+    RrluPlan lds;        // Lds
+    int kM = 0, kN = 0;  // the matrix the KERNEL sees (Reg and the XCD family: transposed for a right-orthogonal factorisation)
+    bool fused = false;  // Reg: the plan can build the candidate matrix in its registers from the accumulators
+
+    static RrluRoute of_xcd(const RrluXcdPlan& plan, int kM, int kN);
+    static RrluRoute of_reg(const RrluRegPlan& plan, int kM, int kN);
+    bool ok() const { return kind != RrluKind::None; }
+    bool on_xcd() const { return kind == RrluKind::OneWave || kind == RrluKind::OneWorkgroup || kind == RrluKind::SingleXcd || kind == RrluKind::MultiXcd; }
+    // profile code of the kernel instantiation (Engine::variant_stats_; bench.py's rrlu_kernel_name decodes it).  saturated: the
+    // sub-aggregate of the launches that ran all max_bond_dim pivot steps
+    int code(bool tie_row_major, bool saturated = false) const;
+    RrluLock lock() const;
+    size_t xcd_mailbox_words() const; // the XCD family: keys, then column slots
+    void launch(const RrluXcdArgs& args, hipStream_t stream) const;                                       // the XCD family
+    void launch_group(const RrluXcdGroupArgs& args, bool tie_row_major, hipStream_t stream) const;         // OneWave .. SingleXcd
+};
+
+// View of the packed result block of one rrLU launch: [dresult 2 f64][iresult 4 i32][pivot values][row perm][col perm]
+// [two u64 time stamps of the kernel, when off_ts != 0]
+struct RrluBlock {
     char* dev = nullptr;
-    char* host = nullptr; // pinned mirror, same layout
-    size_t off_piv = 32, off_rp = 0, off_cp = 0, off_ts = 0, bytes = 0; // off_ts: two u64 time stamps of the kernel (0: none)
+    char* host = nullptr; // pinned mirror, same layout (nullptr: none)
+    size_t off_piv = 32, off_rp = 0, off_cp = 0, off_ts = 0, bytes = 0;
+    static RrluBlock layout(size_t max_steps, size_t M, size_t N, bool with_timestamps);
+    double* dresult() const { return reinterpret_cast<double*>(dev); }
+    int* iresult() const { return reinterpret_cast<int*>(dev + 16); }
+    double* pivot_vals() const { return reinterpret_cast<double*>(dev + off_piv); }
+    int* row_perm() const { return reinterpret_cast<int*>(dev + off_rp); }
+    int* col_perm() const { return reinterpret_cast<int*>(dev + off_cp); }
 };
 
 class Engine {
@@ -129,28 +159,32 @@ public:
     void qr(const double* d_a, int M, int N, double* d_q, double* d_r);
 
     // ---- bond chain: launches without a host round trip (dimensions in device memory) ----
-    bool chain_plan(int kM, int kN, ChainRrluPlan* out) const;
-    // before the first launch of a chain: mailbox capacity for every plan, the XCD (or the whole chip) reserved until chain_end()
-    void chain_begin(const std::vector<ChainRrluPlan>& plans, size_t reserve_mailbox_words = 0);
+    // route of one bond (kind None: not chainable)
+    RrluRoute chain_route(int kM, int kN) const;
+    // before the first launch of a chain: mailbox capacity for every route, the XCD (or the whole chip) reserved until chain_end()
+    void chain_begin(const std::vector<RrluRoute>& routes, size_t reserve_mailbox_words = 0);
     // rrLU of one bond: `left` as in RrLUOptions::left_orthogonal; d_a: the kernel's matrix (already transposed for !left; read
     // through d_rowmap with leading dimension d_dims[3] when d_rowmap != nullptr) unless the plan is fused (then `fused` holds
     // the accumulators of the KERNEL's rows and columns); d_dims: {M, N, poison, lda} of the MATRIX on the device.  Returns the
     // completion token the kernel writes to iresult[3] of the device block (and to int word 7 of the host mirror).
     // spec (single-XCD plans only, may be null): the candidate matrix of the NEXT bond for the launch's pass-through workgroups.
-    unsigned chain_rrlu(const ChainRrluPlan& pl, bool left, const double* d_a, const int* d_rowmap, const FusedPi* fused, const int* d_dims,
-                        size_t max_bond_dim, double rel_tol, double abs_tol, const ChainBlock& blk, const XcdSpecArgs* spec, double* d_aout = nullptr, double* d_urows = nullptr);
+    unsigned chain_rrlu(const RrluRoute& rt, bool left, const double* d_a, const int* d_rowmap, const FusedPi* fused, const int* d_dims,
+                        size_t max_bond_dim, double rel_tol, double abs_tol, const RrluBlock& blk, const XcdSpecArgs* spec, double* d_aout = nullptr, double* d_urows = nullptr);
     void chain_end();
     // Group chain (tci2_chain.hip): several handles advance in lock step, one rrLU launch per bond for all of them, handle i on
-    // XCD `slot` i.  chain_group_plan: the single-XCD plan every member uses for a bond (made for the largest upper bounds in
-    // the group; no single-workgroup plans: a small bond costs a group launch, i.e. an eighth of it per handle).
-    // chain_group_reserve: this member's mailbox for the plans (no lock: the group's leader reserves the chip with
+    // XCD `slot` i.  chain_group_route: the route every member uses for a bond (made for the largest upper bounds in the group;
+    // no chip-wide register plans: a small bond costs a group launch, i.e. an eighth of it per handle).
+    // chain_group_reserve: this member's mailbox for the routes (no lock: the group's leader reserves the chip with
     // chain_group_lock / chain_end).  chain_group_args: the argument block of this member for one bond (advances the member's
-    // salt and ticket base exactly like a launch of its own); the caller launches the assembled blocks with rrlu_xcd_group_launch.
-    static bool chain_group_plan(int kM, int kN, ChainRrluPlan* out);
-    void chain_group_reserve(const std::vector<ChainRrluPlan>& plans, size_t reserve_mailbox_words, hipStream_t order_stream);
+    // salt and ticket base exactly like a launch of its own); the caller launches the assembled blocks with RrluRoute::launch_group.
+    static RrluRoute chain_group_route(int kM, int kN);
+    void chain_group_reserve(const std::vector<RrluRoute>& routes, size_t reserve_mailbox_words, hipStream_t order_stream);
     void chain_group_lock() { chain_lock_.acquire(-1); }
-    unsigned chain_group_args(const ChainRrluPlan& pl, bool left, const double* d_a, const int* d_dims, size_t max_bond_dim, double rel_tol,
-                              double abs_tol, const ChainBlock& blk, int slot, RrluXcdArgs* out, hipStream_t order_stream);
+    unsigned chain_group_args(const RrluRoute& rt, bool left, const double* d_a, const int* d_dims, size_t max_bond_dim, double rel_tol,
+                              double abs_tol, const RrluBlock& blk, int slot, RrluXcdArgs* out, hipStream_t order_stream);
+    // work model of one factorisation of an M x N matrix into prof.v[8..10]; with `record` also its row of
+    // variant_stats_ (and, when `saturated`, the sub-aggregate's)
+    void rrlu_account(const RrluRoute& rt, bool tie_row_major, int M, int N, int rank, bool record, float ms, bool saturated);
     int xcc() const { return xcc_; }
     void set_xcc(int xcc) { xcc_ = xcc & 7; } // (optimize_group: handle i of a group works on XCD i)
 
@@ -166,6 +200,7 @@ public:
     DevBuf<double> d_tmp, d_tmp2;
 
 private:
+    RrluRoute luci_route(int M, int N, bool left) const;
     void build_factors(const LuciResult& r, bool left_orth);
 public:
     // factors_from_rrlu on a factored matrix that sits somewhere else (the per-bond buffers of a chained 1-site sweep): left() /
@@ -179,9 +214,12 @@ private:
     unsigned rrlu_salt_ = 0;
     // single-XCD rrLU kernel: elected XCD, mailboxes, monotonic ticket counter
     int xcc_ = 0;
-    bool xcd_retry_v1_ = false; // luci(): this call re-runs a factorisation a register kernel gave up on (non-finite values) on the chip-wide kernels
+    bool nonfinite_retry_ = false; // luci(): this call re-runs a factorisation an XCD-family kernel gave up on (non-finite values) on the chip-wide kernels
     unsigned xcd_salt_ = 0, xcd_ticket_base_ = 0, xcd_ticket_base_multi_ = 0;
     void xcd_take_tickets(const RrluXcdPlan& plan, RrluXcdArgs& a);
+    void xcd_mailbox_clear(size_t words, hipStream_t stream);
+    void xcd_args(RrluXcdArgs& a, const RrluRoute& rt, bool left, const double* A, int max_steps, double rel_tol, double abs_tol,
+                  const RrluBlock& blk, int xcc);
     DevBuf<unsigned long long> d_xkeys_; // mailbox of the single-XCD kernel: keys, then column slots
     DevBuf<unsigned> d_xticket_;
     DevBuf<double> d_xurows_;
@@ -195,8 +233,6 @@ private:
     PinBuf<char> h_out_;
     int* d_rowperm_ptr_ = nullptr;
     int* d_colperm_ptr_ = nullptr;
-    std::vector<int> h_ints_;
-    std::vector<double> h_dbls_;
     DevBuf<unsigned long long> d_keys_, d_cols_, d_rkeys_, d_rcols_, d_stamps_;
     DevBuf<TrsmProblem> d_trsm_;
     PinBuf<TrsmProblem> h_trsm_;

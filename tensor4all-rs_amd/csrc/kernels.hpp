@@ -161,7 +161,7 @@ size_t rrlu_reg_cols_bytes(const RrluRegPlan& plan, int M);
 // keys_zeroed: the key table is already clear (the previous launch left it clean, see RrluRegArgs::keys_next)
 void rrlu_reg_launch(const RrluRegPlan& plan, const RrluRegArgs& args, hipStream_t stream, bool keys_zeroed = false);
 
-// ---- single-XCD register-resident kernel (kernels_rrlu_xcd.hip): all participating workgroups share one L2 ----
+// ---- single-XCD register-resident kernel (kernels_rrlu_xcd2.hip, plans in rrlu_xcd_plan.hip): all participating workgroups share one L2 ----
 // Bond chain: the candidate matrix of the NEXT bond, evaluated speculatively by the launch's pass-through workgroups (the 7/8
 // of the grid that land on the other XCDs and used to return at once) while the elected XCD factorises this bond:
 // out[j * lda + c] = f(acc(c) + ind_acc[j]), candidate c < M * d: child (parent c / d of this bond's dependent list = the
@@ -232,13 +232,13 @@ size_t rrlu_xcd_keys_bytes(const RrluXcdPlan& plan);
 size_t rrlu_xcd_cols_bytes(const RrluXcdPlan& plan, int M);
 // Eight factorisations in one launch, one per XCD (slot x is run by the workgroups that land on XCD x; a slot with xcc = -1 is
 // empty).  All slots share the plan (made for the largest upper-bound shape among them) and the tie order; every slot brings
-// its own mailbox, ticket counter and result block.  kernels_rrlu_xcd_group.hip.
+// its own mailbox, ticket counter and result block.  Launched through RrluRoute::launch_group (engine.hpp).
 struct RrluXcdGroupArgs {
     RrluXcdArgs p[8];
 };
-// Second generation of the same kernel (kernels_rrlu_xcd2.hip: one-word record, stop tests and tables off the critical path, no
-// hand-zeroed pivot rows): same plan, arguments and mailbox.  It handles finite matrices only: on a NaN / infinity in the input or
-// an overflow in the trailing block the launch gives up with iresult[1] == 2 and the caller runs the first generation.
+// The kernel (kernels_rrlu_xcd2.hip: one-word record, stop tests and tables off the critical path, no hand-zeroed pivot rows)
+// handles finite matrices only: on a NaN / infinity in the input or an overflow in the trailing block the launch gives up with
+// iresult[1] == 2 and the caller runs the chip-wide kernels, which implement the NaN-incumbent rule.
 void rrlu_xcd2_launch(const RrluXcdPlan& plan, const RrluXcdArgs& args, hipStream_t stream);
 // plans with big() (kernels_rrlu_xcd2m.hip): the same kernel body with agents on K XCDs and / or 20 - 24 row slots per lane
 void rrlu_xcd2m_launch(const RrluXcdPlan& plan, const RrluXcdArgs& args, hipStream_t stream);
@@ -352,7 +352,7 @@ struct ChainPrepArgs {
 // The persistent half-sweep (kernels_chain.hip, chain_walk_kernel): one workgroup walks all bonds — preparation, candidate matrix,
 // one-wave rrLU — when every bond's matrix is at most 64 x 64.  Result blocks as the launched chain writes them.
 struct ChainWalkArgs {
-    char* blocks;                       // [n_bonds] packed result blocks (ChainBlock layout)
+    char* blocks;                       // [n_bonds] packed result blocks (RrluBlock layout, engine.hpp)
     size_t block_bytes, off_piv, off_rp, off_cp, off_ts;
     double* pi;                         // candidate matrix of the current bond (64 x 64 doubles)
     int n_bonds;
@@ -377,7 +377,7 @@ void chain_pi_launch(const ChainCommon& c, const FnDevice& fn, int b, int n_dep_
 // Group chain: up to CHAIN_GROUP_MAX handles (independent interpolations: patches of one farm) advance through their
 // half-sweeps in lock step — ONE launch per kernel and bond for all of them.  The per-handle constants of a half-sweep sit in
 // a device table (one slot per handle), the per-bond arguments travel as small arrays in the kernel arguments; the rrLU launch
-// gives every handle its own XCD (rrlu_xcd_group_launch).  Bond indices and the sweep direction are common to the group.
+// gives every handle its own XCD (RrluRoute::launch_group).  Bond indices and the sweep direction are common to the group.
 constexpr int CHAIN_GROUP_MAX = 8;
 struct ChainGroupSlot {
     ChainCommon c;

@@ -18,7 +18,7 @@
 //                        Kronecker part is membership of its parent multi-index in the table (hash in LDS), survivors are
 //                        compacted by a prefix sum; (3) the dimensions of the bond, for the kernels behind it on the stream.
 //   (xcd_spec_work,      the candidate matrix of bond b, evaluated SPECULATIVELY while the rrLU of the previous bond is still
-//   kernels_rrlu_xcd.hip) running: that launch occupies one XCD, and its pass-through workgroups on the other seven do this
+//   kernels_rrlu_xcd2.hip) running: that launch occupies one XCD, and its pass-through workgroups on the other seven do this
 //                        instead of returning at once.  The dependent side of bond b can only consist of children of entries
 //                        of the previous bond's dependent list (a pivot is one of its candidates) and of extras, so f is
 //                        evaluated for ALL of those candidates x the independent list; chain_prep_kernel then only writes a

@@ -18,7 +18,7 @@
 // :593-612); a right-orthogonal factorisation runs as the left-orthogonal one of A^T with the row-major tie order.  Arguments and
 // result block are RrluXcdArgs (kernels.hpp), including the bond-chain extensions (`urows` is not used: the rows of U wait in the
 // LDS).  Finite matrices only: a NaN / infinity in the input or an overflow in the trailing block ends the launch with code 2 and
-// the caller runs the first-generation single-XCD kernel.
+// the caller runs the chip-wide kernels.
 //
 // The body is a header because two kernels run it: the launchers of kernels_rrlu_w1.hip (one matrix per workgroup, wave 0) and the
 // persistent half-sweep of kernels_walk.hip (wave 0 of the walking workgroup).

@@ -12,7 +12,7 @@
 // order.  Arguments, result block, bond-chain extensions (device-side dimensions, row map, speculative candidate matrix of the
 // next bond by the other workgroups of the launch, completion token) are those of the single-XCD kernel (RrluXcdArgs).
 // Non-finite values are not handled (as in kernels_rrlu_xcd2.hip): the launch gives up with code 2 and the caller runs the
-// first-generation single-XCD kernel.
+// chip-wide kernels.
 //
 // Structure of a step (wave w owns columns w + 8 q, lane l rows l + 64 r; columns in register groups of GS so that the two
 // run-time accesses — the candidate's value and its column — index inside one vector):

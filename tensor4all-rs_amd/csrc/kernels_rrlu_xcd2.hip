@@ -1,6 +1,6 @@
 // kernels_rrlu_xcd2.hip — K2 fast path, round 4: second generation of the single-XCD register-resident full-pivot rrLU.
 //
-// Same contract as kernels_rrlu_xcd.hip (bit-identical to rrlu_mut, tensor4all-core/src/matrixlu.rs:735-819; arg-max semantics
+// Same contract as the first generation (bit-identical to rrlu_mut, tensor4all-core/src/matrixlu.rs:735-819; arg-max semantics
 // matrixlu.rs:480-519; a right-orthogonal factorisation runs as the left-orthogonal one of A^T with the row-major tie order), same
 // placement scheme (8 W workgroups launched, the W that land on the elected XCD take part), same mailbox layout and the same
 // data layout (wave = agent that owns whole columns, lane = rows lane + 64 r).  What changed is the PROTOCOL of a pivot step: the
@@ -19,7 +19,7 @@
 //     block, its position comes from an LDS table when a position key is built (normal path: one look-up per step);
 //   * the polling wave owns columns like everybody else but takes no share of the division (seven waves divide);
 //   * NON-FINITE values are not handled here at all: the launch gives up with code 2 (iresult[1]) and the caller runs the
-//     first-generation kernel, which implements the NaN-incumbent rule.  This is exact, not heuristic: a NaN can only appear
+//     chip-wide kernels, which implement the NaN-incumbent rule.  This is exact, not heuristic: a NaN can only appear
 //     in a trailing block after an infinity has (|l| <= 1 under full pivoting, so l * u and a - l * u overflow before anything
 //     becomes NaN), an infinity in the trailing block is some agent's candidate magnitude, and the polling wave sees every
 //     candidate magnitude of every step; NaN / infinity in the INPUT is found while the matrix is loaded and travels in the
@@ -422,7 +422,7 @@ __device__ __forceinline__ void rrlu_xcd2_body(const RrluXcdArgs& p, const RrluX
         // ---- the polling wave(s) gather the early keys and name the winner (matrixlu.rs:480-519 across agents) ----
         if (poller) {
             unsigned spins = 0;
-            int giveup = 0; // 1: a hand-off did not arrive  2: non-finite values (the caller runs the first-generation kernel)
+            int giveup = 0; // 1: a hand-off did not arrive  2: non-finite values (the caller runs the chip-wide kernels)
             XSTAMP(6);
             for (;;) {
                 bool ok = true;
@@ -1115,7 +1115,7 @@ template <int RPT> void xcd2_launch_r(const RrluXcdPlan& plan, const RrluXcdArgs
 }
 
 #else
-// Group launch: eight factorisations, one per XCD (see rrlu_xcd_group_kernel in kernels_rrlu_xcd.hip)
+// Group launch: eight factorisations, one per XCD (RrluXcdGroupArgs, kernels.hpp)
 template <int RPT, int CPT, bool ROWMAJOR>
 __global__ void __launch_bounds__(XT) __attribute__((amdgpu_waves_per_eu(XWAVES / 4, XWAVES / 4))) rrlu_xcd2_group_kernel(RrluXcdGroupArgs g)
 {
@@ -1154,7 +1154,7 @@ template <int RPT> void xcd2_group_launch_r(const RrluXcdPlan& plan, const RrluX
 } // namespace
 
 #if defined(T4A_XCD2_MULTI_TU)
-// the plans rrlu_xcd_make_plan(..., allow_big) hands out (kernels_rrlu_xcd.hip): one XCD with 24 row slots, or three XCDs
+// the plans rrlu_xcd_make_plan(..., allow_big) hands out (rrlu_xcd_plan.hip): one XCD with 24 row slots, or three XCDs
 void rrlu_xcd2m_launch(const RrluXcdPlan& plan, const RrluXcdArgs& a, hipStream_t stream)
 {
     const bool ok = xcd2m_launch_rc<24, 1, 1>(plan, a, stream) || xcd2m_launch_rc<24, 2, 1>(plan, a, stream) ||

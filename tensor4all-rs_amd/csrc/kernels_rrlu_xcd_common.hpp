@@ -1,5 +1,5 @@
-// kernels_rrlu_xcd_common.hpp — helpers shared by the two generations of the single-XCD rrLU kernel (kernels_rrlu_xcd.hip,
-// kernels_rrlu_xcd2.hip): wave reductions through DPP, tagged 16-byte granules, the bitwise-IEEE division through a shared
+// kernels_rrlu_xcd_common.hpp — helpers shared by the single-XCD family of rrLU kernels (kernels_rrlu_xcd2.hip and its multi-XCD /
+// group builds, kernels_rrlu_wg.hip, kernels_rrlu_w1_body.hpp): wave reductions through DPP, tagged 16-byte granules, the bitwise-IEEE division through a shared
 // refined reciprocal, the speculative candidate-matrix work of the pass-through workgroups.  Everything sits in an anonymous
 // namespace: each translation unit gets its own copy (the kernels are templates instantiated per translation unit anyway).
 #pragma once

@@ -1,6 +1,6 @@
 // rrlu_xcd_plan.hip — launch plans of the single-XCD / multi-XCD register-resident rrLU kernels (kernels_rrlu_xcd2.hip,
 // kernels_rrlu_xcd2m.hip): which instantiation (row slots per lane, columns per agent, XCDs) takes a given shape, and the size of
-// its mailbox.  Host code only.  (Round 6: moved out of kernels_rrlu_xcd.hip when the first-generation kernel was retired — non-finite
+// its mailbox.  Host code only.  (Round 6: moved out of the first-generation kernel's source when it was retired — non-finite
 // matrices, the one case it was kept for, go to the chip-wide kernels, which implement the NaN-incumbent rule of matrixlu.rs:480-519.)
 #include "kernels_rrlu_xcd_common.hpp"
 

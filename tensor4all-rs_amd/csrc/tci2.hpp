@@ -300,7 +300,7 @@ private:
         long ext_idx = -1;
         size_t chi = 0;
         std::vector<size_t> order;
-        std::vector<ChainRrluPlan> plans;
+        std::vector<RrluRoute> plans;
         std::vector<unsigned> tokens;
         // a 1-site sweep as a chain (sweep1site, tensorci2.rs:865-1050): set by sweep1site() around chain_enqueue / chain_finish
         bool one_site = false;       // the independent side is the table itself, no extras; both tolerances apply
@@ -314,7 +314,7 @@ private:
         bool walked = false;         // the chain in flight is a persistent half-sweep
         bool prep_dbg = false;       // ... or a launched chain whose preparation kernels stamp their phases (T4A_PREP_DEBUG)
         unsigned walk_token = 1;     // completion tokens of the persistent half-sweep (bond k of a walk: base + k)
-        ChainBlock proto;
+        RrluBlock proto;
         bool timed = false, timed_events = false;
         std::vector<hipEvent_t> t0, t1; // per bond: around the rrLU launch (chain_event_timing)
         // a half-sweep that has been prepared (plans, buffers, tables, kernel constants) and waits for its launch: on its own

@@ -277,7 +277,7 @@ bool Tci2::chain_enqueue(bool forward, const TCI2Options& options, long ext_idx,
     std::vector<size_t> order(nb);
     for (size_t k = 0; k < nb; ++k) order[k] = forward ? k : nb - 1 - k;
     std::vector<size_t> dep_ub(nb), ind_ub(nb), lda_ub(nb, 0);
-    std::vector<ChainRrluPlan> plans(nb);
+    std::vector<RrluRoute> plans(nb);
     size_t Mcap = 1, Ncap = 1, steps_cap = 1, pi_cap = 0, spec_cap = 0, dep_cap = 1, ind_cap = 1;
     for (size_t k = 0; k < nb; ++k) {
         const size_t b = order[k];
@@ -290,21 +290,20 @@ bool Tci2::chain_enqueue(bool forward, const TCI2Options& options, long ext_idx,
         need_cap = std::max(need_cap, rub);
         dep_ub[b] = forward ? Mub : Nub; // the kernel's rows are the dependent side in both directions
         ind_ub[b] = forward ? Nub : Mub;
-        if (dep_ub[b] > 65535 || ind_ub[b] > 65535 || !eng.chain_plan((int)dep_ub[b], (int)ind_ub[b], &plans[b])) {
+        if (dep_ub[b] > 65535 || ind_ub[b] > 65535 || !(plans[b] = eng.chain_route((int)dep_ub[b], (int)ind_ub[b])).ok()) {
             ++(one ? chain_stats_ext[2] : chain_stats[3]);
             return false;
         }
-        plans[b].code += forward ? 0 : 4; // (row-major tie order of the transposed problem)
         Mcap = std::max(Mcap, Mub);
         Ncap = std::max(Ncap, Nub);
         dep_cap = std::max(dep_cap, dep_ub[b]);
         ind_cap = std::max(ind_cap, ind_ub[b]);
         steps_cap = std::max(steps_cap, rub);
-        const bool fused = plans[b].kind == 1 && plans[b].fused;
+        const bool fused = plans[b].fused;
         if (!launch) pi_cap = std::max(pi_cap, dep_ub[b] * ind_ub[b]); // (a group chain evaluates every candidate matrix directly)
         if (!fused) {
             pi_cap = std::max(pi_cap, dep_ub[b] * ind_ub[b]); // (evaluated directly when the previous launch could not speculate)
-            if (k > 0 && plans[order[k - 1]].kind == 2) {
+            if (k > 0 && plans[order[k - 1]].on_xcd()) {
                 const size_t site = forward ? b : b + 1;
                 lda_ub[b] = dep_ub[order[k - 1]] * local_dims[site] + (forward ? eI[b + 1] : eJ[b]);
                 spec_cap = std::max(spec_cap, lda_ub[b] * ind_ub[b]);
@@ -373,12 +372,7 @@ bool Tci2::chain_enqueue(bool forward, const TCI2Options& options, long ext_idx,
         chain_.spec[0].reserve(spec_cap);
         chain_.spec[1].reserve(spec_cap);
     }
-    ChainBlock proto;
-    proto.off_piv = 32;
-    proto.off_rp = proto.off_piv + sizeof(double) * steps_cap;
-    proto.off_cp = proto.off_rp + sizeof(int) * Mcap;
-    proto.off_ts = round_up_sz(proto.off_cp + sizeof(int) * Ncap, 8);
-    proto.bytes = proto.off_ts + 16;
+    const RrluBlock proto = RrluBlock::layout(steps_cap, Mcap, Ncap, true);
     chain_.blocks.reserve(nb * proto.bytes);
     chain_.hblocks.reserve(nb * proto.bytes);
     chain_.dims.reserve(nb * 5 + 2); // {M, N, poison, lda} per bond, then one tile counter per bond (speculative evaluation)
@@ -491,25 +485,23 @@ void Tci2::chain_launch()
     const bool forward = chain_.forward, use_extras = chain_.use_extras, timed_events = chain_.timed_events;
     const size_t chi = chain_.chi, ind_cap = chain_.ind_cap, cap_side = chain_.cap_side;
     const ChainCommon& c = chain_.common;
-    const ChainBlock& proto = chain_.proto;
+    const RrluBlock& proto = chain_.proto;
     const std::vector<size_t>& order = chain_.order;
-    const std::vector<ChainRrluPlan>& plans = chain_.plans;
+    const std::vector<RrluRoute>& plans = chain_.plans;
     const std::vector<size_t>& dep_ub = chain_.dep_ub;
     const std::vector<size_t>& ind_ub = chain_.ind_ub;
     std::vector<unsigned>& tokens = chain_.tokens;
     hipStream_t st = eng.stream();
     // result blocks reach the host in ONE copy behind the chain
     auto block_of = [&](size_t b) {
-        ChainBlock k = proto;
+        RrluBlock k = proto;
         k.dev = chain_.blocks.get() + b * proto.bytes;
-        k.host = nullptr;
         return k;
     };
     {
         size_t reserve_words = 0; // the largest shape this handle can reach: the mailbox is sized once
-        ChainRrluPlan cp;
-        if (cap_side && eng.chain_plan((int)cap_side, (int)cap_side, &cp) && cp.kind == 2)
-            reserve_words = (rrlu_xcd_keys_bytes(cp.xcd) + rrlu_xcd_cols_bytes(cp.xcd, (int)cap_side)) / sizeof(unsigned long long);
+        const RrluRoute cr = cap_side ? eng.chain_route((int)cap_side, (int)cap_side) : RrluRoute();
+        if (cr.on_xcd()) reserve_words = cr.xcd_mailbox_words();
         eng.chain_begin(plans, reserve_words);
     }
     bool counted = false;
@@ -569,10 +561,10 @@ void Tci2::chain_launch()
         bool spec_pending = false; // the previous bond's launch evaluates this bond's candidate matrix
         for (size_t k = 0; !walk && k < nb; ++k) {
             const size_t b = order[k];
-            const ChainRrluPlan& pl = plans[b];
-            const bool fused = pl.kind == 1 && pl.fused;
+            const RrluRoute& pl = plans[b];
+            const bool fused = pl.fused;
             const bool spec_here = spec_pending && !fused;
-            const ChainBlock blk = block_of(b);
+            const RrluBlock blk = block_of(b);
             ChainPrepArgs pa;
             std::memset(&pa, 0, sizeof(pa));
             pa.b = (int)b;
@@ -583,11 +575,11 @@ void Tci2::chain_launch()
             pa.prev_b = -1;
             if (k > 0) {
                 const size_t pb = order[k - 1];
-                const ChainBlock pblk = block_of(pb);
+                const RrluBlock pblk = block_of(pb);
                 pa.prev_b = (int)pb;
-                pa.prev_iresult = reinterpret_cast<const int*>(pblk.dev + 16);
-                pa.prev_rowperm = reinterpret_cast<const int*>(pblk.dev + pblk.off_rp);
-                pa.prev_colperm = reinterpret_cast<const int*>(pblk.dev + pblk.off_cp);
+                pa.prev_iresult = pblk.iresult();
+                pa.prev_rowperm = pblk.row_perm();
+                pa.prev_colperm = pblk.col_perm();
                 pa.prev_token = tokens[pb];
             }
             chain_prep_launch(c, pa, st);
@@ -597,9 +589,9 @@ void Tci2::chain_launch()
             XcdSpecArgs sp;
             std::memset(&sp, 0, sizeof(sp));
             spec_pending = false;
-            if (solo && k + 1 < nb && pl.kind == 2) {
+            if (solo && k + 1 < nb && pl.on_xcd()) {
                 const size_t nx = order[k + 1];
-                if (!(plans[nx].kind == 1 && plans[nx].fused)) {
+                if (!plans[nx].fused) {
                     const size_t site = forward ? nx : nx + 1;
                     const ChainTab& H = forward ? c.HI : c.HJ;
                     const size_t hsite = forward ? nx + 1 : nx;
@@ -631,15 +623,15 @@ void Tci2::chain_launch()
         }
         if (!walk) { // the pivots of the last bond
             const size_t pb = order[nb - 1];
-            const ChainBlock pblk = block_of(pb);
+            const RrluBlock pblk = block_of(pb);
             ChainPrepArgs pa;
             std::memset(&pa, 0, sizeof(pa));
             pa.do_build = 0;
             pa.defer_host_writes = 0;
             pa.prev_b = (int)pb;
-            pa.prev_iresult = reinterpret_cast<const int*>(pblk.dev + 16);
-            pa.prev_rowperm = reinterpret_cast<const int*>(pblk.dev + pblk.off_rp);
-            pa.prev_colperm = reinterpret_cast<const int*>(pblk.dev + pblk.off_cp);
+            pa.prev_iresult = pblk.iresult();
+            pa.prev_rowperm = pblk.row_perm();
+            pa.prev_colperm = pblk.col_perm();
             pa.prev_token = tokens[pb];
             chain_prep_launch(c, pa, st);
         }
@@ -651,15 +643,15 @@ void Tci2::chain_launch()
             std::memset(&jobs, 0, sizeof(jobs));
             size_t max_rows = 1;
             for (size_t b = 0; b < nb; ++b) {
-                const ChainBlock blk = block_of(b);
+                const RrluBlock blk = block_of(b);
                 const size_t rub = std::max<size_t>(std::min({dep_ub[b], ind_ub[b], chi}), 1);
                 DevCore& core = cores[b];
                 core.buf.reserve(std::max<size_t>(dep_ub[b] * rub, 1));
                 LeftCoreJob& j = jobs.j[b];
                 j.lu = chain_.factors.get() + b * chain_.factors_stride;
                 j.dims = c.dims + b * 4;
-                j.iresult = reinterpret_cast<const int*>(blk.dev + 16);
-                j.row_perm = reinterpret_cast<const int*>(blk.dev + blk.off_rp);
+                j.iresult = blk.iresult();
+                j.row_perm = blk.row_perm();
                 j.core = core.buf.get();
                 j.S = (int)local_dims[b];
                 j.token = tokens[b];
@@ -715,7 +707,7 @@ void Tci2::chain_group_launch(const std::vector<Tci2*>& hs)
     }
     const size_t nb = lead->n_ - 1;
     const bool forward = lead->chain_.forward;
-    std::vector<ChainRrluPlan> gplans(nb);
+    std::vector<RrluRoute> gplans(nb);
     size_t side_ub = 0;
     if (ok) {
         for (size_t b = 0; b < nb && ok; ++b) {
@@ -724,8 +716,8 @@ void Tci2::chain_group_launch(const std::vector<Tci2*>& hs)
                 dm = std::max(dm, h->chain_.dep_ub[b]);
                 im = std::max(im, h->chain_.ind_ub[b]);
             }
-            ok = Engine::chain_group_plan((int)dm, (int)im, &gplans[b]);
-            gplans[b].code += forward ? 0 : 4;
+            gplans[b] = Engine::chain_group_route((int)dm, (int)im);
+            ok = gplans[b].ok();
         }
         for (Tci2* h : hs) side_ub = std::max(side_ub, h->chain_.cap_side);
     }
@@ -736,9 +728,8 @@ void Tci2::chain_group_launch(const std::vector<Tci2*>& hs)
     hipStream_t st = lead->eng.stream();
     size_t reserve_words = 0;
     {
-        ChainRrluPlan cp;
-        if (side_ub && Engine::chain_group_plan((int)side_ub, (int)side_ub, &cp))
-            reserve_words = (rrlu_xcd_keys_bytes(cp.xcd) + rrlu_xcd_cols_bytes(cp.xcd, (int)side_ub)) / sizeof(unsigned long long);
+        const RrluRoute cr = side_ub ? Engine::chain_group_route((int)side_ub, (int)side_ub) : RrluRoute();
+        if (cr.ok()) reserve_words = cr.xcd_mailbox_words();
     }
     std::vector<char> counted(nh, 0);
     bool locked = false;
@@ -766,17 +757,16 @@ void Tci2::chain_group_launch(const std::vector<Tci2*>& hs)
         lead->eng.chain_group_lock();
         locked = true;
         auto block_of = [&](Tci2* h, size_t b) {
-            ChainBlock k = h->chain_.proto;
+            RrluBlock k = h->chain_.proto;
             k.dev = h->chain_.blocks.get() + b * k.bytes;
-            k.host = nullptr;
             return k;
         };
         auto prev_of = [&](Tci2* h, size_t pb, ChainPrepArgs& pa) {
-            const ChainBlock pblk = block_of(h, pb);
+            const RrluBlock pblk = block_of(h, pb);
             pa.prev_b = (int)pb;
-            pa.prev_iresult = reinterpret_cast<const int*>(pblk.dev + 16);
-            pa.prev_rowperm = reinterpret_cast<const int*>(pblk.dev + pblk.off_rp);
-            pa.prev_colperm = reinterpret_cast<const int*>(pblk.dev + pblk.off_cp);
+            pa.prev_iresult = pblk.iresult();
+            pa.prev_rowperm = pblk.row_perm();
+            pa.prev_colperm = pblk.col_perm();
             pa.prev_token = h->chain_.tokens[pb];
         };
         chain_indep_group_launch(d_slots, (int)nh, (int)nb, st);
@@ -802,7 +792,7 @@ void Tci2::chain_group_launch(const std::vector<Tci2*>& hs)
                 h->chain_.tokens[b] = h->eng.chain_group_args(gplans[b], forward, h->chain_.pi.get(), h->chain_.common.dims + b * 4, h->chain_.chi,
                                                               h->chain_.tol, 0.0, block_of(h, b), (int)i, &ga.p[i], st);
             }
-            rrlu_xcd_group_launch_v(xcd_version(), gplans[b].xcd, ga, !forward, st);
+            gplans[b].launch_group(ga, !forward, st);
         }
         { // the pivots of the last bond
             ChainPrepGroupArgs pg;
@@ -868,7 +858,7 @@ void Tci2::chain_finish(const TCI2Options& options)
     const size_t nb = n_ - 1;
     const size_t K = (size_t)chain_.n_acc, cap = chain_.cap;
     const bool forward = chain_.forward;
-    const ChainBlock& proto = chain_.proto;
+    const RrluBlock& proto = chain_.proto;
     const auto wait_t0 = std::chrono::steady_clock::now();
     const hipError_t sync_err = hipStreamSynchronize(st);
     g_chain_wait_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - wait_t0).count();
@@ -924,9 +914,9 @@ void Tci2::chain_finish(const TCI2Options& options)
             const size_t b = chain_.order[(size_t)failed_k];
             const int* hd = chain_.hdims.get() + b * 4;
             const int* hi = reinterpret_cast<const int*>(chain_.hblocks.get() + b * proto.bytes + 16);
-            const ChainRrluPlan& pl = chain_.plans[b];
+            const RrluRoute& pl = chain_.plans[b];
             std::fprintf(stderr, "[t4a chain] bond %zu (k = %ld of %zu, %s) did not complete: dims %d x %d poisoned %d lda %d | npiv %d flag %d nan %d token %d (want %u) | plan kind %d %d x %d wg %d RPT %d CPT %d W %d\n",
-                         b, failed_k, nb, forward ? "forward" : "backward", hd[0], hd[1], hd[2], hd[3], hi[0], hi[1], hi[2], hi[3], chain_.tokens[b], pl.kind, pl.kM, pl.kN,
+                         b, failed_k, nb, forward ? "forward" : "backward", hd[0], hd[1], hd[2], hd[3], hi[0], hi[1], hi[2], hi[3], chain_.tokens[b], (int)pl.kind, pl.kM, pl.kN,
                          pl.xcd.wg, pl.xcd.RPT, pl.xcd.CPT, pl.xcd.W);
         }
     }
@@ -948,37 +938,19 @@ void Tci2::chain_finish(const TCI2Options& options)
         j_set[b].count = cnt;
         i_set[b + 1].d.clear();
         j_set[b].d.clear();
-        {   // work model of the factorisation, as Engine::luci counts it
-            double bytes = 8.0 * (double)M * (double)N, flops = 0.0;
-            for (int q = 0; q < rank; ++q) {
-                const double mr = (double)((long)M - q - 1), nr = (double)((long)N - q - 1);
-                bytes += 16.0 * mr * nr;
-                flops += 2.0 * mr * nr + mr;
-            }
-            eng.prof.v[8] += rank;
-            eng.prof.v[9] += bytes;
-            eng.prof.v[10] += flops;
-            eng.prof.v[11] += (double)M * (double)N;
+        {
+            float ms = 0.f;
             if (chain_.timed) { // device-side time stamps of the launch (wall_clock64: 100 MHz)
                 unsigned long long ts[2];
                 std::memcpy(ts, hb + proto.off_ts, sizeof(ts));
-                float ms = ts[1] > ts[0] ? (float)((double)(ts[1] - ts[0]) * 1e-5) : 0.f;
+                ms = ts[1] > ts[0] ? (float)((double)(ts[1] - ts[0]) * 1e-5) : 0.f;
                 if (chain_.timed_events) T4A_HIP(hipEventElapsedTime(&ms, chain_.t0[b], chain_.t1[b]));
                 eng.prof.v[0] += ms;
                 eng.prof.v[1] += 1.0;
-                auto& vs = eng.variant_stats_[chain_.plans[b].code];
-                vs[0] += ms;
-                vs[1] += 1.0;
-                vs[2] += bytes;
-                vs[3] += rank;
-                if (chain_.chi > 0 && (size_t)rank == chain_.chi) { // sub-aggregate: the launches that ran all max_bond_dim pivot steps
-                    auto& sat = eng.variant_stats_[chain_.plans[b].code + 10000000];
-                    sat[0] += ms;
-                    sat[1] += 1.0;
-                    sat[2] += bytes;
-                    sat[3] += rank;
-                }
             }
+            // (the sub-aggregate: the launches that ran all max_bond_dim pivot steps)
+            eng.rrlu_account(chain_.plans[b], !forward, (int)M, (int)N, rank, chain_.timed, ms, chain_.chi > 0 && (size_t)rank == chain_.chi);
+            eng.prof.v[11] += (double)M * (double)N;
         }
         if (abs_max > max_sample_value) max_sample_value = abs_max; // update_max_sample_value over Π (tensorci2.rs:2009-2014)
         bond_errors[b] = last_error; // = pivot_errors.back() (tensorci2.rs:2002-2004, :1040-1046)
@@ -1100,7 +1072,10 @@ void Tci2::chain_finish(const TCI2Options& options)
     sync_digits();
     chain_.tables_valid = false;
     // (only the kernels that ASSUME a placement: the one-workgroup / one-wave plans are booked as kind 2 as well but elect nobody — ADVICE round 4)
-    if (failed_timeout && chain_.plans[chain_.order[(size_t)failed_k]].kind == 2 && chain_.plans[chain_.order[(size_t)failed_k]].xcd.wg == 0) xcd_disable();
+    if (failed_timeout) {
+        const RrluKind kind = chain_.plans[chain_.order[(size_t)failed_k]].kind;
+        if (kind == RrluKind::SingleXcd || kind == RrluKind::MultiXcd) xcd_disable();
+    }
     prep_.valid = false;
     prefetch_.wanted = false;
     prefetch_.fill_site = -1;
