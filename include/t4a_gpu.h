@@ -683,6 +683,50 @@ t4a_gpu_status t4a_gpu_tt_inner_product(const t4a_gpu_tt* a, const t4a_gpu_tt* b
 t4a_gpu_status t4a_gpu_tt_reverse(const t4a_gpu_tt* h, t4a_gpu_tt** out);
 t4a_gpu_status t4a_gpu_tt_partial_sum(const t4a_gpu_tt* h, const size_t* dims, size_t n_dims, t4a_gpu_tt** out);
 
+/* =====================================================================================
+ * MPO<f64> (opaque handle; site tensors resident on the device) and the contraction of two MPOs
+ * tensor4all-simplett/src/mpo/: mpo.rs:35-480, contract_naive.rs:41-172, contract_zipup.rs:45-167, canonical.rs:35-89,
+ * factorize.rs:126-313, contraction.rs:17-42, dispatch.rs:8-92
+ * A site tensor is column-major [left, s1, s2, right]; a state is an MPO whose s2 is 1 (t4a_gpu_mpo_from_tt).
+ * ===================================================================================== */
+typedef struct t4a_gpu_mpo t4a_gpu_mpo;
+
+/* MPO::new(tensors) (mpo.rs:35-60).  dims4 is 4 x n_sites (left, s1, s2, right per site), cores the site tensors
+ * concatenated.  INVALID_ARGUMENT, checked before the device is touched: neighbouring bonds differ, first left or last right
+ * bond != 1, a zero dimension, a site of more than INT_MAX elements or a dimension (s1 * s2 included) above 65535.
+ * n_sites == 0 is the empty MPO. */
+t4a_gpu_status t4a_gpu_mpo_new(const size_t* dims4, size_t n_sites, const double* cores, t4a_gpu_mpo** out);
+void t4a_gpu_mpo_release(t4a_gpu_mpo* h);
+t4a_gpu_status t4a_gpu_mpo_clone(const t4a_gpu_mpo* h, t4a_gpu_mpo** out);
+t4a_gpu_status t4a_gpu_mpo_len(const t4a_gpu_mpo* h, size_t* out);
+t4a_gpu_status t4a_gpu_mpo_dims(const t4a_gpu_mpo* h, size_t* dims4 /* 4 x n_sites */);
+t4a_gpu_status t4a_gpu_mpo_site_tensor(const t4a_gpu_mpo* h, size_t site, double* out);
+/* MPO::evaluate (mpo.rs:245-340) for a batch: idx is 2 n_sites x n_pts column-major, [i1, j1, i2, j2, ...] per point; an index
+ * out of range or an empty MPO is INVALID_ARGUMENT.  sum (mpo.rs:341-392): the empty MPO sums to 0. */
+t4a_gpu_status t4a_gpu_mpo_evaluate(t4a_gpu_mpo* h, const size_t* idx, size_t n_pts, double* out);
+t4a_gpu_status t4a_gpu_mpo_sum(t4a_gpu_mpo* h, double* out);
+/* contract(a, b, algorithm, ContractionOptions{tolerance, max_bond_dim, factorize_method}) (dispatch.rs:67-92).
+ * algorithm: 0 Naive, 1 ZipUp, 2 Fit.  compress (Naive only): 0 = contract_naive(a, b, None), the exact product with bonds
+ * la * lb; != 0 = contract_naive(a, b, Some(options)), i.e. right-canonicalisation by QR (canonical.rs:35-89) and a left-to-right
+ * SVD sweep (contract_naive.rs:100-172).  ZipUp (contract_zipup.rs:45-167) always truncates.  method: 0 SVD, 1 RSVD, 2 LU, 3 CI
+ * (LU and CI fall back to SVD, factorize.rs:133-137).  max_bond_dim == 0 <=> None.  Truncation keeps singular values
+ * s >= tolerance * s_max, at most max_bond_dim of them, at least one (a zero matrix gives a bond of 1, not an error).
+ * INVALID_ARGUMENT: lengths differ, a.s2 != b.s1 at a site (the message names the site and both dimensions), a non-finite value
+ * reaching the SVD, a result site above INT_MAX elements.  NOT_IMPLEMENTED: Fit (contract_fit.rs:65-96) and RSVD (:305-313). */
+#define T4A_GPU_MPO_NAIVE 0
+#define T4A_GPU_MPO_ZIPUP 1
+#define T4A_GPU_MPO_FIT 2
+#define T4A_GPU_FACTORIZE_SVD 0
+#define T4A_GPU_FACTORIZE_RSVD 1
+#define T4A_GPU_FACTORIZE_LU 2
+#define T4A_GPU_FACTORIZE_CI 3
+t4a_gpu_status t4a_gpu_mpo_contract(const t4a_gpu_mpo* a, const t4a_gpu_mpo* b, int32_t algorithm, int32_t compress, int32_t method,
+                                    double tolerance, size_t max_bond_dim, t4a_gpu_mpo** out);
+/* Bridges to t4a_gpu_tt (this project's; no simplett counterpart).  Both are device-to-device copies of the cores:
+ * _from_tt gives site dims (d, 1) (a state as an MPO), _to_tt fuses (s1, s2) into one site index s1 + S1 * s2. */
+t4a_gpu_status t4a_gpu_mpo_from_tt(const t4a_gpu_tt* tt, t4a_gpu_mpo** out);
+t4a_gpu_status t4a_gpu_mpo_to_tt(const t4a_gpu_mpo* mpo, t4a_gpu_tt** out);
+
 /* Bridge between the tensor-train handles and the labelled tensors (tensor4all-treetn/src/simplett_bridge.rs).
  * _tt_to_tensors = tensor_train_to_treetn_with_names_and_site_indices (:118, :706-794) on a chain: out[s] carries the legs
  * [bond_labels[s-1], site_labels[s], bond_labels[s]], the two boundary legs of dimension 1 dropped (a single site gives

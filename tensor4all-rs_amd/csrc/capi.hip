@@ -14,6 +14,7 @@
 #include "tensorops.hpp"
 #include "aci.hpp"
 #include "globalsearch.hpp"
+#include "mpo.hpp"
 
 struct t4a_gpu_tci2 {
     t4a::Tci2 impl;
@@ -57,6 +58,10 @@ struct t4a_gpu_tt {
     t4a::TensorTrain impl;
     t4a_gpu_tt(const std::vector<std::array<size_t, 3>>& d, const double* data) : impl(d, data) {}
     t4a_gpu_tt(const std::vector<t4a::DevCore>& cores, hipStream_t src) : impl(cores, src) {}
+};
+
+struct t4a_gpu_mpo {
+    std::unique_ptr<t4a::Mpo> impl;
 };
 
 namespace t4a {
@@ -3635,6 +3640,129 @@ t4a_gpu_status t4a_gpu_aci_problem_errors(const t4a_gpu_aci_problem* h, double* 
         T4A_REQUIRE_PTR(h);
         if (pivot_errors) std::copy(h->impl->pivot_errors.begin(), h->impl->pivot_errors.end(), pivot_errors);
         if (pivot_scales) std::copy(h->impl->pivot_scales.begin(), h->impl->pivot_scales.end(), pivot_scales);
+    });
+}
+
+
+// ---- MPO<f64> and its contraction (tensor4all-simplett/src/mpo/) ----
+t4a_gpu_status t4a_gpu_mpo_new(const size_t* dims4, size_t n_sites, const double* cores, t4a_gpu_mpo** out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(out);
+        *out = nullptr;
+        if (n_sites) T4A_REQUIRE_PTR(dims4);
+        std::vector<std::array<size_t, 4>> d(n_sites);
+        for (size_t s = 0; s < n_sites; ++s) d[s] = {dims4[4 * s], dims4[4 * s + 1], dims4[4 * s + 2], dims4[4 * s + 3]};
+        mpo_validate_dims(d); // shape errors come before the device is touched
+        if (n_sites) T4A_REQUIRE_PTR(cores);
+        require_device();
+        *out = new t4a_gpu_mpo{std::make_unique<Mpo>(d, cores)};
+    });
+}
+
+void t4a_gpu_mpo_release(t4a_gpu_mpo* h) { delete h; }
+
+t4a_gpu_status t4a_gpu_mpo_clone(const t4a_gpu_mpo* h, t4a_gpu_mpo** out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(h);
+        T4A_REQUIRE_PTR(out);
+        *out = nullptr;
+        *out = new t4a_gpu_mpo{std::make_unique<Mpo>(h->impl->tt.cores, h->impl->tt.eng.stream(), h->impl->sd)};
+    });
+}
+
+t4a_gpu_status t4a_gpu_mpo_len(const t4a_gpu_mpo* h, size_t* out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(h);
+        T4A_REQUIRE_PTR(out);
+        *out = h->impl->len();
+    });
+}
+
+t4a_gpu_status t4a_gpu_mpo_dims(const t4a_gpu_mpo* h, size_t* dims4)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(h);
+        const auto d = h->impl->dims4();
+        if (!d.empty()) T4A_REQUIRE_PTR(dims4);
+        for (size_t s = 0; s < d.size(); ++s)
+            for (int k = 0; k < 4; ++k) dims4[4 * s + k] = d[s][k];
+    });
+}
+
+t4a_gpu_status t4a_gpu_mpo_site_tensor(const t4a_gpu_mpo* h, size_t site, double* out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(h);
+        std::vector<double> v = h->impl->tt.site_tensor_host(site);
+        if (!v.empty()) {
+            T4A_REQUIRE_PTR(out);
+            std::memcpy(out, v.data(), v.size() * sizeof(double));
+        }
+    });
+}
+
+t4a_gpu_status t4a_gpu_mpo_evaluate(t4a_gpu_mpo* h, const size_t* idx, size_t n_pts, double* out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(h);
+        if (n_pts == 0) return;
+        T4A_REQUIRE_PTR(idx);
+        T4A_REQUIRE_PTR(out);
+        std::vector<uint32_t> u = narrow_indices(idx, checked_mul(n_pts, 2 * h->impl->len(), "index buffer"));
+        std::vector<double> v = h->impl->evaluate(u.data(), n_pts);
+        std::memcpy(out, v.data(), n_pts * sizeof(double));
+    });
+}
+
+t4a_gpu_status t4a_gpu_mpo_sum(t4a_gpu_mpo* h, double* out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(h);
+        T4A_REQUIRE_PTR(out);
+        *out = h->impl->sum();
+    });
+}
+
+t4a_gpu_status t4a_gpu_mpo_contract(const t4a_gpu_mpo* a, const t4a_gpu_mpo* b, int32_t algorithm, int32_t compress, int32_t method,
+                                    double tolerance, size_t max_bond_dim, t4a_gpu_mpo** out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(a);
+        T4A_REQUIRE_PTR(b);
+        T4A_REQUIRE_PTR(out);
+        *out = nullptr;
+        if (algorithm < 0 || algorithm > 2) throw Error(T4A_GPU_INVALID_ARGUMENT, "unknown contraction algorithm");
+        if (method < 0 || method > 3) throw Error(T4A_GPU_INVALID_ARGUMENT, "unknown factorize method");
+        MpoContractionOptions o;
+        o.tolerance = tolerance;
+        o.max_bond_dim = max_bond_dim;
+        o.method = (MpoFactorizeMethod)method;
+        *out = new t4a_gpu_mpo{mpo_contract(*a->impl, *b->impl, (MpoAlgorithm)algorithm, compress != 0, o)};
+    });
+}
+
+t4a_gpu_status t4a_gpu_mpo_from_tt(const t4a_gpu_tt* tt, t4a_gpu_mpo** out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(tt);
+        T4A_REQUIRE_PTR(out);
+        *out = nullptr;
+        std::vector<std::array<size_t, 2>> sd;
+        for (const auto& c : tt->impl.cores) sd.push_back({c.s, 1});
+        *out = new t4a_gpu_mpo{std::make_unique<Mpo>(tt->impl.cores, tt->impl.eng.stream(), sd)};
+    });
+}
+
+t4a_gpu_status t4a_gpu_mpo_to_tt(const t4a_gpu_mpo* mpo, t4a_gpu_tt** out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(mpo);
+        T4A_REQUIRE_PTR(out);
+        *out = nullptr;
+        *out = new t4a_gpu_tt(mpo->impl->tt.cores, mpo->impl->tt.eng.stream());
     });
 }
 

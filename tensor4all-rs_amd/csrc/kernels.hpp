@@ -498,6 +498,9 @@ void tt_evaluate_launch(const TtCoreDesc* d_cores, int n_sites, int max_bond, co
 // ------------------------------------------------------------------------------------------------
 // mode 0: core -> left matrix (row l*S+s)   1: left matrix -> core   2: core -> right matrix (col s*R+r)   3: back
 void core_reshape_launch(const double* in, int L, int S, int R, int mode, double* out, hipStream_t stream);
+// out index k takes input index perm[k] (column-major, rank <= PERMUTE_MAX_RANK): out[e] = in[source of e]
+constexpr int PERMUTE_MAX_RANK = 16;
+void permute_launch(const double* in, const size_t* dims, const size_t* perm, int rank, double* out, hipStream_t stream);
 void tt_sum_launch(const TtCoreDesc* d_cores, int n_sites, int max_bond, double* d_out, hipStream_t stream);
 void tt_norm2_step_launch(const TtCoreDesc& core, const double* d_cur, bool first, double* d_nxt, hipStream_t stream);
 void tt_env_left_launch(const TtCoreDesc* d_cores, int split, int max_bond, const uint32_t* d_idx, int n_items,
@@ -506,6 +509,21 @@ void tt_env_right_launch(const TtCoreDesc* d_cores, int n_sites, int split, int 
                          int n_items, double* d_out, int ld, hipStream_t stream);
 void tt_env_dot_launch(const double* d_left, const double* d_right, int len, int ld, const uint32_t* d_il,
                        const uint32_t* d_ir, size_t n_pts, double* d_out, hipStream_t stream);
+
+// ------------------------------------------------------------------------------------------------
+// kernels_mpo.hip — site contraction of the naive MPO-MPO product (simplett/src/mpo/environment.rs:37-80), all sites in one launch:
+// job j writes C[(la*Lb+lb) + La*Lb*(s + S1*(t + T*(ra*Rb+rb)))] = sum_k A[la, s, k, ra] * B[lb, k, t, rb] (k ascending), which is
+// element e - off of the concatenated output range [off, off + size) of the launch.  Jobs ascend in `off`, jobs[0].off == 0; every
+// input and output site holds at most INT_MAX elements.
+// ------------------------------------------------------------------------------------------------
+struct MpoSiteJob {
+    const double* A; // [la, s1, k, ra]
+    const double* B; // [lb, k, t, rb]
+    double* C;       // [la*lb, s1, t, ra*rb]
+    unsigned long long off;
+    int la, s1, k, ra, lb, t, rb, pad_;
+};
+void mpo_site_contract_launch(const MpoSiteJob* d_jobs, int n_jobs, unsigned long long total, hipStream_t stream);
 
 // ------------------------------------------------------------------------------------------------
 // kernels_small.hip — the small-problem engine (round 6): the WHOLE optimize_with_finder loop of a small TensorCI2 problem

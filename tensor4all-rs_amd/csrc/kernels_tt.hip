@@ -4,9 +4,12 @@
 //   sum, norm2                             <- AbstractTensorTrain::sum / norm2 (simplett/src/traits.rs:231-354)
 //   left / right environments + dots       <- TTCache::evaluate_left / evaluate_right / evaluate_many
 //                                            (simplett/src/cache.rs:430-688, einsum_helper.rs:192-268)
+//   generic axis permutation               <- the dense tensor layer (tensorops.hip) and the zip-up MPO contraction (mpo.hip)
 // The chain contractions keep the reference's summation order (index ascending, separately rounded multiply and
 // add; built with -ffp-contract=off), so their results are bit-identical to the CPU oracle's.
 #include "kernels.hpp"
+
+#include <algorithm>
 
 namespace t4a {
 
@@ -208,7 +211,47 @@ __global__ void __launch_bounds__(256) tt_env_dot_kernel(const double* __restric
     }
 }
 
+struct PermuteArgs {
+    int rank;
+    unsigned long long total;
+    unsigned long long out_dims[PERMUTE_MAX_RANK];
+    unsigned long long src_stride[PERMUTE_MAX_RANK]; // stride in the input of output axis k
+};
+
+__global__ void __launch_bounds__(256) permute_kernel(const double* __restrict__ in, double* __restrict__ out, PermuteArgs a)
+{
+    const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
+    for (unsigned long long e = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; e < a.total; e += stride) {
+        unsigned long long rem = e, src = 0;
+        for (int k = 0; k < a.rank; ++k) {
+            const unsigned long long d = a.out_dims[k];
+            const unsigned long long q = rem / d;
+            src += (rem - q * d) * a.src_stride[k];
+            rem = q;
+        }
+        out[e] = in[src];
+    }
+}
+
 } // namespace
+
+void permute_launch(const double* in, const size_t* dims, const size_t* perm, int rank, double* out, hipStream_t stream)
+{
+    size_t total = 1;
+    for (int k = 0; k < rank; ++k) total *= dims[k];
+    if (total == 0) return;
+    unsigned long long in_stride[PERMUTE_MAX_RANK];
+    for (int k = 0; k < rank; ++k) in_stride[k] = k ? in_stride[k - 1] * dims[k - 1] : 1;
+    PermuteArgs a{};
+    a.rank = rank;
+    a.total = total;
+    for (int k = 0; k < rank; ++k) {
+        a.out_dims[k] = dims[perm[k]];
+        a.src_stride[k] = in_stride[perm[k]];
+    }
+    const unsigned blocks = (unsigned)std::min<size_t>((total + 255) / 256, 4096);
+    hipLaunchKernelGGL(permute_kernel, dim3(blocks), dim3(256), 0, stream, in, out, a);
+}
 
 void core_reshape_launch(const double* in, int L, int S, int R, int mode, double* out, hipStream_t stream)
 {

@@ -1,0 +1,359 @@
+// mpo.hip — MPO<f64> and the contraction of two MPOs on the device (see mpo.hpp).  Shape bookkeeping is host work; every
+// floating-point operation runs in gfx950 kernels: the naive site contraction (kernels_mpo.hip), the f64-MFMA GEMM and the
+// gathers (kernels_dense.hip), the axis permutation (kernels_tt.hip), the Householder QR and the Jacobi SVD (kernels_linalg.hip).
+#include "mpo.hpp"
+#include "tensorops.hpp"
+
+#include <algorithm>
+#include <climits>
+#include <string>
+
+namespace t4a {
+
+namespace {
+
+constexpr size_t MPO_DIM_MAX = 65535; // the tensor train's limit, which also holds for the fused site index s1*s2
+
+DevCore new_core(size_t l, size_t s, size_t r)
+{
+    DevCore c;
+    c.l = l;
+    c.s = s;
+    c.r = r;
+    c.buf.reserve(std::max<size_t>(c.size(), 1));
+    return c;
+}
+
+// the kernels and the GEMM index a site with int
+void check_count(size_t a, size_t b, size_t c, size_t d, const std::string& what)
+{
+    const unsigned long long lim = INT_MAX;
+    unsigned long long n = 1;
+    for (size_t x : {a, b, c, d}) {
+        if (x > lim || n * x > lim) throw Error(T4A_GPU_INVALID_ARGUMENT, what + " holds more than INT_MAX elements");
+        n *= x;
+    }
+}
+
+GemmDesc gemm_desc(int m, int n, int k, const double* A, int lda, const double* B, int ldb, double* C, int ldc)
+{
+    GemmDesc g{};
+    g.m = m;
+    g.n = n;
+    g.k = k;
+    g.A = A;
+    g.lda = lda;
+    g.B = B;
+    g.ldb = ldb;
+    g.C = C;
+    g.ldc = ldc;
+    g.alpha = 1.0;
+    g.beta = 0.0;
+    g.batch = 1;
+    return g;
+}
+
+// One contraction: every launch goes to the stream of `eng` (the engine of the left operand).
+struct Contractor {
+    Engine& eng;
+    const MpoContractionOptions& opt;
+    hipStream_t st;
+    DevBuf<double> u, s, vt, m1, m2, q, rr, x, y, cm;
+    std::vector<double> hs;
+
+    Contractor(Engine& e, const MpoContractionOptions& o) : eng(e), opt(o), st(e.stream()) {}
+
+    // factorize (factorize.rs:126-313) with left_orthogonal = true, SVD rank rule: cutoff = tolerance * s_max, values kept
+    // while rank < max_bond_dim and s >= cutoff; a zero matrix keeps nothing and is floored to rank 1 (not an error).  LU and
+    // CI fall back to SVD (:133-137).  U (M x k), S (k), Vt (k x N) stay in u / s / vt for left() / right().
+    size_t svd_rank(const double* d_mat, int M, int N)
+    {
+        if (opt.method == MpoFactorizeMethod::RSVD)
+            throw Error(T4A_GPU_NOT_IMPLEMENTED, "Factorization failed: RSVD factorization not yet implemented"); // :305-313
+        const int k = std::min(M, N);
+        u.reserve((size_t)M * k);
+        s.reserve(k);
+        vt.reserve((size_t)k * N);
+        eng.svd(d_mat, M, N, u.get(), s.get(), vt.get());
+        hs.resize(k);
+        T4A_HIP(hipMemcpyAsync(hs.data(), s.get(), sizeof(double) * k, hipMemcpyDeviceToHost, st));
+        eng.sync();
+        double s_max = 0.0;
+        for (double v : hs) s_max = std::max(s_max, v);
+        size_t rank = 0;
+        if (s_max > 0.0) {
+            const double cutoff = opt.tolerance * s_max;
+            for (int i = 0; i < k; ++i) {
+                if (opt.max_bond_dim != 0 && rank >= opt.max_bond_dim) break;
+                if (hs[i] < cutoff) break;
+                ++rank;
+            }
+        }
+        return std::max<size_t>(rank, 1);
+    }
+    // left = U[:, :rank] (M x rank)
+    void left(int M, int rank, double* out) { gather_launch(u.get(), M, nullptr, M, nullptr, rank, out, M, st); }
+    // right = diag(S[:rank]) Vt[:rank, :] (rank x N)
+    void right(int M, int N, int rank, double* out) { diag_scale_launch(vt.get(), std::min(M, N), rank, N, s.get(), true, out, rank, st); }
+
+    // contract_site_tensors (environment.rs:37-80) of every site in one launch
+    std::vector<DevCore> naive(const Mpo& a, const Mpo& b)
+    {
+        const size_t n = a.len();
+        std::vector<DevCore> out(n);
+        std::vector<MpoSiteJob> jobs(n);
+        unsigned long long off = 0;
+        for (size_t i = 0; i < n; ++i) {
+            const DevCore& x = a.tt.cores[i];
+            const DevCore& y = b.tt.cores[i];
+            const size_t s1 = a.sd[i][0], k = a.sd[i][1], t = b.sd[i][1];
+            check_count(x.l * y.l, s1, t, x.r * y.r, "contract_naive: site " + std::to_string(i));
+            out[i] = new_core(x.l * y.l, s1 * t, x.r * y.r);
+            MpoSiteJob& j = jobs[i];
+            j = MpoSiteJob{};
+            j.A = x.buf.get();
+            j.B = y.buf.get();
+            j.C = out[i].buf.get();
+            j.off = off;
+            j.la = (int)x.l;
+            j.s1 = (int)s1;
+            j.k = (int)k;
+            j.ra = (int)x.r;
+            j.lb = (int)y.l;
+            j.t = (int)t;
+            j.rb = (int)y.r;
+            off += out[i].size();
+        }
+        DevBuf<MpoSiteJob> d_jobs;
+        d_jobs.reserve(n);
+        T4A_HIP(hipMemcpyAsync(d_jobs.get(), jobs.data(), n * sizeof(MpoSiteJob), hipMemcpyHostToDevice, st));
+        mpo_site_contract_launch(d_jobs.get(), (int)n, off, st);
+        T4A_HIP(hipGetLastError());
+        eng.sync(); // `jobs` is pageable host memory, d_jobs goes out of scope
+        return out;
+    }
+
+    // right_canonicalize (canonical.rs:35-89): thin QR of each transposed left x (s1*s2*right) matricisation from the right;
+    // the site becomes Q^T (k = min(left, rest) rows), R^T is absorbed into the left neighbour
+    void right_canonicalize(std::vector<DevCore>& cores)
+    {
+        for (size_t i = cores.size() - 1; i >= 1; --i) {
+            DevCore& c = cores[i];
+            DevCore& p = cores[i - 1];
+            const int L = (int)c.l, rest = (int)(c.s * c.r);
+            const int k = std::min(L, rest);
+            m1.reserve((size_t)rest * L);
+            transpose_launch(c.buf.get(), L, rest, L, m1.get(), rest, st);
+            q.reserve((size_t)rest * k);
+            rr.reserve((size_t)k * L);
+            eng.qr(m1.get(), rest, L, q.get(), rr.get());
+            DevCore nc = new_core(k, c.s, c.r);
+            transpose_launch(q.get(), rest, k, rest, nc.buf.get(), k, st);
+            DevCore np = new_core(p.l, p.s, k);
+            const int pm = (int)(p.l * p.s);
+            GemmDesc g = gemm_desc(pm, k, L, p.buf.get(), pm, rr.get(), k, np.buf.get(), pm);
+            g.transB = 1; // prev (l*s x L) * R^T (L x k)
+            gemm_launch(g, st);
+            T4A_HIP(hipGetLastError());
+            eng.sync(); // the old cores are released below
+            c = std::move(nc);
+            p = std::move(np);
+        }
+    }
+
+    // compress_mpo (contract_naive.rs:100-172): right-canonicalise, then a left-to-right sweep of factorize; the right factor
+    // is absorbed into the next site
+    void compress(std::vector<DevCore>& cores)
+    {
+        const size_t n = cores.size();
+        if (n <= 1) return;
+        right_canonicalize(cores);
+        for (size_t i = 0; i + 1 < n; ++i) {
+            DevCore& c = cores[i];
+            DevCore& nx = cores[i + 1];
+            const int M = (int)(c.l * c.s), N = (int)c.r;
+            const size_t rank = svd_rank(c.buf.get(), M, N);
+            DevCore nc = new_core(c.l, c.s, rank);
+            left(M, (int)rank, nc.buf.get());
+            m2.reserve(rank * N);
+            right(M, N, (int)rank, m2.get());
+            DevCore nn = new_core(rank, nx.s, nx.r);
+            const int rest = (int)(nx.s * nx.r);
+            gemm_launch(gemm_desc((int)rank, rest, N, m2.get(), (int)rank, nx.buf.get(), N, nn.buf.get(), (int)rank), st);
+            T4A_HIP(hipGetLastError());
+            eng.sync();
+            c = std::move(nc);
+            nx = std::move(nn);
+        }
+    }
+
+    // contract_zipup (contract_zipup.rs:45-167).  Per site two pairwise contractions on the MFMA GEMM (never the three-operand
+    // sum, :118-127) and one permutation of the large intermediate; the small input site tensors are permuted so that both
+    // contracted index pairs come out adjacent:
+    //   A'[a, s, c, k] = A[a, s, k, c]                    B'[k, b, t, d] = B[b, k, t, d]
+    //   X[n, s, c, k, b] = sum_a R[n, a, b] A'[a, s, c, k]  (one GEMM per b)
+    //   Y[n, s, c, t, d] = sum_{k, b} X[(n, s, c), (k, b)] B'[(k, b), (t, d)]
+    //   C[n, s, t, c, d] = Y permuted, factorised as (n*s*t) x (c*d): left -> site, right -> the next remainder R[rank, c, d]
+    std::vector<DevCore> zipup(const Mpo& a, const Mpo& b)
+    {
+        const size_t n = a.len();
+        std::vector<DevCore> out;
+        DevBuf<double> rem, rem_next;
+        rem.reserve(1);
+        fill_launch(rem.get(), 1, 1.0, st); // R[new, a, b] = [[[1]]]
+        size_t N0 = 1;
+        for (size_t i = 0; i < n; ++i) {
+            const DevCore& A = a.tt.cores[i];
+            const DevCore& B = b.tt.cores[i];
+            const size_t La = A.l, S1 = a.sd[i][0], K = a.sd[i][1], Ra = A.r;
+            const size_t Lb = B.l, T = b.sd[i][1], Rb = B.r;
+            const std::string where = "contract_zipup: site " + std::to_string(i);
+            check_count(N0 * S1, Ra, K, Lb, where);
+            check_count(N0 * S1, Ra, T, Rb, where);
+            m1.reserve(A.size());
+            m2.reserve(B.size());
+            const size_t da[4] = {La, S1, K, Ra}, pa[4] = {0, 1, 3, 2};
+            const size_t db[4] = {Lb, K, T, Rb}, pb[4] = {1, 0, 2, 3};
+            permute_launch(A.buf.get(), da, pa, 4, m1.get(), st);
+            permute_launch(B.buf.get(), db, pb, 4, m2.get(), st);
+            const size_t xcols = S1 * Ra * K;
+            x.reserve(N0 * xcols * Lb);
+            GemmDesc g = gemm_desc((int)N0, (int)xcols, (int)La, rem.get(), (int)N0, m1.get(), (int)La, x.get(), (int)N0);
+            g.strideA = (long long)(N0 * La);
+            g.strideB = 0;
+            g.strideC = (long long)(N0 * xcols);
+            g.batch = (int)Lb;
+            gemm_launch(g, st);
+            const size_t rows = N0 * S1 * Ra, cols = T * Rb;
+            if (i == n - 1) { // last site: the trailing bonds are 1, Y is C = [n, s1, t, 1]
+                DevCore site = new_core(N0, S1 * T, 1);
+                gemm_launch(gemm_desc((int)rows, (int)cols, (int)(K * Lb), x.get(), (int)rows, m2.get(), (int)(K * Lb), site.buf.get(), (int)rows),
+                            st);
+                T4A_HIP(hipGetLastError());
+                eng.sync();
+                out.push_back(std::move(site));
+                break;
+            }
+            y.reserve(rows * cols);
+            gemm_launch(gemm_desc((int)rows, (int)cols, (int)(K * Lb), x.get(), (int)rows, m2.get(), (int)(K * Lb), y.get(), (int)rows), st);
+            const size_t dy[5] = {N0, S1, Ra, T, Rb}, py[5] = {0, 1, 3, 2, 4};
+            cm.reserve(rows * cols);
+            permute_launch(y.get(), dy, py, 5, cm.get(), st);
+            const int M = (int)(N0 * S1 * T), N = (int)(Ra * Rb);
+            const size_t rank = svd_rank(cm.get(), M, N);
+            DevCore site = new_core(N0, S1 * T, rank);
+            left(M, (int)rank, site.buf.get());
+            rem_next.reserve(rank * N);
+            right(M, N, (int)rank, rem_next.get());
+            T4A_HIP(hipGetLastError());
+            eng.sync();
+            std::swap(rem, rem_next);
+            N0 = rank;
+            out.push_back(std::move(site));
+        }
+        return out;
+    }
+};
+
+} // namespace
+
+void mpo_validate_dims(const std::vector<std::array<size_t, 4>>& d)
+{
+    const size_t n = d.size();
+    for (size_t i = 0; i + 1 < n; ++i)
+        if (d[i][3] != d[i + 1][0])
+            throw Error(T4A_GPU_INVALID_ARGUMENT, "Bond shape mismatch at site " + std::to_string(i) + ": left tensor has right_dim=" +
+                                                      std::to_string(d[i][3]) + ", right tensor has left_dim=" + std::to_string(d[i + 1][0]));
+    if (n && (d[0][0] != 1 || d[n - 1][3] != 1))
+        throw Error(T4A_GPU_INVALID_ARGUMENT,
+                    "Invalid boundary conditions: first tensor must have left_dim=1, last tensor must have right_dim=1");
+    for (size_t i = 0; i < n; ++i) {
+        const std::string site = "MPO site " + std::to_string(i);
+        for (size_t x : d[i])
+            if (x == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, site + " has a zero dimension");
+        check_count(d[i][0], d[i][1], d[i][2], d[i][3], site);
+        if (d[i][0] > MPO_DIM_MAX || d[i][3] > MPO_DIM_MAX || d[i][1] * d[i][2] > MPO_DIM_MAX)
+            throw Error(T4A_GPU_INVALID_ARGUMENT, site + ": dimensions above 65535 are not supported");
+    }
+}
+
+namespace {
+std::vector<std::array<size_t, 3>> fused(const std::vector<std::array<size_t, 4>>& d)
+{
+    mpo_validate_dims(d);
+    std::vector<std::array<size_t, 3>> f(d.size());
+    for (size_t i = 0; i < d.size(); ++i) f[i] = {d[i][0], d[i][1] * d[i][2], d[i][3]};
+    return f;
+}
+std::vector<std::array<size_t, 2>> pairs(const std::vector<std::array<size_t, 4>>& d)
+{
+    std::vector<std::array<size_t, 2>> p(d.size());
+    for (size_t i = 0; i < d.size(); ++i) p[i] = {d[i][1], d[i][2]};
+    return p;
+}
+} // namespace
+
+Mpo::Mpo(const std::vector<std::array<size_t, 4>>& dims4, const double* host_data) : tt(fused(dims4), host_data), sd(pairs(dims4)) {}
+
+Mpo::Mpo(const std::vector<DevCore>& cores, hipStream_t src_stream, const std::vector<std::array<size_t, 2>>& site_dims)
+    : tt(cores, src_stream), sd(site_dims)
+{
+}
+
+Mpo::Mpo(std::vector<DevCore>&& cores, const std::vector<std::array<size_t, 2>>& site_dims) : tt(std::vector<DevCore>{}, nullptr), sd(site_dims)
+{
+    tt.cores = std::move(cores);
+}
+
+std::vector<std::array<size_t, 4>> Mpo::dims4() const
+{
+    std::vector<std::array<size_t, 4>> d(len());
+    for (size_t i = 0; i < len(); ++i) d[i] = {tt.cores[i].l, sd[i][0], sd[i][1], tt.cores[i].r};
+    return d;
+}
+
+std::vector<double> Mpo::evaluate(const uint32_t* idx, size_t n_pts)
+{
+    const size_t n = len();
+    if (n == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "MPO is empty");
+    std::vector<uint32_t> f(n * n_pts);
+    for (size_t p = 0; p < n_pts; ++p)
+        for (size_t s = 0; s < n; ++s) {
+            const uint32_t i = idx[2 * n * p + 2 * s], j = idx[2 * n * p + 2 * s + 1];
+            if (i >= sd[s][0] || j >= sd[s][1])
+                throw Error(T4A_GPU_INVALID_ARGUMENT, "Index out of bounds: index " + std::to_string(std::max(i, j)) + " at site " +
+                                                          std::to_string(s) + " (max: " + std::to_string(std::max(sd[s][0], sd[s][1])) + ")");
+            f[n * p + s] = i + (uint32_t)sd[s][0] * j; // the fused index of the train
+        }
+    return tt.evaluate(f.data(), n_pts);
+}
+
+std::unique_ptr<Mpo> mpo_contract(Mpo& a, Mpo& b, MpoAlgorithm alg, bool compress, const MpoContractionOptions& opt)
+{
+    if (a.len() != b.len())
+        throw Error(T4A_GPU_INVALID_ARGUMENT, "MPO length mismatch: expected " + std::to_string(a.len()) + ", got " + std::to_string(b.len()));
+    const size_t n = a.len();
+    for (size_t i = 0; i < n; ++i)
+        if (a.sd[i][1] != b.sd[i][0])
+            throw Error(T4A_GPU_INVALID_ARGUMENT, "Shared shape mismatch at site " + std::to_string(i) + ": MPO A has site_dim_2=" +
+                                                      std::to_string(a.sd[i][1]) + ", MPO B has site_dim_1=" + std::to_string(b.sd[i][0]));
+    if (alg == MpoAlgorithm::Fit) // contract_fit.rs:65-96
+        throw Error(T4A_GPU_NOT_IMPLEMENTED, "Unsupported operation: simplett variational MPO fitting is not implemented; use contract_naive or "
+                                             "contract_zipup instead");
+    std::vector<std::array<size_t, 2>> sd(n);
+    for (size_t i = 0; i < n; ++i) sd[i] = {a.sd[i][0], b.sd[i][1]};
+    if (n == 0) return std::make_unique<Mpo>(std::vector<DevCore>{}, sd);
+    b.tt.eng.sync(); // b's cores are read on a's stream (TensorTrain::add)
+    Contractor c(a.tt.eng, opt);
+    std::vector<DevCore> cores;
+    if (alg == MpoAlgorithm::ZipUp) {
+        cores = c.zipup(a, b);
+    } else {
+        cores = c.naive(a, b);
+        if (compress) c.compress(cores);
+    }
+    a.tt.eng.sync();
+    return std::make_unique<Mpo>(std::move(cores), sd);
+}
+
+} // namespace t4a

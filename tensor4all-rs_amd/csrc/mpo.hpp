@@ -1,0 +1,50 @@
+// mpo.hpp — device-resident mirror of tensor4all-simplett's MPO<f64> and of the contraction of two MPOs
+// (crates/tensor4all-simplett/src/mpo/: mpo.rs:35-480, contract_naive.rs:41-172, contract_zipup.rs:45-167,
+//  canonical.rs:35-89, factorize.rs:126-313, contraction.rs:17-42, dispatch.rs:8-92).
+// A site tensor is column-major [left, s1, s2, right], which is the [left, s1*s2, right] block of a tensor train over the
+// fused site index s1 + S1*s2: an MPO is held as a TensorTrain over the fused index plus the (s1, s2) pair of every site, and
+// evaluate / sum / the handle lifetime are those of tt.hip.
+#pragma once
+
+#include "tt.hpp"
+
+namespace t4a {
+
+enum class MpoFactorizeMethod : int { SVD = 0, RSVD = 1, LU = 2, CI = 3 }; // factorize.rs:12-20
+enum class MpoAlgorithm : int { Naive = 0, ZipUp = 1, Fit = 2 };          // dispatch.rs:8-16
+
+struct MpoContractionOptions { // ContractionOptions::default() (contraction.rs:17-42)
+    double tolerance = 1e-12;
+    size_t max_bond_dim = 0; // 0 == None
+    MpoFactorizeMethod method = MpoFactorizeMethod::SVD;
+};
+
+// MPO::new (mpo.rs:35-60) on the host, before any device call: equal neighbouring bonds, first left and last right bond 1.
+// This backend also refuses a zero dimension, a site of more than INT_MAX elements (the kernels index with int) and a
+// dimension (fused s1*s2 included) above the tensor train's 65535.  Throws INVALID_ARGUMENT.
+void mpo_validate_dims(const std::vector<std::array<size_t, 4>>& dims4);
+
+class Mpo {
+public:
+    // dims4: (left, s1, s2, right) per site; host_data: the site tensors concatenated, each column-major
+    Mpo(const std::vector<std::array<size_t, 4>>& dims4, const double* host_data);
+    // copy of device cores (fused site index) with their (s1, s2) pairs
+    Mpo(const std::vector<DevCore>& cores, hipStream_t src_stream, const std::vector<std::array<size_t, 2>>& site_dims);
+    // adopt device cores whose producing stream has been synchronised (no copy)
+    Mpo(std::vector<DevCore>&& cores, const std::vector<std::array<size_t, 2>>& site_dims);
+
+    size_t len() const { return tt.len(); }
+    std::vector<std::array<size_t, 4>> dims4() const;
+    // evaluate (mpo.rs:245-340) for a batch: idx is 2 n_sites x n_pts column-major, [i1, j1, i2, j2, ...] per point
+    std::vector<double> evaluate(const uint32_t* idx, size_t n_pts);
+    double sum() { return tt.sum(); } // mpo.rs:341-392 (the empty MPO sums to 0)
+
+    TensorTrain tt;
+    std::vector<std::array<size_t, 2>> sd; // (s1, s2) per site
+};
+
+// contract(a, b, algorithm, options) (dispatch.rs:67-92).  Naive with compress == false is contract_naive(a, b, None);
+// Fit answers NOT_IMPLEMENTED after the shape checks, RSVD where the reference's factorize is reached.
+std::unique_ptr<Mpo> mpo_contract(Mpo& a, Mpo& b, MpoAlgorithm alg, bool compress, const MpoContractionOptions& opt);
+
+} // namespace t4a

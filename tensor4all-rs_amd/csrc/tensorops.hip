@@ -68,28 +68,6 @@ size_t qr_retained_rank(const double* r, size_t k, size_t n, double rtol)
 
 namespace {
 
-struct PermuteArgs {
-    int rank;
-    unsigned long long total;
-    unsigned long long out_dims[TENSOR_MAX_RANK];
-    unsigned long long src_stride[TENSOR_MAX_RANK]; // stride in the input of output axis k
-};
-
-__global__ void __launch_bounds__(256) permute_kernel(const double* __restrict__ in, double* __restrict__ out, PermuteArgs a)
-{
-    const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
-    for (unsigned long long e = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; e < a.total; e += stride) {
-        unsigned long long rem = e, src = 0;
-        for (int k = 0; k < a.rank; ++k) {
-            const unsigned long long d = a.out_dims[k];
-            const unsigned long long q = rem / d;
-            src += (rem - q * d) * a.src_stride[k];
-            rem = q;
-        }
-        out[e] = in[src];
-    }
-}
-
 __global__ void __launch_bounds__(256) diag_scale_kernel(const double* __restrict__ in, int ldi, int rows, int cols,
                                                          const double* __restrict__ s, int by_row, double* __restrict__ out, int ldo)
 {
@@ -123,17 +101,7 @@ void tensor_permute(Engine& e, const TensorView& t, const std::vector<size_t>& p
         T4A_HIP(hipMemcpyAsync(d_out, t.d_data, total * sizeof(double), hipMemcpyDeviceToDevice, e.stream()));
         return;
     }
-    std::vector<unsigned long long> in_stride(r, 1);
-    for (size_t k = 1; k < r; ++k) in_stride[k] = in_stride[k - 1] * t.dims[k - 1];
-    PermuteArgs a{};
-    a.rank = (int)r;
-    a.total = total;
-    for (size_t k = 0; k < r; ++k) {
-        a.out_dims[k] = t.dims[perm[k]];
-        a.src_stride[k] = in_stride[perm[k]];
-    }
-    const unsigned blocks = (unsigned)std::min<size_t>((total + 255) / 256, 4096);
-    hipLaunchKernelGGL(permute_kernel, dim3(blocks), dim3(256), 0, e.stream(), t.d_data, d_out, a);
+    permute_launch(t.d_data, t.dims.data(), perm.data(), (int)r, d_out, e.stream());
     T4A_HIP(hipGetLastError());
 }
 

@@ -10,7 +10,7 @@
 
 namespace t4a {
 
-constexpr int TENSOR_MAX_RANK = 16;
+constexpr int TENSOR_MAX_RANK = PERMUTE_MAX_RANK;
 
 struct SvdPolicy { // truncation.rs:137-147; default relative / per value / 1e-12 (svd.rs:80-87)
     double threshold = 1e-12;

@@ -2122,3 +2122,9 @@ def tensors_to_tensor_train(tensors):
     h = c_void_p()
     _check(_lib.t4a_gpu_tensors_to_tt(arr if tensors else None, c_size_t(len(tensors)), ctypes.byref(h)))
     return SimpleTensorTrain._adopt(h)
+
+
+# MPO<f64> and mpo::contract (simplett/src/mpo/): module t4a_amd.mpo, the dispatching `contract` stays under its module name there
+# (t4a_amd.contract is the labelled-tensor network contraction)
+from . import mpo  # noqa: E402
+from .mpo import MPO, ContractionOptions, ContractionAlgorithm, FactorizeMethod, contract_naive, contract_zipup  # noqa: E402,F401
