@@ -16,6 +16,11 @@ N > 1 : weak scaling over PartitionedTT-style patches (BASELINE.json configs[4],
 
 Prints ONE JSON line on rank 0 (see the contract in the task description).  Inputs are generated on the device
 (built-in functor), so the timed region starts with everything resident in HBM.
+
+A plain run does only what the headline figure needs: set-up, warm-up, the timed steps, --dump-outputs, the line (its roofline
+block is computed from the timed steps' own profile and the committed PMC / MFMA summaries).  --full adds what takes runs of its
+own after the timed steps: the CPU baseline, the aux block (other BASELINE.json configurations and aux.components), the exchange
+floor re-measured by tools/xcd_bench, HIP-event launch times and, at N > 1, the same sweeps without the patch-core gather.
 """
 import argparse
 import json
@@ -94,14 +99,18 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-aux", action="store_true", help="skip the cfg2 / cfg4 / cfg5 single-GPU timings of the aux block")
+    ap.add_argument("--full", action="store_true",
+                    help="headline mode: after the timed steps, also measure what the headline figure does not need — the CPU baseline, "
+                         "the aux block, the exchange floor (tools/xcd_bench), HIP-event launch times and, at N > 1, the sweeps without "
+                         "the patch-core gather; the --no-* options below drop parts of it")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-aux", action="store_true", help="with --full: skip the cfg2 / cfg4 / cfg5 single-GPU timings of the aux block")
     ap.add_argument("--no-components", action="store_true",
-                    help="skip aux.components (tools/bench_components.py: callback path, rook, tree, quantics, ACI, tensor-train utilities, "
-                         "dense kernels, each with the CPU oracle's time beside it; about a minute)")
+                    help="with --full: skip aux.components (tools/bench_components.py: callback path, rook, tree, quantics, ACI, "
+                         "tensor-train utilities, dense kernels, each with the CPU oracle's time beside it; about a minute)")
     ap.add_argument("--no-floor", action="store_true",
-                    help="do not start tools/xcd_bench (a second GPU process) for the exchange floor: use the committed constant — for "
-                         "runs under rocprofv3, whose preload and counters a child process would inherit")
+                    help="with --full: do not start tools/xcd_bench (a second GPU process) for the exchange floor: use the committed "
+                         "constant — for runs under rocprofv3, whose preload and counters a child process would inherit")
     ap.add_argument("--mode", choices=["headline", "site-shard", "patch-farm", "pi-shard"], default="headline",
                     help="headline: BASELINE.json configs[2] (N = 1) / patch farm (N > 1).  site-shard: configs[3] — d = 40, chi = 512, "
                          "bond chain replicated on every rank, fill_site_tensors sharded by site, one device-resident core "
@@ -238,7 +247,7 @@ def main():
     # calibration outside the timed region: the same sweeps with HIP events around every rrLU launch (the timed region uses the
     # kernels' own start / end stamps: event records between the launches of a chain would be two more packets per bond)
     ev_ms = {}
-    if world == 1:
+    if world == 1 and args.full:
         tci.profile_reset()
         tci.set_chain(True, event_timing=True)
         tci.optimize(opts(4), final_sweep1site=False)
@@ -251,13 +260,14 @@ def main():
     per_rank_ms = [dt / args.steps * 1e3]
     gather_view = None
     if world > 1:
-        # what the 8-GPU run needs to be read against (round-4 review, item 10): every rank's own time per step, and what the
-        # patch-core all-gather costs where it is NOT hidden — the same K sweeps once more without it, outside the timed region
+        # what the 8-GPU run needs to be read against (round-4 review, item 10): every rank's own time per step, and (--full) what
+        # the patch-core all-gather costs where it is NOT hidden — the same K sweeps once more without it, outside the timed region
         all_dt = [torch.zeros(1, dtype=torch.float64, device="cuda") for _ in range(world)]
         dist.all_gather(all_dt, dt_t)
         per_rank_ms = [float(t.item()) / args.steps * 1e3 for t in all_dt]
         dist.all_reduce(dt_t, op=dist.ReduceOp.MAX)
         dist.all_reduce(fl_t, op=dist.ReduceOp.SUM)
+    if world > 1 and args.full:
         barrier()
         t1 = time.perf_counter()
         for _ in range(args.steps):
@@ -288,7 +298,7 @@ def main():
         dom = max(variants, key=lambda v: v["ms"]) if variants else None
         dom_steps = dom["steps"] / max(dom["launches"], 1) if dom else float(shapes[N_SITES // 2][2])
         achieved = bytes_per_launch / (rrlu_ms_avg * 1e-3) / 1e9 if rrlu_ms_avg > 0 else 0.0
-        floor_us, floor_src = exchange_floor(skip=args.no_floor)
+        floor_us, floor_src = exchange_floor(skip="--no-floor" if args.no_floor else None if args.full else "a run without --full")
         out = {
             "metric": "TCI2 full-sweep GF/s (d=30, chi=256 fp64)",
             "value": flops_all / dt_max / 1e9,
@@ -349,7 +359,7 @@ def main():
                 "avg_launch_ms_source": "device-side time stamps of rank 0 (wall_clock64) in the timed region",
                 "avg_launch_ms_hip_events": ev_ms.get(int(prof["dom_code"])),
                 "avg_launch_ms_hip_events_source": "hipEventRecord around every launch of this instantiation on the handle's stream, two "
-                                                   "extra sweeps after the timed region",
+                                                   "extra sweeps after the timed region (--full at N = 1; null otherwise)",
                 # the kernel is a chain of dependent pivot steps; each step needs one key all-gather and one pivot-column
                 # hand-off between the workgroups of one XCD: the honest bound is latency, not bandwidth.  The floor is the
                 # measured cost of exactly that exchange with no arithmetic around it (tools/xcd_bench.hip on MI355X:
@@ -384,9 +394,9 @@ def main():
                         "resident (one XCD), the kernel is bound by the per-pivot exchange and instruction latency",
             },
         }
-        if world == 1 and not args.no_cpu_baseline:  # reported on rank 0 at N = 1 only
+        if world == 1 and args.full and not args.no_cpu_baseline:  # reported on rank 0 at N = 1 only
             out["cpu_baseline"] = cpu_baseline(tci, spec)
-        if world == 1 and not args.no_aux:
+        if world == 1 and args.full and not args.no_aux:
             out["aux"] = aux_timings()
             if not args.no_components:
                 try:
@@ -440,17 +450,18 @@ XCD_EXCHANGE_FLOOR_US_R4 = 1.12  # what `tools/xcd_bench floor` measured on the 
 XCD_EXCHANGE_FLOOR_US = 1715 / 2380.0  # tools/xcd_bench.hip on MI355X, round 2 (profiles/r02_xcd_bench.log): the fallback of exchange_floor()
 
 
-def exchange_floor(skip=False):
+def exchange_floor(skip=None):
     """(us, source) of the single-XCD exchange floor: one pivot step's key all-gather + 700-row column hand-off + two barriers
     between 32 workgroups of one XCD with no arithmetic around it.  Re-measured on THIS box by `tools/xcd_bench floor` (built
-    by __graft_entry__.build()); the round-2 constant when the binary is missing or fails."""
+    by __graft_entry__.build()); the round-2 constant when the binary is missing or fails.  skip: why not to re-measure it (the
+    round-4 constant is returned with that reason), or None."""
     exe = os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools", "xcd_bench")
     # a fresh child process (never an exec); a profiler's preload and its variables stay with this process (ADVICE round 4)
     env = {k: v for k, v in os.environ.items() if k != "LD_PRELOAD" and not k.startswith(("ROCP", "ROCPROF", "ROCTX", "HSA_TOOLS"))}
     under_profiler = len(env) != len(os.environ)
     if skip or under_profiler:
         return XCD_EXCHANGE_FLOOR_US_R4, ("constant: tools/xcd_bench floor as measured by the round-4 bench runs (1.12 us; profiles/r04_bench_n1.json)"
-                                          + (" - not re-measured: this run is profiled" if under_profiler else " - not re-measured: --no-floor"))
+                                          " - not re-measured: " + (skip or "this run is profiled"))
     try:
         out = subprocess.run([exe, "floor"], capture_output=True, text=True, timeout=60, env=env).stdout
         for line in out.splitlines():

@@ -106,3 +106,28 @@ def test_bench_dump_outputs(tmp_path):
         assert p == n - 1 or arrays[f"j_set_{p:02d}"].shape == (links[p + 1], n - 1 - p)
         assert np.isfinite(arrays[f"site_tensor_{p:02d}"]).all()
     assert arrays["history_ranks"].tolist() == [256.0, 256.0] and np.isfinite(arrays["history_errors"]).all()
+
+
+def test_bench_plain_run_does_only_the_headline_work():
+    """A plain run times its steps and prints the line; what takes runs of its own after the timed steps (CPU baseline, aux block,
+    exchange floor re-measured by tools/xcd_bench, HIP-event launch times) comes with --full only."""
+    line = _one_line(["--gpus", "1", "--steps", "1", "--warmup", "0"])
+    assert line["value"] > 0 and line["ms_per_step"] > 0
+    assert "cpu_baseline" not in line and "aux" not in line
+    roof = line["roofline"]
+    assert roof["avg_launch_ms"] > 0 and roof["avg_launch_ms_hip_events"] is None
+    assert roof["latency_view"]["exchange_floor_source"].endswith("not re-measured: a run without --full")
+
+
+def test_bench_full_run_keeps_the_extras():
+    """--full: the CPU baseline with its pivot check against the device, the aux block with its identity checks and the HIP-event
+    launch times (--no-components leaves out aux.components, about a minute)."""
+    line = _one_line(["--gpus", "1", "--steps", "1", "--warmup", "0", "--full", "--no-components"])
+    cb = line["cpu_baseline"]
+    assert cb["value"] > 0 and cb["pivots_identical_to_device"] is True
+    aux = line["aux"]
+    assert not [k for k in aux if k.endswith("_error")] and "components" not in aux
+    assert aux["cfg2_time_to_solution_ms"] > 0 and aux["cfg5_patch_max_link_dim"] == 128 and aux["cfg4_size_max_link_dim"] == 512
+    assert aux["cfg5_side_by_side_results_identical"] is True and aux["cfg5_group_results_identical"] is True
+    roof = line["roofline"]
+    assert roof["avg_launch_ms_hip_events"] > 0 and roof["latency_view"]["exchange_floor_us"] > 0
