@@ -26,24 +26,8 @@ struct t4a_gpu_treetci {
     t4a_gpu_treetci(const std::vector<size_t>& d, const t4a::TreeGraph& g) : impl(d, g) {}
 };
 
-struct t4a_gpu_tensor {
-    t4a::DevBuf<double> buf;
-    std::vector<size_t> dims;
-    std::vector<int64_t> labels;
-    size_t size() const
-    {
-        size_t n = 1;
-        for (size_t d : dims) n *= d;
-        return n;
-    }
-    t4a::TensorView view() const
-    {
-        t4a::TensorView v;
-        v.d_data = buf.get();
-        v.dims = dims;
-        v.labels = labels;
-        return v;
-    }
+struct t4a_gpu_tensor : t4a::OwnedTensor {
+    explicit t4a_gpu_tensor(t4a::OwnedTensor&& t) : t4a::OwnedTensor(std::move(t)) {}
 };
 
 struct t4a_gpu_qtci {
@@ -1410,7 +1394,7 @@ t4a_gpu_status t4a_gpu_svd_f64(const double* a, size_t m, size_t n, double* u, d
         const size_t count = checked_mul(m, n, "matrix shape");
         require_int_dims({m, n}, "matrix shape");
         if (count == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "SVD of an empty matrix");
-        if (m > 65535 || n > 65535) throw Error(T4A_GPU_NOT_IMPLEMENTED, "svd: dimensions above 65535 are not supported");
+        Engine::require_factor_dims(m, n, "svd: dimensions");
         T4A_REQUIRE_PTR(a);
         T4A_REQUIRE_PTR(u);
         T4A_REQUIRE_PTR(s);
@@ -1439,7 +1423,7 @@ t4a_gpu_status t4a_gpu_rsvd_f64(const double* a, size_t m, size_t n, size_t k, s
         const size_t count = checked_mul(m, n, "matrix shape");
         require_int_dims({m, n}, "matrix shape");
         if (count == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "SVD of an empty matrix");
-        if (m > 65535 || n > 65535) throw Error(T4A_GPU_NOT_IMPLEMENTED, "svd: dimensions above 65535 are not supported");
+        Engine::require_factor_dims(m, n, "svd: dimensions");
         if (k == 0 || k > std::min(m, n)) throw Error(T4A_GPU_INVALID_ARGUMENT, "rsvd: the rank must be between 1 and min(m, n)");
         T4A_REQUIRE_PTR(a);
         T4A_REQUIRE_PTR(u);
@@ -1521,7 +1505,7 @@ t4a_gpu_status t4a_gpu_qr_f64(const double* a, size_t m, size_t n, double* q, do
         const size_t count = checked_mul(m, n, "matrix shape");
         require_int_dims({m, n}, "matrix shape");
         if (count == 0) return;
-        if (m > 65535 || n > 65535) throw Error(T4A_GPU_NOT_IMPLEMENTED, "qr: dimensions above 65535 are not supported");
+        Engine::require_factor_dims(m, n, "qr: dimensions");
         T4A_REQUIRE_PTR(a);
         T4A_REQUIRE_PTR(q);
         T4A_REQUIRE_PTR(r);
@@ -2684,50 +2668,27 @@ t4a_gpu_status t4a_gpu_tensor_svd_f64(const double* t, const size_t* dims, const
         TensorView tv = host_view(dims, labels, rank);
         if (n_left) T4A_REQUIRE_PTR(left_labels);
         const UnfoldPlan un = plan_unfold_split(tv, std::vector<int64_t>(left_labels, left_labels + n_left));
-        SvdPolicy pol = convert_policy(policy);
-        if (truncate) { // validated before any linear algebra (svd/tests/mod.rs:120-160)
-            if (has_max_bond_dim && max_bond_dim == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "max_bond_dim must be positive when specified");
-            if (!std::isfinite(pol.threshold) || pol.threshold < 0.0)
-                throw Error(T4A_GPU_INVALID_ARGUMENT, "Invalid SVD truncation threshold: threshold must be finite and non-negative");
-        }
-        const size_t m = un.m, n = un.n, k = std::min(m, n), count = tv.size();
-        if (count == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "SVD of an empty tensor");
-        if (m > 65535 || n > 65535) throw Error(T4A_GPU_NOT_IMPLEMENTED, "svd: unfolded dimensions above 65535 are not supported");
+        const SvdOptions opts{truncate != 0, convert_policy(policy), has_max_bond_dim != 0, max_bond_dim};
+        opts.validate();
+        require_factorizable(un, "svd", "SVD");
         T4A_REQUIRE_PTR(t);
         T4A_REQUIRE_PTR(u);
         T4A_REQUIRE_PTR(s);
         T4A_REQUIRE_PTR(v);
         std::lock_guard<std::mutex> lock(g_dense_mutex);
         Engine& e = dense_engine();
-        double* d_t = e.pi(2 * count);
-        upload(e, d_t, t, count);
+        double* d_t = tensor_staging(e, tv.size());
+        upload(e, d_t, t, tv.size());
         tv.d_data = d_t;
-        double* d_mat = d_t + count;
-        tensor_permute(e, tv, un.perm, d_mat);
-        e.d_tmp.reserve(m * k + k + k * n + n * k);
-        double* d_u = e.d_tmp.get();
-        double* d_s = d_u + m * k;
-        double* d_vt = d_s + k;
-        double* d_v = d_vt + k * n;
-        e.svd(d_mat, (int)m, (int)n, d_u, d_s, d_vt);
-        std::vector<double> hs(k);
-        download(e, hs.data(), d_s, k);
-        size_t keep = k;
-        if (truncate) {
-            keep = svd_retained_rank(hs.data(), k, pol);
-            if (has_max_bond_dim) keep = std::min(keep, max_bond_dim);
-            keep = std::max<size_t>(keep, 1);
-        } else {
-            keep = std::max<size_t>(k, 1);
-        }
-        keep = std::min(keep, k);
-        *r = keep;
-        std::copy(hs.begin(), hs.begin() + keep, s);
-        download(e, u, d_u, m * keep);
+        const UnfoldedFactors f = tensor_svd(e, tv, un, opts);
+        *r = f.keep;
+        std::copy(f.s.begin(), f.s.begin() + f.keep, s);
+        download(e, u, f.d_left, f.m * f.keep);
         // V [n x keep] = (first `keep` rows of V^T)^T
-        transpose_launch(d_vt, (int)keep, (int)n, (int)k, d_v, (int)n, e.stream());
+        e.d_tmp2.reserve(f.n * f.keep);
+        transpose_launch(f.d_right, (int)f.keep, (int)f.n, (int)f.k, e.d_tmp2.get(), (int)f.n, e.stream());
         T4A_HIP(hipGetLastError());
-        download(e, v, d_v, n * keep);
+        download(e, v, e.d_tmp2.get(), f.n * f.keep);
     });
 }
 
@@ -2740,49 +2701,44 @@ t4a_gpu_status t4a_gpu_tensor_qr_f64(const double* t, const size_t* dims, const 
         TensorView tv = host_view(dims, labels, rank);
         if (n_left) T4A_REQUIRE_PTR(left_labels);
         const UnfoldPlan un = plan_unfold_split(tv, std::vector<int64_t>(left_labels, left_labels + n_left));
-        const double tol = has_rtol ? rtol : 1e-15; // default_qr_rtol (qr.rs:62-66)
-        if (truncate && (!std::isfinite(tol) || tol < 0.0))
-            throw Error(T4A_GPU_INVALID_ARGUMENT, "Invalid rtol value: rtol must be finite and non-negative");
-        const size_t m = un.m, n = un.n, k = std::min(m, n), count = tv.size();
-        if (count == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "QR of an empty tensor");
-        if (m > 65535 || n > 65535) throw Error(T4A_GPU_NOT_IMPLEMENTED, "qr: unfolded dimensions above 65535 are not supported");
+        const QrOptions opts{truncate != 0, has_rtol ? rtol : QrOptions().rtol};
+        opts.validate();
+        require_factorizable(un, "qr", "QR");
         T4A_REQUIRE_PTR(t);
         T4A_REQUIRE_PTR(q);
         T4A_REQUIRE_PTR(r_factor);
         std::lock_guard<std::mutex> lock(g_dense_mutex);
         Engine& e = dense_engine();
-        double* d_t = e.pi(2 * count);
-        upload(e, d_t, t, count);
+        double* d_t = tensor_staging(e, tv.size());
+        upload(e, d_t, t, tv.size());
         tv.d_data = d_t;
-        double* d_mat = d_t + count;
-        tensor_permute(e, tv, un.perm, d_mat);
-        e.d_tmp.reserve(m * k + 2 * k * n);
-        double* d_q = e.d_tmp.get();
-        double* d_r = d_q + m * k;
-        double* d_rk = d_r + k * n;
-        e.qr(d_mat, (int)m, (int)n, d_q, d_r);
-        std::vector<double> hr(k * n);
-        download(e, hr.data(), d_r, k * n);
-        size_t keep = k;
-        if (truncate) keep = std::min(qr_retained_rank(hr.data(), k, n, tol), k);
-        *r = keep;
-        download(e, q, d_q, m * keep);
+        const UnfoldedFactors f = tensor_qr(e, tv, un, opts);
+        *r = f.keep;
+        download(e, q, f.d_left, f.m * f.keep);
         // leading `keep` rows of R with leading dimension keep
-        gather_launch(d_r, (int)k, nullptr, (int)keep, nullptr, (int)n, d_rk, (int)keep, e.stream());
+        e.d_tmp2.reserve(f.keep * f.n);
+        gather_launch(f.d_right, (int)f.k, nullptr, (int)f.keep, nullptr, (int)f.n, e.d_tmp2.get(), (int)f.keep, e.stream());
         T4A_HIP(hipGetLastError());
-        download(e, r_factor, d_rk, keep * n);
+        download(e, r_factor, e.d_tmp2.get(), f.keep * f.n);
     });
 }
 
 // ------------------------------------------------------------------------------------------------ device-resident labelled tensors
 extern "C++" {
+static std::unique_ptr<t4a_gpu_tensor> make_tensor(OwnedTensor&& t) { return std::make_unique<t4a_gpu_tensor>(std::move(t)); }
 static std::unique_ptr<t4a_gpu_tensor> make_tensor(const std::vector<size_t>& dims, const std::vector<int64_t>& labels)
 {
-    std::unique_ptr<t4a_gpu_tensor> t(new t4a_gpu_tensor());
-    t->dims = dims;
-    t->labels = labels;
-    t->buf.reserve(std::max<size_t>(t->size(), 1));
-    return t;
+    return make_tensor(OwnedTensor(dims, labels));
+}
+// the tail of the pairwise products: the product of two device tensors as a new handle
+static t4a_gpu_tensor* contract_to_handle(const TensorView& va, const TensorView& vb, const ContractPlan& plan)
+{
+    std::lock_guard<std::mutex> lock(g_dense_mutex);
+    Engine& e = dense_engine();
+    auto t = make_tensor(plan.out_dims, plan.out_labels);
+    tensor_contract_pair(e, va, vb, plan, t->buf.get());
+    e.sync();
+    return t.release();
 }
 } // extern "C++"
 
@@ -2892,12 +2848,7 @@ t4a_gpu_status t4a_gpu_tensor_contract(const t4a_gpu_tensor* a, const t4a_gpu_te
         *out = nullptr;
         const TensorView va = a->view(), vb = b->view();
         const ContractPlan plan = plan_contract_pair(va, vb);
-        std::lock_guard<std::mutex> lock(g_dense_mutex);
-        Engine& e = dense_engine();
-        auto t = make_tensor(plan.out_dims, plan.out_labels);
-        tensor_contract_pair(e, va, vb, plan, t->buf.get());
-        e.sync();
-        *out = t.release();
+        *out = contract_to_handle(va, vb, plan);
     });
 }
 
@@ -2917,12 +2868,7 @@ t4a_gpu_status t4a_gpu_tensor_contract_many(const t4a_gpu_tensor* const* tensors
         const std::vector<int64_t> retain(retain_labels, retain_labels + n_retain);
         (void)plan_contract_network(views, retain); // (argument errors before the device is touched)
         std::lock_guard<std::mutex> lock(g_dense_mutex);
-        OwnedTensor r = tensor_contract_network(dense_engine(), views, retain);
-        auto t = std::make_unique<t4a_gpu_tensor>();
-        t->buf = std::move(r.buf);
-        t->dims = std::move(r.dims);
-        t->labels = std::move(r.labels);
-        *out = t.release();
+        *out = make_tensor(tensor_contract_network(dense_engine(), views, retain)).release();
     });
 }
 
@@ -2938,12 +2884,7 @@ t4a_gpu_status t4a_gpu_tensor_outer_product(const t4a_gpu_tensor* a, const t4a_g
             if (std::find(vb.labels.begin(), vb.labels.end(), l) != vb.labels.end())
                 throw Error(T4A_GPU_INVALID_ARGUMENT, "outer_product: the operands share an index; use contract for a contraction");
         const ContractPlan plan = plan_contract_pair(va, vb); // (no common label: M x 1 times 1 x N)
-        std::lock_guard<std::mutex> lock(g_dense_mutex);
-        Engine& e = dense_engine();
-        auto t = make_tensor(plan.out_dims, plan.out_labels);
-        tensor_contract_pair(e, va, vb, plan, t->buf.get());
-        e.sync();
-        *out = t.release();
+        *out = contract_to_handle(va, vb, plan);
     });
 }
 
@@ -2991,12 +2932,7 @@ t4a_gpu_status t4a_gpu_tensor_tensordot(const t4a_gpu_tensor* a, const t4a_gpu_t
         // the paired axes of `b` take the labels of their partners; unpaired axes keep theirs (none is shared, checked above)
         for (size_t p = 0; p < n_pairs; ++p) vb.labels[ax_b[p]] = va.labels[ax_a[p]];
         const ContractPlan plan = plan_contract_pair(va, vb);
-        std::lock_guard<std::mutex> lock(g_dense_mutex);
-        Engine& e = dense_engine();
-        auto t = make_tensor(plan.out_dims, plan.out_labels);
-        tensor_contract_pair(e, va, vb, plan, t->buf.get());
-        e.sync();
-        *out = t.release();
+        *out = contract_to_handle(va, vb, plan);
     });
 }
 
@@ -3013,45 +2949,18 @@ t4a_gpu_status t4a_gpu_tensor_svd(const t4a_gpu_tensor* t, const int64_t* left_l
         *u = *s = *v = nullptr;
         if (n_left) T4A_REQUIRE_PTR(left_labels);
         const TensorView tv = t->view();
-        const std::vector<int64_t> left(left_labels, left_labels + n_left);
-        const UnfoldPlan un = plan_unfold_split(tv, left);
-        SvdPolicy pol = convert_policy(policy);
-        if (truncate) {
-            if (has_max_bond_dim && max_bond_dim == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "max_bond_dim must be positive when specified");
-            if (!std::isfinite(pol.threshold) || pol.threshold < 0.0)
-                throw Error(T4A_GPU_INVALID_ARGUMENT, "Invalid SVD truncation threshold: threshold must be finite and non-negative");
-        }
-        const size_t m = un.m, n = un.n, k = std::min(m, n), count = tv.size();
-        if (count == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "SVD of an empty tensor");
-        if (m > 65535 || n > 65535) throw Error(T4A_GPU_NOT_IMPLEMENTED, "svd: unfolded dimensions above 65535 are not supported");
+        const UnfoldPlan un = plan_unfold_split(tv, std::vector<int64_t>(left_labels, left_labels + n_left));
+        const SvdOptions opts{truncate != 0, convert_policy(policy), has_max_bond_dim != 0, max_bond_dim};
+        opts.validate();
+        require_factorizable(un, "svd", "SVD");
         std::lock_guard<std::mutex> lock(g_dense_mutex);
         Engine& e = dense_engine();
-        double* d_mat = e.pi(count);
-        tensor_permute(e, tv, un.perm, d_mat);
-        e.d_tmp.reserve(m * k + k + k * n);
-        double* d_u = e.d_tmp.get();
-        double* d_s = d_u + m * k;
-        double* d_vt = d_s + k;
-        e.svd(d_mat, (int)m, (int)n, d_u, d_s, d_vt);
-        std::vector<double> hs(k);
-        download(e, hs.data(), d_s, k);
-        size_t keep = k;
-        if (truncate) {
-            keep = svd_retained_rank(hs.data(), k, pol);
-            if (has_max_bond_dim) keep = std::min(keep, max_bond_dim);
-        }
-        keep = std::min(std::max<size_t>(keep, 1), k);
-        std::vector<size_t> ud = un.left_dims, vd = un.right_dims;
-        std::vector<int64_t> ul = left, vl;
-        for (size_t a = n_left; a < un.perm.size(); ++a) vl.push_back(tv.labels[un.perm[a]]);
-        ud.push_back(keep);
-        ul.push_back(bond_label);
-        vd.push_back(keep);
-        vl.push_back(bond_label_v);
-        auto tu = make_tensor(ud, ul), ts = make_tensor({keep}, {bond_label}), tvv = make_tensor(vd, vl);
-        T4A_HIP(hipMemcpyAsync(tu->buf.get(), d_u, m * keep * sizeof(double), hipMemcpyDeviceToDevice, e.stream()));
-        T4A_HIP(hipMemcpyAsync(ts->buf.get(), d_s, keep * sizeof(double), hipMemcpyDeviceToDevice, e.stream()));
-        transpose_launch(d_vt, (int)keep, (int)n, (int)k, tvv->buf.get(), (int)n, e.stream());
+        const UnfoldedFactors f = tensor_svd(e, tv, un, opts);
+        auto tu = make_tensor(bonded_tensor(un.left_dims, un.left_labels, f.keep, bond_label)), ts = make_tensor({f.keep}, {bond_label}),
+             tvv = make_tensor(bonded_tensor(un.right_dims, un.right_labels, f.keep, bond_label_v));
+        T4A_HIP(hipMemcpyAsync(tu->buf.get(), f.d_left, f.m * f.keep * sizeof(double), hipMemcpyDeviceToDevice, e.stream()));
+        T4A_HIP(hipMemcpyAsync(ts->buf.get(), f.d_s, f.keep * sizeof(double), hipMemcpyDeviceToDevice, e.stream()));
+        transpose_launch(f.d_right, (int)f.keep, (int)f.n, (int)f.k, tvv->buf.get(), (int)f.n, e.stream());
         T4A_HIP(hipGetLastError());
         e.sync();
         *u = tu.release();
@@ -3070,39 +2979,17 @@ t4a_gpu_status t4a_gpu_tensor_qr(const t4a_gpu_tensor* t, const int64_t* left_la
         *q = *r = nullptr;
         if (n_left) T4A_REQUIRE_PTR(left_labels);
         const TensorView tv = t->view();
-        const std::vector<int64_t> left(left_labels, left_labels + n_left);
-        const UnfoldPlan un = plan_unfold_split(tv, left);
-        const double tol = has_rtol ? rtol : 1e-15;
-        if (truncate && (!std::isfinite(tol) || tol < 0.0))
-            throw Error(T4A_GPU_INVALID_ARGUMENT, "Invalid rtol value: rtol must be finite and non-negative");
-        const size_t m = un.m, n = un.n, k = std::min(m, n), count = tv.size();
-        if (count == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "QR of an empty tensor");
-        if (m > 65535 || n > 65535) throw Error(T4A_GPU_NOT_IMPLEMENTED, "qr: unfolded dimensions above 65535 are not supported");
+        const UnfoldPlan un = plan_unfold_split(tv, std::vector<int64_t>(left_labels, left_labels + n_left));
+        const QrOptions opts{truncate != 0, has_rtol ? rtol : QrOptions().rtol};
+        opts.validate();
+        require_factorizable(un, "qr", "QR");
         std::lock_guard<std::mutex> lock(g_dense_mutex);
         Engine& e = dense_engine();
-        double* d_mat = e.pi(count);
-        tensor_permute(e, tv, un.perm, d_mat);
-        e.d_tmp.reserve(m * k + k * n);
-        double* d_q = e.d_tmp.get();
-        double* d_r = d_q + m * k;
-        e.qr(d_mat, (int)m, (int)n, d_q, d_r);
-        size_t keep = k;
-        if (truncate) {
-            std::vector<double> hr(k * n);
-            download(e, hr.data(), d_r, k * n);
-            keep = std::min(qr_retained_rank(hr.data(), k, n, tol), k);
-        }
-        std::vector<size_t> qd = un.left_dims, rd{keep};
-        std::vector<int64_t> ql = left, rl{bond_label};
-        qd.push_back(keep);
-        ql.push_back(bond_label);
-        for (size_t a = n_left; a < un.perm.size(); ++a) {
-            rd.push_back(tv.dims[un.perm[a]]);
-            rl.push_back(tv.labels[un.perm[a]]);
-        }
-        auto tq = make_tensor(qd, ql), tr = make_tensor(rd, rl);
-        T4A_HIP(hipMemcpyAsync(tq->buf.get(), d_q, m * keep * sizeof(double), hipMemcpyDeviceToDevice, e.stream()));
-        gather_launch(d_r, (int)k, nullptr, (int)keep, nullptr, (int)n, tr->buf.get(), (int)keep, e.stream());
+        const UnfoldedFactors f = tensor_qr(e, tv, un, opts);
+        auto tq = make_tensor(bonded_tensor(un.left_dims, un.left_labels, f.keep, bond_label)),
+             tr = make_tensor(bonded_tensor(un.right_dims, un.right_labels, f.keep, bond_label, true));
+        T4A_HIP(hipMemcpyAsync(tq->buf.get(), f.d_left, f.m * f.keep * sizeof(double), hipMemcpyDeviceToDevice, e.stream()));
+        gather_launch(f.d_right, (int)f.k, nullptr, (int)f.keep, nullptr, (int)f.n, tr->buf.get(), (int)f.keep, e.stream());
         T4A_HIP(hipGetLastError());
         e.sync();
         *q = tq.release();
@@ -3125,98 +3012,18 @@ t4a_gpu_status t4a_gpu_tensor_factorize(const t4a_gpu_tensor* t, const int64_t* 
         if (alg < 0 || alg > 3) throw Error(T4A_GPU_INVALID_ARGUMENT, "unknown factorization algorithm");
         if (canonical < 0 || canonical > 1) throw Error(T4A_GPU_INVALID_ARGUMENT, "unknown canonical direction");
         const TensorView tv = t->view();
-        const std::vector<int64_t> lf(left_labels, left_labels + n_left);
-        const UnfoldPlan un = plan_unfold_split(tv, lf);
-        const bool trunc = full_rank == 0;
-        SvdPolicy pol = convert_policy(policy);
-        if (alg == 0 && trunc) {
-            if (has_max_bond_dim && max_bond_dim == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "max_bond_dim must be positive when specified");
-            if (!std::isfinite(pol.threshold) || pol.threshold < 0.0)
-                throw Error(T4A_GPU_INVALID_ARGUMENT, "Invalid SVD truncation threshold: threshold must be finite and non-negative");
-        }
-        const double tol = has_qr_rtol ? qr_rtol : 1e-15;
-        if (alg == 1 && trunc && (!std::isfinite(tol) || tol < 0.0))
-            throw Error(T4A_GPU_INVALID_ARGUMENT, "Invalid rtol value: rtol must be finite and non-negative");
-        const size_t m = un.m, n = un.n, k = std::min(m, n), count = tv.size();
-        if (count == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "factorization of an empty tensor");
-        if (m > 65535 || n > 65535) throw Error(T4A_GPU_NOT_IMPLEMENTED, "factorize: unfolded dimensions above 65535 are not supported");
-        std::vector<int64_t> right_labels;
-        for (size_t a = n_left; a < un.perm.size(); ++a) right_labels.push_back(tv.labels[un.perm[a]]);
+        const UnfoldPlan un = plan_unfold_split(tv, std::vector<int64_t>(left_labels, left_labels + n_left));
+        const FactorizeOptions opts{alg, canonical, SvdOptions{!full_rank, convert_policy(policy), has_max_bond_dim != 0, max_bond_dim},
+                                    QrOptions{!full_rank, has_qr_rtol ? qr_rtol : QrOptions().rtol}};
+        opts.validate();
+        require_factorizable(un, "factorize", "factorization");
         std::lock_guard<std::mutex> lock(g_dense_mutex);
-        Engine& e = dense_engine();
-        hipStream_t st = e.stream();
-        double* d_mat = e.pi(count);
-        tensor_permute(e, tv, un.perm, d_mat);
-        size_t keep = 0;
-        auto finish = [&](const double* d_l, int ldl, const double* d_r, int ldr) {
-            // d_l: m x keep (ld ldl), d_r: keep x n (ld ldr) -> handles
-            std::vector<size_t> ld = un.left_dims, rd{keep};
-            std::vector<int64_t> ll = lf, rl{bond_label};
-            ld.push_back(keep);
-            ll.push_back(bond_label);
-            rd.insert(rd.end(), un.right_dims.begin(), un.right_dims.end());
-            rl.insert(rl.end(), right_labels.begin(), right_labels.end());
-            auto tl = make_tensor(ld, ll), tr = make_tensor(rd, rl);
-            gather_launch(d_l, ldl, nullptr, (int)m, nullptr, (int)keep, tl->buf.get(), (int)m, st);
-            gather_launch(d_r, ldr, nullptr, (int)keep, nullptr, (int)n, tr->buf.get(), (int)keep, st);
-            T4A_HIP(hipGetLastError());
-            e.sync();
-            if (rank) *rank = keep;
-            *left = tl.release();
-            *right = tr.release();
-        };
-        if (alg == 0) { // SVD
-            e.d_tmp.reserve(m * k + k + k * n);
-            e.d_tmp2.reserve(std::max(m, n) * k);
-            double* d_u = e.d_tmp.get();
-            double* d_s = d_u + m * k;
-            double* d_vt = d_s + k;
-            e.svd(d_mat, (int)m, (int)n, d_u, d_s, d_vt);
-            std::vector<double> hs(k);
-            download(e, hs.data(), d_s, k);
-            keep = k;
-            if (trunc) {
-                keep = svd_retained_rank(hs.data(), k, pol);
-                if (has_max_bond_dim) keep = std::min(keep, max_bond_dim);
-            }
-            keep = std::min(std::max<size_t>(keep, 1), k);
-            if (singular_values) std::copy(hs.begin(), hs.begin() + keep, singular_values);
-            if (canonical == 0) { // right = S V^H
-                diag_scale_launch(d_vt, (int)k, (int)keep, (int)n, d_s, true, e.d_tmp2.get(), (int)keep, st);
-                finish(d_u, (int)m, e.d_tmp2.get(), (int)keep);
-            } else { // left = U S
-                diag_scale_launch(d_u, (int)m, (int)m, (int)keep, d_s, false, e.d_tmp2.get(), (int)m, st);
-                finish(e.d_tmp2.get(), (int)m, d_vt, (int)k);
-            }
-        } else if (alg == 1) { // QR
-            e.d_tmp.reserve(m * k + k * n);
-            double* d_q = e.d_tmp.get();
-            double* d_r = d_q + m * k;
-            e.qr(d_mat, (int)m, (int)n, d_q, d_r);
-            keep = k;
-            if (trunc) {
-                std::vector<double> hr(k * n);
-                download(e, hr.data(), d_r, k * n);
-                keep = std::min(qr_retained_rank(hr.data(), k, n, tol), k);
-            }
-            finish(d_q, (int)m, d_r, (int)k);
-        } else { // LU / CI on the rrLU kernels
-            RrLUOptions lo;
-            lo.max_bond_dim = (!trunc || !has_max_bond_dim) ? std::numeric_limits<size_t>::max() : max_bond_dim;
-            lo.rel_tol = trunc ? 1e-14 : 0.0;
-            lo.abs_tol = 0.0;
-            lo.left_orthogonal = canonical == 0;
-            if (alg == 2) {
-                LuciResult r = e.luci(d_mat, (int)m, (int)n, lo, false, true);
-                e.lu_permuted_factors(r, lo.left_orthogonal);
-                keep = (size_t)r.rank;
-            } else {
-                LuciResult r = e.luci(d_mat, (int)m, (int)n, lo, true, false);
-                keep = (size_t)r.rank;
-            }
-            if (keep == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "Failed to create bond index: dimension 0");
-            finish(e.left(), (int)m, e.right(), (int)keep);
-        }
+        FactorizeResult f = tensor_factorize(dense_engine(), tv, un, opts, bond_label);
+        if (rank) *rank = f.rank;
+        if (singular_values) std::copy(f.singular_values.begin(), f.singular_values.end(), singular_values);
+        auto tl = make_tensor(std::move(f.left)), tr = make_tensor(std::move(f.right));
+        *left = tl.release();
+        *right = tr.release();
     });
 }
 

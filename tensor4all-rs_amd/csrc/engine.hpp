@@ -150,6 +150,12 @@ public:
     // luci(..., want_lu_copy = true): left() is M x rank, right() is rank x N afterwards.
     void lu_permuted_factors(const LuciResult& r, bool left_orth);
 
+    static constexpr size_t FACTOR_DIM_MAX = 65535; // svd() and qr() take matrices of at most this many rows and columns
+    static void require_factor_dims(size_t m, size_t n, const std::string& what) // `what` e.g. "svd: dimensions"
+    {
+        if (m > FACTOR_DIM_MAX || n > FACTOR_DIM_MAX)
+            throw Error(T4A_GPU_NOT_IMPLEMENTED, what + " above " + std::to_string(FACTOR_DIM_MAX) + " are not supported");
+    }
     // thin SVD (svd_backend, tensorbackend/src/backend.rs:709): d_u M x k, d_s k, d_vt k x N with k = min(M, N);
     // one-sided Jacobi.  Throws INVALID_ARGUMENT for non-finite input.
     void svd(const double* d_a, int M, int N, double* d_u, double* d_s, double* d_vt);

@@ -372,9 +372,7 @@ OwnedTensor tensor_contract_network(Engine& e, const std::vector<TensorView>& ts
     }
     // into the reference's index order
     const TensorView& F = work[0].v;
-    OwnedTensor out;
-    out.dims = plan.out_dims;
-    out.labels = plan.out_labels;
+    OwnedTensor out(plan.out_dims, plan.out_labels);
     std::vector<size_t> perm;
     for (int64_t l : plan.out_labels) {
         const auto it = std::find(F.labels.begin(), F.labels.end(), l);
@@ -382,7 +380,6 @@ OwnedTensor tensor_contract_network(Engine& e, const std::vector<TensorView>& ts
         perm.push_back((size_t)(it - F.labels.begin()));
     }
     if (perm.size() != F.labels.size()) throw Error(T4A_GPU_INTERNAL_ERROR, "contract: an index was left uncontracted");
-    out.buf.reserve(std::max<size_t>(F.size(), 1));
     if (F.dims.empty()) T4A_HIP(hipMemcpyAsync(out.buf.get(), F.d_data, sizeof(double), hipMemcpyDeviceToDevice, st)); // (a scalar)
     else if (F.size() > 0) tensor_permute(e, F, perm, out.buf.get());
     e.sync();
@@ -412,13 +409,145 @@ UnfoldPlan plan_unfold_split(const TensorView& t, const std::vector<int64_t>& le
         const size_t d = t.dims[p.perm[k]];
         if (k < nl) {
             p.left_dims.push_back(d);
+            p.left_labels.push_back(t.labels[p.perm[k]]);
             p.m *= d;
         } else {
             p.right_dims.push_back(d);
+            p.right_labels.push_back(t.labels[p.perm[k]]);
             p.n *= d;
         }
     }
     return p;
+}
+
+OwnedTensor bonded_tensor(std::vector<size_t> dims, std::vector<int64_t> labels, size_t r, int64_t bond, bool bond_first)
+{
+    dims.insert(bond_first ? dims.begin() : dims.end(), r);
+    labels.insert(bond_first ? labels.begin() : labels.end(), bond);
+    return OwnedTensor(dims, labels);
+}
+
+void require_factorizable(const UnfoldPlan& un, const char* op, const char* empty_what)
+{
+    if (un.m * un.n == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, std::string(empty_what) + " of an empty tensor");
+    Engine::require_factor_dims(un.m, un.n, std::string(op) + ": unfolded dimensions");
+}
+
+void SvdOptions::validate() const
+{
+    if (!truncate) return;
+    if (has_max_bond_dim && max_bond_dim == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "max_bond_dim must be positive when specified");
+    if (!std::isfinite(policy.threshold) || policy.threshold < 0.0)
+        throw Error(T4A_GPU_INVALID_ARGUMENT, "Invalid SVD truncation threshold: threshold must be finite and non-negative");
+}
+
+void QrOptions::validate() const
+{
+    if (truncate && (!std::isfinite(rtol) || rtol < 0.0))
+        throw Error(T4A_GPU_INVALID_ARGUMENT, "Invalid rtol value: rtol must be finite and non-negative");
+}
+
+void FactorizeOptions::validate() const
+{
+    if (alg == 0) svd.validate();
+    if (alg == 1) qr.validate();
+}
+
+// the m x n unfolding of `t`, behind the caller's half of the staging block
+static double* unfold(Engine& e, const TensorView& t, const UnfoldPlan& un)
+{
+    double* d_mat = tensor_staging(e, un.m * un.n) + un.m * un.n;
+    tensor_permute(e, t, un.perm, d_mat);
+    return d_mat;
+}
+static void download(Engine& e, double* dst, const double* src, size_t count)
+{
+    T4A_HIP(hipMemcpyAsync(dst, src, count * sizeof(double), hipMemcpyDeviceToHost, e.stream()));
+    e.sync();
+}
+
+UnfoldedFactors tensor_svd(Engine& e, const TensorView& t, const UnfoldPlan& un, const SvdOptions& o)
+{
+    const size_t m = un.m, n = un.n, k = std::min(m, n);
+    const double* d_mat = unfold(e, t, un);
+    e.d_tmp.reserve(m * k + k + k * n);
+    double* d_u = e.d_tmp.get();
+    double* d_s = d_u + m * k;
+    double* d_vt = d_s + k;
+    e.svd(d_mat, (int)m, (int)n, d_u, d_s, d_vt);
+    std::vector<double> hs(k);
+    download(e, hs.data(), d_s, k);
+    size_t keep = k;
+    if (o.truncate) { // svd.rs:279-292
+        keep = svd_retained_rank(hs.data(), k, o.policy);
+        if (o.has_max_bond_dim) keep = std::min(keep, o.max_bond_dim);
+    }
+    keep = std::min(std::max<size_t>(keep, 1), k);
+    return UnfoldedFactors{m, n, k, keep, d_u, d_vt, d_s, std::move(hs)};
+}
+
+UnfoldedFactors tensor_qr(Engine& e, const TensorView& t, const UnfoldPlan& un, const QrOptions& o)
+{
+    const size_t m = un.m, n = un.n, k = std::min(m, n);
+    const double* d_mat = unfold(e, t, un);
+    e.d_tmp.reserve(m * k + k * n);
+    double* d_q = e.d_tmp.get();
+    double* d_r = d_q + m * k;
+    e.qr(d_mat, (int)m, (int)n, d_q, d_r);
+    size_t keep = k;
+    if (o.truncate) {
+        std::vector<double> hr(k * n);
+        download(e, hr.data(), d_r, k * n);
+        keep = std::min(qr_retained_rank(hr.data(), k, n, o.rtol), k);
+    }
+    return UnfoldedFactors{m, n, k, keep, d_q, d_r, nullptr, {}};
+}
+
+FactorizeResult tensor_factorize(Engine& e, const TensorView& t, const UnfoldPlan& un, const FactorizeOptions& o, int64_t bond_label)
+{
+    const size_t m = un.m, n = un.n;
+    hipStream_t st = e.stream();
+    FactorizeResult res;
+    auto finish = [&](size_t keep, const double* d_l, size_t ldl, const double* d_r, size_t ldr) {
+        // d_l: m x keep (ld ldl), d_r: keep x n (ld ldr) -> tensors
+        res.left = bonded_tensor(un.left_dims, un.left_labels, keep, bond_label);
+        res.right = bonded_tensor(un.right_dims, un.right_labels, keep, bond_label, true);
+        gather_launch(d_l, (int)ldl, nullptr, (int)m, nullptr, (int)keep, res.left.buf.get(), (int)m, st);
+        gather_launch(d_r, (int)ldr, nullptr, (int)keep, nullptr, (int)n, res.right.buf.get(), (int)keep, st);
+        T4A_HIP(hipGetLastError());
+        e.sync();
+        res.rank = keep;
+    };
+    if (o.alg == 0) { // SVD
+        const UnfoldedFactors f = tensor_svd(e, t, un, o.svd);
+        e.d_tmp2.reserve(std::max(m, n) * f.keep);
+        res.singular_values.assign(f.s.begin(), f.s.begin() + (long)f.keep);
+        if (o.canonical == 0) { // right = S V^H
+            diag_scale_launch(f.d_right, (int)f.k, (int)f.keep, (int)n, f.d_s, true, e.d_tmp2.get(), (int)f.keep, st);
+            finish(f.keep, f.d_left, m, e.d_tmp2.get(), f.keep);
+        } else { // left = U S
+            diag_scale_launch(f.d_left, (int)m, (int)m, (int)f.keep, f.d_s, false, e.d_tmp2.get(), (int)m, st);
+            finish(f.keep, e.d_tmp2.get(), m, f.d_right, f.k);
+        }
+    } else if (o.alg == 1) { // QR
+        const UnfoldedFactors f = tensor_qr(e, t, un, o.qr);
+        finish(f.keep, f.d_left, m, f.d_right, f.k);
+    } else { // LU / CI on the rrLU kernels
+        const double* d_mat = unfold(e, t, un);
+        const bool trunc = o.svd.truncate;
+        RrLUOptions lo;
+        lo.max_bond_dim = (trunc && o.svd.has_max_bond_dim) ? o.svd.max_bond_dim : std::numeric_limits<size_t>::max();
+        lo.rel_tol = trunc ? 1e-14 : 0.0; // factorize.rs:644, :755
+        lo.abs_tol = 0.0;
+        lo.left_orthogonal = o.canonical == 0;
+        const bool lu = o.alg == 2;
+        const LuciResult r = e.luci(d_mat, (int)m, (int)n, lo, !lu, lu);
+        if (lu) e.lu_permuted_factors(r, lo.left_orthogonal);
+        const size_t keep = (size_t)r.rank;
+        if (keep == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "Failed to create bond index: dimension 0");
+        finish(keep, e.left(), m, e.right(), keep);
+    }
+    return res;
 }
 
 void diag_scale_launch(const double* in, int ldi, int rows, int cols, const double* sv, bool by_row, double* out, int ldo,

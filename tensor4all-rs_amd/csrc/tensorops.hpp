@@ -1,12 +1,14 @@
 // tensorops.hpp — dense part of the dynamic-index tensor layer of tensor4all-core on the gfx950 engine:
 // unfold_split (defaults/idx_tensor.rs:5278-5345), contract_pair for dense operands (defaults/contract.rs:334-343 with
 // prepare_contraction, index_ops.rs:660-696), svd_with (defaults/svd.rs:255-395) and qr_with (defaults/qr.rs:206-328)
-// with the reference's rank rules.  Indices are integer labels; prime levels, tags, structured storage and AD stay with
-// the caller.  Permutations run as one gather kernel, contractions on the f64-MFMA GEMM, factorisations on the
-// Jacobi SVD / Householder QR of kernels_linalg.hip.
+// with the reference's rank rules, factorize (defaults/factorize.rs:86-834) over SVD, QR, LU and CI.  Indices are integer
+// labels; prime levels, tags, structured storage and AD stay with the caller.  Permutations run as one gather kernel,
+// contractions on the f64-MFMA GEMM, factorisations on the Jacobi SVD / Householder QR of kernels_linalg.hip and the rrLU kernels.
 #pragma once
 
 #include "engine.hpp"
+
+#include <algorithm>
 
 namespace t4a {
 
@@ -60,6 +62,10 @@ struct OwnedTensor {
     DevBuf<double> buf;
     std::vector<size_t> dims;
     std::vector<int64_t> labels;
+    OwnedTensor() = default;
+    OwnedTensor(const std::vector<size_t>& d, const std::vector<int64_t>& l) : dims(d), labels(l) { buf.reserve(std::max<size_t>(size(), 1)); }
+    size_t size() const { return view().size(); }
+    TensorView view() const { return TensorView{buf.get(), dims, labels}; }
 };
 struct NetworkPlan {
     std::vector<int64_t> out_labels;
@@ -71,9 +77,56 @@ OwnedTensor tensor_contract_network(Engine& e, const std::vector<TensorView>& ts
 struct UnfoldPlan {
     std::vector<size_t> perm;
     std::vector<size_t> left_dims, right_dims;
+    std::vector<int64_t> left_labels, right_labels;
     size_t m = 1, n = 1;
 };
 UnfoldPlan plan_unfold_split(const TensorView& t, const std::vector<int64_t>& left);
+// a factor of an unfolding, allocated: the legs of one side followed (bond_first: preceded) by a bond of dimension r
+OwnedTensor bonded_tensor(std::vector<size_t> dims, std::vector<int64_t> labels, size_t r, int64_t bond, bool bond_first = false);
+
+// What the factorisations below refuse needs no device to be found, and their callers look before they take one, in this order: the
+// options' values (validate(): INVALID_ARGUMENT; svd/tests/mod.rs:120-160: before any linear algebra), then require_factorizable: an empty
+// tensor (INVALID_ARGUMENT, "<empty_what> of an empty tensor") and an unfolding beyond Engine::FACTOR_DIM_MAX (NOT_IMPLEMENTED, "<op>: unfolded ...").
+void require_factorizable(const UnfoldPlan& un, const char* op, const char* empty_what);
+// They unfold into the second half of e.pi(2 * count), count = t.size(): the first half is free for a caller that has to bring the tensor
+// to the device first, and a view into it stays valid through the call.
+inline double* tensor_staging(Engine& e, size_t count) { return e.pi(2 * count); }
+
+struct SvdOptions { // SvdOptions (svd.rs:80-87) with the truncating / full-rank choice of svd_with
+    bool truncate = true;
+    SvdPolicy policy;
+    bool has_max_bond_dim = false;
+    size_t max_bond_dim = 0;
+    void validate() const;
+};
+struct QrOptions {
+    bool truncate = true;
+    double rtol = 1e-15; // default_qr_rtol (qr.rs:62-66)
+    void validate() const;
+};
+struct UnfoldedFactors { // of the m x n unfolding, k = min(m, n), the leading `keep` columns of left / rows of right retained; pointers into e.d_tmp
+    size_t m, n, k, keep;
+    const double* d_left;  // U or Q: m x k, leading dimension m
+    const double* d_right; // V^T or R: k x n, leading dimension k
+    const double* d_s;     // SVD only: k singular values ...
+    std::vector<double> s; // ... and their host copy
+};
+UnfoldedFactors tensor_svd(Engine& e, const TensorView& t, const UnfoldPlan& un, const SvdOptions& o); // svd.rs:255-395
+UnfoldedFactors tensor_qr(Engine& e, const TensorView& t, const UnfoldPlan& un, const QrOptions& o);   // qr.rs:206-328
+
+struct FactorizeOptions {
+    int alg = 0;       // 0 SVD, 1 QR, 2 LU, 3 CI
+    int canonical = 0; // 0 Left: the left factor is the isometry and the right one takes S (SVD) / the pivot block; 1 Right
+    SvdOptions svd;    // truncate and max_bond_dim also bound LU and CI
+    QrOptions qr;
+    void validate() const; // the chosen algorithm's values only
+};
+struct FactorizeResult {
+    OwnedTensor left, right; // [left.., bond], [bond, right..]
+    size_t rank = 0;
+    std::vector<double> singular_values; // the retained ones; SVD only
+};
+FactorizeResult tensor_factorize(Engine& e, const TensorView& t, const UnfoldPlan& un, const FactorizeOptions& o, int64_t bond_label);
 
 // out[i + ldo*j] = in[i + ldi*j] * (by_row ? s[i] : s[j])   (S absorbed into a factor, factorize.rs:519-557)
 void diag_scale_launch(const double* in, int ldi, int rows, int cols, const double* s, bool by_row, double* out, int ldo,

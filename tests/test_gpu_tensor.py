@@ -75,6 +75,33 @@ def test_svd_and_qr_reconstruct_and_match_oracle(t4a):
     assert len(s) == 60 and np.abs(np.einsum("bak,k,ik->iab", u, s, v) - low).max() < 1e-10
     q, r = t4a.tensor_qr(low, [1, 2, 3], [1], rtol=1e-10)
     assert np.abs(np.einsum("ik,kab->iab", q, r) - low).max() < 1e-10 and q.shape[1] == ob.tensor_qr(low, [1, 2, 3], [1], rtol=1e-10)[0].shape[1]
+    # host buffers, device handles and factorize run one routine on the same unfolding: the factors are the same bits, and where factorize
+    # absorbs S it differs from s * V by the rounding of that one multiplication at most
+    eps = np.finfo(np.float64).eps
+    for x, xl, left, kw_svd, kw_qr in ((t, labels, [9, 7], dict(truncate=False), dict(truncate=False)),
+                                       (t, labels, [3], dict(truncate=False), dict(truncate=False)),
+                                       (low, [1, 2, 3], [1], dict(policy=t4a.SvdTruncationPolicy(1e-10)), dict(rtol=1e-10)),
+                                       (low, [1, 2, 3], [3, 2], dict(policy=t4a.SvdTruncationPolicy(1e-20), max_bond_dim=3), dict())):
+        h = t4a.LabelledTensor(x, xl)
+        u, s, v = t4a.tensor_svd(x, xl, left, **kw_svd)
+        hu, hs, hv = h.svd(left, 100, 101, **kw_svd)
+        assert hu.labels == left + [100] and hv.labels == [a for a in xl if a not in left] + [101]
+        assert np.array_equal(hu.to_numpy(), u) and np.array_equal(hs.to_numpy(), s) and np.array_equal(hv.to_numpy(), v)
+        q, r = t4a.tensor_qr(x, xl, left, **kw_qr)
+        hq, hr = h.qr(left, 100, **kw_qr)
+        assert hq.labels == left + [100] and hr.labels == [100] + [a for a in xl if a not in left]
+        assert np.array_equal(hq.to_numpy(), q) and np.array_equal(hr.to_numpy(), r)
+        if kw_svd != dict(truncate=False):
+            continue
+        svt = np.moveaxis(v, -1, 0) * s.reshape([-1] + [1] * (v.ndim - 1))
+        fl, fr, rank, sv = h.factorize(left, 100, alg=t4a.FACTORIZE_SVD, full_rank=True)
+        assert rank == len(s) and np.array_equal(sv, s) and np.array_equal(fl.to_numpy(), u)
+        assert fr.to_numpy().shape == svt.shape and (np.abs(fr.to_numpy() - svt) <= eps * np.abs(svt)).all()
+        fl, fr, rank, sv = h.factorize(left, 100, alg=t4a.FACTORIZE_SVD, canonical=t4a.CANONICAL_RIGHT, full_rank=True)
+        assert rank == len(s) and np.array_equal(sv, s) and np.array_equal(fr.to_numpy(), np.moveaxis(v, -1, 0))
+        assert fl.to_numpy().shape == u.shape and (np.abs(fl.to_numpy() - u * s) <= eps * np.abs(u * s)).all()
+        fl, fr, rank, _ = h.factorize(left, 100, alg=t4a.FACTORIZE_QR, full_rank=True)
+        assert rank == q.shape[-1] and np.array_equal(fl.to_numpy(), q) and np.array_equal(fr.to_numpy(), r)
 
 
 def test_random_contractions_and_factorisations(t4a):
