@@ -726,6 +726,53 @@ t4a_gpu_status t4a_gpu_mpo_contract(const t4a_gpu_mpo* a, const t4a_gpu_mpo* b, 
  * _from_tt gives site dims (d, 1) (a state as an MPO), _to_tt fuses (s1, s2) into one site index s1 + S1 * s2. */
 t4a_gpu_status t4a_gpu_mpo_from_tt(const t4a_gpu_tt* tt, t4a_gpu_mpo** out);
 t4a_gpu_status t4a_gpu_mpo_to_tt(const t4a_gpu_mpo* mpo, t4a_gpu_tt** out);
+/* LinearOperator::transpose: s1 <-> s2 of every site, one axis permutation per site on the MPO's stream. */
+t4a_gpu_status t4a_gpu_mpo_transpose(const t4a_gpu_mpo* mpo, t4a_gpu_mpo** out);
+
+/* =====================================================================================
+ * Quantics transform operators as MPOs — the real-valued part of tensor4all-quanticstransform
+ * shift.rs:49-291, flip.rs:44-249, cumsum.rs:76-346, common.rs:549-654, affine.rs:497-553, :673-711, :1386-1834,
+ * difference_kernel.rs:29-107.  The complex-valued operators (quantics_fourier_operator, phase_rotation_operator*) are not
+ * part of this f64 library.
+ * An operator acts on a function held as a quantics tensor train with site 0 the most significant bit; its site tensors are
+ * column-major [left, s1 = out, s2 = in, right], the layout of t4a_gpu_mpo.  Building one is exact integer bookkeeping on the
+ * host: the builders and the _len / _dims / _site_tensor readers need no device and work with none visible.
+ * t4a_gpu_qt_op_to_mpo is the one upload; the result is applied with t4a_gpu_mpo_contract.
+ * ===================================================================================== */
+typedef struct t4a_gpu_qt_op t4a_gpu_qt_op;
+#define T4A_GPU_QT_PERIODIC 0
+#define T4A_GPU_QT_ANTIPERIODIC 1
+#define T4A_GPU_QT_OPEN 2
+#define T4A_GPU_QT_LOWER 0
+#define T4A_GPU_QT_UPPER 1
+/* shift_operator: (M g)[x] = g[x - offset]; a wrap-around is weighted 1 / -1 / 0.  Any offset (negative, |offset| >= 2^r).
+ * INVALID_ARGUMENT: r == 0, r > 63.  _multivar (nvariables >= 2, target_var < nvariables): the operator on one variable of a
+ * fused train (site index var0 + 2 var1 + ...), identity on the others. */
+t4a_gpu_status t4a_gpu_qt_shift_operator(size_t r, int64_t offset, int32_t bc, t4a_gpu_qt_op** out);
+t4a_gpu_status t4a_gpu_qt_shift_operator_multivar(size_t r, int64_t offset, int32_t bc, size_t nvariables, size_t target_var,
+                                                  t4a_gpu_qt_op** out);
+/* flip_operator: x -> 2^r - x; x = 0 maps to itself with weight 1 / -1 / 0.  r >= 2. */
+t4a_gpu_status t4a_gpu_qt_flip_operator(size_t r, int32_t bc, t4a_gpu_qt_op** out);
+t4a_gpu_status t4a_gpu_qt_flip_operator_multivar(size_t r, int32_t bc, size_t nvariables, size_t target_var, t4a_gpu_qt_op** out);
+/* triangle_operator: M[i, j] = [i > j] (LOWER) or [i < j] (UPPER); cumsum_operator is LOWER.  r >= 2. */
+t4a_gpu_status t4a_gpu_qt_triangle_operator(size_t r, int32_t triangle, t4a_gpu_qt_op** out);
+t4a_gpu_status t4a_gpu_qt_cumsum_operator(size_t r, t4a_gpu_qt_op** out);
+/* affine_operator: |x> -> |y> with scale * y = a x + b, n input and m output variables (site dims 2^m x 2^n, m + n <= 15).
+ * a (a_len = m * n, column-major a[i + m * j]), b (b_len = m) and scale > 0 are the rational matrix, vector and their common
+ * denominator (AffineParams::to_integer_scaled); bc has n_bc = m entries.  The carries of a site are ordered ascending, so bond
+ * indices are reproducible.  INVALID_ARGUMENT: wrong lengths, r == 0, m + n > 15, scale <= 0, a carry that leaves int64. */
+t4a_gpu_status t4a_gpu_qt_affine_operator(size_t r, const int64_t* a, size_t a_len, const int64_t* b, size_t b_len, int64_t scale,
+                                          size_t m, size_t n, const int32_t* bc, size_t n_bc, t4a_gpu_qt_op** out);
+void t4a_gpu_qt_op_release(t4a_gpu_qt_op* h);
+t4a_gpu_status t4a_gpu_qt_op_len(const t4a_gpu_qt_op* h, size_t* out);
+t4a_gpu_status t4a_gpu_qt_op_dims(const t4a_gpu_qt_op* h, size_t* dims4 /* 4 x n_sites */);
+t4a_gpu_status t4a_gpu_qt_op_site_tensor(const t4a_gpu_qt_op* h, size_t site, double* out);
+/* the upload: NO_DEVICE without a GPU */
+t4a_gpu_status t4a_gpu_qt_op_to_mpo(const t4a_gpu_qt_op* h, t4a_gpu_mpo** out);
+/* difference_kernel_mpo: A[x, x'] = f((x - x') mod 2^r), times -1 for x < x' when ANTIPERIODIC, from a train f with binary
+ * sites that stays on the device.  Bonds are 2 * f's (left = dl * f_left + fl); all sites are formed in one launch of the naive
+ * MPO site contraction.  INVALID_ARGUMENT: OPEN, an empty train, a non-binary site. */
+t4a_gpu_status t4a_gpu_qt_difference_kernel(const t4a_gpu_tt* f, int32_t bc, t4a_gpu_mpo** out);
 
 /* Bridge between the tensor-train handles and the labelled tensors (tensor4all-treetn/src/simplett_bridge.rs).
  * _tt_to_tensors = tensor_train_to_treetn_with_names_and_site_indices (:118, :706-794) on a chain: out[s] carries the legs

@@ -15,6 +15,7 @@
 #include "aci.hpp"
 #include "globalsearch.hpp"
 #include "mpo.hpp"
+#include "quanticstransform.hpp"
 
 struct t4a_gpu_tci2 {
     t4a::Tci2 impl;
@@ -46,6 +47,10 @@ struct t4a_gpu_tt {
 
 struct t4a_gpu_mpo {
     std::unique_ptr<t4a::Mpo> impl;
+};
+
+struct t4a_gpu_qt_op {
+    t4a::QtOperator impl; // host data only
 };
 
 namespace t4a {
@@ -3570,6 +3575,132 @@ t4a_gpu_status t4a_gpu_mpo_to_tt(const t4a_gpu_mpo* mpo, t4a_gpu_tt** out)
         T4A_REQUIRE_PTR(out);
         *out = nullptr;
         *out = new t4a_gpu_tt(mpo->impl->tt.cores, mpo->impl->tt.eng.stream());
+    });
+}
+
+t4a_gpu_status t4a_gpu_mpo_transpose(const t4a_gpu_mpo* mpo, t4a_gpu_mpo** out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(mpo);
+        T4A_REQUIRE_PTR(out);
+        *out = nullptr;
+        *out = new t4a_gpu_mpo{mpo->impl->transpose()};
+    });
+}
+
+// ---- quantics transform operators (tensor4all-quanticstransform): host builders, one upload, the difference kernel ----
+t4a_gpu_status t4a_gpu_qt_shift_operator(size_t r, int64_t offset, int32_t bc, t4a_gpu_qt_op** out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(out);
+        *out = nullptr;
+        *out = new t4a_gpu_qt_op{qt_shift(r, offset, (BoundaryCondition)bc)};
+    });
+}
+
+t4a_gpu_status t4a_gpu_qt_shift_operator_multivar(size_t r, int64_t offset, int32_t bc, size_t nvariables, size_t target_var,
+                                                  t4a_gpu_qt_op** out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(out);
+        *out = nullptr;
+        *out = new t4a_gpu_qt_op{qt_embed(qt_shift(r, offset, (BoundaryCondition)bc), nvariables, target_var)};
+    });
+}
+
+t4a_gpu_status t4a_gpu_qt_flip_operator(size_t r, int32_t bc, t4a_gpu_qt_op** out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(out);
+        *out = nullptr;
+        *out = new t4a_gpu_qt_op{qt_flip(r, (BoundaryCondition)bc)};
+    });
+}
+
+t4a_gpu_status t4a_gpu_qt_flip_operator_multivar(size_t r, int32_t bc, size_t nvariables, size_t target_var, t4a_gpu_qt_op** out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(out);
+        *out = nullptr;
+        *out = new t4a_gpu_qt_op{qt_embed(qt_flip(r, (BoundaryCondition)bc), nvariables, target_var)};
+    });
+}
+
+t4a_gpu_status t4a_gpu_qt_triangle_operator(size_t r, int32_t triangle, t4a_gpu_qt_op** out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(out);
+        *out = nullptr;
+        *out = new t4a_gpu_qt_op{qt_triangle(r, (TriangleType)triangle)};
+    });
+}
+
+t4a_gpu_status t4a_gpu_qt_cumsum_operator(size_t r, t4a_gpu_qt_op** out) { return t4a_gpu_qt_triangle_operator(r, T4A_GPU_QT_LOWER, out); }
+
+t4a_gpu_status t4a_gpu_qt_affine_operator(size_t r, const int64_t* a, size_t a_len, const int64_t* b, size_t b_len, int64_t scale,
+                                          size_t m, size_t n, const int32_t* bc, size_t n_bc, t4a_gpu_qt_op** out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(out);
+        *out = nullptr;
+        if (a_len) T4A_REQUIRE_PTR(a);
+        if (b_len) T4A_REQUIRE_PTR(b);
+        if (n_bc) T4A_REQUIRE_PTR(bc);
+        std::vector<BoundaryCondition> conditions(n_bc);
+        for (size_t i = 0; i < n_bc; ++i) conditions[i] = (BoundaryCondition)bc[i];
+        *out = new t4a_gpu_qt_op{qt_affine(r, std::vector<int64_t>(a, a + a_len), std::vector<int64_t>(b, b + b_len), scale, m, n, conditions)};
+    });
+}
+
+void t4a_gpu_qt_op_release(t4a_gpu_qt_op* h) { delete h; }
+
+t4a_gpu_status t4a_gpu_qt_op_len(const t4a_gpu_qt_op* h, size_t* out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(h);
+        T4A_REQUIRE_PTR(out);
+        *out = h->impl.len();
+    });
+}
+
+t4a_gpu_status t4a_gpu_qt_op_dims(const t4a_gpu_qt_op* h, size_t* dims4)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(h);
+        if (h->impl.len()) T4A_REQUIRE_PTR(dims4);
+        for (size_t s = 0; s < h->impl.len(); ++s)
+            for (int k = 0; k < 4; ++k) dims4[4 * s + k] = h->impl.dims[s][k];
+    });
+}
+
+t4a_gpu_status t4a_gpu_qt_op_site_tensor(const t4a_gpu_qt_op* h, size_t site, double* out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(h);
+        T4A_REQUIRE_PTR(out);
+        if (site >= h->impl.len()) throw Error(T4A_GPU_INVALID_ARGUMENT, "site out of range");
+        const std::vector<double>& v = h->impl.sites[site];
+        std::memcpy(out, v.data(), v.size() * sizeof(double));
+    });
+}
+
+t4a_gpu_status t4a_gpu_qt_op_to_mpo(const t4a_gpu_qt_op* h, t4a_gpu_mpo** out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(h);
+        T4A_REQUIRE_PTR(out);
+        *out = nullptr;
+        *out = new t4a_gpu_mpo{qt_upload(h->impl)};
+    });
+}
+
+t4a_gpu_status t4a_gpu_qt_difference_kernel(const t4a_gpu_tt* f, int32_t bc, t4a_gpu_mpo** out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(f);
+        T4A_REQUIRE_PTR(out);
+        *out = nullptr;
+        *out = new t4a_gpu_mpo{qt_difference_kernel(const_cast<t4a_gpu_tt*>(f)->impl, (BoundaryCondition)bc)};
     });
 }
 

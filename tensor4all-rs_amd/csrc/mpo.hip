@@ -328,6 +328,35 @@ std::vector<double> Mpo::evaluate(const uint32_t* idx, size_t n_pts)
     return tt.evaluate(f.data(), n_pts);
 }
 
+std::unique_ptr<Mpo> Mpo::transpose()
+{
+    const size_t n = len();
+    std::vector<DevCore> out(n);
+    std::vector<std::array<size_t, 2>> tsd(n);
+    const hipStream_t st = tt.eng.stream();
+    for (size_t i = 0; i < n; ++i) {
+        const DevCore& c = tt.cores[i];
+        out[i] = new_core(c.l, c.s, c.r);
+        tsd[i] = {sd[i][1], sd[i][0]};
+        const size_t d[4] = {c.l, sd[i][0], sd[i][1], c.r}, p[4] = {0, 2, 1, 3};
+        permute_launch(c.buf.get(), d, p, 4, out[i].buf.get(), st);
+    }
+    T4A_HIP(hipGetLastError());
+    tt.eng.sync();
+    return std::make_unique<Mpo>(std::move(out), tsd);
+}
+
+void Mpo::relabel_site_dims(const std::vector<std::array<size_t, 2>>& site_dims)
+{
+    if (site_dims.size() != len()) throw Error(T4A_GPU_INVALID_ARGUMENT, "relabel_site_dims: one (s1, s2) pair per site is needed");
+    for (size_t i = 0; i < len(); ++i)
+        if (site_dims[i][0] * site_dims[i][1] != tt.cores[i].s)
+            throw Error(T4A_GPU_INVALID_ARGUMENT, "relabel_site_dims: site " + std::to_string(i) + " has " + std::to_string(tt.cores[i].s) +
+                                                      " fused indices, not " + std::to_string(site_dims[i][0]) + " * " +
+                                                      std::to_string(site_dims[i][1]));
+    sd = site_dims;
+}
+
 std::unique_ptr<Mpo> mpo_contract(Mpo& a, Mpo& b, MpoAlgorithm alg, bool compress, const MpoContractionOptions& opt)
 {
     if (a.len() != b.len())

@@ -38,6 +38,11 @@ public:
     // evaluate (mpo.rs:245-340) for a batch: idx is 2 n_sites x n_pts column-major, [i1, j1, i2, j2, ...] per point
     std::vector<double> evaluate(const uint32_t* idx, size_t n_pts);
     double sum() { return tt.sum(); } // mpo.rs:341-392 (the empty MPO sums to 0)
+    // s1 <-> s2 of every site (LinearOperator::transpose of the quantics operators): one axis permutation per site on this
+    // MPO's stream
+    std::unique_ptr<Mpo> transpose();
+    // read the fused site index s1 + S1 * s2 of every site as another (s1, s2) pair of the same product; the cores stay
+    void relabel_site_dims(const std::vector<std::array<size_t, 2>>& site_dims);
 
     TensorTrain tt;
     std::vector<std::array<size_t, 2>> sd; // (s1, s2) per site

@@ -92,6 +92,12 @@ class MPO:
         _check(_lib.t4a_gpu_mpo_clone(self._h, ctypes.byref(h)))
         return MPO._adopt(h)
 
+    def transpose(self):
+        """s1 <-> s2 of every site (LinearOperator::transpose), permuted on the device (t4a_gpu_mpo_transpose)."""
+        h = c_void_p()
+        _check(_lib.t4a_gpu_mpo_transpose(self._h, ctypes.byref(h)))
+        return MPO._adopt(h)
+
     def __len__(self):
         v = c_size_t(0)
         _check(_lib.t4a_gpu_mpo_len(self._h, ctypes.byref(v)))
