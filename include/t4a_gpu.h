@@ -730,6 +730,64 @@ t4a_gpu_status t4a_gpu_mpo_to_tt(const t4a_gpu_mpo* mpo, t4a_gpu_tt** out);
 t4a_gpu_status t4a_gpu_mpo_transpose(const t4a_gpu_mpo* mpo, t4a_gpu_mpo** out);
 
 /* =====================================================================================
+ * Contraction<f64>: the lazy product A·B of two MPOs (opaque handle; both operands resident on the device)
+ * tensor4all-simplett/src/mpo/contraction.rs:60-383
+ * Single elements and left / right environments of A·B without forming the product with bonds la * lb.  An index tuple is
+ * [i_0, j_0, i_1, j_1, ...]: i_k indexes s1 of A, j_k indexes s2 of B, as in t4a_gpu_mpo_evaluate; idx is 2 n_sites x n_pts
+ * column-major in every call.  Calls on one handle are serialised by a mutex inside it and may come from several threads.
+ * The reference memoises environments across calls; this handle keeps nothing between calls (a batch computes every unique
+ * half of its own points once), so _clear_cache is a no-op kept for parity — results are identical either way.
+ * Contraction::with_transform (contraction.rs:118-125) has no entry here: a transform is applied to the returned values by the
+ * caller (the Python binding does so on the host); a C function pointer per element would be the slowest part of a batch.
+ * ===================================================================================== */
+typedef struct t4a_gpu_contraction t4a_gpu_contraction;
+
+/* Contraction::new (contraction.rs:69-110).  INVALID_ARGUMENT, checked before any device work: lengths differ
+ * ("MPO length mismatch"), a.s2 != b.s1 at a site ("Shared shape mismatch at site", naming the site and both dimensions).  The
+ * handle keeps device copies of both operands: a and b may be released at once. */
+t4a_gpu_status t4a_gpu_contraction_new(const t4a_gpu_mpo* a, const t4a_gpu_mpo* b, t4a_gpu_contraction** out);
+void t4a_gpu_contraction_release(t4a_gpu_contraction* h);
+t4a_gpu_status t4a_gpu_contraction_len(const t4a_gpu_contraction* h, size_t* out);
+/* result_site_dims (contraction.rs:142-147): (s1_a, s2_b) per site, 2 x n_sites */
+t4a_gpu_status t4a_gpu_contraction_result_site_dims(const t4a_gpu_contraction* h, size_t* dims2);
+/* evaluate (contraction.rs:187-252) for a batch.  INVALID_ARGUMENT: the empty contraction ("MPO is empty"), an index out of range
+ * ("Index out of bounds: index .. at site .. (max: ..)", contraction.rs:158-175). */
+t4a_gpu_status t4a_gpu_contraction_evaluate(t4a_gpu_contraction* h, const size_t* idx /* 2 n x n_pts */, size_t n_pts, double* out);
+/* evaluate_left(n, .) / evaluate_right(n, .) (contraction.rs:262-383) for a batch: the environment of sites 0 .. n-1 (ra x rb) /
+ * of sites n .. len-1 (la x lb); out receives n_pts column-major matrices one after the other, dims2 their (rows, cols).
+ * n == 0 / n == len give [[1]].  Only the sites an environment covers are range-checked.  INVALID_ARGUMENT: n > len
+ * ("Site n is out of range [0, len]"), an index out of range. */
+t4a_gpu_status t4a_gpu_contraction_evaluate_left(t4a_gpu_contraction* h, size_t n, const size_t* idx, size_t n_pts, double* out,
+                                                 size_t* dims2);
+t4a_gpu_status t4a_gpu_contraction_evaluate_right(t4a_gpu_contraction* h, size_t n, const size_t* idx, size_t n_pts, double* out,
+                                                  size_t* dims2);
+/* The batch evaluation in the manner of TTCache::evaluate_many (cache.rs:558-744): unique left halves of `split` sites and unique
+ * right halves are found on the host, their environments computed once each and paired on the device.  split == 0 applies
+ * find_split_heuristic (cache.rs:690-744); used_split (may be NULL) receives the split that was used.  Environments whose working
+ * set 2 * max(la*lb) + K * lb * ra exceeds 8192 doubles (64 KiB of LDS) are walked through global scratch, above 2 GiB per
+ * workgroup the call is INVALID_ARGUMENT. */
+t4a_gpu_status t4a_gpu_contraction_evaluate_many(t4a_gpu_contraction* h, const size_t* idx, size_t n_pts, size_t split, double* out,
+                                                 size_t* used_split);
+t4a_gpu_status t4a_gpu_contraction_clear_cache(t4a_gpu_contraction* h);
+/* Points evaluated so far through _evaluate, _evaluate_many and _batch_eval (this project's: the function evaluations a cross
+ * interpolation spent on the handle). */
+t4a_gpu_status t4a_gpu_contraction_n_evaluated(const t4a_gpu_contraction* h, size_t* out);
+/* A t4a_gpu_batch_eval_fn whose ctx is a t4a_gpu_contraction*: idx carries the fused site index f = i + S1_a * j of the product (the
+ * fusion of t4a_gpu_mpo_to_tt), n_sites x n_pts column-major.  Decodes, evaluates as _evaluate_many with split == 0, returns n_pts;
+ * a negative status code after recording the message otherwise.  Hand it to t4a_gpu_tci2_set_callback, t4a_gpu_treetci_*,
+ * t4a_gpu_tt_estimate_true_error, t4a_gpu_tt_floating_zone or t4a_gpu_opt_first_pivot for a device-evaluated operator product. */
+int64_t t4a_gpu_contraction_batch_eval(void* ctx, const uint32_t* idx, size_t n_sites, size_t n_pts, double* out);
+/* The product A·B as an MPO by cross interpolation (this project's; no simplett counterpart — the model is the `algorithm = :TCI`
+ * contraction of TensorCrossInterpolation.jl; t4a_gpu_mpo_contract keeps its three algorithms): a contraction of a and b, a
+ * TensorCI2 over the fused local dims S1_a * S2_b with the callback above, crossinterpolate2 with `options`, to_tensor_train, and
+ * the site dims relabelled to (s1_a, s2_b).  n_pivots == 0: the first pivot is found by opt_first_pivot (optfirstpivot.rs) from
+ * the all-zero index through the same evaluator; what crossinterpolate2 answers for a pivot that is still zero is passed through.
+ * initial_pivots: n_sites x n_pivots column-major fused indices.  info: [termination code, rank, function evaluations, last
+ * error estimate]. */
+t4a_gpu_status t4a_gpu_mpo_contract_tci(const t4a_gpu_mpo* a, const t4a_gpu_mpo* b, const t4a_gpu_tci2_options* options,
+                                        const size_t* initial_pivots, size_t n_pivots, t4a_gpu_mpo** out_mpo, double* info /* [4] */);
+
+/* =====================================================================================
  * Quantics transform operators as MPOs — the real-valued part of tensor4all-quanticstransform
  * shift.rs:49-291, flip.rs:44-249, cumsum.rs:76-346, common.rs:549-654, affine.rs:497-553, :673-711, :1386-1834,
  * difference_kernel.rs:29-107.  The complex-valued operators (quantics_fourier_operator, phase_rotation_operator*) are not

@@ -15,6 +15,7 @@
 #include "aci.hpp"
 #include "globalsearch.hpp"
 #include "mpo.hpp"
+#include "contraction.hpp"
 #include "quanticstransform.hpp"
 
 struct t4a_gpu_tci2 {
@@ -51,6 +52,10 @@ struct t4a_gpu_mpo {
 
 struct t4a_gpu_qt_op {
     t4a::QtOperator impl; // host data only
+};
+
+struct t4a_gpu_contraction {
+    std::unique_ptr<t4a::MpoContraction> impl;
 };
 
 namespace t4a {
@@ -3585,6 +3590,151 @@ t4a_gpu_status t4a_gpu_mpo_transpose(const t4a_gpu_mpo* mpo, t4a_gpu_mpo** out)
         T4A_REQUIRE_PTR(out);
         *out = nullptr;
         *out = new t4a_gpu_mpo{mpo->impl->transpose()};
+    });
+}
+
+// ---- Contraction<f64>: the lazy product of two MPOs (tensor4all-simplett/src/mpo/contraction.rs:60-383) ----
+t4a_gpu_status t4a_gpu_contraction_new(const t4a_gpu_mpo* a, const t4a_gpu_mpo* b, t4a_gpu_contraction** out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(a);
+        T4A_REQUIRE_PTR(b);
+        T4A_REQUIRE_PTR(out);
+        *out = nullptr;
+        *out = new t4a_gpu_contraction{std::make_unique<MpoContraction>(*a->impl, *b->impl)};
+    });
+}
+
+void t4a_gpu_contraction_release(t4a_gpu_contraction* h) { delete h; }
+
+t4a_gpu_status t4a_gpu_contraction_len(const t4a_gpu_contraction* h, size_t* out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(h);
+        T4A_REQUIRE_PTR(out);
+        *out = h->impl->len();
+    });
+}
+
+t4a_gpu_status t4a_gpu_contraction_result_site_dims(const t4a_gpu_contraction* h, size_t* dims2)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(h);
+        const auto d = h->impl->result_site_dims();
+        if (!d.empty()) T4A_REQUIRE_PTR(dims2);
+        for (size_t s = 0; s < d.size(); ++s) {
+            dims2[2 * s] = d[s][0];
+            dims2[2 * s + 1] = d[s][1];
+        }
+    });
+}
+
+t4a_gpu_status t4a_gpu_contraction_evaluate(t4a_gpu_contraction* h, const size_t* idx, size_t n_pts, double* out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(h);
+        if (n_pts == 0) return;
+        T4A_REQUIRE_PTR(idx);
+        T4A_REQUIRE_PTR(out);
+        std::vector<uint32_t> u = narrow_indices(idx, checked_mul(n_pts, 2 * h->impl->len(), "index buffer"));
+        h->impl->evaluate(u.data(), n_pts, out);
+    });
+}
+
+extern "C++" {
+static void contraction_environment(t4a_gpu_contraction* h, bool left, size_t n, const size_t* idx, size_t n_pts, double* out, size_t* dims2)
+{
+    T4A_REQUIRE_PTR(h);
+    T4A_REQUIRE_PTR(dims2);
+    const std::array<size_t, 2> d = left ? h->impl->left_dims(n) : h->impl->right_dims(n); // n out of range is refused here
+    dims2[0] = d[0];
+    dims2[1] = d[1];
+    if (n_pts == 0) return;
+    T4A_REQUIRE_PTR(idx);
+    T4A_REQUIRE_PTR(out);
+    std::vector<uint32_t> u = narrow_indices(idx, checked_mul(n_pts, 2 * h->impl->len(), "index buffer"));
+    if (left)
+        h->impl->evaluate_left(n, u.data(), n_pts, out, dims2);
+    else
+        h->impl->evaluate_right(n, u.data(), n_pts, out, dims2);
+}
+} // extern "C++"
+
+t4a_gpu_status t4a_gpu_contraction_evaluate_left(t4a_gpu_contraction* h, size_t n, const size_t* idx, size_t n_pts, double* out, size_t* dims2)
+{
+    return guarded([&] { contraction_environment(h, true, n, idx, n_pts, out, dims2); });
+}
+
+t4a_gpu_status t4a_gpu_contraction_evaluate_right(t4a_gpu_contraction* h, size_t n, const size_t* idx, size_t n_pts, double* out, size_t* dims2)
+{
+    return guarded([&] { contraction_environment(h, false, n, idx, n_pts, out, dims2); });
+}
+
+t4a_gpu_status t4a_gpu_contraction_evaluate_many(t4a_gpu_contraction* h, const size_t* idx, size_t n_pts, size_t split, double* out,
+                                                 size_t* used_split)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(h);
+        if (used_split) *used_split = split;
+        if (n_pts == 0) return; // cache.rs:563-565
+        T4A_REQUIRE_PTR(idx);
+        T4A_REQUIRE_PTR(out);
+        std::vector<uint32_t> u = narrow_indices(idx, checked_mul(n_pts, 2 * h->impl->len(), "index buffer"));
+        const size_t s = h->impl->evaluate_many(u.data(), n_pts, split, out);
+        if (used_split) *used_split = s;
+    });
+}
+
+t4a_gpu_status t4a_gpu_contraction_clear_cache(t4a_gpu_contraction* h)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(h);
+        h->impl->clear_cache();
+    });
+}
+
+t4a_gpu_status t4a_gpu_contraction_n_evaluated(const t4a_gpu_contraction* h, size_t* out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(h);
+        T4A_REQUIRE_PTR(out);
+        *out = h->impl->n_evaluated();
+    });
+}
+
+int64_t t4a_gpu_contraction_batch_eval(void* ctx, const uint32_t* idx, size_t n_sites, size_t n_pts, double* out)
+{
+    const t4a_gpu_status st = guarded([&] {
+        T4A_REQUIRE_PTR(ctx);
+        if (n_pts == 0) return;
+        T4A_REQUIRE_PTR(idx);
+        T4A_REQUIRE_PTR(out);
+        static_cast<t4a_gpu_contraction*>(ctx)->impl->evaluate_fused(idx, n_sites, n_pts, out);
+    });
+    return st == T4A_GPU_SUCCESS ? (int64_t)n_pts : (int64_t)st; // status codes are negative
+}
+
+t4a_gpu_status t4a_gpu_mpo_contract_tci(const t4a_gpu_mpo* a, const t4a_gpu_mpo* b, const t4a_gpu_tci2_options* options,
+                                        const size_t* initial_pivots, size_t n_pivots, t4a_gpu_mpo** out_mpo, double* info)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(a);
+        T4A_REQUIRE_PTR(b);
+        T4A_REQUIRE_PTR(options);
+        T4A_REQUIRE_PTR(out_mpo);
+        T4A_REQUIRE_PTR(info);
+        *out_mpo = nullptr;
+        if (n_pivots) T4A_REQUIRE_PTR(initial_pivots);
+        const TCI2Options o = convert_options(options);
+        const size_t ns = a->impl->len();
+        std::vector<std::vector<uint32_t>> piv(n_pivots, std::vector<uint32_t>(ns));
+        for (size_t k = 0; k < n_pivots; ++k)
+            for (size_t s = 0; s < ns; ++s) {
+                const size_t v = initial_pivots[s + ns * k];
+                if (v > 0xFFFFFFFFull) throw Error(T4A_GPU_INVALID_ARGUMENT, "pivot value out of bounds");
+                piv[k][s] = (uint32_t)v;
+            }
+        *out_mpo = new t4a_gpu_mpo{mpo_contract_tci(*a->impl, *b->impl, o, std::move(piv), info)};
     });
 }
 

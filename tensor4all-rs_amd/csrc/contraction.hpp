@@ -1,0 +1,87 @@
+// contraction.hpp — device-resident mirror of tensor4all-simplett's Contraction<f64> (crates/tensor4all-simplett/src/mpo/
+// contraction.rs:60-383): the lazy product of two MPOs.  Single elements and left / right environments of A·B are computed
+// without ever forming the product with bonds la*lb.  The environment walks run in the kernels of kernels_contraction.hip, the
+// pairing of a left with a right environment is tt_env_dot (kernels_tt.hip) over la*lb entries; unique halves and the split are
+// host integer work shared with TensorTrain::evaluate_many (tt.hpp).
+//
+// Differences from the reference, none of them visible in a result:
+//  * the reference memoises environments in hash maps across calls; here nothing is kept between calls — a batch call computes
+//    every unique half of ITS points once.  clear_cache() exists for API parity and does nothing.
+//  * the transform function of Contraction::with_transform (contraction.rs:118-125) is applied by the language binding on the
+//    host to the returned values (a C function pointer per element would be the slowest part of a batch); it is not part of
+//    this class.
+#pragma once
+
+#include <mutex>
+
+#include "mpo.hpp"
+
+namespace t4a {
+
+class MpoContraction {
+public:
+    // Contraction::new (contraction.rs:69-110): lengths and the shared dimension a.s2 == b.s1 of every site are checked before
+    // any device work, with the wording of mpo_contract.  The object keeps device copies of both operands (the reference takes
+    // them by value): the caller's MPOs may be released afterwards.
+    MpoContraction(Mpo& a, Mpo& b);
+
+    size_t len() const { return n_; }
+    std::vector<std::array<size_t, 2>> result_site_dims() const; // (s1_a, s2_b) per site (contraction.rs:142-147)
+    std::vector<size_t> fused_local_dims() const;                 // s1_a * s2_b per site: the index i + s1_a * j
+    void clear_cache() {}                                         // contraction.rs:150-153: nothing is cached here
+
+    // idx: 2 len x n_pts column-major, [i_0, j_0, i_1, j_1, ...] per point.
+    // evaluate (contraction.rs:187-252): the left-to-right walk of every point.
+    void evaluate(const uint32_t* idx, size_t n_pts, double* out);
+    // evaluate_left(n, .) / evaluate_right(n, .) (contraction.rs:262-383): out holds n_pts column-major matrices of dims2 =
+    // (rows, cols): ra x rb behind site n-1 / la x lb in front of site n; [[1]] for n == 0 / n == len.
+    void evaluate_left(size_t n, const uint32_t* idx, size_t n_pts, double* out, size_t dims2[2]);
+    void evaluate_right(size_t n, const uint32_t* idx, size_t n_pts, double* out, size_t dims2[2]);
+    std::array<size_t, 2> left_dims(size_t n) const;
+    std::array<size_t, 2> right_dims(size_t n) const;
+    // The batch evaluation in the manner of TTCache::evaluate_many (cache.rs:558-744): unique left halves of `split` sites and
+    // unique right halves, two environment launches, one pairing launch, one download.  split == 0: find_split_heuristic.
+    // Returns the split that was used.
+    size_t evaluate_many(const uint32_t* idx, size_t n_pts, size_t split, double* out);
+    // the same for the fused site index f = i + s1_a * j (n_sites x n_pts column-major): the batch callback of a TensorCI2
+    void evaluate_fused(const uint32_t* fidx, size_t n_sites, size_t n_pts, double* out);
+
+    // points evaluated by evaluate / evaluate_many / evaluate_fused so far
+    size_t n_evaluated()
+    {
+        std::lock_guard<std::mutex> lock(mu_);
+        return n_evaluated_;
+    }
+
+private:
+    struct Site {
+        size_t la, s1, k, ra, lb, s2, rb;
+    };
+    void validate_indices(const uint32_t* idx, size_t n_pts, size_t first, size_t last) const; // contraction.rs:158-175
+    void upload_descs();
+    // environment kernels over sites [0, n) / [n, len): n_items packed index halves in device memory -> d_out (n_items x ld)
+    void launch_left(size_t n, const uint32_t* d_idx, size_t n_items, double* d_out, size_t ld);
+    void launch_right(size_t n, const uint32_t* d_idx, size_t n_items, double* d_out, size_t ld);
+    double* working_set(size_t n_items, int& env_cap, int& t_cap, int& blocks, size_t first, size_t last, bool left);
+    void environments(bool left, size_t n, const uint32_t* idx, size_t n_pts, double* out);
+
+    std::mutex mu_; // every entry point: the callback route may call from several host threads
+    size_t n_ = 0;
+    std::vector<Site> sites_;
+    std::unique_ptr<Mpo> a_, b_;
+    Engine* eng_ = nullptr; // a_'s engine: this object's own stream
+    bool descs_uploaded_ = false;
+    size_t n_evaluated_ = 0;
+    DevBuf<ContractionSiteDesc> d_desc_;
+    DevBuf<uint32_t> d_idx_, d_il_, d_ir_;
+    DevBuf<double> d_vals_, d_envl_, d_envr_, d_scratch_l_, d_scratch_r_;
+};
+
+// contract by cross interpolation (this project's; the model is TensorCrossInterpolation.jl's `algorithm = :TCI` contraction):
+// a TensorCI2 over the fused local dims s1_a * s2_b whose function is MpoContraction::evaluate_fused, then to_tensor_train and an
+// MPO with site dims (s1_a, s2_b).  info: [termination code, rank, function evaluations, last error estimate].
+struct TCI2Options;
+std::unique_ptr<Mpo> mpo_contract_tci(Mpo& a, Mpo& b, const TCI2Options& options, std::vector<std::vector<uint32_t>> initial_pivots,
+                                      double info[4]);
+
+} // namespace t4a

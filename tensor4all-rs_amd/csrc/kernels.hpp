@@ -526,6 +526,25 @@ struct MpoSiteJob {
 void mpo_site_contract_launch(const MpoSiteJob* d_jobs, int n_jobs, unsigned long long total, hipStream_t stream);
 
 // ------------------------------------------------------------------------------------------------
+// kernels_contraction.hip — environments of the lazy product A·B of two MPOs (simplett/src/mpo/contraction.rs:262-383) for a batch
+// of unique index halves, one workgroup per half.  An environment is a matrix over the bond pair, column-major [a + dim_a * b];
+// item `it` of a launch is written to d_out + it * ld.  idx holds the (i, j) pairs of the walked sites per item, item-major.
+// env_cap >= every la*lb and ra*rb of the walked sites (and >= 1), t_cap >= every K*ra*lb (left) / K*la*rb (right).  The working set
+// of a workgroup is 2 * env_cap + t_cap doubles: in the LDS when d_scratch is null (the caller checks CONTRACTION_LDS_DOUBLES), else in
+// d_scratch + block * (2 * env_cap + t_cap), which holds `blocks` such slices.  blocks <= n_items workgroups walk the items.
+// ------------------------------------------------------------------------------------------------
+struct ContractionSiteDesc {
+    const double* A; // [la, s1, k, ra]
+    const double* B; // [lb, k, s2, rb]
+    int la, s1, k, ra, lb, s2, rb, pad_;
+};
+constexpr size_t CONTRACTION_LDS_DOUBLES = 8192; // 64 KiB: what a workgroup can ask for without opting into a larger LDS allocation
+void contraction_env_left_launch(const ContractionSiteDesc* d_sites, int n_walk, const uint32_t* d_idx, int n_items, double* d_out, int ld,
+                                 int env_cap, int t_cap, double* d_scratch, int blocks, hipStream_t stream);
+void contraction_env_right_launch(const ContractionSiteDesc* d_sites, int n_sites, int first, const uint32_t* d_idx, int n_items,
+                                  double* d_out, int ld, int env_cap, int t_cap, double* d_scratch, int blocks, hipStream_t stream);
+
+// ------------------------------------------------------------------------------------------------
 // kernels_small.hip — the small-problem engine (round 6): the WHOLE optimize_with_finder loop of a small TensorCI2 problem
 // (tensorci2.rs:1626-1802: iteration loop, update_pivots chain :1821-2007, fill_site_tensors :1065-1186, convergence_criterion
 // :1407-1437, final sweep1site :1787-1794) in ONE launch.  Index sets, history snapshots and lists live in the LDS, the candidate

@@ -42,40 +42,57 @@ inline uint64_t hash_digits(const uint32_t* p, size_t n)
     }
     return h;
 }
+} // namespace
 
-// First-occurrence unique map of fixed-width digit strings (cache.rs IndexMapper): `first` receives the point
-// index of each unique string in order of first appearance, `which[p]` the position of point p's string.
-struct UniqueMap {
-    std::vector<uint32_t> first, which;
-    void build(const uint32_t* idx, size_t stride, size_t off, size_t width, size_t n_pts)
-    {
-        first.clear();
-        which.assign(n_pts, 0);
-        size_t cap = 16;
-        while (cap < 2 * n_pts + 2) cap <<= 1;
-        std::vector<uint32_t> table(cap, 0xFFFFFFFFu);
-        for (size_t p = 0; p < n_pts; ++p) {
-            const uint32_t* key = idx + p * stride + off;
-            size_t slot = (size_t)hash_digits(key, width) & (cap - 1);
-            for (;;) {
-                const uint32_t u = table[slot];
-                if (u == 0xFFFFFFFFu) {
-                    table[slot] = (uint32_t)first.size();
-                    which[p] = (uint32_t)first.size();
-                    first.push_back((uint32_t)p);
-                    break;
-                }
-                const uint32_t* other = idx + (size_t)first[u] * stride + off;
-                if (std::equal(key, key + width, other)) {
-                    which[p] = u;
-                    break;
-                }
-                slot = (slot + 1) & (cap - 1);
+void UniqueMap::build(const uint32_t* idx, size_t stride, size_t off, size_t width, size_t n_pts)
+{
+    first.clear();
+    which.assign(n_pts, 0);
+    size_t cap = 16;
+    while (cap < 2 * n_pts + 2) cap <<= 1;
+    std::vector<uint32_t> table(cap, 0xFFFFFFFFu);
+    for (size_t p = 0; p < n_pts; ++p) {
+        const uint32_t* key = idx + p * stride + off;
+        size_t slot = (size_t)hash_digits(key, width) & (cap - 1);
+        for (;;) {
+            const uint32_t u = table[slot];
+            if (u == 0xFFFFFFFFu) {
+                table[slot] = (uint32_t)first.size();
+                which[p] = (uint32_t)first.size();
+                first.push_back((uint32_t)p);
+                break;
             }
+            const uint32_t* other = idx + (size_t)first[u] * stride + off;
+            if (std::equal(key, key + width, other)) {
+                which[p] = u;
+                break;
+            }
+            slot = (slot + 1) & (cap - 1);
         }
     }
-};
-} // namespace
+}
+
+size_t find_split_heuristic(const uint32_t* idx, size_t n, size_t digits, size_t n_pts) // cache.rs:690-744
+{
+    if (n <= 1) return std::max<size_t>(n, 1);
+    const size_t cand[3] = {n / 4, n / 2, n * 3 / 4};
+    bool have = false;
+    size_t best_p = 0, best_c = 0;
+    UniqueMap ul, ur;
+    for (size_t p : cand) {
+        if (p < 1 || p >= n) continue;
+        ul.build(idx, n * digits, 0, p * digits, n_pts);
+        ur.build(idx, n * digits, p * digits, (n - p) * digits, n_pts);
+        const size_t c = ul.first.size() + ur.first.size();
+        if (!have || c < best_c) { // min_by_key keeps the first minimum
+            have = true;
+            best_p = p;
+            best_c = c;
+        }
+    }
+    if (!have) throw Error(T4A_GPU_INTERNAL_ERROR, "cache heuristic could not choose a valid split");
+    return best_p;
+}
 
 TensorTrain::TensorTrain(const std::vector<std::array<size_t, 3>>& dims3, const double* host_data)
 {
@@ -422,25 +439,7 @@ void TensorTrain::compress(const CompressionOptions& opt) // compression.rs:375-
 // ------------------------------------------------------------------------------------------------
 size_t TensorTrain::find_split_heuristic(const uint32_t* idx, size_t n_pts) const
 {
-    const size_t n = cores.size();
-    if (n <= 1) return std::max<size_t>(n, 1);
-    const size_t cand[3] = {n / 4, n / 2, n * 3 / 4};
-    bool have = false;
-    size_t best_p = 0, best_c = 0;
-    UniqueMap ul, ur;
-    for (size_t p : cand) {
-        if (p < 1 || p >= n) continue;
-        ul.build(idx, n, 0, p, n_pts);
-        ur.build(idx, n, p, n - p, n_pts);
-        const size_t c = ul.first.size() + ur.first.size();
-        if (!have || c < best_c) { // min_by_key keeps the first minimum
-            have = true;
-            best_p = p;
-            best_c = c;
-        }
-    }
-    if (!have) throw Error(T4A_GPU_INTERNAL_ERROR, "cache heuristic could not choose a valid split");
-    return best_p;
+    return t4a::find_split_heuristic(idx, cores.size(), 1, n_pts);
 }
 
 size_t TensorTrain::evaluate_many(const uint32_t* idx, size_t n_pts, size_t split, double* out)

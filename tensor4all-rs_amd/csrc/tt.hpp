@@ -26,6 +26,19 @@ struct CompressionOptions { // compression.rs:75-125
     bool normalize_error = true;
 };
 
+// First-occurrence unique map of fixed-width digit strings (cache.rs IndexMapper): `first` receives the point
+// index of each unique string in order of first appearance, `which[p]` the position of point p's string.
+// String p is idx[p * stride + off .. + width).
+struct UniqueMap {
+    std::vector<uint32_t> first, which;
+    void build(const uint32_t* idx, size_t stride, size_t off, size_t width, size_t n_pts);
+};
+
+// find_split_heuristic (cache.rs:690-744) for points of n_sites sites with `digits` digits each (1: a tensor train, 2: the
+// (i, j) pairs of an MPO contraction): of the candidates n/4, n/2, 3n/4 inside [1, n) the first with the fewest unique left plus
+// unique right halves.  n_sites <= 1 gives max(n_sites, 1).
+size_t find_split_heuristic(const uint32_t* idx, size_t n_sites, size_t digits, size_t n_pts);
+
 class TensorTrain {
 public:
     // dims3: (l, s, r) per site; host_data: the cores concatenated, each column-major.

@@ -2127,7 +2127,8 @@ def tensors_to_tensor_train(tensors):
 # MPO<f64> and mpo::contract (simplett/src/mpo/): module t4a_amd.mpo, the dispatching `contract` stays under its module name there
 # (t4a_amd.contract is the labelled-tensor network contraction)
 from . import mpo  # noqa: E402
-from .mpo import MPO, ContractionOptions, ContractionAlgorithm, FactorizeMethod, contract_naive, contract_zipup  # noqa: E402,F401
+from .mpo import (MPO, ContractionOptions, ContractionAlgorithm, FactorizeMethod, contract_naive, contract_zipup,  # noqa: E402,F401
+                  Contraction, contract_tci)
 from . import quanticstransform  # noqa: E402
 from .quanticstransform import (BoundaryCondition, TriangleType, AffineParams, QuanticsOperator, shift_operator,  # noqa: E402,F401
                                 shift_operator_multivar, flip_operator, flip_operator_multivar, cumsum_operator, triangle_operator,

@@ -1,13 +1,15 @@
 """MPO<f64> and the contraction of two MPOs (tensor4all-simplett/src/mpo/) — site tensors (left, s1, s2, right) live on the device.
 
 Mirrors the Rust module ``mpo``: ``MPO``, ``ContractionOptions``, ``ContractionAlgorithm``, ``FactorizeMethod``, ``contract``,
-``contract_naive``, ``contract_zipup``.
+``contract_naive``, ``contract_zipup``, and the lazy product ``Contraction`` (mpo/contraction.rs:60-383).  ``contract_tci`` is this
+project's: the product as an MPO by cross interpolation of its elements (the ``algorithm = :TCI`` contraction of
+TensorCrossInterpolation.jl).
 """
 import ctypes
 
 import numpy as np
 
-from . import (_lib, _check, _p, T4aError, INVALID_ARGUMENT, SimpleTensorTrain, c_size_t, c_double, c_int32, c_void_p)
+from . import (_lib, _check, _p, T4aError, INVALID_ARGUMENT, SimpleTensorTrain, TCI2Options, c_size_t, c_double, c_int32, c_void_p)
 
 
 class ContractionAlgorithm:
@@ -188,3 +190,173 @@ def contract_zipup(a, b, options=None):
 def contract(a, b, algorithm=ContractionAlgorithm.Naive, options=None):
     """contract (mpo/dispatch.rs:67-92): Naive always compresses; Fit raises NOT_IMPLEMENTED."""
     return _contract(a, b, algorithm, True, options)
+
+
+def _index_pairs(indices, n, need, exact):
+    """[(i1, j1), ...] or an (n_pts, m, 2) array -> ((n_pts, n, 2) uintp array padded with zeros behind the m pairs given, single).
+    m must equal `need` (exact) or reach it; the messages are those of contraction.rs:187-192, :275-279, :340-348."""
+    idx = np.asarray(indices, dtype=np.int64)
+    if idx.size == 0 and idx.ndim < 3:
+        idx = idx.reshape(0, 2)
+    single = idx.ndim == 2
+    idx = idx[None] if single else idx
+    if idx.ndim != 3 or idx.shape[2] != 2:
+        raise T4aError(INVALID_ARGUMENT, "indices must be [(i1, j1), ...] or an (n_pts, n, 2) array")
+    got = idx.shape[1]
+    if exact and got != need:
+        raise T4aError(INVALID_ARGUMENT, f"Invalid operation: Expected {need} index pairs, got {got}")
+    if got < need:
+        raise T4aError(INVALID_ARGUMENT, f"Invalid operation: Expected at least {need} index pairs, got {got}")
+    if (idx < 0).any():
+        raise T4aError(INVALID_ARGUMENT, "negative index")
+    full = np.zeros((idx.shape[0], n, 2), dtype=np.uintp)
+    k = min(got, n)
+    full[:, :k] = idx[:, :k]
+    return np.ascontiguousarray(full), single
+
+
+def _fused_pivots(initial_pivots, n):
+    """fused multi-indices -> ((n_pivots, n) uintp array, n_pivots); None or an empty list -> no pivots"""
+    if initial_pivots is None or len(initial_pivots) == 0:
+        return np.zeros(1, dtype=np.uintp), 0
+    piv = np.asarray(initial_pivots, dtype=np.int64)
+    if piv.ndim != 2 or piv.shape[1] != n:
+        raise T4aError(INVALID_ARGUMENT, "Pivot length must match number of sites")
+    if (piv < 0).any():
+        raise T4aError(INVALID_ARGUMENT, "negative index")
+    return np.ascontiguousarray(piv.astype(np.uintp)), piv.shape[0]
+
+
+class Contraction:
+    """Contraction<f64> (mpo/contraction.rs:60-383): single elements and left / right environments of A·B without forming the product.
+
+    Both operands are copied on the device: ``a`` and ``b`` may be dropped afterwards.  The reference memoises environments across
+    calls; this one keeps nothing between calls (``clear_cache`` is a no-op), the results are identical either way.
+    An index tuple is ``[(i_1, j_1), (i_2, j_2), ...]``: ``i_k`` indexes s1 of A, ``j_k`` indexes s2 of B."""
+
+    def __init__(self, a, b):
+        self._h = c_void_p()
+        self._f = None
+        _check(_lib.t4a_gpu_contraction_new(a._h, b._h, ctypes.byref(self._h)))
+
+    @classmethod
+    def with_transform(cls, a, b, f):
+        """Contraction::with_transform (contraction.rs:118-125): ``f`` is applied on the host to every value ``evaluate`` and
+        ``evaluate_many`` return — to the whole array at once when it accepts one, else element by element.  It is not part of the
+        C ABI, so ``as_callback`` (the native route) refuses a contraction that has one."""
+        self = cls(a, b)
+        self._f = f
+        return self
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            _lib.t4a_gpu_contraction_release(h)
+            self._h = None
+
+    def __len__(self):
+        v = c_size_t(0)
+        _check(_lib.t4a_gpu_contraction_len(self._h, ctypes.byref(v)))
+        return v.value
+
+    def len(self):
+        return len(self)
+
+    def result_site_dims(self):
+        """[(s1_a, s2_b)] per site (contraction.rs:142-147)."""
+        n = len(self)
+        d = np.zeros(max(2 * n, 1), dtype=np.uintp)
+        _check(_lib.t4a_gpu_contraction_result_site_dims(self._h, _p(d)))
+        return [(int(a), int(b)) for a, b in d[:2 * n].reshape(-1, 2)]
+
+    def clear_cache(self):
+        """clear_cache (contraction.rs:150-153): nothing is cached between calls here, so nothing happens."""
+        _check(_lib.t4a_gpu_contraction_clear_cache(self._h))
+
+    def n_evaluated(self):
+        """Points evaluated so far through evaluate, evaluate_many and the native callback."""
+        v = c_size_t(0)
+        _check(_lib.t4a_gpu_contraction_n_evaluated(self._h, ctypes.byref(v)))
+        return v.value
+
+    def _transform(self, vals):
+        if self._f is None:
+            return vals
+        try:
+            out = np.asarray(self._f(vals), dtype=np.float64)
+            if out.shape == vals.shape:
+                return out
+        except (TypeError, ValueError):
+            pass
+        return np.array([self._f(float(v)) for v in vals], dtype=np.float64)
+
+    def _pairs(self, indices, need, exact):
+        idx, single = _index_pairs(indices, len(self), need, exact)
+        return (idx if idx.size else np.zeros((idx.shape[0], 1, 2), dtype=np.uintp)), single  # never a NULL buffer
+
+    def evaluate(self, indices):
+        """evaluate (contraction.rs:187-252): [(i1, j1), ...] -> float; an (n_pts, n, 2) array -> values."""
+        idx, single = self._pairs(indices, len(self), True)
+        out = np.zeros(idx.shape[0])
+        _check(_lib.t4a_gpu_contraction_evaluate(self._h, _p(idx), c_size_t(idx.shape[0]), _p(out)))
+        out = self._transform(out)
+        return float(out[0]) if single else out
+
+    def _environment(self, fn, n, indices, need):
+        total = len(self)
+        if n > total:  # contraction.rs:263-267, :326-330
+            raise T4aError(INVALID_ARGUMENT, f"Invalid operation: Site {n} is out of range [0, {total}]")
+        if n < 0:
+            raise T4aError(INVALID_ARGUMENT, "negative site")
+        idx, single = self._pairs(indices, need, False)
+        dims = np.zeros(2, dtype=np.uintp)
+        _check(fn(self._h, c_size_t(n), None, c_size_t(0), None, _p(dims)))
+        rows, cols = int(dims[0]), int(dims[1])
+        out = np.zeros(max(idx.shape[0] * rows * cols, 1))
+        _check(fn(self._h, c_size_t(n), _p(idx), c_size_t(idx.shape[0]), _p(out), _p(dims)))
+        mats = out[:idx.shape[0] * rows * cols].reshape((idx.shape[0], cols, rows)).transpose(0, 2, 1)
+        return mats[0].copy() if single else mats.copy()
+
+    def evaluate_left(self, n, indices):
+        """evaluate_left (contraction.rs:262-314): the ra x rb environment of sites 0 .. n-1; [[1]] for n == 0.  At least n pairs."""
+        return self._environment(_lib.t4a_gpu_contraction_evaluate_left, n, indices, 0 if n == 0 else n)
+
+    def evaluate_right(self, n, indices):
+        """evaluate_right (contraction.rs:324-383): the la x lb environment of sites n .. len-1; [[1]] for n == len.  The pairs are
+        read at their absolute positions, so all len of them are needed."""
+        return self._environment(_lib.t4a_gpu_contraction_evaluate_right, n, indices, 0 if n == len(self) else len(self))
+
+    def evaluate_many(self, indices, split=None):
+        """Batch evaluation with shared halves computed once (TTCache::evaluate_many, cache.rs:558-744): (values, split used);
+        ``split=None`` applies find_split_heuristic."""
+        idx, single = self._pairs(indices, len(self), True)
+        if split is not None and split <= 0:
+            raise T4aError(INVALID_ARGUMENT, f"Invalid split position: {split} (n_sites={len(self)})")
+        out = np.zeros(idx.shape[0])
+        used = c_size_t(0)
+        _check(_lib.t4a_gpu_contraction_evaluate_many(self._h, _p(idx), c_size_t(idx.shape[0]), c_size_t(0 if split is None else split),
+                                                      _p(out), ctypes.byref(used)))
+        return self._transform(out), used.value
+
+    def as_callback(self):
+        """(function pointer, ctx, keepalive) for ``TensorCI2.set_callback_raw``: t4a_gpu_contraction_batch_eval over this handle, which
+        takes the fused site index i + s1_a * j.  The third element keeps the contraction alive as long as the TensorCI2 holds it."""
+        if self._f is not None:
+            raise T4aError(INVALID_ARGUMENT, "a contraction with a transform has no native callback: the transform runs in Python")
+        fn = ctypes.cast(_lib.t4a_gpu_contraction_batch_eval, c_void_p).value
+        return fn, self._h.value, self
+
+
+def contract_tci(a, b, options=None, initial_pivots=None):
+    """The product A·B as an MPO by cross interpolation over the fused site index i + s1_a * j (t4a_gpu_mpo_contract_tci; this
+    project's).  ``options``: a TCI2Options, default tolerance 1e-12 without global pivot search; ``initial_pivots``: fused
+    multi-indices, default the result of opt_first_pivot from the all-zero index.  The result carries ``tci_info``:
+    termination, rank, n_evaluations, error."""
+    o = (TCI2Options(tolerance=1e-12, max_nglobal_pivot=0, nsearch=0) if options is None else options).to_c()
+    piv, n_piv = _fused_pivots(initial_pivots, len(a))
+    h = c_void_p()
+    info = np.zeros(4)
+    _check(_lib.t4a_gpu_mpo_contract_tci(a._h, b._h, ctypes.byref(o), _p(piv), c_size_t(n_piv), ctypes.byref(h), _p(info)))
+    m = MPO._adopt(h)
+    m.tci_info = {"termination": int(info[0]), "rank": int(info[1]), "n_evaluations": int(info[2]), "error": float(info[3])}
+    return m
