@@ -782,11 +782,7 @@ TreeAciLocalResult treeaci_local_update(Engine& eng, const std::vector<size_t>& 
         eng.sync();
     }
     for (double v : out.local_values) out.sampled_scale = std::fmax(out.sampled_scale, std::fabs(v)); // (fold with f64::max: a NaN is dropped)
-    RrLUOptions lo;
-    lo.max_bond_dim = max_bond_dim == 0 ? std::numeric_limits<size_t>::max() : max_bond_dim;
-    lo.rel_tol = scale_tolerance ? tolerance : 0.0;
-    lo.abs_tol = scale_tolerance ? 0.0 : tolerance;
-    lo.left_orthogonal = left_orthogonal;
+    const RrLUOptions lo = RrLUOptions::from_abi(max_bond_dim, scale_tolerance ? tolerance : 0.0, scale_tolerance ? 0.0 : tolerance, left_orthogonal);
     LuciResult r = eng.luci(d_pi, (int)row_count, (int)col_count, lo, true, false);
     out.pivot_errors = r.pivot_errors;
     if (r.rank == 0) { // local_update.rs:230-238

@@ -12,6 +12,7 @@
 #include "tree.hpp"
 #include "quantics.hpp"
 #include "tensorops.hpp"
+#include "dense.hpp"
 #include "aci.hpp"
 #include "globalsearch.hpp"
 #include "mpo.hpp"
@@ -174,6 +175,47 @@ size_t checked_mul(size_t a, size_t b, const char* what)
     if (a != 0 && b > std::numeric_limits<size_t>::max() / a)
         throw Error(T4A_GPU_INVALID_ARGUMENT, std::string(what) + " overflows usize");
     return a * b;
+}
+
+// what the three LUCI entry points check before they take the lock (the source is the matrix `a` or the callback `fill_block`;
+// rook: the 65535 limit of the rook routes).  Returns m * n.
+size_t luci_prologue(size_t m, size_t n, const size_t* rank, const size_t* rows, const size_t* cols, const double* pivot_errors,
+                     bool source_is_null, const char* source_is_null_message, const double* left, const double* right, bool rook)
+{
+    T4A_REQUIRE_PTR(rank);
+    T4A_REQUIRE_PTR(rows);
+    T4A_REQUIRE_PTR(cols);
+    T4A_REQUIRE_PTR(pivot_errors);
+    const size_t count = checked_mul(m, n, "matrix shape");
+    require_int_dims({m, n}, "matrix shape");
+    if (count) {
+        if (source_is_null) throw Error(T4A_GPU_NULL_POINTER, source_is_null_message);
+        T4A_REQUIRE_PTR(left);
+        T4A_REQUIRE_PTR(right);
+    }
+    if (rook && (m > 65535 || n > 65535)) throw Error(T4A_GPU_NOT_IMPLEMENTED, "luci: dimensions above 65535 are not supported");
+    return count;
+}
+
+void luci_outputs(Engine& e, const LuciResult& r, size_t m, size_t n, size_t* rank, size_t* rows, size_t* cols,
+                  double* pivot_errors, double* left, double* right)
+{
+    *rank = (size_t)r.rank;
+    for (int i = 0; i < r.rank; ++i) {
+        rows[i] = (size_t)r.row_perm[i];
+        cols[i] = (size_t)r.col_perm[i];
+    }
+    for (size_t i = 0; i < r.pivot_errors.size(); ++i) pivot_errors[i] = r.pivot_errors[i];
+    if (r.rank > 0) {
+        download(e, left, e.left(), m * (size_t)r.rank);
+        download(e, right, e.right(), n * (size_t)r.rank);
+    }
+}
+
+RookWork& dense_rook_work()
+{
+    static RookWork w; // guarded by g_dense_mutex like the dense engine itself
+    return w;
 }
 
 } // namespace
@@ -344,12 +386,7 @@ t4a_gpu_status t4a_gpu_rrlu_f64(double* a_inout, size_t m, size_t n, size_t max_
         Engine& e = dense_engine();
         double* d_a = e.pi(std::max<size_t>(count, 1));
         upload(e, d_a, a_inout, count);
-        RrLUOptions o;
-        o.max_bond_dim = max_bond_dim == 0 ? std::numeric_limits<size_t>::max() : max_bond_dim;
-        o.rel_tol = rel_tol;
-        o.abs_tol = abs_tol;
-        o.left_orthogonal = left_orthogonal != 0;
-        LuciResult r = e.luci(d_a, (int)m, (int)n, o, false, true);
+        LuciResult r = e.luci(d_a, (int)m, (int)n, RrLUOptions::from_abi(max_bond_dim, rel_tol, abs_tol, left_orthogonal != 0), false, true);
         if (count) download(e, a_inout, e.lu_buf(), count);
         for (size_t i = 0; i < m; ++i) row_perm[i] = (size_t)r.row_perm[i];
         for (size_t j = 0; j < n; ++j) col_perm[j] = (size_t)r.col_perm[j];
@@ -363,37 +400,13 @@ t4a_gpu_status t4a_gpu_luci_f64(const double* a, size_t m, size_t n, size_t max_
                                 double* pivot_errors, double* left, double* right)
 {
     return guarded([&] {
-        T4A_REQUIRE_PTR(rank);
-        T4A_REQUIRE_PTR(rows);
-        T4A_REQUIRE_PTR(cols);
-        T4A_REQUIRE_PTR(pivot_errors);
-        const size_t count = checked_mul(m, n, "matrix shape");
-        require_int_dims({m, n}, "matrix shape");
-        if (count) {
-            T4A_REQUIRE_PTR(a);
-            T4A_REQUIRE_PTR(left);
-            T4A_REQUIRE_PTR(right);
-        }
+        const size_t count = luci_prologue(m, n, rank, rows, cols, pivot_errors, a == nullptr, "a is null", left, right, false);
         std::lock_guard<std::mutex> lock(g_dense_mutex);
         Engine& e = dense_engine();
         double* d_a = e.pi(std::max<size_t>(count, 1));
         upload(e, d_a, a, count);
-        RrLUOptions o;
-        o.max_bond_dim = max_bond_dim == 0 ? std::numeric_limits<size_t>::max() : max_bond_dim;
-        o.rel_tol = rel_tol;
-        o.abs_tol = abs_tol;
-        o.left_orthogonal = left_orthogonal != 0;
-        LuciResult r = e.luci(d_a, (int)m, (int)n, o, true, false);
-        *rank = (size_t)r.rank;
-        for (int i = 0; i < r.rank; ++i) {
-            rows[i] = (size_t)r.row_perm[i];
-            cols[i] = (size_t)r.col_perm[i];
-        }
-        for (size_t i = 0; i < r.pivot_errors.size(); ++i) pivot_errors[i] = r.pivot_errors[i];
-        if (r.rank > 0) {
-            download(e, left, e.left(), m * (size_t)r.rank);
-            download(e, right, e.right(), n * (size_t)r.rank);
-        }
+        LuciResult r = e.luci(d_a, (int)m, (int)n, RrLUOptions::from_abi(max_bond_dim, rel_tol, abs_tol, left_orthogonal != 0), true, false);
+        luci_outputs(e, r, m, n, rank, rows, cols, pivot_errors, left, right);
     });
 }
 
@@ -421,23 +434,10 @@ t4a_gpu_status t4a_gpu_gemm_batched_f64(size_t batch, size_t m, size_t k, size_t
         if (k == 0) {
             fill_launch(e.d_tmp2.get(), nc, 0.0, e.stream());
         } else {
-            GemmDesc g;
-            g.m = (int)m;
-            g.n = (int)n;
-            g.k = (int)k;
-            g.A = da;
-            g.lda = (int)m;
+            GemmDesc g = gemm_desc((int)m, (int)n, (int)k, da, (int)m, db, (int)k, e.d_tmp2.get(), (int)m);
             g.strideA = (long long)(m * k);
-            g.transA = 0;
-            g.B = db;
-            g.ldb = (int)k;
             g.strideB = (long long)(k * n);
-            g.transB = 0;
-            g.C = e.d_tmp2.get();
-            g.ldc = (int)m;
             g.strideC = (long long)(m * n);
-            g.alpha = 1.0;
-            g.beta = 0.0;
             g.batch = (int)batch;
             gemm_launch(g, e.stream());
         }
@@ -468,55 +468,12 @@ t4a_gpu_status t4a_gpu_trsm_f64(const double* a, size_t na, const double* b, siz
         if (bcount == 0) return;
         std::lock_guard<std::mutex> lock(g_dense_mutex);
         Engine& e = dense_engine();
-        hipStream_t st = e.stream();
         e.d_tmp.reserve(2 * acount + 1);
         e.d_tmp2.reserve(2 * bcount + 1);
-        double* dA = e.d_tmp.get();
-        double* dAt = dA + acount;
-        double* dB = e.d_tmp2.get();
-        double* dBt = dB + bcount;
-        upload(e, dA, a, acount);
-        upload(e, dB, b, bcount);
-        // reduce to a left-side solve with an untransposed triangular matrix T:  T Y = R
-        //   left : op(A) X = B           -> T = op(A),   R = B
-        //   right: X op(A) = B           -> T = op(A)^T, R = B^T, X = Y^T
-        const bool need_t = left_side ? (transpose_a != 0) : (transpose_a == 0);
-        const double* T = dA;
-        bool low = lower != 0;
-        if (need_t) {
-            transpose_launch(dA, (int)na, (int)na, (int)na, dAt, (int)na, st);
-            T = dAt;
-            low = !low;
-        }
-        double* R = dB;
-        int rn = (int)bm, rrhs = (int)bn;
-        if (!left_side) {
-            transpose_launch(dB, (int)bm, (int)bn, (int)bm, dBt, (int)bn, st);
-            R = dBt;
-            rn = (int)bn;
-            rrhs = (int)bm;
-        }
-        TrsmProblem tp;
-        tp.T = T;
-        tp.ldt = (int)na;
-        tp.n = (int)na;
-        tp.B = R;
-        tp.ldb = rn;
-        tp.nrhs = rrhs;
-        tp.lower = low ? 1 : 0;
-        tp.unit_diag = unit_diagonal ? 1 : 0;
-        tp.skip_flag = nullptr;
-        DevBuf<TrsmProblem> dprob;
-        dprob.reserve(1);
-        T4A_HIP(hipMemcpyAsync(dprob.get(), &tp, sizeof(tp), hipMemcpyHostToDevice, st));
-        T4A_HIP(hipStreamSynchronize(st));
-        trsm_left_batched_launch(dprob.get(), 1, (int)na, rrhs, st);
-        if (!left_side) {
-            transpose_launch(dBt, (int)bn, (int)bm, (int)bn, dB, (int)bm, st);
-            R = dB;
-        }
-        T4A_HIP(hipGetLastError());
-        download(e, x, R, bcount);
+        upload(e, e.d_tmp.get(), a, acount);
+        upload(e, e.d_tmp2.get(), b, bcount);
+        trsm(e, e.d_tmp.get(), na, e.d_tmp2.get(), bm, bn, left_side != 0, lower != 0, transpose_a != 0, unit_diagonal != 0);
+        download(e, x, e.d_tmp2.get(), bcount);
     });
 }
 
@@ -534,56 +491,11 @@ t4a_gpu_status t4a_gpu_solve_f64(const double* a, size_t n, const double* b, siz
         if (bcount == 0) return;
         std::lock_guard<std::mutex> lock(g_dense_mutex);
         Engine& e = dense_engine();
-        hipStream_t st = e.stream();
         e.d_tmp.reserve(acount + 1);
         e.d_tmp2.reserve(bcount + 1);
         upload(e, e.d_tmp.get(), a, acount);
         upload(e, e.d_tmp2.get(), b, bcount);
-        DevBuf<int> dpiv;
-        dpiv.reserve(n + 1);
-        DevBuf<LuProblem> dlp;
-        dlp.reserve(1);
-        DevBuf<TrsmProblem> dtp;
-        dtp.reserve(2);
-        LuProblem lp;
-        lp.A = e.d_tmp.get();
-        lp.lda = (int)n;
-        lp.n = (int)n;
-        lp.piv = dpiv.get();
-        lp.info = dpiv.get() + n;
-        lp.B = e.d_tmp2.get();
-        lp.ldb = (int)n;
-        lp.nrhs = (int)nrhs;
-        lp.pmax_bits = nullptr;
-        TrsmProblem t[2];
-        t[0].T = lp.A;
-        t[0].ldt = lp.lda;
-        t[0].n = lp.n;
-        t[0].B = lp.B;
-        t[0].ldb = lp.ldb;
-        t[0].nrhs = lp.nrhs;
-        t[0].lower = 1;
-        t[0].unit_diag = 1;
-        t[0].skip_flag = nullptr;
-        t[1] = t[0];
-        t[1].lower = 0;
-        t[1].unit_diag = 0;
-        T4A_HIP(hipMemcpyAsync(dlp.get(), &lp, sizeof(lp), hipMemcpyHostToDevice, st));
-        T4A_HIP(hipMemcpyAsync(dtp.get(), t, sizeof(t), hipMemcpyHostToDevice, st));
-        T4A_HIP(hipStreamSynchronize(st));
-        // (round 5) blocked LU + one fused launch for both triangular solves; outside its size range the two-step path
-        const bool fused = lu_solve_blocked_launch(dlp.get(), 1, (int)n, (int)nrhs, st);
-        const bool forward_done = fused || lu_forward_blocked_launch(dlp.get(), 1, (int)n, (int)nrhs, st);
-        if (!forward_done) lu_batched_launch(dlp.get(), 1, (int)n, st);
-        int info = 0;
-        T4A_HIP(hipMemcpyAsync(&info, lp.info, sizeof(int), hipMemcpyDeviceToHost, st));
-        T4A_HIP(hipStreamSynchronize(st));
-        if (info != 0) throw Error(T4A_GPU_SINGULAR_MATRIX, "solve: matrix is singular");
-        if (!fused) {
-            if (!forward_done) trsm_left_batched_launch(dtp.get(), 1, (int)n, (int)nrhs, st);
-            trsm_left_batched_launch(dtp.get() + 1, 1, (int)n, (int)nrhs, st);
-        }
-        T4A_HIP(hipGetLastError());
+        solve(e, e.d_tmp.get(), n, e.d_tmp2.get(), nrhs);
         download(e, x, e.d_tmp2.get(), bcount);
     });
 }
@@ -780,8 +692,7 @@ t4a_gpu_status t4a_gpu_tci2_sweep1site(t4a_gpu_tci2* h, int32_t forward, double 
 {
     return guarded([&] {
         T4A_REQUIRE_PTR(h);
-        h->impl.sweep1site(forward != 0, rel_tol, abs_tol,
-                           max_bond_dim == 0 ? std::numeric_limits<size_t>::max() : max_bond_dim, update_tensors != 0);
+        h->impl.sweep1site(forward != 0, rel_tol, abs_tol, bond_cap(max_bond_dim), update_tensors != 0);
     });
 }
 
@@ -797,7 +708,7 @@ t4a_gpu_status t4a_gpu_tci2_make_canonical(t4a_gpu_tci2* h, double rel_tol, doub
 {
     return guarded([&] {
         T4A_REQUIRE_PTR(h);
-        h->impl.make_canonical(rel_tol, abs_tol, max_bond_dim == 0 ? std::numeric_limits<size_t>::max() : max_bond_dim);
+        h->impl.make_canonical(rel_tol, abs_tol, bond_cap(max_bond_dim));
     });
 }
 
@@ -1277,75 +1188,18 @@ t4a_gpu_status t4a_gpu_tci2_small_stats(const t4a_gpu_tci2* h, uint64_t* out)
 }
 
 // ------------------------------------------------------------------------------------------------ lazy block-rook LUCI
-extern "C++" {
-static void rook_outputs(Engine& e, const LuciResult& r, size_t m, size_t n, size_t* rank, size_t* rows, size_t* cols,
-                         double* pivot_errors, double* left, double* right)
-{
-    *rank = (size_t)r.rank;
-    for (int i = 0; i < r.rank; ++i) {
-        rows[i] = (size_t)r.row_perm[i];
-        cols[i] = (size_t)r.col_perm[i];
-    }
-    for (size_t i = 0; i < r.pivot_errors.size(); ++i) pivot_errors[i] = r.pivot_errors[i];
-    if (r.rank > 0) {
-        download(e, left, e.left(), m * (size_t)r.rank);
-        download(e, right, e.right(), n * (size_t)r.rank);
-    }
-}
-static RookWork& dense_rook_work()
-{
-    static RookWork w; // guarded by g_dense_mutex like the dense engine itself
-    return w;
-}
-} // extern "C++"
-
 t4a_gpu_status t4a_gpu_luci_blocks_f64(size_t m, size_t n, t4a_gpu_fill_block_fn fill_block, void* ctx,
                                        size_t max_bond_dim, double rel_tol, double abs_tol, int32_t left_orthogonal,
                                        size_t* rank, size_t* rows, size_t* cols, double* pivot_errors, double* left,
                                        double* right)
 {
     return guarded([&] {
-        T4A_REQUIRE_PTR(rank);
-        T4A_REQUIRE_PTR(rows);
-        T4A_REQUIRE_PTR(cols);
-        T4A_REQUIRE_PTR(pivot_errors);
-        const size_t count = checked_mul(m, n, "matrix shape");
-        require_int_dims({m, n}, "matrix shape");
-        if (count) {
-            T4A_REQUIRE_PTR(fill_block);
-            T4A_REQUIRE_PTR(left);
-            T4A_REQUIRE_PTR(right);
-        }
-        if (m > 65535 || n > 65535) throw Error(T4A_GPU_NOT_IMPLEMENTED, "luci: dimensions above 65535 are not supported");
+        luci_prologue(m, n, rank, rows, cols, pivot_errors, fill_block == nullptr, "fill_block is null", left, right, true);
         std::lock_guard<std::mutex> lock(g_dense_mutex);
         Engine& e = dense_engine();
-        hipStream_t st = e.stream();
-        std::vector<size_t> all_rows(m), all_cols(n);
-        for (size_t i = 0; i < m; ++i) all_rows[i] = i;
-        for (size_t j = 0; j < n; ++j) all_cols[j] = j;
-        std::vector<double> hbuf(std::max(m, n));
-        RookSource src;
-        src.M = (int)m;
-        src.N = (int)n;
-        src.column = [&](int c, double* d_out) {
-            const size_t cc = (size_t)c;
-            fill_block(ctx, all_rows.data(), m, &cc, 1, hbuf.data());
-            T4A_HIP(hipMemcpyAsync(d_out, hbuf.data(), m * sizeof(double), hipMemcpyHostToDevice, st));
-            T4A_HIP(hipStreamSynchronize(st));
-        };
-        src.row = [&](int r, double* d_out) {
-            const size_t rr = (size_t)r;
-            fill_block(ctx, &rr, 1, all_cols.data(), n, hbuf.data());
-            T4A_HIP(hipMemcpyAsync(d_out, hbuf.data(), n * sizeof(double), hipMemcpyHostToDevice, st));
-            T4A_HIP(hipStreamSynchronize(st));
-        };
-        RrLUOptions o;
-        o.max_bond_dim = max_bond_dim == 0 ? std::numeric_limits<size_t>::max() : max_bond_dim;
-        o.rel_tol = rel_tol;
-        o.abs_tol = abs_tol;
-        o.left_orthogonal = left_orthogonal != 0;
-        LuciResult r = rook_luci(e, dense_rook_work(), src, o, nullptr, nullptr);
-        rook_outputs(e, r, m, n, rank, rows, cols, pivot_errors, left, right);
+        const RookSource src = rook_source_blocks(e, m, n, fill_block, ctx);
+        LuciResult r = rook_luci(e, dense_rook_work(), src, RrLUOptions::from_abi(max_bond_dim, rel_tol, abs_tol, left_orthogonal != 0), nullptr, nullptr);
+        luci_outputs(e, r, m, n, rank, rows, cols, pivot_errors, left, right);
     });
 }
 
@@ -1354,46 +1208,16 @@ t4a_gpu_status t4a_gpu_luci_rook_f64(const double* a, size_t m, size_t n, size_t
                                      double* pivot_errors, double* left, double* right)
 {
     return guarded([&] {
-        T4A_REQUIRE_PTR(rank);
-        T4A_REQUIRE_PTR(rows);
-        T4A_REQUIRE_PTR(cols);
-        T4A_REQUIRE_PTR(pivot_errors);
-        const size_t count = checked_mul(m, n, "matrix shape");
-        require_int_dims({m, n}, "matrix shape");
-        if (count) {
-            T4A_REQUIRE_PTR(a);
-            T4A_REQUIRE_PTR(left);
-            T4A_REQUIRE_PTR(right);
-        }
-        if (m > 65535 || n > 65535) throw Error(T4A_GPU_NOT_IMPLEMENTED, "luci: dimensions above 65535 are not supported");
+        const size_t count = luci_prologue(m, n, rank, rows, cols, pivot_errors, a == nullptr, "a is null", left, right, true);
         std::lock_guard<std::mutex> lock(g_dense_mutex);
         Engine& e = dense_engine();
-        hipStream_t st = e.stream();
         // the dense source lives on the device: A (m x n) and its transpose (rows contiguous)
         e.d_tmp2.reserve(2 * std::max<size_t>(count, 1));
         double* d_a = e.d_tmp2.get();
-        double* d_at = d_a + count;
         upload(e, d_a, a, count);
-        if (count) transpose_launch(d_a, (int)m, (int)n, (int)m, d_at, (int)n, st);
-        RookSource src;
-        src.M = (int)m;
-        src.N = (int)n;
-        src.column = [&](int c, double* d_out) {
-            T4A_HIP(hipMemcpyAsync(d_out, d_a + (size_t)c * m, m * sizeof(double), hipMemcpyDeviceToDevice, st));
-        };
-        src.row = [&](int r, double* d_out) {
-            T4A_HIP(hipMemcpyAsync(d_out, d_at + (size_t)r * n, n * sizeof(double), hipMemcpyDeviceToDevice, st));
-        };
-        static const bool host_driven = std::getenv("T4A_ROOK_HOST") != nullptr; // (A/B and parity of the two search drivers)
-        if (!host_driven)
-            src.full = [&](double* d_out) { T4A_HIP(hipMemcpyAsync(d_out, d_a, count * sizeof(double), hipMemcpyDeviceToDevice, st)); };
-        RrLUOptions o;
-        o.max_bond_dim = max_bond_dim == 0 ? std::numeric_limits<size_t>::max() : max_bond_dim;
-        o.rel_tol = rel_tol;
-        o.abs_tol = abs_tol;
-        o.left_orthogonal = left_orthogonal != 0;
-        LuciResult r = rook_luci(e, dense_rook_work(), src, o, nullptr, nullptr);
-        rook_outputs(e, r, m, n, rank, rows, cols, pivot_errors, left, right);
+        const RookSource src = rook_source_device(e, d_a, d_a + count, m, n);
+        LuciResult r = rook_luci(e, dense_rook_work(), src, RrLUOptions::from_abi(max_bond_dim, rel_tol, abs_tol, left_orthogonal != 0), nullptr, nullptr);
+        luci_outputs(e, r, m, n, rank, rows, cols, pivot_errors, left, right);
     });
 }
 
@@ -1440,70 +1264,19 @@ t4a_gpu_status t4a_gpu_rsvd_f64(const double* a, size_t m, size_t n, size_t k, s
         T4A_REQUIRE_PTR(s);
         T4A_REQUIRE_PTR(vt);
         const size_t l = std::min(std::min(m, n), k + oversample); // sketch width
-        // Omega (n x l): standard normals by Box-Muller on the library's StdRng stream
-        std::vector<double> omega(n * l);
-        {
-            StdRng rng(seed);
-            for (size_t i = 0; i < omega.size(); i += 2) {
-                const double u1 = ((double)(rng.next_u64() >> 11) + 1.0) * (1.0 / 9007199254740992.0);
-                const double u2 = (double)(rng.next_u64() >> 11) * (1.0 / 9007199254740992.0);
-                const double rad = std::sqrt(-2.0 * std::log(u1));
-                omega[i] = rad * std::cos(6.283185307179586 * u2);
-                if (i + 1 < omega.size()) omega[i + 1] = rad * std::sin(6.283185307179586 * u2);
-            }
-        }
+        const std::vector<double> omega = rsvd_sketch(n, l, seed);
         std::lock_guard<std::mutex> lock(g_dense_mutex);
         Engine& e = dense_engine();
-        hipStream_t st = e.stream();
-        DevBuf<double> dA, dO, dY, dQ, dR, dZ, dB, dUb, dSb, dVt, dU;
-        dA.reserve(count);
-        dO.reserve(n * l);
-        dY.reserve(m * l);
-        dQ.reserve(m * l);
-        dR.reserve(l * std::max(l, n));
-        dZ.reserve(n * l);
-        dB.reserve(l * n);
-        dUb.reserve(l * l);
-        dSb.reserve(l);
-        dVt.reserve(l * n);
-        dU.reserve(m * l);
-        upload(e, dA.get(), a, count);
-        upload(e, dO.get(), omega.data(), omega.size());
-        auto gemm = [&](const double* A_, int lda, bool ta, const double* B_, int ldb, double* C_, int ldc, size_t M_, size_t N_, size_t K_) {
-            GemmDesc g{};
-            g.m = (int)M_;
-            g.n = (int)N_;
-            g.k = (int)K_;
-            g.A = A_;
-            g.lda = lda;
-            g.transA = ta ? 1 : 0;
-            g.B = B_;
-            g.ldb = ldb;
-            g.transB = 0;
-            g.C = C_;
-            g.ldc = ldc;
-            g.alpha = 1.0;
-            g.beta = 0.0;
-            g.batch = 1;
-            gemm_launch(g, st);
-        };
-        gemm(dA.get(), (int)m, false, dO.get(), (int)n, dY.get(), (int)m, m, l, n);      // Y = A Omega
-        e.qr(dY.get(), (int)m, (int)l, dQ.get(), dR.get());                             // Q (m x l)
-        for (size_t it = 0; it < power_iters; ++it) {
-            gemm(dA.get(), (int)m, true, dQ.get(), (int)m, dZ.get(), (int)n, n, l, m);  // Z = A^T Q (n x l)
-            e.qr(dZ.get(), (int)n, (int)l, dO.get(), dR.get());                         // orthonormal basis of Z in dO (n x l)
-            gemm(dA.get(), (int)m, false, dO.get(), (int)n, dY.get(), (int)m, m, l, n); // Y = A Z
-            e.qr(dY.get(), (int)m, (int)l, dQ.get(), dR.get());
-        }
-        gemm(dQ.get(), (int)m, true, dA.get(), (int)m, dB.get(), (int)l, l, n, m);      // B = Q^T A (l x n)
-        e.svd(dB.get(), (int)l, (int)n, dUb.get(), dSb.get(), dVt.get());               // B = Ub S Vt, Ub l x l, Vt l x n
-        gemm(dQ.get(), (int)m, false, dUb.get(), (int)l, dU.get(), (int)m, m, l, l);    // U = Q Ub
-        T4A_HIP(hipGetLastError());
-        download(e, u, dU.get(), m * k);  // the first k columns
-        download(e, s, dSb.get(), k);
+        RsvdBuffers w;
+        w.reserve(m, n, l);
+        upload(e, w.A.get(), a, count);
+        upload(e, w.omega.get(), omega.data(), omega.size());
+        rsvd(e, w, m, n, l, power_iters);
+        download(e, u, w.U.get(), m * k);  // the first k columns
+        download(e, s, w.S.get(), k);
         // the first k rows of Vt (l x n, column-major: strided) -> k x n
         std::vector<double> hv(l * n);
-        download(e, hv.data(), dVt.get(), l * n);
+        download(e, hv.data(), w.Vt.get(), l * n);
         for (size_t j = 0; j < n; ++j)
             for (size_t i = 0; i < k; ++i) vt[i + k * j] = hv[i + l * j];
     });
@@ -1549,25 +1322,10 @@ t4a_gpu_status t4a_gpu_full_piv_lu_f64(const double* a, size_t n, double* p, dou
         Engine& e = dense_engine();
         double* d_a = e.pi(count);
         upload(e, d_a, a, count);
-        RrLUOptions o;
-        o.rel_tol = 0.0;
-        o.abs_tol = 0.0;
-        o.left_orthogonal = true;
-        LuciResult r = e.luci(d_a, (int)n, (int)n, o, false, true);
-        // square factors: L = [lower trapezoid of the first rank columns | identity columns], U = [first rank rows ; 0]
-        e.d_tmp.reserve(2 * count);
-        double* d_l = e.d_tmp.get();
-        double* d_u = d_l + count;
-        hipStream_t st = e.stream();
-        set_identity_launch(d_l, (int)n, (int)n, (int)n, st);
-        fill_launch(d_u, count, 0.0, st);
-        if (r.rank > 0) {
-            tri_extract_launch(e.lu_buf(), (int)n, (int)n, r.rank, 1, 1, d_l, (int)n, st);
-            tri_extract_launch(e.lu_buf(), (int)n, r.rank, (int)n, 0, 0, d_u, (int)n, st);
-        }
-        T4A_HIP(hipGetLastError());
+        LuciResult r = e.luci(d_a, (int)n, (int)n, RrLUOptions::from_abi(0, 0.0, 0.0, true), false, true);
+        const double* d_l = full_piv_lu_factors(e, r, n);
         download(e, l, d_l, count);
-        download(e, u, d_u, count);
+        download(e, u, d_l + count, count);
         std::memset(p, 0, count * sizeof(double));
         std::memset(q, 0, count * sizeof(double));
         for (size_t k = 0; k < n; ++k) {
@@ -2106,12 +1864,7 @@ t4a_gpu_status t4a_gpu_treetci_update_edge(t4a_gpu_treetci* h, size_t u, size_t 
 {
     return guarded([&] {
         T4A_REQUIRE_PTR(h);
-        RrLUOptions o;
-        o.max_bond_dim = max_bond_dim == 0 ? std::numeric_limits<size_t>::max() : max_bond_dim;
-        o.rel_tol = rel_tol;
-        o.abs_tol = abs_tol;
-        o.left_orthogonal = true;
-        const EdgeSelection sel = h->impl.update_edge(TreeEdge(u, v), o);
+        const EdgeSelection sel = h->impl.update_edge(TreeEdge(u, v), RrLUOptions::from_abi(max_bond_dim, rel_tol, abs_tol, true));
         if (rank) *rank = sel.rank;
         for (size_t k = 0; k < sel.rank; ++k) {
             if (rows) rows[k] = sel.row_indices[k];

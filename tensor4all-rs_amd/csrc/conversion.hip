@@ -67,11 +67,7 @@ void sweep1site_get_indices(Engine& eng, std::vector<DevCore>& tt, bool forward,
         // group_indices(current, forward, false): forward -> left matrix, backward -> right matrix
         d_m1.reserve(std::max<size_t>(cur.size(), 1));
         core_reshape_launch(cur.buf.get(), cl, cs, cr, forward ? 0 : 2, d_m1.get(), st);
-        RrLUOptions o;
-        o.max_bond_dim = opt.max_bond_dim == 0 ? std::numeric_limits<size_t>::max() : opt.max_bond_dim;
-        o.rel_tol = opt.tolerance;
-        o.abs_tol = 0.0;
-        o.left_orthogonal = forward;
+        const RrLUOptions o = RrLUOptions::from_abi(opt.max_bond_dim, opt.tolerance, 0.0, forward);
         const int M = forward ? cl * cs : cl, N = forward ? cr : cs * cr;
         LuciResult f = eng.luci(d_m1.get(), M, N, o, true, false);
         const int r = f.rank;
@@ -94,25 +90,7 @@ void sweep1site_get_indices(Engine& eng, std::vector<DevCore>& tt, bool forward,
             d_m1.reserve(std::max<size_t>(nxt.size(), 1));
             core_reshape_launch(nxt.buf.get(), nl, ns, nr, 2, d_m1.get(), st);
             d_m2.reserve(std::max<size_t>((size_t)r * ns * nr, 1));
-            GemmDesc g;
-            g.m = r;
-            g.n = ns * nr;
-            g.k = cr;
-            g.A = eng.right();
-            g.lda = r;
-            g.strideA = 0;
-            g.transA = 0;
-            g.B = d_m1.get();
-            g.ldb = nl;
-            g.strideB = 0;
-            g.transB = 0;
-            g.C = d_m2.get();
-            g.ldc = r;
-            g.strideC = 0;
-            g.alpha = 1.0;
-            g.beta = 0.0;
-            g.batch = 1;
-            gemm_launch(g, st);
+            gemm_launch(gemm_desc(r, ns * nr, cr, eng.right(), r, d_m1.get(), nl, d_m2.get(), r), st);
             DevCore nc, nn;
             nc.l = cl;
             nc.s = cs;
@@ -142,25 +120,7 @@ void sweep1site_get_indices(Engine& eng, std::vector<DevCore>& tt, bool forward,
             d_m1.reserve(std::max<size_t>(nxt.size(), 1));
             core_reshape_launch(nxt.buf.get(), nl, ns, nr, 0, d_m1.get(), st);
             d_m2.reserve(std::max<size_t>((size_t)nl * ns * r, 1));
-            GemmDesc g;
-            g.m = nl * ns;
-            g.n = r;
-            g.k = cl;
-            g.A = d_m1.get();
-            g.lda = nl * ns;
-            g.strideA = 0;
-            g.transA = 0;
-            g.B = eng.left();
-            g.ldb = cl;
-            g.strideB = 0;
-            g.transB = 0;
-            g.C = d_m2.get();
-            g.ldc = nl * ns;
-            g.strideC = 0;
-            g.alpha = 1.0;
-            g.beta = 0.0;
-            g.batch = 1;
-            gemm_launch(g, st);
+            gemm_launch(gemm_desc(nl * ns, r, cl, d_m1.get(), nl * ns, eng.left(), cl, d_m2.get(), nl * ns), st);
             DevCore nc, nn;
             nc.l = r;
             nc.s = cs;

@@ -985,25 +985,7 @@ void Engine::build_factors_from(const double* lu, const int* d_rowperm_ptr_, con
         // U needs its own buffer: Wl is still being read by the scatter only until it completes (in-order stream)
         tri_extract_launch(lu, M, rk, N, 0, 0, Ue, rk, stream_);
         double* Rp = d_w2_.get() + (size_t)rk * rk; // rk x N
-        GemmDesc g;
-        g.m = rk;
-        g.n = N;
-        g.k = rk;
-        g.A = L11;
-        g.lda = rk;
-        g.strideA = 0;
-        g.transA = 0;
-        g.B = Ue;
-        g.ldb = rk;
-        g.strideB = 0;
-        g.transB = 0;
-        g.C = Rp;
-        g.ldc = rk;
-        g.strideC = 0;
-        g.alpha = 1.0;
-        g.beta = 0.0;
-        g.batch = 1;
-        gemm_launch(g, stream_);
+        gemm_launch(gemm_desc(rk, N, rk, L11, rk, Ue, rk, Rp, rk), stream_);
         scatter_cols_launch(Rp, rk, rk, d_colperm_ptr_, N, d_right_.get(), rk, stream_);
     } else {
         // left = P_row^T (L U11)   (rrlu_colmatrix, matrix_luci.rs:176-189)
@@ -1012,25 +994,7 @@ void Engine::build_factors_from(const double* lu, const int* d_rowperm_ptr_, con
         double* Lp = d_w2_.get() + (size_t)rk * rk;  // M x rk product, permuted order
         tri_extract_launch(lu, M, M, rk, 1, 0, Le, M, stream_);
         tri_extract_launch(lu, M, rk, rk, 0, 1, U11, rk, stream_);
-        GemmDesc g;
-        g.m = M;
-        g.n = rk;
-        g.k = rk;
-        g.A = Le;
-        g.lda = M;
-        g.strideA = 0;
-        g.transA = 0;
-        g.B = U11;
-        g.ldb = rk;
-        g.strideB = 0;
-        g.transB = 0;
-        g.C = Lp;
-        g.ldc = M;
-        g.strideC = 0;
-        g.alpha = 1.0;
-        g.beta = 0.0;
-        g.batch = 1;
-        gemm_launch(g, stream_);
+        gemm_launch(gemm_desc(M, rk, rk, Le, M, U11, rk, Lp, M), stream_);
         scatter_rows_launch(Lp, M, d_rowperm_ptr_, M, rk, d_left_.get(), M, stream_);
         // right = [I_r , U11^{-1} U12] P_col^T   (rrlu_pivot_solve_times_rows, matrix_luci.rs:231-254)
         double* Wr = d_w1_.get(); // rk x N (ordered after the gemm that read Le on the same stream)
@@ -1157,21 +1121,8 @@ void Engine::svd_in_range(const double* d_a, int M, int N, double* d_u, double* 
     svd_plain(d_pl_.get(), n, n, d_pul_.get(), d_s, d_pvl_.get());       // L = U_L S Vt_L
     // A' = Q L^T = (Q Vt_L^T) S U_L^T
     auto gemm_nt = [&](const double* A_, int lda, const double* B_, int ldb, double* C_, int ldc, int M_, int N_, int K_) {
-        GemmDesc g{};
-        g.m = M_;
-        g.n = N_;
-        g.k = K_;
-        g.A = A_;
-        g.lda = lda;
-        g.transA = 0;
-        g.B = B_;
-        g.ldb = ldb;
+        GemmDesc g = gemm_desc(M_, N_, K_, A_, lda, B_, ldb, C_, ldc);
         g.transB = 1;
-        g.C = C_;
-        g.ldc = ldc;
-        g.alpha = 1.0;
-        g.beta = 0.0;
-        g.batch = 1;
         gemm_launch(g, stream_);
     };
     if (!flip) {

@@ -15,11 +15,23 @@
 
 namespace t4a {
 
+// a bond dimension limit as the ABI and the option structs carry it: 0 == unlimited
+inline size_t bond_cap(size_t max_bond_dim) { return max_bond_dim == 0 ? std::numeric_limits<size_t>::max() : max_bond_dim; }
+
 struct RrLUOptions { // core/src/matrixlu.rs:688-708
     size_t max_bond_dim = std::numeric_limits<size_t>::max();
     double rel_tol = 1e-14;
     double abs_tol = 0.0;
     bool left_orthogonal = true;
+    static RrLUOptions from_abi(size_t max_bond_dim, double rel_tol, double abs_tol, bool left_orthogonal)
+    {
+        RrLUOptions o;
+        o.max_bond_dim = bond_cap(max_bond_dim);
+        o.rel_tol = rel_tol;
+        o.abs_tol = abs_tol;
+        o.left_orthogonal = left_orthogonal;
+        return o;
+    }
 };
 
 struct LuciResult {

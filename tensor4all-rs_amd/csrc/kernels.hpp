@@ -409,6 +409,24 @@ struct GemmDesc {
     double* partial = nullptr;
 };
 void gemm_launch(const GemmDesc& d, hipStream_t stream);
+// One plain product C = A B: no transposes, zero strides, alpha = 1, beta = 0, batch = 1.  Callers assign only what differs.
+inline GemmDesc gemm_desc(int m, int n, int k, const double* A, int lda, const double* B, int ldb, double* C, int ldc)
+{
+    GemmDesc g{};
+    g.m = m;
+    g.n = n;
+    g.k = k;
+    g.A = A;
+    g.lda = lda;
+    g.B = B;
+    g.ldb = ldb;
+    g.C = C;
+    g.ldc = ldc;
+    g.alpha = 1.0;
+    g.beta = 0.0;
+    g.batch = 1;
+    return g;
+}
 
 // LUCI factors of a small factorisation (rank <= 16, M, N <= 1024) in one launch: lu = factored M x N matrix in permuted coordinates (ld M),
 // left: M x rk (ld M), right: rk x N (ld rk), both in original row / column order.  Returns false when the shape is not taken.
@@ -455,6 +473,20 @@ struct LuProblem {
     const unsigned long long* pmax_bits; // optional: bits of max|a_ij|; below EPS the problem is flagged info = -1
 };
 void lu_batched_launch(const LuProblem* d_problems, int n_problems, int max_n, hipStream_t stream);
+// One of the two solves on the factored matrix of `lp`, in place in its right-hand sides: unit-lower (L Y = P B) or upper (U X = Y).
+inline TrsmProblem lu_trsm_problem(const LuProblem& lp, bool lower, const int* skip_flag = nullptr)
+{
+    TrsmProblem t{};
+    t.T = lp.A;
+    t.ldt = lp.lda;
+    t.n = lp.n;
+    t.B = lp.B;
+    t.ldb = lp.ldb;
+    t.nrhs = lp.nrhs;
+    t.lower = t.unit_diag = lower ? 1 : 0;
+    t.skip_flag = skip_flag;
+    return t;
+}
 // Blocked variant that also applies the forward substitution to the right-hand sides: A = P^T L U, B <- L^{-1} P B
 // (bitwise the result of lu_batched_launch followed by the unit-lower triangular solve).  Returns false when
 // max_n > 1024 (nothing was launched; use the two-step path).

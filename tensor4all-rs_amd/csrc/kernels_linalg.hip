@@ -1314,26 +1314,15 @@ void qr_factor_launch(double* A, int m, int n, double* diag, double* tau, double
         if (n2 <= 0) continue;
         const double* Vp = Vall + j0 + (size_t)m * j0; // rows j0 .., columns j0 .. j0 + w - 1 (zero above)
         double* A2 = A + j0 + (size_t)m * (j0 + w);
-        GemmDesc g;
-        g.batch = 1;
-        g.strideA = g.strideB = g.strideC = 0;
-        // W = Vp^T A2   (w x n2)
-        g.m = w; g.n = n2; g.k = mp;
-        g.A = Vp; g.lda = m; g.transA = 1;
-        g.B = A2; g.ldb = m; g.transB = 0;
-        g.C = W; g.ldc = QR_NB; g.alpha = 1.0; g.beta = 0.0;
+        GemmDesc g = gemm_desc(w, n2, mp, Vp, m, A2, m, W, QR_NB); // W = Vp^T A2   (w x n2)
+        g.transA = 1;
         gemm_launch(g, stream);
-        // W2 = T^T W
-        g.m = w; g.n = n2; g.k = w;
-        g.A = Tp; g.lda = QR_NB; g.transA = 1;
-        g.B = W; g.ldb = QR_NB; g.transB = 0;
-        g.C = W2; g.ldc = QR_NB; g.alpha = 1.0; g.beta = 0.0;
+        g = gemm_desc(w, n2, w, Tp, QR_NB, W, QR_NB, W2, QR_NB);   // W2 = T^T W
+        g.transA = 1;
         gemm_launch(g, stream);
-        // A2 -= Vp W2
-        g.m = mp; g.n = n2; g.k = w;
-        g.A = Vp; g.lda = m; g.transA = 0;
-        g.B = W2; g.ldb = QR_NB; g.transB = 0;
-        g.C = A2; g.ldc = m; g.alpha = -1.0; g.beta = 1.0;
+        g = gemm_desc(mp, n2, w, Vp, m, W2, QR_NB, A2, m);         // A2 -= Vp W2
+        g.alpha = -1.0;
+        g.beta = 1.0;
         gemm_launch(g, stream);
     }
 }
@@ -1353,23 +1342,13 @@ void qr_form_launch(const double* A, int m, int n, const double* diag, const dou
         const double* Vp = Vall + j0 + (size_t)m * j0;
         const double* Tp = Tall + (size_t)pi * QR_NB * QR_NB;
         double* Qs = Q + j0 + (size_t)m * j0;
-        GemmDesc g;
-        g.batch = 1;
-        g.strideA = g.strideB = g.strideC = 0;
-        g.m = w; g.n = nq; g.k = mp;
-        g.A = Vp; g.lda = m; g.transA = 1;
-        g.B = Qs; g.ldb = m; g.transB = 0;
-        g.C = W; g.ldc = QR_NB; g.alpha = 1.0; g.beta = 0.0;
+        GemmDesc g = gemm_desc(w, nq, mp, Vp, m, Qs, m, W, QR_NB);
+        g.transA = 1;
         gemm_launch(g, stream);
-        g.m = w; g.n = nq; g.k = w;
-        g.A = Tp; g.lda = QR_NB; g.transA = 0;
-        g.B = W; g.ldb = QR_NB; g.transB = 0;
-        g.C = W2; g.ldc = QR_NB; g.alpha = 1.0; g.beta = 0.0;
-        gemm_launch(g, stream);
-        g.m = mp; g.n = nq; g.k = w;
-        g.A = Vp; g.lda = m; g.transA = 0;
-        g.B = W2; g.ldb = QR_NB; g.transB = 0;
-        g.C = Qs; g.ldc = m; g.alpha = -1.0; g.beta = 1.0;
+        gemm_launch(gemm_desc(w, nq, w, Tp, QR_NB, W, QR_NB, W2, QR_NB), stream);
+        g = gemm_desc(mp, nq, w, Vp, m, W2, QR_NB, Qs, m);
+        g.alpha = -1.0;
+        g.beta = 1.0;
         gemm_launch(g, stream);
     }
 }

@@ -35,24 +35,6 @@ void check_count(size_t a, size_t b, size_t c, size_t d, const std::string& what
     }
 }
 
-GemmDesc gemm_desc(int m, int n, int k, const double* A, int lda, const double* B, int ldb, double* C, int ldc)
-{
-    GemmDesc g{};
-    g.m = m;
-    g.n = n;
-    g.k = k;
-    g.A = A;
-    g.lda = lda;
-    g.B = B;
-    g.ldb = ldb;
-    g.C = C;
-    g.ldc = ldc;
-    g.alpha = 1.0;
-    g.beta = 0.0;
-    g.batch = 1;
-    return g;
-}
-
 // One contraction: every launch goes to the stream of `eng` (the engine of the left operand).
 struct Contractor {
     Engine& eng;

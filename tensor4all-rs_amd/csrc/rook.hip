@@ -554,29 +554,13 @@ LuciResult rook_luci(Engine& eng, RookWork& w, const RookSource& src, const RrLU
         lp.ldb = k;
         lp.nrhs = N;
         lp.pmax_bits = nullptr;
-        for (int q = 0; q < 4; ++q) {
-            tp[q].T = w.P.get();
-            tp[q].ldt = k;
-            tp[q].n = k;
-            tp[q].ldb = k;
-            tp[q].skip_flag = nullptr;
+        tp[0] = lu_trsm_problem(lp, true);  // L X' = P_swap Rw
+        tp[1] = lu_trsm_problem(lp, false); // U X = X'
+        for (int q = 2; q < 4; ++q) {       // single right-hand side (column visits)
+            tp[q] = tp[q - 2];
+            tp[q].B = d_b;
+            tp[q].nrhs = 1;
         }
-        tp[0].B = w.X.get(); // L X' = P_swap Rw
-        tp[0].nrhs = N;
-        tp[0].lower = 1;
-        tp[0].unit_diag = 1;
-        tp[1].B = w.X.get(); // U X = X'
-        tp[1].nrhs = N;
-        tp[1].lower = 0;
-        tp[1].unit_diag = 0;
-        tp[2].B = d_b;       // single right-hand side (column visits)
-        tp[2].nrhs = 1;
-        tp[2].lower = 1;
-        tp[2].unit_diag = 1;
-        tp[3].B = d_b;
-        tp[3].nrhs = 1;
-        tp[3].lower = 0;
-        tp[3].unit_diag = 0;
         T4A_HIP(hipMemcpyAsync(w.lup.get(), &lp, sizeof(lp), hipMemcpyHostToDevice, st));
         T4A_HIP(hipMemcpyAsync(w.trp.get(), tp, sizeof(tp), hipMemcpyHostToDevice, st));
         T4A_HIP(hipStreamSynchronize(st)); // lp / tp are pageable

@@ -1247,20 +1247,8 @@ void Tci2::fill_site_tensors_impl(bool async)
         lp.pmax_bits = d_max + j.b;
         piv_off += j.np;
         lups.push_back(lp);
-        TrsmProblem t;
-        t.T = lp.A;
-        t.ldt = lp.lda;
-        t.n = lp.n;
-        t.B = lp.B;
-        t.ldb = lp.ldb;
-        t.nrhs = lp.nrhs;
-        t.lower = 1;
-        t.unit_diag = 1;
-        t.skip_flag = lp.info;
-        trl.push_back(t);
-        t.lower = 0;
-        t.unit_diag = 0;
-        tru.push_back(t);
+        trl.push_back(lu_trsm_problem(lp, true, lp.info));
+        tru.push_back(lu_trsm_problem(lp, false, lp.info));
         fill_solved_sites_.push_back(j.b);
         max_n = std::max(max_n, lp.n);
         max_nrhs = std::max(max_nrhs, lp.nrhs);

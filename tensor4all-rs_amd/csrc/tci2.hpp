@@ -49,10 +49,7 @@ struct TCI2Options { // tensorci2.rs:73-170
     double tol_margin_global_search = 10.0;
     bool has_seed = false;
     uint64_t seed = 0;
-    size_t max_bond_dim_or_max() const
-    {
-        return max_bond_dim == 0 ? std::numeric_limits<size_t>::max() : max_bond_dim;
-    }
+    size_t max_bond_dim_or_max() const { return bond_cap(max_bond_dim); }
     void validate() const;
 };
 

@@ -157,25 +157,7 @@ void tensor_contract_pair(Engine& e, const TensorView& a, const TensorView& b, c
     e.d_tmp2.reserve(std::max<size_t>(b.size(), 1));
     tensor_permute(e, a, p.perm_a, e.d_tmp.get());
     tensor_permute(e, b, p.perm_b, e.d_tmp2.get());
-    GemmDesc g{};
-    g.m = (int)p.M;
-    g.n = (int)p.N;
-    g.k = (int)p.K;
-    g.A = e.d_tmp.get();
-    g.lda = (int)p.M;
-    g.strideA = 0;
-    g.transA = 0;
-    g.B = e.d_tmp2.get();
-    g.ldb = (int)p.K;
-    g.strideB = 0;
-    g.transB = 0;
-    g.C = d_out;
-    g.ldc = (int)p.M;
-    g.strideC = 0;
-    g.alpha = 1.0;
-    g.beta = 0.0;
-    g.batch = 1;
-    gemm_launch(g, e.stream());
+    gemm_launch(gemm_desc((int)p.M, (int)p.N, (int)p.K, e.d_tmp.get(), (int)p.M, e.d_tmp2.get(), (int)p.K, d_out, (int)p.M), e.stream());
     T4A_HIP(hipGetLastError());
 }
 
@@ -344,23 +326,10 @@ OwnedTensor tensor_contract_network(Engine& e, const std::vector<TensorView>& ts
             e.d_tmp2.reserve(std::max<size_t>(B.size(), 1));
             tensor_permute(e, A, perm_a, e.d_tmp.get());
             tensor_permute(e, B, perm_b, e.d_tmp2.get());
-            GemmDesc g{};
-            g.m = (int)M;
-            g.n = (int)N;
-            g.k = (int)K;
-            g.A = e.d_tmp.get();
-            g.lda = (int)M;
+            GemmDesc g = gemm_desc((int)M, (int)N, (int)K, e.d_tmp.get(), (int)M, e.d_tmp2.get(), (int)K, res.own->get(), (int)M);
             g.strideA = (long long)(M * K);
-            g.transA = 0;
-            g.B = e.d_tmp2.get();
-            g.ldb = (int)K;
             g.strideB = (long long)(K * N);
-            g.transB = 0;
-            g.C = res.own->get();
-            g.ldc = (int)M;
             g.strideC = (long long)(M * N);
-            g.alpha = 1.0;
-            g.beta = 0.0;
             g.batch = (int)Bt;
             gemm_launch(g, st);
             T4A_HIP(hipGetLastError());

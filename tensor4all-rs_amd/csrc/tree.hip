@@ -594,11 +594,7 @@ void TreeTci::optimize(const TreeTciOptions& options) // :95-220 (DefaultPropose
     for (size_t iter = 0; iter < options.max_iter; ++iter) {
         for (size_t pass = 0; pass < INNER_EDGE_PASSES; ++pass) {
             const double scale = options.normalize_error && max_sample_value > 0.0 ? max_sample_value : 1.0;
-            RrLUOptions ko;
-            ko.rel_tol = 1e-14;
-            ko.abs_tol = options.tolerance * scale;
-            ko.max_bond_dim = options.max_bond_dim == 0 ? std::numeric_limits<size_t>::max() : options.max_bond_dim;
-            ko.left_orthogonal = true;
+            const RrLUOptions ko = RrLUOptions::from_abi(options.max_bond_dim, 1e-14, options.tolerance * scale, true);
             ijset_history.push_back(ijset);
             flush_pivot_errors();
             for (const TreeEdge& e : edges) update_edge(e, ko);

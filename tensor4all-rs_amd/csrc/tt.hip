@@ -259,11 +259,7 @@ size_t TensorTrain::factorize(const double* d_mat, int M, int N, CompressionMeth
         reltol = 1e-14;
         abstol = 0.0;
     }
-    RrLUOptions o;
-    o.max_bond_dim = max_bond_dim == 0 ? std::numeric_limits<size_t>::max() : max_bond_dim;
-    o.rel_tol = reltol;
-    o.abs_tol = abstol;
-    o.left_orthogonal = left_orthogonal;
+    const RrLUOptions o = RrLUOptions::from_abi(max_bond_dim, reltol, abstol, left_orthogonal);
     switch (method) {
     case CompressionMethod::LU: {
         LuciResult r = eng.luci(d_mat, M, N, o, false, true);
@@ -304,35 +300,11 @@ size_t TensorTrain::factorize(const double* d_mat, int M, int N, CompressionMeth
         for (size_t i = 0; i < rank; ++i) hd[i + rank * i] = s[i];
         T4A_HIP(hipMemcpyAsync(dg, hd.data(), sizeof(double) * rank * rank, hipMemcpyHostToDevice, eng.stream()));
         eng.sync();
-        GemmDesc g;
-        g.strideA = g.strideB = g.strideC = 0;
-        g.transA = g.transB = 0;
-        g.alpha = 1.0;
-        g.beta = 0.0;
-        g.batch = 1;
         if (left_orthogonal) {
             gather_launch(d_svdu_.get(), M, nullptr, M, nullptr, (int)rank, left, M, eng.stream());
-            g.m = (int)rank;
-            g.n = N;
-            g.k = (int)rank;
-            g.A = dg;
-            g.lda = (int)rank;
-            g.B = d_svdvt_.get();
-            g.ldb = k;
-            g.C = right;
-            g.ldc = (int)rank;
-            gemm_launch(g, eng.stream());
+            gemm_launch(gemm_desc((int)rank, N, (int)rank, dg, (int)rank, d_svdvt_.get(), k, right, (int)rank), eng.stream());
         } else {
-            g.m = M;
-            g.n = (int)rank;
-            g.k = (int)rank;
-            g.A = d_svdu_.get();
-            g.lda = M;
-            g.B = dg;
-            g.ldb = (int)rank;
-            g.C = left;
-            g.ldc = M;
-            gemm_launch(g, eng.stream());
+            gemm_launch(gemm_desc(M, (int)rank, (int)rank, d_svdu_.get(), M, dg, (int)rank, left, M), eng.stream());
             gather_launch(d_svdvt_.get(), k, nullptr, (int)rank, nullptr, N, right, (int)rank, eng.stream());
         }
         T4A_HIP(hipGetLastError());
@@ -348,25 +320,7 @@ void TensorTrain::compress(const CompressionOptions& opt) // compression.rs:375-
     if (n <= 1) return;
     hipStream_t st = eng.stream();
     auto gemm = [&](const double* A, int m, int k, const double* B, int nn, double* C) {
-        GemmDesc g;
-        g.m = m;
-        g.n = nn;
-        g.k = k;
-        g.A = A;
-        g.lda = m;
-        g.strideA = 0;
-        g.transA = 0;
-        g.B = B;
-        g.ldb = k;
-        g.strideB = 0;
-        g.transB = 0;
-        g.C = C;
-        g.ldc = m;
-        g.strideC = 0;
-        g.alpha = 1.0;
-        g.beta = 0.0;
-        g.batch = 1;
-        gemm_launch(g, st);
+        gemm_launch(gemm_desc(m, nn, k, A, m, B, k, C, m), st);
     };
     // left-to-right: orthogonalise without truncation
     for (size_t ell = 0; ell + 1 < n; ++ell) {
@@ -598,37 +552,11 @@ double TensorTrain::inner_product(TensorTrain& other)
         // tmp (eb x S R_a) = env^T * X,  then env' (R_a x R_b) = tmp^T (R_a x eb S) * Y (eb S x R_b)
         tmp.reserve(std::max<size_t>(eb * x.s * x.r, 1));
         nxt.reserve(std::max<size_t>(x.r * y.r, 1));
-        GemmDesc g{};
-        g.m = (int)eb;
-        g.n = (int)(x.s * x.r);
-        g.k = (int)ea;
-        g.A = env.get();
-        g.lda = (int)ea;
+        GemmDesc g = gemm_desc((int)eb, (int)(x.s * x.r), (int)ea, env.get(), (int)ea, x.buf.get(), (int)x.l, tmp.get(), (int)eb);
         g.transA = 1;
-        g.B = x.buf.get();
-        g.ldb = (int)x.l;
-        g.transB = 0;
-        g.C = tmp.get();
-        g.ldc = (int)eb;
-        g.alpha = 1.0;
-        g.beta = 0.0;
-        g.batch = 1;
         gemm_launch(g, st);
-        GemmDesc h{};
-        h.m = (int)x.r;
-        h.n = (int)y.r;
-        h.k = (int)(eb * x.s);
-        h.A = tmp.get();
-        h.lda = (int)(eb * x.s);
+        GemmDesc h = gemm_desc((int)x.r, (int)y.r, (int)(eb * x.s), tmp.get(), (int)(eb * x.s), y.buf.get(), (int)(y.l * y.s), nxt.get(), (int)x.r);
         h.transA = 1;
-        h.B = y.buf.get();
-        h.ldb = (int)(y.l * y.s);
-        h.transB = 0;
-        h.C = nxt.get();
-        h.ldc = (int)x.r;
-        h.alpha = 1.0;
-        h.beta = 0.0;
-        h.batch = 1;
         gemm_launch(h, st);
         eng.sync();
         std::swap(env, nxt);

@@ -172,6 +172,28 @@ def test_gemm_batched(t4a):
         assert np.array_equal(c[q].T, a[q].T @ b[q].T)
 
 
+def test_gemm_empty_dimensions(t4a):
+    """An empty inner dimension is an empty sum: C is overwritten with zeros (mat_mul hands in a zero-filled C, so only a direct
+    call with a non-zero C sees that branch).  An empty C (m == 0 or n == 0) is left alone."""
+    from ctypes import c_size_t, c_void_p
+    lib = t4a._lib
+
+    def call(batch, m, k, n, c):
+        a = np.full(max(batch * m * k, 1), 2.0)
+        b = np.full(max(batch * k * n, 1), 3.0)
+        return lib.t4a_gpu_gemm_batched_f64(c_size_t(batch), c_size_t(m), c_size_t(k), c_size_t(n), a.ctypes.data_as(c_void_p),
+                                            b.ctypes.data_as(c_void_p), c.ctypes.data_as(c_void_p))
+
+    for batch, m, k, n in ((1, 3, 0, 4), (2, 5, 0, 1)):
+        c = np.ones(batch * m * n)
+        assert call(batch, m, k, n, c) == 0
+        assert np.array_equal(c, np.zeros(batch * m * n))
+    for batch, m, k, n in ((1, 0, 3, 4), (1, 3, 2, 0)):
+        c = np.ones(8)
+        assert call(batch, m, k, n, c) == 0
+        assert np.array_equal(c, np.ones(8))
+
+
 @pytest.mark.parametrize("left_side", [True, False])
 @pytest.mark.parametrize("lower", [True, False])
 @pytest.mark.parametrize("trans", [True, False])
