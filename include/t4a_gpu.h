@@ -769,7 +769,7 @@ t4a_gpu_status t4a_gpu_contraction_evaluate_right(t4a_gpu_contraction* h, size_t
 t4a_gpu_status t4a_gpu_contraction_evaluate_many(t4a_gpu_contraction* h, const size_t* idx, size_t n_pts, size_t split, double* out,
                                                  size_t* used_split);
 t4a_gpu_status t4a_gpu_contraction_clear_cache(t4a_gpu_contraction* h);
-/* Points evaluated so far through _evaluate, _evaluate_many and _batch_eval (this project's: the function evaluations a cross
+/* Points evaluated so far through _evaluate, _evaluate_many, _evaluate_matrix and _batch_eval (this project's: the function evaluations a cross
  * interpolation spent on the handle). */
 t4a_gpu_status t4a_gpu_contraction_n_evaluated(const t4a_gpu_contraction* h, size_t* out);
 /* A t4a_gpu_batch_eval_fn whose ctx is a t4a_gpu_contraction*: idx carries the fused site index f = i + S1_a * j of the product (the
@@ -786,6 +786,44 @@ int64_t t4a_gpu_contraction_batch_eval(void* ctx, const uint32_t* idx, size_t n_
  * error estimate]. */
 t4a_gpu_status t4a_gpu_mpo_contract_tci(const t4a_gpu_mpo* a, const t4a_gpu_mpo* b, const t4a_gpu_tci2_options* options,
                                         const size_t* initial_pivots, size_t n_pivots, t4a_gpu_mpo** out_mpo, double* info /* [4] */);
+
+/* ---- candidate matrices of A·B filled on the device (this project's) ----
+ * The four entries below answer INVALID_ARGUMENT, not NULL_POINTER, for a NULL handle or buffer ("... is null"), before a device is
+ * touched.
+ *
+ * _evaluate_matrix: out[r + n_rows * c] = (A·B)(rows[r] + cols[c]) in host memory.  rows: 2 cut x n_rows column-major, the [i, j]
+ * pairs of sites 0 .. cut-1 per row half; cols: 2 (len - cut) x n_cols, the pairs of sites cut .. len-1.  cut == 0 / cut == len:
+ * that side's environment is [[1]] and its buffer is not read.  One environment launch per side (one workgroup per half, as in
+ * _evaluate_many, with its LDS / global-scratch limit), one pairing launch over la * lb at the cut on the f64 matrix cores, one
+ * download.  No unique map: the halves of a candidate matrix are distinct, equal ones would be walked twice.  The bits of an entry depend on its row half and its column half
+ * only — not on n_rows, n_cols, the position of the entry or the other halves of the request: la * lb is summed in chunks of four in
+ * ascending order for every entry alike.  INVALID_ARGUMENT: the empty contraction ("MPO is empty"), cut > len ("Invalid split
+ * position"), an index out of range ("Index out of bounds: ..."), more than INT_MAX rows or 65535 * 64 columns.  n_rows == 0 or
+ * n_cols == 0: nothing is written.  Counts n_rows * n_cols evaluations in _n_evaluated. */
+t4a_gpu_status t4a_gpu_contraction_evaluate_matrix(t4a_gpu_contraction* h, size_t cut, const size_t* rows, size_t n_rows,
+                                                   const size_t* cols, size_t n_cols, double* out);
+/* The contraction as the DEVICE MATRIX SOURCE of a TensorCI2 over the fused site index f = i + S1_a * j: every candidate matrix the
+ * driver builds whole (the two-site matrix of a bond under full pivot search, the matrices of fill_site_tensors, the last tensor of a
+ * one-site sweep) is filled in device memory as _evaluate_matrix does, ordered against the handle's stream by events — no index
+ * buffer, no unique map, no transfer of values.  t4a_gpu_contraction_batch_eval over the same contraction is installed as the host
+ * callback beside it and serves everything that is not a whole matrix: global pivot search, pivot values, error estimates, a
+ * candidate matrix sharded by t4a_gpu_tci2_set_pi_shard, and the single rows and columns of a rook search (pivot_search == 1 goes
+ * through the host evaluator).  The driver otherwise treats the handle as one with a callback.  Replaces a callback or built-in
+ * function set before, and is replaced by setting one.  INVALID_ARGUMENT before any device work: a NULL handle, different lengths,
+ * a local dimension of the TensorCI2 that is not S1_a * S2_b of the site.  The values of the two routes agree to rounding, not
+ * bit for bit (the pairing sums la * lb in another order).
+ * LIFETIME: the TensorCI2 keeps the bare pointer, as it keeps the ctx of _set_callback: `contraction` must outlive `tci2`, or the
+ * next _set_callback / _set_builtin_function / _set_contraction_source on it. */
+t4a_gpu_status t4a_gpu_tci2_set_contraction_source(t4a_gpu_tci2* tci2, t4a_gpu_contraction* contraction);
+/* out[0] candidate matrices filled by a device source, out[1] their entries, out[2] entries this handle asked of its host callback
+ * (matrices of the callback route, rook rows and columns, global pivot search, pivot values; a sharded matrix counts in full).
+ * With a contraction source, out[1] + out[2] is what the TensorCI2 added to t4a_gpu_contraction_n_evaluated. */
+t4a_gpu_status t4a_gpu_tci2_source_stats(const t4a_gpu_tci2* tci2, uint64_t* out /* [3] */);
+/* t4a_gpu_mpo_contract_tci with the contraction set as the device matrix source instead of the host callback; the first pivot search
+ * and `info` are the same (function evaluations count both routes).  t4a_gpu_mpo_contract_tci itself keeps the host route. */
+t4a_gpu_status t4a_gpu_mpo_contract_tci_device(const t4a_gpu_mpo* a, const t4a_gpu_mpo* b, const t4a_gpu_tci2_options* options,
+                                               const size_t* initial_pivots, size_t n_pivots, t4a_gpu_mpo** out_mpo,
+                                               double* info /* [4] */);
 
 /* =====================================================================================
  * Quantics transform operators as MPOs — the real-valued part of tensor4all-quanticstransform

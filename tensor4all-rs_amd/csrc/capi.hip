@@ -3491,6 +3491,71 @@ t4a_gpu_status t4a_gpu_mpo_contract_tci(const t4a_gpu_mpo* a, const t4a_gpu_mpo*
     });
 }
 
+// ---- candidate matrices of A·B on the device: the entries below answer INVALID_ARGUMENT for NULL (t4a_gpu.h) ----
+#define T4A_REQUIRE_ARG(p)                                                            \
+    do {                                                                              \
+        if ((p) == nullptr) throw ::t4a::Error(T4A_GPU_INVALID_ARGUMENT, #p " is null"); \
+    } while (0)
+
+t4a_gpu_status t4a_gpu_contraction_evaluate_matrix(t4a_gpu_contraction* h, size_t cut, const size_t* rows, size_t n_rows, const size_t* cols,
+                                                   size_t n_cols, double* out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_ARG(h);
+        const size_t n = h->impl->len();
+        const size_t wl = 2 * std::min(cut, n), wr = 2 * (n - std::min(cut, n));
+        if (n_rows && wl) T4A_REQUIRE_ARG(rows);
+        if (n_cols && wr) T4A_REQUIRE_ARG(cols);
+        if (n_rows && n_cols) T4A_REQUIRE_ARG(out);
+        const std::vector<uint32_t> r = narrow_indices(rows, checked_mul(n_rows, wl, "index buffer"));
+        const std::vector<uint32_t> c = narrow_indices(cols, checked_mul(n_cols, wr, "index buffer"));
+        checked_mul(n_rows, n_cols, "matrix");
+        h->impl->evaluate_matrix_host(cut, r.data(), n_rows, c.data(), n_cols, out);
+    });
+}
+
+t4a_gpu_status t4a_gpu_tci2_set_contraction_source(t4a_gpu_tci2* tci2, t4a_gpu_contraction* contraction)
+{
+    return guarded([&] {
+        T4A_REQUIRE_ARG(tci2);
+        T4A_REQUIRE_ARG(contraction);
+        tci2->impl.set_source(contraction->impl.get());
+    });
+}
+
+t4a_gpu_status t4a_gpu_tci2_source_stats(const t4a_gpu_tci2* tci2, uint64_t* out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_ARG(tci2);
+        T4A_REQUIRE_ARG(out);
+        for (int k = 0; k < 3; ++k) out[k] = tci2->impl.source_stats[k];
+    });
+}
+
+t4a_gpu_status t4a_gpu_mpo_contract_tci_device(const t4a_gpu_mpo* a, const t4a_gpu_mpo* b, const t4a_gpu_tci2_options* options,
+                                               const size_t* initial_pivots, size_t n_pivots, t4a_gpu_mpo** out_mpo, double* info)
+{
+    return guarded([&] {
+        T4A_REQUIRE_ARG(out_mpo);
+        *out_mpo = nullptr;
+        T4A_REQUIRE_ARG(a);
+        T4A_REQUIRE_ARG(b);
+        T4A_REQUIRE_ARG(options);
+        T4A_REQUIRE_ARG(info);
+        if (n_pivots) T4A_REQUIRE_ARG(initial_pivots);
+        const TCI2Options o = convert_options(options);
+        const size_t ns = a->impl->len();
+        std::vector<std::vector<uint32_t>> piv(n_pivots, std::vector<uint32_t>(ns));
+        for (size_t k = 0; k < n_pivots; ++k)
+            for (size_t s = 0; s < ns; ++s) {
+                const size_t v = initial_pivots[s + ns * k];
+                if (v > 0xFFFFFFFFull) throw Error(T4A_GPU_INVALID_ARGUMENT, "pivot value out of bounds");
+                piv[k][s] = (uint32_t)v;
+            }
+        *out_mpo = new t4a_gpu_mpo{mpo_contract_tci(*a->impl, *b->impl, o, std::move(piv), info, true)};
+    });
+}
+
 // ---- quantics transform operators (tensor4all-quanticstransform): host builders, one upload, the difference kernel ----
 t4a_gpu_status t4a_gpu_qt_shift_operator(size_t r, int64_t offset, int32_t bc, t4a_gpu_qt_op** out)
 {

@@ -45,6 +45,13 @@ MpoContraction::MpoContraction(Mpo& a, Mpo& b)
     eng_ = &a_->tt.eng;
 }
 
+MpoContraction::~MpoContraction()
+{
+    if (eng_) (void)hipStreamSynchronize(eng_->stream()); // (a matrix a consumer never waited for)
+    for (hipEvent_t e : {ev_upload_, ev_consumer_, ev_done_})
+        if (e) (void)hipEventDestroy(e);
+}
+
 std::vector<std::array<size_t, 2>> MpoContraction::result_site_dims() const
 {
     std::vector<std::array<size_t, 2>> d(n_);
@@ -78,6 +85,18 @@ void MpoContraction::validate_indices(const uint32_t* idx, size_t n_pts, size_t 
     for (size_t p = 0; p < n_pts; ++p)
         for (size_t s = first; s < last; ++s) {
             const uint32_t i = idx[2 * n_ * p + 2 * s], j = idx[2 * n_ * p + 2 * s + 1];
+            if (i >= sites_[s].s1 || j >= sites_[s].s2)
+                throw Error(T4A_GPU_INVALID_ARGUMENT, "Index out of bounds: index " + std::to_string(std::max(i, j)) + " at site " +
+                                                          std::to_string(s) + " (max: " + std::to_string(std::max(sites_[s].s1, sites_[s].s2)) + ")");
+        }
+}
+
+void MpoContraction::validate_halves(const uint32_t* packed, size_t n_items, size_t first, size_t last) const
+{
+    const size_t w = last - first;
+    for (size_t p = 0; p < n_items; ++p)
+        for (size_t s = first; s < last; ++s) {
+            const uint32_t i = packed[2 * w * p + 2 * (s - first)], j = packed[2 * w * p + 2 * (s - first) + 1];
             if (i >= sites_[s].s1 || j >= sites_[s].s2)
                 throw Error(T4A_GPU_INVALID_ARGUMENT, "Index out of bounds: index " + std::to_string(std::max(i, j)) + " at site " +
                                                           std::to_string(s) + " (max: " + std::to_string(std::max(sites_[s].s1, sites_[s].s2)) + ")");
@@ -276,6 +295,114 @@ void MpoContraction::evaluate_fused(const uint32_t* fidx, size_t n_sites, size_t
     evaluate_many(idx.data(), n_pts, 0, out);
 }
 
+void MpoContraction::matrix_locked(size_t cut, const uint32_t* rows, size_t n_rows, const uint32_t* cols, size_t n_cols, bool fused,
+                                   double* d_out, size_t ld, bool transposed, hipStream_t consumer)
+{
+    const size_t n = n_;
+    if (n == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "MPO is empty");
+    if (cut > n) throw Error(T4A_GPU_INVALID_ARGUMENT, "Invalid split position: " + std::to_string(cut) + " (n_sites=" + std::to_string(n) + ")");
+    if (n_rows == 0 || n_cols == 0) return;
+    check_batch(n_rows);
+    check_batch(n_cols);
+    if (n_cols > CONTRACTION_PAIR_MAX_COLS)
+        throw Error(T4A_GPU_INVALID_ARGUMENT, "Contraction: more than " + std::to_string(CONTRACTION_PAIR_MAX_COLS) + " columns in one matrix");
+    if (ld < (transposed ? n_cols : n_rows)) throw Error(T4A_GPU_INVALID_ARGUMENT, "Contraction: the leading dimension is below the matrix");
+    const size_t wl = 2 * cut, wr = 2 * (n - cut);
+    const size_t nl = n_rows * wl, nr = n_cols * wr;
+    // the staging buffer is read by the previous call's upload: the one host wait of a call, normally over long ago
+    if (upload_pending_) {
+        T4A_HIP(hipEventSynchronize(ev_upload_));
+        upload_pending_ = false;
+    }
+    h_halves_.reserve(std::max<size_t>(nl + nr, 1));
+    uint32_t* hl = h_halves_.get();
+    uint32_t* hr = hl + nl;
+    if (fused) {
+        auto decode = [this](const uint32_t* f, size_t n_items, size_t first, size_t last, uint32_t* dst) {
+            const size_t w = last - first;
+            for (size_t p = 0; p < n_items; ++p)
+                for (size_t s = first; s < last; ++s) {
+                    const uint32_t v = f[w * p + (s - first)], s1 = (uint32_t)sites_[s].s1;
+                    dst[2 * w * p + 2 * (s - first)] = v % s1; // an f beyond s1 * s2 gives j >= s2: refused by validate_halves
+                    dst[2 * w * p + 2 * (s - first) + 1] = v / s1;
+                }
+        };
+        decode(rows, n_rows, 0, cut, hl);
+        decode(cols, n_cols, cut, n, hr);
+    } else {
+        if (nl) std::copy_n(rows, nl, hl);
+        if (nr) std::copy_n(cols, nr, hr);
+    }
+    validate_halves(hl, n_rows, 0, cut);
+    validate_halves(hr, n_cols, cut, n);
+    // entries of an environment at the cut (the outer bonds of an MPO are 1: K == 1 at cut == 0 and cut == len)
+    const size_t K = cut < n ? sites_[cut].la * sites_[cut].lb : sites_[n - 1].ra * sites_[n - 1].rb;
+    hipStream_t st = eng_->stream();
+    const bool foreign = consumer != nullptr && consumer != st;
+    if (!ev_upload_) {
+        T4A_HIP(hipEventCreateWithFlags(&ev_upload_, hipEventDisableTiming));
+        T4A_HIP(hipEventCreateWithFlags(&ev_consumer_, hipEventDisableTiming));
+        T4A_HIP(hipEventCreateWithFlags(&ev_done_, hipEventDisableTiming));
+    }
+    upload_descs();
+    d_idx_.reserve(std::max<size_t>(nl + nr, 1));
+    d_envl_.reserve(n_rows * K);
+    d_envr_.reserve(n_cols * K);
+    if (nl + nr) {
+        T4A_HIP(hipMemcpyAsync(d_idx_.get(), hl, (nl + nr) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        T4A_HIP(hipEventRecord(ev_upload_, st));
+        upload_pending_ = true;
+    }
+    if (wl)
+        launch_left(cut, d_idx_.get(), n_rows, d_envl_.get(), K);
+    else
+        fill_launch(d_envl_.get(), n_rows * K, 1.0, st); // evaluate_left(0, .) == [[1]]
+    if (wr)
+        launch_right(cut, d_idx_.get() + nl, n_cols, d_envr_.get(), K);
+    else
+        fill_launch(d_envr_.get(), n_cols * K, 1.0, st); // evaluate_right(len, .) == [[1]]
+    if (foreign) { // d_out may still be read or written by what the consumer enqueued before this call
+        T4A_HIP(hipEventRecord(ev_consumer_, consumer));
+        T4A_HIP(hipStreamWaitEvent(st, ev_consumer_, 0));
+    }
+    contraction_pair_launch(d_envl_.get(), (int)n_rows, d_envr_.get(), (int)n_cols, (int)K, d_out, ld, transposed, st);
+    T4A_HIP(hipGetLastError());
+    if (foreign) {
+        T4A_HIP(hipEventRecord(ev_done_, st));
+        T4A_HIP(hipStreamWaitEvent(consumer, ev_done_, 0));
+    }
+    n_evaluated_ += n_rows * n_cols;
+}
+
+void MpoContraction::evaluate_matrix(size_t cut, const uint32_t* rows, size_t n_rows, const uint32_t* cols, size_t n_cols, double* d_out,
+                                     size_t ld, bool transposed, hipStream_t consumer)
+{
+    std::lock_guard<std::mutex> lock(mu_);
+    matrix_locked(cut, rows, n_rows, cols, n_cols, false, d_out, ld, transposed, consumer);
+}
+
+void MpoContraction::fill_matrix(size_t cut, const uint32_t* rows, size_t n_rows, const uint32_t* cols, size_t n_cols, double* d_out,
+                                 size_t ld, bool transposed, hipStream_t consumer)
+{
+    std::lock_guard<std::mutex> lock(mu_);
+    matrix_locked(cut, rows, n_rows, cols, n_cols, true, d_out, ld, transposed, consumer);
+}
+
+void MpoContraction::evaluate_matrix_host(size_t cut, const uint32_t* rows, size_t n_rows, const uint32_t* cols, size_t n_cols, double* out)
+{
+    std::lock_guard<std::mutex> lock(mu_);
+    const size_t total = n_rows * n_cols;
+    d_vals_.reserve(std::max<size_t>(total, 1));
+    matrix_locked(cut, rows, n_rows, cols, n_cols, false, d_vals_.get(), n_rows, false, nullptr);
+    if (total == 0) return;
+    // through pinned memory: a copy straight into the caller's pageable buffer was measured at 30 ms for 2 MiB (the kernels take 0.35 ms)
+    h_vals_.reserve(total);
+    T4A_HIP(hipMemcpyAsync(h_vals_.get(), d_vals_.get(), total * sizeof(double), hipMemcpyDeviceToHost, eng_->stream()));
+    eng_->sync();
+    T4A_HIP(hipGetLastError());
+    std::copy_n(h_vals_.get(), total, out);
+}
+
 namespace {
 // t4a_gpu_batch_eval_fn over an MpoContraction*
 int64_t contraction_thunk(void* ctx, const uint32_t* idx, size_t n_sites, size_t n_pts, double* out)
@@ -291,14 +418,17 @@ int64_t contraction_thunk(void* ctx, const uint32_t* idx, size_t n_sites, size_t
 } // namespace
 
 std::unique_ptr<Mpo> mpo_contract_tci(Mpo& a, Mpo& b, const TCI2Options& options, std::vector<std::vector<uint32_t>> initial_pivots,
-                                      double info[4])
+                                      double info[4], bool device_source)
 {
     MpoContraction c(a, b);
     const size_t n = c.len();
     const std::vector<size_t> dims = c.fused_local_dims();
     options.validate();
     Tci2 tci(dims); // refuses fewer than two sites (tensorci2.rs:381-385)
-    tci.set_callback(&contraction_thunk, &c);
+    if (device_source)
+        tci.set_source(&c);
+    else
+        tci.set_callback(&contraction_thunk, &c);
     if (initial_pivots.empty()) { // optfirstpivot.rs: a local search for a large first pivot, started at the all-zero index
         const SearchFn f = [&c](const uint32_t* idx, size_t n_sites, size_t n_pts, double* out) { c.evaluate_fused(idx, n_sites, n_pts, out); };
         initial_pivots.push_back(opt_first_pivot(f, dims, std::vector<uint32_t>(n, 0), 1000));

@@ -575,6 +575,12 @@ void contraction_env_left_launch(const ContractionSiteDesc* d_sites, int n_walk,
                                  int env_cap, int t_cap, double* d_scratch, int blocks, hipStream_t stream);
 void contraction_env_right_launch(const ContractionSiteDesc* d_sites, int n_sites, int first, const uint32_t* d_idx, int n_items,
                                   double* d_out, int ld, int env_cap, int t_cap, double* d_scratch, int blocks, hipStream_t stream);
+// Every left environment paired with every right one: d_out[r + ld * c] (transposed: d_out[c + ld * r]) = sum_k d_left[r * K + k] *
+// d_right[c * K + k] on the f64 matrix cores, K summed in chunks of four in ascending order for every entry alike — the bits of an
+// entry do not depend on n_rows, n_cols, its position or `transposed`.  n_cols <= CONTRACTION_PAIR_MAX_COLS (the grid's second axis).
+constexpr size_t CONTRACTION_PAIR_MAX_COLS = (size_t)65535 * 64;
+void contraction_pair_launch(const double* d_left, int n_rows, const double* d_right, int n_cols, int K, double* d_out, size_t ld,
+                             bool transposed, hipStream_t stream);
 
 // ------------------------------------------------------------------------------------------------
 // kernels_small.hip — the small-problem engine (round 6): the WHOLE optimize_with_finder loop of a small TensorCI2 problem

@@ -1,5 +1,6 @@
 // kernels_contraction.hip — left / right environments of the lazy product of two MPOs (tensor4all-simplett/src/mpo/contraction.rs:
 // evaluate_left :262-314, evaluate_right :324-383) for a batch of unique index halves, one workgroup per half.
+// At the end of the file: contraction_pair_kernel, every left environment of a cut paired with every right one (a candidate matrix).
 //
 // An environment of the product A·B is a matrix over the bond pair (a, b), held column-major [a + dim_a * b].  A site step
 //   L'[ra, rb] = sum_{la, lb, k} L[la, lb] A[la, i, k, ra] B[lb, k, j, rb]      (contraction.rs:288-308)
@@ -173,7 +174,72 @@ __global__ void __launch_bounds__(256) contraction_env_right_kernel(const Contra
     }
 }
 
+// out[r, c] = sum_k L[r * K + k] * R[c * K + k]: every left environment paired with every right environment of a cut (a candidate
+// matrix of a cross interpolation of A·B).  One workgroup computes a PAIR_TILE x PAIR_TILE tile of the output: the K range is staged
+// through the LDS in panels of PAIR_KC (rows of both operands are contiguous in k, so a panel is read in 256-byte runs), wavefront w
+// owns columns [16 w, 16 w + 16) of the tile and walks its four 16 x 16 row blocks with the R operand held in a register.
+//
+// The bits of an entry depend on its two environments alone: every output goes through the same instruction sequence — K in chunks of
+// four, ascending, one v_mfma_f64_16x16x4_f64 per chunk, the last chunk zero-padded — whatever the shape of the request, the position
+// of the entry in it or the order of the output.  There is no split of K, no atomic and no separate arithmetic for small shapes: rows
+// and columns beyond the request are zero operands of the same instructions.
+//
+// Operand roles as in wg_product above: first operand = R (lane: c = lane & 15, k = lane >> 4), second = L (lane: r = lane & 15,
+// k = lane >> 4), acc[reg] = out[r = lane & 15][c = (lane >> 4) + 4 reg].  The LDS rows are PAIR_KC + 2 doubles apart: the 32 lanes of
+// a half-wavefront (16 rows, two k) then read 32 different 8-byte banks.
+constexpr int PAIR_TILE = 64;
+constexpr int PAIR_KC = 32;
+constexpr int PAIR_LDS_LD = PAIR_KC + 2;
+
+__global__ void __launch_bounds__(256) contraction_pair_kernel(const double* __restrict__ L, int n_rows, const double* __restrict__ R,
+                                                               int n_cols, int K, double* __restrict__ out, size_t ld, int transposed)
+{
+    __shared__ double Ls[PAIR_TILE * PAIR_LDS_LD];
+    __shared__ double Rs[PAIR_TILE * PAIR_LDS_LD];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int lr = lane & 15, lk = lane >> 4;
+    const int r0 = blockIdx.x * PAIR_TILE, c0 = blockIdx.y * PAIR_TILE;
+    double4_t acc[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) acc[t] = (double4_t){0.0, 0.0, 0.0, 0.0};
+    for (int k0 = 0; k0 < K; k0 += PAIR_KC) {
+        for (int e = tid; e < PAIR_TILE * PAIR_KC; e += 256) {
+            const int row = e / PAIR_KC, kk = e % PAIR_KC;
+            const bool k_ok = k0 + kk < K;
+            Ls[row * PAIR_LDS_LD + kk] = (k_ok && r0 + row < n_rows) ? L[(size_t)(r0 + row) * K + k0 + kk] : 0.0;
+            Rs[row * PAIR_LDS_LD + kk] = (k_ok && c0 + row < n_cols) ? R[(size_t)(c0 + row) * K + k0 + kk] : 0.0;
+        }
+        __syncthreads();
+        const int kend = min(PAIR_KC, K - k0); // (chunks behind the last one that holds an element of K are not issued)
+        for (int kk = 0; kk < kend; kk += 4) {
+            const double rv = Rs[(16 * wave + lr) * PAIR_LDS_LD + kk + lk];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                const double lv = Ls[(16 * t + lr) * PAIR_LDS_LD + kk + lk];
+                acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(rv, lv, acc[t], 0, 0, 0);
+            }
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+            const int r = r0 + 16 * t + lr, c = c0 + 16 * wave + lk + 4 * reg;
+            if (r < n_rows && c < n_cols) out[transposed ? (size_t)c + ld * r : (size_t)r + ld * c] = acc[t][reg];
+        }
+}
+
 } // namespace
+
+void contraction_pair_launch(const double* d_left, int n_rows, const double* d_right, int n_cols, int K, double* d_out, size_t ld,
+                             bool transposed, hipStream_t stream)
+{
+    if (n_rows <= 0 || n_cols <= 0 || K <= 0) return;
+    const dim3 grid((unsigned)((n_rows + PAIR_TILE - 1) / PAIR_TILE), (unsigned)((n_cols + PAIR_TILE - 1) / PAIR_TILE));
+    hipLaunchKernelGGL(contraction_pair_kernel, grid, dim3(256), 0, stream, d_left, n_rows, d_right, n_cols, K, d_out, ld,
+                       transposed ? 1 : 0);
+}
 
 void contraction_env_left_launch(const ContractionSiteDesc* d_sites, int n_walk, const uint32_t* d_idx, int n_items, double* d_out, int ld,
                                  int env_cap, int t_cap, double* d_scratch, int blocks, hipStream_t stream)

@@ -193,6 +193,7 @@ void Tci2::set_builtin(int fid, int n_acc, const double* params, const uint64_t*
     std::memcpy(fn_dev_.params, params, sizeof(double) * T4A_FN_MAX_PARAMS);
     weights_.assign(weights, weights + (size_t)n_acc * total_);
     fn_kind_ = FnKind::Builtin;
+    source_ = nullptr;
     chain_.weights_valid = false; // (the accumulators in the device tables belong to the old weights)
     chain_.tables_valid = false;
     chain_.snap_serial[0] = chain_.snap_serial[1] = ~0ull;
@@ -221,6 +222,37 @@ void Tci2::set_callback(t4a_gpu_batch_eval_fn cb, void* ctx)
     cb_ = cb;
     cb_ctx_ = ctx;
     fn_kind_ = FnKind::Callback;
+    source_ = nullptr;
+}
+
+namespace {
+// t4a_gpu_batch_eval_fn over a MatrixSource*: its host point evaluator
+int64_t source_thunk(void* ctx, const uint32_t* idx, size_t n_sites, size_t n_pts, double* out)
+{
+    try {
+        static_cast<MatrixSource*>(ctx)->eval_points(idx, n_sites, n_pts, out);
+        return (int64_t)n_pts;
+    } catch (const std::exception& e) {
+        set_last_error(e.what());
+        return -1;
+    }
+}
+} // namespace
+
+void Tci2::set_source(MatrixSource* src)
+{
+    if (!src) throw Error(T4A_GPU_NULL_POINTER, "source is null");
+    const std::vector<size_t> dims = src->source_local_dims();
+    if (dims.size() != n_)
+        throw Error(T4A_GPU_INVALID_ARGUMENT, "matrix source: length mismatch: the handle has " + std::to_string(n_) + " sites, the source " +
+                                                  std::to_string(dims.size()));
+    for (size_t s = 0; s < n_; ++s)
+        if (dims[s] != local_dims[s])
+            throw Error(T4A_GPU_INVALID_ARGUMENT, "matrix source: local dimension mismatch at site " + std::to_string(s) + ": the handle has " +
+                                                      std::to_string(local_dims[s]) + ", the source " + std::to_string(dims[s]));
+    set_callback(&source_thunk, src);
+    fn_kind_ = FnKind::Source;
+    source_ = src;
 }
 
 void Tci2::require_fn() const
@@ -440,12 +472,24 @@ void Tci2::eval_matrix(const IndexSet& a, size_t a0, const IndexSet& b, size_t b
         stage_accumulators(a, a0, b, b0, acc_a, acc_b, &d_ra, &d_rb);
         pi_eval_launch(fn_dev_, d_ra, (int)na, d_rb, (int)nb, d_out, (int)na, false, d_maxbits, st);
         T4A_HIP(hipGetLastError());
+    } else if (fn_kind_ == FnKind::Source && !pi_shard.active()) {
+        // device matrix source: the set that starts at site 0 holds the rows of the source's matrix; when that is `b`, out (na x nb,
+        // ia fastest) is the source's matrix transposed
+        const bool transposed = a0 != 0;
+        const IndexSet& rows = transposed ? b : a;
+        const IndexSet& cols = transposed ? a : b;
+        source_->fill_matrix(rows.width, rows.d.data(), rows.count, cols.d.data(), cols.count, d_out, na, transposed, st);
+        if (d_maxbits) absmax_launch(d_out, na * nb, d_maxbits, st);
+        T4A_HIP(hipGetLastError());
+        source_stats[0] += 1;
+        source_stats[1] += na * nb;
     } else {
         // host batch callback: points in row-major order of (ia, ib) — `ia` outer, `ib` inner — exactly the
         // order the reference hands to batched_f (tensorci2.rs:1862-1869)
         const size_t npts = na * nb;
         cb_vals_.reserve(npts); // (pinned, grow-only: the previous upload out of it was synchronised below)
         double* const vals = cb_vals_.get();
+        source_stats[2] += npts;
         if (pi_shard.active()) {
             // column blocks over the ranks of the process group + one all-gather (pishard.hpp)
             pi_shard_evaluate(pi_shard, cb_, cb_ctx_, n_, a.d.data(), a.width, a0, na, b.d.data(), b.width, b0, nb, vals);
@@ -525,6 +569,7 @@ std::vector<double> Tci2::eval_points_host(const std::vector<uint32_t>& idx, siz
             out[p] = t4a_fn_value(fn_dev_.fid, acc, fn_dev_.params);
         }
     } else {
+        source_stats[2] += n_pts;
         const int64_t got = cb_(cb_ctx_, idx.data(), n_, n_pts, out.data());
         if (got < 0 || (size_t)got != n_pts)
             throw Error(T4A_GPU_CALLBACK_ERROR, "batch callback returned " + std::to_string(got) + " values for " +
@@ -662,6 +707,7 @@ LuciResult Tci2::rook_on_sets(const IndexSet& is, const IndexSet& js, const RrLU
                     std::memcpy(dst + is.width, js.at(c0 + b), js.width * sizeof(uint32_t));
                 }
             std::vector<double> vals(npts);
+            source_stats[2] += npts;
             const int64_t got = cb_(cb_ctx_, idx.data(), n_, npts, vals.data());
             if (got < 0 || (size_t)got != npts)
                 throw Error(T4A_GPU_CALLBACK_ERROR, "batch callback returned " + std::to_string(got) + " values for " +

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "engine.hpp"
+#include "matrix_source.hpp"
 #include "stdrng.hpp"
 #include "pishard.hpp"
 #include "rook.hpp"
@@ -68,6 +69,18 @@ public:
     // function source
     void set_builtin(int fid, int n_acc, const double* params, const uint64_t* weights);
     void set_callback(t4a_gpu_batch_eval_fn cb, void* ctx);
+    // A device matrix source (matrix_source.hpp): candidate matrices — the two-site matrix of a bond under full search, the
+    // matrices of fill_site_tensors, the last tensor of a one-site sweep — are filled in device memory by src->fill_matrix, without
+    // a host index buffer or a transfer of values.  The source's eval_points is installed as the host callback, and everything that is
+    // not a whole matrix keeps going through it: global pivot search, error estimates, a candidate matrix sharded over ranks
+    // (pi_shard), and the rows and columns a rook search asks for (rook_on_sets evaluates single rows and columns on demand: they
+    // stay on the host route).  Everywhere else the driver treats a source like a callback: the host-driven per-bond path runs, no
+    // bond chain, no one-launch engine, no fill-ahead.  Refused before any device work: a source whose local dims differ from the
+    // handle's.  `src` must outlive the handle or its next set_builtin / set_callback / set_source, each of which replaces it.
+    void set_source(MatrixSource* src);
+    // [0] matrices filled by the source [1] their entries [2] entries asked of the host callback by this handle (candidate matrices of
+    // the callback route, rook rows and columns, global pivot search, pivot values; a sharded matrix counts in full)
+    std::array<uint64_t, 3> source_stats{{0, 0, 0}};
 
     // reference API
     size_t len() const { return n_; }
@@ -191,8 +204,9 @@ public:
     Engine eng;
 
 private:
-    enum class FnKind { None, Builtin, Callback };
+    enum class FnKind { None, Builtin, Callback, Source }; // Source: a Callback whose whole matrices are filled by source_
     FnKind fn_kind_ = FnKind::None;
+    MatrixSource* source_ = nullptr;
     FnDevice fn_dev_{};
     std::vector<uint64_t> weights_; // n_acc * total
     std::vector<size_t> offset_;

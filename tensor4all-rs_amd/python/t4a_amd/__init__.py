@@ -544,6 +544,21 @@ class TensorCI2:
         cb = ctypes.cast(fn_ptr, _BATCH_CB) if not isinstance(fn_ptr, _BATCH_CB) else fn_ptr
         _check(_lib.t4a_gpu_tci2_set_callback(self._h, cb, ctypes.c_void_p(ctx_ptr)))
 
+    def set_contraction_source(self, c):
+        """A ``Contraction`` as the device matrix source (t4a_gpu_tci2_set_contraction_source): whole candidate matrices are filled on
+        the device, everything else (global pivot search, rook rows and columns, pivot values) goes through the contraction's native
+        callback.  ``c`` is kept alive as long as this object holds it; one with a transform is refused, as by ``as_callback``."""
+        if getattr(c, "_f", None) is not None:
+            raise T4aError(INVALID_ARGUMENT, "a contraction with a transform has no native callback: the transform runs in Python")
+        _check(_lib.t4a_gpu_tci2_set_contraction_source(self._h, c._h))
+        self._cb_keepalive = c
+
+    def source_stats(self):
+        """{"matrices", "entries"}: candidate matrices a device source filled; "host_entries": entries asked of the host callback."""
+        out = (ctypes.c_uint64 * 3)()
+        _check(_lib.t4a_gpu_tci2_source_stats(self._h, out))
+        return {"matrices": int(out[0]), "entries": int(out[1]), "host_entries": int(out[2])}
+
     def set_pi_shard(self, rank, world, gather=None):
         """Column-block shard of every callback-evaluated candidate matrix over a process group.
         gather(send: np.ndarray[count]) -> np.ndarray[world * count] (rank-major all-gather on host buffers), e.g.

@@ -338,6 +338,37 @@ class Contraction:
                                                       _p(out), ctypes.byref(used)))
         return self._transform(out), used.value
 
+    def evaluate_matrix(self, cut, rows, cols):
+        """A candidate matrix of A·B (t4a_gpu_contraction_evaluate_matrix): ``rows`` are index halves over sites 0 .. cut-1, an
+        (n_rows, cut, 2) array, ``cols`` halves over sites cut .. len-1, an (n_cols, len - cut, 2) array -> the (n_rows, n_cols) array
+        of (A·B)(rows[r] + cols[c]).  The environments of every half are computed once on the device and paired on the matrix cores;
+        the bits of an entry depend on its two halves alone, not on the request around it.  ``cut`` may be 0 or len (halves of width
+        0, e.g. ``np.zeros((1, 0, 2))``).  The transform of ``with_transform`` is applied to the result."""
+        n = len(self)
+        if cut < 0 or cut > n:
+            raise T4aError(INVALID_ARGUMENT, f"Invalid split position: {cut} (n_sites={n})")
+        halves = []
+        for name, h, w in (("rows", rows, cut), ("cols", cols, n - cut)):
+            h = np.asarray(h, dtype=np.int64)
+            if h.size == 0 and h.ndim < 3:  # [] is no halves, [[]] one half of width 0
+                count = h.shape[0] if h.ndim else 0
+                h = np.zeros((count, w if count == 0 else 0, 2), dtype=np.int64)
+            if h.ndim != 3 or h.shape[2] != 2:
+                raise T4aError(INVALID_ARGUMENT, f"{name} must be an (n, width, 2) array of (i, j) pairs")
+            if h.shape[1] != w:
+                raise T4aError(INVALID_ARGUMENT, f"Invalid operation: Expected {w} index pairs, got {h.shape[1]}")
+            if (h < 0).any():
+                raise T4aError(INVALID_ARGUMENT, "negative index")
+            halves.append(np.ascontiguousarray(h.astype(np.uintp)))
+        r, c = halves
+        n_rows, n_cols = r.shape[0], c.shape[0]
+        out = np.zeros(max(n_rows * n_cols, 1))
+        pad = np.zeros(1, dtype=np.uintp)  # never a NULL buffer
+        _check(_lib.t4a_gpu_contraction_evaluate_matrix(self._h, c_size_t(cut), _p(r if r.size else pad), c_size_t(n_rows),
+                                                        _p(c if c.size else pad), c_size_t(n_cols), _p(out)))
+        vals = self._transform(out[:n_rows * n_cols])
+        return vals.reshape(n_cols, n_rows).T.copy()
+
     def as_callback(self):
         """(function pointer, ctx, keepalive) for ``TensorCI2.set_callback_raw``: t4a_gpu_contraction_batch_eval over this handle, which
         takes the fused site index i + s1_a * j.  The third element keeps the contraction alive as long as the TensorCI2 holds it."""
@@ -347,16 +378,21 @@ class Contraction:
         return fn, self._h.value, self
 
 
-def contract_tci(a, b, options=None, initial_pivots=None):
+def contract_tci(a, b, options=None, initial_pivots=None, route="host"):
     """The product A·B as an MPO by cross interpolation over the fused site index i + s1_a * j (t4a_gpu_mpo_contract_tci; this
     project's).  ``options``: a TCI2Options, default tolerance 1e-12 without global pivot search; ``initial_pivots``: fused
     multi-indices, default the result of opt_first_pivot from the all-zero index.  The result carries ``tci_info``:
-    termination, rank, n_evaluations, error."""
+    termination, rank, n_evaluations, error.  ``route``: "host" feeds the TensorCI2 through the batch callback, "device" sets the
+    contraction as its device matrix source (t4a_gpu_mpo_contract_tci_device): candidate matrices never leave the device; the two
+    agree to rounding, not bit for bit."""
+    if route not in ("host", "device"):
+        raise T4aError(INVALID_ARGUMENT, f"unknown route {route!r}: \"host\" or \"device\"")
     o = (TCI2Options(tolerance=1e-12, max_nglobal_pivot=0, nsearch=0) if options is None else options).to_c()
     piv, n_piv = _fused_pivots(initial_pivots, len(a))
     h = c_void_p()
     info = np.zeros(4)
-    _check(_lib.t4a_gpu_mpo_contract_tci(a._h, b._h, ctypes.byref(o), _p(piv), c_size_t(n_piv), ctypes.byref(h), _p(info)))
+    fn = _lib.t4a_gpu_mpo_contract_tci_device if route == "device" else _lib.t4a_gpu_mpo_contract_tci
+    _check(fn(a._h, b._h, ctypes.byref(o), _p(piv), c_size_t(n_piv), ctypes.byref(h), _p(info)))
     m = MPO._adopt(h)
     m.tci_info = {"termination": int(info[0]), "rank": int(info[1]), "n_evaluations": int(info[2]), "error": float(info[3])}
     return m

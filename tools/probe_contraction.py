@@ -4,11 +4,13 @@
 Shape: two operators of `n` sites, site dims (2, 2), bonds `chi_a` and `chi_b` (the LCG fixtures of the tests).
 
     python tools/probe_contraction.py [n] [chi_a] [chi_b] [reps]          every step, each in a child process under its own `timeout`
-    python tools/probe_contraction.py --step NAME [n] [chi_a] [chi_b] [reps]
+    python tools/probe_contraction.py --step NAME [--route host|device] [n] [chi_a] [chi_b] [reps]
 
 Steps: points (4096 random points), outer (one 512 x 512 outer-product batch split in the middle), naive_points / naive_outer (the same
-batches through the materialised product), tci (contract_tci at tolerance 1e-10 against contract_zipup; the driver runs it at bonds
-8 and 6 unless bonds are given), pairing (one outer batch and
+batches through the materialised product), matrix (the same 512 x 512 outer product as ONE candidate matrix through evaluate_matrix:
+no index buffer, no unique map, paired by contraction_pair_kernel — read its time under `rocprofv3 --kernel-trace --stats`), tci
+(contract_tci at tolerance 1e-10 against contract_zipup, on the route given: "host" is the batch callback, "device" the contraction as
+the device matrix source; the driver runs both at bonds 8 and 6 unless bonds are given), pairing (one outer batch and
 one dense product of the pairing's shape, 512 x la*lb by la*lb x 512: run it under `rocprofv3 --kernel-trace --stats` to read
 tt_env_dot_kernel next to gemm_kernel).  A time is the median of `reps` calls after a warm-up (reps = 0: one cold call); every call ends
 with the synchronisation of its own stream, so the device work is inside the window.  The driver stops at the first step that fails."""
@@ -27,7 +29,8 @@ import numpy as np  # noqa: E402
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(ROOT, "tensor4all-rs_amd", "python"), os.path.join(ROOT, "tests")]
 
-STEPS = [("points", 240), ("outer", 240), ("pairing", 240), ("naive_points", 420), ("naive_outer", 540), ("tci", 540)]
+STEPS = [("points", 240), ("outer", 240), ("matrix", 240), ("pairing", 240), ("naive_points", 420), ("naive_outer", 540), ("tci", 540),
+         ("tci:device", 540)]
 TCI_DEFAULT_BONDS = (8, 6)  # the driver's tci step when no bonds are given: at 32 and 24 (rank 768) one call takes minutes
 ORACLE_MAX_RANK = 64  # the one-thread reference run of the tci step is skipped above this la * lb (minutes of numpy callbacks)
 
@@ -37,14 +40,14 @@ def median_ms(call, reps):
         t0 = time.perf_counter()
         call()
         ms = round((time.perf_counter() - t0) * 1e3, 3)
-        return ms, ms
+        return ms, ms, ms
     call()  # warm-up (allocations, first launches)
     times = []
     for _ in range(reps):
         t0 = time.perf_counter()
         call()
         times.append((time.perf_counter() - t0) * 1e3)
-    return round(float(np.median(times)), 3), round(min(times), 3)
+    return round(float(np.median(times)), 3), round(min(times), 3), round(max(times), 3)
 
 
 def once_ms(call):
@@ -57,7 +60,7 @@ def rel_dev(got, want):
     return float(np.abs(np.asarray(got) - np.asarray(want)).max() / max(1.0, np.abs(want).max()))
 
 
-def step(name, n, chi_a, chi_b, reps):
+def step(name, n, chi_a, chi_b, reps, route="host"):
     import t4a_amd
     import contraction_np as cnp
     a = cnp.random_tensors([1] + [chi_a] * (n - 1) + [1], 2, 2, cnp.SEED)
@@ -72,17 +75,24 @@ def step(name, n, chi_a, chi_b, reps):
     if name in ("points", "outer"):
         batch, split = (points, None) if name == "points" else (outer, h)
         c = t4a_amd.Contraction(A, B)
-        med, best = median_ms(lambda: c.evaluate_many(batch, split=split), reps)
+        med, best, worst = median_ms(lambda: c.evaluate_many(batch, split=split), reps)
         vals, used = c.evaluate_many(batch, split=split)
         want, np_ms = once_ms(lambda: ref.evaluate_many(batch, used))  # the same scheme: unique halves once, then the pairing
-        out.update({"n_pts": len(batch), "split": used, "gpu_ms_median": med, "gpu_ms_min": best, "numpy_1thread_ms": np_ms,
-                    "max_rel_dev": rel_dev(vals, want)})
+        out.update({"n_pts": len(batch), "split": used, "gpu_ms_median": med, "gpu_ms_min": best, "gpu_ms_max": worst,
+                    "numpy_1thread_ms": np_ms, "max_rel_dev": rel_dev(vals, want)})
+    elif name == "matrix":
+        c = t4a_amd.Contraction(A, B)
+        med, best, worst = median_ms(lambda: c.evaluate_matrix(h, rows, cols), reps)
+        vals = c.evaluate_matrix(h, rows, cols)
+        want, np_ms = once_ms(lambda: ref.evaluate_many(outer, h))
+        out.update({"shape": list(vals.shape), "cut": h, "gpu_ms_median": med, "gpu_ms_min": best, "gpu_ms_max": worst,
+                    "numpy_1thread_ms": np_ms, "max_rel_dev": rel_dev(vals.reshape(-1), want)})
     elif name in ("naive_points", "naive_outer"):
         batch = points if name == "naive_points" else outer
         flat = batch.reshape(len(batch), -1)
-        med_c, _ = median_ms(lambda: t4a_amd.contract_naive(A, B, None), reps)
+        med_c, _, _ = median_ms(lambda: t4a_amd.contract_naive(A, B, None), reps)
         prod = t4a_amd.contract_naive(A, B, None)
-        med_e, best_e = median_ms(lambda: prod.evaluate(flat), reps)
+        med_e, best_e, _ = median_ms(lambda: prod.evaluate(flat), reps)
         c = t4a_amd.Contraction(A, B)
         out.update({"n_pts": len(batch), "contract_naive_ms_median": med_c, "evaluate_ms_median": med_e, "evaluate_ms_min": best_e,
                     "route_ms": round(med_c + med_e, 3), "max_rel_dev_vs_contraction": rel_dev(c.evaluate_many(batch)[0], prod.evaluate(flat))})
@@ -90,13 +100,17 @@ def step(name, n, chi_a, chi_b, reps):
         opts = t4a_amd.TCI2Options(tolerance=1e-10, max_nglobal_pivot=0, nsearch=0)
         zopt = t4a_amd.ContractionOptions(tolerance=1e-10)
         keep = {}
-        med, best = median_ms(lambda: keep.__setitem__("m", t4a_amd.contract_tci(A, B, opts)), reps)
-        medz, bestz = median_ms(lambda: keep.__setitem__("z", t4a_amd.contract_zipup(A, B, zopt)), reps)
+        tci = (lambda: t4a_amd.contract_tci(A, B, opts)) if route == "host" else (lambda: t4a_amd.contract_tci(A, B, opts, route=route))
+        med, best, worst = median_ms(lambda: keep.__setitem__("m", tci()), reps)
+        medz, bestz, _ = median_ms(lambda: keep.__setitem__("z", t4a_amd.contract_zipup(A, B, zopt)), reps)
         m, z = keep["m"], keep["z"]
         flat = points.reshape(len(points), -1)
         want = ref.evaluate(points)
         o_ms = "skipped: la * lb above %d" % ORACLE_MAX_RANK
         try:  # the reference algorithm on one CPU thread, fed by the numpy restatement
+            if route != "host":  # the oracle column belongs to the host row of the table: one minute of numpy callbacks, not repeated
+                o_ms = "skipped: reported with route host"
+                raise OverflowError
             if chi_a * chi_b > ORACLE_MAX_RANK:
                 raise OverflowError
             import oracle_binding as ob
@@ -108,7 +122,7 @@ def step(name, n, chi_a, chi_b, reps):
             pass
         except Exception as e:  # the oracle is a test fixture: the probe runs without it
             o_ms = f"unavailable: {e}"
-        out.update({"tci_ms_median": med, "tci_ms_min": best, "tci_link_dims": m.link_dims(), "tci_info": m.tci_info,
+        out.update({"route": route, "tci_ms_median": med, "tci_ms_min": best, "tci_ms_max": worst, "tci_link_dims": m.link_dims(), "tci_info": m.tci_info,
                     "tci_max_rel_dev": rel_dev(m.evaluate(flat), want), "zipup_ms_median": medz, "zipup_ms_min": bestz,
                     "zipup_link_dims": z.link_dims(), "zipup_max_rel_dev": rel_dev(z.evaluate(flat), want),
                     "oracle_tci_numpy_1thread_ms": o_ms})
@@ -117,7 +131,7 @@ def step(name, n, chi_a, chi_b, reps):
         c.evaluate_many(outer, split=h)
         left = c.evaluate_left(h, outer[::512]).reshape(512, -1)       # 512 x la*lb
         right = c.evaluate_right(h, outer[:512]).reshape(512, -1).T    # la*lb x 512
-        med, best = median_ms(lambda: t4a_amd.mat_mul(left, right), reps)
+        med, best, _ = median_ms(lambda: t4a_amd.mat_mul(left, right), reps)
         out.update({"pairing_shape": [left.shape[0], left.shape[1], right.shape[1]], "mat_mul_with_copies_ms_median": med,
                     "max_rel_dev": rel_dev(t4a_amd.mat_mul(left, right).reshape(-1), c.evaluate_many(outer, split=h)[0])})
     else:
@@ -128,16 +142,20 @@ def step(name, n, chi_a, chi_b, reps):
 def main():
     argv = sys.argv[1:]
     name = None
+    route = "host"
     if argv[:1] == ["--step"]:
         name, argv = argv[1], argv[2:]
+    if argv[:1] == ["--route"]:
+        route, argv = argv[1], argv[2:]
     a = [int(x) for x in argv]
     n, chi_a, chi_b, reps = (a + [16, 32, 24, 5][len(a):])[:4]
     if name is not None:
-        return step(name, n, chi_a, chi_b, reps)
+        return step(name, n, chi_a, chi_b, reps, route)
     for s, limit in STEPS:
+        s, _, r = s.partition(":")
         ca, cb = TCI_DEFAULT_BONDS if s == "tci" and len(a) < 3 else (chi_a, chi_b)
-        rc = subprocess.call(["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--step", s, str(n), str(ca),
-                              str(cb), str(reps)])
+        rc = subprocess.call(["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--step", s, "--route", r or "host",
+                              str(n), str(ca), str(cb), str(reps)])
         if rc != 0:
             raise SystemExit(f"step {s} ended with status {rc}: nothing further is started")
 
