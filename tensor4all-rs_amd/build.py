@@ -22,7 +22,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=o
 # kernels_linalg.hip (Jacobi SVD, Householder QR: compared at tolerances, no pivot decision hangs on a rounding): fused multiply-adds —
 # its one-workgroup kernels are bound by the instructions they issue, a separately rounded multiply and add is two of them
 FILE_FLAGS = {"kernels_dense.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"], "kernels_linalg.hip": ["-ffp-contract=fast"]}
-HEADERS = ["common.hpp", "stdrng.hpp", "pishard.hpp", "kernels.hpp", "kernels_rrlu_xcd_common.hpp", "kernels_rrlu_w1_body.hpp", "engine.hpp", "tci2.hpp", "matrix_source.hpp", "tt.hpp", "mpo.hpp", "contraction.hpp", "globalsearch.hpp", "rook.hpp", "patching.hpp", "tree.hpp", "quantics.hpp", "tensorops.hpp", "dense.hpp", "aci.hpp", "quanticstransform.hpp", "../../include/t4a_gpu.h",
+HEADERS = ["common.hpp", "stdrng.hpp", "pishard.hpp", "kernels.hpp", "kernels_rrlu_xcd_common.hpp", "kernels_rrlu_w1_body.hpp", "engine.hpp", "fnsource.hpp", "tci2.hpp", "matrix_source.hpp", "tt.hpp", "mpo.hpp", "contraction.hpp", "globalsearch.hpp", "rook.hpp", "patching.hpp", "tree.hpp", "quantics.hpp", "tensorops.hpp", "dense.hpp", "aci.hpp", "quanticstransform.hpp", "../../include/t4a_gpu.h",
            "../../include/t4a_testfunctions.h"]
 
 

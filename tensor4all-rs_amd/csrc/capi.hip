@@ -514,35 +514,28 @@ t4a_gpu_status t4a_gpu_fn_eval(int32_t fid, int32_t n_acc, const double* params,
             throw Error(T4A_GPU_INVALID_ARGUMENT, "unknown built-in function");
         std::lock_guard<std::mutex> lock(g_dense_mutex);
         Engine& e = dense_engine();
+        FnSource f(std::vector<size_t>(local_dims, local_dims + n_sites));
+        f.set_builtin(fid, n_acc, params, weights);
         // fold every full index into its accumulators as a "row"; a single all-zero "column"
-        std::vector<size_t> off(n_sites);
-        size_t total = 0;
-        for (size_t s = 0; s < n_sites; ++s) {
-            off[s] = total;
-            total += local_dims[s];
-        }
-        std::vector<uint64_t> acc(n_pts * (size_t)n_acc, 0), zero((size_t)n_acc, 0);
+        IndexSet rows;
+        rows.width = n_sites;
+        rows.count = n_pts;
+        rows.d.resize(n_pts * n_sites);
         for (size_t p = 0; p < n_pts; ++p)
-            for (int k = 0; k < n_acc; ++k) {
-                uint64_t a = 0;
-                for (size_t s = 0; s < n_sites; ++s) {
-                    const size_t v = idx[p * n_sites + s];
-                    if (v >= local_dims[s]) throw Error(T4A_GPU_INVALID_ARGUMENT, "index out of bounds");
-                    a += weights[(size_t)k * total + off[s] + v];
-                }
-                acc[p * n_acc + k] = a;
+            for (size_t s = 0; s < n_sites; ++s) {
+                const size_t v = idx[p * n_sites + s];
+                if (v >= local_dims[s]) throw Error(T4A_GPU_INVALID_ARGUMENT, "index out of bounds");
+                rows.d[p * n_sites + s] = (uint32_t)v;
             }
+        std::vector<uint64_t> acc, zero((size_t)n_acc, 0);
+        f.accumulate(rows, f.offset.data(), acc);
         DevBuf<uint64_t> dacc;
         dacc.reserve(acc.size() + zero.size());
         T4A_HIP(hipMemcpyAsync(dacc.get(), acc.data(), acc.size() * 8, hipMemcpyHostToDevice, e.stream()));
         T4A_HIP(hipMemcpyAsync(dacc.get() + acc.size(), zero.data(), zero.size() * 8, hipMemcpyHostToDevice, e.stream()));
         T4A_HIP(hipStreamSynchronize(e.stream()));
         e.d_tmp.reserve(n_pts);
-        FnDevice fn;
-        fn.fid = fid;
-        fn.n_acc = n_acc;
-        std::memcpy(fn.params, params, sizeof(double) * T4A_FN_MAX_PARAMS);
-        pi_eval_launch(fn, dacc.get(), (int)n_pts, dacc.get() + acc.size(), 1, e.d_tmp.get(), (int)n_pts, false, nullptr,
+        pi_eval_launch(f.dev, dacc.get(), (int)n_pts, dacc.get() + acc.size(), 1, e.d_tmp.get(), (int)n_pts, false, nullptr,
                        e.stream());
         T4A_HIP(hipGetLastError());
         download(e, out, e.d_tmp.get(), n_pts);
@@ -1018,8 +1011,7 @@ t4a_gpu_status t4a_gpu_pi_shard_eval(size_t rank, size_t world, t4a_gpu_batch_ev
                 std::memcpy(dst + a0, a + ia * wa, wa * sizeof(uint32_t));
                 std::memcpy(dst + b0, b + ib * wb, wb * sizeof(uint32_t));
             }
-        const int64_t got = cb(cb_ctx, idx.data(), n_sites, na * nb, out);
-        if (got < 0 || (size_t)got != na * nb) throw Error(T4A_GPU_CALLBACK_ERROR, "batch callback returned a wrong number of values");
+        FnSource::call(cb, cb_ctx, idx.data(), n_sites, na * nb, out, "batch callback", "requested entries");
     });
 }
 
@@ -1475,9 +1467,7 @@ extern "C++" {
 static t4a::SearchFn wrap_search_fn(t4a_gpu_batch_eval_fn f, void* ctx)
 {
     return [f, ctx](const uint32_t* idx, size_t n_sites, size_t n_pts, double* out) {
-        const int64_t got = f(ctx, idx, n_sites, n_pts, out);
-        if (got != (int64_t)n_pts)
-            throw Error(T4A_GPU_CALLBACK_ERROR, "batch callback returned " + std::to_string(got) + " values for " + std::to_string(n_pts) + " points");
+        FnSource::call(f, ctx, idx, n_sites, n_pts, out, "batch callback", "points");
     };
 }
 static std::vector<size_t> dims_vec(const size_t* local_dims, size_t n_sites)
@@ -1581,7 +1571,7 @@ t4a_gpu_status t4a_gpu_tci2_from_tensor_train(const t4a_gpu_tt* tt, double toler
 
 // ------------------------------------------------------------------------------------------------ adaptive patching
 extern "C++" {
-static t4a_gpu_ptt* run_adaptive(const size_t* local_dims, size_t n_sites, const FullFunction& f,
+static t4a_gpu_ptt* run_adaptive(const size_t* local_dims, size_t n_sites, const FnSource& f,
                                  const size_t* initial_pivots, size_t n_pivots, const t4a_gpu_tci2_options* tci_options,
                                  const size_t* patch_order, size_t n_initial_pivots, int32_t recycle_pivots)
 {
@@ -1618,16 +1608,8 @@ t4a_gpu_status t4a_gpu_adaptive_interpolate_builtin(const size_t* local_dims, si
         *out = nullptr;
         T4A_REQUIRE_PTR(params);
         T4A_REQUIRE_PTR(weights);
-        if (fid < 0 || fid >= T4A_FN_COUNT) throw Error(T4A_GPU_INVALID_ARGUMENT, "unknown built-in function id");
-        if (n_acc < 1 || n_acc > T4A_FN_MAX_ACC) throw Error(T4A_GPU_INVALID_ARGUMENT, "n_acc out of range");
-        FullFunction f;
-        f.builtin = true;
-        f.fid = fid;
-        f.n_acc = n_acc;
-        std::memcpy(f.params, params, sizeof(double) * T4A_FN_MAX_PARAMS);
-        size_t total = 0;
-        for (size_t s = 0; s < n_sites; ++s) total += local_dims ? local_dims[s] : 0;
-        f.weights.assign(weights, weights + (size_t)n_acc * total);
+        FnSource f(dims_vec(local_dims, local_dims ? n_sites : 0)); // (run_adaptive reports a missing local_dims)
+        f.set_builtin(fid, n_acc, params, weights);
         *out = run_adaptive(local_dims, n_sites, f, initial_pivots, n_pivots, tci_options, patch_order, n_initial_pivots,
                             recycle_pivots);
     });
@@ -1642,10 +1624,8 @@ t4a_gpu_status t4a_gpu_adaptive_interpolate_callback(const size_t* local_dims, s
         T4A_REQUIRE_PTR(out);
         *out = nullptr;
         T4A_REQUIRE_PTR(cb);
-        FullFunction f;
-        f.builtin = false;
-        f.cb = cb;
-        f.ctx = ctx;
+        FnSource f(dims_vec(local_dims, local_dims ? n_sites : 0));
+        f.set_callback(cb, ctx);
         *out = run_adaptive(local_dims, n_sites, f, initial_pivots, n_pivots, tci_options, patch_order, n_initial_pivots,
                             recycle_pivots);
     });

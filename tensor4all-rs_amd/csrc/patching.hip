@@ -30,13 +30,6 @@ using Rng = StdRng; // adaptive_interpolation.rs:164: ONE StdRng::seed_from_u64 
 using Pivot = std::vector<uint32_t>;
 using Projector = std::map<size_t, size_t>;
 
-struct Ctx {
-    const std::vector<size_t>* dims;
-    const FullFunction* f;
-    std::vector<size_t> offset; // per site into the weight tables
-    size_t total = 0;
-};
-
 std::vector<size_t> active_positions(size_t n, const Projector& pr) // :361-367
 {
     std::vector<size_t> a;
@@ -54,28 +47,17 @@ Pivot expand_pivot(const Pivot& local, const std::vector<size_t>& active, const 
 }
 
 // values of the full function at a list of full pivots (host side: candidate screening, single-site patches)
-std::vector<double> eval_full(const Ctx& c, const std::vector<Pivot>& pts)
+std::vector<double> eval_full(const FnSource& f, const std::vector<Pivot>& pts)
 {
-    const size_t n = c.dims->size();
+    const size_t n = f.offset.size();
     std::vector<double> out(pts.size());
     if (pts.empty()) return out;
-    if (c.f->builtin) {
-        for (size_t p = 0; p < pts.size(); ++p) {
-            uint64_t acc[T4A_FN_MAX_ACC] = {0, 0, 0, 0};
-            for (int k = 0; k < c.f->n_acc; ++k) {
-                const uint64_t* w = c.f->weights.data() + (size_t)k * c.total;
-                for (size_t s = 0; s < n; ++s) acc[k] += w[c.offset[s] + pts[p][s]];
-            }
-            out[p] = t4a_fn_value(c.f->fid, acc, c.f->params);
-        }
-    } else {
-        std::vector<uint32_t> flat(pts.size() * n);
-        for (size_t p = 0; p < pts.size(); ++p) std::copy(pts[p].begin(), pts[p].end(), flat.begin() + p * n);
-        const int64_t got = c.f->cb(c.f->ctx, flat.data(), n, pts.size(), out.data());
-        if (got < 0 || (size_t)got != pts.size())
-            throw Error(T4A_GPU_CALLBACK_ERROR, "batch callback returned " + std::to_string(got) + " values for " +
-                                                    std::to_string(pts.size()) + " requested entries");
-    }
+    std::vector<uint32_t> flat(pts.size() * n);
+    for (size_t p = 0; p < pts.size(); ++p) std::copy(pts[p].begin(), pts[p].end(), flat.begin() + p * n);
+    if (f.builtin())
+        f.host_values(flat.data(), pts.size(), out.data());
+    else
+        f.call(flat.data(), n, pts.size(), out.data(), "batch callback", "requested entries");
     return out;
 }
 
@@ -240,7 +222,7 @@ std::vector<Pivot> global_diagonal_pivots(const Tci2& tci, const std::vector<siz
 
 // host-callback trampoline: local pivots of a patch -> full pivots -> user callback
 struct PatchCallback {
-    const FullFunction* f;
+    const FnSource* f;
     const std::vector<size_t>* active;
     Pivot base; // projected values at their positions, 0 elsewhere
     size_t n_full;
@@ -254,7 +236,7 @@ int64_t patch_trampoline(void* vctx, const uint32_t* idx, size_t n_local, size_t
         std::copy(pc->base.begin(), pc->base.end(), dst);
         for (size_t k = 0; k < n_local; ++k) dst[(*pc->active)[k]] = idx[p * n_local + k];
     }
-    return pc->f->cb(pc->f->ctx, full.data(), pc->n_full, n_pts, out);
+    return pc->f->cb(pc->f->cb_ctx, full.data(), pc->n_full, n_pts, out);
 }
 
 std::vector<size_t> validate(const std::vector<size_t>& dims, const std::vector<Pivot>& pivots, const AdaptiveOptions& o) // :264-355
@@ -285,23 +267,14 @@ std::vector<size_t> validate(const std::vector<size_t>& dims, const std::vector<
 
 } // namespace
 
-std::unique_ptr<PartitionedTT> adaptive_interpolate(const std::vector<size_t>& dims, const FullFunction& f,
+std::unique_ptr<PartitionedTT> adaptive_interpolate(const std::vector<size_t>& dims, const FnSource& f,
                                                     const std::vector<std::vector<uint32_t>>& initial_pivots,
                                                     const AdaptiveOptions& options)
 {
     const std::vector<size_t> patch_order = validate(dims, initial_pivots, options);
     const size_t n = dims.size();
-    if (!f.builtin && !f.cb) throw Error(T4A_GPU_NULL_POINTER, "no function given");
-    Ctx ctx;
-    ctx.dims = &dims;
-    ctx.f = &f;
-    ctx.offset.resize(n);
-    for (size_t s = 0; s < n; ++s) {
-        ctx.offset[s] = ctx.total;
-        ctx.total += dims[s];
-    }
-    if (f.builtin && f.weights.size() != (size_t)f.n_acc * ctx.total)
-        throw Error(T4A_GPU_INVALID_ARGUMENT, "built-in function weight table has the wrong size");
+    if (f.kind() == FnKind::None) throw Error(T4A_GPU_NULL_POINTER, "no function given");
+    if (f.offset.size() != n) throw Error(T4A_GPU_INVALID_ARGUMENT, "the function was built for another number of sites");
     std::unique_ptr<PartitionedTT> result(new PartitionedTT(dims));
     hipStream_t st = result->eng.stream();
     Rng rng(options.tci.has_seed ? options.tci.seed : 0);
@@ -317,7 +290,7 @@ std::unique_ptr<PartitionedTT> adaptive_interpolate(const std::vector<size_t>& d
         pending.pop_front();
         const std::vector<size_t> active = active_positions(n, patch.projector);
         if (active.empty()) { // :75-85
-            const double v = eval_full(ctx, {expand_pivot({}, active, patch.projector, n)})[0];
+            const double v = eval_full(f, {expand_pivot({}, active, patch.projector, n)})[0];
             result->patches.push_back(rank_one_patch(dims, patch.projector, v, st));
             continue;
         }
@@ -325,7 +298,7 @@ std::unique_ptr<PartitionedTT> adaptive_interpolate(const std::vector<size_t>& d
             const size_t d = dims[active[0]];
             std::vector<Pivot> pts;
             for (size_t s = 0; s < d; ++s) pts.push_back(expand_pivot({(uint32_t)s}, active, patch.projector, n));
-            const std::vector<double> vals = eval_full(ctx, pts);
+            const std::vector<double> vals = eval_full(f, pts);
             DevCore core;
             make_host_core(core, 1, d, 1, vals, st);
             result->patches.push_back(embed_patch({&core}, dims, active, patch.projector, st));
@@ -336,7 +309,7 @@ std::unique_ptr<PartitionedTT> adaptive_interpolate(const std::vector<size_t>& d
         {
             std::vector<Pivot> full;
             for (const auto& c : cand) full.push_back(expand_pivot(c, active, patch.projector, n));
-            const std::vector<double> vals = eval_full(ctx, full);
+            const std::vector<double> vals = eval_full(f, full);
             bool all_zero = true;
             for (double v : vals)
                 if (!(std::fabs(v) < ZERO_SAMPLE_THRESHOLD)) all_zero = false;
@@ -349,24 +322,24 @@ std::unique_ptr<PartitionedTT> adaptive_interpolate(const std::vector<size_t>& d
         for (size_t p : active) local_dims.push_back(dims[p]);
         Tci2 tci(local_dims);
         PatchCallback pcb;
-        if (f.builtin) {
+        if (f.builtin()) {
             // restrict the integer weight tables to the active sites; the projected sites contribute a constant that is
             // folded into every entry of the first active site (the accumulators are plain wrapping sums)
             size_t ltotal = 0;
             for (size_t d : local_dims) ltotal += d;
-            std::vector<uint64_t> w((size_t)f.n_acc * ltotal);
-            for (int k = 0; k < f.n_acc; ++k) {
-                const uint64_t* src = f.weights.data() + (size_t)k * ctx.total;
+            std::vector<uint64_t> w((size_t)f.dev.n_acc * ltotal);
+            for (int k = 0; k < f.dev.n_acc; ++k) {
+                const uint64_t* src = f.weights.data() + (size_t)k * f.total;
                 uint64_t constant = 0;
-                for (const auto& kv : patch.projector) constant += src[ctx.offset[kv.first] + kv.second];
+                for (const auto& kv : patch.projector) constant += src[f.offset[kv.first] + kv.second];
                 size_t lo = 0;
                 for (size_t a = 0; a < active.size(); ++a) {
                     for (size_t v = 0; v < local_dims[a]; ++v)
-                        w[(size_t)k * ltotal + lo + v] = src[ctx.offset[active[a]] + v] + (a == 0 ? constant : 0);
+                        w[(size_t)k * ltotal + lo + v] = src[f.offset[active[a]] + v] + (a == 0 ? constant : 0);
                     lo += local_dims[a];
                 }
             }
-            tci.set_builtin(f.fid, f.n_acc, f.params, w.data());
+            tci.set_builtin(f.dev.fid, f.dev.n_acc, f.dev.params, w.data());
         } else {
             pcb.f = &f;
             pcb.active = &active;

@@ -18,16 +18,6 @@ struct AdaptiveOptions { // adaptive_interpolation.rs:27-52
     bool recycle_pivots = false;
 };
 
-// the user function over the FULL index space
-struct FullFunction {
-    bool builtin = false;
-    int fid = 0, n_acc = 0;
-    double params[T4A_FN_MAX_PARAMS] = {0};
-    std::vector<uint64_t> weights; // n_acc * sum(dims)
-    t4a_gpu_batch_eval_fn cb = nullptr;
-    void* ctx = nullptr;
-};
-
 struct SubDomain {
     std::map<size_t, size_t> projector; // site position -> fixed value
     std::vector<DevCore> cores;         // over ALL sites; projected sites carry delta ("copy selector") tensors
@@ -48,7 +38,8 @@ private:
     DevBuf<double> d_vals_;
 };
 
-std::unique_ptr<PartitionedTT> adaptive_interpolate(const std::vector<size_t>& dims, const FullFunction& f,
+// `f`: the user function over the FULL index space (a FnSource built from `dims`)
+std::unique_ptr<PartitionedTT> adaptive_interpolate(const std::vector<size_t>& dims, const FnSource& f,
                                                     const std::vector<std::vector<uint32_t>>& initial_pivots,
                                                     const AdaptiveOptions& options);
 

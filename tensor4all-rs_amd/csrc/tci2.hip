@@ -111,14 +111,6 @@ std::vector<size_t> non_empty_or_first(const std::vector<int>& perm, int rank) /
 
 } // namespace
 
-bool IndexSet::contains(const uint32_t* v) const
-{
-    if (width == 0) return count > 0;
-    for (size_t k = 0; k < count; ++k)
-        if (std::memcmp(at(k), v, width * sizeof(uint32_t)) == 0) return true;
-    return false;
-}
-
 void TCI2Options::validate() const // tensorci2.rs:140-149
 {
     auto nonneg_finite = [](const char* n, double v) {
@@ -132,7 +124,7 @@ void TCI2Options::validate() const // tensorci2.rs:140-149
 }
 
 // =================================================================================================
-Tci2::Tci2(const std::vector<size_t>& dims) : n_(dims.size()), local_dims(dims) // tensorci2.rs:380-404
+Tci2::Tci2(const std::vector<size_t>& dims) : n_(dims.size()), local_dims(dims), fn_(dims) // tensorci2.rs:380-404
 {
     if (dims.size() < 2) throw Error(T4A_GPU_INVALID_ARGUMENT, "local_dims should have at least 2 elements");
     for (size_t s = 0; s < dims.size(); ++s)
@@ -151,12 +143,6 @@ Tci2::Tci2(const std::vector<size_t>& dims) : n_(dims.size()), local_dims(dims) 
         cores[p].r = 0;
     }
     bond_errors.assign(n_ - 1, 0.0);
-    offset_.resize(n_);
-    total_ = 0;
-    for (size_t s = 0; s < n_; ++s) {
-        offset_[s] = total_;
-        total_ += dims[s];
-    }
     last_sweep_shapes.assign(n_ - 1, {0, 0, 0});
     d_maxbits_.reserve(2);
     ev_pi_.init();
@@ -181,18 +167,12 @@ Tci2::~Tci2()
 
 void Tci2::set_builtin(int fid, int n_acc, const double* params, const uint64_t* weights)
 {
-    if (fid < 0 || fid >= T4A_FN_COUNT) throw Error(T4A_GPU_INVALID_ARGUMENT, "unknown built-in function id");
-    if (n_acc < 1 || n_acc > T4A_FN_MAX_ACC) throw Error(T4A_GPU_INVALID_ARGUMENT, "n_acc out of range");
+    fn_.set_builtin(fid, n_acc, params, weights); // (refuses bad arguments before anything changes)
     // after a bond chain the pinned mirror is the master copy of the index sets, with accumulators of the OLD weights laid out
     // for the old n_acc: decode the digit tables first (as set_callback does), so that everything below re-accumulates from
     // digits with the new weights
     sync_digits();
     invalidate_fill_cache();
-    fn_dev_.fid = fid;
-    fn_dev_.n_acc = n_acc;
-    std::memcpy(fn_dev_.params, params, sizeof(double) * T4A_FN_MAX_PARAMS);
-    weights_.assign(weights, weights + (size_t)n_acc * total_);
-    fn_kind_ = FnKind::Builtin;
     source_ = nullptr;
     chain_.weights_valid = false; // (the accumulators in the device tables belong to the old weights)
     chain_.tables_valid = false;
@@ -201,14 +181,14 @@ void Tci2::set_builtin(int fid, int n_acc, const double* params, const uint64_t*
     // handle used to upload them — two copies and a stream synchronisation, ~35 us inside the first iteration of every solve)
     {
         hipStream_t st = eng.stream();
-        chain_.weights.reserve(weights_.size());
+        chain_.weights.reserve(fn_.weights.size());
         chain_.siteinfo.reserve(2 * n_);
         std::vector<int> si(2 * n_);
         for (size_t p = 0; p < n_; ++p) {
             si[p] = (int)local_dims[p];
-            si[n_ + p] = (int)offset_[p];
+            si[n_ + p] = (int)fn_.offset[p];
         }
-        T4A_HIP(hipMemcpyAsync(chain_.weights.get(), weights_.data(), weights_.size() * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        T4A_HIP(hipMemcpyAsync(chain_.weights.get(), fn_.weights.data(), fn_.weights.size() * sizeof(uint64_t), hipMemcpyHostToDevice, st));
         T4A_HIP(hipMemcpyAsync(chain_.siteinfo.get(), si.data(), si.size() * sizeof(int), hipMemcpyHostToDevice, st));
         T4A_HIP(hipStreamSynchronize(st));
         chain_.weights_valid = true;
@@ -217,11 +197,8 @@ void Tci2::set_builtin(int fid, int n_acc, const double* params, const uint64_t*
 
 void Tci2::set_callback(t4a_gpu_batch_eval_fn cb, void* ctx)
 {
-    if (!cb) throw Error(T4A_GPU_NULL_POINTER, "callback is null");
+    fn_.set_callback(cb, ctx); // (refuses a null callback before anything changes)
     sync_digits();
-    cb_ = cb;
-    cb_ctx_ = ctx;
-    fn_kind_ = FnKind::Callback;
     source_ = nullptr;
 }
 
@@ -251,14 +228,7 @@ void Tci2::set_source(MatrixSource* src)
             throw Error(T4A_GPU_INVALID_ARGUMENT, "matrix source: local dimension mismatch at site " + std::to_string(s) + ": the handle has " +
                                                       std::to_string(local_dims[s]) + ", the source " + std::to_string(dims[s]));
     set_callback(&source_thunk, src);
-    fn_kind_ = FnKind::Source;
     source_ = src;
-}
-
-void Tci2::require_fn() const
-{
-    if (fn_kind_ == FnKind::None)
-        throw Error(T4A_GPU_INVALID_ARGUMENT, "no function set: call t4a_gpu_tci2_set_builtin_function or _set_callback");
 }
 
 size_t Tci2::rank() const // tensorci2.rs:600-614
@@ -405,27 +375,12 @@ void Tci2::union_extras(IndexSet& base, const IndexSet& extras)
     }
 }
 
-void Tci2::accumulate(const IndexSet& set, size_t first_site, std::vector<uint64_t>& acc) const
-{
-    const int K = fn_dev_.n_acc;
-    acc.assign(set.count * (size_t)K, 0);
-    for (size_t e = 0; e < set.count; ++e) {
-        const uint32_t* v = set.at(e);
-        for (int k = 0; k < K; ++k) {
-            uint64_t a = 0;
-            const uint64_t* w = weights_.data() + (size_t)k * total_;
-            for (size_t s = 0; s < set.width; ++s) a += w[offset_[first_site + s] + v[s]];
-            acc[e * K + k] = a;
-        }
-    }
-}
-
 // Accumulators of both index sets -> pinned arena -> device (one asynchronous copy on the main stream).
 void Tci2::stage_accumulators(const IndexSet& a, size_t a0, const IndexSet& b, size_t b0, const std::vector<uint64_t>* acc_a,
                               const std::vector<uint64_t>* acc_b, const uint64_t** d_ra, const uint64_t** d_rb, bool in_place)
 {
     hipStream_t st = eng.stream();
-    const size_t K = (size_t)fn_dev_.n_acc;
+    const size_t K = (size_t)fn_.dev.n_acc;
     std::vector<uint64_t> ra_own, rb_own;
     if (!acc_a) accumulate(a, a0, ra_own);
     if (!acc_b) accumulate(b, b0, rb_own);
@@ -461,18 +416,18 @@ void Tci2::eval_matrix(const IndexSet& a, size_t a0, const IndexSet& b, size_t b
                        unsigned long long* d_maxbits, const std::vector<uint64_t>* acc_a,
                        const std::vector<uint64_t>* acc_b)
 {
-    require_fn();
+    fn_.require("tci2");
     const size_t na = a.count, nb = b.count;
     if (na == 0 || nb == 0) return;
     if (a.width + b.width != n_) throw Error(T4A_GPU_INTERNAL_ERROR, "eval_matrix: index widths do not cover all sites");
     hipStream_t st = eng.stream();
     eng.prof.v[11] += (double)na * (double)nb;
-    if (fn_kind_ == FnKind::Builtin) {
+    if (fn_.builtin()) {
         const uint64_t *d_ra = nullptr, *d_rb = nullptr;
         stage_accumulators(a, a0, b, b0, acc_a, acc_b, &d_ra, &d_rb);
-        pi_eval_launch(fn_dev_, d_ra, (int)na, d_rb, (int)nb, d_out, (int)na, false, d_maxbits, st);
+        pi_eval_launch(fn_.dev, d_ra, (int)na, d_rb, (int)nb, d_out, (int)na, false, d_maxbits, st);
         T4A_HIP(hipGetLastError());
-    } else if (fn_kind_ == FnKind::Source && !pi_shard.active()) {
+    } else if (source_ && !pi_shard.active()) {
         // device matrix source: the set that starts at site 0 holds the rows of the source's matrix; when that is `b`, out (na x nb,
         // ia fastest) is the source's matrix transposed
         const bool transposed = a0 != 0;
@@ -492,7 +447,7 @@ void Tci2::eval_matrix(const IndexSet& a, size_t a0, const IndexSet& b, size_t b
         source_stats[2] += npts;
         if (pi_shard.active()) {
             // column blocks over the ranks of the process group + one all-gather (pishard.hpp)
-            pi_shard_evaluate(pi_shard, cb_, cb_ctx_, n_, a.d.data(), a.width, a0, na, b.d.data(), b.width, b0, nb, vals);
+            pi_shard_evaluate(pi_shard, fn_.cb, fn_.cb_ctx, n_, a.d.data(), a.width, a0, na, b.d.data(), b.width, b0, nb, vals);
         } else {
             // the index buffer of the callback: grow-only and filled by a few host threads (round 5: measured on the native callback of
             // tools/bench_components.py — the backend's share of a cfg3 sweep through a callback was 0.27 s, most of it this buffer)
@@ -524,15 +479,12 @@ void Tci2::eval_matrix(const IndexSet& a, size_t a0, const IndexSet& b, size_t b
             // docs/design/adaptive-tci-interpolation.md:9-11), so only for callbacks that are thread safe.  Same points, same values.
             const size_t cthr = (callback_threads <= 1 || npts < ((size_t)1 << 14)) ? 1 : std::min<size_t>(callback_threads, npts >> 12);
             if (cthr <= 1) {
-                const int64_t got = cb_(cb_ctx_, idx, n_, npts, vals);
-                if (got < 0 || (size_t)got != npts)
-                    throw Error(T4A_GPU_CALLBACK_ERROR, "batch callback returned " + std::to_string(got) + " values for " +
-                                                            std::to_string(npts) + " requested entries");
+                fn_.call(idx, n_, npts, vals, "batch callback", "requested entries");
             } else {
                 std::vector<int64_t> got(cthr, 0);
                 auto call = [&](size_t t) {
                     const size_t p0 = npts * t / cthr, p1 = npts * (t + 1) / cthr;
-                    got[t] = cb_(cb_ctx_, idx + p0 * n_, n_, p1 - p0, vals + p0) - (int64_t)(p1 - p0);
+                    got[t] = fn_.cb(fn_.cb_ctx, idx + p0 * n_, n_, p1 - p0, vals + p0) - (int64_t)(p1 - p0);
                 };
                 std::vector<std::thread> pool;
                 for (size_t t = 1; t < cthr; ++t) pool.emplace_back(call, t);
@@ -556,24 +508,14 @@ void Tci2::eval_matrix(const IndexSet& a, size_t a0, const IndexSet& b, size_t b
 
 std::vector<double> Tci2::eval_points_host(const std::vector<uint32_t>& idx, size_t n_pts)
 {
-    require_fn();
+    fn_.require("tci2");
     std::vector<double> out(n_pts);
     if (n_pts == 0) return out;
-    if (fn_kind_ == FnKind::Builtin) {
-        for (size_t p = 0; p < n_pts; ++p) {
-            uint64_t acc[T4A_FN_MAX_ACC] = {0, 0, 0, 0};
-            for (int k = 0; k < fn_dev_.n_acc; ++k) {
-                const uint64_t* w = weights_.data() + (size_t)k * total_;
-                for (size_t s = 0; s < n_; ++s) acc[k] += w[offset_[s] + idx[p * n_ + s]];
-            }
-            out[p] = t4a_fn_value(fn_dev_.fid, acc, fn_dev_.params);
-        }
+    if (fn_.builtin()) {
+        fn_.host_values(idx.data(), n_pts, out.data());
     } else {
         source_stats[2] += n_pts;
-        const int64_t got = cb_(cb_ctx_, idx.data(), n_, n_pts, out.data());
-        if (got < 0 || (size_t)got != n_pts)
-            throw Error(T4A_GPU_CALLBACK_ERROR, "batch callback returned " + std::to_string(got) + " values for " +
-                                                    std::to_string(n_pts) + " requested entries");
+        fn_.call(idx.data(), n_, n_pts, out.data(), "batch callback", "requested entries");
     }
     return out;
 }
@@ -587,7 +529,7 @@ void Tci2::build_side(size_t bond, bool cols, const IndexSet& extra, SidePrep& o
     out.set = cols ? kronecker_j(bond + 1) : kronecker_i(bond);
     union_extras(out.set, extra);
     out.acc.clear();
-    if (fn_kind_ == FnKind::Builtin) accumulate(out.set, cols ? bond + 1 : 0, out.acc);
+    if (fn_.builtin()) accumulate(out.set, cols ? bond + 1 : 0, out.acc);
     out.valid = true;
 }
 
@@ -599,7 +541,7 @@ void Tci2::invalidate_fill_cache()
 // Accumulators fill_site_tensors needs for site b (tensorci2.rs:1101-1145): J_b, kron(I_b, d_b) and I_{b+1}.
 void Tci2::prepare_fill_site(size_t b)
 {
-    if (fn_kind_ != FnKind::Builtin || b >= n_) return;
+    if (!fn_.builtin() || b >= n_) return;
     if (chain_.digits_stale) { // after a bond chain the accumulators are in the pinned mirror of the device tables: no digits needed
         prepare_fill_site_from_mirror(b);
         return;
@@ -623,10 +565,10 @@ LuciResult Tci2::luci_on_sets(const IndexSet& is, const IndexSet& js, const RrLU
 {
     const size_t M = is.count, N = js.count;
     hipStream_t st = eng.stream();
-    if (fn_kind_ == FnKind::Builtin && M > 0 && N > 0) {
+    if (fn_.builtin() && M > 0 && N > 0) {
         // built-in functor: only the accumulators travel; the rrLU kernel evaluates Pi into its registers
         FusedPi fp;
-        fp.fn = fn_dev_;
+        fp.fn = fn_.dev;
         // small bonds (the single-workgroup plan with the fused candidate-matrix build takes them): the kernel reads the few
         // hundred bytes of accumulators straight from the pinned arena — no staging kernel in front of a 10 us factorisation
         fp.host_resident = M * N <= (size_t)64 * 64;
@@ -666,36 +608,31 @@ LuciResult Tci2::luci_on_sets(const IndexSet& is, const IndexSet& js, const RrLU
 // block-rook kernel asks for full rows / columns of Pi, which are evaluated on demand (LazyPiEvaluator, :2035-2142).
 LuciResult Tci2::rook_on_sets(const IndexSet& is, const IndexSet& js, const RrLUOptions& o)
 {
-    require_fn();
+    fn_.require("tci2");
     const size_t M = is.count, N = js.count;
     hipStream_t st = eng.stream();
     RookSource src;
     src.M = (int)M;
     src.N = (int)N;
-    if (fn_kind_ == FnKind::Builtin) {
-        const size_t K = (size_t)fn_dev_.n_acc;
+    if (fn_.builtin()) {
+        const size_t K = (size_t)fn_.dev.n_acc;
         std::vector<uint64_t> ra, rb;
         accumulate(is, 0, ra);
         accumulate(js, is.width, rb);
-        d_rowacc_.reserve(ra.size() + rb.size());
         // (one copy out of pinned memory: two copies out of pageable vectors and a synchronisation cost ~60 us per bond on small problems;
         // the staging buffer is free again: every rook search ends with a stream synchronisation)
-        h_rookacc_.reserve(ra.size() + rb.size());
-        std::memcpy(h_rookacc_.get(), ra.data(), ra.size() * sizeof(uint64_t));
-        std::memcpy(h_rookacc_.get() + ra.size(), rb.data(), rb.size() * sizeof(uint64_t));
-        T4A_HIP(hipMemcpyAsync(d_rowacc_.get(), h_rookacc_.get(), (ra.size() + rb.size()) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-        const uint64_t* d_ra = d_rowacc_.get();
-        const uint64_t* d_rb = d_rowacc_.get() + ra.size();
+        const auto d_acc = stage_accumulator_pair(ra, rb, h_rookacc_, d_rowacc_, st);
+        const uint64_t *d_ra = d_acc.first, *d_rb = d_acc.second;
         src.column = [=](int c, double* out) {
-            pi_eval_launch(fn_dev_, d_ra, (int)M, d_rb + (size_t)c * K, 1, out, (int)M, false, nullptr, st);
+            pi_eval_launch(fn_.dev, d_ra, (int)M, d_rb + (size_t)c * K, 1, out, (int)M, false, nullptr, st);
         };
         src.row = [=](int r, double* out) {
-            pi_eval_launch(fn_dev_, d_ra + (size_t)r * K, 1, d_rb, (int)N, out, 1, false, nullptr, st);
+            pi_eval_launch(fn_.dev, d_ra + (size_t)r * K, 1, d_rb, (int)N, out, 1, false, nullptr, st);
         };
         // (a built-in functor costs nothing to evaluate: the search runs device-resident on the materialised matrix, rook.hip)
         static const bool host_driven = std::getenv("T4A_ROOK_HOST") != nullptr; // (A/B and parity of the two search drivers)
         if (!host_driven)
-            src.full = [=](double* out) { pi_eval_launch(fn_dev_, d_ra, (int)M, d_rb, (int)N, out, (int)M, false, nullptr, st); };
+            src.full = [=](double* out) { pi_eval_launch(fn_.dev, d_ra, (int)M, d_rb, (int)N, out, (int)M, false, nullptr, st); };
     } else {
         auto eval_points = [this, st, &is, &js](size_t r0, size_t nr, size_t c0, size_t nc, double* out) {
             const size_t npts = nr * nc;
@@ -708,10 +645,7 @@ LuciResult Tci2::rook_on_sets(const IndexSet& is, const IndexSet& js, const RrLU
                 }
             std::vector<double> vals(npts);
             source_stats[2] += npts;
-            const int64_t got = cb_(cb_ctx_, idx.data(), n_, npts, vals.data());
-            if (got < 0 || (size_t)got != npts)
-                throw Error(T4A_GPU_CALLBACK_ERROR, "batch callback returned " + std::to_string(got) + " values for " +
-                                                        std::to_string(npts) + " requested entries");
+            fn_.call(idx.data(), n_, npts, vals.data(), "batch callback", "requested entries");
             T4A_HIP(hipMemcpyAsync(out, vals.data(), npts * sizeof(double), hipMemcpyHostToDevice, st));
             T4A_HIP(hipStreamSynchronize(st));
         };
@@ -793,7 +727,7 @@ void Tci2::update_pivots(size_t b, bool left_orthogonal, const TCI2Options& opti
     }
     const IndexSet& i_comb = have_rows ? ready.set : i_own;
     const IndexSet& j_comb = have_cols ? ready.set : j_own;
-    const bool acc_ready = ready.valid && fn_kind_ == FnKind::Builtin;
+    const bool acc_ready = ready.valid && fn_.builtin();
     if (i_comb.count == 0 || j_comb.count == 0) return;
     if (prefetch_.wanted || prefetch_.fill_site >= 0) {
         // host work that does not depend on this bond: the independent side of the NEXT bond and the fill
@@ -863,7 +797,7 @@ void Tci2::update_pivots(size_t b, bool left_orthogonal, const TCI2Options& opti
 void Tci2::sweep2site(bool forward, const TCI2Options& options)
 {
     options.validate();
-    require_fn();
+    fn_.require("tci2");
     fill_wait();
     invalidate_site_tensors();
     flush_pivot_errors();
@@ -944,7 +878,7 @@ void Tci2::sweep1site(bool forward, double rel_tol, double abs_tol, size_t max_b
     if (!(rel_tol >= 0.0) || !std::isfinite(rel_tol)) throw Error(T4A_GPU_INVALID_ARGUMENT, "rel_tol must be finite and non-negative");
     if (!(abs_tol >= 0.0) || !std::isfinite(abs_tol)) throw Error(T4A_GPU_INVALID_ARGUMENT, "abs_tol must be finite and non-negative");
     if (max_bond_dim == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "max_bond_dim must be positive");
-    require_fn();
+    fn_.require("tci2");
     fill_wait();
     flush_pivot_errors();
     invalidate_site_tensors();
@@ -1122,7 +1056,7 @@ void Tci2::fill_wait()
 
 void Tci2::fill_site_tensors_impl(bool async)
 {
-    require_fn();
+    fn_.require("tci2");
     // accumulators built ahead are only trusted when optimize() vouches for them (same half-sweep, sets final)
     const bool trust_cache = fill_cache_trusted_;
     fill_cache_trusted_ = false;
@@ -1137,10 +1071,10 @@ void Tci2::fill_site_tensors_impl(bool async)
     };
     auto hpf_t = hpf_t0;
     if (!trust_cache) invalidate_fill_cache();
-    if (fn_kind_ != FnKind::Builtin) sync_digits();
+    if (!fn_.builtin()) sync_digits();
     fill_wait(); // the scratch arenas of the previous fill are free again
     if (!fill_stream_) fill_stream_ = pool::stream_get(2); // lowest priority, recycled through the process-wide cache
-    const bool builtin = fn_kind_ == FnKind::Builtin;
+    const bool builtin = fn_.builtin();
     static const bool sync_fill = std::getenv("T4A_SYNC_FILL") != nullptr; // measurement switch: no overlap at all
     if (!builtin || sync_fill) async = false;
     std::vector<std::function<void()>> ops; // the stream operations of this fill, in order (no event records)
@@ -1150,7 +1084,7 @@ void Tci2::fill_site_tensors_impl(bool async)
     // everything of this fill is ordered after the work already enqueued on the main stream (the per-bond path writes site
     // tensors there).  After a bond chain nothing on the main stream concerns the fill — and the NEXT chain may already be
     // running on it: no wait then.
-    const bool no_main_sync = fill_no_main_sync_ && fn_kind_ == FnKind::Builtin;
+    const bool no_main_sync = fill_no_main_sync_ && fn_.builtin();
     fill_no_main_sync_ = false;
     if (!no_main_sync) T4A_HIP(hipStreamSynchronize(eng.stream()));
     hipStream_t st = fill_stream_;
@@ -1325,7 +1259,7 @@ void Tci2::fill_site_tensors_impl(bool async)
         if (j.nj > (size_t)FILL_SMALL_MAX_N || j.ni > (size_t)FILL_SMALL_MAX_RHS) small_fill = false;
     if (builtin) {
         std::vector<uint64_t> acc_all;
-        const size_t Kacc = (size_t)fn_dev_.n_acc;
+        const size_t Kacc = (size_t)fn_.dev.n_acc;
         for (SiteJob& j : jobs) {
             const bool cached = fill_cache_.size() == n_ && fill_cache_[j.b].valid &&
                                 fill_cache_[j.b].accJ.size() == j.nj * Kacc && fill_cache_[j.b].accK.size() == j.ni * Kacc &&
@@ -1400,7 +1334,7 @@ void Tci2::fill_site_tensors_impl(bool async)
         std::memcpy(hb + off_pk, packs.data(), bytes_pk);
         hpf_mark(7, hpf_t);
         {
-            const FnDevice fn = fn_dev_;
+            const FnDevice fn = fn_.dev;
             const PiJob* dj = reinterpret_cast<const PiJob*>(db + off_pi);
             const int npi = (int)pis.size();
             sg((uint64_t)(uintptr_t)db);
@@ -1472,7 +1406,7 @@ void Tci2::fill_site_tensors_impl(bool async)
         sg((uint64_t)(uintptr_t)d_packs);
         sg((uint64_t)(uintptr_t)d_info);
         sg((uint64_t)(uintptr_t)hinfo);
-        const FnDevice fn = fn_dev_;
+        const FnDevice fn = fn_.dev;
         const int n_site_jobs = (int)jobs.size(), last_site = jobs.back().last ? 1 : 0;
         const bool small = small_fill;
         sg((uint64_t)(uintptr_t)d_pis);
@@ -1793,7 +1727,7 @@ void Tci2::opt_begin(OptRun& r)
     const TCI2Options& options = r.options;
 
     options.validate();
-    require_fn();
+    fn_.require("tci2");
     if (rank() == 0)
         throw Error(T4A_GPU_INVALID_ARGUMENT, "TensorCI2 state must contain at least one pivot before optimization");
     // pipelined mode (keep_site_tensors): a fill left in flight by the previous call keeps running beside the bond
@@ -1813,7 +1747,7 @@ void Tci2::opt_begin(OptRun& r)
     if (small_engine_run(r) && r.small_complete) return;
     // bounded rank, built-in functor: site tensors and fill workspaces get their final size now (a buffer that grows goes
     // through the process-wide cache, which waits for the whole device: once per iteration and buffer while ranks grow)
-    if (fn_kind_ == FnKind::Builtin && options.max_bond_dim != 0 && options.max_bond_dim <= 1024) {
+    if (fn_.builtin() && options.max_bond_dim != 0 && options.max_bond_dim <= 1024) {
         const size_t chi = options.max_bond_dim;
         // what a bond can reach at all: min(chi, product of the local dimensions on either side) — the ends of a train stay small
         std::vector<size_t> lb(n_ + 1, 1), rb(n_ + 1, 1);
@@ -1844,7 +1778,7 @@ void Tci2::opt_begin(OptRun& r)
         size_t acc_words = 0;
         for (size_t b = 0; b < n_; ++b) {
             if (shard_world > 1 && (b % shard_world) != shard_rank) continue;
-            acc_words += chi * (2 + local_dims[b]) * (size_t)fn_dev_.n_acc;
+            acc_words += chi * (2 + local_dims[b]) * (size_t)fn_.dev.n_acc;
         }
         const size_t desc_bytes = n_ * (2 * sizeof(PiJob) + sizeof(LuProblem) + 2 * sizeof(TrsmProblem) + 64) + 256;
         h_fillacc_.reserve(acc_words + desc_bytes / 8 + 64);
@@ -1908,7 +1842,7 @@ bool Tci2::opt_iter_start(OptRun& r, bool defer_launch)
             prep_.valid = false;
             invalidate_fill_cache();
         }
-        const bool fill_ahead = fn_kind_ == FnKind::Builtin && options.pivot_search == 0;
+        const bool fill_ahead = fn_.builtin() && options.pivot_search == 0;
         // built-in functor, full pivot search: the whole half-sweep is enqueued at once (tci2_chain.hip) ...
         r.is_forward = is_forward;
         r.ext_idx = ext_idx;
@@ -2191,7 +2125,7 @@ void Tci2::fill_site_tensors_group(const std::vector<Tci2*>& hs)
 void Tci2::crossinterpolate2(std::vector<std::vector<uint32_t>> pivots, const TCI2Options& options)
 {
     options.validate();
-    require_fn();
+    fn_.require("tci2");
     if (pivots.empty()) pivots.push_back(std::vector<uint32_t>(n_, 0));
     add_global_pivots(pivots);
     std::vector<uint32_t> flat;

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "engine.hpp"
+#include "fnsource.hpp"
 #include "matrix_source.hpp"
 #include "stdrng.hpp"
 #include "pishard.hpp"
@@ -15,25 +16,6 @@
 #include "tt.hpp"
 
 namespace t4a {
-
-// A list of multi-indices of fixed width, flat: entry k = d[k*width .. (k+1)*width)
-struct IndexSet {
-    size_t width = 0;
-    size_t count = 0;
-    std::vector<uint32_t> d;
-    const uint32_t* at(size_t k) const { return d.data() + k * width; }
-    void push(const uint32_t* v)
-    {
-        d.insert(d.end(), v, v + width);
-        ++count;
-    }
-    void clear()
-    {
-        d.clear();
-        count = 0;
-    }
-    bool contains(const uint32_t* v) const;
-};
 
 struct TCI2Options { // tensorci2.rs:73-170
     double tolerance = 1e-8;
@@ -204,21 +186,15 @@ public:
     Engine eng;
 
 private:
-    enum class FnKind { None, Builtin, Callback, Source }; // Source: a Callback whose whole matrices are filled by source_
-    FnKind fn_kind_ = FnKind::None;
-    MatrixSource* source_ = nullptr;
-    FnDevice fn_dev_{};
-    std::vector<uint64_t> weights_; // n_acc * total
-    std::vector<size_t> offset_;
-    size_t total_ = 0;
-    t4a_gpu_batch_eval_fn cb_ = nullptr;
-    void* cb_ctx_ = nullptr;
+    FnSource fn_;                   // (fnsource.hpp)
+    MatrixSource* source_ = nullptr; // set: fn_ is the source's point evaluator as a callback, whole matrices are filled by the source
 
     // index helpers
     IndexSet kronecker_i(size_t p) const;
     IndexSet kronecker_j(size_t p) const;
     static void union_extras(IndexSet& base, const IndexSet& extras);
-    void accumulate(const IndexSet& set, size_t first_site, std::vector<uint64_t>& acc) const;
+    // accumulators of a set whose digits live on the sites from first_site on
+    void accumulate(const IndexSet& set, size_t first_site, std::vector<uint64_t>& acc) const { fn_.accumulate(set, fn_.offset.data() + first_site, acc); }
 
     // Evaluate f into a device matrix: out[ia + a.count*ib] = f(index with a's digits at sites
     // [a0, a0+a.width) and b's digits at [b0, b0+b.width)).  If d_maxbits != nullptr the kernel also
@@ -230,7 +206,6 @@ private:
     void stage_accumulators(const IndexSet& a, size_t a0, const IndexSet& b, size_t b0, const std::vector<uint64_t>* acc_a,
                             const std::vector<uint64_t>* acc_b, const uint64_t** d_ra, const uint64_t** d_rb, bool in_place = false);
     std::vector<double> eval_points_host(const std::vector<uint32_t>& idx, size_t n_pts);
-    void require_fn() const;
 
     struct BondOut {
         LuciResult lu;

@@ -51,7 +51,7 @@ thread_local double g_chain_wait_seconds = 0.0; // time chain_finish spent waiti
 bool Tci2::chain_usable(const TCI2Options& options) const
 {
     static const bool off = std::getenv("T4A_NO_CHAIN") != nullptr;
-    if (off || !chain_enabled || fn_kind_ != FnKind::Builtin || options.pivot_search != 0) return false;
+    if (off || !chain_enabled || !fn_.builtin() || options.pivot_search != 0) return false;
     long double space = 1.0L;
     for (size_t d : local_dims) space *= (long double)d;
     if (space >= 9.0e18L) return false; // codes are 63-bit mixed-radix numbers
@@ -148,7 +148,7 @@ void Tci2::hist_digits(HistEntry& e)
 
 void Tci2::chain_layout(size_t cap)
 {
-    const int K = fn_dev_.n_acc;
+    const int K = fn_.dev.n_acc;
     if (cap <= chain_.cap && K == chain_.n_acc && chain_.tab.get()) return;
     sync_digits(); // (the mirror is about to move: the digit tables take over as the master copy)
     cap = std::max(cap, chain_.cap);
@@ -237,7 +237,7 @@ void Tci2::prepare_fill_site_from_mirror(size_t b)
     for (size_t i = 0; i < ni; ++i)
         for (size_t s = 0; s < d; ++s)
             for (size_t k = 0; k < K; ++k)
-                f.accK[(i * d + s) * K + k] = mi.acc[(b * cap + i) * K + k] + weights_[k * total_ + offset_[b] + s];
+                f.accK[(i * d + s) * K + k] = mi.acc[(b * cap + i) * K + k] + fn_.weights[k * fn_.total + fn_.offset[b] + s];
     if (b + 1 < n_)
         f.accI.assign(mi.acc + (b + 1) * cap * K, mi.acc + (b + 1) * cap * K + i_set[b + 1].count * K);
     else
@@ -253,7 +253,7 @@ bool Tci2::chain_enqueue(bool forward, const TCI2Options& options, long ext_idx,
         return false;
     }
     const size_t nb = n_ - 1;
-    const size_t K = (size_t)fn_dev_.n_acc;
+    const size_t K = (size_t)fn_.dev.n_acc;
     const size_t chi = options.max_bond_dim_or_max();
     hipStream_t st = eng.stream();
     const bool one = chain_.one_site;
@@ -339,14 +339,14 @@ bool Tci2::chain_enqueue(bool forward, const TCI2Options& options, long ext_idx,
     chain_layout(round_up_sz(need_cap, 64));
     const size_t cap = chain_.cap;
     if (!chain_.weights_valid) {
-        chain_.weights.reserve(weights_.size());
+        chain_.weights.reserve(fn_.weights.size());
         chain_.siteinfo.reserve(2 * n_);
         std::vector<int> si(2 * n_);
         for (size_t p = 0; p < n_; ++p) {
             si[p] = (int)local_dims[p];
-            si[n_ + p] = (int)offset_[p];
+            si[n_ + p] = (int)fn_.offset[p];
         }
-        T4A_HIP(hipMemcpyAsync(chain_.weights.get(), weights_.data(), weights_.size() * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        T4A_HIP(hipMemcpyAsync(chain_.weights.get(), fn_.weights.data(), fn_.weights.size() * sizeof(uint64_t), hipMemcpyHostToDevice, st));
         T4A_HIP(hipMemcpyAsync(chain_.siteinfo.get(), si.data(), si.size() * sizeof(int), hipMemcpyHostToDevice, st));
         T4A_HIP(hipStreamSynchronize(st));
         chain_.weights_valid = true;
@@ -426,7 +426,7 @@ bool Tci2::chain_enqueue(bool forward, const TCI2Options& options, long ext_idx,
     c.cap = (int)cap;
     c.K = (int)K;
     c.w = chain_.weights.get();
-    c.total = (int)total_;
+    c.total = (int)fn_.total;
     c.ldim = chain_.siteinfo.get();
     c.woff = chain_.siteinfo.get() + n_;
     c.forward = forward ? 1 : 0;
@@ -547,7 +547,7 @@ void Tci2::chain_launch()
             }
             chain_.walked = true;
             for (size_t k = 0; k < nb; ++k) tokens[order[k]] = w.token_base + (unsigned)k;
-            chain_walk_launch(c, fn_dev_, w, (int)walk_cols, st);
+            chain_walk_launch(c, fn_.dev, w, (int)walk_cols, st);
             ++chain_stats_ext[0];
         }
         static const bool want_prep_dbg = std::getenv("T4A_PREP_DEBUG") != nullptr; // phase times of the preparation kernels of this chain
@@ -584,7 +584,7 @@ void Tci2::chain_launch()
             }
             chain_prep_launch(c, pa, st);
             // nobody speculated on this bond (first bond, or the previous launch was a single workgroup): evaluate it now
-            if (!fused && !spec_here) chain_pi_launch(c, fn_dev_, (int)b, (int)dep_ub[b], (int)ind_ub[b], chain_.pi.get(), st);
+            if (!fused && !spec_here) chain_pi_launch(c, fn_.dev, (int)b, (int)dep_ub[b], (int)ind_ub[b], chain_.pi.get(), st);
             // the candidate matrix of the NEXT bond rides on this bond's launch when that is a single-XCD launch
             XcdSpecArgs sp;
             std::memset(&sp, 0, sizeof(sp));
@@ -597,20 +597,20 @@ void Tci2::chain_launch()
                     const size_t hsite = forward ? nx + 1 : nx;
                     sp.out = chain_.spec[(k + 1) & 1].get();
                     sp.dep_acc = c.dep_acc;
-                    sp.w_site = c.w + offset_[site];
+                    sp.w_site = c.w + fn_.offset[site];
                     sp.ext_acc = H.acc + hsite * cap * K;
                     sp.ext_cnt = use_extras ? H.cnt + hsite : nullptr;
                     sp.ind_acc = c.ind_acc + nx * ind_cap * K;
                     sp.ind_cnt = c.ind_cnt + nx;
                     sp.tile_counter = tile_counters + nx;
-                    sp.total = (int)total_;
+                    sp.total = (int)fn_.total;
                     sp.d = (int)local_dims[site];
-                    sp.fn = fn_dev_;
+                    sp.fn = fn_.dev;
                     spec_pending = true;
                 }
             }
             FusedPi fp;
-            fp.fn = fn_dev_;
+            fp.fn = fn_.dev;
             fp.d_rowacc = c.dep_acc;
             fp.d_colacc = c.ind_acc + b * ind_cap * K;
             fp.host_resident = false;
@@ -669,7 +669,7 @@ void Tci2::chain_launch()
             const size_t entries = a_ub * local_dims[last] * std::max<size_t>(j_set[last].count, 1);
             if (entries <= ((size_t)1 << 24)) {
                 cores[last].buf.reserve(entries);
-                chain_last_core_launch(c, fn_dev_, cores[last].buf.get(), (int)entries, st);
+                chain_last_core_launch(c, fn_.dev, cores[last].buf.get(), (int)entries, st);
                 chain_.last_core_launched = true;
             }
         }
@@ -747,7 +747,7 @@ void Tci2::chain_group_launch(const std::vector<Tci2*>& hs)
             h->eng.chain_group_reserve(gplans, reserve_words, st);
             ChainGroupSlot& slot = lead->chain_.hgslots.get()[i];
             slot.c = h->chain_.common;
-            slot.fn = h->fn_dev_;
+            slot.fn = h->fn_.dev;
             slot.pi = h->chain_.pi.get();
             g_chains_inflight.fetch_add(1);
             counted[i] = 1;

@@ -24,7 +24,7 @@ bool Tci2::small_engine_eligible(const TCI2Options& options) const
 {
     static const bool no_chain = std::getenv("T4A_NO_CHAIN") != nullptr; // (the documented "everything bond by bond" fallback switches the engine off too)
     if (no_chain || !small_enabled || !chain_enabled || chain_verify || chain_event_timing) return false;
-    if (fn_kind_ != FnKind::Builtin || fn_dev_.n_acc > 2 || (options.pivot_search != 0 && options.pivot_search != 1)) return false;
+    if (!fn_.builtin() || fn_.dev.n_acc > 2 || (options.pivot_search != 0 && options.pivot_search != 1)) return false;
     if (options.pivot_search == 1) {
         static const bool rook_host = std::getenv("T4A_ROOK_HOST") != nullptr; // (A/B of the search drivers: rook.hip's host-driven loop is asked for)
         if (rook_host) return false;
@@ -32,7 +32,7 @@ bool Tci2::small_engine_eligible(const TCI2Options& options) const
     if (!(options.nsearch == 0 || options.max_nglobal_pivot == 0)) return false;
     if (!history.empty() || shard_world != 1 || keep_site_tensors || pi_shard.active()) return false;
     if (n_ > (size_t)SMALL_MAX_SITES || options.max_iter > (size_t)SMALL_MAX_ITER || options.ncheck_history > (size_t)SMALL_MAX_ITER) return false;
-    if (small_lds_bytes((int)n_, fn_dev_.n_acc, (int)total_) == 0) return false;
+    if (small_lds_bytes((int)n_, fn_.dev.n_acc, (int)fn_.total) == 0) return false;
     long double space = 1.0L;
     for (size_t d : local_dims) {
         if (d > (size_t)SMALL_TILE) return false;
@@ -53,7 +53,7 @@ bool Tci2::small_engine_run(OptRun& r)
         return false;
     }
     sync_digits();
-    const int n = (int)n_, K = fn_dev_.n_acc, total = (int)total_;
+    const int n = (int)n_, K = fn_.dev.n_acc, total = (int)fn_.total;
     size_t cap_in = 1;
     for (size_t p = 0; p < n_; ++p) cap_in = std::max(cap_in, std::max(i_set[p].count, j_set[p].count));
     // ---- input block ----
@@ -61,7 +61,7 @@ bool Tci2::small_engine_run(OptRun& r)
     SmallHeader& h = a.h;
     h.n = n;
     h.K = K;
-    h.fid = fn_dev_.fid;
+    h.fid = fn_.dev.fid;
     h.total = total;
     h.max_iter = (int)options.max_iter;
     h.ncheck = (int)options.ncheck_history;
@@ -72,7 +72,7 @@ bool Tci2::small_engine_run(OptRun& r)
     h.tile_max = small_tile_max;
     h.tolerance = options.tolerance;
     h.max_sample_value = max_sample_value;
-    std::memcpy(h.params, fn_dev_.params, sizeof(h.params));
+    std::memcpy(h.params, fn_.dev.params, sizeof(h.params));
     size_t o = 0;
     auto take = [&](size_t bytes) {
         const size_t at = o;
@@ -81,7 +81,7 @@ bool Tci2::small_engine_run(OptRun& r)
     };
     h.o_ldim = (int)take(sizeof(int) * n_);
     h.o_woff = (int)take(sizeof(int) * n_);
-    h.o_w = (int)take(sizeof(uint64_t) * (size_t)K * total_);
+    h.o_w = (int)take(sizeof(uint64_t) * (size_t)K * fn_.total);
     h.o_cnt = (int)take(sizeof(int) * 2 * n_);
     h.o_code = (int)take(sizeof(uint64_t) * 2 * n_ * cap_in);
     h.o_acc = (int)take(sizeof(uint64_t) * 2 * n_ * cap_in * (size_t)K);
@@ -94,9 +94,9 @@ bool Tci2::small_engine_run(OptRun& r)
         int* woff = reinterpret_cast<int*>(in + h.o_woff);
         for (size_t p = 0; p < n_; ++p) {
             ldim[p] = (int)local_dims[p];
-            woff[p] = (int)offset_[p];
+            woff[p] = (int)fn_.offset[p];
         }
-        std::memcpy(in + h.o_w, weights_.data(), sizeof(uint64_t) * (size_t)K * total_);
+        std::memcpy(in + h.o_w, fn_.weights.data(), sizeof(uint64_t) * (size_t)K * fn_.total);
         int* cnt = reinterpret_cast<int*>(in + h.o_cnt);
         uint64_t* code = reinterpret_cast<uint64_t*>(in + h.o_code);
         uint64_t* acc = reinterpret_cast<uint64_t*>(in + h.o_acc);

@@ -136,7 +136,7 @@ void TreeTciOptions::validate() const // optimize.rs:49-76
 }
 
 // ================================================================================================= state.rs
-TreeTci::TreeTci(const std::vector<size_t>& dims, const TreeGraph& g) : local_dims(dims), graph(g) // :66-103
+TreeTci::TreeTci(const std::vector<size_t>& dims, const TreeGraph& g) : local_dims(dims), graph(g), fn_(dims) // :66-103
 {
     if (!(dims.size() > 1)) throw Error(T4A_GPU_INVALID_ARGUMENT, "local_dims should have at least 2 elements");
     if (dims.size() != g.n_sites())
@@ -148,38 +148,7 @@ TreeTci::TreeTci(const std::vector<size_t>& dims, const TreeGraph& g) : local_di
         if (dims[s] > 0xFFFFFFFFull) throw Error(T4A_GPU_INVALID_ARGUMENT, "local dimension too large");
     }
     for (const TreeEdge& e : g.edges()) bond_errors[e] = 0.0;
-    offset_.resize(dims.size());
-    total_ = 0;
-    for (size_t s = 0; s < dims.size(); ++s) {
-        offset_[s] = total_;
-        total_ += dims[s];
-    }
     d_maxbits_.reserve(2);
-}
-
-void TreeTci::set_builtin(int fid, int n_acc, const double* params, const uint64_t* weights)
-{
-    if (fid < 0 || fid >= T4A_FN_COUNT) throw Error(T4A_GPU_INVALID_ARGUMENT, "unknown built-in function id");
-    if (n_acc < 1 || n_acc > T4A_FN_MAX_ACC) throw Error(T4A_GPU_INVALID_ARGUMENT, "n_acc out of range");
-    fn_dev_.fid = fid;
-    fn_dev_.n_acc = n_acc;
-    std::memcpy(fn_dev_.params, params, sizeof(double) * T4A_FN_MAX_PARAMS);
-    weights_.assign(weights, weights + (size_t)n_acc * total_);
-    fn_kind_ = FnKind::Builtin;
-}
-
-void TreeTci::set_callback(t4a_gpu_batch_eval_fn cb, void* ctx)
-{
-    if (!cb) throw Error(T4A_GPU_NULL_POINTER, "callback is null");
-    cb_ = cb;
-    cb_ctx_ = ctx;
-    fn_kind_ = FnKind::Callback;
-}
-
-void TreeTci::require_fn() const
-{
-    if (fn_kind_ == FnKind::None)
-        throw Error(T4A_GPU_INVALID_ARGUMENT, "no function set: call t4a_gpu_treetci_set_builtin_function or _set_callback");
 }
 
 const IndexSet& TreeTci::pivots_of(const SubtreeKey& key) const
@@ -399,23 +368,15 @@ void TreeTci::default_candidates(const TreeEdge& edge, IndexSet& left, IndexSet&
 // ================================================================================================= evaluation
 void TreeTci::accumulate(const IndexSet& set, const std::vector<size_t>& sites, std::vector<uint64_t>& acc) const
 {
-    const int K = fn_dev_.n_acc;
-    acc.assign(std::max<size_t>(set.count, 1) * (size_t)K, 0);
-    for (size_t e = 0; e < set.count; ++e) {
-        const uint32_t* v = set.at(e);
-        for (int k = 0; k < K; ++k) {
-            uint64_t a = 0;
-            const uint64_t* w = weights_.data() + (size_t)k * total_;
-            for (size_t s = 0; s < sites.size(); ++s) a += w[offset_[sites[s]] + v[s]];
-            acc[e * K + k] = a;
-        }
-    }
+    std::vector<size_t> off(sites.size()); // (both callers refuse an empty set first: no padding entry is needed)
+    for (size_t s = 0; s < sites.size(); ++s) off[s] = fn_.offset[sites[s]];
+    fn_.accumulate(set, off.data(), acc);
 }
 
 void TreeTci::eval_matrix(const IndexSet& rows, const std::vector<size_t>& row_sites, const IndexSet& cols,
                           const std::vector<size_t>& col_sites, double* d_out, bool transposed, unsigned long long* d_maxbits)
 {
-    require_fn();
+    fn_.require("treetci");
     const size_t n = local_dims.size();
     const size_t nr = rows.count, nc = cols.count;
     if (nr == 0 || nc == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "at least one point is required");
@@ -432,16 +393,12 @@ void TreeTci::eval_matrix(const IndexSet& rows, const std::vector<size_t>& row_s
     }
     hipStream_t st = eng.stream();
     if (nr > 0x7FFFFFFFull || nc > 0x7FFFFFFFull) throw Error(T4A_GPU_INVALID_ARGUMENT, "candidate matrix too large");
-    if (fn_kind_ == FnKind::Builtin) {
+    if (fn_.builtin()) {
         std::vector<uint64_t> ra, rb;
         accumulate(rows, row_sites, ra);
         accumulate(cols, col_sites, rb);
-        d_acc_.reserve(ra.size() + rb.size());
-        h_acc_.reserve(ra.size() + rb.size());
-        std::memcpy(h_acc_.get(), ra.data(), ra.size() * sizeof(uint64_t));
-        std::memcpy(h_acc_.get() + ra.size(), rb.data(), rb.size() * sizeof(uint64_t));
-        T4A_HIP(hipMemcpyAsync(d_acc_.get(), h_acc_.get(), (ra.size() + rb.size()) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-        pi_eval_launch(fn_dev_, d_acc_.get(), (int)nr, d_acc_.get() + ra.size(), (int)nc, d_out,
+        const auto d_acc = stage_accumulator_pair(ra, rb, h_acc_, d_acc_, st);
+        pi_eval_launch(fn_.dev, d_acc.first, (int)nr, d_acc.second, (int)nc, d_out,
                        transposed ? (int)nc : (int)nr, transposed, d_maxbits, st);
         T4A_HIP(hipGetLastError());
         T4A_HIP(hipStreamSynchronize(st)); // (the pinned staging block is reused by the next call)
@@ -456,10 +413,7 @@ void TreeTci::eval_matrix(const IndexSet& rows, const std::vector<size_t>& row_s
                 for (size_t s = 0; s < col_sites.size(); ++s) p[col_sites[s]] = cols.at(j)[s];
             }
         std::vector<double> vals(npts);
-        const int64_t got = cb_(cb_ctx_, idx.data(), n, npts, vals.data());
-        if (got < 0 || (size_t)got != npts)
-            throw Error(T4A_GPU_CALLBACK_ERROR, "batch evaluator returned " + std::to_string(got) + " values for " +
-                                                    std::to_string(npts) + " candidate-matrix entries");
+        fn_.call(idx.data(), n, npts, vals.data(), "batch evaluator", "candidate-matrix entries");
         if (transposed) {
             d_vals_.reserve(npts);
             T4A_HIP(hipMemcpyAsync(d_vals_.get(), vals.data(), npts * sizeof(double), hipMemcpyHostToDevice, st));
@@ -475,11 +429,11 @@ void TreeTci::eval_matrix(const IndexSet& rows, const std::vector<size_t>& row_s
 
 std::vector<double> TreeTci::eval_points(const std::vector<uint32_t>& idx, size_t n_pts)
 {
-    require_fn();
+    fn_.require("treetci");
     const size_t n = local_dims.size();
     std::vector<double> out(n_pts);
     if (n_pts == 0) return out;
-    if (fn_kind_ == FnKind::Builtin) {
+    if (fn_.builtin()) {
         // every point is a "row" over all sites; the single column carries no site
         IndexSet rows, cols;
         rows.width = n;
@@ -493,10 +447,7 @@ std::vector<double> TreeTci::eval_points(const std::vector<uint32_t>& idx, size_
         eval_matrix(rows, all, cols, {}, d_c_.get(), false, nullptr);
         T4A_HIP(hipMemcpy(out.data(), d_c_.get(), n_pts * sizeof(double), hipMemcpyDeviceToHost));
     } else {
-        const int64_t got = cb_(cb_ctx_, idx.data(), n, n_pts, out.data());
-        if (got < 0 || (size_t)got != n_pts)
-            throw Error(T4A_GPU_CALLBACK_ERROR, "batch evaluator returned " + std::to_string(got) + " values for " +
-                                                    std::to_string(n_pts) + " points");
+        fn_.call(idx.data(), n, n_pts, out.data(), "batch evaluator", "points");
     }
     return out;
 }
@@ -504,7 +455,7 @@ std::vector<double> TreeTci::eval_points(const std::vector<uint32_t>& idx, size_
 // ================================================================================================= update.rs
 EdgeSelection TreeTci::update_edge(const TreeEdge& edge, const RrLUOptions& options) // :22-115
 {
-    require_fn();
+    fn_.require("treetci");
     static const bool host_prof = std::getenv("T4A_HOST_PROFILE") != nullptr;
     static double hp[4] = {0, 0, 0, 0};
     static long hp_n = 0;
@@ -523,24 +474,19 @@ EdgeSelection TreeTci::update_edge(const TreeEdge& edge, const RrLUOptions& opti
     RrLUOptions o = options;
     o.left_orthogonal = true;
     LuciResult lu;
-    if (fn_kind_ == FnKind::Builtin) {
+    if (fn_.builtin()) {
         // only the integer accumulators travel: the rrLU kernel evaluates the candidate matrix into its registers
         std::vector<uint64_t> ra, rb;
         accumulate(lc, keys.first, ra);
         accumulate(rc, keys.second, rb);
         t2 = now();
-        d_acc_.reserve(ra.size() + rb.size());
-        hipStream_t st = eng.stream();
         // (one copy out of pinned memory — two copies out of pageable vectors cost ~30 us of an edge update; luci() below ends with a
         // stream synchronisation, the staging block is free again then)
-        h_acc_.reserve(ra.size() + rb.size());
-        std::memcpy(h_acc_.get(), ra.data(), ra.size() * sizeof(uint64_t));
-        std::memcpy(h_acc_.get() + ra.size(), rb.data(), rb.size() * sizeof(uint64_t));
-        T4A_HIP(hipMemcpyAsync(d_acc_.get(), h_acc_.get(), (ra.size() + rb.size()) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        const auto d_acc = stage_accumulator_pair(ra, rb, h_acc_, d_acc_, eng.stream());
         FusedPi fp;
-        fp.fn = fn_dev_;
-        fp.d_rowacc = d_acc_.get();
-        fp.d_colacc = d_acc_.get() + ra.size();
+        fp.fn = fn_.dev;
+        fp.d_rowacc = d_acc.first;
+        fp.d_colacc = d_acc.second;
         lu = eng.luci(nullptr, (int)M, (int)N, o, false, false, &fp); // synchronises the stream
     } else {
         double* d_pi = eng.pi(M * N);
@@ -585,7 +531,7 @@ EdgeSelection TreeTci::update_edge(const TreeEdge& edge, const RrLUOptions& opti
 void TreeTci::optimize(const TreeTciOptions& options) // :95-220 (DefaultProposer, AllEdges)
 {
     options.validate();
-    require_fn();
+    fn_.require("treetci");
     ranks_hist.clear();
     errors_hist.clear();
     std::vector<size_t> nglobal;
@@ -632,7 +578,7 @@ void TreeTci::optimize(const TreeTciOptions& options) // :95-220 (DefaultPropose
 void TreeTci::crossinterpolate2(std::vector<std::vector<uint32_t>> pivots, const TreeTciOptions& options) // api.rs:21-96
 {
     options.validate();
-    require_fn();
+    fn_.require("treetci");
     const size_t n = local_dims.size();
     if (pivots.empty()) pivots.push_back(std::vector<uint32_t>(n, 0));
     add_global_pivots(pivots);
@@ -742,7 +688,7 @@ void TreeTci::site_rows(size_t site, const std::vector<SubtreeKey>& in_keys, Ind
 
 void TreeTci::materialize(size_t center_site) // to_treetn :17-103
 {
-    require_fn();
+    fn_.require("treetci");
     const size_t n = graph.n_sites();
     std::vector<size_t> parents, distances;
     graph.bfs_tree(center_site, parents, distances);

@@ -10,7 +10,8 @@
 #include <vector>
 
 #include "engine.hpp"
-#include "tci2.hpp"
+#include "fnsource.hpp"
+#include "tt.hpp"
 
 namespace t4a {
 
@@ -79,8 +80,8 @@ class TreeTci {
 public:
     TreeTci(const std::vector<size_t>& local_dims, const TreeGraph& graph);
 
-    void set_builtin(int fid, int n_acc, const double* params, const uint64_t* weights);
-    void set_callback(t4a_gpu_batch_eval_fn cb, void* ctx);
+    void set_builtin(int fid, int n_acc, const double* params, const uint64_t* weights) { fn_.set_builtin(fid, n_acc, params, weights); }
+    void set_callback(t4a_gpu_batch_eval_fn cb, void* ctx) { fn_.set_callback(cb, ctx); }
 
     void add_global_pivots(const std::vector<std::vector<uint32_t>>& pivots);
     // PivotCandidateProposer::candidates of the selected proposer (proposer.rs:57-249)
@@ -119,15 +120,7 @@ public:
     Engine eng;
 
 private:
-    enum class FnKind { None, Builtin, Callback };
-    FnKind fn_kind_ = FnKind::None;
-    FnDevice fn_dev_{};
-    std::vector<uint64_t> weights_;
-    std::vector<size_t> offset_;
-    size_t total_ = 0;
-    t4a_gpu_batch_eval_fn cb_ = nullptr;
-    void* cb_ctx_ = nullptr;
-    void require_fn() const;
+    FnSource fn_; // (fnsource.hpp)
 
     // accumulators of a list of partial multi-indices living on `sites` (entry k, digit s <-> site sites[s])
     void accumulate(const IndexSet& set, const std::vector<size_t>& sites, std::vector<uint64_t>& acc) const;
