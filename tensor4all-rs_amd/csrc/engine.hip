@@ -362,9 +362,9 @@ void print_stamps(const RrluRoute& rt, int M, int N, int steps, const unsigned l
     case RrluKind::SingleXcd:
     case RrluKind::MultiXcd:
         std::fprintf(stderr, "[rrlu stamps xcd] M=%d N=%d W=%d steps=%d cycles/step: pass=%.0f search=%.0f publish=%.0f | prefetch=%.0f keys=%.0f pick=%.0f slow+stop=%.0f recwr=%.0f barB=%.0f | record=%.0f "
-                             "tables+u=%.0f colwait=%.0f divide=%.0f barC=%.0f lread=%.0f | pollspins=%llu | launch (cycles): election=%llu load+init=%llu steps=%llu write-out=%llu\n",
+                             "tables+u=%.0f colwait=%.0f divide=%.0f barC=%.0f lread=%.0f | pollspins=%llu exact sweeps=%llu exact picks=%llu | launch (cycles): election=%llu load+init=%llu steps=%llu write-out=%llu\n",
                      M, N, rt.xcd.W, steps, hs[0] / st, hs[1] / st, hs[2] / st, hs[6] / st, hs[8] / st, hs[14] / st, hs[15] / st, hs[9] / st, hs[3] / st, hs[10] / st, hs[11] / st, hs[12] / st,
-                     hs[4] / st, hs[13] / st, hs[7] / st, hs[5], hs[16], hs[17], hs[18], hs[19]);
+                     hs[4] / st, hs[13] / st, hs[7] / st, hs[5], hs[22], hs[23], hs[16], hs[17], hs[18], hs[19]);
         break;
     default: {
         const bool reg = rt.kind == RrluKind::Reg;

@@ -67,6 +67,16 @@ constexpr int X2_QSHIFT = 11, X2_PSHIFT = 11;
 
 constexpr int X2_DIVW = XWAVES - 1; // waves that divide the pivot column (all but the polling wave)
 
+// largest high word, sign cleared, among row slots R0 .. R0 + NR - 1 of one owned column, on top of acc: two slots per instruction
+// (vmax3_hi_abs and its invariant: kernels_rrlu_xcd_common.hpp; an odd slot is paired with itself)
+template <int R0, int NR, int RPT> __device__ __forceinline__ unsigned x2_colmax_hi(unsigned acc, const XSlab<RPT>& col)
+{
+#pragma unroll
+    for (int r = 0; r + 1 < NR; r += 2) acc = vmax3_hi_abs(acc, hi32(col.get(R0 + r)), hi32(col.get(R0 + r + 1)));
+    if constexpr ((NR & 1) != 0) acc = vmax3_hi_abs(acc, hi32(col.get(R0 + NR - 1)), hi32(col.get(R0 + NR - 1)));
+    return acc;
+}
+
 // KX: XCDs the agents live on (round 5).  1: everything inside one XCD's L2 (plain stores, sc1 loads).  > 1: the agents of KX
 // neighbouring XCDs (p.xcc, p.xcc + 1, ... mod 8) — matrices beyond the registers of one XCD, BASELINE.json configs[3]: 1 450 x 1 450
 // with the history extras — exchange through the same mailbox with write-through (sc1) stores; the L2s are kept coherent for such
@@ -170,7 +180,7 @@ __device__ __forceinline__ void rrlu_xcd2_body(const RrluXcdArgs& p, const RrluX
         if (g + NW * q < N) active |= 1u << q;
     XSlab<RPT> a[CPT]; // ext vectors (two per column beyond 16 row slots): the run-time row-slot accesses become s_set_gpr_idx moves
     double local_sqmax = 0.0;
-    bool bad = false; // a NaN or an infinity among my entries of the input
+    bool bad = false; // a NaN, an infinity or an entry whose square overflows among my entries of the input
     // every load is issued before the first one is consumed (clamped addresses instead of branches): the whole matrix is
     // one round trip to memory per lane, not RPT * CPT dependent ones
     // (Row validity travels as a per-lane BIT MASK and is tested again for every column, behind a compiler barrier: as RPT x CPT
@@ -208,6 +218,9 @@ __device__ __forceinline__ void rrlu_xcd2_body(const RrluXcdArgs& p, const RrluX
             a[q].set(r, v);
         }
     }
+    // ... and |v| >= 2^512: an infinite score is the largest magnitude's fate at the first pick anyway (give-up with code 2), and met
+    // HERE it keeps every high word of the step loop clear of f32 NaN patterns (vmax3_hi_abs)
+    bad |= !(local_sqmax < __builtin_huge_val());
     for (int i = tid; i < M; i += XT) {
         posrow[i] = (unsigned short)i;
         rowpos[i] = (unsigned short)i;
@@ -222,7 +235,7 @@ __device__ __forceinline__ void rrlu_xcd2_body(const RrluXcdArgs& p, const RrluX
         if (lane == 0 && wm > 0.0)
             atomicMax((unsigned long long*)&p.dresult[1], (unsigned long long)__double_as_longlong(wm));
     }
-    const unsigned wave_bad = __ballot(bad) != 0ull ? 1u : 0u; // travels in the z word of this agent's early keys
+    const unsigned wave_bad = __ballot(bad) != 0ull ? 1u : 0u; // travels in the z word of this agent's early keys: the first pick gives up with code 2
     __syncthreads();
 
     const bool stamp_on = kXcdStamps && (p.stamps != nullptr) && rank == 0 && tid == 64 * T4A_XCD_STAMP_WAVE;
@@ -252,21 +265,17 @@ __device__ __forceinline__ void rrlu_xcd2_body(const RrluXcdArgs& p, const RrluX
     asm volatile("" : "+v"(spec_frac), "+v"(rel_tol_v), "+v"(abs_tol_v));
     constexpr unsigned XSPIN = 1u << 20; // bounded spins: a hand-off that does not arrive makes the launch give up
 
-    // maxima of the untouched matrix for the first arg-max
-    double mq[CPT];
+    // maxima of the untouched matrix for the first arg-max.  mq[q]: per lane, the largest HIGH WORD (sign cleared) among my rows of
+    // column q — all that is needed before the early key leaves: the poller decides on high words, and the exact candidate is found
+    // by the position search afterwards.  0 for a column outside the trailing block (which is a property of `active`, not of mq).
+    // INVARIANT of the step loop: every entry of the trailing block is below 2^513 in magnitude, so no high word is an f32 NaN
+    // pattern (|v| >= 2^1017).  The input is checked above (`bad`: a launch with |v| >= 2^512 anywhere gives up at its first pick);
+    // a step whose maximum reaches 2^512 has an infinite score and gives up at the pick (its high word is outside hi_mid, so the
+    // exact comparison decides, which tests for it); below that, |l| <= 1 bounds the growth of a step to a factor of two.
+    unsigned mq[CPT];
 #pragma unroll
-    for (int q = 0; q < CPT; ++q) {
-        mq[q] = -1.0;
-        if (active & (1u << q)) {
-            double m0 = -1.0, m1 = -1.0;
-#pragma unroll
-            for (int r = 0; r < RPT; ++r) {
-                if (r & 1) m1 = vmax_abs(m1, a[q].get(r));
-                else m0 = vmax_abs(m0, a[q].get(r));
-            }
-            mq[q] = vmax(m0, m1);
-        }
-    }
+    for (int q = 0; q < CPT; ++q) mq[q] = (active & (1u << q)) ? x2_colmax_hi<0, RPT>(0u, a[q]) : 0u;
+    [[maybe_unused]] unsigned long long n_exact_sweep = 0ull, n_exact_pick = 0ull; // (diagnostic builds: how often the rare paths ran)
     // the division of the pivot column is shared by waves 1 .. 7: wave w takes slot rows (w - 1) + 7 j
     constexpr int XR = (RPT + X2_DIVW - 1) / X2_DIVW;
     const int sr0 = wave - 1; // first slot row of this wave (-1: the polling wave divides nothing)
@@ -275,62 +284,62 @@ __device__ __forceinline__ void rrlu_xcd2_body(const RrluXcdArgs& p, const RrluX
         const int k = kn - 1; // rows / columns at positions > k form the trailing block searched for pivot kn
         const int par = kn & 1;
         const unsigned tag = (p.salt << 16) | (unsigned)(kn + 1);
-        // ---- wave arg-max: (max score, smallest position among the maxima, value there), all wave-uniform ----
-        double m = mq[0];
+        // ---- wave arg-max, first half: the largest HIGH WORD among my entries of the trailing block (wave-uniform; 0 without a
+        // column there: the values are magnitudes, their high words order like them)
+        int mh = (int)mq[0];
 #pragma unroll
-        for (int q = 1; q < CPT; ++q) m = vmax(m, mq[q]);
-        // (m >= 0, or -1 without a column in the trailing block: the high words order like the values)
-        const int whi = wave_max_i32((int)hi32(m));
-        const unsigned long long whb = __ballot((int)hi32(m) == whi);
-        const bool hi_single = __builtin_popcountll(whb) == 1; // one lane holds the largest high word: it holds the maximum
-        const double wmax = hi_single ? readlane_f64(m, (int)__builtin_ctzll(whb)) : wave_max_f64(m);
-        const double sq = wmax * wmax; // the winning score v*v of this agent
-        // ---- early key: the magnitude of the candidate goes out before its position is known.  In the normal case (one
-        // agent holds the largest |v|, its square a normal number) the magnitudes alone decide the winner.  (No candidate: 0,
-        // which sends the pick to the exact path.)  z: this agent met a non-finite input entry (read in the first step only).
+        for (int q = 1; q < CPT; ++q) mh = (int)mq[q] > mh ? (int)mq[q] : mh;
+        const int whi = wave_max_i32(mh);
+        // ---- early key: the high word of the candidate's magnitude goes out before the candidate itself is known.  In the
+        // normal case (one agent holds the largest high word, inside hi_mid) the high words alone name the winning AGENT; every
+        // other case — several agents on one high word, tiny or huge maxima, no candidate (0) — sends the pick to the exact
+        // comparison of the full keys.  z: this agent met an entry of the input it cannot handle (read in the first step only).
         const int kslot = (par * NW + g) * 16;
         {
-            const double k1 = (wmax >= 0.0) ? wmax : 0.0;
             u32x4 kv;
-            kv.x = lo32(k1);
-            kv.y = hi32(k1);
+            kv.x = 0u;
+            kv.y = (unsigned)whi;
             kv.z = wave_bad;
-            kv.w = tag ^ kv.x ^ kv.y ^ kv.z;
+            kv.w = tag ^ kv.y ^ kv.z;
             if (lane == 0) __builtin_amdgcn_raw_buffer_store_b128(kv, mail, kslot, 0, 0); // (read inside this XCD only: a plain store, also when the agents span several XCDs)
         }
         u32x4 kg[4], kh[4];
         bool has_cand = false;         // this agent has a candidate
         double cval = 0.0;             // its value
         int cirow = 0, qstar = 0;      // its row index and my column slot
-        if (wmax >= 0.0) {
+        double sq = 0.0;               // its score v*v
+        if (active != 0u) {
             bool done = false;
-            // while v*v is a normal number, distinct |v| have distinct squares, so the equality sweep can compare |v| itself
-            // (and the rows that are already pivoted hold exact zeros in every active column, which cannot match)
+            // ---- second half: WHICH entry.  If exactly one entry carries the largest high word, it is the largest magnitude (every
+            // other entry is smaller in the high word already); rows that are pivoted and slot rows beyond M hold exact zeros in
+            // every active column, and whi inside hi_mid is not 0.  Inside hi_mid the high words are normal f32 patterns: the
+            // f32 comparison with |.| is the comparison of the high words with the sign cleared.
             if (hi_mid(whi)) {
                 unsigned long long bq[CPT];
                 int nhit = 0;
 #pragma unroll
                 for (int q = 0; q < CPT; ++q) {
-                    bq[q] = __ballot(mq[q] == wmax); // (columns outside the trailing block keep mq = -1)
+                    bq[q] = __ballot(mq[q] == (unsigned)whi); // (columns outside the trailing block keep mq = 0)
                     nhit += __builtin_popcountll(bq[q]);
                 }
-                if (nhit == 1) { // one lane of one column holds the maximum: the normal case
+                if (nhit == 1) { // one lane of one column holds the largest high word: the normal case
 #pragma unroll
                     for (int q = 0; q < CPT; ++q)
                         if (bq[q] != 0ull) {
                             const int hl = (int)__builtin_ctzll(bq[q]);
-                            // which row slot of that lane: bit RPT - 1 - r of `bits` says slot r holds the maximum
-                            // (compare + add-with-carry per slot: bits = 2 bits + (|a| == wmax))
+                            // which row slot of that lane: bit RPT - 1 - r of `bits` says slot r carries whi
+                            // (compare + add-with-carry per slot: bits = 2 bits + (|hi(a)| == whi))
                             unsigned bits = 0u;
 #pragma unroll
                             for (int r = 0; r < RPT; ++r)
-                                asm("v_cmp_eq_f64 vcc, |%1|, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(bits) : "v"((double)a[q].get(r)), "s"(wmax) : "vcc");
+                                asm("v_cmp_eq_f32 vcc, |%1|, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(bits) : "v"(hi32(a[q].get(r))), "s"(whi) : "vcc");
                             const unsigned hb_ = (unsigned)__builtin_amdgcn_readlane((int)bits, hl);
-                            if (__builtin_popcount(hb_) == 1) {
+                            if (__builtin_popcount(hb_) == 1) { // ... and one slot of that lane: this entry is the candidate
                                 const int rstar = RPT - 1 - (int)__builtin_ctz(hb_);
                                 cirow = hl + 64 * rstar;
                                 has_cand = true;
                                 cval = readlane_f64(a[q].dyn(rstar), hl);
+                                sq = cval * cval;
                                 qstar = q;
                                 done = true;
                             }
@@ -338,22 +347,32 @@ __device__ __forceinline__ void rrlu_xcd2_body(const RrluXcdArgs& p, const RrluX
                 }
             }
             if (!done) {
-                // ties, zero / subnormal scores: exact sweep on the squares (an infinite score ends the launch at the pick)
+                // several entries on the largest high word, zero / subnormal / huge maxima: the exact maximum of the scores from
+                // the slab, then the exact sweep on the squares (an infinite score ends the launch at the pick)
+                if (stamp_on) ++n_exact_sweep;
+                double em = 0.0;
+#pragma unroll
+                for (int q = 0; q < CPT; ++q)
+                    if (active & (1u << q)) {
+#pragma unroll
+                        for (int r = 0; r < RPT; ++r) em = vmax_abs(em, a[q].get(r));
+                    }
+                const double wmax = wave_max_f64(em);
+                sq = wmax * wmax;
                 unsigned mypos = XNOPOS;
                 double myval = 0.0;
                 int myrow = 0, myq = 0;
                 const int lane_o = opaque_v(lane), M_o = opaque_s(M); // (nothing of this rare path is hoisted out of the step loop)
 #pragma unroll
                 for (int q = 0; q < CPT; ++q) {
-                    const bool qhit = (mq[q] >= 0.0) & (mq[q] * mq[q] == sq);
-                    if (__ballot(qhit) != 0ull) {
+                    if (active & (1u << q)) {
                         const unsigned cp_ = colpos[opaque_s(g + NW * q)];
                         auto sweep = [&](int r, double av) {
                             const int i = lane_o + 64 * r;
                             const unsigned rp_ = rowpos[i < M_o ? i : 0];
                             const unsigned key = ROWMAJOR ? ((rp_ << X2_PSHIFT) | cp_) : ((cp_ << X2_PSHIFT) | rp_);
                             const double sc = av * av;
-                            const bool hit = qhit & (i < M_o) & ((int)rp_ > k) & (sc == sq);
+                            const bool hit = (i < M_o) & ((int)rp_ > k) & (sc == sq);
                             if (hit && key < mypos) {
                                 mypos = key;
                                 myval = av;
@@ -462,12 +481,12 @@ __device__ __forceinline__ void rrlu_xcd2_body(const RrluXcdArgs& p, const RrluX
                     for (int j = 0; j < 4; ++j) zf |= kg[j].z;
                     if (__ballot(zf != 0u) != 0ull) giveup = 2;
                 }
-                // winner over all agents.  Normal case: the largest candidate magnitude, its square a normal number (distinct
-                // |v| <=> distinct scores), held by exactly one early key: one maximum reduction decides.  (A duplicate of the
-                // last key can only push the count above one: then the exact path decides.  No candidate travels as 0.)
+                // winner over all agents.  Normal case: the largest high word among the early keys (magnitudes: non-negative, so
+                // one integer reduction orders them) lies inside hi_mid — the scores are normal numbers with room to spare — and
+                // exactly one key carries it: that agent holds the largest magnitude.  (A duplicate of the last key can only
+                // push the count above one: then the exact comparison decides.  No candidate travels as 0.)  Everything else —
+                // several agents on one high word, tiny, huge or no maxima — is decided on the FULL keys below.
                 bool decided = false;
-                // first on the high words alone (early keys are magnitudes: non-negative): one integer reduction; the 64-bit
-                // comparison only when several keys share the largest high word
                 int lh = (int)kg[0].y;
 #pragma unroll
                 for (int j = 1; j < 4; ++j) lh = (int)kg[j].y > lh ? (int)kg[j].y : lh;
@@ -479,50 +498,31 @@ __device__ __forceinline__ void rrlu_xcd2_body(const RrluXcdArgs& p, const RrluX
                     hb[j] = __ballot((int)kg[j].y == ghi);
                     nh += __builtin_popcountll(hb[j]);
                 }
-                double gm = 0.0, gsq = 0.0;
-                bool in_range = hi_mid(ghi);
-                if (!(in_range && nh == 1)) {
-                    double lm = -1.0;
+                if (hi_mid(ghi) && nh == 1) {
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) lm = vmax(lm, mk_f64(kg[j].x, kg[j].y));
-                    gm = wave_max_f64(lm);
-                    gsq = gm * gm;
-                    in_range = (gsq >= 2.2250738585072014e-308) && (gsq < __builtin_huge_val());
-                    nh = 0;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        hb[j] = __ballot(mk_f64(kg[j].x, kg[j].y) == gm);
-                        nh += __builtin_popcountll(hb[j]);
-                    }
-                }
-                if (in_range) {
-                    if (nh == 1) {
-#pragma unroll
-                        for (int j = 0; j < 4; ++j)
-                            if (hb[j] != 0ull) {
-                                const int hl = (int)__builtin_ctzll(hb[j]);
-                                wa_ = hl + 64 * j;
-                                // the winner's full key: normally long there; otherwise fetched again until it is
-                                for (;;) {
-                                    wkx = (unsigned)__builtin_amdgcn_readlane((int)kh[j].x, hl);
-                                    wky = (unsigned)__builtin_amdgcn_readlane((int)kh[j].y, hl);
-                                    wkz = (unsigned)__builtin_amdgcn_readlane((int)kh[j].z, hl);
-                                    const unsigned kw = (unsigned)__builtin_amdgcn_readlane((int)kh[j].w, hl);
-                                    if ((wkx ^ wky ^ wkz ^ kw) == tag) break;
-                                    xcd_poll_again();
-                                    if (++spins > XSPIN) {
-                                        giveup = 1;
-                                        break;
-                                    }
-                                    kh[j] = __builtin_amdgcn_raw_buffer_load_b128(mail, (int)k2_base + (par * NW + pbase + min(lane + 64 * j, NWL - 1)) * 16, 0, BUF_SC1);
+                    for (int j = 0; j < 4; ++j)
+                        if (hb[j] != 0ull) {
+                            const int hl = (int)__builtin_ctzll(hb[j]);
+                            wa_ = hl + 64 * j;
+                            // the winner's full key: it leaves its agent a position search behind the early one; fetched again until it is there
+                            for (;;) {
+                                wkx = (unsigned)__builtin_amdgcn_readlane((int)kh[j].x, hl);
+                                wky = (unsigned)__builtin_amdgcn_readlane((int)kh[j].y, hl);
+                                wkz = (unsigned)__builtin_amdgcn_readlane((int)kh[j].z, hl);
+                                const unsigned kw = (unsigned)__builtin_amdgcn_readlane((int)kh[j].w, hl);
+                                if ((wkx ^ wky ^ wkz ^ kw) == tag) break;
+                                xcd_poll_again();
+                                if (++spins > XSPIN) {
+                                    giveup = 1;
+                                    break;
                                 }
+                                kh[j] = __builtin_amdgcn_raw_buffer_load_b128(mail, (int)k2_base + (par * NW + pbase + min(lane + 64 * j, NWL - 1)) * 16, 0, BUF_SC1);
                             }
-                        decided = true;
-                    }
-                } else if (!(gsq < __builtin_huge_val())) {
-                    giveup = 2; // an infinite score: overflow in the trailing block (or an infinite input)
+                        }
+                    decided = true;
+                } else if (stamp_on) {
+                    ++n_exact_pick;
                 }
-                (void)gm;
                 XSTAMP(14);
                 if constexpr (KX > 1) {
                     if (!decided && !giveup) {
@@ -531,8 +531,8 @@ __device__ __forceinline__ void rrlu_xcd2_body(const RrluXcdArgs& p, const RrluX
                     }
                 }
                 if (!decided && !giveup) {
-                    // ties between agents, zero / subnormal scores: exact comparison of (v*v, position key) over the FULL keys;
-                    // an agent without candidate carries value 0 and the largest position key
+                    // several agents on the largest high word, zero / subnormal / infinite scores: exact comparison of (v*v, position
+                    // key) over the FULL keys; an agent without candidate carries value 0 and the largest position key
                     for (;;) {
                         bool ok = true;
 #pragma unroll
@@ -571,6 +571,7 @@ __device__ __forceinline__ void rrlu_xcd2_body(const RrluXcdArgs& p, const RrluX
                         ckey.z = better ? kh[j].z : ckey.z;
                     }
                     const double gmax = wave_max_f64(csc);
+                    if (!(gmax < __builtin_huge_val()) && !giveup) giveup = 2; // an infinite score: overflow in the trailing block (the early keys no longer carry magnitudes to see it on)
                     const unsigned gpos = wave_min_u32((csc == gmax) ? cpk : XNOPOS);
                     const unsigned long long sel = __ballot((csc == gmax) & (cpk == gpos));
                     const int wl = sel ? (int)__builtin_ctzll(sel) : 0;
@@ -894,10 +895,11 @@ __device__ __forceinline__ void rrlu_xcd2_body(const RrluXcdArgs& p, const RrluX
         // fused with the per-column maxima for the next arg-max; the pivot column keeps its un-scaled entries (L = column /
         // pivot is formed when the factored matrix is written out — the column is never read again)
         // =====================================================================================
+        // (the maxima are taken on the high words, two entries per instruction: x2_colmax_hi; a column outside the trailing block keeps 0)
         if constexpr (NH == 1) {
 #pragma unroll
             for (int q = 0; q < CPT; ++q) {
-                mq[q] = -1.0;
+                mq[q] = 0u;
                 if (active & (1u << q)) {
 #pragma unroll
                     for (int r = 0; r < RPT; ++r) { // in place (see sub_in_place); un-fused, one rounding per operation like the reference
@@ -905,19 +907,12 @@ __device__ __forceinline__ void rrlu_xcd2_body(const RrluXcdArgs& p, const RrluX
                         sub_in_place(t, l[r] * u[q]);
                         a[q].set(r, t);
                     }
-                    double m0 = -1.0, m1 = -1.0;
-#pragma unroll
-                    for (int r = 0; r < RPT; ++r) {
-                        if (r & 1) m1 = vmax_abs(m1, a[q].get(r));
-                        else m0 = vmax_abs(m0, a[q].get(r));
-                    }
-                    mq[q] = vmax(m0, m1);
+                    mq[q] = x2_colmax_hi<0, RPT>(0u, a[q]);
                 }
             }
         } else {
-            double m0[CPT], m1[CPT];
 #pragma unroll
-            for (int q = 0; q < CPT; ++q) m0[q] = m1[q] = -1.0;
+            for (int q = 0; q < CPT; ++q) mq[q] = 0u;
 #pragma unroll
             for (int h = 0; h < NH; ++h) {
                 if (h > 0) {
@@ -934,16 +929,10 @@ __device__ __forceinline__ void rrlu_xcd2_body(const RrluXcdArgs& p, const RrluX
                             sub_in_place(t, l[r] * u[q]);
                             a[q].set(h * HR + r, t);
                         }
-#pragma unroll
-                        for (int r = 0; r < HR; ++r) {
-                            if (r & 1) m1[q] = vmax_abs(m1[q], a[q].get(h * HR + r));
-                            else m0[q] = vmax_abs(m0[q], a[q].get(h * HR + r));
-                        }
+                        mq[q] = h == 0 ? x2_colmax_hi<0, HR>(mq[q], a[q]) : x2_colmax_hi<HR, HR>(mq[q], a[q]);
                     }
                 }
             }
-#pragma unroll
-            for (int q = 0; q < CPT; ++q) mq[q] = (active & (1u << q)) ? vmax(m0[q], m1[q]) : -1.0;
         }
         npiv = kn + 1;
         XSTAMP(0);
@@ -970,6 +959,8 @@ __device__ __forceinline__ void rrlu_xcd2_body(const RrluXcdArgs& p, const RrluX
         pe.stamps[16] = t_elected - t_entry; // fixed part of a launch: election ...
         pe.stamps[17] = t_loop - t_elected;  // ... matrix load, tables, first maxima ...
         pe.stamps[18] = t_done - t_loop;     // (the pivot steps)
+        pe.stamps[22] = n_exact_sweep;       // searches of the stamped wave that took the exact sweep ...
+        pe.stamps[23] = n_exact_pick;        // ... and picks decided on the full keys (counted by the polling wave)
     }
     if (timed_out) return;
     // permutations: the tables are stable since the last barrier; device block and host mirror are written side by side

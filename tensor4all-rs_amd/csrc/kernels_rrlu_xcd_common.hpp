@@ -46,6 +46,18 @@ __device__ __forceinline__ double vmax(double a, double b)
     asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
     return r;
 }
+// max(acc, |x|, |y|) on the HIGH WORDS of doubles, read as f32 bit patterns, in one instruction (second generation of the
+// single-XCD kernel: the column maxima of the step loop).  For non-negative doubles the high 32 bits order like the values, and
+// positive non-NaN f32 patterns order like unsigned integers, so the result is the largest high word with the sign cleared.
+// INVARIANT the caller keeps: no operand is an f32 NaN pattern, i.e. no |v| >= 2^1017 and no non-finite v — v_max3_f32 would
+// drop such an operand.  (A high word with biased exponent below 8 reads as an f32 denormal: the default code object keeps f32
+// denormals, float_denorm_mode_32 = 3; were one flushed, the result only ever feeds range tests it fails either way.)
+__device__ __forceinline__ unsigned vmax3_hi_abs(unsigned acc, unsigned x, unsigned y)
+{
+    unsigned r;
+    asm("v_max3_f32 %0, %1, |%2|, |%3|" : "=v"(r) : "v"(acc), "v"(x), "v"(y));
+    return r;
+}
 template <int CTRL> __device__ __forceinline__ int dpp_i32(int v)
 {
     return __builtin_amdgcn_update_dpp(v, v, CTRL, 0xF, 0xF, false);
