@@ -159,3 +159,120 @@ def test_reference_tci_recovers_the_exact_product(case, links, seed):
     dev = float(np.abs(got - dense).max() / np.abs(dense).max())
     print(f"reference TCI of A.B: case {case} seed {seed:#x} link dims {links} deviation {dev:.3e}")
     assert dev <= 1e-12
+
+
+# ------------------------------------------------------------------------------------------------ the exact reference
+def test_exact_bound_is_the_all_ones_product_and_below_2_53_on_every_profile():
+    """exact_bound is the element of the product of all-ones operands (every element is the same), and every profile of the exact
+    device tests keeps it below 2^53: the largest is the mixed profile with a shared dimension of 3."""
+    for name, (bonds_a, bonds_b, (s1, k, s2)) in cnp.EXACT_PROFILES.items():
+        a = [np.ones((l, s1, k, r)) for l, r in zip(bonds_a[:-1], bonds_a[1:])]
+        b = [np.ones((l, k, s2, r)) for l, r in zip(bonds_b[:-1], bonds_b[1:])]
+        bound = cnp.exact_bound(a, b)
+        assert isinstance(bound, int) and 0 < bound < 2 ** 53, (name, bound)
+        assert bound == cnp.exact_bound(*cnp.exact_operands(name)), name
+        n = len(a)
+        ones = cnp.ContractionNP(a, b, exact=True).evaluate(np.zeros((1, n, 2), dtype=np.int64))
+        assert ones.dtype == np.int64 and int(ones[0]) == bound, (name, int(ones[0]), bound)
+    assert cnp.exact_bound(*cnp.exact_operands("P1")) == cnp.exact_bound(*cnp.exact_operands("P2")) == 3077288755200  # 3.08e12
+    assert cnp.exact_bound(*cnp.exact_operands("P1_k3")) == 3077288755200 // 2 ** 6 * 3 ** 6 == 35052242227200  # 3.5e13
+    assert cnp.exact_bound(*cnp.exact_operands("scratch")) == 8 * (64 * 33) ** 2
+    small_a, small_b = [np.ones((1, 2, 3, 4)), np.ones((4, 2, 3, 1))], [np.ones((1, 3, 2, 5)), np.ones((5, 3, 2, 1))]
+    assert cnp.exact_bound(small_a, small_b) == 3 * 3 * 4 * 5
+    assert np.array_equal(cnp.dense_product(small_a, small_b), np.full((2, 2, 2, 2), 180.0))
+
+
+def test_integer_tensors_hold_minus_one_zero_and_one():
+    ts = cnp.integer_tensors([1, 5, 7, 1], 2, 3, cnp.SEED)
+    assert [t.shape for t in ts] == [(1, 2, 3, 5), (5, 2, 3, 7), (7, 2, 3, 1)] and all(t.dtype == np.float64 for t in ts)
+    flat = np.concatenate([t.reshape(-1, order="F") for t in ts])
+    assert set(np.unique(flat)) == {-1.0, 0.0, 1.0}
+    state, want = cnp.SEED, []
+    for _ in range(flat.size):  # one LCG stream through the sites, column-major, as random_tensors draws it
+        state = (state * 6364136223846793005 + 1442695040888963407) & cnp.MASK
+        want.append((state >> 33) % 3 - 1)
+    assert np.array_equal(flat, np.array(want, dtype=np.float64))
+    with pytest.raises(AssertionError):
+        cnp.ContractionNP(cnp.random_tensors([1, 2, 1], 2, 2, 1), cnp.random_tensors([1, 2, 1], 2, 2, 2), exact=True)
+
+
+@pytest.mark.parametrize("name", ["P1", "P2"])
+def test_int64_reference_equals_the_float_restatement_and_the_dense_product(name):
+    """With entries from {-1, 0, 1} and exact_bound < 2^53 the float restatement is exact whatever its order of summation, so the
+    int64 reference, the float restatement and the dense product of the site contractions agree in every digit."""
+    a, b = cnp.exact_operands(name)
+    n = len(a)
+    assert cnp.exact_bound(a, b) < 2 ** 53
+    ref_i, ref_f = cnp.ContractionNP(a, b, exact=True), cnp.ContractionNP(a, b)
+    dense = cnp.dense_product(a, b)
+    assert np.array_equal(dense, np.rint(dense)) and np.abs(dense).max() > 1
+    dims = [[2, 2]] * n
+    pairs = cnp.lcg_points(40, dims, 7)
+    want = dense[tuple(pairs.reshape(len(pairs), -1).T)].astype(np.int64)
+    got = ref_i.evaluate(pairs)
+    assert got.dtype == np.int64 and np.array_equal(got, want) and np.array_equal(ref_f.evaluate(pairs), want)
+    for cut in range(n + 1):
+        left, right = ref_i.evaluate_left(cut, pairs), ref_i.evaluate_right(cut, pairs)
+        assert left.dtype == right.dtype == np.int64
+        assert np.array_equal(left, ref_f.evaluate_left(cut, pairs)) and np.array_equal(right, ref_f.evaluate_right(cut, pairs))
+        assert np.array_equal(np.einsum("pab,pab->p", left, right), want)
+        if cut >= 1:
+            many = ref_i.evaluate_many(pairs, cut)
+            assert many.dtype == np.int64 and np.array_equal(many, want) and np.array_equal(ref_f.evaluate_many(pairs, cut), want)
+        rows, cols = pairs[:5, :cut], pairs[5:12, cut:]
+        block = ref_i.evaluate_matrix(cut, rows, cols)
+        full = np.concatenate([np.repeat(rows, len(cols), axis=0), np.tile(cols, (len(rows), 1, 1))], axis=1)
+        assert block.dtype == np.int64 and block.shape == (5, 7)
+        assert np.array_equal(block, dense[tuple(full.reshape(len(full), -1).T)].reshape(5, 7))
+        assert np.array_equal(block, ref_f.evaluate_matrix(cut, rows, cols))
+    sites_i = [cnp.np_site(x.astype(np.int64), y.astype(np.int64)) for x, y in zip(a, b)]
+    assert all(s.dtype == np.int64 and np.array_equal(s, cnp.np_site(x, y)) for s, x, y in zip(sites_i, a, b))
+
+
+CONTRACTION_LDS_DOUBLES = 8192  # kernels.hpp: what of a working set fits the LDS
+
+
+def core_use(m, n):
+    return m >= 16 and n >= 16
+
+
+def walk_branches(bonds_a, bonds_b):
+    """(left, right): per site the pair (product 1 on the cores, product 2 on the cores) that wg_product decides from the shapes"""
+    left, right = [], []
+    for s in range(len(bonds_a) - 1):
+        la, ra, lb, rb = bonds_a[s], bonds_a[s + 1], bonds_b[s], bonds_b[s + 1]
+        left.append((core_use(ra, lb), core_use(ra, rb)))
+        right.append((core_use(la, rb), core_use(la, lb)))
+    return left, right
+
+
+def test_the_mixed_profiles_reach_every_branch_combination():
+    """The branch table in the docstring of tests/test_gpu_mpo_exact.py restated from the bonds, so that an edit of a profile that
+    loses a combination fails here."""
+    seen_l, seen_r, both_scalar_beside_wide, summed, tiles, edges = set(), set(), 0, set(), set(), set()
+    for name in ("P1", "P2"):
+        ba, bb, _ = cnp.EXACT_PROFILES[name]
+        left, right = walk_branches(ba, bb)
+        seen_l |= set(left)
+        seen_r |= set(right)
+        for s in range(len(ba) - 1):
+            la, ra, lb, rb = ba[s], ba[s + 1], bb[s], bb[s + 1]
+            both_scalar_beside_wide += (ra < 16 and lb >= 16 and rb >= 16) + (la < 16 and lb >= 16 and rb >= 16)
+            for on_cores, m, n, k2 in ((left[s][0], ra, lb, la), (left[s][1], ra, rb, lb), (right[s][0], la, rb, ra), (right[s][1], la, lb, rb)):
+                if on_cores:
+                    summed.add(k2)
+                    tiles.add(((m + 15) // 16) * ((n + 15) // 16))
+                    edges |= {m, n}
+    every = {(False, False), (False, True), (True, False), (True, True)}
+    assert seen_l == every and seen_r == every
+    assert both_scalar_beside_wide >= 2
+    assert {3, 5, 16, 17, 18, 31, 33} <= summed
+    assert 6 in tiles and max(tiles) > 4
+    assert {16, 17, 18, 20, 31, 33} <= edges
+    for name in ("P1", "P2", "P1_k3", "P1_k1"):  # all of them walk in the LDS, "scratch" does not
+        ba, bb, (_, k, _) = cnp.EXACT_PROFILES[name]
+        env = max(x * y for x, y in zip(ba, bb))
+        t = max(k * max(ba[s + 1] * bb[s], ba[s] * bb[s + 1]) for s in range(len(ba) - 1))
+        assert 2 * env + t <= CONTRACTION_LDS_DOUBLES
+    ba, bb, (_, k, _) = cnp.EXACT_PROFILES["scratch"]
+    assert 2 * ba[1] * bb[1] + k * ba[2] * bb[1] == 8448 > CONTRACTION_LDS_DOUBLES
