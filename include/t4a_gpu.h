@@ -987,7 +987,7 @@ t4a_gpu_status t4a_gpu_tci2_chain_stats(const t4a_gpu_tci2* h, uint64_t* out /* 
 t4a_gpu_status t4a_gpu_tci2_chain_stats_ext(const t4a_gpu_tci2* h, uint64_t* out /* [4] */);
 /* out[0] asynchronous fill_site_tensors issued by the optimisation loop, out[1] of them replayed from the captured HIP graph, out[2]
  * graph captures (a capture happens the second time a fill with the same signature — device addresses, shapes, staging buffers —
- * is issued; handles whose cores were exported / imported through stream 0 never replay: csrc/tci2.hip issue_fill_ops). */
+ * is issued; handles whose cores were exported / imported through stream 0 never replay: csrc/tci2_fill.hip issue_fill_ops). */
 t4a_gpu_status t4a_gpu_tci2_fill_stats(const t4a_gpu_tci2* h, uint64_t* out /* [3] */);
 /* PivotSearchStrategy::Rook on this handle: out[0] searches that ran device-resident (one launch, one host synchronisation per bond:
  * built-in functors), out[1] rows / columns they visited, out[2] searches driven from the host (callback functions: one round trip per

@@ -14,7 +14,7 @@ CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "lib")
 OBJ = os.path.join(HERE, "build")
 SOURCES = ["kernels_rrlu.hip", "kernels_rrlu_reg.hip", "rrlu_xcd_plan.hip", "kernels_rrlu_xcd2.hip", "kernels_rrlu_xcd2_group.hip", "kernels_rrlu_xcd2m.hip", "kernels_rrlu_wg.hip", "kernels_rrlu_wg_group.hip", "kernels_rrlu_w1.hip", "kernels_rrlu_global.hip", "kernels_pi.hip", "kernels_chain.hip", "kernels_small.hip", "kernels_dense.hip", "kernels_linalg.hip",
-           "kernels_tt.hip", "kernels_mpo.hip", "kernels_contraction.hip", "pool.hip", "engine.hip", "rook.hip", "tt.hip", "mpo.hip", "contraction.hip", "globalsearch.hip", "tci2.hip", "tci2_chain.hip", "tci2_small.hip", "conversion.hip", "patching.hip", "tree.hip", "quantics.hip", "tensorops.hip", "dense.hip", "aci.hip", "quanticstransform.hip", "capi.hip"]
+           "kernels_tt.hip", "kernels_mpo.hip", "kernels_contraction.hip", "pool.hip", "engine.hip", "rook.hip", "tt.hip", "mpo.hip", "contraction.hip", "globalsearch.hip", "tci2.hip", "tci2_fill.hip", "tci2_chain.hip", "tci2_small.hip", "conversion.hip", "patching.hip", "tree.hip", "quantics.hip", "tensorops.hip", "dense.hip", "aci.hip", "quanticstransform.hip", "capi.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function",
          "-fvisibility=hidden"] + os.environ.get("T4A_EXTRA_FLAGS", "").split()  # e.g. -DT4A_RRLU_TRACE (tools/trace_arrivals.py)
 # per-source flags.  kernels_dense.hip: keep MFMA accumulators in VGPRs — in AGPR form the compiler moves all of them between the
@@ -94,14 +94,14 @@ def build(force=False, verbose=True):
         run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs)
     with open(stamp, "w") as f:
         f.write(flags_now)
-    # test-hook twin (tests/test_gpu_chain.py: fault injection into the issue of a pending fill_site_tensors): tci2.hip compiled with
+    # test-hook twin (tests/test_gpu_chain.py: fault injection into the issue of a pending fill_site_tensors): tci2_fill.hip compiled with
     # -DT4A_TEST_HOOKS, every other object shared with the production library — which therefore carries no injector
     hooks = os.path.join(OUT, "libt4a_gpu_testhooks.so")
-    src = os.path.join(CSRC, "tci2.hip")
-    hobj = os.path.join(OBJ, "tci2_testhooks.obj")
+    src = os.path.join(CSRC, "tci2_fill.hip")
+    hobj = os.path.join(OBJ, "tci2_fill_testhooks.obj")
     if force or jobs or _newer(hobj, [src] + sorted(_includes(src))) or not os.path.exists(hooks):
         run([hipcc] + FLAGS + ["-DT4A_TEST_HOOKS", "-c", src, "-o", hobj])
-        run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", hooks] + [o for o in objs if os.path.basename(o) != "tci2.o"] + [hobj])
+        run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", hooks] + [o for o in objs if os.path.basename(o) != "tci2_fill.o"] + [hobj])
     return lib
 
 

@@ -7,7 +7,6 @@
 #include <exception>
 
 #include <algorithm>
-#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstdlib>
@@ -48,38 +47,6 @@ __global__ void __launch_bounds__(256) pack_right_core_kernel(const double* __re
         const int r = (int)(e / ((size_t)L * S));
         const int col = s * R + r;
         core[e] = (l < mrows && col < mcols) ? mat[(size_t)col * ldm + l] : 0.0;
-    }
-}
-
-// core[l,s,r] = xt[r + ldx*(l*S+s)]   (tensorci2.rs:1167-1181)
-__global__ void __launch_bounds__(256) pack_fill_core_kernel(const double* __restrict__ xt, int ldx,
-                                                             double* __restrict__ core, int L, int S, int R,
-                                                             const int* info)
-{
-    const size_t total = (size_t)L * S * R;
-    const bool zero = info && *info == -1; // numerically zero pivot matrix: zero core (tensorci2.rs:1154-1157)
-    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
-        const int l = (int)(e % L);
-        const int s = (int)((e / L) % S);
-        const int r = (int)(e / ((size_t)L * S));
-        core[e] = zero ? 0.0 : xt[(size_t)(l * S + s) * ldx + r];
-    }
-}
-
-// all cores of one fill_site_tensors in a single launch (blockIdx.y = site job; PackJob: kernels.hpp)
-__global__ void __launch_bounds__(256) pack_fill_batched_kernel(const PackJob* __restrict__ jobs)
-{
-    const PackJob j = jobs[blockIdx.y];
-    const size_t total = (size_t)j.L * j.S * j.R;
-    const bool zero = j.info && *j.info == -1; // numerically zero pivot matrix: zero core (tensorci2.rs:1154-1157)
-    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
-        const int l = (int)(e % j.L);
-        const int s = (int)((e / j.L) % j.S);
-        const int r = (int)(e / ((size_t)j.L * j.S));
-        if (j.last)
-            j.core[e] = j.src[(size_t)r * j.ld + (l * j.S + s)]; // Pi1 itself (tensorci2.rs:1109-1128), R == 1
-        else
-            j.core[e] = zero ? 0.0 : j.src[(size_t)(l * j.S + s) * j.ld + r]; // (tensorci2.rs:1167-1181)
     }
 }
 
@@ -146,7 +113,7 @@ Tci2::Tci2(const std::vector<size_t>& dims) : n_(dims.size()), local_dims(dims),
     last_sweep_shapes.assign(n_ - 1, {0, 0, 0});
     d_maxbits_.reserve(2);
     ev_pi_.init();
-    ev_fill_.init();
+    fill_.ev.init();
 }
 
 Tci2::~Tci2()
@@ -155,11 +122,11 @@ Tci2::~Tci2()
     for (hipEvent_t e : chain_.t0) (void)hipEventDestroy(e);
     for (hipEvent_t e : chain_.t1) (void)hipEventDestroy(e);
     if (chain_.group_ev) (void)hipEventDestroy(chain_.group_ev);
-    if (export_event_) (void)hipEventDestroy(export_event_);
-    if (import_event_) (void)hipEventDestroy(import_event_);
-    if (import_stream_) pool::stream_put(import_stream_, 2); // (synchronises it)
-    if (fill_graph_exec_) (void)hipGraphExecDestroy(fill_graph_exec_);
-    if (fill_stream_) pool::stream_put(fill_stream_, 2); // (synchronises it)
+    if (fill_.export_event) (void)hipEventDestroy(fill_.export_event);
+    if (fill_.import_event) (void)hipEventDestroy(fill_.import_event);
+    if (fill_.import_stream) pool::stream_put(fill_.import_stream, 2); // (synchronises it)
+    if (fill_.graph_exec) (void)hipGraphExecDestroy(fill_.graph_exec);
+    if (fill_.stream) pool::stream_put(fill_.stream, 2); // (synchronises it)
     // every buffer of this handle (and of its engine) was only ever used on the three streams that are idle now: the blocks
     // go back to the process-wide cache without a device-wide synchronisation, which would wait for the other handles' chains
     if (hipStreamSynchronize(eng.stream()) == hipSuccess) idle_scope_.arm();
@@ -531,33 +498,6 @@ void Tci2::build_side(size_t bond, bool cols, const IndexSet& extra, SidePrep& o
     out.acc.clear();
     if (fn_.builtin()) accumulate(out.set, cols ? bond + 1 : 0, out.acc);
     out.valid = true;
-}
-
-void Tci2::invalidate_fill_cache()
-{
-    for (auto& f : fill_cache_) f.valid = false;
-}
-
-// Accumulators fill_site_tensors needs for site b (tensorci2.rs:1101-1145): J_b, kron(I_b, d_b) and I_{b+1}.
-void Tci2::prepare_fill_site(size_t b)
-{
-    if (!fn_.builtin() || b >= n_) return;
-    if (chain_.digits_stale) { // after a bond chain the accumulators are in the pinned mirror of the device tables: no digits needed
-        prepare_fill_site_from_mirror(b);
-        return;
-    }
-    if (fill_cache_.size() != n_) fill_cache_.assign(n_, FillAcc());
-    if (shard_world > 1 && (b % shard_world) != shard_rank) return;
-    FillAcc& f = fill_cache_[b];
-    f.valid = false;
-    if (i_set[b].count == 0 || j_set[b].count == 0) return;
-    accumulate(j_set[b], b + 1, f.accJ);
-    accumulate(kronecker_i(b), 0, f.accK);
-    if (b + 1 < n_)
-        accumulate(i_set[b + 1], 0, f.accI);
-    else
-        f.accI.clear();
-    f.valid = true;
 }
 
 LuciResult Tci2::luci_on_sets(const IndexSet& is, const IndexSet& js, const RrLUOptions& o, bool need_factors,
@@ -949,602 +889,6 @@ void Tci2::make_canonical(double rel_tol, double abs_tol, size_t max_bond_dim)
     sweep1site(true, rel_tol, abs_tol, max_bond_dim, true);
 }
 
-// tensorci2.rs:1065-1186 — all sites are independent given the final I/J sets, so the evaluations, the
-// partial-pivot LU factorisations and the triangular solves of every site are issued as batches.
-// The whole fill runs on its own stream.  With `async` (optimize loop, nsearch == 0, built-in functor) the host
-// does not wait: the next half-sweep's bond updates only need the index sets, so the fill overlaps with them
-// (the rrLU chain leaves most CUs idle).  Errors (singular pivot matrix) surface at the next fill_wait().
-void Tci2::fill_site_tensors() { fill_site_tensors_impl(false); }
-
-// Issues the stream operations of one fill.  Fills of consecutive sweeps at saturated rank are operation-for-operation
-// identical (same device addresses, shapes and pinned staging buffer), so the sequence is captured into a HIP graph the
-// second time a signature is seen and replayed afterwards: one submission instead of ~25, which also keeps the
-// runtime's submission path free for the latency-critical bond updates on the main stream.
-void Tci2::issue_fill_ops(std::vector<std::function<void()>>& ops, const std::vector<uint64_t>& sig)
-{
-    hipStream_t st = fill_stream_;
-    static const bool use_graph = std::getenv("T4A_NO_FILL_GRAPH") == nullptr;
-    if (fill_timed_) T4A_HIP(hipEventRecord(ev_fill_.a, st));
-    bool done = false;
-    // (no graph replay on a handle whose cores are exported / imported through the LEGACY DEFAULT STREAM.  Round 4 saw GPU memory
-    // faults in 25 - 75 % of `bench.py --mode site-shard` runs with replay on; round 5 bisected them (tools/r5_gpu_shardfault*.sh,
-    // profiles/r05_fill_graph_fault_bisect.txt, five runs per arm): they need the replay AND an event protocol that runs through
-    // stream 0 — torch's current stream in a process that never selected another — in BOTH directions (export: stream 0 waits for an
-    // event recorded behind the replay; import: the import stream waits for an event recorded on stream 0).  Replacing either event
-    // by a host wait, moving torch to a side stream, or a device-wide synchronisation in front of the replay: 0 faults of 5; the
-    // pool, the bond chain, kernel serialisation, the order of the export copies and the copy nodes of the graph: no influence.
-    // Every pointer the graph holds is part of the signature (checked again: tables, staging buffers, tickets, flags), so this is
-    // the runtime's implicit ordering of stream 0 against the streams a graph launch runs on, not a stale pointer.  parallel.py and
-    // bench.py therefore exchange on a side stream; a caller that hands in stream 0 gets direct issue, which is what the
-    // round-4 stop-gap did for every shared handle.)
-    // the root cause is NOT identified (the library's streams are non-blocking, so "implicit ordering with stream 0"
-    // does not explain the faults, and no multi-GPU soak of the patch-farm path exists).  The default is therefore the round-4 guard —
-    // no replay on ANY handle whose site tensors are exported / imported asynchronously; the relaxed guard (replay unless the legacy
-    // stream or a blocking stream took part) is an opt-in: t4a_gpu_tci2_set_chain bit 4.  The gain it buys is ~0.4 % of a sweep.
-    const bool shared_ok = !cores_shared_async_ || (fill_graph_relaxed && !cores_shared_legacy_stream_);
-    if (use_graph && !fill_graph_broken_ && shared_ok) {
-        if (fill_graph_exec_ && sig == fill_graph_sig_) {
-            T4A_HIP(hipGraphLaunch(fill_graph_exec_, st));
-            ++fill_stats_[1];
-            done = true;
-        } else if (sig == fill_last_sig_) { // second time in a row: worth capturing
-            if (fill_graph_exec_) {
-                (void)hipGraphExecDestroy(fill_graph_exec_);
-                fill_graph_exec_ = nullptr;
-            }
-            hipGraph_t graph = nullptr;
-            pool::capture_begin(); // (no device-wide synchronisation of another handle's thread may fall into the capture)
-            bool ok = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess;
-            if (ok) {
-                try {
-                    for (auto& f : ops) f();
-                } catch (...) {
-                    ok = false;
-                }
-                if (hipStreamEndCapture(st, &graph) != hipSuccess || !graph) ok = false;
-            }
-            pool::capture_end();
-            if (ok && hipGraphInstantiate(&fill_graph_exec_, graph, nullptr, nullptr, 0) != hipSuccess) {
-                fill_graph_exec_ = nullptr;
-                ok = false;
-            }
-            if (graph) (void)hipGraphDestroy(graph);
-            if (ok) {
-                fill_graph_sig_ = sig;
-                T4A_HIP(hipGraphLaunch(fill_graph_exec_, st));
-                ++fill_stats_[2];
-                done = true;
-            } else {
-                (void)hipGetLastError();
-                fill_graph_broken_ = true; // never try again on this handle; fall through to the direct issue
-            }
-        }
-    }
-    fill_last_sig_ = sig;
-    ++fill_stats_[0];
-    if (!done)
-        for (auto& f : ops) f();
-    if (fill_timed_) T4A_HIP(hipEventRecord(ev_fill_.b, st));
-}
-
-void Tci2::fill_wait()
-{
-    if (import_inflight_) { // cores of the other ranks' sites (site-sharded fill) still on their way into this handle
-        import_inflight_ = false;
-        T4A_HIP(hipStreamSynchronize(import_stream_));
-    }
-    if (!fill_inflight_) return;
-    fill_inflight_ = false;
-    T4A_HIP(hipStreamSynchronize(fill_stream_));
-    T4A_HIP(hipGetLastError());
-    if (eng.prof.enabled && fill_timed_) {
-        float ms = 0.f;
-        T4A_HIP(hipEventElapsedTime(&ms, ev_fill_.a, ev_fill_.b));
-        eng.prof.v[4] += ms;
-        eng.prof.v[5] += 1.0;
-    }
-    fill_timed_ = false;
-    for (size_t k = 0; k < fill_solved_sites_.size(); ++k)
-        if (h_fillinfo_.get()[fill_solved_sites_[k]] > 0) {
-            const size_t site = fill_solved_sites_[k];
-            fill_solved_sites_.clear();
-            throw Error(T4A_GPU_INTERNAL_ERROR, "one-site interpolation solve failed: singular pivot matrix at site " +
-                                                    std::to_string(site));
-        }
-    fill_solved_sites_.clear();
-}
-
-void Tci2::fill_site_tensors_impl(bool async)
-{
-    fn_.require("tci2");
-    // accumulators built ahead are only trusted when optimize() vouches for them (same half-sweep, sets final)
-    const bool trust_cache = fill_cache_trusted_;
-    fill_cache_trusted_ = false;
-    static const bool host_prof_fill = std::getenv("T4A_HOST_PROFILE") != nullptr;
-    const auto hpf_t0 = std::chrono::steady_clock::now();
-    static double hpf_sec[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    auto hpf_mark = [&](int k, std::chrono::steady_clock::time_point& t) {
-        if (!host_prof_fill) return;
-        const auto now = std::chrono::steady_clock::now();
-        hpf_sec[k] += std::chrono::duration<double, std::micro>(now - t).count();
-        t = now;
-    };
-    auto hpf_t = hpf_t0;
-    if (!trust_cache) invalidate_fill_cache();
-    if (!fn_.builtin()) sync_digits();
-    fill_wait(); // the scratch arenas of the previous fill are free again
-    if (!fill_stream_) fill_stream_ = pool::stream_get(2); // lowest priority, recycled through the process-wide cache
-    const bool builtin = fn_.builtin();
-    static const bool sync_fill = std::getenv("T4A_SYNC_FILL") != nullptr; // measurement switch: no overlap at all
-    if (!builtin || sync_fill) async = false;
-    std::vector<std::function<void()>> ops; // the stream operations of this fill, in order (no event records)
-    std::vector<uint64_t> sig;              // everything those operations depend on: equal signature <=> same graph
-    auto dev = [&](std::function<void()> f) { ops.push_back(std::move(f)); };
-    auto sg = [&](uint64_t v) { sig.push_back(v); };
-    // everything of this fill is ordered after the work already enqueued on the main stream (the per-bond path writes site
-    // tensors there).  After a bond chain nothing on the main stream concerns the fill — and the NEXT chain may already be
-    // running on it: no wait then.
-    const bool no_main_sync = fill_no_main_sync_ && fn_.builtin();
-    fill_no_main_sync_ = false;
-    if (!no_main_sync) T4A_HIP(hipStreamSynchronize(eng.stream()));
-    hipStream_t st = fill_stream_;
-    struct SiteJob {
-        size_t b;
-        size_t ni, nj, np;
-        size_t offA, offB; // offsets (doubles) into d_fillA_ / d_fillB_
-        size_t accJ, accK, accI; // offsets (u64) into the accumulator arena: J_b, kron_i(b), I_{b+1}
-        bool last;
-    };
-    std::vector<SiteJob> jobs;
-    size_t totA = 0, totB = 0;
-    for (size_t b = 0; b < n_; ++b) {
-        if (shard_world > 1 && (b % shard_world) != shard_rank) continue;
-        const size_t ni = i_set[b].count * local_dims[b];
-        const size_t nj = j_set[b].count;
-        if (ni == 0 || nj == 0) { // tensorci2.rs:1074-1092
-            const size_t left_dim = (b == 0) ? 1 : std::max<size_t>(i_set[b].count, 1);
-            const size_t right_dim = (b == n_ - 1) ? 1 : std::max<size_t>(i_set[b + 1].count, 1);
-            DevCore& c = cores[b];
-            c.buf.reserve(std::max<size_t>(left_dim * local_dims[b] * right_dim, 1));
-            c.l = left_dim;
-            c.s = local_dims[b];
-            c.r = right_dim;
-            {
-                double* ptr = c.buf.get();
-                const size_t cnt = c.size();
-                sg(0xF111ull);
-                sg((uint64_t)(uintptr_t)ptr);
-                sg((uint64_t)cnt);
-                dev([=]() { fill_launch(ptr, cnt, 0.0, st); });
-            }
-            continue;
-        }
-        SiteJob j;
-        j.b = b;
-        j.ni = ni;
-        j.nj = nj;
-        j.last = (b == n_ - 1);
-        j.np = j.last ? 0 : i_set[b + 1].count;
-        if (!j.last && j.np != nj)
-            throw Error(T4A_GPU_INTERNAL_ERROR, "one-site interpolation solve failed: pivot matrix at bond " +
-                                                    std::to_string(b) + " is not square (" + std::to_string(j.np) + " x " +
-                                                    std::to_string(nj) + ")");
-        j.offA = totA;
-        j.offB = totB;
-        j.accJ = j.accK = j.accI = 0;
-        totA += j.last ? 0 : nj * j.np;
-        totB += nj * ni;
-        jobs.push_back(j);
-    }
-    hpf_mark(0, hpf_t);
-    if (jobs.empty()) {
-        for (auto& f : ops) f();
-        T4A_HIP(hipStreamSynchronize(st));
-        return;
-    }
-    if (!builtin) { // host-callback mode stays immediate (its evaluations are synchronous anyway)
-        for (auto& f : ops) f();
-        ops.clear();
-    }
-    d_fillA_.reserve(std::max<size_t>(totA, 1));
-    d_fillB_.reserve(totB);
-    // max|P| bits (n_ u64) and solve status (n_ ints) share one allocation -> one memset
-    // max|P| bits (n_ u64), solve status (n_ ints) and the work tickets of the trailing updates share one allocation -> one memset
-    const size_t fm_words = n_ + (n_ + 1) / 2 + (LU_MAX_PANEL_STEPS + 1) / 2;
-    d_fillmax_.reserve(fm_words);
-    unsigned long long* d_max = d_fillmax_.get();
-    int* d_info = reinterpret_cast<int*>(d_fillmax_.get() + n_);
-    unsigned* d_tickets = reinterpret_cast<unsigned*>(d_fillmax_.get() + n_ + (n_ + 1) / 2);
-    // beside a bond chain the fill keeps off the chain's XCD where it could not be placed anyway (lu_update_kernel)
-    const int avoid_xcc = (no_main_sync && !xcd_disabled()) ? eng.xcc() : -1;
-    h_fillinfo_.reserve(n_);
-    {
-        unsigned long long* ptr = d_fillmax_.get();
-        const size_t bytes = fm_words * sizeof(unsigned long long);
-        fill_timed_ = eng.prof.enabled;
-        sg((uint64_t)(uintptr_t)ptr);
-        sg((uint64_t)bytes);
-        dev([=]() { T4A_HIP(hipMemsetAsync(ptr, 0, bytes, st)); });
-        if (!builtin) {
-            if (fill_timed_) T4A_HIP(hipEventRecord(ev_fill_.a, st));
-            for (auto& f : ops) f();
-            ops.clear();
-            // the callback evaluations below write max|P| on the MAIN stream: the zeroing must have landed before them, or a late
-            // memset (queued behind other handles' fills, e.g. in fill_site_tensors_group) erases max|P| and the guard zeroes the core
-            T4A_HIP(hipStreamSynchronize(st));
-        }
-    }
-
-    // core shapes are known up front: allocate them now so that every device address below is final
-    for (const SiteJob& j : jobs) {
-        const size_t left_dim = (j.b == 0) ? 1 : i_set[j.b].count;
-        const size_t S = local_dims[j.b];
-        DevCore& c = cores[j.b];
-        c.l = left_dim;
-        c.s = S;
-        c.r = j.last ? 1 : j.np;
-        c.buf.reserve(std::max<size_t>(c.size(), 1));
-    }
-
-    // solve descriptors (device addresses only): built before the upload so that ONE host-to-device copy carries
-    // the accumulators, the evaluation jobs, the LU / triangular-solve problems and the packing jobs
-    std::vector<LuProblem> lups;
-    std::vector<TrsmProblem> trl, tru;
-    std::vector<PackJob> packs;
-    size_t piv_total = 0;
-    for (const SiteJob& j : jobs)
-        if (!j.last) piv_total += j.np;
-    d_fillpiv_.reserve(std::max<size_t>(piv_total, 1));
-    size_t piv_off = 0;
-    int max_n = 0, max_nrhs = 0;
-    size_t max_core = 1;
-    fill_solved_sites_.clear();
-    double flops = 0.0;
-    for (const SiteJob& j : jobs) {
-        const DevCore& c = cores[j.b];
-        PackJob pk;
-        pk.src = d_fillB_.get() + j.offB;
-        pk.core = c.buf.get();
-        pk.L = (int)c.l;
-        pk.S = (int)c.s;
-        pk.R = (int)c.r;
-        pk.last = j.last ? 1 : 0;
-        pk.ld = j.last ? (int)j.ni : (int)j.nj;
-        pk.info = j.last ? nullptr : (const int*)(d_info + j.b);
-        pk.pad_ = 0;
-        packs.push_back(pk);
-        max_core = std::max(max_core, c.size());
-        if (j.last) continue;
-        LuProblem lp;
-        lp.A = d_fillA_.get() + j.offA;
-        lp.lda = (int)j.nj;
-        lp.n = (int)j.nj;
-        lp.piv = d_fillpiv_.get() + piv_off;
-        lp.info = d_info + j.b;
-        lp.B = d_fillB_.get() + j.offB;
-        lp.ldb = (int)j.nj;
-        lp.nrhs = (int)j.ni;
-        lp.pmax_bits = d_max + j.b;
-        piv_off += j.np;
-        lups.push_back(lp);
-        trl.push_back(lu_trsm_problem(lp, true, lp.info));
-        tru.push_back(lu_trsm_problem(lp, false, lp.info));
-        fill_solved_sites_.push_back(j.b);
-        max_n = std::max(max_n, lp.n);
-        max_nrhs = std::max(max_nrhs, lp.nrhs);
-        const double n = (double)j.np;
-        flops += (2.0 / 3.0) * n * n * n + 2.0 * n * n * (double)j.ni;
-    }
-    hpf_mark(1, hpf_t);
-    const size_t np_ = lups.size();
-    const size_t bytes_lu = np_ * sizeof(LuProblem), bytes_tr = 2 * np_ * sizeof(TrsmProblem);
-    const size_t bytes_pk = packs.size() * sizeof(PackJob);
-    auto up8 = [](size_t v) { return (v + 7) / 8 * 8; };
-
-    // (1) evaluations.  B_b = Pi1^T (nj x ni), A_b = P^T (nj x np) — evaluated directly in transposed form
-    //     (solve(P^T, Pi1^T), tensorci2.rs:1160-1162).
-    const LuProblem* d_lups = nullptr;
-    const TrsmProblem* d_trs = nullptr;
-    const PackJob* d_packs = nullptr;
-    const PiJob* d_pis = nullptr;
-    // small problems (BASELINE configs[1], the first iterations of every run): evaluation, solve and packing of all sites in ONE
-    // launch (fill_small_kernel) instead of five dependent ones — bitwise the same cores
-    bool small_fill = builtin;
-#ifdef T4A_TEST_HOOKS
-    // libt4a_gpu_testhooks.so only: the general five-launch path for small problems too, so that a test can compare the two bit by bit
-    // (tests/test_gpu_tci2.py::test_small_problem_fill_in_one_launch_is_bitwise_the_general_path)
-    if (std::getenv("T4A_TEST_NO_SMALL_FILL")) small_fill = false;
-#endif
-    for (const SiteJob& j : jobs)
-        if (j.nj > (size_t)FILL_SMALL_MAX_N || j.ni > (size_t)FILL_SMALL_MAX_RHS) small_fill = false;
-    if (builtin) {
-        std::vector<uint64_t> acc_all;
-        const size_t Kacc = (size_t)fn_.dev.n_acc;
-        for (SiteJob& j : jobs) {
-            const bool cached = fill_cache_.size() == n_ && fill_cache_[j.b].valid &&
-                                fill_cache_[j.b].accJ.size() == j.nj * Kacc && fill_cache_[j.b].accK.size() == j.ni * Kacc &&
-                                (j.last || fill_cache_[j.b].accI.size() == j.np * Kacc);
-            if (!cached) prepare_fill_site(j.b); // sites that became final only with the last bonds of the sweep
-            const FillAcc& f = fill_cache_[j.b];
-            j.accJ = acc_all.size();
-            acc_all.insert(acc_all.end(), f.accJ.begin(), f.accJ.end());
-            j.accK = acc_all.size();
-            acc_all.insert(acc_all.end(), f.accK.begin(), f.accK.end());
-            if (!j.last) {
-                j.accI = acc_all.size();
-                acc_all.insert(acc_all.end(), f.accI.begin(), f.accI.end());
-            }
-        }
-        invalidate_fill_cache();
-        hpf_mark(2, hpf_t);
-        const size_t bytes_acc = acc_all.size() * sizeof(uint64_t);
-        const size_t n_pi = 2 * jobs.size();
-        const size_t off_pi = up8(bytes_acc), off_lu = up8(off_pi + n_pi * sizeof(PiJob));
-        const size_t off_tr = up8(off_lu + bytes_lu), off_pk = up8(off_tr + bytes_tr);
-        const size_t total_bytes = up8(off_pk + bytes_pk);
-        h_fillacc_.reserve(total_bytes / 8);
-        d_fillacc_.reserve(total_bytes / 8);
-        hpf_mark(5, hpf_t);
-        char* hb = reinterpret_cast<char*>(h_fillacc_.get());
-        char* db = reinterpret_cast<char*>(d_fillacc_.get());
-        const uint64_t* da = d_fillacc_.get();
-        std::memcpy(hb, acc_all.data(), bytes_acc);
-        hpf_mark(6, hpf_t);
-        std::vector<PiJob> pis;
-        int max_M = 0, max_N = 0;
-        for (const SiteJob& j : jobs) {
-            eng.prof.v[11] += (double)j.ni * j.nj + (double)j.np * j.nj;
-            PiJob q;
-            q.pad_ = 0;
-            if (j.last) { // last site stores Pi1 itself (:1109-1128): ni x nj
-                q.rowacc = da + j.accK;
-                q.M = (int)j.ni;
-                q.colacc = da + j.accJ;
-                q.N = (int)j.nj;
-                q.out = d_fillB_.get() + j.offB;
-                q.ld = (int)j.ni;
-                q.max_abs_bits = nullptr;
-                pis.push_back(q);
-            } else {
-                q.rowacc = da + j.accJ;
-                q.M = (int)j.nj;
-                q.colacc = da + j.accK;
-                q.N = (int)j.ni;
-                q.out = d_fillB_.get() + j.offB;
-                q.ld = (int)j.nj;
-                q.max_abs_bits = nullptr;
-                pis.push_back(q);
-                q.colacc = da + j.accI;
-                q.N = (int)j.np;
-                q.out = d_fillA_.get() + j.offA;
-                q.max_abs_bits = d_max + j.b;
-                pis.push_back(q);
-            }
-        }
-        for (const PiJob& q : pis) {
-            max_M = std::max(max_M, q.M);
-            max_N = std::max(max_N, q.N);
-        }
-        std::memcpy(hb + off_pi, pis.data(), pis.size() * sizeof(PiJob));
-        if (np_) {
-            std::memcpy(hb + off_lu, lups.data(), bytes_lu);
-            std::memcpy(hb + off_tr, trl.data(), np_ * sizeof(TrsmProblem));
-            std::memcpy(hb + off_tr + np_ * sizeof(TrsmProblem), tru.data(), np_ * sizeof(TrsmProblem));
-        }
-        std::memcpy(hb + off_pk, packs.data(), bytes_pk);
-        hpf_mark(7, hpf_t);
-        {
-            const FnDevice fn = fn_.dev;
-            const PiJob* dj = reinterpret_cast<const PiJob*>(db + off_pi);
-            const int npi = (int)pis.size();
-            sg((uint64_t)(uintptr_t)db);
-            sg((uint64_t)(uintptr_t)hb);
-            sg((uint64_t)total_bytes);
-            sg((uint64_t)npi);
-            sg(((uint64_t)(uint32_t)max_M << 32) | (uint32_t)max_N);
-            sg((uint64_t)fn.fid * 16 + (uint64_t)fn.n_acc);
-            for (int q = 0; q < T4A_FN_MAX_PARAMS; ++q) {
-                uint64_t bits;
-                std::memcpy(&bits, &fn.params[q], sizeof(bits));
-                sg(bits);
-            }
-            sg((uint64_t)small_fill);
-            const bool small = small_fill;
-            dev([=]() {
-                T4A_HIP(hipMemcpyAsync(db, hb, total_bytes, hipMemcpyHostToDevice, st));
-                if (!small) pi_eval_batched_launch(fn, dj, npi, max_M, max_N, st);
-            });
-        }
-        d_lups = reinterpret_cast<const LuProblem*>(db + off_lu);
-        d_trs = reinterpret_cast<const TrsmProblem*>(db + off_tr);
-        d_packs = reinterpret_cast<const PackJob*>(db + off_pk);
-        d_pis = reinterpret_cast<const PiJob*>(db + off_pi);
-    } else {
-        // host callback: evaluated synchronously through eval_matrix (main stream), then continue on `st`
-        for (const SiteJob& j : jobs) {
-            IndexSet ik = kronecker_i(j.b);
-            const IndexSet& jb = j_set[j.b];
-            if (j.last) {
-                eval_matrix(ik, 0, jb, ik.width, d_fillB_.get() + j.offB, nullptr);
-            } else {
-                eval_matrix(jb, j.b + 1, ik, 0, d_fillB_.get() + j.offB, nullptr);
-                eval_matrix(jb, j.b + 1, i_set[j.b + 1], 0, d_fillA_.get() + j.offA, d_max + j.b);
-            }
-        }
-        T4A_HIP(hipStreamSynchronize(eng.stream()));
-        acc_used_ = 0;
-        const size_t off_tr = up8(bytes_lu), off_pk = up8(off_tr + bytes_tr), total_bytes = up8(off_pk + bytes_pk);
-        h_fillacc_.reserve(total_bytes / 8 + 1);
-        d_fillacc_.reserve(total_bytes / 8 + 1);
-        char* hb = reinterpret_cast<char*>(h_fillacc_.get());
-        char* db = reinterpret_cast<char*>(d_fillacc_.get());
-        if (np_) {
-            std::memcpy(hb, lups.data(), bytes_lu);
-            std::memcpy(hb + off_tr, trl.data(), np_ * sizeof(TrsmProblem));
-            std::memcpy(hb + off_tr + np_ * sizeof(TrsmProblem), tru.data(), np_ * sizeof(TrsmProblem));
-        }
-        std::memcpy(hb + off_pk, packs.data(), bytes_pk);
-        T4A_HIP(hipMemcpyAsync(db, hb, total_bytes, hipMemcpyHostToDevice, st));
-        d_lups = reinterpret_cast<const LuProblem*>(db);
-        d_trs = reinterpret_cast<const TrsmProblem*>(db + off_tr);
-        d_packs = reinterpret_cast<const PackJob*>(db + off_pk);
-    }
-
-    // (2) batched solve; the zero-pivot-matrix guard (:1154-1157) is evaluated on the device: lu_kernel reads
-    //     max|P| and flags info = -1, the solves skip flagged problems and the packing writes a zero core
-    {
-        const int npr = (int)np_;
-        const unsigned gx = blocks_for(max_core) > 64 ? 64 : blocks_for(max_core), gy = (unsigned)packs.size();
-        int* hinfo = h_fillinfo_.get();
-        const size_t info_bytes = n_ * sizeof(int);
-        sg((uint64_t)npr);
-        sg((uint64_t)(int64_t)avoid_xcc);
-        sg(((uint64_t)(uint32_t)max_n << 32) | (uint32_t)max_nrhs);
-        sg(((uint64_t)gx << 32) | gy);
-        sg((uint64_t)(uintptr_t)d_lups);
-        sg((uint64_t)(uintptr_t)d_trs);
-        sg((uint64_t)(uintptr_t)d_packs);
-        sg((uint64_t)(uintptr_t)d_info);
-        sg((uint64_t)(uintptr_t)hinfo);
-        const FnDevice fn = fn_.dev;
-        const int n_site_jobs = (int)jobs.size(), last_site = jobs.back().last ? 1 : 0;
-        const bool small = small_fill;
-        sg((uint64_t)(uintptr_t)d_pis);
-        sg(((uint64_t)n_site_jobs << 1) | (uint64_t)last_site);
-        dev([=]() {
-            if (small) {
-                fill_small_launch(fn, d_pis, d_lups, d_packs, n_site_jobs, last_site, st);
-                T4A_HIP(hipMemcpyAsync(hinfo, d_info, info_bytes, hipMemcpyDeviceToHost, st));
-                return;
-            }
-            if (npr) {
-                // blocked LU with the unit-lower forward substitution of the right-hand sides folded in; beyond its size
-                // limit the unblocked kernel + explicit forward solve (bitwise the same result)
-                // (round 5) one fused solve behind the LU of the pivot matrices; outside its size range the two-step path
-                if (!lu_solve_blocked_launch(d_lups, npr, max_n, max_nrhs, st, avoid_xcc, d_tickets)) {
-                    if (!lu_forward_blocked_launch(d_lups, npr, max_n, max_nrhs, st, avoid_xcc, d_tickets)) {
-                        lu_batched_launch(d_lups, npr, max_n, st);
-                        trsm_left_batched_launch(d_trs, npr, max_n, max_nrhs, st);
-                    }
-                    trsm_left_batched_launch(d_trs + npr, npr, max_n, max_nrhs, st);
-                }
-            }
-            // (3) pack all cores in one launch
-            hipLaunchKernelGGL(pack_fill_batched_kernel, dim3(gx, gy), dim3(256), 0, st, d_packs);
-            T4A_HIP(hipMemcpyAsync(hinfo, d_info, info_bytes, hipMemcpyDeviceToHost, st));
-        });
-    }
-    hpf_mark(3, hpf_t);
-    eng.prof.v[10] += flops;
-    if (!builtin) {
-        for (auto& f : ops) f();
-        if (fill_timed_) T4A_HIP(hipEventRecord(ev_fill_.b, st));
-        fill_inflight_ = true;
-    } else {
-        issue_fill_ops(ops, sig);
-        fill_inflight_ = true;
-    }
-    if (host_prof_fill) {
-        static double acc_ms = 0;
-        static long calls = 0;
-        acc_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - hpf_t0).count();
-        hpf_mark(4, hpf_t);
-        if (++calls % 20 == 0)
-            std::fprintf(stderr, "[host profile] fill_site_tensors host part %.1f us per call (wait+jobs %.1f, descriptors %.1f, "
-                                 "accumulators %.1f, staging %.1f, issue %.1f)\n",
-                         1e3 * acc_ms / calls, hpf_sec[0] / calls, hpf_sec[1] / calls, hpf_sec[2] / calls, hpf_sec[3] / calls,
-                         hpf_sec[4] / calls);
-        if (calls % 20 == 0)
-            std::fprintf(stderr, "[host profile]   staging in detail: reserve %.1f, accumulator copy %.1f, job tables %.1f us per call\n",
-                         hpf_sec[5] / calls, hpf_sec[6] / calls, hpf_sec[7] / calls);
-    }
-    if (!async) fill_wait();
-}
-
-// the legacy default stream, or a blocking stream (which orders against it exactly like it): no graph replay beside these
-static bool stream_orders_with_legacy(hipStream_t s)
-{
-    if (s == nullptr) return true;
-    unsigned flags = 0;
-    if (hipStreamGetFlags(s, &flags) != hipSuccess) {
-        (void)hipGetLastError();
-        return true; // (unknown: the careful answer)
-    }
-    return (flags & hipStreamNonBlocking) == 0;
-}
-
-// Copies every site tensor to dst + site * stride (doubles) WITHOUT blocking the host: the copies are ordered after a
-// fill that is still in flight (same stream) and `consumer` waits for them through an event.
-void Tci2::export_site_tensors_async(double* d_dst, size_t stride, hipStream_t consumer)
-{
-    cores_shared_async_ = true;
-    if (stream_orders_with_legacy(consumer)) cores_shared_legacy_stream_ = true; // (see issue_fill_ops)
-    hipStream_t st = fill_inflight_ ? fill_stream_ : eng.stream();
-    for (size_t s = 0; s < n_; ++s) {
-        const DevCore& c = cores[s];
-        if (c.size() > stride) throw Error(T4A_GPU_BUFFER_TOO_SMALL, "export_site_tensors: stride smaller than a site tensor");
-        if (c.size())
-            T4A_HIP(hipMemcpyAsync(d_dst + s * stride, c.buf.get(), c.size() * sizeof(double), hipMemcpyDeviceToDevice, st));
-    }
-    if (!export_event_) T4A_HIP(hipEventCreateWithFlags(&export_event_, hipEventDisableTiming));
-    T4A_HIP(hipEventRecord(export_event_, st));
-    T4A_HIP(hipStreamWaitEvent(consumer, export_event_, 0));
-}
-
-// Site-sharded fill (BASELINE.json configs[3]): the sites s = shard_rank + shard_world * k of this rank go to
-// d_dst + k * stride on the stream of the fill that may still be in flight; `consumer` (the stream of the all-gather) waits.
-void Tci2::export_site_shard_async(double* d_dst, size_t stride, hipStream_t consumer)
-{
-    cores_shared_async_ = true;
-    if (stream_orders_with_legacy(consumer)) cores_shared_legacy_stream_ = true; // (see issue_fill_ops)
-    hipStream_t st = fill_inflight_ ? fill_stream_ : eng.stream();
-    size_t k = 0;
-    for (size_t s = shard_rank; s < n_; s += shard_world, ++k) {
-        const DevCore& c = cores[s];
-        if (c.size() > stride) throw Error(T4A_GPU_BUFFER_TOO_SMALL, "export_site_shard: stride smaller than a site tensor");
-        if (c.size())
-            T4A_HIP(hipMemcpyAsync(d_dst + k * stride, c.buf.get(), c.size() * sizeof(double), hipMemcpyDeviceToDevice, st));
-    }
-    if (!export_event_) T4A_HIP(hipEventCreateWithFlags(&export_event_, hipEventDisableTiming));
-    T4A_HIP(hipEventRecord(export_event_, st));
-    T4A_HIP(hipStreamWaitEvent(consumer, export_event_, 0));
-}
-
-// The other ranks' cores out of the gathered buffer [world][per_rank][stride]: site s of rank r = s % world sits at
-// (r * per_rank + s / world) * stride.  Shapes follow from the (replicated) index sets AS THEY ARE NOW: call this in the same
-// half-sweep as the export on the other ranks (parallel.ShardedCoreExchange does), before the next bond update changes a
-// bond dimension.  The copies run on the handle's import stream after everything `producer` (the all-gather's stream) has
-// enqueued so far; nothing blocks the host, the local fill still in flight is not waited for (it writes other sites), and
-// the first reader of a core (fill_wait) waits for the import.
-void Tci2::import_site_shard_async(const double* d_src, size_t stride, size_t per_rank, hipStream_t producer)
-{
-    cores_shared_async_ = true;
-    if (stream_orders_with_legacy(producer)) cores_shared_legacy_stream_ = true; // (see issue_fill_ops)
-    if (!import_stream_) import_stream_ = pool::stream_get(2);
-    // at most one import in flight: the one of the previous half-sweep is long done (a whole chain of bond updates ago),
-    // and with it every read of the receive buffer that the caller is about to reuse
-    T4A_HIP(hipStreamSynchronize(import_stream_));
-    if (!import_event_) T4A_HIP(hipEventCreateWithFlags(&import_event_, hipEventDisableTiming));
-    T4A_HIP(hipEventRecord(import_event_, producer));
-    T4A_HIP(hipStreamWaitEvent(import_stream_, import_event_, 0));
-    for (size_t s = 0; s < n_; ++s) {
-        const size_t r = s % shard_world;
-        if (r == shard_rank) continue;
-        DevCore& c = cores[s];
-        const size_t l = (s == 0) ? 1 : std::max<size_t>(i_set[s].count, 1);
-        const size_t rr = (s + 1 == n_) ? 1 : std::max<size_t>(i_set[s + 1].count, 1);
-        const size_t count = l * local_dims[s] * rr;
-        if (count > stride) throw Error(T4A_GPU_BUFFER_TOO_SMALL, "import_site_shard: stride smaller than a site tensor");
-        c.buf.reserve(std::max<size_t>(count, 1));
-        c.l = l;
-        c.s = local_dims[s];
-        c.r = rr;
-        T4A_HIP(hipMemcpyAsync(c.buf.get(), d_src + (r * per_rank + s / shard_world) * stride, count * sizeof(double),
-                               hipMemcpyDeviceToDevice, import_stream_));
-    }
-    import_inflight_ = true;
-}
-
 // =================================================================================================
 // TT evaluation / sum
 // =================================================================================================
@@ -1745,48 +1089,7 @@ void Tci2::opt_begin(OptRun& r)
     // small problems: the whole loop in ONE launch (tci2_small.hip); it may finish the call, run the first iterations and hand the
     // rest back, or decline
     if (small_engine_run(r) && r.small_complete) return;
-    // bounded rank, built-in functor: site tensors and fill workspaces get their final size now (a buffer that grows goes
-    // through the process-wide cache, which waits for the whole device: once per iteration and buffer while ranks grow)
-    if (fn_.builtin() && options.max_bond_dim != 0 && options.max_bond_dim <= 1024) {
-        const size_t chi = options.max_bond_dim;
-        // what a bond can reach at all: min(chi, product of the local dimensions on either side) — the ends of a train stay small
-        std::vector<size_t> lb(n_ + 1, 1), rb(n_ + 1, 1);
-        for (size_t b = 0; b < n_; ++b) lb[b + 1] = std::min(chi, lb[b] * local_dims[b]);
-        for (size_t b = n_; b-- > 0;) rb[b] = std::min(chi, rb[b + 1] * local_dims[b]);
-        auto bond = [&](size_t b) { return std::min(lb[b], rb[b]); }; // bond b sits left of site b
-        size_t totA = 0, totB = 0, tot_cores = 0;
-        for (size_t b = 0; b < n_; ++b) {
-            if (shard_world > 1 && (b % shard_world) != shard_rank) continue;
-            const size_t l = bond(b), rr = bond(b + 1);
-            tot_cores += l * local_dims[b] * rr;
-            totA += rr * rr;
-            totB += rr * l * local_dims[b];
-        }
-        // ... and only while the whole reservation stays moderate (chi = 1024 over 100 sites is 4 GB per handle,
-        // times eight handles of a group, for a run that may stay at rank 10): beyond that the buffers grow on demand as before
-        const bool presize = (tot_cores + totA + totB) * sizeof(double) <= ((size_t)1 << 30);
-        for (size_t b = 0; presize && b < n_; ++b) {
-            if (shard_world > 1 && (b % shard_world) != shard_rank) continue;
-            cores[b].buf.reserve(std::max<size_t>(bond(b) * local_dims[b] * bond(b + 1), 1));
-        }
-        if (presize) {
-        d_fillA_.reserve(std::max<size_t>(totA, 1));
-        d_fillB_.reserve(std::max<size_t>(totB, 1));
-        d_fillpiv_.reserve(std::max<size_t>(n_ * chi, 1));
-        // the upload arena of a fill (accumulators of J_b, kron(I_b, d_b), I_{b+1} per site, then the job tables): grown once
-        // per iteration it cost every fill a device-wide wait in the middle of the next chain
-        size_t acc_words = 0;
-        for (size_t b = 0; b < n_; ++b) {
-            if (shard_world > 1 && (b % shard_world) != shard_rank) continue;
-            acc_words += chi * (2 + local_dims[b]) * (size_t)fn_.dev.n_acc;
-        }
-        const size_t desc_bytes = n_ * (2 * sizeof(PiJob) + sizeof(LuProblem) + 2 * sizeof(TrsmProblem) + 64) + 256;
-        h_fillacc_.reserve(acc_words + desc_bytes / 8 + 64);
-        d_fillacc_.reserve(acc_words + desc_bytes / 8 + 64);
-        d_fillmax_.reserve(n_ + (n_ + 1) / 2 + (LU_MAX_PANEL_STEPS + 1) / 2);
-        h_fillinfo_.reserve(n_);
-        }
-    }
+    fill_presize(options); // (bounded rank, built-in functor: site tensors and fill workspaces get their final size now)
 }
 
 bool Tci2::opt_iter_start(OptRun& r, bool defer_launch)
@@ -1854,30 +1157,6 @@ bool Tci2::opt_iter_start(OptRun& r, bool defer_launch)
     return true;
 }
 
-// ... and while the device works on the chain the host issues fill_site_tensors of the PREVIOUS iteration (its accumulators were
-// taken from the mirror when that iteration finished; nothing of it touches the main stream).  Part of opt_iter_finish; a
-// group calls it for every handle before it finishes the first one (the first chain_finish waits for the whole group's chain:
-// whatever the host issues after that no longer overlaps it).
-void Tci2::opt_iter_issue_pending_fill(OptRun& r)
-{
-    if (!r.pending_fill) return;
-    r.pending_fill = false;
-#ifdef T4A_TEST_HOOKS
-    {   // libt4a_gpu_testhooks.so only (build.py; tests/test_gpu_chain.py loads it in a child process): T4A_TEST_THROW_IN_FILL=n makes
-        // the n-th pending fill of the process fail while a chain is in flight.  The production library carries no fault injector.
-        static const long inject_at = std::getenv("T4A_TEST_THROW_IN_FILL") ? std::atol(std::getenv("T4A_TEST_THROW_IN_FILL")) : 0;
-        static std::atomic<long> issued{0};
-        if (inject_at > 0 && ++issued == inject_at)
-            throw Error(T4A_GPU_INTERNAL_ERROR, "injected failure while issuing fill_site_tensors (T4A_TEST_THROW_IN_FILL)");
-    }
-#endif
-    for (size_t b = 0; b < n_; ++b) prepare_fill_site(b); // (from the mirror of the previous chain; the new one writes the other mirror)
-    fill_cache_trusted_ = true;
-    fill_no_main_sync_ = true;
-    fill_site_tensors_impl(true);
-    if (!keep_site_tensors) invalidate_site_tensors(); // (the end of that iteration invalidated them, tensorci2.rs:707-708)
-}
-
 void Tci2::opt_iter_finish(OptRun& r)
 {
     const TCI2Options& options = r.options;
@@ -1888,7 +1167,7 @@ void Tci2::opt_iter_finish(OptRun& r)
     do { // (one pass; `break` = the convergence exit of the reference's loop)
         {
             OptSeg seg_(3);
-            opt_iter_issue_pending_fill(r);
+            opt_issue_pending_fill(r);
         }
         if (chained) {
             OptSeg seg_(4);
@@ -1938,9 +1217,7 @@ void Tci2::opt_iter_finish(OptRun& r)
             // has been enqueued (or after the loop): the device is busy with that chain while the host prepares the fill
             r.pending_fill = true;
         } else {
-            fill_cache_trusted_ = fill_ahead && !chained;
-            fill_no_main_sync_ = chained && chain_.digits_stale;
-            fill_site_tensors_impl(fill_async);
+            fill_run(FillOptions{fill_async, /*trust_cache*/ fill_ahead && !chained, /*no_main_sync*/ chained && chain_.digits_stale});
         }
         OptSeg seg_tail_(5);
         const double error = max_bond_error();
@@ -1965,23 +1242,11 @@ void Tci2::opt_iter_finish(OptRun& r)
     ++r.iter;
 }
 
-void Tci2::opt_end_issue_fill(OptRun& r)
-{
-    if (r.pending_fill) { // the last iteration's fill
-        r.pending_fill = false;
-        for (size_t b = 0; b < n_; ++b) prepare_fill_site(b);
-        fill_cache_trusted_ = true;
-        fill_no_main_sync_ = true;
-        fill_site_tensors_impl(true);
-        if (!keep_site_tensors) invalidate_site_tensors(); // (the end of that iteration invalidated them, tensorci2.rs:707-708)
-    }
-}
-
 void Tci2::opt_end(OptRun& r)
 {
     const TCI2Options& options = r.options;
     const bool final_sweep1site = r.final_sweep1site;
-    opt_end_issue_fill(r);
+    opt_issue_pending_fill(r); // the last iteration's fill
     // the cores of the last iteration are complete (deferred solve errors surface here); in pipelined mode the wait
     // is left to the first reader (site_tensor*, evaluate, export_site_tensors_async, the next fill)
     if (!keep_site_tensors || final_sweep1site) fill_wait();
@@ -2073,7 +1338,7 @@ void Tci2::optimize_group(const std::vector<Tci2*>& hs, const TCI2Options& optio
         // the chained handles first, the group's leader first of all: it holds the chip until its chain has completed, and a
         // handle on the per-bond path needs an XCD of its own
         for (size_t i : active)
-            if (runs[i].chained) hs[i]->opt_iter_issue_pending_fill(runs[i]); // (all of them while the group's chain still runs)
+            if (runs[i].chained) hs[i]->opt_issue_pending_fill(runs[i]); // (all of them while the group's chain still runs)
         t_fill += secs(tc, now());
         for (size_t i : active)
             if (runs[i].chained) hs[i]->opt_iter_finish(runs[i]);
@@ -2090,35 +1355,12 @@ void Tci2::optimize_group(const std::vector<Tci2*>& hs, const TCI2Options& optio
                      hs.size(), iters, 1e3 * t_start, 1e3 * t_launch, 1e3 * t_finish, 1e3 * t_fill, 1e3 * (g_chain_wait_seconds - wait0));
     // the last iteration's fills of ALL handles first (each on its own fill stream), then the waits: handle by handle the device
     // idled while the host issued the next handle's dozen launches
-    for (size_t i = 0; i < hs.size(); ++i) hs[i]->opt_end_issue_fill(runs[i]);
+    for (size_t i = 0; i < hs.size(); ++i) hs[i]->opt_issue_pending_fill(runs[i]);
     for (size_t i = 0; i < hs.size(); ++i) hs[i]->opt_end(runs[i]);
     } catch (...) {
         for (Tci2* h : hs) h->chain_abort(); // (the leader's abort waits for the group's stream and gives the chip back)
         throw;
     }
-}
-
-// fill_site_tensors on several handles: issue all, then complete all (t4a_gpu_tci2_fill_site_tensors_group)
-void Tci2::fill_site_tensors_group(const std::vector<Tci2*>& hs)
-{
-    for (Tci2* h : hs)
-        if (!h) throw Error(T4A_GPU_NULL_POINTER, "fill_site_tensors_group: null handle");
-    std::exception_ptr first_error;
-    for (Tci2* h : hs) {
-        try {
-            h->fill_site_tensors_impl(true); // asynchronous for built-in functors (a host callback fills synchronously)
-        } catch (...) {
-            if (!first_error) first_error = std::current_exception();
-        }
-    }
-    for (Tci2* h : hs) {
-        try {
-            h->fill_wait();
-        } catch (...) {
-            if (!first_error) first_error = std::current_exception();
-        }
-    }
-    if (first_error) std::rethrow_exception(first_error);
 }
 
 // crossinterpolate2 (tensorci2.rs:1513-1563)

@@ -4,6 +4,7 @@
 // master copy on the host (flat digit tables), all matrices and site tensors live on the device.
 #pragma once
 
+#include <cstring>
 #include <memory>
 #include <vector>
 
@@ -40,6 +41,51 @@ struct FromTensorTrainOptions { // tensorci/src/conversion.rs:20-36
     double tolerance = 1e-12;
     size_t max_bond_dim = 0; // 0 == None
     size_t max_iter = 3;
+};
+
+// The stream operations of one fill_site_tensors as data (tci2_fill.hip): fill_issue() reads these records and nothing else, so two
+// fills with bytewise equal records are the same operations, and the records are the key of the captured graph.  Trivially
+// copyable and value-initialised; FillOps has no padding (eight-byte fields first, an even number of ints behind them).
+struct FillZero { // the all-zero core of a site with an empty set
+    double* ptr;
+    size_t count;
+};
+struct FillOps { // the fixed part
+    void* flags;            // max|P| bits, solve status and tickets: one memset of flag_bytes
+    size_t flag_bytes;
+    void* stage_dev;        // the one host-to-device copy: accumulators and job tables out of the pinned staging buffer
+    const void* stage_host;
+    size_t stage_bytes;
+    const PiJob* pis;       // device tables inside stage_dev
+    const LuProblem* lups;
+    const TrsmProblem* trs; // [n_lu] unit-lower, then [n_lu] upper
+    const PackJob* packs;
+    unsigned* tickets;      // work tickets of the blocked LU's trailing updates (inside flags)
+    const int* info_dev;    // solve status: copied back to info_host behind everything else
+    int* info_host;
+    size_t info_bytes;
+    FnDevice fn;
+    int n_pi, max_M, max_N; // n_pi == 0: the candidate matrices are in place already (host callback)
+    int n_lu, max_n, max_nrhs;
+    int avoid_xcc;
+    unsigned pack_gx, pack_gy;
+    int n_site_jobs, last_site;
+    int small;              // 1: evaluation, solve and packing in one launch (fill_small_launch)
+};
+static_assert(sizeof(FillOps) == 13 * 8 + sizeof(FnDevice) + 12 * 4 && sizeof(FnDevice) == 8 + 8 * T4A_FN_MAX_PARAMS, "no padding: compared bytewise");
+struct FillRecords {
+    std::vector<FillZero> zeros;
+    FillOps ops{};
+    bool operator==(const FillRecords& o) const
+    {
+        return zeros.size() == o.zeros.size() && std::memcmp(&ops, &o.ops, sizeof(FillOps)) == 0 &&
+               (zeros.empty() || std::memcmp(zeros.data(), o.zeros.data(), zeros.size() * sizeof(FillZero)) == 0);
+    }
+};
+struct FillOptions { // (aggregate: FillOptions{async, trust_cache, no_main_sync})
+    bool async = false;        // do not wait for the fill (built-in functor only); fill_wait() completes it
+    bool trust_cache = false;  // the accumulators built ahead (prepare_fill_site) belong to the sets as they are now
+    bool no_main_sync = false; // the fill does not depend on work of the main stream (bond chain: no cores written there)
 };
 
 class Tci2 {
@@ -106,15 +152,13 @@ public:
     bool small_engine_eligible(const TCI2Options& options) const;
     bool small_engine_run(OptRun& r);
     void opt_begin(OptRun& r);
-    void opt_iter_issue_pending_fill(OptRun& r);
-    void opt_end_issue_fill(OptRun& r); // the last iteration's fill, issued without waiting (first half of opt_end; a group issues all of them first)
+    void opt_issue_pending_fill(OptRun& r); // the previous (after the loop: the last) iteration's fill, issued without waiting
     bool opt_iter_start(OptRun& r, bool defer_launch = false); // defer_launch: the chain is prepared, not launched (optimize_group)
     void opt_iter_finish(OptRun& r);
     void opt_end(OptRun& r);
     void sweep2site(bool forward, const TCI2Options& options);
     void sweep1site(bool forward, double rel_tol, double abs_tol, size_t max_bond_dim, bool update_tensors);
     void fill_site_tensors();
-    void fill_site_tensors_impl(bool async);
     void fill_wait(); // completes an asynchronous fill (and reports its deferred errors)
     void export_site_tensors_async(double* d_dst, size_t stride, hipStream_t consumer);
     void export_site_shard_async(double* d_dst, size_t stride, hipStream_t consumer);
@@ -136,8 +180,8 @@ public:
     // chain_walk_kernel) [1] 1-site sweeps (sweep1site) that ran as a chain [2] 1-site sweeps that were not eligible and ran bond
     // by bond [3] chained 1-site sweeps that fell back to the per-bond path part-way
     std::array<uint64_t, 4> chain_stats_ext{{0, 0, 0, 0}};
-    const uint64_t* fill_stats() const { return fill_stats_; }
-    const RookWork& rook_work() const { return rook_work_; } // [fills issued asynchronously, graph replays, graph captures]
+    const uint64_t* fill_stats() const { return fill_.stats; } // [fills issued asynchronously, graph replays, graph captures]
+    const RookWork& rook_work() const { return rook_work_; }
     bool chain_enabled = true;  // false: every half-sweep runs bond by bond (A/B measurements, tests)
     bool chain_verify = false;  // true: after every chain the device tables are read back and compared with the host's sets
     bool chain_event_timing = false; // profiling: rrLU launches of a chain are timed with HIP events around each launch instead of
@@ -227,20 +271,39 @@ private:
         const IndexSet* extra = nullptr;
         long fill_site = -1;        // a site whose I/J sets are already final: its fill accumulators can be built now
     } prefetch_;
+    // ---- fill_site_tensors (tci2_fill.hip) ----
     // accumulators of fill_site_tensors (J_b, kron_i(b), I_{b+1}) built ahead of time, site by site, while the bond
     // updates of the same half-sweep are running; only valid inside optimize() between the bond loop and its fill
     struct FillAcc {
         bool valid = false;
         std::vector<uint64_t> accJ, accK, accI;
     };
-    std::vector<FillAcc> fill_cache_;
-    bool fill_cache_trusted_ = false;
-    void issue_fill_ops(std::vector<std::function<void()>>& ops, const std::vector<uint64_t>& sig);
-    std::vector<uint64_t> fill_last_sig_, fill_graph_sig_;
-    hipGraphExec_t fill_graph_exec_ = nullptr;
-    bool fill_graph_broken_ = false;
+    struct FillState {
+        std::vector<FillAcc> cache;
+        DevBuf<double> A, B;                 // per site: P^T; Pi1^T, overwritten by the solution
+        DevBuf<int> piv;
+        DevBuf<unsigned long long> flags;    // [n] max|P| bits, [n] solve status (int), tickets
+        PinBuf<int> hinfo;                   // solve status on the host, read by fill_wait
+        PinBuf<uint64_t> hstage;             // accumulators and job tables of one fill ...
+        DevBuf<uint64_t> dstage;             // ... and their place on the device
+        std::vector<size_t> solved_sites;
+        EventTimer ev;
+        hipStream_t stream = nullptr, import_stream = nullptr;
+        hipEvent_t export_event = nullptr, import_event = nullptr;
+        bool inflight = false, timed = false, import_inflight = false;
+        bool cores_shared_async = false;         // an asynchronous export / import of cores was requested on this handle: fills are issued directly, not replayed from a graph (issue_fill_ops)
+        bool cores_shared_legacy_stream = false; // ... and stream 0 (the legacy default stream) was the consumer / producer of one: no graph replay of the fill (issue_fill_ops)
+        uint64_t stats[3] = {0, 0, 0};           // fills issued through issue_fill_ops, graph replays, graph captures
+        FillRecords last, graph;                 // the records of the previous fill; those the graph was captured from
+        hipGraphExec_t graph_exec = nullptr;
+        bool graph_broken = false;
+    } fill_;
+    void fill_run(FillOptions opt);
+    void fill_presize(const TCI2Options& options);
+    void issue_fill_ops(const FillRecords& rec);
+    void export_cores_async(size_t first, size_t step, double* d_dst, size_t stride, hipStream_t consumer, const char* what);
     void prepare_fill_site(size_t b);
-    void invalidate_fill_cache();                    // set by the sweep loop: which side of which bond is independent of the current one
+    void invalidate_fill_cache();
     void build_side(size_t bond, bool cols, const IndexSet& extra, SidePrep& out) const;
     LuciResult luci_on_sets(const IndexSet& is, const IndexSet& js, const RrLUOptions& o, bool need_factors,
                             const std::vector<uint64_t>* acc_rows = nullptr, const std::vector<uint64_t>* acc_cols = nullptr);
@@ -337,7 +400,6 @@ private:
     void chain_finish(const TCI2Options& options);
     void chain_abort() noexcept; // after an exception between launch and finish: wait, release the XCD, drop the chain's results
     void prepare_fill_site_from_mirror(size_t b);
-    bool fill_no_main_sync_ = false; // the next fill does not depend on work of the main stream (bond chain: no cores written there)
 
     // small-problem engine: input / result blocks (pinned), scratch site tensors
     PinBuf<char> small_in_, small_out_;
@@ -356,29 +418,10 @@ private:
     size_t cb_idx_cap_ = 0;
     PinBuf<double> cb_vals_;
     DevBuf<TtCoreDesc> d_coredesc_;
-    // fill_site_tensors scratch
     PinBuf<uint64_t> h_rookacc_; // rook_on_sets: pinned staging of the row / column accumulators
-    DevBuf<double> d_fillA_, d_fillB_;
-    DevBuf<int> d_fillpiv_, d_fillinfo_;
-    DevBuf<LuProblem> d_lup_;
-    DevBuf<TrsmProblem> d_trp_;
-    DevBuf<unsigned long long> d_fillmax_;
-    EventTimer ev_pi_, ev_fill_;
-    hipStream_t fill_stream_ = nullptr, import_stream_ = nullptr;
-    bool import_inflight_ = false;
-    bool cores_shared_legacy_stream_ = false; // ... and stream 0 (the legacy default stream) was the consumer / producer of one: no graph replay of the fill (issue_fill_ops)
-    uint64_t fill_stats_[3] = {0, 0, 0};       // fills issued through issue_fill_ops, graph replays, graph captures
-    bool cores_shared_async_ = false; // an asynchronous export / import of cores was requested on this handle: fills are issued directly, not replayed from a graph (issue_fill_ops)
+    EventTimer ev_pi_;
 public:
     bool fill_graph_relaxed = false;  // opt-in: replay the fill graph on a handle with shared site tensors unless the legacy / a blocking stream took part
-private:
-    hipEvent_t export_event_ = nullptr, import_event_ = nullptr;
-    bool fill_inflight_ = false, fill_timed_ = false;
-    std::vector<size_t> fill_solved_sites_;
-    PinBuf<int> h_fillinfo_;
-    PinBuf<uint64_t> h_fillacc_;
-    DevBuf<uint64_t> d_fillacc_;
-    PinBuf<char> h_fillprob_;
 };
 
 } // namespace t4a

@@ -223,9 +223,9 @@ void Tci2::chain_upload_hist(HistEntry& e, int slot)
 // accumulators fill_site_tensors needs for site b (J_b, kron(I_b, d_b), I_{b+1}; tensorci2.rs:1101-1145) from the mirror
 void Tci2::prepare_fill_site_from_mirror(size_t b)
 {
-    if (fill_cache_.size() != n_) fill_cache_.assign(n_, FillAcc());
+    if (fill_.cache.size() != n_) fill_.cache.assign(n_, FillAcc());
     if (shard_world > 1 && (b % shard_world) != shard_rank) return;
-    FillAcc& f = fill_cache_[b];
+    FillAcc& f = fill_.cache[b];
     f.valid = false;
     const size_t K = (size_t)chain_.n_acc, cap = chain_.cap;
     const ChainTab mi = chain_mirror(chain_.mcur, 0), mj = chain_mirror(chain_.mcur, 1);
