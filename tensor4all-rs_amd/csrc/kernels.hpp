@@ -88,7 +88,7 @@ struct FnDevice {
     double params[T4A_FN_MAX_PARAMS];
 };
 
-// ---- register-resident fast path (kernels_rrlu_reg.hip): left-orthogonal elimination only ----
+// ---- register-resident fast path (kernels_rrlu_reg.hip; shapes in rrlu_shapes.hpp, plans in rrlu_plan.hip): left-orthogonal elimination only ----
 constexpr int RRLU_MAX_COPIES = 8;
 constexpr int RRLU_FUSED_MAX_VALUES = 16; // fused Π build only for plans with RPT * CPT <= this
 struct RrluRegPlan {
@@ -154,7 +154,7 @@ struct RrluRegArgs {
     const int* rowmap;          // non-null: entry (i, j) of the kernel's matrix is A[rowmap[i] + dims[3] * j] (speculative candidate matrix)
     int ts_u64;                 // > 0: start / end time of the workgroup (wall_clock64) at u64 words ts_u64, ts_u64 + 1 of the result block (single-workgroup launches)
 };
-// false if the shape is outside the fast path (fall back to the LDS kernel)
+// false if the shape is outside the fast path (fall back to the LDS kernel); a plan always names a shape of rrlu_shapes.hpp
 bool rrlu_reg_make_plan(int M, int N, int num_cus, RrluRegPlan* out);
 size_t rrlu_reg_keys_bytes(const RrluRegPlan& plan);
 size_t rrlu_reg_cols_bytes(const RrluRegPlan& plan, int M);
@@ -243,8 +243,8 @@ void rrlu_xcd2_launch(const RrluXcdPlan& plan, const RrluXcdArgs& args, hipStrea
 // plans with big() (kernels_rrlu_xcd2m.hip): the same kernel body with agents on K XCDs and / or 20 - 24 row slots per lane
 void rrlu_xcd2m_launch(const RrluXcdPlan& plan, const RrluXcdArgs& args, hipStream_t stream);
 void rrlu_xcd2_group_launch(const RrluXcdPlan& plan, const RrluXcdGroupArgs& args, bool tie_row_major, hipStream_t stream);
-// One-workgroup kernel (kernels_rrlu_wg.hip): matrices up to 64 x 512 / 128 x 384 in the registers of one compute
-// unit, exchange through its LDS (one barrier per pivot step).  Same arguments and result block; finite matrices only (gives up
+// One-workgroup kernel (kernels_rrlu_wg.hip): matrices up to 64 x 128 / 128 x 64 (the shapes of rrlu_shapes.hpp) in the registers
+// of one compute unit, exchange through its LDS (one barrier per pivot step).  The plan comes from rrlu_plan.hip.  Same arguments and result block; finite matrices only (gives up
 // with iresult[1] == 2 like the second-generation single-XCD kernel).  spec_blocks: workgroups beside the factorising one that
 // evaluate the next bond's candidate matrix (bond chain).  The group launch runs slot x in workgroup x.
 bool rrlu_wg_make_plan(int M, int N, RrluXcdPlan* out, int spec_blocks = 0);

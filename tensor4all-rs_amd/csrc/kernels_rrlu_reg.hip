@@ -35,12 +35,13 @@
 // Thresholded speculative publication of the pivot column is compiled in (measured on MI355X: 42.1 -> 40.8 ms of rrLU per
 // sweep at d = 30, chi = 256; selecting the mode through RrluRegArgs::spec at run time costs the default path 2 ms of
 // code-generation noise, so it is a build-time choice: RrluRegArgs::spec is not read).
-#include "kernels.hpp"
+// Which <RPT, CPT, SINGLE, UNI> exist is the list in rrlu_shapes.hpp — the shapes rrlu_reg_make_plan (rrlu_plan.hip) selects — and
+// the launcher at the end of this file instantiates exactly those, one translation unit per RPT.
+#include "common.hpp"
+#include "rrlu_shapes.hpp"
 
 #include <mutex>
-
-#include <algorithm>
-#include <cstdlib>
+#include <string>
 
 namespace t4a {
 
@@ -160,51 +161,6 @@ __device__ __forceinline__ unsigned wave_min_u32(unsigned v)
     const unsigned c = (unsigned)__builtin_amdgcn_readlane((int)v, 32), d = (unsigned)__builtin_amdgcn_readlane((int)v, 48);
     const unsigned ab = a < b ? a : b, cd = c < d ? c : d;
     return ab < cd ? ab : cd;
-}
-
-__host__ __device__ inline size_t align16(size_t v) { return (v + 15) / 16 * 16; }
-
-struct RegSmem {
-    double* urow;            // TC*CPT pivot-row entries of the owned columns
-    double* lcol;            // M (single-workgroup mode only): raw pivot column
-    double* red_sc;          // 16
-    unsigned* red_pos;       // 16
-    double* red_val;         // 16
-    double* win_d;           // [0] value
-    int* win_i;              // [0] winner wg  [1] position key  [2] abort flag
-    unsigned short* posrow;  // M
-    unsigned short* poscol;  // N
-};
-
-__host__ __device__ inline size_t reg_smem_layout(int M, int N, int cols_per_wg, bool single, RegSmem* s, char* base)
-{
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        size_t o = off;
-        off = align16(off + bytes);
-        return o;
-    };
-    const size_t o_urow = take((size_t)cols_per_wg * 8);
-    const size_t o_lcol = take(single ? (size_t)M * 8 : 8);
-    const size_t o_rsc = take(16 * 8);
-    const size_t o_rpos = take(16 * 4);
-    const size_t o_rval = take(16 * 8);
-    const size_t o_wd = take(2 * 8);
-    const size_t o_wi = take(4 * 4);
-    const size_t o_pr = take((size_t)M * 2);
-    const size_t o_pc = take((size_t)N * 2);
-    if (s) {
-        s->urow = (double*)(base + o_urow);
-        s->lcol = (double*)(base + o_lcol);
-        s->red_sc = (double*)(base + o_rsc);
-        s->red_pos = (unsigned*)(base + o_rpos);
-        s->red_val = (double*)(base + o_rval);
-        s->win_d = (double*)(base + o_wd);
-        s->win_i = (int*)(base + o_wi);
-        s->posrow = (unsigned short*)(base + o_pr);
-        s->poscol = (unsigned short*)(base + o_pc);
-    }
-    return off;
 }
 
 #define T4A_RSTAMP(slot)                                                  \
@@ -861,124 +817,47 @@ void launch_one(const RrluRegPlan& plan, const RrluRegArgs& a, hipStream_t strea
     else launch_tie<RPT, CPT, SINGLE, UNI, false>(plan, a, stream);
 }
 
-template <int RPT, int CPT> void launch_rc(const RrluRegPlan& plan, const RrluRegArgs& a, hipStream_t stream)
-{
-    const bool uni = (plan.TR % 64) == 0;
-    if (plan.W == 1) {
-        if (uni) launch_one<RPT, CPT, true, true>(plan, a, stream);
-        else launch_one<RPT, CPT, true, false>(plan, a, stream);
-    } else {
-        if (uni) launch_one<RPT, CPT, false, true>(plan, a, stream);
-        else launch_one<RPT, CPT, false, false>(plan, a, stream);
-    }
-}
-
-template <int RPT> void launch_r(const RrluRegPlan& plan, const RrluRegArgs& a, hipStream_t stream)
-{
-    switch (plan.CPT) {
-    case 1: launch_rc<RPT, 1>(plan, a, stream); break;
-    case 2: launch_rc<RPT, 2>(plan, a, stream); break;
-    case 3: launch_rc<RPT, 3>(plan, a, stream); break;
-    case 4: launch_rc<RPT, 4>(plan, a, stream); break;
-    case 5: launch_rc<RPT, 5>(plan, a, stream); break;
-    case 6: launch_rc<RPT, 6>(plan, a, stream); break;
-    default: launch_rc<RPT, 8>(plan, a, stream); break;
-    }
-}
-
-int round_up(int v, int m) { return (v + m - 1) / m * m; }
-int norm_cpt(int c) { return c <= 1 ? 1 : (c <= 6 ? c : 8); }
+// This translation unit instantiates the shapes of rrlu_shapes.hpp with T4A_REG_RPT rows per thread: 1 here, 2 to 4 in
+// kernels_rrlu_reg_r2.hip ... _r4.hip, which include this file, so that the four compile side by side.  (Each holds one- and
+// multi-workgroup kernels: with only one kind in a unit the compiler specialises reg_smem_layout for it and emits other code.)
+#ifndef T4A_REG_RPT
+#define T4A_REG_RPT 1
+#define T4A_REG_MAIN_TU 1
+#endif
+#define T4A_CAT_(a, b) a##b
+#define T4A_CAT(a, b) T4A_CAT_(a, b)
 
 } // namespace
 
-bool rrlu_reg_make_plan(int M, int N, int num_cus, RrluRegPlan* out)
+void rrlu_reg_launch_rpt1(const RrluRegPlan& plan, const RrluRegArgs& a, hipStream_t stream);
+void rrlu_reg_launch_rpt2(const RrluRegPlan& plan, const RrluRegArgs& a, hipStream_t stream);
+void rrlu_reg_launch_rpt3(const RrluRegPlan& plan, const RrluRegArgs& a, hipStream_t stream);
+void rrlu_reg_launch_rpt4(const RrluRegPlan& plan, const RrluRegArgs& a, hipStream_t stream);
+
+void T4A_CAT(rrlu_reg_launch_rpt, T4A_REG_RPT)(const RrluRegPlan& plan, const RrluRegArgs& a, hipStream_t stream)
 {
-    RrluRegPlan plan;
-    // (the key-table poller reads 4 keys per lane and the engine reserves 256 slots: never plan more workgroups than that)
-    const int maxw = std::min(num_cus > 16 ? num_cus - 8 : num_cus, 256);
-    const long long elems = (long long)M * N;
-    bool found = false;
-    if (elems <= 64 * 64) {
-        // one workgroup: TR x TC thread grid with <= 4 x 8 elements per thread; minimise the per-thread work,
-        // then the thread count
-        int best_cost = 1 << 30;
-        for (int T = 64; T <= 512; T *= 2) {
-            for (int TR = 16; TR <= T; TR *= 2) {
-                const int TC = T / TR;
-                const int RPT = (M + TR - 1) / TR;
-                const int CPT = norm_cpt((N + TC - 1) / TC);
-                if (RPT > 4 || (long long)TC * CPT < N) continue;
-                if (T > ((RPT * CPT > 24) ? 256 : 512)) continue;
-                const int cost = RPT * CPT * 64 + T / 64;
-                if (cost < best_cost) {
-                    best_cost = cost;
-                    plan.W = 1;
-                    plan.T = T;
-                    plan.TR = TR;
-                    plan.TC = TC;
-                    plan.RPT = RPT;
-                    plan.CPT = CPT;
-                    found = true;
-                }
-            }
-        }
-    }
-    if (!found) {
-        int RPT = (M + 511) / 512; // two waves per SIMD hide the f64 issue latency (measured: T=512 beats 256)
-        if (RPT > 4) RPT = 4;
-        int TR = round_up((M + RPT - 1) / RPT, 64);
-        int TC = 1;
-        if (TR < 256) TC = 256 / TR;
-        if (RPT > 4 || TR > 1024) return false; // beyond the register budget: LDS kernel
-        // more, thinner workgroups win once the key table is shared (measured: 3 columns per thread and 230 workgroups
-        // beat 4 / 172 by 3.5 % at 685 x 688); fall back to 4 and 8 when that would need more workgroups than CUs
-        int CPT = 3;
-        int W = (N + TC * CPT - 1) / (TC * CPT);
-        if (W > maxw) {
-            CPT = 4;
-            W = (N + TC * CPT - 1) / (TC * CPT);
-        }
-        while (W > maxw && CPT < 8) {
-            CPT = CPT < 6 ? CPT + 1 : 8; // 3 -> 4 -> 5 -> 6 -> 8 columns per thread
-            W = (N + TC * CPT - 1) / (TC * CPT);
-        }
-        if (W < 1) W = 1;
-        if (W > maxw || (long long)W * TC * CPT < N) return false;
-        if (TR * TC > ((RPT * CPT > 24) ? 256 : 512)) return false;
-        plan.W = W;
-        plan.T = TR * TC;
-        plan.TR = TR;
-        plan.TC = TC;
-        plan.RPT = RPT;
-        plan.CPT = CPT;
-    }
-    plan.lds_bytes = reg_smem_layout(M, N, plan.TC * plan.CPT, plan.W == 1, nullptr, nullptr);
-    if (plan.lds_bytes > 160 * 1024) return false;
-    if (plan.W > 1 && plan.lds_bytes < 84 * 1024) plan.lds_bytes = 84 * 1024; // one workgroup per CU
-    *out = plan;
-    return true;
+    const bool single = plan.W == 1, uni = (plan.TR % 64) == 0;
+#define T4A_X(R, C, S, U) \
+    if (plan.CPT == C && single == S && uni == U) return launch_one<R, C, S, U>(plan, a, stream);
+    T4A_CAT(T4A_RRLU_REG_SHAPES_, T4A_REG_RPT)(T4A_X)
+#undef T4A_X
+    throw Error(T4A_GPU_INTERNAL_ERROR, "rrLU: no register-resident kernel for the plan RPT " + std::to_string(plan.RPT) + ", CPT " +
+                                            std::to_string(plan.CPT) + ", W " + std::to_string(plan.W) + ", TR " + std::to_string(plan.TR));
 }
 
-size_t rrlu_reg_keys_bytes(const RrluRegPlan& plan)
-{
-    return (size_t)2 * plan.W * 2 * sizeof(unsigned long long);
-}
-size_t rrlu_reg_cols_bytes(const RrluRegPlan& plan, int M)
-{
-    const size_t slots = (size_t)(plan.W > RRLU_MAX_COPIES ? plan.W : RRLU_MAX_COPIES); // speculative mode: one per workgroup
-    return (size_t)2 * slots * (size_t)M * 2 * sizeof(unsigned long long);
-}
-
+#ifdef T4A_REG_MAIN_TU
 void rrlu_reg_launch(const RrluRegPlan& plan, const RrluRegArgs& a, hipStream_t stream, bool keys_zeroed)
 {
     // the key table carries 16-bit step tags and must start zeroed: normally the previous launch cleared it
     if (plan.W > 1 && !keys_zeroed) (void)hipMemsetAsync(a.keys, 0, rrlu_reg_keys_bytes(plan), stream);
     switch (plan.RPT) {
-    case 1: launch_r<1>(plan, a, stream); break;
-    case 2: launch_r<2>(plan, a, stream); break;
-    case 3: launch_r<3>(plan, a, stream); break;
-    default: launch_r<4>(plan, a, stream); break;
+    case 1: return rrlu_reg_launch_rpt1(plan, a, stream);
+    case 2: return rrlu_reg_launch_rpt2(plan, a, stream);
+    case 3: return rrlu_reg_launch_rpt3(plan, a, stream);
+    case 4: return rrlu_reg_launch_rpt4(plan, a, stream);
+    default: throw Error(T4A_GPU_INTERNAL_ERROR, "rrLU: no register-resident kernel with " + std::to_string(plan.RPT) + " rows per thread");
     }
 }
+#endif
 
 } // namespace t4a

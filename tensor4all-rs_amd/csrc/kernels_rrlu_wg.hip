@@ -1,5 +1,5 @@
 // kernels_rrlu_wg.hip — K2 for matrices that fit ONE workgroup (round 4): register-resident full-pivot rrLU with the per-step
-// exchange through the LDS of one compute unit.  Up to 8 waves x 64 lanes x 96 values: 64 x 512, 128 x 384.
+// exchange through the LDS of one compute unit.  8 waves x 64 lanes x up to 16 values: 64 x 128, 128 x 64 (rrlu_shapes.hpp).
 //
 // Why: the single-XCD kernels pay ~2 us per pivot step at ANY size (two L2 hand-offs between 29 compute units) and the
 // single-workgroup plan of the chip-wide kernel 3 100 - 3 600 cycles; the end bonds of every chain, the whole growth phase of a
@@ -21,15 +21,18 @@
 //   all waves (redundantly, no second barrier): read the 8 keys, pick the winner, stop tests, read the winner's column, divide
 //   (l of the pivot row is pivot / pivot = 1: the update zeroes that row exactly, which is all the masking there is), own copy
 //   of the permutation tables, pivot row by v_readlane, rank-1 update fused with the maxima for the next step.
+#include "common.hpp"
 #include "kernels_rrlu_xcd_common.hpp"
+#include "rrlu_shapes.hpp"
 
+#include <string>
 #include <type_traits>
 
 namespace t4a {
 
 namespace {
 
-constexpr int WGW = 8;         // waves per workgroup
+constexpr int WGW = WG_WAVES; // waves per workgroup
 constexpr int WGT = 64 * WGW;  // threads
 template <int RPT> constexpr int wg_gs() { return 8; } // columns per register group (GS * RPT <= 16 doubles: one VGPR tuple; wider tuples — three rows per lane — spill)
 
@@ -587,70 +590,20 @@ template <int RPT, int CPW> void wg_launch_rc(const RrluXcdPlan& plan, bool row_
     else wg_launch_one<RPT, CPW, false>(plan, solo, group, stream);
 }
 
-// instantiated shapes: rows per lane x columns per wave (a plan rounds the columns up to the next one)
-#ifndef T4A_WG_GROUP_TU
-constexpr int kWgCpw1[] = {8, 16, 32, 64};
-constexpr int kWgCpw2[] = {8, 16, 32, 48};
-#endif
-
+// the shapes of rrlu_shapes.hpp, and nothing else
 void wg_dispatch(const RrluXcdPlan& plan, bool row_major, const RrluXcdArgs* solo, const RrluXcdGroupArgs* group, hipStream_t stream)
 {
-    const int key = plan.RPT * 1000 + plan.CPT;
-    switch (key) {
-    case 1008: wg_launch_rc<1, 8>(plan, row_major, solo, group, stream); break;
-    case 1016: wg_launch_rc<1, 16>(plan, row_major, solo, group, stream); break;
-    case 1032: wg_launch_rc<1, 32>(plan, row_major, solo, group, stream); break;
-    case 1064: wg_launch_rc<1, 64>(plan, row_major, solo, group, stream); break;
-    case 2008: wg_launch_rc<2, 8>(plan, row_major, solo, group, stream); break;
-    case 2016: wg_launch_rc<2, 16>(plan, row_major, solo, group, stream); break;
-    case 2032: wg_launch_rc<2, 32>(plan, row_major, solo, group, stream); break;
-    default: wg_launch_rc<2, 48>(plan, row_major, solo, group, stream); break;
-    }
+#define T4A_X(R, C)                                                                                      \
+    static_assert(WgLds<R, C>::bytes == wg_lds_bytes(R, C), "plan.lds_bytes must cover the layout"); \
+    if (plan.RPT == R && plan.CPT == C) return wg_launch_rc<R, C>(plan, row_major, solo, group, stream);
+    T4A_RRLU_WG_SHAPES(T4A_X)
+#undef T4A_X
+    throw Error(T4A_GPU_INTERNAL_ERROR, "rrLU: no one-workgroup kernel for the plan RPT " + std::to_string(plan.RPT) + ", CPT " + std::to_string(plan.CPT));
 }
-
-#ifndef T4A_WG_GROUP_TU
-size_t wg_lds_bytes(int rpt, int cpw)
-{
-    const size_t MP = 64 * (size_t)rpt, NP = (size_t)WGW * cpw;
-    return 2 * WGW * 16 + 2 * WGW * MP * 8 + 64 + MP * 8 + WGW * (2 * MP + 2 * NP) * 2;
-}
-static_assert(WgLds<2, 48>::bytes == 2 * WGW * 16 + 2 * WGW * 128 * 8 + 64 + 128 * 8 + WGW * (2 * 128 + 2 * 384) * 2, "plan.lds_bytes must cover the layout");
-#endif
 
 } // namespace
 
 #ifndef T4A_WG_GROUP_TU
-// One-workgroup plan for an M x N matrix (upper bounds in a bond chain), or false when it does not fit.  spec_blocks: workgroups
-// beside the factorising one that evaluate the next bond's candidate matrix (bond chain, solo launch).
-bool rrlu_wg_make_plan(int M, int N, RrluXcdPlan* out, int spec_blocks)
-{
-    static const bool off = std::getenv("T4A_NO_WG") != nullptr;
-    if (off || M < 1 || N < 1 || M > 128) return false;
-    const int rpt = (M + 63) / 64;
-    const int need = (N + WGW - 1) / WGW;
-    const int* list = rpt == 1 ? kWgCpw1 : kWgCpw2;
-    const int nlist = 4;
-    int cpw = -1;
-    for (int i = 0; i < nlist; ++i)
-        if (need <= list[i]) {
-            cpw = list[i];
-            break;
-        }
-    if (cpw < 0) return false;
-    // beyond 16 values per lane (64 x 128, 128 x 64) the update (2 readlanes + 3 RPT vector instructions per owned column, all on ONE compute unit)
-    // costs more than the single-XCD kernel's two L2 hand-offs (measured: tools/probe_wg.py)
-    if (rpt * cpw > 16) return false;
-    RrluXcdPlan plan;
-    plan.W = 1;
-    plan.RPT = rpt;
-    plan.CPT = cpw;
-    plan.grid = 1 + (spec_blocks > 0 ? spec_blocks : 0);
-    plan.lds_bytes = wg_lds_bytes(rpt, cpw);
-    plan.wg = 1;
-    *out = plan;
-    return true;
-}
-
 void rrlu_wg_launch(const RrluXcdPlan& plan, const RrluXcdArgs& a, hipStream_t stream) { wg_dispatch(plan, a.tie_row_major != 0, &a, nullptr, stream); }
 #else
 // (this half of the file is compiled as its own translation unit: kernels_rrlu_wg_group.hip)
