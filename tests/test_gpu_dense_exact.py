@@ -22,6 +22,8 @@ import sys
 import numpy as np
 import pytest
 
+from fill_exact_np import _pivot_rows, _plu  # noqa: F401  (the matrices of the LU solves; shared with test_gpu_fill_exact.py)
+
 pytestmark = pytest.mark.gpu
 
 EPS = np.finfo(np.float64).eps
@@ -146,39 +148,6 @@ SOLVE_ROUTES = [
     (1025, 1, "lu_kernel + two scalar trsm"),
     (1500, 20, "lu_kernel + two trsm"),
 ]
-
-
-def _pivot_rows(rng, n):
-    """ipiv[k] >= k, the row the partial pivoting must swap with k at step k: no swap, the edges of the panel around k for every panel
-    width (kb + nb - 1, kb + nb), the last row, or anywhere beyond."""
-    ipiv = np.empty(n, dtype=np.int64)
-    for k in range(n):
-        cand = [k, n - 1, int(rng.integers(k, n))]
-        for nb in (8, 16, 32):
-            kb = k - k % nb
-            cand += [kb + nb - 1, kb + nb, kb + 2 * nb]
-        cand = [c for c in cand if k <= c < n]
-        ipiv[k] = cand[int(rng.integers(0, len(cand)))]
-    return ipiv
-
-
-def _plu(rng, n, small):
-    """A = P L U (P from _pivot_rows).  small=False: |l| in {0, 1/4, 1/2}, U small integers with a power-of-two diagonal, every step of
-    the elimination exact.  small=True: l ~ 1e-9 and a diagonally dominant U (kappa of a few)."""
-    if small:
-        l = np.tril(rng.uniform(0.5, 1.0, size=(n, n)) * rng.choice([-1.0, 1.0], size=(n, n)) * 1e-9, -1) + np.eye(n)
-        u = np.triu(rng.uniform(-1, 1, size=(n, n)) / n, 1) + np.diag(rng.choice([1.0, -1.0, 2.0, -2.0], size=n))
-    else:
-        l = np.tril(rng.choice([0.0, 0.25, -0.25, 0.5, -0.5], size=(n, n)), -1) + np.eye(n)
-        u = np.triu(rng.integers(-3, 4, size=(n, n)).astype(np.float64), 1) + np.diag(
-            rng.choice([1.0, -1.0, 2.0, -2.0, 4.0, -4.0, 8.0], size=n))
-    a = l @ u  # exact for the integer construction: multiples of 1/4 below 2^16
-    ipiv = _pivot_rows(rng, n)
-    for k in range(n - 1, -1, -1):  # A = P_0 P_1 ... P_{n-1} L U: partial pivoting swaps k and ipiv[k] at step k
-        p = ipiv[k]
-        if p != k:
-            a[[k, p], :] = a[[p, k], :]
-    return a
 
 
 @pytest.mark.parametrize("n,nrhs,route", SOLVE_ROUTES)

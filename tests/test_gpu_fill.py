@@ -4,6 +4,10 @@ LU / triangular solve / pack route) — and the graph key must cover everything 
 
 The reference in every case: a fresh handle with the same function and the same I/J sets (set_index_set), filled ONCE — the first
 fill of a handle is always issued directly.
+
+This file compares fills with fills: it holds the replayed, sharded and grouped fills to the direct one and says nothing about the
+values.  Those are pinned in tests/test_gpu_fill_exact.py, where every core of a ragged batch — on each route family of fill_issue, with
+a zero pivot matrix inside the batch, replayed, sharded and grouped — must equal an answer that is exact by construction.
 """
 import numpy as np
 import pytest
