@@ -684,6 +684,100 @@ t4a_gpu_status t4a_gpu_tt_reverse(const t4a_gpu_tt* h, t4a_gpu_tt** out);
 t4a_gpu_status t4a_gpu_tt_partial_sum(const t4a_gpu_tt* h, const size_t* dims, size_t n_dims, t4a_gpu_tt** out);
 
 /* =====================================================================================
+ * Gauge forms of a tensor train (opaque handles; tensors and bond vectors resident on the device)
+ * tensor4all-simplett: canonical.rs:102-393 (SiteTensorTrain), :439-544 (center_canonicalize), vidal.rs:199-493
+ * (VidalTensorTrain), :535-767 (InverseTensorTrain).  The MPO-side forms (SiteMPO::move_center_*, VidalMPO::from_mpo,
+ * InverseMPO::from_mpo) are stubs in the reference and have no counterpart here.
+ *
+ * The reference's `qr_decomp` (canonical.rs:17-29, vidal.rs:22-33) is rrlu(matrix, {max_bond_dim: min(m, n), rel_tol: 0,
+ * abs_tol: 0, left_orthogonal: true}) with lu.left(true) / lu.right(true): the gauged cores are unit-lower-trapezoidal LU
+ * factors, not isometries, and the Vidal "singular values" are those of the LU-gauged bond matrices, NOT the Schmidt values of
+ * the tensor.  These functions restate that.  A bond shrinks below min(m, n) only at an exactly zero pivot.
+ *
+ * Every form hands out its stored tensors as a plain train (`_tensors_tt`, a device-to-device copy): evaluate, sum and norm2
+ * of AbstractTensorTrain on a form are t4a_gpu_tt_evaluate / _sum / _norm2 on that train.  Site tensors are column-major
+ * [left, site, right]; dims3 is (left, site, right).  Argument errors are T4A_GPU_INVALID_ARGUMENT with the reference's
+ * message, checked before the device is touched.
+ * ===================================================================================== */
+typedef struct t4a_gpu_site_tt t4a_gpu_site_tt;
+typedef struct t4a_gpu_vidal_tt t4a_gpu_vidal_tt;
+typedef struct t4a_gpu_inverse_tt t4a_gpu_inverse_tt;
+
+/* SiteTensorTrain::from_tensor_train(tt, center) (canonical.rs:118-154): left sweep 0..center, right sweep n-1..center+1.
+ * Errors: "Tensor train is empty", "Center {c} is out of range for {n} tensors". */
+t4a_gpu_status t4a_gpu_site_tt_from_tt(const t4a_gpu_tt* tt, size_t center, t4a_gpu_site_tt** out);
+void t4a_gpu_site_tt_release(t4a_gpu_site_tt* h);
+t4a_gpu_status t4a_gpu_site_tt_len(const t4a_gpu_site_tt* h, size_t* out);
+t4a_gpu_status t4a_gpu_site_tt_dims(const t4a_gpu_site_tt* h, size_t* dims3 /* 3 x n_sites */);
+t4a_gpu_status t4a_gpu_site_tt_site_tensor(const t4a_gpu_site_tt* h, size_t site, double* out);
+t4a_gpu_status t4a_gpu_site_tt_center(const t4a_gpu_site_tt* h, size_t* out);
+/* move_center_left / move_center_right / set_center (canonical.rs:299-353): one gauge step per site moved.
+ * Errors: "Cannot move center left: already at leftmost position", "... right: already at rightmost position",
+ * "New center {c} is out of range for {n} tensors". */
+t4a_gpu_status t4a_gpu_site_tt_move_center_left(t4a_gpu_site_tt* h);
+t4a_gpu_status t4a_gpu_site_tt_move_center_right(t4a_gpu_site_tt* h);
+t4a_gpu_status t4a_gpu_site_tt_set_center(t4a_gpu_site_tt* h, size_t center);
+/* set_site_tensor / set_two_site_tensors (canonical.rs:363-392): plain replacement, nothing is re-gauged and the neighbouring
+ * bonds are not checked (as in the reference).  Errors: site >= len; "Cannot set two-site tensors at site {i} (max {n-2})"
+ * for site >= len - 1; a dimension above 65535 is NOT_IMPLEMENTED. */
+t4a_gpu_status t4a_gpu_site_tt_set_site_tensor(t4a_gpu_site_tt* h, size_t site, const size_t* dims3, const double* data);
+t4a_gpu_status t4a_gpu_site_tt_set_two_site_tensors(t4a_gpu_site_tt* h, size_t site, const size_t* dims3_1, const double* data1,
+                                                    const size_t* dims3_2, const double* data2);
+/* to_tensor_train (canonical.rs:356-358) and the stored tensors as a plain train: the same copy for this form.  A train whose
+ * bonds no longer chain after a replacement is refused here (INVALID_ARGUMENT), not when it is stored. */
+t4a_gpu_status t4a_gpu_site_tt_to_tt(const t4a_gpu_site_tt* h, t4a_gpu_tt** out);
+t4a_gpu_status t4a_gpu_site_tt_tensors_tt(const t4a_gpu_site_tt* h, t4a_gpu_tt** out);
+/* center_canonicalize(tensors, center) (canonical.rs:439-544) in place on a plain train; a silent no-op for n <= 1 or
+ * center >= n, as there. */
+t4a_gpu_status t4a_gpu_tt_center_canonicalize(t4a_gpu_tt* tt, size_t center);
+
+/* VidalTensorTrain::from_tensor_train_with_partition(tt, start..end) (vidal.rs:229-395); from_tensor_train is 0..len.
+ * Left sweep over start..end-1 (the LU-for-QR step), right sweep over end-1..start+1 by SVD without truncation
+ * (singular_values[i-1] = all min(L, S R) values, core i = V^T, core i-1 = prev * (U diag(s))), then every element of the cores
+ * start..end-2 is divided by sv[r] if sv[r] > 1e-15, else by 1.0.  An empty train gives the empty object.
+ * Errors: "Partition end {e} exceeds tensor train length {n}", "Cannot compute Vidal singular values for an empty bond matrix". */
+t4a_gpu_status t4a_gpu_vidal_tt_from_tt(const t4a_gpu_tt* tt, size_t start, size_t end, t4a_gpu_vidal_tt** out);
+/* VidalTensorTrain::new(tensors, singular_values) (vidal.rs:403-428) from host data: cores concatenated as in t4a_gpu_tt_new,
+ * svs the n_svs vectors concatenated with lengths sv_lens.  Only the number of vectors is checked, as in the reference
+ * ("Expected {n-1} singular value vectors, got {n_svs}"); a vector shorter than its bond leaves the remaining indices unscaled,
+ * a longer one is ignored beyond the bond (vidal.rs:476-480).  n_sites == 0 is the empty object (no device needed). */
+t4a_gpu_status t4a_gpu_vidal_tt_new(const size_t* dims3, size_t n_sites, const double* cores, const size_t* sv_lens, size_t n_svs,
+                                    const double* svs, t4a_gpu_vidal_tt** out);
+void t4a_gpu_vidal_tt_release(t4a_gpu_vidal_tt* h);
+t4a_gpu_status t4a_gpu_vidal_tt_len(const t4a_gpu_vidal_tt* h, size_t* out);
+t4a_gpu_status t4a_gpu_vidal_tt_dims(const t4a_gpu_vidal_tt* h, size_t* dims3 /* 3 x n_sites */);
+t4a_gpu_status t4a_gpu_vidal_tt_site_tensor(const t4a_gpu_vidal_tt* h, size_t site, double* out);
+t4a_gpu_status t4a_gpu_vidal_tt_set_site_tensor(t4a_gpu_vidal_tt* h, size_t site, const size_t* dims3, const double* data);
+t4a_gpu_status t4a_gpu_vidal_tt_partition(const t4a_gpu_vidal_tt* h, size_t* start, size_t* end);
+/* singular_values(bond) (vidal.rs:431-433): *len receives the length; the values are written when out != NULL and
+ * capacity >= *len (BUFFER_TOO_SMALL otherwise): query with out == NULL first.  The values live on the device and are read back
+ * here.  set_singular_values replaces the vector (singular_values_mut, vidal.rs:451-453), any length. */
+t4a_gpu_status t4a_gpu_vidal_tt_singular_values(const t4a_gpu_vidal_tt* h, size_t bond, double* out, size_t capacity, size_t* len);
+t4a_gpu_status t4a_gpu_vidal_tt_set_singular_values(t4a_gpu_vidal_tt* h, size_t bond, const double* values, size_t len);
+/* to_tensor_train (vidal.rs:456-492): every core but the last times sv[r] on its right bond, one launch for the train. */
+t4a_gpu_status t4a_gpu_vidal_tt_to_tt(const t4a_gpu_vidal_tt* h, t4a_gpu_tt** out);
+t4a_gpu_status t4a_gpu_vidal_tt_tensors_tt(const t4a_gpu_vidal_tt* h, t4a_gpu_tt** out);
+
+/* InverseTensorTrain::from_vidal (vidal.rs:551-663): element (l, s, r) of a middle core is (val * sv[i-1][l]) * sv[i][r] in that
+ * order, the first core gets only the right factor, the last only the left one; the stored inverse values are 1 / v if
+ * |v| > 1e-15, else 0.  from_tt = from_vidal(VidalTensorTrain::from_tensor_train(tt)) (vidal.rs:671-678). */
+t4a_gpu_status t4a_gpu_inverse_tt_from_vidal(const t4a_gpu_vidal_tt* vidal, t4a_gpu_inverse_tt** out);
+t4a_gpu_status t4a_gpu_inverse_tt_from_tt(const t4a_gpu_tt* tt, t4a_gpu_inverse_tt** out);
+void t4a_gpu_inverse_tt_release(t4a_gpu_inverse_tt* h);
+t4a_gpu_status t4a_gpu_inverse_tt_len(const t4a_gpu_inverse_tt* h, size_t* out);
+t4a_gpu_status t4a_gpu_inverse_tt_dims(const t4a_gpu_inverse_tt* h, size_t* dims3 /* 3 x n_sites */);
+t4a_gpu_status t4a_gpu_inverse_tt_site_tensor(const t4a_gpu_inverse_tt* h, size_t site, double* out);
+t4a_gpu_status t4a_gpu_inverse_tt_partition(const t4a_gpu_inverse_tt* h, size_t* start, size_t* end);
+t4a_gpu_status t4a_gpu_inverse_tt_inverse_singular_values(const t4a_gpu_inverse_tt* h, size_t bond, double* out, size_t capacity,
+                                                          size_t* len);
+/* set_two_site_tensors(i, t1, inv_sv, t2) (vidal.rs:706-727); "Cannot set two-site tensors at site {i} (max {n-2})". */
+t4a_gpu_status t4a_gpu_inverse_tt_set_two_site_tensors(t4a_gpu_inverse_tt* h, size_t site, const size_t* dims3_1, const double* data1,
+                                                       const double* inv_sv, size_t inv_len, const size_t* dims3_2, const double* data2);
+/* to_tensor_train (vidal.rs:730-766): every core but the last times the stored inverse values on its right bond. */
+t4a_gpu_status t4a_gpu_inverse_tt_to_tt(const t4a_gpu_inverse_tt* h, t4a_gpu_tt** out);
+t4a_gpu_status t4a_gpu_inverse_tt_tensors_tt(const t4a_gpu_inverse_tt* h, t4a_gpu_tt** out);
+
+/* =====================================================================================
  * MPO<f64> (opaque handle; site tensors resident on the device) and the contraction of two MPOs
  * tensor4all-simplett/src/mpo/: mpo.rs:35-480, contract_naive.rs:41-172, contract_zipup.rs:45-167, canonical.rs:35-89,
  * factorize.rs:126-313, contraction.rs:17-42, dispatch.rs:8-92

@@ -18,6 +18,7 @@
 #include "mpo.hpp"
 #include "contraction.hpp"
 #include "quanticstransform.hpp"
+#include "tt_canonical.hpp"
 
 struct t4a_gpu_tci2 {
     t4a::Tci2 impl;
@@ -45,6 +46,19 @@ struct t4a_gpu_tt {
     t4a::TensorTrain impl;
     t4a_gpu_tt(const std::vector<std::array<size_t, 3>>& d, const double* data) : impl(d, data) {}
     t4a_gpu_tt(const std::vector<t4a::DevCore>& cores, hipStream_t src) : impl(cores, src) {}
+};
+
+struct t4a_gpu_site_tt {
+    t4a::SiteTrain impl;
+    t4a_gpu_site_tt(const std::vector<t4a::DevCore>& cores, hipStream_t src, size_t center) : impl(cores, src, center) {}
+};
+
+struct t4a_gpu_vidal_tt {
+    std::unique_ptr<t4a::VidalTrain> impl;
+};
+
+struct t4a_gpu_inverse_tt {
+    std::unique_ptr<t4a::InverseTrain> impl;
 };
 
 struct t4a_gpu_mpo {
@@ -2837,6 +2851,377 @@ t4a_gpu_status t4a_gpu_tt_partial_sum(const t4a_gpu_tt* h, const size_t* dims, s
         *out = nullptr;
         if (n_dims) T4A_REQUIRE_PTR(dims);
         *out = wrap_tt(const_cast<t4a_gpu_tt*>(h)->impl.partial_sum(std::vector<size_t>(dims, dims + n_dims)));
+    });
+}
+
+// ---- gauge forms: SiteTensorTrain, VidalTensorTrain, InverseTensorTrain (tt_canonical.hip) ----
+extern "C++" {
+static void cores_dims(const std::vector<DevCore>& cores, size_t* dims3)
+{
+    if (!cores.empty()) T4A_REQUIRE_PTR(dims3);
+    for (size_t s = 0; s < cores.size(); ++s) {
+        dims3[3 * s] = cores[s].l;
+        dims3[3 * s + 1] = cores[s].s;
+        dims3[3 * s + 2] = cores[s].r;
+    }
+}
+static void core_to_host(Engine* eng, const std::vector<DevCore>& cores, size_t site, double* out)
+{
+    if (site >= cores.size()) throw Error(T4A_GPU_INVALID_ARGUMENT, "site " + std::to_string(site) + " is out of range for " + std::to_string(cores.size()) + " tensors");
+    const DevCore& c = cores[site];
+    if (c.size() == 0) return;
+    T4A_REQUIRE_PTR(out);
+    T4A_HIP(hipMemcpyAsync(out, c.buf.get(), c.size() * sizeof(double), hipMemcpyDeviceToHost, eng->stream()));
+    eng->sync();
+}
+static void vector_out(const std::vector<double>& v, double* out, size_t capacity, size_t* len)
+{
+    T4A_REQUIRE_PTR(len);
+    *len = v.size();
+    if (!out) return;
+    if (capacity < v.size())
+        throw Error(T4A_GPU_BUFFER_TOO_SMALL, "output capacity " + std::to_string(capacity) + " is below " + std::to_string(v.size()));
+    if (!v.empty()) std::memcpy(out, v.data(), v.size() * sizeof(double));
+}
+static t4a_gpu_tt* tt_from_cores(const std::vector<DevCore>& cores, hipStream_t stream) { return new t4a_gpu_tt(cores, stream); }
+} // extern "C++"
+
+t4a_gpu_status t4a_gpu_site_tt_from_tt(const t4a_gpu_tt* tt, size_t center, t4a_gpu_site_tt** out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(out);
+        *out = nullptr;
+        T4A_REQUIRE_PTR(tt);
+        SiteTrain::check_new(tt->impl.len(), center);
+        *out = new t4a_gpu_site_tt(tt->impl.cores, tt->impl.eng.stream(), center);
+    });
+}
+
+void t4a_gpu_site_tt_release(t4a_gpu_site_tt* h) { delete h; }
+
+t4a_gpu_status t4a_gpu_site_tt_len(const t4a_gpu_site_tt* h, size_t* out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(h);
+        T4A_REQUIRE_PTR(out);
+        *out = h->impl.len();
+    });
+}
+
+t4a_gpu_status t4a_gpu_site_tt_dims(const t4a_gpu_site_tt* h, size_t* dims3)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(h);
+        cores_dims(h->impl.cores, dims3);
+    });
+}
+
+t4a_gpu_status t4a_gpu_site_tt_site_tensor(const t4a_gpu_site_tt* h, size_t site, double* out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(h);
+        core_to_host(&const_cast<t4a_gpu_site_tt*>(h)->impl.eng, h->impl.cores, site, out);
+    });
+}
+
+t4a_gpu_status t4a_gpu_site_tt_center(const t4a_gpu_site_tt* h, size_t* out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(h);
+        T4A_REQUIRE_PTR(out);
+        *out = h->impl.center();
+    });
+}
+
+t4a_gpu_status t4a_gpu_site_tt_move_center_left(t4a_gpu_site_tt* h)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(h);
+        h->impl.move_center_left();
+    });
+}
+
+t4a_gpu_status t4a_gpu_site_tt_move_center_right(t4a_gpu_site_tt* h)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(h);
+        h->impl.move_center_right();
+    });
+}
+
+t4a_gpu_status t4a_gpu_site_tt_set_center(t4a_gpu_site_tt* h, size_t center)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(h);
+        h->impl.set_center(center);
+    });
+}
+
+t4a_gpu_status t4a_gpu_site_tt_set_site_tensor(t4a_gpu_site_tt* h, size_t site, const size_t* dims3, const double* data)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(h);
+        T4A_REQUIRE_PTR(dims3);
+        h->impl.set_site_tensor(site, dims3, data);
+    });
+}
+
+t4a_gpu_status t4a_gpu_site_tt_set_two_site_tensors(t4a_gpu_site_tt* h, size_t site, const size_t* dims3_1, const double* data1,
+                                                    const size_t* dims3_2, const double* data2)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(h);
+        T4A_REQUIRE_PTR(dims3_1);
+        T4A_REQUIRE_PTR(dims3_2);
+        h->impl.set_two_site_tensors(site, dims3_1, data1, dims3_2, data2);
+    });
+}
+
+t4a_gpu_status t4a_gpu_site_tt_to_tt(const t4a_gpu_site_tt* h, t4a_gpu_tt** out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(out);
+        *out = nullptr;
+        T4A_REQUIRE_PTR(h);
+        *out = tt_from_cores(h->impl.cores, h->impl.eng.stream());
+    });
+}
+
+t4a_gpu_status t4a_gpu_site_tt_tensors_tt(const t4a_gpu_site_tt* h, t4a_gpu_tt** out) { return t4a_gpu_site_tt_to_tt(h, out); }
+
+t4a_gpu_status t4a_gpu_tt_center_canonicalize(t4a_gpu_tt* tt, size_t center)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(tt);
+        center_canonicalize(tt->impl, center);
+    });
+}
+
+t4a_gpu_status t4a_gpu_vidal_tt_from_tt(const t4a_gpu_tt* tt, size_t start, size_t end, t4a_gpu_vidal_tt** out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(out);
+        *out = nullptr;
+        T4A_REQUIRE_PTR(tt);
+        VidalTrain::check_partition(tt->impl.len(), end);
+        auto h = std::make_unique<t4a_gpu_vidal_tt>();
+        h->impl = std::make_unique<VidalTrain>(tt->impl.cores, tt->impl.eng.stream(), start, end);
+        *out = h.release();
+    });
+}
+
+t4a_gpu_status t4a_gpu_vidal_tt_new(const size_t* dims3, size_t n_sites, const double* cores, const size_t* sv_lens, size_t n_svs,
+                                    const double* svs, t4a_gpu_vidal_tt** out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(out);
+        *out = nullptr;
+        auto h = std::make_unique<t4a_gpu_vidal_tt>();
+        if (n_sites == 0) { // vidal.rs:405-411: the empty object whatever the vectors are
+            h->impl = std::make_unique<VidalTrain>();
+            *out = h.release();
+            return;
+        }
+        T4A_REQUIRE_PTR(dims3);
+        VidalTrain::check_new(n_sites, n_svs);
+        if (n_svs) T4A_REQUIRE_PTR(sv_lens);
+        std::vector<std::array<size_t, 3>> d(n_sites);
+        for (size_t s = 0; s < n_sites; ++s) {
+            d[s] = {dims3[3 * s], dims3[3 * s + 1], dims3[3 * s + 2]};
+            checked_mul(checked_mul(d[s][0], d[s][1], "tensor shape"), d[s][2], "tensor shape");
+        }
+        h->impl = std::make_unique<VidalTrain>(d, cores, std::vector<size_t>(sv_lens, sv_lens + n_svs), svs);
+        *out = h.release();
+    });
+}
+
+void t4a_gpu_vidal_tt_release(t4a_gpu_vidal_tt* h) { delete h; }
+
+t4a_gpu_status t4a_gpu_vidal_tt_len(const t4a_gpu_vidal_tt* h, size_t* out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(h);
+        T4A_REQUIRE_PTR(out);
+        *out = h->impl->len();
+    });
+}
+
+t4a_gpu_status t4a_gpu_vidal_tt_dims(const t4a_gpu_vidal_tt* h, size_t* dims3)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(h);
+        cores_dims(h->impl->cores, dims3);
+    });
+}
+
+t4a_gpu_status t4a_gpu_vidal_tt_site_tensor(const t4a_gpu_vidal_tt* h, size_t site, double* out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(h);
+        core_to_host(h->impl->eng.get(), h->impl->cores, site, out);
+    });
+}
+
+t4a_gpu_status t4a_gpu_vidal_tt_set_site_tensor(t4a_gpu_vidal_tt* h, size_t site, const size_t* dims3, const double* data)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(h);
+        T4A_REQUIRE_PTR(dims3);
+        h->impl->set_site_tensor(site, dims3, data);
+    });
+}
+
+t4a_gpu_status t4a_gpu_vidal_tt_partition(const t4a_gpu_vidal_tt* h, size_t* start, size_t* end)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(h);
+        T4A_REQUIRE_PTR(start);
+        T4A_REQUIRE_PTR(end);
+        *start = h->impl->part_start;
+        *end = h->impl->part_end;
+    });
+}
+
+t4a_gpu_status t4a_gpu_vidal_tt_singular_values(const t4a_gpu_vidal_tt* h, size_t bond, double* out, size_t capacity, size_t* len)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(h);
+        T4A_REQUIRE_PTR(len);
+        vector_out(h->impl->singular_values_host(bond), out, capacity, len);
+    });
+}
+
+t4a_gpu_status t4a_gpu_vidal_tt_set_singular_values(t4a_gpu_vidal_tt* h, size_t bond, const double* values, size_t len)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(h);
+        h->impl->set_singular_values(bond, values, len);
+    });
+}
+
+t4a_gpu_status t4a_gpu_vidal_tt_to_tt(const t4a_gpu_vidal_tt* h, t4a_gpu_tt** out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(out);
+        *out = nullptr;
+        T4A_REQUIRE_PTR(h);
+        std::vector<DevCore> cores = h->impl->to_tensor_train_cores();
+        *out = tt_from_cores(cores, h->impl->eng ? h->impl->eng->stream() : nullptr);
+    });
+}
+
+t4a_gpu_status t4a_gpu_vidal_tt_tensors_tt(const t4a_gpu_vidal_tt* h, t4a_gpu_tt** out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(out);
+        *out = nullptr;
+        T4A_REQUIRE_PTR(h);
+        *out = tt_from_cores(h->impl->cores, h->impl->eng ? h->impl->eng->stream() : nullptr);
+    });
+}
+
+t4a_gpu_status t4a_gpu_inverse_tt_from_vidal(const t4a_gpu_vidal_tt* vidal, t4a_gpu_inverse_tt** out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(out);
+        *out = nullptr;
+        T4A_REQUIRE_PTR(vidal);
+        auto h = std::make_unique<t4a_gpu_inverse_tt>();
+        h->impl = std::make_unique<InverseTrain>(*vidal->impl);
+        *out = h.release();
+    });
+}
+
+t4a_gpu_status t4a_gpu_inverse_tt_from_tt(const t4a_gpu_tt* tt, t4a_gpu_inverse_tt** out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(out);
+        *out = nullptr;
+        T4A_REQUIRE_PTR(tt);
+        VidalTrain vidal(tt->impl.cores, tt->impl.eng.stream(), 0, tt->impl.len());
+        auto h = std::make_unique<t4a_gpu_inverse_tt>();
+        h->impl = std::make_unique<InverseTrain>(vidal);
+        *out = h.release();
+    });
+}
+
+void t4a_gpu_inverse_tt_release(t4a_gpu_inverse_tt* h) { delete h; }
+
+t4a_gpu_status t4a_gpu_inverse_tt_len(const t4a_gpu_inverse_tt* h, size_t* out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(h);
+        T4A_REQUIRE_PTR(out);
+        *out = h->impl->len();
+    });
+}
+
+t4a_gpu_status t4a_gpu_inverse_tt_dims(const t4a_gpu_inverse_tt* h, size_t* dims3)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(h);
+        cores_dims(h->impl->cores, dims3);
+    });
+}
+
+t4a_gpu_status t4a_gpu_inverse_tt_site_tensor(const t4a_gpu_inverse_tt* h, size_t site, double* out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(h);
+        core_to_host(h->impl->eng.get(), h->impl->cores, site, out);
+    });
+}
+
+t4a_gpu_status t4a_gpu_inverse_tt_partition(const t4a_gpu_inverse_tt* h, size_t* start, size_t* end)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(h);
+        T4A_REQUIRE_PTR(start);
+        T4A_REQUIRE_PTR(end);
+        *start = h->impl->part_start;
+        *end = h->impl->part_end;
+    });
+}
+
+t4a_gpu_status t4a_gpu_inverse_tt_inverse_singular_values(const t4a_gpu_inverse_tt* h, size_t bond, double* out, size_t capacity,
+                                                          size_t* len)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(h);
+        T4A_REQUIRE_PTR(len);
+        vector_out(h->impl->inverse_singular_values_host(bond), out, capacity, len);
+    });
+}
+
+t4a_gpu_status t4a_gpu_inverse_tt_set_two_site_tensors(t4a_gpu_inverse_tt* h, size_t site, const size_t* dims3_1, const double* data1,
+                                                       const double* inv_sv, size_t inv_len, const size_t* dims3_2, const double* data2)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(h);
+        T4A_REQUIRE_PTR(dims3_1);
+        T4A_REQUIRE_PTR(dims3_2);
+        h->impl->set_two_site_tensors(site, dims3_1, data1, inv_sv, inv_len, dims3_2, data2);
+    });
+}
+
+t4a_gpu_status t4a_gpu_inverse_tt_to_tt(const t4a_gpu_inverse_tt* h, t4a_gpu_tt** out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(out);
+        *out = nullptr;
+        T4A_REQUIRE_PTR(h);
+        std::vector<DevCore> cores = h->impl->to_tensor_train_cores();
+        *out = tt_from_cores(cores, h->impl->eng ? h->impl->eng->stream() : nullptr);
+    });
+}
+
+t4a_gpu_status t4a_gpu_inverse_tt_tensors_tt(const t4a_gpu_inverse_tt* h, t4a_gpu_tt** out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(out);
+        *out = nullptr;
+        T4A_REQUIRE_PTR(h);
+        *out = tt_from_cores(h->impl->cores, h->impl->eng ? h->impl->eng->stream() : nullptr);
     });
 }
 

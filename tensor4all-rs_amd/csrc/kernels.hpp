@@ -534,6 +534,31 @@ void core_reshape_launch(const double* in, int L, int S, int R, int mode, double
 constexpr int PERMUTE_MAX_RANK = 16;
 void permute_launch(const double* in, const size_t* dims, const size_t* perm, int rank, double* out, hipStream_t stream);
 void tt_sum_launch(const TtCoreDesc* d_cores, int n_sites, int max_bond, double* d_out, hipStream_t stream);
+// Vidal / inverse arithmetic of a whole train in one launch (tt_canonical.hip): descriptor k scales the core src (l, s, r) into dst
+// (dst == src allowed) as dst[l, s, r] = (src[l, s, r] lop lv[l]) rop rv[r], left factor first.  A vector shorter than its bond
+// leaves the remaining indices unscaled, a longer one is ignored beyond the bond (simplett/src/vidal.rs:378-382, :476-480).
+enum : int {
+    TT_SCALE_NONE = 0,
+    TT_SCALE_MUL = 1,       // val * v[i]
+    TT_SCALE_DIV_GUARD = 2, // val / (v[i] > 1e-15 ? v[i] : 1.0)            (vidal.rs:378-383)
+    TT_SCALE_INVERT = 3,    // lop only, no vectors: |val| > 1e-15 ? 1 / val : 0  (vidal.rs:648-656)
+};
+struct TtScaleDesc {
+    const double* src;
+    double* dst;
+    int l, s, r;
+    int lanes;                      // tt_scale_lanes(l)
+    const double* lv; int ln, lop;
+    const double* rv; int rn, rop;
+    unsigned long long first_item;  // ascending prefix sum of tt_scale_items over the table
+};
+constexpr int TT_SCALE_COLS = 4;            // passes of 256 / lanes columns per item
+constexpr unsigned TT_SCALE_MAX_BLOCKS = 1024; // more items than this: a workgroup walks several (item += gridDim.x)
+int tt_scale_lanes(int l);
+unsigned long long tt_scale_items(int l, int s, int r);
+void tt_bond_scale_launch(const TtScaleDesc* d_descs, int n_descs, unsigned long long n_items, hipStream_t stream);
+// out (m x n, ldo) = in (m x n, ldi) * diag(d_s), one multiply per element (svd_factorize_right_matrix, vidal.rs:106-111)
+void col_scale_launch(const double* in, int ldi, int m, int n, const double* d_s, double* out, int ldo, hipStream_t stream);
 void tt_norm2_step_launch(const TtCoreDesc& core, const double* d_cur, bool first, double* d_nxt, hipStream_t stream);
 void tt_env_left_launch(const TtCoreDesc* d_cores, int split, int max_bond, const uint32_t* d_idx, int n_items,
                         double* d_out, int ld, hipStream_t stream);

@@ -5,6 +5,7 @@
 //   left / right environments + dots       <- TTCache::evaluate_left / evaluate_right / evaluate_many
 //                                            (simplett/src/cache.rs:430-688, einsum_helper.rs:192-268)
 //   generic axis permutation               <- the dense tensor layer (tensorops.hip) and the zip-up MPO contraction (mpo.hip)
+//   bond scaling, column scaling           <- the Vidal / inverse forms (simplett/src/vidal.rs:106-111, :364-388, :456-492, :551-663, :730-766)
 // The chain contractions keep the reference's summation order (index ascending, separately rounded multiply and
 // add; built with -ffp-contract=off), so their results are bit-identical to the CPU oracle's.
 #include "kernels.hpp"
@@ -211,6 +212,75 @@ __global__ void __launch_bounds__(256) tt_env_dot_kernel(const double* __restric
     }
 }
 
+// One factor of tt_bond_scale_kernel: what the reference multiplies or divides an element by for bond index `i` of a vector of `n`
+// values.  Multiply: v[i], 1.0 beyond the vector (vidal.rs:476-480).  Guarded divide: v[i] if it is above 1e-15, else 1.0 (:378-382).
+__device__ __forceinline__ double bond_factor(const double* v, int n, int op, int i)
+{
+    if (i >= n) return 1.0;
+    const double x = v[i];
+    if (op == TT_SCALE_DIV_GUARD) return x > 1e-15 ? x : 1.0;
+    return x;
+}
+__device__ __forceinline__ double bond_apply(double val, double f, int op)
+{
+    if (op == TT_SCALE_MUL) return val * f;
+    if (op == TT_SCALE_DIV_GUARD) return val / f;
+    return val;
+}
+
+// Vidal / inverse arithmetic of a whole train in one launch: a ragged batch over a descriptor table.  An item is TT_SCALE_COLS
+// passes of 256 / lt columns of one core (lt lanes along l, a power of two; a column is one (s, r) pair, l elements contiguous in
+// memory), so consecutive lanes read consecutive doubles and the right-bond factor is read once per column.  Every element is
+// dst = (src op_l lv[l]) op_r rv[r]: at most two correctly rounded operations, left factor first (vidal.rs:611-616).
+// lop == TT_SCALE_INVERT: the element itself is mapped to 1/v if |v| > 1e-15 else 0 (vidal.rs:648-656), no vectors.
+__global__ void __launch_bounds__(256) tt_bond_scale_kernel(const TtScaleDesc* descs, int n_descs, unsigned long long n_items)
+{
+    const int tid = threadIdx.x;
+    for (unsigned long long item = blockIdx.x; item < n_items; item += gridDim.x) {
+        // the descriptor this item belongs to: first_item ascends, the last one with first_item <= item
+        int lo = 0, hi = n_descs - 1;
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (descs[mid].first_item <= item) lo = mid;
+            else hi = mid - 1;
+        }
+        const TtScaleDesc d = descs[lo];
+        const int lt = d.lanes, cpp = 256 / lt; // columns per pass
+        const int tx = tid & (lt - 1), ty = tid / lt;
+        const size_t ncols = (size_t)d.s * d.r;
+        const size_t c0 = (size_t)(item - d.first_item) * (size_t)(cpp * TT_SCALE_COLS);
+        for (int pass = 0; pass < TT_SCALE_COLS; ++pass) {
+            const size_t c = c0 + (size_t)pass * cpp + ty;
+            if (c >= ncols) break;
+            const int ri = (int)(c / (size_t)d.s);
+            const double fr = d.rop == TT_SCALE_NONE ? 1.0 : bond_factor(d.rv, d.rn, d.rop, ri);
+            const double* src = d.src + (size_t)d.l * c;
+            double* dst = d.dst + (size_t)d.l * c;
+            for (int li = tx; li < d.l; li += lt) {
+                double val = src[li];
+                if (d.lop == TT_SCALE_INVERT) {
+                    val = fabs(val) > 1e-15 ? 1.0 / val : 0.0;
+                } else {
+                    if (d.lop != TT_SCALE_NONE) val = bond_apply(val, bond_factor(d.lv, d.ln, d.lop, li), d.lop);
+                    val = bond_apply(val, fr, d.rop);
+                }
+                dst[li] = val;
+            }
+        }
+    }
+}
+
+// out (m x n, ldo) = in (m x n, ldi) * diag(s): one multiply per element (U * S of vidal.rs:106-111), s read once per column
+__global__ void __launch_bounds__(256) col_scale_kernel(const double* in, int ldi, int m, int n, const double* __restrict__ s, double* out,
+                                                        int ldo)
+{
+    for (int j = blockIdx.y; j < n; j += gridDim.y) {
+        const double f = s[j];
+        for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < m; i += gridDim.x * blockDim.x)
+            out[i + (size_t)ldo * j] = in[i + (size_t)ldi * j] * f;
+    }
+}
+
 struct PermuteArgs {
     int rank;
     unsigned long long total;
@@ -251,6 +321,35 @@ void permute_launch(const double* in, const size_t* dims, const size_t* perm, in
     }
     const unsigned blocks = (unsigned)std::min<size_t>((total + 255) / 256, 4096);
     hipLaunchKernelGGL(permute_kernel, dim3(blocks), dim3(256), 0, stream, in, out, a);
+}
+
+int tt_scale_lanes(int l)
+{
+    int lt = 1;
+    while (lt < l && lt < 256) lt <<= 1;
+    return lt;
+}
+
+unsigned long long tt_scale_items(int l, int s, int r)
+{
+    const unsigned long long ncols = (unsigned long long)s * r;
+    const unsigned long long per = (unsigned long long)(256 / tt_scale_lanes(l)) * TT_SCALE_COLS;
+    return l > 0 ? (ncols + per - 1) / per : 0;
+}
+
+void tt_bond_scale_launch(const TtScaleDesc* d_descs, int n_descs, unsigned long long n_items, hipStream_t stream)
+{
+    if (n_descs <= 0 || n_items == 0) return;
+    const unsigned blocks = (unsigned)std::min<unsigned long long>(n_items, TT_SCALE_MAX_BLOCKS);
+    hipLaunchKernelGGL(tt_bond_scale_kernel, dim3(blocks), dim3(256), 0, stream, d_descs, n_descs, n_items);
+}
+
+void col_scale_launch(const double* in, int ldi, int m, int n, const double* d_s, double* out, int ldo, hipStream_t stream)
+{
+    if (m <= 0 || n <= 0) return;
+    const unsigned bx = (unsigned)std::min((m + 255) / 256, 1024);
+    const unsigned by = (unsigned)std::min(n, 1024);
+    hipLaunchKernelGGL(col_scale_kernel, dim3(bx, by), dim3(256), 0, stream, in, ldi, m, n, d_s, out, ldo);
 }
 
 void core_reshape_launch(const double* in, int L, int S, int R, int mode, double* out, hipStream_t stream)

@@ -2148,3 +2148,5 @@ from . import quanticstransform  # noqa: E402
 from .quanticstransform import (BoundaryCondition, TriangleType, AffineParams, QuanticsOperator, shift_operator,  # noqa: E402,F401
                                 shift_operator_multivar, flip_operator, flip_operator_multivar, cumsum_operator, triangle_operator,
                                 affine_operator, affine_transform_matrix, identity_mpo, difference_kernel_mpo)
+from . import canonical  # noqa: E402
+from .canonical import SiteTensorTrain, VidalTensorTrain, InverseTensorTrain, center_canonicalize  # noqa: E402,F401
