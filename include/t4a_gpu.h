@@ -823,6 +823,41 @@ t4a_gpu_status t4a_gpu_mpo_to_tt(const t4a_gpu_mpo* mpo, t4a_gpu_tt** out);
 /* LinearOperator::transpose: s1 <-> s2 of every site, one axis permutation per site on the MPO's stream. */
 t4a_gpu_status t4a_gpu_mpo_transpose(const t4a_gpu_mpo* mpo, t4a_gpu_mpo** out);
 
+/* Variational (fit) contraction C ~ A·B with a bond cap.  This project's, as t4a_gpu_mpo_contract_tci is: the reference reserves
+ * FitOptions (contract_fit.rs:19-46) and answers Unsupported, and t4a_gpu_mpo_contract(.., T4A_GPU_MPO_FIT, ..) keeps answering
+ * NOT_IMPLEMENTED as dispatch.rs does.  The algorithm is the two-site fit of tensor4all-treetn (treetn/fit.rs) on a chain: C is kept
+ * with an orthogonality centre, the environments of A·B against C are cached, every bond step factorises
+ * Theta = (L_i A_i B_i) (A_{i+1} B_{i+1} R_{i+2}) with the rank rule of t4a_gpu_mpo_contract (s >= tolerance * s_max, at most
+ * max_bond_dim values, at least one; LU and CI fall back to SVD, RSVD is NOT_IMPLEMENTED) and moves the centre.  One sweep visits
+ * bonds 0 .. n-2 to the right, then n-2 .. 0 to the left.  norms[0] is the Frobenius norm of the start, norms[k] the norm of the
+ * singular values kept at the last step of sweep k; the sweeps stop after sweep k when |norms[k] / norms[k-1] - 1| < convergence_tol
+ * or k == max_sweeps.
+ * initial: the start, or NULL for the zip-up product with the same tolerance, cap and method.  It must have the length of a and the
+ * site dims (s1 of a, s2 of b); its bonds are free.  max_sweeps == 0 returns the start as it is, one site gives the exact product,
+ * no site the empty MPO; none of the three runs a sweep (*n_sweeps = 0, norms untouched).
+ * n_sweeps (may be NULL): the sweeps run.  norms (may be NULL): max_sweeps + 1 entries, the first *n_sweeps + 1 are written.
+ * INVALID_ARGUMENT: the shape errors of t4a_gpu_mpo_contract (same messages), an initial of another length or other site dims, a
+ * negative or non-finite tolerance or convergence_tol, an unknown factorize_method. */
+typedef struct {
+    double tolerance;
+    int32_t has_max_bond_dim; /* 0 <=> None */
+    size_t max_bond_dim;
+    size_t max_sweeps;
+    double convergence_tol;
+    int32_t factorize_method; /* T4A_GPU_FACTORIZE_* */
+} t4a_gpu_mpo_fit_options;
+/* FitOptions::default(): 1e-12, Some(100), 10, 1e-10, SVD */
+t4a_gpu_status t4a_gpu_mpo_fit_options_default(t4a_gpu_mpo_fit_options* out);
+t4a_gpu_status t4a_gpu_mpo_contract_fit(const t4a_gpu_mpo* a, const t4a_gpu_mpo* b, const t4a_gpu_mpo_fit_options* options,
+                                        const t4a_gpu_mpo* initial /* may be NULL */, t4a_gpu_mpo** out, size_t* n_sweeps,
+                                        double* norms /* max_sweeps + 1 entries, may be NULL */);
+/* Test hook: one half product of the fit at `site`, launched exactly as the sweeps launch it (csrc/kernels_mpo_fit.hip), with host
+ * arrays in and out, all column-major.  side 0: env is L[n_env, la, lb], out is P[n_env, s1, s2, ra, rb] = L A_site B_site;
+ * side 1: env is R[ra, rb, n_env], out is Q[la, lb, s1, s2, n_env] = A_site B_site R  (la, ra: the bonds of a's site, lb, rb of b's,
+ * s1 of a, s2 of b).  INVALID_ARGUMENT: the shape errors of t4a_gpu_mpo_contract, site out of range, n_env == 0, side not 0 or 1. */
+t4a_gpu_status t4a_gpu_mpo_fit_half(const double* env, size_t n_env, int32_t side, const t4a_gpu_mpo* a, const t4a_gpu_mpo* b,
+                                    size_t site, double* out);
+
 /* =====================================================================================
  * Contraction<f64>: the lazy product A·B of two MPOs (opaque handle; both operands resident on the device)
  * tensor4all-simplett/src/mpo/contraction.rs:60-383

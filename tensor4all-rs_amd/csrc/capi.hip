@@ -3711,6 +3711,64 @@ t4a_gpu_status t4a_gpu_mpo_transpose(const t4a_gpu_mpo* mpo, t4a_gpu_mpo** out)
     });
 }
 
+// ---- variational (fit) contraction of two MPOs (mpo.hpp: mpo_contract_fit) ----
+t4a_gpu_status t4a_gpu_mpo_fit_options_default(t4a_gpu_mpo_fit_options* out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(out);
+        const MpoFitOptions d;
+        out->tolerance = d.tolerance;
+        out->has_max_bond_dim = d.max_bond_dim != 0;
+        out->max_bond_dim = d.max_bond_dim;
+        out->max_sweeps = d.max_sweeps;
+        out->convergence_tol = d.convergence_tol;
+        out->factorize_method = (int32_t)d.method;
+    });
+}
+
+t4a_gpu_status t4a_gpu_mpo_contract_fit(const t4a_gpu_mpo* a, const t4a_gpu_mpo* b, const t4a_gpu_mpo_fit_options* options,
+                                        const t4a_gpu_mpo* initial, t4a_gpu_mpo** out, size_t* n_sweeps, double* norms)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(out);
+        *out = nullptr;
+        if (n_sweeps) *n_sweeps = 0;
+        T4A_REQUIRE_PTR(options);
+        // the options are checked on the host before an operand is looked at
+        if (options->factorize_method < 0 || options->factorize_method > 3) throw Error(T4A_GPU_INVALID_ARGUMENT, "unknown factorize method");
+        MpoFitOptions o;
+        o.tolerance = options->tolerance;
+        o.max_bond_dim = options->has_max_bond_dim ? options->max_bond_dim : 0;
+        if (options->has_max_bond_dim && options->max_bond_dim == 0)
+            throw Error(T4A_GPU_INVALID_ARGUMENT, "contract_fit: max_bond_dim must be at least 1");
+        o.max_sweeps = options->max_sweeps;
+        o.convergence_tol = options->convergence_tol;
+        o.method = (MpoFactorizeMethod)options->factorize_method;
+        mpo_fit_validate_options(o);
+        T4A_REQUIRE_PTR(a);
+        T4A_REQUIRE_PTR(b);
+        MpoFitInfo info;
+        *out = new t4a_gpu_mpo{mpo_contract_fit(*a->impl, *b->impl, o, initial ? initial->impl.get() : nullptr, info)};
+        if (n_sweeps) *n_sweeps = info.n_sweeps;
+        if (norms) std::copy(info.norms.begin(), info.norms.end(), norms);
+    });
+}
+
+t4a_gpu_status t4a_gpu_mpo_fit_half(const double* env, size_t n_env, int32_t side, const t4a_gpu_mpo* a, const t4a_gpu_mpo* b,
+                                    size_t site, double* out)
+{
+    return guarded([&] {
+        if (side != 0 && side != 1) throw Error(T4A_GPU_INVALID_ARGUMENT, "fit_half: side must be 0 (left) or 1 (right)");
+        if (n_env == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "fit_half: the environment has a zero dimension");
+        T4A_REQUIRE_PTR(env);
+        T4A_REQUIRE_PTR(a);
+        T4A_REQUIRE_PTR(b);
+        T4A_REQUIRE_PTR(out);
+        std::vector<double> v = mpo_fit_half(env, n_env, side == 1, *a->impl, *b->impl, site);
+        std::memcpy(out, v.data(), v.size() * sizeof(double));
+    });
+}
+
 // ---- Contraction<f64>: the lazy product of two MPOs (tensor4all-simplett/src/mpo/contraction.rs:60-383) ----
 t4a_gpu_status t4a_gpu_contraction_new(const t4a_gpu_mpo* a, const t4a_gpu_mpo* b, t4a_gpu_contraction** out)
 {

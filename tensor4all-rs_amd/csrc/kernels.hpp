@@ -583,6 +583,27 @@ struct MpoSiteJob {
 void mpo_site_contract_launch(const MpoSiteJob* d_jobs, int n_jobs, unsigned long long total, hipStream_t stream);
 
 // ------------------------------------------------------------------------------------------------
+// kernels_mpo_fit.hip — half product of the variational MPO-MPO fit (mpo_fit.hip): an environment times one site of A and one of B,
+//   out[n on + s os + t ot + c oc + d od] =
+//     sum_{k < K} sum_{b < Lb} ( sum_{a < La} E[n en + a ea + b eb] A[a aa + s as + k ak + c ac] ) B[b bb + k bk + t bt + d bd]
+// for n < N, s < S, t < T, c < C, d < D in one launch (k outer, every sum ascending).  All strides are in elements; every operand
+// and the output hold at most INT_MAX elements.  Both orientations of the fit (left environment / right environment) are this one
+// call with other strides.  Returns false, having launched nothing, when the grid would hold more than INT_MAX workgroups.
+// ------------------------------------------------------------------------------------------------
+struct MpoFitHalfDesc {
+    const double* E;
+    const double* A;
+    const double* B;
+    double* out;
+    int N, La, Lb, S, K, T, C, D;
+    long long en, ea, eb;
+    long long aa, as, ak, ac;
+    long long bb, bk, bt, bd;
+    long long on, os, ot, oc, od;
+};
+bool mpo_fit_half_launch(const MpoFitHalfDesc& d, hipStream_t stream);
+
+// ------------------------------------------------------------------------------------------------
 // kernels_contraction.hip — environments of the lazy product A·B of two MPOs (simplett/src/mpo/contraction.rs:262-383) for a batch
 // of unique index halves, one workgroup per half.  An environment is a matrix over the bond pair, column-major [a + dim_a * b];
 // item `it` of a launch is written to d_out + it * ld.  idx holds the (i, j) pairs of the walked sites per item, item-major.

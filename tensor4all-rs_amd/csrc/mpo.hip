@@ -1,11 +1,13 @@
 // mpo.hip — MPO<f64> and the contraction of two MPOs on the device (see mpo.hpp).  Shape bookkeeping is host work; every
 // floating-point operation runs in gfx950 kernels: the naive site contraction (kernels_mpo.hip), the f64-MFMA GEMM and the
-// gathers (kernels_dense.hip), the axis permutation (kernels_tt.hip), the Householder QR and the Jacobi SVD (kernels_linalg.hip).
+// gathers (kernels_dense.hip), the axis permutation (kernels_tt.hip), the Householder QR and the Jacobi SVD (kernels_linalg.hip),
+// the half products of the variational fit (kernels_mpo_fit.hip).
 #include "mpo.hpp"
 #include "tensorops.hpp"
 
 #include <algorithm>
 #include <climits>
+#include <cmath>
 #include <string>
 
 namespace t4a {
@@ -235,6 +237,139 @@ struct Contractor {
         }
         return out;
     }
+
+    // ---- variational fit (mpo.hpp: mpo_contract_fit).  C_i[c_i, s, t, c_{i+1}] is the fitted MPO,
+    //   L_i[c_i, la_i, lb_i] the contraction of the sites < i of A, B and C,  R_i[la_i, lb_i, c_i] that of the sites >= i,
+    //   P_i[c_i, s, t, la', lb'] = L_i A_i B_i   and   Q_i[la, lb, s, t, c_{i+1}] = A_i B_i R_{i+1}   the half products,
+    // all column-major, so that P_i is a (c_i s t) x (la' lb') matrix and Q_i a (la lb) x (s t c_{i+1}) matrix as they stand.
+    std::vector<DevBuf<double>> envL, envR; // envL[i] = L_i (i < n), envR[i] = R_i (1 <= i <= n)
+    DevBuf<double> hp, hq, theta;
+
+    static MpoFitHalfDesc half_desc(bool right, const double* env, size_t n_env, const double* A, size_t la, size_t s, size_t k, size_t ra,
+                                    const double* B, size_t lb, size_t t, size_t rb, double* out)
+    {
+        MpoFitHalfDesc d{};
+        d.E = env;
+        d.A = A;
+        d.B = B;
+        d.out = out;
+        d.N = (int)n_env;
+        d.S = (int)s;
+        d.K = (int)k;
+        d.T = (int)t;
+        // A[la, s, k, ra], B[lb, k, t, rb]
+        d.as = (long long)la;
+        d.ak = (long long)(la * s);
+        d.bk = (long long)lb;
+        d.bt = (long long)(lb * k);
+        const long long a_l = 1, a_r = (long long)(la * s * k), b_l = 1, b_r = (long long)(lb * k * t);
+        if (!right) { // P: E = L[n, la, lb], out[n, s, t, ra, rb]
+            d.La = (int)la, d.Lb = (int)lb, d.C = (int)ra, d.D = (int)rb;
+            d.en = 1, d.ea = (long long)n_env, d.eb = (long long)(n_env * la);
+            d.aa = a_l, d.ac = a_r, d.bb = b_l, d.bd = b_r;
+            d.on = 1, d.os = (long long)n_env, d.ot = (long long)(n_env * s), d.oc = (long long)(n_env * s * t),
+            d.od = (long long)(n_env * s * t * ra);
+        } else { // Q: E = R[ra, rb, n], out[la, lb, s, t, n]
+            d.La = (int)ra, d.Lb = (int)rb, d.C = (int)la, d.D = (int)lb;
+            d.ea = 1, d.eb = (long long)ra, d.en = (long long)(ra * rb);
+            d.aa = a_r, d.ac = a_l, d.bb = b_r, d.bd = b_l;
+            d.oc = 1, d.od = (long long)la, d.os = (long long)(la * lb), d.ot = (long long)(la * lb * s), d.on = (long long)(la * lb * s * t);
+        }
+        return d;
+    }
+
+    // one half product of site i into `out`: P_i from L_i (n_env = c_i) or Q_i from R_{i+1} (n_env = c_{i+1})
+    void half(const Mpo& a, const Mpo& b, size_t i, bool right, const double* env, size_t n_env, DevBuf<double>& out)
+    {
+        const DevCore& A = a.tt.cores[i];
+        const DevCore& B = b.tt.cores[i];
+        const size_t S1 = a.sd[i][0], K = a.sd[i][1], T = b.sd[i][1];
+        const std::string where = "contract_fit: site " + std::to_string(i);
+        check_count(n_env * S1, T, right ? A.l : A.r, right ? B.l : B.r, where);
+        check_count(n_env, A.l, B.l, 1, where);
+        check_count(n_env, A.r, B.r, 1, where);
+        out.reserve(n_env * S1 * T * (right ? A.l * B.l : A.r * B.r));
+        if (!mpo_fit_half_launch(half_desc(right, env, n_env, A.buf.get(), A.l, S1, K, A.r, B.buf.get(), B.l, T, B.r, out.get()), st))
+            throw Error(T4A_GPU_INVALID_ARGUMENT, where + " needs more than INT_MAX workgroups");
+    }
+
+    // R_i = Q_i C_i^T over (s, t, c_{i+1}), with C_i given as the c_i x (s t c_{i+1}) matrix `rows` of leading dimension ld
+    void right_env(const Mpo& a, const Mpo& b, size_t i, size_t ci, size_t cnext, const double* rows, int ld)
+    {
+        const size_t ab = a.tt.cores[i].l * b.tt.cores[i].l, rest = a.sd[i][0] * b.sd[i][1] * cnext;
+        envR[i].reserve(ab * ci);
+        GemmDesc g = gemm_desc((int)ab, (int)ci, (int)rest, hq.get(), (int)ab, rows, ld, envR[i].get(), (int)ab);
+        g.transB = 1;
+        gemm_launch(g, st);
+    }
+
+    // The sweeps.  `c` is the start (any bonds); it leaves as the fitted MPO with its orthogonality centre on site 0.
+    void fit(const Mpo& a, const Mpo& b, std::vector<DevCore>& c, size_t max_sweeps, double convergence_tol, MpoFitInfo& info)
+    {
+        const size_t n = c.size();
+        right_canonicalize(c);
+        envL.resize(n);
+        envR.resize(n + 1);
+        envL[0].reserve(1);
+        envR[n].reserve(1);
+        fill_launch(envL[0].get(), 1, 1.0, st);
+        fill_launch(envR[n].get(), 1, 1.0, st);
+        for (size_t i = n - 1; i >= 2; --i) {
+            half(a, b, i, true, envR[i + 1].get(), c[i].r, hq);
+            right_env(a, b, i, c[i].l, c[i].r, c[i].buf.get(), (int)c[i].l);
+        }
+        std::vector<double> h0(c[0].size());
+        T4A_HIP(hipMemcpyAsync(h0.data(), c[0].buf.get(), sizeof(double) * h0.size(), hipMemcpyDeviceToHost, st));
+        eng.sync();
+        double norm_prev = 0.0;
+        for (double v : h0) norm_prev = std::hypot(norm_prev, v);
+        info.norms.push_back(norm_prev);
+
+        auto bond_step = [&](size_t i, bool move_right) {
+            const size_t ci = c[i].l, cn = c[i + 1].r;
+            const size_t sl = c[i].s, sr = c[i + 1].s; // s t of the two sites
+            const size_t ab = a.tt.cores[i + 1].l * b.tt.cores[i + 1].l;
+            half(a, b, i, false, envL[i].get(), ci, hp);
+            half(a, b, i + 1, true, envR[i + 2].get(), cn, hq);
+            const int M = (int)(ci * sl), N = (int)(sr * cn);
+            check_count(ci * sl, sr * cn, 1, 1, "contract_fit: bond " + std::to_string(i));
+            theta.reserve((size_t)M * N);
+            gemm_launch(gemm_desc(M, N, (int)ab, hp.get(), M, hq.get(), (int)ab, theta.get(), M), st);
+            const size_t rank = svd_rank(theta.get(), M, N);
+            const int kmin = std::min(M, N);
+            DevCore nl = new_core(ci, sl, rank), nr = new_core(rank, sr, cn);
+            if (move_right) { // C_i = U, C_{i+1} = diag(S) Vt, L_{i+1} = U^T P_i
+                left(M, (int)rank, nl.buf.get());
+                right(M, N, (int)rank, nr.buf.get());
+                envL[i + 1].reserve(rank * ab);
+                GemmDesc g = gemm_desc((int)rank, (int)ab, M, u.get(), M, hp.get(), M, envL[i + 1].get(), (int)rank);
+                g.transA = 1;
+                gemm_launch(g, st);
+            } else { // C_i = U diag(S), C_{i+1} = Vt, R_{i+1} = Q_{i+1} Vt^T
+                diag_scale_launch(u.get(), M, M, (int)rank, s.get(), false, nl.buf.get(), M, st);
+                gather_launch(vt.get(), kmin, nullptr, (int)rank, nullptr, N, nr.buf.get(), (int)rank, st);
+                right_env(a, b, i + 1, rank, cn, vt.get(), kmin);
+            }
+            T4A_HIP(hipGetLastError());
+            eng.sync(); // the old sites are released below; u / s / vt are overwritten by the next step
+            c[i] = std::move(nl);
+            c[i + 1] = std::move(nr);
+            double nrm = 0.0;
+            for (size_t j = 0; j < rank; ++j) nrm = std::hypot(nrm, hs[j]);
+            return nrm;
+        };
+
+        for (size_t sweep = 1; sweep <= max_sweeps; ++sweep) {
+            double nrm = 0.0;
+            for (size_t i = 0; i + 1 < n; ++i) nrm = bond_step(i, true);
+            for (size_t i = n - 1; i-- > 0;) nrm = bond_step(i, false);
+            info.norms.push_back(nrm);
+            info.n_sweeps = sweep;
+            const bool converged = std::fabs(nrm / norm_prev - 1.0) < convergence_tol; // a zero product: 0 / 0 is NaN, never converged
+            norm_prev = nrm;
+            if (converged) break;
+        }
+    }
 };
 
 } // namespace
@@ -339,15 +474,23 @@ void Mpo::relabel_site_dims(const std::vector<std::array<size_t, 2>>& site_dims)
     sd = site_dims;
 }
 
-std::unique_ptr<Mpo> mpo_contract(Mpo& a, Mpo& b, MpoAlgorithm alg, bool compress, const MpoContractionOptions& opt)
+namespace {
+// the shape checks of contract_naive / contract_zipup / contract_fit (contract_fit.rs:74-92)
+void check_operands(const Mpo& a, const Mpo& b)
 {
     if (a.len() != b.len())
         throw Error(T4A_GPU_INVALID_ARGUMENT, "MPO length mismatch: expected " + std::to_string(a.len()) + ", got " + std::to_string(b.len()));
-    const size_t n = a.len();
-    for (size_t i = 0; i < n; ++i)
+    for (size_t i = 0; i < a.len(); ++i)
         if (a.sd[i][1] != b.sd[i][0])
             throw Error(T4A_GPU_INVALID_ARGUMENT, "Shared shape mismatch at site " + std::to_string(i) + ": MPO A has site_dim_2=" +
                                                       std::to_string(a.sd[i][1]) + ", MPO B has site_dim_1=" + std::to_string(b.sd[i][0]));
+}
+} // namespace
+
+std::unique_ptr<Mpo> mpo_contract(Mpo& a, Mpo& b, MpoAlgorithm alg, bool compress, const MpoContractionOptions& opt)
+{
+    check_operands(a, b);
+    const size_t n = a.len();
     if (alg == MpoAlgorithm::Fit) // contract_fit.rs:65-96
         throw Error(T4A_GPU_NOT_IMPLEMENTED, "Unsupported operation: simplett variational MPO fitting is not implemented; use contract_naive or "
                                              "contract_zipup instead");
@@ -365,6 +508,84 @@ std::unique_ptr<Mpo> mpo_contract(Mpo& a, Mpo& b, MpoAlgorithm alg, bool compres
     }
     a.tt.eng.sync();
     return std::make_unique<Mpo>(std::move(cores), sd);
+}
+
+void mpo_fit_validate_options(const MpoFitOptions& opt)
+{
+    if (!(opt.tolerance >= 0.0) || !std::isfinite(opt.tolerance))
+        throw Error(T4A_GPU_INVALID_ARGUMENT, "contract_fit: tolerance must be finite and not negative");
+    if (!(opt.convergence_tol >= 0.0) || !std::isfinite(opt.convergence_tol))
+        throw Error(T4A_GPU_INVALID_ARGUMENT, "contract_fit: convergence_tol must be finite and not negative");
+}
+
+std::unique_ptr<Mpo> mpo_contract_fit(Mpo& a, Mpo& b, const MpoFitOptions& opt, Mpo* initial, MpoFitInfo& info)
+{
+    info = MpoFitInfo{};
+    check_operands(a, b);
+    const size_t n = a.len();
+    std::vector<std::array<size_t, 2>> sd(n);
+    for (size_t i = 0; i < n; ++i) sd[i] = {a.sd[i][0], b.sd[i][1]};
+    if (initial) {
+        if (initial->len() != n)
+            throw Error(T4A_GPU_INVALID_ARGUMENT,
+                        "contract_fit: initial has " + std::to_string(initial->len()) + " sites, the product has " + std::to_string(n));
+        for (size_t i = 0; i < n; ++i)
+            if (initial->sd[i] != sd[i])
+                throw Error(T4A_GPU_INVALID_ARGUMENT, "contract_fit: initial has site dims (" + std::to_string(initial->sd[i][0]) + ", " +
+                                                          std::to_string(initial->sd[i][1]) + ") at site " + std::to_string(i) +
+                                                          ", the product has (" + std::to_string(sd[i][0]) + ", " + std::to_string(sd[i][1]) + ")");
+    }
+    mpo_fit_validate_options(opt);
+    if (n == 0) return std::make_unique<Mpo>(std::vector<DevCore>{}, sd);
+    b.tt.eng.sync(); // b's and initial's cores are read on a's stream
+    if (initial) initial->tt.eng.sync();
+    MpoContractionOptions co;
+    co.tolerance = opt.tolerance;
+    co.max_bond_dim = opt.max_bond_dim;
+    co.method = opt.method;
+    Contractor c(a.tt.eng, co);
+    std::vector<DevCore> cores;
+    if (n == 1) { // the exact one-site product, nothing to sweep
+        cores = c.naive(a, b);
+    } else {
+        if (initial) {
+            for (const DevCore& src : initial->tt.cores) {
+                DevCore cp = new_core(src.l, src.s, src.r);
+                T4A_HIP(hipMemcpyAsync(cp.buf.get(), src.buf.get(), sizeof(double) * src.size(), hipMemcpyDeviceToDevice, c.st));
+                cores.push_back(std::move(cp));
+            }
+        } else {
+            cores = c.zipup(a, b); // the initialiser of treetn::contract_fit, same tolerance, cap and method
+        }
+        if (opt.max_sweeps > 0) c.fit(a, b, cores, opt.max_sweeps, opt.convergence_tol, info);
+    }
+    a.tt.eng.sync();
+    return std::make_unique<Mpo>(std::move(cores), sd);
+}
+
+std::vector<double> mpo_fit_half(const double* env, size_t n_env, bool right, Mpo& a, Mpo& b, size_t site)
+{
+    check_operands(a, b);
+    if (site >= a.len()) throw Error(T4A_GPU_INVALID_ARGUMENT, "fit_half: site " + std::to_string(site) + " is out of range");
+    if (n_env == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "fit_half: the environment has a zero dimension");
+    const DevCore& A = a.tt.cores[site];
+    const DevCore& B = b.tt.cores[site];
+    const size_t ea = right ? A.r : A.l, eb = right ? B.r : B.l, oa = right ? A.l : A.r, ob = right ? B.l : B.r;
+    check_count(n_env, ea, eb, 1, "fit_half: the environment");
+    check_count(n_env * a.sd[site][0], b.sd[site][1], oa, ob, "fit_half: the half product");
+    b.tt.eng.sync();
+    MpoContractionOptions co;
+    Contractor c(a.tt.eng, co);
+    DevBuf<double> d_env, d_out;
+    const size_t ne = n_env * ea * eb, no = n_env * a.sd[site][0] * b.sd[site][1] * oa * ob;
+    d_env.reserve(ne);
+    T4A_HIP(hipMemcpyAsync(d_env.get(), env, sizeof(double) * ne, hipMemcpyHostToDevice, c.st));
+    c.half(a, b, site, right, d_env.get(), n_env, d_out);
+    T4A_HIP(hipGetLastError());
+    std::vector<double> out(no);
+    T4A_HIP(hipMemcpyAsync(out.data(), d_out.get(), sizeof(double) * no, hipMemcpyDeviceToHost, c.st));
+    a.tt.eng.sync();
+    return out;
 }
 
 } // namespace t4a

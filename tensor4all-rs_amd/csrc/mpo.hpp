@@ -52,4 +52,30 @@ public:
 // Fit answers NOT_IMPLEMENTED after the shape checks, RSVD where the reference's factorize is reached.
 std::unique_ptr<Mpo> mpo_contract(Mpo& a, Mpo& b, MpoAlgorithm alg, bool compress, const MpoContractionOptions& opt);
 
+// ---- variational (fit) contraction C ~ A·B.  This project's: the reference reserves FitOptions (contract_fit.rs:19-46) and answers
+// Unsupported; mpo_contract(.., Fit, ..) keeps doing that.  The algorithm is the two-site fit of tensor4all-treetn (treetn/fit.rs)
+// on a chain: C is an MPO with an orthogonality centre, the environments of A·B against C are cached, each bond step forms
+// Theta = P_i Q_{i+1} from two half products (kernels_mpo_fit.hip), factorises it with the SVD rank rule of factorize and moves the
+// centre.  One sweep is bonds 0 .. n-2 to the right, then n-2 .. 0 to the left; sweep k ends with norm_k = |S kept at its last step|,
+// and the sweeps stop when |norm_k / norm_{k-1} - 1| < convergence_tol or k == max_sweeps (norm_0: the start, centred on site 0).
+struct MpoFitOptions { // FitOptions::default()
+    double tolerance = 1e-12;
+    size_t max_bond_dim = 100; // 0 == None
+    size_t max_sweeps = 10;
+    double convergence_tol = 1e-10;
+    MpoFactorizeMethod method = MpoFactorizeMethod::SVD;
+};
+struct MpoFitInfo {
+    size_t n_sweeps = 0;
+    std::vector<double> norms; // norm_0 .. norm_{n_sweeps}; empty when no sweep ran
+};
+// INVALID_ARGUMENT for a negative or non-finite tolerance / convergence_tol (host only)
+void mpo_fit_validate_options(const MpoFitOptions& opt);
+// The start is `initial` (same length and site dims (s1_a, s2_b), any bonds) or, for nullptr, the zip-up product with the same
+// tolerance, cap and method.  max_sweeps == 0 returns the start as it is, one site the exact product, no site the empty MPO.
+std::unique_ptr<Mpo> mpo_contract_fit(Mpo& a, Mpo& b, const MpoFitOptions& opt, Mpo* initial, MpoFitInfo& info);
+// Test hook: the half product of one site exactly as the sweeps launch it.  right == false: env is L[n_env, la, lb] and the result
+// P[n_env, s1, s2, ra, rb]; right == true: env is R[ra, rb, n_env] and the result Q[la, lb, s1, s2, n_env] (all column-major, host).
+std::vector<double> mpo_fit_half(const double* env, size_t n_env, bool right, Mpo& a, Mpo& b, size_t site);
+
 } // namespace t4a

@@ -2143,7 +2143,7 @@ def tensors_to_tensor_train(tensors):
 # (t4a_amd.contract is the labelled-tensor network contraction)
 from . import mpo  # noqa: E402
 from .mpo import (MPO, ContractionOptions, ContractionAlgorithm, FactorizeMethod, contract_naive, contract_zipup,  # noqa: E402,F401
-                  Contraction, contract_tci)
+                  Contraction, contract_tci, FitOptions, FitOptionsC, contract_fit)
 from . import quanticstransform  # noqa: E402
 from .quanticstransform import (BoundaryCondition, TriangleType, AffineParams, QuanticsOperator, shift_operator,  # noqa: E402,F401
                                 shift_operator_multivar, flip_operator, flip_operator_multivar, cumsum_operator, triangle_operator,

@@ -3,7 +3,8 @@
 Mirrors the Rust module ``mpo``: ``MPO``, ``ContractionOptions``, ``ContractionAlgorithm``, ``FactorizeMethod``, ``contract``,
 ``contract_naive``, ``contract_zipup``, and the lazy product ``Contraction`` (mpo/contraction.rs:60-383).  ``contract_tci`` is this
 project's: the product as an MPO by cross interpolation of its elements (the ``algorithm = :TCI`` contraction of
-TensorCrossInterpolation.jl).
+TensorCrossInterpolation.jl).  ``contract_fit`` with ``FitOptions`` is this project's too: the variational two-site fit the
+reference reserves ``FitOptions`` for (mpo/contract_fit.rs) and implements for tree networks (tensor4all-treetn/src/treetn/fit.rs).
 """
 import ctypes
 
@@ -29,6 +30,38 @@ class ContractionOptions:
         self.tolerance = tolerance
         self.max_bond_dim = max_bond_dim
         self.factorize_method = factorize_method
+
+
+class FitOptionsC(ctypes.Structure):
+    """t4a_gpu_mpo_fit_options"""
+    _fields_ = [("tolerance", c_double), ("has_max_bond_dim", c_int32), ("max_bond_dim", c_size_t), ("max_sweeps", c_size_t),
+                ("convergence_tol", c_double), ("factorize_method", c_int32)]
+
+
+class FitOptions:
+    """FitOptions (mpo/contract_fit.rs:19-46); the defaults are FitOptions::default().  ``max_bond_dim=None`` is no cap."""
+
+    def __init__(self, tolerance=1e-12, max_bond_dim=100, max_sweeps=10, convergence_tol=1e-10, factorize_method=FactorizeMethod.SVD):
+        self.tolerance = tolerance
+        self.max_bond_dim = max_bond_dim
+        self.max_sweeps = max_sweeps
+        self.convergence_tol = convergence_tol
+        self.factorize_method = factorize_method
+
+    def to_c(self):
+        for name in ("tolerance", "convergence_tol"):
+            v = float(getattr(self, name))
+            if not (np.isfinite(v) and v >= 0.0):
+                raise T4aError(INVALID_ARGUMENT, f"contract_fit: {name} must be finite and not negative")
+        if self.max_bond_dim is not None and int(self.max_bond_dim) < 1:
+            raise T4aError(INVALID_ARGUMENT, "contract_fit: max_bond_dim must be at least 1")
+        if int(self.max_sweeps) < 0:
+            raise T4aError(INVALID_ARGUMENT, "contract_fit: max_sweeps must not be negative")
+        if self.factorize_method not in (0, 1, 2, 3):
+            raise T4aError(INVALID_ARGUMENT, "unknown factorize method")
+        return FitOptionsC(float(self.tolerance), 0 if self.max_bond_dim is None else 1,
+                           0 if self.max_bond_dim is None else int(self.max_bond_dim), int(self.max_sweeps),
+                           float(self.convergence_tol), int(self.factorize_method))
 
 
 class MPO:
@@ -190,6 +223,46 @@ def contract_zipup(a, b, options=None):
 def contract(a, b, algorithm=ContractionAlgorithm.Naive, options=None):
     """contract (mpo/dispatch.rs:67-92): Naive always compresses; Fit raises NOT_IMPLEMENTED."""
     return _contract(a, b, algorithm, True, options)
+
+
+def contract_fit(a, b, options=None, initial=None, return_info=False):
+    """The truncated product C ~ A·B by the variational two-site fit (t4a_gpu_mpo_contract_fit; this project's, the reference's
+    contract_fit answers Unsupported and ``contract(a, b, ContractionAlgorithm.Fit)`` keeps doing so).  ``options``: a FitOptions,
+    default FitOptions(); ``initial``: the MPO the sweeps start from (same length and site dims as the product, any bonds), default
+    the zip-up product with the same tolerance, cap and method.  ``return_info=True`` gives ``(mpo, info)`` with info
+    ``{"n_sweeps", "norms", "link_dims"}``: norms[0] belongs to the start, norms[k] to sweep k; it is empty when no sweep ran
+    (max_sweeps == 0, fewer than two sites)."""
+    o = (FitOptions() if options is None else options).to_c()
+    if initial is not None and not isinstance(initial, MPO):
+        raise T4aError(INVALID_ARGUMENT, "contract_fit: initial must be an MPO")
+    h = c_void_p()
+    n_sweeps = c_size_t(0)
+    norms = np.full(o.max_sweeps + 1, np.nan)
+    _check(_lib.t4a_gpu_mpo_contract_fit(a._h, b._h, ctypes.byref(o), initial._h if initial is not None else None, ctypes.byref(h),
+                                         ctypes.byref(n_sweeps), _p(norms)))
+    m = MPO._adopt(h)
+    if not return_info:
+        return m
+    k = n_sweeps.value
+    return m, {"n_sweeps": k, "norms": [float(v) for v in norms[:k + 1]] if k else [], "link_dims": m.link_dims()}
+
+
+def _fit_half(env, side, a, b, site):
+    """Test hook (t4a_gpu_mpo_fit_half): side 0, env L[n, la, lb] -> P[n, s1, s2, ra, rb]; side 1, env R[ra, rb, n] ->
+    Q[la, lb, s1, s2, n], with the dims of site ``site`` of ``a`` and ``b``."""
+    env = np.asarray(env, dtype=np.float64)
+    if env.ndim != 3:
+        raise T4aError(INVALID_ARGUMENT, "fit_half: the environment has three legs")
+    la, s1, _, ra = (int(x) for x in a.dims()[site])
+    lb, _, s2, rb = (int(x) for x in b.dims()[site])
+    n = env.shape[2] if side == 1 else env.shape[0]
+    if env.shape != ((ra, rb, n) if side == 1 else (n, la, lb)):
+        raise T4aError(INVALID_ARGUMENT, f"fit_half: the environment has shape {env.shape}")
+    shape = (la, lb, s1, s2, n) if side == 1 else (n, s1, s2, ra, rb)
+    out = np.zeros(max(int(np.prod(shape)), 1))
+    flat = np.ascontiguousarray(env.reshape(-1, order="F")) if env.size else np.zeros(1)
+    _check(_lib.t4a_gpu_mpo_fit_half(_p(flat), c_size_t(n), c_int32(side), a._h, b._h, c_size_t(site), _p(out)))
+    return out[:int(np.prod(shape))].reshape(shape, order="F")
 
 
 def _index_pairs(indices, n, need, exact):
