@@ -1170,6 +1170,110 @@ t4a_gpu_status t4a_gpu_fn_eval(int32_t fid, int32_t n_acc, const double* params,
                                const size_t* local_dims, size_t n_sites, const size_t* idx, size_t n_pts,
                                double* out);
 
+/* =====================================================================================
+ * square_linsolve: (a0 + a1 A) x = b for an MPO A and tensor trains x, b resident on the device
+ * tensor4all-treetn/src/linsolve/ (square/mod.rs:233-351, square/updater.rs, common/projected_operator.rs,
+ * square/projected_state.rs), tensor4all-core/src/krylov.rs:1083-1490 (gmres_affine_impl), restated for a chain.
+ * Scope: a chain, f64, V_in = V_out — every site of A has s1 == s2 == the state's site dimension.  Index mappings, tree
+ * topologies, spectator nodes and complex scalars are not mirrored.
+ * The algorithm is DMRG-style two-site sweeps with a local GMRES.  `init` is canonicalised onto `center` by thin QR sweeps.  The
+ * sweep plan is the Euler tour from `center`, two sites per step, the second node of a step the new centre: bonds center .. n-2 to
+ * the right, n-2 .. 0 to the left, 0 .. center-1 to the right (for center == 0 the order of t4a_gpu_mpo_contract_fit; the reference's
+ * order at an inner centre follows petgraph's adjacency order and is not pinned).  One step at bond (i, i+1): theta_0 = x_i x_{i+1},
+ * the local rhs Lb_i b_i b_{i+1} Rb_{i+2}, GMRES on (a0 + a1 H) theta = rhs from theta_0 with H the projected operator, an SVD of
+ * theta as (chi_l d_i) x (d_{i+1} chi_r) with max_bond_dim and the policy of t4a_gpu_tensor_svd (none: its default), x_i = U and
+ * x_{i+1} = S V^T moving right, x_i = U S and x_{i+1} = V^T moving left, then the environment of the side left behind.
+ * GMRES builds the Arnoldi basis from the unshifted H; a0 and a1 enter the Hessenberg column; Givens rotations and the triangular
+ * solve run on the host, which reads j + 2 doubles per Arnoldi step and one norm per restart.  ||rhs|| < 1e-15 returns the start,
+ * lucky breakdown is at h_{j+1,j} <= 1e-14, the true residual is checked on convergence (local_gmres_options), non-convergence is
+ * a flag, never an error.  Deviation: both orthogonalisation passes are classical Gram-Schmidt (all coefficients of a pass from one
+ * launch), the reference's are modified Gram-Schmidt; the column of H is still pass 1 plus pass 2.
+ * After each sweep with has_convergence_tol the residual ||(a0 + a1 A) x - b|| / ||b|| (the absolute norm when ||b|| <= 1e-15) is
+ * computed from the exact naive apply, add / sub and the norm of the QR-canonical residual train, and the sweeps stop below the
+ * tolerance; otherwise it is computed once at the end if check_residual.  converged is false when no convergence_tol was given.
+ * a1 == 0 or ||A|| <= 1e-15: the solution is rhs / a0, *sweeps = 0 (a0 == 0 as well: INVALID_ARGUMENT).
+ * Memory of a bond step: W (M^2 + N^2 + M N) + (gmres_restart_dim + 1) M N doubles, M = chi_l d_i, N = d_{i+1} chi_r, W the operator
+ * bond between the two sites.
+ * INVALID_ARGUMENT with a message, before the device is touched: fewer than two sites ("the one-site local solve is not
+ * implemented"), lengths differ, a site of A that is not square or does not match the state's or the rhs's site dimension,
+ * center >= n, gmres_restart_dim == 0 or gmres_max_restarts == 0, a negative or non-finite tolerance, a work buffer of a bond step
+ * above INT_MAX elements (the message names the bond).
+ * ===================================================================================== */
+#define T4A_GPU_GMRES_RELATIVE 0
+#define T4A_GPU_GMRES_ABSOLUTE 1
+typedef struct {
+    size_t nfullsweeps;
+    int32_t has_max_bond_dim; /* 0 <=> None */
+    size_t max_bond_dim;
+    int32_t has_svd_policy;   /* 0 <=> None: the default policy of t4a_gpu_tensor_svd */
+    t4a_gpu_svd_policy svd_policy;
+    double gmres_tol;
+    int32_t gmres_tolerance_mode; /* T4A_GPU_GMRES_* */
+    size_t gmres_max_restarts;
+    size_t gmres_restart_dim;
+    double a0, a1;
+    int32_t has_convergence_tol;
+    double convergence_tol;
+    int32_t check_residual;
+} t4a_gpu_linsolve_options;
+typedef struct {
+    size_t local_solves;  /* bond steps */
+    size_t arnoldi_steps; /* over all local solves */
+    size_t apply_calls;   /* projected applies, the residual evaluations of GMRES included */
+} t4a_gpu_linsolve_stats;
+/* LinsolveOptions::default(): 5, None, None, 1e-10, relative, 100, 30, a0 = 0, a1 = 1, None, check_residual = 1 */
+t4a_gpu_status t4a_gpu_linsolve_options_default(t4a_gpu_linsolve_options* out);
+/* The shape checks of t4a_gpu_square_linsolve on plain dimension lists: op_dims4 (left, s1, s2, right) per site, rhs_dims3 (may be
+ * NULL with n_rhs == 0: no rhs) and state_dims3 (left, site, right) per site.  A pure host function, usable without a device. */
+t4a_gpu_status t4a_gpu_linsolve_check_shapes(const size_t* op_dims4, size_t n_op, const size_t* rhs_dims3, size_t n_rhs,
+                                             const size_t* state_dims3, size_t n_state, size_t center, size_t gmres_restart_dim);
+t4a_gpu_status t4a_gpu_square_linsolve(const t4a_gpu_mpo* op, const t4a_gpu_tt* rhs, const t4a_gpu_tt* init, size_t center,
+                                       const t4a_gpu_linsolve_options* options, t4a_gpu_tt** solution, size_t* sweeps,
+                                       int32_t* has_residual, double* residual, int32_t* converged,
+                                       t4a_gpu_linsolve_stats* stats /* may be NULL */);
+/* relative_linear_system_residual (square/mod.rs:432-): ||(a0 + a1 A) x - b|| / ||b||, the absolute norm when ||b|| <= 1e-15 */
+t4a_gpu_status t4a_gpu_relative_linear_system_residual(const t4a_gpu_mpo* op, const t4a_gpu_tt* solution, const t4a_gpu_tt* rhs, double a0,
+                                                       double a1, double* out);
+
+/* ProjectedOperator (common/projected_operator.rs:230-410, :495-631) of <x|A|x> on a chain: an opaque handle that keeps device copies
+ * of the operator and the state.  Environments are column-major L[beta, w, alpha], R[beta, w, alpha] (bra bond, operator bond, ket
+ * bond), computed lazily from the state and cached.
+ * _local_dims: (chi_l, d_site, d_{site+1}, chi_r) of the region (site, site + 1).
+ * _apply: out = H v for that region, v and out column-major [alpha_l, t1, t2, alpha_r] of chi_l d_site d_{site+1} chi_r doubles.
+ * _environment: side 0 the left environment of the sites < bond, side 1 the right environment of the sites >= bond (bond <= n);
+ *   dims receives (chi, W, chi); out may be NULL to query dims.
+ * _invalidate: the caches that contain `site` go stale (left ones beyond it, right ones up to it).
+ * _set_site_tensors: replaces sites (site, site + 1) by host tensors (outer bonds and site dimensions kept, the shared bond free)
+ *   and invalidates both. */
+typedef struct t4a_gpu_projected_operator t4a_gpu_projected_operator;
+t4a_gpu_status t4a_gpu_projected_operator_new(const t4a_gpu_mpo* op, const t4a_gpu_tt* state, t4a_gpu_projected_operator** out);
+void t4a_gpu_projected_operator_release(t4a_gpu_projected_operator* h);
+t4a_gpu_status t4a_gpu_projected_operator_local_dims(const t4a_gpu_projected_operator* h, size_t site, size_t* dims4);
+t4a_gpu_status t4a_gpu_projected_operator_apply(t4a_gpu_projected_operator* h, size_t site, const double* v, double* out);
+t4a_gpu_status t4a_gpu_projected_operator_environment(t4a_gpu_projected_operator* h, int32_t side, size_t bond, size_t* dims3, double* out);
+t4a_gpu_status t4a_gpu_projected_operator_invalidate(t4a_gpu_projected_operator* h, size_t site);
+t4a_gpu_status t4a_gpu_projected_operator_set_site_tensors(t4a_gpu_projected_operator* h, size_t site, const size_t* dims3_a, const double* t_a,
+                                                           const size_t* dims3_b, const double* t_b);
+/* Probe (tools/probe_linsolve.py): device time in milliseconds of the five launches of one Arnoldi step with nb basis vectors at the
+ * region (site, site + 1), each measured with events around `reps` launches behind a warm-up launch: ms[0] T = HL V, ms[1] Y = T HR,
+ * ms[2] gs_dots, ms[3] gs_update, ms[4] gs_normalize. */
+t4a_gpu_status t4a_gpu_projected_operator_time_step(t4a_gpu_projected_operator* h, size_t site, size_t nb, size_t reps, double* ms /* [5] */);
+/* The apply on caller-supplied environments, launched exactly as the sweeps launch it (the two half-operator builders of
+ * csrc/kernels_linsolve.hip and two products); the counterpart of t4a_gpu_mpo_fit_half.  dims = (chi_l, chi_r); L is
+ * [chi_l, W_l, chi_l], R is [chi_r, W_r, chi_r] with the outer operator bonds of sites `site`, `site + 1`; v and out hold
+ * chi_l d_site d_{site+1} chi_r doubles.  hl / hr (may be NULL) receive the half operators: HL (W M) x M with
+ * HL[(beta_l s1) + M w, (alpha_l t1)], HR (W N) x N with HR[w + W (t2 alpha_r), (s2 beta_r)], M = chi_l d_site, N = d_{site+1} chi_r. */
+t4a_gpu_status t4a_gpu_projected_operator_apply_env(const double* L, const double* R, const size_t* dims, const t4a_gpu_mpo* op, size_t site,
+                                                    const double* v, double* out, double* hl, double* hr);
+/* Test hooks.  _orth: one two-pass orthogonalisation step of GMRES as the solver launches it: w (len, in / out) against the nb columns
+ * of basis (len x nb), then normalised; h_out receives 2 nb doubles, the coefficients of pass 1 and of pass 2 (the column of H is
+ * their sum), norm_out the norm of w before the normalisation.
+ * _gmres_dense: the solver the sweeps run on (a0 + a1 H) x = b for a dense n x n matrix H (column-major) applied on the device. */
+t4a_gpu_status t4a_gpu_linsolve_orth(const double* basis, size_t len, size_t nb, double* w_inout, double* h_out, double* norm_out);
+t4a_gpu_status t4a_gpu_linsolve_gmres_dense(const double* H, size_t n, const double* b, const double* x0, double a0, double a1, double tol,
+                                            int32_t mode, size_t restart_dim, size_t max_restarts, double* x, size_t* iterations,
+                                            double* residual, int32_t* converged);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -19,6 +19,7 @@
 #include "contraction.hpp"
 #include "quanticstransform.hpp"
 #include "tt_canonical.hpp"
+#include "linsolve.hpp"
 
 struct t4a_gpu_tci2 {
     t4a::Tci2 impl;
@@ -71,6 +72,10 @@ struct t4a_gpu_qt_op {
 
 struct t4a_gpu_contraction {
     std::unique_ptr<t4a::MpoContraction> impl;
+};
+
+struct t4a_gpu_projected_operator {
+    std::unique_ptr<t4a::ProjectedOperator> impl;
 };
 
 namespace t4a {
@@ -4092,6 +4097,249 @@ t4a_gpu_status t4a_gpu_qt_difference_kernel(const t4a_gpu_tt* f, int32_t bc, t4a
         T4A_REQUIRE_PTR(out);
         *out = nullptr;
         *out = new t4a_gpu_mpo{qt_difference_kernel(const_cast<t4a_gpu_tt*>(f)->impl, (BoundaryCondition)bc)};
+    });
+}
+
+// ---- square_linsolve: (a0 + a1 A) x = b by two-site sweeps with a local GMRES (linsolve.hpp) ----
+t4a_gpu_status t4a_gpu_linsolve_options_default(t4a_gpu_linsolve_options* out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(out);
+        const LinsolveOptions d;
+        *out = t4a_gpu_linsolve_options{};
+        out->nfullsweeps = d.nfullsweeps;
+        out->has_max_bond_dim = d.has_max_bond_dim;
+        out->max_bond_dim = d.max_bond_dim;
+        out->has_svd_policy = d.has_svd_policy;
+        out->svd_policy = t4a_gpu_svd_policy{d.svd_policy.threshold, d.svd_policy.scale, d.svd_policy.measure, d.svd_policy.rule};
+        out->gmres_tol = d.gmres_tol;
+        out->gmres_tolerance_mode = (int32_t)d.gmres_tolerance_mode;
+        out->gmres_max_restarts = d.gmres_max_restarts;
+        out->gmres_restart_dim = d.gmres_restart_dim;
+        out->a0 = d.a0;
+        out->a1 = d.a1;
+        out->has_convergence_tol = d.has_convergence_tol;
+        out->convergence_tol = d.convergence_tol;
+        out->check_residual = d.check_residual;
+    });
+}
+
+extern "C++" {
+static LinsolveOptions convert_linsolve_options(const t4a_gpu_linsolve_options* p)
+{
+    LinsolveOptions o;
+    o.nfullsweeps = p->nfullsweeps;
+    o.has_max_bond_dim = p->has_max_bond_dim != 0;
+    o.max_bond_dim = p->max_bond_dim;
+    o.has_svd_policy = p->has_svd_policy != 0;
+    if (o.has_svd_policy) o.svd_policy = SvdPolicy{p->svd_policy.threshold, p->svd_policy.scale, p->svd_policy.measure, p->svd_policy.rule};
+    o.gmres_tol = p->gmres_tol;
+    if (p->gmres_tolerance_mode != 0 && p->gmres_tolerance_mode != 1) throw Error(T4A_GPU_INVALID_ARGUMENT, "unknown gmres_tolerance_mode");
+    o.gmres_tolerance_mode = (GmresToleranceMode)p->gmres_tolerance_mode;
+    o.gmres_max_restarts = p->gmres_max_restarts;
+    o.gmres_restart_dim = p->gmres_restart_dim;
+    o.a0 = p->a0;
+    o.a1 = p->a1;
+    o.has_convergence_tol = p->has_convergence_tol != 0;
+    o.convergence_tol = p->convergence_tol;
+    o.check_residual = p->check_residual != 0;
+    o.validate();
+    return o;
+}
+static std::vector<std::array<size_t, 3>> dims3_list(const size_t* d, size_t n)
+{
+    std::vector<std::array<size_t, 3>> v(n);
+    for (size_t i = 0; i < n; ++i) v[i] = {d[3 * i], d[3 * i + 1], d[3 * i + 2]};
+    return v;
+}
+}
+
+t4a_gpu_status t4a_gpu_linsolve_check_shapes(const size_t* op_dims4, size_t n_op, const size_t* rhs_dims3, size_t n_rhs,
+                                             const size_t* state_dims3, size_t n_state, size_t center, size_t gmres_restart_dim)
+{
+    return guarded([&] {
+        if (n_op) T4A_REQUIRE_PTR(op_dims4);
+        if (n_rhs) T4A_REQUIRE_PTR(rhs_dims3);
+        if (n_state) T4A_REQUIRE_PTR(state_dims3);
+        std::vector<std::array<size_t, 4>> op(n_op);
+        for (size_t i = 0; i < n_op; ++i) op[i] = {op_dims4[4 * i], op_dims4[4 * i + 1], op_dims4[4 * i + 2], op_dims4[4 * i + 3]};
+        const auto rhs = dims3_list(rhs_dims3, n_rhs);
+        linsolve_validate_shapes(op, rhs_dims3 ? &rhs : nullptr, dims3_list(state_dims3, n_state), center, gmres_restart_dim);
+    });
+}
+
+t4a_gpu_status t4a_gpu_square_linsolve(const t4a_gpu_mpo* op, const t4a_gpu_tt* rhs, const t4a_gpu_tt* init, size_t center,
+                                       const t4a_gpu_linsolve_options* options, t4a_gpu_tt** solution, size_t* sweeps,
+                                       int32_t* has_residual, double* residual, int32_t* converged, t4a_gpu_linsolve_stats* stats)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(solution);
+        *solution = nullptr;
+        T4A_REQUIRE_PTR(options);
+        const LinsolveOptions o = convert_linsolve_options(options); // the options are checked on the host before an operand is looked at
+        T4A_REQUIRE_PTR(op);
+        T4A_REQUIRE_PTR(rhs);
+        T4A_REQUIRE_PTR(init);
+        T4A_REQUIRE_PTR(sweeps);
+        T4A_REQUIRE_PTR(has_residual);
+        T4A_REQUIRE_PTR(residual);
+        T4A_REQUIRE_PTR(converged);
+        LinsolveResult r = square_linsolve(*op->impl, const_cast<t4a_gpu_tt*>(rhs)->impl, const_cast<t4a_gpu_tt*>(init)->impl, center, o);
+        *solution = new t4a_gpu_tt(r.solution->cores, r.solution->eng.stream());
+        *sweeps = r.sweeps;
+        *has_residual = r.has_residual;
+        *residual = r.residual;
+        *converged = r.converged;
+        if (stats) *stats = t4a_gpu_linsolve_stats{r.stats.local_solves, r.stats.arnoldi_steps, r.stats.apply_calls};
+    });
+}
+
+t4a_gpu_status t4a_gpu_relative_linear_system_residual(const t4a_gpu_mpo* op, const t4a_gpu_tt* solution, const t4a_gpu_tt* rhs, double a0,
+                                                       double a1, double* out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(op);
+        T4A_REQUIRE_PTR(solution);
+        T4A_REQUIRE_PTR(rhs);
+        T4A_REQUIRE_PTR(out);
+        *out = relative_linear_system_residual(*op->impl, const_cast<t4a_gpu_tt*>(solution)->impl, const_cast<t4a_gpu_tt*>(rhs)->impl, a0, a1);
+    });
+}
+
+t4a_gpu_status t4a_gpu_projected_operator_new(const t4a_gpu_mpo* op, const t4a_gpu_tt* state, t4a_gpu_projected_operator** out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(out);
+        *out = nullptr;
+        T4A_REQUIRE_PTR(op);
+        T4A_REQUIRE_PTR(state);
+        *out = new t4a_gpu_projected_operator{std::make_unique<ProjectedOperator>(*op->impl, const_cast<t4a_gpu_tt*>(state)->impl, nullptr)};
+    });
+}
+
+void t4a_gpu_projected_operator_release(t4a_gpu_projected_operator* h) { delete h; }
+
+t4a_gpu_status t4a_gpu_projected_operator_local_dims(const t4a_gpu_projected_operator* h, size_t site, size_t* dims4)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(h);
+        T4A_REQUIRE_PTR(dims4);
+        const auto d = h->impl->local_dims(site);
+        std::copy(d.begin(), d.end(), dims4);
+    });
+}
+
+t4a_gpu_status t4a_gpu_projected_operator_apply(t4a_gpu_projected_operator* h, size_t site, const double* v, double* out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(h);
+        T4A_REQUIRE_PTR(v);
+        T4A_REQUIRE_PTR(out);
+        const std::vector<double> y = h->impl->apply(site, v);
+        std::memcpy(out, y.data(), y.size() * sizeof(double));
+    });
+}
+
+t4a_gpu_status t4a_gpu_projected_operator_environment(t4a_gpu_projected_operator* h, int32_t side, size_t bond, size_t* dims3, double* out)
+{
+    return guarded([&] {
+        if (side != 0 && side != 1) throw Error(T4A_GPU_INVALID_ARGUMENT, "projected operator: side must be 0 (left) or 1 (right)");
+        T4A_REQUIRE_PTR(h);
+        T4A_REQUIRE_PTR(dims3);
+        const std::vector<double> e = h->impl->environment(side, bond, dims3);
+        if (out) std::memcpy(out, e.data(), e.size() * sizeof(double));
+    });
+}
+
+t4a_gpu_status t4a_gpu_projected_operator_invalidate(t4a_gpu_projected_operator* h, size_t site)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(h);
+        h->impl->invalidate(site);
+    });
+}
+
+t4a_gpu_status t4a_gpu_projected_operator_set_site_tensors(t4a_gpu_projected_operator* h, size_t site, const size_t* dims3_a, const double* t_a,
+                                                           const size_t* dims3_b, const double* t_b)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(h);
+        T4A_REQUIRE_PTR(dims3_a);
+        T4A_REQUIRE_PTR(t_a);
+        T4A_REQUIRE_PTR(dims3_b);
+        T4A_REQUIRE_PTR(t_b);
+        h->impl->set_site_tensors(site, dims3_a, t_a, dims3_b, t_b);
+    });
+}
+
+t4a_gpu_status t4a_gpu_projected_operator_time_step(t4a_gpu_projected_operator* h, size_t site, size_t nb, size_t reps, double* ms)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(h);
+        T4A_REQUIRE_PTR(ms);
+        h->impl->time_step(site, nb, reps, ms);
+    });
+}
+
+t4a_gpu_status t4a_gpu_projected_operator_apply_env(const double* L, const double* R, const size_t* dims, const t4a_gpu_mpo* op, size_t site,
+                                                    const double* v, double* out, double* hl, double* hr)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(dims);
+        if (dims[0] == 0 || dims[1] == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "apply_env: an environment has a zero dimension");
+        T4A_REQUIRE_PTR(L);
+        T4A_REQUIRE_PTR(R);
+        T4A_REQUIRE_PTR(op);
+        T4A_REQUIRE_PTR(v);
+        T4A_REQUIRE_PTR(out);
+        std::vector<double> vhl, vhr;
+        const std::vector<double> y = projected_apply_env(L, R, dims[0], dims[1], *op->impl, site, v, hl ? &vhl : nullptr, hr ? &vhr : nullptr);
+        std::memcpy(out, y.data(), y.size() * sizeof(double));
+        if (hl) std::memcpy(hl, vhl.data(), vhl.size() * sizeof(double));
+        if (hr) std::memcpy(hr, vhr.data(), vhr.size() * sizeof(double));
+    });
+}
+
+t4a_gpu_status t4a_gpu_linsolve_orth(const double* basis, size_t len, size_t nb, double* w_inout, double* h_out, double* norm_out)
+{
+    return guarded([&] {
+        if (len == 0 || nb == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "linsolve_orth: len and nb must be positive");
+        if (nb > LINSOLVE_RESTART_DIM_MAX + 1 || (unsigned long long)len * nb > (unsigned long long)INT_MAX)
+            throw Error(T4A_GPU_INVALID_ARGUMENT, "linsolve_orth: the basis holds more than INT_MAX elements");
+        T4A_REQUIRE_PTR(basis);
+        T4A_REQUIRE_PTR(w_inout);
+        T4A_REQUIRE_PTR(h_out);
+        T4A_REQUIRE_PTR(norm_out);
+        require_device();
+        linsolve_orth(basis, len, nb, w_inout, h_out, norm_out);
+    });
+}
+
+t4a_gpu_status t4a_gpu_linsolve_gmres_dense(const double* H, size_t n, const double* b, const double* x0, double a0, double a1, double tol,
+                                            int32_t mode, size_t restart_dim, size_t max_restarts, double* x, size_t* iterations,
+                                            double* residual, int32_t* converged)
+{
+    return guarded([&] {
+        if (mode != 0 && mode != 1) throw Error(T4A_GPU_INVALID_ARGUMENT, "unknown gmres_tolerance_mode");
+        LinsolveOptions o;
+        o.gmres_tol = tol;
+        o.gmres_restart_dim = restart_dim;
+        o.gmres_max_restarts = max_restarts;
+        o.validate();
+        if (n == 0 || n > 46340 || (unsigned long long)n * (restart_dim + 1) > (unsigned long long)INT_MAX)
+            throw Error(T4A_GPU_INVALID_ARGUMENT, "gmres_dense: n must be positive and the matrix and the basis must hold at most INT_MAX elements");
+        T4A_REQUIRE_PTR(H);
+        T4A_REQUIRE_PTR(b);
+        T4A_REQUIRE_PTR(x0);
+        T4A_REQUIRE_PTR(x);
+        T4A_REQUIRE_PTR(iterations);
+        T4A_REQUIRE_PTR(residual);
+        T4A_REQUIRE_PTR(converged);
+        require_device();
+        const GmresResult r = gmres_dense(H, n, b, x0, a0, a1, tol, (GmresToleranceMode)mode, restart_dim, max_restarts, x);
+        *iterations = r.iterations;
+        *residual = r.residual;
+        *converged = r.converged;
     });
 }
 

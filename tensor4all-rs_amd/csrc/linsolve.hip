@@ -1,0 +1,911 @@
+// linsolve.hip — the two-site linear solver (a0 + a1 A) x = b on the device (see linsolve.hpp).  Shape bookkeeping, the Givens
+// rotations and the small triangular solve of GMRES are host work; every other floating-point operation runs in gfx950 kernels:
+// the half-operator builders and the Gram–Schmidt launches (kernels_linsolve.hip), the f64-MFMA GEMM (kernels_dense.hip), the
+// Householder QR and the Jacobi SVD behind tensor_svd (kernels_linalg.hip), the naive MPO product of the residual (kernels_mpo.hip).
+#include "linsolve.hpp"
+
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <string>
+
+namespace t4a {
+
+namespace {
+
+DevCore new_core(size_t l, size_t s, size_t r)
+{
+    DevCore c;
+    c.l = l;
+    c.s = s;
+    c.r = r;
+    c.buf.reserve(std::max<size_t>(c.size(), 1));
+    return c;
+}
+
+std::vector<DevCore> copy_cores(const std::vector<DevCore>& src, hipStream_t st)
+{
+    std::vector<DevCore> out;
+    for (const DevCore& c : src) {
+        DevCore cp = new_core(c.l, c.s, c.r);
+        if (c.size()) T4A_HIP(hipMemcpyAsync(cp.buf.get(), c.buf.get(), sizeof(double) * c.size(), hipMemcpyDeviceToDevice, st));
+        out.push_back(std::move(cp));
+    }
+    return out;
+}
+
+bool above_int_max(std::initializer_list<size_t> factors)
+{
+    const unsigned long long lim = INT_MAX;
+    unsigned long long n = 1;
+    for (size_t x : factors) {
+        if (x == 0) return false;
+        if (x > lim || n * x > lim) return true;
+        n *= x;
+    }
+    return false;
+}
+
+// the buffers of the bond step (i, i + 1): HL, HR, T and the Krylov basis
+void check_step_dims(size_t i, size_t chi_l, size_t d1, size_t d2, size_t chi_r, size_t W, size_t restart_dim)
+{
+    const size_t M = chi_l * d1, N = d2 * chi_r;
+    if (above_int_max({W, M, M}) || above_int_max({W, N, N}) || above_int_max({W, M, N}) || above_int_max({restart_dim + 1, M, N}))
+        throw Error(T4A_GPU_INVALID_ARGUMENT, "square_linsolve: a work buffer of the bond step (" + std::to_string(i) + ", " + std::to_string(i + 1) +
+                                                  ") holds more than INT_MAX elements");
+}
+
+// a buffer that may still be read on the stream is not handed back to the pool before the stream has drained
+void grow(Engine& e, DevBuf<double>& b, size_t n)
+{
+    n = std::max<size_t>(n, 1);
+    if (n <= b.cap) return;
+    e.sync();
+    b.reserve(n);
+}
+
+// QR sweeps with the thin Householder QR.  sites > stop from the right: the site becomes Q^T, R^T goes into its left neighbour
+// (np_right_canonicalize of tests/fit_np.py); sites < from the left: the site becomes Q, R goes into its right neighbour.
+struct QrSweeper {
+    Engine& eng;
+    hipStream_t st;
+    DevBuf<double> m1, q, rr;
+    explicit QrSweeper(Engine& e) : eng(e), st(e.stream()) {}
+
+    void right_step(std::vector<DevCore>& cores, size_t i)
+    {
+        DevCore& c = cores[i];
+        DevCore& p = cores[i - 1];
+        const int L = (int)c.l, rest = (int)(c.s * c.r);
+        const int k = std::min(L, rest);
+        grow(eng, m1, (size_t)rest * L);
+        grow(eng, q, (size_t)rest * k);
+        grow(eng, rr, (size_t)k * L);
+        transpose_launch(c.buf.get(), L, rest, L, m1.get(), rest, st);
+        eng.qr(m1.get(), rest, L, q.get(), rr.get());
+        DevCore nc = new_core(k, c.s, c.r);
+        transpose_launch(q.get(), rest, k, rest, nc.buf.get(), k, st);
+        DevCore np = new_core(p.l, p.s, k);
+        const int pm = (int)(p.l * p.s);
+        GemmDesc g = gemm_desc(pm, k, L, p.buf.get(), pm, rr.get(), k, np.buf.get(), pm);
+        g.transB = 1; // prev (l s x L) * R^T (L x k)
+        gemm_launch(g, st);
+        T4A_HIP(hipGetLastError());
+        eng.sync(); // the old cores are released below
+        c = std::move(nc);
+        p = std::move(np);
+    }
+    void left_step(std::vector<DevCore>& cores, size_t i)
+    {
+        DevCore& c = cores[i];
+        DevCore& nx = cores[i + 1];
+        const int rows = (int)(c.l * c.s), R = (int)c.r;
+        const int k = std::min(rows, R);
+        grow(eng, rr, (size_t)k * R);
+        DevCore nc = new_core(c.l, c.s, k);
+        eng.qr(c.buf.get(), rows, R, nc.buf.get(), rr.get());
+        DevCore nn = new_core(k, nx.s, nx.r);
+        const int rest = (int)(nx.s * nx.r);
+        gemm_launch(gemm_desc(k, rest, R, rr.get(), k, nx.buf.get(), R, nn.buf.get(), k), st); // R (k x R) * next (R x s r)
+        T4A_HIP(hipGetLastError());
+        eng.sync();
+        c = std::move(nc);
+        nx = std::move(nn);
+    }
+    void canonicalize(std::vector<DevCore>& cores, size_t center)
+    {
+        for (size_t i = 0; i < center; ++i) left_step(cores, i);
+        for (size_t i = cores.size() - 1; i > center; --i) right_step(cores, i);
+    }
+};
+
+double host_norm(Engine& eng, const DevCore& c)
+{
+    std::vector<double> h(c.size());
+    if (!h.empty()) T4A_HIP(hipMemcpyAsync(h.data(), c.buf.get(), sizeof(double) * h.size(), hipMemcpyDeviceToHost, eng.stream()));
+    eng.sync();
+    double s = 0.0;
+    for (double v : h) s = s + v * v;
+    return std::sqrt(s);
+}
+
+// |t| from the QR right-canonical form of a copy of its cores
+double canonical_norm(TensorTrain& t)
+{
+    if (t.len() == 0) return 0.0;
+    std::vector<DevCore> cores = copy_cores(t.cores, t.eng.stream());
+    QrSweeper sw(t.eng);
+    sw.canonicalize(cores, 0);
+    return host_norm(t.eng, cores[0]);
+}
+
+std::vector<std::array<size_t, 3>> dims3_of(const std::vector<DevCore>& cores)
+{
+    std::vector<std::array<size_t, 3>> d;
+    for (const DevCore& c : cores) d.push_back({c.l, c.s, c.r});
+    return d;
+}
+
+} // namespace
+
+// ------------------------------------------------------------------------------------------------ options and shapes
+void LinsolveOptions::validate() const
+{
+    if (gmres_restart_dim == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "LinsolveOptions::gmres_restart_dim must be greater than zero");
+    if (gmres_restart_dim > LINSOLVE_RESTART_DIM_MAX)
+        throw Error(T4A_GPU_INVALID_ARGUMENT, "LinsolveOptions::gmres_restart_dim above " + std::to_string(LINSOLVE_RESTART_DIM_MAX) + " is not supported");
+    if (gmres_max_restarts == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "LinsolveOptions::gmres_max_restarts must be greater than zero");
+    if (!std::isfinite(gmres_tol) || gmres_tol < 0.0) throw Error(T4A_GPU_INVALID_ARGUMENT, "LinsolveOptions::gmres_tol must be finite and not negative");
+    if (has_convergence_tol && (!std::isfinite(convergence_tol) || convergence_tol < 0.0))
+        throw Error(T4A_GPU_INVALID_ARGUMENT, "LinsolveOptions::convergence_tol must be finite and not negative");
+    if (!std::isfinite(a0) || !std::isfinite(a1)) throw Error(T4A_GPU_INVALID_ARGUMENT, "LinsolveOptions::a0 and a1 must be finite");
+    if (has_max_bond_dim && max_bond_dim == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "LinsolveOptions::max_bond_dim must be positive when specified");
+    if (has_svd_policy) {
+        if (!std::isfinite(svd_policy.threshold) || svd_policy.threshold < 0.0)
+            throw Error(T4A_GPU_INVALID_ARGUMENT, "Invalid SVD truncation threshold: threshold must be finite and non-negative");
+        if (svd_policy.scale < 0 || svd_policy.scale > 1 || svd_policy.measure < 0 || svd_policy.measure > 1 || svd_policy.rule < 0 || svd_policy.rule > 1)
+            throw Error(T4A_GPU_INVALID_ARGUMENT, "LinsolveOptions::svd_policy: unknown scale, measure or rule");
+    }
+}
+
+void linsolve_validate_shapes(const std::vector<std::array<size_t, 4>>& op, const std::vector<std::array<size_t, 3>>* rhs,
+                              const std::vector<std::array<size_t, 3>>& state, size_t center, size_t restart_dim)
+{
+    const size_t n = state.size();
+    if (op.size() != n || (rhs && rhs->size() != n))
+        throw Error(T4A_GPU_INVALID_ARGUMENT, "square_linsolve: lengths differ: the operator has " + std::to_string(op.size()) + " sites, the state " +
+                                                  std::to_string(n) + (rhs ? ", the rhs " + std::to_string(rhs->size()) : std::string()));
+    if (n < 2) throw Error(T4A_GPU_INVALID_ARGUMENT, "square_linsolve: fewer than two sites: the one-site local solve is not implemented");
+    for (size_t i = 0; i < n; ++i) {
+        const size_t d = state[i][1];
+        if (op[i][1] != op[i][2])
+            throw Error(T4A_GPU_INVALID_ARGUMENT, "square_linsolve: site " + std::to_string(i) + " of the operator is not square: (" +
+                                                      std::to_string(op[i][1]) + ", " + std::to_string(op[i][2]) + ")");
+        if (op[i][1] != d)
+            throw Error(T4A_GPU_INVALID_ARGUMENT, "square_linsolve: site " + std::to_string(i) + " of the operator has dimension " +
+                                                      std::to_string(op[i][1]) + ", the state " + std::to_string(d));
+        if (rhs && (*rhs)[i][1] != d)
+            throw Error(T4A_GPU_INVALID_ARGUMENT, "square_linsolve: site " + std::to_string(i) + " of the rhs has dimension " +
+                                                      std::to_string((*rhs)[i][1]) + ", the state " + std::to_string(d));
+    }
+    if (center >= n) throw Error(T4A_GPU_INVALID_ARGUMENT, "square_linsolve: center " + std::to_string(center) + " is out of range (" + std::to_string(n) + " sites)");
+    for (size_t i = 0; i + 1 < n; ++i) check_step_dims(i, state[i][0], state[i][1], state[i + 1][1], state[i + 1][2], op[i][3], restart_dim);
+}
+
+// ------------------------------------------------------------------------------------------------ GMRES
+void Gmres::reserve(size_t len, size_t restart_dim)
+{
+    const size_t m = restart_dim;
+    grow(eng_, basis_, len * (m + 1));
+    grow(eng_, ax_, len);
+    grow(eng_, part_, (m + 1) * GS_MAX_WORKGROUPS);
+    grow(eng_, npart_, GS_MAX_WORKGROUPS);
+    grow(eng_, hcol_, m + 3); // the column of H (m + 2) and one norm
+    grow(eng_, coef_, m + 1);
+}
+
+double Gmres::norm(const double* d_w, size_t len)
+{
+    hipStream_t st = eng_.stream();
+    double v = 0.0;
+    gs_norm2_launch(d_w, len, npart_.get(), st);
+    gs_normalize_launch(d_w, len, npart_.get(), nullptr, hcol_.get(), st);
+    T4A_HIP(hipMemcpyAsync(&v, hcol_.get(), sizeof(double), hipMemcpyDeviceToHost, st));
+    eng_.sync();
+    return v;
+}
+
+void Gmres::orth(const double* d_V, size_t ld, int nb, double* d_w, size_t len, double* d_hcol, double* d_hpass)
+{
+    hipStream_t st = eng_.stream();
+    const int G = gs_workgroups(len);
+    gs_dots_launch(d_V, ld, nb, d_w, len, part_.get(), st);
+    gs_update_launch(d_V, ld, nb, d_w, len, part_.get(), G, d_hcol, true, d_hpass, npart_.get(), st);
+    gs_dots_launch(d_V, ld, nb, d_w, len, part_.get(), st);
+    gs_update_launch(d_V, ld, nb, d_w, len, part_.get(), G, d_hcol, false, d_hpass ? d_hpass + nb : nullptr, npart_.get(), st);
+    gs_normalize_launch(d_w, len, npart_.get(), d_w, d_hcol + nb, st);
+}
+
+namespace {
+// compute_givens_rotation / apply_givens_rotation / solve_upper_triangular (krylov.rs:2708-2772) for real scalars
+void givens(double a, double b, double& c, double& s)
+{
+    const double aa = std::fabs(a), ba = std::fabs(b);
+    const double r = std::sqrt(aa * aa + ba * ba);
+    if (r < 1e-15) {
+        c = 1.0;
+        s = 0.0;
+    } else if (aa < 1e-15) {
+        c = 0.0;
+        s = b / r;
+    } else {
+        const double phase = a / aa;
+        c = aa / r;
+        s = phase * b / r;
+    }
+}
+void rotate(double c, double s, double& x, double& y)
+{
+    const double nx = c * x + s * y, ny = -(s * x) + c * y;
+    x = nx;
+    y = ny;
+}
+std::vector<double> solve_upper(const std::vector<std::vector<double>>& h, const std::vector<double>& g, size_t n)
+{
+    std::vector<double> y(n, 0.0);
+    for (size_t i = n; i-- > 0;) {
+        double sum = g[i];
+        for (size_t j = i + 1; j < n; ++j) sum = sum - h[j][i] * y[j];
+        if (std::fabs(h[i][i]) < 1e-15) throw Error(T4A_GPU_INVALID_ARGUMENT, "Near-singular upper triangular matrix in GMRES");
+        y[i] = sum / h[i][i];
+    }
+    return y;
+}
+} // namespace
+
+GmresResult Gmres::solve(const GmresApply& apply, size_t len, const double* d_b, double* d_x, double a0, double a1, double tol, GmresToleranceMode mode,
+                         size_t restart_dim, size_t max_restarts)
+{
+    GmresResult res;
+    hipStream_t st = eng_.stream();
+    const size_t m = restart_dim;
+    reserve(len, m);
+    const bool relative = mode == GmresToleranceMode::Relative;
+    const double b_norm = norm(d_b, len);
+    auto value = [&](double r) { return relative ? r / b_norm : r; };
+    auto is_converged = [&](double r) { return value(r) < tol; };
+    if (b_norm < 1e-15) {
+        res.converged = true;
+        return res;
+    }
+    if (a0 == 0.0 && a1 == 0.0) throw Error(T4A_GPU_INVALID_ARGUMENT, "gmres: a0 and a1 are both zero");
+    if (a1 == 0.0) {
+        linsolve_scale_launch(d_b, 1.0 / a0, d_x, len, st);
+        T4A_HIP(hipGetLastError());
+        eng_.sync();
+        res.converged = true;
+        return res;
+    }
+    double* V = basis_.get();
+    double* d_hcol = hcol_.get();
+    double* d_norm = hcol_.get() + m + 2;
+    // |b - (a0 x + a1 H x)|; the residual is left in column 0 of the basis, normalised
+    auto residual_norm = [&]() {
+        double v = 0.0;
+        apply(d_x, ax_.get());
+        ++res.apply_calls;
+        linsolve_residual_launch(d_b, d_x, ax_.get(), a0, a1, V, len, npart_.get(), st);
+        gs_normalize_launch(V, len, npart_.get(), V, d_norm, st);
+        T4A_HIP(hipMemcpyAsync(&v, d_norm, sizeof(double), hipMemcpyDeviceToHost, st));
+        eng_.sync();
+        return v;
+    };
+    std::vector<double> neg;
+    auto update_solution = [&](const std::vector<double>& y) { // x += sum_i y_i v_i
+        neg.resize(y.size());
+        for (size_t i = 0; i < y.size(); ++i) neg[i] = -y[i];
+        T4A_HIP(hipMemcpyAsync(coef_.get(), neg.data(), sizeof(double) * neg.size(), hipMemcpyHostToDevice, st));
+        gs_update_launch(V, len, (int)y.size(), d_x, len, coef_.get(), 1, nullptr, true, nullptr, npart_.get(), st);
+        T4A_HIP(hipGetLastError());
+        eng_.sync();
+    };
+    std::vector<double> ha(m + 2);
+    for (size_t restart = 0; restart < max_restarts; ++restart) {
+        const double r_norm = residual_norm();
+        if (is_converged(r_norm)) {
+            res.residual = value(r_norm);
+            res.converged = true;
+            return res;
+        }
+        std::vector<std::vector<double>> hm;
+        std::vector<double> cs, sn, g{r_norm};
+        bool solution_already_updated = false;
+        for (size_t j = 0; j < m; ++j) {
+            ++res.iterations;
+            double* w = V + len * (j + 1);
+            apply(V + len * j, w);
+            ++res.apply_calls;
+            orth(V, len, (int)(j + 1), w, len, d_hcol, nullptr);
+            T4A_HIP(hipMemcpyAsync(ha.data(), d_hcol, sizeof(double) * (j + 2), hipMemcpyDeviceToHost, st));
+            eng_.sync();
+            const double h_next = ha[j + 1];
+            std::vector<double> hc(j + 2);
+            for (size_t i = 0; i < j; ++i) hc[i] = a1 * ha[i];
+            hc[j] = a0 + a1 * ha[j];
+            hc[j + 1] = a1 * ha[j + 1];
+            for (size_t i = 0; i < j; ++i) rotate(cs[i], sn[i], hc[i], hc[i + 1]);
+            double c, s;
+            givens(hc[j], hc[j + 1], c, s);
+            cs.push_back(c);
+            sn.push_back(s);
+            double dummy = hc[j + 1];
+            rotate(c, s, hc[j], dummy);
+            hc[j + 1] = 0.0;
+            double gj = g[j], gn = 0.0;
+            rotate(c, s, gj, gn);
+            g[j] = gj;
+            g.push_back(gn);
+            const double res_norm = std::fabs(gn);
+            hm.push_back(std::move(hc));
+            if (is_converged(res_norm)) {
+                update_solution(solve_upper(hm, g, j + 1));
+                // check_true_residual (local_gmres_options sets it)
+                const double true_res = residual_norm();
+                if (is_converged(true_res)) {
+                    res.residual = value(true_res);
+                    res.converged = true;
+                    return res;
+                }
+                solution_already_updated = true;
+                break;
+            }
+            if (!(h_next > 1e-14)) { // lucky breakdown: v_{j+1} is discarded
+                update_solution(solve_upper(hm, g, j + 1));
+                const double final_res = residual_norm();
+                res.residual = value(final_res);
+                res.converged = is_converged(final_res);
+                return res;
+            }
+        }
+        if (!solution_already_updated) update_solution(solve_upper(hm, g, hm.size()));
+    }
+    const double final_res = residual_norm();
+    res.residual = value(final_res);
+    res.converged = is_converged(final_res);
+    return res;
+}
+
+// ------------------------------------------------------------------------------------------------ the projected operator
+ProjectedOperator::ProjectedOperator(Mpo& op, TensorTrain& state, TensorTrain* rhs)
+{
+    std::vector<std::array<size_t, 3>> rd;
+    if (rhs) rd = dims3_of(rhs->cores);
+    linsolve_validate_shapes(op.dims4(), rhs ? &rd : nullptr, dims3_of(state.cores), 0, 1);
+    op_ = std::make_unique<Mpo>(op.tt.cores, op.tt.eng.stream(), op.sd);
+    Engine& e = engine();
+    state.eng.sync();
+    x = copy_cores(state.cores, e.stream());
+    if (rhs) {
+        rhs->eng.sync();
+        b = copy_cores(rhs->cores, e.stream());
+    }
+    const size_t n = x.size();
+    envL_.resize(n + 1);
+    envR_.resize(n + 1);
+    envLb_.resize(n + 1);
+    envRb_.resize(n + 1);
+    okL_.assign(n + 1, 0);
+    okR_.assign(n + 1, 0);
+    for (DevBuf<double>* one : {&envL_[0], &envR_[n], &envLb_[0], &envRb_[n]}) {
+        one->reserve(1);
+        fill_launch(one->get(), 1, 1.0, e.stream());
+    }
+    okL_[0] = okR_[n] = 1;
+    T4A_HIP(hipGetLastError());
+    e.sync();
+}
+
+std::array<size_t, 4> ProjectedOperator::local_dims(size_t site) const
+{
+    if (site + 1 >= x.size()) throw Error(T4A_GPU_INVALID_ARGUMENT, "projected operator: the region (" + std::to_string(site) + ", " + std::to_string(site + 1) + ") is out of range");
+    return {x[site].l, x[site].s, x[site + 1].s, x[site + 1].r};
+}
+
+void ProjectedOperator::check_step(size_t site, size_t restart_dim) const
+{
+    check_step_dims(site, x[site].l, x[site].s, x[site + 1].s, x[site + 1].r, op_->tt.cores[site].r, restart_dim);
+}
+
+void ProjectedOperator::invalidate(size_t site)
+{
+    if (site >= x.size()) throw Error(T4A_GPU_INVALID_ARGUMENT, "projected operator: site " + std::to_string(site) + " is out of range");
+    for (size_t j = site + 1; j < okL_.size(); ++j) okL_[j] = 0;
+    for (size_t j = 0; j <= site; ++j) okR_[j] = 0;
+    prepared_ = (size_t)-1;
+}
+
+// L_{k+1} from L_k, A_k (as the HL in hl_) and x_k:  T1 = HL X_k, then L_{k+1}[:, w, :] = X_k^T T1_w for every w in one batched product
+void ProjectedOperator::update_left_from_prepared(size_t k)
+{
+    Engine& e = engine();
+    hipStream_t st = e.stream();
+    const DevCore& X = x[k];
+    const DevCore& A = op_->tt.cores[k];
+    const int chi = (int)X.l, d = (int)X.s, cn = (int)X.r, W = (int)A.r, M = chi * d;
+    grow(e, t1_, (size_t)W * M * cn);
+    grow(e, envL_[k + 1], (size_t)cn * W * cn);
+    gemm_launch(gemm_desc(W * M, cn, M, hl_.get(), W * M, X.buf.get(), M, t1_.get(), W * M), st);
+    GemmDesc g = gemm_desc(cn, cn, M, X.buf.get(), M, t1_.get(), W * M, envL_[k + 1].get(), cn * W);
+    g.transA = 1;
+    g.strideA = 0;
+    g.strideB = M;
+    g.strideC = cn;
+    g.batch = W;
+    gemm_launch(g, st);
+    if (!b.empty()) { // Lb_{k+1} = X_k^T (Lb_k B_k)
+        const DevCore& B = b[k];
+        const int bl = (int)B.l, br = (int)B.r;
+        grow(e, p1_, (size_t)M * br);
+        grow(e, envLb_[k + 1], (size_t)cn * br);
+        gemm_launch(gemm_desc(chi, d * br, bl, envLb_[k].get(), chi, B.buf.get(), bl, p1_.get(), chi), st);
+        GemmDesc h = gemm_desc(cn, br, M, X.buf.get(), M, p1_.get(), M, envLb_[k + 1].get(), cn);
+        h.transA = 1;
+        gemm_launch(h, st);
+    }
+    T4A_HIP(hipGetLastError());
+    okL_[k + 1] = 1;
+}
+
+// R_k from R_{k+1}, A_k (as the HR in hr_) and x_k:  T2 = X_k HR^T (chi x W N), then R_k[:, w, :] = T2_w X_k^T
+void ProjectedOperator::update_right_from_prepared(size_t site)
+{
+    const size_t k = site + 1;
+    Engine& e = engine();
+    hipStream_t st = e.stream();
+    const DevCore& X = x[k];
+    const DevCore& A = op_->tt.cores[k];
+    const int chi = (int)X.l, d = (int)X.s, cr = (int)X.r, W = (int)A.l, N = d * cr;
+    grow(e, t1_, (size_t)chi * W * N);
+    grow(e, envR_[k], (size_t)chi * W * chi);
+    GemmDesc g1 = gemm_desc(chi, W * N, N, X.buf.get(), chi, hr_.get(), W * N, t1_.get(), chi);
+    g1.transB = 1;
+    gemm_launch(g1, st);
+    GemmDesc g = gemm_desc(chi, chi, N, t1_.get(), chi * W, X.buf.get(), chi, envR_[k].get(), chi * W);
+    g.transB = 1;
+    g.strideA = chi;
+    g.strideB = 0;
+    g.strideC = chi;
+    g.batch = W;
+    gemm_launch(g, st);
+    if (!b.empty()) { // Rb_k = X_k (B_k Rb_{k+1}^T)^T
+        const DevCore& B = b[k];
+        const int bl = (int)B.l, br = (int)B.r;
+        grow(e, p2_, (size_t)bl * N);
+        grow(e, envRb_[k], (size_t)chi * bl);
+        GemmDesc h1 = gemm_desc(bl * d, cr, br, B.buf.get(), bl * d, envRb_[k + 1].get(), cr, p2_.get(), bl * d);
+        h1.transB = 1;
+        gemm_launch(h1, st);
+        GemmDesc h2 = gemm_desc(chi, bl, N, X.buf.get(), chi, p2_.get(), bl, envRb_[k].get(), chi);
+        h2.transB = 1;
+        gemm_launch(h2, st);
+    }
+    T4A_HIP(hipGetLastError());
+    okR_[k] = 1;
+}
+
+const double* ProjectedOperator::left_env(size_t i)
+{
+    size_t j = i;
+    while (!okL_[j]) --j; // okL_[0] always holds
+    Engine& e = engine();
+    for (size_t k = j; k < i; ++k) {
+        const DevCore& X = x[k];
+        const DevCore& A = op_->tt.cores[k];
+        if (above_int_max({A.r, X.l * X.s, X.l * X.s}) || above_int_max({A.r, X.l * X.s, X.r}))
+            throw Error(T4A_GPU_INVALID_ARGUMENT, "projected operator: the left environment of site " + std::to_string(k + 1) + " needs more than INT_MAX elements");
+        grow(e, hl_, A.r * X.l * X.s * X.l * X.s);
+        prepared_ = (size_t)-1;
+        linsolve_hl_launch(envL_[k].get(), A.buf.get(), hl_.get(), (int)X.l, (int)A.l, (int)X.s, (int)A.r, e.stream());
+        update_left_from_prepared(k);
+    }
+    return envL_[i].get();
+}
+
+const double* ProjectedOperator::right_env(size_t i)
+{
+    size_t j = i;
+    while (!okR_[j]) ++j; // okR_[n] always holds
+    Engine& e = engine();
+    for (size_t k = j; k-- > i;) {
+        const DevCore& X = x[k];
+        const DevCore& A = op_->tt.cores[k];
+        if (above_int_max({A.l, X.s * X.r, X.s * X.r}) || above_int_max({A.l, X.s * X.r, X.l}))
+            throw Error(T4A_GPU_INVALID_ARGUMENT, "projected operator: the right environment of site " + std::to_string(k) + " needs more than INT_MAX elements");
+        grow(e, hr_, A.l * X.s * X.r * X.s * X.r);
+        prepared_ = (size_t)-1;
+        linsolve_hr_launch(A.buf.get(), envR_[k + 1].get(), hr_.get(), (int)X.r, (int)A.l, (int)X.s, (int)A.r, e.stream());
+        update_right_from_prepared(k - 1);
+    }
+    return envR_[i].get();
+}
+
+const double* ProjectedOperator::left_rhs_env(size_t i)
+{
+    left_env(i);
+    return envLb_[i].get();
+}
+const double* ProjectedOperator::right_rhs_env(size_t i)
+{
+    right_env(i);
+    return envRb_[i].get();
+}
+
+void ProjectedOperator::prepare(size_t site)
+{
+    const auto ld = local_dims(site);
+    check_step(site, 0);
+    Engine& e = engine();
+    const double* L = left_env(site);
+    const double* R = right_env(site + 2);
+    const DevCore& A1 = op_->tt.cores[site];
+    const DevCore& A2 = op_->tt.cores[site + 1];
+    const size_t M = ld[0] * ld[1], N = ld[2] * ld[3], W = A1.r;
+    grow(e, hl_, W * M * M);
+    grow(e, hr_, W * N * N);
+    grow(e, t_, W * M * N);
+    linsolve_hl_launch(L, A1.buf.get(), hl_.get(), (int)ld[0], (int)A1.l, (int)ld[1], (int)W, e.stream());
+    linsolve_hr_launch(A2.buf.get(), R, hr_.get(), (int)ld[3], (int)W, (int)ld[2], (int)A2.r, e.stream());
+    T4A_HIP(hipGetLastError());
+    prepared_ = site;
+}
+
+void ProjectedOperator::product_left(const double* d_v) // T = HL V
+{
+    const auto ld = local_dims(prepared_);
+    const int M = (int)(ld[0] * ld[1]), N = (int)(ld[2] * ld[3]), W = (int)op_->tt.cores[prepared_].r;
+    gemm_launch(gemm_desc(W * M, N, M, hl_.get(), W * M, d_v, M, t_.get(), W * M), engine().stream());
+}
+
+void ProjectedOperator::product_right(double* d_out) // Y = T HR, T read as M x (W N)
+{
+    const auto ld = local_dims(prepared_);
+    const int M = (int)(ld[0] * ld[1]), N = (int)(ld[2] * ld[3]), W = (int)op_->tt.cores[prepared_].r;
+    gemm_launch(gemm_desc(M, N, W * N, t_.get(), M, hr_.get(), W * N, d_out, M), engine().stream());
+}
+
+void ProjectedOperator::apply_prepared(const double* d_v, double* d_out)
+{
+    product_left(d_v);
+    product_right(d_out);
+}
+
+void ProjectedOperator::time_step(size_t site, size_t nb, size_t reps, double ms[5])
+{
+    const auto ld = local_dims(site);
+    check_step(site, nb);
+    if (nb == 0 || nb > LINSOLVE_RESTART_DIM_MAX || reps == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "time_step: nb and reps must be positive");
+    const size_t len = ld[0] * ld[1] * ld[2] * ld[3];
+    Engine& e = engine();
+    hipStream_t st = e.stream();
+    prepare(site);
+    DevBuf<double> basis, part, npart, hcol;
+    basis.reserve(len * (nb + 1));
+    part.reserve(nb * GS_MAX_WORKGROUPS);
+    npart.reserve(GS_MAX_WORKGROUPS);
+    hcol.reserve(nb + 1);
+    fill_launch(basis.get(), len * (nb + 1), 1.0 / std::sqrt((double)len), st);
+    double* w = basis.get() + len * nb;
+    const int G = gs_workgroups(len);
+    EventTimer t;
+    t.init();
+    const std::function<void()> pieces[5] = {
+        [&] { product_left(basis.get()); },
+        [&] { product_right(w); },
+        [&] { gs_dots_launch(basis.get(), len, (int)nb, w, len, part.get(), st); },
+        [&] { gs_update_launch(basis.get(), len, (int)nb, w, len, part.get(), G, hcol.get(), true, nullptr, npart.get(), st); },
+        [&] { gs_normalize_launch(w, len, npart.get(), w, hcol.get() + nb, st); },
+    };
+    for (int k = 0; k < 5; ++k) {
+        pieces[k](); // warm-up
+        T4A_HIP(hipEventRecord(t.a, st));
+        for (size_t r = 0; r < reps; ++r) pieces[k]();
+        T4A_HIP(hipEventRecord(t.b, st));
+        T4A_HIP(hipEventSynchronize(t.b));
+        T4A_HIP(hipGetLastError());
+        float f = 0.0f;
+        T4A_HIP(hipEventElapsedTime(&f, t.a, t.b));
+        ms[k] = (double)f / (double)reps;
+    }
+    e.sync();
+}
+
+void ProjectedOperator::local_rhs(size_t site, double* d_out)
+{
+    const auto ld = local_dims(site);
+    Engine& e = engine();
+    hipStream_t st = e.stream();
+    const double* Lb = left_rhs_env(site);
+    const double* Rb = right_rhs_env(site + 2);
+    const DevCore& B1 = b[site];
+    const DevCore& B2 = b[site + 1];
+    const int chi_l = (int)ld[0], d1 = (int)ld[1], d2 = (int)ld[2], chi_r = (int)ld[3];
+    const int bl = (int)B1.l, bm = (int)B1.r, br = (int)B2.r, M = chi_l * d1, N = d2 * chi_r;
+    grow(e, p1_, (size_t)M * bm);
+    grow(e, p2_, (size_t)bm * N);
+    gemm_launch(gemm_desc(chi_l, d1 * bm, bl, Lb, chi_l, B1.buf.get(), bl, p1_.get(), chi_l), st); // (chi_l d1) x bm
+    GemmDesc g = gemm_desc(bm * d2, chi_r, br, B2.buf.get(), bm * d2, Rb, chi_r, p2_.get(), bm * d2); // bm x (d2 chi_r)
+    g.transB = 1;
+    gemm_launch(g, st);
+    gemm_launch(gemm_desc(M, N, bm, p1_.get(), M, p2_.get(), bm, d_out, M), st);
+    T4A_HIP(hipGetLastError());
+}
+
+std::vector<double> ProjectedOperator::apply(size_t site, const double* v)
+{
+    const auto ld = local_dims(site);
+    const size_t len = ld[0] * ld[1] * ld[2] * ld[3];
+    Engine& e = engine();
+    if (prepared_ != site) prepare(site);
+    DevBuf<double> d_v, d_y;
+    d_v.reserve(len);
+    d_y.reserve(len);
+    T4A_HIP(hipMemcpyAsync(d_v.get(), v, sizeof(double) * len, hipMemcpyHostToDevice, e.stream()));
+    apply_prepared(d_v.get(), d_y.get());
+    T4A_HIP(hipGetLastError());
+    std::vector<double> out(len);
+    T4A_HIP(hipMemcpyAsync(out.data(), d_y.get(), sizeof(double) * len, hipMemcpyDeviceToHost, e.stream()));
+    e.sync();
+    return out;
+}
+
+std::vector<double> ProjectedOperator::environment(int side, size_t bond, size_t dims[3])
+{
+    const size_t n = x.size();
+    if (bond > n) throw Error(T4A_GPU_INVALID_ARGUMENT, "projected operator: bond " + std::to_string(bond) + " is out of range");
+    const size_t chi = bond == 0 ? 1 : (bond == n ? 1 : x[bond].l);
+    const size_t W = bond == 0 ? 1 : (bond == n ? 1 : op_->tt.cores[bond].l);
+    dims[0] = chi;
+    dims[1] = W;
+    dims[2] = chi;
+    Engine& e = engine();
+    const double* src = side == 0 ? left_env(bond) : right_env(bond);
+    std::vector<double> out(chi * W * chi);
+    T4A_HIP(hipMemcpyAsync(out.data(), src, sizeof(double) * out.size(), hipMemcpyDeviceToHost, e.stream()));
+    e.sync();
+    return out;
+}
+
+void ProjectedOperator::set_site_tensors(size_t site, const size_t d1[3], const double* t1, const size_t d2[3], const double* t2)
+{
+    const size_t n = x.size();
+    if (site + 1 >= n) throw Error(T4A_GPU_INVALID_ARGUMENT, "projected operator: the region (" + std::to_string(site) + ", " + std::to_string(site + 1) + ") is out of range");
+    if (d1[0] != x[site].l || d1[1] != x[site].s || d2[1] != x[site + 1].s || d2[2] != x[site + 1].r || d1[2] != d2[0] || d1[2] == 0)
+        throw Error(T4A_GPU_INVALID_ARGUMENT, "projected operator: the new site tensors must keep the outer bonds and the site dimensions and share their bond");
+    Engine& e = engine();
+    e.sync();
+    DevCore a = new_core(d1[0], d1[1], d1[2]), c = new_core(d2[0], d2[1], d2[2]);
+    T4A_HIP(hipMemcpyAsync(a.buf.get(), t1, sizeof(double) * a.size(), hipMemcpyHostToDevice, e.stream()));
+    T4A_HIP(hipMemcpyAsync(c.buf.get(), t2, sizeof(double) * c.size(), hipMemcpyHostToDevice, e.stream()));
+    e.sync();
+    x[site] = std::move(a);
+    x[site + 1] = std::move(c);
+    invalidate(site);
+    invalidate(site + 1);
+}
+
+std::vector<double> projected_apply_env(const double* L, const double* R, size_t chi_l, size_t chi_r, Mpo& op, size_t site, const double* v,
+                                        std::vector<double>* hl, std::vector<double>* hr)
+{
+    if (site + 1 >= op.len()) throw Error(T4A_GPU_INVALID_ARGUMENT, "apply_env: the region (" + std::to_string(site) + ", " + std::to_string(site + 1) + ") is out of range");
+    if (chi_l == 0 || chi_r == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "apply_env: an environment has a zero dimension");
+    const DevCore& A1 = op.tt.cores[site];
+    const DevCore& A2 = op.tt.cores[site + 1];
+    if (op.sd[site][0] != op.sd[site][1] || op.sd[site + 1][0] != op.sd[site + 1][1])
+        throw Error(T4A_GPU_INVALID_ARGUMENT, "apply_env: the operator sites are not square");
+    const size_t d1 = op.sd[site][0], d2 = op.sd[site + 1][0], W = A1.r;
+    check_step_dims(site, chi_l, d1, d2, chi_r, W, 0);
+    if (above_int_max({chi_l, A1.l, chi_l}) || above_int_max({chi_r, A2.r, chi_r}))
+        throw Error(T4A_GPU_INVALID_ARGUMENT, "apply_env: an environment holds more than INT_MAX elements");
+    const size_t M = chi_l * d1, N = d2 * chi_r, len = M * N;
+    Engine& e = op.tt.eng;
+    hipStream_t st = e.stream();
+    DevBuf<double> dL, dR, dv, dy, dhl, dhr, dt;
+    const size_t nl = chi_l * A1.l * chi_l, nr = chi_r * A2.r * chi_r;
+    dL.reserve(nl);
+    dR.reserve(nr);
+    dv.reserve(len);
+    dy.reserve(len);
+    dhl.reserve(W * M * M);
+    dhr.reserve(W * N * N);
+    dt.reserve(W * M * N);
+    T4A_HIP(hipMemcpyAsync(dL.get(), L, sizeof(double) * nl, hipMemcpyHostToDevice, st));
+    T4A_HIP(hipMemcpyAsync(dR.get(), R, sizeof(double) * nr, hipMemcpyHostToDevice, st));
+    T4A_HIP(hipMemcpyAsync(dv.get(), v, sizeof(double) * len, hipMemcpyHostToDevice, st));
+    linsolve_hl_launch(dL.get(), A1.buf.get(), dhl.get(), (int)chi_l, (int)A1.l, (int)d1, (int)W, st);
+    linsolve_hr_launch(A2.buf.get(), dR.get(), dhr.get(), (int)chi_r, (int)W, (int)d2, (int)A2.r, st);
+    const int m = (int)M, n = (int)N, w = (int)W;
+    gemm_launch(gemm_desc(w * m, n, m, dhl.get(), w * m, dv.get(), m, dt.get(), w * m), st);
+    gemm_launch(gemm_desc(m, n, w * n, dt.get(), m, dhr.get(), w * n, dy.get(), m), st);
+    T4A_HIP(hipGetLastError());
+    std::vector<double> out(len);
+    T4A_HIP(hipMemcpyAsync(out.data(), dy.get(), sizeof(double) * len, hipMemcpyDeviceToHost, st));
+    if (hl) {
+        hl->resize(W * M * M);
+        T4A_HIP(hipMemcpyAsync(hl->data(), dhl.get(), sizeof(double) * hl->size(), hipMemcpyDeviceToHost, st));
+    }
+    if (hr) {
+        hr->resize(W * N * N);
+        T4A_HIP(hipMemcpyAsync(hr->data(), dhr.get(), sizeof(double) * hr->size(), hipMemcpyDeviceToHost, st));
+    }
+    e.sync();
+    return out;
+}
+
+// ------------------------------------------------------------------------------------------------ the residual and the sweeps
+double relative_linear_system_residual(Mpo& op, TensorTrain& x, TensorTrain& rhs, double a0, double a1)
+{
+    const auto rd = dims3_of(rhs.cores);
+    linsolve_validate_shapes(op.dims4(), &rd, dims3_of(x.cores), 0, 0);
+    x.eng.sync();
+    std::vector<std::array<size_t, 2>> sd;
+    for (const DevCore& c : x.cores) sd.push_back({c.s, 1});
+    Mpo xm(x.cores, x.eng.stream(), sd);
+    MpoContractionOptions co;
+    std::unique_ptr<Mpo> ax = mpo_contract(op, xm, MpoAlgorithm::Naive, false, co); // the exact product, bonds W * chi
+    ax->tt.scale(a1);
+    xm.tt.scale(a0);
+    std::unique_ptr<TensorTrain> lhs = xm.tt.add(ax->tt, false);
+    std::unique_ptr<TensorTrain> r = lhs->add(rhs, true);
+    const double rn = canonical_norm(*r);
+    const double bn = canonical_norm(rhs);
+    return bn > 1e-15 ? rn / bn : rn;
+}
+
+LinsolveResult square_linsolve(Mpo& op, TensorTrain& rhs, TensorTrain& init, size_t center, const LinsolveOptions& o)
+{
+    o.validate();
+    const auto rd = dims3_of(rhs.cores);
+    linsolve_validate_shapes(op.dims4(), &rd, dims3_of(init.cores), center, o.gmres_restart_dim);
+    LinsolveResult out;
+    const bool wants_residual = o.check_residual || o.has_convergence_tol;
+    if (o.a1 == 0.0 || canonical_norm(op.tt) <= 1e-15) { // solve_identity_term_only (square/mod.rs:362-407)
+        if (o.a0 == 0.0) throw Error(T4A_GPU_INVALID_ARGUMENT, "square_linsolve: a0 and effective operator term are both zero");
+        rhs.eng.sync();
+        out.solution = std::make_unique<TensorTrain>(rhs.cores, rhs.eng.stream());
+        out.solution->scale(1.0 / o.a0);
+        if (wants_residual) {
+            out.has_residual = true;
+            out.residual = relative_linear_system_residual(op, *out.solution, rhs, o.a0, o.a1);
+        }
+        out.converged = o.has_convergence_tol && out.has_residual && out.residual < o.convergence_tol;
+        return out;
+    }
+
+    ProjectedOperator po(op, init, &rhs);
+    Engine& e = po.engine();
+    hipStream_t st = e.stream();
+    const size_t n = po.len();
+    {
+        QrSweeper sw(e);
+        sw.canonicalize(po.x, center);
+    }
+    Gmres gm(e);
+    DevBuf<double> theta, bt;
+    SvdOptions so;
+    so.truncate = true;
+    if (o.has_svd_policy) so.policy = o.svd_policy;
+    so.has_max_bond_dim = o.has_max_bond_dim;
+    so.max_bond_dim = o.max_bond_dim;
+
+    auto bond_step = [&](size_t i, bool move_right) {
+        po.check_step(i, o.gmres_restart_dim);
+        const auto ld = po.local_dims(i);
+        const int chi_l = (int)ld[0], d1 = (int)ld[1], d2 = (int)ld[2], chi_r = (int)ld[3];
+        const int M = chi_l * d1, N = d2 * chi_r, mid = (int)po.x[i].r;
+        const size_t len = (size_t)M * N;
+        grow(e, theta, len);
+        grow(e, bt, len);
+        gm.reserve(len, o.gmres_restart_dim);
+        po.local_rhs(i, bt.get());
+        po.prepare(i);
+        gemm_launch(gemm_desc(M, N, mid, po.x[i].buf.get(), M, po.x[i + 1].buf.get(), mid, theta.get(), M), st); // theta_0 = x_i x_{i+1}
+        const GmresResult gr = gm.solve([&](const double* v, double* y) { po.apply_prepared(v, y); }, len, bt.get(), theta.get(), o.a0, o.a1, o.gmres_tol,
+                                        o.gmres_tolerance_mode, o.gmres_restart_dim, o.gmres_max_restarts);
+        ++out.stats.local_solves;
+        out.stats.arnoldi_steps += gr.iterations;
+        out.stats.apply_calls += gr.apply_calls;
+        const TensorView tv{theta.get(), {(size_t)M, (size_t)N}, {0, 1}};
+        const UnfoldPlan un = plan_unfold_split(tv, {0});
+        require_factorizable(un, "square_linsolve", "svd");
+        const UnfoldedFactors f = tensor_svd(e, tv, un, so);
+        const int keep = (int)f.keep, k = (int)f.k;
+        DevCore nl = new_core(ld[0], ld[1], f.keep), nr = new_core(f.keep, ld[2], ld[3]);
+        if (move_right) { // x_i = U, x_{i+1} = S V^T
+            gather_launch(f.d_left, M, nullptr, M, nullptr, keep, nl.buf.get(), M, st);
+            diag_scale_launch(f.d_right, k, keep, N, f.d_s, true, nr.buf.get(), keep, st);
+        } else { // x_i = U S, x_{i+1} = V^T
+            diag_scale_launch(f.d_left, M, M, keep, f.d_s, false, nl.buf.get(), M, st);
+            gather_launch(f.d_right, k, nullptr, keep, nullptr, N, nr.buf.get(), keep, st);
+        }
+        T4A_HIP(hipGetLastError());
+        e.sync(); // the old sites are released below
+        po.x[i] = std::move(nl);
+        po.x[i + 1] = std::move(nr);
+        // both sites changed: every cache that contains one of them is stale; the side left behind is rebuilt from this step's half operator
+        // (HL and HR depend on the environments and the operator only, not on the two sites)
+        po.invalidate(i);
+        po.invalidate(i + 1);
+        if (move_right) po.update_left_from_prepared(i);
+        else po.update_right_from_prepared(i);
+    };
+
+    for (size_t sweep = 0; sweep < o.nfullsweeps; ++sweep) {
+        out.sweeps = sweep + 1;
+        for (size_t i = center; i + 1 < n; ++i) bond_step(i, true);
+        for (size_t i = n - 1; i-- > 0;) bond_step(i, false);
+        for (size_t i = 0; i < center; ++i) bond_step(i, true);
+        if (o.has_convergence_tol) {
+            e.sync();
+            TensorTrain xt(po.x, st);
+            out.has_residual = true;
+            out.residual = relative_linear_system_residual(op, xt, rhs, o.a0, o.a1);
+            if (out.residual < o.convergence_tol) {
+                out.converged = true;
+                break;
+            }
+        }
+    }
+    e.sync();
+    out.solution = std::make_unique<TensorTrain>(po.x, st);
+    if (!out.has_residual && o.check_residual) {
+        out.residual = relative_linear_system_residual(op, *out.solution, rhs, o.a0, o.a1);
+        out.has_residual = true;
+        out.converged = o.has_convergence_tol && out.residual < o.convergence_tol;
+    }
+    return out;
+}
+
+// ------------------------------------------------------------------------------------------------ test hooks
+GmresResult gmres_dense(const double* H, size_t n, const double* b, const double* x0, double a0, double a1, double tol, GmresToleranceMode mode,
+                        size_t restart_dim, size_t max_restarts, double* x_out)
+{
+    Engine e;
+    hipStream_t st = e.stream();
+    DevBuf<double> dH, db, dx;
+    dH.reserve(n * n);
+    db.reserve(n);
+    dx.reserve(n);
+    T4A_HIP(hipMemcpyAsync(dH.get(), H, sizeof(double) * n * n, hipMemcpyHostToDevice, st));
+    T4A_HIP(hipMemcpyAsync(db.get(), b, sizeof(double) * n, hipMemcpyHostToDevice, st));
+    T4A_HIP(hipMemcpyAsync(dx.get(), x0, sizeof(double) * n, hipMemcpyHostToDevice, st));
+    Gmres gm(e);
+    const GmresResult r = gm.solve([&](const double* v, double* y) { gemm_launch(gemm_desc((int)n, 1, (int)n, dH.get(), (int)n, v, (int)n, y, (int)n), st); }, n,
+                                   db.get(), dx.get(), a0, a1, tol, mode, restart_dim, max_restarts);
+    T4A_HIP(hipMemcpyAsync(x_out, dx.get(), sizeof(double) * n, hipMemcpyDeviceToHost, st));
+    e.sync();
+    return r;
+}
+
+void linsolve_orth(const double* basis, size_t len, size_t nb, double* w, double* h_out, double* norm_out)
+{
+    Engine e;
+    hipStream_t st = e.stream();
+    DevBuf<double> dV, dw, dh;
+    dV.reserve(len * nb);
+    dw.reserve(len);
+    dh.reserve(3 * nb + 1);
+    T4A_HIP(hipMemcpyAsync(dV.get(), basis, sizeof(double) * len * nb, hipMemcpyHostToDevice, st));
+    T4A_HIP(hipMemcpyAsync(dw.get(), w, sizeof(double) * len, hipMemcpyHostToDevice, st));
+    Gmres gm(e);
+    gm.reserve(len, nb);
+    gm.orth(dV.get(), len, (int)nb, dw.get(), len, dh.get(), dh.get() + nb + 1);
+    T4A_HIP(hipGetLastError());
+    std::vector<double> hc(nb + 1);
+    T4A_HIP(hipMemcpyAsync(hc.data(), dh.get(), sizeof(double) * (nb + 1), hipMemcpyDeviceToHost, st));
+    T4A_HIP(hipMemcpyAsync(h_out, dh.get() + nb + 1, sizeof(double) * 2 * nb, hipMemcpyDeviceToHost, st));
+    T4A_HIP(hipMemcpyAsync(w, dw.get(), sizeof(double) * len, hipMemcpyDeviceToHost, st));
+    e.sync();
+    *norm_out = hc[nb];
+}
+
+} // namespace t4a

@@ -1,0 +1,183 @@
+// linsolve.hpp — (a0 + a1 A) x = b for an MPO A and tensor trains x, b on the device: the two-site sweeps with a local GMRES of
+// tensor4all-treetn's square_linsolve (crates/tensor4all-treetn/src/linsolve/: square/mod.rs:233-351, square/updater.rs:374-498,
+// :549-622, :848-863, common/projected_operator.rs:230-410, :495-631, square/projected_state.rs, treetn/localupdate.rs:103-160,
+// :377-448; tensor4all-core/src/krylov.rs:1083-1490 gmres_affine_impl), restated for a chain, f64, V_in = V_out: every site of A has
+// s1 == s2 == the site dimension of the state.  Index mappings, tree topologies, spectator nodes and complex scalars stay out.
+//
+// Layouts (column-major): environments L[beta, w, alpha], R[beta, w, alpha] (bra bond, operator bond, ket bond), operator sites
+// A_i[w_l, s, t, w_r], two-site vector v[alpha_l, t1, t2, alpha_r] read as the M x N matrix V, M = chi_l d_i, N = d_{i+1} chi_r.
+// Half operators of a bond step (W the middle operator bond), built once per step by kernels_linsolve.hip:
+//   HL[(beta_l s1) + M w, (alpha_l t1)] = sum_{w_l} L[beta_l, w_l, alpha_l] A_i[w_l, s1, t1, w]          (W M) x M
+//   HR[w + W (t2 alpha_r), (s2 beta_r)] = sum_{w_r} A_{i+1}[w, s2, t2, w_r] R[beta_r, w_r, alpha_r]      (W N) x N
+// The projected apply y = sum_w HL_w V HR_w is two plain products on gemm_launch: T = HL V, (W M) x N, and Y = T HR with the same
+// memory of T read as M x (W N) — index m + M w + M W n in both views, which is why w is the fast index of HR's rows.
+// 2 W M N (M + N) flops per apply; HL and HR take W (M^2 + N^2) doubles, T another W M N, the Krylov basis (restart_dim + 1) M N.
+// A step one of whose buffers would hold more than INT_MAX elements is refused (INVALID_ARGUMENT naming the bond).
+// The environments come from the same operands: L_{i+1}[:, w, :] = X_i^T (HL_w X_i), R_{i+1}[:, w, :] = (X_{i+1} HR_w^T) X_{i+1}^T.
+#pragma once
+
+#include <array>
+#include <functional>
+#include <memory>
+#include <vector>
+
+#include "mpo.hpp"
+#include "tensorops.hpp"
+
+namespace t4a {
+
+// ---- kernels_linsolve.hip.  All pointers are device pointers; launchers enqueue on `stream` and do not synchronise.
+constexpr int GS_MAX_WORKGROUPS = 128;
+// workgroups of every vector kernel below for a vector of `len` elements (a function of len alone: the fixed partition)
+int gs_workgroups(size_t len);
+// HL from L[chi, Wl, chi] and A[Wl, d, d, W]; HR from A[W, d, d, Wr] and R[chi, Wr, chi]
+void linsolve_hl_launch(const double* L, const double* A, double* HL, int chi, int Wl, int d, int W, hipStream_t stream);
+void linsolve_hr_launch(const double* A, const double* R, double* HR, int chi, int W, int d, int Wr, hipStream_t stream);
+// part[i + nb g] = <V[:, i], w> over the elements of workgroup g, i < nb; V is len x nb with leading dimension ld
+void gs_dots_launch(const double* V, size_t ld, int nb, const double* w, size_t len, double* part, hipStream_t stream);
+// c[i] = sum_g part[i + nb g], g < n_part ascending (n_part = gs_workgroups(len) behind gs_dots_launch; 1: part holds the coefficients);
+// w -= sum_i c[i] V[:, i] (i ascending, every term rounded); npart[g] = the share of workgroup g in |w|^2.
+// hcol (may be null): hcol[i] = c[i] when first_pass, else hcol[i] += c[i]; hpass (may be null): hpass[i] = c[i].
+void gs_update_launch(const double* V, size_t ld, int nb, double* w, size_t len, const double* part, int n_part, double* hcol, bool first_pass,
+                      double* hpass, double* npart, hipStream_t stream);
+void gs_norm2_launch(const double* w, size_t len, double* npart, hipStream_t stream);
+// nrm = sqrt(sum_g npart[g]); out = w * (1 / nrm) (out may be w, or null: the norm only); *norm_out = nrm (may be null)
+void gs_normalize_launch(const double* w, size_t len, const double* npart, double* out, double* norm_out, hipStream_t stream);
+// r = b - (a0 x + a1 ax) with the shares of |r|^2 in npart
+void linsolve_residual_launch(const double* b, const double* x, const double* ax, double a0, double a1, double* r, size_t len, double* npart,
+                              hipStream_t stream);
+void linsolve_scale_launch(const double* in, double alpha, double* out, size_t len, hipStream_t stream);
+
+// ---- GMRES on (a0 + a1 H) x = b (krylov.rs:1083-1490).  The Arnoldi basis is built from the unshifted H, a0 and a1 enter the
+// Hessenberg column; Givens rotations and the triangular solve run on the host, which reads j + 2 doubles per step and one norm per
+// restart.  Deviation from the reference: both orthogonalisation passes are classical Gram–Schmidt (all coefficients of a pass from
+// one launch) where the reference's are modified Gram–Schmidt; the column of H is still pass 1 plus pass 2.
+enum class GmresToleranceMode : int { Relative = 0, Absolute = 1 };
+struct GmresResult {
+    size_t iterations = 0;
+    double residual = 0.0;
+    bool converged = false;
+    size_t apply_calls = 0;
+};
+using GmresApply = std::function<void(const double* d_v, double* d_out)>; // enqueues out = H v on the engine's stream
+class Gmres {
+public:
+    explicit Gmres(Engine& e) : eng_(e) {}
+    // x: the start on entry, the solution on exit (device, len doubles).  Non-convergence is a flag.  INVALID_ARGUMENT: a0 == a1 == 0.
+    GmresResult solve(const GmresApply& apply, size_t len, const double* d_b, double* d_x, double a0, double a1, double tol, GmresToleranceMode mode,
+                      size_t restart_dim, size_t max_restarts);
+    // One two-pass orthogonalisation step as solve() launches it: w against the nb columns of V (leading dimension ld), then normalised in
+    // place.  d_hcol: nb + 1 doubles (the column of H, h_{nb} = the norm); d_hpass: 2 nb doubles, the coefficients of pass 1 and of pass 2.
+    void orth(const double* d_V, size_t ld, int nb, double* d_w, size_t len, double* d_hcol, double* d_hpass);
+    void reserve(size_t len, size_t restart_dim);
+
+private:
+    double norm(const double* d_w, size_t len); // host value of |w| (one read)
+    Engine& eng_;
+    DevBuf<double> basis_, ax_, part_, npart_, hcol_, coef_;
+};
+
+// ---- options and results of the solver (LinsolveOptions, SquareLinsolveResult of the reference)
+struct LinsolveOptions {
+    size_t nfullsweeps = 5;
+    bool has_max_bond_dim = false;
+    size_t max_bond_dim = 0;
+    bool has_svd_policy = false; // none: the default policy tensor_svd applies
+    SvdPolicy svd_policy;
+    double gmres_tol = 1e-10;
+    GmresToleranceMode gmres_tolerance_mode = GmresToleranceMode::Relative;
+    size_t gmres_max_restarts = 100;
+    size_t gmres_restart_dim = 30;
+    double a0 = 0.0, a1 = 1.0;
+    bool has_convergence_tol = false;
+    double convergence_tol = 0.0;
+    bool check_residual = true;
+    void validate() const; // INVALID_ARGUMENT (host only)
+};
+struct LinsolveStats {
+    size_t local_solves = 0, arnoldi_steps = 0, apply_calls = 0;
+};
+struct LinsolveResult {
+    std::unique_ptr<TensorTrain> solution;
+    size_t sweeps = 0;
+    bool has_residual = false;
+    double residual = 0.0;
+    bool converged = false;
+    LinsolveStats stats;
+};
+constexpr size_t LINSOLVE_RESTART_DIM_MAX = 8191; // the coefficients of a pass sit in the LDS of gs_update
+
+// The shape checks of the solver on the host, before the device is touched (INVALID_ARGUMENT with a message): fewer than two sites,
+// lengths differ, a site of A that is not square or does not match the state's or the rhs's site dimension, center >= n, and a bond
+// step whose work buffers (HL, HR, T, the Krylov basis of restart_dim + 1 columns) would hold more than INT_MAX elements at the
+// bonds of `state` (the bonds the sweeps reach are checked again as they grow).  rhs may be null (the projected operator alone).
+void linsolve_validate_shapes(const std::vector<std::array<size_t, 4>>& op, const std::vector<std::array<size_t, 3>>* rhs,
+                              const std::vector<std::array<size_t, 3>>& state, size_t center, size_t restart_dim);
+
+// ||(a0 + a1 A) x - b|| / ||b||, the absolute norm when ||b|| <= 1e-15: the exact naive apply, add / sub, and the norm of the residual
+// train from its QR right-canonical form (the transfer-matrix norm2 would lose half of the digits in the cancellation).
+double relative_linear_system_residual(Mpo& op, TensorTrain& x, TensorTrain& rhs, double a0, double a1);
+
+// The projected operator of <x|A|x> on a chain with lazily computed, cached environments; with a rhs also the projected state <x|b>.
+// It owns device copies of the operator, the state and the rhs on an engine of its own.
+class ProjectedOperator {
+public:
+    ProjectedOperator(Mpo& op, TensorTrain& state, TensorTrain* rhs);
+
+    size_t len() const { return x.size(); }
+    // (chi_l, d_i, d_{i+1}, chi_r) of the region (site, site + 1)
+    std::array<size_t, 4> local_dims(size_t site) const;
+    // y = H v for the region (site, site + 1), host arrays of chi_l d_i d_{i+1} chi_r doubles
+    std::vector<double> apply(size_t site, const double* v);
+    // side 0: L_bond[chi, W, chi] of the sites < bond; side 1: R_bond[chi, W, chi] of the sites >= bond (bond <= n); dims receives the shape
+    std::vector<double> environment(int side, size_t bond, size_t dims[3]);
+    // the caches that contain `site` go stale: L_j for j > site, R_j for j <= site
+    void invalidate(size_t site);
+    void set_site_tensors(size_t site, const size_t d1[3], const double* t1, const size_t d2[3], const double* t2);
+
+    // -- the pieces the sweeps use (device side, on the engine's stream)
+    Engine& engine() { return op_->tt.eng; }
+    const double* left_env(size_t i);   // L_i, valid on the stream
+    const double* right_env(size_t i);  // R_i
+    const double* left_rhs_env(size_t i);
+    const double* right_rhs_env(size_t i);
+    void prepare(size_t site);                               // environments and HL, HR of the bond (site, site + 1)
+    void apply_prepared(const double* d_v, double* d_out);   // the two products
+    // Probe: device time in ms (HIP events around `reps` launches behind one warm-up launch) of the five launches of an Arnoldi step
+    // with nb basis vectors at the region (site, site + 1): T = HL V, Y = T HR, gs_dots, gs_update, gs_normalize
+    void time_step(size_t site, size_t nb, size_t reps, double ms[5]);
+    void local_rhs(size_t site, double* d_out);              // Lb_i b_i b_{i+1} Rb_{i+2} as M x N
+    void update_left_from_prepared(size_t site);             // L_{site+1} (and Lb) from x[site] and the HL of prepare(site)
+    void update_right_from_prepared(size_t site);            // R_{site+1} (and Rb) from x[site+1] and the HR of prepare(site)
+    void check_step(size_t site, size_t restart_dim) const;  // INT_MAX bound of the step's buffers
+
+    std::vector<DevCore> x, b;
+
+private:
+    void product_left(const double* d_v);
+    void product_right(double* d_out);
+    std::unique_ptr<Mpo> op_;
+    std::vector<DevBuf<double>> envL_, envR_, envLb_, envRb_;
+    std::vector<char> okL_, okR_;
+    DevBuf<double> hl_, hr_, t_, t1_, p1_, p2_;
+    size_t prepared_ = (size_t)-1;
+};
+
+// The apply on caller-supplied environments (host arrays), launched exactly as the sweeps launch it: L[chi_l, W_l, chi_l],
+// R[chi_r, W_r, chi_r] with the operator bonds of sites `site` and `site + 1`, v and the result chi_l d_i d_{i+1} chi_r doubles.
+// hl / hr (may be null) receive the half operators, (W M) x M and (W N) x N.
+std::vector<double> projected_apply_env(const double* L, const double* R, size_t chi_l, size_t chi_r, Mpo& op, size_t site, const double* v,
+                                        std::vector<double>* hl, std::vector<double>* hr);
+
+// square_linsolve (square/mod.rs:233-351).  `init` is canonicalised onto `center` by thin QR sweeps; the sweep plan is the Euler tour
+// from `center`, two sites per step, the second node of a step the new centre: bonds c .. n-2 to the right, n-2 .. 0 to the left,
+// 0 .. c-1 to the right.  a1 == 0 or ||A|| <= 1e-15: the solution is rhs / a0 and sweeps = 0.
+LinsolveResult square_linsolve(Mpo& op, TensorTrain& rhs, TensorTrain& init, size_t center, const LinsolveOptions& options);
+
+// Test hook: GMRES as the sweeps run it on a dense n x n matrix H (host, column-major) applied on the device.
+GmresResult gmres_dense(const double* H, size_t n, const double* b, const double* x0, double a0, double a1, double tol, GmresToleranceMode mode,
+                        size_t restart_dim, size_t max_restarts, double* x_out);
+// Test hook: Gmres::orth on host arrays: basis len x nb, w len (in/out), h_out 2 nb (pass 1, pass 2), *norm_out
+void linsolve_orth(const double* basis, size_t len, size_t nb, double* w, double* h_out, double* norm_out);
+
+} // namespace t4a

@@ -2150,3 +2150,6 @@ from .quanticstransform import (BoundaryCondition, TriangleType, AffineParams, Q
                                 affine_operator, affine_transform_matrix, identity_mpo, difference_kernel_mpo)
 from . import canonical  # noqa: E402
 from .canonical import SiteTensorTrain, VidalTensorTrain, InverseTensorTrain, center_canonicalize  # noqa: E402,F401
+from . import linsolve  # noqa: E402
+from .linsolve import (GmresToleranceMode, LinsolveOptions, LinsolveOptionsC, SquareLinsolveResult, square_linsolve,  # noqa: E402,F401
+                       relative_linear_system_residual, ProjectedOperator)
