@@ -889,10 +889,7 @@ t4a_gpu_status t4a_gpu_tci2_set_site_tensor_device(t4a_gpu_tci2* h, size_t site,
         h->impl.fill_wait();
         DevCore& c = h->impl.cores[site];
         const size_t count = dims3[0] * dims3[1] * dims3[2];
-        c.buf.reserve(std::max<size_t>(count, 1));
-        c.l = dims3[0];
-        c.s = dims3[1];
-        c.r = dims3[2];
+        c.reshape(dims3[0], dims3[1], dims3[2]);
         if (count) {
             T4A_REQUIRE_PTR(in_device);
             T4A_HIP(hipMemcpyAsync(c.buf.get(), in_device, count * sizeof(double), hipMemcpyDeviceToDevice,

@@ -1,6 +1,7 @@
 // conversion.hip — TensorCI2::from_tensor_train on the device
 // (crates/tensor4all-tensorci/src/conversion.rs:66-433): alternating one-site LUCI sweeps over a copy of the
-// tensor train collect the nested I/J sets; the factor that is not kept is carried into the neighbour by a GEMM.
+// tensor train collect the nested I/J sets; the factor that is not kept is carried into the neighbour by a GEMM
+// (the factor-absorption helpers of tt_chain.hpp).
 #include "tci2.hpp"
 
 #include <algorithm>
@@ -9,12 +10,6 @@
 namespace t4a {
 
 namespace {
-
-struct ConvState {
-    std::vector<DevCore> cores; // working copy of the train (conversion.rs takes `tt` by value)
-};
-
-void move_core(DevCore& dst, DevCore&& src) { dst = std::move(src); }
 
 IndexSet select(const IndexSet& set, const std::vector<int>& perm, int rank) // conversion.rs:401-415
 {
@@ -63,7 +58,6 @@ void sweep1site_get_indices(Engine& eng, std::vector<DevCore>& tt, bool forward,
         DevCore& cur = tt[site];
         DevCore& nxt = tt[next_site];
         const int cl = (int)cur.l, cs = (int)cur.s, cr = (int)cur.r;
-        const int nl = (int)nxt.l, ns = (int)nxt.s, nr = (int)nxt.r;
         // group_indices(current, forward, false): forward -> left matrix, backward -> right matrix
         d_m1.reserve(std::max<size_t>(cur.size(), 1));
         core_reshape_launch(cur.buf.get(), cl, cs, cr, forward ? 0 : 2, d_m1.get(), st);
@@ -87,24 +81,11 @@ void sweep1site_get_indices(Engine& eng, std::vector<DevCore>& tt, bool forward,
             index_set.push_back(select(cand, f.row_perm, r));
             if (spectators) (*spectators)[site] = select((*spectators)[site], f.col_perm, r);
             // next <- right factor (r x cr) * right matrix of next (nl x ns*nr), nl == cr
-            d_m1.reserve(std::max<size_t>(nxt.size(), 1));
-            core_reshape_launch(nxt.buf.get(), nl, ns, nr, 2, d_m1.get(), st);
-            d_m2.reserve(std::max<size_t>((size_t)r * ns * nr, 1));
-            gemm_launch(gemm_desc(r, ns * nr, cr, eng.right(), r, d_m1.get(), nl, d_m2.get(), r), st);
-            DevCore nc, nn;
-            nc.l = cl;
-            nc.s = cs;
-            nc.r = r;
-            nc.buf.reserve(std::max<size_t>(nc.size(), 1));
-            core_reshape_launch(eng.left(), cl, cs, r, 1, nc.buf.get(), st);
-            nn.l = r;
-            nn.s = ns;
-            nn.r = nr;
-            nn.buf.reserve(std::max<size_t>(nn.size(), 1));
-            core_reshape_launch(d_m2.get(), r, ns, nr, 3, nn.buf.get(), st);
+            DevCore nn = absorb_right_into_next(eng, (size_t)r, nxt, d_m1, d_m2);
+            DevCore nc = core_from_left_factor(eng, cur.l, cur.s, (size_t)r);
             eng.sync();
-            move_core(tt[site], std::move(nc));
-            move_core(tt[next_site], std::move(nn));
+            cur = std::move(nc);
+            nxt = std::move(nn);
         } else { // kronecker_prepend :379-399
             cand.width = base.width + 1;
             std::vector<uint32_t> tmp(cand.width);
@@ -117,24 +98,11 @@ void sweep1site_get_indices(Engine& eng, std::vector<DevCore>& tt, bool forward,
             index_set.push_back(select(cand, f.col_perm, r));
             if (spectators) (*spectators)[site] = select((*spectators)[site], f.row_perm, r);
             // next <- left matrix of next (nl*ns x nr) * left factor (cl x r), nr == cl
-            d_m1.reserve(std::max<size_t>(nxt.size(), 1));
-            core_reshape_launch(nxt.buf.get(), nl, ns, nr, 0, d_m1.get(), st);
-            d_m2.reserve(std::max<size_t>((size_t)nl * ns * r, 1));
-            gemm_launch(gemm_desc(nl * ns, r, cl, d_m1.get(), nl * ns, eng.left(), cl, d_m2.get(), nl * ns), st);
-            DevCore nc, nn;
-            nc.l = r;
-            nc.s = cs;
-            nc.r = cr;
-            nc.buf.reserve(std::max<size_t>(nc.size(), 1));
-            core_reshape_launch(eng.right(), r, cs, cr, 3, nc.buf.get(), st);
-            nn.l = nl;
-            nn.s = ns;
-            nn.r = r;
-            nn.buf.reserve(std::max<size_t>(nn.size(), 1));
-            core_reshape_launch(d_m2.get(), nl, ns, r, 1, nn.buf.get(), st);
+            DevCore nn = absorb_left_into_prev(eng, (size_t)r, nxt, d_m1, d_m2);
+            DevCore nc = core_from_right_factor(eng, (size_t)r, cur.s, cur.r);
             eng.sync();
-            move_core(tt[site], std::move(nc));
-            move_core(tt[next_site], std::move(nn));
+            cur = std::move(nc);
+            nxt = std::move(nn);
         }
         // merge_pivot_errors :417-424
         if (pivot_errors.size() < f.pivot_errors.size()) pivot_errors.resize(f.pivot_errors.size(), 0.0);
@@ -159,16 +127,7 @@ void Tci2::assign_from_tensor_train(const TensorTrain& src, const FromTensorTrai
             throw Error(T4A_GPU_INVALID_ARGUMENT, "TensorCI2 conversion: local dimension mismatch");
     fill_wait();
     hipStream_t st = eng.stream();
-    std::vector<DevCore> tt(n_);
-    for (size_t s = 0; s < n_; ++s) {
-        tt[s].l = src.cores[s].l;
-        tt[s].s = src.cores[s].s;
-        tt[s].r = src.cores[s].r;
-        tt[s].buf.reserve(std::max<size_t>(tt[s].size(), 1));
-        if (tt[s].size())
-            T4A_HIP(hipMemcpyAsync(tt[s].buf.get(), src.cores[s].buf.get(), tt[s].size() * sizeof(double),
-                                   hipMemcpyDeviceToDevice, st));
-    }
+    std::vector<DevCore> tt = clone_cores(src.cores, st); // the working copy (conversion.rs takes `tt` by value)
     DevBuf<double> d_m1, d_m2;
     std::vector<IndexSet> iset, jset, tmp;
     std::vector<double> errs, perr;

@@ -2,6 +2,7 @@
 // rotations and the small triangular solve of GMRES are host work; every other floating-point operation runs in gfx950 kernels:
 // the half-operator builders and the Gram–Schmidt launches (kernels_linsolve.hip), the f64-MFMA GEMM (kernels_dense.hip), the
 // Householder QR and the Jacobi SVD behind tensor_svd (kernels_linalg.hip), the naive MPO product of the residual (kernels_mpo.hip).
+// The state is re-gauged by QrSweep and split by split_two_site (tt_chain.hpp).
 #include "linsolve.hpp"
 
 #include <algorithm>
@@ -12,27 +13,6 @@
 namespace t4a {
 
 namespace {
-
-DevCore new_core(size_t l, size_t s, size_t r)
-{
-    DevCore c;
-    c.l = l;
-    c.s = s;
-    c.r = r;
-    c.buf.reserve(std::max<size_t>(c.size(), 1));
-    return c;
-}
-
-std::vector<DevCore> copy_cores(const std::vector<DevCore>& src, hipStream_t st)
-{
-    std::vector<DevCore> out;
-    for (const DevCore& c : src) {
-        DevCore cp = new_core(c.l, c.s, c.r);
-        if (c.size()) T4A_HIP(hipMemcpyAsync(cp.buf.get(), c.buf.get(), sizeof(double) * c.size(), hipMemcpyDeviceToDevice, st));
-        out.push_back(std::move(cp));
-    }
-    return out;
-}
 
 bool above_int_max(std::initializer_list<size_t> factors)
 {
@@ -55,75 +35,9 @@ void check_step_dims(size_t i, size_t chi_l, size_t d1, size_t d2, size_t chi_r,
                                                   ") holds more than INT_MAX elements");
 }
 
-// a buffer that may still be read on the stream is not handed back to the pool before the stream has drained
-void grow(Engine& e, DevBuf<double>& b, size_t n)
-{
-    n = std::max<size_t>(n, 1);
-    if (n <= b.cap) return;
-    e.sync();
-    b.reserve(n);
-}
-
-// QR sweeps with the thin Householder QR.  sites > stop from the right: the site becomes Q^T, R^T goes into its left neighbour
-// (np_right_canonicalize of tests/fit_np.py); sites < from the left: the site becomes Q, R goes into its right neighbour.
-struct QrSweeper {
-    Engine& eng;
-    hipStream_t st;
-    DevBuf<double> m1, q, rr;
-    explicit QrSweeper(Engine& e) : eng(e), st(e.stream()) {}
-
-    void right_step(std::vector<DevCore>& cores, size_t i)
-    {
-        DevCore& c = cores[i];
-        DevCore& p = cores[i - 1];
-        const int L = (int)c.l, rest = (int)(c.s * c.r);
-        const int k = std::min(L, rest);
-        grow(eng, m1, (size_t)rest * L);
-        grow(eng, q, (size_t)rest * k);
-        grow(eng, rr, (size_t)k * L);
-        transpose_launch(c.buf.get(), L, rest, L, m1.get(), rest, st);
-        eng.qr(m1.get(), rest, L, q.get(), rr.get());
-        DevCore nc = new_core(k, c.s, c.r);
-        transpose_launch(q.get(), rest, k, rest, nc.buf.get(), k, st);
-        DevCore np = new_core(p.l, p.s, k);
-        const int pm = (int)(p.l * p.s);
-        GemmDesc g = gemm_desc(pm, k, L, p.buf.get(), pm, rr.get(), k, np.buf.get(), pm);
-        g.transB = 1; // prev (l s x L) * R^T (L x k)
-        gemm_launch(g, st);
-        T4A_HIP(hipGetLastError());
-        eng.sync(); // the old cores are released below
-        c = std::move(nc);
-        p = std::move(np);
-    }
-    void left_step(std::vector<DevCore>& cores, size_t i)
-    {
-        DevCore& c = cores[i];
-        DevCore& nx = cores[i + 1];
-        const int rows = (int)(c.l * c.s), R = (int)c.r;
-        const int k = std::min(rows, R);
-        grow(eng, rr, (size_t)k * R);
-        DevCore nc = new_core(c.l, c.s, k);
-        eng.qr(c.buf.get(), rows, R, nc.buf.get(), rr.get());
-        DevCore nn = new_core(k, nx.s, nx.r);
-        const int rest = (int)(nx.s * nx.r);
-        gemm_launch(gemm_desc(k, rest, R, rr.get(), k, nx.buf.get(), R, nn.buf.get(), k), st); // R (k x R) * next (R x s r)
-        T4A_HIP(hipGetLastError());
-        eng.sync();
-        c = std::move(nc);
-        nx = std::move(nn);
-    }
-    void canonicalize(std::vector<DevCore>& cores, size_t center)
-    {
-        for (size_t i = 0; i < center; ++i) left_step(cores, i);
-        for (size_t i = cores.size() - 1; i > center; --i) right_step(cores, i);
-    }
-};
-
 double host_norm(Engine& eng, const DevCore& c)
 {
-    std::vector<double> h(c.size());
-    if (!h.empty()) T4A_HIP(hipMemcpyAsync(h.data(), c.buf.get(), sizeof(double) * h.size(), hipMemcpyDeviceToHost, eng.stream()));
-    eng.sync();
+    const std::vector<double> h = to_host(eng, c.buf.get(), c.size());
     double s = 0.0;
     for (double v : h) s = s + v * v;
     return std::sqrt(s);
@@ -133,8 +47,8 @@ double host_norm(Engine& eng, const DevCore& c)
 double canonical_norm(TensorTrain& t)
 {
     if (t.len() == 0) return 0.0;
-    std::vector<DevCore> cores = copy_cores(t.cores, t.eng.stream());
-    QrSweeper sw(t.eng);
+    std::vector<DevCore> cores = clone_cores(t.cores, t.eng.stream());
+    QrSweep sw(t.eng);
     sw.canonicalize(cores, 0);
     return host_norm(t.eng, cores[0]);
 }
@@ -384,10 +298,10 @@ ProjectedOperator::ProjectedOperator(Mpo& op, TensorTrain& state, TensorTrain* r
     op_ = std::make_unique<Mpo>(op.tt.cores, op.tt.eng.stream(), op.sd);
     Engine& e = engine();
     state.eng.sync();
-    x = copy_cores(state.cores, e.stream());
+    x = clone_cores(state.cores, e.stream());
     if (rhs) {
         rhs->eng.sync();
-        b = copy_cores(rhs->cores, e.stream());
+        b = clone_cores(rhs->cores, e.stream());
     }
     const size_t n = x.size();
     envL_.resize(n + 1);
@@ -652,10 +566,7 @@ std::vector<double> ProjectedOperator::apply(size_t site, const double* v)
     T4A_HIP(hipMemcpyAsync(d_v.get(), v, sizeof(double) * len, hipMemcpyHostToDevice, e.stream()));
     apply_prepared(d_v.get(), d_y.get());
     T4A_HIP(hipGetLastError());
-    std::vector<double> out(len);
-    T4A_HIP(hipMemcpyAsync(out.data(), d_y.get(), sizeof(double) * len, hipMemcpyDeviceToHost, e.stream()));
-    e.sync();
-    return out;
+    return to_host(e, d_y.get(), len);
 }
 
 std::vector<double> ProjectedOperator::environment(int side, size_t bond, size_t dims[3])
@@ -669,10 +580,7 @@ std::vector<double> ProjectedOperator::environment(int side, size_t bond, size_t
     dims[2] = chi;
     Engine& e = engine();
     const double* src = side == 0 ? left_env(bond) : right_env(bond);
-    std::vector<double> out(chi * W * chi);
-    T4A_HIP(hipMemcpyAsync(out.data(), src, sizeof(double) * out.size(), hipMemcpyDeviceToHost, e.stream()));
-    e.sync();
-    return out;
+    return to_host(e, src, chi * W * chi);
 }
 
 void ProjectedOperator::set_site_tensors(size_t site, const size_t d1[3], const double* t1, const size_t d2[3], const double* t2)
@@ -683,7 +591,7 @@ void ProjectedOperator::set_site_tensors(size_t site, const size_t d1[3], const 
         throw Error(T4A_GPU_INVALID_ARGUMENT, "projected operator: the new site tensors must keep the outer bonds and the site dimensions and share their bond");
     Engine& e = engine();
     e.sync();
-    DevCore a = new_core(d1[0], d1[1], d1[2]), c = new_core(d2[0], d2[1], d2[2]);
+    DevCore a = DevCore::make(d1[0], d1[1], d1[2]), c = DevCore::make(d2[0], d2[1], d2[2]);
     T4A_HIP(hipMemcpyAsync(a.buf.get(), t1, sizeof(double) * a.size(), hipMemcpyHostToDevice, e.stream()));
     T4A_HIP(hipMemcpyAsync(c.buf.get(), t2, sizeof(double) * c.size(), hipMemcpyHostToDevice, e.stream()));
     e.sync();
@@ -786,7 +694,7 @@ LinsolveResult square_linsolve(Mpo& op, TensorTrain& rhs, TensorTrain& init, siz
     hipStream_t st = e.stream();
     const size_t n = po.len();
     {
-        QrSweeper sw(e);
+        QrSweep sw(e);
         sw.canonicalize(po.x, center);
     }
     Gmres gm(e);
@@ -818,15 +726,8 @@ LinsolveResult square_linsolve(Mpo& op, TensorTrain& rhs, TensorTrain& init, siz
         const UnfoldPlan un = plan_unfold_split(tv, {0});
         require_factorizable(un, "square_linsolve", "svd");
         const UnfoldedFactors f = tensor_svd(e, tv, un, so);
-        const int keep = (int)f.keep, k = (int)f.k;
-        DevCore nl = new_core(ld[0], ld[1], f.keep), nr = new_core(f.keep, ld[2], ld[3]);
-        if (move_right) { // x_i = U, x_{i+1} = S V^T
-            gather_launch(f.d_left, M, nullptr, M, nullptr, keep, nl.buf.get(), M, st);
-            diag_scale_launch(f.d_right, k, keep, N, f.d_s, true, nr.buf.get(), keep, st);
-        } else { // x_i = U S, x_{i+1} = V^T
-            diag_scale_launch(f.d_left, M, M, keep, f.d_s, false, nl.buf.get(), M, st);
-            gather_launch(f.d_right, k, nullptr, keep, nullptr, N, nr.buf.get(), keep, st);
-        }
+        DevCore nl = DevCore::make(ld[0], ld[1], f.keep), nr = DevCore::make(f.keep, ld[2], ld[3]);
+        split_two_site(st, f.d_left, M, f.d_s, f.d_right, (int)f.k, N, (int)f.keep, move_right, nl, nr); // x_i = U | x_i = U S
         T4A_HIP(hipGetLastError());
         e.sync(); // the old sites are released below
         po.x[i] = std::move(nl);

@@ -1,7 +1,8 @@
 // mpo.hip — MPO<f64> and the contraction of two MPOs on the device (see mpo.hpp).  Shape bookkeeping is host work; every
 // floating-point operation runs in gfx950 kernels: the naive site contraction (kernels_mpo.hip), the f64-MFMA GEMM and the
 // gathers (kernels_dense.hip), the axis permutation (kernels_tt.hip), the Householder QR and the Jacobi SVD (kernels_linalg.hip),
-// the half products of the variational fit (kernels_mpo_fit.hip).
+// the half products of the variational fit (kernels_mpo_fit.hip).  Sites are made, copied, right-canonicalised (QrSweep) and split
+// after the two-site SVD (split_two_site) with the chain helpers of tt_chain.hpp.
 #include "mpo.hpp"
 #include "tensorops.hpp"
 
@@ -15,16 +16,6 @@ namespace t4a {
 namespace {
 
 constexpr size_t MPO_DIM_MAX = 65535; // the tensor train's limit, which also holds for the fused site index s1*s2
-
-DevCore new_core(size_t l, size_t s, size_t r)
-{
-    DevCore c;
-    c.l = l;
-    c.s = s;
-    c.r = r;
-    c.buf.reserve(std::max<size_t>(c.size(), 1));
-    return c;
-}
 
 // the kernels and the GEMM index a site with int
 void check_count(size_t a, size_t b, size_t c, size_t d, const std::string& what)
@@ -42,10 +33,11 @@ struct Contractor {
     Engine& eng;
     const MpoContractionOptions& opt;
     hipStream_t st;
-    DevBuf<double> u, s, vt, m1, m2, q, rr, x, y, cm;
+    DevBuf<double> u, s, vt, m1, m2, x, y, cm;
     std::vector<double> hs;
+    QrSweep sweeper; // right_canonicalize (canonical.rs:35-89) is sweeper.canonicalize(cores, 0)
 
-    Contractor(Engine& e, const MpoContractionOptions& o) : eng(e), opt(o), st(e.stream()) {}
+    Contractor(Engine& e, const MpoContractionOptions& o) : eng(e), opt(o), st(e.stream()), sweeper(e) {}
 
     // factorize (factorize.rs:126-313) with left_orthogonal = true, SVD rank rule: cutoff = tolerance * s_max, values kept
     // while rank < max_bond_dim and s >= cutoff; a zero matrix keeps nothing and is floored to rank 1 (not an error).  LU and
@@ -92,7 +84,7 @@ struct Contractor {
             const DevCore& y = b.tt.cores[i];
             const size_t s1 = a.sd[i][0], k = a.sd[i][1], t = b.sd[i][1];
             check_count(x.l * y.l, s1, t, x.r * y.r, "contract_naive: site " + std::to_string(i));
-            out[i] = new_core(x.l * y.l, s1 * t, x.r * y.r);
+            out[i] = DevCore::make(x.l * y.l, s1 * t, x.r * y.r);
             MpoSiteJob& j = jobs[i];
             j = MpoSiteJob{};
             j.A = x.buf.get();
@@ -117,51 +109,23 @@ struct Contractor {
         return out;
     }
 
-    // right_canonicalize (canonical.rs:35-89): thin QR of each transposed left x (s1*s2*right) matricisation from the right;
-    // the site becomes Q^T (k = min(left, rest) rows), R^T is absorbed into the left neighbour
-    void right_canonicalize(std::vector<DevCore>& cores)
-    {
-        for (size_t i = cores.size() - 1; i >= 1; --i) {
-            DevCore& c = cores[i];
-            DevCore& p = cores[i - 1];
-            const int L = (int)c.l, rest = (int)(c.s * c.r);
-            const int k = std::min(L, rest);
-            m1.reserve((size_t)rest * L);
-            transpose_launch(c.buf.get(), L, rest, L, m1.get(), rest, st);
-            q.reserve((size_t)rest * k);
-            rr.reserve((size_t)k * L);
-            eng.qr(m1.get(), rest, L, q.get(), rr.get());
-            DevCore nc = new_core(k, c.s, c.r);
-            transpose_launch(q.get(), rest, k, rest, nc.buf.get(), k, st);
-            DevCore np = new_core(p.l, p.s, k);
-            const int pm = (int)(p.l * p.s);
-            GemmDesc g = gemm_desc(pm, k, L, p.buf.get(), pm, rr.get(), k, np.buf.get(), pm);
-            g.transB = 1; // prev (l*s x L) * R^T (L x k)
-            gemm_launch(g, st);
-            T4A_HIP(hipGetLastError());
-            eng.sync(); // the old cores are released below
-            c = std::move(nc);
-            p = std::move(np);
-        }
-    }
-
     // compress_mpo (contract_naive.rs:100-172): right-canonicalise, then a left-to-right sweep of factorize; the right factor
     // is absorbed into the next site
     void compress(std::vector<DevCore>& cores)
     {
         const size_t n = cores.size();
         if (n <= 1) return;
-        right_canonicalize(cores);
+        sweeper.canonicalize(cores, 0);
         for (size_t i = 0; i + 1 < n; ++i) {
             DevCore& c = cores[i];
             DevCore& nx = cores[i + 1];
             const int M = (int)(c.l * c.s), N = (int)c.r;
             const size_t rank = svd_rank(c.buf.get(), M, N);
-            DevCore nc = new_core(c.l, c.s, rank);
+            DevCore nc = DevCore::make(c.l, c.s, rank);
             left(M, (int)rank, nc.buf.get());
             m2.reserve(rank * N);
             right(M, N, (int)rank, m2.get());
-            DevCore nn = new_core(rank, nx.s, nx.r);
+            DevCore nn = DevCore::make(rank, nx.s, nx.r);
             const int rest = (int)(nx.s * nx.r);
             gemm_launch(gemm_desc((int)rank, rest, N, m2.get(), (int)rank, nx.buf.get(), N, nn.buf.get(), (int)rank), st);
             T4A_HIP(hipGetLastError());
@@ -210,7 +174,7 @@ struct Contractor {
             gemm_launch(g, st);
             const size_t rows = N0 * S1 * Ra, cols = T * Rb;
             if (i == n - 1) { // last site: the trailing bonds are 1, Y is C = [n, s1, t, 1]
-                DevCore site = new_core(N0, S1 * T, 1);
+                DevCore site = DevCore::make(N0, S1 * T, 1);
                 gemm_launch(gemm_desc((int)rows, (int)cols, (int)(K * Lb), x.get(), (int)rows, m2.get(), (int)(K * Lb), site.buf.get(), (int)rows),
                             st);
                 T4A_HIP(hipGetLastError());
@@ -225,7 +189,7 @@ struct Contractor {
             permute_launch(y.get(), dy, py, 5, cm.get(), st);
             const int M = (int)(N0 * S1 * T), N = (int)(Ra * Rb);
             const size_t rank = svd_rank(cm.get(), M, N);
-            DevCore site = new_core(N0, S1 * T, rank);
+            DevCore site = DevCore::make(N0, S1 * T, rank);
             left(M, (int)rank, site.buf.get());
             rem_next.reserve(rank * N);
             right(M, N, (int)rank, rem_next.get());
@@ -307,7 +271,7 @@ struct Contractor {
     void fit(const Mpo& a, const Mpo& b, std::vector<DevCore>& c, size_t max_sweeps, double convergence_tol, MpoFitInfo& info)
     {
         const size_t n = c.size();
-        right_canonicalize(c);
+        sweeper.canonicalize(c, 0);
         envL.resize(n);
         envR.resize(n + 1);
         envL[0].reserve(1);
@@ -318,9 +282,7 @@ struct Contractor {
             half(a, b, i, true, envR[i + 1].get(), c[i].r, hq);
             right_env(a, b, i, c[i].l, c[i].r, c[i].buf.get(), (int)c[i].l);
         }
-        std::vector<double> h0(c[0].size());
-        T4A_HIP(hipMemcpyAsync(h0.data(), c[0].buf.get(), sizeof(double) * h0.size(), hipMemcpyDeviceToHost, st));
-        eng.sync();
+        const std::vector<double> h0 = to_host(eng, c[0].buf.get(), c[0].size());
         double norm_prev = 0.0;
         for (double v : h0) norm_prev = std::hypot(norm_prev, v);
         info.norms.push_back(norm_prev);
@@ -337,17 +299,14 @@ struct Contractor {
             gemm_launch(gemm_desc(M, N, (int)ab, hp.get(), M, hq.get(), (int)ab, theta.get(), M), st);
             const size_t rank = svd_rank(theta.get(), M, N);
             const int kmin = std::min(M, N);
-            DevCore nl = new_core(ci, sl, rank), nr = new_core(rank, sr, cn);
+            DevCore nl = DevCore::make(ci, sl, rank), nr = DevCore::make(rank, sr, cn);
+            split_two_site(st, u.get(), M, s.get(), vt.get(), kmin, N, (int)rank, move_right, nl, nr);
             if (move_right) { // C_i = U, C_{i+1} = diag(S) Vt, L_{i+1} = U^T P_i
-                left(M, (int)rank, nl.buf.get());
-                right(M, N, (int)rank, nr.buf.get());
                 envL[i + 1].reserve(rank * ab);
                 GemmDesc g = gemm_desc((int)rank, (int)ab, M, u.get(), M, hp.get(), M, envL[i + 1].get(), (int)rank);
                 g.transA = 1;
                 gemm_launch(g, st);
             } else { // C_i = U diag(S), C_{i+1} = Vt, R_{i+1} = Q_{i+1} Vt^T
-                diag_scale_launch(u.get(), M, M, (int)rank, s.get(), false, nl.buf.get(), M, st);
-                gather_launch(vt.get(), kmin, nullptr, (int)rank, nullptr, N, nr.buf.get(), (int)rank, st);
                 right_env(a, b, i + 1, rank, cn, vt.get(), kmin);
             }
             T4A_HIP(hipGetLastError());
@@ -453,7 +412,7 @@ std::unique_ptr<Mpo> Mpo::transpose()
     const hipStream_t st = tt.eng.stream();
     for (size_t i = 0; i < n; ++i) {
         const DevCore& c = tt.cores[i];
-        out[i] = new_core(c.l, c.s, c.r);
+        out[i] = DevCore::make(c.l, c.s, c.r);
         tsd[i] = {sd[i][1], sd[i][0]};
         const size_t d[4] = {c.l, sd[i][0], sd[i][1], c.r}, p[4] = {0, 2, 1, 3};
         permute_launch(c.buf.get(), d, p, 4, out[i].buf.get(), st);
@@ -549,11 +508,7 @@ std::unique_ptr<Mpo> mpo_contract_fit(Mpo& a, Mpo& b, const MpoFitOptions& opt, 
         cores = c.naive(a, b);
     } else {
         if (initial) {
-            for (const DevCore& src : initial->tt.cores) {
-                DevCore cp = new_core(src.l, src.s, src.r);
-                T4A_HIP(hipMemcpyAsync(cp.buf.get(), src.buf.get(), sizeof(double) * src.size(), hipMemcpyDeviceToDevice, c.st));
-                cores.push_back(std::move(cp));
-            }
+            cores = clone_cores(initial->tt.cores, c.st);
         } else {
             cores = c.zipup(a, b); // the initialiser of treetn::contract_fit, same tolerance, cap and method
         }
@@ -582,10 +537,7 @@ std::vector<double> mpo_fit_half(const double* env, size_t n_env, bool right, Mp
     T4A_HIP(hipMemcpyAsync(d_env.get(), env, sizeof(double) * ne, hipMemcpyHostToDevice, c.st));
     c.half(a, b, site, right, d_env.get(), n_env, d_out);
     T4A_HIP(hipGetLastError());
-    std::vector<double> out(no);
-    T4A_HIP(hipMemcpyAsync(out.data(), d_out.get(), sizeof(double) * no, hipMemcpyDeviceToHost, c.st));
-    a.tt.eng.sync();
-    return out;
+    return to_host(a.tt.eng, d_out.get(), no);
 }
 
 } // namespace t4a

@@ -1,4 +1,5 @@
-// patching.hip — see patching.hpp.  Host queue logic + one device TCI2 per patch.
+// patching.hip — see patching.hpp.  Host queue logic + one device TCI2 per patch; patch cores are shaped and copied with the
+// DevCore helpers of tt_chain.hpp.
 #include "patching.hpp"
 #include "stdrng.hpp"
 
@@ -114,10 +115,7 @@ std::vector<Pivot> patch_candidates(const std::vector<size_t>& dims, const std::
 
 void make_selector_core(DevCore& c, size_t bond, size_t dim, size_t value, double scale, hipStream_t st)
 {
-    c.l = bond;
-    c.s = dim;
-    c.r = bond;
-    c.buf.reserve(std::max<size_t>(c.size(), 1));
+    c.reshape(bond, dim, bond);
     size_t blocks = (c.size() + 255) / 256;
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(copy_selector_kernel, dim3((unsigned)blocks), dim3(256), 0, st, c.buf.get(), (int)bond, (int)dim,
@@ -126,10 +124,7 @@ void make_selector_core(DevCore& c, size_t bond, size_t dim, size_t value, doubl
 
 void make_host_core(DevCore& c, size_t l, size_t s, size_t r, const std::vector<double>& data, hipStream_t st)
 {
-    c.l = l;
-    c.s = s;
-    c.r = r;
-    c.buf.reserve(std::max<size_t>(c.size(), 1));
+    c.reshape(l, s, r);
     if (c.size()) {
         T4A_HIP(hipMemcpyAsync(c.buf.get(), data.data(), c.size() * sizeof(double), hipMemcpyHostToDevice, st));
         T4A_HIP(hipStreamSynchronize(st)); // `data` is pageable
@@ -179,13 +174,7 @@ SubDomain embed_patch(const std::vector<const DevCore*>& active_cores, const std
             const DevCore& src = *active_cores[next_active++];
             if (src.l != l || src.r != r || src.s != dims[p])
                 throw Error(T4A_GPU_INTERNAL_ERROR, "embedded core shape mismatch at site " + std::to_string(p));
-            DevCore& c = sd.cores[p];
-            c.l = l;
-            c.s = dims[p];
-            c.r = r;
-            c.buf.reserve(std::max<size_t>(c.size(), 1));
-            if (c.size())
-                T4A_HIP(hipMemcpyAsync(c.buf.get(), src.buf.get(), c.size() * sizeof(double), hipMemcpyDeviceToDevice, st));
+            sd.cores[p] = clone_core(src, st);
         } else {
             auto it = pr.find(p);
             if (it == pr.end())

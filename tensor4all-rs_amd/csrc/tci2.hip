@@ -602,10 +602,7 @@ LuciResult Tci2::rook_on_sets(const IndexSet& is, const IndexSet& js, const RrLU
 void Tci2::set_core_zero(size_t site, size_t l, size_t s, size_t r)
 {
     DevCore& c = cores[site];
-    c.buf.reserve(std::max<size_t>(l * s * r, 1));
-    c.l = l;
-    c.s = s;
-    c.r = r;
+    c.reshape(l, s, r);
     fill_launch(c.buf.get(), l * s * r, 0.0, eng.stream());
 }
 

@@ -216,8 +216,12 @@ void Tci2::chain_upload_hist(HistEntry& e, int slot)
             std::memcpy(acc + p * cap * K, a.data(), a.size() * sizeof(uint64_t));
             cnt[(size_t)side * n_ + p] = (int)s.count;
         }
-    T4A_HIP(hipMemcpy(chain_tab(2 + 2 * slot).code, buf.data(), buf.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
-    T4A_HIP(hipMemcpy(chain_tab(2 + 2 * slot).cnt, cnt.data(), cnt.size() * sizeof(int), hipMemcpyHostToDevice));
+    // on the handle's own stream, as chain_upload_current does: a synchronous copy on the default stream fails with a capture error
+    // (and invalidates the capture) while another handle's thread records its fill graph
+    hipStream_t st = eng.stream();
+    T4A_HIP(hipMemcpyAsync(chain_tab(2 + 2 * slot).code, buf.data(), buf.size() * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    T4A_HIP(hipMemcpyAsync(chain_tab(2 + 2 * slot).cnt, cnt.data(), cnt.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    T4A_HIP(hipStreamSynchronize(st)); // `buf` and `cnt` are pageable host memory
 }
 
 // accumulators fill_site_tensors needs for site b (J_b, kron(I_b, d_b), I_{b+1}; tensorci2.rs:1101-1145) from the mirror

@@ -398,10 +398,7 @@ void Tci2::fill_run(FillOptions opt)
             const size_t left_dim = (b == 0) ? 1 : std::max<size_t>(i_set[b].count, 1);
             const size_t right_dim = (b == n_ - 1) ? 1 : std::max<size_t>(i_set[b + 1].count, 1);
             DevCore& c = cores[b];
-            c.buf.reserve(std::max<size_t>(left_dim * local_dims[b] * right_dim, 1));
-            c.l = left_dim;
-            c.s = local_dims[b];
-            c.r = right_dim;
+            c.reshape(left_dim, local_dims[b], right_dim);
             rec.zeros.push_back(FillZero{c.buf.get(), c.size()});
             continue;
         }
@@ -463,10 +460,7 @@ void Tci2::fill_run(FillOptions opt)
         j.B = fill_.B.get() + j.offB;
         j.pmax = d_max + j.b;
         DevCore& c = cores[j.b];
-        c.l = (j.b == 0) ? 1 : i_set[j.b].count;
-        c.s = local_dims[j.b];
-        c.r = j.last ? 1 : j.np;
-        c.buf.reserve(std::max<size_t>(c.size(), 1));
+        c.reshape((j.b == 0) ? 1 : i_set[j.b].count, local_dims[j.b], j.last ? 1 : j.np);
         piv_total += j.np;
     }
     fill_.piv.reserve(std::max<size_t>(piv_total, 1));
@@ -692,10 +686,7 @@ void Tci2::import_site_shard_async(const double* d_src, size_t stride, size_t pe
         const size_t rr = (s + 1 == n_) ? 1 : std::max<size_t>(i_set[s + 1].count, 1);
         const size_t count = l * local_dims[s] * rr;
         if (count > stride) throw Error(T4A_GPU_BUFFER_TOO_SMALL, "import_site_shard: stride smaller than a site tensor");
-        c.buf.reserve(std::max<size_t>(count, 1));
-        c.l = l;
-        c.s = local_dims[s];
-        c.r = rr;
+        c.reshape(l, local_dims[s], rr);
         T4A_HIP(hipMemcpyAsync(c.buf.get(), d_src + (r * per_rank + s / shard_world) * stride, count * sizeof(double),
                                hipMemcpyDeviceToDevice, fill_.import_stream));
     }

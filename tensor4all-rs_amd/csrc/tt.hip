@@ -1,5 +1,6 @@
 // tt.hip — SimpleTensorTrain<f64> on the device (see tt.hpp): evaluate / sum / norm2 / compress /
-// TTCache::evaluate_many.  Index bookkeeping (unique halves, split heuristic) is host integer work,
+// TTCache::evaluate_many.  Cores are made, copied and re-gauged with the helpers of tt_chain.hpp.
+// Index bookkeeping (unique halves, split heuristic) is host integer work,
 // every floating-point operation runs in the gfx950 kernels of kernels_tt.hip / kernels_dense.hip /
 // kernels_linalg.hip / kernels_rrlu*.hip.
 #include "tt.hpp"
@@ -12,16 +13,6 @@
 namespace t4a {
 
 namespace {
-void copy_core(DevCore& dst, const DevCore& src, hipStream_t st)
-{
-    dst.l = src.l;
-    dst.s = src.s;
-    dst.r = src.r;
-    dst.buf.reserve(std::max<size_t>(src.size(), 1));
-    if (src.size())
-        T4A_HIP(hipMemcpyAsync(dst.buf.get(), src.buf.get(), src.size() * sizeof(double), hipMemcpyDeviceToDevice, st));
-}
-
 void validate_chain(const std::vector<DevCore>& cores) // SimpleTensorTrain::new, tensortrain.rs:97-124
 {
     if (cores.empty()) return;
@@ -111,7 +102,7 @@ TensorTrain::TensorTrain(const std::vector<std::array<size_t, 3>>& dims3, const 
     if (off && !host_data) throw Error(T4A_GPU_NULL_POINTER, "core data is null");
     off = 0;
     for (auto& c : cores) {
-        c.buf.reserve(std::max<size_t>(c.size(), 1));
+        c.reshape(c.l, c.s, c.r);
         if (c.size())
             T4A_HIP(hipMemcpyAsync(c.buf.get(), host_data + off, c.size() * sizeof(double), hipMemcpyHostToDevice,
                                    eng.stream()));
@@ -124,8 +115,7 @@ TensorTrain::TensorTrain(const std::vector<DevCore>& src, hipStream_t src_stream
 {
     if (src_stream) T4A_HIP(hipStreamSynchronize(src_stream));
     validate_chain(src);
-    cores.resize(src.size());
-    for (size_t s = 0; s < src.size(); ++s) copy_core(cores[s], src[s], eng.stream());
+    cores = clone_cores(src, eng.stream());
     eng.sync();
 }
 
@@ -158,13 +148,7 @@ size_t TensorTrain::max_bond() const
 std::vector<double> TensorTrain::site_tensor_host(size_t site)
 {
     if (site >= cores.size()) throw Error(T4A_GPU_INVALID_ARGUMENT, "site out of range");
-    const DevCore& c = cores[site];
-    std::vector<double> h(c.size());
-    if (!h.empty()) {
-        T4A_HIP(hipMemcpyAsync(h.data(), c.buf.get(), h.size() * sizeof(double), hipMemcpyDeviceToHost, eng.stream()));
-        eng.sync();
-    }
-    return h;
+    return to_host(eng, cores[site].buf.get(), cores[site].size());
 }
 
 void TensorTrain::upload_descs()
@@ -277,9 +261,7 @@ size_t TensorTrain::factorize(const double* d_mat, int M, int N, CompressionMeth
         d_svds_.reserve(k);
         d_svdvt_.reserve((size_t)k * N);
         eng.svd(d_mat, M, N, d_svdu_.get(), d_svds_.get(), d_svdvt_.get());
-        std::vector<double> s(k);
-        T4A_HIP(hipMemcpyAsync(s.data(), d_svds_.get(), sizeof(double) * k, hipMemcpyDeviceToHost, eng.stream()));
-        eng.sync();
+        const std::vector<double> s = to_host(eng, d_svds_.get(), k);
         const double s_max = s[0];
         const double threshold = normalize_error ? tolerance * s_max : tolerance;
         size_t rank = 0;
@@ -319,9 +301,6 @@ void TensorTrain::compress(const CompressionOptions& opt) // compression.rs:375-
     const size_t n = cores.size();
     if (n <= 1) return;
     hipStream_t st = eng.stream();
-    auto gemm = [&](const double* A, int m, int k, const double* B, int nn, double* C) {
-        gemm_launch(gemm_desc(m, nn, k, A, m, B, k, C, m), st);
-    };
     // left-to-right: orthogonalise without truncation
     for (size_t ell = 0; ell + 1 < n; ++ell) {
         DevCore& c = cores[ell];
@@ -331,25 +310,9 @@ void TensorTrain::compress(const CompressionOptions& opt) // compression.rs:375-
         core_reshape_launch(c.buf.get(), L, S, R, 0, d_m1_.get(), st);
         const size_t rk = factorize(d_m1_.get(), L * S, R, opt.method, 0.0, true, 0, true);
         if (rk == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "compress: factorisation returned rank 0 (zero bond matrix)");
-        // current <- left factor (L*S x rk)
-        DevCore nc;
-        nc.l = L;
-        nc.s = S;
-        nc.r = rk;
-        nc.buf.reserve(std::max<size_t>(nc.size(), 1));
-        core_reshape_launch(eng.left(), L, S, (int)rk, 1, nc.buf.get(), st);
-        // next <- right factor (rk x R) * right matrix of next (R x S'*R')
-        const int NS = (int)nx.s, NR = (int)nx.r;
-        d_m1_.reserve(std::max<size_t>(nx.size(), 1));
-        core_reshape_launch(nx.buf.get(), (int)nx.l, NS, NR, 2, d_m1_.get(), st);
-        d_m2_.reserve(std::max<size_t>(rk * NS * NR, 1));
-        gemm(eng.right(), (int)rk, R, d_m1_.get(), NS * NR, d_m2_.get());
-        DevCore nn;
-        nn.l = rk;
-        nn.s = NS;
-        nn.r = NR;
-        nn.buf.reserve(std::max<size_t>(nn.size(), 1));
-        core_reshape_launch(d_m2_.get(), (int)rk, NS, NR, 3, nn.buf.get(), st);
+        // current <- left factor (L*S x rk); next <- right factor (rk x R) * right matrix of next (R x S'*R')
+        DevCore nc = core_from_left_factor(eng, c.l, c.s, rk);
+        DevCore nn = absorb_right_into_next(eng, rk, nx, d_m1_, d_m2_);
         eng.sync(); // the old buffers are released below
         cores[ell] = std::move(nc);
         cores[ell + 1] = std::move(nn);
@@ -364,23 +327,9 @@ void TensorTrain::compress(const CompressionOptions& opt) // compression.rs:375-
         const size_t rk = factorize(d_m1_.get(), L, S * R, opt.method, opt.tolerance, opt.normalize_error,
                                     opt.max_bond_dim, false);
         if (rk == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "compress: factorisation returned rank 0 (zero bond matrix)");
-        DevCore nc;
-        nc.l = rk;
-        nc.s = S;
-        nc.r = R;
-        nc.buf.reserve(std::max<size_t>(nc.size(), 1));
-        core_reshape_launch(eng.right(), (int)rk, S, R, 3, nc.buf.get(), st);
-        const int PL = (int)pv.l, PS = (int)pv.s;
-        d_m1_.reserve(std::max<size_t>(pv.size(), 1));
-        core_reshape_launch(pv.buf.get(), PL, PS, (int)pv.r, 0, d_m1_.get(), st);
-        d_m2_.reserve(std::max<size_t>((size_t)PL * PS * rk, 1));
-        gemm(d_m1_.get(), PL * PS, L, eng.left(), (int)rk, d_m2_.get());
-        DevCore np;
-        np.l = PL;
-        np.s = PS;
-        np.r = rk;
-        np.buf.reserve(std::max<size_t>(np.size(), 1));
-        core_reshape_launch(d_m2_.get(), PL, PS, (int)rk, 1, np.buf.get(), st);
+        // current <- right factor (rk x S*R); previous <- left matrix of previous (L'*S' x L) * left factor (L x rk)
+        DevCore nc = core_from_right_factor(eng, rk, c.s, c.r);
+        DevCore np = absorb_left_into_prev(eng, rk, pv, d_m1_, d_m2_);
         eng.sync();
         cores[ell] = std::move(nc);
         cores[ell - 1] = std::move(np);
@@ -511,11 +460,7 @@ std::unique_ptr<TensorTrain> TensorTrain::add(TensorTrain& other, bool subtract)
         const DevCore& y = other.cores[i];
         const double* yp = i == n - 1 ? other_last : y.buf.get();
         const bool first = i == 0, last = i == n - 1;
-        DevCore& t = out[i];
-        t.l = first ? 1 : x.l + y.l;
-        t.s = x.s;
-        t.r = last ? 1 : x.r + y.r;
-        t.buf.reserve(std::max<size_t>(t.size(), 1));
+        DevCore& t = out[i] = DevCore::make(first ? 1 : x.l + y.l, x.s, last ? 1 : x.r + y.r);
         if (first && last) {
             hipLaunchKernelGGL(tt_add2_kernel, dim3(blocks_for(t.size())), dim3(256), 0, st, x.buf.get(), yp, t.buf.get(), t.size());
             continue;
@@ -577,11 +522,7 @@ std::unique_ptr<TensorTrain> TensorTrain::reverse()
     std::vector<DevCore> out(n);
     for (size_t i = 0; i < n; ++i) {
         const DevCore& x = cores[n - 1 - i];
-        DevCore& t = out[i];
-        t.l = x.r;
-        t.s = x.s;
-        t.r = x.l;
-        t.buf.reserve(std::max<size_t>(t.size(), 1));
+        DevCore& t = out[i] = DevCore::make(x.r, x.s, x.l);
         TensorView v;
         v.d_data = x.buf.get();
         v.dims = {x.l, x.s, x.r};
@@ -617,11 +558,7 @@ std::unique_ptr<TensorTrain> TensorTrain::partial_sum(const std::vector<size_t>&
             std::swap(tprod, next);
             tc = t.r;
         } else {
-            DevCore c;
-            c.l = tr;
-            c.s = t.s;
-            c.r = t.r;
-            c.buf.reserve(std::max<size_t>(c.size(), 1));
+            DevCore c = DevCore::make(tr, t.s, t.r);
             seq_matmul_launch(tprod.get(), (int)tr, t.buf.get(), (int)t.l, c.buf.get(), (int)tr, tr, t.s * t.r, t.l, st);
             out.push_back(std::move(c));
             tr = tc = t.r;
@@ -631,9 +568,7 @@ std::unique_ptr<TensorTrain> TensorTrain::partial_sum(const std::vector<size_t>&
         }
     }
     if (out.empty()) { // everything summed: a one-site train wrapping the scalar
-        DevCore c;
-        c.l = c.s = c.r = 1;
-        c.buf.reserve(1);
+        DevCore c = DevCore::make(1, 1, 1);
         T4A_HIP(hipMemcpyAsync(c.buf.get(), tprod.get(), sizeof(double), hipMemcpyDeviceToDevice, st));
         out.push_back(std::move(c));
     } else { // the trailing product goes into the last kept core

@@ -7,15 +7,9 @@
 #include <memory>
 #include <vector>
 
-#include "engine.hpp"
+#include "tt_chain.hpp"
 
 namespace t4a {
-
-struct DevCore {
-    DevBuf<double> buf;
-    size_t l = 0, s = 0, r = 0;
-    size_t size() const { return l * s * r; }
-};
 
 enum class CompressionMethod : int { LU = 0, CI = 1, SVD = 2 }; // compression.rs:40-52
 

@@ -2,7 +2,8 @@
 // tt_canonical.hpp).  The sweeps are host-paced where the reference's bond dimension is data dependent (the rank of the rrLU, read
 // back per site like TensorTrain::compress does); the Vidal right sweep knows its bonds in advance (min(L, S R), no truncation) and
 // runs without a host turn of its own.  Every floating-point operation runs in the gfx950 kernels of kernels_rrlu*.hip,
-// kernels_linalg.hip, kernels_dense.hip and kernels_tt.hip.
+// kernels_linalg.hip, kernels_dense.hip and kernels_tt.hip.  Cores are made, copied and read back with the helpers of tt_chain.hpp; the
+// LU gauge steps stay here (they skip the reshape of the absorption helpers there and call the rrLU with their own options).
 #include "tt_canonical.hpp"
 
 #include <algorithm>
@@ -10,29 +11,6 @@
 namespace t4a {
 
 namespace {
-
-void copy_cores(std::vector<DevCore>& dst, const std::vector<DevCore>& src, hipStream_t st)
-{
-    dst.resize(src.size());
-    for (size_t i = 0; i < src.size(); ++i) {
-        dst[i].l = src[i].l;
-        dst[i].s = src[i].s;
-        dst[i].r = src[i].r;
-        dst[i].buf.reserve(std::max<size_t>(src[i].size(), 1));
-        if (src[i].size())
-            T4A_HIP(hipMemcpyAsync(dst[i].buf.get(), src[i].buf.get(), src[i].size() * sizeof(double), hipMemcpyDeviceToDevice, st));
-    }
-}
-
-DevCore make_core(size_t l, size_t s, size_t r)
-{
-    DevCore c;
-    c.l = l;
-    c.s = s;
-    c.r = r;
-    c.buf.reserve(std::max<size_t>(c.size(), 1));
-    return c;
-}
 
 void retire(GaugeScratch& w, DevCore& c) { w.retired.push_back(std::move(c.buf)); }
 
@@ -71,13 +49,13 @@ void vidal_right_step(Engine& eng, std::vector<DevCore>& cores, size_t i, DevBuf
     core_reshape_launch(c.buf.get(), (int)L, (int)S, (int)R, 2, w.mat.get(), st);
     eng.svd(w.mat.get(), (int)L, (int)(S * R), w.u.get(), sv.get(), w.vt.get());
     sv_len = k;
-    DevCore nc = make_core(k, S, R); // V^T back in core layout
+    DevCore nc = DevCore::make(k, S, R); // V^T back in core layout
     core_reshape_launch(w.vt.get(), (int)k, (int)S, (int)R, 3, nc.buf.get(), st);
     // prev <- prev * (U diag(s)): prev in memory is already the (PL PS) x L matrix the product needs, and its output the new core
     w.fac.reserve(L * k);
     col_scale_launch(w.u.get(), (int)L, (int)L, (int)k, sv.get(), w.fac.get(), (int)L, st);
     const size_t PM = pv.l * pv.s;
-    DevCore np = make_core(pv.l, pv.s, k);
+    DevCore np = DevCore::make(pv.l, pv.s, k);
     if (PM) gemm_launch(gemm_desc((int)PM, (int)k, (int)L, pv.buf.get(), (int)PM, w.fac.get(), (int)L, np.buf.get(), (int)PM), st);
     retire(w, c);
     retire(w, pv);
@@ -132,7 +110,7 @@ std::vector<DevCore> times_right_vectors(Engine& eng, const std::vector<DevCore>
     std::vector<DevCore> out(n);
     std::vector<TtScaleDesc> descs;
     for (size_t i = 0; i < n; ++i) {
-        out[i] = make_core(cores[i].l, cores[i].s, cores[i].r);
+        out[i] = DevCore::make(cores[i].l, cores[i].s, cores[i].r);
         TtScaleDesc d = scale_desc(cores[i].buf.get(), out[i].buf.get(), cores[i].l, cores[i].s, cores[i].r);
         if (i + 1 < n) {
             d.rop = TT_SCALE_MUL;
@@ -144,16 +122,6 @@ std::vector<DevCore> times_right_vectors(Engine& eng, const std::vector<DevCore>
     DevBuf<TtScaleDesc> table;
     bond_scale(eng, descs, table);
     return out;
-}
-
-std::vector<double> download(Engine& eng, const double* d_src, size_t count)
-{
-    std::vector<double> h(count);
-    if (count) {
-        T4A_HIP(hipMemcpyAsync(h.data(), d_src, count * sizeof(double), hipMemcpyDeviceToHost, eng.stream()));
-        eng.sync();
-    }
-    return h;
 }
 
 void upload_vector(Engine& eng, DevBuf<double>& dst, const double* host, size_t len)
@@ -175,7 +143,7 @@ std::string two_site_message(size_t i, size_t n) // canonical.rs:379-387, vidal.
 void replace_core(Engine& eng, DevCore& dst, const size_t dims[3], const double* host, GaugeScratch& w)
 {
     check_core_dims(dims);
-    DevCore c = make_core(dims[0], dims[1], dims[2]);
+    DevCore c = DevCore::make(dims[0], dims[1], dims[2]);
     if (c.size()) {
         if (!host) throw Error(T4A_GPU_NULL_POINTER, "tensor data is null");
         T4A_HIP(hipMemcpyAsync(c.buf.get(), host, c.size() * sizeof(double), hipMemcpyHostToDevice, eng.stream()));
@@ -195,12 +163,12 @@ void gauge_left_step(Engine& eng, std::vector<DevCore>& cores, size_t i, GaugeSc
     w.mat.reserve(std::max<size_t>(c.size(), 1));
     core_reshape_launch(c.buf.get(), L, S, R, 0, w.mat.get(), st); // rows l * S + s (canonical.rs:39-55)
     const size_t rk = lu_for_qr(eng, w.mat.get(), L * S, R);
-    DevCore nc = make_core(c.l, c.s, rk);
+    DevCore nc = DevCore::make(c.l, c.s, rk);
     core_reshape_launch(eng.left(), L, S, (int)rk, 1, nc.buf.get(), st);
     // next <- right(true) (rk x R) * next: a core in memory is the column-major R x (S' R') matrix and the product's output the new core
     // (the reference's column order s * R' + r of tensor3_to_right_matrix only permutes the columns of both sides of the product)
     const size_t cols = nx.s * nx.r;
-    DevCore nn = make_core(rk, nx.s, nx.r);
+    DevCore nn = DevCore::make(rk, nx.s, nx.r);
     if (cols) gemm_launch(gemm_desc((int)rk, (int)cols, R, eng.right(), (int)rk, nx.buf.get(), R, nn.buf.get(), (int)rk), st);
     retire(w, c);
     retire(w, nx);
@@ -224,14 +192,14 @@ void gauge_right_step(Engine& eng, std::vector<DevCore>& cores, size_t i, GaugeS
     }
     const size_t rk = lu_for_qr(eng, w.mat.get(), (int)(S * R), (int)L);
     // Q = left(true)^T: the (R, S, rk) block reversed to (rk, S, R) is the new core
-    DevCore nc = make_core(rk, S, R);
+    DevCore nc = DevCore::make(rk, S, R);
     {
         const size_t dims[3] = {R, S, rk}, perm[3] = {2, 1, 0};
         permute_launch(eng.left(), dims, perm, 3, nc.buf.get(), st);
     }
     // prev <- prev (PL PS x L) * right(true)^T (L x rk), again in core layout on both sides
     const size_t PM = pv.l * pv.s;
-    DevCore np = make_core(pv.l, pv.s, rk);
+    DevCore np = DevCore::make(pv.l, pv.s, rk);
     if (PM) {
         GemmDesc g = gemm_desc((int)PM, (int)rk, (int)L, pv.buf.get(), (int)PM, eng.right(), (int)rk, np.buf.get(), (int)PM);
         g.transB = 1;
@@ -270,7 +238,7 @@ SiteTrain::SiteTrain(const std::vector<DevCore>& src, hipStream_t src_stream, si
         if (src[i].r != src[i + 1].l)
             throw Error(T4A_GPU_INVALID_ARGUMENT, "Dimension mismatch: tensor at site " + std::to_string(i) + " has incompatible dimensions");
     if (src_stream) T4A_HIP(hipStreamSynchronize(src_stream));
-    copy_cores(cores, src, eng.stream());
+    cores = clone_cores(src, eng.stream());
     const size_t n = cores.size();
     if (n > 1) { // canonicalize (canonical.rs:172-188)
         for (size_t i = 0; i < center_; ++i) gauge_left_step(eng, cores, i, w_);
@@ -340,7 +308,7 @@ VidalTrain::VidalTrain(const std::vector<DevCore>& src, hipStream_t src_stream, 
     check_partition(n, end);
     eng = std::make_unique<Engine>();
     if (src_stream) T4A_HIP(hipStreamSynchronize(src_stream));
-    copy_cores(cores, src, eng->stream());
+    cores = clone_cores(src, eng->stream());
     sv.resize(n - 1);
     sv_len.assign(n - 1, 0);
     part_start = start;
@@ -387,7 +355,7 @@ VidalTrain::VidalTrain(const std::vector<std::array<size_t, 3>>& dims3, const do
     cores.resize(n);
     size_t off = 0;
     for (size_t i = 0; i < n; ++i) {
-        cores[i] = make_core(dims3[i][0], dims3[i][1], dims3[i][2]);
+        cores[i] = DevCore::make(dims3[i][0], dims3[i][1], dims3[i][2]);
         if (cores[i].size())
             T4A_HIP(hipMemcpyAsync(cores[i].buf.get(), cores_host + off, cores[i].size() * sizeof(double), hipMemcpyHostToDevice, eng->stream()));
         off += cores[i].size();
@@ -410,7 +378,7 @@ std::vector<double> VidalTrain::singular_values_host(size_t bond)
 {
     if (bond >= sv.size())
         throw Error(T4A_GPU_INVALID_ARGUMENT, "bond " + std::to_string(bond) + " is out of range for " + std::to_string(sv.size()) + " singular value vectors");
-    return download(*eng, sv[bond].get(), sv_len[bond]);
+    return to_host(*eng, sv[bond].get(), sv_len[bond]);
 }
 
 void VidalTrain::set_singular_values(size_t bond, const double* host, size_t len)
@@ -453,7 +421,7 @@ InverseTrain::InverseTrain(VidalTrain& vidal)
     // first core: right factor only; middle cores: (val * sv[i-1][l]) * sv[i][r]; last core: left factor only (vidal.rs:563-645)
     for (size_t i = 0; i < n; ++i) {
         const DevCore& c = vidal.cores[i];
-        cores[i] = make_core(c.l, c.s, c.r);
+        cores[i] = DevCore::make(c.l, c.s, c.r);
         TtScaleDesc d = scale_desc(c.buf.get(), cores[i].buf.get(), c.l, c.s, c.r);
         if (i > 0) {
             d.lop = TT_SCALE_MUL;
@@ -483,7 +451,7 @@ std::vector<double> InverseTrain::inverse_singular_values_host(size_t bond)
 {
     if (bond >= inv.size())
         throw Error(T4A_GPU_INVALID_ARGUMENT, "bond " + std::to_string(bond) + " is out of range for " + std::to_string(inv.size()) + " singular value vectors");
-    return download(*eng, inv[bond].get(), inv_len[bond]);
+    return to_host(*eng, inv[bond].get(), inv_len[bond]);
 }
 
 void InverseTrain::set_two_site_tensors(size_t i, const size_t d1[3], const double* t1, const double* inv_sv, size_t n_inv, const size_t d2[3],

@@ -190,6 +190,23 @@ def test_special_cases():
     assert r.residual is None and not r.converged and r.sweeps == 1
 
 
+def test_guess_with_bonds_the_chain_cannot_carry():
+    """The QR sweeps to centre 2 meet (l s) < r from the left and l > (s r) from the right: the bonds [4, 6, 6, 4] of the guess shrink
+    to [2, 4, 4, 2] before the first local solve.  a0 = 2 ||A||_2 as in make_case, so the same conditioning argument holds."""
+    n, d = 5, 2
+    ops = ln.random_tensors([1, 2, 2, 2, 2, 1], d, d, ln.SEED ^ 0x51)
+    rhs = ln.random_state([1, 2, 2, 2, 2, 1], d, ln.SEED ^ 0x52)
+    init = ln.random_state([1, 4, 6, 6, 4, 1], d, ln.SEED ^ 0x53)
+    am, bv = ln.np_operator_full(ops), ln.np_state_full(rhs)
+    a0 = 2.0 * float(np.linalg.norm(am, 2))
+    r = square_linsolve(MPO(ops), SimpleTensorTrain(rhs), SimpleTensorTrain(init), 2, device_options(a0, 16))
+    assert r.converged and r.residual < 1e-8
+    x, again = dense_checks(ops, rhs, a0, 1.0, r)
+    want = np.linalg.solve(a0 * np.eye(d ** n) + am, bv)
+    assert np.linalg.norm(ln.np_state_full(x) - want) <= 1e-6 * np.linalg.norm(want)
+    assert all(got <= most for got, most in zip(r.solution.link_dims(), [2, 4, 4, 2]))
+
+
 def test_shape_errors_through_the_handles():
     ops, rhs, init, a0, cap = make_case("n5")
     op, b, x0 = MPO(ops), SimpleTensorTrain(rhs), SimpleTensorTrain(init)
