@@ -1274,6 +1274,84 @@ t4a_gpu_status t4a_gpu_linsolve_gmres_dense(const double* H, size_t n, const dou
                                             int32_t mode, size_t restart_dim, size_t max_restarts, double* x, size_t* iterations,
                                             double* residual, int32_t* converged);
 
+/* =====================================================================================
+ * Two-site DMRG: the lowest eigenpair of an MPO H over tensor trains resident on the device
+ * tensor4all-treetn/src/dmrg/mod.rs (dmrg, dmrg_with_treetn_operator, DmrgOptions, DmrgResult) on the Hermitian Lanczos of
+ * tensor4all-core/src/krylov.rs:517-634 (hermitian_lanczos_lowest_eigenpair, helpers :2500-2675), restated for a chain.
+ * Scope: that of t4a_gpu_square_linsolve — a chain, f64, one site index per node, V_in = V_out (every site of H has s1 == s2 == the
+ * state's site dimension; the dimensions may differ from site to site).  Trees, index mappings, complex scalars and nsite != 2 are
+ * not mirrored; nsite = 1 is refused as the reference refuses it.
+ * `init` is canonicalised onto `center` and swept exactly as t4a_gpu_square_linsolve does it: bonds center .. n-2 to the right,
+ * n-2 .. 0 to the left, 0 .. center-1 to the right, the second node of a step the new centre.  One step at bond (i, i+1): theta_0 =
+ * x_i x_{i+1}, the half operators of the projected operator, Lanczos for its lowest eigenpair from theta_0, the SVD split of the
+ * unit-norm Ritz vector with max_bond_dim and the policy of t4a_gpu_tensor_svd (none: its default), the singular values into the new
+ * centre (no renormalisation after truncation), then the environment of the side left behind from this step's half operator.
+ * Lanczos: v_0 = theta_0 / |theta_0| (|theta_0| <= breakdown_tol: INVALID_ARGUMENT); step j: w = H v_j, two orthogonalisation passes
+ * against v_0 .. v_j, the column of the projected matrix is pass 1 plus pass 2, beta = |w|; the (j+1) x (j+1) projected matrix is the
+ * full upper-Hessenberg data, checked entry pair by entry pair with scale max(1, |a_ij|, |a_ji|) against hermitian_tol
+ * (INVALID_ARGUMENT "projected operator is not Hermitian"), symmetrised, and its lowest eigenpair taken on the host by a cyclic
+ * Jacobi; estimate = beta |c_j|, threshold = max(atol, rtol max(1, |lambda|)); on estimate <= threshold or beta <= breakdown_tol the
+ * Ritz vector sum_i c_i v_i and its true residual |H v - lambda v| are formed on the device and the solve returns if that residual
+ * is below the threshold or on breakdown; after max_iter steps the last Ritz state is returned.  Non-convergence is a flag, never
+ * an error.  The host reads one norm per solve, j + 2 doubles per step and three per finalise.  Deviation: both passes are classical
+ * Gram-Schmidt (all coefficients of a pass from one launch), the reference's are modified Gram-Schmidt.
+ * With has_energy_tol the sweeps stop when the last step's Ritz value moved by <= energy_tol against the sweep before (converged = 1;
+ * the first sweep only records); converged is 0 otherwise.  *energy is the Rayleigh quotient <theta|H theta> / <theta|theta> at the
+ * region (center, center + 1), or (center - 1, center) when center == n - 1, through the projected operator; a denominator <=
+ * real_scalar_tol is INVALID_ARGUMENT ("DMRG Rayleigh quotient denominator is zero").  *max_residual_norm is the maximum of the
+ * steps' true residuals, *local_updates the number of steps.
+ * Memory of a bond step: W (M^2 + N^2 + M N) + (max_iter + 2) M N doubles, M = chi_l d_i, N = d_{i+1} chi_r.
+ * INVALID_ARGUMENT with a message, before the device is touched: nsite != 2, nsweeps == 0, max_bond_dim == 0 when set, energy_tol or
+ * real_scalar_tol negative or non-finite, lanczos.max_iter == 0 or above 8191, a negative or non-finite rtol, atol, breakdown_tol or
+ * hermitian_tol, center >= n, lengths differ, a site of H that is not square or does not match the state, fewer than two sites
+ * ("two-site DMRG requires at least one state edge"), a work buffer of a bond step above INT_MAX elements (the message names the bond).
+ * ===================================================================================== */
+typedef struct {
+    size_t max_iter;
+    double rtol, atol, breakdown_tol, hermitian_tol;
+} t4a_gpu_lanczos_options;
+typedef struct {
+    size_t nsite;
+    size_t nsweeps;
+    int32_t has_max_bond_dim; /* 0 <=> None */
+    size_t max_bond_dim;
+    int32_t has_svd_policy;   /* 0 <=> None: the default policy of t4a_gpu_tensor_svd */
+    t4a_gpu_svd_policy svd_policy;
+    t4a_gpu_lanczos_options lanczos;
+    int32_t has_energy_tol;
+    double energy_tol;
+    double real_scalar_tol;
+} t4a_gpu_dmrg_options;
+typedef struct {
+    size_t local_solves;  /* bond steps */
+    size_t lanczos_steps; /* over all local solves */
+    size_t apply_calls;   /* projected applies, those of the true residuals included */
+} t4a_gpu_dmrg_stats;
+/* DmrgOptions::default(): 2, 5, None, None, (64, 1e-10, 0, 1e-14, 1e-10), None, 1e-10 */
+t4a_gpu_status t4a_gpu_dmrg_options_default(t4a_gpu_dmrg_options* out);
+/* The shape checks of t4a_gpu_dmrg on plain dimension lists: op_dims4 (left, s1, s2, right) and state_dims3 (left, site, right) per
+ * site.  A pure host function, usable without a device. */
+t4a_gpu_status t4a_gpu_dmrg_check_shapes(const size_t* op_dims4, size_t n_op, const size_t* state_dims3, size_t n_state, size_t center,
+                                         size_t max_iter);
+t4a_gpu_status t4a_gpu_dmrg(const t4a_gpu_mpo* op, const t4a_gpu_tt* init, size_t center, const t4a_gpu_dmrg_options* options,
+                            t4a_gpu_tt** state, double* energy, size_t* sweeps_completed, size_t* local_updates, int32_t* converged,
+                            double* max_residual_norm, t4a_gpu_dmrg_stats* stats /* may be NULL */);
+/* The Rayleigh quotient of t4a_gpu_dmrg for any state: a copy is canonicalised onto `center` (real_scalar_tol = 1e-10) */
+t4a_gpu_status t4a_gpu_dmrg_energy(const t4a_gpu_mpo* op, const t4a_gpu_tt* state, size_t center, double* out);
+/* Test hooks.  _lanczos_dense: the solver the sweeps run, on a dense n x n matrix H (column-major) applied on the device, from v0;
+ *   eigenvector receives n doubles.
+ * _krylov_combine: out = sum_i coef[i] basis[:, i] (basis len x nb column-major, i ascending) and *norm2 = |out|^2, as a finalise
+ *   launches it.
+ * _eig_residual: r = hv - lambda v (r may be NULL) and sums3 = (|r|^2, <v, hv>, <v, v>) from the launch pair of a finalise.
+ * Probe (tools/probe_dmrg.py): _lanczos_time_finalise: device milliseconds, events around `reps` launches behind a warm-up launch, of
+ *   krylov_combine, eig_residual and the finishing launch with nb basis vectors of length len. */
+t4a_gpu_status t4a_gpu_lanczos_dense(const double* H, size_t n, const double* v0, const t4a_gpu_lanczos_options* options, double* eigenvalue,
+                                     double* eigenvector, size_t* iterations, double* residual_norm, int32_t* converged);
+t4a_gpu_status t4a_gpu_krylov_combine(const double* basis, size_t len, size_t nb, const double* coef, double* out, double* norm2);
+t4a_gpu_status t4a_gpu_eig_residual(const double* v, const double* hv, size_t len, double lambda, double* r /* may be NULL */,
+                                    double* sums3);
+t4a_gpu_status t4a_gpu_lanczos_time_finalise(size_t len, size_t nb, size_t reps, double* ms /* [3] */);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

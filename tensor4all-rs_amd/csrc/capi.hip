@@ -19,6 +19,7 @@
 #include "contraction.hpp"
 #include "quanticstransform.hpp"
 #include "tt_canonical.hpp"
+#include "dmrg.hpp"
 #include "linsolve.hpp"
 
 struct t4a_gpu_tci2 {
@@ -4337,6 +4338,167 @@ t4a_gpu_status t4a_gpu_linsolve_gmres_dense(const double* H, size_t n, const dou
         *iterations = r.iterations;
         *residual = r.residual;
         *converged = r.converged;
+    });
+}
+
+// ---- two-site DMRG: the lowest eigenpair of an MPO by sweeps with a local Lanczos (dmrg.hpp) ----
+t4a_gpu_status t4a_gpu_dmrg_options_default(t4a_gpu_dmrg_options* out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(out);
+        const DmrgOptions d;
+        *out = t4a_gpu_dmrg_options{};
+        out->nsite = d.nsite;
+        out->nsweeps = d.nsweeps;
+        out->has_max_bond_dim = d.has_max_bond_dim;
+        out->max_bond_dim = d.max_bond_dim;
+        out->has_svd_policy = d.has_svd_policy;
+        out->svd_policy = t4a_gpu_svd_policy{d.svd_policy.threshold, d.svd_policy.scale, d.svd_policy.measure, d.svd_policy.rule};
+        out->lanczos = t4a_gpu_lanczos_options{d.lanczos.max_iter, d.lanczos.rtol, d.lanczos.atol, d.lanczos.breakdown_tol, d.lanczos.hermitian_tol};
+        out->has_energy_tol = d.has_energy_tol;
+        out->energy_tol = d.energy_tol;
+        out->real_scalar_tol = d.real_scalar_tol;
+    });
+}
+
+extern "C++" {
+static LanczosOptions convert_lanczos_options(const t4a_gpu_lanczos_options& p)
+{
+    LanczosOptions o;
+    o.max_iter = p.max_iter;
+    o.rtol = p.rtol;
+    o.atol = p.atol;
+    o.breakdown_tol = p.breakdown_tol;
+    o.hermitian_tol = p.hermitian_tol;
+    return o;
+}
+static DmrgOptions convert_dmrg_options(const t4a_gpu_dmrg_options* p)
+{
+    DmrgOptions o;
+    o.nsite = p->nsite;
+    o.nsweeps = p->nsweeps;
+    o.has_max_bond_dim = p->has_max_bond_dim != 0;
+    o.max_bond_dim = p->max_bond_dim;
+    o.has_svd_policy = p->has_svd_policy != 0;
+    if (o.has_svd_policy) o.svd_policy = SvdPolicy{p->svd_policy.threshold, p->svd_policy.scale, p->svd_policy.measure, p->svd_policy.rule};
+    o.lanczos = convert_lanczos_options(p->lanczos);
+    o.has_energy_tol = p->has_energy_tol != 0;
+    o.energy_tol = p->energy_tol;
+    o.real_scalar_tol = p->real_scalar_tol;
+    o.validate();
+    return o;
+}
+}
+
+t4a_gpu_status t4a_gpu_dmrg_check_shapes(const size_t* op_dims4, size_t n_op, const size_t* state_dims3, size_t n_state, size_t center,
+                                         size_t max_iter)
+{
+    return guarded([&] {
+        if (n_op) T4A_REQUIRE_PTR(op_dims4);
+        if (n_state) T4A_REQUIRE_PTR(state_dims3);
+        LanczosOptions lo;
+        lo.max_iter = max_iter;
+        lo.validate();
+        std::vector<std::array<size_t, 4>> op(n_op);
+        for (size_t i = 0; i < n_op; ++i) op[i] = {op_dims4[4 * i], op_dims4[4 * i + 1], op_dims4[4 * i + 2], op_dims4[4 * i + 3]};
+        dmrg_validate_shapes(op, dims3_list(state_dims3, n_state), center, max_iter);
+    });
+}
+
+t4a_gpu_status t4a_gpu_dmrg(const t4a_gpu_mpo* op, const t4a_gpu_tt* init, size_t center, const t4a_gpu_dmrg_options* options,
+                            t4a_gpu_tt** state, double* energy, size_t* sweeps_completed, size_t* local_updates, int32_t* converged,
+                            double* max_residual_norm, t4a_gpu_dmrg_stats* stats)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(state);
+        *state = nullptr;
+        T4A_REQUIRE_PTR(options);
+        const DmrgOptions o = convert_dmrg_options(options); // the options are checked on the host before an operand is looked at
+        T4A_REQUIRE_PTR(op);
+        T4A_REQUIRE_PTR(init);
+        T4A_REQUIRE_PTR(energy);
+        T4A_REQUIRE_PTR(sweeps_completed);
+        T4A_REQUIRE_PTR(local_updates);
+        T4A_REQUIRE_PTR(converged);
+        T4A_REQUIRE_PTR(max_residual_norm);
+        DmrgResult r = dmrg(*op->impl, const_cast<t4a_gpu_tt*>(init)->impl, center, o);
+        *state = new t4a_gpu_tt(r.state->cores, r.state->eng.stream());
+        *energy = r.energy;
+        *sweeps_completed = r.sweeps_completed;
+        *local_updates = r.local_updates;
+        *converged = r.converged;
+        *max_residual_norm = r.max_residual_norm;
+        if (stats) *stats = t4a_gpu_dmrg_stats{r.stats.local_solves, r.stats.lanczos_steps, r.stats.apply_calls};
+    });
+}
+
+t4a_gpu_status t4a_gpu_dmrg_energy(const t4a_gpu_mpo* op, const t4a_gpu_tt* state, size_t center, double* out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(op);
+        T4A_REQUIRE_PTR(state);
+        T4A_REQUIRE_PTR(out);
+        *out = dmrg_energy(*op->impl, const_cast<t4a_gpu_tt*>(state)->impl, center);
+    });
+}
+
+t4a_gpu_status t4a_gpu_lanczos_dense(const double* H, size_t n, const double* v0, const t4a_gpu_lanczos_options* options, double* eigenvalue,
+                                     double* eigenvector, size_t* iterations, double* residual_norm, int32_t* converged)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(options);
+        const LanczosOptions o = convert_lanczos_options(*options);
+        o.validate();
+        if (n == 0 || n > 46340 || (unsigned long long)n * (o.max_iter + 1) > (unsigned long long)INT_MAX)
+            throw Error(T4A_GPU_INVALID_ARGUMENT, "lanczos_dense: n must be positive and the matrix and the basis must hold at most INT_MAX elements");
+        T4A_REQUIRE_PTR(H);
+        T4A_REQUIRE_PTR(v0);
+        T4A_REQUIRE_PTR(eigenvalue);
+        T4A_REQUIRE_PTR(eigenvector);
+        T4A_REQUIRE_PTR(iterations);
+        T4A_REQUIRE_PTR(residual_norm);
+        T4A_REQUIRE_PTR(converged);
+        require_device();
+        const LanczosResult r = lanczos_dense(H, n, v0, o, eigenvector);
+        *eigenvalue = r.eigenvalue;
+        *iterations = r.iterations;
+        *residual_norm = r.residual_norm;
+        *converged = r.converged;
+    });
+}
+
+t4a_gpu_status t4a_gpu_krylov_combine(const double* basis, size_t len, size_t nb, const double* coef, double* out, double* norm2)
+{
+    return guarded([&] {
+        if (len == 0 || nb == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "krylov_combine: len and nb must be positive");
+        if (nb > LINSOLVE_RESTART_DIM_MAX || (unsigned long long)len * nb > (unsigned long long)INT_MAX)
+            throw Error(T4A_GPU_INVALID_ARGUMENT, "krylov_combine: nb above " + std::to_string(LINSOLVE_RESTART_DIM_MAX) + " or a basis of more than INT_MAX elements");
+        T4A_REQUIRE_PTR(basis);
+        T4A_REQUIRE_PTR(coef);
+        T4A_REQUIRE_PTR(out);
+        T4A_REQUIRE_PTR(norm2);
+        require_device();
+        krylov_combine_host(basis, len, nb, coef, out, norm2);
+    });
+}
+
+t4a_gpu_status t4a_gpu_eig_residual(const double* v, const double* hv, size_t len, double lambda, double* r, double* sums3)
+{
+    return guarded([&] {
+        if (len == 0 || len > (size_t)INT_MAX) throw Error(T4A_GPU_INVALID_ARGUMENT, "eig_residual: len must be positive and at most INT_MAX");
+        T4A_REQUIRE_PTR(v);
+        T4A_REQUIRE_PTR(hv);
+        T4A_REQUIRE_PTR(sums3);
+        require_device();
+        eig_residual_host(v, hv, len, lambda, r, sums3);
+    });
+}
+
+t4a_gpu_status t4a_gpu_lanczos_time_finalise(size_t len, size_t nb, size_t reps, double* ms)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(ms);
+        lanczos_time_finalise(len, nb, reps, ms); // checks its arguments, then the device
     });
 }
 

@@ -8,6 +8,7 @@
 // Every reduction has a fixed partition that depends on the vector length alone: thread t of workgroup g owns the elements
 // g*256 + t + k*(256*G), summed k-ascending; lanes are folded by a fixed shuffle tree, the four waves and then the workgroups in
 // ascending order.  No atomics; multiply and add are rounded separately (-ffp-contract=off): two runs give the same bits.
+#include "krylov_reduce.hpp"
 #include "linsolve.hpp"
 
 #include <algorithm>
@@ -16,25 +17,8 @@ namespace t4a {
 
 namespace {
 
-constexpr int GS_THREADS = 256;
 constexpr int GS_PER_THREAD = 4;  // elements per thread the grid is sized for
 constexpr int GS_BATCH = 32;      // basis vectors per barrier of gs_dots
-
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = v + __shfl_down(v, off, 64);
-    return v; // lane 0
-}
-
-// sum of `v` over the workgroup, valid in thread 0
-__device__ __forceinline__ double block_sum(double v, double* s4)
-{
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) s4[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((s4[0] + s4[1]) + s4[2]) + s4[3];
-}
 
 // HL[(beta + chi s1) + M wm, (alpha + chi t1)] = sum_wl L[beta, wl, alpha] A[wl, s1, t1, wm],  M = chi d, leading dimension W M
 __global__ void __launch_bounds__(256) linsolve_hl_kernel(const double* __restrict__ L, const double* __restrict__ A, double* __restrict__ HL,

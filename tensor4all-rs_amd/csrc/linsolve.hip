@@ -26,13 +26,9 @@ bool above_int_max(std::initializer_list<size_t> factors)
     return false;
 }
 
-// the buffers of the bond step (i, i + 1): HL, HR, T and the Krylov basis
 void check_step_dims(size_t i, size_t chi_l, size_t d1, size_t d2, size_t chi_r, size_t W, size_t restart_dim)
 {
-    const size_t M = chi_l * d1, N = d2 * chi_r;
-    if (above_int_max({W, M, M}) || above_int_max({W, N, N}) || above_int_max({W, M, N}) || above_int_max({restart_dim + 1, M, N}))
-        throw Error(T4A_GPU_INVALID_ARGUMENT, "square_linsolve: a work buffer of the bond step (" + std::to_string(i) + ", " + std::to_string(i + 1) +
-                                                  ") holds more than INT_MAX elements");
+    check_bond_step_dims("square_linsolve", i, chi_l, d1, d2, chi_r, W, restart_dim);
 }
 
 double host_norm(Engine& eng, const DevCore& c)
@@ -63,6 +59,14 @@ std::vector<std::array<size_t, 3>> dims3_of(const std::vector<DevCore>& cores)
 } // namespace
 
 // ------------------------------------------------------------------------------------------------ options and shapes
+void check_bond_step_dims(const char* who, size_t i, size_t chi_l, size_t d1, size_t d2, size_t chi_r, size_t W, size_t basis_dim)
+{
+    const size_t M = chi_l * d1, N = d2 * chi_r;
+    if (above_int_max({W, M, M}) || above_int_max({W, N, N}) || above_int_max({W, M, N}) || above_int_max({basis_dim + 1, M, N}))
+        throw Error(T4A_GPU_INVALID_ARGUMENT, std::string(who) + ": a work buffer of the bond step (" + std::to_string(i) + ", " + std::to_string(i + 1) +
+                                                  ") holds more than INT_MAX elements");
+}
+
 void LinsolveOptions::validate() const
 {
     if (gmres_restart_dim == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "LinsolveOptions::gmres_restart_dim must be greater than zero");
@@ -107,29 +111,25 @@ void linsolve_validate_shapes(const std::vector<std::array<size_t, 4>>& op, cons
 }
 
 // ------------------------------------------------------------------------------------------------ GMRES
-void Gmres::reserve(size_t len, size_t restart_dim)
+void KrylovOrth::reserve(size_t nb_max)
 {
-    const size_t m = restart_dim;
-    grow(eng_, basis_, len * (m + 1));
-    grow(eng_, ax_, len);
-    grow(eng_, part_, (m + 1) * GS_MAX_WORKGROUPS);
-    grow(eng_, npart_, GS_MAX_WORKGROUPS);
-    grow(eng_, hcol_, m + 3); // the column of H (m + 2) and one norm
-    grow(eng_, coef_, m + 1);
+    grow(eng_, part_, std::max<size_t>(nb_max, 1) * GS_MAX_WORKGROUPS);
+    grow(eng_, npart_, 3 * GS_MAX_WORKGROUPS);
+    grow(eng_, scal_, 4);
 }
 
-double Gmres::norm(const double* d_w, size_t len)
+double KrylovOrth::norm(const double* d_w, size_t len, double* d_out)
 {
     hipStream_t st = eng_.stream();
     double v = 0.0;
     gs_norm2_launch(d_w, len, npart_.get(), st);
-    gs_normalize_launch(d_w, len, npart_.get(), nullptr, hcol_.get(), st);
-    T4A_HIP(hipMemcpyAsync(&v, hcol_.get(), sizeof(double), hipMemcpyDeviceToHost, st));
+    gs_normalize_launch(d_w, len, npart_.get(), d_out, scal_.get(), st);
+    T4A_HIP(hipMemcpyAsync(&v, scal_.get(), sizeof(double), hipMemcpyDeviceToHost, st));
     eng_.sync();
     return v;
 }
 
-void Gmres::orth(const double* d_V, size_t ld, int nb, double* d_w, size_t len, double* d_hcol, double* d_hpass)
+void KrylovOrth::orth(const double* d_V, size_t ld, int nb, double* d_w, size_t len, double* d_hcol, double* d_hpass)
 {
     hipStream_t st = eng_.stream();
     const int G = gs_workgroups(len);
@@ -138,6 +138,16 @@ void Gmres::orth(const double* d_V, size_t ld, int nb, double* d_w, size_t len, 
     gs_dots_launch(d_V, ld, nb, d_w, len, part_.get(), st);
     gs_update_launch(d_V, ld, nb, d_w, len, part_.get(), G, d_hcol, false, d_hpass ? d_hpass + nb : nullptr, npart_.get(), st);
     gs_normalize_launch(d_w, len, npart_.get(), d_w, d_hcol + nb, st);
+}
+
+void Gmres::reserve(size_t len, size_t restart_dim)
+{
+    const size_t m = restart_dim;
+    grow(eng_, basis_, len * (m + 1));
+    grow(eng_, ax_, len);
+    gs_.reserve(m + 1);
+    grow(eng_, hcol_, m + 3); // the column of H (m + 2) and one norm
+    grow(eng_, coef_, m + 1);
 }
 
 namespace {
@@ -185,7 +195,7 @@ GmresResult Gmres::solve(const GmresApply& apply, size_t len, const double* d_b,
     const size_t m = restart_dim;
     reserve(len, m);
     const bool relative = mode == GmresToleranceMode::Relative;
-    const double b_norm = norm(d_b, len);
+    const double b_norm = gs_.norm(d_b, len);
     auto value = [&](double r) { return relative ? r / b_norm : r; };
     auto is_converged = [&](double r) { return value(r) < tol; };
     if (b_norm < 1e-15) {
@@ -203,13 +213,14 @@ GmresResult Gmres::solve(const GmresApply& apply, size_t len, const double* d_b,
     double* V = basis_.get();
     double* d_hcol = hcol_.get();
     double* d_norm = hcol_.get() + m + 2;
+    double* npart = gs_.npart();
     // |b - (a0 x + a1 H x)|; the residual is left in column 0 of the basis, normalised
     auto residual_norm = [&]() {
         double v = 0.0;
         apply(d_x, ax_.get());
         ++res.apply_calls;
-        linsolve_residual_launch(d_b, d_x, ax_.get(), a0, a1, V, len, npart_.get(), st);
-        gs_normalize_launch(V, len, npart_.get(), V, d_norm, st);
+        linsolve_residual_launch(d_b, d_x, ax_.get(), a0, a1, V, len, npart, st);
+        gs_normalize_launch(V, len, npart, V, d_norm, st);
         T4A_HIP(hipMemcpyAsync(&v, d_norm, sizeof(double), hipMemcpyDeviceToHost, st));
         eng_.sync();
         return v;
@@ -219,7 +230,7 @@ GmresResult Gmres::solve(const GmresApply& apply, size_t len, const double* d_b,
         neg.resize(y.size());
         for (size_t i = 0; i < y.size(); ++i) neg[i] = -y[i];
         T4A_HIP(hipMemcpyAsync(coef_.get(), neg.data(), sizeof(double) * neg.size(), hipMemcpyHostToDevice, st));
-        gs_update_launch(V, len, (int)y.size(), d_x, len, coef_.get(), 1, nullptr, true, nullptr, npart_.get(), st);
+        gs_update_launch(V, len, (int)y.size(), d_x, len, coef_.get(), 1, nullptr, true, nullptr, npart, st);
         T4A_HIP(hipGetLastError());
         eng_.sync();
     };
@@ -325,9 +336,9 @@ std::array<size_t, 4> ProjectedOperator::local_dims(size_t site) const
     return {x[site].l, x[site].s, x[site + 1].s, x[site + 1].r};
 }
 
-void ProjectedOperator::check_step(size_t site, size_t restart_dim) const
+void ProjectedOperator::check_step(size_t site, size_t restart_dim, const char* who) const
 {
-    check_step_dims(site, x[site].l, x[site].s, x[site + 1].s, x[site + 1].r, op_->tt.cores[site].r, restart_dim);
+    check_bond_step_dims(who, site, x[site].l, x[site].s, x[site + 1].s, x[site + 1].r, op_->tt.cores[site].r, restart_dim);
 }
 
 void ProjectedOperator::invalidate(size_t site)
@@ -491,6 +502,30 @@ void ProjectedOperator::apply_prepared(const double* d_v, double* d_out)
 {
     product_left(d_v);
     product_right(d_out);
+}
+
+void ProjectedOperator::split_and_advance(size_t i, const double* d_theta, const SvdOptions& so, bool move_right, const char* who)
+{
+    Engine& e = engine();
+    hipStream_t st = e.stream();
+    const auto ld = local_dims(i);
+    const int M = (int)(ld[0] * ld[1]), N = (int)(ld[2] * ld[3]);
+    const TensorView tv{d_theta, {(size_t)M, (size_t)N}, {0, 1}};
+    const UnfoldPlan un = plan_unfold_split(tv, {0});
+    require_factorizable(un, who, "svd");
+    const UnfoldedFactors f = tensor_svd(e, tv, un, so);
+    DevCore nl = DevCore::make(ld[0], ld[1], f.keep), nr = DevCore::make(f.keep, ld[2], ld[3]);
+    split_two_site(st, f.d_left, M, f.d_s, f.d_right, (int)f.k, N, (int)f.keep, move_right, nl, nr); // x_i = U | x_i = U S
+    T4A_HIP(hipGetLastError());
+    e.sync(); // the old sites are released below
+    x[i] = std::move(nl);
+    x[i + 1] = std::move(nr);
+    // both sites changed: every cache that contains one of them is stale; the side left behind is rebuilt from this step's half operator
+    // (HL and HR depend on the environments and the operator only, not on the two sites)
+    invalidate(i);
+    invalidate(i + 1);
+    if (move_right) update_left_from_prepared(i);
+    else update_right_from_prepared(i);
 }
 
 void ProjectedOperator::time_step(size_t site, size_t nb, size_t reps, double ms[5])
@@ -722,22 +757,7 @@ LinsolveResult square_linsolve(Mpo& op, TensorTrain& rhs, TensorTrain& init, siz
         ++out.stats.local_solves;
         out.stats.arnoldi_steps += gr.iterations;
         out.stats.apply_calls += gr.apply_calls;
-        const TensorView tv{theta.get(), {(size_t)M, (size_t)N}, {0, 1}};
-        const UnfoldPlan un = plan_unfold_split(tv, {0});
-        require_factorizable(un, "square_linsolve", "svd");
-        const UnfoldedFactors f = tensor_svd(e, tv, un, so);
-        DevCore nl = DevCore::make(ld[0], ld[1], f.keep), nr = DevCore::make(f.keep, ld[2], ld[3]);
-        split_two_site(st, f.d_left, M, f.d_s, f.d_right, (int)f.k, N, (int)f.keep, move_right, nl, nr); // x_i = U | x_i = U S
-        T4A_HIP(hipGetLastError());
-        e.sync(); // the old sites are released below
-        po.x[i] = std::move(nl);
-        po.x[i + 1] = std::move(nr);
-        // both sites changed: every cache that contains one of them is stale; the side left behind is rebuilt from this step's half operator
-        // (HL and HR depend on the environments and the operator only, not on the two sites)
-        po.invalidate(i);
-        po.invalidate(i + 1);
-        if (move_right) po.update_left_from_prepared(i);
-        else po.update_right_from_prepared(i);
+        po.split_and_advance(i, theta.get(), so, move_right, "square_linsolve");
     };
 
     for (size_t sweep = 0; sweep < o.nfullsweeps; ++sweep) {

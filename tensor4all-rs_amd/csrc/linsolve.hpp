@@ -60,21 +60,39 @@ struct GmresResult {
     size_t apply_calls = 0;
 };
 using GmresApply = std::function<void(const double* d_v, double* d_out)>; // enqueues out = H v on the engine's stream
+// What both Krylov solvers (Gmres here, Lanczos of dmrg.hpp) launch around their apply: the two-pass orthogonalisation step, the norm
+// read by the host, and the buffers of the partial sums.
+class KrylovOrth {
+public:
+    explicit KrylovOrth(Engine& e) : eng_(e) {}
+    void reserve(size_t nb_max); // at most nb_max basis vectors per pass
+    // One two-pass orthogonalisation step: w against the nb columns of V (leading dimension ld), then normalised in place.
+    // d_hcol: nb + 1 doubles (the column of H, h_{nb} = the norm); d_hpass (may be null): 2 nb doubles, the coefficients of pass 1 and of pass 2.
+    void orth(const double* d_V, size_t ld, int nb, double* d_w, size_t len, double* d_hcol, double* d_hpass);
+    // host value of |w| (one read); out (may be null, may be w) receives w / |w|
+    double norm(const double* d_w, size_t len, double* d_out = nullptr);
+    double* npart() { return npart_.get(); }   // 3 GS_MAX_WORKGROUPS doubles: the shares of |w|^2, or the three sums of eig_residual
+    double* scalars() { return scal_.get(); }  // 4 doubles: [0] the landing place of norm(), [1..3] free for the caller
+    Engine& engine() { return eng_; }
+
+private:
+    Engine& eng_;
+    DevBuf<double> part_, npart_, scal_;
+};
 class Gmres {
 public:
-    explicit Gmres(Engine& e) : eng_(e) {}
+    explicit Gmres(Engine& e) : eng_(e), gs_(e) {}
     // x: the start on entry, the solution on exit (device, len doubles).  Non-convergence is a flag.  INVALID_ARGUMENT: a0 == a1 == 0.
     GmresResult solve(const GmresApply& apply, size_t len, const double* d_b, double* d_x, double a0, double a1, double tol, GmresToleranceMode mode,
                       size_t restart_dim, size_t max_restarts);
-    // One two-pass orthogonalisation step as solve() launches it: w against the nb columns of V (leading dimension ld), then normalised in
-    // place.  d_hcol: nb + 1 doubles (the column of H, h_{nb} = the norm); d_hpass: 2 nb doubles, the coefficients of pass 1 and of pass 2.
-    void orth(const double* d_V, size_t ld, int nb, double* d_w, size_t len, double* d_hcol, double* d_hpass);
+    // KrylovOrth::orth as solve() launches it
+    void orth(const double* d_V, size_t ld, int nb, double* d_w, size_t len, double* d_hcol, double* d_hpass) { gs_.orth(d_V, ld, nb, d_w, len, d_hcol, d_hpass); }
     void reserve(size_t len, size_t restart_dim);
 
 private:
-    double norm(const double* d_w, size_t len); // host value of |w| (one read)
     Engine& eng_;
-    DevBuf<double> basis_, ax_, part_, npart_, hcol_, coef_;
+    KrylovOrth gs_;
+    DevBuf<double> basis_, ax_, hcol_, coef_;
 };
 
 // ---- options and results of the solver (LinsolveOptions, SquareLinsolveResult of the reference)
@@ -114,6 +132,10 @@ constexpr size_t LINSOLVE_RESTART_DIM_MAX = 8191; // the coefficients of a pass 
 void linsolve_validate_shapes(const std::vector<std::array<size_t, 4>>& op, const std::vector<std::array<size_t, 3>>* rhs,
                               const std::vector<std::array<size_t, 3>>& state, size_t center, size_t restart_dim);
 
+// The INT_MAX bound of the buffers of the bond step (i, i + 1): HL, HR, T and a Krylov basis of basis_dim + 1 columns, M = chi_l d1,
+// N = d2 chi_r, W the operator bond between the two sites.  INVALID_ARGUMENT "<who>: a work buffer of the bond step (i, i+1) ...".
+void check_bond_step_dims(const char* who, size_t i, size_t chi_l, size_t d1, size_t d2, size_t chi_r, size_t W, size_t basis_dim);
+
 // ||(a0 + a1 A) x - b|| / ||b||, the absolute norm when ||b|| <= 1e-15: the exact naive apply, add / sub, and the norm of the residual
 // train from its QR right-canonical form (the transfer-matrix norm2 would lose half of the digits in the cancellation).
 double relative_linear_system_residual(Mpo& op, TensorTrain& x, TensorTrain& rhs, double a0, double a1);
@@ -149,7 +171,11 @@ public:
     void local_rhs(size_t site, double* d_out);              // Lb_i b_i b_{i+1} Rb_{i+2} as M x N
     void update_left_from_prepared(size_t site);             // L_{site+1} (and Lb) from x[site] and the HL of prepare(site)
     void update_right_from_prepared(size_t site);            // R_{site+1} (and Rb) from x[site+1] and the HR of prepare(site)
-    void check_step(size_t site, size_t restart_dim) const;  // INT_MAX bound of the step's buffers
+    void check_step(size_t site, size_t restart_dim, const char* who = "square_linsolve") const;  // INT_MAX bound of the step's buffers
+    // The back half of a bond step of the sweeps (square_linsolve, dmrg): theta (device, M x N of the region (site, site + 1)) is split by
+    // tensor_svd with `so`, x[site] = U | U S and x[site + 1] = S Vt | Vt (move_right | left: the singular values go to the new centre), both
+    // sites are invalidated and the environment of the side left behind is rebuilt from the half operators of prepare(site).
+    void split_and_advance(size_t site, const double* d_theta, const SvdOptions& so, bool move_right, const char* who);
 
     std::vector<DevCore> x, b;
 

@@ -2153,3 +2153,7 @@ from .canonical import SiteTensorTrain, VidalTensorTrain, InverseTensorTrain, ce
 from . import linsolve  # noqa: E402
 from .linsolve import (GmresToleranceMode, LinsolveOptions, LinsolveOptionsC, SquareLinsolveResult, square_linsolve,  # noqa: E402,F401
                        relative_linear_system_residual, ProjectedOperator)
+# t4a_amd.dmrg is the function, as in the Rust crate; its module (the hooks _lanczos_dense, _krylov_combine, _eig_residual) is
+# imported as `from t4a_amd.dmrg import ...` or reached as t4a_amd.dmrg_module
+from . import dmrg as dmrg_module  # noqa: E402
+from .dmrg import (HermitianLanczosOptions, LanczosOptionsC, DmrgOptions, DmrgOptionsC, DmrgResult, dmrg, dmrg_energy)  # noqa: E402,F401
