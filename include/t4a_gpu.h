@@ -1251,6 +1251,14 @@ void t4a_gpu_projected_operator_release(t4a_gpu_projected_operator* h);
 t4a_gpu_status t4a_gpu_projected_operator_local_dims(const t4a_gpu_projected_operator* h, size_t site, size_t* dims4);
 t4a_gpu_status t4a_gpu_projected_operator_apply(t4a_gpu_projected_operator* h, size_t site, const double* v, double* out);
 t4a_gpu_status t4a_gpu_projected_operator_environment(t4a_gpu_projected_operator* h, int32_t side, size_t bond, size_t* dims3, double* out);
+/* _apply_one_site: out = H v for the one-site region `site` (the site correction of t4a_gpu_tdvp), v and out column-major
+ *   [alpha_l, t, alpha_r] of chi_l d_site chi_r doubles: out[b, s, b'] = sum L_site[b, w, a] A_site[w, s, t, w'] v[a, t, a']
+ *   R_{site+1}[b', w', a'], launched as the sweeps launch it (the half operator HL = L A and two products).  *reused_hl (may be NULL)
+ *   is 1 when the HL left behind by an earlier _apply of the bond (site, site + 1) served instead of a new one, else 0.
+ * _time_one_site (tools/probe_tdvp.py): device milliseconds of its three launches, ms[0] HL = L A, ms[1] T = HL V, ms[2] Y = T R^T. */
+t4a_gpu_status t4a_gpu_projected_operator_apply_one_site(t4a_gpu_projected_operator* h, size_t site, const double* v, double* out,
+                                                         int32_t* reused_hl);
+t4a_gpu_status t4a_gpu_projected_operator_time_one_site(t4a_gpu_projected_operator* h, size_t site, size_t reps, double* ms /* [3] */);
 t4a_gpu_status t4a_gpu_projected_operator_invalidate(t4a_gpu_projected_operator* h, size_t site);
 t4a_gpu_status t4a_gpu_projected_operator_set_site_tensors(t4a_gpu_projected_operator* h, size_t site, const size_t* dims3_a, const double* t_a,
                                                            const size_t* dims3_b, const double* t_b);
@@ -1273,6 +1281,14 @@ t4a_gpu_status t4a_gpu_linsolve_orth(const double* basis, size_t len, size_t nb,
 t4a_gpu_status t4a_gpu_linsolve_gmres_dense(const double* H, size_t n, const double* b, const double* x0, double a0, double a1, double tol,
                                             int32_t mode, size_t restart_dim, size_t max_restarts, double* x, size_t* iterations,
                                             double* residual, int32_t* converged);
+/* _krylov_orth: t4a_gpu_linsolve_orth with the launch of the projections chosen: route 0 the serial gs_dots (what GMRES and Lanczos
+ *   run), 1 gs_dots_wide (a second grid dimension over the basis vectors, GS_WIDE = 8 per workgroup), 2 the rule the Krylov exponential
+ *   of t4a_gpu_tdvp applies.  The three give the same bits.
+ * _krylov_dots_route: that rule for a vector of len elements and nb basis vectors (host only) -> 0 or 1.
+ * _krylov_time_dots (tools/probe_tdvp.py): device milliseconds of the serial [0] and the wide [1] launch. */
+t4a_gpu_status t4a_gpu_krylov_orth(const double* basis, size_t len, size_t nb, double* w_inout, int32_t route, double* h_out, double* norm_out);
+t4a_gpu_status t4a_gpu_krylov_dots_route(size_t len, size_t nb, int32_t* route);
+t4a_gpu_status t4a_gpu_krylov_time_dots(size_t len, size_t nb, size_t reps, double* ms /* [2] */);
 
 /* =====================================================================================
  * Two-site DMRG: the lowest eigenpair of an MPO H over tensor trains resident on the device
@@ -1351,6 +1367,71 @@ t4a_gpu_status t4a_gpu_krylov_combine(const double* basis, size_t len, size_t nb
 t4a_gpu_status t4a_gpu_eig_residual(const double* v, const double* hv, size_t len, double lambda, double* r /* may be NULL */,
                                     double* sums3);
 t4a_gpu_status t4a_gpu_lanczos_time_finalise(size_t len, size_t nb, size_t reps, double* ms /* [3] */);
+
+/* =====================================================================================
+ * Two-site TDVP: a tensor train evolved under an MPO H, exp(tau H) per sweep, resident on the device
+ * tensor4all-treetn/src/tdvp/mod.rs (tdvp, tdvp_with_treetn_operator, TdvpOptions, TdvpResult), tdvp/plan.rs (the region plan) on the
+ * Hermitian Krylov exponential of tensor4all-core/src/krylov.rs:693-926 (hermitian_krylov_expm_multiply), restated for a chain.
+ * Scope: that of t4a_gpu_square_linsolve and t4a_gpu_dmrg — a chain, f64, one site index per node, V_in = V_out.  Trees, index
+ * mappings and verbose output are not mirrored.  Deviations from the reference, refused with INVALID_ARGUMENT on the host:
+ *   - the exponent is real: exponent_step_re (default -0.1 where the reference has -0.1i) and exponent_step_im, which must be 0:
+ *     real-time evolution needs complex trains, which this project does not have.  u' = -H u is what a real exponent covers;
+ *   - `center` must be 0 or n - 1: the reference's two-site plan from an inner root of a chain applies a site correction at a leaf
+ *     where the projector splitting needs it at the root (relative error 0.17 against exp(tau H) psi at n = 4 from centre 1, 1e-15
+ *     from an end); from an end it is the standard 2TDVP sweep;
+ *   - nsite = 1 is not implemented (it needs the bond-centre apply), with a message of its own; nsite outside {1, 2} gets the
+ *     reference's.
+ * `init` is canonicalised onto `center`.  One sweep runs the plan of t4a_gpu_tdvp_plan: two-site steps (theta_0 = x_i x_{i+1}, the
+ * Krylov exponential with the step's exponent, an SVD split with max_bond_dim / svd_policy, the singular values into the new centre,
+ * no renormalisation) and, between two of them, the site correction with minus the exponent on the shared site.  Where the centre is
+ * not in a step's region (the start of the second sweep when order = 1) it is moved there by full-rank thin QR steps.
+ * The Krylov solver orthogonalises by two passes of classical Gram-Schmidt (the reference: modified), as GMRES and Lanczos here do.
+ * Errors: INVALID_ARGUMENT with the reference's wording for nsweeps == 0, an order outside {1, 2, 4}, a non-finite exponent,
+ * max_bond_dim == 0 when set, fewer than two sites, and the Krylov options (max_iter == 0 or above 8191, max_time_splits == 0, a
+ * negative or non-finite tolerance); a projected operator that is not Hermitian; INTERNAL_ERROR "hermitian_krylov_expm_multiply did not
+ * converge within max_time_splits=.. and max_iter=..". */
+typedef struct {
+    size_t max_iter;        /* 30 */
+    size_t max_time_splits; /* 100 */
+    double tol;             /* 1e-12, times max(|start|, 1) */
+    double breakdown_tol;   /* 1e-14 */
+    double hermitian_tol;   /* 1e-10 */
+} t4a_gpu_krylov_expm_options;
+typedef struct {
+    size_t nsite;   /* 2 */
+    size_t nsweeps; /* 1 */
+    size_t order;   /* 2: the substeps [1], [1/2, 1/2] or the six of order 4 */
+    double exponent_step_re; /* -0.1 */
+    double exponent_step_im; /* 0, and nothing else */
+    int32_t has_max_bond_dim;
+    size_t max_bond_dim;
+    int32_t has_svd_policy; /* 0: the default policy of t4a_gpu_tensor_svd */
+    t4a_gpu_svd_policy svd_policy;
+    t4a_gpu_krylov_expm_options krylov;
+} t4a_gpu_tdvp_options;
+typedef struct {
+    size_t two_site_steps;
+    size_t corrections;
+    size_t krylov_steps;    /* over all accepted substeps of all local solves */
+    size_t apply_calls;     /* projected applies, those of rejected time splits included */
+    size_t max_time_splits; /* the largest number of time splits a local solve needed */
+} t4a_gpu_tdvp_stats;
+
+t4a_gpu_status t4a_gpu_tdvp_options_default(t4a_gpu_tdvp_options* out);
+/* The shape checks of t4a_gpu_tdvp on plain dimension lists (see t4a_gpu_dmrg_check_shapes), the centre rule included; host only. */
+t4a_gpu_status t4a_gpu_tdvp_check_shapes(const size_t* op_dims4, size_t n_op, const size_t* state_dims3, size_t n_state, size_t center,
+                                         size_t max_iter);
+/* The region plan of one sweep (host only): kinds[k] 0 a two-site step, 1 a site correction; nodes[2 k], nodes[2 k + 1] the region
+ * in the reference's order (the other node, then the new centre; twice the site for a correction); new_centers[k]; exponents[k].
+ * *n_steps receives the number of steps; with the four arrays NULL that is all, else `capacity` must hold it (BUFFER_TOO_SMALL). */
+t4a_gpu_status t4a_gpu_tdvp_plan(size_t n, size_t center, size_t order, double tau, size_t capacity, int32_t* kinds, size_t* nodes,
+                                 size_t* new_centers, double* exponents, size_t* n_steps);
+t4a_gpu_status t4a_gpu_tdvp(const t4a_gpu_mpo* op, const t4a_gpu_tt* init, size_t center, const t4a_gpu_tdvp_options* options, t4a_gpu_tt** state,
+                            size_t* sweeps_completed, size_t* local_updates, double* max_error_estimate, size_t* max_krylov_iterations,
+                            t4a_gpu_tdvp_stats* stats /* may be NULL */);
+/* Test hook: the solver the sweeps run, out = exp(tau H) v0 for a dense n x n matrix H (column-major) applied on the device. */
+t4a_gpu_status t4a_gpu_krylov_expm_dense(const double* H, size_t n, const double* v0, double tau, const t4a_gpu_krylov_expm_options* options,
+                                         double* out, size_t* iterations, double* error_estimate, int32_t* converged, size_t* time_splits);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

@@ -20,6 +20,7 @@
 #include "quanticstransform.hpp"
 #include "tt_canonical.hpp"
 #include "dmrg.hpp"
+#include "tdvp.hpp"
 #include "linsolve.hpp"
 
 struct t4a_gpu_tci2 {
@@ -4238,6 +4239,28 @@ t4a_gpu_status t4a_gpu_projected_operator_apply(t4a_gpu_projected_operator* h, s
     });
 }
 
+t4a_gpu_status t4a_gpu_projected_operator_apply_one_site(t4a_gpu_projected_operator* h, size_t site, const double* v, double* out, int32_t* reused_hl)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(h);
+        T4A_REQUIRE_PTR(v);
+        T4A_REQUIRE_PTR(out);
+        bool reused = false;
+        const std::vector<double> y = h->impl->apply_one_site(site, v, &reused);
+        std::memcpy(out, y.data(), y.size() * sizeof(double));
+        if (reused_hl) *reused_hl = reused;
+    });
+}
+
+t4a_gpu_status t4a_gpu_projected_operator_time_one_site(t4a_gpu_projected_operator* h, size_t site, size_t reps, double* ms)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(h);
+        T4A_REQUIRE_PTR(ms);
+        h->impl->time_one_site(site, reps, ms);
+    });
+}
+
 t4a_gpu_status t4a_gpu_projected_operator_environment(t4a_gpu_projected_operator* h, int32_t side, size_t bond, size_t* dims3, double* out)
 {
     return guarded([&] {
@@ -4310,6 +4333,39 @@ t4a_gpu_status t4a_gpu_linsolve_orth(const double* basis, size_t len, size_t nb,
         T4A_REQUIRE_PTR(norm_out);
         require_device();
         linsolve_orth(basis, len, nb, w_inout, h_out, norm_out);
+    });
+}
+
+t4a_gpu_status t4a_gpu_krylov_orth(const double* basis, size_t len, size_t nb, double* w_inout, int32_t route, double* h_out, double* norm_out)
+{
+    return guarded([&] {
+        if (len == 0 || nb == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "krylov_orth: len and nb must be positive");
+        if (nb > LINSOLVE_RESTART_DIM_MAX + 1 || (unsigned long long)len * nb > (unsigned long long)INT_MAX)
+            throw Error(T4A_GPU_INVALID_ARGUMENT, "krylov_orth: the basis holds more than INT_MAX elements");
+        if (route < 0 || route > 2) throw Error(T4A_GPU_INVALID_ARGUMENT, "krylov_orth: route must be 0 (serial), 1 (wide) or 2 (the rule of krylov_dots_route)");
+        T4A_REQUIRE_PTR(basis);
+        T4A_REQUIRE_PTR(w_inout);
+        T4A_REQUIRE_PTR(h_out);
+        T4A_REQUIRE_PTR(norm_out);
+        require_device();
+        krylov_orth_host(basis, len, nb, w_inout, (KrylovDotsRoute)route, h_out, norm_out);
+    });
+}
+
+t4a_gpu_status t4a_gpu_krylov_dots_route(size_t len, size_t nb, int32_t* route)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(route);
+        if (nb > LINSOLVE_RESTART_DIM_MAX + 1) throw Error(T4A_GPU_INVALID_ARGUMENT, "krylov_dots_route: nb above " + std::to_string(LINSOLVE_RESTART_DIM_MAX + 1));
+        *route = (int32_t)krylov_dots_route(len, (int)nb);
+    });
+}
+
+t4a_gpu_status t4a_gpu_krylov_time_dots(size_t len, size_t nb, size_t reps, double* ms)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(ms);
+        krylov_time_dots(len, nb, reps, ms); // checks its arguments, then the device
     });
 }
 
@@ -4499,6 +4555,144 @@ t4a_gpu_status t4a_gpu_lanczos_time_finalise(size_t len, size_t nb, size_t reps,
     return guarded([&] {
         T4A_REQUIRE_PTR(ms);
         lanczos_time_finalise(len, nb, reps, ms); // checks its arguments, then the device
+    });
+}
+
+// ---- two-site TDVP: a train evolved under an MPO by sweeps of projected Krylov exponentials (tdvp.hpp) ----
+t4a_gpu_status t4a_gpu_tdvp_options_default(t4a_gpu_tdvp_options* out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(out);
+        const TdvpOptions d;
+        *out = t4a_gpu_tdvp_options{};
+        out->nsite = d.nsite;
+        out->nsweeps = d.nsweeps;
+        out->order = d.order;
+        out->exponent_step_re = d.exponent_step_re;
+        out->exponent_step_im = d.exponent_step_im;
+        out->has_max_bond_dim = d.has_max_bond_dim;
+        out->max_bond_dim = d.max_bond_dim;
+        out->has_svd_policy = d.has_svd_policy;
+        out->svd_policy = t4a_gpu_svd_policy{d.svd_policy.threshold, d.svd_policy.scale, d.svd_policy.measure, d.svd_policy.rule};
+        out->krylov = t4a_gpu_krylov_expm_options{d.krylov.max_iter, d.krylov.max_time_splits, d.krylov.tol, d.krylov.breakdown_tol, d.krylov.hermitian_tol};
+    });
+}
+
+extern "C++" {
+static KrylovExpmOptions convert_krylov_expm_options(const t4a_gpu_krylov_expm_options& p)
+{
+    KrylovExpmOptions o;
+    o.max_iter = p.max_iter;
+    o.max_time_splits = p.max_time_splits;
+    o.tol = p.tol;
+    o.breakdown_tol = p.breakdown_tol;
+    o.hermitian_tol = p.hermitian_tol;
+    return o;
+}
+static TdvpOptions convert_tdvp_options(const t4a_gpu_tdvp_options* p)
+{
+    TdvpOptions o;
+    o.nsite = p->nsite;
+    o.nsweeps = p->nsweeps;
+    o.order = p->order;
+    o.exponent_step_re = p->exponent_step_re;
+    o.exponent_step_im = p->exponent_step_im;
+    o.has_max_bond_dim = p->has_max_bond_dim != 0;
+    o.max_bond_dim = p->max_bond_dim;
+    o.has_svd_policy = p->has_svd_policy != 0;
+    if (o.has_svd_policy) o.svd_policy = SvdPolicy{p->svd_policy.threshold, p->svd_policy.scale, p->svd_policy.measure, p->svd_policy.rule};
+    o.krylov = convert_krylov_expm_options(p->krylov);
+    o.validate();
+    return o;
+}
+}
+
+t4a_gpu_status t4a_gpu_tdvp_check_shapes(const size_t* op_dims4, size_t n_op, const size_t* state_dims3, size_t n_state, size_t center,
+                                         size_t max_iter)
+{
+    return guarded([&] {
+        if (n_op) T4A_REQUIRE_PTR(op_dims4);
+        if (n_state) T4A_REQUIRE_PTR(state_dims3);
+        KrylovExpmOptions ko;
+        ko.max_iter = max_iter;
+        ko.validate();
+        std::vector<std::array<size_t, 4>> op(n_op);
+        for (size_t i = 0; i < n_op; ++i) op[i] = {op_dims4[4 * i], op_dims4[4 * i + 1], op_dims4[4 * i + 2], op_dims4[4 * i + 3]};
+        tdvp_validate_shapes(op, dims3_list(state_dims3, n_state), center, max_iter);
+    });
+}
+
+t4a_gpu_status t4a_gpu_tdvp_plan(size_t n, size_t center, size_t order, double tau, size_t capacity, int32_t* kinds, size_t* nodes, size_t* new_centers,
+                                 double* exponents, size_t* n_steps)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(n_steps);
+        const std::vector<TdvpStep> plan = tdvp_plan(n, center, order, tau);
+        *n_steps = plan.size();
+        if (!kinds && !nodes && !new_centers && !exponents) return; // the count only
+        if (capacity < plan.size()) throw Error(T4A_GPU_BUFFER_TOO_SMALL, "tdvp_plan: the plan has " + std::to_string(plan.size()) + " steps");
+        T4A_REQUIRE_PTR(kinds);
+        T4A_REQUIRE_PTR(nodes);
+        T4A_REQUIRE_PTR(new_centers);
+        T4A_REQUIRE_PTR(exponents);
+        for (size_t k = 0; k < plan.size(); ++k) {
+            kinds[k] = (int32_t)plan[k].kind;
+            nodes[2 * k] = plan[k].nodes[0];
+            nodes[2 * k + 1] = plan[k].nodes[1];
+            new_centers[k] = plan[k].new_center;
+            exponents[k] = plan[k].exponent;
+        }
+    });
+}
+
+t4a_gpu_status t4a_gpu_tdvp(const t4a_gpu_mpo* op, const t4a_gpu_tt* init, size_t center, const t4a_gpu_tdvp_options* options, t4a_gpu_tt** state,
+                            size_t* sweeps_completed, size_t* local_updates, double* max_error_estimate, size_t* max_krylov_iterations,
+                            t4a_gpu_tdvp_stats* stats)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(state);
+        *state = nullptr;
+        T4A_REQUIRE_PTR(options);
+        const TdvpOptions o = convert_tdvp_options(options); // the options are checked on the host before an operand is looked at
+        T4A_REQUIRE_PTR(op);
+        T4A_REQUIRE_PTR(init);
+        T4A_REQUIRE_PTR(sweeps_completed);
+        T4A_REQUIRE_PTR(local_updates);
+        T4A_REQUIRE_PTR(max_error_estimate);
+        T4A_REQUIRE_PTR(max_krylov_iterations);
+        TdvpResult r = tdvp(*op->impl, const_cast<t4a_gpu_tt*>(init)->impl, center, o);
+        *state = new t4a_gpu_tt(r.state->cores, r.state->eng.stream());
+        *sweeps_completed = r.sweeps_completed;
+        *local_updates = r.local_updates;
+        *max_error_estimate = r.max_error_estimate;
+        *max_krylov_iterations = r.max_krylov_iterations;
+        if (stats) *stats = t4a_gpu_tdvp_stats{r.stats.two_site_steps, r.stats.corrections, r.stats.krylov_steps, r.stats.apply_calls, r.stats.max_time_splits};
+    });
+}
+
+t4a_gpu_status t4a_gpu_krylov_expm_dense(const double* H, size_t n, const double* v0, double tau, const t4a_gpu_krylov_expm_options* options, double* out,
+                                         size_t* iterations, double* error_estimate, int32_t* converged, size_t* time_splits)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(options);
+        const KrylovExpmOptions o = convert_krylov_expm_options(*options);
+        o.validate();
+        if (!std::isfinite(tau)) throw Error(T4A_GPU_INVALID_ARGUMENT, "krylov_expm_dense: tau must be finite");
+        if (n == 0 || n > 46340 || (unsigned long long)n * (o.max_iter + 1) > (unsigned long long)INT_MAX)
+            throw Error(T4A_GPU_INVALID_ARGUMENT, "krylov_expm_dense: n must be positive and the matrix and the basis must hold at most INT_MAX elements");
+        T4A_REQUIRE_PTR(H);
+        T4A_REQUIRE_PTR(v0);
+        T4A_REQUIRE_PTR(out);
+        T4A_REQUIRE_PTR(iterations);
+        T4A_REQUIRE_PTR(error_estimate);
+        T4A_REQUIRE_PTR(converged);
+        T4A_REQUIRE_PTR(time_splits);
+        require_device();
+        const KrylovExpmResult r = krylov_expm_dense(H, n, v0, tau, o, out);
+        *iterations = r.iterations;
+        *error_estimate = r.error_estimate;
+        *converged = r.converged;
+        *time_splits = r.time_splits;
     });
 }
 

@@ -67,6 +67,13 @@ void check_bond_step_dims(const char* who, size_t i, size_t chi_l, size_t d1, si
                                                   ") holds more than INT_MAX elements");
 }
 
+void check_site_step_dims(const char* who, size_t c, size_t chi_l, size_t d, size_t chi_r, size_t W, size_t basis_dim)
+{
+    const size_t M = chi_l * d;
+    if (above_int_max({W, M, M}) || above_int_max({W, M, chi_r}) || above_int_max({chi_r, W, chi_r}) || above_int_max({basis_dim + 1, M, chi_r}))
+        throw Error(T4A_GPU_INVALID_ARGUMENT, std::string(who) + ": a work buffer of the one-site step at site " + std::to_string(c) + " holds more than INT_MAX elements");
+}
+
 void LinsolveOptions::validate() const
 {
     if (gmres_restart_dim == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "LinsolveOptions::gmres_restart_dim must be greater than zero");
@@ -129,13 +136,22 @@ double KrylovOrth::norm(const double* d_w, size_t len, double* d_out)
     return v;
 }
 
+KrylovDotsRoute krylov_dots_route(size_t, int nb) { return nb > GS_WIDE ? KrylovDotsRoute::Wide : KrylovDotsRoute::Serial; }
+
+void KrylovOrth::dots(const double* d_V, size_t ld, int nb, const double* d_w, size_t len)
+{
+    const KrylovDotsRoute r = route_ == KrylovDotsRoute::Auto ? krylov_dots_route(len, nb) : route_;
+    if (r == KrylovDotsRoute::Wide) gs_dots_wide_launch(d_V, ld, nb, d_w, len, part_.get(), eng_.stream());
+    else gs_dots_launch(d_V, ld, nb, d_w, len, part_.get(), eng_.stream());
+}
+
 void KrylovOrth::orth(const double* d_V, size_t ld, int nb, double* d_w, size_t len, double* d_hcol, double* d_hpass)
 {
     hipStream_t st = eng_.stream();
     const int G = gs_workgroups(len);
-    gs_dots_launch(d_V, ld, nb, d_w, len, part_.get(), st);
+    dots(d_V, ld, nb, d_w, len);
     gs_update_launch(d_V, ld, nb, d_w, len, part_.get(), G, d_hcol, true, d_hpass, npart_.get(), st);
-    gs_dots_launch(d_V, ld, nb, d_w, len, part_.get(), st);
+    dots(d_V, ld, nb, d_w, len);
     gs_update_launch(d_V, ld, nb, d_w, len, part_.get(), G, d_hcol, false, d_hpass ? d_hpass + nb : nullptr, npart_.get(), st);
     gs_normalize_launch(d_w, len, npart_.get(), d_w, d_hcol + nb, st);
 }
@@ -347,6 +363,8 @@ void ProjectedOperator::invalidate(size_t site)
     for (size_t j = site + 1; j < okL_.size(); ++j) okL_[j] = 0;
     for (size_t j = 0; j <= site; ++j) okR_[j] = 0;
     prepared_ = (size_t)-1;
+    prepared1_ = (size_t)-1;
+    if (hl_site_ != (size_t)-1 && site < hl_site_) hl_site_ = (size_t)-1; // L_c A_c depends on the sites < c only
 }
 
 // L_{k+1} from L_k, A_k (as the HL in hl_) and x_k:  T1 = HL X_k, then L_{k+1}[:, w, :] = X_k^T T1_w for every w in one batched product
@@ -430,6 +448,7 @@ const double* ProjectedOperator::left_env(size_t i)
             throw Error(T4A_GPU_INVALID_ARGUMENT, "projected operator: the left environment of site " + std::to_string(k + 1) + " needs more than INT_MAX elements");
         grow(e, hl_, A.r * X.l * X.s * X.l * X.s);
         prepared_ = (size_t)-1;
+        prepared1_ = hl_site_ = (size_t)-1;
         linsolve_hl_launch(envL_[k].get(), A.buf.get(), hl_.get(), (int)X.l, (int)A.l, (int)X.s, (int)A.r, e.stream());
         update_left_from_prepared(k);
     }
@@ -481,7 +500,102 @@ void ProjectedOperator::prepare(size_t site)
     linsolve_hl_launch(L, A1.buf.get(), hl_.get(), (int)ld[0], (int)A1.l, (int)ld[1], (int)W, e.stream());
     linsolve_hr_launch(A2.buf.get(), R, hr_.get(), (int)ld[3], (int)W, (int)ld[2], (int)A2.r, e.stream());
     T4A_HIP(hipGetLastError());
-    prepared_ = site;
+    prepared_ = hl_site_ = site;
+    if (prepared1_ != site) prepared1_ = (size_t)-1;
+}
+
+void ProjectedOperator::check_site_step(size_t c, size_t basis_dim, const char* who) const
+{
+    check_site_step_dims(who, c, x[c].l, x[c].s, x[c].r, op_->tt.cores[c].r, basis_dim);
+}
+
+bool ProjectedOperator::prepare_one_site(size_t c)
+{
+    if (c >= x.size()) throw Error(T4A_GPU_INVALID_ARGUMENT, "projected operator: site " + std::to_string(c) + " is out of range");
+    check_site_step(c, 0, "projected operator");
+    Engine& e = engine();
+    const double* L = left_env(c);
+    r1_ = right_env(c + 1);
+    const DevCore& X = x[c];
+    const DevCore& A = op_->tt.cores[c];
+    const size_t M = X.l * X.s, W = A.r;
+    const bool reuse = hl_site_ == c;
+    if (!reuse) {
+        grow(e, hl_, W * M * M);
+        if (prepared_ != c) prepared_ = (size_t)-1;
+        linsolve_hl_launch(L, A.buf.get(), hl_.get(), (int)X.l, (int)A.l, (int)X.s, (int)W, e.stream());
+        hl_site_ = c;
+    }
+    grow(e, t_, W * M * X.r);
+    T4A_HIP(hipGetLastError());
+    prepared1_ = c;
+    return reuse;
+}
+
+void ProjectedOperator::apply_one_site_prepared(const double* d_v, double* d_out)
+{
+    const DevCore& X = x[prepared1_];
+    const int M = (int)(X.l * X.s), cr = (int)X.r, W = (int)op_->tt.cores[prepared1_].r;
+    hipStream_t st = engine().stream();
+    gemm_launch(gemm_desc(W * M, cr, M, hl_.get(), W * M, d_v, M, t_.get(), W * M), st);
+    GemmDesc g = gemm_desc(M, cr, W * cr, t_.get(), M, r1_, cr, d_out, M);
+    g.transB = 1;
+    gemm_launch(g, st);
+}
+
+std::vector<double> ProjectedOperator::apply_one_site(size_t site, const double* v, bool* reused_hl)
+{
+    if (site >= x.size()) throw Error(T4A_GPU_INVALID_ARGUMENT, "projected operator: site " + std::to_string(site) + " is out of range");
+    const size_t len = x[site].size();
+    Engine& e = engine();
+    bool reused = false;
+    if (prepared1_ != site) reused = prepare_one_site(site);
+    if (reused_hl) *reused_hl = reused;
+    DevBuf<double> d_v, d_y;
+    d_v.reserve(len);
+    d_y.reserve(len);
+    T4A_HIP(hipMemcpyAsync(d_v.get(), v, sizeof(double) * len, hipMemcpyHostToDevice, e.stream()));
+    apply_one_site_prepared(d_v.get(), d_y.get());
+    T4A_HIP(hipGetLastError());
+    return to_host(e, d_y.get(), len);
+}
+
+void ProjectedOperator::time_one_site(size_t c, size_t reps, double ms[3])
+{
+    if (c >= x.size() || reps == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "time_one_site: the site must exist and reps be positive");
+    Engine& e = engine();
+    hipStream_t st = e.stream();
+    prepare_one_site(c);
+    const DevCore& X = x[c];
+    const DevCore& A = op_->tt.cores[c];
+    const double* L = left_env(c);
+    const size_t len = X.size();
+    const int M = (int)(X.l * X.s), cr = (int)X.r, W = (int)A.r;
+    DevBuf<double> v, y;
+    v.reserve(len);
+    y.reserve(len);
+    fill_launch(v.get(), len, 1.0 / std::sqrt((double)len), st);
+    GemmDesc g2 = gemm_desc(M, cr, W * cr, t_.get(), M, r1_, cr, y.get(), M);
+    g2.transB = 1;
+    EventTimer t;
+    t.init();
+    const std::function<void()> pieces[3] = {
+        [&] { linsolve_hl_launch(L, A.buf.get(), hl_.get(), (int)X.l, (int)A.l, (int)X.s, W, st); },
+        [&] { gemm_launch(gemm_desc(W * M, cr, M, hl_.get(), W * M, v.get(), M, t_.get(), W * M), st); },
+        [&] { gemm_launch(g2, st); },
+    };
+    for (int k = 0; k < 3; ++k) {
+        pieces[k](); // warm-up
+        T4A_HIP(hipEventRecord(t.a, st));
+        for (size_t r = 0; r < reps; ++r) pieces[k]();
+        T4A_HIP(hipEventRecord(t.b, st));
+        T4A_HIP(hipEventSynchronize(t.b));
+        T4A_HIP(hipGetLastError());
+        float f = 0.0f;
+        T4A_HIP(hipEventElapsedTime(&f, t.a, t.b));
+        ms[k] = (double)f / (double)reps;
+    }
+    e.sync();
 }
 
 void ProjectedOperator::product_left(const double* d_v) // T = HL V
@@ -827,6 +941,62 @@ void linsolve_orth(const double* basis, size_t len, size_t nb, double* w, double
     T4A_HIP(hipMemcpyAsync(w, dw.get(), sizeof(double) * len, hipMemcpyDeviceToHost, st));
     e.sync();
     *norm_out = hc[nb];
+}
+
+void krylov_orth_host(const double* basis, size_t len, size_t nb, double* w, KrylovDotsRoute route, double* h_out, double* norm_out)
+{
+    Engine e;
+    hipStream_t st = e.stream();
+    DevBuf<double> dV, dw, dh;
+    dV.reserve(len * nb);
+    dw.reserve(len);
+    dh.reserve(3 * nb + 1);
+    T4A_HIP(hipMemcpyAsync(dV.get(), basis, sizeof(double) * len * nb, hipMemcpyHostToDevice, st));
+    T4A_HIP(hipMemcpyAsync(dw.get(), w, sizeof(double) * len, hipMemcpyHostToDevice, st));
+    KrylovOrth gs(e);
+    gs.reserve(nb);
+    gs.set_dots_route(route);
+    gs.orth(dV.get(), len, (int)nb, dw.get(), len, dh.get(), dh.get() + nb + 1);
+    T4A_HIP(hipGetLastError());
+    std::vector<double> hc(nb + 1);
+    T4A_HIP(hipMemcpyAsync(hc.data(), dh.get(), sizeof(double) * (nb + 1), hipMemcpyDeviceToHost, st));
+    T4A_HIP(hipMemcpyAsync(h_out, dh.get() + nb + 1, sizeof(double) * 2 * nb, hipMemcpyDeviceToHost, st));
+    T4A_HIP(hipMemcpyAsync(w, dw.get(), sizeof(double) * len, hipMemcpyDeviceToHost, st));
+    e.sync();
+    *norm_out = hc[nb];
+}
+
+void krylov_time_dots(size_t len, size_t nb, size_t reps, double ms[2])
+{
+    if (len == 0 || nb == 0 || nb > LINSOLVE_RESTART_DIM_MAX || reps == 0)
+        throw Error(T4A_GPU_INVALID_ARGUMENT, "time_dots: len, nb and reps must be positive, nb at most " + std::to_string(LINSOLVE_RESTART_DIM_MAX));
+    if (above_int_max({len, nb + 1})) throw Error(T4A_GPU_INVALID_ARGUMENT, "time_dots: the basis holds more than INT_MAX elements");
+    require_device();
+    Engine e;
+    hipStream_t st = e.stream();
+    DevBuf<double> basis, part;
+    basis.reserve(len * (nb + 1));
+    part.reserve(nb * GS_MAX_WORKGROUPS);
+    fill_launch(basis.get(), len * (nb + 1), 1.0 / std::sqrt((double)len), st);
+    const double* w = basis.get() + len * nb;
+    EventTimer t;
+    t.init();
+    const std::function<void()> pieces[2] = {
+        [&] { gs_dots_launch(basis.get(), len, (int)nb, w, len, part.get(), st); },
+        [&] { gs_dots_wide_launch(basis.get(), len, (int)nb, w, len, part.get(), st); },
+    };
+    for (int k = 0; k < 2; ++k) {
+        pieces[k](); // warm-up
+        T4A_HIP(hipEventRecord(t.a, st));
+        for (size_t r = 0; r < reps; ++r) pieces[k]();
+        T4A_HIP(hipEventRecord(t.b, st));
+        T4A_HIP(hipEventSynchronize(t.b));
+        T4A_HIP(hipGetLastError());
+        float f = 0.0f;
+        T4A_HIP(hipEventElapsedTime(&f, t.a, t.b));
+        ms[k] = (double)f / (double)reps;
+    }
+    e.sync();
 }
 
 } // namespace t4a

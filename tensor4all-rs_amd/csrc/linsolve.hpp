@@ -47,6 +47,16 @@ void gs_normalize_launch(const double* w, size_t len, const double* npart, doubl
 void linsolve_residual_launch(const double* b, const double* x, const double* ax, double a0, double a1, double* r, size_t len, double* npart,
                               hipStream_t stream);
 void linsolve_scale_launch(const double* in, double alpha, double* out, size_t len, hipStream_t stream);
+// ---- kernels_tdvp.hip.  gs_dots with a second grid dimension over the basis vectors: workgroup (g, y) forms part[i + nb g] for the
+// GS_WIDE vectors i = GS_WIDE y .. of element group g, with the element partition, the summation order and the reduction tree of
+// gs_dots_launch: every part[i + nb g] has the same bits, and gs_update_launch runs unchanged behind it.
+constexpr int GS_WIDE = 8;
+void gs_dots_wide_launch(const double* V, size_t ld, int nb, const double* w, size_t len, double* part, hipStream_t stream);
+// Which launch forms the projections of an orthogonalisation pass.  Serial: gs_dots_launch, what Gmres and Lanczos run.  Wide:
+// gs_dots_wide_launch.  Auto: krylov_dots_route(len, nb) decides per pass (KrylovExpm of tdvp.hpp).
+enum class KrylovDotsRoute : int { Serial = 0, Wide = 1, Auto = 2 };
+// The rule of Auto, a function of the shape alone: Wide when the serial kernel would walk more than GS_WIDE vectors per workgroup.
+KrylovDotsRoute krylov_dots_route(size_t len, int nb);
 
 // ---- GMRES on (a0 + a1 H) x = b (krylov.rs:1083-1490).  The Arnoldi basis is built from the unshifted H, a0 and a1 enter the
 // Hessenberg column; Givens rotations and the triangular solve run on the host, which reads j + 2 doubles per step and one norm per
@@ -60,12 +70,13 @@ struct GmresResult {
     size_t apply_calls = 0;
 };
 using GmresApply = std::function<void(const double* d_v, double* d_out)>; // enqueues out = H v on the engine's stream
-// What both Krylov solvers (Gmres here, Lanczos of dmrg.hpp) launch around their apply: the two-pass orthogonalisation step, the norm
+// What the Krylov solvers (Gmres here, Lanczos of dmrg.hpp, KrylovExpm of tdvp.hpp) launch around their apply: the two-pass orthogonalisation step, the norm
 // read by the host, and the buffers of the partial sums.
 class KrylovOrth {
 public:
     explicit KrylovOrth(Engine& e) : eng_(e) {}
     void reserve(size_t nb_max); // at most nb_max basis vectors per pass
+    void set_dots_route(KrylovDotsRoute r) { route_ = r; } // Serial unless a solver asks otherwise; the results have the same bits
     // One two-pass orthogonalisation step: w against the nb columns of V (leading dimension ld), then normalised in place.
     // d_hcol: nb + 1 doubles (the column of H, h_{nb} = the norm); d_hpass (may be null): 2 nb doubles, the coefficients of pass 1 and of pass 2.
     void orth(const double* d_V, size_t ld, int nb, double* d_w, size_t len, double* d_hcol, double* d_hpass);
@@ -76,8 +87,10 @@ public:
     Engine& engine() { return eng_; }
 
 private:
+    void dots(const double* d_V, size_t ld, int nb, const double* d_w, size_t len);
     Engine& eng_;
     DevBuf<double> part_, npart_, scal_;
+    KrylovDotsRoute route_ = KrylovDotsRoute::Serial;
 };
 class Gmres {
 public:
@@ -135,6 +148,10 @@ void linsolve_validate_shapes(const std::vector<std::array<size_t, 4>>& op, cons
 // The INT_MAX bound of the buffers of the bond step (i, i + 1): HL, HR, T and a Krylov basis of basis_dim + 1 columns, M = chi_l d1,
 // N = d2 chi_r, W the operator bond between the two sites.  INVALID_ARGUMENT "<who>: a work buffer of the bond step (i, i+1) ...".
 void check_bond_step_dims(const char* who, size_t i, size_t chi_l, size_t d1, size_t d2, size_t chi_r, size_t W, size_t basis_dim);
+// The same bound for the one-site step at site c: HL (W M M), T (W M chi_r), the environment R_{c+1} (chi_r W chi_r) and a Krylov basis of
+// basis_dim + 1 columns of M chi_r elements, M = chi_l d, W the operator bond to the right of the site.
+// INVALID_ARGUMENT "<who>: a work buffer of the one-site step at site c ...".
+void check_site_step_dims(const char* who, size_t c, size_t chi_l, size_t d, size_t chi_r, size_t W, size_t basis_dim);
 
 // ||(a0 + a1 A) x - b|| / ||b||, the absolute norm when ||b|| <= 1e-15: the exact naive apply, add / sub, and the norm of the residual
 // train from its QR right-canonical form (the transfer-matrix norm2 would lose half of the digits in the cancellation).
@@ -151,6 +168,9 @@ public:
     std::array<size_t, 4> local_dims(size_t site) const;
     // y = H v for the region (site, site + 1), host arrays of chi_l d_i d_{i+1} chi_r doubles
     std::vector<double> apply(size_t site, const double* v);
+    // y = H v for the one-site region `site`, host arrays of chi_l d chi_r doubles: y[b, s, b'] = sum L_c[b, w, a] A_c[w, s, t, w']
+    // v[a, t, a'] R_{c+1}[b', w', a'].  *reused_hl (may be null): whether the HL of an earlier prepare of the bond (site, site + 1) served.
+    std::vector<double> apply_one_site(size_t site, const double* v, bool* reused_hl = nullptr);
     // side 0: L_bond[chi, W, chi] of the sites < bond; side 1: R_bond[chi, W, chi] of the sites >= bond (bond <= n); dims receives the shape
     std::vector<double> environment(int side, size_t bond, size_t dims[3]);
     // the caches that contain `site` go stale: L_j for j > site, R_j for j <= site
@@ -165,6 +185,17 @@ public:
     const double* right_rhs_env(size_t i);
     void prepare(size_t site);                               // environments and HL, HR of the bond (site, site + 1)
     void apply_prepared(const double* d_v, double* d_out);   // the two products
+    // The one-site region c (the site correction of TDVP): environments L_c and R_{c+1} and HL = L_c A_c, (W M) x M with M = chi_l d and
+    // W the bond to the right of A_c, by linsolve_hl_launch — unless hl_ still holds it from prepare(c), the bond step that moved left
+    // onto c (HL depends on the sites < c and on the operator only); -> whether it was reused.
+    bool prepare_one_site(size_t c);
+    // T = HL V, (W M) x chi_r, then Y = T_view R_view^T: T read as M x (W chi_r) with ld M, R_{c+1}[b', w', a'] as chi_r x (W chi_r) with
+    // ld chi_r — the column index is w' + W a' in both views.  2 W M chi_r (M + chi_r) flops.
+    void apply_one_site_prepared(const double* d_v, double* d_out);
+    void check_site_step(size_t c, size_t basis_dim, const char* who) const;  // check_site_step_dims at the present bonds
+    // Probe: device ms of the three launches of the one-site apply at site c (linsolve_hl, T = HL V, Y = T R^T), events around `reps`
+    // launches behind a warm-up launch
+    void time_one_site(size_t c, size_t reps, double ms[3]);
     // Probe: device time in ms (HIP events around `reps` launches behind one warm-up launch) of the five launches of an Arnoldi step
     // with nb basis vectors at the region (site, site + 1): T = HL V, Y = T HR, gs_dots, gs_update, gs_normalize
     void time_step(size_t site, size_t nb, size_t reps, double ms[5]);
@@ -187,6 +218,9 @@ private:
     std::vector<char> okL_, okR_;
     DevBuf<double> hl_, hr_, t_, t1_, p1_, p2_;
     size_t prepared_ = (size_t)-1;
+    size_t prepared1_ = (size_t)-1;  // the site of prepare_one_site
+    size_t hl_site_ = (size_t)-1;    // hl_ holds L_c A_c of this site c
+    const double* r1_ = nullptr;     // R_{c+1} of prepare_one_site
 };
 
 // The apply on caller-supplied environments (host arrays), launched exactly as the sweeps launch it: L[chi_l, W_l, chi_l],
@@ -205,5 +239,10 @@ GmresResult gmres_dense(const double* H, size_t n, const double* b, const double
                         size_t restart_dim, size_t max_restarts, double* x_out);
 // Test hook: Gmres::orth on host arrays: basis len x nb, w len (in/out), h_out 2 nb (pass 1, pass 2), *norm_out
 void linsolve_orth(const double* basis, size_t len, size_t nb, double* w, double* h_out, double* norm_out);
+// Test hook: KrylovOrth::orth with the given route on host arrays, arguments as linsolve_orth
+void krylov_orth_host(const double* basis, size_t len, size_t nb, double* w, KrylovDotsRoute route, double* h_out, double* norm_out);
+// Probe hook: device ms (events around `reps` launches behind a warm-up launch) of gs_dots_launch [0] and gs_dots_wide_launch [1] with nb
+// basis vectors of length len, behind the argument checks (INVALID_ARGUMENT) and require_device
+void krylov_time_dots(size_t len, size_t nb, size_t reps, double ms[2]);
 
 } // namespace t4a

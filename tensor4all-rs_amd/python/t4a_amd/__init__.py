@@ -2157,3 +2157,7 @@ from .linsolve import (GmresToleranceMode, LinsolveOptions, LinsolveOptionsC, Sq
 # imported as `from t4a_amd.dmrg import ...` or reached as t4a_amd.dmrg_module
 from . import dmrg as dmrg_module  # noqa: E402
 from .dmrg import (HermitianLanczosOptions, LanczosOptionsC, DmrgOptions, DmrgOptionsC, DmrgResult, dmrg, dmrg_energy)  # noqa: E402,F401
+# t4a_amd.tdvp is the function as well; its module (the hooks _krylov_expm_dense, _krylov_orth, _apply_one_site, tdvp_plan) is
+# imported as `from t4a_amd.tdvp import ...` or reached as t4a_amd.tdvp_module
+from . import tdvp as tdvp_module  # noqa: E402
+from .tdvp import (HermitianKrylovExpmOptions, KrylovExpmOptionsC, TdvpOptions, TdvpOptionsC, TdvpResult, tdvp)  # noqa: E402,F401
