@@ -172,6 +172,9 @@ __device__ __forceinline__ void rrlu_xcd2_body(const RrluXcdArgs& p, const RrluX
     N = __builtin_amdgcn_readfirstlane(N);
     max_steps = __builtin_amdgcn_readfirstlane(max_steps);
     lda = __builtin_amdgcn_readfirstlane(lda);
+    // row slots that hold rows of THIS matrix (xcd_live_slots, kernels_rrlu_xcd_common.hpp): the update, the publication and the
+    // division of the step loop leave the others out; the rare paths (exact sweep, exact pick) and the write-out test i < M anyway
+    const int nlive = __builtin_amdgcn_readfirstlane(xcd_live_slots(M, RPT));
 
     // ---- my columns (per wave): g + NW q; my rows (per lane): lane + 64 r ----
     unsigned active = 0u; // bit q: column g + NW q exists and is still in the trailing block (wave-uniform)
@@ -431,10 +434,10 @@ __device__ __forceinline__ void rrlu_xcd2_body(const RrluXcdArgs& p, const RrluX
         constexpr int CS = 256, SLOTB = (MP / 16) * CS; // chunk stride / bytes of a column slot
         const int myslot = (int)cols_base + (par * NW + g) * SLOTB + (lane >> 4) * CS + (lane & 15) * 16; // byte offset of my row `lane` in the mailbox
         if (early_pub) {
-            if (qstar == 0) xcd_publish_column<0, RPT, ST_AUX>(a[0], mail, myslot, tag, 4 * CS);
-            if constexpr (CPT > 1) if (qstar == 1) xcd_publish_column<1, RPT, ST_AUX>(a[1], mail, myslot, tag, 4 * CS);
-            if constexpr (CPT > 2) if (qstar == 2) xcd_publish_column<2, RPT, ST_AUX>(a[2], mail, myslot, tag, 4 * CS);
-            if constexpr (CPT > 3) if (qstar == 3) xcd_publish_column<3, RPT, ST_AUX>(a[3], mail, myslot, tag, 4 * CS);
+            if (qstar == 0) xcd_publish_column<0, RPT, ST_AUX>(a[0], mail, myslot, tag, 4 * CS, nlive);
+            if constexpr (CPT > 1) if (qstar == 1) xcd_publish_column<1, RPT, ST_AUX>(a[1], mail, myslot, tag, 4 * CS, nlive);
+            if constexpr (CPT > 2) if (qstar == 2) xcd_publish_column<2, RPT, ST_AUX>(a[2], mail, myslot, tag, 4 * CS, nlive);
+            if constexpr (CPT > 3) if (qstar == 3) xcd_publish_column<3, RPT, ST_AUX>(a[3], mail, myslot, tag, 4 * CS, nlive);
         }
         XSTAMP(2);
 
@@ -728,10 +731,10 @@ __device__ __forceinline__ void rrlu_xcd2_body(const RrluXcdArgs& p, const RrluX
         const int wag = (int)recw;
         // the winner did not speculate: its column goes out now
         if (g == wag && !early_pub) {
-            if (qstar == 0) xcd_publish_column<0, RPT, ST_AUX>(a[0], mail, myslot, tag, 4 * CS);
-            if constexpr (CPT > 1) if (qstar == 1) xcd_publish_column<1, RPT, ST_AUX>(a[1], mail, myslot, tag, 4 * CS);
-            if constexpr (CPT > 2) if (qstar == 2) xcd_publish_column<2, RPT, ST_AUX>(a[2], mail, myslot, tag, 4 * CS);
-            if constexpr (CPT > 3) if (qstar == 3) xcd_publish_column<3, RPT, ST_AUX>(a[3], mail, myslot, tag, 4 * CS);
+            if (qstar == 0) xcd_publish_column<0, RPT, ST_AUX>(a[0], mail, myslot, tag, 4 * CS, nlive);
+            if constexpr (CPT > 1) if (qstar == 1) xcd_publish_column<1, RPT, ST_AUX>(a[1], mail, myslot, tag, 4 * CS, nlive);
+            if constexpr (CPT > 2) if (qstar == 2) xcd_publish_column<2, RPT, ST_AUX>(a[2], mail, myslot, tag, 4 * CS, nlive);
+            if constexpr (CPT > 3) if (qstar == 3) xcd_publish_column<3, RPT, ST_AUX>(a[3], mail, myslot, tag, 4 * CS, nlive);
         }
         // everybody fetches the winner's full key (one granule, the same for all lanes) and — waves 1 .. 7 — its rows of the
         // winner's column: lane + 64 (sr0 + 7 j)
@@ -739,7 +742,7 @@ __device__ __forceinline__ void rrlu_xcd2_body(const RrluXcdArgs& p, const RrluX
         u32x4 cc[XR];
 #pragma unroll
         for (int j = 0; j < XR; ++j)
-            if (sr0 >= 0 && sr0 + X2_DIVW * j < RPT) cc[j] = __builtin_amdgcn_raw_buffer_load_b128(mail, slot_off + j * X2_DIVW * 4 * CS, 0, BUF_SC1);
+            if (sr0 >= 0 && sr0 + X2_DIVW * j < nlive) cc[j] = __builtin_amdgcn_raw_buffer_load_b128(mail, slot_off + j * X2_DIVW * 4 * CS, 0, BUF_SC1);
         // who sits at position kn now (the polling wave moves them behind its stop test)
         int rk_ = 0, ck_ = 0;
         int prp_ = 0, pcp_ = 0; // ... and where the pivot's row and column sit
@@ -819,7 +822,7 @@ __device__ __forceinline__ void rrlu_xcd2_body(const RrluXcdArgs& p, const RrluX
                 bool ok = true;
 #pragma unroll
                 for (int j = 0; j < XR; ++j)
-                    if (sr0 + X2_DIVW * j < RPT) ok &= ((cc[j].x ^ cc[j].y ^ cc[j].z ^ cc[j].w) == tag);
+                    if (sr0 + X2_DIVW * j < nlive) ok &= ((cc[j].x ^ cc[j].y ^ cc[j].z ^ cc[j].w) == tag);
                 if (__all(ok)) break;
                 xcd_poll_again();
                 if (++spins > XSPIN) {
@@ -830,7 +833,7 @@ __device__ __forceinline__ void rrlu_xcd2_body(const RrluXcdArgs& p, const RrluX
                 }
 #pragma unroll
                 for (int j = 0; j < XR; ++j)
-                    if (sr0 + X2_DIVW * j < RPT) cc[j] = __builtin_amdgcn_raw_buffer_load_b128(mail, slot_off + j * X2_DIVW * 4 * CS, 0, BUF_SC1);
+                    if (sr0 + X2_DIVW * j < nlive) cc[j] = __builtin_amdgcn_raw_buffer_load_b128(mail, slot_off + j * X2_DIVW * 4 * CS, 0, BUF_SC1);
             }
             XSTAMP(12);
             // x / p through the shared refined reciprocal (bitwise the IEEE quotient, see refined_rcp); zeros keep the sign
@@ -840,7 +843,7 @@ __device__ __forceinline__ void rrlu_xcd2_body(const RrluXcdArgs& p, const RrluX
 #pragma unroll
             for (int j = 0; j < XR; ++j) {
                 lq[j] = 0.0;
-                if (sr0 + X2_DIVW * j < RPT) {
+                if (sr0 + X2_DIVW * j < nlive) {
                     const double x = mk_f64(cc[j].x, cc[j].y);
                     const double q0 = x * rp;
                     const double qf = __builtin_fma(__builtin_fma(-wval, q0, x), rp, q0);
@@ -854,16 +857,17 @@ __device__ __forceinline__ void rrlu_xcd2_body(const RrluXcdArgs& p, const RrluX
             if (__ballot(slow) != 0ull) {
 #pragma unroll
                 for (int j = 0; j < XR; ++j)
-                    if (sr0 + X2_DIVW * j < RPT) {
+                    if (sr0 + X2_DIVW * j < nlive) {
                         const double x = mk_f64(cc[j].x, cc[j].y);
                         if (!(p_mid & (exp_mid(x) | (x == 0.0)))) lq[j] = x / wval;
                     }
             }
             // (rows pivoted before hold exact zeros in the published column: l = 0; the pivot row gets pivot / pivot = 1;
-            // slot rows beyond M are zeros divided by the pivot)
+            // slot rows beyond M are zeros divided by the pivot; a slot without any row of the matrix keeps the +0.0 of the prologue,
+            // which nobody multiplies)
 #pragma unroll
             for (int j = 0; j < XR; ++j)
-                if (sr0 + X2_DIVW * j < RPT) lbuf[lane * LSTR + sr0 + X2_DIVW * j] = lq[j];
+                if (sr0 + X2_DIVW * j < nlive) lbuf[lane * LSTR + sr0 + X2_DIVW * j] = lq[j];
         }
         XSTAMP(4);
         __syncthreads(); // (C)
@@ -899,14 +903,27 @@ __device__ __forceinline__ void rrlu_xcd2_body(const RrluXcdArgs& p, const RrluX
         if constexpr (NH == 1) {
 #pragma unroll
             for (int q = 0; q < CPT; ++q) {
+                // The two waves of a SIMD share its vector issue, arbitrated by priority, then age: left alone, waves 0 .. 3 run their
+                // update nearly unimpeded and waves 4 .. 7 get the leftover slots, finish some 350 cycles later — and the pick waits for the
+                // LAST early key.  The younger half runs its first column at raised priority and drops back: both halves then finish
+                // closer together (measured at 12 x 3; profiles/xcd2_live_slots_parent_vs_branch.txt).  Back at 0 before any barrier.
+                if constexpr (CPT > 1) {
+                    if (q == 0) {
+                        if (wave >= XWAVES / 2) __builtin_amdgcn_s_setprio(1);
+                    } else if (q == 1) {
+                        __builtin_amdgcn_s_setprio(0);
+                    }
+                }
                 mq[q] = 0u;
                 if (active & (1u << q)) {
 #pragma unroll
                     for (int r = 0; r < RPT; ++r) { // in place (see sub_in_place); un-fused, one rounding per operation like the reference
+                        if (r >= xcd_fixed_slots(RPT) && r >= nlive) continue; // (a slot without rows stays +0.0)
                         double t = a[q].get(r);
                         sub_in_place(t, l[r] * u[q]);
                         a[q].set(r, t);
                     }
+                    // (the maxima still read every slot: two per instruction, and a high word of 0 changes nothing)
                     mq[q] = x2_colmax_hi<0, RPT>(0u, a[q]);
                 }
             }
@@ -925,6 +942,7 @@ __device__ __forceinline__ void rrlu_xcd2_body(const RrluXcdArgs& p, const RrluX
                     if (active & (1u << q)) {
 #pragma unroll
                         for (int r = 0; r < HR; ++r) {
+                            if (h * HR + r >= xcd_fixed_slots(RPT) && h * HR + r >= nlive) continue;
                             double t = a[q].get(h * HR + r);
                             sub_in_place(t, l[r] * u[q]);
                             a[q].set(h * HR + r, t);

@@ -256,12 +256,28 @@ template <int RPT> struct XSlab {
         }
     }
 };
+// Live row slots (second generation).  A launch whose matrix has M rows fills ceil(M / 64) of the RPT row slots of its plan; the
+// slots behind them hold +0.0 from the load on and stay +0.0 (+0 - l u is +0 for l = +-0 and finite u).  Nobody reads them for a
+// result (the write-out and the exact sweeps test i < M, the column maxima see a high word of 0), so the step may leave them out:
+// the rank-1 update does not touch them, the publication does not store them, the dividing waves neither fetch nor divide them.
+// Slots are compile-time registers, so leaving one out is a wave-uniform branch around it.  Only the LAST slot of a plan gets one:
+// the saturated bonds of the chain (679 - 699 rows in a 768-row plan) leave exactly one empty, and every further conditional slot
+// is one more scalar compare and branch per owned column and step for the launches that fill their plan.
+__host__ __device__ constexpr int xcd_fixed_slots(int rpt) { return rpt > 1 ? rpt - 1 : rpt; } // slots below this one are always live
+// row slots the step treats as live: the fixed ones, and the conditional ones that hold rows of the matrix
+__device__ __forceinline__ int xcd_live_slots(int M, int rpt)
+{
+    const int nrs = (M + 63) >> 6, fixed = xcd_fixed_slots(rpt);
+    return nrs < fixed ? fixed : (nrs > rpt ? rpt : nrs);
+}
+// (nlive: xcd_live_slots of the launch, wave-uniform — the readers of the slot skip exactly the same granules)
 template <int Q, int RPT, int AUX = 0>
-__device__ __forceinline__ void xcd_publish_column(const XSlab<RPT>& col, __amdgpu_buffer_rsrc_t mail, int myslot, unsigned tag, int rstride = 1024)
+__device__ __forceinline__ void xcd_publish_column(const XSlab<RPT>& col, __amdgpu_buffer_rsrc_t mail, int myslot, unsigned tag, int rstride, int nlive)
 {
     asm volatile("; column slot %0" ::"n"(Q));
 #pragma unroll
     for (int r = 0; r < RPT; ++r) {
+        if (r >= xcd_fixed_slots(RPT) && r >= nlive) continue;
         const double av = col.get(r);
         u32x4 gv;
         gv.x = lo32(av);
