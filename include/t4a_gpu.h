@@ -1433,6 +1433,71 @@ t4a_gpu_status t4a_gpu_tdvp(const t4a_gpu_mpo* op, const t4a_gpu_tt* init, size_
 t4a_gpu_status t4a_gpu_krylov_expm_dense(const double* H, size_t n, const double* v0, double tau, const t4a_gpu_krylov_expm_options* options,
                                          double* out, size_t* iterations, double* error_estimate, int32_t* converged, size_t* time_splits);
 
+/* ---- global subspace expansion (GSE) and GSE-TDVP: tensor4all-treetn's global_subspace_expand, .._with_references and gse_tdvp
+ * (crates/tensor4all-treetn/src/gse.rs) for a chain, f64, one site index per node, V_in = V_out.  The expansion widens every bond of
+ * `init` by the directions of the references that it does not span yet and does not change the state.  The target and the references
+ * are canonicalised onto `center` (any site); the edges are walked from the leaves to the centre, the left arm first.  Per edge: the
+ * old row basis B of the child (thin SVD), the references projected off it and stacked (t4a_gpu_gse_project), the thin SVD of the
+ * stack — the host reads its singular values and the trace t = sum |R_j|_F^2 and keeps the right singular vectors with
+ * sigma^2 > density_weight_cutoff * t —, and the parents of all trains absorbing the coefficients (t4a_gpu_gse_absorb).
+ * Deviations: the SVD of the stack replaces the reference's eigendecomposition of the Hermitianised P rho P / t (the same eigenvalues
+ * sigma^2 / t and eigenspaces; the kept rows come in descending order: a permutation of the gauge; hermitian_tol is validated and has
+ * nothing else to check); the references of t4a_gpu_gse_krylov_references are built by this project's simplett zip-up
+ * (t4a_gpu_mpo_contract, ZipUp, SVD, max_bond_dim = reference_max_bond_dim, the tolerance of reference_svd_policy or 1e-12), not by
+ * treetn's apply_linear_operator; more than 8 references are NOT_IMPLEMENTED.
+ * Errors (INVALID_ARGUMENT, on the host before the device is touched): "invalid GSE option density_weight_cutoff: must be finite and
+ * non-negative", "invalid GSE option hermitian_tol: must be finite and non-negative", "invalid GSE option reference_max_bond_dim: must
+ * be greater than zero when set", "GSE center <c> is not a state node", "GSE requires target, references, and operator support to have
+ * the same tree topology" (lengths differ), "invalid GSE mapping at node <i>: reference site dimension does not match target";
+ * t4a_gpu_gse_tdvp adds the refusals of t4a_gpu_tdvp unchanged. */
+typedef struct {
+    size_t krylov_dim;                      /* 0 */
+    int32_t has_reference_max_bond_dim;     /* 0: max(link_dims(init)) + 1 */
+    size_t reference_max_bond_dim;
+    int32_t has_reference_svd_policy;       /* 0: threshold 1e-12 */
+    t4a_gpu_svd_policy reference_svd_policy;
+    double density_weight_cutoff;           /* 1e-12 */
+    double hermitian_tol;                   /* 1e-12 */
+    int32_t normalize_references;           /* 1 */
+    int32_t expand_before_first_sweep;      /* 1 */
+} t4a_gpu_gse_options;
+t4a_gpu_status t4a_gpu_gse_options_default(t4a_gpu_gse_options* out);
+/* The option and shape checks of the expansion on plain dimension lists (host only): ref_dims3 holds the dims3 of the n_refs
+ * references one after the other, ref_lens[j] the number of sites of reference j. */
+t4a_gpu_status t4a_gpu_gse_check_shapes(const t4a_gpu_gse_options* options, const size_t* state_dims3, size_t n_state, const size_t* ref_dims3,
+                                        const size_t* ref_lens, size_t n_refs, size_t center);
+/* build_references: H psi, H^2 psi, .. (krylov_dim of them) into refs[0 .. krylov_dim), which the caller releases. */
+t4a_gpu_status t4a_gpu_gse_krylov_references(const t4a_gpu_mpo* op, const t4a_gpu_tt* init, const t4a_gpu_gse_options* options, size_t capacity,
+                                             t4a_gpu_tt** refs, size_t* n_refs);
+t4a_gpu_status t4a_gpu_gse_expand_with_references(const t4a_gpu_tt* init, const t4a_gpu_tt* const* references, size_t n_refs, size_t center,
+                                                  const t4a_gpu_gse_options* options, t4a_gpu_tt** state, size_t* references_built,
+                                                  size_t* edges_processed, size_t* bonds_expanded, size_t* max_added_basis);
+t4a_gpu_status t4a_gpu_gse_expand(const t4a_gpu_mpo* op, const t4a_gpu_tt* init, size_t center, const t4a_gpu_gse_options* options, t4a_gpu_tt** state,
+                                  size_t* references_built, size_t* edges_processed, size_t* bonds_expanded, size_t* max_added_basis);
+/* gse_tdvp: before sweep s an expansion when krylov_dim > 0 and (s > 0 or expand_before_first_sweep), then t4a_gpu_tdvp with nsweeps = 1. */
+t4a_gpu_status t4a_gpu_gse_tdvp(const t4a_gpu_mpo* op, const t4a_gpu_tt* init, size_t center, const t4a_gpu_gse_options* gse,
+                                const t4a_gpu_tdvp_options* tdvp, t4a_gpu_tt** state, size_t* sweeps_completed, size_t* local_updates,
+                                size_t* gse_expansions, double* max_error_estimate, size_t* max_krylov_iterations);
+/* Test hooks: the two launches of an edge on raw column-major operands.  orient 0: a matrix over (bond row a, q index j) is na x q,
+ * X[a + na j] (the child's first leg is the bond to its parent); orient 1: X[j + q a] (its last leg is).  route 0: the fused launch,
+ * 1: the same products composed from the GEMM.
+ * _project: refs holds the K references R_j (rho[j] x q) one after the other, B is kb x q; stack receives N_j = R_j - (R_j B^T) B
+ * stacked over j as (sum rho) x q in the same orientation, *trace = sum_j |R_j|_F^2.
+ * _absorb: children C_j (r[j] x q) and parents one after the other — orient 0: parent j is L[j] x r[j], orient 1: r[j] x L[j], both
+ * column-major; Bn is kn x q; out receives parent_j (C_j Bn^T) as L[j] x kn (orient 1: (Bn C_j^T) parent_j as kn x L[j]) one after
+ * the other.  At most 8 references / 9 trains; every dimension positive and every matrix within INT_MAX elements. */
+t4a_gpu_status t4a_gpu_gse_project(int32_t orient, size_t q, const double* refs, const size_t* rho, size_t K, const double* B, size_t kb,
+                                   int32_t route, double* stack, double* trace);
+t4a_gpu_status t4a_gpu_gse_absorb(int32_t orient, size_t q, const double* children, const size_t* r, const double* parents, const size_t* L,
+                                  size_t n_trains, const double* Bn, size_t kn, int32_t route, double* out);
+/* The route the driver takes at an edge with q columns and target bond `bond` (host only): *route = 0 the fused launches (q * bond <=
+ * 8192), 1 the GEMM composition.  _set_route forces one route for every edge of every later call (0 or 1; -1: back to the rule): a test
+ * hook, so that both routes of the driver run on small trains. */
+t4a_gpu_status t4a_gpu_gse_route(size_t q, size_t bond, int32_t* route);
+t4a_gpu_status t4a_gpu_gse_set_route(int32_t route);
+/* Probe: device ms of project [0] fused [1] GEMMs and absorb [2] fused [3] GEMMs at bond chi, site dimension d, K references of bond chi + 1. */
+t4a_gpu_status t4a_gpu_gse_time_routes(size_t chi, size_t d, size_t K, size_t reps, double* ms4);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

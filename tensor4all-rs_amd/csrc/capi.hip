@@ -21,6 +21,7 @@
 #include "tt_canonical.hpp"
 #include "dmrg.hpp"
 #include "tdvp.hpp"
+#include "gse.hpp"
 #include "linsolve.hpp"
 
 struct t4a_gpu_tci2 {
@@ -4693,6 +4694,258 @@ t4a_gpu_status t4a_gpu_krylov_expm_dense(const double* H, size_t n, const double
         *error_estimate = r.error_estimate;
         *converged = r.converged;
         *time_splits = r.time_splits;
+    });
+}
+
+// ---- global subspace expansion and GSE-TDVP (gse.hpp) ----
+t4a_gpu_status t4a_gpu_gse_options_default(t4a_gpu_gse_options* out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(out);
+        const GseOptions d;
+        *out = t4a_gpu_gse_options{};
+        out->krylov_dim = d.krylov_dim;
+        out->has_reference_max_bond_dim = d.has_reference_max_bond_dim;
+        out->reference_max_bond_dim = d.reference_max_bond_dim;
+        out->has_reference_svd_policy = d.has_reference_svd_policy;
+        out->reference_svd_policy =
+            t4a_gpu_svd_policy{d.reference_svd_policy.threshold, d.reference_svd_policy.scale, d.reference_svd_policy.measure, d.reference_svd_policy.rule};
+        out->density_weight_cutoff = d.density_weight_cutoff;
+        out->hermitian_tol = d.hermitian_tol;
+        out->normalize_references = d.normalize_references;
+        out->expand_before_first_sweep = d.expand_before_first_sweep;
+    });
+}
+
+extern "C++" {
+static GseOptions convert_gse_options(const t4a_gpu_gse_options* p)
+{
+    GseOptions o;
+    o.krylov_dim = p->krylov_dim;
+    o.has_reference_max_bond_dim = p->has_reference_max_bond_dim != 0;
+    o.reference_max_bond_dim = p->reference_max_bond_dim;
+    o.has_reference_svd_policy = p->has_reference_svd_policy != 0;
+    if (o.has_reference_svd_policy)
+        o.reference_svd_policy = SvdPolicy{p->reference_svd_policy.threshold, p->reference_svd_policy.scale, p->reference_svd_policy.measure, p->reference_svd_policy.rule};
+    o.density_weight_cutoff = p->density_weight_cutoff;
+    o.hermitian_tol = p->hermitian_tol;
+    o.normalize_references = p->normalize_references != 0;
+    o.expand_before_first_sweep = p->expand_before_first_sweep != 0;
+    o.validate();
+    return o;
+}
+static void gse_counters(const GseResult& r, size_t* references_built, size_t* edges_processed, size_t* bonds_expanded, size_t* max_added_basis)
+{
+    *references_built = r.references_built;
+    *edges_processed = r.edges_processed;
+    *bonds_expanded = r.bonds_expanded;
+    *max_added_basis = r.max_added_basis;
+}
+// the ragged shape lists of the hooks as ints: every entry positive, at most `max_jobs` of them
+static std::vector<int> gse_int_list(const size_t* v, size_t n, size_t max_jobs, const char* who)
+{
+    if (n == 0 || n > max_jobs) throw Error(T4A_GPU_INVALID_ARGUMENT, std::string(who) + ": between 1 and " + std::to_string(max_jobs) + " operands");
+    T4A_REQUIRE_PTR(v);
+    std::vector<int> out(n);
+    for (size_t i = 0; i < n; ++i) {
+        if (v[i] == 0 || v[i] > (size_t)INT_MAX) throw Error(T4A_GPU_INVALID_ARGUMENT, std::string(who) + ": every dimension must be positive and at most INT_MAX");
+        out[i] = (int)v[i];
+    }
+    return out;
+}
+static void gse_require_fits(size_t a, size_t b, const char* who)
+{
+    if (a == 0 || b == 0 || a > (size_t)INT_MAX || b > (size_t)INT_MAX / a)
+        throw Error(T4A_GPU_INVALID_ARGUMENT, std::string(who) + ": every dimension must be positive and every matrix within INT_MAX elements");
+}
+}
+
+t4a_gpu_status t4a_gpu_gse_check_shapes(const t4a_gpu_gse_options* options, const size_t* state_dims3, size_t n_state, const size_t* ref_dims3,
+                                        const size_t* ref_lens, size_t n_refs, size_t center)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(options);
+        (void)convert_gse_options(options);
+        if (n_state) T4A_REQUIRE_PTR(state_dims3);
+        if (n_refs) T4A_REQUIRE_PTR(ref_lens);
+        std::vector<std::vector<std::array<size_t, 3>>> refs;
+        size_t off = 0;
+        for (size_t j = 0; j < n_refs; ++j) {
+            if (ref_lens[j]) T4A_REQUIRE_PTR(ref_dims3);
+            refs.push_back(dims3_list(ref_dims3 + 3 * off, ref_lens[j]));
+            off += ref_lens[j];
+        }
+        gse_validate_shapes(dims3_list(state_dims3, n_state), refs, center);
+    });
+}
+
+t4a_gpu_status t4a_gpu_gse_krylov_references(const t4a_gpu_mpo* op, const t4a_gpu_tt* init, const t4a_gpu_gse_options* options, size_t capacity,
+                                             t4a_gpu_tt** refs, size_t* n_refs)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(n_refs);
+        *n_refs = 0;
+        T4A_REQUIRE_PTR(options);
+        const GseOptions o = convert_gse_options(options);
+        T4A_REQUIRE_PTR(op);
+        T4A_REQUIRE_PTR(init);
+        if (capacity < o.krylov_dim) throw Error(T4A_GPU_BUFFER_TOO_SMALL, "gse_krylov_references: krylov_dim references are returned");
+        if (o.krylov_dim) T4A_REQUIRE_PTR(refs);
+        std::vector<std::unique_ptr<TensorTrain>> r = gse_krylov_references(*op->impl, const_cast<t4a_gpu_tt*>(init)->impl, o);
+        std::vector<std::unique_ptr<t4a_gpu_tt>> hs;
+        for (auto& t : r) hs.push_back(std::make_unique<t4a_gpu_tt>(t->cores, t->eng.stream()));
+        for (size_t k = 0; k < hs.size(); ++k) refs[k] = hs[k].release();
+        *n_refs = r.size();
+    });
+}
+
+t4a_gpu_status t4a_gpu_gse_expand_with_references(const t4a_gpu_tt* init, const t4a_gpu_tt* const* references, size_t n_refs, size_t center,
+                                                  const t4a_gpu_gse_options* options, t4a_gpu_tt** state, size_t* references_built,
+                                                  size_t* edges_processed, size_t* bonds_expanded, size_t* max_added_basis)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(state);
+        *state = nullptr;
+        T4A_REQUIRE_PTR(options);
+        const GseOptions o = convert_gse_options(options);
+        T4A_REQUIRE_PTR(init);
+        T4A_REQUIRE_PTR(references_built);
+        T4A_REQUIRE_PTR(edges_processed);
+        T4A_REQUIRE_PTR(bonds_expanded);
+        T4A_REQUIRE_PTR(max_added_basis);
+        if (n_refs) T4A_REQUIRE_PTR(references);
+        std::vector<TensorTrain*> refs;
+        for (size_t j = 0; j < n_refs; ++j) {
+            T4A_REQUIRE_PTR(references[j]);
+            refs.push_back(&const_cast<t4a_gpu_tt*>(references[j])->impl);
+        }
+        GseResult r = global_subspace_expand_with_references(const_cast<t4a_gpu_tt*>(init)->impl, refs, center, o);
+        *state = new t4a_gpu_tt(r.state->cores, r.state->eng.stream());
+        gse_counters(r, references_built, edges_processed, bonds_expanded, max_added_basis);
+    });
+}
+
+t4a_gpu_status t4a_gpu_gse_expand(const t4a_gpu_mpo* op, const t4a_gpu_tt* init, size_t center, const t4a_gpu_gse_options* options, t4a_gpu_tt** state,
+                                  size_t* references_built, size_t* edges_processed, size_t* bonds_expanded, size_t* max_added_basis)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(state);
+        *state = nullptr;
+        T4A_REQUIRE_PTR(options);
+        const GseOptions o = convert_gse_options(options);
+        T4A_REQUIRE_PTR(op);
+        T4A_REQUIRE_PTR(init);
+        T4A_REQUIRE_PTR(references_built);
+        T4A_REQUIRE_PTR(edges_processed);
+        T4A_REQUIRE_PTR(bonds_expanded);
+        T4A_REQUIRE_PTR(max_added_basis);
+        GseResult r = global_subspace_expand(*op->impl, const_cast<t4a_gpu_tt*>(init)->impl, center, o);
+        *state = new t4a_gpu_tt(r.state->cores, r.state->eng.stream());
+        gse_counters(r, references_built, edges_processed, bonds_expanded, max_added_basis);
+    });
+}
+
+t4a_gpu_status t4a_gpu_gse_tdvp(const t4a_gpu_mpo* op, const t4a_gpu_tt* init, size_t center, const t4a_gpu_gse_options* gse,
+                                const t4a_gpu_tdvp_options* tdvp_options, t4a_gpu_tt** state, size_t* sweeps_completed, size_t* local_updates,
+                                size_t* gse_expansions, double* max_error_estimate, size_t* max_krylov_iterations)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(state);
+        *state = nullptr;
+        T4A_REQUIRE_PTR(gse);
+        T4A_REQUIRE_PTR(tdvp_options);
+        GseTdvpOptions o;
+        o.gse = convert_gse_options(gse); // the options are checked on the host before an operand is looked at
+        o.tdvp = convert_tdvp_options(tdvp_options);
+        T4A_REQUIRE_PTR(op);
+        T4A_REQUIRE_PTR(init);
+        T4A_REQUIRE_PTR(sweeps_completed);
+        T4A_REQUIRE_PTR(local_updates);
+        T4A_REQUIRE_PTR(gse_expansions);
+        T4A_REQUIRE_PTR(max_error_estimate);
+        T4A_REQUIRE_PTR(max_krylov_iterations);
+        GseTdvpResult r = gse_tdvp(*op->impl, const_cast<t4a_gpu_tt*>(init)->impl, center, o);
+        *state = new t4a_gpu_tt(r.state->cores, r.state->eng.stream());
+        *sweeps_completed = r.sweeps_completed;
+        *local_updates = r.local_updates;
+        *gse_expansions = r.gse_expansions;
+        *max_error_estimate = r.max_error_estimate;
+        *max_krylov_iterations = r.max_krylov_iterations;
+    });
+}
+
+t4a_gpu_status t4a_gpu_gse_project(int32_t orient, size_t q, const double* refs, const size_t* rho, size_t K, const double* B, size_t kb, int32_t route,
+                                   double* stack, double* trace)
+{
+    return guarded([&] {
+        if ((orient != 0 && orient != 1) || (route != 0 && route != 1)) throw Error(T4A_GPU_INVALID_ARGUMENT, "gse_project: orient and route are 0 or 1");
+        const std::vector<int> rh = gse_int_list(rho, K, GSE_MAX_REFERENCES, "gse_project");
+        size_t P = 0;
+        for (int v : rh) P += (size_t)v;
+        gse_require_fits(P, q, "gse_project");
+        gse_require_fits(kb, q, "gse_project");
+        gse_require_fits(P, kb, "gse_project");
+        T4A_REQUIRE_PTR(refs);
+        T4A_REQUIRE_PTR(B);
+        T4A_REQUIRE_PTR(stack);
+        T4A_REQUIRE_PTR(trace);
+        require_device();
+        gse_project_host(orient, (int)q, refs, rh.data(), (int)K, B, (int)kb, route, stack, trace);
+    });
+}
+
+t4a_gpu_status t4a_gpu_gse_absorb(int32_t orient, size_t q, const double* children, const size_t* r, const double* parents, const size_t* L, size_t n_trains,
+                                  const double* Bn, size_t kn, int32_t route, double* out)
+{
+    return guarded([&] {
+        if ((orient != 0 && orient != 1) || (route != 0 && route != 1)) throw Error(T4A_GPU_INVALID_ARGUMENT, "gse_absorb: orient and route are 0 or 1");
+        const std::vector<int> rs = gse_int_list(r, n_trains, GSE_MAX_JOBS, "gse_absorb");
+        const std::vector<int> Ls = gse_int_list(L, n_trains, GSE_MAX_JOBS, "gse_absorb");
+        size_t sumL = 0, sumR = 0;
+        for (size_t j = 0; j < n_trains; ++j) {
+            sumL += (size_t)Ls[j];
+            sumR += (size_t)rs[j];
+            gse_require_fits((size_t)Ls[j], (size_t)rs[j], "gse_absorb");
+        }
+        gse_require_fits(kn, q, "gse_absorb");
+        gse_require_fits(sumL, q, "gse_absorb");
+        gse_require_fits(sumL, kn, "gse_absorb");
+        gse_require_fits(sumR, q, "gse_absorb");
+        gse_require_fits(sumR, kn, "gse_absorb");
+        T4A_REQUIRE_PTR(children);
+        T4A_REQUIRE_PTR(parents);
+        T4A_REQUIRE_PTR(Bn);
+        T4A_REQUIRE_PTR(out);
+        require_device();
+        gse_absorb_host(orient, (int)q, children, rs.data(), parents, Ls.data(), (int)n_trains, Bn, (int)kn, route, out);
+    });
+}
+
+t4a_gpu_status t4a_gpu_gse_route(size_t q, size_t bond, int32_t* route)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(route);
+        gse_require_fits(q, bond, "gse_route");
+        *route = gse_use_fused((int)q, (int)bond) ? 0 : 1;
+    });
+}
+
+t4a_gpu_status t4a_gpu_gse_set_route(int32_t route)
+{
+    return guarded([&] {
+        if (route < -1 || route > 1) throw Error(T4A_GPU_INVALID_ARGUMENT, "gse_set_route: -1 (the rule), 0 (fused) or 1 (GEMM)");
+        gse_set_route(route);
+    });
+}
+
+t4a_gpu_status t4a_gpu_gse_time_routes(size_t chi, size_t d, size_t K, size_t reps, double* ms4)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(ms4);
+        if (chi == 0 || d == 0 || K == 0 || K > (size_t)GSE_MAX_REFERENCES || reps == 0 || chi > 4096 || d > 64)
+            throw Error(T4A_GPU_INVALID_ARGUMENT, "gse_time_routes: chi in 1..4096, d in 1..64, K in 1..8 and reps must be positive");
+        require_device();
+        gse_time_routes(chi, d, K, reps, ms4);
     });
 }
 

@@ -2161,3 +2161,7 @@ from .dmrg import (HermitianLanczosOptions, LanczosOptionsC, DmrgOptions, DmrgOp
 # imported as `from t4a_amd.tdvp import ...` or reached as t4a_amd.tdvp_module
 from . import tdvp as tdvp_module  # noqa: E402
 from .tdvp import (HermitianKrylovExpmOptions, KrylovExpmOptionsC, TdvpOptions, TdvpOptionsC, TdvpResult, tdvp)  # noqa: E402,F401
+# global subspace expansion and GSE-TDVP: module t4a_amd.gse (the hooks _project, _absorb, _time_routes live there)
+from . import gse  # noqa: E402
+from .gse import (GseOptions, GseOptionsC, GseResult, GseTdvpOptions, GseTdvpResult, krylov_references, global_subspace_expand,  # noqa: E402,F401
+                  global_subspace_expand_with_references, gse_tdvp)
