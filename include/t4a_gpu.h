@@ -1498,6 +1498,113 @@ t4a_gpu_status t4a_gpu_gse_set_route(int32_t route);
 /* Probe: device ms of project [0] fused [1] GEMMs and absorb [2] fused [3] GEMMs at bond chi, site dimension d, K references of bond chi + 1. */
 t4a_gpu_status t4a_gpu_gse_time_routes(size_t chi, size_t d, size_t K, size_t reps, double* ms4);
 
+/* =====================================================================================
+ * Partitioned MPOs: the algebra of tensor4all-partitionedtt on device-resident MPOs
+ * crates/tensor4all-partitionedtt/src/: projector.rs:39-268, subdomain_tt.rs:171-443 (project, contract), partitioned_tt.rs:104-480
+ * (from_subdomains, insert, norm, contract, add, contraction_tasks, to_tensor_train), contract.rs:41-110, error.rs
+ * This project's slice: f64 on a chain, sites identified by position, every site an MPO site [left, s1, s2, right] (a train is the
+ * case s2 = 1).  The reference's index objects are legs here: a projector key is (site, leg), leg 0 = s1, leg 1 = s2; a projector
+ * is `count` triples (site, leg, value) of size_t, and a list of projectors is their triples one after the other plus one count each.
+ * In a contraction A·B the shared index is A.(i, 1) == B.(i, 0).  Deviations from the reference: the task order of a contraction is
+ * fixed (a-major, insertion order: the reference iterates a hash map), patches keep their insertion order, _to_mpo sorts by
+ * (site, leg) then value with a shorter prefix first.  partitionedtreetn, budget_squared and autodiff metadata are out of scope.
+ * ===================================================================================== */
+/* ---- projector.rs on the host: no device is touched.  Outputs are triples in ascending (site, leg) order; `out` may be NULL to
+ * query *out_count (never more than count_a + count_b).  A key given twice keeps its last value (from_pairs :57-63); leg > 1 is
+ * INVALID_ARGUMENT. ---- */
+/* validate_invariants against the chain site_dims (2 x n_sites: s1, s2 per site).  INVALID_ARGUMENT: "projector index (site <i>, leg
+ * <l>) is absent from the chain of <n> sites", "projector coordinate <v> is out of range for index (site <i>, leg <l>) with dimension <d>". */
+t4a_gpu_status t4a_gpu_projector_validate(const size_t* site_dims, size_t n_sites, const size_t* p, size_t count);
+t4a_gpu_status t4a_gpu_projector_is_compatible(const size_t* a, size_t count_a, const size_t* b, size_t count_b, int32_t* out); /* :172 */
+/* intersection (:130-145): *compatible = 0 on a conflict (nothing is written then) */
+t4a_gpu_status t4a_gpu_projector_intersection(const size_t* a, size_t count_a, const size_t* b, size_t count_b, int32_t* compatible,
+                                              size_t* out, size_t* out_count);
+t4a_gpu_status t4a_gpu_projector_common_restriction(const size_t* a, size_t count_a, const size_t* b, size_t count_b, size_t* out,
+                                                    size_t* out_count); /* :157-167 */
+t4a_gpu_status t4a_gpu_projector_is_subset_of(const size_t* a, size_t count_a, const size_t* b, size_t count_b, int32_t* out); /* :183-194 */
+t4a_gpu_status t4a_gpu_projector_are_disjoint(const size_t* entries, const size_t* counts, size_t n_projectors, int32_t* out); /* :199-208 */
+/* filter_indices (:214-224): keys is 2 x n_keys (site, leg) */
+t4a_gpu_status t4a_gpu_projector_filter(const size_t* p, size_t count, const size_t* keys, size_t n_keys, size_t* out, size_t* out_count);
+/* the total order of _to_mpo: entries ascending by (site, leg), then value, compared in turn; a proper prefix comes first.  -1, 0, 1. */
+t4a_gpu_status t4a_gpu_projector_compare(const size_t* a, size_t count_a, const size_t* b, size_t count_b, int32_t* out);
+
+/* contraction_tasks (partitioned_tt.rs:401-445) from two projector lists, host only: the analogue of t4a_gpu_tdvp_plan.  A pair
+ * (i, j) is a task when A_i's leg-1 entries and B_j's leg-0 entries agree at every site that both project; tasks are listed a-major in
+ * insertion order.  The result projector of a task is A_i's leg-0 entries plus B_j's leg-1 entries; equal result projectors share one
+ * slot, slots are numbered by first appearance.  *n_tasks, *n_results and *n_result_entries are always written; the arrays are
+ * written when task_capacity >= *n_tasks and entry_capacity >= *n_result_entries (else INVALID_ARGUMENT unless both capacities are 0:
+ * the query).  task_a / task_b / task_result: task_capacity each; result_counts: task_capacity; result_entries: 3 x entry_capacity. */
+t4a_gpu_status t4a_gpu_pmpo_contract_plan(const size_t* a_entries, const size_t* a_counts, size_t n_a, const size_t* b_entries,
+                                          const size_t* b_counts, size_t n_b, size_t task_capacity, size_t entry_capacity, size_t* n_tasks,
+                                          size_t* task_a, size_t* task_b, size_t* task_result, size_t* n_results, size_t* result_counts,
+                                          size_t* result_entries, size_t* n_result_entries);
+/* The host checks of t4a_gpu_pmpo_new on plain dimension lists: patch_site_dims holds (s1, s2) per site of every patch one after the
+ * other, patch_lens[k] the number of sites of patch k. */
+t4a_gpu_status t4a_gpu_pmpo_check(const size_t* site_dims, size_t n_sites, const size_t* patch_site_dims, const size_t* patch_lens,
+                                  size_t n_patches, const size_t* entries, const size_t* counts);
+
+typedef struct t4a_gpu_pmpo t4a_gpu_pmpo;
+/* PartitionedTT::from_subdomains (partitioned_tt.rs:104-110, insert :196-210).  Device copies of the patches are taken, in the order
+ * given; they are NOT masked (as in the reference).  site_dims (2 x n_sites) may be NULL when there is a patch: the first patch's.
+ * INVALID_ARGUMENT, before the device is touched: "partitioned MPO: patch <k> has <m> sites, the chain has <n>", "partitioned MPO:
+ * patch <k> has site dims (<a>, <b>) at site <i>, the chain has (<c>, <d>)", the two messages of _projector_validate, "Projectors
+ * overlap: patches <i> and <j> are not disjoint". */
+t4a_gpu_status t4a_gpu_pmpo_new(const t4a_gpu_mpo* const* patches, size_t n_patches, const size_t* entries, const size_t* counts,
+                                const size_t* site_dims, size_t n_sites, t4a_gpu_pmpo** out);
+/* From the result of adaptive_interpolate: cores copied device-to-device and read as (s1, s2) pairs (Mpo::relabel_site_dims);
+ * site_dims is 2 x n_sites or NULL for (d, 1).  A projected fused value v becomes (v % S1, v / S1) on the two legs. */
+t4a_gpu_status t4a_gpu_pmpo_from_ptt(const t4a_gpu_ptt* ptt, const size_t* site_dims, t4a_gpu_pmpo** out);
+void t4a_gpu_pmpo_release(t4a_gpu_pmpo* h);
+t4a_gpu_status t4a_gpu_pmpo_len(const t4a_gpu_pmpo* h, size_t* out);
+t4a_gpu_status t4a_gpu_pmpo_n_sites(const t4a_gpu_pmpo* h, size_t* out);
+t4a_gpu_status t4a_gpu_pmpo_site_dims(const t4a_gpu_pmpo* h, size_t* site_dims /* 2 x n_sites */);
+/* projector of patch k as triples; `entries` may be NULL to query *count */
+t4a_gpu_status t4a_gpu_pmpo_projector(const t4a_gpu_pmpo* h, size_t k, size_t* count, size_t* entries);
+/* patch k as a new MPO handle (a device copy) */
+t4a_gpu_status t4a_gpu_pmpo_patch(const t4a_gpu_pmpo* h, size_t k, t4a_gpu_mpo** out);
+/* norm (:286-295): sqrt(sum_k norm2(patch k)), norm2 being the tensor train's squared Frobenius norm (t4a_gpu_tt_norm2) */
+t4a_gpu_status t4a_gpu_pmpo_norm(t4a_gpu_pmpo* h, double* out);
+/* a batch in the layout of t4a_gpu_mpo_evaluate, summed over the patches in their order on the host (no patch: zeros) */
+t4a_gpu_status t4a_gpu_pmpo_evaluate(t4a_gpu_pmpo* h, const size_t* idx, size_t n_pts, double* out);
+/* SubDomainTT::project (subdomain_tt.rs:171-260) patch by patch: patches whose projector conflicts with p are dropped, the others are
+ * copied, carry the intersection and are masked — every site of every patch in ONE launch (pmpo_mask_kernel), which stores 0.0 outside
+ * the subdomain and touches nothing inside, so a non-finite value outside disappears (mask_index). */
+t4a_gpu_status t4a_gpu_pmpo_project(const t4a_gpu_pmpo* h, const size_t* p, size_t count, t4a_gpu_pmpo** out);
+/* add (:356-398): the union of the projectors must be pairwise disjoint ("Incompatible projectors: Projectors must be pairwise disjoint
+ * for patch-wise addition"); a patch present on both sides is added by direct sum and truncated by the compress stage of
+ * t4a_gpu_mpo_contract (QR to the right, SVD sweep, s >= tolerance * s_max, at most max_bond_dim, at least one); the others are cloned,
+ * a's first.  tolerance == 0 with max_bond_dim == 0 keeps every singular value: the sweep is skipped and the direct sum returned. */
+t4a_gpu_status t4a_gpu_pmpo_add(const t4a_gpu_pmpo* a, const t4a_gpu_pmpo* b, double tolerance, size_t max_bond_dim, t4a_gpu_pmpo** out);
+/* to_tensor_train (:460-480): the direct sum of the patches in the order of t4a_gpu_projector_compare (bonds: sums of the patch bonds).
+ * Every site of the result is written by one launch (pmpo_direct_sum_kernel); one site is the plain sum of the values.
+ * No patch: INVALID_ARGUMENT "Partitioned tensor train is empty". */
+t4a_gpu_status t4a_gpu_pmpo_to_mpo(const t4a_gpu_pmpo* h, t4a_gpu_mpo** out);
+/* Test and probe hook: _to_mpo by a given route.  1: the reference's chain of G - 1 pairwise train additions; 2: every site of the
+ * result in one launch (pmpo_direct_sum_kernel); 0: what _to_mpo takes (route 2 from two sites and two patches up).  Same bits. */
+t4a_gpu_status t4a_gpu_pmpo_to_mpo_route(const t4a_gpu_pmpo* h, int32_t route, t4a_gpu_mpo** out);
+/* contract (:305-340).  Arguments, rank rule, NOT_IMPLEMENTED (Fit, RSVD) and shape errors of t4a_gpu_mpo_contract.  Every task of
+ * t4a_gpu_pmpo_contract_plan is contracted with both operands projected onto their own projectors (apply_projection); the first result
+ * of a slot is inserted, a later one is added to it by direct sum and truncated with the same tolerance and cap — except for Naive
+ * with compress == 0 (and for tolerance == 0 without a cap), where the direct sum stays as it is.
+ * Naive: the site products of ALL tasks and ALL sites are one launch (pmpo_pair_contract_kernel) with the projection folded in, then
+ * the compress stage per task.  ZipUp: copies of the operands are masked in one launch, then the zip-up of t4a_gpu_mpo_contract per
+ * task.  INVALID_ARGUMENT besides the shape errors: "Projectors overlap: results <i> and <j> of the contraction are not disjoint" (two
+ * result projectors that overlap without being equal, the refusal of PartitionedTT::insert, before the device is touched), a result
+ * site above INT_MAX elements with the task and site in the message. */
+t4a_gpu_status t4a_gpu_pmpo_contract(const t4a_gpu_pmpo* a, const t4a_gpu_pmpo* b, int32_t algorithm, int32_t compress, int32_t method,
+                                     double tolerance, size_t max_bond_dim, t4a_gpu_pmpo** out);
+/* Test hook: the product launch exactly as _contract issues it, on host arrays.  dims is 7 x n_jobs (la, s1, k, ra, lb, t, rb), sel
+ * 4 x n_jobs (k0, k1, s mask, t mask; a mask < 0 = none), A / B / C the sites [la, s1, k, ra] / [lb, k, t, rb] / [la*lb, s1, t, ra*rb]
+ * one after the other.  _mask_sites: the mask launch; dims 4 x n_jobs (l, s1, s2, r), sel 2 x n_jobs (s1 value, s2 value; < 0 = none). */
+t4a_gpu_status t4a_gpu_pmpo_pair_products(const size_t* dims, const int64_t* sel, size_t n_jobs, const double* A, const double* B, double* C);
+t4a_gpu_status t4a_gpu_pmpo_mask_sites(const size_t* dims, const int64_t* sel, size_t n_jobs, double* X);
+/* blocks of 256 threads either launch uses for `total` elements (host only) */
+t4a_gpu_status t4a_gpu_pmpo_launch_blocks(size_t total, size_t* blocks);
+/* Probe (tools/probe_pmpo.py): wall ms per repetition, each ending synced, of [0] the fused product launch of every task of a·b, [1]
+ * the mask launch on copies plus one mpo_site_contract launch per task, [2] the compress stage of every task. */
+t4a_gpu_status t4a_gpu_pmpo_time_contract(const t4a_gpu_pmpo* a, const t4a_gpu_pmpo* b, double tolerance, size_t max_bond_dim, size_t reps,
+                                          double* ms3);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -22,6 +22,7 @@
 #include "dmrg.hpp"
 #include "tdvp.hpp"
 #include "gse.hpp"
+#include "pmpo.hpp"
 #include "linsolve.hpp"
 
 struct t4a_gpu_tci2 {
@@ -67,6 +68,10 @@ struct t4a_gpu_inverse_tt {
 
 struct t4a_gpu_mpo {
     std::unique_ptr<t4a::Mpo> impl;
+};
+
+struct t4a_gpu_pmpo {
+    std::unique_ptr<t4a::PartitionedMpo> impl;
 };
 
 struct t4a_gpu_qt_op {
@@ -4946,6 +4951,386 @@ t4a_gpu_status t4a_gpu_gse_time_routes(size_t chi, size_t d, size_t K, size_t re
             throw Error(T4A_GPU_INVALID_ARGUMENT, "gse_time_routes: chi in 1..4096, d in 1..64, K in 1..8 and reps must be positive");
         require_device();
         gse_time_routes(chi, d, K, reps, ms4);
+    });
+}
+
+// ---- partitioned MPOs (pmpo.hpp): projector.rs, contraction_tasks and the handle ----
+static std::vector<LegProjector> projector_list(const size_t* entries, const size_t* counts, size_t n)
+{
+    std::vector<LegProjector> v(n);
+    if (n) T4A_REQUIRE_PTR(counts);
+    size_t off = 0;
+    for (size_t k = 0; k < n; ++k) {
+        v[k] = projector_from_triples(entries ? entries + 3 * off : nullptr, counts[k]);
+        off += counts[k];
+    }
+    return v;
+}
+
+static void projector_out(const LegProjector& p, size_t* out, size_t* out_count)
+{
+    T4A_REQUIRE_PTR(out_count);
+    *out_count = p.size();
+    if (!out) return;
+    size_t i = 0;
+    for (const auto& kv : p) {
+        out[3 * i] = kv.first.first;
+        out[3 * i + 1] = kv.first.second;
+        out[3 * i + 2] = kv.second;
+        ++i;
+    }
+}
+
+static SiteDims site_dims_list(const size_t* site_dims, size_t n_sites)
+{
+    if (n_sites) T4A_REQUIRE_PTR(site_dims);
+    SiteDims sd(n_sites);
+    for (size_t i = 0; i < n_sites; ++i) sd[i] = {site_dims[2 * i], site_dims[2 * i + 1]};
+    return sd;
+}
+
+t4a_gpu_status t4a_gpu_projector_validate(const size_t* site_dims, size_t n_sites, const size_t* p, size_t count)
+{
+    return guarded([&] { projector_validate(projector_from_triples(p, count), site_dims_list(site_dims, n_sites)); });
+}
+
+t4a_gpu_status t4a_gpu_projector_is_compatible(const size_t* a, size_t count_a, const size_t* b, size_t count_b, int32_t* out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(out);
+        *out = projector_compatible(projector_from_triples(a, count_a), projector_from_triples(b, count_b)) ? 1 : 0;
+    });
+}
+
+t4a_gpu_status t4a_gpu_projector_intersection(const size_t* a, size_t count_a, const size_t* b, size_t count_b, int32_t* compatible,
+                                              size_t* out, size_t* out_count)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(compatible);
+        T4A_REQUIRE_PTR(out_count);
+        LegProjector r;
+        *compatible = projector_intersection(projector_from_triples(a, count_a), projector_from_triples(b, count_b), r) ? 1 : 0;
+        *out_count = 0;
+        if (*compatible) projector_out(r, out, out_count);
+    });
+}
+
+t4a_gpu_status t4a_gpu_projector_common_restriction(const size_t* a, size_t count_a, const size_t* b, size_t count_b, size_t* out,
+                                                    size_t* out_count)
+{
+    return guarded(
+        [&] { projector_out(projector_common_restriction(projector_from_triples(a, count_a), projector_from_triples(b, count_b)), out, out_count); });
+}
+
+t4a_gpu_status t4a_gpu_projector_is_subset_of(const size_t* a, size_t count_a, const size_t* b, size_t count_b, int32_t* out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(out);
+        *out = projector_is_subset_of(projector_from_triples(a, count_a), projector_from_triples(b, count_b)) ? 1 : 0;
+    });
+}
+
+t4a_gpu_status t4a_gpu_projector_are_disjoint(const size_t* entries, const size_t* counts, size_t n_projectors, int32_t* out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(out);
+        *out = projectors_disjoint(projector_list(entries, counts, n_projectors)) ? 1 : 0;
+    });
+}
+
+t4a_gpu_status t4a_gpu_projector_filter(const size_t* p, size_t count, const size_t* keys, size_t n_keys, size_t* out, size_t* out_count)
+{
+    return guarded([&] {
+        if (n_keys) T4A_REQUIRE_PTR(keys);
+        std::vector<std::pair<size_t, size_t>> k(n_keys);
+        for (size_t i = 0; i < n_keys; ++i) k[i] = {keys[2 * i], keys[2 * i + 1]};
+        projector_out(projector_filter(projector_from_triples(p, count), k), out, out_count);
+    });
+}
+
+t4a_gpu_status t4a_gpu_projector_compare(const size_t* a, size_t count_a, const size_t* b, size_t count_b, int32_t* out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(out);
+        *out = projector_compare(projector_from_triples(a, count_a), projector_from_triples(b, count_b));
+    });
+}
+
+t4a_gpu_status t4a_gpu_pmpo_contract_plan(const size_t* a_entries, const size_t* a_counts, size_t n_a, const size_t* b_entries,
+                                          const size_t* b_counts, size_t n_b, size_t task_capacity, size_t entry_capacity, size_t* n_tasks,
+                                          size_t* task_a, size_t* task_b, size_t* task_result, size_t* n_results, size_t* result_counts,
+                                          size_t* result_entries, size_t* n_result_entries)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(n_tasks);
+        T4A_REQUIRE_PTR(n_results);
+        T4A_REQUIRE_PTR(n_result_entries);
+        const PmpoPlan plan = pmpo_contract_plan(projector_list(a_entries, a_counts, n_a), projector_list(b_entries, b_counts, n_b));
+        size_t ne = 0;
+        for (const auto& r : plan.results) ne += r.size();
+        *n_tasks = plan.tasks.size();
+        *n_results = plan.results.size();
+        *n_result_entries = ne;
+        if (task_capacity == 0 && entry_capacity == 0) return; // the query
+        if (task_capacity < plan.tasks.size() || entry_capacity < ne)
+            throw Error(T4A_GPU_INVALID_ARGUMENT, "pmpo_contract_plan: " + std::to_string(plan.tasks.size()) + " tasks and " + std::to_string(ne) +
+                                                      " result entries do not fit the capacities " + std::to_string(task_capacity) + " and " +
+                                                      std::to_string(entry_capacity));
+        if (!plan.tasks.empty()) {
+            T4A_REQUIRE_PTR(task_a);
+            T4A_REQUIRE_PTR(task_b);
+            T4A_REQUIRE_PTR(task_result);
+            T4A_REQUIRE_PTR(result_counts);
+        }
+        if (ne) T4A_REQUIRE_PTR(result_entries);
+        for (size_t t = 0; t < plan.tasks.size(); ++t) {
+            task_a[t] = plan.tasks[t].a;
+            task_b[t] = plan.tasks[t].b;
+            task_result[t] = plan.tasks[t].result;
+        }
+        size_t off = 0;
+        for (size_t r = 0; r < plan.results.size(); ++r) {
+            size_t c = 0;
+            projector_out(plan.results[r], result_entries ? result_entries + 3 * off : nullptr, &c);
+            result_counts[r] = c;
+            off += c;
+        }
+    });
+}
+
+t4a_gpu_status t4a_gpu_pmpo_check(const size_t* site_dims, size_t n_sites, const size_t* patch_site_dims, const size_t* patch_lens,
+                                  size_t n_patches, const size_t* entries, const size_t* counts)
+{
+    return guarded([&] {
+        if (n_patches) T4A_REQUIRE_PTR(patch_lens);
+        std::vector<SiteDims> pd(n_patches);
+        size_t off = 0;
+        for (size_t k = 0; k < n_patches; ++k) {
+            pd[k] = site_dims_list(patch_site_dims ? patch_site_dims + 2 * off : nullptr, patch_lens[k]);
+            off += patch_lens[k];
+        }
+        PartitionedMpo::validate(site_dims_list(site_dims, n_sites), pd, projector_list(entries, counts, n_patches));
+    });
+}
+
+t4a_gpu_status t4a_gpu_pmpo_new(const t4a_gpu_mpo* const* patches, size_t n_patches, const size_t* entries, const size_t* counts,
+                                const size_t* site_dims, size_t n_sites, t4a_gpu_pmpo** out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(out);
+        *out = nullptr;
+        if (n_patches) T4A_REQUIRE_PTR(patches);
+        std::vector<Mpo*> ms(n_patches);
+        for (size_t k = 0; k < n_patches; ++k) {
+            T4A_REQUIRE_PTR(patches[k]);
+            ms[k] = patches[k]->impl.get();
+        }
+        SiteDims sd;
+        if (site_dims) sd = site_dims_list(site_dims, n_sites);
+        *out = new t4a_gpu_pmpo{PartitionedMpo::from_patches(ms, projector_list(entries, counts, n_patches), site_dims ? &sd : nullptr)};
+    });
+}
+
+t4a_gpu_status t4a_gpu_pmpo_from_ptt(const t4a_gpu_ptt* ptt, const size_t* site_dims, t4a_gpu_pmpo** out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(ptt);
+        T4A_REQUIRE_PTR(out);
+        *out = nullptr;
+        PartitionedTT& src = *ptt->impl;
+        const size_t n = src.dims.size();
+        SiteDims fused(n), sd(n);
+        for (size_t i = 0; i < n; ++i) {
+            fused[i] = {src.dims[i], 1};
+            sd[i] = site_dims ? std::array<size_t, 2>{site_dims[2 * i], site_dims[2 * i + 1]} : fused[i];
+            if (sd[i][0] == 0 || sd[i][0] * sd[i][1] != src.dims[i])
+                throw Error(T4A_GPU_INVALID_ARGUMENT, "relabel_site_dims: site " + std::to_string(i) + " has " + std::to_string(src.dims[i]) +
+                                                          " fused indices, not " + std::to_string(sd[i][0]) + " * " + std::to_string(sd[i][1]));
+        }
+        auto r = std::make_unique<PartitionedMpo>(sd);
+        for (const SubDomain& p : src.patches) {
+            LegProjector proj;
+            for (const auto& kv : p.projector) {
+                proj[{kv.first, 0}] = kv.second % sd[kv.first][0];
+                proj[{kv.first, 1}] = kv.second / sd[kv.first][0];
+            }
+            auto m = std::make_unique<Mpo>(p.cores, src.eng.stream(), fused);
+            m->relabel_site_dims(sd);
+            r->patches.push_back({proj, std::move(m)});
+        }
+        *out = new t4a_gpu_pmpo{std::move(r)};
+    });
+}
+
+void t4a_gpu_pmpo_release(t4a_gpu_pmpo* h) { delete h; }
+
+t4a_gpu_status t4a_gpu_pmpo_len(const t4a_gpu_pmpo* h, size_t* out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(h);
+        T4A_REQUIRE_PTR(out);
+        *out = h->impl->len();
+    });
+}
+
+t4a_gpu_status t4a_gpu_pmpo_n_sites(const t4a_gpu_pmpo* h, size_t* out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(h);
+        T4A_REQUIRE_PTR(out);
+        *out = h->impl->sd.size();
+    });
+}
+
+t4a_gpu_status t4a_gpu_pmpo_site_dims(const t4a_gpu_pmpo* h, size_t* site_dims)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(h);
+        if (!h->impl->sd.empty()) T4A_REQUIRE_PTR(site_dims);
+        for (size_t i = 0; i < h->impl->sd.size(); ++i) {
+            site_dims[2 * i] = h->impl->sd[i][0];
+            site_dims[2 * i + 1] = h->impl->sd[i][1];
+        }
+    });
+}
+
+t4a_gpu_status t4a_gpu_pmpo_projector(const t4a_gpu_pmpo* h, size_t k, size_t* count, size_t* entries)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(h);
+        if (k >= h->impl->len()) throw Error(T4A_GPU_INVALID_ARGUMENT, "patch index out of range");
+        projector_out(h->impl->patches[k].proj, entries, count);
+    });
+}
+
+t4a_gpu_status t4a_gpu_pmpo_patch(const t4a_gpu_pmpo* h, size_t k, t4a_gpu_mpo** out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(h);
+        T4A_REQUIRE_PTR(out);
+        *out = nullptr;
+        if (k >= h->impl->len()) throw Error(T4A_GPU_INVALID_ARGUMENT, "patch index out of range");
+        Mpo& m = *h->impl->patches[k].mpo;
+        *out = new t4a_gpu_mpo{std::make_unique<Mpo>(m.tt.cores, m.tt.eng.stream(), m.sd)};
+    });
+}
+
+t4a_gpu_status t4a_gpu_pmpo_norm(t4a_gpu_pmpo* h, double* out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(h);
+        T4A_REQUIRE_PTR(out);
+        *out = h->impl->norm();
+    });
+}
+
+t4a_gpu_status t4a_gpu_pmpo_evaluate(t4a_gpu_pmpo* h, const size_t* idx, size_t n_pts, double* out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(h);
+        if (n_pts == 0) return;
+        T4A_REQUIRE_PTR(idx);
+        T4A_REQUIRE_PTR(out);
+        std::vector<uint32_t> u = narrow_indices(idx, checked_mul(n_pts, 2 * h->impl->sd.size(), "index buffer"));
+        std::vector<double> v = h->impl->evaluate(u.data(), n_pts);
+        std::memcpy(out, v.data(), n_pts * sizeof(double));
+    });
+}
+
+t4a_gpu_status t4a_gpu_pmpo_project(const t4a_gpu_pmpo* h, const size_t* p, size_t count, t4a_gpu_pmpo** out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(h);
+        T4A_REQUIRE_PTR(out);
+        *out = nullptr;
+        *out = new t4a_gpu_pmpo{h->impl->project(projector_from_triples(p, count))};
+    });
+}
+
+static MpoContractionOptions pmpo_options(double tolerance, size_t max_bond_dim, int32_t method)
+{
+    if (method < 0 || method > 3) throw Error(T4A_GPU_INVALID_ARGUMENT, "unknown factorize method");
+    MpoContractionOptions o;
+    o.tolerance = tolerance;
+    o.max_bond_dim = max_bond_dim;
+    o.method = (MpoFactorizeMethod)method;
+    return o;
+}
+
+t4a_gpu_status t4a_gpu_pmpo_add(const t4a_gpu_pmpo* a, const t4a_gpu_pmpo* b, double tolerance, size_t max_bond_dim, t4a_gpu_pmpo** out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(a);
+        T4A_REQUIRE_PTR(b);
+        T4A_REQUIRE_PTR(out);
+        *out = nullptr;
+        *out = new t4a_gpu_pmpo{a->impl->add(*b->impl, pmpo_options(tolerance, max_bond_dim, 0))};
+    });
+}
+
+t4a_gpu_status t4a_gpu_pmpo_to_mpo(const t4a_gpu_pmpo* h, t4a_gpu_mpo** out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(h);
+        T4A_REQUIRE_PTR(out);
+        *out = nullptr;
+        *out = new t4a_gpu_mpo{h->impl->to_mpo()};
+    });
+}
+
+t4a_gpu_status t4a_gpu_pmpo_to_mpo_route(const t4a_gpu_pmpo* h, int32_t route, t4a_gpu_mpo** out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(h);
+        T4A_REQUIRE_PTR(out);
+        *out = nullptr;
+        *out = new t4a_gpu_mpo{h->impl->to_mpo(route)};
+    });
+}
+
+t4a_gpu_status t4a_gpu_pmpo_contract(const t4a_gpu_pmpo* a, const t4a_gpu_pmpo* b, int32_t algorithm, int32_t compress, int32_t method,
+                                     double tolerance, size_t max_bond_dim, t4a_gpu_pmpo** out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(a);
+        T4A_REQUIRE_PTR(b);
+        T4A_REQUIRE_PTR(out);
+        *out = nullptr;
+        if (algorithm < 0 || algorithm > 2) throw Error(T4A_GPU_INVALID_ARGUMENT, "unknown contraction algorithm");
+        const MpoContractionOptions o = pmpo_options(tolerance, max_bond_dim, method);
+        *out = new t4a_gpu_pmpo{a->impl->contract(*b->impl, (MpoAlgorithm)algorithm, compress != 0, o)};
+    });
+}
+
+t4a_gpu_status t4a_gpu_pmpo_pair_products(const size_t* dims, const int64_t* sel, size_t n_jobs, const double* A, const double* B, double* C)
+{
+    return guarded([&] {
+        static_assert(sizeof(long long) == sizeof(int64_t), "selectors are 64-bit");
+        pmpo_pair_products(dims, reinterpret_cast<const long long*>(sel), n_jobs, A, B, C);
+    });
+}
+
+t4a_gpu_status t4a_gpu_pmpo_mask_sites(const size_t* dims, const int64_t* sel, size_t n_jobs, double* X)
+{
+    return guarded([&] { pmpo_mask_sites(dims, reinterpret_cast<const long long*>(sel), n_jobs, X); });
+}
+
+t4a_gpu_status t4a_gpu_pmpo_launch_blocks(size_t total, size_t* blocks)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(blocks);
+        *blocks = pmpo_launch_blocks(total);
+    });
+}
+
+t4a_gpu_status t4a_gpu_pmpo_time_contract(const t4a_gpu_pmpo* a, const t4a_gpu_pmpo* b, double tolerance, size_t max_bond_dim, size_t reps,
+                                          double* ms3)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(a);
+        T4A_REQUIRE_PTR(b);
+        T4A_REQUIRE_PTR(ms3);
+        pmpo_time_contract(*a->impl, *b->impl, pmpo_options(tolerance, max_bond_dim, 0), reps, ms3);
     });
 }
 

@@ -583,6 +583,44 @@ struct MpoSiteJob {
 void mpo_site_contract_launch(const MpoSiteJob* d_jobs, int n_jobs, unsigned long long total, hipStream_t stream);
 
 // ------------------------------------------------------------------------------------------------
+// kernels_pmpo.hip — the launches of a partitioned MPO (pmpo.hip).  All are job lists with ascending offsets, jobs[0].off == 0,
+// every site of at most INT_MAX elements, like MpoSiteJob.
+// Mask (SubDomainTT::project, mask_index): job j owns elements [off, off + l*s1*s2*r) of the launch; an element whose s1 index differs
+// from m1 (m1 >= 0) or whose s2 index differs from m2 (m2 >= 0) is overwritten with 0.0, every other element is left alone.
+// Pair product: MpoSiteJob with the projection of both operands folded in.  The contracted index runs over [k0, k1) only, and an
+// output whose s index differs from sm (sm >= 0) or whose t index differs from tm (tm >= 0) is written as 0.0.
+// ------------------------------------------------------------------------------------------------
+struct PmpoMaskJob {
+    double* X; // [l, s1, s2, r]
+    unsigned long long off;
+    int l, s1, s2, r, m1, m2;
+};
+void pmpo_mask_launch(const PmpoMaskJob* d_jobs, int n_jobs, unsigned long long total, hipStream_t stream);
+struct PmpoPairJob {
+    const double* A; // [la, s1, k, ra]
+    const double* B; // [lb, k, t, rb]
+    double* C;       // [la*lb, s1, t, ra*rb]
+    unsigned long long off;
+    int la, s1, k, ra, lb, t, rb;
+    int k0, k1, sm, tm, pad_;
+};
+void pmpo_pair_contract_launch(const PmpoPairJob* d_jobs, int n_jobs, unsigned long long total, hipStream_t stream);
+// Direct sum of G chains (PartitionedTT::to_tensor_train), every output site in one launch: job j owns the output site dst [L, S, R];
+// patch g's site src[g] is [row0[g+1] - row0[g], S, col0[g+1] - col0[g]] and lands at rows row0[g].. and columns col0[g].., every other
+// element is written as 0.0.  At the first site (L == 1) every patch sits in row 0 and row0 is not read; at the last (R == 1) col0 is not.
+struct PmpoSumJob {
+    double* dst;
+    const double* const* src; // G device pointers
+    const int* row0;          // G + 1 ascending offsets, row0[G] == L
+    const int* col0;          // G + 1 ascending offsets, col0[G] == R
+    unsigned long long off;
+    int L, S, R, G, first, last;
+};
+void pmpo_direct_sum_launch(const PmpoSumJob* d_jobs, int n_jobs, unsigned long long total, hipStream_t stream);
+// blocks of 256 threads these launches use for `total` elements (the grid-stride loop takes the rest)
+unsigned pmpo_launch_blocks(unsigned long long total);
+
+// ------------------------------------------------------------------------------------------------
 // kernels_mpo_fit.hip — half product of the variational MPO-MPO fit (mpo_fit.hip): an environment times one site of A and one of B,
 //   out[n on + s os + t ot + c oc + d od] =
 //     sum_{k < K} sum_{b < Lb} ( sum_{a < La} E[n en + a ea + b eb] A[a aa + s as + k ak + c ac] ) B[b bb + k bk + t bt + d bd]

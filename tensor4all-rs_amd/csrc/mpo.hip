@@ -469,6 +469,13 @@ std::unique_ptr<Mpo> mpo_contract(Mpo& a, Mpo& b, MpoAlgorithm alg, bool compres
     return std::make_unique<Mpo>(std::move(cores), sd);
 }
 
+void mpo_compress_cores(Engine& eng, std::vector<DevCore>& cores, const MpoContractionOptions& opt)
+{
+    Contractor c(eng, opt);
+    c.compress(cores);
+    eng.sync();
+}
+
 void mpo_fit_validate_options(const MpoFitOptions& opt)
 {
     if (!(opt.tolerance >= 0.0) || !std::isfinite(opt.tolerance))

@@ -51,6 +51,10 @@ public:
 // contract(a, b, algorithm, options) (dispatch.rs:67-92).  Naive with compress == false is contract_naive(a, b, None);
 // Fit answers NOT_IMPLEMENTED after the shape checks, RSVD where the reference's factorize is reached.
 std::unique_ptr<Mpo> mpo_contract(Mpo& a, Mpo& b, MpoAlgorithm alg, bool compress, const MpoContractionOptions& opt);
+// The compress stage of contract_naive (compress_mpo, contract_naive.rs:100-172) on site tensors that exist already: right-canonicalise
+// by QR, then the left-to-right SVD sweep with the rank rule of `opt`.  Every launch goes to the stream of `eng`, which the caller has
+// made the owner of `cores`; ends synced.  The partitioned MPO (pmpo.hip) feeds it the output of its one product launch.
+void mpo_compress_cores(Engine& eng, std::vector<DevCore>& cores, const MpoContractionOptions& opt);
 
 // ---- variational (fit) contraction C ~ A·B.  This project's: the reference reserves FitOptions (contract_fit.rs:19-46) and answers
 // Unsupported; mpo_contract(.., Fit, ..) keeps doing that.  The algorithm is the two-site fit of tensor4all-treetn (treetn/fit.rs)

@@ -1163,6 +1163,11 @@ class PartitionedTT:
         grids = np.indices(sd[::-1]).reshape(len(sd), -1)[::-1].T
         return self.evaluate(grids)
 
+    def as_mpo(self, site_dims=None):
+        """The patches as a PartitionedMPO (t4a_amd.partitioned): site k read as ``site_dims[k] = (s1, s2)``, default ``(d, 1)``."""
+        from .partitioned import PartitionedMPO
+        return PartitionedMPO.from_partitioned_tt(self, site_dims)
+
 
 def adaptiveinterpolate(f, local_dims, initial_pivots, options, patch_order=None, n_initial_pivots=5,
                         recycle_pivots=False):
@@ -2165,3 +2170,6 @@ from .tdvp import (HermitianKrylovExpmOptions, KrylovExpmOptionsC, TdvpOptions, 
 from . import gse  # noqa: E402
 from .gse import (GseOptions, GseOptionsC, GseResult, GseTdvpOptions, GseTdvpResult, krylov_references, global_subspace_expand,  # noqa: E402,F401
                   global_subspace_expand_with_references, gse_tdvp)
+# partitioned MPOs: module t4a_amd.partitioned; its `contract` stays under the module name, like t4a_amd.mpo.contract
+from . import partitioned  # noqa: E402
+from .partitioned import Projector, PartitionedMPO, proj_contract  # noqa: E402,F401
