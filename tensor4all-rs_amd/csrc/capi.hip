@@ -152,6 +152,36 @@ TCI2Options convert_options(const t4a_gpu_tci2_options* o)
     return r;
 }
 
+t4a_gpu_svd_policy to_c(const SvdPolicy& p) { return t4a_gpu_svd_policy{p.threshold, p.scale, p.measure, p.rule}; }
+SvdPolicy from_c(const t4a_gpu_svd_policy& p) { return SvdPolicy{p.threshold, p.scale, p.measure, p.rule}; }
+
+// the shape lists of the check_shapes entry points
+std::vector<std::array<size_t, 3>> dims3_list(const size_t* d, size_t n)
+{
+    std::vector<std::array<size_t, 3>> v(n);
+    for (size_t i = 0; i < n; ++i) v[i] = {d[3 * i], d[3 * i + 1], d[3 * i + 2]};
+    return v;
+}
+std::vector<std::array<size_t, 4>> dims4_list(const size_t* d, size_t n)
+{
+    std::vector<std::array<size_t, 4>> v(n);
+    for (size_t i = 0; i < n; ++i) v[i] = {d[4 * i], d[4 * i + 1], d[4 * i + 2], d[4 * i + 3]};
+    return v;
+}
+
+// the dense test hooks of the Krylov solvers: the n x n matrix and the basis of basis_cols columns are indexed with ints
+void require_dense_hook_dims(const char* who, size_t n, size_t basis_cols)
+{
+    if (n == 0 || n > 46340 || (unsigned long long)n * basis_cols > (unsigned long long)INT_MAX)
+        throw Error(T4A_GPU_INVALID_ARGUMENT, std::string(who) + ": n must be positive and the matrix and the basis must hold at most INT_MAX elements");
+}
+// the hooks on a len x nb basis: "<who>: <too_large>" for nb above nb_max or more than INT_MAX elements
+void require_basis_dims(const char* who, size_t len, size_t nb, size_t nb_max, const std::string& too_large)
+{
+    if (len == 0 || nb == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, std::string(who) + ": len and nb must be positive");
+    if (nb > nb_max || (unsigned long long)len * nb > (unsigned long long)INT_MAX) throw Error(T4A_GPU_INVALID_ARGUMENT, std::string(who) + ": " + too_large);
+}
+
 void upload(Engine& e, double* dst, const double* src, size_t count)
 {
     if (count == 0) return;
@@ -4116,7 +4146,7 @@ t4a_gpu_status t4a_gpu_linsolve_options_default(t4a_gpu_linsolve_options* out)
         out->has_max_bond_dim = d.has_max_bond_dim;
         out->max_bond_dim = d.max_bond_dim;
         out->has_svd_policy = d.has_svd_policy;
-        out->svd_policy = t4a_gpu_svd_policy{d.svd_policy.threshold, d.svd_policy.scale, d.svd_policy.measure, d.svd_policy.rule};
+        out->svd_policy = to_c(d.svd_policy);
         out->gmres_tol = d.gmres_tol;
         out->gmres_tolerance_mode = (int32_t)d.gmres_tolerance_mode;
         out->gmres_max_restarts = d.gmres_max_restarts;
@@ -4137,7 +4167,7 @@ static LinsolveOptions convert_linsolve_options(const t4a_gpu_linsolve_options* 
     o.has_max_bond_dim = p->has_max_bond_dim != 0;
     o.max_bond_dim = p->max_bond_dim;
     o.has_svd_policy = p->has_svd_policy != 0;
-    if (o.has_svd_policy) o.svd_policy = SvdPolicy{p->svd_policy.threshold, p->svd_policy.scale, p->svd_policy.measure, p->svd_policy.rule};
+    if (o.has_svd_policy) o.svd_policy = from_c(p->svd_policy);
     o.gmres_tol = p->gmres_tol;
     if (p->gmres_tolerance_mode != 0 && p->gmres_tolerance_mode != 1) throw Error(T4A_GPU_INVALID_ARGUMENT, "unknown gmres_tolerance_mode");
     o.gmres_tolerance_mode = (GmresToleranceMode)p->gmres_tolerance_mode;
@@ -4151,12 +4181,6 @@ static LinsolveOptions convert_linsolve_options(const t4a_gpu_linsolve_options* 
     o.validate();
     return o;
 }
-static std::vector<std::array<size_t, 3>> dims3_list(const size_t* d, size_t n)
-{
-    std::vector<std::array<size_t, 3>> v(n);
-    for (size_t i = 0; i < n; ++i) v[i] = {d[3 * i], d[3 * i + 1], d[3 * i + 2]};
-    return v;
-}
 }
 
 t4a_gpu_status t4a_gpu_linsolve_check_shapes(const size_t* op_dims4, size_t n_op, const size_t* rhs_dims3, size_t n_rhs,
@@ -4166,10 +4190,8 @@ t4a_gpu_status t4a_gpu_linsolve_check_shapes(const size_t* op_dims4, size_t n_op
         if (n_op) T4A_REQUIRE_PTR(op_dims4);
         if (n_rhs) T4A_REQUIRE_PTR(rhs_dims3);
         if (n_state) T4A_REQUIRE_PTR(state_dims3);
-        std::vector<std::array<size_t, 4>> op(n_op);
-        for (size_t i = 0; i < n_op; ++i) op[i] = {op_dims4[4 * i], op_dims4[4 * i + 1], op_dims4[4 * i + 2], op_dims4[4 * i + 3]};
         const auto rhs = dims3_list(rhs_dims3, n_rhs);
-        linsolve_validate_shapes(op, rhs_dims3 ? &rhs : nullptr, dims3_list(state_dims3, n_state), center, gmres_restart_dim);
+        linsolve_validate_shapes(dims4_list(op_dims4, n_op), rhs_dims3 ? &rhs : nullptr, dims3_list(state_dims3, n_state), center, gmres_restart_dim);
     });
 }
 
@@ -4330,9 +4352,7 @@ t4a_gpu_status t4a_gpu_projected_operator_apply_env(const double* L, const doubl
 t4a_gpu_status t4a_gpu_linsolve_orth(const double* basis, size_t len, size_t nb, double* w_inout, double* h_out, double* norm_out)
 {
     return guarded([&] {
-        if (len == 0 || nb == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "linsolve_orth: len and nb must be positive");
-        if (nb > LINSOLVE_RESTART_DIM_MAX + 1 || (unsigned long long)len * nb > (unsigned long long)INT_MAX)
-            throw Error(T4A_GPU_INVALID_ARGUMENT, "linsolve_orth: the basis holds more than INT_MAX elements");
+        require_basis_dims("linsolve_orth", len, nb, LINSOLVE_RESTART_DIM_MAX + 1, "the basis holds more than INT_MAX elements");
         T4A_REQUIRE_PTR(basis);
         T4A_REQUIRE_PTR(w_inout);
         T4A_REQUIRE_PTR(h_out);
@@ -4345,9 +4365,7 @@ t4a_gpu_status t4a_gpu_linsolve_orth(const double* basis, size_t len, size_t nb,
 t4a_gpu_status t4a_gpu_krylov_orth(const double* basis, size_t len, size_t nb, double* w_inout, int32_t route, double* h_out, double* norm_out)
 {
     return guarded([&] {
-        if (len == 0 || nb == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "krylov_orth: len and nb must be positive");
-        if (nb > LINSOLVE_RESTART_DIM_MAX + 1 || (unsigned long long)len * nb > (unsigned long long)INT_MAX)
-            throw Error(T4A_GPU_INVALID_ARGUMENT, "krylov_orth: the basis holds more than INT_MAX elements");
+        require_basis_dims("krylov_orth", len, nb, LINSOLVE_RESTART_DIM_MAX + 1, "the basis holds more than INT_MAX elements");
         if (route < 0 || route > 2) throw Error(T4A_GPU_INVALID_ARGUMENT, "krylov_orth: route must be 0 (serial), 1 (wide) or 2 (the rule of krylov_dots_route)");
         T4A_REQUIRE_PTR(basis);
         T4A_REQUIRE_PTR(w_inout);
@@ -4386,8 +4404,7 @@ t4a_gpu_status t4a_gpu_linsolve_gmres_dense(const double* H, size_t n, const dou
         o.gmres_restart_dim = restart_dim;
         o.gmres_max_restarts = max_restarts;
         o.validate();
-        if (n == 0 || n > 46340 || (unsigned long long)n * (restart_dim + 1) > (unsigned long long)INT_MAX)
-            throw Error(T4A_GPU_INVALID_ARGUMENT, "gmres_dense: n must be positive and the matrix and the basis must hold at most INT_MAX elements");
+        require_dense_hook_dims("gmres_dense", n, restart_dim + 1);
         T4A_REQUIRE_PTR(H);
         T4A_REQUIRE_PTR(b);
         T4A_REQUIRE_PTR(x0);
@@ -4415,7 +4432,7 @@ t4a_gpu_status t4a_gpu_dmrg_options_default(t4a_gpu_dmrg_options* out)
         out->has_max_bond_dim = d.has_max_bond_dim;
         out->max_bond_dim = d.max_bond_dim;
         out->has_svd_policy = d.has_svd_policy;
-        out->svd_policy = t4a_gpu_svd_policy{d.svd_policy.threshold, d.svd_policy.scale, d.svd_policy.measure, d.svd_policy.rule};
+        out->svd_policy = to_c(d.svd_policy);
         out->lanczos = t4a_gpu_lanczos_options{d.lanczos.max_iter, d.lanczos.rtol, d.lanczos.atol, d.lanczos.breakdown_tol, d.lanczos.hermitian_tol};
         out->has_energy_tol = d.has_energy_tol;
         out->energy_tol = d.energy_tol;
@@ -4442,7 +4459,7 @@ static DmrgOptions convert_dmrg_options(const t4a_gpu_dmrg_options* p)
     o.has_max_bond_dim = p->has_max_bond_dim != 0;
     o.max_bond_dim = p->max_bond_dim;
     o.has_svd_policy = p->has_svd_policy != 0;
-    if (o.has_svd_policy) o.svd_policy = SvdPolicy{p->svd_policy.threshold, p->svd_policy.scale, p->svd_policy.measure, p->svd_policy.rule};
+    if (o.has_svd_policy) o.svd_policy = from_c(p->svd_policy);
     o.lanczos = convert_lanczos_options(p->lanczos);
     o.has_energy_tol = p->has_energy_tol != 0;
     o.energy_tol = p->energy_tol;
@@ -4461,9 +4478,7 @@ t4a_gpu_status t4a_gpu_dmrg_check_shapes(const size_t* op_dims4, size_t n_op, co
         LanczosOptions lo;
         lo.max_iter = max_iter;
         lo.validate();
-        std::vector<std::array<size_t, 4>> op(n_op);
-        for (size_t i = 0; i < n_op; ++i) op[i] = {op_dims4[4 * i], op_dims4[4 * i + 1], op_dims4[4 * i + 2], op_dims4[4 * i + 3]};
-        dmrg_validate_shapes(op, dims3_list(state_dims3, n_state), center, max_iter);
+        dmrg_validate_shapes(dims4_list(op_dims4, n_op), dims3_list(state_dims3, n_state), center, max_iter);
     });
 }
 
@@ -4511,8 +4526,7 @@ t4a_gpu_status t4a_gpu_lanczos_dense(const double* H, size_t n, const double* v0
         T4A_REQUIRE_PTR(options);
         const LanczosOptions o = convert_lanczos_options(*options);
         o.validate();
-        if (n == 0 || n > 46340 || (unsigned long long)n * (o.max_iter + 1) > (unsigned long long)INT_MAX)
-            throw Error(T4A_GPU_INVALID_ARGUMENT, "lanczos_dense: n must be positive and the matrix and the basis must hold at most INT_MAX elements");
+        require_dense_hook_dims("lanczos_dense", n, o.max_iter + 1);
         T4A_REQUIRE_PTR(H);
         T4A_REQUIRE_PTR(v0);
         T4A_REQUIRE_PTR(eigenvalue);
@@ -4532,9 +4546,8 @@ t4a_gpu_status t4a_gpu_lanczos_dense(const double* H, size_t n, const double* v0
 t4a_gpu_status t4a_gpu_krylov_combine(const double* basis, size_t len, size_t nb, const double* coef, double* out, double* norm2)
 {
     return guarded([&] {
-        if (len == 0 || nb == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "krylov_combine: len and nb must be positive");
-        if (nb > LINSOLVE_RESTART_DIM_MAX || (unsigned long long)len * nb > (unsigned long long)INT_MAX)
-            throw Error(T4A_GPU_INVALID_ARGUMENT, "krylov_combine: nb above " + std::to_string(LINSOLVE_RESTART_DIM_MAX) + " or a basis of more than INT_MAX elements");
+        require_basis_dims("krylov_combine", len, nb, LINSOLVE_RESTART_DIM_MAX,
+                           "nb above " + std::to_string(LINSOLVE_RESTART_DIM_MAX) + " or a basis of more than INT_MAX elements");
         T4A_REQUIRE_PTR(basis);
         T4A_REQUIRE_PTR(coef);
         T4A_REQUIRE_PTR(out);
@@ -4579,7 +4592,7 @@ t4a_gpu_status t4a_gpu_tdvp_options_default(t4a_gpu_tdvp_options* out)
         out->has_max_bond_dim = d.has_max_bond_dim;
         out->max_bond_dim = d.max_bond_dim;
         out->has_svd_policy = d.has_svd_policy;
-        out->svd_policy = t4a_gpu_svd_policy{d.svd_policy.threshold, d.svd_policy.scale, d.svd_policy.measure, d.svd_policy.rule};
+        out->svd_policy = to_c(d.svd_policy);
         out->krylov = t4a_gpu_krylov_expm_options{d.krylov.max_iter, d.krylov.max_time_splits, d.krylov.tol, d.krylov.breakdown_tol, d.krylov.hermitian_tol};
     });
 }
@@ -4606,7 +4619,7 @@ static TdvpOptions convert_tdvp_options(const t4a_gpu_tdvp_options* p)
     o.has_max_bond_dim = p->has_max_bond_dim != 0;
     o.max_bond_dim = p->max_bond_dim;
     o.has_svd_policy = p->has_svd_policy != 0;
-    if (o.has_svd_policy) o.svd_policy = SvdPolicy{p->svd_policy.threshold, p->svd_policy.scale, p->svd_policy.measure, p->svd_policy.rule};
+    if (o.has_svd_policy) o.svd_policy = from_c(p->svd_policy);
     o.krylov = convert_krylov_expm_options(p->krylov);
     o.validate();
     return o;
@@ -4622,9 +4635,7 @@ t4a_gpu_status t4a_gpu_tdvp_check_shapes(const size_t* op_dims4, size_t n_op, co
         KrylovExpmOptions ko;
         ko.max_iter = max_iter;
         ko.validate();
-        std::vector<std::array<size_t, 4>> op(n_op);
-        for (size_t i = 0; i < n_op; ++i) op[i] = {op_dims4[4 * i], op_dims4[4 * i + 1], op_dims4[4 * i + 2], op_dims4[4 * i + 3]};
-        tdvp_validate_shapes(op, dims3_list(state_dims3, n_state), center, max_iter);
+        tdvp_validate_shapes(dims4_list(op_dims4, n_op), dims3_list(state_dims3, n_state), center, max_iter);
     });
 }
 
@@ -4684,8 +4695,7 @@ t4a_gpu_status t4a_gpu_krylov_expm_dense(const double* H, size_t n, const double
         const KrylovExpmOptions o = convert_krylov_expm_options(*options);
         o.validate();
         if (!std::isfinite(tau)) throw Error(T4A_GPU_INVALID_ARGUMENT, "krylov_expm_dense: tau must be finite");
-        if (n == 0 || n > 46340 || (unsigned long long)n * (o.max_iter + 1) > (unsigned long long)INT_MAX)
-            throw Error(T4A_GPU_INVALID_ARGUMENT, "krylov_expm_dense: n must be positive and the matrix and the basis must hold at most INT_MAX elements");
+        require_dense_hook_dims("krylov_expm_dense", n, o.max_iter + 1);
         T4A_REQUIRE_PTR(H);
         T4A_REQUIRE_PTR(v0);
         T4A_REQUIRE_PTR(out);
@@ -4713,8 +4723,7 @@ t4a_gpu_status t4a_gpu_gse_options_default(t4a_gpu_gse_options* out)
         out->has_reference_max_bond_dim = d.has_reference_max_bond_dim;
         out->reference_max_bond_dim = d.reference_max_bond_dim;
         out->has_reference_svd_policy = d.has_reference_svd_policy;
-        out->reference_svd_policy =
-            t4a_gpu_svd_policy{d.reference_svd_policy.threshold, d.reference_svd_policy.scale, d.reference_svd_policy.measure, d.reference_svd_policy.rule};
+        out->reference_svd_policy = to_c(d.reference_svd_policy);
         out->density_weight_cutoff = d.density_weight_cutoff;
         out->hermitian_tol = d.hermitian_tol;
         out->normalize_references = d.normalize_references;
@@ -4730,8 +4739,7 @@ static GseOptions convert_gse_options(const t4a_gpu_gse_options* p)
     o.has_reference_max_bond_dim = p->has_reference_max_bond_dim != 0;
     o.reference_max_bond_dim = p->reference_max_bond_dim;
     o.has_reference_svd_policy = p->has_reference_svd_policy != 0;
-    if (o.has_reference_svd_policy)
-        o.reference_svd_policy = SvdPolicy{p->reference_svd_policy.threshold, p->reference_svd_policy.scale, p->reference_svd_policy.measure, p->reference_svd_policy.rule};
+    if (o.has_reference_svd_policy) o.reference_svd_policy = from_c(p->reference_svd_policy);
     o.density_weight_cutoff = p->density_weight_cutoff;
     o.hermitian_tol = p->hermitian_tol;
     o.normalize_references = p->normalize_references != 0;

@@ -1,6 +1,6 @@
 // dmrg.hip — two-site DMRG on the device (see dmrg.hpp).  Shape bookkeeping and the lowest eigenpair of the small projected matrix
-// of Lanczos (a cyclic Jacobi) are host work; every other floating-point operation runs in gfx950 kernels: the projected apply and
-// the orthogonalisation of linsolve.hpp, the Ritz combination, the eigen-residual and the finishing sums of kernels_dmrg.hip, the
+// of Lanczos (a cyclic Jacobi) are host work; every other floating-point operation runs in gfx950 kernels: the projected apply of
+// linsolve.hpp, the Arnoldi step of krylov.hpp, the Ritz combination, the eigen-residual and the finishing sums of kernels_dmrg.hip, the
 // QR and the SVD behind QrSweep and tensor_svd.
 #include "dmrg.hpp"
 
@@ -10,22 +10,6 @@
 #include <string>
 
 namespace t4a {
-
-namespace {
-
-void require_tol(double v, const std::string& what)
-{
-    if (!std::isfinite(v) || v < 0.0) throw Error(T4A_GPU_INVALID_ARGUMENT, what);
-}
-
-std::vector<std::array<size_t, 3>> dims3_of(const std::vector<DevCore>& cores)
-{
-    std::vector<std::array<size_t, 3>> d;
-    for (const DevCore& c : cores) d.push_back({c.l, c.s, c.r});
-    return d;
-}
-
-} // namespace
 
 // ------------------------------------------------------------------------------------------------ options and shapes
 void LanczosOptions::validate() const
@@ -50,99 +34,35 @@ void DmrgOptions::validate() const
     if (has_energy_tol) require_tol(energy_tol, "invalid DMRG option energy_tol: must be finite and non-negative");
     require_tol(real_scalar_tol, "invalid DMRG option real_scalar_tol: must be finite and non-negative");
     lanczos.validate();
-    if (has_svd_policy) {
-        if (!std::isfinite(svd_policy.threshold) || svd_policy.threshold < 0.0)
-            throw Error(T4A_GPU_INVALID_ARGUMENT, "Invalid SVD truncation threshold: threshold must be finite and non-negative");
-        if (svd_policy.scale < 0 || svd_policy.scale > 1 || svd_policy.measure < 0 || svd_policy.measure > 1 || svd_policy.rule < 0 || svd_policy.rule > 1)
-            throw Error(T4A_GPU_INVALID_ARGUMENT, "DmrgOptions::svd_policy: unknown scale, measure or rule");
-    }
+    if (has_svd_policy) validate_svd_policy(svd_policy, "DmrgOptions::svd_policy");
 }
 
 void dmrg_validate_shapes(const std::vector<std::array<size_t, 4>>& op, const std::vector<std::array<size_t, 3>>& state, size_t center, size_t max_iter)
 {
     const size_t n = state.size();
-    if (op.size() != n)
-        throw Error(T4A_GPU_INVALID_ARGUMENT, "dmrg: lengths differ: the operator has " + std::to_string(op.size()) + " sites, the state " + std::to_string(n));
-    if (n < 2) throw Error(T4A_GPU_INVALID_ARGUMENT, "dmrg: two-site DMRG requires at least one state edge");
-    for (size_t i = 0; i < n; ++i) {
-        if (op[i][1] != op[i][2])
-            throw Error(T4A_GPU_INVALID_ARGUMENT, "dmrg: site " + std::to_string(i) + " of the operator is not square: (" + std::to_string(op[i][1]) + ", " +
-                                                      std::to_string(op[i][2]) + ")");
-        if (op[i][1] != state[i][1])
-            throw Error(T4A_GPU_INVALID_ARGUMENT, "dmrg: site " + std::to_string(i) + " of the operator has dimension " + std::to_string(op[i][1]) +
-                                                      ", the state " + std::to_string(state[i][1]));
-    }
+    validate_chain_operands("dmrg", op, nullptr, state, "two-site DMRG requires at least one state edge");
     if (center >= n) throw Error(T4A_GPU_INVALID_ARGUMENT, "dmrg: center " + std::to_string(center) + " is not a state node (" + std::to_string(n) + " sites)");
     for (size_t i = 0; i + 1 < n; ++i) check_bond_step_dims("dmrg", i, state[i][0], state[i][1], state[i + 1][1], state[i + 1][2], op[i][3], max_iter);
-}
-
-// ------------------------------------------------------------------------------------------------ the small eigenproblem
-double jacobi_lowest_eigenpair(const std::vector<double>& a_in, size_t n, std::vector<double>& vec)
-{
-    std::vector<double> a(a_in), v(n * n, 0.0);
-    for (size_t i = 0; i < n; ++i) v[i + n * i] = 1.0;
-    double fro = 0.0;
-    for (double x : a) fro = fro + x * x;
-    fro = std::sqrt(fro);
-    const double tiny = 1e-19 * fro;
-    for (int sweep = 0; sweep < 100; ++sweep) {
-        bool rotated = false;
-        for (size_t p = 0; p + 1 < n; ++p) {
-            for (size_t q = p + 1; q < n; ++q) {
-                const double apq = a[p + n * q];
-                if (!(std::fabs(apq) > tiny)) continue;
-                rotated = true;
-                const double theta = (a[q + n * q] - a[p + n * p]) / (2.0 * apq);
-                const double t = (theta >= 0.0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
-                const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
-                a[p + n * p] = a[p + n * p] - t * apq;
-                a[q + n * q] = a[q + n * q] + t * apq;
-                a[p + n * q] = a[q + n * p] = 0.0;
-                for (size_t k = 0; k < n; ++k) {
-                    if (k != p && k != q) {
-                        const double akp = a[k + n * p], akq = a[k + n * q];
-                        a[k + n * p] = a[p + n * k] = c * akp - s * akq;
-                        a[k + n * q] = a[q + n * k] = s * akp + c * akq;
-                    }
-                    const double vkp = v[k + n * p], vkq = v[k + n * q];
-                    v[k + n * p] = c * vkp - s * vkq;
-                    v[k + n * q] = s * vkp + c * vkq;
-                }
-            }
-        }
-        if (!rotated) break;
-    }
-    size_t lo = 0;
-    for (size_t i = 1; i < n; ++i)
-        if (a[i + n * i] < a[lo + n * lo]) lo = i;
-    vec.assign(v.begin() + n * lo, v.begin() + n * (lo + 1));
-    double nn = 0.0;
-    for (double x : vec) nn = nn + x * x;
-    nn = std::sqrt(nn);
-    for (double& x : vec) x = x / nn;
-    return a[lo + n * lo];
 }
 
 // ------------------------------------------------------------------------------------------------ Lanczos
 void Lanczos::reserve(size_t len, size_t max_iter)
 {
-    grow(eng_, basis_, len * (max_iter + 1));
+    ar_.reserve(len, max_iter);
     grow(eng_, ax_, len);
-    gs_.reserve(max_iter + 1);
-    grow(eng_, hcol_, max_iter + 2);
-    grow(eng_, coef_, max_iter + 1);
 }
 
 void Lanczos::residual_sums(const GmresApply& apply, size_t len, const double* d_v, double lambda, double sums[3])
 {
     hipStream_t st = eng_.stream();
+    KrylovOrth& gs = ar_.orth();
     grow(eng_, ax_, len);
-    gs_.reserve(1);
+    gs.reserve(1);
     apply(d_v, ax_.get());
-    eig_residual_launch(d_v, ax_.get(), lambda, nullptr, len, gs_.npart(), st);
-    krylov_finish_launch(gs_.npart(), gs_workgroups(len), 3, gs_.scalars() + 1, st);
+    eig_residual_launch(d_v, ax_.get(), lambda, nullptr, len, gs.npart(), st);
+    krylov_finish_launch(gs.npart(), gs_workgroups(len), 3, gs.scalars() + 1, st);
     T4A_HIP(hipGetLastError());
-    T4A_HIP(hipMemcpyAsync(sums, gs_.scalars() + 1, sizeof(double) * 3, hipMemcpyDeviceToHost, st));
+    T4A_HIP(hipMemcpyAsync(sums, gs.scalars() + 1, sizeof(double) * 3, hipMemcpyDeviceToHost, st));
     eng_.sync();
 }
 
@@ -152,18 +72,16 @@ LanczosResult Lanczos::solve(const GmresApply& apply, size_t len, double* d_x, c
     hipStream_t st = eng_.stream();
     const size_t m = o.max_iter;
     reserve(len, m);
-    double* V = basis_.get();
-    const double n0 = gs_.norm(d_x, len, V); // v_0 = theta_0 / |theta_0|
+    const double n0 = ar_.start(d_x, len); // v_0 = theta_0 / |theta_0|
     if (!(n0 > o.breakdown_tol)) throw Error(T4A_GPU_INVALID_ARGUMENT, "hermitian_lanczos_lowest_eigenpair: the initial vector is numerically zero");
 
-    std::vector<std::vector<double>> hcols;
-    std::vector<double> a, coef;
+    std::vector<double> coef;
     // the Ritz vector sum_i c_i v_i into d_x and its true residual
     auto finalise = [&](size_t dim, double lambda, const std::vector<double>& c) {
-        T4A_HIP(hipMemcpyAsync(coef_.get(), c.data(), sizeof(double) * dim, hipMemcpyHostToDevice, st));
+        T4A_HIP(hipMemcpyAsync(ar_.coef(), c.data(), sizeof(double) * dim, hipMemcpyHostToDevice, st));
         // (the shares of |x|^2 that the combine leaves in npart are not read here: eig_residual below overwrites them with its own three
         // sums, and <v, v> comes from there)
-        krylov_combine_launch(V, len, (int)dim, coef_.get(), d_x, len, gs_.npart(), st);
+        krylov_combine_launch(ar_.basis(), len, (int)dim, ar_.coef(), d_x, len, ar_.orth().npart(), st);
         double sums[3];
         residual_sums(apply, len, d_x, lambda, sums);
         ++res.apply_calls;
@@ -174,31 +92,10 @@ LanczosResult Lanczos::solve(const GmresApply& apply, size_t len, double* d_x, c
     };
     double last_lambda = 0.0;
     for (size_t j = 0; j < m; ++j) {
-        double* w = V + len * (j + 1);
-        apply(V + len * j, w);
+        const double beta = ar_.step(apply, j, o.hermitian_tol, "hermitian_lanczos_lowest_eigenpair");
         ++res.apply_calls;
-        gs_.orth(V, len, (int)(j + 1), w, len, hcol_.get(), nullptr); // w is left normalised: v_{j+1}
-        std::vector<double> hc(j + 2);
-        T4A_HIP(hipMemcpyAsync(hc.data(), hcol_.get(), sizeof(double) * (j + 2), hipMemcpyDeviceToHost, st));
-        eng_.sync();
-        const double beta = hc[j + 1];
-        hcols.push_back(std::move(hc));
-        // projected_matrix_from_columns: the upper-Hessenberg data, rows below the subdiagonal zero
         const size_t dim = j + 1;
-        a.assign(dim * dim, 0.0);
-        for (size_t col = 0; col < dim; ++col)
-            for (size_t row = 0; row < dim && row < hcols[col].size(); ++row) a[row + dim * col] = hcols[col][row];
-        for (size_t r = 0; r < dim; ++r)
-            for (size_t c = r + 1; c < dim; ++c) {
-                const double x = a[r + dim * c], y = a[c + dim * r];
-                const double scale = std::max(1.0, std::max(std::fabs(x), std::fabs(y)));
-                if (!(std::fabs(x - y) <= o.hermitian_tol * scale))
-                    throw Error(T4A_GPU_INVALID_ARGUMENT, "hermitian_lanczos_lowest_eigenpair: projected operator is not Hermitian: entries (" +
-                                                              std::to_string(r) + ", " + std::to_string(c) + ") and its transpose differ by " +
-                                                              std::to_string(std::fabs(x - y)));
-                a[r + dim * c] = a[c + dim * r] = 0.5 * (x + y);
-            }
-        const double lambda = jacobi_lowest_eigenpair(a, dim, coef);
+        const double lambda = jacobi_lowest_eigenpair(ar_.projected(), dim, coef);
         last_lambda = lambda;
         const double estimate = beta * std::fabs(coef[dim - 1]);
         const bool broke_down = beta <= o.breakdown_tol;
@@ -217,45 +114,22 @@ void Lanczos::time_finalise(size_t len, size_t nb, size_t reps, double ms[3])
     reserve(len, nb);
     DevBuf<double> x;
     x.reserve(len);
-    fill_launch(basis_.get(), len * (nb + 1), 1.0 / std::sqrt((double)len), st);
-    fill_launch(coef_.get(), nb, 1.0 / std::sqrt((double)nb), st);
+    KrylovOrth& gs = ar_.orth();
+    fill_launch(ar_.basis(), len * (nb + 1), 1.0 / std::sqrt((double)len), st);
+    fill_launch(ar_.coef(), nb, 1.0 / std::sqrt((double)nb), st);
     fill_launch(ax_.get(), len, 1.0, st);
     const int G = gs_workgroups(len);
-    EventTimer t;
-    t.init();
     const std::function<void()> pieces[3] = {
-        [&] { krylov_combine_launch(basis_.get(), len, (int)nb, coef_.get(), x.get(), len, gs_.npart(), st); },
-        [&] { eig_residual_launch(x.get(), ax_.get(), 0.5, nullptr, len, gs_.npart(), st); },
-        [&] { krylov_finish_launch(gs_.npart(), G, 3, gs_.scalars() + 1, st); },
+        [&] { krylov_combine_launch(ar_.basis(), len, (int)nb, ar_.coef(), x.get(), len, gs.npart(), st); },
+        [&] { eig_residual_launch(x.get(), ax_.get(), 0.5, nullptr, len, gs.npart(), st); },
+        [&] { krylov_finish_launch(gs.npart(), G, 3, gs.scalars() + 1, st); },
     };
-    for (int k = 0; k < 3; ++k) {
-        pieces[k](); // warm-up
-        T4A_HIP(hipEventRecord(t.a, st));
-        for (size_t r = 0; r < reps; ++r) pieces[k]();
-        T4A_HIP(hipEventRecord(t.b, st));
-        T4A_HIP(hipEventSynchronize(t.b));
-        T4A_HIP(hipGetLastError());
-        float f = 0.0f;
-        T4A_HIP(hipEventElapsedTime(&f, t.a, t.b));
-        ms[k] = (double)f / (double)reps;
-    }
+    time_pieces(st, pieces, 3, reps, ms);
     eng_.sync();
 }
 
 // ------------------------------------------------------------------------------------------------ the sweeps
 namespace {
-
-// theta = x_i x_{i+1} as M x N into `theta`; -> len
-size_t two_site_vector(ProjectedOperator& po, size_t i, DevBuf<double>& theta)
-{
-    Engine& e = po.engine();
-    const auto ld = po.local_dims(i);
-    const int M = (int)(ld[0] * ld[1]), N = (int)(ld[2] * ld[3]), mid = (int)po.x[i].r;
-    const size_t len = (size_t)M * N;
-    grow(e, theta, len);
-    gemm_launch(gemm_desc(M, N, mid, po.x[i].buf.get(), M, po.x[i + 1].buf.get(), mid, theta.get(), M), e.stream());
-    return len;
-}
 
 // the Rayleigh quotient at the region of `center` (rayleigh_region: the centre and a neighbour)
 double rayleigh_quotient(ProjectedOperator& po, Lanczos& lz, size_t center, double real_scalar_tol)
@@ -264,7 +138,7 @@ double rayleigh_quotient(ProjectedOperator& po, Lanczos& lz, size_t center, doub
     const size_t i = center + 1 < n ? center : center - 1;
     po.check_step(i, 1, "dmrg");
     DevBuf<double> theta;
-    const size_t len = two_site_vector(po, i, theta);
+    const size_t len = po.two_site_vector(i, theta);
     po.prepare(i);
     double sums[3];
     lz.residual_sums([&](const double* v, double* y) { po.apply_prepared(v, y); }, len, theta.get(), 0.0, sums);
@@ -283,22 +157,15 @@ DmrgResult dmrg(Mpo& op, TensorTrain& init, size_t center, const DmrgOptions& o)
     Engine& e = po.engine();
     hipStream_t st = e.stream();
     const size_t n = po.len();
-    {
-        QrSweep sw(e);
-        sw.canonicalize(po.x, center);
-    }
+    po.canonicalize(center);
     Lanczos lz(e);
     DevBuf<double> theta;
-    SvdOptions so;
-    so.truncate = true;
-    if (o.has_svd_policy) so.policy = o.svd_policy;
-    so.has_max_bond_dim = o.has_max_bond_dim;
-    so.max_bond_dim = o.max_bond_dim;
+    const SvdOptions so = sweep_svd_options(o.has_svd_policy, o.svd_policy, o.has_max_bond_dim, o.max_bond_dim);
     double last_energy = 0.0;
 
     auto bond_step = [&](size_t i, bool move_right) {
         po.check_step(i, o.lanczos.max_iter, "dmrg");
-        const size_t len = two_site_vector(po, i, theta); // theta_0 = x_i x_{i+1}
+        const size_t len = po.two_site_vector(i, theta); // theta_0 = x_i x_{i+1}
         lz.reserve(len, o.lanczos.max_iter);
         po.prepare(i);
         const LanczosResult lr = lz.solve([&](const double* v, double* y) { po.apply_prepared(v, y); }, len, theta.get(), o.lanczos);
@@ -314,9 +181,7 @@ DmrgResult dmrg(Mpo& op, TensorTrain& init, size_t center, const DmrgOptions& o)
     bool has_previous = false;
     double previous = 0.0;
     for (size_t sweep = 0; sweep < o.nsweeps; ++sweep) {
-        for (size_t i = center; i + 1 < n; ++i) bond_step(i, true);
-        for (size_t i = n - 1; i-- > 0;) bond_step(i, false);
-        for (size_t i = 0; i < center; ++i) bond_step(i, true);
+        for_each_bond_from(center, n, bond_step);
         out.sweeps_completed = sweep + 1;
         if (o.has_energy_tol) {
             if (has_previous && std::fabs(last_energy - previous) <= o.energy_tol) {
@@ -335,15 +200,11 @@ DmrgResult dmrg(Mpo& op, TensorTrain& init, size_t center, const DmrgOptions& o)
 
 double dmrg_energy(Mpo& op, TensorTrain& state, size_t center, double real_scalar_tol)
 {
-    if (!std::isfinite(real_scalar_tol) || real_scalar_tol < 0.0)
-        throw Error(T4A_GPU_INVALID_ARGUMENT, "invalid DMRG option real_scalar_tol: must be finite and non-negative");
+    require_tol(real_scalar_tol, "invalid DMRG option real_scalar_tol: must be finite and non-negative");
     dmrg_validate_shapes(op.dims4(), dims3_of(state.cores), center, 1);
     ProjectedOperator po(op, state, nullptr);
     Engine& e = po.engine();
-    {
-        QrSweep sw(e);
-        sw.canonicalize(po.x, center);
-    }
+    po.canonicalize(center);
     Lanczos lz(e);
     const double v = rayleigh_quotient(po, lz, center, real_scalar_tol);
     e.sync();
@@ -355,14 +216,9 @@ LanczosResult lanczos_dense(const double* H, size_t n, const double* v0, const L
 {
     Engine e;
     hipStream_t st = e.stream();
-    DevBuf<double> dH, dx;
-    dH.reserve(n * n);
-    dx.reserve(n);
-    T4A_HIP(hipMemcpyAsync(dH.get(), H, sizeof(double) * n * n, hipMemcpyHostToDevice, st));
-    T4A_HIP(hipMemcpyAsync(dx.get(), v0, sizeof(double) * n, hipMemcpyHostToDevice, st));
+    DevBuf<double> dH = upload_vector(st, H, n * n), dx = upload_vector(st, v0, n);
     Lanczos lz(e);
-    const LanczosResult r =
-        lz.solve([&](const double* v, double* y) { gemm_launch(gemm_desc((int)n, 1, (int)n, dH.get(), (int)n, v, (int)n, y, (int)n), st); }, n, dx.get(), o);
+    const LanczosResult r = lz.solve(dense_apply(dH.get(), n, st), n, dx.get(), o);
     T4A_HIP(hipMemcpyAsync(v_out, dx.get(), sizeof(double) * n, hipMemcpyDeviceToHost, st));
     e.sync();
     return r;

@@ -15,17 +15,6 @@
 
 namespace t4a {
 
-// ---- kernels_dmrg.hip.  Device pointers; launchers enqueue on `stream` and do not synchronise.  The partition is gs_workgroups(len).
-// out = sum_i c[i] V[:, i] (i ascending from c[0] V[:, 0], every term rounded); npart[g] = the share of workgroup g in |out|^2.
-// nb <= LINSOLVE_RESTART_DIM_MAX: the coefficients sit in LDS.  Lanczos::solve does not read npart: eig_residual runs behind the combine on
-// the same buffer and supplies <v, v>; the reduction serves t4a_gpu_krylov_combine.  The launchers throw INVALID_ARGUMENT on an empty vector,
-// nb <= 0 or nq outside 1 .. 64 instead of leaving an output untouched.
-void krylov_combine_launch(const double* V, size_t ld, int nb, const double* c, double* out, size_t len, double* npart, hipStream_t stream);
-// r = hv - lambda v (r may be null); part3[3 g + (0, 1, 2)] = the shares of workgroup g in |r|^2, <v, hv>, <v, v>
-void eig_residual_launch(const double* v, const double* hv, double lambda, double* r, size_t len, double* part3, hipStream_t stream);
-// out[q] = sum_g part[q + nq g], g < n_part ascending, q < nq <= 64
-void krylov_finish_launch(const double* part, int n_part, int nq, double* out, hipStream_t stream);
-
 // ---- hermitian_lanczos_lowest_eigenpair (krylov.rs:530-634)
 struct LanczosOptions { // HermitianLanczosOptions::default()
     size_t max_iter = 64;
@@ -40,12 +29,9 @@ struct LanczosResult {
     bool converged = false;
     size_t apply_calls = 0;
 };
-// The lowest eigenpair of a symmetric n x n matrix (column-major, only read) by cyclic Jacobi on the host -> eigenvalue; vec: n doubles.
-double jacobi_lowest_eigenpair(const std::vector<double>& a, size_t n, std::vector<double>& vec);
-
 class Lanczos {
 public:
-    explicit Lanczos(Engine& e) : eng_(e), gs_(e) {}
+    explicit Lanczos(Engine& e) : eng_(e), ar_(e) {}
     void reserve(size_t len, size_t max_iter); // the basis: (max_iter + 1) len doubles
     // d_x: the start on entry, the unit-norm Ritz vector on exit.  The host reads one norm per solve, j + 2 doubles per step and three
     // per finalise.  INVALID_ARGUMENT: |start| <= breakdown_tol (ZeroInitialVector), a projected matrix that is not Hermitian.
@@ -58,8 +44,8 @@ public:
 
 private:
     Engine& eng_;
-    KrylovOrth gs_;
-    DevBuf<double> basis_, ax_, hcol_, coef_;
+    HermitianArnoldi ar_;
+    DevBuf<double> ax_;
 };
 
 // ---- DmrgOptions, DmrgResult of the reference

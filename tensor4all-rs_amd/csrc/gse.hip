@@ -13,13 +13,6 @@ namespace t4a {
 
 namespace {
 
-std::vector<std::array<size_t, 3>> dims3_of(const std::vector<DevCore>& cores)
-{
-    std::vector<std::array<size_t, 3>> d;
-    for (const DevCore& c : cores) d.push_back({c.l, c.s, c.r});
-    return d;
-}
-
 void require_int(size_t a, size_t b, size_t edge_child, const char* what)
 {
     if (a != 0 && b > (size_t)INT_MAX / a)
@@ -37,19 +30,11 @@ struct EdgeWork {
 // ------------------------------------------------------------------------------------------------ options and shapes
 void GseOptions::validate() const
 {
-    if (!std::isfinite(density_weight_cutoff) || density_weight_cutoff < 0.0)
-        throw Error(T4A_GPU_INVALID_ARGUMENT, "invalid GSE option density_weight_cutoff: must be finite and non-negative");
-    if (!std::isfinite(hermitian_tol) || hermitian_tol < 0.0)
-        throw Error(T4A_GPU_INVALID_ARGUMENT, "invalid GSE option hermitian_tol: must be finite and non-negative");
+    require_tol(density_weight_cutoff, "invalid GSE option density_weight_cutoff: must be finite and non-negative");
+    require_tol(hermitian_tol, "invalid GSE option hermitian_tol: must be finite and non-negative");
     if (has_reference_max_bond_dim && reference_max_bond_dim == 0)
         throw Error(T4A_GPU_INVALID_ARGUMENT, "invalid GSE option reference_max_bond_dim: must be greater than zero when set");
-    if (has_reference_svd_policy) {
-        if (!std::isfinite(reference_svd_policy.threshold) || reference_svd_policy.threshold < 0.0)
-            throw Error(T4A_GPU_INVALID_ARGUMENT, "Invalid SVD truncation threshold: threshold must be finite and non-negative");
-        if (reference_svd_policy.scale < 0 || reference_svd_policy.scale > 1 || reference_svd_policy.measure < 0 || reference_svd_policy.measure > 1 ||
-            reference_svd_policy.rule < 0 || reference_svd_policy.rule > 1)
-            throw Error(T4A_GPU_INVALID_ARGUMENT, "GseOptions::reference_svd_policy: unknown scale, measure or rule");
-    }
+    if (has_reference_svd_policy) validate_svd_policy(reference_svd_policy, "GseOptions::reference_svd_policy");
 }
 
 void gse_validate_shapes(const std::vector<std::array<size_t, 3>>& state, const std::vector<std::vector<std::array<size_t, 3>>>& refs, size_t center)
@@ -455,8 +440,6 @@ void gse_time_routes(size_t chi, size_t d, size_t K, size_t reps, double ms[4])
     part.reserve(gse_tiles(r + 1, (int)K));
     trace.reserve(1);
     ticket.reserve(1);
-    EventTimer t;
-    t.init();
     const std::function<void()> pieces[4] = {
         [&] {
             T4A_HIP(hipMemsetAsync(ticket.get(), 0, sizeof(unsigned), st));
@@ -469,18 +452,7 @@ void gse_time_routes(size_t chi, size_t d, size_t K, size_t reps, double ms[4])
         [&] { gse_absorb_launch(0, q, child, r, parent, L, nt, B.get(), kn, out, scratch.get(), st); },
         [&] { gse_absorb_gemm(e, 0, q, child, r, parent, L, nt, B.get(), kn, out, scratch.get()); },
     };
-    for (int p = 0; p < 4; ++p) {
-        pieces[p]();
-        T4A_HIP(hipGetLastError());
-        T4A_HIP(hipEventRecord(t.a, st));
-        for (size_t k = 0; k < reps; ++k) pieces[p]();
-        T4A_HIP(hipEventRecord(t.b, st));
-        T4A_HIP(hipEventSynchronize(t.b));
-        T4A_HIP(hipGetLastError());
-        float f = 0.0f;
-        T4A_HIP(hipEventElapsedTime(&f, t.a, t.b));
-        ms[p] = (double)f / (double)reps;
-    }
+    time_pieces(st, pieces, 4, reps, ms);
     e.sync();
 }
 

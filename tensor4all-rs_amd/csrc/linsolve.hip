@@ -49,13 +49,6 @@ double canonical_norm(TensorTrain& t)
     return host_norm(t.eng, cores[0]);
 }
 
-std::vector<std::array<size_t, 3>> dims3_of(const std::vector<DevCore>& cores)
-{
-    std::vector<std::array<size_t, 3>> d;
-    for (const DevCore& c : cores) d.push_back({c.l, c.s, c.r});
-    return d;
-}
-
 } // namespace
 
 // ------------------------------------------------------------------------------------------------ options and shapes
@@ -80,82 +73,75 @@ void LinsolveOptions::validate() const
     if (gmres_restart_dim > LINSOLVE_RESTART_DIM_MAX)
         throw Error(T4A_GPU_INVALID_ARGUMENT, "LinsolveOptions::gmres_restart_dim above " + std::to_string(LINSOLVE_RESTART_DIM_MAX) + " is not supported");
     if (gmres_max_restarts == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "LinsolveOptions::gmres_max_restarts must be greater than zero");
-    if (!std::isfinite(gmres_tol) || gmres_tol < 0.0) throw Error(T4A_GPU_INVALID_ARGUMENT, "LinsolveOptions::gmres_tol must be finite and not negative");
-    if (has_convergence_tol && (!std::isfinite(convergence_tol) || convergence_tol < 0.0))
-        throw Error(T4A_GPU_INVALID_ARGUMENT, "LinsolveOptions::convergence_tol must be finite and not negative");
+    require_tol(gmres_tol, "LinsolveOptions::gmres_tol must be finite and not negative");
+    if (has_convergence_tol) require_tol(convergence_tol, "LinsolveOptions::convergence_tol must be finite and not negative");
     if (!std::isfinite(a0) || !std::isfinite(a1)) throw Error(T4A_GPU_INVALID_ARGUMENT, "LinsolveOptions::a0 and a1 must be finite");
     if (has_max_bond_dim && max_bond_dim == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "LinsolveOptions::max_bond_dim must be positive when specified");
-    if (has_svd_policy) {
-        if (!std::isfinite(svd_policy.threshold) || svd_policy.threshold < 0.0)
-            throw Error(T4A_GPU_INVALID_ARGUMENT, "Invalid SVD truncation threshold: threshold must be finite and non-negative");
-        if (svd_policy.scale < 0 || svd_policy.scale > 1 || svd_policy.measure < 0 || svd_policy.measure > 1 || svd_policy.rule < 0 || svd_policy.rule > 1)
-            throw Error(T4A_GPU_INVALID_ARGUMENT, "LinsolveOptions::svd_policy: unknown scale, measure or rule");
+    if (has_svd_policy) validate_svd_policy(svd_policy, "LinsolveOptions::svd_policy");
+}
+
+std::vector<std::array<size_t, 3>> dims3_of(const std::vector<DevCore>& cores)
+{
+    std::vector<std::array<size_t, 3>> d;
+    for (const DevCore& c : cores) d.push_back({c.l, c.s, c.r});
+    return d;
+}
+
+void require_tol(double v, const std::string& what)
+{
+    if (!std::isfinite(v) || v < 0.0) throw Error(T4A_GPU_INVALID_ARGUMENT, what);
+}
+
+void validate_svd_policy(const SvdPolicy& p, const char* who)
+{
+    require_tol(p.threshold, "Invalid SVD truncation threshold: threshold must be finite and non-negative");
+    if (p.scale < 0 || p.scale > 1 || p.measure < 0 || p.measure > 1 || p.rule < 0 || p.rule > 1)
+        throw Error(T4A_GPU_INVALID_ARGUMENT, std::string(who) + ": unknown scale, measure or rule");
+}
+
+void validate_chain_operands(const char* who, const std::vector<std::array<size_t, 4>>& op, const std::vector<std::array<size_t, 3>>* rhs,
+                             const std::vector<std::array<size_t, 3>>& state, const char* few_sites)
+{
+    const std::string w = std::string(who) + ": ";
+    const size_t n = state.size();
+    if (op.size() != n || (rhs && rhs->size() != n))
+        throw Error(T4A_GPU_INVALID_ARGUMENT, w + "lengths differ: the operator has " + std::to_string(op.size()) + " sites, the state " + std::to_string(n) +
+                                                  (rhs ? ", the rhs " + std::to_string(rhs->size()) : std::string()));
+    if (n < 2) throw Error(T4A_GPU_INVALID_ARGUMENT, w + few_sites);
+    for (size_t i = 0; i < n; ++i) {
+        const size_t d = state[i][1];
+        if (op[i][1] != op[i][2])
+            throw Error(T4A_GPU_INVALID_ARGUMENT, w + "site " + std::to_string(i) + " of the operator is not square: (" + std::to_string(op[i][1]) + ", " +
+                                                      std::to_string(op[i][2]) + ")");
+        if (op[i][1] != d)
+            throw Error(T4A_GPU_INVALID_ARGUMENT, w + "site " + std::to_string(i) + " of the operator has dimension " + std::to_string(op[i][1]) +
+                                                      ", the state " + std::to_string(d));
+        if (rhs && (*rhs)[i][1] != d)
+            throw Error(T4A_GPU_INVALID_ARGUMENT, w + "site " + std::to_string(i) + " of the rhs has dimension " + std::to_string((*rhs)[i][1]) +
+                                                      ", the state " + std::to_string(d));
     }
+}
+
+SvdOptions sweep_svd_options(bool has_policy, const SvdPolicy& policy, bool has_max_bond_dim, size_t max_bond_dim)
+{
+    SvdOptions so;
+    so.truncate = true;
+    if (has_policy) so.policy = policy;
+    so.has_max_bond_dim = has_max_bond_dim;
+    so.max_bond_dim = max_bond_dim;
+    return so;
 }
 
 void linsolve_validate_shapes(const std::vector<std::array<size_t, 4>>& op, const std::vector<std::array<size_t, 3>>* rhs,
                               const std::vector<std::array<size_t, 3>>& state, size_t center, size_t restart_dim)
 {
     const size_t n = state.size();
-    if (op.size() != n || (rhs && rhs->size() != n))
-        throw Error(T4A_GPU_INVALID_ARGUMENT, "square_linsolve: lengths differ: the operator has " + std::to_string(op.size()) + " sites, the state " +
-                                                  std::to_string(n) + (rhs ? ", the rhs " + std::to_string(rhs->size()) : std::string()));
-    if (n < 2) throw Error(T4A_GPU_INVALID_ARGUMENT, "square_linsolve: fewer than two sites: the one-site local solve is not implemented");
-    for (size_t i = 0; i < n; ++i) {
-        const size_t d = state[i][1];
-        if (op[i][1] != op[i][2])
-            throw Error(T4A_GPU_INVALID_ARGUMENT, "square_linsolve: site " + std::to_string(i) + " of the operator is not square: (" +
-                                                      std::to_string(op[i][1]) + ", " + std::to_string(op[i][2]) + ")");
-        if (op[i][1] != d)
-            throw Error(T4A_GPU_INVALID_ARGUMENT, "square_linsolve: site " + std::to_string(i) + " of the operator has dimension " +
-                                                      std::to_string(op[i][1]) + ", the state " + std::to_string(d));
-        if (rhs && (*rhs)[i][1] != d)
-            throw Error(T4A_GPU_INVALID_ARGUMENT, "square_linsolve: site " + std::to_string(i) + " of the rhs has dimension " +
-                                                      std::to_string((*rhs)[i][1]) + ", the state " + std::to_string(d));
-    }
+    validate_chain_operands("square_linsolve", op, rhs, state, "fewer than two sites: the one-site local solve is not implemented");
     if (center >= n) throw Error(T4A_GPU_INVALID_ARGUMENT, "square_linsolve: center " + std::to_string(center) + " is out of range (" + std::to_string(n) + " sites)");
     for (size_t i = 0; i + 1 < n; ++i) check_step_dims(i, state[i][0], state[i][1], state[i + 1][1], state[i + 1][2], op[i][3], restart_dim);
 }
 
 // ------------------------------------------------------------------------------------------------ GMRES
-void KrylovOrth::reserve(size_t nb_max)
-{
-    grow(eng_, part_, std::max<size_t>(nb_max, 1) * GS_MAX_WORKGROUPS);
-    grow(eng_, npart_, 3 * GS_MAX_WORKGROUPS);
-    grow(eng_, scal_, 4);
-}
-
-double KrylovOrth::norm(const double* d_w, size_t len, double* d_out)
-{
-    hipStream_t st = eng_.stream();
-    double v = 0.0;
-    gs_norm2_launch(d_w, len, npart_.get(), st);
-    gs_normalize_launch(d_w, len, npart_.get(), d_out, scal_.get(), st);
-    T4A_HIP(hipMemcpyAsync(&v, scal_.get(), sizeof(double), hipMemcpyDeviceToHost, st));
-    eng_.sync();
-    return v;
-}
-
-KrylovDotsRoute krylov_dots_route(size_t, int nb) { return nb > GS_WIDE ? KrylovDotsRoute::Wide : KrylovDotsRoute::Serial; }
-
-void KrylovOrth::dots(const double* d_V, size_t ld, int nb, const double* d_w, size_t len)
-{
-    const KrylovDotsRoute r = route_ == KrylovDotsRoute::Auto ? krylov_dots_route(len, nb) : route_;
-    if (r == KrylovDotsRoute::Wide) gs_dots_wide_launch(d_V, ld, nb, d_w, len, part_.get(), eng_.stream());
-    else gs_dots_launch(d_V, ld, nb, d_w, len, part_.get(), eng_.stream());
-}
-
-void KrylovOrth::orth(const double* d_V, size_t ld, int nb, double* d_w, size_t len, double* d_hcol, double* d_hpass)
-{
-    hipStream_t st = eng_.stream();
-    const int G = gs_workgroups(len);
-    dots(d_V, ld, nb, d_w, len);
-    gs_update_launch(d_V, ld, nb, d_w, len, part_.get(), G, d_hcol, true, d_hpass, npart_.get(), st);
-    dots(d_V, ld, nb, d_w, len);
-    gs_update_launch(d_V, ld, nb, d_w, len, part_.get(), G, d_hcol, false, d_hpass ? d_hpass + nb : nullptr, npart_.get(), st);
-    gs_normalize_launch(d_w, len, npart_.get(), d_w, d_hcol + nb, st);
-}
-
 void Gmres::reserve(size_t len, size_t restart_dim)
 {
     const size_t m = restart_dim;
@@ -266,7 +252,7 @@ GmresResult Gmres::solve(const GmresApply& apply, size_t len, const double* d_b,
             double* w = V + len * (j + 1);
             apply(V + len * j, w);
             ++res.apply_calls;
-            orth(V, len, (int)(j + 1), w, len, d_hcol, nullptr);
+            gs_.orth(V, len, (int)(j + 1), w, len, d_hcol, nullptr);
             T4A_HIP(hipMemcpyAsync(ha.data(), d_hcol, sizeof(double) * (j + 2), hipMemcpyDeviceToHost, st));
             eng_.sync();
             const double h_next = ha[j + 1];
@@ -577,24 +563,12 @@ void ProjectedOperator::time_one_site(size_t c, size_t reps, double ms[3])
     fill_launch(v.get(), len, 1.0 / std::sqrt((double)len), st);
     GemmDesc g2 = gemm_desc(M, cr, W * cr, t_.get(), M, r1_, cr, y.get(), M);
     g2.transB = 1;
-    EventTimer t;
-    t.init();
     const std::function<void()> pieces[3] = {
         [&] { linsolve_hl_launch(L, A.buf.get(), hl_.get(), (int)X.l, (int)A.l, (int)X.s, W, st); },
         [&] { gemm_launch(gemm_desc(W * M, cr, M, hl_.get(), W * M, v.get(), M, t_.get(), W * M), st); },
         [&] { gemm_launch(g2, st); },
     };
-    for (int k = 0; k < 3; ++k) {
-        pieces[k](); // warm-up
-        T4A_HIP(hipEventRecord(t.a, st));
-        for (size_t r = 0; r < reps; ++r) pieces[k]();
-        T4A_HIP(hipEventRecord(t.b, st));
-        T4A_HIP(hipEventSynchronize(t.b));
-        T4A_HIP(hipGetLastError());
-        float f = 0.0f;
-        T4A_HIP(hipEventElapsedTime(&f, t.a, t.b));
-        ms[k] = (double)f / (double)reps;
-    }
+    time_pieces(st, pieces, 3, reps, ms);
     e.sync();
 }
 
@@ -642,6 +616,23 @@ void ProjectedOperator::split_and_advance(size_t i, const double* d_theta, const
     else update_right_from_prepared(i);
 }
 
+size_t ProjectedOperator::two_site_vector(size_t i, DevBuf<double>& theta)
+{
+    Engine& e = engine();
+    const auto ld = local_dims(i);
+    const int M = (int)(ld[0] * ld[1]), N = (int)(ld[2] * ld[3]), mid = (int)x[i].r;
+    const size_t len = (size_t)M * N;
+    grow(e, theta, len);
+    gemm_launch(gemm_desc(M, N, mid, x[i].buf.get(), M, x[i + 1].buf.get(), mid, theta.get(), M), e.stream());
+    return len;
+}
+
+void ProjectedOperator::canonicalize(size_t center)
+{
+    QrSweep sw(engine());
+    sw.canonicalize(x, center);
+}
+
 void ProjectedOperator::time_step(size_t site, size_t nb, size_t reps, double ms[5])
 {
     const auto ld = local_dims(site);
@@ -659,8 +650,6 @@ void ProjectedOperator::time_step(size_t site, size_t nb, size_t reps, double ms
     fill_launch(basis.get(), len * (nb + 1), 1.0 / std::sqrt((double)len), st);
     double* w = basis.get() + len * nb;
     const int G = gs_workgroups(len);
-    EventTimer t;
-    t.init();
     const std::function<void()> pieces[5] = {
         [&] { product_left(basis.get()); },
         [&] { product_right(w); },
@@ -668,17 +657,7 @@ void ProjectedOperator::time_step(size_t site, size_t nb, size_t reps, double ms
         [&] { gs_update_launch(basis.get(), len, (int)nb, w, len, part.get(), G, hcol.get(), true, nullptr, npart.get(), st); },
         [&] { gs_normalize_launch(w, len, npart.get(), w, hcol.get() + nb, st); },
     };
-    for (int k = 0; k < 5; ++k) {
-        pieces[k](); // warm-up
-        T4A_HIP(hipEventRecord(t.a, st));
-        for (size_t r = 0; r < reps; ++r) pieces[k]();
-        T4A_HIP(hipEventRecord(t.b, st));
-        T4A_HIP(hipEventSynchronize(t.b));
-        T4A_HIP(hipGetLastError());
-        float f = 0.0f;
-        T4A_HIP(hipEventElapsedTime(&f, t.a, t.b));
-        ms[k] = (double)f / (double)reps;
-    }
+    time_pieces(st, pieces, 5, reps, ms);
     e.sync();
 }
 
@@ -842,30 +821,21 @@ LinsolveResult square_linsolve(Mpo& op, TensorTrain& rhs, TensorTrain& init, siz
     Engine& e = po.engine();
     hipStream_t st = e.stream();
     const size_t n = po.len();
-    {
-        QrSweep sw(e);
-        sw.canonicalize(po.x, center);
-    }
+    po.canonicalize(center);
     Gmres gm(e);
     DevBuf<double> theta, bt;
-    SvdOptions so;
-    so.truncate = true;
-    if (o.has_svd_policy) so.policy = o.svd_policy;
-    so.has_max_bond_dim = o.has_max_bond_dim;
-    so.max_bond_dim = o.max_bond_dim;
+    const SvdOptions so = sweep_svd_options(o.has_svd_policy, o.svd_policy, o.has_max_bond_dim, o.max_bond_dim);
 
     auto bond_step = [&](size_t i, bool move_right) {
         po.check_step(i, o.gmres_restart_dim);
         const auto ld = po.local_dims(i);
-        const int chi_l = (int)ld[0], d1 = (int)ld[1], d2 = (int)ld[2], chi_r = (int)ld[3];
-        const int M = chi_l * d1, N = d2 * chi_r, mid = (int)po.x[i].r;
-        const size_t len = (size_t)M * N;
-        grow(e, theta, len);
+        const size_t len = ld[0] * ld[1] * ld[2] * ld[3];
+        grow(e, theta, len); // both vectors of the step are sized (and the stream drained, if one grows) before anything is queued
         grow(e, bt, len);
         gm.reserve(len, o.gmres_restart_dim);
         po.local_rhs(i, bt.get());
         po.prepare(i);
-        gemm_launch(gemm_desc(M, N, mid, po.x[i].buf.get(), M, po.x[i + 1].buf.get(), mid, theta.get(), M), st); // theta_0 = x_i x_{i+1}
+        po.two_site_vector(i, theta); // theta_0 = x_i x_{i+1}
         const GmresResult gr = gm.solve([&](const double* v, double* y) { po.apply_prepared(v, y); }, len, bt.get(), theta.get(), o.a0, o.a1, o.gmres_tol,
                                         o.gmres_tolerance_mode, o.gmres_restart_dim, o.gmres_max_restarts);
         ++out.stats.local_solves;
@@ -876,9 +846,7 @@ LinsolveResult square_linsolve(Mpo& op, TensorTrain& rhs, TensorTrain& init, siz
 
     for (size_t sweep = 0; sweep < o.nfullsweeps; ++sweep) {
         out.sweeps = sweep + 1;
-        for (size_t i = center; i + 1 < n; ++i) bond_step(i, true);
-        for (size_t i = n - 1; i-- > 0;) bond_step(i, false);
-        for (size_t i = 0; i < center; ++i) bond_step(i, true);
+        for_each_bond_from(center, n, bond_step);
         if (o.has_convergence_tol) {
             e.sync();
             TensorTrain xt(po.x, st);
@@ -906,16 +874,9 @@ GmresResult gmres_dense(const double* H, size_t n, const double* b, const double
 {
     Engine e;
     hipStream_t st = e.stream();
-    DevBuf<double> dH, db, dx;
-    dH.reserve(n * n);
-    db.reserve(n);
-    dx.reserve(n);
-    T4A_HIP(hipMemcpyAsync(dH.get(), H, sizeof(double) * n * n, hipMemcpyHostToDevice, st));
-    T4A_HIP(hipMemcpyAsync(db.get(), b, sizeof(double) * n, hipMemcpyHostToDevice, st));
-    T4A_HIP(hipMemcpyAsync(dx.get(), x0, sizeof(double) * n, hipMemcpyHostToDevice, st));
+    DevBuf<double> dH = upload_vector(st, H, n * n), db = upload_vector(st, b, n), dx = upload_vector(st, x0, n);
     Gmres gm(e);
-    const GmresResult r = gm.solve([&](const double* v, double* y) { gemm_launch(gemm_desc((int)n, 1, (int)n, dH.get(), (int)n, v, (int)n, y, (int)n), st); }, n,
-                                   db.get(), dx.get(), a0, a1, tol, mode, restart_dim, max_restarts);
+    const GmresResult r = gm.solve(dense_apply(dH.get(), n, st), n, db.get(), dx.get(), a0, a1, tol, mode, restart_dim, max_restarts);
     T4A_HIP(hipMemcpyAsync(x_out, dx.get(), sizeof(double) * n, hipMemcpyDeviceToHost, st));
     e.sync();
     return r;
@@ -923,36 +884,16 @@ GmresResult gmres_dense(const double* H, size_t n, const double* b, const double
 
 void linsolve_orth(const double* basis, size_t len, size_t nb, double* w, double* h_out, double* norm_out)
 {
-    Engine e;
-    hipStream_t st = e.stream();
-    DevBuf<double> dV, dw, dh;
-    dV.reserve(len * nb);
-    dw.reserve(len);
-    dh.reserve(3 * nb + 1);
-    T4A_HIP(hipMemcpyAsync(dV.get(), basis, sizeof(double) * len * nb, hipMemcpyHostToDevice, st));
-    T4A_HIP(hipMemcpyAsync(dw.get(), w, sizeof(double) * len, hipMemcpyHostToDevice, st));
-    Gmres gm(e);
-    gm.reserve(len, nb);
-    gm.orth(dV.get(), len, (int)nb, dw.get(), len, dh.get(), dh.get() + nb + 1);
-    T4A_HIP(hipGetLastError());
-    std::vector<double> hc(nb + 1);
-    T4A_HIP(hipMemcpyAsync(hc.data(), dh.get(), sizeof(double) * (nb + 1), hipMemcpyDeviceToHost, st));
-    T4A_HIP(hipMemcpyAsync(h_out, dh.get() + nb + 1, sizeof(double) * 2 * nb, hipMemcpyDeviceToHost, st));
-    T4A_HIP(hipMemcpyAsync(w, dw.get(), sizeof(double) * len, hipMemcpyDeviceToHost, st));
-    e.sync();
-    *norm_out = hc[nb];
+    krylov_orth_host(basis, len, nb, w, KrylovDotsRoute::Serial, h_out, norm_out);
 }
 
 void krylov_orth_host(const double* basis, size_t len, size_t nb, double* w, KrylovDotsRoute route, double* h_out, double* norm_out)
 {
     Engine e;
     hipStream_t st = e.stream();
-    DevBuf<double> dV, dw, dh;
-    dV.reserve(len * nb);
-    dw.reserve(len);
+    DevBuf<double> dV = upload_vector(st, basis, len * nb), dw = upload_vector(st, w, len);
+    DevBuf<double> dh;
     dh.reserve(3 * nb + 1);
-    T4A_HIP(hipMemcpyAsync(dV.get(), basis, sizeof(double) * len * nb, hipMemcpyHostToDevice, st));
-    T4A_HIP(hipMemcpyAsync(dw.get(), w, sizeof(double) * len, hipMemcpyHostToDevice, st));
     KrylovOrth gs(e);
     gs.reserve(nb);
     gs.set_dots_route(route);
@@ -979,23 +920,11 @@ void krylov_time_dots(size_t len, size_t nb, size_t reps, double ms[2])
     part.reserve(nb * GS_MAX_WORKGROUPS);
     fill_launch(basis.get(), len * (nb + 1), 1.0 / std::sqrt((double)len), st);
     const double* w = basis.get() + len * nb;
-    EventTimer t;
-    t.init();
     const std::function<void()> pieces[2] = {
         [&] { gs_dots_launch(basis.get(), len, (int)nb, w, len, part.get(), st); },
         [&] { gs_dots_wide_launch(basis.get(), len, (int)nb, w, len, part.get(), st); },
     };
-    for (int k = 0; k < 2; ++k) {
-        pieces[k](); // warm-up
-        T4A_HIP(hipEventRecord(t.a, st));
-        for (size_t r = 0; r < reps; ++r) pieces[k]();
-        T4A_HIP(hipEventRecord(t.b, st));
-        T4A_HIP(hipEventSynchronize(t.b));
-        T4A_HIP(hipGetLastError());
-        float f = 0.0f;
-        T4A_HIP(hipEventElapsedTime(&f, t.a, t.b));
-        ms[k] = (double)f / (double)reps;
-    }
+    time_pieces(st, pieces, 2, reps, ms);
     e.sync();
 }
 

@@ -21,42 +21,21 @@
 #include <memory>
 #include <vector>
 
+#include "krylov.hpp"
 #include "mpo.hpp"
 #include "tensorops.hpp"
 
 namespace t4a {
 
-// ---- kernels_linsolve.hip.  All pointers are device pointers; launchers enqueue on `stream` and do not synchronise.
-constexpr int GS_MAX_WORKGROUPS = 128;
-// workgroups of every vector kernel below for a vector of `len` elements (a function of len alone: the fixed partition)
-int gs_workgroups(size_t len);
+// ---- kernels_linsolve.hip (the vector kernels of the Krylov solvers are declared in krylov.hpp).  All pointers are device pointers;
+// launchers enqueue on `stream` and do not synchronise.
 // HL from L[chi, Wl, chi] and A[Wl, d, d, W]; HR from A[W, d, d, Wr] and R[chi, Wr, chi]
 void linsolve_hl_launch(const double* L, const double* A, double* HL, int chi, int Wl, int d, int W, hipStream_t stream);
 void linsolve_hr_launch(const double* A, const double* R, double* HR, int chi, int W, int d, int Wr, hipStream_t stream);
-// part[i + nb g] = <V[:, i], w> over the elements of workgroup g, i < nb; V is len x nb with leading dimension ld
-void gs_dots_launch(const double* V, size_t ld, int nb, const double* w, size_t len, double* part, hipStream_t stream);
-// c[i] = sum_g part[i + nb g], g < n_part ascending (n_part = gs_workgroups(len) behind gs_dots_launch; 1: part holds the coefficients);
-// w -= sum_i c[i] V[:, i] (i ascending, every term rounded); npart[g] = the share of workgroup g in |w|^2.
-// hcol (may be null): hcol[i] = c[i] when first_pass, else hcol[i] += c[i]; hpass (may be null): hpass[i] = c[i].
-void gs_update_launch(const double* V, size_t ld, int nb, double* w, size_t len, const double* part, int n_part, double* hcol, bool first_pass,
-                      double* hpass, double* npart, hipStream_t stream);
-void gs_norm2_launch(const double* w, size_t len, double* npart, hipStream_t stream);
-// nrm = sqrt(sum_g npart[g]); out = w * (1 / nrm) (out may be w, or null: the norm only); *norm_out = nrm (may be null)
-void gs_normalize_launch(const double* w, size_t len, const double* npart, double* out, double* norm_out, hipStream_t stream);
 // r = b - (a0 x + a1 ax) with the shares of |r|^2 in npart
 void linsolve_residual_launch(const double* b, const double* x, const double* ax, double a0, double a1, double* r, size_t len, double* npart,
                               hipStream_t stream);
 void linsolve_scale_launch(const double* in, double alpha, double* out, size_t len, hipStream_t stream);
-// ---- kernels_tdvp.hip.  gs_dots with a second grid dimension over the basis vectors: workgroup (g, y) forms part[i + nb g] for the
-// GS_WIDE vectors i = GS_WIDE y .. of element group g, with the element partition, the summation order and the reduction tree of
-// gs_dots_launch: every part[i + nb g] has the same bits, and gs_update_launch runs unchanged behind it.
-constexpr int GS_WIDE = 8;
-void gs_dots_wide_launch(const double* V, size_t ld, int nb, const double* w, size_t len, double* part, hipStream_t stream);
-// Which launch forms the projections of an orthogonalisation pass.  Serial: gs_dots_launch, what Gmres and Lanczos run.  Wide:
-// gs_dots_wide_launch.  Auto: krylov_dots_route(len, nb) decides per pass (KrylovExpm of tdvp.hpp).
-enum class KrylovDotsRoute : int { Serial = 0, Wide = 1, Auto = 2 };
-// The rule of Auto, a function of the shape alone: Wide when the serial kernel would walk more than GS_WIDE vectors per workgroup.
-KrylovDotsRoute krylov_dots_route(size_t len, int nb);
 
 // ---- GMRES on (a0 + a1 H) x = b (krylov.rs:1083-1490).  The Arnoldi basis is built from the unshifted H, a0 and a1 enter the
 // Hessenberg column; Givens rotations and the triangular solve run on the host, which reads j + 2 doubles per step and one norm per
@@ -69,37 +48,12 @@ struct GmresResult {
     bool converged = false;
     size_t apply_calls = 0;
 };
-using GmresApply = std::function<void(const double* d_v, double* d_out)>; // enqueues out = H v on the engine's stream
-// What the Krylov solvers (Gmres here, Lanczos of dmrg.hpp, KrylovExpm of tdvp.hpp) launch around their apply: the two-pass orthogonalisation step, the norm
-// read by the host, and the buffers of the partial sums.
-class KrylovOrth {
-public:
-    explicit KrylovOrth(Engine& e) : eng_(e) {}
-    void reserve(size_t nb_max); // at most nb_max basis vectors per pass
-    void set_dots_route(KrylovDotsRoute r) { route_ = r; } // Serial unless a solver asks otherwise; the results have the same bits
-    // One two-pass orthogonalisation step: w against the nb columns of V (leading dimension ld), then normalised in place.
-    // d_hcol: nb + 1 doubles (the column of H, h_{nb} = the norm); d_hpass (may be null): 2 nb doubles, the coefficients of pass 1 and of pass 2.
-    void orth(const double* d_V, size_t ld, int nb, double* d_w, size_t len, double* d_hcol, double* d_hpass);
-    // host value of |w| (one read); out (may be null, may be w) receives w / |w|
-    double norm(const double* d_w, size_t len, double* d_out = nullptr);
-    double* npart() { return npart_.get(); }   // 3 GS_MAX_WORKGROUPS doubles: the shares of |w|^2, or the three sums of eig_residual
-    double* scalars() { return scal_.get(); }  // 4 doubles: [0] the landing place of norm(), [1..3] free for the caller
-    Engine& engine() { return eng_; }
-
-private:
-    void dots(const double* d_V, size_t ld, int nb, const double* d_w, size_t len);
-    Engine& eng_;
-    DevBuf<double> part_, npart_, scal_;
-    KrylovDotsRoute route_ = KrylovDotsRoute::Serial;
-};
 class Gmres {
 public:
     explicit Gmres(Engine& e) : eng_(e), gs_(e) {}
     // x: the start on entry, the solution on exit (device, len doubles).  Non-convergence is a flag.  INVALID_ARGUMENT: a0 == a1 == 0.
     GmresResult solve(const GmresApply& apply, size_t len, const double* d_b, double* d_x, double a0, double a1, double tol, GmresToleranceMode mode,
                       size_t restart_dim, size_t max_restarts);
-    // KrylovOrth::orth as solve() launches it
-    void orth(const double* d_V, size_t ld, int nb, double* d_w, size_t len, double* d_hcol, double* d_hpass) { gs_.orth(d_V, ld, nb, d_w, len, d_hcol, d_hpass); }
     void reserve(size_t len, size_t restart_dim);
 
 private:
@@ -152,6 +106,26 @@ void check_bond_step_dims(const char* who, size_t i, size_t chi_l, size_t d1, si
 // basis_dim + 1 columns of M chi_r elements, M = chi_l d, W the operator bond to the right of the site.
 // INVALID_ARGUMENT "<who>: a work buffer of the one-site step at site c ...".
 void check_site_step_dims(const char* who, size_t c, size_t chi_l, size_t d, size_t chi_r, size_t W, size_t basis_dim);
+
+// ---- what the sweeps of square_linsolve, dmrg, tdvp and gse share on the host
+std::vector<std::array<size_t, 3>> dims3_of(const std::vector<DevCore>& cores);
+void require_tol(double v, const std::string& what); // INVALID_ARGUMENT `what` unless v is finite and not negative
+// INVALID_ARGUMENT: a threshold that is not finite or negative, "<who>: unknown scale, measure or rule"
+void validate_svd_policy(const SvdPolicy& policy, const char* who);
+// The checks every solver starts with, in this order: "<who>: lengths differ: ..", "<who>: <few_sites>" for fewer than two sites, then per
+// site an operator site that is not square, one that does not match the state's dimension, a rhs site (rhs may be null) that does not.
+void validate_chain_operands(const char* who, const std::vector<std::array<size_t, 4>>& op, const std::vector<std::array<size_t, 3>>* rhs,
+                             const std::vector<std::array<size_t, 3>>& state, const char* few_sites);
+// The options of the split of a bond step: truncating, `policy` and `max_bond_dim` where the solver's options carry them
+SvdOptions sweep_svd_options(bool has_policy, const SvdPolicy& policy, bool has_max_bond_dim, size_t max_bond_dim);
+// The Euler tour of the bonds from `center`, the second node of a step the new centre: f(i, move_right) for the bonds c .. n-2 to the
+// right, n-2 .. 0 to the left, 0 .. c-1 to the right
+template <class F> void for_each_bond_from(size_t center, size_t n, F&& f)
+{
+    for (size_t i = center; i + 1 < n; ++i) f(i, true);
+    for (size_t i = n - 1; i-- > 0;) f(i, false);
+    for (size_t i = 0; i < center; ++i) f(i, true);
+}
 
 // ||(a0 + a1 A) x - b|| / ||b||, the absolute norm when ||b|| <= 1e-15: the exact naive apply, add / sub, and the norm of the residual
 // train from its QR right-canonical form (the transfer-matrix norm2 would lose half of the digits in the cancellation).
@@ -207,6 +181,8 @@ public:
     // tensor_svd with `so`, x[site] = U | U S and x[site + 1] = S Vt | Vt (move_right | left: the singular values go to the new centre), both
     // sites are invalidated and the environment of the side left behind is rebuilt from the half operators of prepare(site).
     void split_and_advance(size_t site, const double* d_theta, const SvdOptions& so, bool move_right, const char* who);
+    size_t two_site_vector(size_t site, DevBuf<double>& theta); // theta = x_site x_{site+1} as M x N, grown as needed -> M N
+    void canonicalize(size_t center);                            // x onto `center` by the thin QR steps of a QrSweep
 
     std::vector<DevCore> x, b;
 
@@ -237,9 +213,9 @@ LinsolveResult square_linsolve(Mpo& op, TensorTrain& rhs, TensorTrain& init, siz
 // Test hook: GMRES as the sweeps run it on a dense n x n matrix H (host, column-major) applied on the device.
 GmresResult gmres_dense(const double* H, size_t n, const double* b, const double* x0, double a0, double a1, double tol, GmresToleranceMode mode,
                         size_t restart_dim, size_t max_restarts, double* x_out);
-// Test hook: Gmres::orth on host arrays: basis len x nb, w len (in/out), h_out 2 nb (pass 1, pass 2), *norm_out
+// Test hook: krylov_orth_host on the serial route, what Gmres launches: basis len x nb, w len (in/out), h_out 2 nb (pass 1, pass 2), *norm_out
 void linsolve_orth(const double* basis, size_t len, size_t nb, double* w, double* h_out, double* norm_out);
-// Test hook: KrylovOrth::orth with the given route on host arrays, arguments as linsolve_orth
+// Test hook: KrylovOrth::orth with the given route on host arrays
 void krylov_orth_host(const double* basis, size_t len, size_t nb, double* w, KrylovDotsRoute route, double* h_out, double* norm_out);
 // Probe hook: device ms (events around `reps` launches behind a warm-up launch) of gs_dots_launch [0] and gs_dots_wide_launch [1] with nb
 // basis vectors of length len, behind the argument checks (INVALID_ARGUMENT) and require_device

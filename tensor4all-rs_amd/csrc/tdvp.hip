@@ -1,6 +1,6 @@
 // tdvp.hip — two-site TDVP on the device (see tdvp.hpp).  Shape bookkeeping, the region plan and the exponential of the small projected
 // matrix of the Krylov solver (a cyclic Jacobi) are host work; every other floating-point operation runs in gfx950 kernels: the
-// projected applies and the orthogonalisation of linsolve.hpp (with the projections of kernels_tdvp.hip), the combination of
+// projected applies of linsolve.hpp, the Arnoldi step of krylov.hpp (with the projections of kernels_tdvp.hip), the combination of
 // kernels_dmrg.hip, the QR and the SVD behind QrSweep and tensor_svd.
 #include "tdvp.hpp"
 
@@ -10,22 +10,6 @@
 #include <string>
 
 namespace t4a {
-
-namespace {
-
-void require_tol(double v, const std::string& what)
-{
-    if (!std::isfinite(v) || v < 0.0) throw Error(T4A_GPU_INVALID_ARGUMENT, what);
-}
-
-std::vector<std::array<size_t, 3>> dims3_of(const std::vector<DevCore>& cores)
-{
-    std::vector<std::array<size_t, 3>> d;
-    for (const DevCore& c : cores) d.push_back({c.l, c.s, c.r});
-    return d;
-}
-
-} // namespace
 
 // ------------------------------------------------------------------------------------------------ options and shapes
 void KrylovExpmOptions::validate() const
@@ -57,12 +41,7 @@ void TdvpOptions::validate() const
         throw Error(T4A_GPU_INVALID_ARGUMENT,
                     "tdvp: exponent_step must be real here: real-time evolution (a non-zero imaginary part) needs complex tensor trains, which this project does not have");
     krylov.validate();
-    if (has_svd_policy) {
-        if (!std::isfinite(svd_policy.threshold) || svd_policy.threshold < 0.0)
-            throw Error(T4A_GPU_INVALID_ARGUMENT, "Invalid SVD truncation threshold: threshold must be finite and non-negative");
-        if (svd_policy.scale < 0 || svd_policy.scale > 1 || svd_policy.measure < 0 || svd_policy.measure > 1 || svd_policy.rule < 0 || svd_policy.rule > 1)
-            throw Error(T4A_GPU_INVALID_ARGUMENT, "TdvpOptions::svd_policy: unknown scale, measure or rule");
-    }
+    if (has_svd_policy) validate_svd_policy(svd_policy, "TdvpOptions::svd_policy");
 }
 
 namespace {
@@ -78,17 +57,7 @@ void require_end_center(size_t n, size_t center)
 void tdvp_validate_shapes(const std::vector<std::array<size_t, 4>>& op, const std::vector<std::array<size_t, 3>>& state, size_t center, size_t max_iter)
 {
     const size_t n = state.size();
-    if (op.size() != n)
-        throw Error(T4A_GPU_INVALID_ARGUMENT, "tdvp: lengths differ: the operator has " + std::to_string(op.size()) + " sites, the state " + std::to_string(n));
-    if (n < 2) throw Error(T4A_GPU_INVALID_ARGUMENT, "tdvp: two-site TDVP requires at least one state edge");
-    for (size_t i = 0; i < n; ++i) {
-        if (op[i][1] != op[i][2])
-            throw Error(T4A_GPU_INVALID_ARGUMENT, "tdvp: site " + std::to_string(i) + " of the operator is not square: (" + std::to_string(op[i][1]) + ", " +
-                                                      std::to_string(op[i][2]) + ")");
-        if (op[i][1] != state[i][1])
-            throw Error(T4A_GPU_INVALID_ARGUMENT, "tdvp: site " + std::to_string(i) + " of the operator has dimension " + std::to_string(op[i][1]) +
-                                                      ", the state " + std::to_string(state[i][1]));
-    }
+    validate_chain_operands("tdvp", op, nullptr, state, "two-site TDVP requires at least one state edge");
     require_end_center(n, center);
     for (size_t i = 0; i + 1 < n; ++i) check_bond_step_dims("tdvp", i, state[i][0], state[i][1], state[i + 1][1], state[i + 1][2], op[i][3], max_iter);
     for (size_t c = 1; c + 1 < n; ++c) check_site_step_dims("tdvp", c, state[c][0], state[c][1], state[c][2], op[c][3], max_iter);
@@ -135,55 +104,11 @@ std::vector<TdvpStep> tdvp_plan(size_t n, size_t center, size_t order, double ta
     return steps;
 }
 
-// ------------------------------------------------------------------------------------------------ the small eigenproblem
-void jacobi_eigh(const std::vector<double>& a_in, size_t n, std::vector<double>& evals, std::vector<double>& v)
-{
-    std::vector<double> a(a_in);
-    v.assign(n * n, 0.0);
-    for (size_t i = 0; i < n; ++i) v[i + n * i] = 1.0;
-    double fro = 0.0;
-    for (double x : a) fro = fro + x * x;
-    fro = std::sqrt(fro);
-    const double tiny = 1e-19 * fro;
-    for (int sweep = 0; sweep < 100; ++sweep) {
-        bool rotated = false;
-        for (size_t p = 0; p + 1 < n; ++p) {
-            for (size_t q = p + 1; q < n; ++q) {
-                const double apq = a[p + n * q];
-                if (!(std::fabs(apq) > tiny)) continue;
-                rotated = true;
-                const double theta = (a[q + n * q] - a[p + n * p]) / (2.0 * apq);
-                const double t = (theta >= 0.0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
-                const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
-                a[p + n * p] = a[p + n * p] - t * apq;
-                a[q + n * q] = a[q + n * q] + t * apq;
-                a[p + n * q] = a[q + n * p] = 0.0;
-                for (size_t k = 0; k < n; ++k) {
-                    if (k != p && k != q) {
-                        const double akp = a[k + n * p], akq = a[k + n * q];
-                        a[k + n * p] = a[p + n * k] = c * akp - s * akq;
-                        a[k + n * q] = a[q + n * k] = s * akp + c * akq;
-                    }
-                    const double vkp = v[k + n * p], vkq = v[k + n * q];
-                    v[k + n * p] = c * vkp - s * vkq;
-                    v[k + n * q] = s * vkp + c * vkq;
-                }
-            }
-        }
-        if (!rotated) break;
-    }
-    evals.resize(n);
-    for (size_t i = 0; i < n; ++i) evals[i] = a[i + n * i];
-}
-
 // ------------------------------------------------------------------------------------------------ the Krylov exponential
 void KrylovExpm::reserve(size_t len, size_t max_iter)
 {
-    grow(eng_, basis_, len * (max_iter + 1));
+    ar_.reserve(len, max_iter);
     grow(eng_, start_, len);
-    gs_.reserve(max_iter + 1);
-    grow(eng_, hcol_, max_iter + 2);
-    grow(eng_, coef_, max_iter + 1);
 }
 
 // hermitian_krylov_expm_multiply_once (krylov.rs:790-906)
@@ -192,50 +117,28 @@ KrylovExpmResult KrylovExpm::once(const GmresApply& apply, size_t len, double* d
     KrylovExpmResult res;
     hipStream_t st = eng_.stream();
     const size_t m = o.max_iter;
-    double* V = basis_.get();
-    const double n0 = gs_.norm(d_x, len, V); // v_0 = theta / |theta|
+    const double n0 = ar_.start(d_x, len); // v_0 = theta / |theta|
     if (n0 <= o.breakdown_tol) {
         res.converged = true;
         return res;
     }
     const double threshold = o.tol * std::max(n0, 1.0);
-    std::vector<std::vector<double>> hcols;
-    std::vector<double> a, lams, q, coef, scaled;
+    std::vector<double> lams, q, coef, scaled;
     // out = |theta| sum_i c_i v_i into d_x: the coefficients scaled on the host, one copy
     auto finalise = [&](size_t dim) {
         scaled.resize(dim);
         for (size_t i = 0; i < dim; ++i) scaled[i] = n0 * coef[i];
-        T4A_HIP(hipMemcpyAsync(coef_.get(), scaled.data(), sizeof(double) * dim, hipMemcpyHostToDevice, st));
-        krylov_combine_launch(V, len, (int)dim, coef_.get(), d_x, len, gs_.npart(), st);
+        T4A_HIP(hipMemcpyAsync(ar_.coef(), scaled.data(), sizeof(double) * dim, hipMemcpyHostToDevice, st));
+        krylov_combine_launch(ar_.basis(), len, (int)dim, ar_.coef(), d_x, len, ar_.orth().npart(), st);
         T4A_HIP(hipGetLastError());
         eng_.sync();
         res.iterations = res.apply_calls = dim;
     };
     for (size_t j = 0; j < m; ++j) {
-        double* w = V + len * (j + 1);
-        apply(V + len * j, w);
-        gs_.orth(V, len, (int)(j + 1), w, len, hcol_.get(), nullptr); // w is left normalised: v_{j+1}
-        std::vector<double> hc(j + 2);
-        T4A_HIP(hipMemcpyAsync(hc.data(), hcol_.get(), sizeof(double) * (j + 2), hipMemcpyDeviceToHost, st));
-        eng_.sync();
-        const double beta = hc[j + 1];
-        hcols.push_back(std::move(hc));
-        // projected_matrix_from_columns: the upper-Hessenberg data, rows below the subdiagonal zero
+        const double beta = ar_.step(apply, j, o.hermitian_tol, "hermitian_krylov_expm_multiply");
         const size_t dim = j + 1;
-        a.assign(dim * dim, 0.0);
-        for (size_t col = 0; col < dim; ++col)
-            for (size_t row = 0; row < dim && row < hcols[col].size(); ++row) a[row + dim * col] = hcols[col][row];
-        for (size_t r = 0; r < dim; ++r)
-            for (size_t c = r + 1; c < dim; ++c) {
-                const double x = a[r + dim * c], y = a[c + dim * r];
-                const double scale = std::max(1.0, std::max(std::fabs(x), std::fabs(y)));
-                if (!(std::fabs(x - y) <= o.hermitian_tol * scale))
-                    throw Error(T4A_GPU_INVALID_ARGUMENT, "hermitian_krylov_expm_multiply: projected operator is not Hermitian: entries (" + std::to_string(r) +
-                                                              ", " + std::to_string(c) + ") and its transpose differ by " + std::to_string(std::fabs(x - y)));
-                a[r + dim * c] = a[c + dim * r] = 0.5 * (x + y);
-            }
         // c = Q exp(tau Lambda) Q^T e_1
-        jacobi_eigh(a, dim, lams, q);
+        jacobi_eigh(ar_.projected(), dim, lams, q);
         coef.assign(dim, 0.0);
         for (size_t k = 0; k < dim; ++k) {
             const double f = std::exp(tau * lams[k]) * q[dim * k];
@@ -261,7 +164,7 @@ KrylovExpmResult KrylovExpm::solve(const GmresApply& apply, size_t len, double* 
     if (tau == 0.0) return out;
     hipStream_t st = eng_.stream();
     reserve(len, o.max_iter);
-    if (gs_.norm(d_x, len) <= o.breakdown_tol) return out;
+    if (ar_.orth().norm(d_x, len) <= o.breakdown_tol) return out;
     T4A_HIP(hipMemcpyAsync(start_.get(), d_x, sizeof(double) * len, hipMemcpyDeviceToDevice, st));
     size_t splits = 1;
     for (bool first = true;; first = false) {
@@ -308,11 +211,7 @@ TdvpResult tdvp(Mpo& op, TensorTrain& init, size_t center, const TdvpOptions& o)
     size_t cur = center;
     KrylovExpm kx(e);
     DevBuf<double> theta;
-    SvdOptions so;
-    so.truncate = true;
-    if (o.has_svd_policy) so.policy = o.svd_policy;
-    so.has_max_bond_dim = o.has_max_bond_dim;
-    so.max_bond_dim = o.max_bond_dim;
+    const SvdOptions so = sweep_svd_options(o.has_svd_policy, o.svd_policy, o.has_max_bond_dim, o.max_bond_dim);
 
     auto book = [&](const KrylovExpmResult& r) {
         out.max_error_estimate = std::max(out.max_error_estimate, r.error_estimate);
@@ -347,11 +246,7 @@ TdvpResult tdvp(Mpo& op, TensorTrain& init, size_t center, const TdvpOptions& o)
             if (s.kind == TdvpStepKind::TwoSite) {
                 const size_t i = std::min(s.nodes[0], s.nodes[1]);
                 po.check_step(i, o.krylov.max_iter, "tdvp");
-                const auto ld = po.local_dims(i);
-                const int M = (int)(ld[0] * ld[1]), N = (int)(ld[2] * ld[3]), mid = (int)po.x[i].r;
-                const size_t len = (size_t)M * N;
-                grow(e, theta, len);
-                gemm_launch(gemm_desc(M, N, mid, po.x[i].buf.get(), M, po.x[i + 1].buf.get(), mid, theta.get(), M), st); // theta_0 = x_i x_{i+1}
+                const size_t len = po.two_site_vector(i, theta); // theta_0 = x_i x_{i+1}
                 po.prepare(i);
                 book(kx.solve([&](const double* v, double* y) { po.apply_prepared(v, y); }, len, theta.get(), s.exponent, o.krylov));
                 po.split_and_advance(i, theta.get(), so, s.new_center == i + 1, "tdvp"); // the singular values go to the new centre, no renormalisation
@@ -378,14 +273,9 @@ KrylovExpmResult krylov_expm_dense(const double* H, size_t n, const double* v0, 
 {
     Engine e;
     hipStream_t st = e.stream();
-    DevBuf<double> dH, dx;
-    dH.reserve(n * n);
-    dx.reserve(n);
-    T4A_HIP(hipMemcpyAsync(dH.get(), H, sizeof(double) * n * n, hipMemcpyHostToDevice, st));
-    T4A_HIP(hipMemcpyAsync(dx.get(), v0, sizeof(double) * n, hipMemcpyHostToDevice, st));
+    DevBuf<double> dH = upload_vector(st, H, n * n), dx = upload_vector(st, v0, n);
     KrylovExpm kx(e);
-    const KrylovExpmResult r =
-        kx.solve([&](const double* v, double* y) { gemm_launch(gemm_desc((int)n, 1, (int)n, dH.get(), (int)n, v, (int)n, y, (int)n), st); }, n, dx.get(), tau, o);
+    const KrylovExpmResult r = kx.solve(dense_apply(dH.get(), n, st), n, dx.get(), tau, o);
     T4A_HIP(hipMemcpyAsync(v_out, dx.get(), sizeof(double) * n, hipMemcpyDeviceToHost, st));
     e.sync();
     return r;

@@ -37,13 +37,9 @@ struct KrylovExpmResult {
     bool converged = false;
     size_t time_splits = 1;
 };
-// All eigenpairs of a symmetric n x n matrix (column-major, only read) by cyclic Jacobi on the host: a = evecs diag(evals) evecs^T,
-// evecs column-major with orthonormal columns, in the order the diagonal is left in (not sorted).
-void jacobi_eigh(const std::vector<double>& a, size_t n, std::vector<double>& evals, std::vector<double>& evecs);
-
 class KrylovExpm {
 public:
-    explicit KrylovExpm(Engine& e) : eng_(e), gs_(e) { gs_.set_dots_route(KrylovDotsRoute::Auto); }
+    explicit KrylovExpm(Engine& e) : eng_(e), ar_(e) { ar_.orth().set_dots_route(KrylovDotsRoute::Auto); }
     void reserve(size_t len, size_t max_iter); // the basis: (max_iter + 1) len doubles, and a copy of the start
     // d_x: the start on entry, exp(tau H) start on exit.  tau == 0 or |start| <= breakdown_tol: d_x is left as it is.  The host reads one
     // norm per substep and j + 2 doubles per Krylov step.  INVALID_ARGUMENT: a projected matrix that is not Hermitian; INTERNAL_ERROR:
@@ -53,8 +49,8 @@ public:
 private:
     KrylovExpmResult once(const GmresApply& apply, size_t len, double* d_x, double tau, const KrylovExpmOptions& o);
     Engine& eng_;
-    KrylovOrth gs_;
-    DevBuf<double> basis_, start_, hcol_, coef_;
+    HermitianArnoldi ar_;
+    DevBuf<double> start_;
 };
 
 // ---- the region plan (plan.rs) of a chain rooted at an end
