@@ -858,6 +858,50 @@ t4a_gpu_status t4a_gpu_mpo_contract_fit(const t4a_gpu_mpo* a, const t4a_gpu_mpo*
 t4a_gpu_status t4a_gpu_mpo_fit_half(const double* env, size_t n_env, int32_t side, const t4a_gpu_mpo* a, const t4a_gpu_mpo* b,
                                     size_t site, double* out);
 
+/* Partial contraction of two MPOs: every leg is contracted, identified (diagonal) or kept (tensor4all-treetn/src/treetn/
+ * partial_contraction.rs: partial_contract with PartialContractionSpec { contract_pairs, diagonal_pairs, output_order }), on a chain
+ * and by position.  A pair is four numbers (site_a, leg_a, site_b, leg_b), leg 0 or 1 of the site tensor [left, leg 0, leg 1, right];
+ * every leg is in at most one pair and the two dimensions of a pair are equal.  At a site the legs form three groups, each fused with
+ * its first leg fastest and of dimension 1 when empty: S, the legs of a in no contract pair, in leg order (a diagonal pair keeps a's
+ * leg); K, the contract pairs ordered by a's leg; T, the legs of b in no pair, in leg order.  The result is the MPO
+ *   C_i[(a, b), s, t, (a', b')] = sum_{kappa in K} A_i[a, x(s, kappa), a'] * B_i[b, y(s, kappa, t), b']
+ * with site dims (|S|, |T|) and the bonds fused as t4a_gpu_mpo_contract fuses them; a leg of b that is diagonally paired takes its
+ * value from s.  {contract (i, 1, i, 0) for all i} is the matrix product, {diagonal (i, 0, i, 0), (i, 1, i, 1)} the Hadamard product
+ * of two operators (site dims (s1 * s2, 1)), no pair at all the outer product.  The site product and the half product are HIP
+ * kernels of their own (csrc/kernels_partial.hip); no copy tensor is multiplied into an operand.
+ * INVALID_ARGUMENT (the reference's messages, contract pairs checked before diagonal ones): lengths differ; a site or leg out of range,
+ * "partial_contract: (site i, leg l) from contract_pairs not found in first MPO external indices" (second for b); "partial_contract:
+ * contract_pairs index shape mismatch: 2 != 3"; "partial_contract: first MPO index (site i, leg l) appears in multiple pairs"; |S| * |T|
+ * above 65535.  NOT_IMPLEMENTED: a pair whose legs sit on two sites and output_order (n_output_order != 0) — the reference moves site
+ * indices with swap_site_indices, which this backend does not have.  Trees, mismatched topologies and complex scalars are outside it. */
+/* Host only: validates the spec against the (leg 0, leg 1) tables of both operands (2 x n each) and writes the result's site dims
+ * (2 x n_a: |S|, |T|) and per-leg dims (4 x n_a: the legs of S, two slots, then those of T, two slots; 0 = no such leg).  Either
+ * output may be NULL. */
+t4a_gpu_status t4a_gpu_mpo_partial_plan(const size_t* a_site_dims, size_t n_a, const size_t* b_site_dims, size_t n_b,
+                                        const size_t* contract_pairs, size_t n_contract, const size_t* diagonal_pairs, size_t n_diagonal,
+                                        size_t n_output_order, size_t* out_site_dims, size_t* out_leg_dims);
+/* algorithm: T4A_GPU_MPO_NAIVE (all site products in one launch; compress != 0 adds the compress stage of t4a_gpu_mpo_contract) or
+ * T4A_GPU_MPO_ZIPUP (the recursion of t4a_gpu_mpo_contract, each site step one launch of the half product, no permutation).  method,
+ * tolerance, max_bond_dim and the rank rule are those of t4a_gpu_mpo_contract; T4A_GPU_MPO_FIT and RSVD answer NOT_IMPLEMENTED with
+ * its messages (the fit is t4a_gpu_mpo_partial_contract_fit). */
+t4a_gpu_status t4a_gpu_mpo_partial_contract(const t4a_gpu_mpo* a, const t4a_gpu_mpo* b, const size_t* contract_pairs, size_t n_contract,
+                                            const size_t* diagonal_pairs, size_t n_diagonal, size_t n_output_order, int32_t algorithm,
+                                            int32_t compress, int32_t method, double tolerance, size_t max_bond_dim, t4a_gpu_mpo** out);
+/* t4a_gpu_mpo_contract_fit for a spec: options, initial (site dims (|S|, |T|)), n_sweeps and norms as there. */
+t4a_gpu_status t4a_gpu_mpo_partial_contract_fit(const t4a_gpu_mpo* a, const t4a_gpu_mpo* b, const size_t* contract_pairs, size_t n_contract,
+                                                const size_t* diagonal_pairs, size_t n_diagonal, size_t n_output_order,
+                                                const t4a_gpu_mpo_fit_options* options, const t4a_gpu_mpo* initial /* may be NULL */,
+                                                t4a_gpu_mpo** out, size_t* n_sweeps, double* norms /* max_sweeps + 1 entries, may be NULL */);
+/* Test hook, the counterpart of t4a_gpu_mpo_fit_half for a spec: side 0, env L[n_env, la, lb] -> P[n_env, s, t, ra, rb]; side 1, env
+ * R[ra, rb, n_env] -> Q[la, lb, s, t, n_env], launched as zip-up and the fit launch it. */
+t4a_gpu_status t4a_gpu_mpo_partial_half(const double* env, size_t n_env, int32_t side, const t4a_gpu_mpo* a, const t4a_gpu_mpo* b,
+                                        const size_t* contract_pairs, size_t n_contract, const size_t* diagonal_pairs, size_t n_diagonal,
+                                        size_t site, double* out);
+/* Reads the fused site index s1 + S1 * s2 of every site as another (s1, s2) pair of the same product, in place; the cores stay
+ * (Mpo::relabel_site_dims).  The Hadamard product of two operators comes out with site dims (s1 * s2, 1) and is relabelled to
+ * (s1, s2) with it.  INVALID_ARGUMENT: n_sites is not the length, or a product differs. */
+t4a_gpu_status t4a_gpu_mpo_relabel_site_dims(t4a_gpu_mpo* mpo, const size_t* site_dims /* 2 x n_sites */, size_t n_sites);
+
 /* =====================================================================================
  * Contraction<f64>: the lazy product A·B of two MPOs (opaque handle; both operands resident on the device)
  * tensor4all-simplett/src/mpo/contraction.rs:60-383

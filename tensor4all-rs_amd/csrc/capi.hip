@@ -3809,6 +3809,121 @@ t4a_gpu_status t4a_gpu_mpo_fit_half(const double* env, size_t n_env, int32_t sid
     });
 }
 
+// ---- partial contraction of two MPOs (mpo.hpp: mpo_partial_contract) ----
+namespace {
+PartialSpec partial_spec(const size_t* contract_pairs, size_t n_contract, const size_t* diagonal_pairs, size_t n_diagonal, size_t n_output_order)
+{
+    PartialSpec spec;
+    if (n_contract) T4A_REQUIRE_PTR(contract_pairs);
+    if (n_diagonal) T4A_REQUIRE_PTR(diagonal_pairs);
+    for (size_t i = 0; i < n_contract; ++i)
+        spec.contract_pairs.push_back({contract_pairs[4 * i], contract_pairs[4 * i + 1], contract_pairs[4 * i + 2], contract_pairs[4 * i + 3]});
+    for (size_t i = 0; i < n_diagonal; ++i)
+        spec.diagonal_pairs.push_back({diagonal_pairs[4 * i], diagonal_pairs[4 * i + 1], diagonal_pairs[4 * i + 2], diagonal_pairs[4 * i + 3]});
+    spec.has_output_order = n_output_order != 0;
+    return spec;
+}
+} // namespace
+
+t4a_gpu_status t4a_gpu_mpo_partial_plan(const size_t* a_site_dims, size_t n_a, const size_t* b_site_dims, size_t n_b,
+                                        const size_t* contract_pairs, size_t n_contract, const size_t* diagonal_pairs, size_t n_diagonal,
+                                        size_t n_output_order, size_t* out_site_dims, size_t* out_leg_dims)
+{
+    return guarded([&] {
+        if (n_a) T4A_REQUIRE_PTR(a_site_dims);
+        if (n_b) T4A_REQUIRE_PTR(b_site_dims);
+        std::vector<std::array<size_t, 2>> sa(n_a), sb(n_b);
+        for (size_t i = 0; i < n_a; ++i) sa[i] = {a_site_dims[2 * i], a_site_dims[2 * i + 1]};
+        for (size_t i = 0; i < n_b; ++i) sb[i] = {b_site_dims[2 * i], b_site_dims[2 * i + 1]};
+        const std::vector<PartialSitePlan> plan =
+            mpo_partial_plan(sa, sb, partial_spec(contract_pairs, n_contract, diagonal_pairs, n_diagonal, n_output_order));
+        for (size_t i = 0; i < plan.size(); ++i) {
+            if (out_site_dims) out_site_dims[2 * i] = plan[i].S, out_site_dims[2 * i + 1] = plan[i].T;
+            if (out_leg_dims)
+                for (int k = 0; k < 4; ++k) out_leg_dims[4 * i + k] = plan[i].leg_dims[k];
+        }
+    });
+}
+
+t4a_gpu_status t4a_gpu_mpo_partial_contract(const t4a_gpu_mpo* a, const t4a_gpu_mpo* b, const size_t* contract_pairs, size_t n_contract,
+                                            const size_t* diagonal_pairs, size_t n_diagonal, size_t n_output_order, int32_t algorithm,
+                                            int32_t compress, int32_t method, double tolerance, size_t max_bond_dim, t4a_gpu_mpo** out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(a);
+        T4A_REQUIRE_PTR(b);
+        T4A_REQUIRE_PTR(out);
+        *out = nullptr;
+        if (algorithm < 0 || algorithm > 2) throw Error(T4A_GPU_INVALID_ARGUMENT, "unknown contraction algorithm");
+        if (method < 0 || method > 3) throw Error(T4A_GPU_INVALID_ARGUMENT, "unknown factorize method");
+        MpoContractionOptions o;
+        o.tolerance = tolerance;
+        o.max_bond_dim = max_bond_dim;
+        o.method = (MpoFactorizeMethod)method;
+        const PartialSpec spec = partial_spec(contract_pairs, n_contract, diagonal_pairs, n_diagonal, n_output_order);
+        *out = new t4a_gpu_mpo{mpo_partial_contract(*a->impl, *b->impl, spec, (MpoAlgorithm)algorithm, compress != 0, o)};
+    });
+}
+
+t4a_gpu_status t4a_gpu_mpo_partial_contract_fit(const t4a_gpu_mpo* a, const t4a_gpu_mpo* b, const size_t* contract_pairs, size_t n_contract,
+                                                const size_t* diagonal_pairs, size_t n_diagonal, size_t n_output_order,
+                                                const t4a_gpu_mpo_fit_options* options, const t4a_gpu_mpo* initial, t4a_gpu_mpo** out,
+                                                size_t* n_sweeps, double* norms)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(out);
+        *out = nullptr;
+        if (n_sweeps) *n_sweeps = 0;
+        T4A_REQUIRE_PTR(options);
+        // the options are checked on the host before an operand is looked at, as in t4a_gpu_mpo_contract_fit
+        if (options->factorize_method < 0 || options->factorize_method > 3) throw Error(T4A_GPU_INVALID_ARGUMENT, "unknown factorize method");
+        MpoFitOptions o;
+        o.tolerance = options->tolerance;
+        o.max_bond_dim = options->has_max_bond_dim ? options->max_bond_dim : 0;
+        if (options->has_max_bond_dim && options->max_bond_dim == 0)
+            throw Error(T4A_GPU_INVALID_ARGUMENT, "contract_fit: max_bond_dim must be at least 1");
+        o.max_sweeps = options->max_sweeps;
+        o.convergence_tol = options->convergence_tol;
+        o.method = (MpoFactorizeMethod)options->factorize_method;
+        mpo_fit_validate_options(o);
+        T4A_REQUIRE_PTR(a);
+        T4A_REQUIRE_PTR(b);
+        const PartialSpec spec = partial_spec(contract_pairs, n_contract, diagonal_pairs, n_diagonal, n_output_order);
+        MpoFitInfo info;
+        *out = new t4a_gpu_mpo{mpo_partial_contract_fit(*a->impl, *b->impl, spec, o, initial ? initial->impl.get() : nullptr, info)};
+        if (n_sweeps) *n_sweeps = info.n_sweeps;
+        if (norms) std::copy(info.norms.begin(), info.norms.end(), norms);
+    });
+}
+
+t4a_gpu_status t4a_gpu_mpo_partial_half(const double* env, size_t n_env, int32_t side, const t4a_gpu_mpo* a, const t4a_gpu_mpo* b,
+                                        const size_t* contract_pairs, size_t n_contract, const size_t* diagonal_pairs, size_t n_diagonal,
+                                        size_t site, double* out)
+{
+    return guarded([&] {
+        if (side != 0 && side != 1) throw Error(T4A_GPU_INVALID_ARGUMENT, "partial_half: side must be 0 (left) or 1 (right)");
+        if (n_env == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "partial_half: the environment has a zero dimension");
+        T4A_REQUIRE_PTR(env);
+        T4A_REQUIRE_PTR(a);
+        T4A_REQUIRE_PTR(b);
+        T4A_REQUIRE_PTR(out);
+        const PartialSpec spec = partial_spec(contract_pairs, n_contract, diagonal_pairs, n_diagonal, 0);
+        std::vector<double> v = mpo_partial_half(env, n_env, side == 1, *a->impl, *b->impl, spec, site);
+        std::memcpy(out, v.data(), v.size() * sizeof(double));
+    });
+}
+
+t4a_gpu_status t4a_gpu_mpo_relabel_site_dims(t4a_gpu_mpo* mpo, const size_t* site_dims, size_t n_sites)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(mpo);
+        if (n_sites) T4A_REQUIRE_PTR(site_dims);
+        std::vector<std::array<size_t, 2>> sd(n_sites);
+        for (size_t i = 0; i < n_sites; ++i) sd[i] = {site_dims[2 * i], site_dims[2 * i + 1]};
+        mpo->impl->relabel_site_dims(sd);
+    });
+}
+
 // ---- Contraction<f64>: the lazy product of two MPOs (tensor4all-simplett/src/mpo/contraction.rs:60-383) ----
 t4a_gpu_status t4a_gpu_contraction_new(const t4a_gpu_mpo* a, const t4a_gpu_mpo* b, t4a_gpu_contraction** out)
 {

@@ -642,6 +642,42 @@ struct MpoFitHalfDesc {
 bool mpo_fit_half_launch(const MpoFitHalfDesc& d, hipStream_t stream);
 
 // ------------------------------------------------------------------------------------------------
+// kernels_partial.hip — the local products of the partial contraction of two MPOs (mpo.hpp: PartialSitePlan).  s, kappa and t are the
+// fused groups of a site (kept legs of A, contract pairs, free legs of B), each of at most two legs with the first fastest;
+// s0 / k0 / t0 is the dimension of the first leg of the group (the dimension of the group when it has fewer than two).
+// Site product, all sites in one launch (job list as MpoSiteJob; strides in units of the fused site index x0 + X0 x1 of an operand):
+//   C[(a lb + b) + la lb (s + S (t + T (a' rb + b')))] = sum_kappa A[a + la (fA + FA a')] * B[b + lb (fB + FB b')],  kappa ascending,
+//   fA = (s % s0) as0 + (s / s0) as1 + (kappa % k0) ak0 + (kappa / k0) ak1,
+//   fB = (s % s0) bs0 + (s / s0) bs1 + (kappa % k0) bk0 + (kappa / k0) bk1 + (t % t0) bt0 + (t / t0) bt1.
+// Half product: MpoFitHalfDesc with the strides of s, kappa and t split per leg and strides of B along s (all in elements);
+// returns false, having launched nothing, when the grid would hold more than INT_MAX workgroups.
+// ------------------------------------------------------------------------------------------------
+struct MpoPartialSiteJob {
+    const double* A; // [la, FA, ra]
+    const double* B; // [lb, FB, rb]
+    double* C;       // [la*lb, S, T, ra*rb]
+    unsigned long long off;
+    int la, FA, ra, lb, FB, rb;
+    int S, K, T, s0, k0, t0;
+    int as0, as1, ak0, ak1;
+    int bs0, bs1, bk0, bk1, bt0, bt1;
+};
+void mpo_partial_site_launch(const MpoPartialSiteJob* d_jobs, int n_jobs, unsigned long long total, hipStream_t stream);
+struct MpoPartialHalfDesc {
+    const double* E;
+    const double* A;
+    const double* B;
+    double* out;
+    int N, La, Lb, S, K, T, C, D;
+    int s0, k0, t0;
+    long long en, ea, eb;
+    long long aa, ac, as0, as1, ak0, ak1;
+    long long bb, bd, bs0, bs1, bk0, bk1, bt0, bt1;
+    long long on, os, ot, oc, od;
+};
+bool mpo_partial_half_launch(const MpoPartialHalfDesc& d, hipStream_t stream);
+
+// ------------------------------------------------------------------------------------------------
 // kernels_contraction.hip — environments of the lazy product A·B of two MPOs (simplett/src/mpo/contraction.rs:262-383) for a batch
 // of unique index halves, one workgroup per half.  An environment is a matrix over the bond pair, column-major [a + dim_a * b];
 // item `it` of a launch is written to d_out + it * ld.  idx holds the (i, j) pairs of the walked sites per item, item-major.

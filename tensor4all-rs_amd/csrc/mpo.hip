@@ -1,7 +1,8 @@
 // mpo.hip — MPO<f64> and the contraction of two MPOs on the device (see mpo.hpp).  Shape bookkeeping is host work; every
 // floating-point operation runs in gfx950 kernels: the naive site contraction (kernels_mpo.hip), the f64-MFMA GEMM and the
 // gathers (kernels_dense.hip), the axis permutation (kernels_tt.hip), the Householder QR and the Jacobi SVD (kernels_linalg.hip),
-// the half products of the variational fit (kernels_mpo_fit.hip).  Sites are made, copied, right-canonicalised (QrSweep) and split
+// the half products of the variational fit (kernels_mpo_fit.hip), the site and half products of the partial contraction
+// (kernels_partial.hip; the host plan mpo_partial_plan is at the end of this file).  Sites are made, copied, right-canonicalised (QrSweep) and split
 // after the two-site SVD (split_two_site) with the chain helpers of tt_chain.hpp.
 #include "mpo.hpp"
 #include "tensorops.hpp"
@@ -37,7 +38,13 @@ struct Contractor {
     std::vector<double> hs;
     QrSweep sweeper; // right_canonicalize (canonical.rs:35-89) is sweeper.canonicalize(cores, 0)
 
+    // the site plans of a partial contraction (mpo_partial_contract*); null: the matrix product, on the code path it always had
+    const std::vector<PartialSitePlan>* plan = nullptr;
+
     Contractor(Engine& e, const MpoContractionOptions& o) : eng(e), opt(o), st(e.stream()), sweeper(e) {}
+
+    // the fused site dimension s * t of the product at site i
+    size_t st_dim(const Mpo& a, const Mpo& b, size_t i) const { return plan ? (*plan)[i].S * (*plan)[i].T : a.sd[i][0] * b.sd[i][1]; }
 
     // factorize (factorize.rs:126-313) with left_orthogonal = true, SVD rank rule: cutoff = tolerance * s_max, values kept
     // while rank < max_bond_dim and s >= cutoff; a zero matrix keeps nothing and is floored to rank 1 (not an error).  LU and
@@ -104,6 +111,43 @@ struct Contractor {
         d_jobs.reserve(n);
         T4A_HIP(hipMemcpyAsync(d_jobs.get(), jobs.data(), n * sizeof(MpoSiteJob), hipMemcpyHostToDevice, st));
         mpo_site_contract_launch(d_jobs.get(), (int)n, off, st);
+        T4A_HIP(hipGetLastError());
+        eng.sync(); // `jobs` is pageable host memory, d_jobs goes out of scope
+        return out;
+    }
+
+    // the site product of a plan for every site in one launch (kernels_partial.hip)
+    std::vector<DevCore> naive_partial(const Mpo& a, const Mpo& b)
+    {
+        const size_t n = a.len();
+        std::vector<DevCore> out(n);
+        std::vector<MpoPartialSiteJob> jobs(n);
+        unsigned long long off = 0;
+        for (size_t i = 0; i < n; ++i) {
+            const DevCore& x = a.tt.cores[i];
+            const DevCore& y = b.tt.cores[i];
+            const PartialSitePlan& p = (*plan)[i];
+            check_count(x.l * y.l, p.S, p.T, x.r * y.r, "partial_contract: site " + std::to_string(i));
+            out[i] = DevCore::make(x.l * y.l, p.S * p.T, x.r * y.r);
+            MpoPartialSiteJob& j = jobs[i];
+            j = MpoPartialSiteJob{};
+            j.A = x.buf.get();
+            j.B = y.buf.get();
+            j.C = out[i].buf.get();
+            j.off = off;
+            j.la = (int)x.l, j.FA = (int)x.s, j.ra = (int)x.r;
+            j.lb = (int)y.l, j.FB = (int)y.s, j.rb = (int)y.r;
+            j.S = (int)p.S, j.K = (int)p.K, j.T = (int)p.T;
+            j.s0 = (int)p.s0, j.k0 = (int)p.k0, j.t0 = (int)p.t0;
+            j.as0 = (int)p.as[0], j.as1 = (int)p.as[1], j.ak0 = (int)p.ak[0], j.ak1 = (int)p.ak[1];
+            j.bs0 = (int)p.bs[0], j.bs1 = (int)p.bs[1], j.bk0 = (int)p.bk[0], j.bk1 = (int)p.bk[1];
+            j.bt0 = (int)p.bt[0], j.bt1 = (int)p.bt[1];
+            off += out[i].size();
+        }
+        DevBuf<MpoPartialSiteJob> d_jobs;
+        d_jobs.reserve(n);
+        T4A_HIP(hipMemcpyAsync(d_jobs.get(), jobs.data(), n * sizeof(MpoPartialSiteJob), hipMemcpyHostToDevice, st));
+        mpo_partial_site_launch(d_jobs.get(), (int)n, off, st);
         T4A_HIP(hipGetLastError());
         eng.sync(); // `jobs` is pageable host memory, d_jobs goes out of scope
         return out;
@@ -202,6 +246,43 @@ struct Contractor {
         return out;
     }
 
+    // zipup for a plan: the site step C[n, s, t, c, d] = R A_i B_i is ONE launch of the half product with E = the remainder, and its
+    // output is the (n s t) x (c d) matrix svd_rank reads: no permutation of a site or of the intermediate.  left() / right() and the
+    // last-site rule are those of zipup.
+    std::vector<DevCore> zipup_partial(const Mpo& a, const Mpo& b)
+    {
+        const size_t n = a.len();
+        std::vector<DevCore> out;
+        DevBuf<double> rem, rem_next;
+        rem.reserve(1);
+        fill_launch(rem.get(), 1, 1.0, st); // R[new, a, b] = [[[1]]]
+        size_t N0 = 1;
+        for (size_t i = 0; i < n; ++i) {
+            const size_t Ra = a.tt.cores[i].r, Rb = b.tt.cores[i].r, ST = st_dim(a, b, i);
+            if (i == n - 1) { // last site: the trailing bonds are 1, the half product is C = [n, s t, 1]
+                DevCore site = DevCore::make(N0, ST, 1);
+                half_into(a, b, i, false, rem.get(), N0, site.buf.get(), "partial_contract (zipup): site ");
+                T4A_HIP(hipGetLastError());
+                eng.sync();
+                out.push_back(std::move(site));
+                break;
+            }
+            half(a, b, i, false, rem.get(), N0, cm, "partial_contract (zipup): site ");
+            const int M = (int)(N0 * ST), N = (int)(Ra * Rb);
+            const size_t rank = svd_rank(cm.get(), M, N);
+            DevCore site = DevCore::make(N0, ST, rank);
+            left(M, (int)rank, site.buf.get());
+            rem_next.reserve(rank * N);
+            right(M, N, (int)rank, rem_next.get());
+            T4A_HIP(hipGetLastError());
+            eng.sync();
+            std::swap(rem, rem_next);
+            N0 = rank;
+            out.push_back(std::move(site));
+        }
+        return out;
+    }
+
     // ---- variational fit (mpo.hpp: mpo_contract_fit).  C_i[c_i, s, t, c_{i+1}] is the fitted MPO,
     //   L_i[c_i, la_i, lb_i] the contraction of the sites < i of A, B and C,  R_i[la_i, lb_i, c_i] that of the sites >= i,
     //   P_i[c_i, s, t, la', lb'] = L_i A_i B_i   and   Q_i[la, lb, s, t, c_{i+1}] = A_i B_i R_{i+1}   the half products,
@@ -242,13 +323,69 @@ struct Contractor {
         return d;
     }
 
-    // one half product of site i into `out`: P_i from L_i (n_env = c_i) or Q_i from R_{i+1} (n_env = c_{i+1})
-    void half(const Mpo& a, const Mpo& b, size_t i, bool right, const double* env, size_t n_env, DevBuf<double>& out)
+    // half_desc for a site plan: the strides of s, kappa and t per leg, and those of B along s (a diagonal pair)
+    static MpoPartialHalfDesc partial_half_desc(bool right, const double* env, size_t n_env, const DevCore& A, const DevCore& B,
+                                                const PartialSitePlan& p, double* out)
+    {
+        MpoPartialHalfDesc d{};
+        const size_t la = A.l, ra = A.r, lb = B.l, rb = B.r, s = p.S, t = p.T;
+        d.E = env;
+        d.A = A.buf.get();
+        d.B = B.buf.get();
+        d.out = out;
+        d.N = (int)n_env;
+        d.S = (int)s, d.K = (int)p.K, d.T = (int)t;
+        d.s0 = (int)p.s0, d.k0 = (int)p.k0, d.t0 = (int)p.t0;
+        // A[la, fA, ra], B[lb, fB, rb]
+        d.as0 = (long long)(la * p.as[0]), d.as1 = (long long)(la * p.as[1]);
+        d.ak0 = (long long)(la * p.ak[0]), d.ak1 = (long long)(la * p.ak[1]);
+        d.bs0 = (long long)(lb * p.bs[0]), d.bs1 = (long long)(lb * p.bs[1]);
+        d.bk0 = (long long)(lb * p.bk[0]), d.bk1 = (long long)(lb * p.bk[1]);
+        d.bt0 = (long long)(lb * p.bt[0]), d.bt1 = (long long)(lb * p.bt[1]);
+        const long long a_l = 1, a_r = (long long)(la * A.s), b_l = 1, b_r = (long long)(lb * B.s);
+        if (!right) { // P: E = L[n, la, lb], out[n, s, t, ra, rb]
+            d.La = (int)la, d.Lb = (int)lb, d.C = (int)ra, d.D = (int)rb;
+            d.en = 1, d.ea = (long long)n_env, d.eb = (long long)(n_env * la);
+            d.aa = a_l, d.ac = a_r, d.bb = b_l, d.bd = b_r;
+            d.on = 1, d.os = (long long)n_env, d.ot = (long long)(n_env * s), d.oc = (long long)(n_env * s * t),
+            d.od = (long long)(n_env * s * t * ra);
+        } else { // Q: E = R[ra, rb, n], out[la, lb, s, t, n]
+            d.La = (int)ra, d.Lb = (int)rb, d.C = (int)la, d.D = (int)lb;
+            d.ea = 1, d.eb = (long long)ra, d.en = (long long)(ra * rb);
+            d.aa = a_r, d.ac = a_l, d.bb = b_r, d.bd = b_l;
+            d.oc = 1, d.od = (long long)la, d.os = (long long)(la * lb), d.ot = (long long)(la * lb * s), d.on = (long long)(la * lb * s * t);
+        }
+        return d;
+    }
+
+    // the half product of site i of a plan into device memory that holds it
+    void half_into(const Mpo& a, const Mpo& b, size_t i, bool right, const double* env, size_t n_env, double* out, const char* what)
     {
         const DevCore& A = a.tt.cores[i];
         const DevCore& B = b.tt.cores[i];
+        const PartialSitePlan& p = (*plan)[i];
+        const std::string where = what + std::to_string(i);
+        check_count(n_env * p.S, p.T, right ? A.l : A.r, right ? B.l : B.r, where);
+        check_count(n_env, A.l, B.l, 1, where);
+        check_count(n_env, A.r, B.r, 1, where);
+        if (!mpo_partial_half_launch(partial_half_desc(right, env, n_env, A, B, p, out), st))
+            throw Error(T4A_GPU_INVALID_ARGUMENT, where + " needs more than INT_MAX workgroups");
+    }
+
+    // one half product of site i into `out`: P_i from L_i (n_env = c_i) or Q_i from R_{i+1} (n_env = c_{i+1})
+    void half(const Mpo& a, const Mpo& b, size_t i, bool right, const double* env, size_t n_env, DevBuf<double>& out,
+              const char* what = "contract_fit: site ")
+    {
+        const DevCore& A = a.tt.cores[i];
+        const DevCore& B = b.tt.cores[i];
+        if (plan) {
+            check_count(n_env * (*plan)[i].S, (*plan)[i].T, right ? A.l : A.r, right ? B.l : B.r, what + std::to_string(i));
+            out.reserve(n_env * st_dim(a, b, i) * (right ? A.l * B.l : A.r * B.r));
+            half_into(a, b, i, right, env, n_env, out.get(), what);
+            return;
+        }
         const size_t S1 = a.sd[i][0], K = a.sd[i][1], T = b.sd[i][1];
-        const std::string where = "contract_fit: site " + std::to_string(i);
+        const std::string where = what + std::to_string(i);
         check_count(n_env * S1, T, right ? A.l : A.r, right ? B.l : B.r, where);
         check_count(n_env, A.l, B.l, 1, where);
         check_count(n_env, A.r, B.r, 1, where);
@@ -260,7 +397,7 @@ struct Contractor {
     // R_i = Q_i C_i^T over (s, t, c_{i+1}), with C_i given as the c_i x (s t c_{i+1}) matrix `rows` of leading dimension ld
     void right_env(const Mpo& a, const Mpo& b, size_t i, size_t ci, size_t cnext, const double* rows, int ld)
     {
-        const size_t ab = a.tt.cores[i].l * b.tt.cores[i].l, rest = a.sd[i][0] * b.sd[i][1] * cnext;
+        const size_t ab = a.tt.cores[i].l * b.tt.cores[i].l, rest = st_dim(a, b, i) * cnext;
         envR[i].reserve(ab * ci);
         GemmDesc g = gemm_desc((int)ab, (int)ci, (int)rest, hq.get(), (int)ab, rows, ld, envR[i].get(), (int)ab);
         g.transB = 1;
@@ -484,13 +621,13 @@ void mpo_fit_validate_options(const MpoFitOptions& opt)
         throw Error(T4A_GPU_INVALID_ARGUMENT, "contract_fit: convergence_tol must be finite and not negative");
 }
 
-std::unique_ptr<Mpo> mpo_contract_fit(Mpo& a, Mpo& b, const MpoFitOptions& opt, Mpo* initial, MpoFitInfo& info)
+namespace {
+// what mpo_contract_fit and mpo_partial_contract_fit share behind their shape checks: `sd` are the site dims of the product, `plan` the
+// site plans of a partial contraction or null for the matrix product
+std::unique_ptr<Mpo> fit_driver(Mpo& a, Mpo& b, const std::vector<PartialSitePlan>* plan, const std::vector<std::array<size_t, 2>>& sd,
+                                const MpoFitOptions& opt, Mpo* initial, MpoFitInfo& info)
 {
-    info = MpoFitInfo{};
-    check_operands(a, b);
     const size_t n = a.len();
-    std::vector<std::array<size_t, 2>> sd(n);
-    for (size_t i = 0; i < n; ++i) sd[i] = {a.sd[i][0], b.sd[i][1]};
     if (initial) {
         if (initial->len() != n)
             throw Error(T4A_GPU_INVALID_ARGUMENT,
@@ -510,19 +647,30 @@ std::unique_ptr<Mpo> mpo_contract_fit(Mpo& a, Mpo& b, const MpoFitOptions& opt, 
     co.max_bond_dim = opt.max_bond_dim;
     co.method = opt.method;
     Contractor c(a.tt.eng, co);
+    c.plan = plan;
     std::vector<DevCore> cores;
     if (n == 1) { // the exact one-site product, nothing to sweep
-        cores = c.naive(a, b);
+        cores = plan ? c.naive_partial(a, b) : c.naive(a, b);
     } else {
         if (initial) {
             cores = clone_cores(initial->tt.cores, c.st);
         } else {
-            cores = c.zipup(a, b); // the initialiser of treetn::contract_fit, same tolerance, cap and method
+            cores = plan ? c.zipup_partial(a, b) : c.zipup(a, b); // the initialiser of treetn::contract_fit, same tolerance, cap and method
         }
         if (opt.max_sweeps > 0) c.fit(a, b, cores, opt.max_sweeps, opt.convergence_tol, info);
     }
     a.tt.eng.sync();
     return std::make_unique<Mpo>(std::move(cores), sd);
+}
+} // namespace
+
+std::unique_ptr<Mpo> mpo_contract_fit(Mpo& a, Mpo& b, const MpoFitOptions& opt, Mpo* initial, MpoFitInfo& info)
+{
+    info = MpoFitInfo{};
+    check_operands(a, b);
+    std::vector<std::array<size_t, 2>> sd(a.len());
+    for (size_t i = 0; i < a.len(); ++i) sd[i] = {a.sd[i][0], b.sd[i][1]};
+    return fit_driver(a, b, nullptr, sd, opt, initial, info);
 }
 
 std::vector<double> mpo_fit_half(const double* env, size_t n_env, bool right, Mpo& a, Mpo& b, size_t site)
@@ -543,6 +691,159 @@ std::vector<double> mpo_fit_half(const double* env, size_t n_env, bool right, Mp
     d_env.reserve(ne);
     T4A_HIP(hipMemcpyAsync(d_env.get(), env, sizeof(double) * ne, hipMemcpyHostToDevice, c.st));
     c.half(a, b, site, right, d_env.get(), n_env, d_out);
+    T4A_HIP(hipGetLastError());
+    return to_host(a.tt.eng, d_out.get(), no);
+}
+
+// ---- partial contraction (mpo.hpp) ----
+std::vector<PartialSitePlan> mpo_partial_plan(const std::vector<std::array<size_t, 2>>& a_sd, const std::vector<std::array<size_t, 2>>& b_sd,
+                                              const PartialSpec& spec)
+{
+    if (a_sd.size() != b_sd.size())
+        throw Error(T4A_GPU_INVALID_ARGUMENT, "MPO length mismatch: expected " + std::to_string(a_sd.size()) + ", got " + std::to_string(b_sd.size()));
+    const size_t n = a_sd.size();
+    enum Role : int { Free = 0, Contract = 1, Diagonal = 2 };
+    struct Leg {
+        Role role = Free;
+        size_t partner = 0; // the leg of the other operand at the same site
+    };
+    std::vector<std::array<Leg, 2>> ra(n), rb(n);
+    std::vector<std::array<bool, 2>> seen_a(n, {false, false}), seen_b(n, {false, false});
+    auto name = [](size_t site, size_t leg) { return "(site " + std::to_string(site) + ", leg " + std::to_string(leg) + ")"; };
+    const PartialPair* cross = nullptr;
+    for (int kind = 0; kind < 2; ++kind) {
+        const std::string kname = kind == 0 ? "contract_pairs" : "diagonal_pairs";
+        for (const PartialPair& p : kind == 0 ? spec.contract_pairs : spec.diagonal_pairs) {
+            if (p.site_a >= n || p.leg_a > 1)
+                throw Error(T4A_GPU_INVALID_ARGUMENT,
+                            "partial_contract: " + name(p.site_a, p.leg_a) + " from " + kname + " not found in first MPO external indices");
+            if (p.site_b >= n || p.leg_b > 1)
+                throw Error(T4A_GPU_INVALID_ARGUMENT,
+                            "partial_contract: " + name(p.site_b, p.leg_b) + " from " + kname + " not found in second MPO external indices");
+            const size_t da = a_sd[p.site_a][p.leg_a], db = b_sd[p.site_b][p.leg_b];
+            if (da != db)
+                throw Error(T4A_GPU_INVALID_ARGUMENT,
+                            "partial_contract: " + kname + " index shape mismatch: " + std::to_string(da) + " != " + std::to_string(db));
+            if (seen_a[p.site_a][p.leg_a])
+                throw Error(T4A_GPU_INVALID_ARGUMENT, "partial_contract: first MPO index " + name(p.site_a, p.leg_a) + " appears in multiple pairs");
+            if (seen_b[p.site_b][p.leg_b])
+                throw Error(T4A_GPU_INVALID_ARGUMENT, "partial_contract: second MPO index " + name(p.site_b, p.leg_b) + " appears in multiple pairs");
+            seen_a[p.site_a][p.leg_a] = seen_b[p.site_b][p.leg_b] = true;
+            if (p.site_a != p.site_b) {
+                if (!cross) cross = &p;
+                continue;
+            }
+            ra[p.site_a][p.leg_a] = Leg{kind == 0 ? Contract : Diagonal, p.leg_b};
+            rb[p.site_b][p.leg_b] = Leg{kind == 0 ? Contract : Diagonal, p.leg_a};
+        }
+    }
+    if (cross)
+        throw Error(T4A_GPU_NOT_IMPLEMENTED, "partial_contract: the pair " + name(cross->site_a, cross->leg_a) + " - " +
+                                                 name(cross->site_b, cross->leg_b) +
+                                                 " joins two sites; moving a site index (swap_site_indices) is not implemented");
+    if (spec.has_output_order)
+        throw Error(T4A_GPU_NOT_IMPLEMENTED, "partial_contract: output_order is not implemented (it needs swap_site_indices)");
+    std::vector<PartialSitePlan> plan(n);
+    for (size_t i = 0; i < n; ++i) {
+        PartialSitePlan& p = plan[i];
+        const size_t stride_a[2] = {1, a_sd[i][0]}, stride_b[2] = {1, b_sd[i][0]};
+        size_t ns = 0, nk = 0, nt = 0;
+        for (size_t leg = 0; leg < 2; ++leg) {
+            const Leg& l = ra[i][leg];
+            const size_t dim = a_sd[i][leg];
+            if (l.role == Contract) {
+                p.ak[nk] = stride_a[leg];
+                p.bk[nk] = stride_b[l.partner];
+                if (nk == 0) p.k0 = dim;
+                p.K *= dim;
+                ++nk;
+            } else {
+                p.as[ns] = stride_a[leg];
+                p.bs[ns] = l.role == Diagonal ? stride_b[l.partner] : 0;
+                if (ns == 0) p.s0 = dim;
+                p.S *= dim;
+                p.leg_dims[ns] = dim;
+                ++ns;
+            }
+        }
+        for (size_t leg = 0; leg < 2; ++leg) {
+            if (rb[i][leg].role != Free) continue;
+            const size_t dim = b_sd[i][leg];
+            p.bt[nt] = stride_b[leg];
+            if (nt == 0) p.t0 = dim;
+            p.T *= dim;
+            p.leg_dims[2 + nt] = dim;
+            ++nt;
+        }
+        if (p.S == 0 || p.T == 0 || p.K == 0)
+            throw Error(T4A_GPU_INVALID_ARGUMENT, "partial_contract: site " + std::to_string(i) + " has a zero dimension");
+        check_count(p.S, p.T, 1, 1, "partial_contract: site " + std::to_string(i));
+        if (p.S * p.T > MPO_DIM_MAX)
+            throw Error(T4A_GPU_INVALID_ARGUMENT, "partial_contract: site " + std::to_string(i) + ": dimensions above 65535 are not supported");
+    }
+    return plan;
+}
+
+namespace {
+std::vector<PartialSitePlan> plan_of(const Mpo& a, const Mpo& b, const PartialSpec& spec) { return mpo_partial_plan(a.sd, b.sd, spec); }
+std::vector<std::array<size_t, 2>> plan_site_dims(const std::vector<PartialSitePlan>& plan)
+{
+    std::vector<std::array<size_t, 2>> sd(plan.size());
+    for (size_t i = 0; i < plan.size(); ++i) sd[i] = {plan[i].S, plan[i].T};
+    return sd;
+}
+} // namespace
+
+std::unique_ptr<Mpo> mpo_partial_contract(Mpo& a, Mpo& b, const PartialSpec& spec, MpoAlgorithm alg, bool compress,
+                                          const MpoContractionOptions& opt)
+{
+    const std::vector<PartialSitePlan> plan = plan_of(a, b, spec);
+    const size_t n = a.len();
+    if (alg == MpoAlgorithm::Fit) // as mpo_contract
+        throw Error(T4A_GPU_NOT_IMPLEMENTED, "Unsupported operation: simplett variational MPO fitting is not implemented; use contract_naive or "
+                                             "contract_zipup instead");
+    const std::vector<std::array<size_t, 2>> sd = plan_site_dims(plan);
+    if (n == 0) return std::make_unique<Mpo>(std::vector<DevCore>{}, sd);
+    b.tt.eng.sync(); // b's cores are read on a's stream
+    Contractor c(a.tt.eng, opt);
+    c.plan = &plan;
+    std::vector<DevCore> cores;
+    if (alg == MpoAlgorithm::ZipUp) {
+        cores = c.zipup_partial(a, b);
+    } else {
+        cores = c.naive_partial(a, b);
+        if (compress) c.compress(cores);
+    }
+    a.tt.eng.sync();
+    return std::make_unique<Mpo>(std::move(cores), sd);
+}
+
+std::unique_ptr<Mpo> mpo_partial_contract_fit(Mpo& a, Mpo& b, const PartialSpec& spec, const MpoFitOptions& opt, Mpo* initial, MpoFitInfo& info)
+{
+    info = MpoFitInfo{};
+    const std::vector<PartialSitePlan> plan = plan_of(a, b, spec);
+    return fit_driver(a, b, &plan, plan_site_dims(plan), opt, initial, info);
+}
+
+std::vector<double> mpo_partial_half(const double* env, size_t n_env, bool right, Mpo& a, Mpo& b, const PartialSpec& spec, size_t site)
+{
+    const std::vector<PartialSitePlan> plan = plan_of(a, b, spec);
+    if (site >= a.len()) throw Error(T4A_GPU_INVALID_ARGUMENT, "partial_half: site " + std::to_string(site) + " is out of range");
+    if (n_env == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "partial_half: the environment has a zero dimension");
+    const DevCore& A = a.tt.cores[site];
+    const DevCore& B = b.tt.cores[site];
+    const size_t ea = right ? A.r : A.l, eb = right ? B.r : B.l, oa = right ? A.l : A.r, ob = right ? B.l : B.r;
+    check_count(n_env, ea, eb, 1, "partial_half: the environment");
+    check_count(n_env * plan[site].S, plan[site].T, oa, ob, "partial_half: the half product");
+    b.tt.eng.sync();
+    MpoContractionOptions co;
+    Contractor c(a.tt.eng, co);
+    c.plan = &plan;
+    DevBuf<double> d_env, d_out;
+    const size_t ne = n_env * ea * eb, no = n_env * plan[site].S * plan[site].T * oa * ob;
+    d_env.reserve(ne);
+    T4A_HIP(hipMemcpyAsync(d_env.get(), env, sizeof(double) * ne, hipMemcpyHostToDevice, c.st));
+    c.half(a, b, site, right, d_env.get(), n_env, d_out, "partial_half: site ");
     T4A_HIP(hipGetLastError());
     return to_host(a.tt.eng, d_out.get(), no);
 }

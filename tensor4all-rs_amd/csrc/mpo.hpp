@@ -82,4 +82,44 @@ std::unique_ptr<Mpo> mpo_contract_fit(Mpo& a, Mpo& b, const MpoFitOptions& opt, 
 // P[n_env, s1, s2, ra, rb]; right == true: env is R[ra, rb, n_env] and the result Q[la, lb, s1, s2, n_env] (all column-major, host).
 std::vector<double> mpo_fit_half(const double* env, size_t n_env, bool right, Mpo& a, Mpo& b, size_t site);
 
+// ---- partial contraction of two MPOs: per leg contract, diagonal or keep (tensor4all-treetn/src/treetn/partial_contraction.rs,
+// partial_contract with PartialContractionSpec, on a chain and by position).  A leg is (site, leg) with leg 0 or 1 of the site tensor
+// [left, leg 0, leg 1, right].  A contract pair sums the two legs away; a diagonal pair identifies them and keeps A's ("the left-hand
+// site index remains").  At a site the legs fall into three groups, each fused with its first leg fastest, an empty one of dimension 1:
+//   S: the legs of A in no contract pair, in leg order;  K: the contract pairs, ordered by A's leg;  T: the legs of B in no pair,
+//   C_i[(a, b), s, t, (a', b')] = sum_{kappa in K} A_i[a, x(s, kappa), a'] * B_i[b, y(s, kappa, t), b']
+// with the bonds fused as the naive product fuses them; the result is an MPO with site dims (|S|, |T|).  The matrix product is
+// {contract (i, 1)-(i, 0) for all i}, the Hadamard product of operators {diagonal (i, 0)-(i, 0), diagonal (i, 1)-(i, 1)}.
+// Pairs across two sites and output_order are NOT_IMPLEMENTED (the reference moves indices with swap_site_indices, which this
+// project does not have); trees, mismatched topologies and complex scalars are outside this backend.
+struct PartialPair {
+    size_t site_a, leg_a, site_b, leg_b;
+};
+struct PartialSpec {
+    std::vector<PartialPair> contract_pairs, diagonal_pairs;
+    bool has_output_order = false;
+};
+struct PartialSitePlan {
+    size_t S = 1, K = 1, T = 1;    // the fused groups
+    size_t s0 = 1, k0 = 1, t0 = 1; // the dimension of the first leg of each group (the group's dimension below two legs)
+    // offsets into the fused site index x0 + X0 x1 of A and y0 + Y0 y1 of B per step of the (first, second) leg of a group
+    size_t as[2] = {0, 0}, ak[2] = {0, 0};
+    size_t bs[2] = {0, 0}, bk[2] = {0, 0}, bt[2] = {0, 0};
+    size_t leg_dims[4] = {0, 0, 0, 0}; // the dims of the legs of S (two slots), then of T (two slots); 0 = no such leg
+};
+// Host only.  a_sd / b_sd: (leg 0, leg 1) per site.  INVALID_ARGUMENT with the reference's messages (a leg out of range is "not found in
+// first / second MPO external indices", then "index shape mismatch", then "appears in multiple pairs"; contract pairs before diagonal
+// ones), lengths that differ, |S| * |T| above 65535; NOT_IMPLEMENTED for a pair across two sites and for output_order.
+std::vector<PartialSitePlan> mpo_partial_plan(const std::vector<std::array<size_t, 2>>& a_sd, const std::vector<std::array<size_t, 2>>& b_sd,
+                                              const PartialSpec& spec);
+// Naive (one launch of the site product of kernels_partial.hip for the chain, then the compress stage of mpo_contract when `compress`)
+// or ZipUp (the recursion of mpo_contract with the site step done by one launch of the half product of kernels_partial.hip, whose
+// output is the matrix the SVD reads).  Fit and RSVD answer NOT_IMPLEMENTED as in mpo_contract.
+std::unique_ptr<Mpo> mpo_partial_contract(Mpo& a, Mpo& b, const PartialSpec& spec, MpoAlgorithm alg, bool compress,
+                                          const MpoContractionOptions& opt);
+// mpo_contract_fit for a spec: same sweeps, environments and convergence rule, the half products taking the site plan.
+std::unique_ptr<Mpo> mpo_partial_contract_fit(Mpo& a, Mpo& b, const PartialSpec& spec, const MpoFitOptions& opt, Mpo* initial, MpoFitInfo& info);
+// Test hook, the counterpart of mpo_fit_half: env L[n_env, la, lb] -> P[n_env, s, t, ra, rb], or R[ra, rb, n_env] -> Q[la, lb, s, t, n_env].
+std::vector<double> mpo_partial_half(const double* env, size_t n_env, bool right, Mpo& a, Mpo& b, const PartialSpec& spec, size_t site);
+
 } // namespace t4a

@@ -2173,3 +2173,6 @@ from .gse import (GseOptions, GseOptionsC, GseResult, GseTdvpOptions, GseTdvpRes
 # partitioned MPOs: module t4a_amd.partitioned; its `contract` stays under the module name, like t4a_amd.mpo.contract
 from . import partitioned  # noqa: E402
 from .partitioned import Projector, PartitionedMPO, proj_contract  # noqa: E402,F401
+# partial contraction of two MPOs (contract, diagonal or keep per leg) and the Hadamard product: module t4a_amd.partial
+from . import partial  # noqa: E402
+from .partial import PartialContractionSpec, partial_plan, partial_contract, partial_contract_fit, hadamard  # noqa: E402,F401
