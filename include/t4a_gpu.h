@@ -1649,6 +1649,66 @@ t4a_gpu_status t4a_gpu_pmpo_launch_blocks(size_t total, size_t* blocks);
 t4a_gpu_status t4a_gpu_pmpo_time_contract(const t4a_gpu_pmpo* a, const t4a_gpu_pmpo* b, double tolerance, size_t max_bond_dim, size_t reps,
                                           double* ms3);
 
+/* =====================================================================================
+ * swap_site_indices on a chain: which site holds which site index
+ * tensor4all-treetn/src/treetn/swap.rs (SwapOptions, ScheduledSwapStep, SwapSchedule::build), treetn/mod.rs (swap_on_edge,
+ * swap_site_indices), for f64 and by position.
+ * A leg train is a tensor train over fused site indices plus, per site, an ordered list of legs (key, dim): keys are unique across
+ * the train and ordered as int64, the first leg of a site is the fastest in its fused index, a site may hold no leg or several.
+ * Legs travel as leg_counts[n_sites] and the keys / dims of all sites one after the other.
+ * LEG ORDER WRITTEN BY A STEP: on both sites of a step the legs are stored in ascending key order; sites that no step touches keep
+ * their order (this project's rule; the reference has index objects and no positional order).
+ * ===================================================================================== */
+typedef struct t4a_gpu_swap_schedule t4a_gpu_swap_schedule;
+#define T4A_GPU_SWAP_PASSES_DIAMETER ((size_t)-1)
+#define T4A_GPU_SWAP_ROUTE_SCALAR 1 /* a tile of the step kernel summed per thread */
+#define T4A_GPU_SWAP_ROUTE_MFMA 2   /* a tile on the f64 matrix cores */
+/* SwapSchedule::build on a chain of n_sites; host only, usable with no device.  current / target: (key, site) pairs; the base sweep
+ * starts at root (for root 0: the edges (i, i+1) rightwards, then (i+1, i) leftwards), at most max_passes passes
+ * (T4A_GPU_SWAP_PASSES_DIAMETER: n_sites - 1, as the reference), a step only where a targeted leg crosses.  INVALID_ARGUMENT with the
+ * reference's messages: "root .. not in topology", "target_assignment contains index .. which is not in the network", "target node ..
+ * is not in the topology", "did not converge within {n} passes".
+ * cur_dims (may be NULL; one per current leg) adds the plan checks, still before any device is touched: a step whose merged pair
+ * holds more than 8 legs, a step either of whose sides exceeds the fused-dimension limit 65535 and, with link_dims (may be NULL;
+ * n_sites - 1 bonds), a work matrix above INT_MAX elements (max_bond_dim: 0 = none). */
+t4a_gpu_status t4a_gpu_swap_schedule_build(size_t n_sites, const int64_t* cur_keys, const size_t* cur_sites, const size_t* cur_dims,
+                                           size_t n_current, const int64_t* target_keys, const size_t* target_sites, size_t n_target,
+                                           size_t root, size_t max_passes, const size_t* link_dims, size_t max_bond_dim,
+                                           t4a_gpu_swap_schedule** out);
+void t4a_gpu_swap_schedule_release(t4a_gpu_swap_schedule* schedule);
+t4a_gpu_status t4a_gpu_swap_schedule_len(const t4a_gpu_swap_schedule* schedule, size_t* n_steps);
+/* sizes[3]: the lengths of transport_path, a_side and b_side of a step; _step reads it out (node_ab[2] = node_a, node_b; the sides in
+ * ascending key order — they are sets). */
+t4a_gpu_status t4a_gpu_swap_schedule_step_sizes(const t4a_gpu_swap_schedule* schedule, size_t step, size_t* sizes);
+t4a_gpu_status t4a_gpu_swap_schedule_step(const t4a_gpu_swap_schedule* schedule, size_t step, size_t* transport_path, size_t* node_ab,
+                                          int64_t* a_side, int64_t* b_side);
+/* swap_site_indices: a new train with every targeted leg on its target site.  An empty target or an empty schedule: *out is a copy,
+ * the legs as given, *moved = 0 and no canonicalisation (as in the reference).  Otherwise QR canonicalisation around site 0, then per
+ * step the exact QR transport of the centre, the step kernel, the truncated SVD (threshold = rtol, or 0 for has_rtol == 0 — never a
+ * global default —, Relative / Value / PerValue; max_bond_dim when has_max_bond_dim) and the split with node_a's site the isometry and
+ * node_b's carrying S; *center = node_b of the last step.  out_keys / out_dims hold as many legs as came in.  ms3 (may be NULL): device
+ * ms of the step kernel, the SVD with the split, and the QR steps (tools/probe_swap.py). */
+t4a_gpu_status t4a_gpu_tt_swap_site_indices(const t4a_gpu_tt* tt, const size_t* leg_counts, const int64_t* keys, const size_t* dims,
+                                            const int64_t* target_keys, const size_t* target_sites, size_t n_target,
+                                            int32_t has_max_bond_dim, size_t max_bond_dim, int32_t has_rtol, double rtol, t4a_gpu_tt** out,
+                                            size_t* out_leg_counts, int64_t* out_keys, size_t* out_dims, int32_t* moved, size_t* center,
+                                            size_t* n_steps, double* ms3);
+/* Test hook, the counterpart of t4a_gpu_mpo_partial_half: the step kernel exactly as a step launches it on the host cores
+ * left[l, X, m] and right[m, Y, r] (chain order; X, Y the products of the leg dims).  to_left / to_right: the keys that end on the
+ * left / the right site, stored there in ascending order.  out: Theta' with M = l |left'| rows and N = |right'| r columns,
+ * column-major, row = l_idx + l xa', column = xb' + |right'| r_idx; mn[2] = (M, N); *route = the T4A_GPU_SWAP_ROUTE_* bits taken. */
+t4a_gpu_status t4a_gpu_swap_theta(const double* left, size_t l, size_t m, const double* right, size_t r, const int64_t* left_keys,
+                                  const size_t* left_dims, size_t n_left, const int64_t* right_keys, const size_t* right_dims,
+                                  size_t n_right, const int64_t* to_left, size_t n_to_left, const int64_t* to_right, size_t n_to_right,
+                                  double* out, size_t* mn, int32_t* route);
+/* Probe (tools/probe_swap.py): device ms per launch over `reps` launches, binary legs exchanged at l = m = r = bond, of [0] the step
+ * kernel and [1] the composition from existing pieces: GEMM, then one permutation launch. */
+t4a_gpu_status t4a_gpu_swap_theta_time(size_t bond, size_t reps, double* ms2);
+/* The legs of the named sites in another order, in place, one gather launch over all of them.  order_counts[n_named] keys per named
+ * site, each a permutation of the site's keys; leg_counts / keys / dims describe the train and are rewritten. */
+t4a_gpu_status t4a_gpu_legtrain_reorder(t4a_gpu_tt* tt, const size_t* leg_counts, int64_t* keys, size_t* dims, const size_t* sites,
+                                        const size_t* order_counts, const int64_t* order_keys, size_t n_named);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -24,6 +24,7 @@
 #include "gse.hpp"
 #include "pmpo.hpp"
 #include "linsolve.hpp"
+#include "swap.hpp"
 
 struct t4a_gpu_tci2 {
     t4a::Tci2 impl;
@@ -80,6 +81,10 @@ struct t4a_gpu_qt_op {
 
 struct t4a_gpu_contraction {
     std::unique_ptr<t4a::MpoContraction> impl;
+};
+
+struct t4a_gpu_swap_schedule {
+    t4a::SwapSchedule impl; // host data only
 };
 
 struct t4a_gpu_projected_operator {
@@ -5454,6 +5459,200 @@ t4a_gpu_status t4a_gpu_pmpo_time_contract(const t4a_gpu_pmpo* a, const t4a_gpu_p
         T4A_REQUIRE_PTR(b);
         T4A_REQUIRE_PTR(ms3);
         pmpo_time_contract(*a->impl, *b->impl, pmpo_options(tolerance, max_bond_dim, 0), reps, ms3);
+    });
+}
+
+// ---- swap_site_indices on a chain (swap.hpp) ----
+namespace {
+SiteLegs site_legs(size_t n, const size_t* leg_counts, const int64_t* keys, const size_t* dims)
+{
+    SiteLegs legs(n);
+    if (n) T4A_REQUIRE_PTR(leg_counts);
+    size_t at = 0;
+    for (size_t i = 0; i < n; ++i)
+        for (size_t k = 0; k < leg_counts[i]; ++k, ++at) {
+            T4A_REQUIRE_PTR(keys);
+            T4A_REQUIRE_PTR(dims);
+            legs[i].push_back({keys[at], dims[at]});
+        }
+    return legs;
+}
+void write_legs(const SiteLegs& legs, size_t* leg_counts, int64_t* keys, size_t* dims)
+{
+    size_t at = 0;
+    for (size_t i = 0; i < legs.size(); ++i) {
+        if (leg_counts) leg_counts[i] = legs[i].size();
+        for (const SwapLeg& g : legs[i]) {
+            if (keys) keys[at] = g.key;
+            if (dims) dims[at] = g.dim;
+            ++at;
+        }
+    }
+}
+SwapAssignment assignment(const int64_t* keys, const size_t* sites, size_t count)
+{
+    SwapAssignment a;
+    if (count) {
+        T4A_REQUIRE_PTR(keys);
+        T4A_REQUIRE_PTR(sites);
+    }
+    for (size_t k = 0; k < count; ++k) a.push_back({keys[k], sites[k]});
+    return a;
+}
+std::vector<SwapLeg> leg_list(const int64_t* keys, const size_t* dims, size_t count)
+{
+    std::vector<SwapLeg> v;
+    if (count) {
+        T4A_REQUIRE_PTR(keys);
+        T4A_REQUIRE_PTR(dims);
+    }
+    for (size_t k = 0; k < count; ++k) v.push_back({keys[k], dims[k]});
+    return v;
+}
+} // namespace
+
+t4a_gpu_status t4a_gpu_swap_schedule_build(size_t n_sites, const int64_t* cur_keys, const size_t* cur_sites, const size_t* cur_dims,
+                                           size_t n_current, const int64_t* target_keys, const size_t* target_sites, size_t n_target,
+                                           size_t root, size_t max_passes, const size_t* link_dims, size_t max_bond_dim,
+                                           t4a_gpu_swap_schedule** out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(out);
+        *out = nullptr;
+        const SwapAssignment current = assignment(cur_keys, cur_sites, n_current);
+        SwapSchedule sched = swap_schedule_build(n_sites, current, assignment(target_keys, target_sites, n_target), root, max_passes);
+        if (cur_dims) {
+            SiteLegs legs(n_sites);
+            for (size_t k = 0; k < n_current; ++k) legs[current[k].second].push_back({current[k].first, cur_dims[k]});
+            std::vector<size_t> links;
+            if (link_dims && n_sites) links.assign(link_dims, link_dims + (n_sites - 1));
+            swap_plan_check(sched, legs, link_dims ? &links : nullptr, max_bond_dim);
+        }
+        *out = new t4a_gpu_swap_schedule{std::move(sched)};
+    });
+}
+
+void t4a_gpu_swap_schedule_release(t4a_gpu_swap_schedule* h) { delete h; }
+
+t4a_gpu_status t4a_gpu_swap_schedule_len(const t4a_gpu_swap_schedule* h, size_t* n_steps)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(h);
+        T4A_REQUIRE_PTR(n_steps);
+        *n_steps = h->impl.steps.size();
+    });
+}
+
+t4a_gpu_status t4a_gpu_swap_schedule_step_sizes(const t4a_gpu_swap_schedule* h, size_t step, size_t* sizes)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(h);
+        T4A_REQUIRE_PTR(sizes);
+        if (step >= h->impl.steps.size()) throw Error(T4A_GPU_INVALID_ARGUMENT, "swap schedule: step out of range");
+        const ScheduledSwapStep& s = h->impl.steps[step];
+        sizes[0] = s.transport_path.size(), sizes[1] = s.a_side.size(), sizes[2] = s.b_side.size();
+    });
+}
+
+t4a_gpu_status t4a_gpu_swap_schedule_step(const t4a_gpu_swap_schedule* h, size_t step, size_t* transport_path, size_t* node_ab,
+                                          int64_t* a_side, int64_t* b_side)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(h);
+        T4A_REQUIRE_PTR(node_ab);
+        if (step >= h->impl.steps.size()) throw Error(T4A_GPU_INVALID_ARGUMENT, "swap schedule: step out of range");
+        const ScheduledSwapStep& s = h->impl.steps[step];
+        if (!s.transport_path.empty()) T4A_REQUIRE_PTR(transport_path);
+        if (!s.a_side.empty()) T4A_REQUIRE_PTR(a_side);
+        if (!s.b_side.empty()) T4A_REQUIRE_PTR(b_side);
+        std::copy(s.transport_path.begin(), s.transport_path.end(), transport_path);
+        std::copy(s.a_side.begin(), s.a_side.end(), a_side);
+        std::copy(s.b_side.begin(), s.b_side.end(), b_side);
+        node_ab[0] = s.node_a, node_ab[1] = s.node_b;
+    });
+}
+
+t4a_gpu_status t4a_gpu_tt_swap_site_indices(const t4a_gpu_tt* tt, const size_t* leg_counts, const int64_t* keys, const size_t* dims,
+                                            const int64_t* target_keys, const size_t* target_sites, size_t n_target,
+                                            int32_t has_max_bond_dim, size_t max_bond_dim, int32_t has_rtol, double rtol, t4a_gpu_tt** out,
+                                            size_t* out_leg_counts, int64_t* out_keys, size_t* out_dims, int32_t* moved, size_t* center,
+                                            size_t* n_steps, double* ms3)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(out);
+        *out = nullptr;
+        T4A_REQUIRE_PTR(tt);
+        SwapOptions o;
+        o.has_max_bond_dim = has_max_bond_dim != 0, o.max_bond_dim = max_bond_dim;
+        o.has_rtol = has_rtol != 0, o.rtol = rtol;
+        o.validate();
+        SiteLegs legs = site_legs(tt->impl.len(), leg_counts, keys, dims);
+        const SwapAssignment target = assignment(target_keys, target_sites, n_target);
+        // the work happens on a copy with an engine of its own; the input stays as it is
+        std::unique_ptr<t4a_gpu_tt> res(new t4a_gpu_tt(tt->impl.cores, tt->impl.eng.stream()));
+        SwapTimings tm;
+        const SwapResult r = swap_site_indices(res->impl.eng, res->impl.cores, legs, target, o, ms3 ? &tm : nullptr);
+        res->impl.eng.sync();
+        write_legs(legs, out_leg_counts, out_keys, out_dims);
+        if (moved) *moved = r.moved ? 1 : 0;
+        if (center) *center = r.center;
+        if (n_steps) *n_steps = r.n_steps;
+        if (ms3) ms3[0] = tm.kernel_ms, ms3[1] = tm.svd_ms, ms3[2] = tm.qr_ms;
+        *out = res.release();
+    });
+}
+
+t4a_gpu_status t4a_gpu_swap_theta(const double* left, size_t l, size_t m, const double* right, size_t r, const int64_t* left_keys,
+                                  const size_t* left_dims, size_t n_left, const int64_t* right_keys, const size_t* right_dims,
+                                  size_t n_right, const int64_t* to_left, size_t n_to_left, const int64_t* to_right, size_t n_to_right,
+                                  double* out, size_t* mn, int32_t* route)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(left);
+        T4A_REQUIRE_PTR(right);
+        T4A_REQUIRE_PTR(out);
+        if (n_to_left) T4A_REQUIRE_PTR(to_left);
+        if (n_to_right) T4A_REQUIRE_PTR(to_right);
+        const std::vector<int64_t> tl(to_left, to_left + n_to_left), tr(to_right, to_right + n_to_right);
+        size_t M = 0, N = 0;
+        int rt = 0;
+        require_device();
+        const std::vector<double> v = swap_theta(left, l, m, right, r, leg_list(left_keys, left_dims, n_left),
+                                                 leg_list(right_keys, right_dims, n_right), tl, tr, M, N, rt);
+        std::memcpy(out, v.data(), v.size() * sizeof(double));
+        if (mn) mn[0] = M, mn[1] = N;
+        if (route) *route = rt;
+    });
+}
+
+t4a_gpu_status t4a_gpu_swap_theta_time(size_t bond, size_t reps, double* ms2)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(ms2);
+        require_device();
+        swap_theta_time(bond, (int)std::min<size_t>(reps, 1u << 20), &ms2[0], &ms2[1]);
+    });
+}
+
+t4a_gpu_status t4a_gpu_legtrain_reorder(t4a_gpu_tt* tt, const size_t* leg_counts, int64_t* keys, size_t* dims, const size_t* sites,
+                                        const size_t* order_counts, const int64_t* order_keys, size_t n_named)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(tt);
+        SiteLegs legs = site_legs(tt->impl.len(), leg_counts, keys, dims);
+        std::vector<std::pair<size_t, std::vector<int64_t>>> orders;
+        if (n_named) {
+            T4A_REQUIRE_PTR(sites);
+            T4A_REQUIRE_PTR(order_counts);
+        }
+        size_t at = 0;
+        for (size_t k = 0; k < n_named; ++k) {
+            if (order_counts[k]) T4A_REQUIRE_PTR(order_keys);
+            orders.push_back({sites[k], std::vector<int64_t>(order_keys + at, order_keys + at + order_counts[k])});
+            at += order_counts[k];
+        }
+        legtrain_reorder(tt->impl.eng, tt->impl.cores, legs, orders);
+        write_legs(legs, nullptr, keys, dims);
     });
 }
 

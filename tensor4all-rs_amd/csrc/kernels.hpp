@@ -678,6 +678,41 @@ struct MpoPartialHalfDesc {
 bool mpo_partial_half_launch(const MpoPartialHalfDesc& d, hipStream_t stream);
 
 // ------------------------------------------------------------------------------------------------
+// kernels_swap.hip — the step of swap_site_indices (swap.hpp) and the leg reordering of a leg train.
+// Step: two neighbouring cores A[l, x, m] and B[m, y, r] (x, y: the fused site indices, first leg fastest) are contracted over m
+// and written as the column-major M x N matrix the SVD reads, M = l * Ra, N = Cb * r, with the legs of the pair redistributed:
+//   out[(l_idx + l * xa) + M * (xb + Cb * r_idx)] = sum_m A[l_idx, x, m] * B[m, y, r_idx]
+// Leg j of the merged pair (at most SWAP_MAX_LEGS) has dimension dim[j], is the digit (x or y) / src[j] % dim[j] of x (from_right[j] == 0)
+// or y, and contributes digit * dst[j] to xa (to_col[j] == 0) or to xb.  Ra * Cb == X * Y.
+// swap_theta_launch returns false, having launched nothing, when the grid would hold more than INT_MAX workgroups.
+// ------------------------------------------------------------------------------------------------
+constexpr int SWAP_MAX_LEGS = 8;
+struct SwapThetaDesc {
+    const double* A; // [l, X, m]
+    const double* B; // [m, Y, r]
+    double* out;     // [l * Ra, Cb * r]
+    int l, X, m, Y, r;
+    int Ra, Cb;
+    int n_legs;
+    int dim[SWAP_MAX_LEGS], src[SWAP_MAX_LEGS], dst[SWAP_MAX_LEGS];
+    unsigned char from_right[SWAP_MAX_LEGS], to_col[SWAP_MAX_LEGS];
+};
+constexpr int SWAP_ROUTE_SCALAR = 1, SWAP_ROUTE_MFMA = 2; // bits of the route a launch takes: tiles per thread / on the matrix cores
+int swap_theta_route(int l, int r);
+bool swap_theta_launch(const SwapThetaDesc& d, hipStream_t stream);
+// Leg reordering, every named site in one launch (job list as MpoPartialSiteJob): the fused site index of dst is read with the legs in
+// their new order, leg j of that order having dimension dim[j] and the stride src[j] in the fused site index of src.
+struct LegReorderJob {
+    const double* src; // [l, s, r]
+    double* dst;       // [l, s, r]
+    unsigned long long off;
+    int l, s, r;
+    int n_legs;
+    int dim[SWAP_MAX_LEGS], stride[SWAP_MAX_LEGS];
+};
+void leg_reorder_launch(const LegReorderJob* d_jobs, int n_jobs, unsigned long long total, hipStream_t stream);
+
+// ------------------------------------------------------------------------------------------------
 // kernels_contraction.hip — environments of the lazy product A·B of two MPOs (simplett/src/mpo/contraction.rs:262-383) for a batch
 // of unique index halves, one workgroup per half.  An environment is a matrix over the bond pair, column-major [a + dim_a * b];
 // item `it` of a launch is written to d_out + it * ld.  idx holds the (i, j) pairs of the walked sites per item, item-major.

@@ -90,8 +90,8 @@ std::vector<double> mpo_fit_half(const double* env, size_t n_env, bool right, Mp
 //   C_i[(a, b), s, t, (a', b')] = sum_{kappa in K} A_i[a, x(s, kappa), a'] * B_i[b, y(s, kappa, t), b']
 // with the bonds fused as the naive product fuses them; the result is an MPO with site dims (|S|, |T|).  The matrix product is
 // {contract (i, 1)-(i, 0) for all i}, the Hadamard product of operators {diagonal (i, 0)-(i, 0), diagonal (i, 1)-(i, 1)}.
-// Pairs across two sites and output_order are NOT_IMPLEMENTED (the reference moves indices with swap_site_indices, which this
-// project does not have); trees, mismatched topologies and complex scalars are outside this backend.
+// Pairs across two sites and output_order are NOT_IMPLEMENTED (the reference moves indices with swap_site_indices; this project's,
+// swap.hpp, is not wired in here yet); trees, mismatched topologies and complex scalars are outside this backend.
 struct PartialPair {
     size_t site_a, leg_a, site_b, leg_b;
 };

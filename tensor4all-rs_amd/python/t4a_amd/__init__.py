@@ -2176,3 +2176,6 @@ from .partitioned import Projector, PartitionedMPO, proj_contract  # noqa: E402,
 # partial contraction of two MPOs (contract, diagonal or keep per leg) and the Hadamard product: module t4a_amd.partial
 from . import partial  # noqa: E402
 from .partial import PartialContractionSpec, partial_plan, partial_contract, partial_contract_fit, hadamard  # noqa: E402,F401
+from . import swap  # noqa: E402
+from .swap import (SwapOptions, ScheduledSwapStep, SwapSchedule, LegTrain, swap_site_indices, swap_site_indices_by_index,  # noqa: E402,F401
+                   swap_site_indices_legs, regroup_quantics, quantics_target, swap_theta)
