@@ -138,6 +138,34 @@ t4a_gpu_status t4a_gpu_gemm_f64(const double* a, const double* b, size_t m, size
 t4a_gpu_status t4a_gpu_gemm_batched_f64(size_t batch, size_t m, size_t k, size_t n, const double* a,
                                         const double* b, double* c);
 
+/* The route the GEMM launcher takes for `batch` products of shape m x n x k (host only; m, n, batch positive, k may be 0, all within
+ * int): *bn = 32 (narrow 64 x 32 block tiles) or 64 (wide 64 x 64), *ksplit = slices of a split-K product (1: none), the grid of
+ * *grid_m x *grid_n tiles per problem and slice, *remapped = 1 when (grid_m * grid_n) % 8 == 0: the XCD-aware tile order.  The launcher
+ * launches what this reports. */
+t4a_gpu_status t4a_gpu_gemm_route(size_t m, size_t n, size_t k, size_t batch, int32_t* bn, int32_t* ksplit, int32_t* grid_m,
+                                  int32_t* grid_n, int32_t* remapped);
+/* Test hook: the GEMM exactly as every layer launches it, one whole descriptor per product on flat host buffers.  Product p is
+ *   C_j = alpha op(A_j) op(B_j) + beta C_j,  j < batch,   op(A) m x k, op(B) k x n, C m x n, all column-major,
+ * with A_j at a[off_a + j stride_a] (stored m x k with leading dimension lda, or k x m when trans_a != 0), B_j at
+ * b[off_b + j stride_b] likewise and C_j at c[off_c + j stride_c] (ldc); strides and offsets count elements, stride_a / stride_b may
+ * be 0 (one operand shared by the batch).  a (na elements), b (nb) and c (nc) are uploaded, the n_descs products are queued in order
+ * on one stream with no synchronisation between them, and c is downloaded after one synchronisation.  beta == 0: C is not read.
+ * k == 0 goes to the kernel as it stands (C = beta C).  Refused with INVALID_ARGUMENT before the device is touched: a negative size or
+ * one beyond int (m, n, k: beyond INT_MAX - 63), trans_a / trans_b other than 0 or 1, a leading dimension below the rows of the stored operand (or below 1), an
+ * operand or result that runs past its buffer, results of two problems of one product that overlap (stride_c = 0 with batch > 1
+ * included), more problems times split-K slices than the 65535 a launch takes.  No product code calls this. */
+typedef struct t4a_gpu_gemm_desc {
+    int64_t m, n, k;
+    int64_t lda, ldb, ldc;
+    int32_t trans_a, trans_b;
+    double alpha, beta;
+    int64_t batch;
+    int64_t stride_a, stride_b, stride_c;
+    int64_t off_a, off_b, off_c;
+} t4a_gpu_gemm_desc;
+t4a_gpu_status t4a_gpu_gemm_desc_f64(const t4a_gpu_gemm_desc* descs, size_t n_descs, const double* a, size_t na, const double* b,
+                                     size_t nb, double* c, size_t nc);
+
 /* triangular_solve_matrix(A,B,left_side,lower,transpose_a,unit_diagonal) (tensorbackend/src/backend.rs:924):
  * solves op(A) X = B (left_side) or X op(A) = B.  A is na x na, B and X are bm x bn. */
 t4a_gpu_status t4a_gpu_trsm_f64(const double* a, size_t na, const double* b, size_t bm, size_t bn,

@@ -513,6 +513,107 @@ t4a_gpu_status t4a_gpu_gemm_f64(const double* a, const double* b, size_t m, size
     return t4a_gpu_gemm_batched_f64(1, m, k, n, a, b, c);
 }
 
+t4a_gpu_status t4a_gpu_gemm_route(size_t m, size_t n, size_t k, size_t batch, int32_t* bn, int32_t* ksplit, int32_t* grid_m, int32_t* grid_n,
+                                  int32_t* remapped)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(bn);
+        T4A_REQUIRE_PTR(ksplit);
+        T4A_REQUIRE_PTR(grid_m);
+        T4A_REQUIRE_PTR(grid_n);
+        T4A_REQUIRE_PTR(remapped);
+        require_int_dims({m, n, k, batch}, "gemm_route");
+        if (m == 0 || n == 0 || batch == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "gemm_route: m, n and batch must be positive (an empty product launches nothing)");
+        const GemmPlan p = gemm_plan((int)m, (int)n, (int)k, (int)batch);
+        *bn = p.bn;
+        *ksplit = p.ksplit;
+        *grid_m = p.grid_m;
+        *grid_n = p.grid_n;
+        *remapped = p.remapped ? 1 : 0;
+    });
+}
+
+namespace {
+// what t4a_gpu_gemm_desc_f64 refuses, all of it on the host: "gemm_desc[i]: <what>"
+void require_gemm_desc(const t4a_gpu_gemm_desc& d, size_t i, size_t na, size_t nb, size_t nc)
+{
+    auto refuse = [&](const std::string& what) { throw Error(T4A_GPU_INVALID_ARGUMENT, "gemm_desc[" + std::to_string(i) + "]: " + what); };
+    const int64_t imax = std::numeric_limits<int>::max();
+    for (int64_t v : {d.m, d.n, d.k, d.lda, d.ldb, d.ldc, d.batch, d.stride_a, d.stride_b, d.stride_c, d.off_a, d.off_b, d.off_c})
+        if (v < 0) refuse("negative size, leading dimension, stride or offset");
+    for (int64_t v : {d.m, d.n, d.k, d.lda, d.ldb, d.ldc, d.batch})
+        if (v > imax) refuse("dimension exceeds the 32-bit index range of the device kernels");
+    // (the kernel rounds m, n and k up to whole tiles in int)
+    for (int64_t v : {d.m, d.n, d.k})
+        if (v > imax - 63) refuse("m, n and k must be at most INT_MAX - 63: the kernel rounds them up to whole tiles in 32-bit integers");
+    if ((d.trans_a != 0 && d.trans_a != 1) || (d.trans_b != 0 && d.trans_b != 1)) refuse("trans_a and trans_b must be 0 or 1");
+    const int64_t a_rows = d.trans_a ? d.k : d.m, a_cols = d.trans_a ? d.m : d.k;
+    const int64_t b_rows = d.trans_b ? d.n : d.k, b_cols = d.trans_b ? d.k : d.n;
+    if (d.lda < std::max<int64_t>(a_rows, 1)) refuse("lda is smaller than the rows of the stored A");
+    if (d.ldb < std::max<int64_t>(b_rows, 1)) refuse("ldb is smaller than the rows of the stored B");
+    if (d.ldc < std::max<int64_t>(d.m, 1)) refuse("ldc is smaller than the rows of C");
+    // (every factor is below 2^31 except strides and offsets, which are compared step by step: no overflow)
+    auto fits = [&](int64_t off, int64_t stride, int64_t rows, int64_t cols, int64_t ld, size_t count) {
+        if (rows == 0 || cols == 0 || d.batch == 0) return true;
+        const unsigned __int128 end = (unsigned __int128)off + (unsigned __int128)(d.batch - 1) * (unsigned __int128)stride +
+                                      (unsigned __int128)(cols - 1) * (unsigned __int128)ld + (unsigned __int128)rows;
+        return end <= (unsigned __int128)count;
+    };
+    if (!fits(d.off_a, d.stride_a, a_rows, a_cols, d.lda, na)) refuse("A runs past its buffer");
+    if (!fits(d.off_b, d.stride_b, b_rows, b_cols, d.ldb, nb)) refuse("B runs past its buffer");
+    if (!fits(d.off_c, d.stride_c, d.m, d.n, d.ldc, nc)) refuse("C runs past its buffer");
+    if (d.m == 0 || d.n == 0 || d.batch == 0) return;
+    if (d.batch > 1) {
+        // results do not overlap when a problem ends before the next begins, or when the problems interleave inside ldc
+        const unsigned __int128 span = (unsigned __int128)(d.n - 1) * (unsigned __int128)d.ldc + (unsigned __int128)d.m;
+        const bool apart = (unsigned __int128)d.stride_c >= span;
+        const bool interleaved = d.stride_c >= d.m && (unsigned __int128)(d.batch - 1) * (unsigned __int128)d.stride_c + (unsigned __int128)d.m <= (unsigned __int128)d.ldc;
+        if (!apart && !interleaved) refuse("stride_c makes the results of two problems overlap");
+    }
+    const GemmPlan p = gemm_plan((int)d.m, (int)d.n, (int)d.k, (int)d.batch);
+    if (d.batch * (int64_t)p.ksplit > 65535 || p.grid_n > 65535) refuse("more problems, split-K slices or tile columns than the 65535 a launch takes");
+}
+} // namespace
+
+t4a_gpu_status t4a_gpu_gemm_desc_f64(const t4a_gpu_gemm_desc* descs, size_t n_descs, const double* a, size_t na, const double* b, size_t nb,
+                                     double* c, size_t nc)
+{
+    return guarded([&] {
+        if (n_descs) T4A_REQUIRE_PTR(descs);
+        if (na) T4A_REQUIRE_PTR(a);
+        if (nb) T4A_REQUIRE_PTR(b);
+        if (nc) T4A_REQUIRE_PTR(c);
+        checked_mul(checked_mul(std::max(std::max(na, nb), nc), 2, "gemm_desc buffers"), sizeof(double), "gemm_desc buffers");
+        for (size_t i = 0; i < n_descs; ++i) require_gemm_desc(descs[i], i, na, nb, nc);
+        std::lock_guard<std::mutex> lock(g_dense_mutex);
+        Engine& e = dense_engine();
+        e.d_tmp.reserve(std::max<size_t>(na + nb, 1));
+        e.d_tmp2.reserve(std::max<size_t>(nc, 1));
+        double* da = e.d_tmp.get();
+        double* db = da + na;
+        double* dc = e.d_tmp2.get();
+        StreamSyncOnExit sync_on_exit(e);
+        upload_async(e, da, a, na);
+        upload_async(e, db, b, nb);
+        upload_async(e, dc, c, nc);
+        for (size_t i = 0; i < n_descs; ++i) {
+            const t4a_gpu_gemm_desc& d = descs[i];
+            GemmDesc g = gemm_desc((int)d.m, (int)d.n, (int)d.k, da + d.off_a, (int)d.lda, db + d.off_b, (int)d.ldb, dc + d.off_c, (int)d.ldc);
+            g.transA = d.trans_a;
+            g.transB = d.trans_b;
+            g.strideA = (long long)d.stride_a;
+            g.strideB = (long long)d.stride_b;
+            g.strideC = (long long)d.stride_c;
+            g.alpha = d.alpha;
+            g.beta = d.beta;
+            g.batch = (int)d.batch;
+            gemm_launch(g, e.stream()); // (queued behind its predecessor: no synchronisation between the products)
+        }
+        T4A_HIP(hipGetLastError());
+        download(e, c, dc, nc);
+    });
+}
+
 t4a_gpu_status t4a_gpu_trsm_f64(const double* a, size_t na, const double* b, size_t bm, size_t bn, int32_t left_side,
                                 int32_t lower, int32_t transpose_a, int32_t unit_diagonal, double* x)
 {

@@ -409,6 +409,14 @@ struct GemmDesc {
     double* partial = nullptr;
 };
 void gemm_launch(const GemmDesc& d, hipStream_t stream);
+// The route gemm_launch takes for a shape (host only; m, n, batch > 0, k >= 0): 64 x bn block tiles (bn = 32 narrow, 64 wide) on a grid of
+// grid_m x grid_n x (batch * ksplit) workgroups; remapped: (grid_m * grid_n) % 8 == 0, the XCD-aware tile order of gemm_kernel.
+// gemm_launch launches what this returns, so a test that asserts a route asserts the launch.
+struct GemmPlan {
+    int bn, ksplit, grid_m, grid_n;
+    bool remapped;
+};
+GemmPlan gemm_plan(int m, int n, int k, int batch);
 // One plain product C = A B: no transposes, zero strides, alpha = 1, beta = 0, batch = 1.  Callers assign only what differs.
 inline GemmDesc gemm_desc(int m, int n, int k, const double* A, int lda, const double* B, int ldb, double* C, int ldc)
 {

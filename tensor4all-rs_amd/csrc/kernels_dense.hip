@@ -1322,9 +1322,9 @@ static double* splitk_workspace(hipStream_t stream, size_t doubles)
     return b.get();
 }
 
-template <int BN> static void gemm_launch_bn(const GemmDesc& d, hipStream_t stream)
+template <int BN> static void gemm_launch_bn(const GemmDesc& d, const GemmPlan& p, hipStream_t stream)
 {
-    dim3 grid((d.m + GBM - 1) / GBM, (d.n + BN - 1) / BN, d.batch * d.ksplit);
+    dim3 grid(p.grid_m, p.grid_n, d.batch * d.ksplit);
     constexpr size_t lds = 2 * sizeof(double) * GBK * ((GBM + GPAD) + (BN + GPAD));
     static std::atomic<bool> attr_set{false}; // (launches come from several host threads; setting the attribute twice is harmless)
     if (!attr_set) {
@@ -1334,29 +1334,41 @@ template <int BN> static void gemm_launch_bn(const GemmDesc& d, hipStream_t stre
     hipLaunchKernelGGL(gemm_kernel<BN>, grid, dim3(256), lds, stream, d);
 }
 
-void gemm_launch(const GemmDesc& d, hipStream_t stream)
+GemmPlan gemm_plan(int m, int n, int k, int batch)
 {
-    if (d.m <= 0 || d.n <= 0 || d.batch <= 0) return;
     // two workgroups per compute unit hide each other's LDS / barrier stalls: narrower tiles when 64 x 64 ones cannot provide them
-    const long long tiles64 = (long long)((d.m + GBM - 1) / GBM) * ((d.n + 63) / 64) * d.batch;
-    const bool narrow = tiles64 < 512 && d.n > 32;
+    // (every rounding-up in long long: m, n and k may stand at INT_MAX)
+    const long long tiles64 = (((long long)m + GBM - 1) / GBM) * (((long long)n + 63) / 64) * batch;
+    const bool narrow = tiles64 < 512 && n > 32;
     // small outputs leave most of the chip idle (a 256 x 256 result is 32 narrow tiles on 256 compute units): split K over
     // blockIdx.z and sum the slices in a second pass (a separate launch: the fence of an in-kernel reduction cost more than it
     // saved).  Slices of >= 2 k-tiles, as many as fill the chip twice, at most 16.
-    const long long tiles = (long long)((d.m + GBM - 1) / GBM) * ((d.n + (narrow ? 31 : 63)) / (narrow ? 32 : 64)) * d.batch;
-    const int ktiles = (d.k + GBK - 1) / GBK;
-    int ksplit = 1;
-    if (tiles < 256 && ktiles >= 8) ksplit = (int)std::min<long long>(std::min<long long>(16, ktiles / 2), (512 + tiles - 1) / tiles);
-    if (ksplit <= 1) {
-        if (narrow) gemm_launch_bn<32>(d, stream);
-        else gemm_launch_bn<64>(d, stream);
+    GemmPlan p;
+    p.bn = narrow ? 32 : 64;
+    p.grid_m = (int)(((long long)m + GBM - 1) / GBM);
+    p.grid_n = (int)(((long long)n + p.bn - 1) / p.bn);
+    const long long tiles = (long long)p.grid_m * p.grid_n * batch;
+    const int ktiles = (int)(((long long)k + GBK - 1) / GBK);
+    p.ksplit = 1;
+    if (tiles < 256 && ktiles >= 8) p.ksplit = (int)std::min<long long>(std::min<long long>(16, ktiles / 2), (512 + tiles - 1) / tiles);
+    p.remapped = ((long long)p.grid_m * p.grid_n) % 8 == 0;
+    return p;
+}
+
+void gemm_launch(const GemmDesc& d, hipStream_t stream)
+{
+    if (d.m <= 0 || d.n <= 0 || d.batch <= 0) return;
+    const GemmPlan p = gemm_plan(d.m, d.n, d.k, d.batch);
+    if (p.ksplit <= 1) {
+        if (p.bn == 32) gemm_launch_bn<32>(d, p, stream);
+        else gemm_launch_bn<64>(d, p, stream);
         return;
     }
     GemmDesc ds = d;
-    ds.ksplit = ksplit;
-    ds.partial = splitk_workspace(stream, (size_t)ksplit * d.batch * d.m * d.n);
-    if (narrow) gemm_launch_bn<32>(ds, stream);
-    else gemm_launch_bn<64>(ds, stream);
+    ds.ksplit = p.ksplit;
+    ds.partial = splitk_workspace(stream, (size_t)p.ksplit * d.batch * d.m * d.n);
+    if (p.bn == 32) gemm_launch_bn<32>(ds, p, stream);
+    else gemm_launch_bn<64>(ds, p, stream);
     const size_t mn = (size_t)d.m * d.n;
     hipLaunchKernelGGL(gemm_splitk_reduce_kernel, dim3((unsigned)((mn + 255) / 256), d.batch), dim3(256), 0, stream, ds);
 }

@@ -378,6 +378,49 @@ def batched_mat_mul_same_shape(batch, m, k, n, a, b):
     return c
 
 
+class GemmDescC(ctypes.Structure):
+    _fields_ = [("m", ctypes.c_int64), ("n", ctypes.c_int64), ("k", ctypes.c_int64),
+                ("lda", ctypes.c_int64), ("ldb", ctypes.c_int64), ("ldc", ctypes.c_int64),
+                ("trans_a", c_int32), ("trans_b", c_int32), ("alpha", c_double), ("beta", c_double), ("batch", ctypes.c_int64),
+                ("stride_a", ctypes.c_int64), ("stride_b", ctypes.c_int64), ("stride_c", ctypes.c_int64),
+                ("off_a", ctypes.c_int64), ("off_b", ctypes.c_int64), ("off_c", ctypes.c_int64)]
+
+
+def gemm_desc_c(desc):
+    """A dict with the fields of t4a_gpu_gemm_desc -> GemmDescC.  m, n, k are required; the rest defaults to one plain product: no
+    transposes, dense leading dimensions, alpha 1, beta 0, batch 1, zero strides and offsets."""
+    d = dict(desc)
+    m, n, k = int(d.pop("m")), int(d.pop("n")), int(d.pop("k"))
+    ta, tb = int(d.pop("trans_a", 0)), int(d.pop("trans_b", 0))
+    o = GemmDescC(m=m, n=n, k=k, trans_a=ta, trans_b=tb,
+                  lda=int(d.pop("lda", max(k if ta else m, 1))), ldb=int(d.pop("ldb", max(n if tb else k, 1))), ldc=int(d.pop("ldc", max(m, 1))),
+                  alpha=float(d.pop("alpha", 1.0)), beta=float(d.pop("beta", 0.0)), batch=int(d.pop("batch", 1)),
+                  stride_a=int(d.pop("stride_a", 0)), stride_b=int(d.pop("stride_b", 0)), stride_c=int(d.pop("stride_c", 0)),
+                  off_a=int(d.pop("off_a", 0)), off_b=int(d.pop("off_b", 0)), off_c=int(d.pop("off_c", 0)))
+    if d:
+        raise T4aError(INVALID_ARGUMENT, f"gemm_desc: unknown fields {sorted(d)}")
+    return o
+
+
+def gemm_desc(descs, a, b, c):
+    """Test hook (t4a_gpu_gemm_desc_f64): the products ``descs`` (dicts, see gemm_desc_c) in order on the flat buffers a, b and c, queued
+    on one stream without a synchronisation between them -> the whole c buffer afterwards (c itself is left alone)."""
+    a = np.ascontiguousarray(np.asarray(a, dtype=np.float64).ravel())
+    b = np.ascontiguousarray(np.asarray(b, dtype=np.float64).ravel())
+    out = np.array(np.asarray(c, dtype=np.float64).ravel(), copy=True)
+    arr = (GemmDescC * max(len(descs), 1))(*[gemm_desc_c(d) for d in descs])
+    _check(_lib.t4a_gpu_gemm_desc_f64(arr, c_size_t(len(descs)), _p(a) if a.size else None, c_size_t(a.size), _p(b) if b.size else None,
+                                      c_size_t(b.size), _p(out) if out.size else None, c_size_t(out.size)))
+    return out
+
+
+def gemm_route(m, n, k, batch=1):
+    """The route of the GEMM launcher for a shape (t4a_gpu_gemm_route, host only) -> dict(bn, ksplit, grid_m, grid_n, remapped)."""
+    v = [c_int32(0) for _ in range(5)]
+    _check(_lib.t4a_gpu_gemm_route(c_size_t(m), c_size_t(n), c_size_t(k), c_size_t(batch), *[ctypes.byref(x) for x in v]))
+    return dict(bn=v[0].value, ksplit=v[1].value, grid_m=v[2].value, grid_n=v[3].value, remapped=bool(v[4].value))
+
+
 def triangular_solve_matrix(a, b, left_side, lower, transpose_a, unit_diagonal):
     a = _f(a)
     b = _f(b)
