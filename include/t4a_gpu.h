@@ -1186,6 +1186,19 @@ t4a_gpu_status t4a_gpu_tci2_chain_stats(const t4a_gpu_tci2* h, uint64_t* out /* 
  * index table itself, the site tensors come from the factored matrices the chain leaves behind; out[2] 1-site sweeps that were
  * not eligible and ran bond by bond; out[3] chained 1-site sweeps that fell back to the per-bond path part-way. */
 t4a_gpu_status t4a_gpu_tci2_chain_stats_ext(const t4a_gpu_tci2* h, uint64_t* out /* [4] */);
+/* Segments of launched chains.  A half-sweep whose middle bonds outgrow 64 x 32 is launched bond by bond, but every maximal run of
+ * consecutive bonds that do fit (the two ends of such a chain) runs as ONE persistent workgroup between the launches of its
+ * neighbours: out[0] such walked segments since the handle was created, out[1] the bonds in them.  A half-sweep that is one walk
+ * as a whole counts in chain_stats_ext out[0] and not here; 1-site sweeps, group chains, chains with event timing and T4A_NO_WALK=1
+ * have no segments.  Diagnostics only: a segment computes what the launches it replaces compute, bit for bit. */
+t4a_gpu_status t4a_gpu_tci2_chain_segments(const t4a_gpu_tci2* h, uint64_t* out /* [2] */);
+/* The split behind it (host only, no device is touched): bond b of n_bonds has the upper bounds dep_ub[b] rows of the dependent and
+ * ind_ub[b] of the independent side, order[k] is the bond at position k of the half-sweep.  Segment s covers positions first[s] ..
+ * first[s] + count[s] - 1 and is walked (walked[s] = 1) when every bond in it has dep_ub <= 64 and ind_ub <= 32; segments are maximal,
+ * in sweep order, and cover every position once.  *n_segments is always written; with the three arrays NULL that is all, else
+ * `capacity` must hold it (BUFFER_TOO_SMALL). */
+t4a_gpu_status t4a_gpu_tci2_chain_plan_segments(const size_t* dep_ub, const size_t* ind_ub, const size_t* order, size_t n_bonds, size_t capacity,
+                                                size_t* first, size_t* count, int32_t* walked, size_t* n_segments);
 /* out[0] asynchronous fill_site_tensors issued by the optimisation loop, out[1] of them replayed from the captured HIP graph, out[2]
  * graph captures (a capture happens the second time a fill with the same signature — device addresses, shapes, staging buffers —
  * is issued; handles whose cores were exported / imported through stream 0 never replay: csrc/tci2_fill.hip issue_fill_ops). */

@@ -1282,6 +1282,42 @@ t4a_gpu_status t4a_gpu_tci2_chain_stats_ext(const t4a_gpu_tci2* h, uint64_t* out
     });
 }
 
+t4a_gpu_status t4a_gpu_tci2_chain_segments(const t4a_gpu_tci2* h, uint64_t* out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(h);
+        T4A_REQUIRE_PTR(out);
+        for (int k = 0; k < 2; ++k) out[k] = h->impl.chain_segments[k];
+    });
+}
+
+t4a_gpu_status t4a_gpu_tci2_chain_plan_segments(const size_t* dep_ub, const size_t* ind_ub, const size_t* order, size_t n_bonds, size_t capacity,
+                                                size_t* first, size_t* count, int32_t* walked, size_t* n_segments)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(n_segments);
+        if (n_bonds > 0) {
+            T4A_REQUIRE_PTR(dep_ub);
+            T4A_REQUIRE_PTR(ind_ub);
+            T4A_REQUIRE_PTR(order);
+        }
+        for (size_t k = 0; k < n_bonds; ++k)
+            if (order[k] >= n_bonds) throw t4a::Error(T4A_GPU_INVALID_ARGUMENT, "chain_plan_segments: order[" + std::to_string(k) + "] is not a bond of the chain");
+        const std::vector<t4a::ChainSegment> segs = t4a::chain_plan_segments(dep_ub, ind_ub, order, n_bonds);
+        *n_segments = segs.size();
+        if (!first && !count && !walked) return;
+        T4A_REQUIRE_PTR(first);
+        T4A_REQUIRE_PTR(count);
+        T4A_REQUIRE_PTR(walked);
+        if (capacity < segs.size()) throw t4a::Error(T4A_GPU_BUFFER_TOO_SMALL, "chain_plan_segments: " + std::to_string(segs.size()) + " segments, room for " + std::to_string(capacity));
+        for (size_t s = 0; s < segs.size(); ++s) {
+            first[s] = segs[s].first;
+            count[s] = segs[s].count;
+            walked[s] = segs[s].walked ? 1 : 0;
+        }
+    });
+}
+
 t4a_gpu_status t4a_gpu_tci2_rook_stats(const t4a_gpu_tci2* h, uint64_t* out)
 {
     return guarded([&] {

@@ -350,7 +350,8 @@ struct ChainPrepArgs {
                               // the kernel — a store over PCIe is acknowledged after microseconds, and every barrier waits for it
 };
 // The persistent half-sweep (kernels_chain.hip, chain_walk_kernel): one workgroup walks all bonds — preparation, candidate matrix,
-// one-wave rrLU — when every bond's matrix is at most 64 x 64.  Result blocks as the launched chain writes them.
+// one-wave rrLU — when every bond's matrix is at most 64 x 32 — or a run of consecutive bonds of a launched chain that are.  Result
+// blocks as the launched chain writes them.
 struct ChainWalkArgs {
     char* blocks;                       // [n_bonds] packed result blocks (RrluBlock layout, engine.hpp)
     size_t block_bytes, off_piv, off_rp, off_cp, off_ts;
@@ -360,7 +361,20 @@ struct ChainWalkArgs {
     double rel_tol, abs_tol;
     double* factors;                    // != nullptr: the factored matrix of bond b (permuted coordinates, original orientation) at factors + b * factors_stride
     size_t factors_stride;
-    unsigned token_base;                // bond number k of the half-sweep completes with token token_base + k
+    unsigned token_base;                // bond number k of the half-sweep completes with token token_base + (k - k_first)
+    // A SEGMENT of a launched chain (tci2_chain.hip, chain_plan_segments): the walk covers positions k_first .. k_first + k_count - 1 of
+    // the sweep order (bond b = k sweeping forward, n_bonds - 1 - k sweeping backward) and touches the dimensions, list sizes, tables
+    // and mirror entries of those bonds only.  The whole half-sweep is k_first = 0, k_count = n_bonds.
+    //   k_first > 0: the bond in front was launched — its result, permutations and token come from its global result block, its lists
+    //   from global memory, and the first preparation gathers its pivots as chain_prep_kernel would (a predecessor that gave up poisons
+    //   the segment);
+    //   k_first + k_count < n_bonds: a launched bond follows — the walk does NOT gather the pivots of its last bond: it leaves that
+    //   bond's dependent list in ChainCommon::dep_code / dep_acc, and the launched preparation gathers from the result block as always.
+    int k_first, k_count;
+    const int* prev_iresult;            // (k_first > 0) of the launched bond in front: [0] npiv [1] gave up [3] completion token
+    const int* prev_rowperm;
+    const int* prev_colperm;
+    unsigned prev_token;
     int timed;                          // device time stamps of every factorisation at off_ts
     int lean_prep;                      // 1: the preparation of a bond by one wave out of the LDS (walk_prep_wave0); 0: chain_prep_body
     unsigned long long* phase_ticks;    // diagnostic (T4A_WALK_DEBUG): [8] 100 MHz ticks summed over the bonds: preparation, candidate matrix, rrLU, total; [4] gather [5] dependent list (inside the preparation)

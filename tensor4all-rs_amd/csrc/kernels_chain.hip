@@ -418,7 +418,9 @@ __global__ void __launch_bounds__(256) chain_pi_group_kernel(const ChainGroupSlo
 // dimensions into hdims.  A preparation that stores into pinned memory itself pays the PCIe write acknowledgement at its kernel's
 // end, on the critical path between two rrLU launches; here it is paid once per half-sweep.  (The gather of a poisoned bond wrote
 // nothing: chain_finish ignores everything from the first poisoned bond on.)
-__device__ __forceinline__ void chain_mirror_body(const ChainCommon& c, int nb)
+// A walk that is a segment of a launched chain copies what it wrote itself: the tables I_{g+1}, J_g of the bonds g_lo <= g < g_hi whose
+// pivots it gathered, the dimensions of its own bonds b_lo <= b < b_hi (the launched preparations around it write their own entries).
+__device__ __forceinline__ void chain_mirror_body(const ChainCommon& c, int g_lo, int g_hi, int b_lo, int b_hi)
 {
     const int K = c.K;
     const size_t cap = (size_t)c.cap;
@@ -427,9 +429,8 @@ __device__ __forceinline__ void chain_mirror_body(const ChainCommon& c, int nb)
     // tables with every thread of the grid reading every count in turn, the copy was 38 dependent device-scope loads long at d = 20 —
     // ~20 of the 135 us of a persistent half-sweep of configs[1].)
     const int lane = (int)(threadIdx.x & 63), gwave = gtid >> 6, nwaves = gsz >> 6;
-    for (int pf = gwave; pf < 2 * (nb + 1); pf += nwaves) {
-        const int site = pf >> 1, fam = pf & 1;
-        if ((fam == 0 && site == 0) || (fam == 1 && site == nb)) continue; // (I_0 and J_{n-1} are never written)
+    for (int pf = 2 * g_lo + gwave; pf < 2 * g_hi; pf += nwaves) {
+        const int fam = pf & 1, site = (pf >> 1) + (fam == 0 ? 1 : 0); // (bond g: I_{g+1} and J_g; I_0 and J_{n-1} are never written)
         const ChainTab& T = fam == 0 ? c.I : c.J;
         const ChainTab& Mr = fam == 0 ? c.mI : c.mJ;
         const int cnt = __hip_atomic_load(T.cnt + site, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -441,7 +442,7 @@ __device__ __forceinline__ void chain_mirror_body(const ChainCommon& c, int nb)
         if (lane == 0) Mr.cnt[site] = cnt;
     }
     if (c.hdims)
-        for (int e = gtid; e < nb * 4; e += gsz)
+        for (int e = b_lo * 4 + gtid; e < b_hi * 4; e += gsz)
             if ((e & 3) != 3) c.hdims[e] = __hip_atomic_load(c.dims + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
@@ -500,8 +501,18 @@ __device__ __forceinline__ int walk_load_i32(const int* p) { return __hip_atomic
 // Kronecker order (tensorci2.rs:1224-1246) and the same order-preserving union with the extras (:1837-1846) as chain_prep_body,
 // whose hash and prefix sum over 1 024 threads cost five barriers and ~3 - 4.5 us per bond for lists of a handful of entries.
 // Membership of an extra in the Kronecker part = its parent code is one of the gathered parents (a loop over <= 64 LDS broadcasts).
-template <bool FORWARD>
-__device__ __forceinline__ void walk_prep_wave0(const ChainCommon& c, WalkShared* ws, int b, int prev_b, unsigned prev_token, bool do_build, unsigned long long* dbg = nullptr)
+// Where the first preparation of a segment finds the LAUNCHED bond in front of it: everything chain_prep_kernel reads of its predecessor,
+// in global memory (the kernel boundary in front of the walk made all of it visible).
+struct WalkPrevGlobal {
+    const int* dims;                    // ChainCommon::dims of that bond
+    const int *iresult, *rowperm, *colperm;
+    const uint64_t *dep_code, *dep_acc; // its dependent list (ChainCommon::dep_code: nobody has overwritten it yet)
+    const uint64_t *ind_code, *ind_acc; // its independent list
+};
+// PREV_GLOBAL: the previous bond is that launched one (`g`); otherwise a bond of this walk, whose leavings sit in the LDS.
+template <bool FORWARD, bool PREV_GLOBAL = false>
+__device__ __forceinline__ void walk_prep_wave0(const ChainCommon& c, WalkShared* ws, int b, int prev_b, unsigned prev_token, bool do_build, unsigned long long* dbg = nullptr,
+                                                const WalkPrevGlobal* g = nullptr)
 {
     const unsigned long long dbg_t0 = dbg ? wall_clock64() : 0ull;
     const int lane = threadIdx.x & 63;
@@ -512,24 +523,30 @@ __device__ __forceinline__ void walk_prep_wave0(const ChainCommon& c, WalkShared
     // ---- 1. pivots of the previous bond -> tables I_{pb+1}, J_{pb}; they are the parents of this bond's dependent list ----
     if (prev_b >= 0) {
         const int pb = prev_b;
-        const int pm = ws->dims[pb * 4], pn = ws->dims[pb * 4 + 1];
-        const bool bad = ws->dims[pb * 4 + 2] != 0 || ws->prev_ires[1] != 0 || ws->prev_ires[3] != (int)prev_token || pm <= 0 || pn <= 0;
-        const int r = ws->prev_ires[0];
+        const int* const pdims = PREV_GLOBAL ? g->dims : ws->dims + pb * 4;
+        const int* const pires = PREV_GLOBAL ? g->iresult : ws->prev_ires;
+        const int pm = pdims[0], pn = pdims[1];
+        const bool bad = pdims[2] != 0 || pires[1] != 0 || pires[3] != (int)prev_token || pm <= 0 || pn <= 0;
+        const int r = pires[0];
         const int cnt = r > 0 ? r : 1;
         if (bad || cnt > c.cap || cnt > pm || cnt > pn || cnt > WALK_MAX_LIST) {
             poison = true;
         } else {
-            const uint64_t* const pind_code = ws->ind_code[pb & 1];
-            const uint64_t* const pind_acc = ws->ind_acc[pb & 1];
+            const uint64_t* const pind_code = PREV_GLOBAL ? g->ind_code : ws->ind_code[pb & 1];
+            const uint64_t* const pind_acc = PREV_GLOBAL ? g->ind_acc : ws->ind_acc[pb & 1];
+            const uint64_t* const pdep_code = PREV_GLOBAL ? g->dep_code : ws->dep_code;
+            const uint64_t* const pdep_acc = PREV_GLOBAL ? g->dep_acc : ws->dep_acc;
+            const int* const prp = PREV_GLOBAL ? g->rowperm : ws->perm_rp;
+            const int* const pcp = PREV_GLOBAL ? g->colperm : ws->perm_cp;
             uint64_t rc = 0, cc = 0, ra[T4A_FN_MAX_ACC] = {0, 0, 0, 0}, ca[T4A_FN_MAX_ACC] = {0, 0, 0, 0};
             if (lane < cnt) {
-                const int ri = r > 0 ? ws->perm_rp[lane] : 0, ci = r > 0 ? ws->perm_cp[lane] : 0;
+                const int ri = r > 0 ? prp[lane] : 0, ci = r > 0 ? pcp[lane] : 0;
                 // forward: rows of the previous bond were its dependent list, columns its independent list; backward: the reverse
-                rc = FORWARD ? ws->dep_code[ri] : pind_code[ri];
-                cc = FORWARD ? pind_code[ci] : ws->dep_code[ci];
+                rc = FORWARD ? pdep_code[ri] : pind_code[ri];
+                cc = FORWARD ? pind_code[ci] : pdep_code[ci];
                 for (int q = 0; q < K; ++q) {
-                    ra[q] = FORWARD ? ws->dep_acc[(size_t)ri * K + q] : pind_acc[(size_t)ri * K + q];
-                    ca[q] = FORWARD ? pind_acc[(size_t)ci * K + q] : ws->dep_acc[(size_t)ci * K + q];
+                    ra[q] = FORWARD ? pdep_acc[(size_t)ri * K + q] : pind_acc[(size_t)ri * K + q];
+                    ca[q] = FORWARD ? pind_acc[(size_t)ci * K + q] : pdep_acc[(size_t)ci * K + q];
                 }
             }
             // (every read of the old dependent list is in registers now: the parents may be written)
@@ -682,9 +699,14 @@ __global__ void __launch_bounds__(WALK_T) chain_walk_kernel(ChainCommon c, FnDev
     cw.dep_code = ws->dep_code;
     cw.dep_acc = ws->dep_acc;
     cw.dep_cap = WALK_MAX_LIST;
-    for (int e = tid; e < nb * 4; e += (int)blockDim.x) ws->dims[e] = 0;
-    for (int e = tid; e < nb; e += (int)blockDim.x) ws->ind_cnt[e] = c.ind_cnt[e];
-    for (int e = tid; e <= nb; e += (int)blockDim.x) { // (nb + 1 sites)
+    // the range of this walk: positions k0 <= k < k1 of the sweep order, i.e. bonds b_lo <= b < b_hi (the whole half-sweep: 0 .. nb)
+    const int k0 = w.k_first, k1 = w.k_first + w.k_count;
+    const bool behind = k0 > 0;  // a launched bond in front: the first preparation gathers its pivots from global memory
+    const bool ends = k1 == nb;  // the half-sweep ends here: the pivots of the last bond are gathered by the walk
+    const int b_lo = FORWARD ? k0 : nb - k1, b_hi = FORWARD ? k1 : nb - k0;
+    for (int e = b_lo * 4 + tid; e < b_hi * 4; e += (int)blockDim.x) ws->dims[e] = 0;
+    for (int e = b_lo + tid; e < b_hi; e += (int)blockDim.x) ws->ind_cnt[e] = c.ind_cnt[e];
+    for (int e = b_lo + tid; e <= b_hi; e += (int)blockDim.x) { // (the sites of these bonds: one more than bonds)
         ws->ldim[e] = c.ldim[e];
         ws->woff[e] = c.woff[e];
     }
@@ -698,13 +720,26 @@ __global__ void __launch_bounds__(WALK_T) chain_walk_kernel(ChainCommon c, FnDev
         }
     }
     walk_phase_barrier();
-    walk_prefetch(c, ws, FORWARD ? 0 : nb - 1, 0, (int)blockDim.x); // (the first bond's static inputs: nobody could fetch them ahead)
+    walk_prefetch(c, ws, FORWARD ? k0 : nb - 1 - k0, 0, (int)blockDim.x); // (the first bond's static inputs: nobody could fetch them ahead)
     walk_phase_barrier();
-    for (int k = 0; k <= nb; ++k) {
+    WalkPrevGlobal pg = {};
+    if (behind) {
+        const int pb = FORWARD ? k0 - 1 : nb - k0;
+        pg.dims = c.dims + (size_t)pb * 4;
+        pg.iresult = w.prev_iresult;
+        pg.rowperm = w.prev_rowperm;
+        pg.colperm = w.prev_colperm;
+        pg.dep_code = c.dep_code;
+        pg.dep_acc = c.dep_acc;
+        pg.ind_code = c.ind_code + (size_t)pb * c.ind_cap;
+        pg.ind_acc = c.ind_acc + (size_t)pb * c.ind_cap * c.K;
+    }
+    const int k_end = ends ? k1 : k1 - 1; // (in front of a launched bond there is no gather-only step: that bond's preparation gathers)
+    for (int k = k0; k <= k_end; ++k) {
         const int b = FORWARD ? k : nb - 1 - k;
         ChainPrepArgs pa;
         pa.b = b;
-        pa.do_build = k < nb ? 1 : 0; // (behind the last bond: its pivots only)
+        pa.do_build = k < k1 ? 1 : 0; // (behind the last bond: its pivots only)
         pa.with_rowmap = 0;
         pa.prev_b = -1;
         pa.prev_iresult = nullptr;
@@ -713,21 +748,23 @@ __global__ void __launch_bounds__(WALK_T) chain_walk_kernel(ChainCommon c, FnDev
         pa.prev_token = 0u;
         pa.dbg = nullptr;
         pa.defer_host_writes = 1;
-        if (k > 0) {
+        if (k > k0) {
             pa.prev_b = FORWARD ? b - 1 : b + 1;
             pa.prev_iresult = ws->prev_ires;
             pa.prev_rowperm = ws->perm_rp;
             pa.prev_colperm = ws->perm_cp;
-            pa.prev_token = w.token_base + (unsigned)(k - 1);
+            pa.prev_token = w.token_base + (unsigned)(k - k0 - 1);
         }
-        if (w.lean_prep) {
-            if (tid < 64) walk_prep_wave0<FORWARD>(cw, ws, b, pa.prev_b, pa.prev_token, k < nb, w.phase_ticks);
+        if (k == k0 && behind) { // (the host plans a segment with lean_prep only)
+            if (tid < 64) walk_prep_wave0<FORWARD, true>(cw, ws, b, FORWARD ? b - 1 : b + 1, w.prev_token, true, w.phase_ticks, &pg);
+        } else if (w.lean_prep) {
+            if (tid < 64) walk_prep_wave0<FORWARD>(cw, ws, b, pa.prev_b, pa.prev_token, k < k1, w.phase_ticks);
         } else {
             chain_prep_body(cw, pa, w.phase_ticks, ws);
         }
         walk_phase_barrier(!w.lean_prep);
         phase(0);
-        if (k == nb) break;
+        if (k == k1) break;
         // ---- the candidate matrix: pi[j * nd + i] = f(dependent i, independent j) ----
         const int d0 = ws->dims[b * 4], d1 = ws->dims[b * 4 + 1], poisoned = ws->dims[b * 4 + 2];
         const int nd = FORWARD ? d0 : d1, ni = FORWARD ? d1 : d0;
@@ -747,7 +784,7 @@ __global__ void __launch_bounds__(WALK_T) chain_walk_kernel(ChainCommon c, FnDev
         phase(1);
         // ---- the factorisation: wave 0 (rows = the dependent side in both directions); the other waves fetch the next bond's
         // static inputs meanwhile (its slot held the previous bond's lists: the gather of this bond was their last reader) ----
-        if (tid >= 64 && k + 1 < nb) walk_prefetch(c, ws, FORWARD ? b + 1 : b - 1, 64, (int)blockDim.x - 64);
+        if (tid >= 64 && k + 1 < k1) walk_prefetch(c, ws, FORWARD ? b + 1 : b - 1, 64, (int)blockDim.x - 64);
         if (tid < 64) {
             int npiv = -2;
             char* blk = w.blocks + (size_t)b * w.block_bytes;
@@ -773,7 +810,7 @@ __global__ void __launch_bounds__(WALK_T) chain_walk_kernel(ChainCommon c, FnDev
                 a.dresult = reinterpret_cast<double*>(blk);
                 a.pivot_vals = reinterpret_cast<double*>(blk + w.off_piv);
                 a.keys = nullptr;
-                a.salt = w.token_base + (unsigned)k;
+                a.salt = w.token_base + (unsigned)(k - k0);
                 a.spec_frac = 0.0;
                 a.stamps = nullptr;
                 a.h_block = nullptr;
@@ -802,17 +839,31 @@ __global__ void __launch_bounds__(WALK_T) chain_walk_kernel(ChainCommon c, FnDev
                 ws->prev_ires[0] = npiv >= 0 ? npiv : 0;
                 ws->prev_ires[1] = npiv >= 0 ? 0 : 1;
                 ws->prev_ires[2] = 0;
-                ws->prev_ires[3] = npiv >= 0 ? (int)(w.token_base + (unsigned)k) : 0;
+                ws->prev_ires[3] = npiv >= 0 ? (int)(w.token_base + (unsigned)(k - k0)) : 0;
             }
         }
         walk_phase_barrier(!w.lean_prep);
         phase(2);
     }
     // ---- the host's copies, in bulk (chain_mirror_body): tables into the pinned mirror, dimensions into global memory and hdims ----
-    for (int e = tid; e < nb * 4; e += (int)blockDim.x) c.dims[e] = ws->dims[e];
+    for (int e = b_lo * 4 + tid; e < b_hi * 4; e += (int)blockDim.x) c.dims[e] = ws->dims[e];
+    if (!ends) {
+        // a launched bond follows: its preparation gathers the pivots of this walk's last bond from that bond's result block and lists
+        // as behind any launched bond — the dependent list is the one thing the walk kept to itself
+        const int bl = FORWARD ? k1 - 1 : nb - k1;
+        int nd = ws->dims[bl * 4 + 2] != 0 ? 0 : ws->dims[bl * 4 + (FORWARD ? 0 : 1)];
+        nd = nd < 0 ? 0 : (nd > WALK_MAX_LIST ? WALK_MAX_LIST : nd);
+        if (nd > c.dep_cap) nd = 0;
+        for (int e = tid; e < nd * (1 + c.K); e += (int)blockDim.x) {
+            if (e < nd) c.dep_code[e] = ws->dep_code[e];
+            else c.dep_acc[e - nd] = ws->dep_acc[e - nd];
+        }
+    }
     __threadfence(); // (the copy below reads counts and dimensions with device-scope loads: every store of the walk is out first)
     __syncthreads();
-    chain_mirror_body(c, nb);
+    // the tables this walk gathered into: the bond in front (if any) and its own bonds but the last one, which is gathered here only when the half-sweep ends
+    const int gk0 = behind ? k0 - 1 : k0, gk1 = ends ? k1 : k1 - 1;
+    chain_mirror_body(c, FORWARD ? gk0 : nb - gk1, FORWARD ? gk1 : nb - gk0, b_lo, b_hi);
     if (w.phase_ticks && tid == 0) {
         for (int i = 0; i < 3; ++i) w.phase_ticks[i] = ph[i];
         w.phase_ticks[3] = wall_clock64() - ph_t0;

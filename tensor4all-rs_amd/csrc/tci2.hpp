@@ -37,6 +37,17 @@ struct TCI2Options { // tensorci2.rs:73-170
     void validate() const;
 };
 
+// The split of a launched half-sweep (tci2_chain.hip): maximal runs of consecutive positions of the sweep order.  A run is WALKED — one
+// chain_walk_kernel launch for all its bonds — when every bond b = order[k] in it has dep_ub[b] <= CHAIN_WALK_MAX_DEP and
+// ind_ub[b] <= CHAIN_WALK_MAX_IND (what the one-wave kernel of the persistent half-sweep takes); every other bond keeps its launch
+// pair.  Pure: bounds (indexed by bond) and order in, runs out, in sweep order, covering 0 .. n_bonds - 1 exactly once.
+constexpr size_t CHAIN_WALK_MAX_DEP = 64, CHAIN_WALK_MAX_IND = 32;
+struct ChainSegment {
+    size_t first, count; // positions first .. first + count - 1 of the sweep order
+    bool walked;
+};
+std::vector<ChainSegment> chain_plan_segments(const size_t* dep_ub, const size_t* ind_ub, const size_t* order, size_t n_bonds);
+
 struct FromTensorTrainOptions { // tensorci/src/conversion.rs:20-36
     double tolerance = 1e-12;
     size_t max_bond_dim = 0; // 0 == None
@@ -180,6 +191,9 @@ public:
     // chain_walk_kernel) [1] 1-site sweeps (sweep1site) that ran as a chain [2] 1-site sweeps that were not eligible and ran bond
     // by bond [3] chained 1-site sweeps that fell back to the per-bond path part-way
     std::array<uint64_t, 4> chain_stats_ext{{0, 0, 0, 0}};
+    // walked segments inside LAUNCHED chains (chain_plan_segments): [0] segments [1] bonds in them.  A half-sweep that is one walk
+    // counts in chain_stats_ext[0] and not here.
+    std::array<uint64_t, 2> chain_segments{{0, 0}};
     const uint64_t* fill_stats() const { return fill_.stats; } // [fills issued asynchronously, graph replays, graph captures]
     const RookWork& rook_work() const { return rook_work_; }
     bool chain_enabled = true;  // false: every half-sweep runs bond by bond (A/B measurements, tests)
@@ -361,6 +375,7 @@ private:
         bool last_core_launched = false, last_core_ok = false; // forward 1-site chain: the last site's tensor was evaluated behind the chain / the whole chain completed, it is valid
         DevBuf<unsigned long long> walk_dbg; // diagnostic phase times of the persistent half-sweep (T4A_WALK_DEBUG)
         bool walked = false;         // the chain in flight is a persistent half-sweep
+        std::vector<char> seg_walked; // per bond: it ran inside a walk (the whole half-sweep or a segment of a launched chain)
         bool prep_dbg = false;       // ... or a launched chain whose preparation kernels stamp their phases (T4A_PREP_DEBUG)
         unsigned walk_token = 1;     // completion tokens of the persistent half-sweep (bond k of a walk: base + k)
         RrluBlock proto;

@@ -48,6 +48,20 @@ std::atomic<int> g_chains_inflight{0};
 } // namespace
 thread_local double g_chain_wait_seconds = 0.0; // time chain_finish spent waiting for the device (T4A_GROUP_PROF, tci2.hip)
 
+std::vector<ChainSegment> chain_plan_segments(const size_t* dep_ub, const size_t* ind_ub, const size_t* order, size_t n_bonds)
+{
+    std::vector<ChainSegment> segs;
+    for (size_t k = 0; k < n_bonds; ++k) {
+        const size_t b = order[k];
+        const bool walked = dep_ub[b] <= CHAIN_WALK_MAX_DEP && ind_ub[b] <= CHAIN_WALK_MAX_IND;
+        if (!segs.empty() && segs.back().walked == walked)
+            ++segs.back().count;
+        else
+            segs.push_back(ChainSegment{k, 1, walked});
+    }
+    return segs;
+}
+
 bool Tci2::chain_usable(const TCI2Options& options) const
 {
     static const bool off = std::getenv("T4A_NO_CHAIN") != nullptr;
@@ -283,11 +297,22 @@ bool Tci2::chain_enqueue(bool forward, const TCI2Options& options, long ext_idx,
     std::vector<size_t> dep_ub(nb), ind_ub(nb), lda_ub(nb, 0);
     std::vector<RrluRoute> plans(nb);
     size_t Mcap = 1, Ncap = 1, steps_cap = 1, pi_cap = 0, spec_cap = 0, dep_cap = 1, ind_cap = 1;
+    // The rows of bond b are distinct multi-indices over sites 0 .. b, its columns over sites b + 1 .. n - 1 (a Kronecker product of a
+    // set, joined by the extras that are not in it): neither side has more entries than its index space.  Near the ends of a chain
+    // that is far below "set size times local dimension plus extras", and it keeps the end bonds within what a walk takes.
+    std::vector<size_t> space_l(nb, 1), space_r(nb, 1);
+    if (!one) {
+        const size_t big = (size_t)1 << 40;
+        size_t acc = 1;
+        for (size_t b = 0; b < nb; ++b) space_l[b] = acc = std::min(big, acc * local_dims[b]);
+        acc = 1;
+        for (size_t b = nb; b-- > 0;) space_r[b] = acc = std::min(big, acc * local_dims[b + 1]);
+    }
     for (size_t k = 0; k < nb; ++k) {
         const size_t b = order[k];
         // (1-site sweep: the independent side is J_b / I_{b+1} itself, tensorci2.rs:931-944)
-        const size_t Mub = one ? (forward ? cI[b] * local_dims[b] : cI[b + 1]) : cI[b] * local_dims[b] + eI[b + 1];
-        const size_t Nub = one ? (forward ? cJ[b] : cJ[b + 1] * local_dims[b + 1]) : cJ[b + 1] * local_dims[b + 1] + eJ[b];
+        const size_t Mub = one ? (forward ? cI[b] * local_dims[b] : cI[b + 1]) : std::min(cI[b] * local_dims[b] + eI[b + 1], space_l[b]);
+        const size_t Nub = one ? (forward ? cJ[b] : cJ[b + 1] * local_dims[b + 1]) : std::min(cJ[b + 1] * local_dims[b + 1] + eJ[b], space_r[b]);
         const size_t rub = std::max<size_t>(std::min({Mub, Nub, chi}), 1);
         cI[b + 1] = rub; // bond b writes I_{b+1} and J_b
         cJ[b] = rub;
@@ -514,15 +539,33 @@ void Tci2::chain_launch()
         unsigned* tile_counters = reinterpret_cast<unsigned*>(chain_.dims.get() + nb * 4);
         const bool solo = g_chains_inflight.fetch_add(1) == 0;
         counted = true;
-        // every matrix of the half-sweep fits the one-wave kernel: ONE persistent workgroup walks the bonds (kernels_chain.hip)
+        // every matrix of the half-sweep fits the one-wave kernel (64 x 32; wider, the launched chain's one-workgroup kernel beats one
+        // wave): ONE persistent workgroup walks the bonds (kernels_chain.hip).  Where only some do — the two ends of every chain whose
+        // middle ranks pass 32 — each maximal run of them is one walk, a SEGMENT, between the launch pairs of the wide bonds: a small bond
+        // costs a walk ~1 us per pivot step, a launch pair its prologue, election, device-side reads of the dimensions and end-of-kernel
+        // release on top.  No segments in 1-site sweeps and group chains, none with event timing; T4A_NO_WALK switches them off with the walk.
         static const bool no_walk = std::getenv("T4A_NO_WALK") != nullptr;
-        size_t walk_cols = 0;
-        bool walk = !no_walk && !timed_events && nb <= 128; // (128: WALK_MAX_BONDS, kernels_chain.hip)
-        for (size_t b = 0; walk && b < nb; ++b) {
-            walk = dep_ub[b] <= 64 && ind_ub[b] <= 32; // (wider: the launched chain's one-workgroup kernel beats one wave)
-            walk_cols = std::max(walk_cols, ind_ub[b]);
+        const bool may_walk = !no_walk && !timed_events && nb <= 128; // (128: WALK_MAX_BONDS, kernels_chain.hip)
+        std::vector<ChainSegment> segs;
+        if (may_walk) segs = chain_plan_segments(dep_ub.data(), ind_ub.data(), order.data(), nb);
+        const bool walk = may_walk && (nb == 0 || (segs.size() == 1 && segs[0].walked));
+        std::vector<char> walked_k(nb, walk ? 1 : 0); // per position of the sweep order: inside a walk
+        if (may_walk && !walk && !chain_.one_site)
+            for (const ChainSegment& s : segs)
+                for (size_t k = s.first; s.walked && k < s.first + s.count; ++k) walked_k[k] = 1;
+        chain_.seg_walked.assign(nb, 0);
+        for (size_t k = 0; k < nb; ++k) chain_.seg_walked[order[k]] = walked_k[k];
+        static const bool plan_dbg = std::getenv("T4A_CHAIN_DEBUG") != nullptr;
+        if (plan_dbg) {
+            std::fprintf(stderr, "[t4a chain] %s half-sweep, %zu bonds, dependent x independent bounds in sweep order (w: walked):", forward ? "forward" : "backward", nb);
+            for (size_t k = 0; k < nb; ++k) std::fprintf(stderr, " %zux%zu%s", dep_ub[order[k]], ind_ub[order[k]], walked_k[k] ? "w" : "");
+            std::fprintf(stderr, "\n");
         }
-        if (walk) {
+        // one walk over positions first .. first + count - 1 (the whole half-sweep, or a segment between launched bonds)
+        auto launch_walk = [&](size_t first, size_t count) {
+            size_t walk_cols = 0;
+            for (size_t k = first; k < first + count; ++k) walk_cols = std::max(walk_cols, ind_ub[order[k]]);
+            const bool whole = count == nb;
             ChainWalkArgs w;
             std::memset(&w, 0, sizeof(w));
             w.blocks = chain_.blocks.get();
@@ -540,20 +583,36 @@ void Tci2::chain_launch()
             w.factors_stride = chain_.factors_stride;
             if (chain_.walk_token > 0xFFFF0000u || chain_.walk_token == 0u) chain_.walk_token = 1u;
             w.token_base = chain_.walk_token;
-            chain_.walk_token += (unsigned)nb;
+            chain_.walk_token += (unsigned)count;
+            w.k_first = (int)first;
+            w.k_count = (int)count;
+            if (first > 0) { // behind a launched bond: its result block, as the preparation of a launched bond gets it
+                const size_t pb = order[first - 1];
+                const RrluBlock pblk = block_of(pb);
+                w.prev_iresult = pblk.iresult();
+                w.prev_rowperm = pblk.row_perm();
+                w.prev_colperm = pblk.col_perm();
+                w.prev_token = tokens[pb];
+            }
             w.timed = chain_.timed ? 1 : 0;
             w.lean_prep = 1;
             static const bool walk_dbg = std::getenv("T4A_WALK_DEBUG") != nullptr;
-            if (walk_dbg) {
+            if (walk_dbg && whole) {
                 chain_.walk_dbg.reserve(8);
                 T4A_HIP(hipMemsetAsync(chain_.walk_dbg.get(), 0, 8 * sizeof(unsigned long long), st));
                 w.phase_ticks = chain_.walk_dbg.get();
             }
-            chain_.walked = true;
-            for (size_t k = 0; k < nb; ++k) tokens[order[k]] = w.token_base + (unsigned)k;
+            for (size_t k = 0; k < count; ++k) tokens[order[first + k]] = w.token_base + (unsigned)k;
             chain_walk_launch(c, fn_.dev, w, (int)walk_cols, st);
-            ++chain_stats_ext[0];
-        }
+            if (whole) {
+                chain_.walked = true;
+                ++chain_stats_ext[0];
+            } else {
+                ++chain_segments[0];
+                chain_segments[1] += count;
+            }
+        };
+        if (walk) launch_walk(0, nb);
         static const bool want_prep_dbg = std::getenv("T4A_PREP_DEBUG") != nullptr; // phase times of the preparation kernels of this chain
         unsigned long long* prep_dbg = nullptr;
         if (want_prep_dbg && !walk) {
@@ -564,6 +623,14 @@ void Tci2::chain_launch()
         }
         bool spec_pending = false; // the previous bond's launch evaluates this bond's candidate matrix
         for (size_t k = 0; !walk && k < nb; ++k) {
+            if (walked_k[k]) { // a segment: one launch for the whole run (its first bond has no speculative matrix to use, its last starts none)
+                size_t count = 1;
+                while (k + count < nb && walked_k[k + count]) ++count;
+                launch_walk(k, count);
+                k += count - 1;
+                spec_pending = false;
+                continue;
+            }
             const size_t b = order[k];
             const RrluRoute& pl = plans[b];
             const bool fused = pl.fused;
@@ -593,7 +660,7 @@ void Tci2::chain_launch()
             XcdSpecArgs sp;
             std::memset(&sp, 0, sizeof(sp));
             spec_pending = false;
-            if (solo && k + 1 < nb && pl.on_xcd()) {
+            if (solo && k + 1 < nb && !walked_k[k + 1] && pl.on_xcd()) { // (a walked bond evaluates its own matrix)
                 const size_t nx = order[k + 1];
                 if (!plans[nx].fused) {
                     const size_t site = forward ? nx : nx + 1;
@@ -625,7 +692,7 @@ void Tci2::chain_launch()
                                        chain_.factors_stride ? chain_.factors.get() + b * chain_.factors_stride : nullptr, chain_.urows.get());
             if (timed_events) T4A_HIP(hipEventRecord(chain_.t1[b], st));
         }
-        if (!walk) { // the pivots of the last bond
+        if (nb > 0 && !walked_k[nb - 1]) { // the pivots of the last bond (a walk that ends the half-sweep gathered them itself)
             const size_t pb = order[nb - 1];
             const RrluBlock pblk = block_of(pb);
             ChainPrepArgs pa;
@@ -820,6 +887,7 @@ void Tci2::chain_group_launch(const std::vector<Tci2*>& hs)
     }
     for (Tci2* h : hs) {
         h->chain_.plans = gplans;
+        h->chain_.seg_walked.clear(); // (a group chain walks nothing)
         h->chain_.inflight = true;
         h->chain_.wait_stream = st;
         h->chain_.group_role = h == lead ? 1 : 2;
@@ -1077,8 +1145,10 @@ void Tci2::chain_finish(const TCI2Options& options)
     chain_.tables_valid = false;
     // (only the kernels that ASSUME a placement: the one-workgroup / one-wave plans are booked as kind 2 as well but elect nobody — ADVICE round 4)
     if (failed_timeout) {
-        const RrluKind kind = chain_.plans[chain_.order[(size_t)failed_k]].kind;
-        if (kind == RrluKind::SingleXcd || kind == RrluKind::MultiXcd) xcd_disable();
+        const size_t fb = chain_.order[(size_t)failed_k];
+        const RrluKind kind = chain_.plans[fb].kind;
+        const bool in_walk = fb < chain_.seg_walked.size() && chain_.seg_walked[fb]; // (a walked bond never ran its plan: it elected nobody)
+        if (!in_walk && (kind == RrluKind::SingleXcd || kind == RrluKind::MultiXcd)) xcd_disable();
     }
     prep_.valid = false;
     prefetch_.wanted = false;

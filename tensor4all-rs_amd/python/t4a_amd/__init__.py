@@ -889,6 +889,33 @@ class TensorCI2:
                     group_half_sweeps=int(out[4]), walked_sweeps=int(ext[0]), one_site_sweeps=int(ext[1]),
                     one_site_not_eligible=int(ext[2]), one_site_fell_back=int(ext[3]))
 
+    def chain_segments(self):
+        """Walked segments inside LAUNCHED chains (t4a_gpu_tci2_chain_segments): dict(segments, bonds) since the handle was created — the
+        runs of consecutive bonds of at most 64 x 32 at the ends of a half-sweep whose middle is wider, each one persistent workgroup.
+        A half-sweep that is one walk as a whole counts in chain_stats()["walked_sweeps"] and not here."""
+        out = np.zeros(2, dtype=np.uint64)
+        _check(_lib.t4a_gpu_tci2_chain_segments(self._h, _p(out)))
+        return dict(segments=int(out[0]), bonds=int(out[1]))
+
+
+def chain_plan_segments(dep_ub, ind_ub, order):
+    """The split of a launched half-sweep (t4a_gpu_tci2_chain_plan_segments, host only): upper bounds of the dependent and the
+    independent side per bond and the bond at every position of the sweep -> [(first, count, walked)], maximal runs of positions; a
+    run is walked when every bond in it has dep_ub <= 64 and ind_ub <= 32."""
+    dep = np.ascontiguousarray(dep_ub, dtype=np.uintp)
+    ind = np.ascontiguousarray(ind_ub, dtype=np.uintp)
+    order = np.ascontiguousarray(order, dtype=np.uintp)
+    nb = int(order.size)
+    if dep.size != nb or ind.size != nb:
+        raise T4aError(INVALID_ARGUMENT, "chain_plan_segments: dep_ub, ind_ub and order have one entry per bond")
+    ptr = (lambda a: _p(a) if nb else None)
+    n = ctypes.c_size_t(0)
+    _check(_lib.t4a_gpu_tci2_chain_plan_segments(ptr(dep), ptr(ind), ptr(order), ctypes.c_size_t(nb), ctypes.c_size_t(0), None, None, None, ctypes.byref(n)))
+    k = n.value
+    first, count, walked = np.zeros(max(k, 1), dtype=np.uintp), np.zeros(max(k, 1), dtype=np.uintp), np.zeros(max(k, 1), dtype=np.int32)
+    _check(_lib.t4a_gpu_tci2_chain_plan_segments(ptr(dep), ptr(ind), ptr(order), ctypes.c_size_t(nb), ctypes.c_size_t(k), _p(first), _p(count), _p(walked), ctypes.byref(n)))
+    return [(int(first[s]), int(count[s]), bool(walked[s])) for s in range(k)]
+
 
 def optimize_group(tcis, options, final_sweep1site=True):
     """optimize() on up to eight TensorCI2 handles at once, in lock-step from this thread (one XCD per handle): the per-GPU form
