@@ -1691,6 +1691,62 @@ t4a_gpu_status t4a_gpu_pmpo_time_contract(const t4a_gpu_pmpo* a, const t4a_gpu_p
                                           double* ms3);
 
 /* =====================================================================================
+ * The compress stage as an operation of its own, and for many MPOs in lock step
+ * This project's (the reference reaches compress_mpo, contract_naive.rs:100-172, only through contract_naive).
+ * _mpo_compress: the stage of t4a_gpu_mpo_contract on a copy of one MPO: right-canonicalisation by thin QR, then the left-to-right SVD
+ * sweep keeping s >= tolerance * s_max, at most max_bond_dim (0 = no cap), at least one; U[:, :rank] stays, diag(S) Vt goes into the
+ * next site.  The operand is untouched; fewer than two sites give a copy.
+ * _mpo_compress_many: the same result for `count` MPOs of the same number of sites (site dims and bonds may differ), out[k] for mpos[k].
+ * An item is inside the ENVELOPE when, after the bound the shapes give (k_n = 1, k_i = min(l_i, s1_i s2_i k_{i+1}) from the right), every
+ * bond is at most T4A_GPU_COMPRESS_MANY_BMAX = 64.  route BATCHED sends every item inside the envelope through the batched site-step
+ * kernels: one workgroup per item, n - 1 right-step launches and n - 1 left-step launches for the whole call whatever `count` is, no
+ * host synchronisation inside a sweep and ONE per call; every other item takes the serial stage of _mpo_compress in the same call.
+ * SERIAL takes the serial stage for every item (the bits of _mpo_compress).  AUTO is BATCHED when no bond k_i of the items inside the
+ * envelope is above 16 or when at least 16 items are inside it, else SERIAL (the measured rule).  Ranks, the dense
+ * operator (to the tolerance) and the left-orthogonality of the sites 0 .. n-2 are those of the serial stage; the gauge (signs,
+ * rotations inside degenerate subspaces) is not.  A zero matrix is forced to rank 1 with a unit column in U and a zero right factor.
+ * Two calls give the same bits, and an item's bits do not depend on the other items of the call.
+ * INVALID_ARGUMENT: count == 0 ("compress_many: the list is empty"), items of different length ("compress_many: item <k> has <a> sites,
+ * item 0 has <b>"), an unknown route — all before the device is touched; a non-finite value: "compress_many: item <k>: SVD computation
+ * failed: non-finite input" with the lowest such k, and every out[k] stays NULL.  NULL_POINTER: a null list or item.
+ * _counted: as _compress_many; counts4 (may be NULL) receives what the driver counted for the batched part — kernel launches, stream
+ * synchronisations — and the number of items on the batched and on the serial route.  Outside that count: the call synchronises every
+ * operand's own stream before it reads it, and items on the serial stage synchronise as that stage does.
+ * RSVD is NOT_IMPLEMENTED up front on every route here (t4a_gpu_pmpo_contract_routed passes a method), also for chains of fewer than
+ * two sites, which the serial stage of t4a_gpu_mpo_contract copies without reaching its factorisation; on the BATCHED and AUTO routes
+ * of t4a_gpu_pmpo_contract_routed an error of the compress stage reads "compress_many: item <task>: ..." .
+ * _plan (host only, no device needed): item k has n_sites[k] sites, dims4 holds (l, s1, s2, r) of all sites of all items one after the
+ * other.  batched[count]: 1 = the kernels, 0 = the serial stage; bonds / qr_bonds: n_sites[k] + 1 values per item, the bounds of the
+ * result's bonds (k_i, the rank bound min(l s, r) and the cap, from the left) and the bonds after the right sweep (k_i, exact); counts3:
+ * launches and synchronisations of the batched part (2 (n - 1) and 1; 0 and 0 when nothing is batched) and the number of batched items.
+ * Any output may be NULL.  Refuses what _compress_many refuses, and shapes t4a_gpu_mpo_new refuses ("compress_many: item <k>: ...").
+ * What stays serial: zip-up (its SVDs interleave with its products), the add_truncate of partitioned results that share a projector,
+ * and items outside the envelope. */
+#define T4A_GPU_COMPRESS_AUTO 0
+#define T4A_GPU_COMPRESS_BATCHED 1
+#define T4A_GPU_COMPRESS_SERIAL 2
+#define T4A_GPU_COMPRESS_MANY_BMAX 64
+t4a_gpu_status t4a_gpu_mpo_compress(const t4a_gpu_mpo* mpo, double tolerance, size_t max_bond_dim, t4a_gpu_mpo** out);
+t4a_gpu_status t4a_gpu_mpo_compress_many(const t4a_gpu_mpo* const* mpos, size_t count, double tolerance, size_t max_bond_dim, int32_t route,
+                                         t4a_gpu_mpo** out);
+t4a_gpu_status t4a_gpu_mpo_compress_many_counted(const t4a_gpu_mpo* const* mpos, size_t count, double tolerance, size_t max_bond_dim,
+                                                 int32_t route, t4a_gpu_mpo** out, size_t* counts4);
+t4a_gpu_status t4a_gpu_mpo_compress_many_plan(const size_t* dims4, const size_t* n_sites, size_t count, double tolerance, size_t max_bond_dim,
+                                              int32_t route, int32_t* batched, size_t* bonds, size_t* qr_bonds, size_t* counts3);
+/* Probe (tools/probe_compress_many.py): wall ms per repetition, each ending synced, of the compress stage on copies of the same chains:
+ * ms2[0] item by item on the serial stage, ms2[1] one call on the batched route; the two alternate, one warm-up round of each first. */
+t4a_gpu_status t4a_gpu_mpo_time_compress_many(const t4a_gpu_mpo* const* mpos, size_t count, double tolerance, size_t max_bond_dim, size_t reps,
+                                              double* ms2);
+/* t4a_gpu_pmpo_contract with the route of its compress stage (Naive with compress != 0): SERIAL is t4a_gpu_pmpo_contract, bit for bit;
+ * BATCHED and AUTO hand the products of ALL tasks to one _mpo_compress_many call.  ZipUp with BATCHED is INVALID_ARGUMENT.  The
+ * add_truncate of results that share a projector is serial on every route.  _time_compress: _mpo_time_compress_many on the task
+ * products of a·b. */
+t4a_gpu_status t4a_gpu_pmpo_contract_routed(const t4a_gpu_pmpo* a, const t4a_gpu_pmpo* b, int32_t algorithm, int32_t compress, int32_t method,
+                                            double tolerance, size_t max_bond_dim, int32_t route, t4a_gpu_pmpo** out);
+t4a_gpu_status t4a_gpu_pmpo_time_compress(const t4a_gpu_pmpo* a, const t4a_gpu_pmpo* b, double tolerance, size_t max_bond_dim, size_t reps,
+                                          double* ms2);
+
+/* =====================================================================================
  * swap_site_indices on a chain: which site holds which site index
  * tensor4all-treetn/src/treetn/swap.rs (SwapOptions, ScheduledSwapStep, SwapSchedule::build), treetn/mod.rs (swap_on_edge,
  * swap_site_indices), for f64 and by position.

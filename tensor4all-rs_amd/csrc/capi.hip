@@ -5599,6 +5599,139 @@ t4a_gpu_status t4a_gpu_pmpo_time_contract(const t4a_gpu_pmpo* a, const t4a_gpu_p
     });
 }
 
+// ---- the compress stage as an operation of its own, and for many MPOs in lock step (batch_compress.hpp) ----
+namespace {
+CompressRoute compress_route(int32_t route)
+{
+    if (route < 0 || route > 2) throw Error(T4A_GPU_INVALID_ARGUMENT, "unknown compress route");
+    return (CompressRoute)route;
+}
+std::vector<Mpo*> mpo_list(const t4a_gpu_mpo* const* mpos, size_t count, const char* what)
+{
+    if (count == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, std::string(what) + ": the list is empty");
+    T4A_REQUIRE_PTR(mpos);
+    std::vector<Mpo*> items(count);
+    for (size_t k = 0; k < count; ++k) {
+        if (!mpos[k]) throw Error(T4A_GPU_NULL_POINTER, std::string(what) + ": item " + std::to_string(k) + " is null");
+        items[k] = mpos[k]->impl.get();
+    }
+    return items;
+}
+} // namespace
+
+t4a_gpu_status t4a_gpu_mpo_compress(const t4a_gpu_mpo* mpo, double tolerance, size_t max_bond_dim, t4a_gpu_mpo** out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(mpo);
+        T4A_REQUIRE_PTR(out);
+        *out = nullptr;
+        *out = new t4a_gpu_mpo{mpo_compress(*mpo->impl, pmpo_options(tolerance, max_bond_dim, 0))};
+    });
+}
+
+t4a_gpu_status t4a_gpu_mpo_compress_many_counted(const t4a_gpu_mpo* const* mpos, size_t count, double tolerance, size_t max_bond_dim,
+                                                 int32_t route, t4a_gpu_mpo** out, size_t* counts4)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(out);
+        for (size_t k = 0; k < count; ++k) out[k] = nullptr;
+        const CompressRoute r = compress_route(route);
+        const std::vector<Mpo*> items = mpo_list(mpos, count, "compress_many");
+        CompressManyStats st;
+        std::vector<std::unique_ptr<Mpo>> res = mpo_compress_many(items, pmpo_options(tolerance, max_bond_dim, 0), r, &st);
+        std::vector<t4a_gpu_mpo*> handles;
+        for (auto& m : res) handles.push_back(new t4a_gpu_mpo{std::move(m)});
+        for (size_t k = 0; k < count; ++k) out[k] = handles[k];
+        if (counts4) {
+            counts4[0] = st.launches;
+            counts4[1] = st.syncs;
+            counts4[2] = st.n_batched;
+            counts4[3] = st.n_serial;
+        }
+    });
+}
+
+t4a_gpu_status t4a_gpu_mpo_compress_many(const t4a_gpu_mpo* const* mpos, size_t count, double tolerance, size_t max_bond_dim, int32_t route,
+                                         t4a_gpu_mpo** out)
+{
+    return t4a_gpu_mpo_compress_many_counted(mpos, count, tolerance, max_bond_dim, route, out, nullptr);
+}
+
+t4a_gpu_status t4a_gpu_mpo_compress_many_plan(const size_t* dims4, const size_t* n_sites, size_t count, double tolerance, size_t max_bond_dim,
+                                              int32_t route, int32_t* batched, size_t* bonds, size_t* qr_bonds, size_t* counts3)
+{
+    return guarded([&] {
+        const CompressRoute r = compress_route(route);
+        if (count == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "compress_many: the list is empty");
+        T4A_REQUIRE_PTR(n_sites);
+        std::vector<std::vector<std::array<size_t, 4>>> shapes(count);
+        size_t at = 0;
+        for (size_t k = 0; k < count; ++k) {
+            if (n_sites[k]) T4A_REQUIRE_PTR(dims4);
+            for (size_t i = 0; i < n_sites[k]; ++i, ++at) shapes[k].push_back({dims4[4 * at], dims4[4 * at + 1], dims4[4 * at + 2], dims4[4 * at + 3]});
+        }
+        const CompressManyPlan p = compress_many_plan(shapes, pmpo_options(tolerance, max_bond_dim, 0), r);
+        size_t ob = 0;
+        for (size_t k = 0; k < count; ++k) {
+            if (batched) batched[k] = p.batched[k];
+            for (size_t i = 0; i < p.bonds[k].size(); ++i, ++ob) {
+                if (bonds) bonds[ob] = p.bonds[k][i];
+                if (qr_bonds) qr_bonds[ob] = p.qr_bonds[k][i];
+            }
+        }
+        if (counts3) {
+            counts3[0] = p.launches;
+            counts3[1] = p.syncs;
+            counts3[2] = p.n_batched;
+        }
+    });
+}
+
+t4a_gpu_status t4a_gpu_mpo_time_compress_many(const t4a_gpu_mpo* const* mpos, size_t count, double tolerance, size_t max_bond_dim, size_t reps,
+                                              double* ms2)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(ms2);
+        const std::vector<Mpo*> items = mpo_list(mpos, count, "time_compress_many");
+        for (Mpo* m : items)
+            if (m->len() != items[0]->len()) throw Error(T4A_GPU_INVALID_ARGUMENT, "time_compress_many: the items differ in length");
+        Engine& eng = items[0]->tt.eng;
+        std::vector<std::vector<DevCore>> chains;
+        for (Mpo* m : items) {
+            m->tt.eng.sync();
+            chains.push_back(clone_cores(m->tt.cores, eng.stream()));
+        }
+        eng.sync();
+        compress_many_time(eng, chains, pmpo_options(tolerance, max_bond_dim, 0), reps, ms2);
+    });
+}
+
+t4a_gpu_status t4a_gpu_pmpo_contract_routed(const t4a_gpu_pmpo* a, const t4a_gpu_pmpo* b, int32_t algorithm, int32_t compress, int32_t method,
+                                            double tolerance, size_t max_bond_dim, int32_t route, t4a_gpu_pmpo** out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(a);
+        T4A_REQUIRE_PTR(b);
+        T4A_REQUIRE_PTR(out);
+        *out = nullptr;
+        if (algorithm < 0 || algorithm > 2) throw Error(T4A_GPU_INVALID_ARGUMENT, "unknown contraction algorithm");
+        const CompressRoute r = compress_route(route);
+        const MpoContractionOptions o = pmpo_options(tolerance, max_bond_dim, method);
+        *out = new t4a_gpu_pmpo{a->impl->contract(*b->impl, (MpoAlgorithm)algorithm, compress != 0, o, r)};
+    });
+}
+
+t4a_gpu_status t4a_gpu_pmpo_time_compress(const t4a_gpu_pmpo* a, const t4a_gpu_pmpo* b, double tolerance, size_t max_bond_dim, size_t reps,
+                                          double* ms2)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(a);
+        T4A_REQUIRE_PTR(b);
+        T4A_REQUIRE_PTR(ms2);
+        pmpo_time_compress(*a->impl, *b->impl, pmpo_options(tolerance, max_bond_dim, 0), reps, ms2);
+    });
+}
+
 // ---- swap_site_indices on a chain (swap.hpp) ----
 namespace {
 SiteLegs site_legs(size_t n, const size_t* leg_counts, const int64_t* keys, const size_t* dims)

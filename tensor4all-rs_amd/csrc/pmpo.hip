@@ -441,9 +441,13 @@ std::unique_ptr<Mpo> PartitionedMpo::to_mpo(int route)
     return std::make_unique<Mpo>(std::move(out), sd);
 }
 
-std::unique_ptr<PartitionedMpo> PartitionedMpo::contract(PartitionedMpo& other, MpoAlgorithm alg, bool compress, const MpoContractionOptions& opt)
+std::unique_ptr<PartitionedMpo> PartitionedMpo::contract(PartitionedMpo& other, MpoAlgorithm alg, bool compress, const MpoContractionOptions& opt,
+                                                         CompressRoute compress_route)
 {
     check_operands(*this, other);
+    if (alg == MpoAlgorithm::ZipUp && compress_route == CompressRoute::Batched)
+        throw Error(T4A_GPU_INVALID_ARGUMENT, "contract: the batched compress route needs the naive algorithm (the SVDs of zip-up interleave with "
+                                              "its products)");
     if (alg == MpoAlgorithm::Fit) // contract_fit.rs:65-96
         throw Error(T4A_GPU_NOT_IMPLEMENTED, "Unsupported operation: simplett variational MPO fitting is not implemented; use contract_naive or "
                                              "contract_zipup instead");
@@ -499,8 +503,13 @@ std::unique_ptr<PartitionedMpo> PartitionedMpo::contract(PartitionedMpo& other, 
                 off += cores[t][i].size();
             }
         launch_pairs(eng, jobs, off);
+        if (compress && compress_route != CompressRoute::Serial) { // every task product in one call (batch_compress.hpp)
+            std::vector<std::vector<DevCore>*> chains;
+            for (auto& c : cores) chains.push_back(&c);
+            compress_many_cores(eng, chains, opt, compress_route, nullptr);
+        }
         for (size_t t = 0; t < nt; ++t) {
-            if (compress) mpo_compress_cores(eng, cores[t], opt);
+            if (compress && compress_route == CompressRoute::Serial) mpo_compress_cores(eng, cores[t], opt);
             products[t] = std::make_unique<Mpo>(std::move(cores[t]), rsd);
         }
     }
@@ -575,6 +584,28 @@ void pmpo_time_contract(PartitionedMpo& a, PartitionedMpo& b, const MpoContracti
         if (r) total += since(t0); // the first round warms up
     }
     ms[2] = total / reps;
+}
+
+void pmpo_time_compress(PartitionedMpo& a, PartitionedMpo& b, const MpoContractionOptions& opt, size_t reps, double ms[2])
+{
+    check_operands(a, b);
+    const PmpoPlan plan = pmpo_contract_plan(projectors_of(a), projectors_of(b));
+    if (plan.tasks.empty() || a.sd.empty()) throw Error(T4A_GPU_INVALID_ARGUMENT, "pmpo_time_compress: the operands have no task");
+    const size_t n = a.sd.size(), nt = plan.tasks.size();
+    Engine& eng = a.patches[plan.tasks[0].a].mpo->tt.eng;
+    sync_all(a);
+    sync_all(b);
+    std::vector<std::vector<DevCore>> cores(nt);
+    for (auto& c : cores) c.resize(n);
+    std::vector<PmpoPairJob> jobs;
+    unsigned long long off = 0;
+    for (size_t t = 0; t < nt; ++t)
+        for (size_t i = 0; i < n; ++i) {
+            jobs.push_back(pair_job(a.patches[plan.tasks[t].a], b.patches[plan.tasks[t].b], a.sd, b.sd, t, i, cores[t][i], off));
+            off += cores[t][i].size();
+        }
+    launch_pairs(eng, jobs, off);
+    compress_many_time(eng, cores, opt, reps, ms);
 }
 
 void pmpo_pair_products(const size_t* dims, const long long* sel, size_t n_jobs, const double* A, const double* B, double* C)

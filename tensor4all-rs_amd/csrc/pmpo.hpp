@@ -11,7 +11,7 @@
 #include <map>
 #include <utility>
 
-#include "mpo.hpp"
+#include "batch_compress.hpp"
 
 namespace t4a {
 
@@ -77,8 +77,12 @@ public:
     // (pmpo_direct_sum_kernel; the same bits: both copy); route 0: the measured rule, which is route 2 from two sites
     // and two patches up.
     std::unique_ptr<Mpo> to_mpo(int route = 0);
-    // contract (:305-340), arguments and rank rule of mpo_contract
-    std::unique_ptr<PartitionedMpo> contract(PartitionedMpo& other, MpoAlgorithm alg, bool compress, const MpoContractionOptions& opt);
+    // contract (:305-340), arguments and rank rule of mpo_contract.  compress_route (batch_compress.hpp): Serial compresses the task
+    // products one after the other with mpo_compress_cores; Batched and Auto hand all of them to compress_many_cores in one call (Naive
+    // with compress only: ZipUp refuses Batched, its SVDs interleave with its products).  The add_truncate of results that share a
+    // projector stays serial on every route.
+    std::unique_ptr<PartitionedMpo> contract(PartitionedMpo& other, MpoAlgorithm alg, bool compress, const MpoContractionOptions& opt,
+                                             CompressRoute compress_route = CompressRoute::Serial);
 
     SiteDims sd;
     std::vector<PmpoPatch> patches;
@@ -88,6 +92,9 @@ public:
 // composition "mask launch on copies plus one mpo_site_contract launch per task", [2] the compress stage of every task (tolerance and
 // cap of `opt`) on copies of the products.
 void pmpo_time_contract(PartitionedMpo& a, PartitionedMpo& b, const MpoContractionOptions& opt, size_t reps, double ms[3]);
+// Probe hook (tools/probe_compress_many.py): milliseconds per repetition of the compress stage of every task product of a·b, [0] task by
+// task on the serial stage, [1] all tasks in one compress_many_cores call on the batched route; copies of the same products, alternating.
+void pmpo_time_compress(PartitionedMpo& a, PartitionedMpo& b, const MpoContractionOptions& opt, size_t reps, double ms[2]);
 
 // Test hook: the product launch of `n_jobs` sites exactly as contract() issues it, host arrays in and out.  dims is 7 x n_jobs
 // (la, s1, k, ra, lb, t, rb), sel 4 x n_jobs (k0, k1, sm, tm; sm / tm < 0 = no mask), A / B / C the sites concatenated.

@@ -199,6 +199,98 @@ class MPO:
         grid = np.indices(shape[::-1]).reshape(len(shape), -1)[::-1].T  # leftmost fastest
         return self.evaluate(grid.reshape(total, len(shape))).reshape(shape, order="F")
 
+    def compress(self, options=None):
+        """The compress stage of ``contract_naive`` (compress_mpo, contract_naive.rs:100-172) on a copy of this MPO
+        (t4a_gpu_mpo_compress): right-canonicalisation by thin QR, then the left-to-right SVD sweep with the rank rule of ``options``
+        (default ``ContractionOptions()``; the factorize method is SVD).  ``self`` is untouched."""
+        o = ContractionOptions() if options is None else options
+        h = c_void_p()
+        _check(_lib.t4a_gpu_mpo_compress(self._h, c_double(o.tolerance), c_size_t(0 if o.max_bond_dim is None else o.max_bond_dim),
+                                         ctypes.byref(h)))
+        return MPO._adopt(h)
+
+
+COMPRESS_MANY_BMAX = 64  # T4A_GPU_COMPRESS_MANY_BMAX: the largest bond (after the shape-only bound) of a batched item
+_ROUTES = {"auto": 0, "batched": 1, "serial": 2}
+
+
+def _route_code(route):
+    if route not in _ROUTES:
+        raise T4aError(INVALID_ARGUMENT, f"unknown compress route {route!r}: one of 'auto', 'batched', 'serial'")
+    return _ROUTES[route]
+
+
+def _compress_many(mpos, options, route):
+    """(results, counts) with counts = {"launches", "syncs", "n_batched", "n_serial"} as the driver counted them"""
+    mpos = list(mpos)
+    for m in mpos:
+        if not isinstance(m, MPO):
+            raise T4aError(INVALID_ARGUMENT, "compress_many: every item must be an MPO")
+    o = ContractionOptions() if options is None else options
+    code = _route_code(route)
+    arr = (c_void_p * max(len(mpos), 1))(*[m._h for m in mpos])
+    out = (c_void_p * max(len(mpos), 1))()
+    counts = np.zeros(4, dtype=np.uintp)
+    _check(_lib.t4a_gpu_mpo_compress_many_counted(arr, c_size_t(len(mpos)), c_double(o.tolerance),
+                                                  c_size_t(0 if o.max_bond_dim is None else o.max_bond_dim), c_int32(code), out, _p(counts)))
+    res = [MPO._adopt(c_void_p(out[k])) for k in range(len(mpos))]
+    return res, dict(zip(("launches", "syncs", "n_batched", "n_serial"), (int(v) for v in counts)))
+
+
+def compress_many(mpos, options=None, route="auto"):
+    """``[m.compress(options) for m in mpos]`` for MPOs of the same number of sites, in lock step (t4a_gpu_mpo_compress_many).
+    ``route="batched"``: every item whose bonds, after the bound the shapes give, are at most ``COMPRESS_MANY_BMAX`` goes through the
+    batched site-step kernels — one workgroup per item, ``2 (n - 1)`` launches and one host synchronisation for the whole call — and
+    every other item through the serial stage; ``"serial"``: the serial stage for every item (the bits of ``MPO.compress``);
+    ``"auto"``: ``"batched"`` when no bond of the items inside the envelope is above 16 (after the bound of the shapes) or when at
+    least 16 items are inside it, else ``"serial"`` (the measured rule).  Ranks, the dense operator and the left-orthogonality of the sites
+    are those of ``MPO.compress``; the gauge is not.  The operands are untouched."""
+    return _compress_many(mpos, options, route)[0]
+
+
+def compress_many_plan(shapes, options=None, route="auto"):
+    """What ``compress_many`` will do, from shapes alone (t4a_gpu_mpo_compress_many_plan; host only, no device needed).  ``shapes``:
+    per item the list of ``(l, s1, s2, r)`` per site.  Returns ``{"routes": ["batched" | "serial"], "bonds": [...], "qr_bonds": [...],
+    "launches", "syncs", "n_batched"}``: per item the bounds of the result's bonds and the bonds after the right sweep (``n + 1``
+    values each), and the kernel launches and host synchronisations of the batched part of the call."""
+    shapes = [[tuple(int(x) for x in site) for site in item] for item in shapes]
+    for item in shapes:
+        for site in item:
+            if len(site) != 4 or min(site) < 0:
+                raise T4aError(INVALID_ARGUMENT, "compress_many_plan: a site is (l, s1, s2, r)")
+    o = ContractionOptions() if options is None else options
+    code = _route_code(route)
+    flat = [x for item in shapes for site in item for x in site]
+    dims = np.ascontiguousarray(np.array(flat or [0], dtype=np.uintp))
+    lens = np.ascontiguousarray(np.array([len(item) for item in shapes] or [0], dtype=np.uintp))
+    nb = sum(len(item) + 1 for item in shapes)
+    batched = np.zeros(max(len(shapes), 1), dtype=np.int32)
+    bonds = np.zeros(max(nb, 1), dtype=np.uintp)
+    qr_bonds = np.zeros(max(nb, 1), dtype=np.uintp)
+    counts = np.zeros(3, dtype=np.uintp)
+    _check(_lib.t4a_gpu_mpo_compress_many_plan(_p(dims), _p(lens), c_size_t(len(shapes)), c_double(o.tolerance),
+                                               c_size_t(0 if o.max_bond_dim is None else o.max_bond_dim), c_int32(code), _p(batched), _p(bonds),
+                                               _p(qr_bonds), _p(counts)))
+    out = {"routes": ["batched" if batched[k] else "serial" for k in range(len(shapes))], "bonds": [], "qr_bonds": [],
+           "launches": int(counts[0]), "syncs": int(counts[1]), "n_batched": int(counts[2])}
+    at = 0
+    for item in shapes:
+        out["bonds"].append([int(v) for v in bonds[at:at + len(item) + 1]])
+        out["qr_bonds"].append([int(v) for v in qr_bonds[at:at + len(item) + 1]])
+        at += len(item) + 1
+    return out
+
+
+def _time_compress_many(mpos, options=None, reps=5):
+    """Probe (t4a_gpu_mpo_time_compress_many): ms per repetition of (the serial stage item by item, one batched call) on copies."""
+    mpos = list(mpos)
+    o = ContractionOptions() if options is None else options
+    arr = (c_void_p * max(len(mpos), 1))(*[m._h for m in mpos])
+    ms = np.zeros(2)
+    _check(_lib.t4a_gpu_mpo_time_compress_many(arr, c_size_t(len(mpos)), c_double(o.tolerance),
+                                               c_size_t(0 if o.max_bond_dim is None else o.max_bond_dim), c_size_t(reps), _p(ms)))
+    return float(ms[0]), float(ms[1])
+
 
 def _contract(a, b, algorithm, compress, options):
     o = ContractionOptions() if options is None else options

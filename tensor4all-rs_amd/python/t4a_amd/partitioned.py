@@ -13,7 +13,7 @@ import ctypes
 import numpy as np
 
 from . import (_lib, _check, _p, T4aError, INVALID_ARGUMENT, c_size_t, c_double, c_int32, c_void_p)
-from .mpo import MPO, ContractionAlgorithm, ContractionOptions, FactorizeMethod
+from .mpo import MPO, ContractionAlgorithm, ContractionOptions, FactorizeMethod, _route_code
 
 
 def _triples(entries):
@@ -335,21 +335,27 @@ class PartitionedMPO:
         _check(_lib.t4a_gpu_pmpo_to_mpo_route(self._h, c_int32(route), ctypes.byref(h)))
         return MPO._adopt(h)
 
-    def contract(self, other, algorithm=ContractionAlgorithm.Naive, compress=True, options=None):
+    def contract(self, other, algorithm=ContractionAlgorithm.Naive, compress=True, options=None, compress_route="serial"):
         """contract (partitioned_tt.rs:305-340): every compatible pair of patches contracted over ``self.(i, 1) == other.(i, 0)`` with
-        both projected onto their own projectors, results of equal projector summed and truncated with the same options."""
+        both projected onto their own projectors, results of equal projector summed and truncated with the same options.
+        ``compress_route`` (Naive with ``compress``): ``"serial"`` compresses the task products one after the other, ``"batched"`` and
+        ``"auto"`` hand all of them to one ``mpo.compress_many`` call (t4a_gpu_pmpo_contract_routed); ZipUp refuses ``"batched"``.  The
+        sum of results that share a projector is truncated serially on every route."""
         o = ContractionOptions() if options is None else options
         h = c_void_p()
-        _check(_lib.t4a_gpu_pmpo_contract(self._h, other._h, c_int32(algorithm), c_int32(1 if compress else 0), c_int32(o.factorize_method),
-                                          c_double(o.tolerance), c_size_t(0 if o.max_bond_dim is None else o.max_bond_dim), ctypes.byref(h)))
+        _check(_lib.t4a_gpu_pmpo_contract_routed(self._h, other._h, c_int32(algorithm), c_int32(1 if compress else 0),
+                                                 c_int32(o.factorize_method), c_double(o.tolerance),
+                                                 c_size_t(0 if o.max_bond_dim is None else o.max_bond_dim), c_int32(_route_code(compress_route)),
+                                                 ctypes.byref(h)))
         return PartitionedMPO._adopt(h)
 
 
 def contract(a, b, algorithm=ContractionAlgorithm.Naive, compress=True, tolerance=1e-12, max_bond_dim=None,
-             factorize_method=FactorizeMethod.SVD):
+             factorize_method=FactorizeMethod.SVD, compress_route="serial"):
     """contract (contract.rs:41-47, partitioned_tt.rs:305-340) of two PartitionedMPO.  ``compress=False`` (Naive only) keeps the
-    exact products and direct sums; Fit and RSVD raise NOT_IMPLEMENTED as ``mpo.contract`` does."""
-    return a.contract(b, algorithm, compress, ContractionOptions(tolerance, max_bond_dim, factorize_method))
+    exact products and direct sums; Fit and RSVD raise NOT_IMPLEMENTED as ``mpo.contract`` does.  ``compress_route``: see
+    ``PartitionedMPO.contract``."""
+    return a.contract(b, algorithm, compress, ContractionOptions(tolerance, max_bond_dim, factorize_method), compress_route)
 
 
 def proj_contract(a, b, projector, shared=None, **options):
@@ -363,6 +369,15 @@ def proj_contract(a, b, projector, shared=None, **options):
     pa.update({(int(s), 1): int(v) for s, v in shared.items()})
     pb.update({(int(s), 0): int(v) for s, v in shared.items()})
     return contract(a.project(pa), b.project(pb), **options)
+
+
+def _time_compress(a, b, tolerance=1e-12, max_bond_dim=None, reps=5):
+    """Probe (t4a_gpu_pmpo_time_compress): ms per repetition of the compress stage of every task product of a·b, (task by task on the
+    serial stage, all tasks in one batched call)."""
+    ms = np.zeros(2)
+    _check(_lib.t4a_gpu_pmpo_time_compress(a._h, b._h, c_double(tolerance), c_size_t(0 if max_bond_dim is None else max_bond_dim),
+                                           c_size_t(reps), _p(ms)))
+    return float(ms[0]), float(ms[1])
 
 
 def _pair_products(dims, sel, A, B):
