@@ -718,6 +718,16 @@ void AciProblem::run() // elementwise.rs:126-210
         for (size_t b = 0; b + 1 < n; ++b) local_update(b, true);
 }
 
+AciHostOp aci_host_op(AciOpKind kind, t4a_gpu_aci_op_fn op, void* user, const char* null_message, const char* failed_message)
+{
+    if (kind != AciOpKind::Callback) return {};
+    if (!op) throw Error(T4A_GPU_NULL_POINTER, null_message);
+    const std::string failed = failed_message;
+    return [op, user, failed](const double* v, size_t K, size_t np, double* out) {
+        if (op(user, v, K, np, out) != 0) throw Error(T4A_GPU_CALLBACK_ERROR, failed);
+    };
+}
+
 TreeAciLocalResult treeaci_local_update(Engine& eng, const std::vector<size_t>& bond_dims, const std::vector<const double*>& row_frames,
                                         const std::vector<const double*>& col_frames, size_t row_count, size_t col_count, AciOpKind kind,
                                         const AciHostOp& host_op, size_t max_bond_dim, double tolerance, bool scale_tolerance,

@@ -22,6 +22,9 @@ enum class AciTermination : int { Converged = 0, RankLimited = 1, MaxIterations 
 
 // values[input + n_inputs * point] -> out[point] (batch.rs:33-217); throws to stop the sweep
 using AciHostOp = std::function<void(const double* values, size_t n_inputs, size_t n_points, double* out)>;
+// the C callback of the ABI as a host operator (empty for the built-in kinds): NULL_POINTER with `null_message` for a missing callback,
+// CALLBACK_ERROR with `failed_message` when it returns non-zero
+AciHostOp aci_host_op(AciOpKind kind, t4a_gpu_aci_op_fn op, void* user, const char* null_message, const char* failed_message);
 
 struct AciOptions { // options.rs:37-168
     size_t max_iters = 20;

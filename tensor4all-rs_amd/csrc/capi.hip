@@ -91,6 +91,10 @@ struct t4a_gpu_projected_operator {
     std::unique_ptr<t4a::ProjectedOperator> impl;
 };
 
+struct t4a_gpu_aci_problem {
+    std::unique_ptr<t4a::AciProblem> impl;
+};
+
 namespace t4a {
 const std::string& last_error_ref();
 
@@ -239,6 +243,41 @@ size_t checked_mul(size_t a, size_t b, const char* what)
     return a * b;
 }
 
+// caller indices -> the 32-bit indices of the device: `count` of them in one list ...
+std::vector<uint32_t> narrow_indices(const size_t* idx, size_t count, const char* out_of_bounds = "index out of bounds")
+{
+    std::vector<uint32_t> u(count);
+    for (size_t k = 0; k < count; ++k) {
+        if (idx[k] > 0xFFFFFFFFull) throw Error(T4A_GPU_INVALID_ARGUMENT, out_of_bounds);
+        u[k] = (uint32_t)idx[k];
+    }
+    return u;
+}
+// ... and n_pivots pivots of n_sites indices each
+std::vector<std::vector<uint32_t>> narrow_pivots(const size_t* pivots, size_t n_pivots, size_t n_sites, const char* out_of_bounds)
+{
+    std::vector<std::vector<uint32_t>> p(n_pivots, std::vector<uint32_t>(n_sites));
+    for (size_t k = 0; k < n_pivots; ++k)
+        for (size_t s = 0; s < n_sites; ++s) {
+            const size_t v = pivots[s + n_sites * k];
+            if (v > 0xFFFFFFFFull) throw Error(T4A_GPU_INVALID_ARGUMENT, out_of_bounds);
+            p[k][s] = (uint32_t)v;
+        }
+    return p;
+}
+
+// an array of handles -> what `get` takes from each; a null entry throws NULL_POINTER with `null_message`
+template <class H, class Get> auto handle_list(H* const* handles, size_t n, const char* null_message, Get get)
+{
+    std::vector<decltype(get(*handles[0]))> v;
+    v.reserve(n);
+    for (size_t i = 0; i < n; ++i) {
+        if (!handles[i]) throw Error(T4A_GPU_NULL_POINTER, null_message);
+        v.push_back(get(*handles[i]));
+    }
+    return v;
+}
+
 // what the three LUCI entry points check before they take the lock (the source is the matrix `a` or the callback `fill_block`;
 // rook: the 65535 limit of the rook routes).  Returns m * n.
 size_t luci_prologue(size_t m, size_t n, const size_t* rank, const size_t* rows, const size_t* cols, const double* pivot_errors,
@@ -284,6 +323,545 @@ RookWork& dense_rook_work()
 } // namespace t4a
 
 using namespace t4a;
+
+namespace {
+
+// what t4a_gpu_gemm_desc_f64 refuses, all of it on the host: "gemm_desc[i]: <what>"
+void require_gemm_desc(const t4a_gpu_gemm_desc& d, size_t i, size_t na, size_t nb, size_t nc)
+{
+    auto refuse = [&](const std::string& what) { throw Error(T4A_GPU_INVALID_ARGUMENT, "gemm_desc[" + std::to_string(i) + "]: " + what); };
+    const int64_t imax = std::numeric_limits<int>::max();
+    for (int64_t v : {d.m, d.n, d.k, d.lda, d.ldb, d.ldc, d.batch, d.stride_a, d.stride_b, d.stride_c, d.off_a, d.off_b, d.off_c})
+        if (v < 0) refuse("negative size, leading dimension, stride or offset");
+    for (int64_t v : {d.m, d.n, d.k, d.lda, d.ldb, d.ldc, d.batch})
+        if (v > imax) refuse("dimension exceeds the 32-bit index range of the device kernels");
+    // (the kernel rounds m, n and k up to whole tiles in int)
+    for (int64_t v : {d.m, d.n, d.k})
+        if (v > imax - 63) refuse("m, n and k must be at most INT_MAX - 63: the kernel rounds them up to whole tiles in 32-bit integers");
+    if ((d.trans_a != 0 && d.trans_a != 1) || (d.trans_b != 0 && d.trans_b != 1)) refuse("trans_a and trans_b must be 0 or 1");
+    const int64_t a_rows = d.trans_a ? d.k : d.m, a_cols = d.trans_a ? d.m : d.k;
+    const int64_t b_rows = d.trans_b ? d.n : d.k, b_cols = d.trans_b ? d.k : d.n;
+    if (d.lda < std::max<int64_t>(a_rows, 1)) refuse("lda is smaller than the rows of the stored A");
+    if (d.ldb < std::max<int64_t>(b_rows, 1)) refuse("ldb is smaller than the rows of the stored B");
+    if (d.ldc < std::max<int64_t>(d.m, 1)) refuse("ldc is smaller than the rows of C");
+    // (every factor is below 2^31 except strides and offsets, which are compared step by step: no overflow)
+    auto fits = [&](int64_t off, int64_t stride, int64_t rows, int64_t cols, int64_t ld, size_t count) {
+        if (rows == 0 || cols == 0 || d.batch == 0) return true;
+        const unsigned __int128 end = (unsigned __int128)off + (unsigned __int128)(d.batch - 1) * (unsigned __int128)stride +
+                                      (unsigned __int128)(cols - 1) * (unsigned __int128)ld + (unsigned __int128)rows;
+        return end <= (unsigned __int128)count;
+    };
+    if (!fits(d.off_a, d.stride_a, a_rows, a_cols, d.lda, na)) refuse("A runs past its buffer");
+    if (!fits(d.off_b, d.stride_b, b_rows, b_cols, d.ldb, nb)) refuse("B runs past its buffer");
+    if (!fits(d.off_c, d.stride_c, d.m, d.n, d.ldc, nc)) refuse("C runs past its buffer");
+    if (d.m == 0 || d.n == 0 || d.batch == 0) return;
+    if (d.batch > 1) {
+        // results do not overlap when a problem ends before the next begins, or when the problems interleave inside ldc
+        const unsigned __int128 span = (unsigned __int128)(d.n - 1) * (unsigned __int128)d.ldc + (unsigned __int128)d.m;
+        const bool apart = (unsigned __int128)d.stride_c >= span;
+        const bool interleaved = d.stride_c >= d.m && (unsigned __int128)(d.batch - 1) * (unsigned __int128)d.stride_c + (unsigned __int128)d.m <= (unsigned __int128)d.ldc;
+        if (!apart && !interleaved) refuse("stride_c makes the results of two problems overlap");
+    }
+    const GemmPlan p = gemm_plan((int)d.m, (int)d.n, (int)d.k, (int)d.batch);
+    if (d.batch * (int64_t)p.ksplit > 65535 || p.grid_n > 65535) refuse("more problems, split-K slices or tile columns than the 65535 a launch takes");
+}
+
+std::vector<Tci2*> tci2_list(t4a_gpu_tci2* const* handles, size_t n_handles)
+{
+    if (n_handles) T4A_REQUIRE_PTR(handles);
+    return handle_list(handles, n_handles, "handles[i] is null", [](t4a_gpu_tci2& h) { return &h.impl; });
+}
+
+t4a::SearchFn wrap_search_fn(t4a_gpu_batch_eval_fn f, void* ctx)
+{
+    return [f, ctx](const uint32_t* idx, size_t n_sites, size_t n_pts, double* out) {
+        FnSource::call(f, ctx, idx, n_sites, n_pts, out, "batch callback", "points");
+    };
+}
+
+std::vector<size_t> dims_vec(const size_t* local_dims, size_t n_sites)
+{
+    return std::vector<size_t>(local_dims, local_dims + n_sites);
+}
+
+t4a_gpu_ptt* run_adaptive(const size_t* local_dims, size_t n_sites, const FnSource& f,
+                          const size_t* initial_pivots, size_t n_pivots, const t4a_gpu_tci2_options* tci_options,
+                          const size_t* patch_order, size_t n_initial_pivots, int32_t recycle_pivots)
+{
+    if (n_sites) T4A_REQUIRE_PTR(local_dims);
+    if (n_pivots) T4A_REQUIRE_PTR(initial_pivots);
+    AdaptiveOptions ao;
+    ao.tci = convert_options(tci_options);
+    ao.n_initial_pivots = n_initial_pivots;
+    ao.recycle_pivots = recycle_pivots != 0;
+    if (patch_order) ao.patch_order.assign(patch_order, patch_order + n_sites);
+    std::vector<size_t> dims(local_dims, local_dims + n_sites);
+    std::vector<std::vector<uint32_t>> piv(n_pivots, std::vector<uint32_t>(n_sites));
+    for (size_t k = 0; k < n_pivots; ++k)
+        for (size_t s = 0; s < n_sites; ++s) {
+            const size_t v = initial_pivots[s + n_sites * k];
+            // out-of-range values are reported by the driver's own validation; keep them representable
+            piv[k][s] = v > 0xFFFFFFFEull ? 0xFFFFFFFFu : (uint32_t)v;
+        }
+    require_device();
+    std::unique_ptr<t4a_gpu_ptt> h(new t4a_gpu_ptt);
+    h->impl = adaptive_interpolate(dims, f, piv, ao);
+    return h.release();
+}
+
+TreeTciOptions convert_tree_options(const t4a_gpu_treetci_options* o)
+{
+    TreeTciOptions r;
+    if (!o) return r;
+    r.tolerance = o->tolerance;
+    r.max_iter = o->max_iter;
+    r.max_bond_dim = o->max_bond_dim;
+    r.normalize_error = o->normalize_error != 0;
+    r.enable_global_pivots = o->enable_global_pivots != 0;
+    r.nsearch = o->nsearch;
+    r.max_nglobal_pivot = o->max_nglobal_pivot;
+    r.tol_margin_global_search = o->tol_margin_global_search;
+    r.has_seed = o->has_seed != 0;
+    r.seed = o->seed;
+    return r;
+}
+
+void write_index_set(const IndexSet& s, size_t* count, size_t* out)
+{
+    *count = s.count;
+    if (out)
+        for (size_t k = 0; k < s.count * s.width; ++k) out[k] = s.d[k];
+}
+
+void write_history(const t4a_gpu_treetci* h, size_t* n_iter, size_t* ranks, double* errors)
+{
+    if (n_iter) *n_iter = h->impl.ranks_hist.size();
+    for (size_t k = 0; k < h->impl.ranks_hist.size(); ++k) {
+        if (ranks) ranks[k] = h->impl.ranks_hist[k];
+        if (errors) errors[k] = h->impl.errors_hist[k];
+    }
+}
+
+QtciOptions convert_qtci_options(const t4a_gpu_qtci_options* o)
+{
+    QtciOptions r;
+    if (!o) return r;
+    r.tolerance = o->tolerance;
+    r.max_bond_dim = o->max_bond_dim;
+    r.max_iter = o->max_iter;
+    r.n_random_init_pivot = o->n_random_init_pivot;
+    if (o->unfolding_scheme != 0 && o->unfolding_scheme != 1) throw Error(T4A_GPU_INVALID_ARGUMENT, "unknown unfolding scheme");
+    r.unfolding = o->unfolding_scheme ? Unfolding::Fused : Unfolding::Interleaved;
+    r.normalize_error = o->normalize_error != 0;
+    r.has_seed = o->has_seed != 0;
+    r.seed = o->seed;
+    r.to_treetci_options().validate();
+    return r;
+}
+
+std::vector<std::vector<size_t>> qtci_pivots(const size_t* pivots, size_t n_pivots, size_t n_vars)
+{
+    std::vector<std::vector<size_t>> p;
+    for (size_t k = 0; k < n_pivots; ++k) p.emplace_back(pivots + k * n_vars, pivots + (k + 1) * n_vars);
+    return p;
+}
+
+void qtci_run(t4a_gpu_qtci** out, std::unique_ptr<QuanticsTci> q, int32_t has_pivots, const size_t* pivots,
+              size_t n_pivots, const QtciOptions& o)
+{
+    const auto pv = qtci_pivots(pivots, has_pivots ? n_pivots : 0, q->grid.n_vars());
+    q->run(has_pivots ? &pv : nullptr, o);
+    auto* h = new t4a_gpu_qtci();
+    h->impl = std::move(q);
+    *out = h;
+}
+
+SvdPolicy convert_policy(const t4a_gpu_svd_policy* p)
+{
+    SvdPolicy r;
+    if (!p) return r;
+    r.threshold = p->threshold;
+    r.scale = p->scale;
+    r.measure = p->measure;
+    r.rule = p->rule;
+    if (r.scale < 0 || r.scale > 1 || r.measure < 0 || r.measure > 1 || r.rule < 0 || r.rule > 1)
+        throw Error(T4A_GPU_INVALID_ARGUMENT, "unknown SVD truncation policy field");
+    return r;
+}
+
+TensorView host_view(const size_t* dims, const int64_t* labels, size_t rank)
+{
+    TensorView v;
+    v.d_data = nullptr;
+    if (rank) {
+        T4A_REQUIRE_PTR(dims);
+        T4A_REQUIRE_PTR(labels);
+    }
+    v.dims.assign(dims, dims + rank);
+    v.labels.assign(labels, labels + rank);
+    size_t n = 1;
+    for (size_t d : v.dims) n = checked_mul(n, d, "tensor shape");
+    return v;
+}
+
+std::unique_ptr<t4a_gpu_tensor> make_tensor(OwnedTensor&& t) { return std::make_unique<t4a_gpu_tensor>(std::move(t)); }
+
+std::unique_ptr<t4a_gpu_tensor> make_tensor(const std::vector<size_t>& dims, const std::vector<int64_t>& labels)
+{
+    return make_tensor(OwnedTensor(dims, labels));
+}
+
+// the tail of the pairwise products: the product of two device tensors as a new handle
+t4a_gpu_tensor* contract_to_handle(const TensorView& va, const TensorView& vb, const ContractPlan& plan)
+{
+    std::lock_guard<std::mutex> lock(g_dense_mutex);
+    Engine& e = dense_engine();
+    auto t = make_tensor(plan.out_dims, plan.out_labels);
+    tensor_contract_pair(e, va, vb, plan, t->buf.get());
+    e.sync();
+    return t.release();
+}
+
+t4a_gpu_tt* wrap_tt(std::unique_ptr<TensorTrain> r)
+{
+    r->eng.sync();
+    return new t4a_gpu_tt(r->cores, r->eng.stream());
+}
+
+void cores_dims(const std::vector<DevCore>& cores, size_t* dims3)
+{
+    if (!cores.empty()) T4A_REQUIRE_PTR(dims3);
+    for (size_t s = 0; s < cores.size(); ++s) {
+        dims3[3 * s] = cores[s].l;
+        dims3[3 * s + 1] = cores[s].s;
+        dims3[3 * s + 2] = cores[s].r;
+    }
+}
+
+void core_to_host(Engine* eng, const std::vector<DevCore>& cores, size_t site, double* out)
+{
+    if (site >= cores.size()) throw Error(T4A_GPU_INVALID_ARGUMENT, "site " + std::to_string(site) + " is out of range for " + std::to_string(cores.size()) + " tensors");
+    const DevCore& c = cores[site];
+    if (c.size() == 0) return;
+    T4A_REQUIRE_PTR(out);
+    T4A_HIP(hipMemcpyAsync(out, c.buf.get(), c.size() * sizeof(double), hipMemcpyDeviceToHost, eng->stream()));
+    eng->sync();
+}
+
+void vector_out(const std::vector<double>& v, double* out, size_t capacity, size_t* len)
+{
+    T4A_REQUIRE_PTR(len);
+    *len = v.size();
+    if (!out) return;
+    if (capacity < v.size())
+        throw Error(T4A_GPU_BUFFER_TOO_SMALL, "output capacity " + std::to_string(capacity) + " is below " + std::to_string(v.size()));
+    if (!v.empty()) std::memcpy(out, v.data(), v.size() * sizeof(double));
+}
+
+t4a_gpu_tt* tt_from_cores(const std::vector<DevCore>& cores, hipStream_t stream) { return new t4a_gpu_tt(cores, stream); }
+
+AciOptions convert_aci(const t4a_gpu_aci_options* o)
+{
+    AciOptions a;
+    if (o) {
+        a.max_iters = o->max_iters;
+        a.min_iters = o->min_iters;
+        a.has_max_bond_dim = o->has_max_bond_dim != 0;
+        a.max_bond_dim = o->max_bond_dim;
+        a.tolerance = o->tolerance;
+        a.scale_tolerance = o->scale_tolerance != 0;
+        a.rng_seed = o->rng_seed;
+        a.enable_global_guard = o->enable_global_guard != 0;
+        a.nsearch_global_pivots = o->nsearch_global_pivots;
+        a.max_nglobal_pivot = o->max_nglobal_pivot;
+        a.nsweeps_global_search = o->nsweeps_global_search;
+        a.tol_margin_global_search = o->tol_margin_global_search;
+    }
+    return a;
+}
+
+AciOpKind aci_op_kind(int32_t kind, const char* unknown_message)
+{
+    if (kind < 0 || kind > 2) throw Error(T4A_GPU_INVALID_ARGUMENT, unknown_message);
+    return (AciOpKind)kind;
+}
+
+std::vector<TensorTrain*> aci_inputs(const t4a_gpu_tt* const* inputs, size_t n)
+{
+    if (n == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "inputs must not be empty");
+    if (!inputs) throw Error(T4A_GPU_NULL_POINTER, "inputs is null");
+    return handle_list(inputs, n, "input tensor train is null", [](const t4a_gpu_tt& t) { return const_cast<TensorTrain*>(&t.impl); });
+}
+
+PartialSpec partial_spec(const size_t* contract_pairs, size_t n_contract, const size_t* diagonal_pairs, size_t n_diagonal, size_t n_output_order)
+{
+    PartialSpec spec;
+    if (n_contract) T4A_REQUIRE_PTR(contract_pairs);
+    if (n_diagonal) T4A_REQUIRE_PTR(diagonal_pairs);
+    for (size_t i = 0; i < n_contract; ++i)
+        spec.contract_pairs.push_back({contract_pairs[4 * i], contract_pairs[4 * i + 1], contract_pairs[4 * i + 2], contract_pairs[4 * i + 3]});
+    for (size_t i = 0; i < n_diagonal; ++i)
+        spec.diagonal_pairs.push_back({diagonal_pairs[4 * i], diagonal_pairs[4 * i + 1], diagonal_pairs[4 * i + 2], diagonal_pairs[4 * i + 3]});
+    spec.has_output_order = n_output_order != 0;
+    return spec;
+}
+
+void contraction_environment(t4a_gpu_contraction* h, bool left, size_t n, const size_t* idx, size_t n_pts, double* out, size_t* dims2)
+{
+    T4A_REQUIRE_PTR(h);
+    T4A_REQUIRE_PTR(dims2);
+    const std::array<size_t, 2> d = left ? h->impl->left_dims(n) : h->impl->right_dims(n); // n out of range is refused here
+    dims2[0] = d[0];
+    dims2[1] = d[1];
+    if (n_pts == 0) return;
+    T4A_REQUIRE_PTR(idx);
+    T4A_REQUIRE_PTR(out);
+    std::vector<uint32_t> u = narrow_indices(idx, checked_mul(n_pts, 2 * h->impl->len(), "index buffer"));
+    if (left)
+        h->impl->evaluate_left(n, u.data(), n_pts, out, dims2);
+    else
+        h->impl->evaluate_right(n, u.data(), n_pts, out, dims2);
+}
+
+// the entry points of the candidate matrices of A·B answer INVALID_ARGUMENT for NULL (t4a_gpu.h)
+#define T4A_REQUIRE_ARG(p)                                                            \
+    do {                                                                              \
+        if ((p) == nullptr) throw ::t4a::Error(T4A_GPU_INVALID_ARGUMENT, #p " is null"); \
+    } while (0)
+
+LinsolveOptions convert_linsolve_options(const t4a_gpu_linsolve_options* p)
+{
+    LinsolveOptions o;
+    o.nfullsweeps = p->nfullsweeps;
+    o.has_max_bond_dim = p->has_max_bond_dim != 0;
+    o.max_bond_dim = p->max_bond_dim;
+    o.has_svd_policy = p->has_svd_policy != 0;
+    if (o.has_svd_policy) o.svd_policy = from_c(p->svd_policy);
+    o.gmres_tol = p->gmres_tol;
+    if (p->gmres_tolerance_mode != 0 && p->gmres_tolerance_mode != 1) throw Error(T4A_GPU_INVALID_ARGUMENT, "unknown gmres_tolerance_mode");
+    o.gmres_tolerance_mode = (GmresToleranceMode)p->gmres_tolerance_mode;
+    o.gmres_max_restarts = p->gmres_max_restarts;
+    o.gmres_restart_dim = p->gmres_restart_dim;
+    o.a0 = p->a0;
+    o.a1 = p->a1;
+    o.has_convergence_tol = p->has_convergence_tol != 0;
+    o.convergence_tol = p->convergence_tol;
+    o.check_residual = p->check_residual != 0;
+    o.validate();
+    return o;
+}
+
+LanczosOptions convert_lanczos_options(const t4a_gpu_lanczos_options& p)
+{
+    LanczosOptions o;
+    o.max_iter = p.max_iter;
+    o.rtol = p.rtol;
+    o.atol = p.atol;
+    o.breakdown_tol = p.breakdown_tol;
+    o.hermitian_tol = p.hermitian_tol;
+    return o;
+}
+
+DmrgOptions convert_dmrg_options(const t4a_gpu_dmrg_options* p)
+{
+    DmrgOptions o;
+    o.nsite = p->nsite;
+    o.nsweeps = p->nsweeps;
+    o.has_max_bond_dim = p->has_max_bond_dim != 0;
+    o.max_bond_dim = p->max_bond_dim;
+    o.has_svd_policy = p->has_svd_policy != 0;
+    if (o.has_svd_policy) o.svd_policy = from_c(p->svd_policy);
+    o.lanczos = convert_lanczos_options(p->lanczos);
+    o.has_energy_tol = p->has_energy_tol != 0;
+    o.energy_tol = p->energy_tol;
+    o.real_scalar_tol = p->real_scalar_tol;
+    o.validate();
+    return o;
+}
+
+KrylovExpmOptions convert_krylov_expm_options(const t4a_gpu_krylov_expm_options& p)
+{
+    KrylovExpmOptions o;
+    o.max_iter = p.max_iter;
+    o.max_time_splits = p.max_time_splits;
+    o.tol = p.tol;
+    o.breakdown_tol = p.breakdown_tol;
+    o.hermitian_tol = p.hermitian_tol;
+    return o;
+}
+
+TdvpOptions convert_tdvp_options(const t4a_gpu_tdvp_options* p)
+{
+    TdvpOptions o;
+    o.nsite = p->nsite;
+    o.nsweeps = p->nsweeps;
+    o.order = p->order;
+    o.exponent_step_re = p->exponent_step_re;
+    o.exponent_step_im = p->exponent_step_im;
+    o.has_max_bond_dim = p->has_max_bond_dim != 0;
+    o.max_bond_dim = p->max_bond_dim;
+    o.has_svd_policy = p->has_svd_policy != 0;
+    if (o.has_svd_policy) o.svd_policy = from_c(p->svd_policy);
+    o.krylov = convert_krylov_expm_options(p->krylov);
+    o.validate();
+    return o;
+}
+
+GseOptions convert_gse_options(const t4a_gpu_gse_options* p)
+{
+    GseOptions o;
+    o.krylov_dim = p->krylov_dim;
+    o.has_reference_max_bond_dim = p->has_reference_max_bond_dim != 0;
+    o.reference_max_bond_dim = p->reference_max_bond_dim;
+    o.has_reference_svd_policy = p->has_reference_svd_policy != 0;
+    if (o.has_reference_svd_policy) o.reference_svd_policy = from_c(p->reference_svd_policy);
+    o.density_weight_cutoff = p->density_weight_cutoff;
+    o.hermitian_tol = p->hermitian_tol;
+    o.normalize_references = p->normalize_references != 0;
+    o.expand_before_first_sweep = p->expand_before_first_sweep != 0;
+    o.validate();
+    return o;
+}
+
+void gse_counters(const GseResult& r, size_t* references_built, size_t* edges_processed, size_t* bonds_expanded, size_t* max_added_basis)
+{
+    *references_built = r.references_built;
+    *edges_processed = r.edges_processed;
+    *bonds_expanded = r.bonds_expanded;
+    *max_added_basis = r.max_added_basis;
+}
+
+// the ragged shape lists of the hooks as ints: every entry positive, at most `max_jobs` of them
+std::vector<int> gse_int_list(const size_t* v, size_t n, size_t max_jobs, const char* who)
+{
+    if (n == 0 || n > max_jobs) throw Error(T4A_GPU_INVALID_ARGUMENT, std::string(who) + ": between 1 and " + std::to_string(max_jobs) + " operands");
+    T4A_REQUIRE_PTR(v);
+    std::vector<int> out(n);
+    for (size_t i = 0; i < n; ++i) {
+        if (v[i] == 0 || v[i] > (size_t)INT_MAX) throw Error(T4A_GPU_INVALID_ARGUMENT, std::string(who) + ": every dimension must be positive and at most INT_MAX");
+        out[i] = (int)v[i];
+    }
+    return out;
+}
+
+void gse_require_fits(size_t a, size_t b, const char* who)
+{
+    if (a == 0 || b == 0 || a > (size_t)INT_MAX || b > (size_t)INT_MAX / a)
+        throw Error(T4A_GPU_INVALID_ARGUMENT, std::string(who) + ": every dimension must be positive and every matrix within INT_MAX elements");
+}
+
+std::vector<LegProjector> projector_list(const size_t* entries, const size_t* counts, size_t n)
+{
+    std::vector<LegProjector> v(n);
+    if (n) T4A_REQUIRE_PTR(counts);
+    size_t off = 0;
+    for (size_t k = 0; k < n; ++k) {
+        v[k] = projector_from_triples(entries ? entries + 3 * off : nullptr, counts[k]);
+        off += counts[k];
+    }
+    return v;
+}
+
+void projector_out(const LegProjector& p, size_t* out, size_t* out_count)
+{
+    T4A_REQUIRE_PTR(out_count);
+    *out_count = p.size();
+    if (!out) return;
+    size_t i = 0;
+    for (const auto& kv : p) {
+        out[3 * i] = kv.first.first;
+        out[3 * i + 1] = kv.first.second;
+        out[3 * i + 2] = kv.second;
+        ++i;
+    }
+}
+
+SiteDims site_dims_list(const size_t* site_dims, size_t n_sites)
+{
+    if (n_sites) T4A_REQUIRE_PTR(site_dims);
+    SiteDims sd(n_sites);
+    for (size_t i = 0; i < n_sites; ++i) sd[i] = {site_dims[2 * i], site_dims[2 * i + 1]};
+    return sd;
+}
+
+MpoContractionOptions pmpo_options(double tolerance, size_t max_bond_dim, int32_t method)
+{
+    if (method < 0 || method > 3) throw Error(T4A_GPU_INVALID_ARGUMENT, "unknown factorize method");
+    MpoContractionOptions o;
+    o.tolerance = tolerance;
+    o.max_bond_dim = max_bond_dim;
+    o.method = (MpoFactorizeMethod)method;
+    return o;
+}
+
+CompressRoute compress_route(int32_t route)
+{
+    if (route < 0 || route > 2) throw Error(T4A_GPU_INVALID_ARGUMENT, "unknown compress route");
+    return (CompressRoute)route;
+}
+
+std::vector<Mpo*> mpo_list(const t4a_gpu_mpo* const* mpos, size_t count, const char* what)
+{
+    if (count == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, std::string(what) + ": the list is empty");
+    T4A_REQUIRE_PTR(mpos);
+    std::vector<Mpo*> items(count);
+    for (size_t k = 0; k < count; ++k) {
+        if (!mpos[k]) throw Error(T4A_GPU_NULL_POINTER, std::string(what) + ": item " + std::to_string(k) + " is null");
+        items[k] = mpos[k]->impl.get();
+    }
+    return items;
+}
+
+SiteLegs site_legs(size_t n, const size_t* leg_counts, const int64_t* keys, const size_t* dims)
+{
+    SiteLegs legs(n);
+    if (n) T4A_REQUIRE_PTR(leg_counts);
+    size_t at = 0;
+    for (size_t i = 0; i < n; ++i)
+        for (size_t k = 0; k < leg_counts[i]; ++k, ++at) {
+            T4A_REQUIRE_PTR(keys);
+            T4A_REQUIRE_PTR(dims);
+            legs[i].push_back({keys[at], dims[at]});
+        }
+    return legs;
+}
+
+void write_legs(const SiteLegs& legs, size_t* leg_counts, int64_t* keys, size_t* dims)
+{
+    size_t at = 0;
+    for (size_t i = 0; i < legs.size(); ++i) {
+        if (leg_counts) leg_counts[i] = legs[i].size();
+        for (const SwapLeg& g : legs[i]) {
+            if (keys) keys[at] = g.key;
+            if (dims) dims[at] = g.dim;
+            ++at;
+        }
+    }
+}
+
+SwapAssignment assignment(const int64_t* keys, const size_t* sites, size_t count)
+{
+    SwapAssignment a;
+    if (count) {
+        T4A_REQUIRE_PTR(keys);
+        T4A_REQUIRE_PTR(sites);
+    }
+    for (size_t k = 0; k < count; ++k) a.push_back({keys[k], sites[k]});
+    return a;
+}
+
+std::vector<SwapLeg> leg_list(const int64_t* keys, const size_t* dims, size_t count)
+{
+    std::vector<SwapLeg> v;
+    if (count) {
+        T4A_REQUIRE_PTR(keys);
+        T4A_REQUIRE_PTR(dims);
+    }
+    for (size_t k = 0; k < count; ++k) v.push_back({keys[k], dims[k]});
+    return v;
+}
+
+} // namespace
 
 extern "C" {
 
@@ -429,6 +1007,7 @@ t4a_gpu_status t4a_gpu_set_device(int32_t device)
 }
 
 const char* t4a_gpu_version(void) { return "t4a-mi355x 0.1.0 (gfx950)"; }
+
 int32_t t4a_gpu_diag_switches_enabled(void) { return 0; }
 
 // ------------------------------------------------------------------------------------------------ dense
@@ -532,48 +1111,6 @@ t4a_gpu_status t4a_gpu_gemm_route(size_t m, size_t n, size_t k, size_t batch, in
         *remapped = p.remapped ? 1 : 0;
     });
 }
-
-namespace {
-// what t4a_gpu_gemm_desc_f64 refuses, all of it on the host: "gemm_desc[i]: <what>"
-void require_gemm_desc(const t4a_gpu_gemm_desc& d, size_t i, size_t na, size_t nb, size_t nc)
-{
-    auto refuse = [&](const std::string& what) { throw Error(T4A_GPU_INVALID_ARGUMENT, "gemm_desc[" + std::to_string(i) + "]: " + what); };
-    const int64_t imax = std::numeric_limits<int>::max();
-    for (int64_t v : {d.m, d.n, d.k, d.lda, d.ldb, d.ldc, d.batch, d.stride_a, d.stride_b, d.stride_c, d.off_a, d.off_b, d.off_c})
-        if (v < 0) refuse("negative size, leading dimension, stride or offset");
-    for (int64_t v : {d.m, d.n, d.k, d.lda, d.ldb, d.ldc, d.batch})
-        if (v > imax) refuse("dimension exceeds the 32-bit index range of the device kernels");
-    // (the kernel rounds m, n and k up to whole tiles in int)
-    for (int64_t v : {d.m, d.n, d.k})
-        if (v > imax - 63) refuse("m, n and k must be at most INT_MAX - 63: the kernel rounds them up to whole tiles in 32-bit integers");
-    if ((d.trans_a != 0 && d.trans_a != 1) || (d.trans_b != 0 && d.trans_b != 1)) refuse("trans_a and trans_b must be 0 or 1");
-    const int64_t a_rows = d.trans_a ? d.k : d.m, a_cols = d.trans_a ? d.m : d.k;
-    const int64_t b_rows = d.trans_b ? d.n : d.k, b_cols = d.trans_b ? d.k : d.n;
-    if (d.lda < std::max<int64_t>(a_rows, 1)) refuse("lda is smaller than the rows of the stored A");
-    if (d.ldb < std::max<int64_t>(b_rows, 1)) refuse("ldb is smaller than the rows of the stored B");
-    if (d.ldc < std::max<int64_t>(d.m, 1)) refuse("ldc is smaller than the rows of C");
-    // (every factor is below 2^31 except strides and offsets, which are compared step by step: no overflow)
-    auto fits = [&](int64_t off, int64_t stride, int64_t rows, int64_t cols, int64_t ld, size_t count) {
-        if (rows == 0 || cols == 0 || d.batch == 0) return true;
-        const unsigned __int128 end = (unsigned __int128)off + (unsigned __int128)(d.batch - 1) * (unsigned __int128)stride +
-                                      (unsigned __int128)(cols - 1) * (unsigned __int128)ld + (unsigned __int128)rows;
-        return end <= (unsigned __int128)count;
-    };
-    if (!fits(d.off_a, d.stride_a, a_rows, a_cols, d.lda, na)) refuse("A runs past its buffer");
-    if (!fits(d.off_b, d.stride_b, b_rows, b_cols, d.ldb, nb)) refuse("B runs past its buffer");
-    if (!fits(d.off_c, d.stride_c, d.m, d.n, d.ldc, nc)) refuse("C runs past its buffer");
-    if (d.m == 0 || d.n == 0 || d.batch == 0) return;
-    if (d.batch > 1) {
-        // results do not overlap when a problem ends before the next begins, or when the problems interleave inside ldc
-        const unsigned __int128 span = (unsigned __int128)(d.n - 1) * (unsigned __int128)d.ldc + (unsigned __int128)d.m;
-        const bool apart = (unsigned __int128)d.stride_c >= span;
-        const bool interleaved = d.stride_c >= d.m && (unsigned __int128)(d.batch - 1) * (unsigned __int128)d.stride_c + (unsigned __int128)d.m <= (unsigned __int128)d.ldc;
-        if (!apart && !interleaved) refuse("stride_c makes the results of two problems overlap");
-    }
-    const GemmPlan p = gemm_plan((int)d.m, (int)d.n, (int)d.k, (int)d.batch);
-    if (d.batch * (int64_t)p.ksplit > 65535 || p.grid_n > 65535) refuse("more problems, split-K slices or tile columns than the 65535 a launch takes");
-}
-} // namespace
 
 t4a_gpu_status t4a_gpu_gemm_desc_f64(const t4a_gpu_gemm_desc* descs, size_t n_descs, const double* a, size_t na, const double* b, size_t nb,
                                      double* c, size_t nc)
@@ -766,25 +1303,12 @@ t4a_gpu_status t4a_gpu_tci2_set_callback(t4a_gpu_tci2* h, t4a_gpu_batch_eval_fn 
     });
 }
 
-static std::vector<std::vector<uint32_t>> pivots_from(const t4a_gpu_tci2* h, const size_t* pivots, size_t n_pivots)
-{
-    const size_t ns = h->impl.len();
-    std::vector<std::vector<uint32_t>> p(n_pivots, std::vector<uint32_t>(ns));
-    for (size_t k = 0; k < n_pivots; ++k)
-        for (size_t s = 0; s < ns; ++s) {
-            const size_t v = pivots[s + ns * k];
-            if (v > 0xFFFFFFFFull) throw Error(T4A_GPU_INVALID_ARGUMENT, "pivot value out of bounds");
-            p[k][s] = (uint32_t)v;
-        }
-    return p;
-}
-
 t4a_gpu_status t4a_gpu_tci2_add_global_pivots(t4a_gpu_tci2* h, const size_t* pivots, size_t n_pivots)
 {
     return guarded([&] {
         T4A_REQUIRE_PTR(h);
         if (n_pivots) T4A_REQUIRE_PTR(pivots);
-        h->impl.add_global_pivots(pivots_from(h, pivots, n_pivots));
+        h->impl.add_global_pivots(narrow_pivots(pivots, n_pivots, h->impl.len(), "pivot value out of bounds"));
     });
 }
 
@@ -796,7 +1320,7 @@ t4a_gpu_status t4a_gpu_tci2_crossinterpolate2(t4a_gpu_tci2* h, const size_t* ini
         if (n_pivots) T4A_REQUIRE_PTR(initial_pivots);
         TCI2Options o = convert_options(options);
         o.validate(); // options are validated before any callback runs (tensorci2/tests/mod.rs:7-144)
-        h->impl.crossinterpolate2(pivots_from(h, initial_pivots, n_pivots), o);
+        h->impl.crossinterpolate2(narrow_pivots(initial_pivots, n_pivots, h->impl.len(), "pivot value out of bounds"), o);
     });
 }
 
@@ -812,12 +1336,7 @@ t4a_gpu_status t4a_gpu_tci2_optimize_group(t4a_gpu_tci2* const* handles, size_t 
                                            int32_t final_sweep1site)
 {
     return guarded([&] {
-        if (n_handles) T4A_REQUIRE_PTR(handles);
-        std::vector<Tci2*> hs;
-        for (size_t i = 0; i < n_handles; ++i) {
-            T4A_REQUIRE_PTR(handles[i]);
-            hs.push_back(&handles[i]->impl);
-        }
+        const std::vector<Tci2*> hs = tci2_list(handles, n_handles); // (a null handle is reported before null options)
         Tci2::optimize_group(hs, convert_options(options), final_sweep1site != 0);
     });
 }
@@ -825,13 +1344,7 @@ t4a_gpu_status t4a_gpu_tci2_optimize_group(t4a_gpu_tci2* const* handles, size_t 
 t4a_gpu_status t4a_gpu_tci2_fill_site_tensors_group(t4a_gpu_tci2* const* handles, size_t n_handles)
 {
     return guarded([&] {
-        if (n_handles) T4A_REQUIRE_PTR(handles);
-        std::vector<Tci2*> hs;
-        for (size_t i = 0; i < n_handles; ++i) {
-            T4A_REQUIRE_PTR(handles[i]);
-            hs.push_back(&handles[i]->impl);
-        }
-        Tci2::fill_site_tensors_group(hs);
+        Tci2::fill_site_tensors_group(tci2_list(handles, n_handles));
     });
 }
 
@@ -876,6 +1389,7 @@ t4a_gpu_status t4a_gpu_tci2_len(const t4a_gpu_tci2* h, size_t* out)
         *out = h->impl.len();
     });
 }
+
 t4a_gpu_status t4a_gpu_tci2_rank(const t4a_gpu_tci2* h, size_t* out)
 {
     return guarded([&] {
@@ -884,6 +1398,7 @@ t4a_gpu_status t4a_gpu_tci2_rank(const t4a_gpu_tci2* h, size_t* out)
         *out = h->impl.rank();
     });
 }
+
 t4a_gpu_status t4a_gpu_tci2_link_dims(const t4a_gpu_tci2* h, size_t* out)
 {
     return guarded([&] {
@@ -893,6 +1408,7 @@ t4a_gpu_status t4a_gpu_tci2_link_dims(const t4a_gpu_tci2* h, size_t* out)
         for (size_t i = 0; i < v.size(); ++i) out[i] = v[i];
     });
 }
+
 t4a_gpu_status t4a_gpu_tci2_max_sample_value(const t4a_gpu_tci2* h, double* out)
 {
     return guarded([&] {
@@ -901,6 +1417,7 @@ t4a_gpu_status t4a_gpu_tci2_max_sample_value(const t4a_gpu_tci2* h, double* out)
         *out = h->impl.max_sample_value;
     });
 }
+
 t4a_gpu_status t4a_gpu_tci2_max_bond_error(const t4a_gpu_tci2* h, double* out)
 {
     return guarded([&] {
@@ -909,6 +1426,7 @@ t4a_gpu_status t4a_gpu_tci2_max_bond_error(const t4a_gpu_tci2* h, double* out)
         *out = h->impl.max_bond_error();
     });
 }
+
 t4a_gpu_status t4a_gpu_tci2_bond_errors(const t4a_gpu_tci2* h, double* out)
 {
     return guarded([&] {
@@ -917,6 +1435,7 @@ t4a_gpu_status t4a_gpu_tci2_bond_errors(const t4a_gpu_tci2* h, double* out)
         for (size_t i = 0; i < h->impl.bond_errors.size(); ++i) out[i] = h->impl.bond_errors[i];
     });
 }
+
 t4a_gpu_status t4a_gpu_tci2_pivot_errors(const t4a_gpu_tci2* h, size_t* count, double* out)
 {
     return guarded([&] {
@@ -949,24 +1468,7 @@ t4a_gpu_status t4a_gpu_tci2_set_index_set(t4a_gpu_tci2* h, int32_t which, size_t
 {
     return guarded([&] {
         T4A_REQUIRE_PTR(h);
-        if (site >= h->impl.len() || which < 0 || which > 1) throw Error(T4A_GPU_INVALID_ARGUMENT, "site/which out of range");
-        h->impl.sync_digits();
-        IndexSet& s = which == 0 ? h->impl.i_set[site] : h->impl.j_set[site];
-        const size_t first_site = which == 0 ? 0 : site + 1;
-        if (count * s.width) T4A_REQUIRE_PTR(data);
-        IndexSet n;
-        n.width = s.width;
-        n.count = count;
-        n.d.resize(count * s.width);
-        for (size_t k = 0; k < count; ++k)
-            for (size_t q = 0; q < s.width; ++q) {
-                const size_t v = data[k * s.width + q];
-                if (v >= h->impl.local_dims[first_site + q]) throw Error(T4A_GPU_INVALID_ARGUMENT, "index out of bounds");
-                n.d[k * s.width + q] = (uint32_t)v;
-            }
-        s = n;
-        h->impl.invalidate_site_tensors();
-        h->impl.mark_sets_changed();
+        h->impl.set_index_set(which, site, count, data);
     });
 }
 
@@ -1010,15 +1512,7 @@ t4a_gpu_status t4a_gpu_tci2_site_tensor_device(const t4a_gpu_tci2* h, size_t sit
     return guarded([&] {
         T4A_REQUIRE_PTR(h);
         T4A_REQUIRE_PTR(out_device);
-        if (site >= h->impl.len()) throw Error(T4A_GPU_INVALID_ARGUMENT, "site out of range");
-        t4a_gpu_tci2* hh = const_cast<t4a_gpu_tci2*>(h);
-        hh->impl.fill_wait();
-        const DevCore& c = h->impl.cores[site];
-        if (c.size()) {
-            T4A_HIP(hipMemcpyAsync(out_device, c.buf.get(), c.size() * sizeof(double), hipMemcpyDeviceToDevice,
-                                   hh->impl.eng.stream()));
-            T4A_HIP(hipStreamSynchronize(hh->impl.eng.stream()));
-        }
+        const_cast<t4a_gpu_tci2*>(h)->impl.site_tensor_device(site, static_cast<double*>(out_device));
     });
 }
 
@@ -1028,18 +1522,7 @@ t4a_gpu_status t4a_gpu_tci2_set_site_tensor_device(t4a_gpu_tci2* h, size_t site,
     return guarded([&] {
         T4A_REQUIRE_PTR(h);
         T4A_REQUIRE_PTR(dims3);
-        if (site >= h->impl.len()) throw Error(T4A_GPU_INVALID_ARGUMENT, "site out of range");
-        if (dims3[1] != h->impl.local_dims[site]) throw Error(T4A_GPU_INVALID_ARGUMENT, "site dimension mismatch");
-        h->impl.fill_wait();
-        DevCore& c = h->impl.cores[site];
-        const size_t count = dims3[0] * dims3[1] * dims3[2];
-        c.reshape(dims3[0], dims3[1], dims3[2]);
-        if (count) {
-            T4A_REQUIRE_PTR(in_device);
-            T4A_HIP(hipMemcpyAsync(c.buf.get(), in_device, count * sizeof(double), hipMemcpyDeviceToDevice,
-                                   h->impl.eng.stream()));
-            T4A_HIP(hipStreamSynchronize(h->impl.eng.stream()));
-        }
+        h->impl.set_site_tensor_device(site, dims3, static_cast<const double*>(in_device));
     });
 }
 
@@ -1062,6 +1545,7 @@ t4a_gpu_status t4a_gpu_tci2_n_iterations(const t4a_gpu_tci2* h, size_t* out)
         *out = h->impl.errors_hist.size();
     });
 }
+
 t4a_gpu_status t4a_gpu_tci2_history(const t4a_gpu_tci2* h, size_t* ranks, double* errors)
 {
     return guarded([&] {
@@ -1072,6 +1556,7 @@ t4a_gpu_status t4a_gpu_tci2_history(const t4a_gpu_tci2* h, size_t* ranks, double
         }
     });
 }
+
 t4a_gpu_status t4a_gpu_tci2_termination(const t4a_gpu_tci2* h, int32_t* out)
 {
     return guarded([&] {
@@ -1088,12 +1573,7 @@ t4a_gpu_status t4a_gpu_tci2_evaluate(t4a_gpu_tci2* h, const size_t* idx, size_t 
         if (n_pts == 0) return;
         T4A_REQUIRE_PTR(idx);
         T4A_REQUIRE_PTR(out);
-        const size_t ns = h->impl.len();
-        std::vector<uint32_t> u(n_pts * ns);
-        for (size_t k = 0; k < u.size(); ++k) {
-            if (idx[k] > 0xFFFFFFFFull) throw Error(T4A_GPU_INVALID_ARGUMENT, "evaluate: index out of bounds");
-            u[k] = (uint32_t)idx[k];
-        }
+        const std::vector<uint32_t> u = narrow_indices(idx, n_pts * h->impl.len(), "evaluate: index out of bounds");
         std::vector<double> v = h->impl.evaluate(u.data(), n_pts);
         std::memcpy(out, v.data(), n_pts * sizeof(double));
     });
@@ -1112,9 +1592,7 @@ t4a_gpu_status t4a_gpu_tci2_set_site_shard(t4a_gpu_tci2* h, size_t rank, size_t 
 {
     return guarded([&] {
         T4A_REQUIRE_PTR(h);
-        if (world == 0 || rank >= world) throw Error(T4A_GPU_INVALID_ARGUMENT, "invalid shard (rank, world)");
-        h->impl.shard_rank = rank;
-        h->impl.shard_world = world;
+        h->impl.set_site_shard(rank, world);
     });
 }
 
@@ -1122,13 +1600,7 @@ t4a_gpu_status t4a_gpu_tci2_set_pi_shard(t4a_gpu_tci2* h, size_t rank, size_t wo
 {
     return guarded([&] {
         T4A_REQUIRE_PTR(h);
-        if (world == 0 || rank >= world) throw Error(T4A_GPU_INVALID_ARGUMENT, "invalid shard (rank, world)");
-        if (world > 1 && !gather) throw Error(T4A_GPU_NULL_POINTER, "a column-block shard over more than one rank needs an all-gather callback");
-        h->impl.pi_shard = PiShard();
-        h->impl.pi_shard.rank = rank;
-        h->impl.pi_shard.world = world;
-        h->impl.pi_shard.gather = world > 1 ? gather : nullptr;
-        h->impl.pi_shard.gather_ctx = ctx;
+        h->impl.set_pi_shard(rank, world, gather, ctx);
     });
 }
 
@@ -1154,24 +1626,13 @@ t4a_gpu_status t4a_gpu_pi_shard_eval(size_t rank, size_t world, t4a_gpu_batch_ev
         T4A_REQUIRE_PTR(b);
         T4A_REQUIRE_PTR(out);
         if (wa + wb != n_sites || a0 + wa > n_sites || b0 + wb > n_sites) throw Error(T4A_GPU_INVALID_ARGUMENT, "index halves do not cover all sites");
-        if (world > 1) {
-            if (!gather) throw Error(T4A_GPU_NULL_POINTER, "a column-block shard over more than one rank needs an all-gather callback");
-            PiShard ps;
-            ps.rank = rank;
-            ps.world = world;
-            ps.gather = gather;
-            ps.gather_ctx = gather_ctx;
-            pi_shard_evaluate(ps, cb, cb_ctx, n_sites, a, wa, a0, na, b, wb, b0, nb, out);
-            return;
-        }
-        std::vector<uint32_t> idx(na * nb * n_sites);
-        for (size_t ia = 0; ia < na; ++ia)
-            for (size_t ib = 0; ib < nb; ++ib) {
-                uint32_t* dst = idx.data() + (ia * nb + ib) * n_sites;
-                std::memcpy(dst + a0, a + ia * wa, wa * sizeof(uint32_t));
-                std::memcpy(dst + b0, b + ib * wb, wb * sizeof(uint32_t));
-            }
-        FnSource::call(cb, cb_ctx, idx.data(), n_sites, na * nb, out, "batch callback", "requested entries");
+        if (world > 1 && !gather) throw Error(T4A_GPU_NULL_POINTER, "a column-block shard over more than one rank needs an all-gather callback");
+        PiShard ps;
+        ps.rank = rank;
+        ps.world = world;
+        ps.gather = gather;
+        ps.gather_ctx = gather_ctx;
+        pi_shard_evaluate(ps, cb, cb_ctx, n_sites, a, wa, a0, na, b, wb, b0, nb, out);
     });
 }
 
@@ -1219,6 +1680,7 @@ t4a_gpu_status t4a_gpu_tci2_profile_enable(t4a_gpu_tci2* h, int32_t enable)
         h->impl.eng.prof.enabled = enable != 0;
     });
 }
+
 t4a_gpu_status t4a_gpu_tci2_profile_reset(t4a_gpu_tci2* h)
 {
     return guarded([&] {
@@ -1227,6 +1689,7 @@ t4a_gpu_status t4a_gpu_tci2_profile_reset(t4a_gpu_tci2* h)
         h->impl.eng.variant_stats_.clear();
     });
 }
+
 t4a_gpu_status t4a_gpu_tci2_profile_get(const t4a_gpu_tci2* h, double* out)
 {
     return guarded([&] {
@@ -1245,6 +1708,7 @@ t4a_gpu_status t4a_gpu_tci2_profile_get(const t4a_gpu_tci2* h, double* out)
             }
     });
 }
+
 t4a_gpu_status t4a_gpu_tci2_profile_variants(const t4a_gpu_tci2* h, double* out, size_t cap_rows, size_t* n_rows)
 {
     return guarded([&] {
@@ -1262,7 +1726,6 @@ t4a_gpu_status t4a_gpu_tci2_profile_variants(const t4a_gpu_tci2* h, double* out,
         }
     });
 }
-
 
 t4a_gpu_status t4a_gpu_tci2_chain_stats(const t4a_gpu_tci2* h, uint64_t* out)
 {
@@ -1524,18 +1987,6 @@ t4a_gpu_status t4a_gpu_full_piv_lu_f64(const double* a, size_t n, double* p, dou
 }
 
 // ------------------------------------------------------------------------------------------------ SimpleTensorTrain
-extern "C++" {
-static std::vector<uint32_t> narrow_indices(const size_t* idx, size_t count)
-{
-    std::vector<uint32_t> u(count);
-    for (size_t k = 0; k < count; ++k) {
-        if (idx[k] > 0xFFFFFFFFull) throw Error(T4A_GPU_INVALID_ARGUMENT, "index out of bounds");
-        u[k] = (uint32_t)idx[k];
-    }
-    return u;
-}
-} // extern "C++"
-
 t4a_gpu_status t4a_gpu_tt_new(const size_t* dims3, size_t n_sites, const double* cores, t4a_gpu_tt** out)
 {
     return guarded([&] {
@@ -1659,19 +2110,6 @@ t4a_gpu_status t4a_gpu_tt_evaluate_many(t4a_gpu_tt* h, const size_t* idx, size_t
 }
 
 // ---- estimate_true_error / floating_zone / opt_first_pivot (tensorci/src/globalsearch.rs, optfirstpivot.rs) ----
-extern "C++" {
-static t4a::SearchFn wrap_search_fn(t4a_gpu_batch_eval_fn f, void* ctx)
-{
-    return [f, ctx](const uint32_t* idx, size_t n_sites, size_t n_pts, double* out) {
-        FnSource::call(f, ctx, idx, n_sites, n_pts, out, "batch callback", "points");
-    };
-}
-static std::vector<size_t> dims_vec(const size_t* local_dims, size_t n_sites)
-{
-    return std::vector<size_t>(local_dims, local_dims + n_sites);
-}
-} // extern "C++"
-
 t4a_gpu_status t4a_gpu_tt_floating_zone(t4a_gpu_tt* tt, t4a_gpu_batch_eval_fn f, void* ctx, const size_t* local_dims, size_t n_sites,
                                         const size_t* init_p, uint64_t seed, double early_stop_tol, size_t* pivot_out, double* error_out)
 {
@@ -1764,35 +2202,7 @@ t4a_gpu_status t4a_gpu_tci2_from_tensor_train(const t4a_gpu_tt* tt, double toler
     });
 }
 
-
 // ------------------------------------------------------------------------------------------------ adaptive patching
-extern "C++" {
-static t4a_gpu_ptt* run_adaptive(const size_t* local_dims, size_t n_sites, const FnSource& f,
-                                 const size_t* initial_pivots, size_t n_pivots, const t4a_gpu_tci2_options* tci_options,
-                                 const size_t* patch_order, size_t n_initial_pivots, int32_t recycle_pivots)
-{
-    if (n_sites) T4A_REQUIRE_PTR(local_dims);
-    if (n_pivots) T4A_REQUIRE_PTR(initial_pivots);
-    AdaptiveOptions ao;
-    ao.tci = convert_options(tci_options);
-    ao.n_initial_pivots = n_initial_pivots;
-    ao.recycle_pivots = recycle_pivots != 0;
-    if (patch_order) ao.patch_order.assign(patch_order, patch_order + n_sites);
-    std::vector<size_t> dims(local_dims, local_dims + n_sites);
-    std::vector<std::vector<uint32_t>> piv(n_pivots, std::vector<uint32_t>(n_sites));
-    for (size_t k = 0; k < n_pivots; ++k)
-        for (size_t s = 0; s < n_sites; ++s) {
-            const size_t v = initial_pivots[s + n_sites * k];
-            // out-of-range values are reported by the driver's own validation; keep them representable
-            piv[k][s] = v > 0xFFFFFFFEull ? 0xFFFFFFFFu : (uint32_t)v;
-        }
-    require_device();
-    std::unique_ptr<t4a_gpu_ptt> h(new t4a_gpu_ptt);
-    h->impl = adaptive_interpolate(dims, f, piv, ao);
-    return h.release();
-}
-} // extern "C++"
-
 t4a_gpu_status t4a_gpu_adaptive_interpolate_builtin(const size_t* local_dims, size_t n_sites, int32_t fid, int32_t n_acc,
                                                     const double* params, const uint64_t* weights,
                                                     const size_t* initial_pivots, size_t n_pivots,
@@ -1898,39 +2308,6 @@ t4a_gpu_status t4a_gpu_treetci_options_default(t4a_gpu_treetci_options* o)
     });
 }
 
-extern "C++" {
-static TreeTciOptions convert_tree_options(const t4a_gpu_treetci_options* o)
-{
-    TreeTciOptions r;
-    if (!o) return r;
-    r.tolerance = o->tolerance;
-    r.max_iter = o->max_iter;
-    r.max_bond_dim = o->max_bond_dim;
-    r.normalize_error = o->normalize_error != 0;
-    r.enable_global_pivots = o->enable_global_pivots != 0;
-    r.nsearch = o->nsearch;
-    r.max_nglobal_pivot = o->max_nglobal_pivot;
-    r.tol_margin_global_search = o->tol_margin_global_search;
-    r.has_seed = o->has_seed != 0;
-    r.seed = o->seed;
-    return r;
-}
-static void write_index_set(const IndexSet& s, size_t* count, size_t* out)
-{
-    *count = s.count;
-    if (out)
-        for (size_t k = 0; k < s.count * s.width; ++k) out[k] = s.d[k];
-}
-static void write_history(const t4a_gpu_treetci* h, size_t* n_iter, size_t* ranks, double* errors)
-{
-    if (n_iter) *n_iter = h->impl.ranks_hist.size();
-    for (size_t k = 0; k < h->impl.ranks_hist.size(); ++k) {
-        if (ranks) ranks[k] = h->impl.ranks_hist[k];
-        if (errors) errors[k] = h->impl.errors_hist[k];
-    }
-}
-} // extern "C++"
-
 t4a_gpu_status t4a_gpu_treetci_new(const size_t* local_dims, size_t n_sites, const size_t* edges, size_t n_edges,
                                    t4a_gpu_treetci** out)
 {
@@ -1972,27 +2349,12 @@ t4a_gpu_status t4a_gpu_treetci_set_callback(t4a_gpu_treetci* h, t4a_gpu_batch_ev
     });
 }
 
-extern "C++" {
-static std::vector<std::vector<uint32_t>> tree_pivots_from(const t4a_gpu_treetci* h, const size_t* pivots, size_t n_pivots)
-{
-    const size_t ns = h->impl.local_dims.size();
-    std::vector<std::vector<uint32_t>> p(n_pivots, std::vector<uint32_t>(ns));
-    for (size_t k = 0; k < n_pivots; ++k)
-        for (size_t s = 0; s < ns; ++s) {
-            const size_t v = pivots[s + ns * k];
-            if (v > 0xFFFFFFFFull) throw Error(T4A_GPU_INVALID_ARGUMENT, "pivot value out of bounds");
-            p[k][s] = (uint32_t)v;
-        }
-    return p;
-}
-} // extern "C++"
-
 t4a_gpu_status t4a_gpu_treetci_add_global_pivots(t4a_gpu_treetci* h, const size_t* pivots, size_t n_pivots)
 {
     return guarded([&] {
         T4A_REQUIRE_PTR(h);
         if (n_pivots) T4A_REQUIRE_PTR(pivots);
-        h->impl.add_global_pivots(tree_pivots_from(h, pivots, n_pivots));
+        h->impl.add_global_pivots(narrow_pivots(pivots, n_pivots, h->impl.local_dims.size(), "pivot value out of bounds"));
     });
 }
 
@@ -2072,7 +2434,7 @@ t4a_gpu_status t4a_gpu_treetci_crossinterpolate2(t4a_gpu_treetci* h, const size_
         if (n_pivots) T4A_REQUIRE_PTR(initial_pivots);
         const TreeTciOptions o = convert_tree_options(options);
         o.validate();
-        h->impl.crossinterpolate2(tree_pivots_from(h, initial_pivots, n_pivots), o);
+        h->impl.crossinterpolate2(narrow_pivots(initial_pivots, n_pivots, h->impl.local_dims.size(), "pivot value out of bounds"), o);
         write_history(h, n_iter, ranks, errors);
     });
 }
@@ -2221,40 +2583,6 @@ t4a_gpu_status t4a_gpu_qtci_options_default(t4a_gpu_qtci_options* o)
     });
 }
 
-extern "C++" {
-static QtciOptions convert_qtci_options(const t4a_gpu_qtci_options* o)
-{
-    QtciOptions r;
-    if (!o) return r;
-    r.tolerance = o->tolerance;
-    r.max_bond_dim = o->max_bond_dim;
-    r.max_iter = o->max_iter;
-    r.n_random_init_pivot = o->n_random_init_pivot;
-    if (o->unfolding_scheme != 0 && o->unfolding_scheme != 1) throw Error(T4A_GPU_INVALID_ARGUMENT, "unknown unfolding scheme");
-    r.unfolding = o->unfolding_scheme ? Unfolding::Fused : Unfolding::Interleaved;
-    r.normalize_error = o->normalize_error != 0;
-    r.has_seed = o->has_seed != 0;
-    r.seed = o->seed;
-    r.to_treetci_options().validate();
-    return r;
-}
-static std::vector<std::vector<size_t>> qtci_pivots(const size_t* pivots, size_t n_pivots, size_t n_vars)
-{
-    std::vector<std::vector<size_t>> p;
-    for (size_t k = 0; k < n_pivots; ++k) p.emplace_back(pivots + k * n_vars, pivots + (k + 1) * n_vars);
-    return p;
-}
-static void qtci_run(t4a_gpu_qtci** out, std::unique_ptr<QuanticsTci> q, int32_t has_pivots, const size_t* pivots,
-                     size_t n_pivots, const QtciOptions& o)
-{
-    const auto pv = qtci_pivots(pivots, has_pivots ? n_pivots : 0, q->grid.n_vars());
-    q->run(has_pivots ? &pv : nullptr, o);
-    auto* h = new t4a_gpu_qtci();
-    h->impl = std::move(q);
-    *out = h;
-}
-} // extern "C++"
-
 t4a_gpu_status t4a_gpu_quanticscrossinterpolate(const size_t* rs, size_t n_vars, const double* lower, const double* upper,
                                                 int32_t include_endpoint, int32_t grid_unfolding, t4a_gpu_coord_eval_fn f,
                                                 void* ctx, int32_t has_pivots, const size_t* initial_pivots, size_t n_pivots,
@@ -2319,23 +2647,7 @@ t4a_gpu_status t4a_gpu_quanticscrossinterpolate_from_arrays(const double* xvals,
             xv.emplace_back(xvals + off, xvals + off + sizes[d]);
             off += sizes[d];
         }
-        const bool uniform = qtci_check_xvals_uniform(xv);
-        std::vector<size_t> rs;
-        for (const auto& x : xv) rs.push_back((size_t)std::log2((double)x.size()));
-        if (uniform) {
-            std::vector<double> lo, up;
-            for (const auto& x : xv) {
-                lo.push_back(x.front());
-                up.push_back(x.back());
-            }
-            QuanticsGrid grid(rs, o.unfolding, true, lo, up, true);
-            qtci_run(out, std::unique_ptr<QuanticsTci>(new QuanticsTci(grid, f, nullptr, ctx, {})), has_pivots, initial_pivots,
-                     n_pivots, o);
-        } else {
-            QuanticsGrid grid(rs, o.unfolding, false);
-            qtci_run(out, std::unique_ptr<QuanticsTci>(new QuanticsTci(grid, f, nullptr, ctx, xv)), has_pivots, initial_pivots,
-                     n_pivots, o);
-        }
+        qtci_run(out, qtci_from_arrays(xv, f, ctx, o), has_pivots, initial_pivots, n_pivots, o);
     });
 }
 
@@ -2520,35 +2832,6 @@ t4a_gpu_status t4a_gpu_quanticscrossinterpolate_batched(const size_t* rs, size_t
 }
 
 // ------------------------------------------------------------------------------------------------ dense labelled tensors
-extern "C++" {
-static SvdPolicy convert_policy(const t4a_gpu_svd_policy* p)
-{
-    SvdPolicy r;
-    if (!p) return r;
-    r.threshold = p->threshold;
-    r.scale = p->scale;
-    r.measure = p->measure;
-    r.rule = p->rule;
-    if (r.scale < 0 || r.scale > 1 || r.measure < 0 || r.measure > 1 || r.rule < 0 || r.rule > 1)
-        throw Error(T4A_GPU_INVALID_ARGUMENT, "unknown SVD truncation policy field");
-    return r;
-}
-static TensorView host_view(const size_t* dims, const int64_t* labels, size_t rank)
-{
-    TensorView v;
-    v.d_data = nullptr;
-    if (rank) {
-        T4A_REQUIRE_PTR(dims);
-        T4A_REQUIRE_PTR(labels);
-    }
-    v.dims.assign(dims, dims + rank);
-    v.labels.assign(labels, labels + rank);
-    size_t n = 1;
-    for (size_t d : v.dims) n = checked_mul(n, d, "tensor shape");
-    return v;
-}
-} // extern "C++"
-
 t4a_gpu_status t4a_gpu_svd_retained_rank(const double* s, size_t n, const t4a_gpu_svd_policy* policy, size_t* out)
 {
     return guarded([&] {
@@ -2663,24 +2946,6 @@ t4a_gpu_status t4a_gpu_tensor_qr_f64(const double* t, const size_t* dims, const 
 }
 
 // ------------------------------------------------------------------------------------------------ device-resident labelled tensors
-extern "C++" {
-static std::unique_ptr<t4a_gpu_tensor> make_tensor(OwnedTensor&& t) { return std::make_unique<t4a_gpu_tensor>(std::move(t)); }
-static std::unique_ptr<t4a_gpu_tensor> make_tensor(const std::vector<size_t>& dims, const std::vector<int64_t>& labels)
-{
-    return make_tensor(OwnedTensor(dims, labels));
-}
-// the tail of the pairwise products: the product of two device tensors as a new handle
-static t4a_gpu_tensor* contract_to_handle(const TensorView& va, const TensorView& vb, const ContractPlan& plan)
-{
-    std::lock_guard<std::mutex> lock(g_dense_mutex);
-    Engine& e = dense_engine();
-    auto t = make_tensor(plan.out_dims, plan.out_labels);
-    tensor_contract_pair(e, va, vb, plan, t->buf.get());
-    e.sync();
-    return t.release();
-}
-} // extern "C++"
-
 t4a_gpu_status t4a_gpu_tensor_new(const double* data, const size_t* dims, const int64_t* labels, size_t rank,
                                   t4a_gpu_tensor** out)
 {
@@ -2689,9 +2954,7 @@ t4a_gpu_status t4a_gpu_tensor_new(const double* data, const size_t* dims, const 
         *out = nullptr;
         TensorView hv = host_view(dims, labels, rank);
         if (rank > (size_t)TENSOR_MAX_RANK) throw Error(T4A_GPU_NOT_IMPLEMENTED, "tensor rank above 16");
-        for (size_t a = 0; a < rank; ++a)
-            for (size_t b = a + 1; b < rank; ++b)
-                if (labels[a] == labels[b]) throw Error(T4A_GPU_INVALID_ARGUMENT, "duplicate index in tensor");
+        require_distinct_labels(hv);
         std::lock_guard<std::mutex> lock(g_dense_mutex);
         Engine& e = dense_engine();
         auto t = make_tensor(hv.dims, hv.labels);
@@ -2742,15 +3005,7 @@ t4a_gpu_status t4a_gpu_tensor_permute(const t4a_gpu_tensor* h, const int64_t* la
         *out = nullptr;
         const size_t r = h->dims.size();
         if (r) T4A_REQUIRE_PTR(labels);
-        std::vector<size_t> perm(r);
-        std::vector<char> used(r, 0);
-        for (size_t k = 0; k < r; ++k) {
-            auto it = std::find(h->labels.begin(), h->labels.end(), labels[k]);
-            if (it == h->labels.end()) throw Error(T4A_GPU_INVALID_ARGUMENT, "permute: index not found in tensor");
-            perm[k] = (size_t)(it - h->labels.begin());
-            if (used[perm[k]]) throw Error(T4A_GPU_INVALID_ARGUMENT, "permute: duplicate index");
-            used[perm[k]] = 1;
-        }
+        const std::vector<size_t> perm = plan_permute(h->view(), labels);
         std::vector<size_t> nd(r);
         std::vector<int64_t> nl(r);
         for (size_t k = 0; k < r; ++k) {
@@ -2770,11 +3025,7 @@ t4a_gpu_status t4a_gpu_tensor_relabel(t4a_gpu_tensor* h, int64_t from, int64_t t
 {
     return guarded([&] {
         T4A_REQUIRE_PTR(h);
-        auto it = std::find(h->labels.begin(), h->labels.end(), from);
-        if (it == h->labels.end()) throw Error(T4A_GPU_INVALID_ARGUMENT, "relabel: index not found in tensor");
-        if (from != to && std::find(h->labels.begin(), h->labels.end(), to) != h->labels.end())
-            throw Error(T4A_GPU_INVALID_ARGUMENT, "relabel: the new label is already present");
-        *it = to;
+        h->labels[plan_relabel(h->view(), from, to)] = to;
     });
 }
 
@@ -2799,11 +3050,7 @@ t4a_gpu_status t4a_gpu_tensor_contract_many(const t4a_gpu_tensor* const* tensors
         *out = nullptr;
         if (n_tensors) T4A_REQUIRE_PTR(tensors);
         if (n_retain) T4A_REQUIRE_PTR(retain_labels);
-        std::vector<TensorView> views;
-        for (size_t i = 0; i < n_tensors; ++i) {
-            T4A_REQUIRE_PTR(tensors[i]);
-            views.push_back(tensors[i]->view());
-        }
+        const std::vector<TensorView> views = handle_list(tensors, n_tensors, "tensors[i] is null", [](const t4a_gpu_tensor& t) { return t.view(); });
         const std::vector<int64_t> retain(retain_labels, retain_labels + n_retain);
         (void)plan_contract_network(views, retain); // (argument errors before the device is touched)
         std::lock_guard<std::mutex> lock(g_dense_mutex);
@@ -2819,11 +3066,7 @@ t4a_gpu_status t4a_gpu_tensor_outer_product(const t4a_gpu_tensor* a, const t4a_g
         T4A_REQUIRE_PTR(out);
         *out = nullptr;
         const TensorView va = a->view(), vb = b->view();
-        for (int64_t l : va.labels)
-            if (std::find(vb.labels.begin(), vb.labels.end(), l) != vb.labels.end())
-                throw Error(T4A_GPU_INVALID_ARGUMENT, "outer_product: the operands share an index; use contract for a contraction");
-        const ContractPlan plan = plan_contract_pair(va, vb); // (no common label: M x 1 times 1 x N)
-        *out = contract_to_handle(va, vb, plan);
+        *out = contract_to_handle(va, vb, plan_outer_product(va, vb));
     });
 }
 
@@ -2835,42 +3078,13 @@ t4a_gpu_status t4a_gpu_tensor_tensordot(const t4a_gpu_tensor* a, const t4a_gpu_t
         T4A_REQUIRE_PTR(b);
         T4A_REQUIRE_PTR(out);
         *out = nullptr;
-        if (n_pairs == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "tensordot: No pairs specified for contraction");
-        T4A_REQUIRE_PTR(labels_a);
-        T4A_REQUIRE_PTR(labels_b);
+        if (n_pairs) {
+            T4A_REQUIRE_PTR(labels_a);
+            T4A_REQUIRE_PTR(labels_b);
+        }
         const TensorView va = a->view();
         TensorView vb = b->view();
-        // prepare_contraction_pairs (index_ops.rs): every pair names one axis of each operand, no axis twice, equal dimensions; a label the
-        // operands have in common that is not paired would be a batch contraction (not implemented in the reference either)
-        std::vector<size_t> ax_a, ax_b;
-        for (size_t p = 0; p < n_pairs; ++p) {
-            const auto ia = std::find(va.labels.begin(), va.labels.end(), labels_a[p]);
-            const auto ib = std::find(vb.labels.begin(), vb.labels.end(), labels_b[p]);
-            if (ia == va.labels.end()) throw Error(T4A_GPU_INVALID_ARGUMENT, "tensordot: Index not found in self tensor");
-            if (ib == vb.labels.end()) throw Error(T4A_GPU_INVALID_ARGUMENT, "tensordot: Index not found in other tensor");
-            const size_t pa = (size_t)(ia - va.labels.begin()), pb = (size_t)(ib - vb.labels.begin());
-            if (std::find(ax_a.begin(), ax_a.end(), pa) != ax_a.end())
-                throw Error(T4A_GPU_INVALID_ARGUMENT, "tensordot: Duplicate axis " + std::to_string(pa) + " in self tensor");
-            if (std::find(ax_b.begin(), ax_b.end(), pb) != ax_b.end())
-                throw Error(T4A_GPU_INVALID_ARGUMENT, "tensordot: Duplicate axis " + std::to_string(pb) + " in other tensor");
-            if (va.dims[pa] != vb.dims[pb])
-                throw Error(T4A_GPU_INVALID_ARGUMENT, "tensordot: Dimension mismatch: self[" + std::to_string(pa) + "]=" + std::to_string(va.dims[pa]) +
-                                                          " != other[" + std::to_string(pb) + "]=" + std::to_string(vb.dims[pb]));
-            ax_a.push_back(pa);
-            ax_b.push_back(pb);
-        }
-        for (size_t i = 0; i < va.labels.size(); ++i)
-            for (size_t j = 0; j < vb.labels.size(); ++j)
-                if (va.labels[i] == vb.labels[j]) {
-                    bool paired = false;
-                    for (size_t p = 0; p < n_pairs; ++p) paired = paired || (ax_a[p] == i && ax_b[p] == j);
-                    if (!paired)
-                        throw Error(T4A_GPU_NOT_IMPLEMENTED,
-                                    "tensordot: Common index found but not in contraction pairs. Batch contraction is not yet implemented.");
-                }
-        // the paired axes of `b` take the labels of their partners; unpaired axes keep theirs (none is shared, checked above)
-        for (size_t p = 0; p < n_pairs; ++p) vb.labels[ax_b[p]] = va.labels[ax_a[p]];
-        const ContractPlan plan = plan_contract_pair(va, vb);
+        const ContractPlan plan = plan_tensordot(va, vb, labels_a, labels_b, n_pairs);
         *out = contract_to_handle(va, vb, plan);
     });
 }
@@ -2967,14 +3181,6 @@ t4a_gpu_status t4a_gpu_tensor_factorize(const t4a_gpu_tensor* t, const int64_t* 
 }
 
 // ---- SimpleTensorTrain arithmetic ----
-extern "C++" {
-static t4a_gpu_tt* wrap_tt(std::unique_ptr<TensorTrain> r)
-{
-    r->eng.sync();
-    return new t4a_gpu_tt(r->cores, r->eng.stream());
-}
-} // extern "C++"
-
 t4a_gpu_status t4a_gpu_tt_add(const t4a_gpu_tt* a, const t4a_gpu_tt* b, t4a_gpu_tt** out)
 {
     return guarded([&] {
@@ -3037,37 +3243,6 @@ t4a_gpu_status t4a_gpu_tt_partial_sum(const t4a_gpu_tt* h, const size_t* dims, s
 }
 
 // ---- gauge forms: SiteTensorTrain, VidalTensorTrain, InverseTensorTrain (tt_canonical.hip) ----
-extern "C++" {
-static void cores_dims(const std::vector<DevCore>& cores, size_t* dims3)
-{
-    if (!cores.empty()) T4A_REQUIRE_PTR(dims3);
-    for (size_t s = 0; s < cores.size(); ++s) {
-        dims3[3 * s] = cores[s].l;
-        dims3[3 * s + 1] = cores[s].s;
-        dims3[3 * s + 2] = cores[s].r;
-    }
-}
-static void core_to_host(Engine* eng, const std::vector<DevCore>& cores, size_t site, double* out)
-{
-    if (site >= cores.size()) throw Error(T4A_GPU_INVALID_ARGUMENT, "site " + std::to_string(site) + " is out of range for " + std::to_string(cores.size()) + " tensors");
-    const DevCore& c = cores[site];
-    if (c.size() == 0) return;
-    T4A_REQUIRE_PTR(out);
-    T4A_HIP(hipMemcpyAsync(out, c.buf.get(), c.size() * sizeof(double), hipMemcpyDeviceToHost, eng->stream()));
-    eng->sync();
-}
-static void vector_out(const std::vector<double>& v, double* out, size_t capacity, size_t* len)
-{
-    T4A_REQUIRE_PTR(len);
-    *len = v.size();
-    if (!out) return;
-    if (capacity < v.size())
-        throw Error(T4A_GPU_BUFFER_TOO_SMALL, "output capacity " + std::to_string(capacity) + " is below " + std::to_string(v.size()));
-    if (!v.empty()) std::memcpy(out, v.data(), v.size() * sizeof(double));
-}
-static t4a_gpu_tt* tt_from_cores(const std::vector<DevCore>& cores, hipStream_t stream) { return new t4a_gpu_tt(cores, stream); }
-} // extern "C++"
-
 t4a_gpu_status t4a_gpu_site_tt_from_tt(const t4a_gpu_tt* tt, size_t center, t4a_gpu_site_tt** out)
 {
     return guarded([&] {
@@ -3419,36 +3594,12 @@ t4a_gpu_status t4a_gpu_tt_to_tensors(const t4a_gpu_tt* tt, const int64_t* site_l
         T4A_REQUIRE_PTR(out);
         if (n > 1) T4A_REQUIRE_PTR(bond_labels);
         for (size_t s = 0; s < n; ++s) out[s] = nullptr;
-        std::vector<int64_t> all(site_labels, site_labels + n);
-        if (n > 1) all.insert(all.end(), bond_labels, bond_labels + n - 1);
-        std::sort(all.begin(), all.end());
-        if (std::adjacent_find(all.begin(), all.end()) != all.end())
-            throw Error(T4A_GPU_INVALID_ARGUMENT, "tensor_train_to_treetn: site and bond indices must be distinct");
         std::lock_guard<std::mutex> lock(g_dense_mutex);
-        Engine& e = dense_engine();
-        const_cast<t4a_gpu_tt*>(tt)->impl.eng.sync();
-        std::vector<std::unique_ptr<t4a_gpu_tensor>> made;
-        for (size_t s = 0; s < n; ++s) {
-            const DevCore& c = tt->impl.cores[s];
-            std::vector<size_t> dims;
-            std::vector<int64_t> labels;
-            if (s > 0) {
-                dims.push_back(c.l);
-                labels.push_back(bond_labels[s - 1]);
-            }
-            dims.push_back(c.s);
-            labels.push_back(site_labels[s]);
-            if (s + 1 < n) {
-                dims.push_back(c.r);
-                labels.push_back(bond_labels[s]);
-            }
-            auto t = make_tensor(dims, labels); // boundary legs have dimension 1: the column-major data is unchanged
-            if (c.size())
-                T4A_HIP(hipMemcpyAsync(t->buf.get(), c.buf.get(), c.size() * sizeof(double), hipMemcpyDeviceToDevice, e.stream()));
-            made.push_back(std::move(t));
-        }
-        e.sync();
-        for (size_t s = 0; s < n; ++s) out[s] = made[s].release();
+        require_distinct_chain_labels(site_labels, bond_labels, n);
+        std::vector<OwnedTensor> made = chain_to_tensors(dense_engine(), const_cast<t4a_gpu_tt*>(tt)->impl.eng, tt->impl.cores, site_labels, bond_labels);
+        std::vector<std::unique_ptr<t4a_gpu_tensor>> handles;
+        for (OwnedTensor& t : made) handles.push_back(make_tensor(std::move(t)));
+        for (size_t s = 0; s < n; ++s) out[s] = handles[s].release();
     });
 }
 
@@ -3463,50 +3614,11 @@ t4a_gpu_status t4a_gpu_tensors_to_tt(const t4a_gpu_tensor* const* tensors, size_
             return;
         }
         T4A_REQUIRE_PTR(tensors);
-        for (size_t s = 0; s < n_sites; ++s) T4A_REQUIRE_PTR(tensors[s]);
-        auto shared = [&](size_t a, size_t b) { // the one label two neighbours share
-            std::vector<int64_t> common;
-            for (int64_t l : tensors[a]->labels)
-                if (std::find(tensors[b]->labels.begin(), tensors[b]->labels.end(), l) != tensors[b]->labels.end()) common.push_back(l);
-            if (common.size() != 1)
-                throw Error(T4A_GPU_INVALID_ARGUMENT, "treetn_to_tensor_train: missing chain edge between nodes " + std::to_string(a) + " and " +
-                                                          std::to_string(b));
-            return common[0];
-        };
-        std::vector<int64_t> bonds(n_sites > 0 ? n_sites - 1 : 0);
-        for (size_t s = 0; s + 1 < n_sites; ++s) bonds[s] = shared(s, s + 1);
-        for (size_t a = 0; a < n_sites; ++a) // a chain: no label may connect nodes that are not neighbours
-            for (size_t b = a + 2; b < n_sites; ++b)
-                for (int64_t l : tensors[a]->labels)
-                    if (std::find(tensors[b]->labels.begin(), tensors[b]->labels.end(), l) != tensors[b]->labels.end())
-                        throw Error(T4A_GPU_INVALID_ARGUMENT, "treetn_to_tensor_train: expected a chain with " + std::to_string(n_sites - 1) + " edges");
+        const std::vector<TensorView> views = handle_list(tensors, n_sites, "tensors[s] is null", [](const t4a_gpu_tensor& t) { return t.view(); });
+        const ChainPlan plan = plan_tensors_to_chain(views); // (argument errors before the device is touched)
         std::lock_guard<std::mutex> lock(g_dense_mutex);
         Engine& e = dense_engine();
-        std::vector<DevCore> cores(n_sites);
-        for (size_t s = 0; s < n_sites; ++s) {
-            const t4a_gpu_tensor* t = tensors[s];
-            const size_t want = 1 + (s > 0 ? 1 : 0) + (s + 1 < n_sites ? 1 : 0);
-            if (t->labels.size() != want)
-                throw Error(T4A_GPU_INVALID_ARGUMENT, "treetn_to_tensor_train: node " + std::to_string(s) + " must have exactly one site index");
-            std::vector<size_t> perm;
-            auto pos = [&](int64_t l) { return (size_t)(std::find(t->labels.begin(), t->labels.end(), l) - t->labels.begin()); };
-            size_t site_axis = 0;
-            for (size_t a = 0; a < t->labels.size(); ++a)
-                if ((s == 0 || t->labels[a] != bonds[s - 1]) && (s + 1 >= n_sites || t->labels[a] != bonds[s])) site_axis = a;
-            if (s > 0) perm.push_back(pos(bonds[s - 1]));
-            perm.push_back(site_axis);
-            if (s + 1 < n_sites) perm.push_back(pos(bonds[s]));
-            DevCore& c = cores[s];
-            c.l = s > 0 ? t->dims[perm[0]] : 1;
-            c.s = t->dims[site_axis];
-            c.r = s + 1 < n_sites ? t->dims[perm.back()] : 1;
-            if (c.l == 0 || c.s == 0 || c.r == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "treetn_to_tensor_train: a resulting core has a zero dimension");
-            c.buf.reserve(c.size());
-            tensor_permute(e, t->view(), perm, c.buf.get());
-        }
-        T4A_HIP(hipGetLastError());
-        e.sync();
-        *out = new t4a_gpu_tt(cores, e.stream());
+        *out = new t4a_gpu_tt(tensors_to_chain(e, views, plan), e.stream());
     });
 }
 
@@ -3531,56 +3643,6 @@ t4a_gpu_status t4a_gpu_aci_options_default(t4a_gpu_aci_options* o)
     });
 }
 
-} // extern "C"
-
-struct t4a_gpu_aci_problem {
-    std::unique_ptr<t4a::AciProblem> impl;
-};
-
-namespace {
-AciOptions convert_aci(const t4a_gpu_aci_options* o)
-{
-    AciOptions a;
-    if (o) {
-        a.max_iters = o->max_iters;
-        a.min_iters = o->min_iters;
-        a.has_max_bond_dim = o->has_max_bond_dim != 0;
-        a.max_bond_dim = o->max_bond_dim;
-        a.tolerance = o->tolerance;
-        a.scale_tolerance = o->scale_tolerance != 0;
-        a.rng_seed = o->rng_seed;
-        a.enable_global_guard = o->enable_global_guard != 0;
-        a.nsearch_global_pivots = o->nsearch_global_pivots;
-        a.max_nglobal_pivot = o->max_nglobal_pivot;
-        a.nsweeps_global_search = o->nsweeps_global_search;
-        a.tol_margin_global_search = o->tol_margin_global_search;
-    }
-    return a;
-}
-AciHostOp make_aci_op(int32_t kind, t4a_gpu_aci_op_fn op, void* user)
-{
-    if (kind < 0 || kind > 2) throw Error(T4A_GPU_INVALID_ARGUMENT, "unknown ACI operator kind");
-    if (kind != 0) return {};
-    if (!op) throw Error(T4A_GPU_NULL_POINTER, "operator callback is null");
-    return [op, user](const double* v, size_t K, size_t np, double* out) {
-        if (op(user, v, K, np, out) != 0) throw Error(T4A_GPU_CALLBACK_ERROR, "operator callback reported an error");
-    };
-}
-std::vector<TensorTrain*> aci_inputs(const t4a_gpu_tt* const* inputs, size_t n)
-{
-    if (n == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "inputs must not be empty");
-    if (!inputs) throw Error(T4A_GPU_NULL_POINTER, "inputs is null");
-    std::vector<TensorTrain*> v(n);
-    for (size_t k = 0; k < n; ++k) {
-        if (!inputs[k]) throw Error(T4A_GPU_NULL_POINTER, "input tensor train is null");
-        v[k] = const_cast<TensorTrain*>(&inputs[k]->impl);
-    }
-    return v;
-}
-} // namespace
-
-extern "C" {
-
 t4a_gpu_status t4a_gpu_aci_elementwise(const t4a_gpu_tt* const* inputs, size_t n_inputs, int32_t op_kind, t4a_gpu_aci_op_fn op,
                                        void* user, const t4a_gpu_aci_options* options, const t4a_gpu_tt* initial_guess,
                                        t4a_gpu_tt** result, size_t* n_iters, size_t* ranks, double* errors,
@@ -3592,7 +3654,7 @@ t4a_gpu_status t4a_gpu_aci_elementwise(const t4a_gpu_tt* const* inputs, size_t n
         const AciOptions o = convert_aci(options);
         o.validate();
         std::vector<TensorTrain*> in = aci_inputs(inputs, n_inputs);
-        AciHostOp hop = make_aci_op(op_kind, op, user);
+        AciHostOp hop = aci_host_op(aci_op_kind(op_kind, "unknown ACI operator kind"), op, user, "operator callback is null", "operator callback reported an error");
         require_device();
         if (n_iters) *n_iters = 0;
         if (in[0] && in[0]->len() == 1) {
@@ -3626,7 +3688,7 @@ t4a_gpu_status t4a_gpu_aci_problem_new(const t4a_gpu_tt* const* inputs, size_t n
         const AciOptions o = convert_aci(options);
         o.validate();
         std::vector<TensorTrain*> in = aci_inputs(inputs, n_inputs);
-        AciHostOp hop = make_aci_op(op_kind, op, user);
+        AciHostOp hop = aci_host_op(aci_op_kind(op_kind, "unknown ACI operator kind"), op, user, "operator callback is null", "operator callback reported an error");
         require_device();
         auto h = std::make_unique<t4a_gpu_aci_problem>();
         h->impl = std::make_unique<AciProblem>(in, initial_guess ? &initial_guess->impl : nullptr, o, (AciOpKind)op_kind, hop);
@@ -3655,7 +3717,7 @@ t4a_gpu_status t4a_gpu_treeaci_local_update_f64(size_t n_inputs, const size_t* b
         T4A_REQUIRE_PTR(left);
         T4A_REQUIRE_PTR(right);
         T4A_REQUIRE_PTR(sampled_scale);
-        if (op_kind < 0 || op_kind > 2) throw Error(T4A_GPU_INVALID_ARGUMENT, "unknown operator kind");
+        const AciOpKind kind = aci_op_kind(op_kind, "unknown operator kind");
         checked_mul(row_count, col_count, "local matrix elements");
         require_int_dims({row_count, col_count}, "local matrix shape");
         std::vector<size_t> bd(bond_dims, bond_dims + n_inputs);
@@ -3665,15 +3727,9 @@ t4a_gpu_status t4a_gpu_treeaci_local_update_f64(size_t n_inputs, const size_t* b
             rf[k] = row_frames[k];
             cf[k] = col_frames[k];
         }
-        AciHostOp host;
-        if (op_kind == T4A_GPU_ACI_OP_CALLBACK) {
-            T4A_REQUIRE_PTR(op);
-            host = [op, user](const double* values, size_t ni, size_t npts, double* out) {
-                if (op(user, values, ni, npts, out) != 0) throw Error(T4A_GPU_CALLBACK_ERROR, "elementwise operator callback failed");
-            };
-        }
+        const AciHostOp host = aci_host_op(kind, op, user, "op is null", "elementwise operator callback failed");
         std::lock_guard<std::mutex> lock(g_dense_mutex);
-        TreeAciLocalResult r = treeaci_local_update(dense_engine(), bd, rf, cf, row_count, col_count, (AciOpKind)op_kind, host, max_bond_dim,
+        TreeAciLocalResult r = treeaci_local_update(dense_engine(), bd, rf, cf, row_count, col_count, kind, host, max_bond_dim,
                                                     tolerance, scale_tolerance != 0, left_orthogonal != 0);
         *rank = r.rank;
         for (size_t i = 0; i < r.rank; ++i) {
@@ -3702,14 +3758,7 @@ t4a_gpu_status t4a_gpu_aci_problem_add_global_pivots(t4a_gpu_aci_problem* h, con
     return guarded([&] {
         T4A_REQUIRE_PTR(h);
         if (n_pivots) T4A_REQUIRE_PTR(pivots);
-        const size_t n = h->impl->len();
-        std::vector<std::vector<uint32_t>> pv(n_pivots, std::vector<uint32_t>(n));
-        for (size_t p = 0; p < n_pivots; ++p)
-            for (size_t s = 0; s < n; ++s) {
-                if (pivots[s + n * p] > 0xFFFFFFFFull) throw Error(T4A_GPU_INVALID_ARGUMENT, "global pivot index out of bounds");
-                pv[p][s] = (uint32_t)pivots[s + n * p];
-            }
-        const size_t a = h->impl->add_global_pivots(pv);
+        const size_t a = h->impl->add_global_pivots(narrow_pivots(pivots, n_pivots, h->impl->len(), "global pivot index out of bounds"));
         if (added) *added = a;
     });
 }
@@ -3759,7 +3808,6 @@ t4a_gpu_status t4a_gpu_aci_problem_errors(const t4a_gpu_aci_problem* h, double* 
         if (pivot_scales) std::copy(h->impl->pivot_scales.begin(), h->impl->pivot_scales.end(), pivot_scales);
     });
 }
-
 
 // ---- MPO<f64> and its contraction (tensor4all-simplett/src/mpo/) ----
 t4a_gpu_status t4a_gpu_mpo_new(const size_t* dims4, size_t n_sites, const double* cores, t4a_gpu_mpo** out)
@@ -3952,21 +4000,6 @@ t4a_gpu_status t4a_gpu_mpo_fit_half(const double* env, size_t n_env, int32_t sid
 }
 
 // ---- partial contraction of two MPOs (mpo.hpp: mpo_partial_contract) ----
-namespace {
-PartialSpec partial_spec(const size_t* contract_pairs, size_t n_contract, const size_t* diagonal_pairs, size_t n_diagonal, size_t n_output_order)
-{
-    PartialSpec spec;
-    if (n_contract) T4A_REQUIRE_PTR(contract_pairs);
-    if (n_diagonal) T4A_REQUIRE_PTR(diagonal_pairs);
-    for (size_t i = 0; i < n_contract; ++i)
-        spec.contract_pairs.push_back({contract_pairs[4 * i], contract_pairs[4 * i + 1], contract_pairs[4 * i + 2], contract_pairs[4 * i + 3]});
-    for (size_t i = 0; i < n_diagonal; ++i)
-        spec.diagonal_pairs.push_back({diagonal_pairs[4 * i], diagonal_pairs[4 * i + 1], diagonal_pairs[4 * i + 2], diagonal_pairs[4 * i + 3]});
-    spec.has_output_order = n_output_order != 0;
-    return spec;
-}
-} // namespace
-
 t4a_gpu_status t4a_gpu_mpo_partial_plan(const size_t* a_site_dims, size_t n_a, const size_t* b_site_dims, size_t n_b,
                                         const size_t* contract_pairs, size_t n_contract, const size_t* diagonal_pairs, size_t n_diagonal,
                                         size_t n_output_order, size_t* out_site_dims, size_t* out_leg_dims)
@@ -4114,25 +4147,6 @@ t4a_gpu_status t4a_gpu_contraction_evaluate(t4a_gpu_contraction* h, const size_t
     });
 }
 
-extern "C++" {
-static void contraction_environment(t4a_gpu_contraction* h, bool left, size_t n, const size_t* idx, size_t n_pts, double* out, size_t* dims2)
-{
-    T4A_REQUIRE_PTR(h);
-    T4A_REQUIRE_PTR(dims2);
-    const std::array<size_t, 2> d = left ? h->impl->left_dims(n) : h->impl->right_dims(n); // n out of range is refused here
-    dims2[0] = d[0];
-    dims2[1] = d[1];
-    if (n_pts == 0) return;
-    T4A_REQUIRE_PTR(idx);
-    T4A_REQUIRE_PTR(out);
-    std::vector<uint32_t> u = narrow_indices(idx, checked_mul(n_pts, 2 * h->impl->len(), "index buffer"));
-    if (left)
-        h->impl->evaluate_left(n, u.data(), n_pts, out, dims2);
-    else
-        h->impl->evaluate_right(n, u.data(), n_pts, out, dims2);
-}
-} // extern "C++"
-
 t4a_gpu_status t4a_gpu_contraction_evaluate_left(t4a_gpu_contraction* h, size_t n, const size_t* idx, size_t n_pts, double* out, size_t* dims2)
 {
     return guarded([&] { contraction_environment(h, true, n, idx, n_pts, out, dims2); });
@@ -4199,24 +4213,12 @@ t4a_gpu_status t4a_gpu_mpo_contract_tci(const t4a_gpu_mpo* a, const t4a_gpu_mpo*
         *out_mpo = nullptr;
         if (n_pivots) T4A_REQUIRE_PTR(initial_pivots);
         const TCI2Options o = convert_options(options);
-        const size_t ns = a->impl->len();
-        std::vector<std::vector<uint32_t>> piv(n_pivots, std::vector<uint32_t>(ns));
-        for (size_t k = 0; k < n_pivots; ++k)
-            for (size_t s = 0; s < ns; ++s) {
-                const size_t v = initial_pivots[s + ns * k];
-                if (v > 0xFFFFFFFFull) throw Error(T4A_GPU_INVALID_ARGUMENT, "pivot value out of bounds");
-                piv[k][s] = (uint32_t)v;
-            }
+        std::vector<std::vector<uint32_t>> piv = narrow_pivots(initial_pivots, n_pivots, a->impl->len(), "pivot value out of bounds");
         *out_mpo = new t4a_gpu_mpo{mpo_contract_tci(*a->impl, *b->impl, o, std::move(piv), info)};
     });
 }
 
 // ---- candidate matrices of A·B on the device: the entries below answer INVALID_ARGUMENT for NULL (t4a_gpu.h) ----
-#define T4A_REQUIRE_ARG(p)                                                            \
-    do {                                                                              \
-        if ((p) == nullptr) throw ::t4a::Error(T4A_GPU_INVALID_ARGUMENT, #p " is null"); \
-    } while (0)
-
 t4a_gpu_status t4a_gpu_contraction_evaluate_matrix(t4a_gpu_contraction* h, size_t cut, const size_t* rows, size_t n_rows, const size_t* cols,
                                                    size_t n_cols, double* out)
 {
@@ -4264,14 +4266,7 @@ t4a_gpu_status t4a_gpu_mpo_contract_tci_device(const t4a_gpu_mpo* a, const t4a_g
         T4A_REQUIRE_ARG(info);
         if (n_pivots) T4A_REQUIRE_ARG(initial_pivots);
         const TCI2Options o = convert_options(options);
-        const size_t ns = a->impl->len();
-        std::vector<std::vector<uint32_t>> piv(n_pivots, std::vector<uint32_t>(ns));
-        for (size_t k = 0; k < n_pivots; ++k)
-            for (size_t s = 0; s < ns; ++s) {
-                const size_t v = initial_pivots[s + ns * k];
-                if (v > 0xFFFFFFFFull) throw Error(T4A_GPU_INVALID_ARGUMENT, "pivot value out of bounds");
-                piv[k][s] = (uint32_t)v;
-            }
+        std::vector<std::vector<uint32_t>> piv = narrow_pivots(initial_pivots, n_pivots, a->impl->len(), "pivot value out of bounds");
         *out_mpo = new t4a_gpu_mpo{mpo_contract_tci(*a->impl, *b->impl, o, std::move(piv), info, true)};
     });
 }
@@ -4414,30 +4409,6 @@ t4a_gpu_status t4a_gpu_linsolve_options_default(t4a_gpu_linsolve_options* out)
         out->convergence_tol = d.convergence_tol;
         out->check_residual = d.check_residual;
     });
-}
-
-extern "C++" {
-static LinsolveOptions convert_linsolve_options(const t4a_gpu_linsolve_options* p)
-{
-    LinsolveOptions o;
-    o.nfullsweeps = p->nfullsweeps;
-    o.has_max_bond_dim = p->has_max_bond_dim != 0;
-    o.max_bond_dim = p->max_bond_dim;
-    o.has_svd_policy = p->has_svd_policy != 0;
-    if (o.has_svd_policy) o.svd_policy = from_c(p->svd_policy);
-    o.gmres_tol = p->gmres_tol;
-    if (p->gmres_tolerance_mode != 0 && p->gmres_tolerance_mode != 1) throw Error(T4A_GPU_INVALID_ARGUMENT, "unknown gmres_tolerance_mode");
-    o.gmres_tolerance_mode = (GmresToleranceMode)p->gmres_tolerance_mode;
-    o.gmres_max_restarts = p->gmres_max_restarts;
-    o.gmres_restart_dim = p->gmres_restart_dim;
-    o.a0 = p->a0;
-    o.a1 = p->a1;
-    o.has_convergence_tol = p->has_convergence_tol != 0;
-    o.convergence_tol = p->convergence_tol;
-    o.check_residual = p->check_residual != 0;
-    o.validate();
-    return o;
-}
 }
 
 t4a_gpu_status t4a_gpu_linsolve_check_shapes(const size_t* op_dims4, size_t n_op, const size_t* rhs_dims3, size_t n_rhs,
@@ -4697,35 +4668,6 @@ t4a_gpu_status t4a_gpu_dmrg_options_default(t4a_gpu_dmrg_options* out)
     });
 }
 
-extern "C++" {
-static LanczosOptions convert_lanczos_options(const t4a_gpu_lanczos_options& p)
-{
-    LanczosOptions o;
-    o.max_iter = p.max_iter;
-    o.rtol = p.rtol;
-    o.atol = p.atol;
-    o.breakdown_tol = p.breakdown_tol;
-    o.hermitian_tol = p.hermitian_tol;
-    return o;
-}
-static DmrgOptions convert_dmrg_options(const t4a_gpu_dmrg_options* p)
-{
-    DmrgOptions o;
-    o.nsite = p->nsite;
-    o.nsweeps = p->nsweeps;
-    o.has_max_bond_dim = p->has_max_bond_dim != 0;
-    o.max_bond_dim = p->max_bond_dim;
-    o.has_svd_policy = p->has_svd_policy != 0;
-    if (o.has_svd_policy) o.svd_policy = from_c(p->svd_policy);
-    o.lanczos = convert_lanczos_options(p->lanczos);
-    o.has_energy_tol = p->has_energy_tol != 0;
-    o.energy_tol = p->energy_tol;
-    o.real_scalar_tol = p->real_scalar_tol;
-    o.validate();
-    return o;
-}
-}
-
 t4a_gpu_status t4a_gpu_dmrg_check_shapes(const size_t* op_dims4, size_t n_op, const size_t* state_dims3, size_t n_state, size_t center,
                                          size_t max_iter)
 {
@@ -4854,35 +4796,6 @@ t4a_gpu_status t4a_gpu_tdvp_options_default(t4a_gpu_tdvp_options* out)
     });
 }
 
-extern "C++" {
-static KrylovExpmOptions convert_krylov_expm_options(const t4a_gpu_krylov_expm_options& p)
-{
-    KrylovExpmOptions o;
-    o.max_iter = p.max_iter;
-    o.max_time_splits = p.max_time_splits;
-    o.tol = p.tol;
-    o.breakdown_tol = p.breakdown_tol;
-    o.hermitian_tol = p.hermitian_tol;
-    return o;
-}
-static TdvpOptions convert_tdvp_options(const t4a_gpu_tdvp_options* p)
-{
-    TdvpOptions o;
-    o.nsite = p->nsite;
-    o.nsweeps = p->nsweeps;
-    o.order = p->order;
-    o.exponent_step_re = p->exponent_step_re;
-    o.exponent_step_im = p->exponent_step_im;
-    o.has_max_bond_dim = p->has_max_bond_dim != 0;
-    o.max_bond_dim = p->max_bond_dim;
-    o.has_svd_policy = p->has_svd_policy != 0;
-    if (o.has_svd_policy) o.svd_policy = from_c(p->svd_policy);
-    o.krylov = convert_krylov_expm_options(p->krylov);
-    o.validate();
-    return o;
-}
-}
-
 t4a_gpu_status t4a_gpu_tdvp_check_shapes(const size_t* op_dims4, size_t n_op, const size_t* state_dims3, size_t n_state, size_t center,
                                          size_t max_iter)
 {
@@ -4986,48 +4899,6 @@ t4a_gpu_status t4a_gpu_gse_options_default(t4a_gpu_gse_options* out)
         out->normalize_references = d.normalize_references;
         out->expand_before_first_sweep = d.expand_before_first_sweep;
     });
-}
-
-extern "C++" {
-static GseOptions convert_gse_options(const t4a_gpu_gse_options* p)
-{
-    GseOptions o;
-    o.krylov_dim = p->krylov_dim;
-    o.has_reference_max_bond_dim = p->has_reference_max_bond_dim != 0;
-    o.reference_max_bond_dim = p->reference_max_bond_dim;
-    o.has_reference_svd_policy = p->has_reference_svd_policy != 0;
-    if (o.has_reference_svd_policy) o.reference_svd_policy = from_c(p->reference_svd_policy);
-    o.density_weight_cutoff = p->density_weight_cutoff;
-    o.hermitian_tol = p->hermitian_tol;
-    o.normalize_references = p->normalize_references != 0;
-    o.expand_before_first_sweep = p->expand_before_first_sweep != 0;
-    o.validate();
-    return o;
-}
-static void gse_counters(const GseResult& r, size_t* references_built, size_t* edges_processed, size_t* bonds_expanded, size_t* max_added_basis)
-{
-    *references_built = r.references_built;
-    *edges_processed = r.edges_processed;
-    *bonds_expanded = r.bonds_expanded;
-    *max_added_basis = r.max_added_basis;
-}
-// the ragged shape lists of the hooks as ints: every entry positive, at most `max_jobs` of them
-static std::vector<int> gse_int_list(const size_t* v, size_t n, size_t max_jobs, const char* who)
-{
-    if (n == 0 || n > max_jobs) throw Error(T4A_GPU_INVALID_ARGUMENT, std::string(who) + ": between 1 and " + std::to_string(max_jobs) + " operands");
-    T4A_REQUIRE_PTR(v);
-    std::vector<int> out(n);
-    for (size_t i = 0; i < n; ++i) {
-        if (v[i] == 0 || v[i] > (size_t)INT_MAX) throw Error(T4A_GPU_INVALID_ARGUMENT, std::string(who) + ": every dimension must be positive and at most INT_MAX");
-        out[i] = (int)v[i];
-    }
-    return out;
-}
-static void gse_require_fits(size_t a, size_t b, const char* who)
-{
-    if (a == 0 || b == 0 || a > (size_t)INT_MAX || b > (size_t)INT_MAX / a)
-        throw Error(T4A_GPU_INVALID_ARGUMENT, std::string(who) + ": every dimension must be positive and every matrix within INT_MAX elements");
-}
 }
 
 t4a_gpu_status t4a_gpu_gse_check_shapes(const t4a_gpu_gse_options* options, const size_t* state_dims3, size_t n_state, const size_t* ref_dims3,
@@ -5220,40 +5091,6 @@ t4a_gpu_status t4a_gpu_gse_time_routes(size_t chi, size_t d, size_t K, size_t re
 }
 
 // ---- partitioned MPOs (pmpo.hpp): projector.rs, contraction_tasks and the handle ----
-static std::vector<LegProjector> projector_list(const size_t* entries, const size_t* counts, size_t n)
-{
-    std::vector<LegProjector> v(n);
-    if (n) T4A_REQUIRE_PTR(counts);
-    size_t off = 0;
-    for (size_t k = 0; k < n; ++k) {
-        v[k] = projector_from_triples(entries ? entries + 3 * off : nullptr, counts[k]);
-        off += counts[k];
-    }
-    return v;
-}
-
-static void projector_out(const LegProjector& p, size_t* out, size_t* out_count)
-{
-    T4A_REQUIRE_PTR(out_count);
-    *out_count = p.size();
-    if (!out) return;
-    size_t i = 0;
-    for (const auto& kv : p) {
-        out[3 * i] = kv.first.first;
-        out[3 * i + 1] = kv.first.second;
-        out[3 * i + 2] = kv.second;
-        ++i;
-    }
-}
-
-static SiteDims site_dims_list(const size_t* site_dims, size_t n_sites)
-{
-    if (n_sites) T4A_REQUIRE_PTR(site_dims);
-    SiteDims sd(n_sites);
-    for (size_t i = 0; i < n_sites; ++i) sd[i] = {site_dims[2 * i], site_dims[2 * i + 1]};
-    return sd;
-}
-
 t4a_gpu_status t4a_gpu_projector_validate(const size_t* site_dims, size_t n_sites, const size_t* p, size_t count)
 {
     return guarded([&] { projector_validate(projector_from_triples(p, count), site_dims_list(site_dims, n_sites)); });
@@ -5385,11 +5222,7 @@ t4a_gpu_status t4a_gpu_pmpo_new(const t4a_gpu_mpo* const* patches, size_t n_patc
         T4A_REQUIRE_PTR(out);
         *out = nullptr;
         if (n_patches) T4A_REQUIRE_PTR(patches);
-        std::vector<Mpo*> ms(n_patches);
-        for (size_t k = 0; k < n_patches; ++k) {
-            T4A_REQUIRE_PTR(patches[k]);
-            ms[k] = patches[k]->impl.get();
-        }
+        const std::vector<Mpo*> ms = handle_list(patches, n_patches, "patches[k] is null", [](const t4a_gpu_mpo& m) { return m.impl.get(); });
         SiteDims sd;
         if (site_dims) sd = site_dims_list(site_dims, n_sites);
         *out = new t4a_gpu_pmpo{PartitionedMpo::from_patches(ms, projector_list(entries, counts, n_patches), site_dims ? &sd : nullptr)};
@@ -5402,28 +5235,7 @@ t4a_gpu_status t4a_gpu_pmpo_from_ptt(const t4a_gpu_ptt* ptt, const size_t* site_
         T4A_REQUIRE_PTR(ptt);
         T4A_REQUIRE_PTR(out);
         *out = nullptr;
-        PartitionedTT& src = *ptt->impl;
-        const size_t n = src.dims.size();
-        SiteDims fused(n), sd(n);
-        for (size_t i = 0; i < n; ++i) {
-            fused[i] = {src.dims[i], 1};
-            sd[i] = site_dims ? std::array<size_t, 2>{site_dims[2 * i], site_dims[2 * i + 1]} : fused[i];
-            if (sd[i][0] == 0 || sd[i][0] * sd[i][1] != src.dims[i])
-                throw Error(T4A_GPU_INVALID_ARGUMENT, "relabel_site_dims: site " + std::to_string(i) + " has " + std::to_string(src.dims[i]) +
-                                                          " fused indices, not " + std::to_string(sd[i][0]) + " * " + std::to_string(sd[i][1]));
-        }
-        auto r = std::make_unique<PartitionedMpo>(sd);
-        for (const SubDomain& p : src.patches) {
-            LegProjector proj;
-            for (const auto& kv : p.projector) {
-                proj[{kv.first, 0}] = kv.second % sd[kv.first][0];
-                proj[{kv.first, 1}] = kv.second / sd[kv.first][0];
-            }
-            auto m = std::make_unique<Mpo>(p.cores, src.eng.stream(), fused);
-            m->relabel_site_dims(sd);
-            r->patches.push_back({proj, std::move(m)});
-        }
-        *out = new t4a_gpu_pmpo{std::move(r)};
+        *out = new t4a_gpu_pmpo{PartitionedMpo::from_ptt(*ptt->impl, site_dims)};
     });
 }
 
@@ -5512,16 +5324,6 @@ t4a_gpu_status t4a_gpu_pmpo_project(const t4a_gpu_pmpo* h, const size_t* p, size
     });
 }
 
-static MpoContractionOptions pmpo_options(double tolerance, size_t max_bond_dim, int32_t method)
-{
-    if (method < 0 || method > 3) throw Error(T4A_GPU_INVALID_ARGUMENT, "unknown factorize method");
-    MpoContractionOptions o;
-    o.tolerance = tolerance;
-    o.max_bond_dim = max_bond_dim;
-    o.method = (MpoFactorizeMethod)method;
-    return o;
-}
-
 t4a_gpu_status t4a_gpu_pmpo_add(const t4a_gpu_pmpo* a, const t4a_gpu_pmpo* b, double tolerance, size_t max_bond_dim, t4a_gpu_pmpo** out)
 {
     return guarded([&] {
@@ -5600,25 +5402,6 @@ t4a_gpu_status t4a_gpu_pmpo_time_contract(const t4a_gpu_pmpo* a, const t4a_gpu_p
 }
 
 // ---- the compress stage as an operation of its own, and for many MPOs in lock step (batch_compress.hpp) ----
-namespace {
-CompressRoute compress_route(int32_t route)
-{
-    if (route < 0 || route > 2) throw Error(T4A_GPU_INVALID_ARGUMENT, "unknown compress route");
-    return (CompressRoute)route;
-}
-std::vector<Mpo*> mpo_list(const t4a_gpu_mpo* const* mpos, size_t count, const char* what)
-{
-    if (count == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, std::string(what) + ": the list is empty");
-    T4A_REQUIRE_PTR(mpos);
-    std::vector<Mpo*> items(count);
-    for (size_t k = 0; k < count; ++k) {
-        if (!mpos[k]) throw Error(T4A_GPU_NULL_POINTER, std::string(what) + ": item " + std::to_string(k) + " is null");
-        items[k] = mpos[k]->impl.get();
-    }
-    return items;
-}
-} // namespace
-
 t4a_gpu_status t4a_gpu_mpo_compress(const t4a_gpu_mpo* mpo, double tolerance, size_t max_bond_dim, t4a_gpu_mpo** out)
 {
     return guarded([&] {
@@ -5733,54 +5516,6 @@ t4a_gpu_status t4a_gpu_pmpo_time_compress(const t4a_gpu_pmpo* a, const t4a_gpu_p
 }
 
 // ---- swap_site_indices on a chain (swap.hpp) ----
-namespace {
-SiteLegs site_legs(size_t n, const size_t* leg_counts, const int64_t* keys, const size_t* dims)
-{
-    SiteLegs legs(n);
-    if (n) T4A_REQUIRE_PTR(leg_counts);
-    size_t at = 0;
-    for (size_t i = 0; i < n; ++i)
-        for (size_t k = 0; k < leg_counts[i]; ++k, ++at) {
-            T4A_REQUIRE_PTR(keys);
-            T4A_REQUIRE_PTR(dims);
-            legs[i].push_back({keys[at], dims[at]});
-        }
-    return legs;
-}
-void write_legs(const SiteLegs& legs, size_t* leg_counts, int64_t* keys, size_t* dims)
-{
-    size_t at = 0;
-    for (size_t i = 0; i < legs.size(); ++i) {
-        if (leg_counts) leg_counts[i] = legs[i].size();
-        for (const SwapLeg& g : legs[i]) {
-            if (keys) keys[at] = g.key;
-            if (dims) dims[at] = g.dim;
-            ++at;
-        }
-    }
-}
-SwapAssignment assignment(const int64_t* keys, const size_t* sites, size_t count)
-{
-    SwapAssignment a;
-    if (count) {
-        T4A_REQUIRE_PTR(keys);
-        T4A_REQUIRE_PTR(sites);
-    }
-    for (size_t k = 0; k < count; ++k) a.push_back({keys[k], sites[k]});
-    return a;
-}
-std::vector<SwapLeg> leg_list(const int64_t* keys, const size_t* dims, size_t count)
-{
-    std::vector<SwapLeg> v;
-    if (count) {
-        T4A_REQUIRE_PTR(keys);
-        T4A_REQUIRE_PTR(dims);
-    }
-    for (size_t k = 0; k < count; ++k) v.push_back({keys[k], dims[k]});
-    return v;
-}
-} // namespace
-
 t4a_gpu_status t4a_gpu_swap_schedule_build(size_t n_sites, const int64_t* cur_keys, const size_t* cur_sites, const size_t* cur_dims,
                                            size_t n_current, const int64_t* target_keys, const size_t* target_sites, size_t n_target,
                                            size_t root, size_t max_passes, const size_t* link_dims, size_t max_bond_dim,

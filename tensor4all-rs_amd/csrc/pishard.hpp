@@ -15,6 +15,7 @@
 
 #include "../../include/t4a_gpu.h"
 #include "common.hpp"
+#include "fnsource.hpp"
 
 namespace t4a {
 
@@ -31,6 +32,17 @@ struct PiShard {
 inline void pi_shard_evaluate(PiShard& ps, t4a_gpu_batch_eval_fn cb, void* cb_ctx, size_t n_sites, const uint32_t* a_digits, size_t wa, size_t a0,
                               size_t na, const uint32_t* b_digits, size_t wb, size_t b0, size_t nb, double* out)
 {
+    if (ps.world == 1) { // one rank evaluates every entry through its callback and gathers nothing
+        std::vector<uint32_t> idx(na * nb * n_sites);
+        for (size_t ia = 0; ia < na; ++ia)
+            for (size_t ib = 0; ib < nb; ++ib) {
+                uint32_t* dst = idx.data() + (ia * nb + ib) * n_sites;
+                std::memcpy(dst + a0, a_digits + ia * wa, wa * sizeof(uint32_t));
+                std::memcpy(dst + b0, b_digits + ib * wb, wb * sizeof(uint32_t));
+            }
+        FnSource::call(cb, cb_ctx, idx.data(), n_sites, na * nb, out, "batch callback", "requested entries");
+        return;
+    }
     const size_t W = ps.world;
     const size_t cbk = (nb + W - 1) / W; // columns per rank (the last blocks may be short or empty)
     const size_t c0 = ps.rank * cbk < nb ? ps.rank * cbk : nb;

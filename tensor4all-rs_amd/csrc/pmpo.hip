@@ -2,6 +2,7 @@
 // runs in gfx950 kernels: the mask launch, the fused pair-product launch and the direct sum of to_mpo (kernels_pmpo.hip), TensorTrain::add, the
 // compress stage and the zip-up of mpo.hip.
 #include "pmpo.hpp"
+#include "patching.hpp"
 
 #include <chrono>
 #include <climits>
@@ -295,6 +296,31 @@ std::unique_ptr<PartitionedMpo> PartitionedMpo::from_patches(const std::vector<M
     for (size_t k = 0; k < ms.size(); ++k)
         out->patches.push_back({projectors[k], std::make_unique<Mpo>(ms[k]->tt.cores, ms[k]->tt.eng.stream(), sd)});
     return out;
+}
+
+std::unique_ptr<PartitionedMpo> PartitionedMpo::from_ptt(PartitionedTT& src, const size_t* site_dims)
+{
+    const size_t n = src.dims.size();
+    SiteDims fused(n), sd(n);
+    for (size_t i = 0; i < n; ++i) {
+        fused[i] = {src.dims[i], 1};
+        sd[i] = site_dims ? std::array<size_t, 2>{site_dims[2 * i], site_dims[2 * i + 1]} : fused[i];
+        if (sd[i][0] == 0 || sd[i][0] * sd[i][1] != src.dims[i])
+            throw Error(T4A_GPU_INVALID_ARGUMENT, "relabel_site_dims: site " + std::to_string(i) + " has " + std::to_string(src.dims[i]) +
+                                                      " fused indices, not " + std::to_string(sd[i][0]) + " * " + std::to_string(sd[i][1]));
+    }
+    auto r = std::make_unique<PartitionedMpo>(sd);
+    for (const SubDomain& p : src.patches) {
+        LegProjector proj;
+        for (const auto& kv : p.projector) {
+            proj[{kv.first, 0}] = kv.second % sd[kv.first][0];
+            proj[{kv.first, 1}] = kv.second / sd[kv.first][0];
+        }
+        auto m = std::make_unique<Mpo>(p.cores, src.eng.stream(), fused);
+        m->relabel_site_dims(sd);
+        r->patches.push_back({proj, std::move(m)});
+    }
+    return r;
 }
 
 double PartitionedMpo::norm()

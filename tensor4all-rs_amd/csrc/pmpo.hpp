@@ -52,6 +52,8 @@ struct PmpoPatch {
     std::unique_ptr<Mpo> mpo;
 };
 
+class PartitionedTT; // patching.hpp
+
 class PartitionedMpo {
 public:
     explicit PartitionedMpo(SiteDims d) : sd(std::move(d)) {}
@@ -60,6 +62,9 @@ public:
     // overlap").  Device copies of the patches are taken; they are not masked (as in the reference) and keep their order.
     static std::unique_ptr<PartitionedMpo> from_patches(const std::vector<Mpo*>& patches, const std::vector<LegProjector>& projectors,
                                                         const SiteDims* site_dims);
+    // a PartitionedTT of fused site indices as a partitioned MPO: site i splits into site_dims[2 i] x site_dims[2 i + 1] (NULL: d x 1),
+    // every projected fused index into its two legs; the patches are copied
+    static std::unique_ptr<PartitionedMpo> from_ptt(PartitionedTT& src, const size_t* site_dims);
     // the host half of from_patches, usable with no patch at hand
     static void validate(const SiteDims& sd, const std::vector<SiteDims>& patch_dims, const std::vector<LegProjector>& projectors);
 

@@ -143,6 +143,21 @@ bool qtci_check_xvals_uniform(const std::vector<std::vector<double>>& xvals)
     return uniform;
 }
 
+std::unique_ptr<QuanticsTci> qtci_from_arrays(const std::vector<std::vector<double>>& xv, t4a_gpu_coord_eval_fn f, void* ctx,
+                                              const QtciOptions& o)
+{
+    const bool uniform = qtci_check_xvals_uniform(xv);
+    std::vector<size_t> rs;
+    for (const auto& x : xv) rs.push_back((size_t)std::log2((double)x.size()));
+    if (!uniform) return std::unique_ptr<QuanticsTci>(new QuanticsTci(QuanticsGrid(rs, o.unfolding, false), f, nullptr, ctx, xv));
+    std::vector<double> lo, up;
+    for (const auto& x : xv) {
+        lo.push_back(x.front());
+        up.push_back(x.back());
+    }
+    return std::unique_ptr<QuanticsTci>(new QuanticsTci(QuanticsGrid(rs, o.unfolding, true, lo, up, true), f, nullptr, ctx, {}));
+}
+
 QuanticsTci::QuanticsTci(const QuanticsGrid& g, t4a_gpu_coord_eval_fn coord_cb, t4a_gpu_grididx_eval_fn grididx_cb, void* ctx,
                          std::vector<std::vector<double>> xvals)
     : grid(g), coord_cb_(coord_cb), grididx_cb_(grididx_cb), ctx_(ctx), xvals_(std::move(xvals))

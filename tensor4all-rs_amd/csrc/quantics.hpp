@@ -102,5 +102,9 @@ std::unique_ptr<TensorTrain> combine_component_tts(std::vector<std::unique_ptr<T
 // quanticscrossinterpolate_from_arrays / _discrete input checks (:322-375, :449-472)
 void qtci_check_sizes(const std::vector<size_t>& sizes);
 bool qtci_check_xvals_uniform(const std::vector<std::vector<double>>& xvals);
+// ... and its grid: 2^R points per variable in the options' unfolding; uniformly spaced coordinates become the grid's own (first and last
+// value as bounds, end point included), others are looked up by grid index.  The interpolation over it, not yet run.
+std::unique_ptr<QuanticsTci> qtci_from_arrays(const std::vector<std::vector<double>>& xvals, t4a_gpu_coord_eval_fn f, void* ctx,
+                                              const QtciOptions& options);
 
 } // namespace t4a

@@ -904,6 +904,72 @@ std::vector<double> Tci2::site_tensor_host(size_t site, size_t dims3[3])
     return h;
 }
 
+void Tci2::site_tensor_device(size_t site, double* d_out)
+{
+    if (site >= len()) throw Error(T4A_GPU_INVALID_ARGUMENT, "site out of range");
+    fill_wait();
+    const DevCore& c = cores[site];
+    if (c.size()) {
+        T4A_HIP(hipMemcpyAsync(d_out, c.buf.get(), c.size() * sizeof(double), hipMemcpyDeviceToDevice, eng.stream()));
+        T4A_HIP(hipStreamSynchronize(eng.stream()));
+    }
+}
+
+void Tci2::set_site_tensor_device(size_t site, const size_t dims3[3], const double* d_in)
+{
+    if (site >= len()) throw Error(T4A_GPU_INVALID_ARGUMENT, "site out of range");
+    if (dims3[1] != local_dims[site]) throw Error(T4A_GPU_INVALID_ARGUMENT, "site dimension mismatch");
+    fill_wait();
+    DevCore& c = cores[site];
+    const size_t count = dims3[0] * dims3[1] * dims3[2];
+    c.reshape(dims3[0], dims3[1], dims3[2]);
+    if (count) {
+        if (!d_in) throw Error(T4A_GPU_NULL_POINTER, "in_device is null");
+        T4A_HIP(hipMemcpyAsync(c.buf.get(), d_in, count * sizeof(double), hipMemcpyDeviceToDevice, eng.stream()));
+        T4A_HIP(hipStreamSynchronize(eng.stream()));
+    }
+}
+
+void Tci2::set_index_set(int which, size_t site, size_t count, const size_t* data)
+{
+    if (site >= len() || which < 0 || which > 1) throw Error(T4A_GPU_INVALID_ARGUMENT, "site/which out of range");
+    sync_digits();
+    IndexSet& s = which == 0 ? i_set[site] : j_set[site];
+    const size_t first_site = which == 0 ? 0 : site + 1;
+    if (count * s.width && !data) throw Error(T4A_GPU_NULL_POINTER, "data is null");
+    IndexSet n;
+    n.width = s.width;
+    n.count = count;
+    n.d.resize(count * s.width);
+    for (size_t k = 0; k < count; ++k)
+        for (size_t q = 0; q < s.width; ++q) {
+            const size_t v = data[k * s.width + q];
+            if (v >= local_dims[first_site + q]) throw Error(T4A_GPU_INVALID_ARGUMENT, "index out of bounds");
+            n.d[k * s.width + q] = (uint32_t)v;
+        }
+    s = n;
+    invalidate_site_tensors();
+    mark_sets_changed();
+}
+
+void Tci2::set_site_shard(size_t rank, size_t world)
+{
+    if (world == 0 || rank >= world) throw Error(T4A_GPU_INVALID_ARGUMENT, "invalid shard (rank, world)");
+    shard_rank = rank;
+    shard_world = world;
+}
+
+void Tci2::set_pi_shard(size_t rank, size_t world, t4a_gpu_allgather_fn gather, void* ctx)
+{
+    if (world == 0 || rank >= world) throw Error(T4A_GPU_INVALID_ARGUMENT, "invalid shard (rank, world)");
+    if (world > 1 && !gather) throw Error(T4A_GPU_NULL_POINTER, "a column-block shard over more than one rank needs an all-gather callback");
+    pi_shard = PiShard();
+    pi_shard.rank = rank;
+    pi_shard.world = world;
+    pi_shard.gather = world > 1 ? gather : nullptr;
+    pi_shard.gather_ctx = ctx;
+}
+
 static void check_tt_chain(const std::vector<DevCore>& cores) // SimpleTensorTrain::new, simplett/src/tensortrain.rs:97
 {
     if (cores.front().l != 1) throw Error(T4A_GPU_INVALID_ARGUMENT, "First tensor must have left dimension 1");

@@ -204,6 +204,14 @@ public:
     std::vector<double> evaluate(const uint32_t* idx, size_t n_pts); // idx n_sites x n_pts col-major
     double sum();
     std::vector<double> site_tensor_host(size_t site, size_t dims3[3]);
+    // one site tensor copied device to device on this object's stream, after a pending fill; the setter takes the shape [l, s, r] with it
+    void site_tensor_device(size_t site, double* d_out);
+    void set_site_tensor_device(size_t site, const size_t dims3[3], const double* d_in);
+    // replaces I (which = 0) or J (which = 1) of `site` by `count` multi-indices, bounds-checked against local_dims; site tensors and the
+    // chain's device tables are invalid afterwards
+    void set_index_set(int which, size_t site, size_t count, const size_t* data);
+    void set_site_shard(size_t rank, size_t world);
+    void set_pi_shard(size_t rank, size_t world, t4a_gpu_allgather_fn gather, void* ctx);
 
     // TensorCI2::from_tensor_train (tensorci/src/conversion.rs:66-121): replaces the I/J sets, site tensors,
     // pivot errors and max_sample_value of this (freshly constructed) object.  `tt` is left untouched.

@@ -161,6 +161,173 @@ void tensor_contract_pair(Engine& e, const TensorView& a, const TensorView& b, c
     T4A_HIP(hipGetLastError());
 }
 
+void require_distinct_labels(const TensorView& t)
+{
+    for (size_t a = 0; a < t.labels.size(); ++a)
+        for (size_t b = a + 1; b < t.labels.size(); ++b)
+            if (t.labels[a] == t.labels[b]) throw Error(T4A_GPU_INVALID_ARGUMENT, "duplicate index in tensor");
+}
+
+std::vector<size_t> plan_permute(const TensorView& t, const int64_t* labels)
+{
+    const size_t r = t.dims.size();
+    std::vector<size_t> perm(r);
+    std::vector<char> used(r, 0);
+    for (size_t k = 0; k < r; ++k) {
+        auto it = std::find(t.labels.begin(), t.labels.end(), labels[k]);
+        if (it == t.labels.end()) throw Error(T4A_GPU_INVALID_ARGUMENT, "permute: index not found in tensor");
+        perm[k] = (size_t)(it - t.labels.begin());
+        if (used[perm[k]]) throw Error(T4A_GPU_INVALID_ARGUMENT, "permute: duplicate index");
+        used[perm[k]] = 1;
+    }
+    return perm;
+}
+
+size_t plan_relabel(const TensorView& t, int64_t from, int64_t to)
+{
+    auto it = std::find(t.labels.begin(), t.labels.end(), from);
+    if (it == t.labels.end()) throw Error(T4A_GPU_INVALID_ARGUMENT, "relabel: index not found in tensor");
+    if (from != to && std::find(t.labels.begin(), t.labels.end(), to) != t.labels.end())
+        throw Error(T4A_GPU_INVALID_ARGUMENT, "relabel: the new label is already present");
+    return (size_t)(it - t.labels.begin());
+}
+
+ContractPlan plan_outer_product(const TensorView& a, const TensorView& b)
+{
+    for (int64_t l : a.labels)
+        if (std::find(b.labels.begin(), b.labels.end(), l) != b.labels.end())
+            throw Error(T4A_GPU_INVALID_ARGUMENT, "outer_product: the operands share an index; use contract for a contraction");
+    return plan_contract_pair(a, b);
+}
+
+ContractPlan plan_tensordot(const TensorView& a, TensorView& b, const int64_t* labels_a, const int64_t* labels_b, size_t n_pairs)
+{
+    if (n_pairs == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "tensordot: No pairs specified for contraction");
+    std::vector<size_t> ax_a, ax_b;
+    for (size_t p = 0; p < n_pairs; ++p) {
+        const auto ia = std::find(a.labels.begin(), a.labels.end(), labels_a[p]);
+        const auto ib = std::find(b.labels.begin(), b.labels.end(), labels_b[p]);
+        if (ia == a.labels.end()) throw Error(T4A_GPU_INVALID_ARGUMENT, "tensordot: Index not found in self tensor");
+        if (ib == b.labels.end()) throw Error(T4A_GPU_INVALID_ARGUMENT, "tensordot: Index not found in other tensor");
+        const size_t pa = (size_t)(ia - a.labels.begin()), pb = (size_t)(ib - b.labels.begin());
+        if (std::find(ax_a.begin(), ax_a.end(), pa) != ax_a.end())
+            throw Error(T4A_GPU_INVALID_ARGUMENT, "tensordot: Duplicate axis " + std::to_string(pa) + " in self tensor");
+        if (std::find(ax_b.begin(), ax_b.end(), pb) != ax_b.end())
+            throw Error(T4A_GPU_INVALID_ARGUMENT, "tensordot: Duplicate axis " + std::to_string(pb) + " in other tensor");
+        if (a.dims[pa] != b.dims[pb])
+            throw Error(T4A_GPU_INVALID_ARGUMENT, "tensordot: Dimension mismatch: self[" + std::to_string(pa) + "]=" + std::to_string(a.dims[pa]) +
+                                                      " != other[" + std::to_string(pb) + "]=" + std::to_string(b.dims[pb]));
+        ax_a.push_back(pa);
+        ax_b.push_back(pb);
+    }
+    for (size_t i = 0; i < a.labels.size(); ++i)
+        for (size_t j = 0; j < b.labels.size(); ++j)
+            if (a.labels[i] == b.labels[j]) {
+                bool paired = false;
+                for (size_t p = 0; p < n_pairs; ++p) paired = paired || (ax_a[p] == i && ax_b[p] == j);
+                if (!paired)
+                    throw Error(T4A_GPU_NOT_IMPLEMENTED,
+                                "tensordot: Common index found but not in contraction pairs. Batch contraction is not yet implemented.");
+            }
+    // unpaired axes keep their labels (none is shared, checked above)
+    for (size_t p = 0; p < n_pairs; ++p) b.labels[ax_b[p]] = a.labels[ax_a[p]];
+    return plan_contract_pair(a, b);
+}
+
+void require_distinct_chain_labels(const int64_t* site_labels, const int64_t* bond_labels, size_t n)
+{
+    std::vector<int64_t> all(site_labels, site_labels + n);
+    if (n > 1) all.insert(all.end(), bond_labels, bond_labels + n - 1);
+    std::sort(all.begin(), all.end());
+    if (std::adjacent_find(all.begin(), all.end()) != all.end())
+        throw Error(T4A_GPU_INVALID_ARGUMENT, "tensor_train_to_treetn: site and bond indices must be distinct");
+}
+
+std::vector<OwnedTensor> chain_to_tensors(Engine& e, Engine& src, const std::vector<DevCore>& cores, const int64_t* site_labels, const int64_t* bond_labels)
+{
+    const size_t n = cores.size();
+    src.sync();
+    std::vector<OwnedTensor> made;
+    for (size_t s = 0; s < n; ++s) {
+        const DevCore& c = cores[s];
+        std::vector<size_t> dims;
+        std::vector<int64_t> labels;
+        if (s > 0) {
+            dims.push_back(c.l);
+            labels.push_back(bond_labels[s - 1]);
+        }
+        dims.push_back(c.s);
+        labels.push_back(site_labels[s]);
+        if (s + 1 < n) {
+            dims.push_back(c.r);
+            labels.push_back(bond_labels[s]);
+        }
+        OwnedTensor t(dims, labels); // boundary legs have dimension 1: the column-major data is unchanged
+        if (c.size())
+            T4A_HIP(hipMemcpyAsync(t.buf.get(), c.buf.get(), c.size() * sizeof(double), hipMemcpyDeviceToDevice, e.stream()));
+        made.push_back(std::move(t));
+    }
+    e.sync();
+    return made;
+}
+
+ChainPlan plan_tensors_to_chain(const std::vector<TensorView>& tensors)
+{
+    const size_t n_sites = tensors.size();
+    auto shared = [&](size_t a, size_t b) { // the one label two neighbours share
+        std::vector<int64_t> common;
+        for (int64_t l : tensors[a].labels)
+            if (std::find(tensors[b].labels.begin(), tensors[b].labels.end(), l) != tensors[b].labels.end()) common.push_back(l);
+        if (common.size() != 1)
+            throw Error(T4A_GPU_INVALID_ARGUMENT, "treetn_to_tensor_train: missing chain edge between nodes " + std::to_string(a) + " and " +
+                                                      std::to_string(b));
+        return common[0];
+    };
+    std::vector<int64_t> bonds(n_sites > 0 ? n_sites - 1 : 0);
+    for (size_t s = 0; s + 1 < n_sites; ++s) bonds[s] = shared(s, s + 1);
+    for (size_t a = 0; a < n_sites; ++a) // a chain: no label may connect nodes that are not neighbours
+        for (size_t b = a + 2; b < n_sites; ++b)
+            for (int64_t l : tensors[a].labels)
+                if (std::find(tensors[b].labels.begin(), tensors[b].labels.end(), l) != tensors[b].labels.end())
+                    throw Error(T4A_GPU_INVALID_ARGUMENT, "treetn_to_tensor_train: expected a chain with " + std::to_string(n_sites - 1) + " edges");
+    ChainPlan plan;
+    for (size_t s = 0; s < n_sites; ++s) {
+        const TensorView& t = tensors[s];
+        const size_t want = 1 + (s > 0 ? 1 : 0) + (s + 1 < n_sites ? 1 : 0);
+        if (t.labels.size() != want)
+            throw Error(T4A_GPU_INVALID_ARGUMENT, "treetn_to_tensor_train: node " + std::to_string(s) + " must have exactly one site index");
+        std::vector<size_t> perm;
+        auto pos = [&](int64_t l) { return (size_t)(std::find(t.labels.begin(), t.labels.end(), l) - t.labels.begin()); };
+        size_t site_axis = 0;
+        for (size_t a = 0; a < t.labels.size(); ++a)
+            if ((s == 0 || t.labels[a] != bonds[s - 1]) && (s + 1 >= n_sites || t.labels[a] != bonds[s])) site_axis = a;
+        if (s > 0) perm.push_back(pos(bonds[s - 1]));
+        perm.push_back(site_axis);
+        if (s + 1 < n_sites) perm.push_back(pos(bonds[s]));
+        const std::array<size_t, 3> d = {s > 0 ? t.dims[perm[0]] : 1, t.dims[site_axis], s + 1 < n_sites ? t.dims[perm.back()] : 1};
+        if (d[0] == 0 || d[1] == 0 || d[2] == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "treetn_to_tensor_train: a resulting core has a zero dimension");
+        plan.perm.push_back(perm);
+        plan.dims.push_back(d);
+    }
+    return plan;
+}
+
+std::vector<DevCore> tensors_to_chain(Engine& e, const std::vector<TensorView>& tensors, const ChainPlan& plan)
+{
+    std::vector<DevCore> cores(tensors.size());
+    for (size_t s = 0; s < tensors.size(); ++s) {
+        DevCore& c = cores[s];
+        c.l = plan.dims[s][0];
+        c.s = plan.dims[s][1];
+        c.r = plan.dims[s][2];
+        c.buf.reserve(c.size());
+        tensor_permute(e, tensors[s], plan.perm[s], c.buf.get());
+    }
+    T4A_HIP(hipGetLastError());
+    e.sync();
+    return cores;
+}
+
 NetworkPlan plan_contract_network(const std::vector<TensorView>& ts, const std::vector<int64_t>& retain) // contract.rs:530-572, :885-941
 {
     if (ts.empty()) throw Error(T4A_GPU_INVALID_ARGUMENT, "No tensors to contract");

@@ -7,6 +7,7 @@
 #pragma once
 
 #include "engine.hpp"
+#include "tt_chain.hpp"
 
 #include <algorithm>
 
@@ -50,6 +51,17 @@ ContractPlan plan_contract_pair(const TensorView& a, const TensorView& b);
 // d_out: M x N doubles = the result tensor [free a.., free b..]; uses e.d_tmp / e.d_tmp2 as permutation scratch
 void tensor_contract_pair(Engine& e, const TensorView& a, const TensorView& b, const ContractPlan& plan, double* d_out);
 
+// What the operations on one or two labelled tensors refuse (index_ops.rs, defaults/contract.rs).  Host only: their callers look before
+// they take a device.
+void require_distinct_labels(const TensorView& t);                            // "duplicate index in tensor"
+std::vector<size_t> plan_permute(const TensorView& t, const int64_t* labels); // out axis k takes the axis labelled labels[k]
+size_t plan_relabel(const TensorView& t, int64_t from, int64_t to);           // the axis that takes the new label
+ContractPlan plan_outer_product(const TensorView& a, const TensorView& b);    // operands without a common label: M x 1 times 1 x N
+// tensordot (prepare_contraction_pairs, index_ops.rs): pair p contracts the axis of `a` labelled labels_a[p] with the axis of `b` labelled
+// labels_b[p]: every pair names one axis of each operand, no axis twice, equal dimensions; a label the operands have in common that is not
+// paired would be a batch contraction (not implemented in the reference either).  The paired axes of `b` take the labels of their partners.
+ContractPlan plan_tensordot(const TensorView& a, TensorView& b, const int64_t* labels_a, const int64_t* labels_b, size_t n_pairs);
+
 // N-ary contraction of a connected tensor network (defaults/contract.rs:283-298 contract / contract_with_options, plan :885-941,
 // connectivity :1167-1230): every label that occurs in more than one operand is summed unless it is retained; the result carries the
 // labels that occur once, or are retained, in order of first appearance (operands in order, axes in order).  Errors like the
@@ -73,6 +85,20 @@ struct NetworkPlan {
 };
 NetworkPlan plan_contract_network(const std::vector<TensorView>& ts, const std::vector<int64_t>& retain); // validation + result indices (host only)
 OwnedTensor tensor_contract_network(Engine& e, const std::vector<TensorView>& ts, const std::vector<int64_t>& retain);
+
+// simplett_bridge.rs on a chain; in each direction a host-only check or plan, then the device step.
+// To tensors (tensor_train_to_treetn, :706-794): n site labels and n - 1 bond labels, all distinct; one tensor per core with legs
+// [bond s-1, site s, bond s], boundary legs dropped.  `src` is the engine the cores were written on.
+void require_distinct_chain_labels(const int64_t* site_labels, const int64_t* bond_labels, size_t n);
+std::vector<OwnedTensor> chain_to_tensors(Engine& e, Engine& src, const std::vector<DevCore>& cores, const int64_t* site_labels, const int64_t* bond_labels);
+// Back (treetn_to_tensor_train, :172-277): neighbours share exactly one label, no other pair shares any, and every node has one more leg,
+// its site index; legs in any order.  Per site the permutation into [l, s, r] and that shape.
+struct ChainPlan {
+    std::vector<std::vector<size_t>> perm;
+    std::vector<std::array<size_t, 3>> dims;
+};
+ChainPlan plan_tensors_to_chain(const std::vector<TensorView>& tensors);
+std::vector<DevCore> tensors_to_chain(Engine& e, const std::vector<TensorView>& tensors, const ChainPlan& plan);
 
 struct UnfoldPlan {
     std::vector<size_t> perm;

@@ -341,3 +341,55 @@ def test_outer_product_and_tensordot(t4a):
         T(a, [1, 2]).tensordot(T(c, [7, 8, 9]), [(5, 7)])
     with pytest.raises(t4a.T4aError, match="Batch contraction"):
         T(a, [1, 2]).tensordot(T(c, [2, 1, 9]), [(1, 1)])
+
+
+# ---- argument checks of the labelled-tensor operations and of the chain bridge: status code and whole message of each ----
+def _refused(t4a, code, message, call):
+    with pytest.raises(t4a.T4aError) as e:
+        call()
+    assert (e.value.code, e.value.message) == (code, message)
+
+
+def test_permute_relabel_and_new_refusals(t4a):
+    T = t4a.LabelledTensor
+    bad, a = t4a.INVALID_ARGUMENT, _arange_tensor((2, 3))
+    _refused(t4a, bad, "permute: index not found in tensor", lambda: T(a, [1, 2]).permute([1, 3]))
+    _refused(t4a, bad, "permute: duplicate index", lambda: T(a, [1, 2]).permute([1, 1]))
+    _refused(t4a, bad, "relabel: index not found in tensor", lambda: T(a, [1, 2]).relabel(5, 6))
+    _refused(t4a, bad, "relabel: the new label is already present", lambda: T(a, [1, 2]).relabel(1, 2))
+    assert T(a, [1, 2]).relabel(1, 1).labels == [1, 2]  # onto itself: nothing to refuse
+    _refused(t4a, bad, "duplicate index in tensor", lambda: T(a, [1, 1]))
+
+
+def test_outer_product_and_tensordot_refusals(t4a):
+    T = t4a.LabelledTensor
+    bad = t4a.INVALID_ARGUMENT
+    a, c = T(_arange_tensor((2, 3)), [1, 2]), T(_arange_tensor((3, 2, 2)), [7, 8, 9])
+    _refused(t4a, bad, "outer_product: the operands share an index; use contract for a contraction",
+             lambda: a.outer_product(T(_arange_tensor((3, 2)), [2, 4])))
+    _refused(t4a, bad, "tensordot: No pairs specified for contraction", lambda: a.tensordot(c, []))
+    _refused(t4a, bad, "tensordot: Index not found in self tensor", lambda: a.tensordot(c, [(5, 7)]))
+    _refused(t4a, bad, "tensordot: Index not found in other tensor", lambda: a.tensordot(c, [(1, 5)]))
+    _refused(t4a, bad, "tensordot: Duplicate axis 0 in self tensor", lambda: a.tensordot(c, [(1, 8), (1, 9)]))
+    _refused(t4a, bad, "tensordot: Duplicate axis 1 in other tensor", lambda: a.tensordot(c, [(1, 8), (2, 8)]))
+    _refused(t4a, bad, "tensordot: Dimension mismatch: self[0]=2 != other[0]=3", lambda: a.tensordot(c, [(1, 7)]))
+    _refused(t4a, t4a.NOT_IMPLEMENTED, "tensordot: Common index found but not in contraction pairs. Batch contraction is not yet implemented.",
+             lambda: a.tensordot(T(_arange_tensor((3, 2, 2)), [2, 1, 9]), [(1, 1)]))
+
+
+def test_chain_bridge_refusals(t4a):
+    T = t4a.LabelledTensor
+    bad = t4a.INVALID_ARGUMENT
+    tt = t4a.SimpleTensorTrain([_arange_tensor(s) for s in [(1, 2, 3), (3, 2, 2), (2, 3, 1)]])
+    _refused(t4a, bad, "tensor_train_to_treetn: site and bond indices must be distinct",
+             lambda: t4a.tensor_train_to_tensors(tt, [10, 11, 12], [20, 10]))
+    first, mid, last = T(_arange_tensor((2, 3)), [10, 20]), T(_arange_tensor((3, 2, 2)), [20, 11, 21]), T(_arange_tensor((2, 3)), [21, 12])
+    assert [tuple(d) for d in t4a.tensors_to_tensor_train([first, mid, last]).dims()] == [(1, 2, 3), (3, 2, 2), (2, 3, 1)]
+    _refused(t4a, bad, "treetn_to_tensor_train: missing chain edge between nodes 0 and 1",
+             lambda: t4a.tensors_to_tensor_train([T(_arange_tensor((2, 3)), [10, 30]), mid, last]))
+    _refused(t4a, bad, "treetn_to_tensor_train: expected a chain with 2 edges",
+             lambda: t4a.tensors_to_tensor_train([first, mid, T(_arange_tensor((2, 3, 2)), [21, 12, 10])]))
+    _refused(t4a, bad, "treetn_to_tensor_train: node 0 must have exactly one site index",
+             lambda: t4a.tensors_to_tensor_train([T(_arange_tensor((2, 2, 3)), [10, 13, 20]), mid, last]))
+    _refused(t4a, bad, "treetn_to_tensor_train: a resulting core has a zero dimension",
+             lambda: t4a.tensors_to_tensor_train([T(np.zeros((0, 3)), [10, 20]), mid, last]))
