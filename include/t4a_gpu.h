@@ -1747,6 +1747,92 @@ t4a_gpu_status t4a_gpu_pmpo_time_compress(const t4a_gpu_pmpo* a, const t4a_gpu_p
                                           double* ms2);
 
 /* =====================================================================================
+ * Budgeted truncation of many MPOs in lock step, and adaptive patching of partitioned MPOs
+ * TensorTrain::truncate (itensorlike/src/tensortrain.rs:1180, treetn/truncate.rs:129-198) and
+ * crates/tensor4all-partitionedtt/src/patching.rs ("Adaptive Patching for Tensor Train Computations", arXiv:2602.22372), for f64 on
+ * a chain with legs (site, leg) in place of index objects.  Out of scope: partitionedtreetn, trees, complex scalars, autodiff
+ * metadata.
+ * _mpo_truncate_many: out[k] is mpos[k] truncated as TensorTrain::truncate does it — canonicalised onto the last site, then every bond
+ * truncated twice, on the way from n - 1 down to 0 and on the way back — under policies[k] (all eight combinations of scale, measure
+ * and rule; the rank is t4a_gpu_svd_retained_rank of the singular values, then max_bond_dims[k], 0 = none, then at least one).
+ * The envelope, the routes and the determinism are those of _mpo_compress_many, with the shape bound taken from the left (k_0 = 1,
+ * k_{i+1} = min(k_i s1_i s2_i, r_{i+1})): the batched part is n - 1 QR-step launches and 2 (n - 1) SVD-step launches whatever `count`
+ * is, and ONE host synchronisation; the two directions of the SVD step are mirrored instantiations of one kernel.  Items outside the
+ * envelope take a serial stage with the same policy in the same call.  bonds (may be NULL) receives n + 1 values per item.  With
+ * ranks_only != 0 the same launches run and `out` (may be NULL) stays NULL: only the bonds come back.
+ * INVALID_ARGUMENT as _mpo_compress_many with "truncate_many" in the messages, and for a negative or non-finite threshold or an unknown
+ * policy field ("truncate_many: item <k>: ...").
+ * _counted: counts4 as _mpo_compress_many_counted.  _plan (host only): as _mpo_compress_many_plan with a cap per item; counts3 =
+ * launches (3 (n - 1)), synchronisations (1; 2 with rules_from_norms != 0, the call shape of the patching driver, which reads the norms
+ * after the QR sweep to derive the budgets), batched items.
+ * _trace (test hook): as _counted with ranks_only, and per item norm2 (the squared Frobenius norm the QR sweep found), ranks
+ * (2 (n - 1) per item: the SVD steps in the order they run) and sv (64 values per step: the singular values the step computed,
+ * non-increasing, zero-filled). */
+t4a_gpu_status t4a_gpu_mpo_truncate_many(const t4a_gpu_mpo* const* mpos, size_t count, const t4a_gpu_svd_policy* policies,
+                                         const size_t* max_bond_dims, int32_t route, int32_t ranks_only, t4a_gpu_mpo** out, size_t* bonds);
+t4a_gpu_status t4a_gpu_mpo_truncate_many_counted(const t4a_gpu_mpo* const* mpos, size_t count, const t4a_gpu_svd_policy* policies,
+                                                 const size_t* max_bond_dims, int32_t route, int32_t ranks_only, t4a_gpu_mpo** out,
+                                                 size_t* bonds, size_t* counts4);
+t4a_gpu_status t4a_gpu_mpo_truncate_many_plan(const size_t* dims4, const size_t* n_sites, size_t count, const size_t* max_bond_dims,
+                                              int32_t route, int32_t rules_from_norms, int32_t* batched, size_t* bonds, size_t* qr_bonds,
+                                              size_t* counts3);
+t4a_gpu_status t4a_gpu_mpo_truncate_many_trace(const t4a_gpu_mpo* const* mpos, size_t count, const t4a_gpu_svd_policy* policies,
+                                               const size_t* max_bond_dims, int32_t route, size_t* bonds, size_t* counts4, double* norm2,
+                                               int32_t* ranks, double* sv);
+/* PatchingOptions (patching.rs:68-107).  patch_order: n_patch_order pairs (site, leg).  Defaults: rtol 1e-12, max_bond_dim 100,
+ * an empty order, EXACT_PARAMETER_GAIN. */
+#define T4A_GPU_PATCH_SPLIT_SEQUENTIAL 0
+#define T4A_GPU_PATCH_SPLIT_EXACT_PARAMETER_GAIN 1
+typedef struct {
+    double rtol;
+    int32_t has_max_bond_dim;
+    size_t max_bond_dim;
+    const size_t* patch_order;
+    size_t n_patch_order;
+    int32_t split_strategy;
+} t4a_gpu_patching_options;
+/* Host only.  _validate: "rtol must be finite and non-negative", "max_bond_dim must be at least 1", a leg outside the chain,
+ * "patch_order cannot contain zero-dimensional indices".  _patch_volume: the product of the dims of the unprojected legs ("subdomain
+ * volume overflowed usize").  _patch_budgets: budgets[k] = rtol^2 sum(norm2) volumes[k] / sum(volumes), drop[k] = norm2[k] <=
+ * budgets[k]; *empty = 1 (and nothing else written) for no patch or a zero total volume; "partition volume overflowed usize",
+ * "partitioned norm is not finite", "rtol produced a non-finite truncation budget".  _split_candidates: the unprojected legs of
+ * patch_order, or all legs in chain order when it is empty, duplicates removed; legs holds up to 2 n_sites pairs. */
+t4a_gpu_status t4a_gpu_pmpo_validate_patching_options(const t4a_gpu_patching_options* options, const size_t* site_dims, size_t n_sites);
+t4a_gpu_status t4a_gpu_pmpo_patch_volume(const size_t* entries, size_t count, const size_t* site_dims, size_t n_sites, size_t* out);
+t4a_gpu_status t4a_gpu_pmpo_patch_budgets(const size_t* volumes, const double* norm2, size_t count, double rtol, double* budgets,
+                                          int32_t* drop, int32_t* empty);
+t4a_gpu_status t4a_gpu_pmpo_split_candidates(const size_t* entries, size_t count, const size_t* site_dims, size_t n_sites,
+                                             const t4a_gpu_patching_options* options, size_t* legs, size_t* n_legs);
+/* truncate_adaptive (:566-615): every patch masked by its own projector (one launch), budgets from the norms of ONE batched call's QR
+ * sweep, patches at or below their budget dropped, the others truncated by the same call's SVD sweeps with Absolute / SquaredValue /
+ * DiscardedTailSum at the budget and the cap.  The survivors keep their order and carry budget_squared (_pmpo_budget_squared: *has = 0
+ * where unset).  add_with_patching (:154-198): the loop of the reference on the patches of `subdomains`; chosen (may be NULL,
+ * 2 * chosen_capacity values) receives the legs of the splits in order, *n_chosen their number.  counts6 (may be NULL): rounds,
+ * tensor calls, ranks-only calls, launches and synchronisations of their batched parts, splits. */
+t4a_gpu_status t4a_gpu_pmpo_truncate_adaptive(const t4a_gpu_pmpo* p, double rtol, int32_t has_max_bond_dim, size_t max_bond_dim,
+                                              int32_t route, t4a_gpu_pmpo** out, size_t* counts6);
+/* Probe (tools/probe_patching.py): _pmpo_truncate_adaptive on the BATCHED route with the stream drained after every sweep; ms5 = wall ms
+ * of the QR sweep, the first synchronisation with its read of the norms, the leftward sweep, the rightward sweep, the last
+ * synchronisation with its read of the ranks.  The result is dropped. */
+t4a_gpu_status t4a_gpu_pmpo_truncate_adaptive_timed(const t4a_gpu_pmpo* p, double rtol, int32_t has_max_bond_dim, size_t max_bond_dim,
+                                                    double* ms5);
+t4a_gpu_status t4a_gpu_pmpo_add_with_patching(const t4a_gpu_pmpo* subdomains, const t4a_gpu_patching_options* options, int32_t route,
+                                              t4a_gpu_pmpo** out, size_t* counts6, size_t* chosen, size_t chosen_capacity,
+                                              size_t* n_chosen);
+/* contract_adaptive (:282-412): the pairwise products of the patches (both sides in the order of t4a_gpu_projector_compare, algorithm /
+ * method / tolerance / max_bond_dim as _pmpo_contract with compress on) grouped by result projector; per group the contributions are
+ * summed by direct sum and truncated after each addition with the same rank rule; when the sum or a contribution REACHES the cap of
+ * `options` the group is split along a leg of the result — (i, 0) is a's s1 leg of site i, (i, 1) b's s2 leg — chosen as in
+ * _pmpo_add_with_patching, the operand that has the leg is projected per value (once per projector and value) and truncated with
+ * Relative / Value / PerValue at 64 eps, and the group recurses; a final _pmpo_truncate_adaptive runs over everything.  Refusals before
+ * the device is touched: the messages of _pmpo_contract for the shapes, those of _pmpo_validate_patching_options on the result's site
+ * dims.  counts6 as above (launches and synchronisations of the truncate_many calls; splits = groups split). */
+t4a_gpu_status t4a_gpu_pmpo_contract_adaptive(const t4a_gpu_pmpo* a, const t4a_gpu_pmpo* b, int32_t algorithm, int32_t method, double tolerance,
+                                              size_t max_bond_dim, const t4a_gpu_patching_options* options, int32_t route, t4a_gpu_pmpo** out,
+                                              size_t* counts6);
+t4a_gpu_status t4a_gpu_pmpo_budget_squared(const t4a_gpu_pmpo* p, size_t k, int32_t* has, double* value);
+
+/* =====================================================================================
  * swap_site_indices on a chain: which site holds which site index
  * tensor4all-treetn/src/treetn/swap.rs (SwapOptions, ScheduledSwapStep, SwapSchedule::build), treetn/mod.rs (swap_on_edge,
  * swap_site_indices), for f64 and by position.

@@ -23,6 +23,7 @@
 #include "tdvp.hpp"
 #include "gse.hpp"
 #include "pmpo.hpp"
+#include "pmpo_patching.hpp"
 #include "linsolve.hpp"
 #include "swap.hpp"
 
@@ -810,6 +811,59 @@ std::vector<Mpo*> mpo_list(const t4a_gpu_mpo* const* mpos, size_t count, const c
         items[k] = mpos[k]->impl.get();
     }
     return items;
+}
+
+std::vector<BtRule> truncate_rules(const t4a_gpu_svd_policy* policies, const size_t* max_bond_dims, size_t count)
+{
+    if (count) T4A_REQUIRE_PTR(policies);
+    std::vector<BtRule> rules(count);
+    for (size_t k = 0; k < count; ++k) {
+        const SvdPolicy p{policies[k].threshold, policies[k].scale, policies[k].measure, policies[k].rule}; // (fields are checked by the driver, per item)
+        rules[k] = bt_rule(p, max_bond_dims ? max_bond_dims[k] : 0);
+    }
+    return rules;
+}
+
+void truncate_out(std::vector<std::unique_ptr<Mpo>>& res, const std::vector<std::vector<size_t>>& b, const TruncateManyStats& st, bool ranks_only,
+                  t4a_gpu_mpo** out, size_t* bonds, size_t* counts4)
+{
+    if (!ranks_only) {
+        std::vector<t4a_gpu_mpo*> handles;
+        for (auto& m : res) handles.push_back(new t4a_gpu_mpo{std::move(m)});
+        for (size_t k = 0; k < res.size(); ++k) out[k] = handles[k];
+    }
+    if (bonds) {
+        size_t at = 0;
+        for (const auto& v : b)
+            for (size_t x : v) bonds[at++] = x;
+    }
+    if (counts4) {
+        counts4[0] = st.launches;
+        counts4[1] = st.syncs;
+        counts4[2] = st.n_batched;
+        counts4[3] = st.n_serial;
+    }
+}
+
+PatchingOptions patching_options(const t4a_gpu_patching_options* o)
+{
+    PatchingOptions r;
+    if (!o) return r;
+    r.rtol = o->rtol;
+    r.has_max_bond_dim = o->has_max_bond_dim != 0;
+    r.max_bond_dim = o->max_bond_dim;
+    if (o->n_patch_order) T4A_REQUIRE_PTR(o->patch_order);
+    for (size_t k = 0; k < o->n_patch_order; ++k) r.patch_order.push_back({o->patch_order[2 * k], o->patch_order[2 * k + 1]});
+    if (o->split_strategy < 0 || o->split_strategy > 1) throw Error(T4A_GPU_INVALID_ARGUMENT, "unknown patch split strategy");
+    r.split_strategy = (PatchSplitStrategy)o->split_strategy;
+    return r;
+}
+
+void patching_counts(const PatchingStats& st, size_t* counts6)
+{
+    if (!counts6) return;
+    counts6[0] = st.rounds, counts6[1] = st.truncate_calls, counts6[2] = st.ranks_only_calls;
+    counts6[3] = st.launches, counts6[4] = st.syncs, counts6[5] = st.splits;
 }
 
 SiteLegs site_legs(size_t n, const size_t* leg_counts, const int64_t* keys, const size_t* dims)
@@ -5512,6 +5566,221 @@ t4a_gpu_status t4a_gpu_pmpo_time_compress(const t4a_gpu_pmpo* a, const t4a_gpu_p
         T4A_REQUIRE_PTR(b);
         T4A_REQUIRE_PTR(ms2);
         pmpo_time_compress(*a->impl, *b->impl, pmpo_options(tolerance, max_bond_dim, 0), reps, ms2);
+    });
+}
+
+// ---- budgeted truncation of many MPOs (batch_truncate.hpp) and adaptive patching (pmpo_patching.hpp) ----
+t4a_gpu_status t4a_gpu_mpo_truncate_many_counted(const t4a_gpu_mpo* const* mpos, size_t count, const t4a_gpu_svd_policy* policies,
+                                                 const size_t* max_bond_dims, int32_t route, int32_t ranks_only, t4a_gpu_mpo** out,
+                                                 size_t* bonds, size_t* counts4)
+{
+    return guarded([&] {
+        if (!ranks_only) T4A_REQUIRE_PTR(out);
+        if (out)
+            for (size_t k = 0; k < count; ++k) out[k] = nullptr;
+        const CompressRoute r = compress_route(route);
+        const std::vector<Mpo*> items = mpo_list(mpos, count, "truncate_many");
+        const std::vector<BtRule> rules = truncate_rules(policies, max_bond_dims, count);
+        TruncateManyStats st;
+        std::vector<std::vector<size_t>> b;
+        std::vector<std::unique_ptr<Mpo>> res = mpo_truncate_many(items, rules, r, ranks_only != 0, b, &st, nullptr);
+        truncate_out(res, b, st, ranks_only != 0, out, bonds, counts4);
+    });
+}
+
+t4a_gpu_status t4a_gpu_mpo_truncate_many(const t4a_gpu_mpo* const* mpos, size_t count, const t4a_gpu_svd_policy* policies,
+                                         const size_t* max_bond_dims, int32_t route, int32_t ranks_only, t4a_gpu_mpo** out, size_t* bonds)
+{
+    return t4a_gpu_mpo_truncate_many_counted(mpos, count, policies, max_bond_dims, route, ranks_only, out, bonds, nullptr);
+}
+
+t4a_gpu_status t4a_gpu_mpo_truncate_many_trace(const t4a_gpu_mpo* const* mpos, size_t count, const t4a_gpu_svd_policy* policies,
+                                               const size_t* max_bond_dims, int32_t route, size_t* bonds, size_t* counts4, double* norm2,
+                                               int32_t* ranks, double* sv)
+{
+    return guarded([&] {
+        const CompressRoute r = compress_route(route);
+        const std::vector<Mpo*> items = mpo_list(mpos, count, "truncate_many");
+        const std::vector<BtRule> rules = truncate_rules(policies, max_bond_dims, count);
+        TruncateManyStats st;
+        TruncateManyTrace tr;
+        std::vector<std::vector<size_t>> b;
+        std::vector<std::unique_ptr<Mpo>> res = mpo_truncate_many(items, rules, r, true, b, &st, &tr);
+        truncate_out(res, b, st, true, nullptr, bonds, counts4);
+        const size_t steps2 = items[0]->len() ? 2 * (items[0]->len() - 1) : 0;
+        for (size_t k = 0; k < count; ++k) {
+            if (norm2) norm2[k] = tr.norm2[k];
+            for (size_t t = 0; t < steps2 && t < tr.ranks[k].size(); ++t) {
+                if (ranks) ranks[k * steps2 + t] = tr.ranks[k][t];
+                if (sv) std::memcpy(sv + (k * steps2 + t) * 64, tr.sv[k].data() + t * 64, 64 * sizeof(double));
+            }
+        }
+    });
+}
+
+t4a_gpu_status t4a_gpu_mpo_truncate_many_plan(const size_t* dims4, const size_t* n_sites, size_t count, const size_t* max_bond_dims,
+                                              int32_t route, int32_t rules_from_norms, int32_t* batched, size_t* bonds, size_t* qr_bonds,
+                                              size_t* counts3)
+{
+    return guarded([&] {
+        const CompressRoute r = compress_route(route);
+        if (count == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "truncate_many: the list is empty");
+        T4A_REQUIRE_PTR(n_sites);
+        std::vector<std::vector<std::array<size_t, 4>>> shapes(count);
+        std::vector<size_t> caps(count, 0);
+        size_t at = 0;
+        for (size_t k = 0; k < count; ++k) {
+            if (n_sites[k]) T4A_REQUIRE_PTR(dims4);
+            if (max_bond_dims) caps[k] = max_bond_dims[k];
+            for (size_t i = 0; i < n_sites[k]; ++i, ++at) shapes[k].push_back({dims4[4 * at], dims4[4 * at + 1], dims4[4 * at + 2], dims4[4 * at + 3]});
+        }
+        const TruncateManyPlan p = truncate_many_plan(shapes, caps, r, rules_from_norms != 0);
+        size_t ob = 0;
+        for (size_t k = 0; k < count; ++k) {
+            if (batched) batched[k] = p.batched[k];
+            for (size_t i = 0; i < p.bonds[k].size(); ++i, ++ob) {
+                if (bonds) bonds[ob] = p.bonds[k][i];
+                if (qr_bonds) qr_bonds[ob] = p.qr_bonds[k][i];
+            }
+        }
+        if (counts3) {
+            counts3[0] = p.launches;
+            counts3[1] = p.syncs;
+            counts3[2] = p.n_batched;
+        }
+    });
+}
+
+t4a_gpu_status t4a_gpu_pmpo_validate_patching_options(const t4a_gpu_patching_options* options, const size_t* site_dims, size_t n_sites)
+{
+    return guarded([&] { validate_patching_options(patching_options(options), site_dims_list(site_dims, n_sites)); });
+}
+
+t4a_gpu_status t4a_gpu_pmpo_patch_volume(const size_t* entries, size_t count, const size_t* site_dims, size_t n_sites, size_t* out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(out);
+        const SiteDims sd = site_dims_list(site_dims, n_sites);
+        const LegProjector p = projector_from_triples(entries, count);
+        projector_validate(p, sd);
+        *out = patch_volume(p, sd);
+    });
+}
+
+t4a_gpu_status t4a_gpu_pmpo_patch_budgets(const size_t* volumes, const double* norm2, size_t count, double rtol, double* budgets,
+                                          int32_t* drop, int32_t* empty)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(empty);
+        if (count) {
+            T4A_REQUIRE_PTR(volumes);
+            T4A_REQUIRE_PTR(norm2);
+        }
+        validate_truncation_options(rtol, false, 0);
+        const PatchBudgets b = patch_budgets(std::vector<size_t>(volumes, volumes + count), std::vector<double>(norm2, norm2 + count), rtol);
+        *empty = b.empty ? 1 : 0;
+        if (b.empty) return;
+        for (size_t k = 0; k < count; ++k) {
+            if (budgets) budgets[k] = b.budget[k];
+            if (drop) drop[k] = b.drop[k];
+        }
+    });
+}
+
+t4a_gpu_status t4a_gpu_pmpo_split_candidates(const size_t* entries, size_t count, const size_t* site_dims, size_t n_sites,
+                                             const t4a_gpu_patching_options* options, size_t* legs, size_t* n_legs)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(n_legs);
+        const SiteDims sd = site_dims_list(site_dims, n_sites);
+        const PatchingOptions o = patching_options(options);
+        validate_patching_options(o, sd);
+        const LegProjector p = projector_from_triples(entries, count);
+        projector_validate(p, sd);
+        const std::vector<PatchLeg> c = split_candidates(p, sd, o);
+        *n_legs = c.size();
+        if (!legs) return;
+        for (size_t k = 0; k < c.size(); ++k) legs[2 * k] = c[k].first, legs[2 * k + 1] = c[k].second;
+    });
+}
+
+t4a_gpu_status t4a_gpu_pmpo_truncate_adaptive(const t4a_gpu_pmpo* p, double rtol, int32_t has_max_bond_dim, size_t max_bond_dim,
+                                              int32_t route, t4a_gpu_pmpo** out, size_t* counts6)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(p);
+        T4A_REQUIRE_PTR(out);
+        *out = nullptr;
+        const CompressRoute r = compress_route(route);
+        validate_truncation_options(rtol, has_max_bond_dim != 0, max_bond_dim);
+        PatchingStats st;
+        *out = new t4a_gpu_pmpo{truncate_adaptive(*p->impl, rtol, has_max_bond_dim != 0, max_bond_dim, r, &st)};
+        patching_counts(st, counts6);
+    });
+}
+
+t4a_gpu_status t4a_gpu_pmpo_truncate_adaptive_timed(const t4a_gpu_pmpo* p, double rtol, int32_t has_max_bond_dim, size_t max_bond_dim,
+                                                    double* ms5)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(p);
+        T4A_REQUIRE_PTR(ms5);
+        for (int k = 0; k < 5; ++k) ms5[k] = 0.0;
+        validate_truncation_options(rtol, has_max_bond_dim != 0, max_bond_dim);
+        truncate_adaptive(*p->impl, rtol, has_max_bond_dim != 0, max_bond_dim, CompressRoute::Batched, nullptr, ms5);
+    });
+}
+
+t4a_gpu_status t4a_gpu_pmpo_add_with_patching(const t4a_gpu_pmpo* subdomains, const t4a_gpu_patching_options* options, int32_t route,
+                                              t4a_gpu_pmpo** out, size_t* counts6, size_t* chosen, size_t chosen_capacity,
+                                              size_t* n_chosen)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(subdomains);
+        T4A_REQUIRE_PTR(out);
+        *out = nullptr;
+        const CompressRoute r = compress_route(route);
+        const PatchingOptions o = patching_options(options);
+        validate_patching_options(o, subdomains->impl->sd);
+        PatchingStats st;
+        std::vector<PatchLeg> legs;
+        std::unique_ptr<PartitionedMpo> res = add_with_patching(*subdomains->impl, o, r, &st, &legs);
+        patching_counts(st, counts6);
+        if (n_chosen) *n_chosen = legs.size();
+        if (chosen)
+            for (size_t k = 0; k < legs.size() && k < chosen_capacity; ++k) chosen[2 * k] = legs[k].first, chosen[2 * k + 1] = legs[k].second;
+        *out = new t4a_gpu_pmpo{std::move(res)};
+    });
+}
+
+t4a_gpu_status t4a_gpu_pmpo_contract_adaptive(const t4a_gpu_pmpo* a, const t4a_gpu_pmpo* b, int32_t algorithm, int32_t method, double tolerance,
+                                              size_t max_bond_dim, const t4a_gpu_patching_options* options, int32_t route, t4a_gpu_pmpo** out,
+                                              size_t* counts6)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(a);
+        T4A_REQUIRE_PTR(b);
+        T4A_REQUIRE_PTR(out);
+        *out = nullptr;
+        if (algorithm < 0 || algorithm > 2) throw Error(T4A_GPU_INVALID_ARGUMENT, "unknown contraction algorithm");
+        const CompressRoute r = compress_route(route);
+        const MpoContractionOptions o = pmpo_options(tolerance, max_bond_dim, method);
+        const PatchingOptions po = patching_options(options);
+        PatchingStats st;
+        *out = new t4a_gpu_pmpo{contract_adaptive(*a->impl, *b->impl, (MpoAlgorithm)algorithm, o, po, r, &st)};
+        patching_counts(st, counts6);
+    });
+}
+
+t4a_gpu_status t4a_gpu_pmpo_budget_squared(const t4a_gpu_pmpo* p, size_t k, int32_t* has, double* value)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(p);
+        T4A_REQUIRE_PTR(has);
+        T4A_REQUIRE_PTR(value);
+        if (k >= p->impl->len()) throw Error(T4A_GPU_INVALID_ARGUMENT, "patch index out of range");
+        *has = p->impl->patches[k].has_budget ? 1 : 0;
+        *value = p->impl->patches[k].budget_squared;
     });
 }
 

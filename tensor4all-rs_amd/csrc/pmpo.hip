@@ -258,6 +258,12 @@ std::unique_ptr<Mpo> add_truncate(Mpo& x, Mpo& y, bool truncate, const MpoContra
 
 } // namespace
 
+void pmpo_mask_chains(Engine& eng, const std::vector<std::vector<DevCore>*>& chains, const std::vector<const LegProjector*>& projs,
+                      const SiteDims& sd)
+{
+    mask_chains(eng, chains, projs, sd);
+}
+
 // ------------------------------------------------------------------------------------------------ the handle
 void PartitionedMpo::validate(const SiteDims& sd, const std::vector<SiteDims>& patch_dims, const std::vector<LegProjector>& projectors)
 {

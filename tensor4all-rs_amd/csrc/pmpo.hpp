@@ -5,7 +5,8 @@
 // case s2 = 1).  The reference's index objects are legs here: the key of a projector is (site, leg), leg 0 = s1, leg 1 = s2, and the
 // shared index of a contraction A·B is A.(i, 1) == B.(i, 0).  Deviations: the task order of a contraction is fixed (a-major, insertion
 // order; the reference iterates a hash map), patches keep their insertion order, and to_mpo sorts by keys then values with a shorter
-// prefix first.  partitionedtreetn, budget_squared and autodiff metadata are out of scope.
+// prefix first.  A patch may carry budget_squared, the absolute squared-error budget adaptive patching gave it (pmpo_patching.hpp, which
+// restates patching.rs); partitionedtreetn, trees, complex scalars and autodiff metadata are out of scope.
 #pragma once
 
 #include <map>
@@ -50,6 +51,8 @@ PmpoPlan pmpo_contract_plan(const std::vector<LegProjector>& pa, const std::vect
 struct PmpoPatch {
     LegProjector proj;
     std::unique_ptr<Mpo> mpo;
+    bool has_budget = false; // with_budget_squared (subdomain_tt.rs): set by adaptive patching, not carried through the other operations
+    double budget_squared = 0.0;
 };
 
 class PartitionedTT; // patching.hpp
@@ -104,6 +107,10 @@ void pmpo_time_compress(PartitionedMpo& a, PartitionedMpo& b, const MpoContracti
 // Test hook: the product launch of `n_jobs` sites exactly as contract() issues it, host arrays in and out.  dims is 7 x n_jobs
 // (la, s1, k, ra, lb, t, rb), sel 4 x n_jobs (k0, k1, sm, tm; sm / tm < 0 = no mask), A / B / C the sites concatenated.
 void pmpo_pair_products(const size_t* dims, const long long* sel, size_t n_jobs, const double* A, const double* B, double* C);
+// project every listed chain onto its projector: one job per site that carries a projected leg, ONE launch of pmpo_mask_kernel for all
+// of them on `eng`'s stream; ends synced
+void pmpo_mask_chains(Engine& eng, const std::vector<std::vector<DevCore>*>& chains, const std::vector<const LegProjector*>& projs,
+                      const SiteDims& sd);
 // Test hook: the mask launch on host arrays.  dims is 4 x n_jobs (l, s1, s2, r), sel 2 x n_jobs (m1, m2; < 0 = none), X in place.
 void pmpo_mask_sites(const size_t* dims, const long long* sel, size_t n_jobs, double* X);
 

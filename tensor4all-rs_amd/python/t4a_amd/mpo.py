@@ -281,6 +281,98 @@ def compress_many_plan(shapes, options=None, route="auto"):
     return out
 
 
+def _truncate_args(n_items, policies, max_bond_dims, who):
+    """one policy and one cap per item, or one of either for all -> (SvdPolicyC array, uintp array)"""
+    from . import SvdPolicyC, SvdTruncationPolicy
+    if policies is None or isinstance(policies, SvdTruncationPolicy):
+        policies = [policies] * n_items
+    if max_bond_dims is None or isinstance(max_bond_dims, (int, np.integer)):
+        max_bond_dims = [max_bond_dims] * n_items
+    policies, max_bond_dims = list(policies), list(max_bond_dims)
+    if len(policies) != n_items or len(max_bond_dims) != n_items:
+        raise T4aError(INVALID_ARGUMENT, f"{who}: {len(policies)} policies and {len(max_bond_dims)} caps for {n_items} items")
+    pol = (SvdPolicyC * max(n_items, 1))()
+    for k, p in enumerate(policies):
+        pol[k] = (SvdTruncationPolicy() if p is None else p).to_c()
+    for c in max_bond_dims:
+        if c is not None and int(c) < 1:
+            raise T4aError(INVALID_ARGUMENT, f"{who}: max_bond_dim must be at least 1")
+    caps = np.ascontiguousarray(np.array([0 if c is None else int(c) for c in max_bond_dims] or [0], dtype=np.uintp))
+    return pol, caps
+
+
+def _truncate_many(mpos, policies, max_bond_dims, route, ranks_only, trace=False):
+    """(results or None, bonds, counts[, trace]) as the driver counted them"""
+    mpos = list(mpos)
+    for m in mpos:
+        if not isinstance(m, MPO):
+            raise T4aError(INVALID_ARGUMENT, "truncate_many: every item must be an MPO")
+    code = _route_code(route)
+    pol, caps = _truncate_args(len(mpos), policies, max_bond_dims, "truncate_many")
+    arr = (c_void_p * max(len(mpos), 1))(*[m._h for m in mpos])
+    n = len(mpos[0]) if mpos else 0
+    bonds = np.zeros(max(len(mpos) * (n + 1), 1), dtype=np.uintp)
+    counts = np.zeros(4, dtype=np.uintp)
+    names = ("launches", "syncs", "n_batched", "n_serial")
+    if trace:
+        steps2 = 2 * max(n - 1, 0)
+        norm2 = np.zeros(max(len(mpos), 1))
+        ranks = np.zeros(max(len(mpos) * steps2, 1), dtype=np.int32)
+        sv = np.zeros(max(len(mpos) * steps2 * 64, 1))
+        _check(_lib.t4a_gpu_mpo_truncate_many_trace(arr, c_size_t(len(mpos)), pol, _p(caps), c_int32(code), _p(bonds), _p(counts), _p(norm2),
+                                                    _p(ranks), _p(sv)))
+        tr = {"norm2": norm2[:len(mpos)], "ranks": ranks[:len(mpos) * steps2].reshape(len(mpos), steps2),
+              "sv": sv[:len(mpos) * steps2 * 64].reshape(len(mpos), steps2, 64)}
+        return None, bonds[:len(mpos) * (n + 1)].reshape(len(mpos), n + 1).astype(np.int64).tolist(), dict(zip(names, (int(v) for v in counts))), tr
+    out = (c_void_p * max(len(mpos), 1))()
+    _check(_lib.t4a_gpu_mpo_truncate_many_counted(arr, c_size_t(len(mpos)), pol, _p(caps), c_int32(code), c_int32(1 if ranks_only else 0),
+                                                  None if ranks_only else out, _p(bonds), _p(counts)))
+    res = None if ranks_only else [MPO._adopt(c_void_p(out[k])) for k in range(len(mpos))]
+    return res, bonds[:len(mpos) * (n + 1)].reshape(len(mpos), n + 1).astype(np.int64).tolist(), dict(zip(names, (int(v) for v in counts)))
+
+
+def truncate_many(mpos, policies=None, max_bond_dims=None, route="auto", ranks_only=False):
+    """``TensorTrain::truncate`` for MPOs of the same number of sites, in lock step, each under its own rule
+    (t4a_gpu_mpo_truncate_many): canonicalise onto the last site, then truncate every bond twice — from ``n - 1`` down to ``0`` and
+    back — with ``policies[k]`` (an ``SvdTruncationPolicy``; all eight combinations) and ``max_bond_dims[k]`` (``None``: no cap); one
+    policy or one cap stands for all items.  Routes and envelope as ``compress_many``; the batched part is ``3 (n - 1)`` launches and
+    one host synchronisation.  ``ranks_only=True`` runs the same launches and returns the bonds (``n + 1`` per item) in place of
+    the MPOs.  The operands are untouched."""
+    res, bonds, _ = _truncate_many(mpos, policies, max_bond_dims, route, ranks_only)
+    return bonds if ranks_only else res
+
+
+def truncate_many_plan(shapes, max_bond_dims=None, route="auto", rules_from_norms=False):
+    """What ``truncate_many`` will do, from shapes alone (t4a_gpu_mpo_truncate_many_plan; host only).  As ``compress_many_plan``;
+    ``launches`` is ``3 (n - 1)``, ``syncs`` 1 — 2 with ``rules_from_norms``, the call shape of the patching driver, which reads the
+    norms after the QR sweep to derive its budgets."""
+    shapes = [[tuple(int(x) for x in site) for site in item] for item in shapes]
+    for item in shapes:
+        for site in item:
+            if len(site) != 4 or min(site) < 0:
+                raise T4aError(INVALID_ARGUMENT, "truncate_many_plan: a site is (l, s1, s2, r)")
+    code = _route_code(route)
+    _, caps = _truncate_args(len(shapes), None, max_bond_dims, "truncate_many_plan")
+    flat = [x for item in shapes for site in item for x in site]
+    dims = np.ascontiguousarray(np.array(flat or [0], dtype=np.uintp))
+    lens = np.ascontiguousarray(np.array([len(item) for item in shapes] or [0], dtype=np.uintp))
+    nb = sum(len(item) + 1 for item in shapes)
+    batched = np.zeros(max(len(shapes), 1), dtype=np.int32)
+    bonds = np.zeros(max(nb, 1), dtype=np.uintp)
+    qr_bonds = np.zeros(max(nb, 1), dtype=np.uintp)
+    counts = np.zeros(3, dtype=np.uintp)
+    _check(_lib.t4a_gpu_mpo_truncate_many_plan(_p(dims), _p(lens), c_size_t(len(shapes)), _p(caps), c_int32(code),
+                                               c_int32(1 if rules_from_norms else 0), _p(batched), _p(bonds), _p(qr_bonds), _p(counts)))
+    out = {"routes": ["batched" if batched[k] else "serial" for k in range(len(shapes))], "bonds": [], "qr_bonds": [],
+           "launches": int(counts[0]), "syncs": int(counts[1]), "n_batched": int(counts[2])}
+    at = 0
+    for item in shapes:
+        out["bonds"].append([int(v) for v in bonds[at:at + len(item) + 1]])
+        out["qr_bonds"].append([int(v) for v in qr_bonds[at:at + len(item) + 1]])
+        at += len(item) + 1
+    return out
+
+
 def _time_compress_many(mpos, options=None, reps=5):
     """Probe (t4a_gpu_mpo_time_compress_many): ms per repetition of (the serial stage item by item, one batched call) on copies."""
     mpos = list(mpos)

@@ -7,6 +7,11 @@ Mirrors ``Projector`` (projector.rs:39-268), ``SubDomainTT::project`` / ``contra
 ``(site, leg)``, leg 0 = s1, leg 1 = s2, and the shared index of ``A·B`` is ``A.(i, 1) == B.(i, 0)``.  Deviations: the task order of a
 contraction is fixed (a-major, insertion order; the reference iterates a hash map), patches keep their insertion order, ``to_mpo``
 sorts by keys then values with a shorter prefix first.  ``Projector`` and ``contract_plan`` touch no device.
+
+Adaptive patching (patching.rs; "Adaptive Patching for Tensor Train Computations", arXiv:2602.22372): ``PatchingOptions``,
+``PatchSplitStrategy``, ``truncate_adaptive``, ``add_with_patching`` and ``contract_adaptive``; ``patch_volume``, ``patch_budgets``, ``split_candidates`` and
+``validate_patching_options`` are their host arithmetic and touch no device; ``contract_adaptive`` is the patch-wise product with
+the same splitting.
 """
 import ctypes
 
@@ -306,6 +311,12 @@ class PartitionedMPO:
         grid = np.indices(shape[::-1]).reshape(len(shape), -1)[::-1].T
         return self.evaluate(grid.reshape(total, len(shape))).reshape(shape, order="F")
 
+    def budget_squared(self, k):
+        """The absolute squared-error budget adaptive patching gave patch k (``SubDomainTT::budget_squared``), or None where unset."""
+        has, v = c_int32(0), c_double(0)
+        _check(_lib.t4a_gpu_pmpo_budget_squared(self._h, c_size_t(k), ctypes.byref(has), ctypes.byref(v)))
+        return v.value if has.value else None
+
     def project(self, projector):
         """SubDomainTT::project (subdomain_tt.rs:171-260) patch by patch: incompatible patches are dropped, the others are masked —
         zeros are stored outside the subdomain, in one launch for all sites of all patches — and carry the intersection."""
@@ -423,3 +434,172 @@ def _time_contract(a, b, tolerance=1e-12, max_bond_dim=None, reps=10):
     _check(_lib.t4a_gpu_pmpo_time_contract(a._h, b._h, c_double(tolerance), c_size_t(0 if max_bond_dim is None else max_bond_dim),
                                            c_size_t(reps), _p(ms)))
     return [float(v) for v in ms]
+
+
+# ---------------------------------------------------------------------------------------- adaptive patching (patching.rs)
+class PatchSplitStrategy:
+    """PatchSplitStrategy (patching.rs:41-48); the default is ExactParameterGain."""
+    Sequential, ExactParameterGain = 0, 1
+
+
+class PatchingOptionsC(ctypes.Structure):
+    """t4a_gpu_patching_options"""
+    _fields_ = [("rtol", c_double), ("has_max_bond_dim", c_int32), ("max_bond_dim", c_size_t), ("patch_order", ctypes.POINTER(c_size_t)),
+                ("n_patch_order", c_size_t), ("split_strategy", c_int32)]
+
+
+class PatchingOptions:
+    """PatchingOptions (patching.rs:68-107); the defaults are PatchingOptions::default().  ``patch_order`` is a list of legs
+    ``(site, leg)``; ``max_bond_dim=None`` is no cap."""
+
+    def __init__(self, rtol=1e-12, max_bond_dim=100, patch_order=(), split_strategy=PatchSplitStrategy.ExactParameterGain):
+        self.rtol = rtol
+        self.max_bond_dim = max_bond_dim
+        self.patch_order = list(patch_order)
+        self.split_strategy = split_strategy
+
+    def to_c(self):
+        """(struct, the array it points into): keep both alive through the call"""
+        flat = []
+        for site, leg in self.patch_order:
+            if int(site) < 0 or int(leg) < 0:
+                raise T4aError(INVALID_ARGUMENT, f"patch_order: leg ({site}, {leg}) is negative")
+            flat += [int(site), int(leg)]
+        if self.max_bond_dim is not None and int(self.max_bond_dim) < 0:
+            raise T4aError(INVALID_ARGUMENT, "max_bond_dim must be at least 1")
+        order = (c_size_t * max(len(flat), 1))(*flat)
+        c = PatchingOptionsC(float(self.rtol), 0 if self.max_bond_dim is None else 1, 0 if self.max_bond_dim is None else int(self.max_bond_dim),
+                             ctypes.cast(order, ctypes.POINTER(c_size_t)), len(self.patch_order), int(self.split_strategy))
+        return c, order
+
+
+def _site_dims(site_dims):
+    return np.ascontiguousarray(np.array([[int(a), int(b)] for a, b in site_dims] or [[0, 0]], dtype=np.uintp).reshape(-1))
+
+
+def validate_patching_options(options, site_dims):
+    """validate_patching_options (patching.rs:617-627) on a chain, host only: raises INVALID_ARGUMENT with the reference's messages."""
+    c, keep = options.to_c()
+    _check(_lib.t4a_gpu_pmpo_validate_patching_options(ctypes.byref(c), _p(_site_dims(site_dims)), c_size_t(len(site_dims))))
+    del keep
+
+
+def patch_volume(projector, site_dims):
+    """subdomain_volume (patching.rs:724-738), host only: the product of the dims of the unprojected legs."""
+    t, c = Projector._of(projector)._c()
+    v = c_size_t(0)
+    _check(_lib.t4a_gpu_pmpo_patch_volume(_p(t), c_size_t(c), _p(_site_dims(site_dims)), c_size_t(len(site_dims)), ctypes.byref(v)))
+    return v.value
+
+
+def patch_budgets(volumes, norms_squared, rtol):
+    """The budget arithmetic of ``truncate_adaptive`` (patching.rs:577-606), host only: ``(budgets, drop)`` with ``budgets[k] = rtol^2
+    sum(norms_squared) volumes[k] / sum(volumes)`` and ``drop[k] = norms_squared[k] <= budgets[k]``; ``None`` for no patch or a zero
+    total volume (the empty result)."""
+    vol = [int(v) for v in volumes]
+    if min(vol or [0]) < 0:
+        raise T4aError(INVALID_ARGUMENT, "patch_budgets: a volume is negative")
+    v = np.ascontiguousarray(np.array(vol or [0], dtype=np.uintp))
+    n2 = np.ascontiguousarray(np.array(list(norms_squared) or [0.0], dtype=np.float64))
+    if len(vol) != len(list(norms_squared)):
+        raise T4aError(INVALID_ARGUMENT, f"patch_budgets: {len(vol)} volumes but {len(list(norms_squared))} norms")
+    budgets, drop, empty = np.zeros(max(len(vol), 1)), np.zeros(max(len(vol), 1), dtype=np.int32), c_int32(0)
+    _check(_lib.t4a_gpu_pmpo_patch_budgets(_p(v), _p(n2), c_size_t(len(vol)), c_double(rtol), _p(budgets), _p(drop), ctypes.byref(empty)))
+    if empty.value:
+        return None
+    return budgets[:len(vol)], [bool(d) for d in drop[:len(vol)]]
+
+
+def split_candidates(projector, site_dims, options):
+    """split_candidates (patching.rs:801-823), host only: the unprojected legs of ``options.patch_order``, or all legs in chain order
+    when it is empty; duplicates removed."""
+    t, c = Projector._of(projector)._c()
+    o, keep = options.to_c()
+    legs, n = np.zeros(max(4 * len(site_dims), 2), dtype=np.uintp), c_size_t(0)
+    _check(_lib.t4a_gpu_pmpo_split_candidates(_p(t), c_size_t(c), _p(_site_dims(site_dims)), c_size_t(len(site_dims)), ctypes.byref(o), _p(legs),
+                                              ctypes.byref(n)))
+    del keep
+    return [(int(legs[2 * k]), int(legs[2 * k + 1])) for k in range(n.value)]
+
+
+_COUNTS6 = ("rounds", "truncate_calls", "ranks_only_calls", "launches", "syncs", "splits")
+
+
+def _truncate_adaptive(p, rtol, max_bond_dim, route):
+    h = c_void_p()
+    counts = np.zeros(6, dtype=np.uintp)
+    if max_bond_dim is not None and int(max_bond_dim) < 0:
+        raise T4aError(INVALID_ARGUMENT, "max_bond_dim must be at least 1")
+    _check(_lib.t4a_gpu_pmpo_truncate_adaptive(p._h, c_double(rtol), c_int32(0 if max_bond_dim is None else 1),
+                                               c_size_t(0 if max_bond_dim is None else int(max_bond_dim)), c_int32(_route_code(route)),
+                                               ctypes.byref(h), _p(counts)))
+    return PartitionedMPO._adopt(h), dict(zip(_COUNTS6, (int(v) for v in counts)))
+
+
+def truncate_adaptive(p, rtol, max_bond_dim=None, route="auto"):
+    """truncate_adaptive (patching.rs:566-615): every patch gets the absolute squared-error budget ``rtol^2 |F|^2 volume / total
+    volume``; patches whose squared norm is at or below their budget are dropped, the others are truncated with Absolute /
+    SquaredValue / DiscardedTailSum at the budget and ``max_bond_dim``, all in ONE ``mpo.truncate_many`` call whose QR sweep supplies the
+    norms (two host synchronisations).  The survivors keep their order, are the truncations of the masked patches, and carry
+    ``budget_squared``.  ``route``: that of ``mpo.truncate_many``."""
+    return _truncate_adaptive(p, rtol, max_bond_dim, route)[0]
+
+
+def _time_truncate_adaptive(p, rtol, max_bond_dim=None):
+    """Probe (t4a_gpu_pmpo_truncate_adaptive_timed): wall ms of (QR sweep, first sync, leftward sweep, rightward sweep, last sync) of the
+    batched part of one ``truncate_adaptive`` call, the stream drained after every sweep."""
+    ms = np.zeros(5)
+    _check(_lib.t4a_gpu_pmpo_truncate_adaptive_timed(p._h, c_double(rtol), c_int32(0 if max_bond_dim is None else 1),
+                                                     c_size_t(0 if max_bond_dim is None else int(max_bond_dim)), _p(ms)))
+    return [float(v) for v in ms]
+
+
+def _add_with_patching(patches, projectors, options, route, site_dims=None):
+    o = PatchingOptions() if options is None else options
+    src = patches if isinstance(patches, PartitionedMPO) else None
+    if src is None:
+        patches = list(patches)
+        if patches:
+            validate_patching_options(o, site_dims if site_dims is not None else patches[0].site_dims())
+        src = PartitionedMPO(patches, projectors, site_dims)
+    c, keep = o.to_c()
+    h = c_void_p()
+    counts = np.zeros(6, dtype=np.uintp)
+    cap = 2 * max(src.n_sites(), 1) * max(len(src), 1) * 64
+    chosen, n_chosen = np.zeros(2 * cap, dtype=np.uintp), c_size_t(0)
+    _check(_lib.t4a_gpu_pmpo_add_with_patching(src._h, ctypes.byref(c), c_int32(_route_code(route)), ctypes.byref(h), _p(counts), _p(chosen),
+                                               c_size_t(cap), ctypes.byref(n_chosen)))
+    del keep
+    legs = [(int(chosen[2 * k]), int(chosen[2 * k + 1])) for k in range(min(n_chosen.value, cap))]
+    return PartitionedMPO._adopt(h), dict(zip(_COUNTS6, (int(v) for v in counts))), legs
+
+
+def add_with_patching(patches, projectors=None, options=None, route="auto", site_dims=None):
+    """add_with_patching (patching.rs:154-198) over MPO patches with their projectors (or a ``PartitionedMPO``): each round assigns the
+    volume budgets, budget-truncates without a cap, and replaces every patch that stays above ``options.max_bond_dim`` by its children
+    along a leg — the first candidate (``Sequential``) or the one whose budget-truncated children hold the fewest parameters
+    (``ExactParameterGain``: all children of all candidates of all such patches in one ranks-only ``mpo.truncate_many`` call; ties keep
+    the first).  Ends with ``truncate_adaptive``."""
+    return _add_with_patching(patches, projectors, options, route, site_dims)[0]
+
+
+def _contract_adaptive(a, b, algorithm, options, patching_options, route):
+    o = ContractionOptions() if options is None else options
+    po = PatchingOptions() if patching_options is None else patching_options
+    c, keep = po.to_c()
+    h = c_void_p()
+    counts = np.zeros(6, dtype=np.uintp)
+    _check(_lib.t4a_gpu_pmpo_contract_adaptive(a._h, b._h, c_int32(algorithm), c_int32(o.factorize_method), c_double(o.tolerance),
+                                               c_size_t(0 if o.max_bond_dim is None else o.max_bond_dim), ctypes.byref(c),
+                                               c_int32(_route_code(route)), ctypes.byref(h), _p(counts)))
+    del keep
+    return PartitionedMPO._adopt(h), dict(zip(_COUNTS6, (int(v) for v in counts)))
+
+
+def contract_adaptive(a, b, algorithm=ContractionAlgorithm.Naive, options=None, patching_options=None, route="auto"):
+    """contract_adaptive (patching.rs:282-412): the pairwise products of the patches of ``a`` and ``b`` (``options``: the
+    ``ContractionOptions`` of ``contract``) grouped by result projector; per group the contributions are summed by direct sum and
+    truncated after each addition; when the sum or a contribution reaches ``patching_options.max_bond_dim`` the group is split along a leg
+    of the result — ``(i, 0)`` is ``a``'s s1 leg of site i, ``(i, 1)`` ``b``'s s2 leg —, the operand that has the leg is projected per
+    value and truncated with Relative / Value / PerValue at 64 eps, and the group recurses.  Ends with ``truncate_adaptive``."""
+    return _contract_adaptive(a, b, algorithm, options, patching_options, route)[0]
