@@ -1892,6 +1892,72 @@ t4a_gpu_status t4a_gpu_swap_theta_time(size_t bond, size_t reps, double* ms2);
 t4a_gpu_status t4a_gpu_legtrain_reorder(t4a_gpu_tt* tt, const size_t* leg_counts, int64_t* keys, size_t* dims, const size_t* sites,
                                         const size_t* order_counts, const int64_t* order_keys, size_t n_named);
 
+/* ---- fuse_to, split_to and restructure_to on a chain (tensor4all-treetn: treetn/transform.rs, treetn/restructure/mod.rs,
+ * options.rs: SplitOptions, RestructureOptions), f64, by position.  The train is described as for swap_site_indices (leg_counts / keys /
+ * dims: per site its legs, first leg fastest).  The target is an ordered list of n_groups groups of keys (group_counts[n_groups],
+ * group_keys): group j is site j of the result and the order of its keys the leg order of that site, first key fastest.  Refused
+ * before the device is touched: an empty group, a key in two groups, a key set that differs from the train's. */
+#define T4A_GPU_RESTRUCTURE_FUSE_ONLY 0
+#define T4A_GPU_RESTRUCTURE_SWAP_THEN_FUSE 1
+#define T4A_GPU_RESTRUCTURE_SPLIT_ONLY 2
+#define T4A_GPU_RESTRUCTURE_SWAP_ONLY 3
+#define T4A_GPU_RESTRUCTURE_SPLIT_THEN_FUSE 4
+#define T4A_GPU_FUSE_MAX_LEGS 16
+#define T4A_GPU_FUSE_ROUTE_SCALAR 1
+#define T4A_GPU_FUSE_ROUTE_MFMA 2
+/* The plan, host only (no device is needed).  op 0: restructure_to — *kind receives the T4A_GPU_RESTRUCTURE_* kind, chosen with the
+ * precedence of build_plan; op 1: fuse_to and op 2: split_to with their own conditions and messages (*kind = FUSE_ONLY / SPLIT_ONLY).
+ * link_dims (n_sites - 1 bonds, may be NULL) adds the check that no core of a fuse exceeds INT_MAX elements.  out_leg_counts (n_groups
+ * entries) / out_keys / out_dims (as many legs as came in): the legs of the result.  counts4: [0] the rounds of the fuse phase
+ * (k_max - 1), [1] its launches (the rounds plus one when a group of one site is reordered; for op 2 the reorder launch of the split),
+ * [2] the QR factorisations of the split phase, [3] the entries of the swap target written to swap_keys / swap_sites (capacity: the
+ * number of legs; may be NULL when not wanted). */
+t4a_gpu_status t4a_gpu_restructure_plan(int32_t op, size_t n_sites, const size_t* leg_counts, const int64_t* keys, const size_t* dims,
+                                        const size_t* link_dims, size_t n_groups, const size_t* group_counts, const int64_t* group_keys,
+                                        int32_t* kind, size_t* out_leg_counts, int64_t* out_keys, size_t* out_dims, size_t* counts4,
+                                        int64_t* swap_keys, size_t* swap_sites);
+/* fuse_to: a new train of n_groups sites, exact.  Every site's legs lie in one group, the sites of a group are contiguous, groups
+ * ascend; sites without legs are absorbed as in the reference.  All groups are contracted in lock step, left to right: k_max - 1
+ * launches of one kernel for a largest group of k_max sites, the last round of a group writing its legs in the target's order; a group
+ * of one site in another order costs one reorder launch.  center: the train's centre or -1; *out_center the group that holds it or -1.
+ * _counted also reports the launches. */
+t4a_gpu_status t4a_gpu_tt_fuse_to(const t4a_gpu_tt* tt, const size_t* leg_counts, const int64_t* keys, const size_t* dims, int64_t center,
+                                  size_t n_groups, const size_t* group_counts, const int64_t* group_keys, t4a_gpu_tt** out,
+                                  size_t* out_leg_counts, int64_t* out_keys, size_t* out_dims, int64_t* out_center);
+t4a_gpu_status t4a_gpu_tt_fuse_to_counted(const t4a_gpu_tt* tt, const size_t* leg_counts, const int64_t* keys, const size_t* dims,
+                                          int64_t center, size_t n_groups, const size_t* group_counts, const int64_t* group_keys,
+                                          t4a_gpu_tt** out, size_t* out_leg_counts, int64_t* out_keys, size_t* out_dims,
+                                          int64_t* out_center, size_t* launches);
+/* split_to: every group's legs lie on one site, the groups of a site are consecutive and sites ascend.  Phase 1 (exact): one reorder
+ * launch, then fragment after fragment peeled from the left by the thin QR with the rank rule of t4a_gpu_qr_retained_rank at rtol 0.
+ * form: 0 unitary (1 LU, 2 CI: NOT_IMPLEMENTED).  final_sweep != 0: TensorTrain::truncate by the serial stage of
+ * t4a_gpu_mpo_truncate_many with `policy` (NULL: the default policy) and max_bond_dim.  The result has no centre.  *n_qr (may be NULL):
+ * the QR factorisations. */
+t4a_gpu_status t4a_gpu_tt_split_to(const t4a_gpu_tt* tt, const size_t* leg_counts, const int64_t* keys, const size_t* dims, size_t n_groups,
+                                   const size_t* group_counts, const int64_t* group_keys, int32_t form, const t4a_gpu_svd_policy* policy,
+                                   int32_t has_max_bond_dim, size_t max_bond_dim, int32_t final_sweep, t4a_gpu_tt** out,
+                                   size_t* out_leg_counts, int64_t* out_keys, size_t* out_dims, size_t* n_qr);
+/* restructure_to: plan (t4a_gpu_restructure_plan, op 0), then the phases of the kind with the split options (as t4a_gpu_tt_split_to), the
+ * swap options (as t4a_gpu_tt_swap_site_indices) and, when final_policy is not NULL, a final truncation as above with final_policy and
+ * final_max_bond_dim (0: no cap).  counts3 (may be NULL): launches of the fuse and reorder kernels, QR factorisations, swap steps. */
+t4a_gpu_status t4a_gpu_tt_restructure_to(const t4a_gpu_tt* tt, const size_t* leg_counts, const int64_t* keys, const size_t* dims,
+                                         int64_t center, size_t n_groups, const size_t* group_counts, const int64_t* group_keys,
+                                         int32_t split_form, const t4a_gpu_svd_policy* split_policy, int32_t split_has_max_bond_dim,
+                                         size_t split_max_bond_dim, int32_t split_final_sweep, int32_t swap_has_max_bond_dim,
+                                         size_t swap_max_bond_dim, int32_t swap_has_rtol, double swap_rtol,
+                                         const t4a_gpu_svd_policy* final_policy, size_t final_max_bond_dim, t4a_gpu_tt** out,
+                                         size_t* out_leg_counts, int64_t* out_keys, size_t* out_dims, int32_t* kind, int64_t* out_center,
+                                         size_t* counts3);
+/* Test hook, the counterpart of t4a_gpu_swap_theta: ONE launch of the fuse kernel over n_jobs jobs on host cores.  Job k: shapes5[5 k ..]
+ * = (l, X, m, Y, r), A[l, X, m] and B[m, Y, r] concatenated in a / b; leg_counts[k] legs of the result site with their dims in chain
+ * order (leg_dims) and, per leg of the result in its new order, its position in chain order (leg_order); leg_counts[k] == 0: chain
+ * order.  out: the results [l, X Y, r] concatenated; routes[k]: the T4A_GPU_FUSE_ROUTE_* bits of job k. */
+t4a_gpu_status t4a_gpu_fuse_round(size_t n_jobs, const double* a, const double* b, const size_t* shapes5, const size_t* leg_counts,
+                                  const size_t* leg_dims, const size_t* leg_order, double* out, int32_t* routes);
+/* Probe (tools/probe_restructure.py): device ms per repetition of fusing n_groups pairs of binary-leg sites with every bond equal to
+ * `bond`: [0] the one lock-step launch, [1] one t4a_gpu_swap_theta kernel launch per pair, issued group by group. */
+t4a_gpu_status t4a_gpu_fuse_time(size_t n_groups, size_t bond, size_t reps, double* ms2);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -26,6 +26,7 @@
 #include "pmpo_patching.hpp"
 #include "linsolve.hpp"
 #include "swap.hpp"
+#include "restructure.hpp"
 
 struct t4a_gpu_tci2 {
     t4a::Tci2 impl;
@@ -913,6 +914,62 @@ std::vector<SwapLeg> leg_list(const int64_t* keys, const size_t* dims, size_t co
     }
     for (size_t k = 0; k < count; ++k) v.push_back({keys[k], dims[k]});
     return v;
+}
+
+RestructureTarget restructure_target(size_t n_groups, const size_t* group_counts, const int64_t* group_keys)
+{
+    RestructureTarget t(n_groups);
+    if (n_groups) T4A_REQUIRE_PTR(group_counts);
+    size_t at = 0;
+    for (size_t j = 0; j < n_groups; ++j)
+        for (size_t k = 0; k < group_counts[j]; ++k, ++at) {
+            T4A_REQUIRE_PTR(group_keys);
+            t[j].push_back(group_keys[at]);
+        }
+    return t;
+}
+
+SplitOptions split_options(int32_t form, const t4a_gpu_svd_policy* policy, int32_t has_max_bond_dim, size_t max_bond_dim, int32_t final_sweep)
+{
+    SplitOptions o;
+    o.form = form;
+    o.has_policy = policy != nullptr;
+    if (policy) o.policy = SvdPolicy{policy->threshold, policy->scale, policy->measure, policy->rule};
+    o.has_max_bond_dim = has_max_bond_dim != 0, o.max_bond_dim = max_bond_dim;
+    o.final_sweep = final_sweep != 0;
+    return o;
+}
+
+size_t center_in(int64_t center, size_t n)
+{
+    if (center < 0) return NO_CENTER;
+    if ((size_t)center >= n) throw Error(T4A_GPU_INVALID_ARGUMENT, "the centre " + std::to_string(center) + " is not a site of the train");
+    return (size_t)center;
+}
+
+t4a_gpu_status tt_fuse_to(const t4a_gpu_tt* tt, const size_t* leg_counts, const int64_t* keys, const size_t* dims, int64_t center,
+                          size_t n_groups, const size_t* group_counts, const int64_t* group_keys, t4a_gpu_tt** out, size_t* out_leg_counts,
+                          int64_t* out_keys, size_t* out_dims, int64_t* out_center, size_t* launches)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(out);
+        *out = nullptr;
+        T4A_REQUIRE_PTR(tt);
+        SiteLegs legs = site_legs(tt->impl.len(), leg_counts, keys, dims);
+        const RestructureTarget target = restructure_target(n_groups, group_counts, group_keys);
+        const size_t c = center_in(center, tt->impl.len());
+        std::vector<size_t> links;
+        for (size_t i = 0; i + 1 < tt->impl.len(); ++i) links.push_back(tt->impl.cores[i].r);
+        fuse_plan(legs, target, &links); // the refusals, before the device is touched
+        // the work happens on a copy with an engine of its own; the input stays as it is
+        std::unique_ptr<t4a_gpu_tt> res(new t4a_gpu_tt(tt->impl.cores, tt->impl.eng.stream()));
+        const RestructureResult r = fuse_to(res->impl.eng, res->impl.cores, legs, target, c);
+        res->impl.eng.sync();
+        write_legs(legs, out_leg_counts, out_keys, out_dims);
+        if (out_center) *out_center = r.center == NO_CENTER ? -1 : (int64_t)r.center;
+        if (launches) *launches = r.launches;
+        *out = res.release();
+    });
 }
 
 } // namespace
@@ -5927,6 +5984,165 @@ t4a_gpu_status t4a_gpu_legtrain_reorder(t4a_gpu_tt* tt, const size_t* leg_counts
         }
         legtrain_reorder(tt->impl.eng, tt->impl.cores, legs, orders);
         write_legs(legs, nullptr, keys, dims);
+    });
+}
+
+
+// ---- fuse_to, split_to, restructure_to on a chain (restructure.hpp) ----
+t4a_gpu_status t4a_gpu_restructure_plan(int32_t op, size_t n_sites, const size_t* leg_counts, const int64_t* keys, const size_t* dims,
+                                        const size_t* link_dims, size_t n_groups, const size_t* group_counts, const int64_t* group_keys,
+                                        int32_t* kind, size_t* out_leg_counts, int64_t* out_keys, size_t* out_dims, size_t* counts4,
+                                        int64_t* swap_keys, size_t* swap_sites)
+{
+    return guarded([&] {
+        if (op < 0 || op > 2) throw Error(T4A_GPU_INVALID_ARGUMENT, "restructure_plan: op is 0 (restructure_to), 1 (fuse_to) or 2 (split_to)");
+        const SiteLegs legs = site_legs(n_sites, leg_counts, keys, dims);
+        const RestructureTarget target = restructure_target(n_groups, group_counts, group_keys);
+        std::vector<size_t> links;
+        if (link_dims && n_sites) links.assign(link_dims, link_dims + (n_sites - 1));
+        RestructurePlan p;
+        if (op == 1) {
+            const FusePlan fp = fuse_plan(legs, target, link_dims ? &links : nullptr);
+            p.kind = RestructureKind::FuseOnly;
+            p.legs = fp.legs, p.fuse_rounds = fp.rounds, p.fuse_launches = fp.launches;
+        } else if (op == 2) {
+            const SplitPlan sp = split_plan(legs, target);
+            p.kind = RestructureKind::SplitOnly;
+            p.legs = sp.legs, p.n_qr = sp.n_qr, p.fuse_launches = sp.launches;
+        } else {
+            p = restructure_plan(legs, target, link_dims ? &links : nullptr);
+        }
+        if (kind) *kind = (int32_t)p.kind;
+        write_legs(p.legs, out_leg_counts, out_keys, out_dims);
+        if (counts4) counts4[0] = p.fuse_rounds, counts4[1] = p.fuse_launches, counts4[2] = p.n_qr, counts4[3] = p.swap_target.size();
+        for (size_t k = 0; k < p.swap_target.size(); ++k) {
+            if (swap_keys) swap_keys[k] = p.swap_target[k].first;
+            if (swap_sites) swap_sites[k] = p.swap_target[k].second;
+        }
+    });
+}
+
+t4a_gpu_status t4a_gpu_tt_fuse_to(const t4a_gpu_tt* tt, const size_t* leg_counts, const int64_t* keys, const size_t* dims, int64_t center,
+                                  size_t n_groups, const size_t* group_counts, const int64_t* group_keys, t4a_gpu_tt** out,
+                                  size_t* out_leg_counts, int64_t* out_keys, size_t* out_dims, int64_t* out_center)
+{
+    return tt_fuse_to(tt, leg_counts, keys, dims, center, n_groups, group_counts, group_keys, out, out_leg_counts, out_keys, out_dims, out_center,
+                      nullptr);
+}
+
+t4a_gpu_status t4a_gpu_tt_fuse_to_counted(const t4a_gpu_tt* tt, const size_t* leg_counts, const int64_t* keys, const size_t* dims,
+                                          int64_t center, size_t n_groups, const size_t* group_counts, const int64_t* group_keys,
+                                          t4a_gpu_tt** out, size_t* out_leg_counts, int64_t* out_keys, size_t* out_dims,
+                                          int64_t* out_center, size_t* launches)
+{
+    return tt_fuse_to(tt, leg_counts, keys, dims, center, n_groups, group_counts, group_keys, out, out_leg_counts, out_keys, out_dims, out_center,
+                      launches);
+}
+
+t4a_gpu_status t4a_gpu_tt_split_to(const t4a_gpu_tt* tt, const size_t* leg_counts, const int64_t* keys, const size_t* dims, size_t n_groups,
+                                   const size_t* group_counts, const int64_t* group_keys, int32_t form, const t4a_gpu_svd_policy* policy,
+                                   int32_t has_max_bond_dim, size_t max_bond_dim, int32_t final_sweep, t4a_gpu_tt** out,
+                                   size_t* out_leg_counts, int64_t* out_keys, size_t* out_dims, size_t* n_qr)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(out);
+        *out = nullptr;
+        T4A_REQUIRE_PTR(tt);
+        const SplitOptions o = split_options(form, policy, has_max_bond_dim, max_bond_dim, final_sweep);
+        o.validate();
+        SiteLegs legs = site_legs(tt->impl.len(), leg_counts, keys, dims);
+        const RestructureTarget target = restructure_target(n_groups, group_counts, group_keys);
+        split_plan(legs, target); // the refusals, before the device is touched
+        std::unique_ptr<t4a_gpu_tt> res(new t4a_gpu_tt(tt->impl.cores, tt->impl.eng.stream()));
+        const RestructureResult r = split_to(res->impl.eng, res->impl.cores, legs, target, o);
+        res->impl.eng.sync();
+        write_legs(legs, out_leg_counts, out_keys, out_dims);
+        if (n_qr) *n_qr = r.n_qr;
+        *out = res.release();
+    });
+}
+
+t4a_gpu_status t4a_gpu_tt_restructure_to(const t4a_gpu_tt* tt, const size_t* leg_counts, const int64_t* keys, const size_t* dims,
+                                         int64_t center, size_t n_groups, const size_t* group_counts, const int64_t* group_keys,
+                                         int32_t split_form, const t4a_gpu_svd_policy* split_policy, int32_t split_has_max_bond_dim,
+                                         size_t split_max_bond_dim, int32_t split_final_sweep, int32_t swap_has_max_bond_dim,
+                                         size_t swap_max_bond_dim, int32_t swap_has_rtol, double swap_rtol,
+                                         const t4a_gpu_svd_policy* final_policy, size_t final_max_bond_dim, t4a_gpu_tt** out,
+                                         size_t* out_leg_counts, int64_t* out_keys, size_t* out_dims, int32_t* kind, int64_t* out_center,
+                                         size_t* counts3)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(out);
+        *out = nullptr;
+        T4A_REQUIRE_PTR(tt);
+        RestructureOptions o;
+        o.split = split_options(split_form, split_policy, split_has_max_bond_dim, split_max_bond_dim, split_final_sweep);
+        o.swap.has_max_bond_dim = swap_has_max_bond_dim != 0, o.swap.max_bond_dim = swap_max_bond_dim;
+        o.swap.has_rtol = swap_has_rtol != 0, o.swap.rtol = swap_rtol;
+        o.has_final_truncation = final_policy != nullptr;
+        if (final_policy) o.final_policy = SvdPolicy{final_policy->threshold, final_policy->scale, final_policy->measure, final_policy->rule};
+        o.final_max_bond_dim = final_max_bond_dim;
+        o.validate();
+        SiteLegs legs = site_legs(tt->impl.len(), leg_counts, keys, dims);
+        const RestructureTarget target = restructure_target(n_groups, group_counts, group_keys);
+        const size_t c = center_in(center, tt->impl.len());
+        std::vector<size_t> links;
+        for (size_t i = 0; i + 1 < tt->impl.len(); ++i) links.push_back(tt->impl.cores[i].r);
+        restructure_plan(legs, target, &links); // the refusals, before the device is touched
+        std::unique_ptr<t4a_gpu_tt> res(new t4a_gpu_tt(tt->impl.cores, tt->impl.eng.stream()));
+        RestructureKind k = RestructureKind::FuseOnly;
+        const RestructureResult r = restructure_to(res->impl.eng, res->impl.cores, legs, target, o, c, &k);
+        res->impl.eng.sync();
+        write_legs(legs, out_leg_counts, out_keys, out_dims);
+        if (kind) *kind = (int32_t)k;
+        if (out_center) *out_center = r.center == NO_CENTER ? -1 : (int64_t)r.center;
+        if (counts3) counts3[0] = r.launches, counts3[1] = r.n_qr, counts3[2] = r.n_swap_steps;
+        *out = res.release();
+    });
+}
+
+t4a_gpu_status t4a_gpu_fuse_round(size_t n_jobs, const double* a, const double* b, const size_t* shapes5, const size_t* leg_counts,
+                                  const size_t* leg_dims, const size_t* leg_order, double* out, int32_t* routes)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(a);
+        T4A_REQUIRE_PTR(b);
+        T4A_REQUIRE_PTR(shapes5);
+        T4A_REQUIRE_PTR(leg_counts);
+        T4A_REQUIRE_PTR(out);
+        std::vector<FuseRoundHostJob> jobs(n_jobs);
+        size_t at_a = 0, at_b = 0, at_leg = 0;
+        for (size_t k = 0; k < n_jobs; ++k) {
+            FuseRoundHostJob& j = jobs[k];
+            j.l = shapes5[5 * k], j.X = shapes5[5 * k + 1], j.m = shapes5[5 * k + 2], j.Y = shapes5[5 * k + 3], j.r = shapes5[5 * k + 4];
+            j.A = a + at_a, j.B = b + at_b;
+            at_a += j.l * j.X * j.m, at_b += j.m * j.Y * j.r;
+            if (leg_counts[k]) {
+                T4A_REQUIRE_PTR(leg_dims);
+                T4A_REQUIRE_PTR(leg_order);
+                j.leg_dims.assign(leg_dims + at_leg, leg_dims + at_leg + leg_counts[k]);
+                j.order.assign(leg_order + at_leg, leg_order + at_leg + leg_counts[k]);
+                at_leg += leg_counts[k];
+            }
+        }
+        require_device();
+        std::vector<int> rt;
+        const std::vector<std::vector<double>> res = fuse_round(jobs, rt);
+        size_t at = 0;
+        for (size_t k = 0; k < n_jobs; ++k) {
+            std::memcpy(out + at, res[k].data(), res[k].size() * sizeof(double));
+            at += res[k].size();
+            if (routes) routes[k] = rt[k];
+        }
+    });
+}
+
+t4a_gpu_status t4a_gpu_fuse_time(size_t n_groups, size_t bond, size_t reps, double* ms2)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(ms2);
+        require_device();
+        fuse_time(n_groups, bond, (int)std::min<size_t>(reps, 1u << 20), &ms2[0], &ms2[1]);
     });
 }
 

@@ -735,6 +735,29 @@ struct LegReorderJob {
 void leg_reorder_launch(const LegReorderJob* d_jobs, int n_jobs, unsigned long long total, hipStream_t stream);
 
 // ------------------------------------------------------------------------------------------------
+// kernels_restructure.hip — one round of fuse_to (restructure.hpp) for every group of a chain: per job
+//   out[l_idx + l * (f + X * Y * r_idx)] = sum_m A[l_idx, x, m] * B[m, y, r_idx]
+// with f = x + X * y read through the leg table: leg k of the result site in chain order (at most FUSE_MAX_LEGS) has dimension dim[k]
+// and contributes its digit of x + X * y times dst[k]; n_legs == 0 is the chain order (f = x + X * y).  Job k owns the work items
+// off[k] .. off[k] + fuse_round_items(l, X, Y, r); n_items is their sum.  fuse_round_launch returns false, having launched nothing,
+// when the grid would hold more than INT_MAX workgroups.
+// ------------------------------------------------------------------------------------------------
+constexpr int FUSE_MAX_LEGS = 16;
+struct FuseRoundJob {
+    const double* A; // [l, X, m]
+    const double* B; // [m, Y, r]
+    double* out;     // [l, X * Y, r]
+    unsigned long long off;
+    int l, X, m, Y, r;
+    int n_legs;
+    int dim[FUSE_MAX_LEGS], dst[FUSE_MAX_LEGS];
+};
+constexpr int FUSE_ROUTE_SCALAR = 1, FUSE_ROUTE_MFMA = 2; // bits of the route a job takes: tiles per thread / on the matrix cores
+int fuse_round_route(int l, int r);
+unsigned long long fuse_round_items(int l, int X, int Y, int r);
+bool fuse_round_launch(const FuseRoundJob* d_jobs, int n_jobs, unsigned long long n_items, hipStream_t stream);
+
+// ------------------------------------------------------------------------------------------------
 // kernels_contraction.hip — environments of the lazy product A·B of two MPOs (simplett/src/mpo/contraction.rs:262-383) for a batch
 // of unique index halves, one workgroup per half.  An environment is a matrix over the bond pair, column-major [a + dim_a * b];
 // item `it` of a launch is written to d_out + it * ld.  idx holds the (i, j) pairs of the walked sites per item, item-major.

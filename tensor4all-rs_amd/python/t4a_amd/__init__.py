@@ -2249,3 +2249,7 @@ from .partial import PartialContractionSpec, partial_plan, partial_contract, par
 from . import swap  # noqa: E402
 from .swap import (SwapOptions, ScheduledSwapStep, SwapSchedule, LegTrain, swap_site_indices, swap_site_indices_by_index,  # noqa: E402,F401
                    swap_site_indices_legs, regroup_quantics, quantics_target, swap_theta)
+# fuse_to, split_to and restructure_to: module t4a_amd.restructure (the hooks fuse_round, fuse_time and the plans live there)
+from . import restructure  # noqa: E402
+from .restructure import (SplitOptions, RestructureOptions, fuse_to, split_to, restructure_to, restructure_plan, fuse_plan,  # noqa: E402,F401
+                          split_plan, fuse_quantics, unfuse_quantics, fuse_round)
