@@ -1344,6 +1344,11 @@ t4a_gpu_status t4a_gpu_projected_operator_environment(t4a_gpu_projected_operator
 t4a_gpu_status t4a_gpu_projected_operator_apply_one_site(t4a_gpu_projected_operator* h, size_t site, const double* v, double* out,
                                                          int32_t* reused_hl);
 t4a_gpu_status t4a_gpu_projected_operator_time_one_site(t4a_gpu_projected_operator* h, size_t site, size_t reps, double* ms /* [3] */);
+/* Test hook of one-site TDVP: the environment of the bond-centre step next to `site`, built with the PRESENT tensor of that site as the
+ * isometry Q (ProjectedOperator::prepare_bond_center): toward_right 1: La[:, w, :] = Q^T (HL_w Q) with HL = L_site A_site, which is also
+ * L_{site+1}; 0: Rb[:, w, :] = (Q HR_w^T) Q^T with HR = A_site R_{site+1}, which is also R_site.  dims3 receives (k, W, k); out may be NULL. */
+t4a_gpu_status t4a_gpu_projected_operator_bond_center_env(t4a_gpu_projected_operator* h, size_t site, int32_t toward_right, size_t* dims3,
+                                                          double* out);
 t4a_gpu_status t4a_gpu_projected_operator_invalidate(t4a_gpu_projected_operator* h, size_t site);
 t4a_gpu_status t4a_gpu_projected_operator_set_site_tensors(t4a_gpu_projected_operator* h, size_t site, const size_t* dims3_a, const double* t_a,
                                                            const size_t* dims3_b, const double* t_b);
@@ -1464,8 +1469,8 @@ t4a_gpu_status t4a_gpu_lanczos_time_finalise(size_t len, size_t nb, size_t reps,
  *   - `center` must be 0 or n - 1: the reference's two-site plan from an inner root of a chain applies a site correction at a leaf
  *     where the projector splitting needs it at the root (relative error 0.17 against exp(tau H) psi at n = 4 from centre 1, 1e-15
  *     from an end); from an end it is the standard 2TDVP sweep;
- *   - nsite = 1 is not implemented (it needs the bond-centre apply), with a message of its own; nsite outside {1, 2} gets the
- *     reference's.
+ *   - nsite = 1 is refused here with a message of its own (nsite outside {1, 2} gets the reference's): one-site TDVP has entry points
+ *     of its own, t4a_gpu_tdvp_one_site_plan and t4a_gpu_tdvp_one_site below.
  * `init` is canonicalised onto `center`.  One sweep runs the plan of t4a_gpu_tdvp_plan: two-site steps (theta_0 = x_i x_{i+1}, the
  * Krylov exponential with the step's exponent, an SVD split with max_bond_dim / svd_policy, the singular values into the new centre,
  * no renormalisation) and, between two of them, the site correction with minus the exponent on the shared site.  Where the centre is
@@ -1518,6 +1523,63 @@ t4a_gpu_status t4a_gpu_tdvp(const t4a_gpu_mpo* op, const t4a_gpu_tt* init, size_
 t4a_gpu_status t4a_gpu_krylov_expm_dense(const double* H, size_t n, const double* v0, double tau, const t4a_gpu_krylov_expm_options* options,
                                          double* out, size_t* iterations, double* error_estimate, int32_t* converged, size_t* time_splits);
 
+/* ---- one-site TDVP (TdvpOptions::with_nsite(1), tdvp/mod.rs:639-914, tdvp/plan.rs:97-111): every bond dimension stays fixed, a step
+ * needs no SVD.  Scope and the real exponent as t4a_gpu_tdvp; ANY centre 0 <= center < n.
+ * The plan (t4a_gpu_tdvp_one_site_plan, host only, in the shape of t4a_gpu_tdvp_plan): the nodes in post order from `center` — the left
+ * arm leaf first (0 .. c-1), then the right arm leaf first (n-1 .. c+1), then c —, every step of kind 2 (one site) with nodes (node, node),
+ * new_center = node and the exponent tau * weight; every even substep (1-based) is the reversed list.
+ * The driver: `init` is canonicalised onto `center`; per step the centre moves to the node by full-rank thin QR steps, then the Krylov
+ * exponential with the step's exponent on the site tensor.  A bond correction follows iff the next step of the same sweep's plan exists and
+ * has another node: the site is factorised towards it by the full-rank thin QR of the centre moves (x = Q C to the right, C Q to the left,
+ * k = min(rows, columns)), the Krylov exponential with MINUS the exponent runs on the bond matrix C under
+ *   Y[b, b'] = sum_w sum_a sum_a' La[b, w, a] C[a, a'] Rb[b', w, a']
+ * (t4a_gpu_tdvp_bond_apply; the environment that contains Q is built once per step), Q stays in the site and C' is absorbed into the
+ * neighbour.  No renormalisation.  *local_updates counts site and bond solves: w (2 n - 1) per sweep, w in {1, 2, 6} substeps.
+ * Deviations from the reference: (1) the gauge — the reference stores Q C' and factorises it again on the next centre move; the state is
+ * the same and the bond dimension is k in both.  (2) At the one jump of a REVERSED substep from an inner centre (from a leaf to the node
+ * next to the centre) the reference corrects the first edge of the path, which it has corrected one step earlier, and never the edge into
+ * the next node; that is not a projector splitting (a second-order sweep at n = 5 from centre 2 is 5e-2 away from exp(tau H) psi at full
+ * bonds).  Here a reversed substep moves the centre to the neighbour of the next node first and corrects the LAST edge of the path, the
+ * mirror image of the post-order substep: exact at full bonds from every centre.  Paths of one edge are the reference's.
+ * Errors (INVALID_ARGUMENT on the host before an operand is looked at, in this order): nsite != 1 ("tdvp_one_site: one-site TDVP requires
+ * nsite=1, got nsite=..; nsite=2 is tdvp"), nsweeps, order and the exponent as t4a_gpu_tdvp, max_bond_dim == 0 when set, "invalid TDVP
+ * option max_bond_dim: one-site TDVP has fixed ranks; use nsite=2 for truncation", the same for svd_policy, the Krylov options; then the
+ * shapes: lengths differ, a single site (a message of its own), operator sites that are not square or do not match, center >= n, a
+ * one-site or bond-centre step with a work buffer above INT_MAX elements (the message names the site or the bond). */
+typedef struct {
+    size_t one_site_steps;
+    size_t bond_corrections;
+    size_t qr_steps;        /* full-rank thin QR steps: centre moves and the factorisations of the bond corrections */
+    size_t krylov_steps;
+    size_t apply_calls;
+    size_t max_time_splits;
+    size_t fused_applies;   /* bond-centre applies by the fused launch */
+    size_t gemm_applies;    /* and by the two GEMMs */
+} t4a_gpu_tdvp_one_site_stats;
+/* t4a_gpu_tdvp_options_default with nsite = 1 */
+t4a_gpu_status t4a_gpu_tdvp_one_site_options_default(t4a_gpu_tdvp_options* out);
+t4a_gpu_status t4a_gpu_tdvp_one_site_check_shapes(const size_t* op_dims4, size_t n_op, const size_t* state_dims3, size_t n_state, size_t center,
+                                                  size_t max_iter);
+t4a_gpu_status t4a_gpu_tdvp_one_site_plan(size_t n, size_t center, size_t order, double tau, size_t capacity, int32_t* kinds, size_t* nodes,
+                                          size_t* new_centers, double* exponents, size_t* n_steps);
+t4a_gpu_status t4a_gpu_tdvp_one_site(const t4a_gpu_mpo* op, const t4a_gpu_tt* init, size_t center, const t4a_gpu_tdvp_options* options,
+                                     t4a_gpu_tt** state, size_t* sweeps_completed, size_t* local_updates, double* max_error_estimate,
+                                     size_t* max_krylov_iterations, t4a_gpu_tdvp_one_site_stats* stats /* may be NULL */);
+/* The bond-centre apply on caller-supplied host arrays (column-major): L[ka, W, ka], R[kb, W, kb] (bra bond fastest), C and out ka x kb.
+ * route 0: the fused launch (one kernel; a workgroup holds T = La C for 16 rows in the LDS, so W kb <= 512, else INVALID_ARGUMENT),
+ * 1: two GEMMs (T = La_view C, Y = T_view Rb_view^T), 2: the rule of the driver.  *route_taken (may be NULL) receives 0 or 1.  The bits of
+ * a result depend on the operands, the shape and the route alone.
+ * _route: the rule, a function of the shape alone (host only).  _fused_admits: the envelope (host only).  _set_bond_apply_route forces the
+ * route of every bond-centre apply of the drivers (0: fused where admitted, 1: GEMM, anything else: the rule).
+ * _time (tools/probe_tdvp_one_site.py): device milliseconds, events around `reps` launches behind a warm-up launch, of the fused launch
+ * ms[0] (NaN outside its envelope) and the two GEMMs ms[1]. */
+t4a_gpu_status t4a_gpu_tdvp_bond_apply(const double* L, const double* R, const double* C, size_t ka, size_t kb, size_t W, int32_t route, double* out,
+                                       int32_t* route_taken);
+t4a_gpu_status t4a_gpu_tdvp_bond_apply_route(size_t ka, size_t kb, size_t W, int32_t* route);
+t4a_gpu_status t4a_gpu_tdvp_bond_apply_fused_admits(size_t ka, size_t kb, size_t W, int32_t* admits);
+t4a_gpu_status t4a_gpu_tdvp_set_bond_apply_route(int32_t route);
+t4a_gpu_status t4a_gpu_tdvp_bond_apply_time(size_t ka, size_t kb, size_t W, size_t reps, double* ms /* [2] */);
+
 /* ---- global subspace expansion (GSE) and GSE-TDVP: tensor4all-treetn's global_subspace_expand, .._with_references and gse_tdvp
  * (crates/tensor4all-treetn/src/gse.rs) for a chain, f64, one site index per node, V_in = V_out.  The expansion widens every bond of
  * `init` by the directions of the references that it does not span yet and does not change the state.  The target and the references
@@ -1534,7 +1596,7 @@ t4a_gpu_status t4a_gpu_krylov_expm_dense(const double* H, size_t n, const double
  * non-negative", "invalid GSE option hermitian_tol: must be finite and non-negative", "invalid GSE option reference_max_bond_dim: must
  * be greater than zero when set", "GSE center <c> is not a state node", "GSE requires target, references, and operator support to have
  * the same tree topology" (lengths differ), "invalid GSE mapping at node <i>: reference site dimension does not match target";
- * t4a_gpu_gse_tdvp adds the refusals of t4a_gpu_tdvp unchanged. */
+ * t4a_gpu_gse_tdvp adds the refusals of t4a_gpu_tdvp unchanged (nsite = 1 included: that is t4a_gpu_gse_tdvp_one_site). */
 typedef struct {
     size_t krylov_dim;                      /* 0 */
     int32_t has_reference_max_bond_dim;     /* 0: max(link_dims(init)) + 1 */
@@ -1563,6 +1625,11 @@ t4a_gpu_status t4a_gpu_gse_expand(const t4a_gpu_mpo* op, const t4a_gpu_tt* init,
 t4a_gpu_status t4a_gpu_gse_tdvp(const t4a_gpu_mpo* op, const t4a_gpu_tt* init, size_t center, const t4a_gpu_gse_options* gse,
                                 const t4a_gpu_tdvp_options* tdvp, t4a_gpu_tt** state, size_t* sweeps_completed, size_t* local_updates,
                                 size_t* gse_expansions, double* max_error_estimate, size_t* max_krylov_iterations);
+/* gse_tdvp with t4a_gpu_tdvp_one_site (tdvp->nsite == 1) for the one-sweep evolution after each expansion: the expansion grows the bonds,
+ * the fixed-rank integrator evolves inside them.  Any centre.  The refusals of the expansion plus those of t4a_gpu_tdvp_one_site. */
+t4a_gpu_status t4a_gpu_gse_tdvp_one_site(const t4a_gpu_mpo* op, const t4a_gpu_tt* init, size_t center, const t4a_gpu_gse_options* gse,
+                                         const t4a_gpu_tdvp_options* tdvp, t4a_gpu_tt** state, size_t* sweeps_completed, size_t* local_updates,
+                                         size_t* gse_expansions, double* max_error_estimate, size_t* max_krylov_iterations);
 /* Test hooks: the two launches of an edge on raw column-major operands.  orient 0: a matrix over (bond row a, q index j) is na x q,
  * X[a + na j] (the child's first leg is the bond to its parent); orient 1: X[j + q a] (its last leg is).  route 0: the fused launch,
  * 1: the same products composed from the GEMM.

@@ -709,6 +709,23 @@ TdvpOptions convert_tdvp_options(const t4a_gpu_tdvp_options* p)
     return o;
 }
 
+TdvpOptions convert_tdvp_one_site_options(const t4a_gpu_tdvp_options* p)
+{
+    TdvpOptions o;
+    o.nsite = p->nsite;
+    o.nsweeps = p->nsweeps;
+    o.order = p->order;
+    o.exponent_step_re = p->exponent_step_re;
+    o.exponent_step_im = p->exponent_step_im;
+    o.has_max_bond_dim = p->has_max_bond_dim != 0;
+    o.max_bond_dim = p->max_bond_dim;
+    o.has_svd_policy = p->has_svd_policy != 0;
+    if (o.has_svd_policy) o.svd_policy = from_c(p->svd_policy);
+    o.krylov = convert_krylov_expm_options(p->krylov);
+    o.validate_one_site();
+    return o;
+}
+
 GseOptions convert_gse_options(const t4a_gpu_gse_options* p)
 {
     GseOptions o;
@@ -4639,6 +4656,17 @@ t4a_gpu_status t4a_gpu_projected_operator_environment(t4a_gpu_projected_operator
     });
 }
 
+t4a_gpu_status t4a_gpu_projected_operator_bond_center_env(t4a_gpu_projected_operator* h, size_t site, int32_t toward_right, size_t* dims3, double* out)
+{
+    return guarded([&] {
+        if (toward_right != 0 && toward_right != 1) throw Error(T4A_GPU_INVALID_ARGUMENT, "projected operator: toward_right must be 0 or 1");
+        T4A_REQUIRE_PTR(h);
+        T4A_REQUIRE_PTR(dims3);
+        const std::vector<double> e = h->impl->bond_center_environment(site, toward_right != 0, dims3);
+        if (out) std::memcpy(out, e.data(), e.size() * sizeof(double));
+    });
+}
+
 t4a_gpu_status t4a_gpu_projected_operator_invalidate(t4a_gpu_projected_operator* h, size_t site)
 {
     return guarded([&] {
@@ -4968,6 +4996,127 @@ t4a_gpu_status t4a_gpu_tdvp(const t4a_gpu_mpo* op, const t4a_gpu_tt* init, size_
     });
 }
 
+// ---- one-site TDVP: fixed ranks, a bond-centre correction between two site steps (tdvp.hpp) ----
+t4a_gpu_status t4a_gpu_tdvp_one_site_options_default(t4a_gpu_tdvp_options* out)
+{
+    const t4a_gpu_status st = t4a_gpu_tdvp_options_default(out);
+    if (st == T4A_GPU_SUCCESS) out->nsite = 1;
+    return st;
+}
+
+t4a_gpu_status t4a_gpu_tdvp_one_site_check_shapes(const size_t* op_dims4, size_t n_op, const size_t* state_dims3, size_t n_state, size_t center,
+                                                  size_t max_iter)
+{
+    return guarded([&] {
+        if (n_op) T4A_REQUIRE_PTR(op_dims4);
+        if (n_state) T4A_REQUIRE_PTR(state_dims3);
+        KrylovExpmOptions ko;
+        ko.max_iter = max_iter;
+        ko.validate();
+        tdvp_one_site_validate_shapes(dims4_list(op_dims4, n_op), dims3_list(state_dims3, n_state), center, max_iter);
+    });
+}
+
+t4a_gpu_status t4a_gpu_tdvp_one_site_plan(size_t n, size_t center, size_t order, double tau, size_t capacity, int32_t* kinds, size_t* nodes,
+                                          size_t* new_centers, double* exponents, size_t* n_steps)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(n_steps);
+        const std::vector<TdvpStep> plan = tdvp_one_site_plan(n, center, order, tau);
+        *n_steps = plan.size();
+        if (!kinds && !nodes && !new_centers && !exponents) return; // the count only
+        if (capacity < plan.size()) throw Error(T4A_GPU_BUFFER_TOO_SMALL, "tdvp_one_site_plan: the plan has " + std::to_string(plan.size()) + " steps");
+        T4A_REQUIRE_PTR(kinds);
+        T4A_REQUIRE_PTR(nodes);
+        T4A_REQUIRE_PTR(new_centers);
+        T4A_REQUIRE_PTR(exponents);
+        for (size_t k = 0; k < plan.size(); ++k) {
+            kinds[k] = (int32_t)plan[k].kind;
+            nodes[2 * k] = plan[k].nodes[0];
+            nodes[2 * k + 1] = plan[k].nodes[1];
+            new_centers[k] = plan[k].new_center;
+            exponents[k] = plan[k].exponent;
+        }
+    });
+}
+
+t4a_gpu_status t4a_gpu_tdvp_one_site(const t4a_gpu_mpo* op, const t4a_gpu_tt* init, size_t center, const t4a_gpu_tdvp_options* options, t4a_gpu_tt** state,
+                                     size_t* sweeps_completed, size_t* local_updates, double* max_error_estimate, size_t* max_krylov_iterations,
+                                     t4a_gpu_tdvp_one_site_stats* stats)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(state);
+        *state = nullptr;
+        T4A_REQUIRE_PTR(options);
+        const TdvpOptions o = convert_tdvp_one_site_options(options); // the options are checked on the host before an operand is looked at
+        T4A_REQUIRE_PTR(op);
+        T4A_REQUIRE_PTR(init);
+        T4A_REQUIRE_PTR(sweeps_completed);
+        T4A_REQUIRE_PTR(local_updates);
+        T4A_REQUIRE_PTR(max_error_estimate);
+        T4A_REQUIRE_PTR(max_krylov_iterations);
+        TdvpOneSiteResult r = tdvp_one_site(*op->impl, const_cast<t4a_gpu_tt*>(init)->impl, center, o);
+        *state = new t4a_gpu_tt(r.state->cores, r.state->eng.stream());
+        *sweeps_completed = r.sweeps_completed;
+        *local_updates = r.local_updates;
+        *max_error_estimate = r.max_error_estimate;
+        *max_krylov_iterations = r.max_krylov_iterations;
+        if (stats)
+            *stats = t4a_gpu_tdvp_one_site_stats{r.stats.one_site_steps, r.stats.bond_corrections, r.stats.qr_steps,      r.stats.krylov_steps,
+                                                 r.stats.apply_calls,    r.stats.max_time_splits,  r.stats.fused_applies, r.stats.gemm_applies};
+    });
+}
+
+t4a_gpu_status t4a_gpu_tdvp_bond_apply_route(size_t ka, size_t kb, size_t W, int32_t* route)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(route);
+        if (ka == 0 || kb == 0 || W == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "tdvp_bond_apply_route: ka, kb and W must be positive");
+        *route = (int32_t)tdvp_bond_apply_route(ka, kb, W);
+    });
+}
+
+t4a_gpu_status t4a_gpu_tdvp_bond_apply_fused_admits(size_t ka, size_t kb, size_t W, int32_t* admits)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(admits);
+        *admits = tdvp_bond_apply_fused_admits(ka, kb, W) ? 1 : 0;
+    });
+}
+
+t4a_gpu_status t4a_gpu_tdvp_set_bond_apply_route(int32_t route)
+{
+    return guarded([&] { tdvp_set_bond_apply_route(route); });
+}
+
+t4a_gpu_status t4a_gpu_tdvp_bond_apply(const double* L, const double* R, const double* C, size_t ka, size_t kb, size_t W, int32_t route, double* out,
+                                       int32_t* route_taken)
+{
+    return guarded([&] {
+        if (route < 0 || route > 2) throw Error(T4A_GPU_INVALID_ARGUMENT, "tdvp_bond_apply: route is 0 (fused), 1 (GEMM) or 2 (the rule)");
+        if (ka == 0 || kb == 0 || W == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "tdvp_bond_apply: ka, kb and W must be positive");
+        check_bond_center_dims("tdvp_bond_apply", 0, ka, kb, W, 0);
+        if (route == 0 && !tdvp_bond_apply_fused_admits(ka, kb, W))
+            throw Error(T4A_GPU_INVALID_ARGUMENT, "tdvp_bond_apply: the fused launch holds 16 W k_b doubles in the LDS: W k_b must be at most " +
+                                                      std::to_string(TDVP_BOND_FUSED_MAX_PANEL));
+        T4A_REQUIRE_PTR(L);
+        T4A_REQUIRE_PTR(R);
+        T4A_REQUIRE_PTR(C);
+        T4A_REQUIRE_PTR(out);
+        require_device();
+        const BondApplyRoute taken = tdvp_bond_apply_host(L, R, C, ka, kb, W, (BondApplyRoute)route, out);
+        if (route_taken) *route_taken = (int32_t)taken;
+    });
+}
+
+t4a_gpu_status t4a_gpu_tdvp_bond_apply_time(size_t ka, size_t kb, size_t W, size_t reps, double* ms)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(ms);
+        tdvp_bond_apply_time(ka, kb, W, reps, ms); // checks its arguments, then the device
+    });
+}
+
 t4a_gpu_status t4a_gpu_krylov_expm_dense(const double* H, size_t n, const double* v0, double tau, const t4a_gpu_krylov_expm_options* options, double* out,
                                          size_t* iterations, double* error_estimate, int32_t* converged, size_t* time_splits)
 {
@@ -5117,6 +5266,35 @@ t4a_gpu_status t4a_gpu_gse_tdvp(const t4a_gpu_mpo* op, const t4a_gpu_tt* init, s
         T4A_REQUIRE_PTR(max_error_estimate);
         T4A_REQUIRE_PTR(max_krylov_iterations);
         GseTdvpResult r = gse_tdvp(*op->impl, const_cast<t4a_gpu_tt*>(init)->impl, center, o);
+        *state = new t4a_gpu_tt(r.state->cores, r.state->eng.stream());
+        *sweeps_completed = r.sweeps_completed;
+        *local_updates = r.local_updates;
+        *gse_expansions = r.gse_expansions;
+        *max_error_estimate = r.max_error_estimate;
+        *max_krylov_iterations = r.max_krylov_iterations;
+    });
+}
+
+t4a_gpu_status t4a_gpu_gse_tdvp_one_site(const t4a_gpu_mpo* op, const t4a_gpu_tt* init, size_t center, const t4a_gpu_gse_options* gse,
+                                         const t4a_gpu_tdvp_options* tdvp_options, t4a_gpu_tt** state, size_t* sweeps_completed, size_t* local_updates,
+                                         size_t* gse_expansions, double* max_error_estimate, size_t* max_krylov_iterations)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(state);
+        *state = nullptr;
+        T4A_REQUIRE_PTR(gse);
+        T4A_REQUIRE_PTR(tdvp_options);
+        GseTdvpOptions o;
+        o.gse = convert_gse_options(gse); // the options are checked on the host before an operand is looked at
+        o.tdvp = convert_tdvp_one_site_options(tdvp_options);
+        T4A_REQUIRE_PTR(op);
+        T4A_REQUIRE_PTR(init);
+        T4A_REQUIRE_PTR(sweeps_completed);
+        T4A_REQUIRE_PTR(local_updates);
+        T4A_REQUIRE_PTR(gse_expansions);
+        T4A_REQUIRE_PTR(max_error_estimate);
+        T4A_REQUIRE_PTR(max_krylov_iterations);
+        GseTdvpResult r = gse_tdvp_one_site(*op->impl, const_cast<t4a_gpu_tt*>(init)->impl, center, o);
         *state = new t4a_gpu_tt(r.state->cores, r.state->eng.stream());
         *sweeps_completed = r.sweeps_completed;
         *local_updates = r.local_updates;

@@ -37,7 +37,8 @@
 //   non-negative", "invalid GSE option reference_max_bond_dim: must be greater than zero when set", "GSE center <c> is not a state node",
 //   "GSE requires target, references, and operator support to have the same tree topology" (lengths differ), "invalid GSE mapping at
 //   node <i>: reference site dimension does not match target", "gse: more than 8 references are not implemented" (NOT_IMPLEMENTED);
-//   gse_tdvp adds tdvp's own refusals unchanged (a real exponent, center in {0, n - 1}, nsite = 2).
+//   gse_tdvp adds tdvp's own refusals unchanged (a real exponent, center in {0, n - 1}, nsite = 2); gse_tdvp_one_site adds those of
+//   tdvp_one_site (nsite = 1, no max_bond_dim, no svd_policy; any centre).
 #pragma once
 
 #include "tdvp.hpp"
@@ -143,6 +144,9 @@ std::vector<std::unique_ptr<TensorTrain>> gse_krylov_references(Mpo& op, TensorT
 GseResult global_subspace_expand_with_references(TensorTrain& init, const std::vector<TensorTrain*>& references, size_t center, const GseOptions& o);
 GseResult global_subspace_expand(Mpo& op, TensorTrain& init, size_t center, const GseOptions& o);
 GseTdvpResult gse_tdvp(Mpo& op, TensorTrain& init, size_t center, const GseTdvpOptions& o);
+// The loop of gse_tdvp with tdvp_one_site (o.tdvp.nsite == 1) for the one-sweep evolution after each expansion: the expansion grows the
+// bonds globally, the fixed-rank integrator evolves inside them.  Any centre, since both parts allow it.
+GseTdvpResult gse_tdvp_one_site(Mpo& op, TensorTrain& init, size_t center, const GseTdvpOptions& o);
 
 // Test hooks on host arrays (column-major, layouts of gse_project_launch / gse_absorb_launch); route 0: the fused launch, 1: the GEMM
 // composition.  project: refs concatenated, stack (sum rho) x q (orient 1: q x sum rho).  absorb: children, parents and results concatenated.

@@ -67,6 +67,13 @@ void check_site_step_dims(const char* who, size_t c, size_t chi_l, size_t d, siz
         throw Error(T4A_GPU_INVALID_ARGUMENT, std::string(who) + ": a work buffer of the one-site step at site " + std::to_string(c) + " holds more than INT_MAX elements");
 }
 
+void check_bond_center_dims(const char* who, size_t i, size_t ka, size_t kb, size_t W, size_t basis_dim)
+{
+    if (above_int_max({ka, W, ka}) || above_int_max({kb, W, kb}) || above_int_max({ka, W, kb}) || above_int_max({basis_dim + 1, ka, kb}))
+        throw Error(T4A_GPU_INVALID_ARGUMENT, std::string(who) + ": a work buffer of the bond-centre step at the bond (" + std::to_string(i) + ", " +
+                                                  std::to_string(i + 1) + ") holds more than INT_MAX elements");
+}
+
 void LinsolveOptions::validate() const
 {
     if (gmres_restart_dim == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "LinsolveOptions::gmres_restart_dim must be greater than zero");
@@ -516,6 +523,58 @@ bool ProjectedOperator::prepare_one_site(size_t c)
     T4A_HIP(hipGetLastError());
     prepared1_ = c;
     return reuse;
+}
+
+void ProjectedOperator::prepare_bond_center(size_t c, bool toward_right)
+{
+    if (c >= x.size() || (toward_right ? c + 1 >= x.size() : c == 0))
+        throw Error(T4A_GPU_INVALID_ARGUMENT, "projected operator: site " + std::to_string(c) + " has no neighbour on that side");
+    Engine& e = engine();
+    const DevCore& X = x[c];
+    const DevCore& A = op_->tt.cores[c];
+    if (toward_right) {
+        prepare_one_site(c); // L_c, R_{c+1} and HL = L_c A_c (hl_ reused when it still holds it)
+        update_left_from_prepared(c); // L_{c+1}[:, w, :] = Q^T (HL_w Q)
+        bc_la_ = envL_[c + 1].get();
+        bc_rb_ = right_env(c + 1);
+        bc_ka_ = X.r;
+        bc_kb_ = x[c + 1].l;
+        bc_w_ = A.r;
+        bc_bond_ = c;
+    } else {
+        bc_la_ = left_env(c);
+        const double* R = right_env(c + 1);
+        if (above_int_max({A.l, X.s * X.r, X.s * X.r}) || above_int_max({A.l, X.s * X.r, X.l}))
+            throw Error(T4A_GPU_INVALID_ARGUMENT, "projected operator: the right environment of site " + std::to_string(c) + " needs more than INT_MAX elements");
+        grow(e, hr_, A.l * X.s * X.r * X.s * X.r);
+        prepared_ = (size_t)-1;
+        linsolve_hr_launch(A.buf.get(), R, hr_.get(), (int)X.r, (int)A.l, (int)X.s, (int)A.r, e.stream());
+        update_right_from_prepared(c - 1); // R_c[:, w, :] = (Q HR_w^T) Q^T
+        bc_rb_ = envR_[c].get();
+        bc_ka_ = x[c - 1].r;
+        bc_kb_ = X.l;
+        bc_w_ = A.l;
+        bc_bond_ = c - 1;
+    }
+    check_bond_center(0, "projected operator");
+    grow(e, t_, bc_ka_ * bc_w_ * bc_kb_);
+    T4A_HIP(hipGetLastError());
+    prepared1_ = (size_t)-1; // t_ may have been regrown
+}
+
+void ProjectedOperator::check_bond_center(size_t basis_dim, const char* who) const
+{
+    check_bond_center_dims(who, bc_bond_, bc_ka_, bc_kb_, bc_w_, basis_dim);
+}
+
+std::vector<double> ProjectedOperator::bond_center_environment(size_t c, bool toward_right, size_t dims[3])
+{
+    prepare_bond_center(c, toward_right);
+    const size_t k = toward_right ? bc_ka_ : bc_kb_;
+    dims[0] = k;
+    dims[1] = bc_w_;
+    dims[2] = k;
+    return to_host(engine(), toward_right ? bc_la_ : bc_rb_, k * bc_w_ * k);
 }
 
 void ProjectedOperator::apply_one_site_prepared(const double* d_v, double* d_out)

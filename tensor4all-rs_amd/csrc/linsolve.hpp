@@ -107,6 +107,11 @@ void check_bond_step_dims(const char* who, size_t i, size_t chi_l, size_t d1, si
 // INVALID_ARGUMENT "<who>: a work buffer of the one-site step at site c ...".
 void check_site_step_dims(const char* who, size_t c, size_t chi_l, size_t d, size_t chi_r, size_t W, size_t basis_dim);
 
+// The same bound for the bond-centre step of one-site TDVP at the bond (i, i + 1): the environments La (ka W ka) and Rb (kb W kb), T
+// (ka W kb) and a Krylov basis of basis_dim + 1 columns of ka kb elements.
+// INVALID_ARGUMENT "<who>: a work buffer of the bond-centre step at the bond (i, i+1) ...".
+void check_bond_center_dims(const char* who, size_t i, size_t ka, size_t kb, size_t W, size_t basis_dim);
+
 // ---- what the sweeps of square_linsolve, dmrg, tdvp and gse share on the host
 std::vector<std::array<size_t, 3>> dims3_of(const std::vector<DevCore>& cores);
 void require_tol(double v, const std::string& what); // INVALID_ARGUMENT `what` unless v is finite and not negative
@@ -167,6 +172,23 @@ public:
     // ld chi_r — the column index is w' + W a' in both views.  2 W M chi_r (M + chi_r) flops.
     void apply_one_site_prepared(const double* d_v, double* d_out);
     void check_site_step(size_t c, size_t basis_dim, const char* who) const;  // check_site_step_dims at the present bonds
+    // The bond-centre (zero-site) region of one-site TDVP next to site c, whose tensor x[c] holds the isometry Q of the full-rank thin QR
+    // x_c = Q C (toward_right) or x_c = C Q: the operator on the bond matrix C (ka x kb) is
+    //   Y[b, b'] = sum_w sum_a sum_a' La[b, w, a] C[a, a'] Rb[b', w, a'].
+    // toward_right: Rb = R_{c+1} from the cache and La[:, w, :] = Q^T (HL_w Q) from HL = L_c A_c (prepare_one_site(c), reused when hl_
+    // still holds it) — the arithmetic of update_left_from_prepared, whose result is also the cache entry L_{c+1}; ka = x[c].r, kb the bond
+    // to the right.  Else the mirror image: La = L_c, HR = A_c R_{c+1} by linsolve_hr_launch and Rb[:, w, :] = (Q HR_w^T) Q^T as
+    // update_right_from_prepared forms it, the cache entry R_c; ka the bond to the left, kb = x[c].l.  Built once per step.
+    void prepare_bond_center(size_t c, bool toward_right);
+    // y = the operator above on the device matrix d_c, by the route of tdvp_bond_apply_route (or the forced one)
+    void apply_bond_center_prepared(const double* d_c, double* d_out);
+    std::array<size_t, 3> bond_center_dims() const { return {bc_ka_, bc_kb_, bc_w_}; }
+    // Test hook: prepare_bond_center(c, toward_right) with the present x[c] as Q -> the environment that contains it on the host,
+    // La[k, W, k] (toward_right) or Rb[k, W, k]; dims receives (k, W, k)
+    std::vector<double> bond_center_environment(size_t c, bool toward_right, size_t dims[3]);
+    void check_bond_center(size_t basis_dim, const char* who) const;  // check_bond_center_dims at the prepared bond
+    const double* bond_center_env(bool left) const { return left ? bc_la_ : bc_rb_; }
+    size_t fused_applies = 0, gemm_applies = 0;                       // launches of apply_bond_center_prepared by route
     // Probe: device ms of the three launches of the one-site apply at site c (linsolve_hl, T = HL V, Y = T R^T), events around `reps`
     // launches behind a warm-up launch
     void time_one_site(size_t c, size_t reps, double ms[3]);
@@ -197,6 +219,8 @@ private:
     size_t prepared1_ = (size_t)-1;  // the site of prepare_one_site
     size_t hl_site_ = (size_t)-1;    // hl_ holds L_c A_c of this site c
     const double* r1_ = nullptr;     // R_{c+1} of prepare_one_site
+    const double *bc_la_ = nullptr, *bc_rb_ = nullptr;  // the environments of prepare_bond_center
+    size_t bc_ka_ = 0, bc_kb_ = 0, bc_w_ = 0, bc_bond_ = 0;
 };
 
 // The apply on caller-supplied environments (host arrays), launched exactly as the sweeps launch it: L[chi_l, W_l, chi_l],

@@ -1,12 +1,14 @@
-// tdvp.hip — two-site TDVP on the device (see tdvp.hpp).  Shape bookkeeping, the region plan and the exponential of the small projected
+// tdvp.hip — two-site and one-site TDVP on the device (see tdvp.hpp).  Shape bookkeeping, the region plan and the exponential of the small projected
 // matrix of the Krylov solver (a cyclic Jacobi) are host work; every other floating-point operation runs in gfx950 kernels: the
 // projected applies of linsolve.hpp, the Arnoldi step of krylov.hpp (with the projections of kernels_tdvp.hip), the combination of
 // kernels_dmrg.hip, the QR and the SVD behind QrSweep and tensor_svd.
 #include "tdvp.hpp"
 
 #include <algorithm>
+#include <atomic>
 #include <climits>
 #include <cmath>
+#include <limits>
 #include <string>
 
 namespace t4a {
@@ -44,6 +46,24 @@ void TdvpOptions::validate() const
     if (has_svd_policy) validate_svd_policy(svd_policy, "TdvpOptions::svd_policy");
 }
 
+void TdvpOptions::validate_one_site() const
+{
+    if (nsite != 1)
+        throw Error(T4A_GPU_INVALID_ARGUMENT, "tdvp_one_site: one-site TDVP requires nsite=1, got nsite=" + std::to_string(nsite) + "; nsite=2 is tdvp");
+    if (nsweeps == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "invalid TDVP option nsweeps: must be greater than zero");
+    if (order != 1 && order != 2 && order != 4)
+        throw Error(T4A_GPU_INVALID_ARGUMENT, "TDVP applyexp order " + std::to_string(order) + " is not supported; supported orders are 1, 2, and 4");
+    if (!std::isfinite(exponent_step_re) || !std::isfinite(exponent_step_im))
+        throw Error(T4A_GPU_INVALID_ARGUMENT, "invalid TDVP option exponent_step: real and imaginary parts must be finite");
+    if (exponent_step_im != 0.0)
+        throw Error(T4A_GPU_INVALID_ARGUMENT,
+                    "tdvp_one_site: exponent_step must be real here: real-time evolution (a non-zero imaginary part) needs complex tensor trains, which this project does not have");
+    if (has_max_bond_dim && max_bond_dim == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "invalid TDVP option max_bond_dim: must be greater than zero when set");
+    if (has_max_bond_dim) throw Error(T4A_GPU_INVALID_ARGUMENT, "invalid TDVP option max_bond_dim: one-site TDVP has fixed ranks; use nsite=2 for truncation");
+    if (has_svd_policy) throw Error(T4A_GPU_INVALID_ARGUMENT, "invalid TDVP option svd_policy: one-site TDVP has fixed ranks; use nsite=2 for truncation");
+    krylov.validate();
+}
+
 namespace {
 void require_end_center(size_t n, size_t center)
 {
@@ -61,6 +81,16 @@ void tdvp_validate_shapes(const std::vector<std::array<size_t, 4>>& op, const st
     require_end_center(n, center);
     for (size_t i = 0; i + 1 < n; ++i) check_bond_step_dims("tdvp", i, state[i][0], state[i][1], state[i + 1][1], state[i + 1][2], op[i][3], max_iter);
     for (size_t c = 1; c + 1 < n; ++c) check_site_step_dims("tdvp", c, state[c][0], state[c][1], state[c][2], op[c][3], max_iter);
+}
+
+void tdvp_one_site_validate_shapes(const std::vector<std::array<size_t, 4>>& op, const std::vector<std::array<size_t, 3>>& state, size_t center, size_t max_iter)
+{
+    const size_t n = state.size();
+    validate_chain_operands("tdvp_one_site", op, nullptr, state, "a single site has no bond to correct and the shared chain checks need two sites: one-site TDVP requires at least two sites");
+    if (center >= n)
+        throw Error(T4A_GPU_INVALID_ARGUMENT, "tdvp_one_site: TDVP center " + std::to_string(center) + " is not a state node (" + std::to_string(n) + " sites)");
+    for (size_t c = 0; c < n; ++c) check_site_step_dims("tdvp_one_site", c, state[c][0], state[c][1], state[c][2], op[c][3], max_iter);
+    for (size_t i = 0; i + 1 < n; ++i) check_bond_center_dims("tdvp_one_site", i, state[i][2], state[i][2], op[i][3], max_iter);
 }
 
 // ------------------------------------------------------------------------------------------------ the plan
@@ -99,6 +129,27 @@ std::vector<TdvpStep> tdvp_plan(size_t n, size_t center, size_t order, double ta
                 s.new_center = s.nodes[1];
             }
         }
+        steps.insert(steps.end(), part.begin(), part.end());
+    }
+    return steps;
+}
+
+std::vector<TdvpStep> tdvp_one_site_plan(size_t n, size_t center, size_t order, double tau)
+{
+    const std::vector<double> weights = tdvp_sub_steps(order);
+    if (!std::isfinite(tau)) throw Error(T4A_GPU_INVALID_ARGUMENT, "invalid TDVP option exponent_step: real and imaginary parts must be finite");
+    if (n == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "tdvp_one_site: the plan of an empty chain");
+    if (center >= n)
+        throw Error(T4A_GPU_INVALID_ARGUMENT, "tdvp_one_site: TDVP center " + std::to_string(center) + " is not a state node (" + std::to_string(n) + " sites)");
+    std::vector<TdvpStep> base; // post order: the left arm leaf first, the right arm leaf first, the centre
+    for (size_t j = 0; j < center; ++j) base.push_back({TdvpStepKind::OneSite, {j, j}, j, tau});
+    for (size_t j = n - 1; j > center; --j) base.push_back({TdvpStepKind::OneSite, {j, j}, j, tau});
+    base.push_back({TdvpStepKind::OneSite, {center, center}, center, tau});
+    std::vector<TdvpStep> steps;
+    for (size_t k = 0; k < weights.size(); ++k) {
+        std::vector<TdvpStep> part = base;
+        for (TdvpStep& s : part) s.exponent = s.exponent * weights[k];
+        if ((k + 1) % 2 == 0) std::reverse(part.begin(), part.end());
         steps.insert(steps.end(), part.begin(), part.end());
     }
     return steps;
@@ -268,7 +319,232 @@ TdvpResult tdvp(Mpo& op, TensorTrain& init, size_t center, const TdvpOptions& o)
     return out;
 }
 
-// ------------------------------------------------------------------------------------------------ test hook
+// ------------------------------------------------------------------------------------------------ the bond-centre apply
+// Measured on an MI355X at k_a = k_b = k (tools/probe_tdvp_one_site.py): the fused launch takes 0.36 - 0.78 of the
+// two GEMMs at k = 8, 16, 32 with W = 4 and at k = 8, 16 with W = 16, and 1.15 - 3.1 times as long at k = 64, 128 with W = 4 and k = 32 with
+// W = 16.  A workgroup owns 16 rows whatever the shape and its wavefronts walk W k_b (k_a + k_b) / 4 chunks of the summed indices between
+// them, while the GEMM tiles both output dimensions: W k_b (k_a + k_b) is 8192 at the largest measured wins and 32768 at the smallest
+// measured losses.  The spread of a measurement (min - max of 7) is below 8 % of its median, every win and loss above 14 %.  Shapes up to
+// the measured wins take the fused launch; everything above, the unmeasured shapes between the two included, takes the GEMMs.
+namespace {
+std::atomic<int> g_bond_route{-1};
+}
+void tdvp_set_bond_apply_route(int route) { g_bond_route.store(route < 0 || route > 1 ? -1 : route); }
+
+BondApplyRoute tdvp_bond_apply_route(size_t ka, size_t kb, size_t W)
+{
+    return tdvp_bond_apply_fused_admits(ka, kb, W) && W * kb * (ka + kb) <= TDVP_BOND_FUSED_AUTO_WORK ? BondApplyRoute::Fused : BondApplyRoute::Gemm;
+}
+
+void tdvp_bond_apply_gemm(const double* La, const double* C, const double* Rb, double* T, double* Y, int ka, int kb, int W, hipStream_t stream)
+{
+    gemm_launch(gemm_desc(ka * W, kb, ka, La, ka * W, C, ka, T, ka * W), stream);
+    GemmDesc g = gemm_desc(ka, kb, W * kb, T, ka, Rb, kb, Y, ka);
+    g.transB = 1;
+    gemm_launch(g, stream);
+}
+
+namespace {
+BondApplyRoute resolve_bond_route(BondApplyRoute route, size_t ka, size_t kb, size_t W)
+{
+    return route == BondApplyRoute::Auto ? tdvp_bond_apply_route(ka, kb, W) : route;
+}
+} // namespace
+
+void ProjectedOperator::apply_bond_center_prepared(const double* d_c, double* d_out)
+{
+    hipStream_t st = engine().stream();
+    const int forced = g_bond_route.load();
+    BondApplyRoute route = tdvp_bond_apply_route(bc_ka_, bc_kb_, bc_w_);
+    if (forced == 1) route = BondApplyRoute::Gemm;
+    if (forced == 0 && tdvp_bond_apply_fused_admits(bc_ka_, bc_kb_, bc_w_)) route = BondApplyRoute::Fused;
+    if (route == BondApplyRoute::Fused) {
+        tdvp_bond_apply_launch(bc_la_, d_c, bc_rb_, d_out, (int)bc_ka_, (int)bc_kb_, (int)bc_w_, st);
+        ++fused_applies;
+    } else {
+        tdvp_bond_apply_gemm(bc_la_, d_c, bc_rb_, t_.get(), d_out, (int)bc_ka_, (int)bc_kb_, (int)bc_w_, st);
+        ++gemm_applies;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ the one-site sweeps
+TdvpOneSiteResult tdvp_one_site(Mpo& op, TensorTrain& init, size_t center, const TdvpOptions& o)
+{
+    o.validate_one_site();
+    tdvp_one_site_validate_shapes(op.dims4(), dims3_of(init.cores), center, o.krylov.max_iter);
+    const size_t n = init.cores.size();
+    const std::vector<TdvpStep> plan = tdvp_one_site_plan(n, center, o.order, o.exponent_step_re);
+    TdvpOneSiteResult out;
+    ProjectedOperator po(op, init, nullptr);
+    Engine& e = po.engine();
+    hipStream_t st = e.stream();
+    QrSweep sw(e);
+    sw.canonicalize(po.x, center);
+    size_t cur = center;
+    KrylovExpm kx(e);
+    DevBuf<double> cm, m1, qt, rr; // the bond matrix and the scratch of its factorisation
+
+    auto book = [&](const KrylovExpmResult& r) {
+        out.max_error_estimate = std::max(out.max_error_estimate, r.error_estimate);
+        out.max_krylov_iterations = std::max(out.max_krylov_iterations, r.iterations);
+        out.stats.krylov_steps += r.iterations;
+        out.stats.apply_calls += r.apply_calls;
+        out.stats.max_time_splits = std::max(out.stats.max_time_splits, r.time_splits);
+        ++out.local_updates;
+    };
+    // move_center_to_region_full_rank: thin QR steps, every cache that contains a changed site goes stale
+    auto move_center = [&](size_t target) {
+        while (cur < target) {
+            sw.left_step(po.x, cur);
+            po.invalidate(cur);
+            po.invalidate(cur + 1);
+            ++cur;
+            ++out.stats.qr_steps;
+        }
+        while (cur > target) {
+            sw.right_step(po.x, cur);
+            po.invalidate(cur);
+            po.invalidate(cur - 1);
+            --cur;
+            ++out.stats.qr_steps;
+        }
+    };
+    // apply_one_site_bond_correction (mod.rs:702-860) at the centre c towards its neighbour on that side -> the new centre
+    auto bond_correction = [&](size_t c, bool right, double exponent) {
+        DevCore& X = po.x[c];
+        size_t ka, kb; // the shape of C
+        DevCore q;
+        if (right) { // x_c as (l s) x r is Q C
+            const int rows = (int)(X.l * X.s), R = (int)X.r, k = std::min(rows, R);
+            grow(e, cm, (size_t)k * R);
+            q = DevCore::make(X.l, X.s, (size_t)k);
+            e.qr(X.buf.get(), rows, R, q.buf.get(), cm.get());
+            ka = (size_t)k;
+            kb = (size_t)R;
+        } else { // x_c as l x (s r) is C Q: the QR of its transpose
+            const int L = (int)X.l, rest = (int)(X.s * X.r), k = std::min(L, rest);
+            grow(e, m1, (size_t)rest * L);
+            grow(e, qt, (size_t)rest * k);
+            grow(e, rr, (size_t)k * L);
+            grow(e, cm, (size_t)L * k);
+            transpose_launch(X.buf.get(), L, rest, L, m1.get(), rest, st);
+            e.qr(m1.get(), rest, L, qt.get(), rr.get());
+            q = DevCore::make((size_t)k, X.s, X.r);
+            transpose_launch(qt.get(), rest, k, rest, q.buf.get(), k, st);
+            transpose_launch(rr.get(), k, L, k, cm.get(), L, st); // C = R^T, l x k
+            ka = (size_t)L;
+            kb = (size_t)k;
+        }
+        T4A_HIP(hipGetLastError());
+        e.sync(); // the old site is released below
+        po.x[c] = std::move(q);
+        po.invalidate(c);
+        ++out.stats.qr_steps;
+        po.prepare_bond_center(c, right);
+        po.check_bond_center(o.krylov.max_iter, "tdvp_one_site");
+        book(kx.solve([&](const double* v, double* y) { po.apply_bond_center_prepared(v, y); }, ka * kb, cm.get(), exponent, o.krylov));
+        ++out.stats.bond_corrections;
+        // the neighbour absorbs C'; the environment built with Q stays the valid cache entry
+        const size_t nb = right ? c + 1 : c - 1;
+        const DevCore& Nb = po.x[nb];
+        DevCore nn;
+        if (right) {
+            nn = DevCore::make(ka, Nb.s, Nb.r);
+            const int rest = (int)(Nb.s * Nb.r);
+            gemm_launch(gemm_desc((int)ka, rest, (int)kb, cm.get(), (int)ka, Nb.buf.get(), (int)kb, nn.buf.get(), (int)ka), st);
+        } else {
+            nn = DevCore::make(Nb.l, Nb.s, kb);
+            const int pm = (int)(Nb.l * Nb.s);
+            gemm_launch(gemm_desc(pm, (int)kb, (int)ka, Nb.buf.get(), pm, cm.get(), (int)ka, nn.buf.get(), pm), st);
+        }
+        T4A_HIP(hipGetLastError());
+        e.sync();
+        po.x[nb] = std::move(nn);
+        po.invalidate(nb); // keeps L_{c+1} (right) or R_c (left): they do not contain the neighbour
+        return nb;
+    };
+
+    for (size_t sweep = 0; sweep < o.nsweeps; ++sweep) {
+        for (size_t k = 0; k < plan.size(); ++k) {
+            const TdvpStep& s = plan[k];
+            size_t c = s.nodes[0];
+            move_center(c);
+            po.check_site_step(c, o.krylov.max_iter, "tdvp_one_site");
+            po.prepare_one_site(c);
+            book(kx.solve([&](const double* v, double* y) { po.apply_one_site_prepared(v, y); }, po.x[c].size(), po.x[c].buf.get(), s.exponent, o.krylov));
+            po.invalidate(c);
+            ++out.stats.one_site_steps;
+            if (k + 1 < plan.size() && plan[k + 1].nodes[0] != c) {
+                const size_t t = plan[k + 1].nodes[0];
+                const bool right = t > c;
+                if ((k / n) % 2 == 1) { // a reversed substep corrects the last edge of the path (tdvp.hpp)
+                    move_center(right ? t - 1 : t + 1);
+                    c = cur;
+                }
+                cur = bond_correction(c, right, -s.exponent);
+            }
+        }
+        out.sweeps_completed = sweep + 1;
+    }
+    e.sync();
+    out.stats.fused_applies = po.fused_applies;
+    out.stats.gemm_applies = po.gemm_applies;
+    out.state = std::make_unique<TensorTrain>(po.x, st);
+    return out;
+}
+
+// ------------------------------------------------------------------------------------------------ test hooks
+BondApplyRoute tdvp_bond_apply_host(const double* L, const double* R, const double* C, size_t ka, size_t kb, size_t W, BondApplyRoute route, double* out)
+{
+    route = resolve_bond_route(route, ka, kb, W);
+    if (route == BondApplyRoute::Fused && !tdvp_bond_apply_fused_admits(ka, kb, W))
+        throw Error(T4A_GPU_INVALID_ARGUMENT, "tdvp_bond_apply: the fused launch holds 16 W k_b doubles in the LDS: W k_b must be at most " +
+                                                  std::to_string(TDVP_BOND_FUSED_MAX_PANEL));
+    Engine e;
+    hipStream_t st = e.stream();
+    DevBuf<double> dL = upload_vector(st, L, ka * W * ka), dR = upload_vector(st, R, kb * W * kb), dC = upload_vector(st, C, ka * kb), dT, dY;
+    dT.reserve(ka * W * kb);
+    dY.reserve(ka * kb);
+    if (route == BondApplyRoute::Fused)
+        tdvp_bond_apply_launch(dL.get(), dC.get(), dR.get(), dY.get(), (int)ka, (int)kb, (int)W, st);
+    else
+        tdvp_bond_apply_gemm(dL.get(), dC.get(), dR.get(), dT.get(), dY.get(), (int)ka, (int)kb, (int)W, st);
+    T4A_HIP(hipGetLastError());
+    T4A_HIP(hipMemcpyAsync(out, dY.get(), sizeof(double) * ka * kb, hipMemcpyDeviceToHost, st));
+    e.sync();
+    return route;
+}
+
+void tdvp_bond_apply_time(size_t ka, size_t kb, size_t W, size_t reps, double ms[2])
+{
+    if (ka == 0 || kb == 0 || W == 0 || reps == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "tdvp_bond_apply_time: ka, kb, W and reps must be positive");
+    check_bond_center_dims("tdvp_bond_apply_time", 0, ka, kb, W, 0);
+    require_device();
+    Engine e;
+    hipStream_t st = e.stream();
+    DevBuf<double> dL, dR, dC, dT, dY;
+    dL.reserve(ka * W * ka);
+    dR.reserve(kb * W * kb);
+    dC.reserve(ka * kb);
+    dT.reserve(ka * W * kb);
+    dY.reserve(ka * kb);
+    fill_launch(dL.get(), ka * W * ka, 1.0 / std::sqrt((double)(ka * W)), st);
+    fill_launch(dR.get(), kb * W * kb, 1.0 / std::sqrt((double)(kb * W)), st);
+    fill_launch(dC.get(), ka * kb, 1.0 / std::sqrt((double)(ka * kb)), st);
+    const bool fused = tdvp_bond_apply_fused_admits(ka, kb, W);
+    const std::function<void()> pieces[2] = {
+        [&] { tdvp_bond_apply_launch(dL.get(), dC.get(), dR.get(), dY.get(), (int)ka, (int)kb, (int)W, st); },
+        [&] { tdvp_bond_apply_gemm(dL.get(), dC.get(), dR.get(), dT.get(), dY.get(), (int)ka, (int)kb, (int)W, st); },
+    };
+    if (fused) {
+        time_pieces(st, pieces, 2, reps, ms);
+    } else {
+        ms[0] = std::numeric_limits<double>::quiet_NaN();
+        time_pieces(st, pieces + 1, 1, reps, ms + 1);
+    }
+    e.sync();
+}
+
 KrylovExpmResult krylov_expm_dense(const double* H, size_t n, const double* v0, double tau, const KrylovExpmOptions& o, double* v_out)
 {
     Engine e;

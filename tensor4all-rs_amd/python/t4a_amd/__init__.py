@@ -2235,11 +2235,12 @@ from .dmrg import (HermitianLanczosOptions, LanczosOptionsC, DmrgOptions, DmrgOp
 # t4a_amd.tdvp is the function as well; its module (the hooks _krylov_expm_dense, _krylov_orth, _apply_one_site, tdvp_plan) is
 # imported as `from t4a_amd.tdvp import ...` or reached as t4a_amd.tdvp_module
 from . import tdvp as tdvp_module  # noqa: E402
-from .tdvp import (HermitianKrylovExpmOptions, KrylovExpmOptionsC, TdvpOptions, TdvpOptionsC, TdvpResult, tdvp)  # noqa: E402,F401
+from .tdvp import (HermitianKrylovExpmOptions, KrylovExpmOptionsC, TdvpOptions, TdvpOptionsC, TdvpResult, tdvp, tdvp_one_site,  # noqa: E402,F401
+                   tdvp_one_site_plan, TdvpOneSiteStatsC)
 # global subspace expansion and GSE-TDVP: module t4a_amd.gse (the hooks _project, _absorb, _time_routes live there)
 from . import gse  # noqa: E402
 from .gse import (GseOptions, GseOptionsC, GseResult, GseTdvpOptions, GseTdvpResult, krylov_references, global_subspace_expand,  # noqa: E402,F401
-                  global_subspace_expand_with_references, gse_tdvp)
+                  global_subspace_expand_with_references, gse_tdvp, gse_tdvp_one_site)
 # partitioned MPOs: module t4a_amd.partitioned; its `contract` stays under the module name, like t4a_amd.mpo.contract
 from . import partitioned  # noqa: E402
 from .partitioned import Projector, PartitionedMPO, proj_contract  # noqa: E402,F401

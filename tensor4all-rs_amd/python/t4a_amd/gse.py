@@ -151,7 +151,8 @@ def global_subspace_expand(operator, init, center=0, options=None):
 
 def gse_tdvp(operator, init, center=0, options=None):
     """gse_tdvp (gse.rs:374-424) -> GseTdvpResult: before sweep s an expansion when ``krylov_dim > 0 and (s > 0 or
-    expand_before_first_sweep)``, then ``tdvp`` with ``nsweeps = 1``.  tdvp's own refusals apply unchanged."""
+    expand_before_first_sweep)``, then ``tdvp`` with ``nsweeps = 1``.  tdvp's own refusals apply unchanged (``nsite = 1`` is
+    ``gse_tdvp_one_site``)."""
     _operands(operator, init)
     o = GseTdvpOptions() if options is None else options
     if not isinstance(o, GseTdvpOptions) or not isinstance(o.tdvp, TdvpOptions):
@@ -162,6 +163,23 @@ def gse_tdvp(operator, init, center=0, options=None):
     sweeps, updates, expansions, err, iters = c_size_t(0), c_size_t(0), c_size_t(0), c_double(0.0), c_size_t(0)
     _check(_lib.t4a_gpu_gse_tdvp(operator._h, init._h, c, ctypes.byref(g), ctypes.byref(t), ctypes.byref(h), ctypes.byref(sweeps), ctypes.byref(updates),
                                  ctypes.byref(expansions), ctypes.byref(err), ctypes.byref(iters)))
+    return GseTdvpResult(SimpleTensorTrain._adopt(h), sweeps.value, updates.value, expansions.value, err.value, iters.value)
+
+
+def gse_tdvp_one_site(operator, init, center=0, options=None):
+    """The loop of ``gse_tdvp`` with ``tdvp_one_site`` for the one-sweep evolution after each expansion -> GseTdvpResult: the expansion
+    grows the bonds globally, the fixed-rank integrator evolves inside them.  Any ``center``.  ``options`` defaults to a GseTdvpOptions
+    whose ``tdvp`` has ``nsite = 1``; the refusals are those of the expansion and of ``tdvp_one_site``."""
+    _operands(operator, init)
+    o = GseTdvpOptions(tdvp=TdvpOptions(nsite=1)) if options is None else options
+    if not isinstance(o, GseTdvpOptions) or not isinstance(o.tdvp, TdvpOptions):
+        raise T4aError(INVALID_ARGUMENT, "gse_tdvp_one_site: options must be a GseTdvpOptions of a GseOptions and a TdvpOptions")
+    g, t = _options(o.gse), o.tdvp.to_c()
+    c = _center(center)
+    h = c_void_p()
+    sweeps, updates, expansions, err, iters = c_size_t(0), c_size_t(0), c_size_t(0), c_double(0.0), c_size_t(0)
+    _check(_lib.t4a_gpu_gse_tdvp_one_site(operator._h, init._h, c, ctypes.byref(g), ctypes.byref(t), ctypes.byref(h), ctypes.byref(sweeps),
+                                          ctypes.byref(updates), ctypes.byref(expansions), ctypes.byref(err), ctypes.byref(iters)))
     return GseTdvpResult(SimpleTensorTrain._adopt(h), sweeps.value, updates.value, expansions.value, err.value, iters.value)
 
 

@@ -8,7 +8,8 @@ Deviations from the reference: the exponent is REAL — ``exponent_step`` defaul
 is accepted and a non-zero imaginary part refused, because real-time evolution needs complex trains, which this project does not have
 (u' = -H u: heat and diffusion flows, imaginary-time relaxation, is what a real exponent covers); ``center`` must be 0 or n - 1, because
 the reference's two-site plan from an inner root of a chain applies a site correction at a leaf where the projector splitting needs it
-at the root; ``nsite = 1`` is not implemented.  Trees, index mappings and ``verbose`` are not mirrored.
+at the root; ``tdvp`` refuses ``nsite = 1``: one-site TDVP has entry points of its own, ``tdvp_one_site_plan`` and ``tdvp_one_site``
+below (fixed bond dimensions, any centre).  Trees, index mappings and ``verbose`` are not mirrored.
 """
 import ctypes
 
@@ -19,7 +20,8 @@ from . import (_lib, _check, _p, T4aError, INVALID_ARGUMENT, SimpleTensorTrain, 
 from .linsolve import _operands, _flat
 
 ROUTE_SERIAL, ROUTE_WIDE, ROUTE_AUTO = 0, 1, 2  # KrylovDotsRoute
-TWO_SITE, SITE_CORRECTION = 0, 1                # the kinds of a plan step
+TWO_SITE, SITE_CORRECTION, ONE_SITE = 0, 1, 2    # the kinds of a plan step
+BOND_FUSED, BOND_GEMM, BOND_AUTO = 0, 1, 2       # BondApplyRoute
 
 
 class KrylovExpmOptionsC(ctypes.Structure):
@@ -38,6 +40,12 @@ class TdvpStatsC(ctypes.Structure):
     """t4a_gpu_tdvp_stats"""
     _fields_ = [("two_site_steps", c_size_t), ("corrections", c_size_t), ("krylov_steps", c_size_t), ("apply_calls", c_size_t),
                 ("max_time_splits", c_size_t)]
+
+
+class TdvpOneSiteStatsC(ctypes.Structure):
+    """t4a_gpu_tdvp_one_site_stats"""
+    _fields_ = [("one_site_steps", c_size_t), ("bond_corrections", c_size_t), ("qr_steps", c_size_t), ("krylov_steps", c_size_t),
+                ("apply_calls", c_size_t), ("max_time_splits", c_size_t), ("fused_applies", c_size_t), ("gemm_applies", c_size_t)]
 
 
 class HermitianKrylovExpmOptions:
@@ -103,7 +111,7 @@ class TdvpResult:
 
 def tdvp(operator, init, center=0, options=None):
     """Two-site TDVP: ``nsweeps`` sweeps of exp(exponent_step * operator) on ``init`` from ``center`` (0 or n - 1) (tdvp/mod.rs:1107-1217)
-    -> TdvpResult.  The state is not renormalised."""
+    -> TdvpResult.  The state is not renormalised.  ``nsite = 1`` is refused here: see ``tdvp_one_site``."""
     _operands(operator, init)
     if int(center) < 0:
         raise T4aError(INVALID_ARGUMENT, "tdvp: center must not be negative")
@@ -128,6 +136,86 @@ def tdvp_plan(n, center, order, tau):
     _check(_lib.t4a_gpu_tdvp_plan(*args, c_size_t(k), _p(kinds), _p(nodes), _p(centers), _p(exps), ctypes.byref(count)))
     return [(int(kinds[j]), (int(nodes[2 * j]), int(nodes[2 * j + 1])) if kinds[j] == TWO_SITE else (int(nodes[2 * j]),), int(centers[j]), float(exps[j]))
             for j in range(k)]
+
+
+def tdvp_one_site(operator, init, center=0, options=None):
+    """One-site TDVP (TdvpOptions::with_nsite(1), tdvp/mod.rs:639-914): ``nsweeps`` sweeps of exp(exponent_step * operator) on ``init``
+    from any ``center`` with every bond dimension fixed -> TdvpResult, whose ``stats`` count one-site steps, bond corrections, QR steps,
+    Krylov steps, applies, time splits and the bond-centre applies by route.  ``options`` defaults to ``TdvpOptions(nsite=1)``;
+    ``max_bond_dim`` and ``svd_policy`` are refused (fixed ranks).  ``local_updates`` counts site and bond solves, w (2n - 1) per sweep."""
+    _operands(operator, init)
+    if int(center) < 0:
+        raise T4aError(INVALID_ARGUMENT, "tdvp_one_site: center must not be negative")
+    o = (TdvpOptions(nsite=1) if options is None else options).to_c()
+    h = c_void_p()
+    sweeps, updates, err, iters = c_size_t(0), c_size_t(0), c_double(0.0), c_size_t(0)
+    stats = TdvpOneSiteStatsC()
+    _check(_lib.t4a_gpu_tdvp_one_site(operator._h, init._h, c_size_t(int(center)), ctypes.byref(o), ctypes.byref(h), ctypes.byref(sweeps),
+                                      ctypes.byref(updates), ctypes.byref(err), ctypes.byref(iters), ctypes.byref(stats)))
+    return TdvpResult(SimpleTensorTrain._adopt(h), sweeps.value, updates.value, err.value, iters.value,
+                      {name: getattr(stats, name) for name, _ in TdvpOneSiteStatsC._fields_})
+
+
+def tdvp_one_site_plan(n, center, order, tau):
+    """The one-site plan of one sweep (t4a_gpu_tdvp_one_site_plan, host only) -> [(ONE_SITE, (node,), node, exponent)]: post order from
+    ``center``, the left arm leaf first, every even substep reversed."""
+    count = c_size_t(0)
+    args = (c_size_t(int(n)), c_size_t(int(center)), c_size_t(int(order)), c_double(float(tau)))
+    _check(_lib.t4a_gpu_tdvp_one_site_plan(*args, c_size_t(0), None, None, None, None, ctypes.byref(count)))
+    k = count.value
+    kinds, nodes, centers, exps = np.zeros(max(k, 1), dtype=np.int32), np.zeros(2 * max(k, 1), dtype=np.uintp), np.zeros(max(k, 1), dtype=np.uintp), np.zeros(max(k, 1))
+    _check(_lib.t4a_gpu_tdvp_one_site_plan(*args, c_size_t(k), _p(kinds), _p(nodes), _p(centers), _p(exps), ctypes.byref(count)))
+    return [(int(kinds[j]), (int(nodes[2 * j]),), int(centers[j]), float(exps[j])) for j in range(k)]
+
+
+def _apply_bond_center(left, right, c, route=BOND_AUTO):
+    """Test hook (t4a_gpu_tdvp_bond_apply): left [ka, W, ka], right [kb, W, kb], c (ka, kb) -> (Y (ka, kb), the route taken)."""
+    left, right, c = (np.asarray(a, dtype=np.float64) for a in (left, right, c))
+    if left.ndim != 3 or right.ndim != 3 or c.ndim != 2 or left.shape[0] != left.shape[2] or right.shape[0] != right.shape[2] \
+            or left.shape[1] != right.shape[1] or c.shape != (left.shape[0], right.shape[0]):
+        raise T4aError(INVALID_ARGUMENT, "apply_bond_center: left [ka, W, ka], right [kb, W, kb] and c (ka, kb)")
+    ka, kb, w = left.shape[0], right.shape[0], left.shape[1]
+    out = np.zeros(max(c.size, 1))
+    taken = c_int32(-1)
+    _check(_lib.t4a_gpu_tdvp_bond_apply(_p(_flat(left)), _p(_flat(right)), _p(_flat(c)), c_size_t(ka), c_size_t(kb), c_size_t(w), c_int32(route), _p(out),
+                                        ctypes.byref(taken)))
+    return out[:c.size].reshape(c.shape, order="F"), taken.value
+
+
+def _bond_apply_route(ka, kb, w):
+    """tdvp_bond_apply_route(ka, kb, W) (host only) -> BOND_FUSED or BOND_GEMM"""
+    r = c_int32(0)
+    _check(_lib.t4a_gpu_tdvp_bond_apply_route(c_size_t(ka), c_size_t(kb), c_size_t(w), ctypes.byref(r)))
+    return r.value
+
+
+def _bond_apply_fused_admits(ka, kb, w):
+    """whether the fused launch admits the shape (host only)"""
+    r = c_int32(0)
+    _check(_lib.t4a_gpu_tdvp_bond_apply_fused_admits(c_size_t(ka), c_size_t(kb), c_size_t(w), ctypes.byref(r)))
+    return bool(r.value)
+
+
+def _set_bond_apply_route(route):
+    """Test hook: forces the route of the bond-centre applies of the drivers (BOND_FUSED where admitted, BOND_GEMM; BOND_AUTO: the rule)"""
+    _check(_lib.t4a_gpu_tdvp_set_bond_apply_route(c_int32(route if route in (BOND_FUSED, BOND_GEMM) else -1)))
+
+
+def _bond_center_env(po, site, toward_right):
+    """Test hook (t4a_gpu_projected_operator_bond_center_env): the environment [k, W, k] of the bond-centre step next to ``site`` built
+    with the present tensor of that site as Q."""
+    dims = np.zeros(3, dtype=np.uintp)
+    _check(_lib.t4a_gpu_projected_operator_bond_center_env(po._h, c_size_t(site), c_int32(1 if toward_right else 0), _p(dims), None))
+    out = np.zeros(max(int(np.prod(dims)), 1))
+    _check(_lib.t4a_gpu_projected_operator_bond_center_env(po._h, c_size_t(site), c_int32(1 if toward_right else 0), _p(dims), _p(out)))
+    return out[:int(np.prod(dims))].reshape(tuple(int(d) for d in dims), order="F")
+
+
+def _time_bond_apply(ka, kb, w, reps=20):
+    """Probe (t4a_gpu_tdvp_bond_apply_time) -> {"fused", "gemm"} in device milliseconds (fused: nan outside the envelope)."""
+    ms = np.zeros(2)
+    _check(_lib.t4a_gpu_tdvp_bond_apply_time(c_size_t(ka), c_size_t(kb), c_size_t(w), c_size_t(reps), _p(ms)))
+    return {"fused": float(ms[0]), "gemm": float(ms[1])}
 
 
 def _apply_one_site(po, site, v):
