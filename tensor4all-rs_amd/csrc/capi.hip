@@ -692,7 +692,7 @@ KrylovExpmOptions convert_krylov_expm_options(const t4a_gpu_krylov_expm_options&
     return o;
 }
 
-TdvpOptions convert_tdvp_options(const t4a_gpu_tdvp_options* p)
+TdvpOptions convert_tdvp_options(const t4a_gpu_tdvp_options* p, TdvpMode mode)
 {
     TdvpOptions o;
     o.nsite = p->nsite;
@@ -705,25 +705,62 @@ TdvpOptions convert_tdvp_options(const t4a_gpu_tdvp_options* p)
     o.has_svd_policy = p->has_svd_policy != 0;
     if (o.has_svd_policy) o.svd_policy = from_c(p->svd_policy);
     o.krylov = convert_krylov_expm_options(p->krylov);
-    o.validate();
+    o.validate(mode);
     return o;
 }
 
-TdvpOptions convert_tdvp_one_site_options(const t4a_gpu_tdvp_options* p)
+// ---- what the two-site and the one-site TDVP entry points share: each is its mode, its name and its own stats struct
+void check_tdvp_shapes(TdvpMode mode, const size_t* op_dims4, size_t n_op, const size_t* state_dims3, size_t n_state, size_t center, size_t max_iter)
 {
-    TdvpOptions o;
-    o.nsite = p->nsite;
-    o.nsweeps = p->nsweeps;
-    o.order = p->order;
-    o.exponent_step_re = p->exponent_step_re;
-    o.exponent_step_im = p->exponent_step_im;
-    o.has_max_bond_dim = p->has_max_bond_dim != 0;
-    o.max_bond_dim = p->max_bond_dim;
-    o.has_svd_policy = p->has_svd_policy != 0;
-    if (o.has_svd_policy) o.svd_policy = from_c(p->svd_policy);
-    o.krylov = convert_krylov_expm_options(p->krylov);
-    o.validate_one_site();
-    return o;
+    if (n_op) T4A_REQUIRE_PTR(op_dims4);
+    if (n_state) T4A_REQUIRE_PTR(state_dims3);
+    KrylovExpmOptions ko;
+    ko.max_iter = max_iter;
+    ko.validate();
+    tdvp_validate_shapes(mode, dims4_list(op_dims4, n_op), dims3_list(state_dims3, n_state), center, max_iter);
+}
+
+// The plan into the caller's arrays; all four null: the count only.  `who` names the entry point in BUFFER_TOO_SMALL.
+void write_tdvp_plan(const char* who, const std::vector<TdvpStep>& plan, size_t capacity, int32_t* kinds, size_t* nodes, size_t* new_centers, double* exponents,
+                     size_t* n_steps)
+{
+    *n_steps = plan.size();
+    if (!kinds && !nodes && !new_centers && !exponents) return;
+    if (capacity < plan.size()) throw Error(T4A_GPU_BUFFER_TOO_SMALL, std::string(who) + ": the plan has " + std::to_string(plan.size()) + " steps");
+    T4A_REQUIRE_PTR(kinds);
+    T4A_REQUIRE_PTR(nodes);
+    T4A_REQUIRE_PTR(new_centers);
+    T4A_REQUIRE_PTR(exponents);
+    for (size_t k = 0; k < plan.size(); ++k) {
+        kinds[k] = (int32_t)plan[k].kind;
+        nodes[2 * k] = plan[k].nodes[0];
+        nodes[2 * k + 1] = plan[k].nodes[1];
+        new_centers[k] = plan[k].new_center;
+        exponents[k] = plan[k].exponent;
+    }
+}
+
+// -> the counters of the run, for the entry point's own stats struct
+TdvpStats run_tdvp(TdvpMode mode, const t4a_gpu_mpo* op, const t4a_gpu_tt* init, size_t center, const t4a_gpu_tdvp_options* options, t4a_gpu_tt** state,
+                   size_t* sweeps_completed, size_t* local_updates, double* max_error_estimate, size_t* max_krylov_iterations)
+{
+    T4A_REQUIRE_PTR(state);
+    *state = nullptr;
+    T4A_REQUIRE_PTR(options);
+    const TdvpOptions o = convert_tdvp_options(options, mode); // the options are checked on the host before an operand is looked at
+    T4A_REQUIRE_PTR(op);
+    T4A_REQUIRE_PTR(init);
+    T4A_REQUIRE_PTR(sweeps_completed);
+    T4A_REQUIRE_PTR(local_updates);
+    T4A_REQUIRE_PTR(max_error_estimate);
+    T4A_REQUIRE_PTR(max_krylov_iterations);
+    TdvpResult r = tdvp(mode, *op->impl, const_cast<t4a_gpu_tt*>(init)->impl, center, o);
+    *state = new t4a_gpu_tt(r.state->cores, r.state->eng.stream());
+    *sweeps_completed = r.sweeps_completed;
+    *local_updates = r.local_updates;
+    *max_error_estimate = r.max_error_estimate;
+    *max_krylov_iterations = r.max_krylov_iterations;
+    return r.stats;
 }
 
 GseOptions convert_gse_options(const t4a_gpu_gse_options* p)
@@ -748,6 +785,34 @@ void gse_counters(const GseResult& r, size_t* references_built, size_t* edges_pr
     *edges_processed = r.edges_processed;
     *bonds_expanded = r.bonds_expanded;
     *max_added_basis = r.max_added_basis;
+}
+
+// t4a_gpu_gse_tdvp and t4a_gpu_gse_tdvp_one_site but for the mode
+void run_gse_tdvp(TdvpMode mode, const t4a_gpu_mpo* op, const t4a_gpu_tt* init, size_t center, const t4a_gpu_gse_options* gse, const t4a_gpu_tdvp_options* tdvp_options,
+                  t4a_gpu_tt** state, size_t* sweeps_completed, size_t* local_updates, size_t* gse_expansions, double* max_error_estimate,
+                  size_t* max_krylov_iterations)
+{
+    T4A_REQUIRE_PTR(state);
+    *state = nullptr;
+    T4A_REQUIRE_PTR(gse);
+    T4A_REQUIRE_PTR(tdvp_options);
+    GseTdvpOptions o;
+    o.gse = convert_gse_options(gse); // the options are checked on the host before an operand is looked at
+    o.tdvp = convert_tdvp_options(tdvp_options, mode);
+    T4A_REQUIRE_PTR(op);
+    T4A_REQUIRE_PTR(init);
+    T4A_REQUIRE_PTR(sweeps_completed);
+    T4A_REQUIRE_PTR(local_updates);
+    T4A_REQUIRE_PTR(gse_expansions);
+    T4A_REQUIRE_PTR(max_error_estimate);
+    T4A_REQUIRE_PTR(max_krylov_iterations);
+    GseTdvpResult r = gse_tdvp(mode, *op->impl, const_cast<t4a_gpu_tt*>(init)->impl, center, o);
+    *state = new t4a_gpu_tt(r.state->cores, r.state->eng.stream());
+    *sweeps_completed = r.sweeps_completed;
+    *local_updates = r.local_updates;
+    *gse_expansions = r.gse_expansions;
+    *max_error_estimate = r.max_error_estimate;
+    *max_krylov_iterations = r.max_krylov_iterations;
 }
 
 // the ragged shape lists of the hooks as ints: every entry positive, at most `max_jobs` of them
@@ -4938,14 +5003,7 @@ t4a_gpu_status t4a_gpu_tdvp_options_default(t4a_gpu_tdvp_options* out)
 t4a_gpu_status t4a_gpu_tdvp_check_shapes(const size_t* op_dims4, size_t n_op, const size_t* state_dims3, size_t n_state, size_t center,
                                          size_t max_iter)
 {
-    return guarded([&] {
-        if (n_op) T4A_REQUIRE_PTR(op_dims4);
-        if (n_state) T4A_REQUIRE_PTR(state_dims3);
-        KrylovExpmOptions ko;
-        ko.max_iter = max_iter;
-        ko.validate();
-        tdvp_validate_shapes(dims4_list(op_dims4, n_op), dims3_list(state_dims3, n_state), center, max_iter);
-    });
+    return guarded([&] { check_tdvp_shapes(TdvpMode::TwoSite, op_dims4, n_op, state_dims3, n_state, center, max_iter); });
 }
 
 t4a_gpu_status t4a_gpu_tdvp_plan(size_t n, size_t center, size_t order, double tau, size_t capacity, int32_t* kinds, size_t* nodes, size_t* new_centers,
@@ -4953,21 +5011,7 @@ t4a_gpu_status t4a_gpu_tdvp_plan(size_t n, size_t center, size_t order, double t
 {
     return guarded([&] {
         T4A_REQUIRE_PTR(n_steps);
-        const std::vector<TdvpStep> plan = tdvp_plan(n, center, order, tau);
-        *n_steps = plan.size();
-        if (!kinds && !nodes && !new_centers && !exponents) return; // the count only
-        if (capacity < plan.size()) throw Error(T4A_GPU_BUFFER_TOO_SMALL, "tdvp_plan: the plan has " + std::to_string(plan.size()) + " steps");
-        T4A_REQUIRE_PTR(kinds);
-        T4A_REQUIRE_PTR(nodes);
-        T4A_REQUIRE_PTR(new_centers);
-        T4A_REQUIRE_PTR(exponents);
-        for (size_t k = 0; k < plan.size(); ++k) {
-            kinds[k] = (int32_t)plan[k].kind;
-            nodes[2 * k] = plan[k].nodes[0];
-            nodes[2 * k + 1] = plan[k].nodes[1];
-            new_centers[k] = plan[k].new_center;
-            exponents[k] = plan[k].exponent;
-        }
+        write_tdvp_plan("tdvp_plan", tdvp_plan(n, center, order, tau), capacity, kinds, nodes, new_centers, exponents, n_steps);
     });
 }
 
@@ -4976,25 +5020,11 @@ t4a_gpu_status t4a_gpu_tdvp(const t4a_gpu_mpo* op, const t4a_gpu_tt* init, size_
                             t4a_gpu_tdvp_stats* stats)
 {
     return guarded([&] {
-        T4A_REQUIRE_PTR(state);
-        *state = nullptr;
-        T4A_REQUIRE_PTR(options);
-        const TdvpOptions o = convert_tdvp_options(options); // the options are checked on the host before an operand is looked at
-        T4A_REQUIRE_PTR(op);
-        T4A_REQUIRE_PTR(init);
-        T4A_REQUIRE_PTR(sweeps_completed);
-        T4A_REQUIRE_PTR(local_updates);
-        T4A_REQUIRE_PTR(max_error_estimate);
-        T4A_REQUIRE_PTR(max_krylov_iterations);
-        TdvpResult r = tdvp(*op->impl, const_cast<t4a_gpu_tt*>(init)->impl, center, o);
-        *state = new t4a_gpu_tt(r.state->cores, r.state->eng.stream());
-        *sweeps_completed = r.sweeps_completed;
-        *local_updates = r.local_updates;
-        *max_error_estimate = r.max_error_estimate;
-        *max_krylov_iterations = r.max_krylov_iterations;
-        if (stats) *stats = t4a_gpu_tdvp_stats{r.stats.two_site_steps, r.stats.corrections, r.stats.krylov_steps, r.stats.apply_calls, r.stats.max_time_splits};
+        const TdvpStats s = run_tdvp(TdvpMode::TwoSite, op, init, center, options, state, sweeps_completed, local_updates, max_error_estimate, max_krylov_iterations);
+        if (stats) *stats = t4a_gpu_tdvp_stats{s.two_site_steps, s.corrections, s.krylov_steps, s.apply_calls, s.max_time_splits};
     });
 }
+
 
 // ---- one-site TDVP: fixed ranks, a bond-centre correction between two site steps (tdvp.hpp) ----
 t4a_gpu_status t4a_gpu_tdvp_one_site_options_default(t4a_gpu_tdvp_options* out)
@@ -5007,14 +5037,7 @@ t4a_gpu_status t4a_gpu_tdvp_one_site_options_default(t4a_gpu_tdvp_options* out)
 t4a_gpu_status t4a_gpu_tdvp_one_site_check_shapes(const size_t* op_dims4, size_t n_op, const size_t* state_dims3, size_t n_state, size_t center,
                                                   size_t max_iter)
 {
-    return guarded([&] {
-        if (n_op) T4A_REQUIRE_PTR(op_dims4);
-        if (n_state) T4A_REQUIRE_PTR(state_dims3);
-        KrylovExpmOptions ko;
-        ko.max_iter = max_iter;
-        ko.validate();
-        tdvp_one_site_validate_shapes(dims4_list(op_dims4, n_op), dims3_list(state_dims3, n_state), center, max_iter);
-    });
+    return guarded([&] { check_tdvp_shapes(TdvpMode::OneSite, op_dims4, n_op, state_dims3, n_state, center, max_iter); });
 }
 
 t4a_gpu_status t4a_gpu_tdvp_one_site_plan(size_t n, size_t center, size_t order, double tau, size_t capacity, int32_t* kinds, size_t* nodes,
@@ -5022,21 +5045,7 @@ t4a_gpu_status t4a_gpu_tdvp_one_site_plan(size_t n, size_t center, size_t order,
 {
     return guarded([&] {
         T4A_REQUIRE_PTR(n_steps);
-        const std::vector<TdvpStep> plan = tdvp_one_site_plan(n, center, order, tau);
-        *n_steps = plan.size();
-        if (!kinds && !nodes && !new_centers && !exponents) return; // the count only
-        if (capacity < plan.size()) throw Error(T4A_GPU_BUFFER_TOO_SMALL, "tdvp_one_site_plan: the plan has " + std::to_string(plan.size()) + " steps");
-        T4A_REQUIRE_PTR(kinds);
-        T4A_REQUIRE_PTR(nodes);
-        T4A_REQUIRE_PTR(new_centers);
-        T4A_REQUIRE_PTR(exponents);
-        for (size_t k = 0; k < plan.size(); ++k) {
-            kinds[k] = (int32_t)plan[k].kind;
-            nodes[2 * k] = plan[k].nodes[0];
-            nodes[2 * k + 1] = plan[k].nodes[1];
-            new_centers[k] = plan[k].new_center;
-            exponents[k] = plan[k].exponent;
-        }
+        write_tdvp_plan("tdvp_one_site_plan", tdvp_one_site_plan(n, center, order, tau), capacity, kinds, nodes, new_centers, exponents, n_steps);
     });
 }
 
@@ -5045,27 +5054,13 @@ t4a_gpu_status t4a_gpu_tdvp_one_site(const t4a_gpu_mpo* op, const t4a_gpu_tt* in
                                      t4a_gpu_tdvp_one_site_stats* stats)
 {
     return guarded([&] {
-        T4A_REQUIRE_PTR(state);
-        *state = nullptr;
-        T4A_REQUIRE_PTR(options);
-        const TdvpOptions o = convert_tdvp_one_site_options(options); // the options are checked on the host before an operand is looked at
-        T4A_REQUIRE_PTR(op);
-        T4A_REQUIRE_PTR(init);
-        T4A_REQUIRE_PTR(sweeps_completed);
-        T4A_REQUIRE_PTR(local_updates);
-        T4A_REQUIRE_PTR(max_error_estimate);
-        T4A_REQUIRE_PTR(max_krylov_iterations);
-        TdvpOneSiteResult r = tdvp_one_site(*op->impl, const_cast<t4a_gpu_tt*>(init)->impl, center, o);
-        *state = new t4a_gpu_tt(r.state->cores, r.state->eng.stream());
-        *sweeps_completed = r.sweeps_completed;
-        *local_updates = r.local_updates;
-        *max_error_estimate = r.max_error_estimate;
-        *max_krylov_iterations = r.max_krylov_iterations;
+        const TdvpStats s = run_tdvp(TdvpMode::OneSite, op, init, center, options, state, sweeps_completed, local_updates, max_error_estimate, max_krylov_iterations);
         if (stats)
-            *stats = t4a_gpu_tdvp_one_site_stats{r.stats.one_site_steps, r.stats.bond_corrections, r.stats.qr_steps,      r.stats.krylov_steps,
-                                                 r.stats.apply_calls,    r.stats.max_time_splits,  r.stats.fused_applies, r.stats.gemm_applies};
+            *stats = t4a_gpu_tdvp_one_site_stats{s.one_site_steps, s.bond_corrections, s.qr_steps, s.krylov_steps, s.apply_calls, s.max_time_splits, s.fused_applies,
+                                                 s.gemm_applies};
     });
 }
+
 
 t4a_gpu_status t4a_gpu_tdvp_bond_apply_route(size_t ka, size_t kb, size_t W, int32_t* route)
 {
@@ -5251,27 +5246,8 @@ t4a_gpu_status t4a_gpu_gse_tdvp(const t4a_gpu_mpo* op, const t4a_gpu_tt* init, s
                                 size_t* gse_expansions, double* max_error_estimate, size_t* max_krylov_iterations)
 {
     return guarded([&] {
-        T4A_REQUIRE_PTR(state);
-        *state = nullptr;
-        T4A_REQUIRE_PTR(gse);
-        T4A_REQUIRE_PTR(tdvp_options);
-        GseTdvpOptions o;
-        o.gse = convert_gse_options(gse); // the options are checked on the host before an operand is looked at
-        o.tdvp = convert_tdvp_options(tdvp_options);
-        T4A_REQUIRE_PTR(op);
-        T4A_REQUIRE_PTR(init);
-        T4A_REQUIRE_PTR(sweeps_completed);
-        T4A_REQUIRE_PTR(local_updates);
-        T4A_REQUIRE_PTR(gse_expansions);
-        T4A_REQUIRE_PTR(max_error_estimate);
-        T4A_REQUIRE_PTR(max_krylov_iterations);
-        GseTdvpResult r = gse_tdvp(*op->impl, const_cast<t4a_gpu_tt*>(init)->impl, center, o);
-        *state = new t4a_gpu_tt(r.state->cores, r.state->eng.stream());
-        *sweeps_completed = r.sweeps_completed;
-        *local_updates = r.local_updates;
-        *gse_expansions = r.gse_expansions;
-        *max_error_estimate = r.max_error_estimate;
-        *max_krylov_iterations = r.max_krylov_iterations;
+        run_gse_tdvp(TdvpMode::TwoSite, op, init, center, gse, tdvp_options, state, sweeps_completed, local_updates, gse_expansions, max_error_estimate,
+                     max_krylov_iterations);
     });
 }
 
@@ -5280,29 +5256,11 @@ t4a_gpu_status t4a_gpu_gse_tdvp_one_site(const t4a_gpu_mpo* op, const t4a_gpu_tt
                                          size_t* gse_expansions, double* max_error_estimate, size_t* max_krylov_iterations)
 {
     return guarded([&] {
-        T4A_REQUIRE_PTR(state);
-        *state = nullptr;
-        T4A_REQUIRE_PTR(gse);
-        T4A_REQUIRE_PTR(tdvp_options);
-        GseTdvpOptions o;
-        o.gse = convert_gse_options(gse); // the options are checked on the host before an operand is looked at
-        o.tdvp = convert_tdvp_one_site_options(tdvp_options);
-        T4A_REQUIRE_PTR(op);
-        T4A_REQUIRE_PTR(init);
-        T4A_REQUIRE_PTR(sweeps_completed);
-        T4A_REQUIRE_PTR(local_updates);
-        T4A_REQUIRE_PTR(gse_expansions);
-        T4A_REQUIRE_PTR(max_error_estimate);
-        T4A_REQUIRE_PTR(max_krylov_iterations);
-        GseTdvpResult r = gse_tdvp_one_site(*op->impl, const_cast<t4a_gpu_tt*>(init)->impl, center, o);
-        *state = new t4a_gpu_tt(r.state->cores, r.state->eng.stream());
-        *sweeps_completed = r.sweeps_completed;
-        *local_updates = r.local_updates;
-        *gse_expansions = r.gse_expansions;
-        *max_error_estimate = r.max_error_estimate;
-        *max_krylov_iterations = r.max_krylov_iterations;
+        run_gse_tdvp(TdvpMode::OneSite, op, init, center, gse, tdvp_options, state, sweeps_completed, local_updates, gse_expansions, max_error_estimate,
+                     max_krylov_iterations);
     });
 }
+
 
 t4a_gpu_status t4a_gpu_gse_project(int32_t orient, size_t q, const double* refs, const size_t* rho, size_t K, const double* B, size_t kb, int32_t route,
                                    double* stack, double* trace)

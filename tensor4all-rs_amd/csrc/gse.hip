@@ -288,11 +288,11 @@ GseResult global_subspace_expand(Mpo& op, TensorTrain& init, size_t center, cons
     return global_subspace_expand_with_references(init, ptrs, center, o);
 }
 
-GseTdvpResult gse_tdvp(Mpo& op, TensorTrain& init, size_t center, const GseTdvpOptions& o)
+GseTdvpResult gse_tdvp(TdvpMode mode, Mpo& op, TensorTrain& init, size_t center, const GseTdvpOptions& o)
 {
     o.gse.validate();
-    o.tdvp.validate();
-    tdvp_validate_shapes(op.dims4(), dims3_of(init.cores), center, o.tdvp.krylov.max_iter);
+    o.tdvp.validate(mode);
+    tdvp_validate_shapes(mode, op.dims4(), dims3_of(init.cores), center, o.tdvp.krylov.max_iter);
     if (o.gse.krylov_dim > (size_t)GSE_MAX_REFERENCES)
         throw Error(T4A_GPU_NOT_IMPLEMENTED, "gse: more than " + std::to_string(GSE_MAX_REFERENCES) + " references are not implemented");
     GseTdvpResult out;
@@ -307,38 +307,7 @@ GseTdvpResult gse_tdvp(Mpo& op, TensorTrain& init, size_t center, const GseTdvpO
             cur = state.get();
             ++out.gse_expansions;
         }
-        TdvpResult r = tdvp(op, *cur, center, one);
-        state = std::move(r.state);
-        cur = state.get();
-        out.sweeps_completed += r.sweeps_completed;
-        out.local_updates += r.local_updates;
-        out.max_error_estimate = std::max(out.max_error_estimate, r.max_error_estimate);
-        out.max_krylov_iterations = std::max(out.max_krylov_iterations, r.max_krylov_iterations);
-    }
-    out.state = std::move(state);
-    return out;
-}
-
-GseTdvpResult gse_tdvp_one_site(Mpo& op, TensorTrain& init, size_t center, const GseTdvpOptions& o)
-{
-    o.gse.validate();
-    o.tdvp.validate_one_site();
-    tdvp_one_site_validate_shapes(op.dims4(), dims3_of(init.cores), center, o.tdvp.krylov.max_iter);
-    if (o.gse.krylov_dim > (size_t)GSE_MAX_REFERENCES)
-        throw Error(T4A_GPU_NOT_IMPLEMENTED, "gse: more than " + std::to_string(GSE_MAX_REFERENCES) + " references are not implemented");
-    GseTdvpResult out;
-    std::unique_ptr<TensorTrain> state;
-    TensorTrain* cur = &init;
-    TdvpOptions one = o.tdvp;
-    one.nsweeps = 1;
-    for (size_t sweep = 0; sweep < o.tdvp.nsweeps; ++sweep) {
-        if (o.gse.krylov_dim > 0 && (sweep > 0 || o.gse.expand_before_first_sweep)) {
-            GseResult ex = global_subspace_expand(op, *cur, center, o.gse);
-            state = std::move(ex.state);
-            cur = state.get();
-            ++out.gse_expansions;
-        }
-        TdvpOneSiteResult r = tdvp_one_site(op, *cur, center, one);
+        TdvpResult r = tdvp(mode, op, *cur, center, one);
         state = std::move(r.state);
         cur = state.get();
         out.sweeps_completed += r.sweeps_completed;

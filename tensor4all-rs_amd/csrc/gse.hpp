@@ -143,10 +143,10 @@ void gse_validate_shapes(const std::vector<std::array<size_t, 3>>& state, const 
 std::vector<std::unique_ptr<TensorTrain>> gse_krylov_references(Mpo& op, TensorTrain& init, const GseOptions& o);
 GseResult global_subspace_expand_with_references(TensorTrain& init, const std::vector<TensorTrain*>& references, size_t center, const GseOptions& o);
 GseResult global_subspace_expand(Mpo& op, TensorTrain& init, size_t center, const GseOptions& o);
-GseTdvpResult gse_tdvp(Mpo& op, TensorTrain& init, size_t center, const GseTdvpOptions& o);
-// The loop of gse_tdvp with tdvp_one_site (o.tdvp.nsite == 1) for the one-sweep evolution after each expansion: the expansion grows the
-// bonds globally, the fixed-rank integrator evolves inside them.  Any centre, since both parts allow it.
-GseTdvpResult gse_tdvp_one_site(Mpo& op, TensorTrain& init, size_t center, const GseTdvpOptions& o);
+// gse_tdvp (TwoSite) and gse_tdvp_one_site (OneSite): one loop, the one-sweep evolution after each expansion is the driver of `mode`,
+// whose rules for o.tdvp and the shapes apply.  One-site: the expansion grows the bonds globally, the fixed-rank integrator evolves
+// inside them; any centre, since both parts allow it.
+GseTdvpResult gse_tdvp(TdvpMode mode, Mpo& op, TensorTrain& init, size_t center, const GseTdvpOptions& o);
 
 // Test hooks on host arrays (column-major, layouts of gse_project_launch / gse_absorb_launch); route 0: the fused launch, 1: the GEMM
 // composition.  project: refs concatenated, stack (sum rho) x q (orient 1: q x sum rho).  absorb: children, parents and results concatenated.

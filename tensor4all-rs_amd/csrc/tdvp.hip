@@ -26,48 +26,66 @@ void KrylovExpmOptions::validate() const
     require_tol(hermitian_tol, who + "hermitian_tol must be finite and non-negative");
 }
 
-void TdvpOptions::validate() const
+// The rules both modes share, each with the message of the reference
+namespace {
+void require_sweeps_and_order(const TdvpOptions& o)
 {
-    if (nsite != 1 && nsite != 2)
-        throw Error(T4A_GPU_INVALID_ARGUMENT, "TDVP supports nsite=1 or nsite=2 in this version, got nsite=" + std::to_string(nsite));
-    if (nsweeps == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "invalid TDVP option nsweeps: must be greater than zero");
-    if (order != 1 && order != 2 && order != 4)
-        throw Error(T4A_GPU_INVALID_ARGUMENT, "TDVP applyexp order " + std::to_string(order) + " is not supported; supported orders are 1, 2, and 4");
-    if (!std::isfinite(exponent_step_re) || !std::isfinite(exponent_step_im))
-        throw Error(T4A_GPU_INVALID_ARGUMENT, "invalid TDVP option exponent_step: real and imaginary parts must be finite");
-    if (has_max_bond_dim && max_bond_dim == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "invalid TDVP option max_bond_dim: must be greater than zero when set");
-    // this project's own restrictions
-    if (nsite == 1)
-        throw Error(T4A_GPU_INVALID_ARGUMENT, "tdvp: one-site TDVP (nsite=1) is not implemented here: it needs the bond-centre apply; use nsite=2");
-    if (exponent_step_im != 0.0)
-        throw Error(T4A_GPU_INVALID_ARGUMENT,
-                    "tdvp: exponent_step must be real here: real-time evolution (a non-zero imaginary part) needs complex tensor trains, which this project does not have");
-    krylov.validate();
-    if (has_svd_policy) validate_svd_policy(svd_policy, "TdvpOptions::svd_policy");
+    if (o.nsweeps == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "invalid TDVP option nsweeps: must be greater than zero");
+    if (o.order != 1 && o.order != 2 && o.order != 4)
+        throw Error(T4A_GPU_INVALID_ARGUMENT, "TDVP applyexp order " + std::to_string(o.order) + " is not supported; supported orders are 1, 2, and 4");
 }
-
-void TdvpOptions::validate_one_site() const
+void require_finite_exponent(const TdvpOptions& o)
 {
-    if (nsite != 1)
-        throw Error(T4A_GPU_INVALID_ARGUMENT, "tdvp_one_site: one-site TDVP requires nsite=1, got nsite=" + std::to_string(nsite) + "; nsite=2 is tdvp");
-    if (nsweeps == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "invalid TDVP option nsweeps: must be greater than zero");
-    if (order != 1 && order != 2 && order != 4)
-        throw Error(T4A_GPU_INVALID_ARGUMENT, "TDVP applyexp order " + std::to_string(order) + " is not supported; supported orders are 1, 2, and 4");
-    if (!std::isfinite(exponent_step_re) || !std::isfinite(exponent_step_im))
+    if (!std::isfinite(o.exponent_step_re) || !std::isfinite(o.exponent_step_im))
         throw Error(T4A_GPU_INVALID_ARGUMENT, "invalid TDVP option exponent_step: real and imaginary parts must be finite");
-    if (exponent_step_im != 0.0)
-        throw Error(T4A_GPU_INVALID_ARGUMENT,
-                    "tdvp_one_site: exponent_step must be real here: real-time evolution (a non-zero imaginary part) needs complex tensor trains, which this project does not have");
-    if (has_max_bond_dim && max_bond_dim == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "invalid TDVP option max_bond_dim: must be greater than zero when set");
-    if (has_max_bond_dim) throw Error(T4A_GPU_INVALID_ARGUMENT, "invalid TDVP option max_bond_dim: one-site TDVP has fixed ranks; use nsite=2 for truncation");
-    if (has_svd_policy) throw Error(T4A_GPU_INVALID_ARGUMENT, "invalid TDVP option svd_policy: one-site TDVP has fixed ranks; use nsite=2 for truncation");
-    krylov.validate();
+}
+void require_real_exponent(const TdvpOptions& o, const char* who) // this project's own restriction
+{
+    if (o.exponent_step_im != 0.0)
+        throw Error(T4A_GPU_INVALID_ARGUMENT, std::string(who) + ": exponent_step must be real here: real-time evolution (a non-zero imaginary part) needs complex "
+                                                                 "tensor trains, which this project does not have");
+}
+void require_positive_max_bond_dim(const TdvpOptions& o)
+{
+    if (o.has_max_bond_dim && o.max_bond_dim == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "invalid TDVP option max_bond_dim: must be greater than zero when set");
+}
+} // namespace
+
+void TdvpOptions::validate(TdvpMode mode) const
+{
+    if (mode == TdvpMode::TwoSite) {
+        if (nsite != 1 && nsite != 2)
+            throw Error(T4A_GPU_INVALID_ARGUMENT, "TDVP supports nsite=1 or nsite=2 in this version, got nsite=" + std::to_string(nsite));
+        require_sweeps_and_order(*this);
+        require_finite_exponent(*this);
+        require_positive_max_bond_dim(*this);
+        if (nsite == 1) // this project's own restriction
+            throw Error(T4A_GPU_INVALID_ARGUMENT, "tdvp: one-site TDVP (nsite=1) is not implemented here: it needs the bond-centre apply; use nsite=2");
+        require_real_exponent(*this, "tdvp");
+        krylov.validate();
+        if (has_svd_policy) validate_svd_policy(svd_policy, "TdvpOptions::svd_policy");
+    } else {
+        if (nsite != 1)
+            throw Error(T4A_GPU_INVALID_ARGUMENT, "tdvp_one_site: one-site TDVP requires nsite=1, got nsite=" + std::to_string(nsite) + "; nsite=2 is tdvp");
+        require_sweeps_and_order(*this);
+        require_finite_exponent(*this);
+        require_real_exponent(*this, "tdvp_one_site");
+        require_positive_max_bond_dim(*this);
+        if (has_max_bond_dim) throw Error(T4A_GPU_INVALID_ARGUMENT, "invalid TDVP option max_bond_dim: one-site TDVP has fixed ranks; use nsite=2 for truncation");
+        if (has_svd_policy) throw Error(T4A_GPU_INVALID_ARGUMENT, "invalid TDVP option svd_policy: one-site TDVP has fixed ranks; use nsite=2 for truncation");
+        krylov.validate();
+    }
 }
 
 namespace {
+void require_state_node(const char* who, size_t n, size_t center)
+{
+    if (center >= n)
+        throw Error(T4A_GPU_INVALID_ARGUMENT, std::string(who) + ": TDVP center " + std::to_string(center) + " is not a state node (" + std::to_string(n) + " sites)");
+}
 void require_end_center(size_t n, size_t center)
 {
-    if (center >= n) throw Error(T4A_GPU_INVALID_ARGUMENT, "tdvp: TDVP center " + std::to_string(center) + " is not a state node (" + std::to_string(n) + " sites)");
+    require_state_node("tdvp", n, center);
     if (center != 0 && center != n - 1)
         throw Error(T4A_GPU_INVALID_ARGUMENT, "tdvp: center " + std::to_string(center) + " is an inner node of the chain: the two-site region plan from an inner root applies the site "
                                               "correction at a leaf instead of the root, which is not a projector splitting; start from 0 or " + std::to_string(n - 1));
@@ -87,10 +105,14 @@ void tdvp_one_site_validate_shapes(const std::vector<std::array<size_t, 4>>& op,
 {
     const size_t n = state.size();
     validate_chain_operands("tdvp_one_site", op, nullptr, state, "a single site has no bond to correct and the shared chain checks need two sites: one-site TDVP requires at least two sites");
-    if (center >= n)
-        throw Error(T4A_GPU_INVALID_ARGUMENT, "tdvp_one_site: TDVP center " + std::to_string(center) + " is not a state node (" + std::to_string(n) + " sites)");
+    require_state_node("tdvp_one_site", n, center);
     for (size_t c = 0; c < n; ++c) check_site_step_dims("tdvp_one_site", c, state[c][0], state[c][1], state[c][2], op[c][3], max_iter);
     for (size_t i = 0; i + 1 < n; ++i) check_bond_center_dims("tdvp_one_site", i, state[i][2], state[i][2], op[i][3], max_iter);
+}
+
+void tdvp_validate_shapes(TdvpMode mode, const std::vector<std::array<size_t, 4>>& op, const std::vector<std::array<size_t, 3>>& state, size_t center, size_t max_iter)
+{
+    mode == TdvpMode::TwoSite ? tdvp_validate_shapes(op, state, center, max_iter) : tdvp_one_site_validate_shapes(op, state, center, max_iter);
 }
 
 // ------------------------------------------------------------------------------------------------ the plan
@@ -105,10 +127,33 @@ std::vector<double> tdvp_sub_steps(size_t order)
     throw Error(T4A_GPU_INVALID_ARGUMENT, "TDVP applyexp order " + std::to_string(order) + " is not supported; supported orders are 1, 2, and 4");
 }
 
+namespace {
+// One sweep: the base list once per substep with its exponents scaled by the weight; every even substep (1-based) is the reversed list,
+// and `reversed(step)` does to each of its steps what the mode's reversal does beyond the order.
+template <class F> std::vector<TdvpStep> expand_sub_steps(const std::vector<TdvpStep>& base, const std::vector<double>& weights, F&& reversed)
+{
+    std::vector<TdvpStep> steps;
+    for (size_t k = 0; k < weights.size(); ++k) {
+        std::vector<TdvpStep> part = base;
+        for (TdvpStep& s : part) s.exponent = s.exponent * weights[k];
+        if ((k + 1) % 2 == 0) {
+            std::reverse(part.begin(), part.end());
+            for (TdvpStep& s : part) reversed(s);
+        }
+        steps.insert(steps.end(), part.begin(), part.end());
+    }
+    return steps;
+}
+void require_finite_tau(double tau)
+{
+    if (!std::isfinite(tau)) throw Error(T4A_GPU_INVALID_ARGUMENT, "invalid TDVP option exponent_step: real and imaginary parts must be finite");
+}
+} // namespace
+
 std::vector<TdvpStep> tdvp_plan(size_t n, size_t center, size_t order, double tau)
 {
     const std::vector<double> weights = tdvp_sub_steps(order);
-    if (!std::isfinite(tau)) throw Error(T4A_GPU_INVALID_ARGUMENT, "invalid TDVP option exponent_step: real and imaginary parts must be finite");
+    require_finite_tau(tau);
     if (n < 2) throw Error(T4A_GPU_INVALID_ARGUMENT, "tdvp: two-site TDVP requires at least one state edge");
     require_end_center(n, center);
     auto node = [&](size_t j) { return center == 0 ? j : n - 1 - j; }; // the chain as the walk from the root sees it
@@ -118,41 +163,23 @@ std::vector<TdvpStep> tdvp_plan(size_t n, size_t center, size_t order, double ta
         base.push_back({TdvpStepKind::TwoSite, {a, b}, b, tau});
         if (j + 2 < n) base.push_back({TdvpStepKind::SiteCorrection, {b, b}, b, -tau});
     }
-    std::vector<TdvpStep> steps;
-    for (size_t k = 0; k < weights.size(); ++k) {
-        std::vector<TdvpStep> part = base;
-        for (TdvpStep& s : part) s.exponent = s.exponent * weights[k];
-        if ((k + 1) % 2 == 0) {
-            std::reverse(part.begin(), part.end());
-            for (TdvpStep& s : part) {
-                std::swap(s.nodes[0], s.nodes[1]);
-                s.new_center = s.nodes[1];
-            }
-        }
-        steps.insert(steps.end(), part.begin(), part.end());
-    }
-    return steps;
+    return expand_sub_steps(base, weights, [](TdvpStep& s) { // the nodes reversed, the last node the new centre
+        std::swap(s.nodes[0], s.nodes[1]);
+        s.new_center = s.nodes[1];
+    });
 }
 
 std::vector<TdvpStep> tdvp_one_site_plan(size_t n, size_t center, size_t order, double tau)
 {
     const std::vector<double> weights = tdvp_sub_steps(order);
-    if (!std::isfinite(tau)) throw Error(T4A_GPU_INVALID_ARGUMENT, "invalid TDVP option exponent_step: real and imaginary parts must be finite");
+    require_finite_tau(tau);
     if (n == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "tdvp_one_site: the plan of an empty chain");
-    if (center >= n)
-        throw Error(T4A_GPU_INVALID_ARGUMENT, "tdvp_one_site: TDVP center " + std::to_string(center) + " is not a state node (" + std::to_string(n) + " sites)");
+    require_state_node("tdvp_one_site", n, center);
     std::vector<TdvpStep> base; // post order: the left arm leaf first, the right arm leaf first, the centre
     for (size_t j = 0; j < center; ++j) base.push_back({TdvpStepKind::OneSite, {j, j}, j, tau});
     for (size_t j = n - 1; j > center; --j) base.push_back({TdvpStepKind::OneSite, {j, j}, j, tau});
     base.push_back({TdvpStepKind::OneSite, {center, center}, center, tau});
-    std::vector<TdvpStep> steps;
-    for (size_t k = 0; k < weights.size(); ++k) {
-        std::vector<TdvpStep> part = base;
-        for (TdvpStep& s : part) s.exponent = s.exponent * weights[k];
-        if ((k + 1) % 2 == 0) std::reverse(part.begin(), part.end());
-        steps.insert(steps.end(), part.begin(), part.end());
-    }
-    return steps;
+    return expand_sub_steps(base, weights, [](TdvpStep&) {}); // a one-site step is its own mirror image
 }
 
 // ------------------------------------------------------------------------------------------------ the Krylov exponential
@@ -247,78 +274,6 @@ KrylovExpmResult KrylovExpm::solve(const GmresApply& apply, size_t len, double* 
     }
 }
 
-// ------------------------------------------------------------------------------------------------ the sweeps
-TdvpResult tdvp(Mpo& op, TensorTrain& init, size_t center, const TdvpOptions& o)
-{
-    o.validate();
-    tdvp_validate_shapes(op.dims4(), dims3_of(init.cores), center, o.krylov.max_iter);
-    const std::vector<TdvpStep> plan = tdvp_plan(init.cores.size(), center, o.order, o.exponent_step_re);
-    TdvpResult out;
-    ProjectedOperator po(op, init, nullptr);
-    Engine& e = po.engine();
-    hipStream_t st = e.stream();
-    QrSweep sw(e);
-    sw.canonicalize(po.x, center);
-    size_t cur = center;
-    KrylovExpm kx(e);
-    DevBuf<double> theta;
-    const SvdOptions so = sweep_svd_options(o.has_svd_policy, o.svd_policy, o.has_max_bond_dim, o.max_bond_dim);
-
-    auto book = [&](const KrylovExpmResult& r) {
-        out.max_error_estimate = std::max(out.max_error_estimate, r.error_estimate);
-        out.max_krylov_iterations = std::max(out.max_krylov_iterations, r.iterations);
-        out.stats.krylov_steps += r.iterations;
-        out.stats.apply_calls += r.apply_calls;
-        out.stats.max_time_splits = std::max(out.stats.max_time_splits, r.time_splits);
-        ++out.local_updates;
-    };
-    // move_center_to_region_full_rank: thin QR steps to the nearest node of the region
-    auto move_center = [&](size_t target) {
-        while (cur < target) {
-            sw.left_step(po.x, cur);
-            po.invalidate(cur);
-            po.invalidate(cur + 1);
-            ++cur;
-        }
-        while (cur > target) {
-            sw.right_step(po.x, cur);
-            po.invalidate(cur);
-            po.invalidate(cur - 1);
-            --cur;
-        }
-    };
-
-    for (size_t sweep = 0; sweep < o.nsweeps; ++sweep) {
-        for (const TdvpStep& s : plan) {
-            if (cur != s.nodes[0] && cur != s.nodes[1]) {
-                const size_t d0 = cur > s.nodes[0] ? cur - s.nodes[0] : s.nodes[0] - cur, d1 = cur > s.nodes[1] ? cur - s.nodes[1] : s.nodes[1] - cur;
-                move_center(d0 <= d1 ? s.nodes[0] : s.nodes[1]);
-            }
-            if (s.kind == TdvpStepKind::TwoSite) {
-                const size_t i = std::min(s.nodes[0], s.nodes[1]);
-                po.check_step(i, o.krylov.max_iter, "tdvp");
-                const size_t len = po.two_site_vector(i, theta); // theta_0 = x_i x_{i+1}
-                po.prepare(i);
-                book(kx.solve([&](const double* v, double* y) { po.apply_prepared(v, y); }, len, theta.get(), s.exponent, o.krylov));
-                po.split_and_advance(i, theta.get(), so, s.new_center == i + 1, "tdvp"); // the singular values go to the new centre, no renormalisation
-                ++out.stats.two_site_steps;
-            } else {
-                const size_t c = s.nodes[0];
-                po.check_site_step(c, o.krylov.max_iter, "tdvp");
-                po.prepare_one_site(c);
-                book(kx.solve([&](const double* v, double* y) { po.apply_one_site_prepared(v, y); }, po.x[c].size(), po.x[c].buf.get(), s.exponent, o.krylov));
-                po.invalidate(c);
-                ++out.stats.corrections;
-            }
-            cur = s.new_center;
-        }
-        out.sweeps_completed = sweep + 1;
-    }
-    e.sync();
-    out.state = std::make_unique<TensorTrain>(po.x, st);
-    return out;
-}
-
 // ------------------------------------------------------------------------------------------------ the bond-centre apply
 // Measured on an MI355X at k_a = k_b = k (tools/probe_tdvp_one_site.py): the fused launch takes 0.36 - 0.78 of the
 // two GEMMs at k = 8, 16, 32 with W = 4 and at k = 8, 16 with W = 16, and 1.15 - 3.1 times as long at k = 64, 128 with W = 4 and k = 32 with
@@ -345,9 +300,12 @@ void tdvp_bond_apply_gemm(const double* La, const double* C, const double* Rb, d
 }
 
 namespace {
-BondApplyRoute resolve_bond_route(BondApplyRoute route, size_t ka, size_t kb, size_t W)
+// The route of an apply that `forced` asks a route of: Gemm is taken as it is, Fused where the envelope admits the shape; Auto, and Fused
+// outside the envelope, are the rule.
+BondApplyRoute resolve_bond_route(BondApplyRoute forced, size_t ka, size_t kb, size_t W)
 {
-    return route == BondApplyRoute::Auto ? tdvp_bond_apply_route(ka, kb, W) : route;
+    if (forced == BondApplyRoute::Gemm || (forced == BondApplyRoute::Fused && tdvp_bond_apply_fused_admits(ka, kb, W))) return forced;
+    return tdvp_bond_apply_route(ka, kb, W);
 }
 } // namespace
 
@@ -355,10 +313,7 @@ void ProjectedOperator::apply_bond_center_prepared(const double* d_c, double* d_
 {
     hipStream_t st = engine().stream();
     const int forced = g_bond_route.load();
-    BondApplyRoute route = tdvp_bond_apply_route(bc_ka_, bc_kb_, bc_w_);
-    if (forced == 1) route = BondApplyRoute::Gemm;
-    if (forced == 0 && tdvp_bond_apply_fused_admits(bc_ka_, bc_kb_, bc_w_)) route = BondApplyRoute::Fused;
-    if (route == BondApplyRoute::Fused) {
+    if (resolve_bond_route(forced < 0 ? BondApplyRoute::Auto : (BondApplyRoute)forced, bc_ka_, bc_kb_, bc_w_) == BondApplyRoute::Fused) {
         tdvp_bond_apply_launch(bc_la_, d_c, bc_rb_, d_out, (int)bc_ka_, (int)bc_kb_, (int)bc_w_, st);
         ++fused_applies;
     } else {
@@ -367,73 +322,92 @@ void ProjectedOperator::apply_bond_center_prepared(const double* d_c, double* d_
     }
 }
 
-// ------------------------------------------------------------------------------------------------ the one-site sweeps
-TdvpOneSiteResult tdvp_one_site(Mpo& op, TensorTrain& init, size_t center, const TdvpOptions& o)
-{
-    o.validate_one_site();
-    tdvp_one_site_validate_shapes(op.dims4(), dims3_of(init.cores), center, o.krylov.max_iter);
-    const size_t n = init.cores.size();
-    const std::vector<TdvpStep> plan = tdvp_one_site_plan(n, center, o.order, o.exponent_step_re);
-    TdvpOneSiteResult out;
-    ProjectedOperator po(op, init, nullptr);
-    Engine& e = po.engine();
-    hipStream_t st = e.stream();
-    QrSweep sw(e);
-    sw.canonicalize(po.x, center);
-    size_t cur = center;
-    KrylovExpm kx(e);
-    DevBuf<double> cm, m1, qt, rr; // the bond matrix and the scratch of its factorisation
+// ------------------------------------------------------------------------------------------------ the sweeps
+namespace {
+// What a sweep of either mode runs on: the state inside the projected operator, canonicalised onto `cur`, and the steps of tdvp.hpp.
+// `who` is the driver's name in the messages of the step checks.
+struct TdvpSweep {
+    const TdvpOptions& o;
+    const char* who;
+    ProjectedOperator po;
+    Engine& e;
+    hipStream_t st;
+    QrSweep sw;
+    KrylovExpm kx;
+    size_t cur;
+    DevBuf<double> theta, cm; // the two-site vector; the bond matrix where it is not the R of the QR sweep
+    TdvpResult out;
 
-    auto book = [&](const KrylovExpmResult& r) {
+    TdvpSweep(Mpo& op, TensorTrain& init, size_t center, const TdvpOptions& options, const char* name)
+        : o(options), who(name), po(op, init, nullptr), e(po.engine()), st(e.stream()), sw(e), kx(e), cur(center)
+    {
+        sw.canonicalize(po.x, center);
+    }
+
+    void book(const KrylovExpmResult& r)
+    {
         out.max_error_estimate = std::max(out.max_error_estimate, r.error_estimate);
         out.max_krylov_iterations = std::max(out.max_krylov_iterations, r.iterations);
         out.stats.krylov_steps += r.iterations;
         out.stats.apply_calls += r.apply_calls;
         out.stats.max_time_splits = std::max(out.stats.max_time_splits, r.time_splits);
         ++out.local_updates;
-    };
+    }
+
     // move_center_to_region_full_rank: thin QR steps, every cache that contains a changed site goes stale
-    auto move_center = [&](size_t target) {
-        while (cur < target) {
-            sw.left_step(po.x, cur);
+    void move_center(size_t target)
+    {
+        while (cur != target) {
+            const size_t next = cur < target ? cur + 1 : cur - 1;
+            if (next > cur)
+                sw.left_step(po.x, cur);
+            else
+                sw.right_step(po.x, cur);
             po.invalidate(cur);
-            po.invalidate(cur + 1);
-            ++cur;
+            po.invalidate(next);
+            cur = next;
             ++out.stats.qr_steps;
         }
-        while (cur > target) {
-            sw.right_step(po.x, cur);
-            po.invalidate(cur);
-            po.invalidate(cur - 1);
-            --cur;
-            ++out.stats.qr_steps;
-        }
-    };
-    // apply_one_site_bond_correction (mod.rs:702-860) at the centre c towards its neighbour on that side -> the new centre
-    auto bond_correction = [&](size_t c, bool right, double exponent) {
-        DevCore& X = po.x[c];
+    }
+
+    // exp(exponent H_c) on x_c, the centre: the one-site step of the one-site mode, the site correction of the two-site mode
+    void site_exponential(size_t c, double exponent)
+    {
+        po.check_site_step(c, o.krylov.max_iter, who);
+        po.prepare_one_site(c);
+        book(kx.solve([&](const double* v, double* y) { po.apply_one_site_prepared(v, y); }, po.x[c].size(), po.x[c].buf.get(), exponent, o.krylov));
+        po.invalidate(c);
+    }
+
+    // exp(exponent H_{i,i+1}) on theta = x_i x_{i+1}, then the split: the singular values go to the new centre, no renormalisation
+    void two_site_step(size_t i, double exponent, const SvdOptions& so, bool move_right)
+    {
+        po.check_step(i, o.krylov.max_iter, who);
+        const size_t len = po.two_site_vector(i, theta); // theta_0 = x_i x_{i+1}
+        po.prepare(i);
+        book(kx.solve([&](const double* v, double* y) { po.apply_prepared(v, y); }, len, theta.get(), exponent, o.krylov));
+        po.split_and_advance(i, theta.get(), so, move_right, who);
+        cur = move_right ? i + 1 : i;
+        ++out.stats.two_site_steps;
+    }
+
+    // apply_one_site_bond_correction (mod.rs:702-860) at the centre c towards its neighbour on that side, which becomes the centre
+    void bond_correction(size_t c, bool right, double exponent)
+    {
+        const DevCore& X = po.x[c];
+        DevCore q = right ? sw.factor_left(X) : sw.factor_right(X);
         size_t ka, kb; // the shape of C
-        DevCore q;
-        if (right) { // x_c as (l s) x r is Q C
-            const int rows = (int)(X.l * X.s), R = (int)X.r, k = std::min(rows, R);
-            grow(e, cm, (size_t)k * R);
-            q = DevCore::make(X.l, X.s, (size_t)k);
-            e.qr(X.buf.get(), rows, R, q.buf.get(), cm.get());
-            ka = (size_t)k;
-            kb = (size_t)R;
-        } else { // x_c as l x (s r) is C Q: the QR of its transpose
-            const int L = (int)X.l, rest = (int)(X.s * X.r), k = std::min(L, rest);
-            grow(e, m1, (size_t)rest * L);
-            grow(e, qt, (size_t)rest * k);
-            grow(e, rr, (size_t)k * L);
-            grow(e, cm, (size_t)L * k);
-            transpose_launch(X.buf.get(), L, rest, L, m1.get(), rest, st);
-            e.qr(m1.get(), rest, L, qt.get(), rr.get());
-            q = DevCore::make((size_t)k, X.s, X.r);
-            transpose_launch(qt.get(), rest, k, rest, q.buf.get(), k, st);
-            transpose_launch(rr.get(), k, L, k, cm.get(), L, st); // C = R^T, l x k
-            ka = (size_t)L;
-            kb = (size_t)k;
+        double* C;
+        if (right) { // x_c as (l s) x r is Q C: C is the R of the sweep
+            ka = q.r;
+            kb = X.r;
+            C = sw.rr.get();
+        } else { // x_c as l x (s r) is C Q: the QR of its transpose, C = R^T, l x k
+            ka = X.l;
+            kb = q.l;
+            grow(e, cm, ka * kb);
+            transpose_launch(sw.rr.get(), (int)kb, (int)ka, (int)kb, cm.get(), (int)ka, st);
+            C = cm.get();
         }
         T4A_HIP(hipGetLastError());
         e.sync(); // the old site is released below
@@ -441,8 +415,8 @@ TdvpOneSiteResult tdvp_one_site(Mpo& op, TensorTrain& init, size_t center, const
         po.invalidate(c);
         ++out.stats.qr_steps;
         po.prepare_bond_center(c, right);
-        po.check_bond_center(o.krylov.max_iter, "tdvp_one_site");
-        book(kx.solve([&](const double* v, double* y) { po.apply_bond_center_prepared(v, y); }, ka * kb, cm.get(), exponent, o.krylov));
+        po.check_bond_center(o.krylov.max_iter, who);
+        book(kx.solve([&](const double* v, double* y) { po.apply_bond_center_prepared(v, y); }, ka * kb, C, exponent, o.krylov));
         ++out.stats.bond_corrections;
         // the neighbour absorbs C'; the environment built with Q stays the valid cache entry
         const size_t nb = right ? c + 1 : c - 1;
@@ -451,55 +425,93 @@ TdvpOneSiteResult tdvp_one_site(Mpo& op, TensorTrain& init, size_t center, const
         if (right) {
             nn = DevCore::make(ka, Nb.s, Nb.r);
             const int rest = (int)(Nb.s * Nb.r);
-            gemm_launch(gemm_desc((int)ka, rest, (int)kb, cm.get(), (int)ka, Nb.buf.get(), (int)kb, nn.buf.get(), (int)ka), st);
+            gemm_launch(gemm_desc((int)ka, rest, (int)kb, C, (int)ka, Nb.buf.get(), (int)kb, nn.buf.get(), (int)ka), st);
         } else {
             nn = DevCore::make(Nb.l, Nb.s, kb);
             const int pm = (int)(Nb.l * Nb.s);
-            gemm_launch(gemm_desc(pm, (int)kb, (int)ka, Nb.buf.get(), pm, cm.get(), (int)ka, nn.buf.get(), pm), st);
+            gemm_launch(gemm_desc(pm, (int)kb, (int)ka, Nb.buf.get(), pm, C, (int)ka, nn.buf.get(), pm), st);
         }
         T4A_HIP(hipGetLastError());
         e.sync();
         po.x[nb] = std::move(nn);
         po.invalidate(nb); // keeps L_{c+1} (right) or R_c (left): they do not contain the neighbour
-        return nb;
-    };
+        cur = nb;
+    }
 
+    TdvpResult finish()
+    {
+        e.sync();
+        out.stats.fused_applies = po.fused_applies;
+        out.stats.gemm_applies = po.gemm_applies;
+        out.state = std::make_unique<TensorTrain>(po.x, st);
+        return std::move(out);
+    }
+};
+} // namespace
+
+TdvpResult tdvp(Mpo& op, TensorTrain& init, size_t center, const TdvpOptions& o)
+{
+    o.validate(TdvpMode::TwoSite);
+    tdvp_validate_shapes(op.dims4(), dims3_of(init.cores), center, o.krylov.max_iter);
+    const std::vector<TdvpStep> plan = tdvp_plan(init.cores.size(), center, o.order, o.exponent_step_re);
+    TdvpSweep s(op, init, center, o, "tdvp");
+    const SvdOptions so = sweep_svd_options(o.has_svd_policy, o.svd_policy, o.has_max_bond_dim, o.max_bond_dim);
+    for (size_t sweep = 0; sweep < o.nsweeps; ++sweep) {
+        for (const TdvpStep& t : plan) {
+            if (s.cur != t.nodes[0] && s.cur != t.nodes[1]) { // to the nearest node of the region
+                const size_t d0 = s.cur > t.nodes[0] ? s.cur - t.nodes[0] : t.nodes[0] - s.cur, d1 = s.cur > t.nodes[1] ? s.cur - t.nodes[1] : t.nodes[1] - s.cur;
+                s.move_center(d0 <= d1 ? t.nodes[0] : t.nodes[1]);
+            }
+            if (t.kind == TdvpStepKind::TwoSite) {
+                const size_t i = std::min(t.nodes[0], t.nodes[1]);
+                s.two_site_step(i, t.exponent, so, t.new_center == i + 1);
+            } else {
+                s.site_exponential(t.nodes[0], t.exponent);
+                ++s.out.stats.corrections;
+            }
+        }
+        s.out.sweeps_completed = sweep + 1;
+    }
+    return s.finish();
+}
+
+TdvpResult tdvp_one_site(Mpo& op, TensorTrain& init, size_t center, const TdvpOptions& o)
+{
+    o.validate(TdvpMode::OneSite);
+    tdvp_one_site_validate_shapes(op.dims4(), dims3_of(init.cores), center, o.krylov.max_iter);
+    const size_t n = init.cores.size();
+    const std::vector<TdvpStep> plan = tdvp_one_site_plan(n, center, o.order, o.exponent_step_re);
+    TdvpSweep s(op, init, center, o, "tdvp_one_site");
     for (size_t sweep = 0; sweep < o.nsweeps; ++sweep) {
         for (size_t k = 0; k < plan.size(); ++k) {
-            const TdvpStep& s = plan[k];
-            size_t c = s.nodes[0];
-            move_center(c);
-            po.check_site_step(c, o.krylov.max_iter, "tdvp_one_site");
-            po.prepare_one_site(c);
-            book(kx.solve([&](const double* v, double* y) { po.apply_one_site_prepared(v, y); }, po.x[c].size(), po.x[c].buf.get(), s.exponent, o.krylov));
-            po.invalidate(c);
-            ++out.stats.one_site_steps;
+            const size_t c = plan[k].nodes[0];
+            s.move_center(c);
+            s.site_exponential(c, plan[k].exponent);
+            ++s.out.stats.one_site_steps;
             if (k + 1 < plan.size() && plan[k + 1].nodes[0] != c) {
                 const size_t t = plan[k + 1].nodes[0];
                 const bool right = t > c;
-                if ((k / n) % 2 == 1) { // a reversed substep corrects the last edge of the path (tdvp.hpp)
-                    move_center(right ? t - 1 : t + 1);
-                    c = cur;
-                }
-                cur = bond_correction(c, right, -s.exponent);
+                if ((k / n) % 2 == 1) s.move_center(right ? t - 1 : t + 1); // a reversed substep corrects the last edge of the path (tdvp.hpp)
+                s.bond_correction(s.cur, right, -plan[k].exponent);
             }
         }
-        out.sweeps_completed = sweep + 1;
+        s.out.sweeps_completed = sweep + 1;
     }
-    e.sync();
-    out.stats.fused_applies = po.fused_applies;
-    out.stats.gemm_applies = po.gemm_applies;
-    out.state = std::make_unique<TensorTrain>(po.x, st);
-    return out;
+    return s.finish();
+}
+
+TdvpResult tdvp(TdvpMode mode, Mpo& op, TensorTrain& init, size_t center, const TdvpOptions& o)
+{
+    return mode == TdvpMode::TwoSite ? tdvp(op, init, center, o) : tdvp_one_site(op, init, center, o);
 }
 
 // ------------------------------------------------------------------------------------------------ test hooks
 BondApplyRoute tdvp_bond_apply_host(const double* L, const double* R, const double* C, size_t ka, size_t kb, size_t W, BondApplyRoute route, double* out)
 {
-    route = resolve_bond_route(route, ka, kb, W);
     if (route == BondApplyRoute::Fused && !tdvp_bond_apply_fused_admits(ka, kb, W))
         throw Error(T4A_GPU_INVALID_ARGUMENT, "tdvp_bond_apply: the fused launch holds 16 W k_b doubles in the LDS: W k_b must be at most " +
                                                   std::to_string(TDVP_BOND_FUSED_MAX_PANEL));
+    route = resolve_bond_route(route, ka, kb, W);
     Engine e;
     hipStream_t st = e.stream();
     DevBuf<double> dL = upload_vector(st, L, ka * W * ka), dR = upload_vector(st, R, kb * W * kb), dC = upload_vector(st, C, ka * kb), dT, dY;

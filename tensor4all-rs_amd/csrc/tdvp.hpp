@@ -1,24 +1,33 @@
-// tdvp.hpp — two-site TDVP on the device: a tensor train evolved under an MPO H by sweeps of projected exponentials, tensor4all-treetn's
-// tdvp / tdvp_with_treetn_operator (crates/tensor4all-treetn/src/tdvp/mod.rs:1107-1268, update_two_site :916-1042, the site correction
-// :639-700, the full-rank centre move :1318-1390, the region plan tdvp/plan.rs:41-181) on the Hermitian Krylov exponential of
-// tensor4all-core (krylov.rs:693-926), restated for what square_linsolve and dmrg cover: a chain, f64, one site index per node,
-// V_in = V_out (every site of H has s1 == s2 == the state's site dimension; the dimensions may differ from site to site).  Trees, index
-// mappings and verbose output stay out.
+// tdvp.hpp — TDVP on the device in two modes, two-site (tdvp) and one-site (tdvp_one_site): a tensor train evolved under an MPO H by sweeps
+// of projected exponentials, tensor4all-treetn's tdvp / tdvp_with_treetn_operator (crates/tensor4all-treetn/src/tdvp/mod.rs:1107-1268,
+// update_two_site :916-1042, the site correction :639-700, the one-site update and its bond correction :639-914, the full-rank centre move
+// :1318-1390, the region plan tdvp/plan.rs:41-181) on the Hermitian Krylov exponential of tensor4all-core (krylov.rs:693-926), restated
+// for what square_linsolve and dmrg cover: a chain, f64, one site index per node, V_in = V_out (every site of H has s1 == s2 == the
+// state's site dimension; the dimensions may differ from site to site).  Trees, index mappings and verbose output stay out.
 //
-// Deviations from the reference, both refused on the host with INVALID_ARGUMENT before the device is touched:
+// The shared core.  Both modes are one driver with two thin loops (tdvp.hip): one validator of TdvpOptions that takes the mode the
+// caller requires (TdvpMode), one expansion of a base sweep over tdvp_sub_steps, one TdvpResult, and one sweep context that owns the
+// projected operator, the QR sweep, the Krylov exponential, the centre and the result and provides the steps — the centre move by
+// full-rank thin QR steps, the site exponential (the two-site mode's site correction and the one-site mode's site step are this one
+// function), the two-site step, the bond correction, the epilogue.  A mode is its base plan, its shape checks and its loop over the plan.
+//
+// Deviations from the reference that both modes share, refused on the host with INVALID_ARGUMENT before the device is touched:
 //   * The exponent is REAL.  The reference's exponent_step is complex with the default -0.1i; this code base has no complex scalars, so
 //     the options carry exponent_step_re (default -0.1) and exponent_step_im, and a non-zero imaginary part is refused: real-time
 //     evolution needs complex trains.  u' = -H u (heat and diffusion flows, imaginary-time relaxation) is what a real exponent covers.
+// Deviations of the two-site mode, refused in the same way:
 //   * `center` must be 0 or n - 1.  The reference's two-site plan walks root-edge-first DFS edges; from an inner root of a chain it runs
 //     one arm to its leaf, applies the site correction at that leaf and jumps to the other arm, while the projector splitting needs that
 //     correction at the root (DESIGN.md §8 has the measured errors).  From an end the plan is the standard 2TDVP sweep.
 //   * tdvp refuses nsite = 1: one-site TDVP has entry points of its own, tdvp_one_site_plan and tdvp_one_site below.
+// The deviations of the one-site mode stand with tdvp_one_site below.
 //
 // The projected operator, its cached environments, the half operators, the QR canonicalisation and the SVD split are those of
 // linsolve.hpp.  A two-site step at bond (i, i+1): theta_0 = x_i x_{i+1}, prepare(i), KrylovExpm with the step's exponent, tensor_svd
-// (no renormalisation), the singular values into the new centre.  A correction step at site c: prepare_one_site(c), KrylovExpm with
-// minus the step's exponent on x_c, the result replaces x_c.  Both orthogonalisation passes of the Krylov basis are classical
-// Gram–Schmidt (the deviation of Gmres and Lanczos); their projections come from gs_dots_wide where krylov_dots_route says so.
+// (no renormalisation), the singular values into the new centre.  A site exponential at site c: prepare_one_site(c), KrylovExpm with
+// the step's exponent on x_c (minus tau for the correction of the two-site mode), the result replaces x_c.  Both orthogonalisation
+// passes of the Krylov basis are classical Gram–Schmidt (the deviation of Gmres and Lanczos); their projections come from gs_dots_wide
+// where krylov_dots_route says so.
 #pragma once
 
 #include "dmrg.hpp"
@@ -77,6 +86,7 @@ std::vector<TdvpStep> tdvp_plan(size_t n, size_t center, size_t order, double ta
 std::vector<TdvpStep> tdvp_one_site_plan(size_t n, size_t center, size_t order, double tau);
 
 // ---- TdvpOptions, TdvpResult of the reference
+enum class TdvpMode : int { OneSite = 1, TwoSite = 2 }; // the driver a caller is about to run; its value is the nsite it requires
 struct TdvpOptions {
     size_t nsite = 2, nsweeps = 1, order = 2;
     double exponent_step_re = -0.1, exponent_step_im = 0.0;
@@ -85,14 +95,18 @@ struct TdvpOptions {
     bool has_svd_policy = false; // none: the default policy tensor_svd applies
     SvdPolicy svd_policy;
     KrylovExpmOptions krylov;
-    void validate() const; // INVALID_ARGUMENT (host only); the rules of tdvp (nsite = 1 is refused: see tdvp_one_site)
-    // The rules of tdvp_one_site, in the order of the reference's validate_options (mod.rs:1270-1316): nsite != 1 (this project's message,
-    // naming tdvp for nsite = 2), nsweeps, order, the exponent finite and real, max_bond_dim == 0 when set, then "invalid TDVP option
-    // max_bond_dim: one-site TDVP has fixed ranks; use nsite=2 for truncation" and the same for svd_policy, then the Krylov options.
-    void validate_one_site() const;
+    // INVALID_ARGUMENT (host only), the first rule that is broken.  TwoSite, the rules of tdvp: nsite outside {1, 2}, nsweeps, order, the
+    // exponent finite, max_bond_dim == 0 when set, nsite == 1 (refused: see tdvp_one_site), the exponent real, the Krylov options, the
+    // SVD policy.  OneSite, the rules of tdvp_one_site in the order of the reference's validate_options (mod.rs:1270-1316): nsite != 1
+    // (this project's message, naming tdvp for nsite = 2), nsweeps, order, the exponent finite and real, max_bond_dim == 0 when set, then
+    // "invalid TDVP option max_bond_dim: one-site TDVP has fixed ranks; use nsite=2 for truncation" and the same for svd_policy, then the
+    // Krylov options.
+    void validate(TdvpMode mode) const;
 };
+// The counters of both modes: a mode leaves those of the other at zero (qr_steps, the centre moves, is counted in both).
 struct TdvpStats {
-    size_t two_site_steps = 0, corrections = 0, krylov_steps = 0, apply_calls = 0, max_time_splits = 0;
+    size_t two_site_steps = 0, corrections = 0, one_site_steps = 0, bond_corrections = 0, qr_steps = 0, krylov_steps = 0, apply_calls = 0, max_time_splits = 0,
+           fused_applies = 0, gemm_applies = 0;
 };
 struct TdvpResult {
     std::unique_ptr<TensorTrain> state;
@@ -128,21 +142,15 @@ TdvpResult tdvp(Mpo& op, TensorTrain& init, size_t center, const TdvpOptions& op
 //     Here a reversed substep first moves the centre to the neighbour of the next node and corrects the LAST edge of the path: the exact
 //     mirror image of the post-order substep, exact at full bonds from every centre.  Paths of one edge — every step from an end centre,
 //     and every step but the jump from an inner one — are the reference's.
-struct TdvpOneSiteStats {
-    size_t one_site_steps = 0, bond_corrections = 0, qr_steps = 0, krylov_steps = 0, apply_calls = 0, max_time_splits = 0, fused_applies = 0, gemm_applies = 0;
-};
-struct TdvpOneSiteResult {
-    std::unique_ptr<TensorTrain> state;
-    size_t sweeps_completed = 0, local_updates = 0;
-    double max_error_estimate = 0.0;
-    size_t max_krylov_iterations = 0;
-    TdvpOneSiteStats stats;
-};
 // The shape checks on the host (INVALID_ARGUMENT): the shared chain checks of validate_chain_operands (a single site is refused with a
 // message of its own: they need two), center >= n, and a one-site step or a bond-centre step whose work buffers would hold more than
 // INT_MAX elements (the message names the site or the bond).
 void tdvp_one_site_validate_shapes(const std::vector<std::array<size_t, 4>>& op, const std::vector<std::array<size_t, 3>>& state, size_t center, size_t max_iter);
-TdvpOneSiteResult tdvp_one_site(Mpo& op, TensorTrain& init, size_t center, const TdvpOptions& options);
+TdvpResult tdvp_one_site(Mpo& op, TensorTrain& init, size_t center, const TdvpOptions& options);
+
+// For callers that carry the mode as a value (GSE-TDVP, the C ABI): the shape checks and the driver of that mode.
+void tdvp_validate_shapes(TdvpMode mode, const std::vector<std::array<size_t, 4>>& op, const std::vector<std::array<size_t, 3>>& state, size_t center, size_t max_iter);
+TdvpResult tdvp(TdvpMode mode, Mpo& op, TensorTrain& init, size_t center, const TdvpOptions& options);
 
 // ---- the bond-centre apply (kernels_tdvp.hip, tdvp.hip; its environments: ProjectedOperator::prepare_bond_center).  Fused: tdvp_bond_apply_kernel, one launch, inside its envelope
 // W k_b <= TDVP_BOND_FUSED_MAX_PANEL (16 W k_b doubles of LDS).  Gemm: T = La_view C with La read as (k_a W) x k_a, then Y = T_view Rb_view^T

@@ -30,10 +30,8 @@ std::vector<double> to_host(Engine& eng, const double* d_src, size_t count)
     return h;
 }
 
-void QrSweep::right_step(std::vector<DevCore>& cores, size_t i)
+DevCore QrSweep::factor_right(const DevCore& c)
 {
-    DevCore& c = cores[i];
-    DevCore& p = cores[i - 1];
     const int L = (int)c.l, rest = (int)(c.s * c.r);
     const int k = std::min(L, rest);
     grow(eng, m1, (size_t)rest * L);
@@ -43,6 +41,25 @@ void QrSweep::right_step(std::vector<DevCore>& cores, size_t i)
     eng.qr(m1.get(), rest, L, q.get(), rr.get());
     DevCore nc = DevCore::make(k, c.s, c.r);
     transpose_launch(q.get(), rest, k, rest, nc.buf.get(), k, st);
+    return nc;
+}
+
+DevCore QrSweep::factor_left(const DevCore& c)
+{
+    const int rows = (int)(c.l * c.s), R = (int)c.r;
+    const int k = std::min(rows, R);
+    grow(eng, rr, (size_t)k * R);
+    DevCore nc = DevCore::make(c.l, c.s, k);
+    eng.qr(c.buf.get(), rows, R, nc.buf.get(), rr.get());
+    return nc;
+}
+
+void QrSweep::right_step(std::vector<DevCore>& cores, size_t i)
+{
+    DevCore& c = cores[i];
+    DevCore& p = cores[i - 1];
+    DevCore nc = factor_right(c);
+    const int L = (int)c.l, k = (int)nc.l;
     DevCore np = DevCore::make(p.l, p.s, k);
     const int pm = (int)(p.l * p.s);
     GemmDesc g = gemm_desc(pm, k, L, p.buf.get(), pm, rr.get(), k, np.buf.get(), pm);
@@ -58,11 +75,8 @@ void QrSweep::left_step(std::vector<DevCore>& cores, size_t i)
 {
     DevCore& c = cores[i];
     DevCore& nx = cores[i + 1];
-    const int rows = (int)(c.l * c.s), R = (int)c.r;
-    const int k = std::min(rows, R);
-    grow(eng, rr, (size_t)k * R);
-    DevCore nc = DevCore::make(c.l, c.s, k);
-    eng.qr(c.buf.get(), rows, R, nc.buf.get(), rr.get());
+    DevCore nc = factor_left(c);
+    const int R = (int)c.r, k = (int)nc.r;
     DevCore nn = DevCore::make(k, nx.s, nx.r);
     const int rest = (int)(nx.s * nx.r);
     gemm_launch(gemm_desc(k, rest, R, rr.get(), k, nx.buf.get(), R, nn.buf.get(), k), st); // R (k x R) * next (R x s r)

@@ -52,11 +52,17 @@ std::vector<double> to_host(Engine& eng, const double* d_src, size_t count);
 // QR sweeps with the thin Householder QR (right_canonicalize, canonical.rs:35-89).  right_step: site i becomes Q^T of its transposed
 // l x (s r) matricisation (k = min(l, s r) rows) and R^T goes into its left neighbour; left_step: site i becomes Q of its (l s) x r
 // matricisation and R goes into its right neighbour.  Each step ends synced, since it releases the two old cores.
+// A step is its factorising half followed by the absorbing GEMM.  The factorising halves, for callers that do something of their own
+// with the triangular factor (the bond correction of one-site TDVP): factor_left -> Q as the core (l, s, k) and R (k x r) in rr;
+// factor_right -> Q^T as the core (k, s, r) and R (k x l, its transpose is the factor to the left of Q^T) in rr.  They sync nothing and
+// leave `c` as it is; rr holds the factor until the next step of this sweep.
 struct QrSweep {
     Engine& eng;
     hipStream_t st;
     DevBuf<double> m1, q, rr;
     explicit QrSweep(Engine& e) : eng(e), st(e.stream()) {}
+    DevCore factor_right(const DevCore& c);
+    DevCore factor_left(const DevCore& c);
     void right_step(std::vector<DevCore>& cores, size_t i);
     void left_step(std::vector<DevCore>& cores, size_t i);
     // sites < center from the left, then sites > center from the right

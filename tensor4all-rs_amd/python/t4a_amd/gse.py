@@ -149,38 +149,33 @@ def global_subspace_expand(operator, init, center=0, options=None):
     return _result(h, counters)
 
 
-def gse_tdvp(operator, init, center=0, options=None):
-    """gse_tdvp (gse.rs:374-424) -> GseTdvpResult: before sweep s an expansion when ``krylov_dim > 0 and (s > 0 or
-    expand_before_first_sweep)``, then ``tdvp`` with ``nsweeps = 1``.  tdvp's own refusals apply unchanged (``nsite = 1`` is
-    ``gse_tdvp_one_site``)."""
+def _gse_tdvp(fn, who, default_nsite, operator, init, center, options):
+    """The driver ``fn`` (t4a_gpu_gse_tdvp or t4a_gpu_gse_tdvp_one_site) -> GseTdvpResult"""
     _operands(operator, init)
-    o = GseTdvpOptions() if options is None else options
+    o = GseTdvpOptions(tdvp=TdvpOptions(nsite=default_nsite)) if options is None else options
     if not isinstance(o, GseTdvpOptions) or not isinstance(o.tdvp, TdvpOptions):
-        raise T4aError(INVALID_ARGUMENT, "gse_tdvp: options must be a GseTdvpOptions of a GseOptions and a TdvpOptions")
+        raise T4aError(INVALID_ARGUMENT, who + ": options must be a GseTdvpOptions of a GseOptions and a TdvpOptions")
     g, t = _options(o.gse), o.tdvp.to_c()
     c = _center(center)
     h = c_void_p()
     sweeps, updates, expansions, err, iters = c_size_t(0), c_size_t(0), c_size_t(0), c_double(0.0), c_size_t(0)
-    _check(_lib.t4a_gpu_gse_tdvp(operator._h, init._h, c, ctypes.byref(g), ctypes.byref(t), ctypes.byref(h), ctypes.byref(sweeps), ctypes.byref(updates),
-                                 ctypes.byref(expansions), ctypes.byref(err), ctypes.byref(iters)))
+    _check(fn(operator._h, init._h, c, ctypes.byref(g), ctypes.byref(t), ctypes.byref(h), ctypes.byref(sweeps), ctypes.byref(updates), ctypes.byref(expansions),
+              ctypes.byref(err), ctypes.byref(iters)))
     return GseTdvpResult(SimpleTensorTrain._adopt(h), sweeps.value, updates.value, expansions.value, err.value, iters.value)
+
+
+def gse_tdvp(operator, init, center=0, options=None):
+    """gse_tdvp (gse.rs:374-424) -> GseTdvpResult: before sweep s an expansion when ``krylov_dim > 0 and (s > 0 or
+    expand_before_first_sweep)``, then ``tdvp`` with ``nsweeps = 1``.  tdvp's own refusals apply unchanged (``nsite = 1`` is
+    ``gse_tdvp_one_site``)."""
+    return _gse_tdvp(_lib.t4a_gpu_gse_tdvp, "gse_tdvp", 2, operator, init, center, options)
 
 
 def gse_tdvp_one_site(operator, init, center=0, options=None):
     """The loop of ``gse_tdvp`` with ``tdvp_one_site`` for the one-sweep evolution after each expansion -> GseTdvpResult: the expansion
     grows the bonds globally, the fixed-rank integrator evolves inside them.  Any ``center``.  ``options`` defaults to a GseTdvpOptions
     whose ``tdvp`` has ``nsite = 1``; the refusals are those of the expansion and of ``tdvp_one_site``."""
-    _operands(operator, init)
-    o = GseTdvpOptions(tdvp=TdvpOptions(nsite=1)) if options is None else options
-    if not isinstance(o, GseTdvpOptions) or not isinstance(o.tdvp, TdvpOptions):
-        raise T4aError(INVALID_ARGUMENT, "gse_tdvp_one_site: options must be a GseTdvpOptions of a GseOptions and a TdvpOptions")
-    g, t = _options(o.gse), o.tdvp.to_c()
-    c = _center(center)
-    h = c_void_p()
-    sweeps, updates, expansions, err, iters = c_size_t(0), c_size_t(0), c_size_t(0), c_double(0.0), c_size_t(0)
-    _check(_lib.t4a_gpu_gse_tdvp_one_site(operator._h, init._h, c, ctypes.byref(g), ctypes.byref(t), ctypes.byref(h), ctypes.byref(sweeps),
-                                          ctypes.byref(updates), ctypes.byref(expansions), ctypes.byref(err), ctypes.byref(iters)))
-    return GseTdvpResult(SimpleTensorTrain._adopt(h), sweeps.value, updates.value, expansions.value, err.value, iters.value)
+    return _gse_tdvp(_lib.t4a_gpu_gse_tdvp_one_site, "gse_tdvp_one_site", 1, operator, init, center, options)
 
 
 def _project(refs, basis, orient=0, route=ROUTE_FUSED):

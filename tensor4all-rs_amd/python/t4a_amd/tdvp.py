@@ -109,33 +109,43 @@ class TdvpResult:
         self.stats = stats
 
 
+def _run(fn, stats_cls, who, default_nsite, operator, init, center, options):
+    """The driver ``fn`` (t4a_gpu_tdvp or t4a_gpu_tdvp_one_site) with its stats struct -> TdvpResult"""
+    _operands(operator, init)
+    if int(center) < 0:
+        raise T4aError(INVALID_ARGUMENT, who + ": center must not be negative")
+    o = (TdvpOptions(nsite=default_nsite) if options is None else options).to_c()
+    h = c_void_p()
+    sweeps, updates, err, iters = c_size_t(0), c_size_t(0), c_double(0.0), c_size_t(0)
+    stats = stats_cls()
+    _check(fn(operator._h, init._h, c_size_t(int(center)), ctypes.byref(o), ctypes.byref(h), ctypes.byref(sweeps), ctypes.byref(updates), ctypes.byref(err),
+              ctypes.byref(iters), ctypes.byref(stats)))
+    return TdvpResult(SimpleTensorTrain._adopt(h), sweeps.value, updates.value, err.value, iters.value,
+                      {name: getattr(stats, name) for name, _ in stats_cls._fields_})
+
+
+def _plan(fn, n, center, order, tau):
+    """The plan entry ``fn``: the count-only call, then the arrays -> [(kind, both nodes, new_center, exponent)]"""
+    count = c_size_t(0)
+    args = (c_size_t(int(n)), c_size_t(int(center)), c_size_t(int(order)), c_double(float(tau)))
+    _check(fn(*args, c_size_t(0), None, None, None, None, ctypes.byref(count)))
+    k = count.value
+    kinds, nodes, centers, exps = np.zeros(max(k, 1), dtype=np.int32), np.zeros(2 * max(k, 1), dtype=np.uintp), np.zeros(max(k, 1), dtype=np.uintp), np.zeros(max(k, 1))
+    _check(fn(*args, c_size_t(k), _p(kinds), _p(nodes), _p(centers), _p(exps), ctypes.byref(count)))
+    return [(int(kinds[j]), (int(nodes[2 * j]), int(nodes[2 * j + 1])), int(centers[j]), float(exps[j])) for j in range(k)]
+
+
 def tdvp(operator, init, center=0, options=None):
     """Two-site TDVP: ``nsweeps`` sweeps of exp(exponent_step * operator) on ``init`` from ``center`` (0 or n - 1) (tdvp/mod.rs:1107-1217)
     -> TdvpResult.  The state is not renormalised.  ``nsite = 1`` is refused here: see ``tdvp_one_site``."""
-    _operands(operator, init)
-    if int(center) < 0:
-        raise T4aError(INVALID_ARGUMENT, "tdvp: center must not be negative")
-    o = (TdvpOptions() if options is None else options).to_c()
-    h = c_void_p()
-    sweeps, updates, err, iters = c_size_t(0), c_size_t(0), c_double(0.0), c_size_t(0)
-    stats = TdvpStatsC()
-    _check(_lib.t4a_gpu_tdvp(operator._h, init._h, c_size_t(int(center)), ctypes.byref(o), ctypes.byref(h), ctypes.byref(sweeps), ctypes.byref(updates),
-                             ctypes.byref(err), ctypes.byref(iters), ctypes.byref(stats)))
-    return TdvpResult(SimpleTensorTrain._adopt(h), sweeps.value, updates.value, err.value, iters.value,
-                      {name: getattr(stats, name) for name, _ in TdvpStatsC._fields_})
+    return _run(_lib.t4a_gpu_tdvp, TdvpStatsC, "tdvp", 2, operator, init, center, options)
 
 
 def tdvp_plan(n, center, order, tau):
     """The region plan of one sweep (t4a_gpu_tdvp_plan, host only) -> [(kind, nodes, new_center, exponent)], nodes a tuple of two sites
     for a two-site step (the other node, the new centre) and of one for a site correction."""
-    count = c_size_t(0)
-    args = (c_size_t(int(n)), c_size_t(int(center)), c_size_t(int(order)), c_double(float(tau)))
-    _check(_lib.t4a_gpu_tdvp_plan(*args, c_size_t(0), None, None, None, None, ctypes.byref(count)))
-    k = count.value
-    kinds, nodes, centers, exps = np.zeros(max(k, 1), dtype=np.int32), np.zeros(2 * max(k, 1), dtype=np.uintp), np.zeros(max(k, 1), dtype=np.uintp), np.zeros(max(k, 1))
-    _check(_lib.t4a_gpu_tdvp_plan(*args, c_size_t(k), _p(kinds), _p(nodes), _p(centers), _p(exps), ctypes.byref(count)))
-    return [(int(kinds[j]), (int(nodes[2 * j]), int(nodes[2 * j + 1])) if kinds[j] == TWO_SITE else (int(nodes[2 * j]),), int(centers[j]), float(exps[j]))
-            for j in range(k)]
+    return [(kind, nodes if kind == TWO_SITE else nodes[:1], new_center, exponent)
+            for kind, nodes, new_center, exponent in _plan(_lib.t4a_gpu_tdvp_plan, n, center, order, tau)]
 
 
 def tdvp_one_site(operator, init, center=0, options=None):
@@ -143,29 +153,13 @@ def tdvp_one_site(operator, init, center=0, options=None):
     from any ``center`` with every bond dimension fixed -> TdvpResult, whose ``stats`` count one-site steps, bond corrections, QR steps,
     Krylov steps, applies, time splits and the bond-centre applies by route.  ``options`` defaults to ``TdvpOptions(nsite=1)``;
     ``max_bond_dim`` and ``svd_policy`` are refused (fixed ranks).  ``local_updates`` counts site and bond solves, w (2n - 1) per sweep."""
-    _operands(operator, init)
-    if int(center) < 0:
-        raise T4aError(INVALID_ARGUMENT, "tdvp_one_site: center must not be negative")
-    o = (TdvpOptions(nsite=1) if options is None else options).to_c()
-    h = c_void_p()
-    sweeps, updates, err, iters = c_size_t(0), c_size_t(0), c_double(0.0), c_size_t(0)
-    stats = TdvpOneSiteStatsC()
-    _check(_lib.t4a_gpu_tdvp_one_site(operator._h, init._h, c_size_t(int(center)), ctypes.byref(o), ctypes.byref(h), ctypes.byref(sweeps),
-                                      ctypes.byref(updates), ctypes.byref(err), ctypes.byref(iters), ctypes.byref(stats)))
-    return TdvpResult(SimpleTensorTrain._adopt(h), sweeps.value, updates.value, err.value, iters.value,
-                      {name: getattr(stats, name) for name, _ in TdvpOneSiteStatsC._fields_})
+    return _run(_lib.t4a_gpu_tdvp_one_site, TdvpOneSiteStatsC, "tdvp_one_site", 1, operator, init, center, options)
 
 
 def tdvp_one_site_plan(n, center, order, tau):
     """The one-site plan of one sweep (t4a_gpu_tdvp_one_site_plan, host only) -> [(ONE_SITE, (node,), node, exponent)]: post order from
     ``center``, the left arm leaf first, every even substep reversed."""
-    count = c_size_t(0)
-    args = (c_size_t(int(n)), c_size_t(int(center)), c_size_t(int(order)), c_double(float(tau)))
-    _check(_lib.t4a_gpu_tdvp_one_site_plan(*args, c_size_t(0), None, None, None, None, ctypes.byref(count)))
-    k = count.value
-    kinds, nodes, centers, exps = np.zeros(max(k, 1), dtype=np.int32), np.zeros(2 * max(k, 1), dtype=np.uintp), np.zeros(max(k, 1), dtype=np.uintp), np.zeros(max(k, 1))
-    _check(_lib.t4a_gpu_tdvp_one_site_plan(*args, c_size_t(k), _p(kinds), _p(nodes), _p(centers), _p(exps), ctypes.byref(count)))
-    return [(int(kinds[j]), (int(nodes[2 * j]),), int(centers[j]), float(exps[j])) for j in range(k)]
+    return [(kind, nodes[:1], new_center, exponent) for kind, nodes, new_center, exponent in _plan(_lib.t4a_gpu_tdvp_one_site_plan, n, center, order, tau)]
 
 
 def _apply_bond_center(left, right, c, route=BOND_AUTO):

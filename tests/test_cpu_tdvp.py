@@ -228,22 +228,60 @@ BAD_OPTIONS = ([("nsite", 3, "TDVP supports nsite=1 or nsite=2 in this version, 
                + _tolerance_refusals("krylov.hermitian_tol", "hermitian_krylov_expm_multiply: hermitian_tol must be finite and non-negative"))
 
 
-@pytest.mark.parametrize("field, value, message", BAD_OPTIONS, ids=["%s=%s" % (f, v) for f, v, _ in BAD_OPTIONS])
-def test_bad_options_are_refused_before_an_operand_is_looked_at(field, value, message):
-    """The operands are NULL: an answer other than INVALID_ARGUMENT would mean they were looked at first."""
+# Two violations at once: the message of the rule that comes first in the validator wins.  The order of tdvp: nsite outside {1, 2},
+# nsweeps, order, the exponent finite, max_bond_dim == 0, nsite == 1, the exponent real, the Krylov options (max_iter, max_time_splits,
+# tol, breakdown_tol, hermitian_tol), the SVD policy.  Every adjacent pair, the pairs tdvp_one_site orders the other way round (the real
+# exponent against max_bond_dim == 0, the Krylov options against the SVD policy) and both nsite rules against every other rule.
+_R = {"nsite3": (("nsite", 3), "TDVP supports nsite=1 or nsite=2 in this version, got nsite=3"),
+      "nsweeps": (("nsweeps", 0), "invalid TDVP option nsweeps: must be greater than zero"),
+      "order": (("order", 3), "TDVP applyexp order 3 is not supported; supported orders are 1, 2, and 4"),
+      "finite": (("exponent_step_re", NAN), "invalid TDVP option exponent_step: real and imaginary parts must be finite"),
+      "bond0": (("max_bond_dim", 0), "invalid TDVP option max_bond_dim: must be greater than zero when set"),
+      "nsite1": (("nsite", 1), "tdvp: one-site TDVP (nsite=1) is not implemented here"),
+      "real": (("exponent_step_im", -0.1), "tdvp: exponent_step must be real here"),
+      "max_iter": (("krylov.max_iter", 0), "hermitian_krylov_expm_multiply: max_iter must be greater than zero"),
+      "splits": (("krylov.max_time_splits", 0), "hermitian_krylov_expm_multiply: max_time_splits must be greater than zero"),
+      "tol": (("krylov.tol", NAN), "hermitian_krylov_expm_multiply: tol must be finite and non-negative"),
+      "breakdown": (("krylov.breakdown_tol", -1.0), "hermitian_krylov_expm_multiply: breakdown_tol must be finite and non-negative"),
+      "hermitian": (("krylov.hermitian_tol", INF), "hermitian_krylov_expm_multiply: hermitian_tol must be finite and non-negative"),
+      "policy": (("svd_policy.threshold", NAN), "Invalid SVD truncation threshold: threshold must be finite and non-negative")}
+_ORDER = ["nsite3", "nsweeps", "order", "finite", "bond0", "nsite1", "real", "max_iter", "splits", "tol", "breakdown", "hermitian", "policy"]
+# (the winner, the loser)
+BAD_PAIRS = (list(zip(_ORDER, _ORDER[1:])) + [("finite", "real"), ("bond0", "real"), ("max_iter", "policy"), ("real", "policy")]
+             + [("nsite3", r) for r in _ORDER[2:] if r != "nsite1"]
+             + [(r, "nsite1") for r in ("nsweeps", "order", "finite")] + [("nsite1", r) for r in _ORDER[7:]])
+CASES = [([(f, v)], m) for f, v, m in BAD_OPTIONS] + [([_R[a][0], _R[b][0]], _R[a][1]) for a, b in BAD_PAIRS]
+CASE_IDS = ["%s=%s" % (f, v) for f, v, _ in BAD_OPTIONS] + ["%s-beats-%s" % p for p in BAD_PAIRS]
+
+
+def set_option(o, field, value):
+    if field == "max_bond_dim":
+        o.has_max_bond_dim = 1
+    if field.startswith("svd_policy."):
+        o.has_svd_policy = 1
+    if "." in field:
+        setattr(getattr(o, field.split(".")[0]), field.split(".")[1], value)
+    else:
+        setattr(o, field, value)
+
+
+@pytest.mark.parametrize("settings, message", CASES, ids=CASE_IDS)
+def test_bad_options_are_refused_before_an_operand_is_looked_at(settings, message):
+    """The operands are NULL: an answer other than INVALID_ARGUMENT would mean they were looked at first.  With two bad options the
+    message is that of the rule the validator checks first."""
     import t4a_amd
     o = t4a_amd.TdvpOptionsC()
     t4a_amd._lib.t4a_gpu_tdvp_options_default(ctypes.byref(o))
-    if field == "max_bond_dim":
-        o.has_max_bond_dim = 1
-    if field.startswith("krylov."):
-        setattr(o.krylov, field.split(".")[1], value)
-    else:
-        setattr(o, field, value)
+    for field, value in settings:
+        set_option(o, field, value)
     h = ctypes.c_void_p()
     st = t4a_amd._lib.t4a_gpu_tdvp(None, None, ctypes.c_size_t(0), ctypes.byref(o), ctypes.byref(h), None, None, None, None, None)
     assert st == t4a_amd.INVALID_ARGUMENT, t4a_amd.last_error_message()
     assert not h and message in t4a_amd.last_error_message()
+    g = t4a_amd.GseOptionsC()
+    assert t4a_amd._lib.t4a_gpu_gse_options_default(ctypes.byref(g)) == 0
+    st = t4a_amd._lib.t4a_gpu_gse_tdvp(None, None, ctypes.c_size_t(0), ctypes.byref(g), ctypes.byref(o), ctypes.byref(h), None, None, None, None, None)
+    assert st == t4a_amd.INVALID_ARGUMENT and not h and message in t4a_amd.last_error_message()
 
 
 def check_shapes(op, state, center=0, max_iter=30):

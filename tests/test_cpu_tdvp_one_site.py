@@ -184,17 +184,44 @@ BAD_OPTIONS = [("nsite", 2, "tdvp_one_site: one-site TDVP requires nsite=1, got 
                ("krylov.tol", -1e-3, "hermitian_krylov_expm_multiply: tol must be finite and non-negative")]
 
 
-@pytest.mark.parametrize("field, value, message", BAD_OPTIONS, ids=["%s=%s" % (f, v) for f, v, _ in BAD_OPTIONS])
-def test_bad_options_are_refused_before_an_operand_is_looked_at(field, value, message):
-    """The operands are NULL: an answer other than INVALID_ARGUMENT would mean they were looked at first."""
+# Two violations at once: the message of the rule that comes first in the validator wins.  The order of tdvp_one_site: nsite != 1,
+# nsweeps, order, the exponent finite, the exponent real, max_bond_dim == 0, max_bond_dim set, svd_policy set, the Krylov options
+# (max_iter, max_time_splits, tol, breakdown_tol, hermitian_tol).  Every adjacent pair, the pairs tdvp orders the other way round (the real
+# exponent against max_bond_dim == 0, the SVD policy against the Krylov options) and the nsite rule against every other rule.
+_R = {"nsite": (("nsite", 2), "tdvp_one_site: one-site TDVP requires nsite=1, got nsite=2; nsite=2 is tdvp"),
+      "nsweeps": (("nsweeps", 0), "invalid TDVP option nsweeps: must be greater than zero"),
+      "order": (("order", 3), "TDVP applyexp order 3 is not supported; supported orders are 1, 2, and 4"),
+      "finite": (("exponent_step_re", NAN), "invalid TDVP option exponent_step: real and imaginary parts must be finite"),
+      "real": (("exponent_step_im", -0.1), "tdvp_one_site: exponent_step must be real here"),
+      "bond0": (("max_bond_dim", 0), "invalid TDVP option max_bond_dim: must be greater than zero when set"),
+      "bond": (("max_bond_dim", 8), "invalid TDVP option max_bond_dim: one-site TDVP has fixed ranks; use nsite=2 for truncation"),
+      "policy": (("has_svd_policy", 1), "invalid TDVP option svd_policy: one-site TDVP has fixed ranks; use nsite=2 for truncation"),
+      "max_iter": (("krylov.max_iter", 0), "hermitian_krylov_expm_multiply: max_iter must be greater than zero"),
+      "splits": (("krylov.max_time_splits", 0), "hermitian_krylov_expm_multiply: max_time_splits must be greater than zero"),
+      "tol": (("krylov.tol", NAN), "hermitian_krylov_expm_multiply: tol must be finite and non-negative"),
+      "breakdown": (("krylov.breakdown_tol", -1.0), "hermitian_krylov_expm_multiply: breakdown_tol must be finite and non-negative"),
+      "hermitian": (("krylov.hermitian_tol", float("inf")), "hermitian_krylov_expm_multiply: hermitian_tol must be finite and non-negative")}
+_ORDER = ["nsite", "nsweeps", "order", "finite", "real", "bond0", "bond", "policy", "max_iter", "splits", "tol", "breakdown", "hermitian"]
+# (the winner, the loser); bond0 and bond set the same field, so bond0 meets its next neighbour, policy
+BAD_PAIRS = ([(a, b) for a, b in zip(_ORDER, _ORDER[1:]) if (a, b) != ("bond0", "bond")] + [("bond0", "policy"), ("real", "bond"), ("finite", "bond0")]
+             + [("nsite", r) for r in _ORDER[2:]])
+CASES = [([(f, v)], m) for f, v, m in BAD_OPTIONS] + [([_R[a][0], _R[b][0]], _R[a][1]) for a, b in BAD_PAIRS]
+CASE_IDS = ["%s=%s" % (f, v) for f, v, _ in BAD_OPTIONS] + ["%s-beats-%s" % p for p in BAD_PAIRS]
+
+
+@pytest.mark.parametrize("settings, message", CASES, ids=CASE_IDS)
+def test_bad_options_are_refused_before_an_operand_is_looked_at(settings, message):
+    """The operands are NULL: an answer other than INVALID_ARGUMENT would mean they were looked at first.  With two bad options the
+    message is that of the rule the validator checks first."""
     import t4a_amd
     o = one_site_options()
-    if field == "max_bond_dim":
-        o.has_max_bond_dim = 1
-    if field.startswith("krylov."):
-        setattr(o.krylov, field.split(".")[1], value)
-    else:
-        setattr(o, field, value)
+    for field, value in settings:
+        if field == "max_bond_dim":
+            o.has_max_bond_dim = 1
+        if field.startswith("krylov."):
+            setattr(o.krylov, field.split(".")[1], value)
+        else:
+            setattr(o, field, value)
     h = ctypes.c_void_p()
     st = t4a_amd._lib.t4a_gpu_tdvp_one_site(None, None, ctypes.c_size_t(0), ctypes.byref(o), ctypes.byref(h), None, None, None, None, None)
     assert st == t4a_amd.INVALID_ARGUMENT, t4a_amd.last_error_message()
