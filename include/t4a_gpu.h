@@ -2025,6 +2025,85 @@ t4a_gpu_status t4a_gpu_fuse_round(size_t n_jobs, const double* a, const double* 
  * `bond`: [0] the one lock-step launch, [1] one t4a_gpu_swap_theta kernel launch per pair, issued group by group. */
 t4a_gpu_status t4a_gpu_fuse_time(size_t n_groups, size_t bond, size_t reps, double* ms2);
 
+/* =====================================================================================
+ * Variational sum of many tensor trains or MPOs resident on the device: fit_sum
+ * tensor4all-treetn/src/treetn/fit.rs:1521-1644 (fit_sum, SumFitUpdater :1140-1337, fit_two_site_update :648-771, run_fit_sweeps
+ * :1076-1113), restated for a chain, f64, by position; an MPO enters over its fused site index s1 + S1 s2.  Trees, complex scalars and
+ * the QR, LU and CI factorisations are not mirrored (a valid request for one of the three: NOT_IMPLEMENTED naming it).
+ * One result C is swept two sites at a time against the environments <C|T_k> of every target, the local optimum of a bond being
+ * Theta = sum_k L_k T_k[i] T_k[i+1] R_k; the sum T_1 + .. + T_K with its bond sum_k chi_k is never formed.  The environments of all
+ * targets at a bond are one matrix with the targets' bonds concatenated: a bond step is two half launches (one kernel launch each for
+ * all targets), Theta = P Q as one GEMM over the concatenated index, the SVD split and one GEMM for the environment left behind.
+ * `initial` (NULL: a clone of targets[0], this project's extension) gives the length, the site dimensions and the starting bonds; it is
+ * canonicalised onto `center` by forced thin-QR sweeps, every environment towards the centre is built, and each full sweep is the Euler
+ * tour bonds center .. n-2 to the right, n-2 .. 0 to the left, 0 .. center-1 to the right, the second node of a step the new centre.
+ * The split is Canonical::Left: the first node of the step takes the orthonormal factor, the second S Vt, by the policy of
+ * t4a_gpu_tensor_svd (none: its default).  The bond cap is max_bond_dim when given, else none when svd_policy or qr_rtol is given, else
+ * THE PRESENT DIMENSION OF THAT BOND: with no option set the ranks never grow.  With has_convergence_tol the sweeps stop after a sweep
+ * with |exp(log|psi|_after - log|psi|_before) - 1| < convergence_tol (*converged = 1); else exactly nfullsweeps sweeps run.
+ * nfullsweeps == 0 returns a clone of the initial after validation; one site returns the elementwise sum of the targets' tensors.
+ * coefficients (NULL: all ones; this project's extension): one finite real per target, sum_k w_k T_k, applied once by scaling a copy of
+ * site 0 of a target whose weight is not 1.
+ * route: T4A_GPU_FIT_SUM_AUTO, _FUSED (the one launch per half) or _GEMM (the same halves from one GEMM per target for P and one per
+ * target and site index for Q).  On integer operands the routes give equal integers; on real operands not necessarily equal bits.
+ * INVALID_ARGUMENT with a message, before an operand is looked at: "convergence tolerance must be finite and non-negative", "QR
+ * relative tolerance must be finite and non-negative", max_bond_dim == 0 when set, an invalid svd_policy, "SVD factorization does not
+ * accept qr_rtol" (FactorizeOptions::validate; QR with svd_policy, LU/CI with either likewise), an unknown route; then "fit_sum: targets
+ * must not be empty", an empty initial, "fit_sum: center node is not in initial TreeTN", per target "fit_sum: target i has an
+ * incompatible named topology" (another length) and "fit_sum: target i site-space validation failed" (another site dimension), a
+ * coefficient that is not finite, and a work matrix of a bond step (P, Q, Theta, an environment) above INT_MAX elements.
+ * ===================================================================================== */
+#define T4A_GPU_FIT_SUM_AUTO 0
+#define T4A_GPU_FIT_SUM_FUSED 1
+#define T4A_GPU_FIT_SUM_GEMM 2
+typedef struct {
+    size_t nfullsweeps;
+    int32_t has_max_bond_dim; /* 0 <=> None */
+    size_t max_bond_dim;
+    int32_t has_svd_policy;   /* 0 <=> None: the default policy of t4a_gpu_tensor_svd */
+    t4a_gpu_svd_policy svd_policy;
+    int32_t has_qr_rtol;      /* 0 <=> None */
+    double qr_rtol;
+    int32_t factorize_alg;    /* 0 SVD, 1 QR, 2 LU, 3 CI */
+    int32_t has_convergence_tol;
+    double convergence_tol;
+} t4a_gpu_fit_sum_options;
+/* FitOptions::new(1): 1, None, None, None, SVD, None */
+t4a_gpu_status t4a_gpu_fit_sum_options_default(t4a_gpu_fit_sum_options* out);
+/* The checks of t4a_gpu_tt_fit_sum on plain dimension lists, a pure host function: options (may be NULL: not checked), then the shapes.
+ * target_dims3: (left, site, right) per site of every target, one target after the other; target_lens: sites per target.
+ * has_initial == 0: the first target stands in for the initial. */
+t4a_gpu_status t4a_gpu_fit_sum_check_shapes(const size_t* target_dims3, const size_t* target_lens, size_t n_targets, int32_t has_initial,
+                                            const size_t* initial_dims3, size_t n_initial, size_t center,
+                                            const t4a_gpu_fit_sum_options* options);
+/* norms (may be NULL): room for nfullsweeps doubles, |psi| after each completed sweep */
+t4a_gpu_status t4a_gpu_tt_fit_sum(const t4a_gpu_tt* const* targets, size_t n_targets, const double* coefficients /* may be NULL */,
+                                  const t4a_gpu_tt* initial /* may be NULL */, size_t center, const t4a_gpu_fit_sum_options* options,
+                                  int32_t route, t4a_gpu_tt** out, size_t* sweeps_completed, size_t* local_updates, int32_t* converged,
+                                  double* norms);
+/* the same for MPOs; every target must have the (s1, s2) pairs of the initial */
+t4a_gpu_status t4a_gpu_mpo_fit_sum(const t4a_gpu_mpo* const* targets, size_t n_targets, const double* coefficients /* may be NULL */,
+                                   const t4a_gpu_mpo* initial /* may be NULL */, size_t center, const t4a_gpu_fit_sum_options* options,
+                                   int32_t route, t4a_gpu_mpo** out, size_t* sweeps_completed, size_t* local_updates, int32_t* converged,
+                                   double* norms);
+/* Test hook: one half for K targets on raw column-major host operands, route _FUSED or _GEMM.  cores: T_k[a_k, S, b_k] one after the
+ * other; right == 0: env is EL (chi x sum a_k), out P (chi S) x (sum b_k), block k at column sum_{j<k} b_j:
+ *   P[c + chi (s + S (off_k + b))] = sum_a EL[c, offL_k + a] T_k[a, s, b];
+ * right != 0: env is ER (sum b_k x chi), out Q (sum a_k) x (S chi), block k at row sum_{j<k} a_j:
+ *   Q[(off_k + a) + A (s + S c)] = sum_b T_k[a, s, b] ER[offR_k + b, c].
+ * has_fill != 0: the output buffer and 64 guard doubles behind it hold `fill` before the launch, and `out` (room for 64 more doubles)
+ * receives the guard behind the result. */
+t4a_gpu_status t4a_gpu_fit_sum_half(int32_t right, int32_t route, const double* env, size_t chi, size_t S, const double* cores,
+                                    const size_t* a, const size_t* b, size_t K, int32_t has_fill, double fill, double* out);
+/* Host only: the route T4A_GPU_FIT_SUM_AUTO takes for a half with n_targets targets whose largest bond is target_bond. */
+t4a_gpu_status t4a_gpu_fit_sum_route(size_t n_targets, size_t target_bond, size_t result_bond, size_t site_dim, int32_t* route);
+/* Host only: out6 = bond steps per sweep, then per bond step half launches, GEMMs and SVDs, then half launches and GEMMs of the
+ * preparation, for a chain of n_sites sites of dimension site_dim on route _FUSED or _GEMM. */
+t4a_gpu_status t4a_gpu_fit_sum_plan(size_t n_sites, size_t center, size_t n_targets, size_t site_dim, int32_t route, size_t* out6);
+/* Probe (tools/probe_fit_sum.py): device ms per repetition (events around `reps` launches behind a warm-up) of one half for K targets
+ * of bond `bond`, site dimension S and result bond chi: [0] the fused launch, [1] the GEMM composition. */
+t4a_gpu_status t4a_gpu_fit_sum_time_half(int32_t right, size_t K, size_t bond, size_t S, size_t chi, size_t reps, double* ms2);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -27,6 +27,7 @@
 #include "linsolve.hpp"
 #include "swap.hpp"
 #include "restructure.hpp"
+#include "fit_sum.hpp"
 
 struct t4a_gpu_tci2 {
     t4a::Tci2 impl;
@@ -681,6 +682,29 @@ DmrgOptions convert_dmrg_options(const t4a_gpu_dmrg_options* p)
     return o;
 }
 
+FitSumOptions convert_fit_sum_options(const t4a_gpu_fit_sum_options* p)
+{
+    FitSumOptions o;
+    o.nfullsweeps = p->nfullsweeps;
+    o.has_max_bond_dim = p->has_max_bond_dim != 0;
+    o.max_bond_dim = p->max_bond_dim;
+    o.has_svd_policy = p->has_svd_policy != 0;
+    if (o.has_svd_policy) o.svd_policy = from_c(p->svd_policy);
+    o.has_qr_rtol = p->has_qr_rtol != 0;
+    o.qr_rtol = p->qr_rtol;
+    o.factorize_alg = p->factorize_alg;
+    o.has_convergence_tol = p->has_convergence_tol != 0;
+    o.convergence_tol = p->convergence_tol;
+    o.validate();
+    return o;
+}
+
+FitSumRoute convert_fit_sum_route(int32_t route, bool allow_auto)
+{
+    if (route < (allow_auto ? 0 : 1) || route > 2) throw Error(T4A_GPU_INVALID_ARGUMENT, allow_auto ? "fit_sum: unknown route" : "fit_sum: the route must be fused or gemm");
+    return (FitSumRoute)route;
+}
+
 KrylovExpmOptions convert_krylov_expm_options(const t4a_gpu_krylov_expm_options& p)
 {
     KrylovExpmOptions o;
@@ -1052,6 +1076,37 @@ t4a_gpu_status tt_fuse_to(const t4a_gpu_tt* tt, const size_t* leg_counts, const 
         if (launches) *launches = r.launches;
         *out = res.release();
     });
+}
+
+// what t4a_gpu_tt_fit_sum and t4a_gpu_mpo_fit_sum share: the checks in their order, the operands of the handles, the scalar outputs
+template <class H, class Cores, class Eng, class Pre, class Wrap>
+void fit_sum_entry(const H* const* targets, size_t n_targets, const double* coefficients, const H* initial, size_t center,
+                   const t4a_gpu_fit_sum_options* options, int32_t route, size_t* sweeps_completed, size_t* local_updates, int32_t* converged,
+                   double* norms, Cores&& cores_of, Eng&& engine_of, Pre&& pre, Wrap&& wrap)
+{
+    T4A_REQUIRE_PTR(options);
+    const FitSumOptions o = convert_fit_sum_options(options); // the options are checked on the host before an operand is looked at
+    const FitSumRoute rt = convert_fit_sum_route(route, true);
+    if (n_targets == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "fit_sum: targets must not be empty");
+    T4A_REQUIRE_PTR(targets);
+    T4A_REQUIRE_PTR(sweeps_completed);
+    T4A_REQUIRE_PTR(local_updates);
+    T4A_REQUIRE_PTR(converged);
+    std::vector<const std::vector<DevCore>*> cores;
+    std::vector<Engine*> engines;
+    for (size_t k = 0; k < n_targets; ++k) {
+        if (!targets[k]) throw Error(T4A_GPU_NULL_POINTER, "fit_sum: target " + std::to_string(k) + " is null");
+        cores.push_back(cores_of(targets[k]));
+        engines.push_back(engine_of(targets[k]));
+    }
+    pre();
+    FitSumResult r = fit_sum(cores, engines, coefficients, initial ? cores_of(initial) : nullptr, initial ? engine_of(initial) : nullptr, center, o, rt);
+    wrap(r);
+    *sweeps_completed = r.sweeps_completed;
+    *local_updates = r.local_updates;
+    *converged = r.converged;
+    if (norms)
+        for (size_t i = 0; i < r.norms.size(); ++i) norms[i] = r.norms[i];
 }
 
 } // namespace
@@ -6279,6 +6334,129 @@ t4a_gpu_status t4a_gpu_fuse_time(size_t n_groups, size_t bond, size_t reps, doub
         T4A_REQUIRE_PTR(ms2);
         require_device();
         fuse_time(n_groups, bond, (int)std::min<size_t>(reps, 1u << 20), &ms2[0], &ms2[1]);
+    });
+}
+
+// ---- fit_sum: the variational sum of many trains or MPOs (fit_sum.hpp) ----
+t4a_gpu_status t4a_gpu_fit_sum_options_default(t4a_gpu_fit_sum_options* out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(out);
+        const FitSumOptions d;
+        *out = t4a_gpu_fit_sum_options{};
+        out->nfullsweeps = d.nfullsweeps;
+        out->has_max_bond_dim = d.has_max_bond_dim;
+        out->max_bond_dim = d.max_bond_dim;
+        out->has_svd_policy = d.has_svd_policy;
+        out->svd_policy = to_c(d.svd_policy);
+        out->has_qr_rtol = d.has_qr_rtol;
+        out->qr_rtol = d.qr_rtol;
+        out->factorize_alg = d.factorize_alg;
+        out->has_convergence_tol = d.has_convergence_tol;
+        out->convergence_tol = d.convergence_tol;
+    });
+}
+
+t4a_gpu_status t4a_gpu_fit_sum_check_shapes(const size_t* target_dims3, const size_t* target_lens, size_t n_targets, int32_t has_initial,
+                                            const size_t* initial_dims3, size_t n_initial, size_t center, const t4a_gpu_fit_sum_options* options)
+{
+    return guarded([&] {
+        if (options) convert_fit_sum_options(options);
+        if (n_targets) T4A_REQUIRE_PTR(target_lens);
+        std::vector<std::vector<std::array<size_t, 3>>> targets;
+        size_t off = 0;
+        for (size_t k = 0; k < n_targets; ++k) {
+            if (target_lens[k]) T4A_REQUIRE_PTR(target_dims3);
+            targets.push_back(dims3_list(target_dims3 + 3 * off, target_lens[k]));
+            off += target_lens[k];
+        }
+        if (has_initial && n_initial) T4A_REQUIRE_PTR(initial_dims3);
+        const auto init = dims3_list(initial_dims3, has_initial ? n_initial : 0);
+        fit_sum_validate_shapes(targets, has_initial ? &init : nullptr, center);
+    });
+}
+
+t4a_gpu_status t4a_gpu_tt_fit_sum(const t4a_gpu_tt* const* targets, size_t n_targets, const double* coefficients, const t4a_gpu_tt* initial,
+                                  size_t center, const t4a_gpu_fit_sum_options* options, int32_t route, t4a_gpu_tt** out, size_t* sweeps_completed,
+                                  size_t* local_updates, int32_t* converged, double* norms)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(out);
+        *out = nullptr;
+        fit_sum_entry(
+            targets, n_targets, coefficients, initial, center, options, route, sweeps_completed, local_updates, converged, norms,
+            [](const t4a_gpu_tt* h) { return &h->impl.cores; }, [](const t4a_gpu_tt* h) { return &const_cast<t4a_gpu_tt*>(h)->impl.eng; },
+            [] {}, [&](FitSumResult& r) { *out = new t4a_gpu_tt(r.cores, nullptr); });
+    });
+}
+
+t4a_gpu_status t4a_gpu_mpo_fit_sum(const t4a_gpu_mpo* const* targets, size_t n_targets, const double* coefficients, const t4a_gpu_mpo* initial,
+                                   size_t center, const t4a_gpu_fit_sum_options* options, int32_t route, t4a_gpu_mpo** out, size_t* sweeps_completed,
+                                   size_t* local_updates, int32_t* converged, double* norms)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(out);
+        *out = nullptr;
+        fit_sum_entry(
+            targets, n_targets, coefficients, initial, center, options, route, sweeps_completed, local_updates, converged, norms,
+            [](const t4a_gpu_mpo* h) { return &h->impl->tt.cores; }, [](const t4a_gpu_mpo* h) { return &h->impl->tt.eng; },
+            [&] {
+                // the fused site index is checked by fit_sum; the (s1, s2) pairs behind an equal fused index have to agree as well
+                const std::vector<std::array<size_t, 2>>& sd = (initial ? initial : targets[0])->impl->sd;
+                for (size_t k = 0; k < n_targets; ++k) {
+                    const std::vector<std::array<size_t, 2>>& td = targets[k]->impl->sd;
+                    if (td.size() != sd.size()) continue;
+                    for (size_t i = 0; i < sd.size(); ++i)
+                        if (td[i][0] * td[i][1] == sd[i][0] * sd[i][1] && td[i] != sd[i])
+                            throw Error(T4A_GPU_INVALID_ARGUMENT, "fit_sum: target " + std::to_string(k) + " site-space validation failed");
+                }
+            },
+            [&](FitSumResult& r) {
+                const std::vector<std::array<size_t, 2>>& sd = (initial ? initial : targets[0])->impl->sd;
+                *out = new t4a_gpu_mpo{std::make_unique<Mpo>(std::move(r.cores), sd)};
+            });
+    });
+}
+
+t4a_gpu_status t4a_gpu_fit_sum_half(int32_t right, int32_t route, const double* env, size_t chi, size_t S, const double* cores, const size_t* a,
+                                    const size_t* b, size_t K, int32_t has_fill, double fill, double* out)
+{
+    return guarded([&] {
+        const FitSumRoute rt = convert_fit_sum_route(route, false);
+        T4A_REQUIRE_PTR(env);
+        T4A_REQUIRE_PTR(cores);
+        T4A_REQUIRE_PTR(a);
+        T4A_REQUIRE_PTR(b);
+        T4A_REQUIRE_PTR(out);
+        const std::vector<double> r = fit_sum_half(right != 0, rt, env, chi, S, cores, a, b, K, has_fill ? &fill : nullptr);
+        std::memcpy(out, r.data(), r.size() * sizeof(double));
+    });
+}
+
+t4a_gpu_status t4a_gpu_fit_sum_route(size_t n_targets, size_t target_bond, size_t result_bond, size_t site_dim, int32_t* route)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(route);
+        if (n_targets == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "fit_sum: targets must not be empty");
+        *route = (int32_t)fit_sum_route(n_targets, target_bond, result_bond, site_dim);
+    });
+}
+
+t4a_gpu_status t4a_gpu_fit_sum_plan(size_t n_sites, size_t center, size_t n_targets, size_t site_dim, int32_t route, size_t* out6)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(out6);
+        const FitSumPlan p = fit_sum_plan(n_sites, center, n_targets, site_dim, convert_fit_sum_route(route, false));
+        out6[0] = p.bond_steps_per_sweep, out6[1] = p.half_launches_per_step, out6[2] = p.gemms_per_step, out6[3] = p.svds_per_step;
+        out6[4] = p.prepare_half_launches, out6[5] = p.prepare_gemms;
+    });
+}
+
+t4a_gpu_status t4a_gpu_fit_sum_time_half(int32_t right, size_t K, size_t bond, size_t S, size_t chi, size_t reps, double* ms2)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(ms2);
+        fit_sum_time_half(right != 0, K, bond, S, chi, std::min<size_t>(reps, 1u << 20), ms2);
     });
 }
 

@@ -2254,3 +2254,7 @@ from .swap import (SwapOptions, ScheduledSwapStep, SwapSchedule, LegTrain, swap_
 from . import restructure  # noqa: E402
 from .restructure import (SplitOptions, RestructureOptions, fuse_to, split_to, restructure_to, restructure_plan, fuse_plan,  # noqa: E402,F401
                           split_plan, fuse_quantics, unfuse_quantics, fuse_round)
+# fit_sum, the variational sum of many trains or MPOs: module t4a_amd.fitsum (the hooks _half and _time_half live there)
+from . import fitsum  # noqa: E402
+from .fitsum import (FitSumOptions, FitSumOptionsC, FitSumResult, FactorizeAlg, fit_sum, fit_sum_plan, fit_sum_route,  # noqa: E402,F401
+                     fit_sum_check_shapes)
