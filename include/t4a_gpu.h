@@ -2104,6 +2104,63 @@ t4a_gpu_status t4a_gpu_fit_sum_plan(size_t n_sites, size_t center, size_t n_targ
  * of bond `bond`, site dimension S and result bond chi: [0] the fused launch, [1] the GEMM composition. */
 t4a_gpu_status t4a_gpu_fit_sum_time_half(int32_t right, size_t K, size_t bond, size_t S, size_t chi, size_t reps, double* ms2);
 
+/* ---- an operator applied on a subset of a state's sites (csrc/linop.hpp; tensor4all-treetn/src/operator/: apply.rs, compose.rs,
+ * identity.rs, on a chain and by position).  The operator is an MPO of k >= 1 sites O_j[a, y, x, a'] (leg 0 the output, leg 1 the
+ * input), `sites` its k strictly ascending state positions.  A state site is an operator site (kind 0), a bridge between two operator
+ * sites that carries the operator bond through unchanged (kind 1), or outside the operator's span (kind 2).  Result bonds are fused
+ * with the operator index slow and the state index fast.  Refusals (INVALID_ARGUMENT, all before the device is touched): `sites` not
+ * strictly ascending, "Operator nodes [..] are not a subset of state nodes [..]", "Shared shape mismatch at site i: operator has input
+ * dim p, the state has site dim q", a fused bond above 65535, a core of more than INT_MAX elements. */
+#define T4A_GPU_LINOP_NAIVE 0
+#define T4A_GPU_LINOP_ZIPUP 1
+#define T4A_GPU_LINOP_FIT 2
+#define T4A_GPU_LINOP_ROUTE_AUTO 0
+#define T4A_GPU_LINOP_ROUTE_FUSED 1    /* the kernels of csrc/kernels_apply.hip: no identity is materialised */
+#define T4A_GPU_LINOP_ROUTE_COMPOSED 2 /* t4a_gpu_linop_extend, then the MPO-MPO contraction */
+typedef struct {
+    int32_t method;           /* T4A_GPU_LINOP_NAIVE / _ZIPUP / _FIT; naive ignores everything below */
+    double tolerance;         /* the SVD rank rule of the MPO contraction: values below tolerance * s_max are dropped */
+    int32_t has_max_bond_dim; /* 0 <=> None */
+    size_t max_bond_dim;
+    size_t nfullsweeps;       /* fit */
+    int32_t has_convergence_tol; /* fit; 0 <=> None: every sweep runs */
+    double convergence_tol;
+} t4a_gpu_linop_options;
+/* ApplyOptions::default(): zip-up, 1e-12, None, 1, None */
+t4a_gpu_status t4a_gpu_linop_options_default(t4a_gpu_linop_options* out);
+/* Host only.  op_dims4: (left, s1, s2, right) per operator site; state_dims3: (left, site, right) per state site.  Outputs (each may be
+ * NULL), one entry per state site: kinds; bonds: the operator bond (left, right) of the site; result_dims3. */
+t4a_gpu_status t4a_gpu_linop_plan(const size_t* op_dims4, size_t n_op, const size_t* sites, size_t n_sites, const size_t* state_dims3,
+                                  size_t n_state, int32_t* kinds, size_t* bonds, size_t* result_dims3);
+/* initial (may be NULL): the start of the fit, a train with the result's site dims; NULL is the zip-up with the same tolerance and cap.
+ * n_sweeps, norms (room for nfullsweeps + 1 doubles: the start, then one per sweep), route_taken may be NULL. */
+t4a_gpu_status t4a_gpu_linop_apply(const t4a_gpu_mpo* op, const size_t* sites, size_t n_sites, const t4a_gpu_tt* state,
+                                   const t4a_gpu_linop_options* options, int32_t route, const t4a_gpu_tt* initial, t4a_gpu_tt** out,
+                                   size_t* n_sweeps, double* norms, int32_t* route_taken);
+/* extend_operator_to_full_space: operator sites are device copies, bridge sites delta_{aa'} delta_{yx} of shape [m, d, d, m], outside
+ * sites [1, d, d, 1] identities. */
+t4a_gpu_status t4a_gpu_linop_extend(const t4a_gpu_mpo* op, const size_t* sites, size_t n_sites, const size_t* state_site_dims, size_t n_state,
+                                    t4a_gpu_mpo** out);
+/* are_exclusive_operators, host only.  sites: the positions of every operator one after the other; lens: positions per operator. */
+t4a_gpu_status t4a_gpu_linop_exclusive(size_t n_state, const size_t* sites, const size_t* lens, size_t n_ops, int32_t* exclusive);
+/* compose_exclusive_linear_operators: the full-length operator, gaps identities with bond 1.  INVALID_ARGUMENT "... Operators are not
+ * exclusive: they may overlap or not form connected subtrees". */
+t4a_gpu_status t4a_gpu_linop_compose(const size_t* state_site_dims, size_t n_state, const t4a_gpu_mpo* const* ops, const size_t* sites,
+                                     const size_t* lens, size_t n_ops, t4a_gpu_mpo** out);
+/* Test hook: the half product of a gap site on host buffers, launched exactly as the drivers launch it (column-major throughout).
+ * right == 0: env is L[n_env, m, lb], x is X[lb, d, rb], out P[n_env, d, m, rb] = sum_b L[n, a, b] X[b, x, c];
+ * right != 0: env is R[m, rb, n_env], out Q[m, lb, d, n_env] = sum_c X[b, x, c] R[a, c, n].
+ * has_fill != 0: the output buffer and 64 guard doubles behind it hold `fill` before the launch and `out` has room for 64 more doubles,
+ * which receive the guard. */
+t4a_gpu_status t4a_gpu_linop_gap_half(int32_t right, const double* env, size_t n_env, size_t m, const double* x, size_t lb, size_t d,
+                                      size_t rb, int32_t has_fill, double fill, double* out);
+/* Host only: the route T4A_GPU_LINOP_ROUTE_AUTO takes. */
+t4a_gpu_status t4a_gpu_linop_route(int32_t method, size_t n_state, size_t n_gap_sites, size_t state_bond, size_t op_bond, int32_t* route);
+/* Probe (tools/probe_linop.py): device ms per repetition (events around `reps` launches behind a warm-up) of the left half of a bridge
+ * site with operator bond m, site dim d, state bonds lb x rb and n_env environment rows: [0] apply_gap_half_kernel, [1] the half kernel
+ * of the partial contraction on the materialised bridge site. */
+t4a_gpu_status t4a_gpu_linop_time_half(size_t n_env, size_t m, size_t lb, size_t d, size_t rb, size_t reps, double* ms2);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -15,7 +15,7 @@ OUT = os.path.join(HERE, "lib")
 OBJ = os.path.join(HERE, "build")
 # (the slowest units first: four compile at a time, and the build is never shorter than its longest unit)
 SOURCES = ["kernels_rrlu_xcd2_group.hip", "kernels_rrlu_xcd2.hip", "kernels_rrlu_reg_r3.hip", "kernels_rrlu_reg_r2.hip", "kernels_rrlu_reg_r4.hip", "kernels_rrlu_reg.hip", "kernels_rrlu_xcd2m.hip", "kernels_rrlu_wg.hip", "kernels_rrlu_wg_group.hip", "kernels_rrlu_w1.hip", "kernels_rrlu.hip", "rrlu_plan.hip", "rrlu_xcd_plan.hip", "kernels_rrlu_global.hip", "kernels_pi.hip", "kernels_chain.hip", "kernels_small.hip", "kernels_dense.hip", "kernels_linalg.hip", "kernels_batch_compress.hip", "kernels_batch_truncate.hip",
-           "kernels_tt.hip", "kernels_mpo.hip", "kernels_mpo_fit.hip", "kernels_partial.hip", "kernels_swap.hip", "kernels_restructure.hip", "kernels_linsolve.hip", "kernels_dmrg.hip", "kernels_tdvp.hip", "kernels_gse.hip", "kernels_fit_sum.hip", "kernels_pmpo.hip", "kernels_contraction.hip", "pool.hip", "engine.hip", "rook.hip", "tt_chain.hip", "tt.hip", "tt_canonical.hip", "mpo.hip", "batch_compress.hip", "batch_truncate.hip", "krylov.hip", "linsolve.hip", "dmrg.hip", "tdvp.hip", "gse.hip", "fit_sum.hip", "pmpo.hip", "pmpo_patching.hip", "swap.hip", "restructure.hip", "contraction.hip", "globalsearch.hip", "tci2.hip", "tci2_fill.hip", "tci2_chain.hip", "tci2_small.hip", "conversion.hip", "patching.hip", "tree.hip", "quantics.hip", "tensorops.hip", "dense.hip", "aci.hip", "quanticstransform.hip", "capi.hip"]
+           "kernels_tt.hip", "kernels_mpo.hip", "kernels_mpo_fit.hip", "kernels_partial.hip", "kernels_swap.hip", "kernels_restructure.hip", "kernels_linsolve.hip", "kernels_dmrg.hip", "kernels_tdvp.hip", "kernels_gse.hip", "kernels_fit_sum.hip", "kernels_apply.hip", "kernels_pmpo.hip", "kernels_contraction.hip", "pool.hip", "engine.hip", "rook.hip", "tt_chain.hip", "tt.hip", "tt_canonical.hip", "mpo.hip", "batch_compress.hip", "batch_truncate.hip", "krylov.hip", "linsolve.hip", "dmrg.hip", "tdvp.hip", "gse.hip", "fit_sum.hip", "linop.hip", "pmpo.hip", "pmpo_patching.hip", "swap.hip", "restructure.hip", "contraction.hip", "globalsearch.hip", "tci2.hip", "tci2_fill.hip", "tci2_chain.hip", "tci2_small.hip", "conversion.hip", "patching.hip", "tree.hip", "quantics.hip", "tensorops.hip", "dense.hip", "aci.hip", "quanticstransform.hip", "capi.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function",
          "-fvisibility=hidden"] + os.environ.get("T4A_EXTRA_FLAGS", "").split()  # e.g. -DT4A_RRLU_TRACE (tools/trace_arrivals.py)
 # per-source flags.  kernels_dense.hip: keep MFMA accumulators in VGPRs — in AGPR form the compiler moves all of them between the
@@ -24,7 +24,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=o
 # its one-workgroup kernels are bound by the instructions they issue, a separately rounded multiply and add is two of them
 FILE_FLAGS = {"kernels_dense.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"], "kernels_linalg.hip": ["-ffp-contract=fast"],
               "kernels_batch_compress.hip": ["-ffp-contract=fast"], "kernels_batch_truncate.hip": ["-ffp-contract=fast"]}  # (the Jacobi arithmetic of kernels_linalg.hip, kernels_jacobi_common.hpp)
-HEADERS = ["common.hpp", "stdrng.hpp", "pishard.hpp", "kernels.hpp", "kernels_jacobi_common.hpp", "kernels_batch_steps.hpp", "rrlu_shapes.hpp", "kernels_rrlu_xcd_common.hpp", "kernels_rrlu_w1_body.hpp", "engine.hpp", "fnsource.hpp", "tci2.hpp", "matrix_source.hpp", "tt_chain.hpp", "tt.hpp", "tt_canonical.hpp", "mpo.hpp", "batch_compress.hpp", "batch_truncate.hpp", "krylov.hpp", "linsolve.hpp", "krylov_reduce.hpp", "dmrg.hpp", "tdvp.hpp", "gse.hpp", "fit_sum.hpp", "pmpo.hpp", "pmpo_patching.hpp", "swap.hpp", "restructure.hpp", "contraction.hpp", "globalsearch.hpp", "rook.hpp", "patching.hpp", "tree.hpp", "quantics.hpp", "tensorops.hpp", "dense.hpp", "aci.hpp", "quanticstransform.hpp", "../../include/t4a_gpu.h",
+HEADERS = ["common.hpp", "stdrng.hpp", "pishard.hpp", "kernels.hpp", "kernels_jacobi_common.hpp", "kernels_batch_steps.hpp", "rrlu_shapes.hpp", "kernels_rrlu_xcd_common.hpp", "kernels_rrlu_w1_body.hpp", "engine.hpp", "fnsource.hpp", "tci2.hpp", "matrix_source.hpp", "tt_chain.hpp", "tt.hpp", "tt_canonical.hpp", "mpo.hpp", "batch_compress.hpp", "batch_truncate.hpp", "krylov.hpp", "linsolve.hpp", "krylov_reduce.hpp", "dmrg.hpp", "tdvp.hpp", "gse.hpp", "fit_sum.hpp", "linop.hpp", "pmpo.hpp", "pmpo_patching.hpp", "swap.hpp", "restructure.hpp", "contraction.hpp", "globalsearch.hpp", "rook.hpp", "patching.hpp", "tree.hpp", "quantics.hpp", "tensorops.hpp", "dense.hpp", "aci.hpp", "quanticstransform.hpp", "../../include/t4a_gpu.h",
            "../../include/t4a_testfunctions.h"]
 
 

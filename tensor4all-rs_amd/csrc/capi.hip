@@ -28,6 +28,7 @@
 #include "swap.hpp"
 #include "restructure.hpp"
 #include "fit_sum.hpp"
+#include "linop.hpp"
 
 struct t4a_gpu_tci2 {
     t4a::Tci2 impl;
@@ -594,6 +595,18 @@ std::vector<TensorTrain*> aci_inputs(const t4a_gpu_tt* const* inputs, size_t n)
     if (n == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "inputs must not be empty");
     if (!inputs) throw Error(T4A_GPU_NULL_POINTER, "inputs is null");
     return handle_list(inputs, n, "input tensor train is null", [](const t4a_gpu_tt& t) { return const_cast<TensorTrain*>(&t.impl); });
+}
+
+// the positions of every operator of t4a_gpu_linop_exclusive / _compose, one list per operator
+std::vector<std::vector<size_t>> linop_supports(const size_t* sites, const size_t* lens, size_t n_ops)
+{
+    std::vector<std::vector<size_t>> s(n_ops);
+    size_t off = 0;
+    for (size_t q = 0; q < n_ops; ++q) {
+        s[q].assign(sites + off, sites + off + lens[q]);
+        off += lens[q];
+    }
+    return s;
 }
 
 PartialSpec partial_spec(const size_t* contract_pairs, size_t n_contract, const size_t* diagonal_pairs, size_t n_diagonal, size_t n_output_order)
@@ -6457,6 +6470,159 @@ t4a_gpu_status t4a_gpu_fit_sum_time_half(int32_t right, size_t K, size_t bond, s
     return guarded([&] {
         T4A_REQUIRE_PTR(ms2);
         fit_sum_time_half(right != 0, K, bond, S, chi, std::min<size_t>(reps, 1u << 20), ms2);
+    });
+}
+
+// ---- an operator applied on a subset of a state's sites (linop.hpp) ----
+t4a_gpu_status t4a_gpu_linop_options_default(t4a_gpu_linop_options* out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(out);
+        const ApplyOptions d;
+        out->method = (int32_t)d.method;
+        out->tolerance = d.tolerance;
+        out->has_max_bond_dim = d.max_bond_dim != 0;
+        out->max_bond_dim = d.max_bond_dim;
+        out->nfullsweeps = d.max_sweeps;
+        out->has_convergence_tol = d.has_convergence_tol;
+        out->convergence_tol = d.convergence_tol;
+    });
+}
+
+t4a_gpu_status t4a_gpu_linop_plan(const size_t* op_dims4, size_t n_op, const size_t* sites, size_t n_sites, const size_t* state_dims3,
+                                  size_t n_state, int32_t* kinds, size_t* bonds, size_t* result_dims3)
+{
+    return guarded([&] {
+        if (n_op) T4A_REQUIRE_PTR(op_dims4);
+        if (n_sites) T4A_REQUIRE_PTR(sites);
+        if (n_state) T4A_REQUIRE_PTR(state_dims3);
+        std::vector<std::array<size_t, 4>> od(n_op);
+        std::vector<std::array<size_t, 3>> sd(n_state);
+        for (size_t i = 0; i < n_op; ++i) od[i] = {op_dims4[4 * i], op_dims4[4 * i + 1], op_dims4[4 * i + 2], op_dims4[4 * i + 3]};
+        for (size_t i = 0; i < n_state; ++i) sd[i] = {state_dims3[3 * i], state_dims3[3 * i + 1], state_dims3[3 * i + 2]};
+        const std::vector<ApplySitePlan> plan = apply_plan(od, std::vector<size_t>(sites, sites + n_sites), sd);
+        for (size_t i = 0; i < plan.size(); ++i) {
+            if (kinds) kinds[i] = (int32_t)plan[i].kind;
+            if (bonds) bonds[2 * i] = plan[i].m_left, bonds[2 * i + 1] = plan[i].m_right;
+            if (result_dims3)
+                for (int k = 0; k < 3; ++k) result_dims3[3 * i + k] = plan[i].result[k];
+        }
+    });
+}
+
+t4a_gpu_status t4a_gpu_linop_apply(const t4a_gpu_mpo* op, const size_t* sites, size_t n_sites, const t4a_gpu_tt* state,
+                                   const t4a_gpu_linop_options* options, int32_t route, const t4a_gpu_tt* initial, t4a_gpu_tt** out,
+                                   size_t* n_sweeps, double* norms, int32_t* route_taken)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(out);
+        *out = nullptr;
+        if (n_sweeps) *n_sweeps = 0;
+        T4A_REQUIRE_PTR(options);
+        // the options are checked on the host before an operand is looked at
+        if (options->method < 0 || options->method > 2) throw Error(T4A_GPU_INVALID_ARGUMENT, "apply_linear_operator: unknown method");
+        if (route < 0 || route > 2) throw Error(T4A_GPU_INVALID_ARGUMENT, "apply_linear_operator: route must be auto, fused or composed");
+        if (options->has_max_bond_dim && options->max_bond_dim == 0)
+            throw Error(T4A_GPU_INVALID_ARGUMENT, "apply_linear_operator: max_bond_dim must be at least 1");
+        ApplyOptions o;
+        o.method = (MpoAlgorithm)options->method;
+        o.tolerance = options->tolerance;
+        o.max_bond_dim = options->has_max_bond_dim ? options->max_bond_dim : 0;
+        o.max_sweeps = options->nfullsweeps;
+        o.has_convergence_tol = options->has_convergence_tol != 0;
+        o.convergence_tol = options->convergence_tol;
+        apply_validate_options(o);
+        T4A_REQUIRE_PTR(op);
+        T4A_REQUIRE_PTR(state);
+        if (n_sites) T4A_REQUIRE_PTR(sites);
+        TensorTrain& st = const_cast<t4a_gpu_tt*>(state)->impl;
+        std::unique_ptr<Mpo> init;
+        if (initial && o.method == MpoAlgorithm::Fit) { // the start as an MPO with site dims (d, 1)
+            std::vector<std::array<size_t, 2>> sd;
+            for (const auto& c : initial->impl.cores) sd.push_back({c.s, 1});
+            init = std::make_unique<Mpo>(initial->impl.cores, initial->impl.eng.stream(), sd);
+        }
+        MpoFitInfo info;
+        ApplyRoute taken = ApplyRoute::Composed;
+        std::unique_ptr<Mpo> r =
+            apply_linear_operator(*op->impl, std::vector<size_t>(sites, sites + n_sites), st, o, (ApplyRoute)route, init.get(), info, &taken);
+        *out = new t4a_gpu_tt(r->tt.cores, r->tt.eng.stream());
+        if (n_sweeps) *n_sweeps = info.n_sweeps;
+        if (norms) std::copy(info.norms.begin(), info.norms.end(), norms);
+        if (route_taken) *route_taken = (int32_t)taken;
+    });
+}
+
+t4a_gpu_status t4a_gpu_linop_extend(const t4a_gpu_mpo* op, const size_t* sites, size_t n_sites, const size_t* state_site_dims, size_t n_state,
+                                    t4a_gpu_mpo** out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(op);
+        T4A_REQUIRE_PTR(out);
+        *out = nullptr;
+        if (n_sites) T4A_REQUIRE_PTR(sites);
+        if (n_state) T4A_REQUIRE_PTR(state_site_dims);
+        *out = new t4a_gpu_mpo{extend_operator_to_full_space(*op->impl, std::vector<size_t>(sites, sites + n_sites),
+                                                              std::vector<size_t>(state_site_dims, state_site_dims + n_state))};
+    });
+}
+
+t4a_gpu_status t4a_gpu_linop_exclusive(size_t n_state, const size_t* sites, const size_t* lens, size_t n_ops, int32_t* exclusive)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(exclusive);
+        if (n_ops) T4A_REQUIRE_PTR(lens);
+        if (n_ops) T4A_REQUIRE_PTR(sites);
+        *exclusive = are_exclusive_operators(n_state, linop_supports(sites, lens, n_ops)) ? 1 : 0;
+    });
+}
+
+t4a_gpu_status t4a_gpu_linop_compose(const size_t* state_site_dims, size_t n_state, const t4a_gpu_mpo* const* ops, const size_t* sites,
+                                     const size_t* lens, size_t n_ops, t4a_gpu_mpo** out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(out);
+        *out = nullptr;
+        if (n_state) T4A_REQUIRE_PTR(state_site_dims);
+        if (n_ops) T4A_REQUIRE_PTR(ops);
+        if (n_ops) T4A_REQUIRE_PTR(lens);
+        if (n_ops) T4A_REQUIRE_PTR(sites);
+        std::vector<Mpo*> v(n_ops);
+        for (size_t q = 0; q < n_ops; ++q) {
+            T4A_REQUIRE_PTR(ops[q]);
+            v[q] = ops[q]->impl.get();
+        }
+        *out = new t4a_gpu_mpo{compose_exclusive_linear_operators(std::vector<size_t>(state_site_dims, state_site_dims + n_state), v,
+                                                                   linop_supports(sites, lens, n_ops))};
+    });
+}
+
+t4a_gpu_status t4a_gpu_linop_gap_half(int32_t right, const double* env, size_t n_env, size_t m, const double* x, size_t lb, size_t d,
+                                      size_t rb, int32_t has_fill, double fill, double* out)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(env);
+        T4A_REQUIRE_PTR(x);
+        T4A_REQUIRE_PTR(out);
+        const std::vector<double> v = apply_gap_half(right != 0, env, n_env, m, x, lb, d, rb, has_fill ? &fill : nullptr, has_fill ? 64 : 0);
+        std::memcpy(out, v.data(), v.size() * sizeof(double));
+    });
+}
+
+t4a_gpu_status t4a_gpu_linop_route(int32_t method, size_t n_state, size_t n_gap_sites, size_t state_bond, size_t op_bond, int32_t* route)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(route);
+        if (method < 0 || method > 2) throw Error(T4A_GPU_INVALID_ARGUMENT, "apply_linear_operator: unknown method");
+        *route = (int32_t)apply_route((MpoAlgorithm)method, n_state, n_gap_sites, state_bond, op_bond);
+    });
+}
+
+t4a_gpu_status t4a_gpu_linop_time_half(size_t n_env, size_t m, size_t lb, size_t d, size_t rb, size_t reps, double* ms2)
+{
+    return guarded([&] {
+        T4A_REQUIRE_PTR(ms2);
+        linop_time_half(n_env, m, lb, d, rb, std::min<size_t>(reps, 1u << 20), ms2);
     });
 }
 

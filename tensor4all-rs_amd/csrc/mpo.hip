@@ -5,6 +5,8 @@
 // (kernels_partial.hip; the host plan mpo_partial_plan is at the end of this file).  Sites are made, copied, right-canonicalised (QrSweep) and split
 // after the two-site SVD (split_two_site) with the chain helpers of tt_chain.hpp.
 #include "mpo.hpp"
+#include "linop.hpp"
+#include "krylov.hpp"
 #include "tensorops.hpp"
 
 #include <algorithm>
@@ -40,6 +42,9 @@ struct Contractor {
 
     // the site plans of a partial contraction (mpo_partial_contract*); null: the matrix product, on the code path it always had
     const std::vector<PartialSitePlan>* plan = nullptr;
+    // the site kinds of an operator applied on a subset of the state's sites (linop.hpp: linop_fused_contract); null everywhere else.
+    // At a gap site `a` holds a shape only (the pass-through bond) and the half product is that of kernels_apply.hip.
+    const std::vector<ApplySitePlan>* gaps = nullptr;
 
     Contractor(Engine& e, const MpoContractionOptions& o) : eng(e), opt(o), st(e.stream()), sweeper(e) {}
 
@@ -358,6 +363,30 @@ struct Contractor {
         return d;
     }
 
+    // the half product of a gap site with pass-through bond m of the operator: P[n, x, a, d] from E = L[n, a, b], or Q[a, b, x, n] from
+    // E = R[a, d, n], in the layouts partial_half_desc gives the same outputs (t = 1, the operator's bonds la = ra = m)
+    static ApplyGapHalfDesc gap_half_desc(bool right, const double* env, size_t n_env, size_t m, const DevCore& X, double* out)
+    {
+        ApplyGapHalfDesc d{};
+        const size_t lb = X.l, s = X.s, rb = X.r;
+        d.E = env;
+        d.X = X.buf.get();
+        d.out = out;
+        d.N = (int)n_env, d.M = (int)m, d.S = (int)s;
+        if (!right) {
+            d.K = (int)lb, d.C = (int)rb;
+            d.en = 1, d.ea = (long long)n_env, d.ek = (long long)(n_env * m);
+            d.xk = 1, d.xx = (long long)lb, d.xc = (long long)(lb * s);
+            d.on = 1, d.ox = (long long)n_env, d.oa = (long long)(n_env * s), d.oc = (long long)(n_env * s * m);
+        } else {
+            d.K = (int)rb, d.C = (int)lb;
+            d.ea = 1, d.ek = (long long)m, d.en = (long long)(m * rb);
+            d.xk = (long long)(lb * s), d.xx = (long long)lb, d.xc = 1;
+            d.oa = 1, d.oc = (long long)m, d.ox = (long long)(m * lb), d.on = (long long)(m * lb * s);
+        }
+        return d;
+    }
+
     // the half product of site i of a plan into device memory that holds it
     void half_into(const Mpo& a, const Mpo& b, size_t i, bool right, const double* env, size_t n_env, double* out, const char* what)
     {
@@ -368,6 +397,11 @@ struct Contractor {
         check_count(n_env * p.S, p.T, right ? A.l : A.r, right ? B.l : B.r, where);
         check_count(n_env, A.l, B.l, 1, where);
         check_count(n_env, A.r, B.r, 1, where);
+        if (gaps && (*gaps)[i].kind != ApplySiteKind::Op) {
+            if (!apply_gap_half_launch(gap_half_desc(right, env, n_env, A.l, B, out), st))
+                throw Error(T4A_GPU_INVALID_ARGUMENT, where + " needs more than INT_MAX workgroups");
+            return;
+        }
         if (!mpo_partial_half_launch(partial_half_desc(right, env, n_env, A, B, p, out), st))
             throw Error(T4A_GPU_INVALID_ARGUMENT, where + " needs more than INT_MAX workgroups");
     }
@@ -846,6 +880,133 @@ std::vector<double> mpo_partial_half(const double* env, size_t n_env, bool right
     c.half(a, b, site, right, d_env.get(), n_env, d_out, "partial_half: site ");
     T4A_HIP(hipGetLastError());
     return to_host(a.tt.eng, d_out.get(), no);
+}
+
+// ---- an operator on a subset of the state's sites, fused route (linop.hpp) ----
+namespace {
+// A chain of cores that belong to somebody else, read as an MPO for the length of one contraction: nothing is copied and nothing is
+// released.  A core without a buffer is a shape only (the operator at a gap site).  A borrowed pointer never sits in a DevCore outside
+// this object, whose destructor forgets it before the DevBuf could hand it to the pool.
+struct BorrowedMpo {
+    Mpo m;
+    BorrowedMpo(size_t n, const std::vector<std::array<size_t, 2>>& sd) : m(std::vector<DevCore>(n), sd) {}
+    BorrowedMpo(const BorrowedMpo&) = delete;
+    BorrowedMpo& operator=(const BorrowedMpo&) = delete;
+    ~BorrowedMpo()
+    {
+        for (DevCore& c : m.tt.cores) c.buf.p = nullptr, c.buf.cap = 0, c.buf.bytes_ = 0;
+    }
+    void view(size_t i, double* p, size_t l, size_t s, size_t r)
+    {
+        DevCore& c = m.tt.cores[i];
+        c.buf.p = p;
+        c.buf.cap = p ? l * s * r : 0;
+        c.l = l, c.s = s, c.r = r;
+    }
+};
+} // namespace
+
+std::unique_ptr<Mpo> linop_fused_contract(Mpo& op, TensorTrain& state, const std::vector<ApplySitePlan>& ap, bool fit, const MpoFitOptions& opt,
+                                          Mpo* initial, MpoFitInfo& info)
+{
+    info = MpoFitInfo{};
+    const size_t n = state.len();
+    std::vector<std::array<size_t, 2>> sd(n), a_sd(n), b_sd(n);
+    PartialSpec spec;
+    for (size_t i = 0; i < n; ++i) {
+        sd[i] = {ap[i].d_out, 1};
+        a_sd[i] = {ap[i].d_out, ap[i].d_in};
+        b_sd[i] = {ap[i].d_in, 1};
+        spec.contract_pairs.push_back(PartialPair{i, 1, i, 0});
+    }
+    BorrowedMpo a(n, a_sd), b(n, b_sd);
+    for (size_t i = 0; i < n; ++i) {
+        const ApplySitePlan& p = ap[i];
+        const DevCore& X = state.cores[i];
+        a.view(i, p.kind == ApplySiteKind::Op ? op.tt.cores[p.op_site].buf.get() : nullptr, p.m_left, p.d_out * p.d_in, p.m_right);
+        b.view(i, X.buf.get(), X.l, X.s, X.r);
+    }
+    const std::vector<PartialSitePlan> plan = mpo_partial_plan(a_sd, b_sd, spec); // the matrix-product plan: S = d_out, K = d_in, T = 1
+    if (initial) {
+        if (initial->len() != n)
+            throw Error(T4A_GPU_INVALID_ARGUMENT,
+                        "apply_linear_operator: initial has " + std::to_string(initial->len()) + " sites, the result has " + std::to_string(n));
+        for (size_t i = 0; i < n; ++i)
+            if (initial->sd[i] != sd[i])
+                throw Error(T4A_GPU_INVALID_ARGUMENT, "apply_linear_operator: initial has site dim " + std::to_string(initial->sd[i][0]) + " at site " +
+                                                          std::to_string(i) + ", the result has " + std::to_string(sd[i][0]));
+    }
+    mpo_fit_validate_options(opt);
+    if (n == 0) return std::make_unique<Mpo>(std::vector<DevCore>{}, sd);
+    op.tt.eng.sync(); // the operands' cores are read on the stream of the view
+    state.eng.sync();
+    if (initial) initial->tt.eng.sync();
+    MpoContractionOptions co;
+    co.tolerance = opt.tolerance;
+    co.max_bond_dim = opt.max_bond_dim;
+    co.method = opt.method;
+    Contractor c(a.m.tt.eng, co);
+    c.plan = &plan;
+    c.gaps = &ap;
+    std::vector<DevCore> cores;
+    if (fit && initial) cores = clone_cores(initial->tt.cores, c.st);
+    else cores = c.zipup_partial(a.m, b.m);
+    if (fit && n > 1 && opt.max_sweeps > 0) c.fit(a.m, b.m, cores, opt.max_sweeps, opt.convergence_tol, info);
+    a.m.tt.eng.sync();
+    return std::make_unique<Mpo>(std::move(cores), sd);
+}
+
+std::vector<double> apply_gap_half(bool right, const double* env, size_t n_env, size_t m, const double* x, size_t lb, size_t d, size_t rb,
+                                   const double* fill, size_t guard)
+{
+    if (n_env == 0 || m == 0 || lb == 0 || d == 0 || rb == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "linop_gap_half: a dimension is zero");
+    const size_t k = right ? rb : lb, c = right ? lb : rb;
+    check_count(n_env, m, k, 1, "linop_gap_half: the environment");
+    check_count(lb, d, rb, 1, "linop_gap_half: the site");
+    check_count(n_env * d, m, c, 1, "linop_gap_half: the half product");
+    Engine eng;
+    const hipStream_t st = eng.stream();
+    DevBuf<double> d_env, d_out;
+    DevCore X = DevCore::make(lb, d, rb);
+    const size_t ne = n_env * m * k, no = n_env * d * m * c;
+    d_env.reserve(ne);
+    d_out.reserve(no + guard);
+    T4A_HIP(hipMemcpyAsync(d_env.get(), env, sizeof(double) * ne, hipMemcpyHostToDevice, st));
+    T4A_HIP(hipMemcpyAsync(X.buf.get(), x, sizeof(double) * X.size(), hipMemcpyHostToDevice, st));
+    if (fill) fill_launch(d_out.get(), no + guard, *fill, st);
+    if (!apply_gap_half_launch(Contractor::gap_half_desc(right, d_env.get(), n_env, m, X, d_out.get()), st))
+        throw Error(T4A_GPU_INVALID_ARGUMENT, "linop_gap_half needs more than INT_MAX workgroups");
+    T4A_HIP(hipGetLastError());
+    return to_host(eng, d_out.get(), fill ? no + guard : no);
+}
+
+void linop_time_half(size_t n_env, size_t m, size_t lb, size_t d, size_t rb, size_t reps, double ms[2])
+{
+    if (reps == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "linop_time_half: reps must be positive");
+    if (n_env == 0 || m == 0 || lb == 0 || d == 0 || rb == 0) throw Error(T4A_GPU_INVALID_ARGUMENT, "linop_time_half: a dimension is zero");
+    check_count(n_env, m, lb, 1, "linop_time_half: the environment");
+    check_count(lb, d, rb, 1, "linop_time_half: the site");
+    check_count(m, d, d, m, "linop_time_half: the bridge site");
+    check_count(n_env * d, m, rb, 1, "linop_time_half: the half product");
+    Engine eng;
+    const hipStream_t st = eng.stream();
+    DevBuf<double> d_env, d_out;
+    DevCore X = DevCore::make(lb, d, rb), O = DevCore::make(m, d * d, m);
+    d_env.reserve(n_env * m * lb);
+    d_out.reserve(n_env * d * m * rb);
+    fill_launch(d_env.get(), n_env * m * lb, 0.5, st); // constant operands: the time does not depend on the values
+    fill_launch(X.buf.get(), X.size(), 0.25, st);
+    fill_launch(O.buf.get(), O.size(), 1.0, st);
+    PartialSitePlan p; // the matrix-product plan of O[m, d, d, m] on X[lb, d, 1, rb]
+    p.S = p.s0 = d, p.K = p.k0 = d, p.T = p.t0 = 1;
+    p.as[0] = 1, p.ak[0] = d, p.bk[0] = 1;
+    const std::function<void()> pieces[2] = {
+        [&] { apply_gap_half_launch(Contractor::gap_half_desc(false, d_env.get(), n_env, m, X, d_out.get()), st); },
+        [&] { mpo_partial_half_launch(Contractor::partial_half_desc(false, d_env.get(), n_env, O, X, p, d_out.get()), st); },
+    };
+    time_pieces(st, pieces, 2, reps, ms);
+    T4A_HIP(hipGetLastError());
+    eng.sync();
 }
 
 } // namespace t4a

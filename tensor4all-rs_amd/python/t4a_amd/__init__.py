@@ -2258,3 +2258,8 @@ from .restructure import (SplitOptions, RestructureOptions, fuse_to, split_to, r
 from . import fitsum  # noqa: E402
 from .fitsum import (FitSumOptions, FitSumOptionsC, FitSumResult, FactorizeAlg, fit_sum, fit_sum_plan, fit_sum_route,  # noqa: E402,F401
                      fit_sum_check_shapes)
+# an operator applied on a subset of a state's sites (apply_linear_operator, compose): module t4a_amd.linop (the hooks _gap_half and
+# _time_half live there)
+from . import linop  # noqa: E402
+from .linop import (LinearOperator, ApplyOptions, ApplyOptionsC, ContractionMethod, apply_linear_operator, apply_plan, apply_route,  # noqa: E402,F401
+                    extend_operator_to_full_space, are_exclusive_operators, compose_exclusive_linear_operators)
